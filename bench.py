@@ -13,10 +13,14 @@ rank of that launch.
 A "step" is one sampling step (U-ViT forward + fused DDPM update) over the rank's batch.
 K = 1000 (default) is one complete sampling run and `value` is then measured, not extrapolated.
 For K < 1000 the K timed steps keep the 30 % shallow / 70 % full mix (switch after
-round(0.3 K) steps) and value = images / (T_K * 1000 / K).
+round(0.3 K) steps) and value = images / (T_K * 1000 / K).  K > 1000 runs K // 1000 complete sampling runs and one
+run of the remaining K % 1000 steps, each from the same x_T.  ms_per_step = T_K / K.
 Every rank samples its own batch (seed + rank): weak scaling, no collective inside the loop;
 one RCCL all_gather of the finished images closes the timed region.
 Prints ONE JSON line on rank 0.
+
+--dump-outputs DIR writes what the last timed step computed (the finished images of every rank) as DIR/images.npy.
+Weights, x_T, labels and the device noise derive from fixed seeds: the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -74,7 +78,37 @@ def parse(argv=None):
     p.add_argument("--launch_timeout", type=float, default=3000.0, help="--gpus N self-launch: seconds before the parent gives up and stops its ranks")
     p.add_argument("--num_cus", type=int, default=0, help="dd_set_num_cus: CU count the persistent GEMM grids are sized for (experiments)")
     p.add_argument("--dev_flags", type=int, default=0, help="dd_dev_set_flags value (include/duodiff_dev.h): same-process kernel-variant A/B runs only")
-    return p.parse_args(argv)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the images the last timed step produced as DIR/<name>.npy (float32, <= 64 MB)")
+    a = p.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def sampling_runs(n, t_switch):
+    """n sampling steps as consecutive runs of at most 1000 steps (a DDPM run has 1000), each from x_T: [(steps, switch after)].
+    A complete run switches after t_switch steps; a shorter one keeps the 30 % shallow / 70 % full mix."""
+    return [(k, t_switch if k == 1000 else max(1, round(t_switch * k / 1000.0)))
+            for k in [1000] * (n // 1000) + ([n % 1000] if n % 1000 else [])]
+
+
+DUMP_LIMIT = 64 * 10**6 - 4096     # bytes of all dumped arrays together (the .npy headers fit in the rest of 64 MB)
+
+
+def dump_outputs(d, arrays):
+    """Write each array as d/<name>.npy in float32.  Above DUMP_LIMIT in all, every array keeps the same share of its leading-axis
+    entries (whole images), a fixed seeded sample, so that runs with the same arguments stay comparable entry for entry."""
+    d = Path(d)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    for name, v in arrays.items():
+        if total > DUMP_LIMIT:
+            keep = max(1, int(v.shape[0] * DUMP_LIMIT // total))
+            v = v[np.sort(np.random.default_rng(0).choice(v.shape[0], keep, replace=False))]
+        np.save(d / f"{name}.npy", v)
+        log(f"dumped {name}{list(v.shape)} to {d / (name + '.npy')}")
 
 
 def host_cores():
@@ -344,18 +378,19 @@ def main():
         y = torch.randint(1, 1001, (B,)).clamp(max=mp_f.num_classes - 1).to(dev)
     stream = torch.cuda.Stream(device=dev)
     use_graph = not a.no_graph
-    # K timed steps: t = 999 .. 1000-K, switch after round(t_switch * K / 1000) steps
-    k_switch = a.t_switch if K == 1000 else max(1, round(a.t_switch * K / 1000.0))
-    t_end = 1000 - K
+    # K timed steps: each sampling run of k steps is t = 999 .. 1000-k, switch after round(t_switch * k / 1000) steps
+    runs = sampling_runs(K, a.t_switch)
+    k_switch = runs[-1][1]
 
-    def run(x, n_steps, t_sw, t_stop):
+    def run(x, k, k_sw):
         with torch.cuda.stream(stream):
-            sample_loop(ctx, es, ef, x, t_switch=t_sw, t_start=999, t_end=t_stop, y=y, seed=seed, noise="philox",
+            sample_loop(ctx, es, ef, x, t_switch=k_sw, t_start=999, t_end=1000 - k, y=y, seed=seed, noise="philox",
                         use_graph=use_graph, stream=stream)
 
     # One timed pass = K sampling steps + the output conversion (x+1)/2 -> NHWC (library kernel, reference
     # sampler.py:145-146) + for N > 1 the single RCCL all_gather of the finished images.  Nothing else runs between
-    # t0 and dt: no torch op, no allocation (every buffer below is created before the warm-up).
+    # t0 and dt: no allocation (every buffer below is created before the warm-up); the only torch op is the x_T copy in
+    # front of each sampling run after the first (K > 1000).
     # (ImageNet-256: x is the 32x32x4 latent; the reference decodes it once per run with the KL-VAE -- 2.8 ms / image on this
     # engine, 1.4 % of a 1000-step latent, DESIGN section 7 -- outside the per-step metric.)
     x = x_T.clone()  # one persistent state buffer: the captured graphs bake its address in
@@ -364,9 +399,19 @@ def main():
     stream.wait_stream(torch.cuda.current_stream())   # x_T.clone() / allocations above ran on the default stream
 
     ev_g0, ev_g1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    # K > 1000: dd_sample times only its own call, so the timed runs are bracketed by event pairs of their own
+    ev_runs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in runs] if len(runs) > 1 else []
 
-    def one_pass(n_steps, t_sw, t_stop):
-        run(x, n_steps, t_sw, t_stop)
+    def one_pass(pass_runs, evs=()):
+        for i, (k, k_sw) in enumerate(pass_runs):
+            if i:
+                with torch.cuda.stream(stream):
+                    x.copy_(x_T, non_blocking=True)
+            if evs:
+                evs[i][0].record(stream)
+            run(x, k, k_sw)
+            if evs:
+                evs[i][1].record(stream)
         ctx.to_images(x, out=imgs, stream=stream)
         if dist is not None:
             with torch.cuda.stream(stream):
@@ -383,7 +428,7 @@ def main():
     # pass (output kernel, all_gather), so that no first-use cost (code-object load, graph upload, communicator
     # set-up) is left for the timed window even at K = 20
     if W > 0:
-        one_pass(W, max(1, W // 2), 1000 - W)
+        one_pass([(k, max(1, k // 2)) for k, _ in sampling_runs(W, a.t_switch)])
         stream.synchronize()
         with torch.cuda.stream(stream):
             x.copy_(x_T, non_blocking=True)
@@ -394,7 +439,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    one_pass(K, k_switch, t_end)
+    one_pass(runs, ev_runs)
     stream.synchronize()
     torch.cuda.synchronize()
     if dist is not None:
@@ -402,6 +447,8 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     timing = ctx.last_sample_timing()   # hipEvents around the K steps of this rank's dd_sample call
+    if ev_runs:                         # several calls: their total, no split by backbone
+        timing = (sum(e0.elapsed_time(e1) for e0, e1 in ev_runs), None, None)
     chains = int(ctx.lib.dd_dev_last_sample_chains(ctx.handle))   # 2: the batch ran as two half-batch chains on two streams
     on_dev = dist is None or dist.get_backend() == "nccl"
     gather_ms = ev_g0.elapsed_time(ev_g1) if (dist is not None and dist.get_backend() == "nccl") else 0.0
@@ -414,6 +461,8 @@ def main():
     chains_min = int(round(-float(t_all[4].item())))     # a rank that fell back to one chain (odd batch, flag) shows here
     log(f"timed region done: {dt:.3f} s")
     finite = bool(torch.isfinite(imgs).all().item())
+    if a.dump_outputs and rank == 0:    # before the roofline leg below reuses x
+        dump_outputs(a.dump_outputs, {"images": (torch.cat(gathered) if gathered is not None and on_dev else imgs).cpu().numpy()})
 
     if rank == 0:
         images = B * world
@@ -465,7 +514,7 @@ def main():
                        # one chain's HBM-bound phases overlap the other's MFMA phases); the roofline leg below times the kernel ALONE
                        # on the chip at the full batch, one chain
                        "chains_in_timed_region": chains, "chains_min_over_ranks": chains_min,
-                       "timed_steps": K, "switch_after_steps": k_switch,
+                       "timed_steps": K, "switch_after_steps": k_switch, "sampling_runs": len(runs),
                        "seconds_per_sample": (dt * 1000.0 / K) / images, "finite": finite,
                        "gpu_ms_total": timing[0], "gpu_ms_first_backbone": timing[1], "gpu_ms_late_backbone": timing[2],
                        # wall time of the timed region (MAX over ranks) minus the slowest rank's GPU time of the K steps: output kernel,

@@ -201,6 +201,34 @@ def test_bench_roofline_leg_follows_the_committed_kernel_table():
     assert lib.dd_profile_select(None, 0) == _lib.DD_ERR_INVALID      # (a null context is refused: the symbol exists and checks its arguments)
 
 
+def test_bench_steps_and_output_dump(tmp_path):
+    """--steps K runs exactly K timed steps (runs of at most 1000, the 30 / 70 mix in each) and --dump-outputs stays under 64 MB with a
+    fixed sample of whole images when the output is larger."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", REPO / "bench.py")
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert b.sampling_runs(20, 300) == [(20, 6)] and b.sampling_runs(1000, 300) == [(1000, 300)]
+    assert b.sampling_runs(2500, 300) == [(1000, 300), (1000, 300), (500, 150)] and b.sampling_runs(1, 300) == [(1, 1)]
+    for K in (1, 7, 999, 1000, 1001, 3999, 4000):
+        assert sum(k for k, _ in b.sampling_runs(K, 300)) == K
+    assert b.parse(["--steps", "3", "--dump-outputs", str(tmp_path)]).dump_outputs == str(tmp_path)
+    with pytest.raises(SystemExit):
+        b.parse(["--steps", "0"])
+    small = np.arange(2 * 4 * 4 * 3, dtype=np.float64).reshape(2, 4, 4, 3)
+    b.dump_outputs(tmp_path / "small", {"images": small})
+    got = np.load(tmp_path / "small" / "images.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    big = np.arange(1024 * 64 * 64 * 3, dtype=np.float32).reshape(1024, 64, 64, 3)      # 50 MB x 2
+    for d in ("a", "b"):
+        b.dump_outputs(tmp_path / d, {"images": big, "other": big})
+    files = sorted((tmp_path / "a").glob("*.npy"))
+    assert [f.name for f in files] == ["images.npy", "other.npy"] and sum(f.stat().st_size for f in files) <= 64 * 10**6
+    a0, b0 = np.load(tmp_path / "a" / "images.npy"), np.load(tmp_path / "b" / "images.npy")
+    assert np.array_equal(a0, b0) and a0.shape[1:] == big.shape[1:] and a0.shape[0] > 500
+    assert np.isin(a0[:, 0, 0, 0], big[:, 0, 0, 0]).all()                                # whole images of the output
+
+
 def test_documents_quote_the_committed_profiles():
     """README.md and DESIGN.md carry ONE generated performance block (tools/perf_tables.py: the driver's BENCH_rNN.json records + the newest
     profiles/rNN collection); it must be what the files say (no number in the documents that a file under profiles/ contradicts)."""

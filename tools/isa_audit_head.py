@@ -18,6 +18,7 @@ on the compiled ISA (a forward dataflow over the kernel's basic blocks: the set 
 import re
 import subprocess
 import sys
+import tempfile
 from pathlib import Path
 
 REPO = Path(__file__).resolve().parents[1]
@@ -125,10 +126,11 @@ def audit(name, body):
 
 
 def main():
-    out = "/tmp/rowops_audit.s"
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", f"-I{REPO / 'include'}", "-S", "--cuda-device-only",
-                    str(SRC), "-o", out], check=True, stderr=subprocess.DEVNULL)
-    lines = open(out).read().split("\n")
+    with tempfile.TemporaryDirectory() as tmp:    # private to this run: concurrent runs and other users never collide on it
+        out = Path(tmp) / "rowops_audit.s"
+        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", f"-I{REPO / 'include'}", "-S", "--cuda-device-only",
+                        str(SRC), "-o", str(out)], check=True, stderr=subprocess.DEVNULL)
+        lines = out.read_text().split("\n")
     rc = 0
     seen = 0
     for i, l in enumerate(lines):

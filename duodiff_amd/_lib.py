@@ -12,7 +12,7 @@ DD_PREC_BF16, DD_PREC_FP32 = 0, 1
 DD_VAR_BETA_TILDE, DD_VAR_BETA = 0, 1
 DD_NOISE_NONE, DD_NOISE_BUFFER, DD_NOISE_PHILOX = 0, 1, 2
 DD_EE_MLP_PER_LAYER, DD_EE_MLP_PER_TIMESTEP, DD_EE_MLP_PER_LAYER_PER_TIMESTEP, DD_EE_ATTENTION_PROBE = 0, 1, 2, 3
-ABI_VERSION = 5
+ABI_VERSION = 6
 DD_DEV_NO_FUSED_MLP, DD_DEV_NO_FUSED_PROJ, DD_DEV_NO_FUSED_HEAD, DD_DEV_GENERIC_EMBED, DD_DEV_MLP_EXTRAS_ONLY = 1, 2, 4, 8, 16
 DD_DEV_NO_FUSED_SKIP, DD_DEV_NO_FUSED_QKV, DD_DEV_NO_FUSED_QA = 32, 64, 128
 DD_PROF_DOMINANT, DD_PROF_BLOCK_TAIL, DD_PROF_FC1, DD_PROF_ROWLIN, DD_PROF_QKV_ATTENTION, DD_PROF_SPLITK = 0, 1, 2, 3, 4, 5
@@ -39,6 +39,11 @@ class dd_affine_sample_args(C.Structure):
                 ("c", C.POINTER(C.c_float)), ("noise", C.POINTER(C.c_int32)), ("noise_mode", C.c_int32),
                 ("use_graph", C.c_int32), ("seed", C.c_uint64), ("y_dev", C.c_void_p), ("x_dev", C.c_void_p),
                 ("B", C.c_int32), ("counter_base", C.c_int32)]
+
+
+class dd_guidance(C.Structure):
+    """classifier-free guidance: eps = eps_c + scale * (eps_c - eps_u), the unconditional rows labelled null_label"""
+    _fields_ = [("scale", C.c_float), ("null_label", C.c_int32)]
 
 
 class dd_ee_sample_args(C.Structure):
@@ -79,6 +84,10 @@ SIGNATURES = {
     "dd_sample": (C.c_int, [C.c_void_p, C.POINTER(dd_sample_args), C.c_void_p]),
     "dd_sample_affine": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.c_void_p]),
     "dd_sample_early_exit": (C.c_int, [C.c_void_p, C.POINTER(dd_ee_sample_args), C.c_void_p]),
+    "dd_forward_guided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.POINTER(dd_guidance), C.c_void_p,
+                                    C.c_int, C.c_void_p]),
+    "dd_sample_guided": (C.c_int, [C.c_void_p, C.POINTER(dd_sample_args), C.POINTER(dd_guidance), C.c_void_p]),
+    "dd_sample_affine_guided": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.POINTER(dd_guidance), C.c_void_p]),
     "dd_bench_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
     "dd_vae_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "dd_vae_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),

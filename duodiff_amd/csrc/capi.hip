@@ -102,9 +102,14 @@ struct GraphKey {
     const void *aux0 = nullptr, *aux1 = nullptr;                     // dd_sample_early_exit: the two log tables
     float thr = 0.f;                                                 //                        and the threshold
     int b0 = 0;                                                      // first image of a half-batch chain within the whole batch
+    int gnull = -1;                                                  // classifier-free guidance: the null label (-1: unguided)
+    unsigned gscale = 0;                                             //   and the bits of the scale (+0 and -0 round differently)
     bool operator==(const GraphKey& o) const {
         return x == o.x && y == o.y && B == o.B && noise == o.noise && variance == o.variance && num_cus == o.num_cus &&
-               atab == o.atab && aux0 == o.aux0 && aux1 == o.aux1 && thr == o.thr && b0 == o.b0;
+               atab == o.atab && aux0 == o.aux0 && aux1 == o.aux1 && thr == o.thr && b0 == o.b0 && gnull == o.gnull && gscale == o.gscale;
+    }
+    void guide(const dd_guidance* g) {
+        if (g) { gnull = g->null_label; gscale = __builtin_bit_cast(unsigned, g->scale); }
     }
 };
 
@@ -859,38 +864,86 @@ int check_call(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev) {
     return DD_OK;
 }
 
+// a guided call of B images on m (include/duodiff.h dd_guidance): every check before anything is enqueued
+int check_guided(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev, const dd_guidance* g) {
+    if (!c || !m) return DD_ERR_INVALID;
+    if (!g) return fail(c, DD_ERR_INVALID, "null dd_guidance");
+    if (m->cfg.num_classes <= 0) return fail(c, DD_ERR_INVALID, "classifier-free guidance needs a class-conditional model");
+    if (m->ee_type >= 0) return fail(c, DD_ERR_INVALID, "classifier-free guidance is not supported for early-exit models");
+    if (g->null_label < 0 || g->null_label >= m->cfg.num_classes)
+        return fail(c, DD_ERR_INVALID, "guidance null_label outside [0, num_classes) of the model");
+    if (!std::isfinite(g->scale)) return fail(c, DD_ERR_INVALID, "guidance scale is not finite");
+    if (B < 1 || 2LL * B > m->cfg.max_batch)
+        return fail(c, DD_ERR_INVALID, "a guided batch of B images runs 2 B backbone rows: need 1 <= B and 2 B <= max_batch");
+    return check_call(c, m, 2 * B, y_dev);
+}
+
 // one sampling step enqueued on s: x <- update(x, model(x, t)) ; t comes from ctx->st
 // advance != 0: the step's last kernel also decrements the device-resident timestep (graph replays / dd_sample)
+// g != null (classifier-free guidance): B images, the backbone runs the 2 B rows [x | x] with labels [y | null] (stage_guided's layout)
 int enqueue_step(dd_ctx* c, dd_model* m, float* x_dev, const int64_t* y_dev, int noise_mode, const float* z_dev,
-                 int variance, float* eps_out, int B, hipStream_t s, int advance = 0, const AffineRow* atab = nullptr, int b0 = 0) {
-    int rc = run_model(m, x_dev, nullptr, y_dev, B, s);
+                 int variance, float* eps_out, int B, hipStream_t s, int advance = 0, const AffineRow* atab = nullptr, int b0 = 0,
+                 const dd_guidance* g = nullptr) {
+    int rc = run_model(m, x_dev, nullptr, y_dev, g ? 2 * B : B, s);
     if (rc) return rc;
     FinalArgs fa{m->dec, m->wconv, m->bconv, x_dev, z_dev, eps_out, x_dev, c->st, c->coef,
                  B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, noise_mode, variance, advance, atab, b0};
+    if (g) { fa.pair_B = B; fa.guide_scale = g->scale; }
     DD_HIP(c, launch_final(fa, s));
     return DD_OK;
 }
 
 // dd_sample / dd_sample_affine with graphs: the loop runs on context-owned staging copies of x / y, so the captured step
 // does not depend on the caller's tensor addresses
-int stage_inputs(dd_ctx* c, const float* x_dev, const int64_t* y_dev, int B, size_t x_elems, hipStream_t s, float** x_run,
-                 const int64_t** y_run) {
+int grow_stage(dd_ctx* c, size_t x_elems, size_t y_elems) {
     if (c->x_stage_elems < x_elems) {       // grows only: model graphs keyed on the old address are re-captured once
         if (c->x_stage) (void)hipFree(c->x_stage);
         c->x_stage = nullptr; c->x_stage_elems = 0;
         DD_HIP(c, hipMalloc((void**)&c->x_stage, x_elems * sizeof(float)));
         c->x_stage_elems = x_elems;
     }
-    if (y_dev && c->y_stage_elems < (size_t)B) {
+    if (c->y_stage_elems < y_elems) {
         if (c->y_stage) (void)hipFree(c->y_stage);
         c->y_stage = nullptr; c->y_stage_elems = 0;
-        DD_HIP(c, hipMalloc((void**)&c->y_stage, (size_t)B * sizeof(int64_t)));
-        c->y_stage_elems = (size_t)B;
+        DD_HIP(c, hipMalloc((void**)&c->y_stage, y_elems * sizeof(int64_t)));
+        c->y_stage_elems = y_elems;
     }
+    return DD_OK;
+}
+int stage_inputs(dd_ctx* c, const float* x_dev, const int64_t* y_dev, int B, size_t x_elems, hipStream_t s, float** x_run,
+                 const int64_t** y_run) {
+    if (int rc = grow_stage(c, x_elems, y_dev ? (size_t)B : 0)) return rc;
     DD_HIP(c, hipMemcpyAsync(c->x_stage, x_dev, x_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (y_dev) DD_HIP(c, hipMemcpyAsync(c->y_stage, y_dev, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     *x_run = c->x_stage;
     *y_run = y_dev ? c->y_stage : nullptr;
+    return DD_OK;
+}
+
+// A guided call (eager or graph-replayed) always runs on the staging buffers, 2 B images: chain k (images [o_k, o_k + B_k), o_0 = 0,
+// o_1 = B0) owns images [2 o_k, 2 o_k + 2 B_k) of them -- its B_k images, then the same images again -- and labels [y_k | null x B_k].
+// B0 == B: one chain.
+int stage_guided(dd_ctx* c, const float* x_dev, const int64_t* y_dev, int B, int B0, size_t chw, int null_label, hipStream_t s,
+                 float** x_run, const int64_t** y_run) {
+    if (int rc = grow_stage(c, 2 * (size_t)B * chw, 2 * (size_t)B)) return rc;
+    for (int k = 0; k < 2; ++k) {
+        const int o = k ? B0 : 0, Bk = k ? B - B0 : B0;
+        if (Bk == 0) continue;
+        float* xs = c->x_stage + 2 * (size_t)o * chw;
+        DD_HIP(c, hipMemcpyAsync(xs, x_dev + (size_t)o * chw, (size_t)Bk * chw * sizeof(float), hipMemcpyDeviceToDevice, s));
+        DD_HIP(c, hipMemcpyAsync(xs + (size_t)Bk * chw, x_dev + (size_t)o * chw, (size_t)Bk * chw * sizeof(float), hipMemcpyDeviceToDevice, s));
+        DD_HIP(c, launch_guided_labels((const long long*)y_dev + o, (long long*)c->y_stage + 2 * (size_t)o, Bk, null_label, s));
+    }
+    *x_run = c->x_stage;
+    *y_run = c->y_stage;
+    return DD_OK;
+}
+// ... and the first half of each chain's block back to the caller's images
+int unstage_guided(dd_ctx* c, float* x_dev, const float* x_run, int B, int B0, size_t chw, hipStream_t s) {
+    for (int k = 0; k < 2; ++k) {
+        const int o = k ? B0 : 0, Bk = k ? B - B0 : B0;
+        if (Bk) DD_HIP(c, hipMemcpyAsync(x_dev + (size_t)o * chw, x_run + 2 * (size_t)o * chw, (size_t)Bk * chw * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
     return DD_OK;
 }
 
@@ -1473,6 +1526,25 @@ int dd_to_images(dd_ctx* c, const float* x_dev, float* images_dev, int B, int C,
     DD_HIP(c, launch_to_images(x_dev, images_dev, B, C, S, (hipStream_t)stream));
     return DD_OK;
 }
+int dd_forward_guided(dd_ctx* c, dd_model* m, const float* x_dev, float t, const int64_t* y_dev, const dd_guidance* g,
+                      float* eps_dev, int B, void* stream) {
+    int rc = check_guided(c, m, B, y_dev, g);
+    if (rc) return rc;
+    if (!x_dev || !eps_dev) return fail(c, DD_ERR_INVALID, "null tensor");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t chw = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
+    float* x_run = nullptr;
+    const int64_t* y_run = nullptr;
+    if ((rc = stage_guided(c, x_dev, y_dev, B, B, chw, g->null_label, s, &x_run, &y_run))) return rc;
+    DD_HIP(c, launch_set_state_float(c->st, t, s));
+    rc = run_model(m, x_run, nullptr, y_run, 2 * B, s);
+    if (rc) return rc;
+    FinalArgs fa{m->dec, m->wconv, m->bconv, nullptr, nullptr, eps_dev, nullptr, c->st, c->coef,
+                 B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, DD_NOISE_NONE, 0, 0};
+    fa.pair_B = B; fa.guide_scale = g->scale;
+    DD_HIP(c, launch_final(fa, s));
+    return DD_OK;
+}
 
 int dd_sample_step(dd_ctx* c, dd_model* m, float* x_dev, int t, const int64_t* y_dev, int noise_mode, const float* z_dev,
                    uint64_t seed, int variance, float* eps_out_dev, int B, void* stream) {
@@ -1486,11 +1558,16 @@ int dd_sample_step(dd_ctx* c, dd_model* m, float* x_dev, int t, const int64_t* y
     return enqueue_step(c, m, x_dev, y_dev, noise_mode, z_dev, variance, eps_out_dev, B, s);
 }
 
-int dd_sample(dd_ctx* c, const dd_sample_args* a, void* stream) {
+}  // extern "C"
+
+namespace {
+// dd_sample (g == nullptr) and dd_sample_guided: one path
+int sample_ddpm(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* stream) {
     if (!c || !a) return DD_ERR_INVALID;
-    int rc = check_call(c, a->first, a->B, a->y_dev);
+    auto check = [&](dd_model* m) { return g ? check_guided(c, m, a->B, a->y_dev, g) : check_call(c, m, a->B, a->y_dev); };
+    int rc = check(a->first);
     if (rc) return rc;
-    if (a->late && (rc = check_call(c, a->late, a->B, a->y_dev))) return rc;
+    if (a->late && (rc = check(a->late))) return rc;
     if (!a->x_dev) return fail(c, DD_ERR_INVALID, "null tensor");
     if (a->t_start > 999 || a->t_end < 0 || a->t_end > a->t_start) return fail(c, DD_ERR_INVALID, "need 999 >= t_start >= t_end >= 0");
     if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE)
@@ -1512,26 +1589,33 @@ int dd_sample(dd_ctx* c, const dd_sample_args* a, void* stream) {
     // batch size, so chain 0 = images [0, B/2) on the caller's stream and chain 1 = images [B/2, B) on the context's side stream
     // compute bit for bit what the undivided batch computes (Philox pixel ids carry the image offset) -- with the two chains free
     // to drift apart, so that one's HBM-bound phases (row prologues / epilogues, attention row fetch) run under the other's MFMA phases.
-    const bool chained = a->use_graph && use_chains(c, a->first, a->B) && (!switching || use_chains(c, a->late, a->B));
-    const int B0 = chained ? a->B / 2 : a->B, B1 = a->B - B0;
+    // Guided: the decisions are made on the 2 B backbone rows and the split is by image (chain 0 takes the larger half, on the workspace
+    // sized for max_batch >= 2 B rows; the second chain's workspace holds (max_batch + 1) / 2 rows >= 2 * floor(B / 2)).
+    const int rows = g ? 2 * a->B : a->B;
+    const bool chained = a->use_graph && use_chains(c, a->first, rows) && (!switching || use_chains(c, a->late, rows)) && (!g || a->B >= 2);
+    const int B0 = chained ? (g ? (a->B + 1) / 2 : a->B / 2) : a->B, B1 = a->B - B0;
+    const size_t xo1 = g ? 2 * (size_t)B0 : (size_t)B0;     // the second chain's first row in x_run / y_run
     c->last_chains = chained ? 2 : 1;
+    if (g && (rc = stage_guided(c, a->x_dev, a->y_dev, a->B, B0, chw, g->null_label, s, &x_run, &y_run))) return rc;
     if (a->use_graph) {
-        if ((rc = stage_inputs(c, a->x_dev, a->y_dev, a->B, x_elems, s, &x_run, &y_run))) return rc;
+        if (!g && (rc = stage_inputs(c, a->x_dev, a->y_dev, a->B, x_elems, s, &x_run, &y_run))) return rc;
         // (the captured persistent GEMM grids are sized from c->num_cus: halved for both chains of a large GEMM-path batch)
         struct CusGuard { dd_ctx* c; int saved; ~CusGuard() { c->num_cus = saved; } } cus_guard{c, c->num_cus};
-        if (chained) c->num_cus = std::min(chain_gemm_cus(c, a->first, a->B), switching ? chain_gemm_cus(c, a->late, a->B) : c->num_cus);
+        if (chained) c->num_cus = std::min(chain_gemm_cus(c, a->first, rows), switching ? chain_gemm_cus(c, a->late, rows) : c->num_cus);
         GraphKey key{x_run, y_run, B0, a->noise_mode, a->variance, c->num_cus, nullptr};
-        auto step = [&](dd_model* m) { return enqueue_step(c, m, x_run, y_run, a->noise_mode, nullptr, a->variance, nullptr, B0, s, 1); };
+        key.guide(g);
+        auto step = [&](dd_model* m) { return enqueue_step(c, m, x_run, y_run, a->noise_mode, nullptr, a->variance, nullptr, B0, s, 1, nullptr, 0, g); };
         if ((rc = get_graph(c, a->first, 0, key, s, step))) return rc;
         if (switching && (rc = get_graph(c, a->late, 0, key, s, step))) return rc;
         if (chained) {
-            float* x1 = x_run + (size_t)B0 * chw;
-            const int64_t* y1 = y_run ? y_run + B0 : nullptr;
+            float* x1 = x_run + xo1 * chw;
+            const int64_t* y1 = y_run ? y_run + xo1 : nullptr;
             GraphKey key1{x1, y1, B1, a->noise_mode, a->variance, c->num_cus, nullptr};
             key1.b0 = B0;
+            key1.guide(g);
             auto step1 = [&](dd_model* m) {     // the same launch sequence on the second chain's workspace and step state
                 swap_chain(m); std::swap(c->st, c->st2);
-                const int r = enqueue_step(c, m, x1, y1, a->noise_mode, nullptr, a->variance, nullptr, B1, s, 1, nullptr, B0);
+                const int r = enqueue_step(c, m, x1, y1, a->noise_mode, nullptr, a->variance, nullptr, B1, s, 1, nullptr, B0, g);
                 swap_chain(m); std::swap(c->st, c->st2);
                 return r;
             };
@@ -1554,7 +1638,7 @@ int dd_sample(dd_ctx* c, const dd_sample_args* a, void* stream) {
             DD_HIP(c, hipGraphLaunch(cur->graph[0], s));
             if (chained) DD_HIP(c, hipGraphLaunch(cur->graph[3], c->side));
         } else {
-            rc = enqueue_step(c, cur, x_run, y_run, a->noise_mode, nullptr, a->variance, nullptr, a->B, s, 1);
+            rc = enqueue_step(c, cur, x_run, y_run, a->noise_mode, nullptr, a->variance, nullptr, a->B, s, 1, nullptr, 0, g);
             if (rc) return rc;
         }
         if (switching && t == t_sw) {
@@ -1570,15 +1654,18 @@ int dd_sample(dd_ctx* c, const dd_sample_args* a, void* stream) {
     }
     if (!marked) DD_HIP(c, hipEventRecord(c->ev[1], s));
     DD_HIP(c, hipEventRecord(c->ev[2], s));
+    if (g) return unstage_guided(c, a->x_dev, x_run, a->B, B0, chw, s);
     if (x_run != a->x_dev) DD_HIP(c, hipMemcpyAsync(a->x_dev, x_run, x_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
     return DD_OK;
 }
 
-int dd_sample_affine(dd_ctx* c, const dd_affine_sample_args* a, void* stream) {
+// dd_sample_affine (g == nullptr) and dd_sample_affine_guided: one path
+int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, void* stream) {
     if (!c || !a) return DD_ERR_INVALID;
-    int rc = check_call(c, a->first, a->B, a->y_dev);
+    auto check = [&](dd_model* m) { return g ? check_guided(c, m, a->B, a->y_dev, g) : check_call(c, m, a->B, a->y_dev); };
+    int rc = check(a->first);
     if (rc) return rc;
-    if (a->late && (rc = check_call(c, a->late, a->B, a->y_dev))) return rc;
+    if (a->late && (rc = check(a->late))) return rc;
     if (!a->x_dev || !a->t || !a->a || !a->b || !a->c || !a->noise) return fail(c, DD_ERR_INVALID, "null tensor / table");
     if (a->n_steps < 1 || a->n_steps > (1 << 20)) return fail(c, DD_ERR_INVALID, "n_steps outside [1, 2^20]");
     if (a->counter_base < 0 || a->counter_base > (1 << 20)) return fail(c, DD_ERR_INVALID, "counter_base outside [0, 2^20]");
@@ -1608,25 +1695,30 @@ int dd_sample_affine(dd_ctx* c, const dd_affine_sample_args* a, void* stream) {
     const size_t chw = (size_t)a->first->cfg.in_chans * a->first->cfg.img_size * a->first->cfg.img_size;
     const size_t x_elems = (size_t)a->B * chw;
     // two half-batch chains, as dd_sample (both read the one step table; each has its own step index and Philox image offset)
-    const bool chained = a->use_graph && use_chains(c, a->first, a->B) && (!switching || use_chains(c, a->late, a->B));
-    const int B0 = chained ? a->B / 2 : a->B, B1 = a->B - B0;
+    const int rows = g ? 2 * a->B : a->B;
+    const bool chained = a->use_graph && use_chains(c, a->first, rows) && (!switching || use_chains(c, a->late, rows)) && (!g || a->B >= 2);
+    const int B0 = chained ? (g ? (a->B + 1) / 2 : a->B / 2) : a->B, B1 = a->B - B0;
+    const size_t xo1 = g ? 2 * (size_t)B0 : (size_t)B0;
     c->last_chains = chained ? 2 : 1;
+    if (g && (rc = stage_guided(c, a->x_dev, a->y_dev, a->B, B0, chw, g->null_label, s, &x_run, &y_run))) return rc;
     if (a->use_graph) {
-        if ((rc = stage_inputs(c, a->x_dev, a->y_dev, a->B, x_elems, s, &x_run, &y_run))) return rc;
+        if (!g && (rc = stage_inputs(c, a->x_dev, a->y_dev, a->B, x_elems, s, &x_run, &y_run))) return rc;
         struct CusGuard { dd_ctx* c; int saved; ~CusGuard() { c->num_cus = saved; } } cus_guard{c, c->num_cus};
-        if (chained) c->num_cus = std::min(chain_gemm_cus(c, a->first, a->B), switching ? chain_gemm_cus(c, a->late, a->B) : c->num_cus);
-        const GraphKey key{x_run, y_run, B0, a->noise_mode, 0, c->num_cus, c->atab};
-        auto step = [&](dd_model* m) { return enqueue_step(c, m, x_run, y_run, a->noise_mode, nullptr, 0, nullptr, B0, s, 1, c->atab); };
+        if (chained) c->num_cus = std::min(chain_gemm_cus(c, a->first, rows), switching ? chain_gemm_cus(c, a->late, rows) : c->num_cus);
+        GraphKey key{x_run, y_run, B0, a->noise_mode, 0, c->num_cus, c->atab};
+        key.guide(g);
+        auto step = [&](dd_model* m) { return enqueue_step(c, m, x_run, y_run, a->noise_mode, nullptr, 0, nullptr, B0, s, 1, c->atab, 0, g); };
         if ((rc = get_graph(c, a->first, 1, key, s, step))) return rc;
         if (switching && (rc = get_graph(c, a->late, 1, key, s, step))) return rc;
         if (chained) {
-            float* x1 = x_run + (size_t)B0 * chw;
-            const int64_t* y1 = y_run ? y_run + B0 : nullptr;
+            float* x1 = x_run + xo1 * chw;
+            const int64_t* y1 = y_run ? y_run + xo1 : nullptr;
             GraphKey key1{x1, y1, B1, a->noise_mode, 0, c->num_cus, c->atab};
             key1.b0 = B0;
+            key1.guide(g);
             auto step1 = [&](dd_model* m) {
                 swap_chain(m); std::swap(c->st, c->st2);
-                const int r = enqueue_step(c, m, x1, y1, a->noise_mode, nullptr, 0, nullptr, B1, s, 1, c->atab, B0);
+                const int r = enqueue_step(c, m, x1, y1, a->noise_mode, nullptr, 0, nullptr, B1, s, 1, c->atab, B0, g);
                 swap_chain(m); std::swap(c->st, c->st2);
                 return r;
             };
@@ -1654,7 +1746,7 @@ int dd_sample_affine(dd_ctx* c, const dd_affine_sample_args* a, void* stream) {
             DD_HIP(c, hipGraphLaunch(cur->graph[1], s));
             if (chained) DD_HIP(c, hipGraphLaunch(cur->graph[4], c->side));
         } else {
-            rc = enqueue_step(c, cur, x_run, y_run, a->noise_mode, nullptr, 0, nullptr, a->B, s, 1, c->atab);
+            rc = enqueue_step(c, cur, x_run, y_run, a->noise_mode, nullptr, 0, nullptr, a->B, s, 1, c->atab, 0, g);
             if (rc) return rc;
         }
     }
@@ -1665,8 +1757,23 @@ int dd_sample_affine(dd_ctx* c, const dd_affine_sample_args* a, void* stream) {
     }
     if (!marked) DD_HIP(c, hipEventRecord(c->ev[1], s));
     DD_HIP(c, hipEventRecord(c->ev[2], s));
+    if (g) return unstage_guided(c, a->x_dev, x_run, a->B, B0, chw, s);
     if (x_run != a->x_dev) DD_HIP(c, hipMemcpyAsync(a->x_dev, x_run, x_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
     return DD_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int dd_sample(dd_ctx* c, const dd_sample_args* a, void* stream) { return sample_ddpm(c, a, nullptr, stream); }
+int dd_sample_guided(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* stream) {
+    if (c && !g) return fail(c, DD_ERR_INVALID, "null dd_guidance");
+    return sample_ddpm(c, a, g, stream);
+}
+int dd_sample_affine(dd_ctx* c, const dd_affine_sample_args* a, void* stream) { return sample_affine(c, a, nullptr, stream); }
+int dd_sample_affine_guided(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, void* stream) {
+    if (c && !g) return fail(c, DD_ERR_INVALID, "null dd_guidance");
+    return sample_affine(c, a, g, stream);
 }
 
 // One early-exit sampling step on the device (reference eesampler.py:56-81): EarlyExitUViT.forward with every head and

@@ -271,6 +271,11 @@ struct FinalArgs {
     // (the fields below are set by name, never positionally: the aggregate initialisers of the step launches end at b0)
     int layer_B = 0;       // > 0: the B "images" are layer_B images of B / layer_B early-exit layers, one after the other (dec, eps_out contiguous that way);
     long long w_stride = 0, b_stride = 0;   //   layer i convolves with wconv + i * w_stride / bconv + i * b_stride (floats): ONE launch for every layer's head
+    // classifier-free guidance (pair_B > 0): dec holds 2 pair_B images, image b's conditional rows first and its unconditional rows at b + pair_B;
+    // the grid covers the B = pair_B images, eps = eps_c + guide_scale * (eps_c - eps_u) goes through the update, x_in [b] is read and x_out [b]
+    // AND x_out [b + pair_B] are written (the next step's unconditional rows then hold their input); z, eps_out: [B, C, S, S]; layer_B must be 0
+    float guide_scale = 0.f;
+    int pair_B = 0;
 };
 hipError_t launch_final(const FinalArgs& a, hipStream_t s);
 
@@ -336,6 +341,7 @@ hipError_t launch_ddpm_step_state(float* x, const float* eps, StepState* st, con
 hipError_t launch_set_state(StepState* st, int t, unsigned long long seed, hipStream_t s);
 hipError_t launch_set_state_table(StepState* st, const AffineRow* atab, unsigned long long seed, hipStream_t s);   // step index 0
 hipError_t launch_set_state_float(StepState* st, float t, hipStream_t s);
+hipError_t launch_guided_labels(const long long* y, long long* out, int B, long long null_label, hipStream_t s);   // out [2 B] = [y [0, B) | null_label x B]
 // (x + 1) / 2, NCHW -> NHWC: the output convention of reference sampler.py:145-146
 hipError_t launch_to_images(const float* x, float* out, int B, int C, int S, hipStream_t s);
 

@@ -500,17 +500,12 @@ __device__ __forceinline__ f32x4 philox_normal4(unsigned long long seed, unsigne
 // reference models/uvit.py:125-132), 3x3 conv pad 1 (:382), then
 //   x <- sqrt(1/a_t) (x - (1-a_t)/sqrt(1-abar_t) eps) + sigma_t z      (sampler.py:47-56)
 // One thread per pixel, all output channels; eps never goes to HBM unless asked for.
+// G (classifier-free guidance, FinalArgs::pair_B): the pixel's conv runs on the conditional decoder rows of image b and on the unconditional
+// rows of image b + pair_B, eps = eps_c + s (eps_c - eps_u) feeds the update, and x' is written to both images.
 // ------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) final_kernel(const FinalArgs a) {
-#pragma clang fp contract(off)  // the update must round like the reference: mul, sub, mul, add -- no FMA
-    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void final_conv_pixel(const FinalArgs& a, int b, int y, int x, float (&acc)[4]) {
     const int S = a.S, P = a.P, C = a.C;
-    const long long npix = (long long)a.B * S * S;
-    if (pix >= npix) return;
-    const int b = (int)(pix / (S * S)), y = (int)((pix / S) % S), x = (int)(pix % S);
     const int g = S / P, pd = P * P * C;
-
-    float acc[4];  // C <= 4
 #pragma unroll
     for (int co = 0; co < 4; ++co) acc[co] = co < C ? a.bconv[co] : 0.f;
 #pragma unroll
@@ -531,6 +526,29 @@ __global__ void __launch_bounds__(256) final_kernel(const FinalArgs a) {
             }
         }
     }
+}
+
+template <bool G>
+__global__ void __launch_bounds__(256) final_kernel(const FinalArgs a) {
+#pragma clang fp contract(off)  // the update must round like the reference: mul, sub, mul, add -- no FMA
+    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int S = a.S, C = a.C;
+    const long long npix = (long long)a.B * S * S;
+    if (pix >= npix) return;
+    const int b = (int)(pix / (S * S)), y = (int)((pix / S) % S), x = (int)(pix % S);
+
+    float acc[4];  // C <= 4
+    final_conv_pixel(a, b, y, x, acc);
+    const long long pair = G ? (long long)a.pair_B * C * S * S : 0;   // element offset of the unconditional twin of image b
+    if constexpr (G) {
+        float accu[4];
+        final_conv_pixel(a, b + a.pair_B, y, x, accu);
+#pragma unroll
+        for (int co = 0; co < 4; ++co) {
+            const float d = acc[co] - accu[co];
+            acc[co] = acc[co] + a.guide_scale * d;
+        }
+    }
 
     const int t = a.st->t_final;
     if (a.atab) {   // table-driven loop (dd_sample_affine): t is the step index
@@ -547,6 +565,7 @@ __global__ void __launch_bounds__(256) final_kernel(const FinalArgs a) {
                 float v = row.a * a.x_in[e] + row.b * eps;      // affine_step_kernel's order and roundings
                 if (nz) v = v + row.c * zn[co];
                 a.x_out[e] = v;
+                if (G) a.x_out[e + pair] = v;
             }
         }
         return;
@@ -568,6 +587,7 @@ __global__ void __launch_bounds__(256) final_kernel(const FinalArgs a) {
                 else if (a.noise_mode == 2) v = v + sigma * zn[co];
             }
             a.x_out[e] = v;
+            if (G) a.x_out[e + pair] = v;
         }
     }
 }
@@ -579,12 +599,17 @@ __global__ void __launch_bounds__(256) final_kernel(const FinalArgs a) {
 // CT = the channel count at compile time (3, 4; 0: a.C at run time): with it the 9 C^2 conv weights are unconditional scalar loads, one
 // output channel's 9 C at a time, PT = the patch size likewise (the halo gather divides by it) -- the run-time form tested co < C / ci < C around every one of 144 candidate loads (221 scalar branches,
 // 151 s_load_dword, the weights' SGPRs spilled to VGPR lanes: ~3 900 instructions for a kernel every sampling step waits for).
-template <int CT, int PT>
+// G (classifier-free guidance, FinalArgs::pair_B): the workgroup of image b parks TWO halos, the conditional decoder rows of image b and the
+// unconditional ones of image b + pair_B (2 x 13.8 KB of LDS), gathered by one loop so that both sets of loads are in flight together -- the
+// alternative, a second gather into the one halo behind the first conv, would put a second dependent global round trip on a kernel that is
+// a chain of them; then eps = eps_c + s (eps_c - eps_u), and x' goes to images b and b + pair_B.
+template <int CT, int PT, bool G>
 __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
 #pragma clang fp contract(off)
     // (row pitch 48 = 16 mod 32 words: the two 16-pixel rows a 32-lane group reads fall into disjoint bank halves; pitch 19 gave every tap read
     // a 2-way conflict on three banks -- 1.7 conflict cycles per LDS-active cycle in the round 2-4 profiles, for a kernel that is latency, not LDS)
-    __shared__ float u[4][18][48];
+    constexpr int NH = G ? 2 : 1;     // halos: conditional (, unconditional)
+    __shared__ float u[NH][4][18][48];
     const int S = a.S, P = PT ? PT : a.P, C = CT ? CT : a.C, g = S / P, pd = P * P * C;
     const int tiles = (S + 15) / 16;
     const int b = blockIdx.x / (tiles * tiles), ty = (blockIdx.x / tiles) % tiles, tx = blockIdx.x % tiles;
@@ -614,13 +639,14 @@ __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
     const int layer = a.layer_B > 0 ? b / a.layer_B : 0;      // (early-exit heads batched into one launch: this image's layer)
     const float* wconv = a.wconv + layer * a.w_stride;
     const float* bconv = a.bconv + layer * a.b_stride;
-    for (int idx = tid; idx < 18 * 18; idx += 256) {
-        const int hy = idx / 18, hx = idx % 18;
+    for (int idx = tid; idx < NH * 18 * 18; idx += 256) {
+        const int hh = NH == 1 ? 0 : idx / (18 * 18), hi = NH == 1 ? idx : idx - hh * (18 * 18);
+        const int hy = hi / 18, hx = hi % 18;
         const int yy = ty * 16 + hy - 1, xx = tx * 16 + hx - 1;
         const bool in = yy >= 0 && yy < S && xx >= 0 && xx < S;
-        const float* src = a.dec + ((long long)b * a.L + a.extras + (in ? (yy / P) * g + (xx / P) : 0)) * pd +
+        const float* src = a.dec + ((long long)(b + hh * a.pair_B) * a.L + a.extras + (in ? (yy / P) * g + (xx / P) : 0)) * pd +
                            (in ? ((yy % P) * P + (xx % P)) * C : 0);
-        for (int ci = 0; ci < C; ++ci) u[ci][hy][hx] = in ? src[ci] : 0.f;
+        for (int ci = 0; ci < C; ++ci) u[hh][ci][hy][hx] = in ? src[ci] : 0.f;
     }
     f32x4 zn = {0.f, 0.f, 0.f, 0.f};
     if (inside && a.x_out && draw && a.noise_mode == 2)
@@ -633,32 +659,43 @@ __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
     }
     if (!inside) return;
     constexpr int CM = CT ? CT : 4;
-    float uu[CM][9];
+    float acc[NH][4] = {};
 #pragma unroll
-    for (int ci = 0; ci < CM; ++ci)
+    for (int hh = 0; hh < NH; ++hh) {
+        float uu[CM][9];
 #pragma unroll
-        for (int k = 0; k < 9; ++k) uu[ci][k] = ci < C ? u[ci][ly + k / 3][lx + k % 3] : 0.f;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int ci = 0; ci < CM; ++ci)
 #pragma unroll
-    for (int co = 0; co < CM; ++co) {
-        if (co < C) {
-            // uniform address, constant address space: scalar loads (s_load_dwordx8 ...), one output channel's 9 C weights live at a time
-            const __attribute__((address_space(4))) float* wp = (const __attribute__((address_space(4))) float*)(wconv + co * C * 9);
-            float v = bconv[co];
+            for (int k = 0; k < 9; ++k) uu[ci][k] = ci < C ? u[hh][ci][ly + k / 3][lx + k % 3] : 0.f;
 #pragma unroll
-            for (int k = 0; k < 9; ++k)
+        for (int co = 0; co < CM; ++co) {
+            if (co < C) {
+                // uniform address, constant address space: scalar loads (s_load_dwordx8 ...), one output channel's 9 C weights live at a time
+                const __attribute__((address_space(4))) float* wp = (const __attribute__((address_space(4))) float*)(wconv + co * C * 9);
+                float v = bconv[co];
 #pragma unroll
-                for (int ci = 0; ci < CM; ++ci)
-                    if (ci < C) v = fmaf(wp[ci * 9 + k], uu[ci][k], v);
-            acc[co] = v;
+                for (int k = 0; k < 9; ++k)
+#pragma unroll
+                    for (int ci = 0; ci < CM; ++ci)
+                        if (ci < C) v = fmaf(wp[ci * 9 + k], uu[ci][k], v);
+                acc[hh][co] = v;
+            }
         }
     }
+    if constexpr (G) {
+#pragma unroll
+        for (int co = 0; co < 4; ++co) {
+            const float d = acc[0][co] - acc[1][co];
+            acc[0][co] = acc[0][co] + a.guide_scale * d;
+        }
+    }
+    const long long pair = G ? (long long)a.pair_B * C * S * S : 0;   // element offset of the unconditional twin of image b
     const float sigma = a.variance == 1 ? cf.sigma_beta : cf.sigma_tilde;
 #pragma unroll
     for (int co = 0; co < 4; ++co) {
         if (co < C) {
             const long long e = (((long long)b * C + co) * S + y) * S + x;
-            const float eps = acc[co];
+            const float eps = acc[0][co];
             if (a.eps_out) a.eps_out[e] = eps;
             if (a.x_out) {
                 float v;
@@ -674,6 +711,7 @@ __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
                     }
                 }
                 a.x_out[e] = v;
+                if (G) a.x_out[e + pair] = v;
             }
         }
     }
@@ -769,6 +807,11 @@ __global__ void set_state_table_kernel(StepState* st, const AffineRow* atab, uns
     st->t_final = 0;
     st->t_model = atab[0].t_model;
     st->seed = seed;
+}
+// the label rows of one guided chain: [y [0, B) | null_label x B]
+__global__ void __launch_bounds__(256) guided_labels_kernel(const long long* __restrict__ y, long long* __restrict__ out, int B, long long null_label) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < 2 * B) out[i] = i < B ? y[i] : null_label;
 }
 __global__ void set_state_float_kernel(StepState* st, float t) {
     st->t = (int)t;
@@ -1363,17 +1406,26 @@ template hipError_t launch_fill_random<bf16_t>(bf16_t*, long long, unsigned, flo
 template hipError_t launch_fill_random<float>(float*, long long, unsigned, float, hipStream_t);
 
 hipError_t launch_final(const FinalArgs& a, hipStream_t s) {
+    if (a.pair_B > 0 && (a.pair_B != a.B || a.layer_B > 0)) return hipErrorInvalidValue;
     if (a.S >= 16) {
         const int tiles = (a.S + 15) / 16;
         const dim3 grid(a.B * tiles * tiles);
-        if (a.C == 3 && a.P == 4) hipLaunchKernelGGL((final_tiled_kernel<3, 4>), grid, dim3(256), 0, s, a);          // CelebA-64, ImageNet-64
-        else if (a.C == 3 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<3, 2>), grid, dim3(256), 0, s, a);     // CIFAR-10
-        else if (a.C == 4 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<4, 2>), grid, dim3(256), 0, s, a);     // latent 32 x 32 x 4
-        else hipLaunchKernelGGL((final_tiled_kernel<0, 0>), grid, dim3(256), 0, s, a);
+        if (a.pair_B > 0) {   // classifier-free guidance: a.B images, 2 a.B decoder images
+            if (a.C == 3 && a.P == 4) hipLaunchKernelGGL((final_tiled_kernel<3, 4, true>), grid, dim3(256), 0, s, a);
+            else if (a.C == 3 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<3, 2, true>), grid, dim3(256), 0, s, a);
+            else if (a.C == 4 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<4, 2, true>), grid, dim3(256), 0, s, a);   // ImageNet-256 latents
+            else hipLaunchKernelGGL((final_tiled_kernel<0, 0, true>), grid, dim3(256), 0, s, a);
+            return hipGetLastError();
+        }
+        if (a.C == 3 && a.P == 4) hipLaunchKernelGGL((final_tiled_kernel<3, 4, false>), grid, dim3(256), 0, s, a);          // CelebA-64, ImageNet-64
+        else if (a.C == 3 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<3, 2, false>), grid, dim3(256), 0, s, a);     // CIFAR-10
+        else if (a.C == 4 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<4, 2, false>), grid, dim3(256), 0, s, a);     // latent 32 x 32 x 4
+        else hipLaunchKernelGGL((final_tiled_kernel<0, 0, false>), grid, dim3(256), 0, s, a);
         return hipGetLastError();
     }
     const long long npix = (long long)a.B * a.S * a.S;
-    hipLaunchKernelGGL(final_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, a);
+    if (a.pair_B > 0) hipLaunchKernelGGL(final_kernel<true>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(final_kernel<false>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -1442,6 +1494,10 @@ hipError_t launch_set_state(StepState* st, int t, unsigned long long seed, hipSt
 }
 hipError_t launch_set_state_table(StepState* st, const AffineRow* atab, unsigned long long seed, hipStream_t s) {
     hipLaunchKernelGGL(set_state_table_kernel, dim3(1), dim3(1), 0, s, st, atab, seed);
+    return hipGetLastError();
+}
+hipError_t launch_guided_labels(const long long* y, long long* out, int B, long long null_label, hipStream_t s) {
+    hipLaunchKernelGGL(guided_labels_kernel, dim3((unsigned)((2 * B + 255) / 256)), dim3(256), 0, s, y, out, B, null_label);
     return hipGetLastError();
 }
 hipError_t launch_set_state_float(StepState* st, float t, hipStream_t s) {

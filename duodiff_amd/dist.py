@@ -98,11 +98,14 @@ def main(argv=None):
     if torch.cuda.is_available():
         torch.cuda.set_device(local_rank % torch.cuda.device_count())   # (ranks may share a GPU when rehearsed on one)
     config = sampler.load_config(args.config_path)
-    model, mp = sampler.build_model(config, args.checkpoint_path, args.precision, args.batch_size)
+    config_late = sampler.load_config(args.config_path_late) if args.checkpoint_path_late else None
+    sampler.validate_guidance(args, sampler.ModelParams.from_dict(config).num_classes,
+                              sampler.ModelParams.from_dict(config_late).num_classes if config_late is not None else None)
+    rows = 2 * args.batch_size if args.cfg_scale is not None else args.batch_size    # guided: 2 B backbone rows
+    model, mp = sampler.build_model(config, args.checkpoint_path, args.precision, rows)
     late = None
-    if args.checkpoint_path_late:
-        late, _ = sampler.build_model(sampler.load_config(args.config_path_late), args.checkpoint_path_late,
-                                      args.precision, args.batch_size)
+    if config_late is not None:
+        late, _ = sampler.build_model(config_late, args.checkpoint_path_late, args.precision, rows)
     post = {"predict_noise": sampler.predict_noise_postprocessing, "predict_original": sampler.predict_original_postprocessing,
             "predict_previous": sampler.predict_previous_postprocessing}[args.parametrization]
     autoencoder = None
@@ -113,13 +116,14 @@ def main(argv=None):
 
     def one_rank(seed):
         y = None
-        if args.class_id is not None:
+        if args.class_id is not None or args.class_label is not None:
             sampler.seed_everything(seed)
-            y = sampler.draw_labels(args.batch_size, mp.num_classes)      # same range check as the single-GPU CLI
+            y = sampler.labels_from_args(args, args.batch_size, mp.num_classes)   # same range check as the single-GPU CLI
         s, _ = sampler.get_samples(model, args.batch_size, post, seed, mp.in_chans, mp.img_size, mp.img_size,
                                    use_ddim=args.use_ddim, ddim_steps=args.ddim_steps, ddim_eta=args.ddim_eta,
                                    timesteps_save=[], y=y, autoencoder=autoencoder, late_model=late, t_switch=args.t_switch,
-                                   noise=args.noise, use_graph=not args.no_graph, return_device_tensor=True)
+                                   noise=args.noise, use_graph=not args.no_graph, return_device_tensor=True,
+                                   cfg_scale=args.cfg_scale, cfg_null_label=args.cfg_null_label)
         return s
 
     tic = time.time()

@@ -212,6 +212,16 @@ class Model:
                                                _ptr(y), _ptr(out), B, _stream_ptr(stream)))
         return out
 
+    def forward_guided(self, x, t, y, scale, null_label, out=None, stream=None):
+        """Classifier-free guided eps = eps_c + scale * (eps_c - eps_u) at timestep t (dd_forward_guided): the backbone runs 2 B rows,
+        x with labels y, then x with null_label; max_batch must hold them."""
+        B = x.shape[0]
+        out = torch.empty_like(x) if out is None else out
+        g = guidance_struct((scale, null_label))
+        self.ctx.check(self.ctx.lib.dd_forward_guided(self.ctx.handle, self.handle, _ptr(x), float(t), _ptr(y), C.byref(g),
+                                                      _ptr(out), B, _stream_ptr(stream)))
+        return out
+
     def sample_step(self, x, t, y=None, z=None, noise="buffer", seed=0, variance="beta_tilde", eps_out=None,
                     stream=None):
         mode = {"none": L.DD_NOISE_NONE, "buffer": L.DD_NOISE_BUFFER, "philox": L.DD_NOISE_PHILOX}[noise]
@@ -259,9 +269,16 @@ class Model:
             pass
 
 
+def guidance_struct(guidance):
+    """(scale, null_label) -> the C ABI's dd_guidance"""
+    scale, null_label = guidance
+    return L.dd_guidance(float(scale), int(null_label))
+
+
 def sample_loop(ctx: Context, first: Model, late, x, *, t_switch=0, t_start=999, t_end=0, y=None, seed=0,
-                noise="philox", variance="beta_tilde", use_graph=True, stream=None):
-    """dd_sample: the whole DDPM loop on the device (hipGraph replay per backbone), in place on x."""
+                noise="philox", variance="beta_tilde", use_graph=True, stream=None, guidance=None):
+    """dd_sample: the whole DDPM loop on the device (hipGraph replay per backbone), in place on x.
+    guidance = (scale, null_label): classifier-free guidance (dd_sample_guided; labels y required, max_batch >= 2 B)."""
     args = L.dd_sample_args()
     args.first = first.handle
     args.late = late.handle if late is not None else None
@@ -274,6 +291,11 @@ def sample_loop(ctx: Context, first: Model, late, x, *, t_switch=0, t_start=999,
     args.y_dev = y.data_ptr() if y is not None else None
     args.x_dev = x.data_ptr()
     args.B = x.shape[0]
+    if guidance is None:
+        call = lambda st: ctx.lib.dd_sample(ctx.handle, C.byref(args), st)
+    else:
+        g = guidance_struct(guidance)
+        call = lambda st: ctx.lib.dd_sample_guided(ctx.handle, C.byref(args), C.byref(g), st)
     cur = stream if stream is not None else torch.cuda.current_stream(x.device)
     if use_graph and cur.cuda_stream == 0:
         # hipGraph capture is not permitted on the legacy default stream: run the loop on a private side stream, ordered
@@ -281,19 +303,20 @@ def sample_loop(ctx: Context, first: Model, late, x, *, t_switch=0, t_start=999,
         side = ctx.side_stream(x.device)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            ctx.check(ctx.lib.dd_sample(ctx.handle, C.byref(args), _stream_ptr(side)))
+            ctx.check(call(_stream_ptr(side)))
         cur.wait_stream(side)
     else:
-        ctx.check(ctx.lib.dd_sample(ctx.handle, C.byref(args), _stream_ptr(cur)))
+        ctx.check(call(_stream_ptr(cur)))
     return x
 
 
 def sample_affine_loop(ctx: Context, first: Model, late, x, t, a, b, c, noise_flags, *, switch_after=None, y=None, seed=0,
-                       counter_base=0, noise="philox", use_graph=True, stream=None):
+                       counter_base=0, noise="philox", use_graph=True, stream=None, guidance=None):
     """dd_sample_affine: the table-driven loops (DDIM, predict_original / predict_previous) on the device, in place on x:
     x <- a[k] x + b[k] model(x, t[k]) + c[k] z for k = 0 .. len(t) - 1; the late model runs from step switch_after on.
     Step k draws z from Philox(key = seed, counter = counter_base + k): a loop cut into several calls passes the number
-    of steps already done as counter_base and draws exactly the z of the uncut loop."""
+    of steps already done as counter_base and draws exactly the z of the uncut loop.
+    guidance = (scale, null_label): classifier-free guidance of the model output (dd_sample_affine_guided)."""
     n = len(t)
     f32 = lambda v: np.ascontiguousarray(v, np.float32)
     tt, aa, bb, cc = f32(t), f32(a), f32(b), f32(c)
@@ -314,15 +337,20 @@ def sample_affine_loop(ctx: Context, first: Model, late, x, t, a, b, c, noise_fl
     args.y_dev = y.data_ptr() if y is not None else None
     args.x_dev = x.data_ptr()
     args.B = x.shape[0]
+    if guidance is None:
+        call = lambda st: ctx.lib.dd_sample_affine(ctx.handle, C.byref(args), st)
+    else:
+        g = guidance_struct(guidance)
+        call = lambda st: ctx.lib.dd_sample_affine_guided(ctx.handle, C.byref(args), C.byref(g), st)
     cur = stream if stream is not None else torch.cuda.current_stream(x.device)
     if use_graph and cur.cuda_stream == 0:      # no capture on the legacy default stream (see sample_loop)
         side = ctx.side_stream(x.device)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            ctx.check(ctx.lib.dd_sample_affine(ctx.handle, C.byref(args), _stream_ptr(side)))
+            ctx.check(call(_stream_ptr(side)))
         cur.wait_stream(side)
     else:
-        ctx.check(ctx.lib.dd_sample_affine(ctx.handle, C.byref(args), _stream_ptr(cur)))
+        ctx.check(call(_stream_ptr(cur)))
     return x
 
 

@@ -13,6 +13,10 @@ bit-identical noise for parity runs).
 DDIM (--use_ddim) and the predict_original / predict_previous parametrizations run
 the U-ViT forward on the engine plus one fused affine update per step; ImageNet-256 latents are decoded by the
 engine's KL-VAE decoder when the YAML carries an ``autoencoder`` block (next-1).
+
+Classifier-free guidance (engine option, not in the reference): ``--cfg_scale 0.4 --class_label 207`` samples a class-conditional
+model with eps = eps_c + s (eps_c - eps_u), the unconditional rows labelled ``--cfg_null_label`` (U-ViT's null class 1000), the
+combination fused into the step kernel of every loop.
 """
 import math
 import random
@@ -123,8 +127,12 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
                 sample_height: int, sample_width: int, use_ddim: bool = False, ddim_steps: int = 50,
                 ddim_eta: float = 0.0, timesteps_save: List[int] = (), y=None, autoencoder=None,
                 late_model=None, t_switch=np.inf, *, noise: str = "torch_cpu", use_graph: bool = True,
-                num_steps: int = 1000, return_device_tensor: bool = False):
+                num_steps: int = 1000, return_device_tensor: bool = False, cfg_scale=None, cfg_null_label: int = 1000):
     """reference sampler.py:82-155.  Returns (samples[B,H,W,C] float32 numpy = (x+1)/2, intermediates).
+
+    cfg_scale (None: the unguided loops, unchanged): classifier-free guidance of every step's model output,
+        eps_c + cfg_scale * (eps_c - eps_u) with the unconditional rows labelled cfg_null_label; needs labels y.  The backbones run
+        2 * batch_size rows (their max_batch grows to that).
 
     noise="torch_cpu": x_T and every z come from the torch CPU generator after seed_everything(seed),
         in the reference's order -> identical random numbers to a CPU reference run.
@@ -132,6 +140,10 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
     num_steps < 1000 runs only the first steps (t = 999 ...), for bounded benchmarks.
     """
     device = model.device
+    guidance = None if cfg_scale is None else (float(cfg_scale), int(cfg_null_label))
+    if guidance is not None and y is None:
+        raise ValueError("classifier-free guidance needs class labels")
+    rows = 2 * batch_size if guidance is not None else batch_size           # backbone rows per step
     seed_everything(seed)                                                    # sampler.py:99
     x = torch.randn(batch_size, num_channels, sample_height, sample_width).to(device).contiguous()  # :100
     if y is not None:
@@ -139,8 +151,8 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
     intermediate = []
     saves = set(int(v) for v in timesteps_save)
     t_last = 1000 - int(num_steps)
-    first = model.engine_model(batch_size)
-    late = late_model.engine_model(batch_size) if late_model is not None else None
+    first = model.engine_model(rows)
+    late = late_model.engine_model(rows) if late_model is not None else None
     ctx = first.ctx
     # the DDPM loop switches AFTER the step at t == 1000 - t_switch (sampler.py:135-136): a t_switch outside
     # [1, 1000] (0, negative, > 1000, inf) never matches a t in 999..0, i.e. the first model runs every step
@@ -150,6 +162,12 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
 
     def draw(shape):
         return torch.randn(shape).to(device) if noise == "torch_cpu" else torch.randn(shape, device=device)
+
+    def model_output(m, t, out):
+        """the model output at t for the host-noise loops: guided through dd_forward_guided when guidance is on"""
+        if guidance is None:
+            return m.forward(x, float(t), y, out=out)
+        return m.forward_guided(x, float(t), y, guidance[0], guidance[1], out=out)
 
     def affine_segments(steps, switch_after):
         """noise == "device": the table-driven loop on the device (dd_sample_affine: one hipGraph replay per step, Philox z),
@@ -163,7 +181,8 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
             seg_first, seg_late = (first, late) if (sw is None or sw > 0) else (late, None)
             sample_affine_loop(ctx, seg_first, seg_late if sw is not None and 0 < sw < len(seg) else None, x,
                                [v[0] for v in seg], [v[1] for v in seg], [v[2] for v in seg], [v[3] for v in seg],
-                               [int(v[4]) for v in seg], switch_after=sw, y=y, seed=seed, counter_base=k0, noise="philox", use_graph=use_graph)
+                               [int(v[4]) for v in seg], switch_after=sw, y=y, seed=seed, counter_base=k0, noise="philox", use_graph=use_graph,
+                               guidance=guidance)
             if seg[-1][5]:
                 intermediate.append(x.clone())
             k0 = k1
@@ -184,7 +203,7 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
             eps = torch.empty_like(x)
             cur = first
             for t, s_ in pairs:
-                cur.forward(x, float(t), y, out=eps)                             # :108-110
+                model_output(cur, t, eps)                                        # :108-110
                 a, b, c = affine_coefficients("ddim", t, s_, ddim_eta)           # :112-117
                 z = draw(x.shape) if s_ > 0 else None                            # :119
                 ctx.affine_step(x, eps, z, a, b, c, out=x)                       # :120
@@ -210,7 +229,7 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
             eps = torch.empty_like(x)
             cur = first
             for t in range(999, t_last - 1, -1):
-                cur.forward(x, float(t), y, out=eps)
+                model_output(cur, t, eps)
                 a, b, c = affine_coefficients(kind, t)
                 ctx.affine_step(x, eps, draw(x.shape) if t > 0 else None, a, b, c, out=x)
                 if switch_t is not None and t == switch_t:
@@ -227,15 +246,20 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
             if switch_t is not None and t <= switch_t - 1 and cur_late is not None:
                 cur_first, cur_late, cur_switch = late, None, 0  # already past the switch
             sample_loop(ctx, cur_first, cur_late, x, t_switch=cur_switch, t_start=t, t_end=seg_end, y=y,
-                        seed=seed, noise="philox", use_graph=use_graph)
+                        seed=seed, noise="philox", use_graph=use_graph, guidance=guidance)
             if seg_end in stops:
                 intermediate.append(x.clone())
             t = seg_end - 1
     elif noise == "torch_cpu":
         cur = first
+        eps = torch.empty_like(x) if guidance is not None else None
         for t in range(999, t_last - 1, -1):                                 # :129
             z = torch.randn(x.shape).to(device) if t > 0 else None           # :52 (CPU stream)
-            cur.sample_step(x, t, y=y, z=z, noise="buffer")                  # :130-133
+            if guidance is None:
+                cur.sample_step(x, t, y=y, z=z, noise="buffer")              # :130-133
+            else:
+                model_output(cur, t, eps)
+                ctx.ddpm_step(x, eps, z, t, out=x)
             if switch_t is not None and t == switch_t:                       # :135-136
                 cur = late
             if 1000 - t in saves:                                            # :138-139
@@ -261,6 +285,39 @@ def draw_labels(batch_size: int, num_classes: int):
     if int(y.max()) >= num_classes or int(y.min()) < 0:
         raise IndexError("index out of range in self")
     return y
+
+
+def validate_guidance(args, num_classes: int, num_classes_late=None):
+    """The label and guidance options against the configs' num_classes, before any GPU work: ValueError on a bad combination."""
+    for n in ([num_classes] + ([num_classes_late] if num_classes_late is not None else [])):
+        if args.class_label is not None:
+            if n <= 0:
+                raise ValueError("--class_label needs a class-conditional config (num_classes > 0)")
+            if not 0 <= args.class_label < n:
+                raise ValueError(f"--class_label {args.class_label} outside [0, {n}) of the config")
+        if args.cfg_scale is None:
+            continue
+        if n <= 0:
+            raise ValueError("--cfg_scale needs a class-conditional config (num_classes > 0)")
+        if not 0 <= args.cfg_null_label < n:
+            raise ValueError(f"--cfg_null_label {args.cfg_null_label} outside [0, {n}): the config has no null-class row to guide against "
+                             "(U-ViT's ImageNet-256 layout is num_classes 1001 = 1000 classes + the null label 1000)")
+    if args.class_id is not None and args.class_label is not None:
+        raise ValueError("--class_id and --class_label are exclusive")
+    if args.cfg_scale is not None:
+        if not math.isfinite(args.cfg_scale):
+            raise ValueError("--cfg_scale must be finite")
+        if args.class_id is None and args.class_label is None:
+            raise ValueError("--cfg_scale needs class labels: --class_id or --class_label")
+
+
+def labels_from_args(args, batch_size: int, num_classes: int):
+    """y of a run: --class_label K for every image, --class_id's reference draw (quirk Q4), or None."""
+    if args.class_label is not None:
+        return torch.full((batch_size,), int(args.class_label), dtype=torch.int64)
+    if args.class_id is not None:
+        return draw_labels(batch_size, num_classes)
+    return None
 
 
 def dump_samples(samples, output_folder: Path, timestep=1000):
@@ -313,6 +370,15 @@ def get_args(argv=None):
     p.add_argument("--noise", choices=["torch_cpu", "device"], default="device")
     p.add_argument("--no_graph", action="store_true", help="launch kernels eagerly instead of hipGraph replay")
     p.add_argument("--no_png", action="store_true", help="write samples.npy instead of PNG files")
+    p.add_argument("--class_label", type=int, default=None,
+                   help="(engine option) every image gets this class label (what --class_id's help promises; --class_id keeps the "
+                        "reference's random draw)")
+    p.add_argument("--cfg_scale", type=float, default=None,
+                   help="(engine option) classifier-free guidance eps = eps_c + S (eps_c - eps_u); any value, 0 included, selects the "
+                        "guided loops (default: unguided).  Needs a class-conditional config with a null-class row and --class_label or "
+                        "--class_id; an image whose drawn --class_id label equals the null label is sampled unguided")
+    p.add_argument("--cfg_null_label", type=int, default=1000,
+                   help="(engine option) label of the unconditional rows (default 1000: U-ViT's null class)")
     return p.parse_args(argv)
 
 
@@ -337,16 +403,18 @@ def main(argv=None):
             "predict_previous": predict_previous_postprocessing}[args.parametrization]
 
     config = load_config(args.config_path)
-    model, mp = build_model(config, args.checkpoint_path, args.precision, args.batch_size)
+    config_late = load_config(args.config_path_late) if args.checkpoint_path_late else None
+    validate_guidance(args, ModelParams.from_dict(config).num_classes,
+                      ModelParams.from_dict(config_late).num_classes if config_late is not None else None)
+    rows = 2 * args.batch_size if args.cfg_scale is not None else args.batch_size
+    model, mp = build_model(config, args.checkpoint_path, args.precision, rows)
     model_late = None
-    if args.checkpoint_path_late:
-        config = load_config(args.config_path_late)
-        model_late, _ = build_model(config, args.checkpoint_path_late, args.precision, args.batch_size)
+    if config_late is not None:
+        config = config_late
+        model_late, _ = build_model(config, args.checkpoint_path_late, args.precision, rows)
 
     seed_everything(args.seed)
-    y = None
-    if args.class_id is not None:
-        y = draw_labels(args.batch_size, mp.num_classes)
+    y = labels_from_args(args, args.batch_size, mp.num_classes)
     autoencoder = None
     if "autoencoder" in config:                                              # reference sampler.py:320-325
         ae_path = args.autoencoder_checkpoint_path or config["autoencoder"]["autoencoder_checkpoint_path"]
@@ -357,7 +425,8 @@ def main(argv=None):
                                  num_channels=mp.in_chans, sample_height=mp.img_size, sample_width=mp.img_size,
                                  use_ddim=args.use_ddim, ddim_steps=args.ddim_steps, ddim_eta=args.ddim_eta,
                                  y=y, autoencoder=autoencoder, late_model=model_late, t_switch=args.t_switch,
-                                 timesteps_save=args.timesteps_save, noise=args.noise, use_graph=not args.no_graph)
+                                 timesteps_save=args.timesteps_save, noise=args.noise, use_graph=not args.no_graph,
+                                 cfg_scale=args.cfg_scale, cfg_null_label=args.cfg_null_label)
     tac = time.time()
     dump_statistics(tac - tic, out, args.batch_size)
     if args.no_png:

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define DD_ABI_VERSION 5
+#define DD_ABI_VERSION 6
 
 typedef struct dd_ctx dd_ctx;
 typedef struct dd_model dd_model;
@@ -214,6 +214,30 @@ typedef struct dd_affine_sample_args {
                              * into several calls (intermediate saves) with counter_base = steps already done draws the z of one uncut call   */
 } dd_affine_sample_args;
 int dd_sample_affine(dd_ctx* ctx, const dd_affine_sample_args* args, void* stream);
+
+/* ---- classifier-free guidance (class-conditional models trained with a null class, U-ViT's ImageNet-256 layout) ---- */
+/* A guided step runs the backbone on 2 B rows: the B images with their labels (eps_c), then the same images with null_label
+ * (eps_u), and the update uses
+ *     eps = eps_c + scale * (eps_c - eps_u)      in fp32, in exactly that order: d = eps_c - eps_u; eps = eps_c + scale * d
+ * inside the step's last kernel (no extra launch).  The models' max_batch must hold 2 B rows.  When the loop runs as two chains
+ * (the decision is made on 2 B rows), the split is by image: an image's conditional and unconditional rows stay in one chain.
+ * Philox noise is drawn per image exactly as the unguided loop draws it, so scale 0 reproduces dd_sample / dd_sample_affine with
+ * the same labels.  A label equal to null_label simply makes that image unguided (eps_c == eps_u).
+ * DDIM and the predict_original / predict_previous parametrisations guide the raw model output with the same rule: for a fixed
+ * x_t both outputs are affine in eps, and the weights (1 + scale, -scale) sum to 1, so guiding the output is guiding eps.
+ * Every entry returns DD_ERR_INVALID (with dd_last_error) before enqueueing anything when a model is unconditional, null_label is
+ * outside [0, num_classes) of a model, 2 B > max_batch, a model carries early-exit heads (not supported with guidance), or
+ * scale is not finite. */
+typedef struct dd_guidance {
+    float scale;            /* eps = eps_c + scale * (eps_c - eps_u), fp32, in that order */
+    int32_t null_label;     /* label of the unconditional rows, 0 <= null_label < num_classes */
+} dd_guidance;
+/* x_dev [B,C,S,S], y_dev [B] int64 (required), eps_dev [B,C,S,S]: the guided eps at timestep t (host-noise loops, parity) */
+int dd_forward_guided(dd_ctx* ctx, dd_model* m, const float* x_dev, float t, const int64_t* y_dev, const dd_guidance* g,
+                      float* eps_dev, int B, void* stream);
+/* dd_sample / dd_sample_affine with guidance; args->B images, args->y_dev required */
+int dd_sample_guided(dd_ctx* ctx, const dd_sample_args* args, const dd_guidance* g, void* stream);
+int dd_sample_affine_guided(dd_ctx* ctx, const dd_affine_sample_args* args, const dd_guidance* g, void* stream);
 
 /* The early-exit baseline's loop (reference eesampler.py:40-89) as a device-resident loop: per step EarlyExitUViT.forward
  * (all heads and probes), the per-sample exit selection with the global threshold, the DDPM update (sigma^2 = beta-tilde)

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <new>
 #include <string>
@@ -31,9 +32,8 @@ int device_num_cus();
 struct dd_ctx {
     int device = 0;
     std::string err;
-    StepState* st = nullptr;     // device
-    StepState* st2 = nullptr;    // device: the second half-batch chain of dd_sample (its own timestep / counter)
-    hipStream_t side = nullptr;  // that chain's stream (context-owned, non-blocking)
+    StepState* st[2] = {nullptr, nullptr};   // device: the step state (timestep / counter) of each half-batch chain (Chain)
+    hipStream_t side = nullptr;  // the second chain's stream (context-owned, non-blocking)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t ev_ee_fork = nullptr, ev_ee_join = nullptr;   // early-exit heads / probes of a layer on the side stream, beside the block's attention launch
     StepCoef* coef = nullptr;    // device [1000]
@@ -41,7 +41,6 @@ struct dd_ctx {
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     float timing[3] = {0, 0, 0};
     int num_cus = 256;           // CU count the persistent GEMM grids are sized for (dd_set_num_cus), a multiple of 8
-    int base_cus = 256;          // ... as set; num_cus itself is halved while a chained call captures the graphs of a large GEMM-path batch
     // dd_sample's graphs run on context-owned staging copies of x / y, so a captured step does not depend on the caller's
     // tensor addresses (reference get_samples allocates a fresh x per call: the graphs would be re-captured every time)
     float* x_stage = nullptr;
@@ -53,7 +52,6 @@ struct dd_ctx {
     AffineRow* atab = nullptr;
     size_t atab_rows = 0;
     std::vector<AffineRow> atab_host;
-    bool ee_inline = false;      // early-exit heads / probes stay on the launch stream (set while the two chains of dd_sample_early_exit are enqueued: `side` is a chain's stream then)
     int prof_kind = 0;           // dd_profile_select: which launches dd_profile_steps brackets (DD_PROF_*)
     unsigned dev_flags = 0;      // dd_dev_set_flags (include/duodiff_dev.h): kernel-variant switches of the development harness
 };
@@ -113,6 +111,9 @@ struct GraphKey {
     }
 };
 
+// the captured step of each sampling loop: dd_model::graph[kind][chain]
+enum GraphKind { GRAPH_DDPM, GRAPH_AFFINE, GRAPH_EARLY_EXIT, GRAPH_KINDS };
+
 }  // namespace
 
 // The activation workspace of one chain: dd_sample runs a large batch as TWO independent half-batch chains on two streams (one
@@ -120,9 +121,13 @@ struct GraphKey {
 struct WsPtrs {
     float* x = nullptr; void *h = nullptr, *ao = nullptr, *qkv = nullptr, *hid = nullptr, *xb = nullptr;
     std::vector<void*> skips;
-    float* dec = nullptr; float* mlp_partial = nullptr; bf16_t* qkv_dump = nullptr; bf16_t* hfrag = nullptr; float* ytap = nullptr;
+    float* dec = nullptr;
+    float* mlp_partial = nullptr;         // partial slabs of hidden-split leftover tiles (mlp_fused_plan)
+    bf16_t* qkv_dump = nullptr;           // scratch for the qkv stores of rows past the end of a ragged tile
+    bf16_t* hfrag = nullptr;              // fused_qa: norm1 of the patch rows in MFMA fragment order (MlpFusedArgs::ln_out_frag)
+    float* ytap = nullptr;                // early-exit models with fused_skip: the block output y of the launches that run the next skip_linear (MlpFusedArgs::y_tap)
 };
-struct WsOffsets { size_t x, h, ao, qkv, hid, xb, dec, part, dump, hf, bytes; std::vector<size_t> sk; bool has_part, has_dump, has_hf; size_t part_bytes = 0; size_t tap = 0; bool has_tap = false; };
+struct WsOffsets { size_t x, h, ao, qkv, hid, xb, dec, part, dump, hf, bytes; std::vector<size_t> sk; bool has_part, has_dump, has_hf; size_t tap = 0; bool has_tap = false; };
 
 struct dd_model {
     dd_ctx* ctx = nullptr;
@@ -133,15 +138,11 @@ struct dd_model {
     int prec = DD_PREC_BF16;
     size_t esize = 2;
     char* warena = nullptr;    // weights
-    char* wsarena = nullptr;   // activations
     std::vector<BlockW> blocks;  // in.., mid, out..
     const float *emb_wt = nullptr, *emb_b = nullptr, *pos = nullptr, *label = nullptr;
     const float *tm_w1t = nullptr, *tm_b1 = nullptr, *tm_w2t = nullptr, *tm_b2 = nullptr;   // time_embed MLP (mlp_time_embed)
     const float *norm_g = nullptr, *norm_b = nullptr, *wdec = nullptr, *bdec = nullptr, *wconv = nullptr, *bconv = nullptr;
     const float *wdec_g = nullptr, *dec_c = nullptr;   // head_dec_kernel operands (decoder weight * norm gamma; bias + W . beta [pd], then the row sums of wdec_g [pd]) or null
-    float* x = nullptr; void* h = nullptr; void* ao = nullptr; void* qkv = nullptr; void* hid = nullptr; void* xb = nullptr;
-    std::vector<void*> skips;
-    float* dec = nullptr;
     // early-exit baseline (models/early_exit.py:193-268): per-layer output heads + MLP probes; ee_type < 0: plain U-ViT
     int ee_type = -1, n_probe = 0;
     std::vector<HeadW> heads;             // head i is applied to the input of block i
@@ -160,19 +161,14 @@ struct dd_model {
     bool rowlin_fc2 = false;              // embed_dim 768 on the GEMM path: mlp.fc2 + residual + the next block's norm1 in one row-resident launch (rowlin.hip)
     bool fused_qa = false;                // attn.qkv computed inside the attention launch (attention.hip qkv_attention_kernel): takes precedence over
                                           // fused_qkv wherever the previous block's fused launch leaves norm1 in h
-    bf16_t* qkv_dump = nullptr;           // scratch for the qkv stores of rows past the end of a ragged tile
-    bf16_t* hfrag = nullptr;              // fused_qa: norm1 of the patch rows in MFMA fragment order (MlpFusedArgs::ln_out_frag)
-    float* ytap = nullptr;                // early-exit models with fused_skip: the block output y of the launches that run the next skip_linear (MlpFusedArgs::y_tap)
-    float* mlp_partial = nullptr;         // partial slabs of hidden-split leftover tiles (mlp_fused_plan)
-    size_t mlp_partial_bytes = 0;
-    hipGraphExec_t graph[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [0] DDPM step (dd_sample), [1] table-driven step (dd_sample_affine),
-    GraphKey gkey[6]{};                                      // [2] early-exit step (dd_sample_early_exit), [3] / [4] / [5]: [0] / [1] / [2] of the second chain
-    WsOffsets wsoff{}, wsoff2{};                             // layout of the main workspace (max_batch) and of the second chain's (half of it)
-    char* wsarena2 = nullptr;                                // the second chain's workspace (allocated by the first chained dd_sample)
-    WsPtrs ws2;
-    float* ee_ws = nullptr;                                  // dd_sample_early_exit scratch: eps | model_output | cls | outs (two chains: one such block per chain, half the batch each)
-    float* ee_sums = nullptr;                                // ... and the chains' per-step sums of the predicted errors [2][1000][depth]
-    size_t ee_ws_elems = 0;
+    // each chain's activation workspace: [0] laid out for max_batch (dd_model_finalize), [1] for half of it (ensure_chain_ws, on the first chained call)
+    WsOffsets wsoff[2]{};
+    char* wsarena[2] = {nullptr, nullptr};
+    WsPtrs ws[2];
+    hipGraphExec_t graph[GRAPH_KINDS][2] = {};                // each loop's captured step, per chain
+    GraphKey gkey[GRAPH_KINDS][2]{};
+    float* ee_ws = nullptr;                                  // dd_sample_early_exit scratch: eps | cls | outs (two chains: one such block per chain, half the batch each),
+                                                             // then the chains' per-step sums of the predicted errors [2][1000][depth]
     // in-context timing (dd_profile_steps): event pairs recorded around each launch of kind ctx->prof_kind when enabled
     bool time_fc1 = false;
     std::vector<hipEvent_t> fc1_events;   // pairs, grown on demand
@@ -467,30 +463,33 @@ WsOffsets ws_layout(const dd_model* m, int batch) {
     const size_t o_tap = take(has_tap ? Mp * D * 4 : 0);
     WsOffsets o{o_x, o_h, o_ao, o_qkv, o_hid, o_xb, o_dec, o_part, o_dump, o_hf, off, o_sk, part_bytes != 0, m->fused_qkv, m->fused_qa};
     o.bytes = off;
-    o.part_bytes = part_bytes;
     o.tap = o_tap; o.has_tap = has_tap;
     return o;
 }
-// exchange the model's workspace pointers with the second chain's (the caller swaps the context's step state too): the launch sequence of a step is
-// enqueued / captured for that chain by the same code, on the same weights
-void swap_chain(dd_model* m) {
-    WsPtrs& w = m->ws2;
-    std::swap(m->x, w.x); std::swap(m->h, w.h); std::swap(m->ao, w.ao); std::swap(m->qkv, w.qkv); std::swap(m->hid, w.hid);
-    std::swap(m->xb, w.xb); std::swap(m->dec, w.dec); std::swap(m->skips, w.skips); std::swap(m->mlp_partial, w.mlp_partial);
-    std::swap(m->qkv_dump, w.qkv_dump); std::swap(m->hfrag, w.hfrag); std::swap(m->ytap, w.ytap);
-}
+// What a step runs on: the launch sequence of a step is enqueued / captured for either half-batch chain by the same code, on the same
+// weights, with the chain's own workspace and step state.  cus: the CU count its persistent GEMM grids are sized for (halved for both
+// chains of a large GEMM-path batch, chain_gemm_cus); ee_fork: early-exit heads / probes may fork onto the context's side stream (not
+// while `side` carries the second chain).
+struct Chain {
+    const WsPtrs* ws;
+    StepState* st;
+    int cus;
+    bool ee_fork;
+};
+Chain whole_batch(dd_ctx* c, dd_model* m) { return Chain{&m->ws[0], c->st[0], c->num_cus, true}; }
 
-// ---- the forward: tokens -> blocks -> decoder_pred patches (m->dec) ---------------------------
+// ---- the forward: tokens -> blocks -> decoder_pred patches (the chain's dec) -----------------------
 // early-exit taps of one forward (EarlyExitUViT.forward, early_exit.py:290-313): cls [depth, B], outs [depth, B, C, S, S]
 struct EeTaps { float* cls; float* outs; int t; };
 
 template <typename T>
-int run_backbone(dd_model* m, const float* x_img, const float* t_vec, const int64_t* y_dev, int B, hipStream_t s,
+int run_backbone(dd_model* m, const Chain& ch, const float* x_img, const float* t_vec, const int64_t* y_dev, int B, hipStream_t s,
                  const EeTaps* ee = nullptr) {
     dd_ctx* c = m->ctx;
+    const WsPtrs& ws = *ch.ws;
     const int D = m->D, L = m->L, M = B * L;
     const int Mp = round_up(M, 256);
-    EmbedArgs ea{x_img, m->emb_wt, m->emb_b, m->pos, m->label, (const long long*)y_dev, t_vec, c->st, m->x,
+    EmbedArgs ea{x_img, m->emb_wt, m->emb_b, m->pos, m->label, (const long long*)y_dev, t_vec, ch.st, ws.x,
                  B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, D, L, m->extras,
                  m->cfg.num_classes, m->cfg.normalize_timesteps, Mp, (c->dev_flags & DD_DEV_GENERIC_EMBED) ? 1 : 0};
     // the first block's norm1 of the patch rows from the embed launch's registers (where the attention launch computes attn.qkv itself and
@@ -498,13 +497,13 @@ int run_backbone(dd_model* m, const float* x_img, const float* t_vec, const int6
     bool ln1_done = false;
     if constexpr (sizeof(T) == 2) {
         if (m->fused_qa && !(c->dev_flags & DD_DEV_NO_EMBED_LN) && embed_ln_supported(ea)) {
-            ea.ln_g = m->blocks[0].ln1_g; ea.ln_b = m->blocks[0].ln1_b; ea.ln_frag = m->hfrag;
+            ea.ln_g = m->blocks[0].ln1_g; ea.ln_b = m->blocks[0].ln1_b; ea.ln_frag = ws.hfrag;
             ln1_done = true;
         }
     }
     DD_HIP(c, launch_embed(ea, s));
     if (m->tm_w1t) {   // mlp_time_embed: the time token goes through Linear -> SiLU -> Linear (models/uvit.py:264-272, 358)
-        TimeMlpArgs ta{m->tm_w1t, m->tm_b1, m->tm_w2t, m->tm_b2, m->pos, t_vec, c->st, m->x, B, D, L, m->extras, m->cfg.normalize_timesteps};
+        TimeMlpArgs ta{m->tm_w1t, m->tm_b1, m->tm_w2t, m->tm_b2, m->pos, t_vec, ch.st, ws.x, B, D, L, m->extras, m->cfg.normalize_timesteps};
         DD_HIP(c, launch_time_mlp(ta, s));
     }
 
@@ -521,9 +520,9 @@ int run_backbone(dd_model* m, const float* x_img, const float* t_vec, const int6
         return DD_OK;
     };
     // 128 x 128 or 256 x 256 tiles for a bf16 Linear: decided for the model's max_batch on the context's CU count -- never for the batch (or the
-    // chain-halved grid) of this call, so that a row takes the same kernel alone, in a full batch and in a half-batch chain
-    auto tile128 = [&](int N, int K, int K1) { return sizeof(T) == 2 && gemm_prefers_128(m->cfg.max_batch * L, N, K, K1, c->base_cus) ? 1 : 0; };
-    T* h = (T*)m->h; T* ao = (T*)m->ao; T* qkv = (T*)m->qkv; T* hid = (T*)m->hid; T* xb = (T*)m->xb;
+    // chain-halved grid, Chain::cus) of this call, so that a row takes the same kernel alone, in a full batch and in a half-batch chain
+    auto tile128 = [&](int N, int K, int K1) { return sizeof(T) == 2 && gemm_prefers_128(m->cfg.max_batch * L, N, K, K1, c->num_cus) ? 1 : 0; };
+    T* h = (T*)ws.h; T* ao = (T*)ws.ao; T* qkv = (T*)ws.qkv; T* hid = (T*)ws.hid; T* xb = (T*)ws.xb;
     const int nb = (int)m->blocks.size();
     bool h_ready = ln1_done;   // h already holds norm1 of the coming block (written by the fused MLP of the previous one / the embed launch)
     bool skip_done = false; // ... and x already holds that block's skip_linear output (the previous fused launch ran it too)
@@ -538,7 +537,7 @@ int run_backbone(dd_model* m, const float* x_img, const float* t_vec, const int6
     float* ee_srow_all = nullptr;
     if (ee && sizeof(T) == 2 && m->fused_mlp && m->ee_conv_stride_ok && m->heads[0].wg && m->cfg.img_size >= 16 &&
         (size_t)nb * ((size_t)M * m->pd + (size_t)B * L) * sizeof(float) <= (size_t)Mp * m->hid_ld * m->esize) {
-        ee_dec_all = (float*)m->hid;
+        ee_dec_all = (float*)ws.hid;
         ee_srow_all = ee_dec_all + (size_t)nb * M * m->pd;
     }
     for (int bi = 0; bi < nb; ++bi) {
@@ -551,8 +550,8 @@ int run_backbone(dd_model* m, const float* x_img, const float* t_vec, const int6
             // writes x (attn.proj).  Out-blocks start with skip_linear, which overwrites x: their heads stay in line.
             const HeadW& hd = m->heads[bi];
             // (the previous launch ran this block's skip_linear already: x holds its output, the tapped y is in ytap)
-            const float* xin = (skip_done && m->ytap) ? m->ytap : m->x;
-            ee_side = !is_out && c->side && s != c->side && !c->ee_inline;
+            const float* xin = (skip_done && ws.ytap) ? ws.ytap : ws.x;
+            ee_side = !is_out && ch.ee_fork && c->side && s != c->side;
             hipStream_t hs = ee_side ? c->side : s;
             if (ee_side) {
                 DD_HIP(c, hipEventRecord(c->ev_ee_fork, s));
@@ -564,51 +563,51 @@ int run_backbone(dd_model* m, const float* x_img, const float* t_vec, const int6
             const int add = m->ee_type == DD_EE_MLP_PER_TIMESTEP ? 0 : bi;
             bool probe_done = false;
             if (hd.wg) {   // the head's LayerNorm + decoder_pred in one exact-fp32 launch (the final head's kernel), patch rows only
-                HeadDecArgs ha{xin, hd.wg, hd.dc, ee_dec_all ? ee_dec_all + (size_t)bi * M * m->pd : m->dec, M, m->pd, (L - m->extras) % 16 == 0 ? L : 0, m->extras};
+                HeadDecArgs ha{xin, hd.wg, hd.dc, ee_dec_all ? ee_dec_all + (size_t)bi * M * m->pd : ws.dec, M, m->pd, (L - m->extras) % 16 == 0 ? L : 0, m->extras};
                 if (hd.wsplit) { ha.wg = hd.wsplit; ha.c = hd.dcs; ha.split = 1; }      // (bf16 engine: the split-bf16 product, rowops.hip SPLIT)
                 if (ee_srow_all && m->ee_type != DD_EE_ATTENTION_PROBE && head_dec_probe_supported(D)) {   // ... and the MLP probe's per-token values of the same rows
-                    ha.srow = ee_srow_all + (size_t)bi * B * L; ha.pw_base = m->probe_w; ha.pb_base = m->probe_b; ha.st = c->st; ha.t_mul = t_mul; ha.add = add;
+                    ha.srow = ee_srow_all + (size_t)bi * B * L; ha.pw_base = m->probe_w; ha.pb_base = m->probe_b; ha.st = ch.st; ha.t_mul = t_mul; ha.add = add;
                     probe_done = true;
                 }
-                DD_HIP(c, launch_head_dec(ha, D, c->num_cus, hs));
+                DD_HIP(c, launch_head_dec(ha, D, ch.cus, hs));
             } else {
-                float* hf = (float*)m->hid;   // the MLP hidden buffer is free between blocks
+                float* hf = (float*)ws.hid;   // the MLP hidden buffer is free between blocks
                 DD_HIP(c, launch_layernorm<float>(xin, hd.ng, hd.nb, hf, M, D, hs));
-                GemmArgs<float> g{hf, nullptr, hd.wdec, hd.bdec, m->dec, nullptr, M, m->pd, D, D, D, 0, m->pd};
-                DD_HIP(c, launch_gemm<float>(g, EPI_BIAS_SET, hs, c->num_cus));
+                GemmArgs<float> g{hf, nullptr, hd.wdec, hd.bdec, ws.dec, nullptr, M, m->pd, D, D, D, 0, m->pd};
+                DD_HIP(c, launch_gemm<float>(g, EPI_BIAS_SET, hs, ch.cus));
             }
             const long long chw = (long long)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
             if (!ee_dec_all) {
-                FinalArgs fa{m->dec, hd.wconv, hd.bconv, nullptr, nullptr, ee->outs + (long long)bi * B * chw, nullptr, c->st,
+                FinalArgs fa{ws.dec, hd.wconv, hd.bconv, nullptr, nullptr, ee->outs + (long long)bi * B * chw, nullptr, ch.st,
                              c->coef, B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, DD_NOISE_NONE, 0, 0};
                 DD_HIP(c, launch_final(fa, hs));
             }
             if (m->ee_type == DD_EE_ATTENTION_PROBE) {
                 DD_HIP(c, launch_ee_attn_probe(xin, m->attn_probes[bi], ee->cls + (long long)bi * B, B, L, D, hs));
             } else if (!probe_done) {
-                if (ee_srow_all) DD_HIP(c, launch_ee_probe(xin, m->probe_w, m->probe_b, nullptr, ee_srow_all + (size_t)bi * B * L, B, L, D, c->st, t_mul, add, hs));   // rows only: reduced behind the last block
-                else DD_HIP(c, launch_ee_probe(xin, m->probe_w, m->probe_b, ee->cls + (long long)bi * B, (float*)m->hid, B, L, D, c->st, t_mul, add, hs));   // (the MLP hidden buffer is free between blocks)
+                if (ee_srow_all) DD_HIP(c, launch_ee_probe(xin, m->probe_w, m->probe_b, nullptr, ee_srow_all + (size_t)bi * B * L, B, L, D, ch.st, t_mul, add, hs));   // rows only: reduced behind the last block
+                else DD_HIP(c, launch_ee_probe(xin, m->probe_w, m->probe_b, ee->cls + (long long)bi * B, (float*)ws.hid, B, L, D, ch.st, t_mul, add, hs));   // (the MLP hidden buffer is free between blocks)
             }
             if (ee_side) DD_HIP(c, hipEventRecord(c->ev_ee_join, c->side));
         }
         if (is_out && !skip_done) {
             const int oi = bi - m->half_depth - 1;
-            const T* skip = (const T*)m->skips[m->half_depth - 1 - oi];  // LIFO (uvit.py:374-375)
-            GemmArgs<T> g{xb, skip, (const T*)w.skip_w, w.skip_b, m->x, nullptr, M, D, 2 * D, D, D, D, D};
+            const T* skip = (const T*)ws.skips[m->half_depth - 1 - oi];  // LIFO (uvit.py:374-375)
+            GemmArgs<T> g{xb, skip, (const T*)w.skip_w, w.skip_b, ws.x, nullptr, M, D, 2 * D, D, D, D, D};
             g.tile128 = tile128(D, 2 * D, D);
             bool done = false;
             if constexpr (sizeof(T) == 2) {
                 if (m->rowlin_skip) {     // (embed_dim 768) x = skip_linear(cat[x, skip]) and this block's norm1 in one row-resident launch
                     RowLinArgs ra{};
                     ra.A = (const bf16_t*)xb; ra.A2 = (const bf16_t*)skip; ra.k_split = D; ra.set_x = 1; ra.lda = D; ra.K = 2 * D;
-                    ra.wimg = w.rls_img; ra.bias = w.skip_b; ra.xres = m->x; ra.partial = m->mlp_partial; ra.ln_g = w.ln1_g; ra.ln_b = w.ln1_b;
-                    if (m->fused_qa) ra.h_frag = m->hfrag; else ra.h_out = (bf16_t*)h;
+                    ra.wimg = w.rls_img; ra.bias = w.skip_b; ra.xres = ws.x; ra.partial = ws.mlp_partial; ra.ln_g = w.ln1_g; ra.ln_b = w.ln1_b;
+                    if (m->fused_qa) ra.h_frag = ws.hfrag; else ra.h_out = (bf16_t*)h;
                     rowlin_plan(B, m->N, m->extras, L, 2 * D, ra);
                     if (int rc = mark(DD_PROF_ROWLIN)) return rc;
                     DD_HIP(c, launch_rowlin(ra, s));
                     if (int rc = mark(DD_PROF_ROWLIN)) return rc;
                     MlpFusedArgs fr{};
-                    fr.b2 = w.skip_b; fr.xres = m->x; fr.partial = m->mlp_partial; fr.ldo = D; fr.reduce_set = 1;
+                    fr.b2 = w.skip_b; fr.xres = ws.x; fr.partial = ws.mlp_partial; fr.ldo = D; fr.reduce_set = 1;
                     fr.tok_n = ra.tok_n; fr.tok_e = ra.tok_e; fr.tok_l = ra.tok_l; fr.n_extra = ra.n_extra; fr.tiles_left = ra.tiles_extra;
                     fr.groups = ra.groups; fr.prows = 128;
                     if (!m->fused_qa) { fr.ln_out_g = w.ln1_g; fr.ln_out_b = w.ln1_b; fr.ln_out = (bf16_t*)h; }
@@ -618,40 +617,40 @@ int run_backbone(dd_model* m, const float* x_img, const float* t_vec, const int6
             }
             if constexpr (sizeof(T) == 2) {
                 if (m->splitk && !done) {     // split-K halves -> slabs; x = bias + slabs and this block's norm1 in the row pass behind it
-                    g.partial = m->mlp_partial; g.splits = 2;
+                    g.partial = ws.mlp_partial; g.splits = 2;
                     if (int rc = mark(DD_PROF_SPLITK)) return rc;
-                    DD_HIP(c, launch_gemm_splitk(g, s, c->num_cus));
+                    DD_HIP(c, launch_gemm_splitk(g, s, ch.cus));
                     if (int rc = mark(DD_PROF_SPLITK)) return rc;
-                    ReduceLnArgs ra{m->x, m->mlp_partial, (long long)M * D, 2, 0, w.skip_b, nullptr, D, w.ln1_g, w.ln1_b, (bf16_t*)h,
-                                    m->fused_qa ? m->hfrag : nullptr, L, m->extras, M};
+                    ReduceLnArgs ra{ws.x, ws.mlp_partial, (long long)M * D, 2, 0, w.skip_b, nullptr, D, w.ln1_g, w.ln1_b, (bf16_t*)h,
+                                    m->fused_qa ? ws.hfrag : nullptr, L, m->extras, M};
                     DD_HIP(c, launch_reduce_ln(ra, D, s));
                     h_ready = true; qa_ready = m->fused_qa; done = true;
                 }
             }
-            if (!done) DD_HIP(c, launch_gemm<T>(g, EPI_BIAS_SET, s, c->num_cus));
+            if (!done) DD_HIP(c, launch_gemm<T>(g, EPI_BIAS_SET, s, ch.cus));
         }
         skip_done = false;
         if (!h_ready && !qkv_done) {     // else: written by the previous block's fused MLP
             if (sizeof(T) == 2 && m->fused_qa) {
                 // (the first block; blocks behind a skip_linear GEMM when that fusion is off) norm1 straight into the order the
                 // attention launch loads it, so that these blocks take the same launch as the others
-                DD_HIP(c, launch_layernorm_frag(m->x, w.ln1_g, w.ln1_b, (bf16_t*)h, m->hfrag, M, D, L, m->extras, s));
+                DD_HIP(c, launch_layernorm_frag(ws.x, w.ln1_g, w.ln1_b, (bf16_t*)h, ws.hfrag, M, D, L, m->extras, s));
                 qa_ready = true;
             } else {
-                DD_HIP(c, launch_layernorm<T>(m->x, w.ln1_g, w.ln1_b, h, M, D, s));
+                DD_HIP(c, launch_layernorm<T>(ws.x, w.ln1_g, w.ln1_b, h, M, D, s));
             }
         }
         h_ready = false;
         if (qa_ready) {
             if (int rc = mark(DD_PROF_QKV_ATTENTION)) return rc;
             if constexpr (sizeof(T) == 2)
-                DD_HIP(c, launch_qkv_attention(m->hfrag, w.qa_img, w.qkv_b, nullptr, m->x, w.ln1_g, w.ln1_b, (bf16_t*)ao, B, L, m->H, D, m->extras, s));
+                DD_HIP(c, launch_qkv_attention(ws.hfrag, w.qa_img, w.qkv_b, nullptr, ws.x, w.ln1_g, w.ln1_b, (bf16_t*)ao, B, L, m->H, D, m->extras, s));
             if (int rc = mark(DD_PROF_QKV_ATTENTION)) return rc;
         } else {
             if (!qkv_done) {
                 GemmArgs<T> g{h, nullptr, (const T*)w.qkv_w, w.qkv_b, nullptr, qkv, M, 3 * D, D, D, D, 0, 3 * D};
                 g.hm = make_head_major(L, m->H);     // head-major: each (q | k | v, head) unit of an image is contiguous (attention.hip)
-                DD_HIP(c, launch_gemm<T>(g, w.qkv_b ? EPI_BIAS_STORE : EPI_STORE, s, c->num_cus));
+                DD_HIP(c, launch_gemm<T>(g, w.qkv_b ? EPI_BIAS_STORE : EPI_STORE, s, ch.cus));
             }
             if (int rc = mark(DD_PROF_QKV_ATTENTION)) return rc;
             DD_HIP(c, launch_attention<T>(qkv, ao, B, L, m->H, D, s));
@@ -667,14 +666,14 @@ int run_backbone(dd_model* m, const float* x_img, const float* t_vec, const int6
             if (m->rowlin_proj) {
                 // (embed_dim 768) x += proj(ao) + b and norm2 of the updated rows in one row-resident launch (see mlp.fc2 below)
                 RowLinArgs ra{};
-                ra.A = (const bf16_t*)ao; ra.lda = D; ra.K = D; ra.wimg = w.rlp_img; ra.bias = w.proj_b; ra.xres = m->x;
-                ra.partial = m->mlp_partial; ra.ln_g = w.ln2_g; ra.ln_b = w.ln2_b; ra.h_out = (bf16_t*)h;
+                ra.A = (const bf16_t*)ao; ra.lda = D; ra.K = D; ra.wimg = w.rlp_img; ra.bias = w.proj_b; ra.xres = ws.x;
+                ra.partial = ws.mlp_partial; ra.ln_g = w.ln2_g; ra.ln_b = w.ln2_b; ra.h_out = (bf16_t*)h;
                 rowlin_plan(B, m->N, m->extras, L, D, ra);
                 if (int rc = mark(DD_PROF_ROWLIN)) return rc;
                 DD_HIP(c, launch_rowlin(ra, s));
                 if (int rc = mark(DD_PROF_ROWLIN)) return rc;
                 MlpFusedArgs fr{};
-                fr.b2 = w.proj_b; fr.xres = m->x; fr.partial = m->mlp_partial; fr.ldo = D;
+                fr.b2 = w.proj_b; fr.xres = ws.x; fr.partial = ws.mlp_partial; fr.ldo = D;
                 fr.tok_n = ra.tok_n; fr.tok_e = ra.tok_e; fr.tok_l = ra.tok_l; fr.n_extra = ra.n_extra; fr.tiles_left = ra.tiles_extra;
                 fr.groups = ra.groups; fr.prows = 128;
                 fr.ln_out_g = w.ln2_g; fr.ln_out_b = w.ln2_b; fr.ln_out = (bf16_t*)h;
@@ -685,24 +684,24 @@ int run_backbone(dd_model* m, const float* x_img, const float* t_vec, const int6
         if constexpr (sizeof(T) == 2) {
             if (m->splitk && !ln2_done) {     // attn.proj as split-K halves; x += bias + slabs and norm2 in the row pass behind it
                 GemmArgs<T> g{ao, nullptr, (const T*)w.proj_w, nullptr, nullptr, nullptr, M, D, D, D, D, 0, D};
-                g.partial = m->mlp_partial; g.splits = 2;
+                g.partial = ws.mlp_partial; g.splits = 2;
                 if (int rc = mark(DD_PROF_SPLITK)) return rc;
-                DD_HIP(c, launch_gemm_splitk(g, s, c->num_cus));
+                DD_HIP(c, launch_gemm_splitk(g, s, ch.cus));
                 if (int rc = mark(DD_PROF_SPLITK)) return rc;
-                ReduceLnArgs ra{m->x, m->mlp_partial, (long long)M * D, 2, 1, w.proj_b, nullptr, D, w.ln2_g, w.ln2_b, (bf16_t*)h, nullptr, L, m->extras, M};
+                ReduceLnArgs ra{ws.x, ws.mlp_partial, (long long)M * D, 2, 1, w.proj_b, nullptr, D, w.ln2_g, w.ln2_b, (bf16_t*)h, nullptr, L, m->extras, M};
                 DD_HIP(c, launch_reduce_ln(ra, D, s));
                 ln2_done = true;
             }
         }
         if (!ln2_done && !(sizeof(T) == 2 && m->fused_proj)) {   // fused: x += proj(ao) + b happens inside the fused MLP launch below
-            GemmArgs<T> g{ao, nullptr, (const T*)w.proj_w, w.proj_b, m->x, nullptr, M, D, D, D, D, 0, D};
+            GemmArgs<T> g{ao, nullptr, (const T*)w.proj_w, w.proj_b, ws.x, nullptr, M, D, D, D, D, 0, D};
             g.tile128 = tile128(D, D, D);
-            DD_HIP(c, launch_gemm<T>(g, EPI_BIAS_RESID, s, c->num_cus));
+            DD_HIP(c, launch_gemm<T>(g, EPI_BIAS_RESID, s, ch.cus));
         }
-        if (!ln2_done && !(sizeof(T) == 2 && m->fused_mlp)) DD_HIP(c, launch_layernorm<T>(m->x, w.ln2_g, w.ln2_b, h, M, D, s));   // fused MLP: norm2 in its prologue
+        if (!ln2_done && !(sizeof(T) == 2 && m->fused_mlp)) DD_HIP(c, launch_layernorm<T>(ws.x, w.ln2_g, w.ln2_b, h, M, D, s));   // fused MLP: norm2 in its prologue
         // the T-typed copy of the block output feeds a later skip_linear: as the `skip`
         // operand (in-blocks) or as the `x` operand (mid / out blocks, except the last)
-        T* copy = is_in ? (T*)m->skips[bi] : (bi + 1 < nb ? xb : nullptr);
+        T* copy = is_in ? (T*)ws.skips[bi] : (bi + 1 < nb ? xb : nullptr);
         if constexpr (sizeof(T) == 2) {
             if (m->fused_mlp) {
                 MlpFusedArgs fa{};
@@ -712,14 +711,14 @@ int run_backbone(dd_model* m, const float* x_img, const float* t_vec, const int6
                     fa.ln_out_g = m->blocks[bi + 1].ln1_g; fa.ln_out_b = m->blocks[bi + 1].ln1_b; fa.ln_out = (bf16_t*)h;
                     h_ready = true;
                 }
-                fa.xres = m->x; fa.out = (bf16_t*)copy; fa.ldo = D; fa.partial = m->mlp_partial;
+                fa.xres = ws.x; fa.out = (bf16_t*)copy; fa.ldo = D; fa.partial = ws.mlp_partial;
                 if (m->fused_proj) { fa.ao = (const bf16_t*)ao; fa.bproj = w.proj_b; fa.nproj = D / 32; }
                 const bool skip_next = m->fused_skip && bi >= m->half_depth && bi + 1 < nb;   // the next block starts with skip_linear
                 if (skip_next) {
                     const BlockW& wn = m->blocks[bi + 1];
                     const int oi = bi - m->half_depth;                                // index of the NEXT block among the out-blocks
-                    fa.skip = (const bf16_t*)m->skips[m->half_depth - 1 - oi];      // LIFO (uvit.py:374-375)
-                    if (ee) fa.y_tap = m->ytap;                                       // the next block's head / probe read y, which this launch consumes
+                    fa.skip = (const bf16_t*)ws.skips[m->half_depth - 1 - oi];      // LIFO (uvit.py:374-375)
+                    if (ee) fa.y_tap = ws.ytap;                                       // the next block's head / probe read y, which this launch consumes
                     fa.bskip = wn.skip_b; fa.nskip = D / 16;
                     fa.ln_out_g = wn.ln1_g; fa.ln_out_b = wn.ln1_b; fa.ln_out = (bf16_t*)h;
                     h_ready = true; skip_done = true;
@@ -730,11 +729,11 @@ int run_backbone(dd_model* m, const float* x_img, const float* t_vec, const int6
                 const bool h_next = bi + 1 < nb && (bi < m->half_depth || skip_next);
                 const bool qa_next = m->fused_qa && h_next;
                 const bool qkv_next = !qa_next && m->fused_qkv && h_next;
-                if (qa_next) fa.ln_out_frag = m->hfrag;      // the patch rows' norm1 in the order the attention launch loads it
+                if (qa_next) fa.ln_out_frag = ws.hfrag;      // the patch rows' norm1 in the order the attention launch loads it
                 if (qkv_next) {
                     const BlockW& wn = m->blocks[bi + 1];
                     fa.ln_out_g = wn.ln1_g; fa.ln_out_b = wn.ln1_b; fa.ln_out = (bf16_t*)h;   // (written for the extra-token rows only)
-                    fa.qkv_out = (bf16_t*)qkv; fa.qkv_dump = m->qkv_dump; fa.hm = make_head_major(L, m->H); fa.nqkv = 3 * D / 32;
+                    fa.qkv_out = (bf16_t*)qkv; fa.qkv_dump = ws.qkv_dump; fa.hm = make_head_major(L, m->H); fa.nqkv = 3 * D / 32;
                     h_ready = true; qkv_done = true;
                 }
                 mlp_fused_plan(B, m->N, m->extras, L, m->hidden, fa);
@@ -768,7 +767,7 @@ int run_backbone(dd_model* m, const float* x_img, const float* t_vec, const int6
             GemmArgs<T> g{h, nullptr, (const T*)w.fc1_w, w.fc1_b, nullptr, hid, M, m->hidden, D, D, D, 0, m->hid_ld};
             g.tile128 = tile128(m->hidden, D, D);
             if (int rc = mark(DD_PROF_FC1)) return rc;
-            DD_HIP(c, launch_gemm<T>(g, EPI_BIAS_GELU, s, c->num_cus));
+            DD_HIP(c, launch_gemm<T>(g, EPI_BIAS_GELU, s, ch.cus));
             if (int rc = mark(DD_PROF_FC1)) return rc;
         }
         if constexpr (sizeof(T) == 2) {
@@ -776,19 +775,19 @@ int run_backbone(dd_model* m, const float* x_img, const float* t_vec, const int6
                 // x += fc2(hid) + b with each wave's 32 residual rows resident in registers; where the next block starts with norm1 (in- and
                 // mid-blocks) that LayerNorm leaves from the same registers -- in the attention launch's fragment order under fused_qa
                 RowLinArgs ra{};
-                ra.A = (const bf16_t*)hid; ra.lda = m->hid_ld; ra.K = m->hidden; ra.wimg = w.rl_img; ra.bias = w.fc2_b; ra.xres = m->x;
-                ra.x_copy = (bf16_t*)copy; ra.partial = m->mlp_partial;
+                ra.A = (const bf16_t*)hid; ra.lda = m->hid_ld; ra.K = m->hidden; ra.wimg = w.rl_img; ra.bias = w.fc2_b; ra.xres = ws.x;
+                ra.x_copy = (bf16_t*)copy; ra.partial = ws.mlp_partial;
                 const bool ln_next = bi + 1 < nb && bi + 1 <= m->half_depth;
                 if (ln_next) {
                     ra.ln_g = m->blocks[bi + 1].ln1_g; ra.ln_b = m->blocks[bi + 1].ln1_b;
-                    if (m->fused_qa) ra.h_frag = m->hfrag; else ra.h_out = (bf16_t*)h;
+                    if (m->fused_qa) ra.h_frag = ws.hfrag; else ra.h_out = (bf16_t*)h;
                 }
                 rowlin_plan(B, m->N, m->extras, L, m->hidden, ra);
                 if (int rc = mark(DD_PROF_ROWLIN)) return rc;
                 DD_HIP(c, launch_rowlin(ra, s));
                 if (int rc = mark(DD_PROF_ROWLIN)) return rc;
                 MlpFusedArgs fr{};           // the extra-token rows: bias + residual + the K-split slabs in a fixed order (+ their norm1 rows)
-                fr.b2 = w.fc2_b; fr.xres = m->x; fr.out = (bf16_t*)copy; fr.ldo = D; fr.partial = m->mlp_partial;
+                fr.b2 = w.fc2_b; fr.xres = ws.x; fr.out = (bf16_t*)copy; fr.ldo = D; fr.partial = ws.mlp_partial;
                 fr.tok_n = ra.tok_n; fr.tok_e = ra.tok_e; fr.tok_l = ra.tok_l; fr.n_extra = ra.n_extra; fr.tiles_left = ra.tiles_extra;
                 fr.groups = ra.groups; fr.prows = 128;
                 if (ln_next && !m->fused_qa) { fr.ln_out_g = ra.ln_g; fr.ln_out_b = ra.ln_b; fr.ln_out = (bf16_t*)h; }
@@ -801,14 +800,14 @@ int run_backbone(dd_model* m, const float* x_img, const float* t_vec, const int6
         if constexpr (sizeof(T) == 2) {
             if (m->splitk) {     // mlp.fc2 as split-K halves; x += bias + slabs, the bf16 copy and (in- / mid-blocks) the next block's norm1 in the row pass
                 GemmArgs<T> g{hid, nullptr, (const T*)w.fc2_w, nullptr, nullptr, nullptr, M, D, m->hidden, m->hidden, m->hid_ld, m->hid_ld, D};
-                g.partial = m->mlp_partial; g.splits = 2;
+                g.partial = ws.mlp_partial; g.splits = 2;
                 if (int rc = mark(DD_PROF_SPLITK)) return rc;
-                DD_HIP(c, launch_gemm_splitk(g, s, c->num_cus));
+                DD_HIP(c, launch_gemm_splitk(g, s, ch.cus));
                 if (int rc = mark(DD_PROF_SPLITK)) return rc;
                 const bool ln_next = bi + 1 < nb && bi + 1 <= m->half_depth;
-                ReduceLnArgs ra{m->x, m->mlp_partial, (long long)M * D, 2, 1, w.fc2_b, (bf16_t*)copy, D,
+                ReduceLnArgs ra{ws.x, ws.mlp_partial, (long long)M * D, 2, 1, w.fc2_b, (bf16_t*)copy, D,
                                 ln_next ? m->blocks[bi + 1].ln1_g : nullptr, ln_next ? m->blocks[bi + 1].ln1_b : nullptr, (bf16_t*)h,
-                                ln_next && m->fused_qa ? m->hfrag : nullptr, L, m->extras, M};
+                                ln_next && m->fused_qa ? ws.hfrag : nullptr, L, m->extras, M};
                 DD_HIP(c, launch_reduce_ln(ra, D, s));
                 h_ready = ln_next;
                 qa_ready = ln_next && m->fused_qa;
@@ -816,15 +815,15 @@ int run_backbone(dd_model* m, const float* x_img, const float* t_vec, const int6
             }
         }
         {
-            GemmArgs<T> g{hid, nullptr, (const T*)w.fc2_w, w.fc2_b, m->x, copy, M, D, m->hidden, m->hidden,
+            GemmArgs<T> g{hid, nullptr, (const T*)w.fc2_w, w.fc2_b, ws.x, copy, M, D, m->hidden, m->hidden,
                           m->hid_ld, m->hid_ld, D};
             g.tile128 = tile128(D, m->hidden, m->hidden);
-            DD_HIP(c, launch_gemm<T>(g, EPI_BIAS_RESID, s, c->num_cus));
+            DD_HIP(c, launch_gemm<T>(g, EPI_BIAS_RESID, s, ch.cus));
         }
     }
     if (ee_dec_all) {     // every layer's unpatchify + conv in one launch (layer i: images [i B, (i + 1) B) of nb B, its own conv weights), every MLP probe's mean in one
         const long long chw = (long long)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
-        FinalArgs fa{ee_dec_all, m->heads[0].wconv, m->heads[0].bconv, nullptr, nullptr, ee->outs, nullptr, c->st,
+        FinalArgs fa{ee_dec_all, m->heads[0].wconv, m->heads[0].bconv, nullptr, nullptr, ee->outs, nullptr, ch.st,
                      c->coef, nb * B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, DD_NOISE_NONE, 0, 0};
         fa.layer_B = B; fa.w_stride = m->ee_wconv_stride; fa.b_stride = m->ee_bconv_stride;
         DD_HIP(c, launch_final(fa, s));
@@ -835,21 +834,21 @@ int run_backbone(dd_model* m, const float* x_img, const float* t_vec, const int6
     // free here), then decoder_pred as an exact-fp32 MFMA GEMM in BOTH precision modes, so eps is
     // never rounded to bf16.  dec holds all L tokens per image; the extras are skipped downstream.
     if (m->wdec_g) {   // fused: rows read once, normalised rows never written
-        HeadDecArgs ha{m->x, m->wdec_g, m->dec_c, m->dec, M, m->pd, (L - m->extras) % 16 == 0 ? L : 0, m->extras};   // (only the patch rows)
-        DD_HIP(c, launch_head_dec(ha, D, c->num_cus, s));
+        HeadDecArgs ha{ws.x, m->wdec_g, m->dec_c, ws.dec, M, m->pd, (L - m->extras) % 16 == 0 ? L : 0, m->extras};   // (only the patch rows)
+        DD_HIP(c, launch_head_dec(ha, D, ch.cus, s));
         return DD_OK;
     }
-    float* hf = (float*)m->hid;
-    DD_HIP(c, launch_layernorm<float>(m->x, m->norm_g, m->norm_b, hf, M, D, s));
-    GemmArgs<float> g{hf, nullptr, m->wdec, m->bdec, m->dec, nullptr, M, m->pd, D, D, D, 0, m->pd};
-    DD_HIP(c, launch_gemm<float>(g, EPI_BIAS_SET, s, c->num_cus));
+    float* hf = (float*)ws.hid;
+    DD_HIP(c, launch_layernorm<float>(ws.x, m->norm_g, m->norm_b, hf, M, D, s));
+    GemmArgs<float> g{hf, nullptr, m->wdec, m->bdec, ws.dec, nullptr, M, m->pd, D, D, D, 0, m->pd};
+    DD_HIP(c, launch_gemm<float>(g, EPI_BIAS_SET, s, ch.cus));
     return DD_OK;
 }
 
-int run_model(dd_model* m, const float* x_img, const float* t_vec, const int64_t* y_dev, int B, hipStream_t s,
+int run_model(dd_model* m, const Chain& ch, const float* x_img, const float* t_vec, const int64_t* y_dev, int B, hipStream_t s,
               const EeTaps* ee = nullptr) {
-    return m->prec == DD_PREC_BF16 ? run_backbone<bf16_t>(m, x_img, t_vec, y_dev, B, s, ee)
-                                   : run_backbone<float>(m, x_img, t_vec, y_dev, B, s, ee);
+    return m->prec == DD_PREC_BF16 ? run_backbone<bf16_t>(m, ch, x_img, t_vec, y_dev, B, s, ee)
+                                   : run_backbone<float>(m, ch, x_img, t_vec, y_dev, B, s, ee);
 }
 
 int check_call(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev) {
@@ -878,16 +877,30 @@ int check_guided(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev, const dd_g
     return check_call(c, m, 2 * B, y_dev);
 }
 
-// one sampling step enqueued on s: x <- update(x, model(x, t)) ; t comes from ctx->st
+// one sampling step of chain ch enqueued on s: x <- update(x, model(x, t)) ; t comes from ch.st
 // advance != 0: the step's last kernel also decrements the device-resident timestep (graph replays / dd_sample)
 // g != null (classifier-free guidance): B images, the backbone runs the 2 B rows [x | x] with labels [y | null] (stage_guided's layout)
-int enqueue_step(dd_ctx* c, dd_model* m, float* x_dev, const int64_t* y_dev, int noise_mode, const float* z_dev,
+int enqueue_step(dd_ctx* c, dd_model* m, const Chain& ch, float* x_dev, const int64_t* y_dev, int noise_mode, const float* z_dev,
                  int variance, float* eps_out, int B, hipStream_t s, int advance = 0, const AffineRow* atab = nullptr, int b0 = 0,
                  const dd_guidance* g = nullptr) {
-    int rc = run_model(m, x_dev, nullptr, y_dev, g ? 2 * B : B, s);
+    int rc = run_model(m, ch, x_dev, nullptr, y_dev, g ? 2 * B : B, s);
     if (rc) return rc;
-    FinalArgs fa{m->dec, m->wconv, m->bconv, x_dev, z_dev, eps_out, x_dev, c->st, c->coef,
+    FinalArgs fa{ch.ws->dec, m->wconv, m->bconv, x_dev, z_dev, eps_out, x_dev, ch.st, c->coef,
                  B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, noise_mode, variance, advance, atab, b0};
+    if (g) { fa.pair_B = B; fa.guide_scale = g->scale; }
+    DD_HIP(c, launch_final(fa, s));
+    return DD_OK;
+}
+
+// eps = model(x, t) and nothing else (dd_forward*, the early-exit step): t_set != null first puts that timestep into the chain's step
+// state; g != null: the backbone runs the 2 B rows of stage_guided's layout and the output head combines them into B guided images
+int forward_eps(dd_ctx* c, dd_model* m, const Chain& ch, const float* t_set, const float* x_dev, const float* t_vec, const int64_t* y_dev,
+                float* eps_dev, int B, hipStream_t s, const EeTaps* ee = nullptr, const dd_guidance* g = nullptr) {
+    if (t_set) DD_HIP(c, launch_set_state_float(ch.st, *t_set, s));
+    int rc = run_model(m, ch, x_dev, t_vec, y_dev, g ? 2 * B : B, s, ee);
+    if (rc) return rc;
+    FinalArgs fa{ch.ws->dec, m->wconv, m->bconv, nullptr, nullptr, eps_dev, nullptr, ch.st, c->coef,
+                 B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, DD_NOISE_NONE, 0, 0};
     if (g) { fa.pair_B = B; fa.guide_scale = g->scale; }
     DD_HIP(c, launch_final(fa, s));
     return DD_OK;
@@ -953,7 +966,7 @@ int unstage_guided(dd_ctx* c, float* x_dev, const float* x_run, int B, int B0, s
 // large batches (ImageNet-64, B = 256) with the persistent GEMM grids of both chains sized for HALF the CUs (chain_gemm_cus): a full-size
 // grid holds every CU's LDS, two of them only queue behind each other (-4.7 %), two half-size ones run side by side (+4.7 %).
 // Development flags force the split on for any even batch, or switch it off.
-bool use_chains(dd_ctx* c, dd_model* m, int B, bool early_exit_loop = false) {
+bool use_chains(dd_ctx* c, dd_model* m, int B, bool early_exit_loop) {
     if ((c->dev_flags & DD_DEV_NO_CHAINS) || (B & 1) || B < 2 || ((m->ee_type >= 0) != early_exit_loop)) return false;
     return B >= 32 || (c->dev_flags & DD_DEV_FORCE_CHAINS);
 }
@@ -967,11 +980,11 @@ int chain_gemm_cus(dd_ctx* c, dd_model* m, int B) {
 // the chain's first step ran while the memset was still sweeping the arena: the first images of the second half came out wrong on the very
 // first chained call of a model, intermittently)
 int ensure_chain_ws(dd_ctx* c, dd_model* m, hipStream_t s) {
-    if (m->wsarena2) return DD_OK;
-    m->wsoff2 = ws_layout(m, (m->cfg.max_batch + 1) / 2);     // a chain never runs more than half of max_batch
-    DD_HIP(c, hipMalloc((void**)&m->wsarena2, m->wsoff2.bytes));
-    DD_HIP(c, hipMemsetAsync(m->wsarena2, 0, m->wsoff2.bytes, s));
-    bind_ws(m->wsoff2, m->wsarena2, m->ws2);
+    if (m->wsarena[1]) return DD_OK;
+    m->wsoff[1] = ws_layout(m, (m->cfg.max_batch + 1) / 2);     // a chain never runs more than half of max_batch
+    DD_HIP(c, hipMalloc((void**)&m->wsarena[1], m->wsoff[1].bytes));
+    DD_HIP(c, hipMemsetAsync(m->wsarena[1], 0, m->wsoff[1].bytes, s));
+    bind_ws(m->wsoff[1], m->wsarena[1], m->ws[1]);
     return DD_OK;
 }
 // a failure between the fork and the join of a chained call must not leave the side stream running on the second chain's buffers behind
@@ -981,22 +994,180 @@ struct SideJoin {
     ~SideJoin() { if (armed && c->side) (void)hipStreamSynchronize(c->side); }
 };
 
-// the model's captured step of kind `which` (0 DDPM, 1 table-driven) for this key: reused, or captured now from enqueue(m)
+// the model's captured step of this kind for this chain and key: reused, or captured now from enqueue()
 template <typename F>
-int get_graph(dd_ctx* c, dd_model* m, int which, const GraphKey& key, hipStream_t s, F&& enqueue) {
-    if (m->graph[which] && m->gkey[which] == key) return DD_OK;
-    if (m->graph[which]) { (void)hipGraphExecDestroy(m->graph[which]); m->graph[which] = nullptr; }
+int get_graph(dd_ctx* c, dd_model* m, GraphKind kind, int chain, const GraphKey& key, hipStream_t s, F&& enqueue) {
+    hipGraphExec_t& exec = m->graph[kind][chain];
+    if (exec && m->gkey[kind][chain] == key) return DD_OK;
+    if (exec) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
     hipGraph_t g = nullptr;
     DD_HIP(c, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    const int r = enqueue(m);
+    const int r = enqueue();
     const hipError_t e2 = hipStreamEndCapture(s, &g);
     if (r) { if (g) (void)hipGraphDestroy(g); return r; }
     if (e2 != hipSuccess) return fail_hip(c, e2, "hipStreamEndCapture");
-    const hipError_t e3 = hipGraphInstantiate(&m->graph[which], g, nullptr, nullptr, 0);
+    const hipError_t e3 = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
-    if (e3 != hipSuccess) { m->graph[which] = nullptr; return fail_hip(c, e3, "hipGraphInstantiate"); }
-    m->gkey[which] = key;
+    if (e3 != hipSuccess) { exec = nullptr; return fail_hip(c, e3, "hipGraphInstantiate"); }
+    m->gkey[kind][chain] = key;
     ++c->graph_captures;
+    return DD_OK;
+}
+
+// One chain's share of a sampling loop's batch: the caller's images [b0, b0 + B), at x / y in the buffers the loop runs on
+struct Slice { int chain, chains; float* x; const int64_t* y; int B, b0; };
+
+// A sampling loop as run_loop drives it: the entry point has run its checks and supplies what differs between the loops
+struct Loop {
+    GraphKind kind;
+    dd_model* first;
+    dd_model* late;      // the model the loop may switch to (its graphs are captured along with first's), or null
+    int steps;
+    int switch_at;       // late runs steps [switch_at, steps), ev[1] is recorded in front of step switch_at; -1: ev[1] behind the join and the tail
+    float* x_dev;
+    const int64_t* y_dev;
+    int B;
+    const dd_guidance* g;
+    bool use_graph;
+    std::function<hipError_t(StepState*, hipStream_t)> set_state;                   // a chain's step state at the start of the loop
+    std::function<void(GraphKey&, const Slice&)> key;                                // the loop's own fields of a chain's graph key
+    std::function<int(dd_model*, const Chain&, const Slice&, hipStream_t)> step;     // one step of one chain
+    std::function<int(int chains, hipStream_t)> tail = nullptr;                      // behind the join of the chains
+};
+
+// dd_sample, dd_sample_affine (both also guided) and dd_sample_early_exit: staging, the half-batch chains, graph capture and replay, timing
+int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
+    // Two half-batch chains (graph replays only).  Images are independent and a row's path through the kernels does not depend on the
+    // batch size, so chain 0 = images [0, B0) on the caller's stream and chain 1 = images [B0, B) on the context's side stream compute
+    // bit for bit what the undivided batch computes (Philox pixel ids carry the image offset) -- with the two chains free to drift apart,
+    // so that one's HBM-bound phases (row prologues / epilogues, attention row fetch) run under the other's MFMA phases.
+    // Guided: the decisions are made on the 2 B backbone rows and the split is by image (chain 0 takes the larger half, on the workspace
+    // sized for max_batch >= 2 B rows; the second chain's workspace holds (max_batch + 1) / 2 rows >= 2 * floor(B / 2)).
+    const bool ee = L.kind == GRAPH_EARLY_EXIT;
+    const int rows = L.g ? 2 * L.B : L.B;
+    const bool chained = L.use_graph && use_chains(c, L.first, rows, ee) && (!L.late || use_chains(c, L.late, rows, ee)) && (!L.g || L.B >= 2);
+    const int chains = chained ? 2 : 1;
+    const int B0 = chained ? (L.g ? (L.B + 1) / 2 : L.B / 2) : L.B;
+    c->last_chains = chains;
+    // the captured persistent GEMM grids: halved for both chains of a large GEMM-path batch (the early-exit loop keeps the full grids)
+    const int cus = chained && !ee ? std::min(chain_gemm_cus(c, L.first, rows), L.late ? chain_gemm_cus(c, L.late, rows) : c->num_cus) : c->num_cus;
+    // the loop runs on x_run / y_run: guided, or with graphs, the context's staging buffers (copied in here, copied back at the end)
+    const size_t chw = (size_t)L.first->cfg.in_chans * L.first->cfg.img_size * L.first->cfg.img_size;
+    float* x_run = L.x_dev;
+    const int64_t* y_run = L.y_dev;
+    int rc = DD_OK;
+    if (L.g) rc = stage_guided(c, L.x_dev, L.y_dev, L.B, B0, chw, L.g->null_label, s, &x_run, &y_run);
+    else if (L.use_graph) rc = stage_inputs(c, L.x_dev, L.y_dev, L.B, (size_t)L.B * chw, s, &x_run, &y_run);
+    if (rc) return rc;
+    auto slice = [&](int k) {
+        const size_t row = k ? (L.g ? 2 * (size_t)B0 : (size_t)B0) : 0;     // the chain's first row in x_run / y_run
+        return Slice{k, chains, x_run + row * chw, y_run ? y_run + row : nullptr, k ? L.B - B0 : B0, k ? B0 : 0};
+    };
+    auto chain = [&](dd_model* m, int k) { return Chain{&m->ws[k], c->st[k], cus, !chained}; };
+    if (L.use_graph) {
+        for (int k = 0; k < chains; ++k) {
+            const Slice sl = slice(k);
+            GraphKey key{sl.x, sl.y, sl.B, 0, 0, cus, nullptr};
+            key.b0 = sl.b0;
+            key.guide(L.g);
+            L.key(key, sl);
+            for (dd_model* m : {L.first, L.late}) {
+                if (!m) continue;
+                if (k && (rc = ensure_chain_ws(c, m, s))) return rc;
+                if ((rc = get_graph(c, m, L.kind, k, key, s, [&] { return L.step(m, chain(m, k), sl, s); }))) return rc;
+            }
+        }
+    }
+    for (int k = 0; k < chains; ++k) DD_HIP(c, L.set_state(c->st[k], s));
+    if (chained) {
+        DD_HIP(c, hipEventRecord(c->ev_fork, s));                 // the side stream starts behind the staging copies and the state
+        DD_HIP(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
+    }
+    SideJoin side_join{c, chained};
+    DD_HIP(c, hipEventRecord(c->ev[0], s));
+    dd_model* cur = L.first;
+    for (int k = 0; k < L.steps; ++k) {
+        if (k == L.switch_at) {
+            cur = L.late;
+            DD_HIP(c, hipEventRecord(c->ev[1], s));
+        }
+        if (L.use_graph) {
+            DD_HIP(c, hipGraphLaunch(cur->graph[L.kind][0], s));
+            if (chained) DD_HIP(c, hipGraphLaunch(cur->graph[L.kind][1], c->side));
+        } else if ((rc = L.step(cur, chain(cur, 0), slice(0), s))) {
+            return rc;
+        }
+    }
+    if (L.switch_at == L.steps) DD_HIP(c, hipEventRecord(c->ev[1], s));
+    if (chained) {
+        DD_HIP(c, hipEventRecord(c->ev_join, c->side));
+        DD_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0));
+        side_join.armed = false;
+    }
+    if (L.tail && (rc = L.tail(chains, s))) return rc;
+    if (L.switch_at < 0) DD_HIP(c, hipEventRecord(c->ev[1], s));
+    DD_HIP(c, hipEventRecord(c->ev[2], s));
+    if (L.g) return unstage_guided(c, L.x_dev, x_run, L.B, B0, chw, s);
+    if (x_run != L.x_dev) DD_HIP(c, hipMemcpyAsync(L.x_dev, x_run, (size_t)L.B * chw * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return DD_OK;
+}
+
+// dd_sample_early_exit's scratch for B images: eps | cls | outs.  Linear in B: chain 1's block starts behind chain 0's B0 images.
+size_t ee_scratch_elems(const dd_model* m, int B) {
+    const size_t chw = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
+    return (size_t)B * ((1 + m->cfg.depth) * chw + m->cfg.depth);
+}
+
+// dd_profile_steps (chains == 1) and dd_profile_steps_chained (chains == 2: dd_sample's two half-batch chains enqueued eagerly on `stream`
+// and on the context's side stream, step by step -- the launches overlap the other chain's kernels exactly as the graph replays of the
+// timed loop do): an event pair around every launch of the selected kind in every chain; out: the average ms of one such launch
+int profile_steps(dd_ctx* c, dd_model* m, float* x_dev, const int64_t* y_dev, int t_start, int steps, int B, int chains, void* stream,
+                  float* ms_out, int* launches_out) {
+    int rc = check_call(c, m, B, y_dev);
+    if (rc) return rc;
+    const bool chained = chains == 2;
+    if (!x_dev || !ms_out || steps < 1 || t_start > 999 || t_start - steps + 1 < 0 || (chained && ((B & 1) || B < 2)))
+        return fail(c, DD_ERR_INVALID, "bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    const hipStream_t cs[2] = {s, c->side};
+    if (chained && (rc = ensure_chain_ws(c, m, s))) return rc;
+    const int B0 = B / chains;
+    const size_t chw = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
+    const int cus = chained ? chain_gemm_cus(c, m, B) : c->num_cus;     // (both chains' persistent GEMM grids sized as dd_sample sizes them)
+    if (chained) {
+        DD_HIP(c, hipEventRecord(c->ev_fork, s));
+        DD_HIP(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
+    }
+    SideJoin side_join{c, chained};
+    m->time_fc1 = true;
+    m->fc1_used = 0;
+    for (int i = 0; i < steps && !rc; ++i) {
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < chains && e == hipSuccess; ++k) e = launch_set_state(c->st[k], t_start - i, 12345ull, cs[k]);
+        if (e != hipSuccess) { m->time_fc1 = false; return fail_hip(c, e, "set_state"); }
+        for (int k = 0; k < chains && !rc; ++k) {
+            const int b0 = k ? B0 : 0;
+            rc = enqueue_step(c, m, Chain{&m->ws[k], c->st[k], cus, !chained}, x_dev + (size_t)b0 * chw, y_dev ? y_dev + b0 : nullptr,
+                              DD_NOISE_PHILOX, nullptr, DD_VAR_BETA_TILDE, nullptr, k ? B - B0 : B0, cs[k], 0, nullptr, b0);
+        }
+    }
+    m->time_fc1 = false;
+    if (rc) return rc;
+    if (chained) {
+        DD_HIP(c, hipEventRecord(c->ev_join, c->side));
+        DD_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0));
+        side_join.armed = false;
+    }
+    DD_HIP(c, hipStreamSynchronize(s));
+    double total = 0.0;
+    for (size_t i = 0; i + 1 < m->fc1_used; i += 2) {
+        float ms = 0.f;
+        DD_HIP(c, hipEventElapsedTime(&ms, m->fc1_events[i], m->fc1_events[i + 1]));
+        total += ms;
+    }
+    const int n = (int)(m->fc1_used / 2);
+    *ms_out = n ? (float)(total / n) : 0.f;
+    if (launches_out) *launches_out = n;
     return DD_OK;
 }
 
@@ -1060,13 +1231,12 @@ int dd_ctx_create(int device, dd_ctx** out) {
     if (!c) return DD_ERR_NOMEM;
     c->device = device;
     c->num_cus = device_num_cus();
-    c->base_cus = c->num_cus;
     const Schedule& s = schedule();
     for (int i = 0; i < 1000; ++i) c->coef_host[i] = StepCoef{s.c1[i], s.c2[i], s.sigma[i], s.sigma_beta[i]};
-    bool ok = hipMalloc(&c->st, sizeof(StepState)) == hipSuccess && hipMalloc(&c->coef, sizeof(StepCoef) * 1000) == hipSuccess &&
+    bool ok = hipMalloc(&c->st[0], sizeof(StepState)) == hipSuccess && hipMalloc(&c->coef, sizeof(StepCoef) * 1000) == hipSuccess &&
               hipMemcpy(c->coef, c->coef_host, sizeof(StepCoef) * 1000, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemset(c->st, 0, sizeof(StepState)) == hipSuccess && hipMalloc(&c->st2, sizeof(StepState)) == hipSuccess &&
-              hipMemset(c->st2, 0, sizeof(StepState)) == hipSuccess &&
+              hipMemset(c->st[0], 0, sizeof(StepState)) == hipSuccess && hipMalloc(&c->st[1], sizeof(StepState)) == hipSuccess &&
+              hipMemset(c->st[1], 0, sizeof(StepState)) == hipSuccess &&
               hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) == hipSuccess &&
               hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess &&
@@ -1089,8 +1259,7 @@ void dd_ctx_destroy(dd_ctx* c) {
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->ev_ee_fork) (void)hipEventDestroy(c->ev_ee_fork);
     if (c->ev_ee_join) (void)hipEventDestroy(c->ev_ee_join);
-    if (c->st) (void)hipFree(c->st);
-    if (c->st2) (void)hipFree(c->st2);
+    for (StepState* st : c->st) if (st) (void)hipFree(st);
     if (c->coef) (void)hipFree(c->coef);
     if (c->x_stage) (void)hipFree(c->x_stage);
     if (c->y_stage) (void)hipFree(c->y_stage);
@@ -1400,17 +1569,11 @@ int dd_model_finalize(dd_model* m, int precision) {
     m->norm_g = F(o_ng); m->norm_b = F(o_nb); m->wdec = F(o_wdec); m->bdec = F(o_bd); m->wconv = F(o_wc); m->bconv = F(o_bc);
 
     // ---- activation workspace (HBM-resident for the life of the model)
-    m->wsoff = ws_layout(m, m->cfg.max_batch);
-    DD_HIP(c, hipMalloc((void**)&m->wsarena, m->wsoff.bytes));
-    DD_HIP(c, hipMemset(m->wsarena, 0, m->wsoff.bytes));
+    m->wsoff[0] = ws_layout(m, m->cfg.max_batch);
+    DD_HIP(c, hipMalloc((void**)&m->wsarena[0], m->wsoff[0].bytes));
+    DD_HIP(c, hipMemset(m->wsarena[0], 0, m->wsoff[0].bytes));
     DD_HIP(c, hipStreamSynchronize(nullptr));    // (callers run the model on non-blocking streams, which a null-stream memset does not order itself before)
-    {
-        WsPtrs w;
-        bind_ws(m->wsoff, m->wsarena, w);
-        m->x = w.x; m->h = w.h; m->ao = w.ao; m->qkv = w.qkv; m->hid = w.hid; m->xb = w.xb; m->dec = w.dec; m->skips = w.skips;
-        m->mlp_partial = w.mlp_partial; m->qkv_dump = w.qkv_dump; m->hfrag = w.hfrag; m->ytap = w.ytap;
-    }
-    m->mlp_partial_bytes = m->wsoff.part_bytes;
+    bind_ws(m->wsoff[0], m->wsarena[0], m->ws[0]);
 
     // host copies are no longer needed
     for (auto& kv : m->params) { std::vector<float>().swap(kv.second.data); }
@@ -1421,13 +1584,12 @@ int dd_model_finalize(dd_model* m, int precision) {
 void dd_model_destroy(dd_model* m) {
     if (!m) return;
     (void)hipSetDevice(m->ctx->device);
-    for (auto g : m->graph) if (g) (void)hipGraphExecDestroy(g);
+    for (auto& kind : m->graph)
+        for (hipGraphExec_t g : kind) if (g) (void)hipGraphExecDestroy(g);
     for (hipEvent_t e : m->fc1_events) (void)hipEventDestroy(e);
     if (m->ee_ws) (void)hipFree(m->ee_ws);
-    if (m->ee_sums) (void)hipFree(m->ee_sums);
     if (m->warena) (void)hipFree(m->warena);
-    if (m->wsarena) (void)hipFree(m->wsarena);
-    if (m->wsarena2) (void)hipFree(m->wsarena2);
+    for (char* a : m->wsarena) if (a) (void)hipFree(a);
     delete m;
 }
 
@@ -1436,14 +1598,7 @@ int dd_forward(dd_ctx* c, dd_model* m, const float* x_dev, float t, const float*
     int rc = check_call(c, m, B, y_dev);
     if (rc) return rc;
     if (!x_dev || !eps_dev) return fail(c, DD_ERR_INVALID, "null tensor");
-    hipStream_t s = (hipStream_t)stream;
-    DD_HIP(c, launch_set_state_float(c->st, t, s));
-    rc = run_model(m, x_dev, t_dev, y_dev, B, s);
-    if (rc) return rc;
-    FinalArgs fa{m->dec, m->wconv, m->bconv, nullptr, nullptr, eps_dev, nullptr, c->st, c->coef,
-                 B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, DD_NOISE_NONE, 0, 0};
-    DD_HIP(c, launch_final(fa, s));
-    return DD_OK;
+    return forward_eps(c, m, whole_batch(c, m), &t, x_dev, t_dev, y_dev, eps_dev, B, (hipStream_t)stream);
 }
 
 int dd_model_enable_early_exit(dd_model* m, int classifier_type) {
@@ -1464,15 +1619,8 @@ int dd_forward_early_exit(dd_ctx* c, dd_model* m, const float* x_dev, float t, c
     if (!x_dev || !eps_dev || !classifier_dev || !outputs_dev) return fail(c, DD_ERR_INVALID, "null tensor");
     const int ti = (int)t;                                   // t = int(timesteps[0]) (early_exit.py:271)
     if (m->ee_type != DD_EE_MLP_PER_LAYER && m->ee_type != DD_EE_ATTENTION_PROBE && (ti < 0 || ti > 999)) return fail(c, DD_ERR_NOT_FOUND, "no probe for this timestep (KeyError in the reference)");
-    hipStream_t s = (hipStream_t)stream;
-    DD_HIP(c, launch_set_state_float(c->st, t, s));
     const EeTaps ee{classifier_dev, outputs_dev, ti};
-    rc = run_model(m, x_dev, t_dev, y_dev, B, s, &ee);
-    if (rc) return rc;
-    FinalArgs fa{m->dec, m->wconv, m->bconv, nullptr, nullptr, eps_dev, nullptr, c->st, c->coef,
-                 B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, DD_NOISE_NONE, 0, 0};
-    DD_HIP(c, launch_final(fa, s));
-    return DD_OK;
+    return forward_eps(c, m, whole_batch(c, m), &t, x_dev, t_dev, y_dev, eps_dev, B, (hipStream_t)stream, &ee);
 }
 
 int dd_early_exit_select(dd_ctx* c, const float* outputs_dev, const float* eps_dev, const float* classifier_dev,
@@ -1536,14 +1684,7 @@ int dd_forward_guided(dd_ctx* c, dd_model* m, const float* x_dev, float t, const
     float* x_run = nullptr;
     const int64_t* y_run = nullptr;
     if ((rc = stage_guided(c, x_dev, y_dev, B, B, chw, g->null_label, s, &x_run, &y_run))) return rc;
-    DD_HIP(c, launch_set_state_float(c->st, t, s));
-    rc = run_model(m, x_run, nullptr, y_run, 2 * B, s);
-    if (rc) return rc;
-    FinalArgs fa{m->dec, m->wconv, m->bconv, nullptr, nullptr, eps_dev, nullptr, c->st, c->coef,
-                 B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, DD_NOISE_NONE, 0, 0};
-    fa.pair_B = B; fa.guide_scale = g->scale;
-    DD_HIP(c, launch_final(fa, s));
-    return DD_OK;
+    return forward_eps(c, m, whole_batch(c, m), &t, x_run, nullptr, y_run, eps_dev, B, s, nullptr, g);
 }
 
 int dd_sample_step(dd_ctx* c, dd_model* m, float* x_dev, int t, const int64_t* y_dev, int noise_mode, const float* z_dev,
@@ -1554,8 +1695,8 @@ int dd_sample_step(dd_ctx* c, dd_model* m, float* x_dev, int t, const int64_t* y
     if (t < 0 || t > 999) return fail(c, DD_ERR_INVALID, "timestep outside [0, 999]");
     if (noise_mode == DD_NOISE_BUFFER && !z_dev && t > 0) return fail(c, DD_ERR_INVALID, "DD_NOISE_BUFFER needs z_dev");
     hipStream_t s = (hipStream_t)stream;
-    DD_HIP(c, launch_set_state(c->st, t, (unsigned long long)seed, s));
-    return enqueue_step(c, m, x_dev, y_dev, noise_mode, z_dev, variance, eps_out_dev, B, s);
+    DD_HIP(c, launch_set_state(c->st[0], t, (unsigned long long)seed, s));
+    return enqueue_step(c, m, whole_batch(c, m), x_dev, y_dev, noise_mode, z_dev, variance, eps_out_dev, B, s);
 }
 
 }  // extern "C"
@@ -1576,87 +1717,17 @@ int sample_ddpm(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* 
         const dd_config &f = a->first->cfg, &l = a->late->cfg;
         if (f.img_size != l.img_size || f.in_chans != l.in_chans) return fail(c, DD_ERR_INVALID, "first and late model disagree on image shape");
     }
-    hipStream_t s = (hipStream_t)stream;
     const bool switching = a->late && a->t_switch > 0 && a->t_switch <= 1000;
     const int t_sw = 1000 - a->t_switch;  // the late model takes over AFTER this step (sampler.py:135-136)
-
-    // the loop runs on x_run / y_run: with graphs the context's staging buffers (copied in here, copied back at the end)
-    float* x_run = a->x_dev;
-    const int64_t* y_run = a->y_dev;
-    const size_t chw = (size_t)a->first->cfg.in_chans * a->first->cfg.img_size * a->first->cfg.img_size;
-    const size_t x_elems = (size_t)a->B * chw;
-    // Two half-batch chains (graph replays only).  Images are independent and a row's path through the kernels does not depend on the
-    // batch size, so chain 0 = images [0, B/2) on the caller's stream and chain 1 = images [B/2, B) on the context's side stream
-    // compute bit for bit what the undivided batch computes (Philox pixel ids carry the image offset) -- with the two chains free
-    // to drift apart, so that one's HBM-bound phases (row prologues / epilogues, attention row fetch) run under the other's MFMA phases.
-    // Guided: the decisions are made on the 2 B backbone rows and the split is by image (chain 0 takes the larger half, on the workspace
-    // sized for max_batch >= 2 B rows; the second chain's workspace holds (max_batch + 1) / 2 rows >= 2 * floor(B / 2)).
-    const int rows = g ? 2 * a->B : a->B;
-    const bool chained = a->use_graph && use_chains(c, a->first, rows) && (!switching || use_chains(c, a->late, rows)) && (!g || a->B >= 2);
-    const int B0 = chained ? (g ? (a->B + 1) / 2 : a->B / 2) : a->B, B1 = a->B - B0;
-    const size_t xo1 = g ? 2 * (size_t)B0 : (size_t)B0;     // the second chain's first row in x_run / y_run
-    c->last_chains = chained ? 2 : 1;
-    if (g && (rc = stage_guided(c, a->x_dev, a->y_dev, a->B, B0, chw, g->null_label, s, &x_run, &y_run))) return rc;
-    if (a->use_graph) {
-        if (!g && (rc = stage_inputs(c, a->x_dev, a->y_dev, a->B, x_elems, s, &x_run, &y_run))) return rc;
-        // (the captured persistent GEMM grids are sized from c->num_cus: halved for both chains of a large GEMM-path batch)
-        struct CusGuard { dd_ctx* c; int saved; ~CusGuard() { c->num_cus = saved; } } cus_guard{c, c->num_cus};
-        if (chained) c->num_cus = std::min(chain_gemm_cus(c, a->first, rows), switching ? chain_gemm_cus(c, a->late, rows) : c->num_cus);
-        GraphKey key{x_run, y_run, B0, a->noise_mode, a->variance, c->num_cus, nullptr};
-        key.guide(g);
-        auto step = [&](dd_model* m) { return enqueue_step(c, m, x_run, y_run, a->noise_mode, nullptr, a->variance, nullptr, B0, s, 1, nullptr, 0, g); };
-        if ((rc = get_graph(c, a->first, 0, key, s, step))) return rc;
-        if (switching && (rc = get_graph(c, a->late, 0, key, s, step))) return rc;
-        if (chained) {
-            float* x1 = x_run + xo1 * chw;
-            const int64_t* y1 = y_run ? y_run + xo1 : nullptr;
-            GraphKey key1{x1, y1, B1, a->noise_mode, a->variance, c->num_cus, nullptr};
-            key1.b0 = B0;
-            key1.guide(g);
-            auto step1 = [&](dd_model* m) {     // the same launch sequence on the second chain's workspace and step state
-                swap_chain(m); std::swap(c->st, c->st2);
-                const int r = enqueue_step(c, m, x1, y1, a->noise_mode, nullptr, a->variance, nullptr, B1, s, 1, nullptr, B0, g);
-                swap_chain(m); std::swap(c->st, c->st2);
-                return r;
-            };
-            if ((rc = ensure_chain_ws(c, a->first, s)) || (rc = get_graph(c, a->first, 3, key1, s, step1))) return rc;
-            if (switching && ((rc = ensure_chain_ws(c, a->late, s)) || (rc = get_graph(c, a->late, 3, key1, s, step1)))) return rc;
-        }
-    }
-    DD_HIP(c, launch_set_state(c->st, a->t_start, (unsigned long long)a->seed, s));
-    if (chained) {
-        DD_HIP(c, launch_set_state(c->st2, a->t_start, (unsigned long long)a->seed, s));
-        DD_HIP(c, hipEventRecord(c->ev_fork, s));                 // the side stream starts behind the staging copies and the state
-        DD_HIP(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-    }
-    SideJoin side_join{c, chained};
-    DD_HIP(c, hipEventRecord(c->ev[0], s));
-    bool marked = false;
-    dd_model* cur = a->first;
-    for (int t = a->t_start; t >= a->t_end; --t) {
-        if (a->use_graph) {
-            DD_HIP(c, hipGraphLaunch(cur->graph[0], s));
-            if (chained) DD_HIP(c, hipGraphLaunch(cur->graph[3], c->side));
-        } else {
-            rc = enqueue_step(c, cur, x_run, y_run, a->noise_mode, nullptr, a->variance, nullptr, a->B, s, 1, nullptr, 0, g);
-            if (rc) return rc;
-        }
-        if (switching && t == t_sw) {
-            cur = a->late;
-            DD_HIP(c, hipEventRecord(c->ev[1], s));
-            marked = true;
-        }
-    }
-    if (chained) {
-        DD_HIP(c, hipEventRecord(c->ev_join, c->side));
-        DD_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0));
-        side_join.armed = false;
-    }
-    if (!marked) DD_HIP(c, hipEventRecord(c->ev[1], s));
-    DD_HIP(c, hipEventRecord(c->ev[2], s));
-    if (g) return unstage_guided(c, a->x_dev, x_run, a->B, B0, chw, s);
-    if (x_run != a->x_dev) DD_HIP(c, hipMemcpyAsync(a->x_dev, x_run, x_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return DD_OK;
+    const bool switch_here = switching && t_sw <= a->t_start && t_sw >= a->t_end;
+    Loop L{GRAPH_DDPM, a->first, switching ? a->late : nullptr, a->t_start - a->t_end + 1, switch_here ? a->t_start - t_sw + 1 : -1,
+           a->x_dev, a->y_dev, a->B, g, a->use_graph != 0};
+    L.set_state = [&](StepState* st, hipStream_t s) { return launch_set_state(st, a->t_start, (unsigned long long)a->seed, s); };
+    L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.variance = a->variance; };
+    L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t s) {
+        return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, a->variance, nullptr, sl.B, s, 1, nullptr, sl.b0, g);
+    };
+    return run_loop(c, L, (hipStream_t)stream);
 }
 
 // dd_sample_affine (g == nullptr) and dd_sample_affine_guided: one path
@@ -1689,77 +1760,15 @@ int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* 
     c->atab_host.assign((size_t)n + 1, AffineRow{0.f, 0.f, 0.f, 0.f, 0, 0, 0, 0});
     for (int k = 0; k < n; ++k) c->atab_host[k] = AffineRow{a->t[k], a->a[k], a->b[k], a->c[k], a->noise[k] ? 1 : 0, a->counter_base + k, 0, 0};
     DD_HIP(c, hipMemcpyAsync(c->atab, c->atab_host.data(), ((size_t)n + 1) * sizeof(AffineRow), hipMemcpyHostToDevice, s));
-
-    float* x_run = a->x_dev;
-    const int64_t* y_run = a->y_dev;
-    const size_t chw = (size_t)a->first->cfg.in_chans * a->first->cfg.img_size * a->first->cfg.img_size;
-    const size_t x_elems = (size_t)a->B * chw;
-    // two half-batch chains, as dd_sample (both read the one step table; each has its own step index and Philox image offset)
-    const int rows = g ? 2 * a->B : a->B;
-    const bool chained = a->use_graph && use_chains(c, a->first, rows) && (!switching || use_chains(c, a->late, rows)) && (!g || a->B >= 2);
-    const int B0 = chained ? (g ? (a->B + 1) / 2 : a->B / 2) : a->B, B1 = a->B - B0;
-    const size_t xo1 = g ? 2 * (size_t)B0 : (size_t)B0;
-    c->last_chains = chained ? 2 : 1;
-    if (g && (rc = stage_guided(c, a->x_dev, a->y_dev, a->B, B0, chw, g->null_label, s, &x_run, &y_run))) return rc;
-    if (a->use_graph) {
-        if (!g && (rc = stage_inputs(c, a->x_dev, a->y_dev, a->B, x_elems, s, &x_run, &y_run))) return rc;
-        struct CusGuard { dd_ctx* c; int saved; ~CusGuard() { c->num_cus = saved; } } cus_guard{c, c->num_cus};
-        if (chained) c->num_cus = std::min(chain_gemm_cus(c, a->first, rows), switching ? chain_gemm_cus(c, a->late, rows) : c->num_cus);
-        GraphKey key{x_run, y_run, B0, a->noise_mode, 0, c->num_cus, c->atab};
-        key.guide(g);
-        auto step = [&](dd_model* m) { return enqueue_step(c, m, x_run, y_run, a->noise_mode, nullptr, 0, nullptr, B0, s, 1, c->atab, 0, g); };
-        if ((rc = get_graph(c, a->first, 1, key, s, step))) return rc;
-        if (switching && (rc = get_graph(c, a->late, 1, key, s, step))) return rc;
-        if (chained) {
-            float* x1 = x_run + xo1 * chw;
-            const int64_t* y1 = y_run ? y_run + xo1 : nullptr;
-            GraphKey key1{x1, y1, B1, a->noise_mode, 0, c->num_cus, c->atab};
-            key1.b0 = B0;
-            key1.guide(g);
-            auto step1 = [&](dd_model* m) {
-                swap_chain(m); std::swap(c->st, c->st2);
-                const int r = enqueue_step(c, m, x1, y1, a->noise_mode, nullptr, 0, nullptr, B1, s, 1, c->atab, B0, g);
-                swap_chain(m); std::swap(c->st, c->st2);
-                return r;
-            };
-            if ((rc = ensure_chain_ws(c, a->first, s)) || (rc = get_graph(c, a->first, 4, key1, s, step1))) return rc;
-            if (switching && ((rc = ensure_chain_ws(c, a->late, s)) || (rc = get_graph(c, a->late, 4, key1, s, step1)))) return rc;
-        }
-    }
-    DD_HIP(c, launch_set_state_table(c->st, c->atab, (unsigned long long)a->seed, s));
-    if (chained) {
-        DD_HIP(c, launch_set_state_table(c->st2, c->atab, (unsigned long long)a->seed, s));
-        DD_HIP(c, hipEventRecord(c->ev_fork, s));
-        DD_HIP(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-    }
-    SideJoin side_join{c, chained};
-    DD_HIP(c, hipEventRecord(c->ev[0], s));
-    bool marked = false;
-    dd_model* cur = a->first;
-    for (int k = 0; k < n; ++k) {
-        if (switching && k == a->switch_after) {
-            cur = a->late;
-            DD_HIP(c, hipEventRecord(c->ev[1], s));
-            marked = true;
-        }
-        if (a->use_graph) {
-            DD_HIP(c, hipGraphLaunch(cur->graph[1], s));
-            if (chained) DD_HIP(c, hipGraphLaunch(cur->graph[4], c->side));
-        } else {
-            rc = enqueue_step(c, cur, x_run, y_run, a->noise_mode, nullptr, 0, nullptr, a->B, s, 1, c->atab, 0, g);
-            if (rc) return rc;
-        }
-    }
-    if (chained) {
-        DD_HIP(c, hipEventRecord(c->ev_join, c->side));
-        DD_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0));
-        side_join.armed = false;
-    }
-    if (!marked) DD_HIP(c, hipEventRecord(c->ev[1], s));
-    DD_HIP(c, hipEventRecord(c->ev[2], s));
-    if (g) return unstage_guided(c, a->x_dev, x_run, a->B, B0, chw, s);
-    if (x_run != a->x_dev) DD_HIP(c, hipMemcpyAsync(a->x_dev, x_run, x_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return DD_OK;
+    // (two half-batch chains, as dd_sample: both read the one step table; each has its own step index and Philox image offset)
+    Loop L{GRAPH_AFFINE, a->first, switching ? a->late : nullptr, n, switching ? a->switch_after : -1, a->x_dev, a->y_dev, a->B, g,
+           a->use_graph != 0};
+    L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_table(st, c->atab, (unsigned long long)a->seed, ss); };
+    L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.atab = c->atab; };
+    L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
+        return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, 0, nullptr, sl.B, ss, 1, c->atab, sl.b0, g);
+    };
+    return run_loop(c, L, s);
 }
 }  // namespace
 
@@ -1778,26 +1787,20 @@ int dd_sample_affine_guided(dd_ctx* c, const dd_affine_sample_args* a, const dd_
 
 // One early-exit sampling step on the device (reference eesampler.py:56-81): EarlyExitUViT.forward with every head and
 // probe -> per-sample exit selection -> DDPM update with the selected output; rows t of the two log tables are written.
-// ws: the chain's scratch block (eps | model_output | cls | outs for B images); b0 / B_all: the chain's first image within the whole batch and
-// the whole batch (idx_tab rows are B_all wide); sums: err_tab is the chain's table of per-layer SUMS (launch_ee_mean_combine joins the chains)
-static int enqueue_ee_step(dd_ctx* c, dd_model* m, float* ws, float* x, const int64_t* y, float thr, float* err_tab, int32_t* idx_tab,
-                           int noise_mode, int B, hipStream_t s, int b0 = 0, int B_all = 0, bool sums = false) {
+// ws: the chain's scratch block (eps | cls | outs for B images, ee_scratch_elems); b0 / B_all: the chain's first image within the whole batch
+// and the whole batch (idx_tab rows are B_all wide); sums: err_tab is the chain's table of per-layer SUMS (launch_ee_mean_combine joins the chains)
+static int enqueue_ee_step(dd_ctx* c, dd_model* m, const Chain& ch, float* ws, float* x, const int64_t* y, float thr, float* err_tab,
+                           int32_t* idx_tab, int noise_mode, int B, hipStream_t s, int b0, int B_all, bool sums) {
     const long long chw = (long long)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
     const int depth = m->cfg.depth;
     float* eps = ws;
-    float* mo = eps + (size_t)B * chw;
-    float* cls = mo + (size_t)B * chw;
+    float* cls = eps + (size_t)B * chw;
     float* outs = cls + (size_t)depth * B;
     const EeTaps ee{cls, outs, 0};
-    int rc = run_model(m, x, nullptr, y, B, s, &ee);
-    if (rc) return rc;
-    FinalArgs fa{m->dec, m->wconv, m->bconv, nullptr, nullptr, eps, nullptr, c->st, c->coef,
-                 B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, DD_NOISE_NONE, 0, 0};
-    DD_HIP(c, launch_final(fa, s));
+    if (int rc = forward_eps(c, m, ch, nullptr, x, nullptr, y, eps, B, s, &ee)) return rc;
     // exit layer per image, the selected output and the DDPM update in one launch (dd_early_exit_select + the step kernel, fused: same arithmetic)
-    DD_HIP(c, launch_ee_select_step(x, outs, eps, cls, thr, depth, idx_tab, err_tab, B_all > 0 ? B_all : B, b0, sums, c->st, c->coef, B,
+    DD_HIP(c, launch_ee_select_step(x, outs, eps, cls, thr, depth, idx_tab, err_tab, B_all, b0, sums, ch.st, c->coef, B,
                                     m->cfg.in_chans, m->cfg.img_size, noise_mode, 1, s));
-    (void)mo;
     return DD_OK;
 }
 
@@ -1811,80 +1814,29 @@ int dd_sample_early_exit(dd_ctx* c, const dd_ee_sample_args* a, void* stream) {
     if (a->t_start > 999 || a->t_end < 0 || a->t_end > a->t_start) return fail(c, DD_ERR_INVALID, "need 999 >= t_start >= t_end >= 0");
     if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE)
         return fail(c, DD_ERR_INVALID, "dd_sample_early_exit generates noise on the device; for host noise drive dd_forward_early_exit");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t chw = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
-    const size_t need = (size_t)m->cfg.max_batch * ((2 + m->cfg.depth) * chw + m->cfg.depth);
-    if (m->ee_ws_elems < need) {
-        if (m->ee_ws) (void)hipFree(m->ee_ws);
-        m->ee_ws = nullptr; m->ee_ws_elems = 0;
-        DD_HIP(c, hipMalloc((void**)&m->ee_ws, need * sizeof(float)));
-        m->ee_ws_elems = need;
-    }
-    float* x_run = a->x_dev;
-    const int64_t* y_run = a->y_dev;
     // Two half-batch chains, as dd_sample: the samples are independent (every exit decision is per sample); the one quantity over the whole
     // batch -- the logged per-layer mean of the predicted errors, eesampler.py:70 -- becomes per-chain sums that one small launch joins
-    // behind the loop, (chain 0 + chain 1) / B.  Heads and probes stay on each chain's own stream.
-    const bool chained = a->use_graph && use_chains(c, m, a->B, true);
-    const int B0 = chained ? a->B / 2 : a->B, B1 = a->B - B0;
-    c->last_chains = chained ? 2 : 1;
-    float* ws1 = m->ee_ws + (size_t)B0 * ((2 + m->cfg.depth) * chw + m->cfg.depth);     // (the block's size is linear in the batch: two halves fit)
-    float *sum0 = nullptr, *sum1 = nullptr;
-    if (chained && a->err_dev) {
-        if (!m->ee_sums) DD_HIP(c, hipMalloc((void**)&m->ee_sums, (size_t)2 * 1000 * m->cfg.depth * sizeof(float)));
-        sum0 = m->ee_sums; sum1 = m->ee_sums + (size_t)1000 * m->cfg.depth;
-    }
-    struct InlineGuard { dd_ctx* c; bool saved; ~InlineGuard() { c->ee_inline = saved; } } inline_guard{c, c->ee_inline};
-    c->ee_inline = chained;      // (measured: the 13 forks as parallel branches of each chain's graph cost +0.9 ms per step -- 5.22 against 4.23 ms; profiles/r05/ab_round5.txt)
-    if (a->use_graph) {
-        if ((rc = stage_inputs(c, a->x_dev, a->y_dev, a->B, (size_t)a->B * chw, s, &x_run, &y_run))) return rc;
-        GraphKey key{x_run, y_run, B0, a->noise_mode, 0, c->num_cus, nullptr};
-        key.aux0 = chained ? (const void*)sum0 : (const void*)a->err_dev; key.aux1 = a->idx_dev; key.thr = a->threshold; key.b0 = chained ? -1 : 0;   // (-1: chain 0 of two -- not the whole batch's graph)
-        auto step = [&](dd_model* mm) {
-            return enqueue_ee_step(c, mm, mm->ee_ws, x_run, y_run, a->threshold, chained ? sum0 : a->err_dev, a->idx_dev, a->noise_mode, B0, s, 0, a->B, chained);
-        };
-        if ((rc = get_graph(c, m, 2, key, s, step))) return rc;
-        if (chained) {
-            float* x1 = x_run + (size_t)B0 * chw;
-            const int64_t* y1 = y_run ? y_run + B0 : nullptr;
-            GraphKey key1{x1, y1, B1, a->noise_mode, 0, c->num_cus, nullptr};
-            key1.aux0 = sum1; key1.aux1 = a->idx_dev; key1.thr = a->threshold; key1.b0 = B0;
-            auto step1 = [&](dd_model* mm) {
-                swap_chain(mm); std::swap(c->st, c->st2);
-                const int r = enqueue_ee_step(c, mm, ws1, x1, y1, a->threshold, sum1, a->idx_dev, a->noise_mode, B1, s, B0, a->B, true);
-                swap_chain(mm); std::swap(c->st, c->st2);
-                return r;
-            };
-            if ((rc = ensure_chain_ws(c, m, s)) || (rc = get_graph(c, m, 5, key1, s, step1))) return rc;
-        }
-    }
-    DD_HIP(c, launch_set_state(c->st, a->t_start, (unsigned long long)a->seed, s));
-    if (chained) {
-        DD_HIP(c, launch_set_state(c->st2, a->t_start, (unsigned long long)a->seed, s));
-        DD_HIP(c, hipEventRecord(c->ev_fork, s));
-        DD_HIP(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-    }
-    SideJoin side_join{c, chained};
-    DD_HIP(c, hipEventRecord(c->ev[0], s));
-    for (int t = a->t_start; t >= a->t_end; --t) {
-        if (a->use_graph) {
-            DD_HIP(c, hipGraphLaunch(m->graph[2], s));
-            if (chained) DD_HIP(c, hipGraphLaunch(m->graph[5], c->side));
-        } else {
-            rc = enqueue_ee_step(c, m, m->ee_ws, x_run, y_run, a->threshold, a->err_dev, a->idx_dev, a->noise_mode, a->B, s);
-            if (rc) return rc;
-        }
-    }
-    if (chained) {
-        DD_HIP(c, hipEventRecord(c->ev_join, c->side));
-        DD_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0));
-        side_join.armed = false;
-        if (a->err_dev) DD_HIP(c, launch_ee_mean_combine(sum0, sum1, a->err_dev, m->cfg.depth, a->t_end, a->t_start, a->B, s));
-    }
-    DD_HIP(c, hipEventRecord(c->ev[1], s));
-    DD_HIP(c, hipEventRecord(c->ev[2], s));
-    if (x_run != a->x_dev) DD_HIP(c, hipMemcpyAsync(a->x_dev, x_run, (size_t)a->B * chw * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return DD_OK;
+    // behind the loop, (chain 0 + chain 1) / B.  Heads and probes stay on each chain's own stream (measured: the 13 forks as parallel
+    // branches of each chain's graph cost +0.9 ms per step -- 5.22 against 4.23 ms; profiles/r05/ab_round5.txt).
+    const size_t tab = (size_t)1000 * m->cfg.depth;
+    if (!m->ee_ws) DD_HIP(c, hipMalloc((void**)&m->ee_ws, (ee_scratch_elems(m, m->cfg.max_batch) + 2 * tab) * sizeof(float)));
+    float* sums = m->ee_ws + ee_scratch_elems(m, m->cfg.max_batch);
+    auto err_tab = [&](const Slice& sl) { return sl.chains == 1 || !a->err_dev ? a->err_dev : sums + sl.chain * tab; };
+    Loop L{GRAPH_EARLY_EXIT, m, nullptr, a->t_start - a->t_end + 1, -1, a->x_dev, a->y_dev, a->B, nullptr, a->use_graph != 0};
+    L.set_state = [&](StepState* st, hipStream_t s) { return launch_set_state(st, a->t_start, (unsigned long long)a->seed, s); };
+    L.key = [&](GraphKey& k, const Slice& sl) {
+        k.noise = a->noise_mode; k.aux0 = err_tab(sl); k.aux1 = a->idx_dev; k.thr = a->threshold;
+        if (sl.chains == 2 && sl.chain == 0) k.b0 = -1;     // (chain 0 of two -- not the whole batch's graph)
+    };
+    L.step = [&](dd_model* mm, const Chain& ch, const Slice& sl, hipStream_t s) {
+        return enqueue_ee_step(c, mm, ch, mm->ee_ws + ee_scratch_elems(mm, sl.b0), sl.x, sl.y, a->threshold, err_tab(sl), a->idx_dev,
+                               a->noise_mode, sl.B, s, sl.b0, a->B, sl.chains == 2);
+    };
+    L.tail = [&](int chains, hipStream_t s) -> int {
+        if (chains == 2 && a->err_dev) DD_HIP(c, launch_ee_mean_combine(sums, sums + tab, a->err_dev, m->cfg.depth, a->t_end, a->t_start, a->B, s));
+        return DD_OK;
+    };
+    return run_loop(c, L, (hipStream_t)stream);
 }
 
 long long dd_dev_graph_captures(dd_ctx* c) { return c ? c->graph_captures : -1; }
@@ -1894,8 +1846,7 @@ int dd_dev_poison_workspaces(dd_ctx* c, dd_model* m, void* stream) {
     if (!c || !m || m->ctx != c || !m->finalized) return DD_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     if (int rc = ensure_chain_ws(c, m, s)) return rc;
-    DD_HIP(c, hipMemsetAsync(m->wsarena, 0xFF, m->wsoff.bytes, s));
-    DD_HIP(c, hipMemsetAsync(m->wsarena2, 0xFF, m->wsoff2.bytes, s));
+    for (int k = 0; k < 2; ++k) DD_HIP(c, hipMemsetAsync(m->wsarena[k], 0xFF, m->wsoff[k].bytes, s));
     return DD_OK;
 }
 
@@ -1922,79 +1873,11 @@ int dd_last_sample_timing(dd_ctx* c, float out3[3]) {
 
 int dd_profile_steps(dd_ctx* c, dd_model* m, float* x_dev, const int64_t* y_dev, int t_start, int steps, int B,
                      void* stream, float* fc1_ms_out, int* launches_out) {
-    int rc = check_call(c, m, B, y_dev);
-    if (rc) return rc;
-    if (!x_dev || !fc1_ms_out || steps < 1 || t_start > 999 || t_start - steps + 1 < 0) return fail(c, DD_ERR_INVALID, "bad arguments");
-    hipStream_t s = (hipStream_t)stream;
-    m->time_fc1 = true;
-    m->fc1_used = 0;
-    for (int i = 0; i < steps && !rc; ++i) {
-        hipError_t e = launch_set_state(c->st, t_start - i, 12345ull, s);
-        if (e != hipSuccess) { m->time_fc1 = false; return fail_hip(c, e, "set_state"); }
-        rc = enqueue_step(c, m, x_dev, y_dev, DD_NOISE_PHILOX, nullptr, DD_VAR_BETA_TILDE, nullptr, B, s);
-    }
-    m->time_fc1 = false;
-    if (rc) return rc;
-    DD_HIP(c, hipStreamSynchronize(s));
-    double total = 0.0;
-    for (size_t i = 0; i + 1 < m->fc1_used; i += 2) {
-        float ms = 0.f;
-        DD_HIP(c, hipEventElapsedTime(&ms, m->fc1_events[i], m->fc1_events[i + 1]));
-        total += ms;
-    }
-    const int n = (int)(m->fc1_used / 2);
-    *fc1_ms_out = n ? (float)(total / n) : 0.f;
-    if (launches_out) *launches_out = n;
-    return DD_OK;
+    return profile_steps(c, m, x_dev, y_dev, t_start, steps, B, 1, stream, fc1_ms_out, launches_out);
 }
-
-// dd_profile_steps for the way dd_sample runs a large batch: the two half-batch chains enqueued eagerly on `stream` and on the
-// context's side stream, step by step, with an event pair around every launch of the dominant kernel in BOTH chains -- the
-// launches overlap the other chain's kernels exactly as the graph replays of the timed loop do.
 int dd_profile_steps_chained(dd_ctx* c, dd_model* m, float* x_dev, const int64_t* y_dev, int t_start, int steps, int B,
                              void* stream, float* ms_out, int* launches_out) {
-    int rc = check_call(c, m, B, y_dev);
-    if (rc) return rc;
-    if (!x_dev || !ms_out || steps < 1 || t_start > 999 || t_start - steps + 1 < 0 || (B & 1) || B < 2) return fail(c, DD_ERR_INVALID, "bad arguments");
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = ensure_chain_ws(c, m, s))) return rc;
-    const int B0 = B / 2, B1 = B - B0;
-    const size_t chw = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
-    // (the persistent GEMM grids of both chains sized as dd_sample sizes them: halved for a large GEMM-path batch)
-    struct CusGuard { dd_ctx* c; int saved; ~CusGuard() { c->num_cus = saved; } } cus_guard{c, c->num_cus};
-    c->num_cus = chain_gemm_cus(c, m, B);
-    DD_HIP(c, hipEventRecord(c->ev_fork, s));
-    DD_HIP(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-    SideJoin side_join{c, true};
-    m->time_fc1 = true;
-    m->fc1_used = 0;
-    for (int i = 0; i < steps && !rc; ++i) {
-        hipError_t e = launch_set_state(c->st, t_start - i, 12345ull, s);
-        if (e == hipSuccess) e = launch_set_state(c->st2, t_start - i, 12345ull, c->side);
-        if (e != hipSuccess) { m->time_fc1 = false; return fail_hip(c, e, "set_state"); }
-        rc = enqueue_step(c, m, x_dev, y_dev, DD_NOISE_PHILOX, nullptr, DD_VAR_BETA_TILDE, nullptr, B0, s);
-        if (rc) break;
-        swap_chain(m); std::swap(c->st, c->st2);
-        rc = enqueue_step(c, m, x_dev + (size_t)B0 * chw, y_dev ? y_dev + B0 : nullptr, DD_NOISE_PHILOX, nullptr, DD_VAR_BETA_TILDE, nullptr,
-                          B1, c->side, 0, nullptr, B0);
-        swap_chain(m); std::swap(c->st, c->st2);
-    }
-    m->time_fc1 = false;
-    if (rc) return rc;
-    DD_HIP(c, hipEventRecord(c->ev_join, c->side));
-    DD_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0));
-    side_join.armed = false;
-    DD_HIP(c, hipStreamSynchronize(s));
-    double total = 0.0;
-    for (size_t i = 0; i + 1 < m->fc1_used; i += 2) {
-        float ms = 0.f;
-        DD_HIP(c, hipEventElapsedTime(&ms, m->fc1_events[i], m->fc1_events[i + 1]));
-        total += ms;
-    }
-    const int n = (int)(m->fc1_used / 2);
-    *ms_out = n ? (float)(total / n) : 0.f;
-    if (launches_out) *launches_out = n;
-    return DD_OK;
+    return profile_steps(c, m, x_dev, y_dev, t_start, steps, B, 2, stream, ms_out, launches_out);
 }
 
 int dd_bench_gemm(dd_ctx* c, dd_model* m, int B, int iters, void* stream, float* ms_out, double* flops_out) {
@@ -2006,11 +1889,11 @@ int dd_bench_gemm(dd_ctx* c, dd_model* m, int B, int iters, void* stream, float*
     const BlockW& w = m->blocks[0];
     auto once = [&]() -> hipError_t {
         if (m->prec == DD_PREC_BF16) {
-            GemmArgs<bf16_t> g{(const bf16_t*)m->h, nullptr, (const bf16_t*)w.fc1_w, w.fc1_b, nullptr, (bf16_t*)m->hid,
+            GemmArgs<bf16_t> g{(const bf16_t*)m->ws[0].h, nullptr, (const bf16_t*)w.fc1_w, w.fc1_b, nullptr, (bf16_t*)m->ws[0].hid,
                                M, m->hidden, D, D, D, 0, m->hid_ld};
             return launch_gemm<bf16_t>(g, EPI_BIAS_GELU, s, c->num_cus);
         }
-        GemmArgs<float> g{(const float*)m->h, nullptr, (const float*)w.fc1_w, w.fc1_b, nullptr, (float*)m->hid,
+        GemmArgs<float> g{(const float*)m->ws[0].h, nullptr, (const float*)w.fc1_w, w.fc1_b, nullptr, (float*)m->ws[0].hid,
                           M, m->hidden, D, D, D, 0, m->hid_ld};
         return launch_gemm<float>(g, EPI_BIAS_GELU, s, c->num_cus);
     };
@@ -2248,7 +2131,6 @@ int dd_set_num_cus(dd_ctx* c, int n) {
     if (!c) return DD_ERR_INVALID;
     if (n < 8) return fail(c, DD_ERR_INVALID, "need at least 8 CUs");
     c->num_cus = n / 8 * 8;      // the persistent kernels deal tiles to workgroups in groups of 8 (one per XCD)
-    c->base_cus = c->num_cus;
     return DD_OK;
 }
 

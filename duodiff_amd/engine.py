@@ -275,27 +275,14 @@ def guidance_struct(guidance):
     return L.dd_guidance(float(scale), int(null_label))
 
 
-def sample_loop(ctx: Context, first: Model, late, x, *, t_switch=0, t_start=999, t_end=0, y=None, seed=0,
-                noise="philox", variance="beta_tilde", use_graph=True, stream=None, guidance=None):
-    """dd_sample: the whole DDPM loop on the device (hipGraph replay per backbone), in place on x.
-    guidance = (scale, null_label): classifier-free guidance (dd_sample_guided; labels y required, max_batch >= 2 B)."""
-    args = L.dd_sample_args()
-    args.first = first.handle
-    args.late = late.handle if late is not None else None
-    args.t_switch = int(t_switch) if t_switch and np.isfinite(t_switch) else 0
-    args.t_start, args.t_end = int(t_start), int(t_end)
-    args.variance = L.DD_VAR_BETA if variance == "beta" else L.DD_VAR_BETA_TILDE
+def _run_loop(ctx: Context, args, x, y, seed, noise, use_graph, stream, call):
+    """Fill the fields every loop's argument struct shares (x in place, y, the device noise) and run call(stream) on the caller's stream."""
     args.noise_mode = {"none": L.DD_NOISE_NONE, "philox": L.DD_NOISE_PHILOX}[noise]
     args.use_graph = int(bool(use_graph))
     args.seed = int(seed)
     args.y_dev = y.data_ptr() if y is not None else None
     args.x_dev = x.data_ptr()
     args.B = x.shape[0]
-    if guidance is None:
-        call = lambda st: ctx.lib.dd_sample(ctx.handle, C.byref(args), st)
-    else:
-        g = guidance_struct(guidance)
-        call = lambda st: ctx.lib.dd_sample_guided(ctx.handle, C.byref(args), C.byref(g), st)
     cur = stream if stream is not None else torch.cuda.current_stream(x.device)
     if use_graph and cur.cuda_stream == 0:
         # hipGraph capture is not permitted on the legacy default stream: run the loop on a private side stream, ordered
@@ -308,6 +295,24 @@ def sample_loop(ctx: Context, first: Model, late, x, *, t_switch=0, t_start=999,
     else:
         ctx.check(call(_stream_ptr(cur)))
     return x
+
+
+def sample_loop(ctx: Context, first: Model, late, x, *, t_switch=0, t_start=999, t_end=0, y=None, seed=0,
+                noise="philox", variance="beta_tilde", use_graph=True, stream=None, guidance=None):
+    """dd_sample: the whole DDPM loop on the device (hipGraph replay per backbone), in place on x.
+    guidance = (scale, null_label): classifier-free guidance (dd_sample_guided; labels y required, max_batch >= 2 B)."""
+    args = L.dd_sample_args()
+    args.first = first.handle
+    args.late = late.handle if late is not None else None
+    args.t_switch = int(t_switch) if t_switch and np.isfinite(t_switch) else 0
+    args.t_start, args.t_end = int(t_start), int(t_end)
+    args.variance = L.DD_VAR_BETA if variance == "beta" else L.DD_VAR_BETA_TILDE
+    if guidance is None:
+        call = lambda st: ctx.lib.dd_sample(ctx.handle, C.byref(args), st)
+    else:
+        g = guidance_struct(guidance)
+        call = lambda st: ctx.lib.dd_sample_guided(ctx.handle, C.byref(args), C.byref(g), st)
+    return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
 
 def sample_affine_loop(ctx: Context, first: Model, late, x, t, a, b, c, noise_flags, *, switch_after=None, y=None, seed=0,
@@ -330,28 +335,13 @@ def sample_affine_loop(ctx: Context, first: Model, late, x, t, a, b, c, noise_fl
     args.switch_after = n if (late is None or switch_after is None) else int(switch_after)
     args.t, args.a, args.b, args.c = (v.ctypes.data_as(fp) for v in (tt, aa, bb, cc))
     args.noise = nz.ctypes.data_as(ip)
-    args.noise_mode = {"none": L.DD_NOISE_NONE, "philox": L.DD_NOISE_PHILOX}[noise]
-    args.use_graph = int(bool(use_graph))
-    args.seed = int(seed)
     args.counter_base = int(counter_base)
-    args.y_dev = y.data_ptr() if y is not None else None
-    args.x_dev = x.data_ptr()
-    args.B = x.shape[0]
     if guidance is None:
         call = lambda st: ctx.lib.dd_sample_affine(ctx.handle, C.byref(args), st)
     else:
         g = guidance_struct(guidance)
         call = lambda st: ctx.lib.dd_sample_affine_guided(ctx.handle, C.byref(args), C.byref(g), st)
-    cur = stream if stream is not None else torch.cuda.current_stream(x.device)
-    if use_graph and cur.cuda_stream == 0:      # no capture on the legacy default stream (see sample_loop)
-        side = ctx.side_stream(x.device)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            ctx.check(call(_stream_ptr(side)))
-        cur.wait_stream(side)
-    else:
-        ctx.check(call(_stream_ptr(cur)))
-    return x
+    return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
 
 def sample_early_exit_loop(ctx: Context, model: Model, x, threshold, *, t_start=999, t_end=0, y=None, seed=0, noise="philox",
@@ -362,25 +352,11 @@ def sample_early_exit_loop(ctx: Context, model: Model, x, threshold, *, t_start=
     args.model = model.handle
     args.threshold = float(threshold)
     args.t_start, args.t_end = int(t_start), int(t_end)
-    args.noise_mode = {"none": L.DD_NOISE_NONE, "philox": L.DD_NOISE_PHILOX}[noise]
-    args.use_graph = int(bool(use_graph))
-    args.B = x.shape[0]
-    args.seed = int(seed)
-    args.y_dev = y.data_ptr() if y is not None else None
-    args.x_dev = x.data_ptr()
     if err is not None:
         assert err.is_cuda and err.dtype == torch.float32 and err.is_contiguous() and err.shape[0] == 1000
     if idx is not None:
         assert idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and tuple(idx.shape) == (1000, x.shape[0])
     args.err_dev = err.data_ptr() if err is not None else None
     args.idx_dev = idx.data_ptr() if idx is not None else None
-    cur = stream if stream is not None else torch.cuda.current_stream(x.device)
-    if use_graph and cur.cuda_stream == 0:      # no capture on the legacy default stream (see sample_loop)
-        side = ctx.side_stream(x.device)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            ctx.check(ctx.lib.dd_sample_early_exit(ctx.handle, C.byref(args), _stream_ptr(side)))
-        cur.wait_stream(side)
-    else:
-        ctx.check(ctx.lib.dd_sample_early_exit(ctx.handle, C.byref(args), _stream_ptr(cur)))
-    return x
+    call = lambda st: ctx.lib.dd_sample_early_exit(ctx.handle, C.byref(args), st)
+    return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)

@@ -41,6 +41,13 @@ class dd_affine_sample_args(C.Structure):
                 ("B", C.c_int32), ("counter_base", C.c_int32)]
 
 
+class dd_multistep_sample_args(C.Structure):
+    """dd_affine_sample_args' fields, then the history half of the rows and the history register (include/duodiff.h)"""
+    _fields_ = dd_affine_sample_args._fields_ + [
+        ("d", C.POINTER(C.c_float)), ("p", C.POINTER(C.c_float)), ("q", C.POINTER(C.c_float)), ("hist", C.POINTER(C.c_int32)),
+        ("h_dev", C.c_void_p)]
+
+
 class dd_guidance(C.Structure):
     """classifier-free guidance: eps = eps_c + scale * (eps_c - eps_u), the unconditional rows labelled null_label"""
     _fields_ = [("scale", C.c_float), ("null_label", C.c_int32)]
@@ -88,6 +95,10 @@ SIGNATURES = {
                                     C.c_int, C.c_void_p]),
     "dd_sample_guided": (C.c_int, [C.c_void_p, C.POINTER(dd_sample_args), C.POINTER(dd_guidance), C.c_void_p]),
     "dd_sample_affine_guided": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.POINTER(dd_guidance), C.c_void_p]),
+    "dd_multistep_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_float] * 6 +
+                          [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "dd_sample_multistep": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.c_void_p]),
+    "dd_sample_multistep_guided": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_guidance), C.c_void_p]),
     "dd_bench_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
     "dd_vae_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "dd_vae_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),

@@ -52,6 +52,12 @@ struct dd_ctx {
     AffineRow* atab = nullptr;
     size_t atab_rows = 0;
     std::vector<AffineRow> atab_host;
+    // dd_sample_multistep: the history half of the rows beside atab, and the history register the loop runs on ([B, C, S, S], staged like x)
+    HistRow* htab = nullptr;
+    size_t htab_rows = 0;
+    std::vector<HistRow> htab_host;
+    float* h_stage = nullptr;
+    size_t h_stage_elems = 0;
     int prof_kind = 0;           // dd_profile_select: which launches dd_profile_steps brackets (DD_PROF_*)
     unsigned dev_flags = 0;      // dd_dev_set_flags (include/duodiff_dev.h): kernel-variant switches of the development harness
 };
@@ -112,7 +118,7 @@ struct GraphKey {
 };
 
 // the captured step of each sampling loop: dd_model::graph[kind][chain]
-enum GraphKind { GRAPH_DDPM, GRAPH_AFFINE, GRAPH_EARLY_EXIT, GRAPH_KINDS };
+enum GraphKind { GRAPH_DDPM, GRAPH_AFFINE, GRAPH_EARLY_EXIT, GRAPH_MULTISTEP, GRAPH_KINDS };
 
 }  // namespace
 
@@ -880,14 +886,17 @@ int check_guided(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev, const dd_g
 // one sampling step of chain ch enqueued on s: x <- update(x, model(x, t)) ; t comes from ch.st
 // advance != 0: the step's last kernel also decrements the device-resident timestep (graph replays / dd_sample)
 // g != null (classifier-free guidance): B images, the backbone runs the 2 B rows [x | x] with labels [y | null] (stage_guided's layout)
+// htab != null (the multistep loop, atab set): the update adds row k's history term and writes h' to h [B, C, S, S]
 int enqueue_step(dd_ctx* c, dd_model* m, const Chain& ch, float* x_dev, const int64_t* y_dev, int noise_mode, const float* z_dev,
                  int variance, float* eps_out, int B, hipStream_t s, int advance = 0, const AffineRow* atab = nullptr, int b0 = 0,
-                 const dd_guidance* g = nullptr) {
+                 const dd_guidance* g = nullptr, const HistRow* htab = nullptr, float* h = nullptr) {
     int rc = run_model(m, ch, x_dev, nullptr, y_dev, g ? 2 * B : B, s);
     if (rc) return rc;
     FinalArgs fa{ch.ws->dec, m->wconv, m->bconv, x_dev, z_dev, eps_out, x_dev, ch.st, c->coef,
                  B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, noise_mode, variance, advance, atab, b0};
     if (g) { fa.pair_B = B; fa.guide_scale = g->scale; }
+    fa.htab = htab;
+    fa.h = h;
     DD_HIP(c, launch_final(fa, s));
     return DD_OK;
 }
@@ -1264,6 +1273,8 @@ void dd_ctx_destroy(dd_ctx* c) {
     if (c->x_stage) (void)hipFree(c->x_stage);
     if (c->y_stage) (void)hipFree(c->y_stage);
     if (c->atab) (void)hipFree(c->atab);
+    if (c->htab) (void)hipFree(c->htab);
+    if (c->h_stage) (void)hipFree(c->h_stage);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     delete c;
 }
@@ -1666,6 +1677,16 @@ int dd_affine_step(dd_ctx* c, const float* x_dev, const float* m_dev, const floa
     return DD_OK;
 }
 
+int dd_multistep_step(dd_ctx* c, const float* x_dev, const float* m_dev, const float* z_dev, float* h_dev, float a, float b, float cc,
+                      float d, float p, float q, int use_hist, float* out_dev, int64_t n, void* stream) {
+    if (!c) return DD_ERR_INVALID;
+    if (!x_dev || !m_dev || !h_dev || !out_dev || n < 0) return fail(c, DD_ERR_INVALID, "null tensor");
+    if (h_dev == x_dev || h_dev == out_dev || h_dev == m_dev) return fail(c, DD_ERR_INVALID, "h_dev must not alias x, m or out");
+    if (n == 0) return DD_OK;
+    DD_HIP(c, launch_multistep_step(x_dev, m_dev, z_dev, h_dev, out_dev, a, b, cc, d, p, q, use_hist ? 1 : 0, (long long)n, (hipStream_t)stream));
+    return DD_OK;
+}
+
 int dd_to_images(dd_ctx* c, const float* x_dev, float* images_dev, int B, int C, int S, void* stream) {
     if (!c) return DD_ERR_INVALID;
     if (!x_dev || !images_dev) return fail(c, DD_ERR_INVALID, "null tensor");
@@ -1730,26 +1751,9 @@ int sample_ddpm(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* 
     return run_loop(c, L, (hipStream_t)stream);
 }
 
-// dd_sample_affine (g == nullptr) and dd_sample_affine_guided: one path
-int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, void* stream) {
-    if (!c || !a) return DD_ERR_INVALID;
-    auto check = [&](dd_model* m) { return g ? check_guided(c, m, a->B, a->y_dev, g) : check_call(c, m, a->B, a->y_dev); };
-    int rc = check(a->first);
-    if (rc) return rc;
-    if (a->late && (rc = check(a->late))) return rc;
-    if (!a->x_dev || !a->t || !a->a || !a->b || !a->c || !a->noise) return fail(c, DD_ERR_INVALID, "null tensor / table");
-    if (a->n_steps < 1 || a->n_steps > (1 << 20)) return fail(c, DD_ERR_INVALID, "n_steps outside [1, 2^20]");
-    if (a->counter_base < 0 || a->counter_base > (1 << 20)) return fail(c, DD_ERR_INVALID, "counter_base outside [0, 2^20]");
-    if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE)
-        return fail(c, DD_ERR_INVALID, "dd_sample_affine generates noise on the device; for host noise drive dd_forward + dd_affine_step");
-    if (a->late) {
-        const dd_config &f = a->first->cfg, &l = a->late->cfg;
-        if (f.img_size != l.img_size || f.in_chans != l.in_chans) return fail(c, DD_ERR_INVALID, "first and late model disagree on image shape");
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const int n = a->n_steps;
-    const bool switching = a->late && a->switch_after >= 0 && a->switch_after < n;
-    // the table: n rows + one more whose timestep the last step hands on (never used)
+// the step table of dd_sample_affine / dd_sample_multistep on the device: n rows + one more whose timestep the last step hands on (never used)
+int upload_atab(dd_ctx* c, int n, const float* t, const float* a, const float* b, const float* cc, const int32_t* noise, int counter_base,
+                hipStream_t s) {
     if (c->atab_rows < (size_t)n + 1) {
         if (c->atab) (void)hipFree(c->atab);
         c->atab = nullptr; c->atab_rows = 0;
@@ -1758,8 +1762,39 @@ int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* 
     }
     DD_HIP(c, hipStreamSynchronize(s));            // a previous call's upload may still read the host staging copy
     c->atab_host.assign((size_t)n + 1, AffineRow{0.f, 0.f, 0.f, 0.f, 0, 0, 0, 0});
-    for (int k = 0; k < n; ++k) c->atab_host[k] = AffineRow{a->t[k], a->a[k], a->b[k], a->c[k], a->noise[k] ? 1 : 0, a->counter_base + k, 0, 0};
+    for (int k = 0; k < n; ++k) c->atab_host[k] = AffineRow{t[k], a[k], b[k], cc[k], noise[k] ? 1 : 0, counter_base + k, 0, 0};
     DD_HIP(c, hipMemcpyAsync(c->atab, c->atab_host.data(), ((size_t)n + 1) * sizeof(AffineRow), hipMemcpyHostToDevice, s));
+    return DD_OK;
+}
+
+// the checks of a table-driven loop (dd_sample_affine, dd_sample_multistep: a's fields are dd_affine_sample_args'), before anything is
+// enqueued; host_noise: the message for a host noise mode
+template <typename Args>
+int check_table_loop(dd_ctx* c, const Args* a, const dd_guidance* g, const char* host_noise) {
+    auto check = [&](dd_model* m) { return g ? check_guided(c, m, a->B, a->y_dev, g) : check_call(c, m, a->B, a->y_dev); };
+    int rc = check(a->first);
+    if (rc) return rc;
+    if (a->late && (rc = check(a->late))) return rc;
+    if (!a->x_dev || !a->t || !a->a || !a->b || !a->c || !a->noise) return fail(c, DD_ERR_INVALID, "null tensor / table");
+    if (a->n_steps < 1 || a->n_steps > (1 << 20)) return fail(c, DD_ERR_INVALID, "n_steps outside [1, 2^20]");
+    if (a->counter_base < 0 || a->counter_base > (1 << 20)) return fail(c, DD_ERR_INVALID, "counter_base outside [0, 2^20]");
+    if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE) return fail(c, DD_ERR_INVALID, host_noise);
+    if (a->late) {
+        const dd_config &f = a->first->cfg, &l = a->late->cfg;
+        if (f.img_size != l.img_size || f.in_chans != l.in_chans) return fail(c, DD_ERR_INVALID, "first and late model disagree on image shape");
+    }
+    return DD_OK;
+}
+
+// dd_sample_affine (g == nullptr) and dd_sample_affine_guided: one path
+int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, void* stream) {
+    if (!c || !a) return DD_ERR_INVALID;
+    int rc = check_table_loop(c, a, g, "dd_sample_affine generates noise on the device; for host noise drive dd_forward + dd_affine_step");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int n = a->n_steps;
+    const bool switching = a->late && a->switch_after >= 0 && a->switch_after < n;
+    if ((rc = upload_atab(c, n, a->t, a->a, a->b, a->c, a->noise, a->counter_base, s))) return rc;
     // (two half-batch chains, as dd_sample: both read the one step table; each has its own step index and Philox image offset)
     Loop L{GRAPH_AFFINE, a->first, switching ? a->late : nullptr, n, switching ? a->switch_after : -1, a->x_dev, a->y_dev, a->B, g,
            a->use_graph != 0};
@@ -1767,6 +1802,54 @@ int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* 
     L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.atab = c->atab; };
     L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
         return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, 0, nullptr, sl.B, ss, 1, c->atab, sl.b0, g);
+    };
+    return run_loop(c, L, s);
+}
+
+// dd_sample_multistep (g == nullptr) and dd_sample_multistep_guided: dd_sample_affine's loop with the history register.  h is staged
+// like x: copied into the context's h_stage before the loop, chain k's images at h_stage + o_k chw (guided too: h holds B images,
+// not 2 B), and copied back behind the join of the chains.
+int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, void* stream) {
+    if (!c || !a) return DD_ERR_INVALID;
+    for (dd_model* m : {a->first, a->late})
+        if (m && m->ee_type >= 0) return fail(c, DD_ERR_INVALID, "the multistep loop is not supported for early-exit models");
+    int rc = check_table_loop(c, a, g, "dd_sample_multistep generates noise on the device; for host noise drive dd_forward + dd_multistep_step");
+    if (rc) return rc;
+    if (!a->d || !a->p || !a->q || !a->hist) return fail(c, DD_ERR_INVALID, "null tensor / table");
+    if (!a->h_dev) return fail(c, DD_ERR_INVALID, "null h_dev: the multistep loop needs its history register");
+    hipStream_t s = (hipStream_t)stream;
+    const int n = a->n_steps;
+    const bool switching = a->late && a->switch_after >= 0 && a->switch_after < n;
+    if ((rc = upload_atab(c, n, a->t, a->a, a->b, a->c, a->noise, a->counter_base, s))) return rc;
+    if (c->htab_rows < (size_t)n + 1) {
+        if (c->htab) (void)hipFree(c->htab);
+        c->htab = nullptr; c->htab_rows = 0;
+        DD_HIP(c, hipMalloc((void**)&c->htab, ((size_t)n + 1) * sizeof(HistRow)));
+        c->htab_rows = (size_t)n + 1;
+    }
+    c->htab_host.assign((size_t)n + 1, HistRow{0.f, 0.f, 0.f, 0});     // (upload_atab synchronised s: no upload still reads it)
+    for (int k = 0; k < n; ++k) c->htab_host[k] = HistRow{a->d[k], a->p[k], a->q[k], a->hist[k] ? 1 : 0};
+    DD_HIP(c, hipMemcpyAsync(c->htab, c->htab_host.data(), ((size_t)n + 1) * sizeof(HistRow), hipMemcpyHostToDevice, s));
+    const size_t chw = (size_t)a->first->cfg.in_chans * a->first->cfg.img_size * a->first->cfg.img_size;
+    const size_t h_elems = (size_t)a->B * chw;
+    if (c->h_stage_elems < h_elems) {       // grows only: graphs keyed on the old address are re-captured once
+        if (c->h_stage) (void)hipFree(c->h_stage);
+        c->h_stage = nullptr; c->h_stage_elems = 0;
+        DD_HIP(c, hipMalloc((void**)&c->h_stage, h_elems * sizeof(float)));
+        c->h_stage_elems = h_elems;
+    }
+    DD_HIP(c, hipMemcpyAsync(c->h_stage, a->h_dev, h_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    Loop L{GRAPH_MULTISTEP, a->first, switching ? a->late : nullptr, n, switching ? a->switch_after : -1, a->x_dev, a->y_dev, a->B, g,
+           a->use_graph != 0};
+    L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_table(st, c->atab, (unsigned long long)a->seed, ss); };
+    L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.atab = c->atab; k.aux0 = c->htab; k.aux1 = c->h_stage; };
+    L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
+        return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, 0, nullptr, sl.B, ss, 1, c->atab, sl.b0, g, c->htab,
+                            c->h_stage + (size_t)sl.b0 * chw);
+    };
+    L.tail = [&](int, hipStream_t ss) -> int {
+        DD_HIP(c, hipMemcpyAsync(a->h_dev, c->h_stage, h_elems * sizeof(float), hipMemcpyDeviceToDevice, ss));
+        return DD_OK;
     };
     return run_loop(c, L, s);
 }
@@ -1783,6 +1866,11 @@ int dd_sample_affine(dd_ctx* c, const dd_affine_sample_args* a, void* stream) { 
 int dd_sample_affine_guided(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, void* stream) {
     if (c && !g) return fail(c, DD_ERR_INVALID, "null dd_guidance");
     return sample_affine(c, a, g, stream);
+}
+int dd_sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, void* stream) { return sample_multistep(c, a, nullptr, stream); }
+int dd_sample_multistep_guided(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, void* stream) {
+    if (c && !g) return fail(c, DD_ERR_INVALID, "null dd_guidance");
+    return sample_multistep(c, a, g, stream);
 }
 
 // One early-exit sampling step on the device (reference eesampler.py:56-81): EarlyExitUViT.forward with every head and

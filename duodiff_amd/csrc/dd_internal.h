@@ -52,6 +52,11 @@ struct AffineRow {
     float t_model, a, b, c;
     int noise, ctr, pad1, pad2;   // ctr: the Philox counter of this step's z (the step's index in the WHOLE loop, not in this call's table)
 };
+// dd_sample_multistep: the history part of step k's row, beside AffineRow k: x' = a x + b m [+ d h if hist] [+ c z], h' = p x + q m
+struct HistRow {
+    float d, p, q;
+    int hist;                     // 0: h does not enter the update at all (0 * NaN is NaN: the first step, a caller's uninitialised buffer)
+};
 
 enum GemmEpilogue {
     EPI_STORE = 0,        // out = T(acc)                                  (qkv)
@@ -276,6 +281,10 @@ struct FinalArgs {
     // AND x_out [b + pair_B] are written (the next step's unconditional rows then hold their input); z, eps_out: [B, C, S, S]; layer_B must be 0
     float guide_scale = 0.f;
     int pair_B = 0;
+    // multistep loop (htab != null, atab set): row k of htab adds d h to the update when its hist flag is set, and h' = p x + q m is
+    // written on every step; h [B, C, S, S] holds this launch's B images (guided: the conditional images only), x_out must be set
+    const HistRow* htab = nullptr;
+    float* h = nullptr;
 };
 hipError_t launch_final(const FinalArgs& a, hipStream_t s);
 
@@ -318,6 +327,9 @@ template <typename T> hipError_t launch_cast(const float* x, T* out, long long n
 
 hipError_t launch_affine_step(const float* x, const float* m, const float* z, float* out, float a, float b, float c,
                               long long n, hipStream_t s);
+// out = a x + b m [+ d h if use_hist] [+ c z if z], h = p x + q m (read before it is written): the multistep row, elementwise
+hipError_t launch_multistep_step(const float* x, const float* m, const float* z, float* h, float* out, float a, float b, float c, float d,
+                                 float p, float q, int use_hist, long long n, hipStream_t s);
 // AttentionProbe operands of one layer (capi.hip finalize folds them): u [D], Wv^T [D, D], bv [D], W0^T [D, D], b0 [D], w2 [D], b2 [1]
 struct AttnProbeW { const float *u, *wvt, *bv, *w0t, *b0, *w2, *b2; };
 hipError_t launch_ee_attn_probe(const float* x, const AttnProbeW& w, float* out, int B, int L, int D, hipStream_t s);

@@ -502,6 +502,8 @@ __device__ __forceinline__ f32x4 philox_normal4(unsigned long long seed, unsigne
 // One thread per pixel, all output channels; eps never goes to HBM unless asked for.
 // G (classifier-free guidance, FinalArgs::pair_B): the pixel's conv runs on the conditional decoder rows of image b and on the unconditional
 // rows of image b + pair_B, eps = eps_c + s (eps_c - eps_u) feeds the update, and x' is written to both images.
+// H (multistep loop, FinalArgs::htab): the table-driven update gains the history term of row t, x' = a x + b eps [+ d h] [+ c z], and
+// h' = p x + q eps goes back to h (image b's slot: guided, the conditional image only).  H = false compiles to the code it did before.
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ void final_conv_pixel(const FinalArgs& a, int b, int y, int x, float (&acc)[4]) {
     const int S = a.S, P = a.P, C = a.C;
@@ -528,7 +530,7 @@ __device__ __forceinline__ void final_conv_pixel(const FinalArgs& a, int b, int 
     }
 }
 
-template <bool G>
+template <bool G, bool H>
 __global__ void __launch_bounds__(256) final_kernel(const FinalArgs a) {
 #pragma clang fp contract(off)  // the update must round like the reference: mul, sub, mul, add -- no FMA
     const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -553,6 +555,8 @@ __global__ void __launch_bounds__(256) final_kernel(const FinalArgs a) {
     const int t = a.st->t_final;
     if (a.atab) {   // table-driven loop (dd_sample_affine): t is the step index
         const AffineRow row = a.atab[t];
+        HistRow hr{0.f, 0.f, 0.f, 0};
+        if constexpr (H) hr = a.htab[t];
         if (a.advance && pix == 0) { a.st->t = t + 1; a.st->t_model = a.atab[t + 1].t_model; }
         const bool nz = row.noise != 0 && a.noise_mode == 2;
         f32x4 zn = {0.f, 0.f, 0.f, 0.f};
@@ -561,7 +565,15 @@ __global__ void __launch_bounds__(256) final_kernel(const FinalArgs a) {
             const long long e = (((long long)b * C + co) * S + y) * S + x;
             const float eps = acc[co];
             if (a.eps_out) a.eps_out[e] = eps;
-            if (a.x_out) {
+            if constexpr (H) {
+                const float xv = a.x_in[e];
+                float v = row.a * xv + row.b * eps;             // multistep_step_kernel's order and roundings
+                if (hr.hist) v = v + hr.d * a.h[e];
+                if (nz) v = v + row.c * zn[co];
+                a.h[e] = hr.p * xv + hr.q * eps;
+                a.x_out[e] = v;
+                if (G) a.x_out[e + pair] = v;
+            } else if (a.x_out) {
                 float v = row.a * a.x_in[e] + row.b * eps;      // affine_step_kernel's order and roundings
                 if (nz) v = v + row.c * zn[co];
                 a.x_out[e] = v;
@@ -603,7 +615,10 @@ __global__ void __launch_bounds__(256) final_kernel(const FinalArgs a) {
 // unconditional ones of image b + pair_B (2 x 13.8 KB of LDS), gathered by one loop so that both sets of loads are in flight together -- the
 // alternative, a second gather into the one halo behind the first conv, would put a second dependent global round trip on a kernel that is
 // a chain of them; then eps = eps_c + s (eps_c - eps_u), and x' goes to images b and b + pair_B.
-template <int CT, int PT, bool G>
+// H (multistep loop, FinalArgs::htab): as in final_kernel.  The h pixels are requested with x_in, ahead of the halo gather and without
+// waiting for row t's hist flag (a load behind the step state -> row chain would hold the gather back); a step without history loads
+// them but never lets them into x', so a NaN in h (the first step, an uninitialised buffer) cannot reach the result.
+template <int CT, int PT, bool G, bool H>
 __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
 #pragma clang fp contract(off)
     // (row pitch 48 = 16 mod 32 words: the two 16-pixel rows a 32-lane group reads fall into disjoint bank halves; pitch 19 gave every tap read
@@ -626,6 +641,9 @@ __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
     const StepCoef cf = a.coef[table ? 0 : (t < 0 ? 0 : (t > 999 ? 999 : t))];
     const bool draw = table ? (row.noise != 0) : (t > 0);
     float xin[4] = {0.f, 0.f, 0.f, 0.f}, zin[4] = {0.f, 0.f, 0.f, 0.f};
+    HistRow hr{0.f, 0.f, 0.f, 0};
+    float hin[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (H) hr = a.htab[t];
     if (inside && a.x_out) {
 #pragma unroll
         for (int co = 0; co < 4; ++co) {
@@ -633,6 +651,7 @@ __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
                 const long long e = (((long long)b * C + co) * S + y) * S + x;
                 xin[co] = a.x_in[e];
                 if (draw && a.noise_mode == 1) zin[co] = a.z[e];
+                if constexpr (H) hin[co] = a.h[e];     // (not behind the row: used only where hr.hist is set)
             }
         }
     }
@@ -701,6 +720,10 @@ __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
                 float v;
                 if (table) {
                     v = row.a * xin[co] + row.b * eps;                  // affine_step_kernel's order and roundings
+                    if constexpr (H) {                                  // multistep_step_kernel's
+                        if (hr.hist) v = v + hr.d * hin[co];
+                        a.h[e] = hr.p * xin[co] + hr.q * eps;
+                    }
                     if (draw && a.noise_mode == 1) v = v + row.c * zin[co];
                     else if (draw && a.noise_mode == 2) v = v + row.c * zn[co];
                 } else {
@@ -793,6 +816,22 @@ __global__ void affine_step_kernel(const float* __restrict__ x, const float* __r
     if (i >= n) return;
     float v = a * x[i] + b * m[i];
     if (z) v = v + c * z[i];
+    out[i] = v;
+}
+
+// out = a*x + b*m [+ d*h if use_hist] [+ c*z if z], then h = p*x + q*m, each product rounded, the terms added in this order: the
+// multistep row (dd_multistep_step, DPM-Solver++), the update the multistep final kernels fuse.  h is not read when use_hist is 0;
+// x and out may alias (in place), h must alias neither.
+__global__ void multistep_step_kernel(const float* x, const float* __restrict__ m, const float* __restrict__ z, float* h, float* out,
+                                      float a, float b, float c, float d, float p, float q, int use_hist, long long n) {
+#pragma clang fp contract(off)
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float xv = x[i], mv = m[i];
+    float v = a * xv + b * mv;
+    if (use_hist) v = v + d * h[i];
+    if (z) v = v + c * z[i];
+    h[i] = p * xv + q * mv;
     out[i] = v;
 }
 
@@ -1405,27 +1444,37 @@ hipError_t launch_fill_random(T* p, long long n, unsigned seed, float scale, hip
 template hipError_t launch_fill_random<bf16_t>(bf16_t*, long long, unsigned, float, hipStream_t);
 template hipError_t launch_fill_random<float>(float*, long long, unsigned, float, hipStream_t);
 
-hipError_t launch_final(const FinalArgs& a, hipStream_t s) {
-    if (a.pair_B > 0 && (a.pair_B != a.B || a.layer_B > 0)) return hipErrorInvalidValue;
+template <bool H>
+static void launch_final_kind(const FinalArgs& a, hipStream_t s) {
     if (a.S >= 16) {
         const int tiles = (a.S + 15) / 16;
         const dim3 grid(a.B * tiles * tiles);
         if (a.pair_B > 0) {   // classifier-free guidance: a.B images, 2 a.B decoder images
-            if (a.C == 3 && a.P == 4) hipLaunchKernelGGL((final_tiled_kernel<3, 4, true>), grid, dim3(256), 0, s, a);
-            else if (a.C == 3 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<3, 2, true>), grid, dim3(256), 0, s, a);
-            else if (a.C == 4 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<4, 2, true>), grid, dim3(256), 0, s, a);   // ImageNet-256 latents
-            else hipLaunchKernelGGL((final_tiled_kernel<0, 0, true>), grid, dim3(256), 0, s, a);
-            return hipGetLastError();
+            if (a.C == 3 && a.P == 4) hipLaunchKernelGGL((final_tiled_kernel<3, 4, true, H>), grid, dim3(256), 0, s, a);
+            else if (a.C == 3 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<3, 2, true, H>), grid, dim3(256), 0, s, a);
+            else if (a.C == 4 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<4, 2, true, H>), grid, dim3(256), 0, s, a);   // ImageNet-256 latents
+            else hipLaunchKernelGGL((final_tiled_kernel<0, 0, true, H>), grid, dim3(256), 0, s, a);
+            return;
         }
-        if (a.C == 3 && a.P == 4) hipLaunchKernelGGL((final_tiled_kernel<3, 4, false>), grid, dim3(256), 0, s, a);          // CelebA-64, ImageNet-64
-        else if (a.C == 3 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<3, 2, false>), grid, dim3(256), 0, s, a);     // CIFAR-10
-        else if (a.C == 4 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<4, 2, false>), grid, dim3(256), 0, s, a);     // latent 32 x 32 x 4
-        else hipLaunchKernelGGL((final_tiled_kernel<0, 0, false>), grid, dim3(256), 0, s, a);
-        return hipGetLastError();
+        if (a.C == 3 && a.P == 4) hipLaunchKernelGGL((final_tiled_kernel<3, 4, false, H>), grid, dim3(256), 0, s, a);          // CelebA-64, ImageNet-64
+        else if (a.C == 3 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<3, 2, false, H>), grid, dim3(256), 0, s, a);     // CIFAR-10
+        else if (a.C == 4 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<4, 2, false, H>), grid, dim3(256), 0, s, a);     // latent 32 x 32 x 4
+        else hipLaunchKernelGGL((final_tiled_kernel<0, 0, false, H>), grid, dim3(256), 0, s, a);
+        return;
     }
     const long long npix = (long long)a.B * a.S * a.S;
-    if (a.pair_B > 0) hipLaunchKernelGGL(final_kernel<true>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(final_kernel<false>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, a);
+    if (a.pair_B > 0) hipLaunchKernelGGL((final_kernel<true, H>), dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((final_kernel<false, H>), dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, a);
+}
+
+hipError_t launch_final(const FinalArgs& a, hipStream_t s) {
+    if (a.pair_B > 0 && (a.pair_B != a.B || a.layer_B > 0)) return hipErrorInvalidValue;
+    if (a.htab) {         // the multistep loop: a table-driven step that writes x and h
+        if (!a.atab || !a.h || !a.x_in || !a.x_out || a.layer_B > 0) return hipErrorInvalidValue;
+        launch_final_kind<true>(a, s);
+    } else {
+        launch_final_kind<false>(a, s);
+    }
     return hipGetLastError();
 }
 
@@ -1440,6 +1489,12 @@ hipError_t launch_ddpm_step(const float* x, const float* eps, const float* z, fl
 hipError_t launch_affine_step(const float* x, const float* m, const float* z, float* out, float a, float b, float c,
                               long long n, hipStream_t s) {
     hipLaunchKernelGGL(affine_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, m, z, out, a, b, c, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_multistep_step(const float* x, const float* m, const float* z, float* h, float* out, float a, float b, float c, float d,
+                                 float p, float q, int use_hist, long long n, hipStream_t s) {
+    hipLaunchKernelGGL(multistep_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, m, z, h, out, a, b, c, d, p, q, use_hist, n);
     return hipGetLastError();
 }
 

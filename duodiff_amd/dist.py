@@ -94,6 +94,7 @@ def main(argv=None):
 
     from . import sampler
     args = sampler.get_args(argv)
+    sampler.validate_solver(args)
     rank, world, local_rank = init()
     if torch.cuda.is_available():
         torch.cuda.set_device(local_rank % torch.cuda.device_count())   # (ranks may share a GPU when rehearsed on one)
@@ -123,7 +124,7 @@ def main(argv=None):
                                    use_ddim=args.use_ddim, ddim_steps=args.ddim_steps, ddim_eta=args.ddim_eta,
                                    timesteps_save=[], y=y, autoencoder=autoencoder, late_model=late, t_switch=args.t_switch,
                                    noise=args.noise, use_graph=not args.no_graph, return_device_tensor=True,
-                                   cfg_scale=args.cfg_scale, cfg_null_label=args.cfg_null_label)
+                                   cfg_scale=args.cfg_scale, cfg_null_label=args.cfg_null_label, **sampler.solver_kwargs(args))
         return s
 
     tic = time.time()

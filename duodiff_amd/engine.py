@@ -116,6 +116,16 @@ class Context:
                                            float(c), _ptr(out), x.numel(), _stream_ptr(stream)))
         return out
 
+    def multistep_step(self, x, m, z, h, a, b, c, d, p, q, use_hist, out=None, stream=None):
+        """out = a*x + b*m [+ d*h if use_hist] [+ c*z if z is not None], then h <- p*x + q*m (dd_multistep_step): one DPM-Solver++ row,
+        h updated in place."""
+        out = torch.empty_like(x) if out is None else out
+        assert h.is_cuda and h.dtype == torch.float32 and h.is_contiguous() and h.numel() == x.numel()
+        self.check(self.lib.dd_multistep_step(self.handle, _ptr(x.contiguous()), _ptr(m.contiguous()),
+                                              _ptr(z.contiguous() if z is not None else None), _ptr(h), float(a), float(b), float(c),
+                                              float(d), float(p), float(q), int(bool(use_hist)), _ptr(out), x.numel(), _stream_ptr(stream)))
+        return out
+
     def set_num_cus(self, n):
         """CU count this context's persistent GEMM grids are sized for (CU-masked streams)."""
         self.check(self.lib.dd_set_num_cus(self.handle, int(n)))
@@ -341,6 +351,38 @@ def sample_affine_loop(ctx: Context, first: Model, late, x, t, a, b, c, noise_fl
     else:
         g = guidance_struct(guidance)
         call = lambda st: ctx.lib.dd_sample_affine_guided(ctx.handle, C.byref(args), C.byref(g), st)
+    return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
+
+
+def sample_multistep_loop(ctx: Context, first: Model, late, x, h, rows, *, switch_after=None, y=None, seed=0, counter_base=0,
+                          noise="philox", use_graph=True, stream=None, guidance=None):
+    """dd_sample_multistep: the DPM-Solver++ loop on the device, in place on x and on its history register h (same shape as x):
+    x <- a[k] x + b[k] m_k [+ d[k] h if hist[k]] [+ c[k] z if noise[k]], h <- p[k] x + q[k] m_k for k = 0 .. len(t) - 1, m_k the
+    model output at t[k].  rows: a dict with t, a, b, c, d, p, q, noise, hist (sampler.multistep_coefficients, or any slice of it).
+    The late model runs from step switch_after on; Philox counters as sample_affine_loop.  A loop cut into several calls passes h on.
+    guidance = (scale, null_label): classifier-free guidance of the model output (dd_sample_multistep_guided)."""
+    n = len(rows["t"])
+    f32 = lambda v: np.ascontiguousarray(v, np.float32)
+    i32 = lambda v: np.ascontiguousarray(v, np.int32)
+    tab = {k: f32(rows[k]) for k in "tabcdpq"}
+    tab.update(noise=i32(rows["noise"]), hist=i32(rows["hist"]))
+    assert all(v.shape == (n,) for v in tab.values())
+    assert h.is_cuda and h.dtype == torch.float32 and h.is_contiguous() and h.shape == x.shape
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    args = L.dd_multistep_sample_args()
+    args.first = first.handle
+    args.late = late.handle if late is not None else None
+    args.n_steps = n
+    args.switch_after = n if (late is None or switch_after is None) else int(switch_after)
+    args.t, args.a, args.b, args.c, args.d, args.p, args.q = (tab[k].ctypes.data_as(fp) for k in "tabcdpq")
+    args.noise, args.hist = tab["noise"].ctypes.data_as(ip), tab["hist"].ctypes.data_as(ip)
+    args.counter_base = int(counter_base)
+    args.h_dev = h.data_ptr()
+    if guidance is None:
+        call = lambda st: ctx.lib.dd_sample_multistep(ctx.handle, C.byref(args), st)
+    else:
+        g = guidance_struct(guidance)
+        call = lambda st: ctx.lib.dd_sample_multistep_guided(ctx.handle, C.byref(args), C.byref(g), st)
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
 

@@ -17,6 +17,9 @@ engine's KL-VAE decoder when the YAML carries an ``autoencoder`` block (next-1).
 Classifier-free guidance (engine option, not in the reference): ``--cfg_scale 0.4 --class_label 207`` samples a class-conditional
 model with eps = eps_c + s (eps_c - eps_u), the unconditional rows labelled ``--cfg_null_label`` (U-ViT's null class 1000), the
 combination fused into the step kernel of every loop.
+
+DPM-Solver++ (engine option, not in the reference): ``--dpm_solver ode --dpm_solver_steps 20`` samples with the second-order multistep
+solver (``sde``: its SDE variant) in 20 model evaluations; the table-driven loop with one history register per image.
 """
 import math
 import random
@@ -30,7 +33,7 @@ import torch
 
 from .config import ModelParams, load_config
 from .autoencoder import get_autoencoder
-from .engine import Context, sample_affine_loop, sample_loop, schedule_tables
+from .engine import Context, sample_affine_loop, sample_loop, sample_multistep_loop, schedule_tables
 from .uvit import UViT
 
 
@@ -105,6 +108,86 @@ def affine_coefficients(kind, t, s=None, eta=0.0):
     raise ValueError(kind)
 
 
+MULTISTEP_KINDS = ("dpmsolver++", "sde-dpmsolver++")
+
+
+def multistep_rows(kind, alphas_bar, order=2, parametrization="predict_noise", lower_order_final=True):
+    """float64 DPM-Solver++ (Lu et al., 2022) rows of the multistep update, for the steps alphas_bar[k] -> alphas_bar[k + 1]
+    (len(alphas_bar) = N + 1 values of abar along the grid; the model sees the first N):
+
+        x' = a x + b m [+ d h  if hist]  [+ c z  if noise]        h' = p x + q m
+
+    m: the model output at step k, h: the previous step's data prediction x0 = p x + q m.  kind: "dpmsolver++" (ODE, no noise)
+    or "sde-dpmsolver++" (the midpoint 2M SDE: every row here has noise = 1; multistep_coefficients drops the z of a step landing on
+    t = 0).  order 2: step 0 is first order (no history yet), and with lower_order_final the last step too (on the product grid it
+    lands on t = 0, where lambda jumps: a second-order step there extrapolates with r ~ 0.2 and overshoots).
+    Returns a dict of float64 arrays a, b, c, d, p, q and int32 arrays hist, noise."""
+    if kind not in MULTISTEP_KINDS:
+        raise ValueError(f"solver must be one of {MULTISTEP_KINDS}, not {kind!r}")
+    if order not in (1, 2):
+        raise ValueError("solver order must be 1 or 2")
+    if parametrization == "predict_previous":
+        raise ValueError("DPM-Solver++ needs a model that predicts the noise or the data (predict_noise / predict_original), "
+                         "not predict_previous")
+    if parametrization not in ("predict_noise", "predict_original"):
+        raise ValueError(parametrization)
+    ab = np.asarray(alphas_bar, np.float64)
+    n = len(ab) - 1
+    if n < 1:
+        raise ValueError("need at least one step")
+    alpha, sigma = np.sqrt(ab), np.sqrt(1.0 - ab)
+    lam = np.log(alpha) - np.log(sigma)
+    h = lam[1:] - lam[:-1]
+    rows = {k: np.zeros(n) for k in "abcdpq"}
+    rows["hist"], rows["noise"] = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    for k in range(n):
+        if parametrization == "predict_noise":
+            p, q = 1.0 / alpha[k], -sigma[k] / alpha[k]
+        else:
+            p, q = 0.0, 1.0
+        second = order == 2 and k > 0 and not (lower_order_final and k == n - 1)
+        if second:
+            r = h[k - 1] / h[k]
+            w0, w1 = 1.0 + 1.0 / (2.0 * r), -1.0 / (2.0 * r)
+        else:
+            w0, w1 = 1.0, 0.0
+        if kind == "dpmsolver++":
+            A, phi, c = sigma[k + 1] / sigma[k], alpha[k + 1] * -np.expm1(-h[k]), 0.0
+        else:
+            A, phi = sigma[k + 1] / sigma[k] * np.exp(-h[k]), alpha[k + 1] * -np.expm1(-2.0 * h[k])
+            c = sigma[k + 1] * np.sqrt(-np.expm1(-2.0 * h[k]))
+        rows["a"][k], rows["b"][k], rows["c"][k], rows["d"][k] = A + phi * w0 * p, phi * w0 * q, c, phi * w1
+        rows["p"][k], rows["q"][k] = p, q
+        rows["hist"][k] = int(w1 != 0.0)
+        rows["noise"][k] = int(kind == "sde-dpmsolver++")
+    return rows
+
+
+def multistep_grid(n_steps):
+    """The integer timestep grid of an N-evaluation DPM-Solver++ run: N + 1 points from 999 down to 0; the model sees the first N."""
+    n = int(n_steps)
+    if not 1 <= n <= 999:
+        raise ValueError(f"DPM-Solver++ steps must be in [1, 999], not {n}")
+    return np.linspace(999, 0, n + 1).round().astype(int)
+
+
+def multistep_coefficients(kind, ts, order=2, parametrization="predict_noise"):
+    """The fp32 rows of a DPM-Solver++ run over the integer grid ts (descending, N + 1 timesteps, the last one usually 0), from the
+    engine's bit-exact schedule tables: multistep_rows in float64, each coefficient rounded once.  Returns a dict of per-step arrays
+    t (float32 model timesteps t_0 .. t_{N-1}), a, b, c, d, p, q (float32), hist, noise (int32).  The SDE draws z on every step but
+    one landing on t = 0 (the reference's DDPM / DDIM convention)."""
+    ts = np.asarray(ts, np.int64)
+    if ts.ndim != 1 or len(ts) < 2 or (ts < 0).any() or (ts > 999).any() or (np.diff(ts) >= 0).any():
+        raise ValueError("ts must be a strictly decreasing grid of timesteps in [0, 999] with at least two points")
+    ab = schedule_tables()["alphas_bar"].astype(np.float64)[ts]
+    r = multistep_rows(kind, ab, order, parametrization)
+    out = {k: r[k].astype(np.float32) for k in "abcdpq"}
+    out["t"] = ts[:-1].astype(np.float32)
+    out["hist"] = r["hist"]
+    out["noise"] = (r["noise"] * (ts[1:] > 0)).astype(np.int32)
+    return out
+
+
 def _affine_post(kind, model_output, x, t, z=None):
     ctx = Context.get(x.device)
     a, b, c = affine_coefficients(kind, t)
@@ -127,7 +210,8 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
                 sample_height: int, sample_width: int, use_ddim: bool = False, ddim_steps: int = 50,
                 ddim_eta: float = 0.0, timesteps_save: List[int] = (), y=None, autoencoder=None,
                 late_model=None, t_switch=np.inf, *, noise: str = "torch_cpu", use_graph: bool = True,
-                num_steps: int = 1000, return_device_tensor: bool = False, cfg_scale=None, cfg_null_label: int = 1000):
+                num_steps: int = 1000, return_device_tensor: bool = False, cfg_scale=None, cfg_null_label: int = 1000,
+                solver=None, solver_steps: int = 20, solver_order: int = 2):
     """reference sampler.py:82-155.  Returns (samples[B,H,W,C] float32 numpy = (x+1)/2, intermediates).
 
     cfg_scale (None: the unguided loops, unchanged): classifier-free guidance of every step's model output,
@@ -138,7 +222,21 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
         in the reference's order -> identical random numbers to a CPU reference run.
     noise="device": x_T as above, z from the device Philox generator inside the graph-replayed loop.
     num_steps < 1000 runs only the first steps (t = 999 ...), for bounded benchmarks.
+
+    solver ("dpmsolver++" | "sde-dpmsolver++", engine option, not in the reference): DPM-Solver++ multistep sampling with
+        solver_steps model evaluations on the grid multistep_grid(solver_steps) and order solver_order (multistep_coefficients);
+        predict_noise or predict_original models.  Step k runs the late model iff t_k < 1000 - t_switch (the DDPM loop's rule).
+        Intermediate saves: after the step whose model timestep t has 1000 - t in timesteps_save.
     """
+    if solver is not None:
+        if use_ddim:
+            raise ValueError("DPM-Solver++ and DDIM are exclusive")
+        multistep_grid(solver_steps)                                          # range check
+        solver_param = {predict_noise_postprocessing: "predict_noise", predict_original_postprocessing: "predict_original",
+                        predict_previous_postprocessing: "predict_previous"}.get(postprocessing)
+        if solver_param is None:
+            raise ValueError("postprocessing must be one of this module's predict_*_postprocessing functions")
+        solver_rows = multistep_coefficients(solver, multistep_grid(solver_steps), solver_order, solver_param)
     device = model.device
     guidance = None if cfg_scale is None else (float(cfg_scale), int(cfg_null_label))
     if guidance is not None and y is None:
@@ -187,7 +285,41 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
                 intermediate.append(x.clone())
             k0 = k1
 
-    if use_ddim:
+    if solver is not None:
+        # DPM-Solver++: the table-driven loop with one history register per image (h, carried across the save points)
+        rows, n = solver_rows, len(solver_rows["t"])
+        switch_after = None
+        if switch_t is not None:
+            switch_after = next((k for k in range(n) if rows["t"][k] < switch_t), None)
+        save_after = [(1000 - int(t)) in saves for t in rows["t"]]
+        h = torch.zeros_like(x)
+        if noise == "device":
+            k0 = 0
+            while k0 < n:
+                k1 = next((k + 1 for k in range(k0, n) if save_after[k]), n)
+                sw = None if switch_after is None else min(max(switch_after - k0, 0), k1 - k0)
+                seg_first, seg_late = (first, late) if (sw is None or sw > 0) else (late, None)
+                sample_multistep_loop(ctx, seg_first, seg_late if sw is not None and 0 < sw < k1 - k0 else None, x, h,
+                                      {key: v[k0:k1] for key, v in rows.items()}, switch_after=sw, y=y, seed=seed, counter_base=k0,
+                                      noise="philox", use_graph=use_graph, guidance=guidance)
+                if save_after[k1 - 1]:
+                    intermediate.append(x.clone())
+                k0 = k1
+        elif noise == "torch_cpu":
+            eps = torch.empty_like(x)
+            cur = first
+            for k in range(n):
+                if k == switch_after:
+                    cur = late
+                model_output(cur, float(rows["t"][k]), eps)
+                z = draw(x.shape) if rows["noise"][k] else None
+                ctx.multistep_step(x, eps, z, h, rows["a"][k], rows["b"][k], rows["c"][k], rows["d"][k], rows["p"][k], rows["q"][k],
+                                   rows["hist"][k], out=x)
+                if save_after[k]:
+                    intermediate.append(x.clone())
+        else:
+            raise ValueError("noise must be 'torch_cpu' or 'device'")
+    elif use_ddim:
         # reference sampler.py:103-126.  U-ViT forward on the engine + one fused affine update per step.
         ts = np.linspace(0, 999, ddim_steps).astype(int)[::-1]
         pairs = [(int(t), int(s_)) for t, s_ in zip(ts[:-1], ts[1:])]
@@ -311,6 +443,27 @@ def validate_guidance(args, num_classes: int, num_classes_late=None):
             raise ValueError("--cfg_scale needs class labels: --class_id or --class_label")
 
 
+SOLVERS = {"ode": "dpmsolver++", "sde": "sde-dpmsolver++"}
+
+
+def validate_solver(args):
+    """The DPM-Solver++ options, before any GPU work: ValueError on a bad combination."""
+    if args.dpm_solver is None:
+        return
+    if args.use_ddim:
+        raise ValueError("--dpm_solver and --use_ddim are exclusive")
+    if args.parametrization == "predict_previous":
+        raise ValueError("--dpm_solver needs --parametrization predict_noise or predict_original, not predict_previous")
+    if not 1 <= args.dpm_solver_steps <= 999:
+        raise ValueError(f"--dpm_solver_steps {args.dpm_solver_steps} outside [1, 999]")
+
+
+def solver_kwargs(args):
+    """get_samples' solver arguments from the command line"""
+    return dict(solver=SOLVERS[args.dpm_solver] if args.dpm_solver is not None else None, solver_steps=args.dpm_solver_steps,
+                solver_order=args.dpm_solver_order)
+
+
 def labels_from_args(args, batch_size: int, num_classes: int):
     """y of a run: --class_label K for every image, --class_id's reference draw (quirk Q4), or None."""
     if args.class_label is not None:
@@ -379,6 +532,11 @@ def get_args(argv=None):
                         "--class_id; an image whose drawn --class_id label equals the null label is sampled unguided")
     p.add_argument("--cfg_null_label", type=int, default=1000,
                    help="(engine option) label of the unconditional rows (default 1000: U-ViT's null class)")
+    p.add_argument("--dpm_solver", choices=sorted(SOLVERS), default=None,
+                   help="(engine option) DPM-Solver++ multistep sampling: ode = DPM-Solver++(2M), sde = SDE-DPM-Solver++(2M) "
+                        "(default: the reference's loops).  Exclusive with --use_ddim; predict_noise / predict_original models")
+    p.add_argument("--dpm_solver_steps", type=int, default=20, help="(engine option) DPM-Solver++ model evaluations, 1 .. 999")
+    p.add_argument("--dpm_solver_order", type=int, choices=[1, 2], default=2, help="(engine option) DPM-Solver++ order")
     return p.parse_args(argv)
 
 
@@ -402,6 +560,7 @@ def main(argv=None):
     post = {"predict_noise": predict_noise_postprocessing, "predict_original": predict_original_postprocessing,
             "predict_previous": predict_previous_postprocessing}[args.parametrization]
 
+    validate_solver(args)
     config = load_config(args.config_path)
     config_late = load_config(args.config_path_late) if args.checkpoint_path_late else None
     validate_guidance(args, ModelParams.from_dict(config).num_classes,
@@ -426,7 +585,7 @@ def main(argv=None):
                                  use_ddim=args.use_ddim, ddim_steps=args.ddim_steps, ddim_eta=args.ddim_eta,
                                  y=y, autoencoder=autoencoder, late_model=model_late, t_switch=args.t_switch,
                                  timesteps_save=args.timesteps_save, noise=args.noise, use_graph=not args.no_graph,
-                                 cfg_scale=args.cfg_scale, cfg_null_label=args.cfg_null_label)
+                                 cfg_scale=args.cfg_scale, cfg_null_label=args.cfg_null_label, **solver_kwargs(args))
     tac = time.time()
     dump_statistics(tac - tic, out, args.batch_size)
     if args.no_png:

@@ -239,6 +239,43 @@ int dd_forward_guided(dd_ctx* ctx, dd_model* m, const float* x_dev, float t, con
 int dd_sample_guided(dd_ctx* ctx, const dd_sample_args* args, const dd_guidance* g, void* stream);
 int dd_sample_affine_guided(dd_ctx* ctx, const dd_affine_sample_args* args, const dd_guidance* g, void* stream);
 
+/* ---- multistep update (DPM-Solver++(2M), Lu et al. 2022): the affine row plus one history register per image ---------- */
+/*     out = a*x + b*m  [+ d*h  if use_hist]  [+ c*z  if z]        h = p*x + q*m     (x, m: this step's inputs)
+ * Each product rounded on its own (no FMA contraction), the terms added in exactly this order (dd_affine_step's, extended).  h is
+ * not read when use_hist is 0 (the first step, an uninitialised buffer: 0 * NaN would be NaN); it is written on every step.  x_dev and out_dev may alias;
+ * h_dev aliases neither.  m: the model output (guided, with guidance).  The host computes the rows (duodiff_amd.sampler). */
+int dd_multistep_step(dd_ctx* ctx, const float* x_dev, const float* m_dev, const float* z_dev, float* h_dev, float a, float b,
+                      float c, float d, float p, float q, int use_hist, float* out_dev, int64_t n, void* stream);
+/* The multistep loop on the device, as dd_sample_affine (same graphs-per-chain driver, Philox counters, backbone switch) with the
+ * history term fused into the step's last kernel.  h_dev [B,C,S,S] fp32 is read at the start and written back at the end, so a
+ * loop cut into several calls carries its history across the cuts.  DD_ERR_INVALID before anything is enqueued for n_steps < 1,
+ * h_dev == NULL, host noise, an early-exit model, and the guided checks (dd_sample_multistep_guided: h holds the B images). */
+typedef struct dd_multistep_sample_args {
+    dd_model* first;        /* model used from step 0                                                           */
+    dd_model* late;         /* or NULL; runs from step index switch_after on                                    */
+    int32_t n_steps;
+    int32_t switch_after;   /* >= n_steps (or late == NULL): never                                              */
+    const float* t;         /* host [n_steps]: the timestep the model sees at step k                            */
+    const float* a;         /* host [n_steps]                                                                   */
+    const float* b;         /* host [n_steps]                                                                   */
+    const float* c;         /* host [n_steps]                                                                   */
+    const int32_t* noise;   /* host [n_steps]: != 0: the c z term is added at step k                            */
+    int32_t noise_mode;     /* DD_NOISE_PHILOX or DD_NOISE_NONE                                                 */
+    int32_t use_graph;
+    uint64_t seed;
+    const int64_t* y_dev;   /* [B] or NULL                                                                      */
+    float* x_dev;           /* in / out, [B,C,S,S] fp32                                                         */
+    int32_t B;
+    int32_t counter_base;   /* as dd_affine_sample_args                                                         */
+    const float* d;         /* host [n_steps]                                                                   */
+    const float* p;         /* host [n_steps]                                                                   */
+    const float* q;         /* host [n_steps]                                                                   */
+    const int32_t* hist;    /* host [n_steps]: != 0: the d h term is added at step k (h never enters x' otherwise) */
+    float* h_dev;           /* in / out, [B,C,S,S] fp32: the history register                                  */
+} dd_multistep_sample_args;
+int dd_sample_multistep(dd_ctx* ctx, const dd_multistep_sample_args* args, void* stream);
+int dd_sample_multistep_guided(dd_ctx* ctx, const dd_multistep_sample_args* args, const dd_guidance* g, void* stream);
+
 /* The early-exit baseline's loop (reference eesampler.py:40-89) as a device-resident loop: per step EarlyExitUViT.forward
  * (all heads and probes), the per-sample exit selection with the global threshold, the DDPM update (sigma^2 = beta-tilde)
  * with the selected output; row t of err_dev [1000, depth] (batch-mean predicted error per layer, :70) and of idx_dev

@@ -325,6 +325,24 @@ def sample_loop(ctx: Context, first: Model, late, x, *, t_switch=0, t_start=999,
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
 
+def _step_table(args, first, late, rows, floats, ints, switch_after, counter_base):
+    """Fill the fields dd_sample_affine's and dd_sample_multistep's argument structs share: the models, the switch, the Philox counter
+    base and the step table, rows[k] for k in floats as float32 and in ints as int32, one value per step.  Returns the arrays, which
+    must outlive the call."""
+    tab = {k: np.ascontiguousarray(rows[k], np.float32) for k in floats}
+    tab.update((k, np.ascontiguousarray(rows[k], np.int32)) for k in ints)
+    n = len(rows["t"])
+    assert all(v.shape == (n,) for v in tab.values())
+    for k, v in tab.items():
+        setattr(args, k, v.ctypes.data_as(C.POINTER(C.c_float if v.dtype == np.float32 else C.c_int32)))
+    args.first = first.handle
+    args.late = late.handle if late is not None else None
+    args.n_steps = n
+    args.switch_after = n if (late is None or switch_after is None) else int(switch_after)
+    args.counter_base = int(counter_base)
+    return tab
+
+
 def sample_affine_loop(ctx: Context, first: Model, late, x, t, a, b, c, noise_flags, *, switch_after=None, y=None, seed=0,
                        counter_base=0, noise="philox", use_graph=True, stream=None, guidance=None):
     """dd_sample_affine: the table-driven loops (DDIM, predict_original / predict_previous) on the device, in place on x:
@@ -332,20 +350,9 @@ def sample_affine_loop(ctx: Context, first: Model, late, x, t, a, b, c, noise_fl
     Step k draws z from Philox(key = seed, counter = counter_base + k): a loop cut into several calls passes the number
     of steps already done as counter_base and draws exactly the z of the uncut loop.
     guidance = (scale, null_label): classifier-free guidance of the model output (dd_sample_affine_guided)."""
-    n = len(t)
-    f32 = lambda v: np.ascontiguousarray(v, np.float32)
-    tt, aa, bb, cc = f32(t), f32(a), f32(b), f32(c)
-    nz = np.ascontiguousarray(noise_flags, np.int32)
-    assert tt.shape == aa.shape == bb.shape == cc.shape == nz.shape == (n,)
-    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
     args = L.dd_affine_sample_args()
-    args.first = first.handle
-    args.late = late.handle if late is not None else None
-    args.n_steps = n
-    args.switch_after = n if (late is None or switch_after is None) else int(switch_after)
-    args.t, args.a, args.b, args.c = (v.ctypes.data_as(fp) for v in (tt, aa, bb, cc))
-    args.noise = nz.ctypes.data_as(ip)
-    args.counter_base = int(counter_base)
+    tab = _step_table(args, first, late, dict(t=t, a=a, b=b, c=c, noise=noise_flags), "tabc", ("noise",), switch_after,  # noqa: F841
+                      counter_base)
     if guidance is None:
         call = lambda st: ctx.lib.dd_sample_affine(ctx.handle, C.byref(args), st)
     else:
@@ -361,22 +368,9 @@ def sample_multistep_loop(ctx: Context, first: Model, late, x, h, rows, *, switc
     model output at t[k].  rows: a dict with t, a, b, c, d, p, q, noise, hist (sampler.multistep_coefficients, or any slice of it).
     The late model runs from step switch_after on; Philox counters as sample_affine_loop.  A loop cut into several calls passes h on.
     guidance = (scale, null_label): classifier-free guidance of the model output (dd_sample_multistep_guided)."""
-    n = len(rows["t"])
-    f32 = lambda v: np.ascontiguousarray(v, np.float32)
-    i32 = lambda v: np.ascontiguousarray(v, np.int32)
-    tab = {k: f32(rows[k]) for k in "tabcdpq"}
-    tab.update(noise=i32(rows["noise"]), hist=i32(rows["hist"]))
-    assert all(v.shape == (n,) for v in tab.values())
-    assert h.is_cuda and h.dtype == torch.float32 and h.is_contiguous() and h.shape == x.shape
-    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
     args = L.dd_multistep_sample_args()
-    args.first = first.handle
-    args.late = late.handle if late is not None else None
-    args.n_steps = n
-    args.switch_after = n if (late is None or switch_after is None) else int(switch_after)
-    args.t, args.a, args.b, args.c, args.d, args.p, args.q = (tab[k].ctypes.data_as(fp) for k in "tabcdpq")
-    args.noise, args.hist = tab["noise"].ctypes.data_as(ip), tab["hist"].ctypes.data_as(ip)
-    args.counter_base = int(counter_base)
+    tab = _step_table(args, first, late, rows, "tabcdpq", ("noise", "hist"), switch_after, counter_base)  # noqa: F841
+    assert h.is_cuda and h.dtype == torch.float32 and h.is_contiguous() and h.shape == x.shape
     args.h_dev = h.data_ptr()
     if guidance is None:
         call = lambda st: ctx.lib.dd_sample_multistep(ctx.handle, C.byref(args), st)

@@ -26,7 +26,7 @@ import random
 import time
 from argparse import ArgumentParser
 from pathlib import Path
-from typing import List
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -206,6 +206,73 @@ def predict_previous_postprocessing(model_output, x, t, z=None):
     return _affine_post("predict_previous", model_output, x, t, z)
 
 
+class StepPlan(NamedTuple):
+    """What get_samples runs, step by step.  kind: "ddpm" (dd_sample / ddpm_step: the update follows from t), "affine" (rows a, b, c)
+    or "multistep" (rows a, b, c, d, p, q, hist: multistep_coefficients).  rows: per-step arrays, always with t (the model timestep,
+    float32) and noise (int32: the step draws z).  save_after[k]: x is saved after step k.  switch_after: the first step the late model
+    runs, or None; it may lie past the last step (a DDPM switch beyond num_steps), where it only hands the late model to dd_sample."""
+    kind: str
+    rows: dict
+    save_after: list
+    switch_after: Optional[int]
+
+
+_PARAMETRIZATIONS = {predict_noise_postprocessing: "predict_noise", predict_original_postprocessing: "predict_original",
+                     predict_previous_postprocessing: "predict_previous"}
+
+
+def step_plan(parametrization, timesteps_save=(), has_late=False, t_switch=np.inf, num_steps=1000, use_ddim=False, ddim_steps=50,
+              ddim_eta=0.0, solver=None, solver_steps=20, solver_order=2):
+    """The StepPlan of get_samples' arguments (parametrization: "predict_noise" | "predict_original" | "predict_previous", or None
+    for a postprocessing function of elsewhere; has_late: a late model is given).  Host arithmetic only, no torch."""
+    # the DDPM loop switches AFTER the step at t == 1000 - t_switch (sampler.py:135-136): a t_switch outside [1, 1000] (0, negative,
+    # > 1000, inf) never matches a t in 999..0, i.e. the first model runs every step
+    in_range = has_late and np.isfinite(t_switch) and 1 <= int(t_switch) <= 1000
+    if solver is not None:
+        if use_ddim:
+            raise ValueError("DPM-Solver++ and DDIM are exclusive")
+        grid = multistep_grid(solver_steps)                                   # range check first
+        if parametrization is None:
+            raise ValueError("postprocessing must be one of this module's predict_*_postprocessing functions")
+        kind, rows = "multistep", multistep_coefficients(solver, grid, solver_order, parametrization)
+        switch_after = next((k for k, t in enumerate(rows["t"]) if t < 1000 - int(t_switch)), None) if in_range else None
+    elif use_ddim:
+        # reference sampler.py:103-126; z is drawn (:119) whenever s > 0, also at eta = 0
+        ts = np.linspace(0, 999, ddim_steps).astype(int)[::-1]
+        pairs = [(int(t), int(s)) for t, s in zip(ts[:-1], ts[1:])]
+        kind, rows = "affine", _affine_rows([t for t, _ in pairs], [affine_coefficients("ddim", t, s, ddim_eta) for t, s in pairs],
+                                            [s > 0 for _, s in pairs])
+        # :122-123: the late model from the step after the first t < 1000 - t_switch (raw t_switch: <= 0 switches after step 0)
+        switch_after = next((k + 1 for k, (t, _) in enumerate(pairs) if t < 1000 - t_switch), None) if has_late else None
+    else:
+        # sampler.py:129-139: t = 999 .. 1000 - num_steps; predict_original / predict_previous (:59-79) as affine rows
+        ts = list(range(999, 999 - int(num_steps), -1))
+        if parametrization == "predict_noise":
+            kind, rows = "ddpm", {"t": np.array(ts, np.float32), "noise": np.array([t > 0 for t in ts], np.int32)}
+        elif parametrization in ("predict_original", "predict_previous"):
+            kind, rows = "affine", _affine_rows(ts, [affine_coefficients(parametrization, t) for t in ts], [t > 0 for t in ts])
+        else:
+            raise ValueError("postprocessing must be one of this module's predict_*_postprocessing functions")
+        switch_after = int(t_switch) if in_range else None                    # the step after t == 1000 - t_switch
+    saves = set(int(v) for v in timesteps_save)
+    return StepPlan(kind, rows, [(1000 - int(t)) in saves for t in rows["t"]], switch_after)
+
+
+def _affine_rows(ts, coefficients, noise):
+    a, b, c = zip(*coefficients) if coefficients else ((), (), ())
+    return {"t": np.array(ts, np.float32), "a": np.array(a, np.float32), "b": np.array(b, np.float32), "c": np.array(c, np.float32),
+            "noise": np.array(noise, np.int32)}
+
+
+def _segments(save_after):
+    """(k0, k1) of the device loop cut after every save step"""
+    k0 = 0
+    for k, save in enumerate(save_after):
+        if save or k == len(save_after) - 1:
+            yield k0, k + 1
+            k0 = k + 1
+
+
 def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num_channels: int,
                 sample_height: int, sample_width: int, use_ddim: bool = False, ddim_steps: int = 50,
                 ddim_eta: float = 0.0, timesteps_save: List[int] = (), y=None, autoencoder=None,
@@ -228,15 +295,10 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
         predict_noise or predict_original models.  Step k runs the late model iff t_k < 1000 - t_switch (the DDPM loop's rule).
         Intermediate saves: after the step whose model timestep t has 1000 - t in timesteps_save.
     """
-    if solver is not None:
-        if use_ddim:
-            raise ValueError("DPM-Solver++ and DDIM are exclusive")
-        multistep_grid(solver_steps)                                          # range check
-        solver_param = {predict_noise_postprocessing: "predict_noise", predict_original_postprocessing: "predict_original",
-                        predict_previous_postprocessing: "predict_previous"}.get(postprocessing)
-        if solver_param is None:
-            raise ValueError("postprocessing must be one of this module's predict_*_postprocessing functions")
-        solver_rows = multistep_coefficients(solver, multistep_grid(solver_steps), solver_order, solver_param)
+    if noise not in ("torch_cpu", "device"):
+        raise ValueError("noise must be 'torch_cpu' or 'device'")
+    plan = step_plan(_PARAMETRIZATIONS.get(postprocessing), timesteps_save, late_model is not None, t_switch, num_steps, use_ddim,
+                     ddim_steps, ddim_eta, solver, solver_steps, solver_order)
     device = model.device
     guidance = None if cfg_scale is None else (float(cfg_scale), int(cfg_null_label))
     if guidance is not None and y is None:
@@ -246,158 +308,53 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
     x = torch.randn(batch_size, num_channels, sample_height, sample_width).to(device).contiguous()  # :100
     if y is not None:
         y = torch.as_tensor(y).to(device, torch.int64).contiguous()
-    intermediate = []
-    saves = set(int(v) for v in timesteps_save)
-    t_last = 1000 - int(num_steps)
     first = model.engine_model(rows)
     late = late_model.engine_model(rows) if late_model is not None else None
     ctx = first.ctx
-    # the DDPM loop switches AFTER the step at t == 1000 - t_switch (sampler.py:135-136): a t_switch outside
-    # [1, 1000] (0, negative, > 1000, inf) never matches a t in 999..0, i.e. the first model runs every step
-    switch_t = None
-    if late is not None and np.isfinite(t_switch) and 0 <= 1000 - int(t_switch) <= 999:
-        switch_t = 1000 - int(t_switch)
-
-    def draw(shape):
-        return torch.randn(shape).to(device) if noise == "torch_cpu" else torch.randn(shape, device=device)
-
-    def model_output(m, t, out):
-        """the model output at t for the host-noise loops: guided through dd_forward_guided when guidance is on"""
-        if guidance is None:
-            return m.forward(x, float(t), y, out=out)
-        return m.forward_guided(x, float(t), y, guidance[0], guidance[1], out=out)
-
-    def affine_segments(steps, switch_after):
-        """noise == "device": the table-driven loop on the device (dd_sample_affine: one hipGraph replay per step, Philox z),
-        cut at the save points.  steps: [(t, a, b, c, draws_noise, saves_after)].  Every segment keeps the seed and passes its
-        first step's index as the Philox counter base: the final samples do not depend on where the loop is cut."""
-        k0 = 0
-        while k0 < len(steps):
-            k1 = next((k + 1 for k in range(k0, len(steps)) if steps[k][5]), len(steps))
-            seg = steps[k0:k1]
-            sw = None if switch_after is None else min(max(switch_after - k0, 0), len(seg))
-            seg_first, seg_late = (first, late) if (sw is None or sw > 0) else (late, None)
-            sample_affine_loop(ctx, seg_first, seg_late if sw is not None and 0 < sw < len(seg) else None, x,
-                               [v[0] for v in seg], [v[1] for v in seg], [v[2] for v in seg], [v[3] for v in seg],
-                               [int(v[4]) for v in seg], switch_after=sw, y=y, seed=seed, counter_base=k0, noise="philox", use_graph=use_graph,
-                               guidance=guidance)
-            if seg[-1][5]:
-                intermediate.append(x.clone())
-            k0 = k1
-
-    if solver is not None:
-        # DPM-Solver++: the table-driven loop with one history register per image (h, carried across the save points)
-        rows, n = solver_rows, len(solver_rows["t"])
-        switch_after = None
-        if switch_t is not None:
-            switch_after = next((k for k in range(n) if rows["t"][k] < switch_t), None)
-        save_after = [(1000 - int(t)) in saves for t in rows["t"]]
-        h = torch.zeros_like(x)
-        if noise == "device":
-            k0 = 0
-            while k0 < n:
-                k1 = next((k + 1 for k in range(k0, n) if save_after[k]), n)
-                sw = None if switch_after is None else min(max(switch_after - k0, 0), k1 - k0)
-                seg_first, seg_late = (first, late) if (sw is None or sw > 0) else (late, None)
-                sample_multistep_loop(ctx, seg_first, seg_late if sw is not None and 0 < sw < k1 - k0 else None, x, h,
-                                      {key: v[k0:k1] for key, v in rows.items()}, switch_after=sw, y=y, seed=seed, counter_base=k0,
-                                      noise="philox", use_graph=use_graph, guidance=guidance)
-                if save_after[k1 - 1]:
-                    intermediate.append(x.clone())
-                k0 = k1
-        elif noise == "torch_cpu":
-            eps = torch.empty_like(x)
-            cur = first
-            for k in range(n):
-                if k == switch_after:
-                    cur = late
-                model_output(cur, float(rows["t"][k]), eps)
-                z = draw(x.shape) if rows["noise"][k] else None
-                ctx.multistep_step(x, eps, z, h, rows["a"][k], rows["b"][k], rows["c"][k], rows["d"][k], rows["p"][k], rows["q"][k],
-                                   rows["hist"][k], out=x)
-                if save_after[k]:
-                    intermediate.append(x.clone())
-        else:
-            raise ValueError("noise must be 'torch_cpu' or 'device'")
-    elif use_ddim:
-        # reference sampler.py:103-126.  U-ViT forward on the engine + one fused affine update per step.
-        ts = np.linspace(0, 999, ddim_steps).astype(int)[::-1]
-        pairs = [(int(t), int(s_)) for t, s_ in zip(ts[:-1], ts[1:])]
-        if noise == "device":
-            steps, switch_after = [], None
-            for k, (t, s_) in enumerate(pairs):
-                a, b, c = affine_coefficients("ddim", t, s_, ddim_eta)
-                steps.append((float(t), a, b, c, s_ > 0, (1000 - t) in saves))
-                if switch_after is None and late is not None and t < 1000 - t_switch:   # :122-123: from the NEXT step on
-                    switch_after = k + 1
-            affine_segments(steps, switch_after)
-        else:
-            eps = torch.empty_like(x)
-            cur = first
-            for t, s_ in pairs:
-                model_output(cur, t, eps)                                        # :108-110
-                a, b, c = affine_coefficients("ddim", t, s_, ddim_eta)           # :112-117
-                z = draw(x.shape) if s_ > 0 else None                            # :119
-                ctx.affine_step(x, eps, z, a, b, c, out=x)                       # :120
-                if late is not None and t < 1000 - t_switch:                     # :122-123
-                    cur = late
-                if 1000 - t in saves:                                            # :125-126
-                    intermediate.append(x.clone())
-    elif postprocessing is not predict_noise_postprocessing:
-        # predict_original / predict_previous (sampler.py:59-79): same loop, affine update
-        kind = {predict_original_postprocessing: "predict_original",
-                predict_previous_postprocessing: "predict_previous"}.get(postprocessing)
-        if kind is None:
-            raise ValueError("postprocessing must be one of this module's predict_*_postprocessing functions")
-        if noise == "device":
-            steps, switch_after = [], None
-            for k, t in enumerate(range(999, t_last - 1, -1)):
-                a, b, c = affine_coefficients(kind, t)
-                steps.append((float(t), a, b, c, t > 0, (1000 - t) in saves))
-                if switch_t is not None and t == switch_t:
-                    switch_after = k + 1
-            affine_segments(steps, switch_after)
-        else:
-            eps = torch.empty_like(x)
-            cur = first
-            for t in range(999, t_last - 1, -1):
-                model_output(cur, t, eps)
-                a, b, c = affine_coefficients(kind, t)
-                ctx.affine_step(x, eps, draw(x.shape) if t > 0 else None, a, b, c, out=x)
-                if switch_t is not None and t == switch_t:
-                    cur = late
-                if 1000 - t in saves:
-                    intermediate.append(x.clone())
-    elif noise == "device":
-        # segments between save points; each segment is one dd_sample call (graph replays)
-        stops = sorted({1000 - s for s in saves if t_last <= 1000 - s <= 999}, reverse=True)
-        t = 999
-        cur_first, cur_late, cur_switch = first, late, (int(t_switch) if switch_t is not None else 0)
-        while t >= t_last:
-            seg_end = next((s for s in stops if s <= t), t_last)
-            if switch_t is not None and t <= switch_t - 1 and cur_late is not None:
-                cur_first, cur_late, cur_switch = late, None, 0  # already past the switch
-            sample_loop(ctx, cur_first, cur_late, x, t_switch=cur_switch, t_start=t, t_end=seg_end, y=y,
-                        seed=seed, noise="philox", use_graph=use_graph, guidance=guidance)
-            if seg_end in stops:
-                intermediate.append(x.clone())
-            t = seg_end - 1
-    elif noise == "torch_cpu":
-        cur = first
-        eps = torch.empty_like(x) if guidance is not None else None
-        for t in range(999, t_last - 1, -1):                                 # :129
-            z = torch.randn(x.shape).to(device) if t > 0 else None           # :52 (CPU stream)
-            if guidance is None:
-                cur.sample_step(x, t, y=y, z=z, noise="buffer")              # :130-133
+    tab, n = plan.rows, len(plan.rows["t"])
+    h = torch.zeros_like(x) if plan.kind == "multistep" else None          # the solver's history, carried across save points
+    intermediate = []
+    if noise == "device":
+        # one loop call per segment between save points (hipGraph replays, Philox z).  Every segment keeps the seed and passes its first
+        # step's index as the Philox counter base: the final samples do not depend on where the loop is cut.
+        for k0, k1 in _segments(plan.save_after):
+            sw = None if plan.switch_after is None else min(max(plan.switch_after - k0, 0), k1 - k0)
+            kw = dict(y=y, seed=seed, noise="philox", use_graph=use_graph, guidance=guidance)
+            if plan.kind == "ddpm":                                          # dd_sample counts t_switch from t = 999, as switch_after
+                sample_loop(ctx, late if sw == 0 else first, None if sw == 0 else late, x, t_switch=plan.switch_after if sw else 0,
+                            t_start=int(tab["t"][k0]), t_end=int(tab["t"][k1 - 1]), **kw)
             else:
-                model_output(cur, t, eps)
-                ctx.ddpm_step(x, eps, z, t, out=x)
-            if switch_t is not None and t == switch_t:                       # :135-136
-                cur = late
-            if 1000 - t in saves:                                            # :138-139
+                seg = {key: v[k0:k1] for key, v in tab.items()}
+                m0, m1 = late if sw == 0 else first, late if sw and sw < k1 - k0 else None
+                if plan.kind == "affine":
+                    sample_affine_loop(ctx, m0, m1, x, seg["t"], seg["a"], seg["b"], seg["c"], seg["noise"], switch_after=sw,
+                                       counter_base=k0, **kw)
+                else:
+                    sample_multistep_loop(ctx, m0, m1, x, h, seg, switch_after=sw, counter_base=k0, **kw)
+            if plan.save_after[k1 - 1]:
                 intermediate.append(x.clone())
     else:
-        raise ValueError("noise must be 'torch_cpu' or 'device'")
+        eps, cur = torch.empty_like(x), first
+        for k in range(n):                                                   # sampler.py:129-139 / :103-126
+            if k == plan.switch_after:
+                cur = late
+            t = tab["t"][k]
+            z = torch.randn(x.shape).to(device) if tab["noise"][k] else None  # randn_like on the torch CPU stream (:52, :67, :119)
+            if plan.kind == "ddpm" and guidance is None:
+                cur.sample_step(x, int(t), y=y, z=z, noise="buffer")          # :130-133, fused
+            else:
+                if guidance is None:
+                    cur.forward(x, float(t), y, out=eps)
+                else:
+                    cur.forward_guided(x, float(t), y, guidance[0], guidance[1], out=eps)
+                if plan.kind == "ddpm":
+                    ctx.ddpm_step(x, eps, z, int(t), out=x)
+                elif plan.kind == "affine":
+                    ctx.affine_step(x, eps, z, tab["a"][k], tab["b"][k], tab["c"][k], out=x)
+                else:
+                    ctx.multistep_step(x, eps, z, h, *(tab[key][k] for key in "abcdpq"), tab["hist"][k], out=x)
+            if plan.save_after[k]:
+                intermediate.append(x.clone())
 
     if autoencoder is not None:                                              # :141-143, :149-150
         print("Decode the images...")

@@ -156,6 +156,7 @@ struct dd_model {
     std::vector<AttnProbeW> attn_probes;                  // DD_EE_ATTENTION_PROBE: one per layer
     bool ee_conv_stride_ok = false;                       // the heads' conv weights / biases sit at a constant stride in the weight arena (one batched conv launch)
     long long ee_wconv_stride = 0, ee_bconv_stride = 0;
+    bool ee_batched = false;                              // early-exit heads / probes batched behind the last block (Backbone::ee_dec_all)
     bool fused_mlp = false;               // bf16 mode, D in {64,128,256,512}: fc1+GELU+fc2+residual in one launch
     bool fused_proj = false;              // ... and attn.proj + residual in front of it (D % 128 == 0): patch rows only
     bool fused_skip = false;              // ... and the NEXT block's skip_linear + norm1 behind it (mid / out blocks; early-exit models tap y on the way,
@@ -488,34 +489,40 @@ Chain whole_batch(dd_ctx* c, dd_model* m) { return Chain{&m->ws[0], c->st[0], c-
 // early-exit taps of one forward (EarlyExitUViT.forward, early_exit.py:290-313): cls [depth, B], outs [depth, B, C, S, S]
 struct EeTaps { float* cls; float* outs; int t; };
 
+// What block bi finds already done when it starts: left by the launches in front of it (the embed launch; the previous block's last launches).
+// h, frag and qkv say where its norm1 went and exclude one another; all false: the block starts from the residual stream x alone.
+struct Handoff {
+    bool h = false;      // its norm1 is in h (row-major)
+    bool frag = false;   // the patch rows' norm1 is in hfrag, in the order the attention launch loads it: that launch computes attn.qkv (and
+                         // normalises the extra-token rows itself, from x)
+    bool qkv = false;    // its attn.qkv is in qkv
+    bool skip = false;   // its skip_linear has run: x holds the output, ytap the block input y that its early-exit heads read
+};
+
+// one forward of B rows of chain ch, enqueued on s (Backbone<T>{m, ch, B, s, ee}): the stages of a block each enqueue their launches and
+// pass the next one a Handoff
 template <typename T>
-int run_backbone(dd_model* m, const Chain& ch, const float* x_img, const float* t_vec, const int64_t* y_dev, int B, hipStream_t s,
-                 const EeTaps* ee = nullptr) {
+struct Backbone {
+    static constexpr bool bf16 = sizeof(T) == 2;
+    dd_model* m;
+    const Chain& ch;
+    int B;
+    hipStream_t s;
+    const EeTaps* ee;
     dd_ctx* c = m->ctx;
     const WsPtrs& ws = *ch.ws;
-    const int D = m->D, L = m->L, M = B * L;
-    const int Mp = round_up(M, 256);
-    EmbedArgs ea{x_img, m->emb_wt, m->emb_b, m->pos, m->label, (const long long*)y_dev, t_vec, ch.st, ws.x,
-                 B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, D, L, m->extras,
-                 m->cfg.num_classes, m->cfg.normalize_timesteps, Mp, (c->dev_flags & DD_DEV_GENERIC_EMBED) ? 1 : 0};
-    // the first block's norm1 of the patch rows from the embed launch's registers (where the attention launch computes attn.qkv itself and
-    // normalises the extra-token rows from the residual stream: the time_embed MLP below only rewrites such a row)
-    bool ln1_done = false;
-    if constexpr (sizeof(T) == 2) {
-        if (m->fused_qa && !(c->dev_flags & DD_DEV_NO_EMBED_LN) && embed_ln_supported(ea)) {
-            ea.ln_g = m->blocks[0].ln1_g; ea.ln_b = m->blocks[0].ln1_b; ea.ln_frag = ws.hfrag;
-            ln1_done = true;
-        }
-    }
-    DD_HIP(c, launch_embed(ea, s));
-    if (m->tm_w1t) {   // mlp_time_embed: the time token goes through Linear -> SiLU -> Linear (models/uvit.py:264-272, 358)
-        TimeMlpArgs ta{m->tm_w1t, m->tm_b1, m->tm_w2t, m->tm_b2, m->pos, t_vec, ch.st, ws.x, B, D, L, m->extras, m->cfg.normalize_timesteps};
-        DD_HIP(c, launch_time_mlp(ta, s));
-    }
+    const int D = m->D, L = m->L, M = B * L, nb = (int)m->blocks.size();
+    const int prof = c->prof_kind == DD_PROF_DOMINANT ? ((bf16 && m->fused_mlp) ? DD_PROF_BLOCK_TAIL : DD_PROF_FC1) : c->prof_kind;
+    T *h = (T*)ws.h, *ao = (T*)ws.ao, *qkv = (T*)ws.qkv, *hid = (T*)ws.hid, *xb = (T*)ws.xb;
+    // Early-exit heads (m->ee_batched): every layer's LayerNorm + decoder_pred launch writes its own slice of a [depth][B L, pd] buffer and every
+    // MLP probe's row launch its own [B, L] slice; ONE unpatchify / conv launch and ONE probe reduce launch behind the last block finish all
+    // layers (the per-layer arithmetic is unchanged; 2 x 12 launches less on each step's critical path).  The buffers live in the MLP hidden
+    // buffer, which the fused block tail never touches.
+    float* ee_dec_all = ee && m->ee_batched ? (float*)ws.hid : nullptr;
+    float* ee_srow_all = ee_dec_all ? ee_dec_all + (size_t)nb * M * m->pd : nullptr;
 
-    // in-context timing (dd_profile_steps): an event on s in front of and behind every launch of the selected kind
-    const int prof = c->prof_kind == DD_PROF_DOMINANT ? ((sizeof(T) == 2 && m->fused_mlp) ? DD_PROF_BLOCK_TAIL : DD_PROF_FC1) : c->prof_kind;
-    auto mark = [&](int kind) -> int {
+    // in-context timing (dd_profile_steps): an event on s in front of and behind every launch of the selected kind (DD_TIMED)
+    int mark(int kind) {
         if (!m->time_fc1 || kind != prof) return DD_OK;
         while (m->fc1_events.size() < m->fc1_used + 1) {
             hipEvent_t e;
@@ -524,331 +531,290 @@ int run_backbone(dd_model* m, const Chain& ch, const float* x_img, const float* 
         }
         DD_HIP(c, hipEventRecord(m->fc1_events[m->fc1_used++], s));
         return DD_OK;
-    };
+    }
+#define DD_TIMED(kind, expr) \
+    do { if (int rc_ = mark(kind)) return rc_; DD_HIP(c, expr); if (int rc_ = mark(kind)) return rc_; } while (0)
+
     // 128 x 128 or 256 x 256 tiles for a bf16 Linear: decided for the model's max_batch on the context's CU count -- never for the batch (or the
     // chain-halved grid, Chain::cus) of this call, so that a row takes the same kernel alone, in a full batch and in a half-batch chain
-    auto tile128 = [&](int N, int K, int K1) { return sizeof(T) == 2 && gemm_prefers_128(m->cfg.max_batch * L, N, K, K1, c->num_cus) ? 1 : 0; };
-    T* h = (T*)ws.h; T* ao = (T*)ws.ao; T* qkv = (T*)ws.qkv; T* hid = (T*)ws.hid; T* xb = (T*)ws.xb;
-    const int nb = (int)m->blocks.size();
-    bool h_ready = ln1_done;   // h already holds norm1 of the coming block (written by the fused MLP of the previous one / the embed launch)
-    bool skip_done = false; // ... and x already holds that block's skip_linear output (the previous fused launch ran it too)
-    bool qkv_done = false;  // ... and qkv already holds that block's attn.qkv output (ditto)
-    bool qa_ready = ln1_done;  // ... or only the extra-token rows of it: the patch rows' qkv is computed inside the attention launch
-    bool ee_side = false;   // this block's early-exit head / probe launches are in flight on the side stream
-    // Early-exit heads: every layer's LayerNorm + decoder_pred launch writes its own slice of a [depth][B L, pd] buffer and every MLP probe's row
-    // launch its own [B, L] slice; ONE unpatchify / conv launch and ONE probe reduce launch behind the last block finish all layers (the
-    // per-layer arithmetic is unchanged; 2 x 12 launches less on each step's critical path).  The buffers live in the MLP hidden buffer, which
-    // the fused block tail never touches; models on the GEMM path (and images below one 16 x 16 tile) keep the per-layer launches.
-    float* ee_dec_all = nullptr;
-    float* ee_srow_all = nullptr;
-    if (ee && sizeof(T) == 2 && m->fused_mlp && m->ee_conv_stride_ok && m->heads[0].wg && m->cfg.img_size >= 16 &&
-        (size_t)nb * ((size_t)M * m->pd + (size_t)B * L) * sizeof(float) <= (size_t)Mp * m->hid_ld * m->esize) {
-        ee_dec_all = (float*)ws.hid;
-        ee_srow_all = ee_dec_all + (size_t)nb * M * m->pd;
+    int tile128(int N, int K, int K1) const { return bf16 && gemm_prefers_128(m->cfg.max_batch * L, N, K, K1, c->num_cus) ? 1 : 0; }
+    // the long-skip operand of out-block bi: the in-blocks' outputs, last in first out (uvit.py:374-375)
+    const T* skip_of(int bi) const { return (const T*)ws.skips[nb - 1 - bi]; }
+    // what a row pass that wrote the next block's norm1 leaves: row-major, or (fused_qa) the patch rows in the attention launch's order
+    Handoff norm1_written() const { return Handoff{!m->fused_qa, m->fused_qa}; }
+
+    // The two row-pass variants of an N = D Linear g (skip_linear, attn.proj, mlp.fc2): x = [x +] g + bias (resid), g's bf16 copy (g.out), and
+    // LayerNorm ln_g / ln_b of the updated rows into h -- under frag the patch rows into hfrag instead, in the order the attention launch loads them.
+    // (embed_dim 768) the row-resident launch (rowlin.hip: W image wimg), then the launch that finishes its extra-token rows from the K-split slabs
+    int rowlin_then_reduce(const GemmArgs<T>& g, int resid, const char* wimg, const float* ln_g, const float* ln_b, bool frag) {
+        RowLinArgs ra{};
+        ra.A = (const bf16_t*)g.A; ra.A2 = (const bf16_t*)g.A2; ra.k_split = g.A2 ? g.K1 : 0; ra.set_x = !resid; ra.lda = g.lda; ra.K = g.K;
+        ra.wimg = wimg; ra.bias = g.bias; ra.xres = ws.x; ra.x_copy = (bf16_t*)g.out; ra.partial = ws.mlp_partial;
+        if (ln_g) {
+            ra.ln_g = ln_g; ra.ln_b = ln_b;
+            if (frag) ra.h_frag = ws.hfrag; else ra.h_out = (bf16_t*)h;
+        }
+        rowlin_plan(B, m->N, m->extras, L, ra.K, ra);
+        DD_TIMED(DD_PROF_ROWLIN, launch_rowlin(ra, s));
+        MlpFusedArgs fr{};
+        fr.b2 = ra.bias; fr.xres = ws.x; fr.partial = ws.mlp_partial; fr.out = ra.x_copy; fr.ldo = D; fr.reduce_set = ra.set_x;
+        fr.tok_n = ra.tok_n; fr.tok_e = ra.tok_e; fr.tok_l = ra.tok_l; fr.n_extra = ra.n_extra; fr.tiles_left = ra.tiles_extra;
+        fr.groups = ra.groups; fr.prows = 128;
+        if (ra.h_out) { fr.ln_out_g = ra.ln_g; fr.ln_out_b = ra.ln_b; fr.ln_out = ra.h_out; }
+        DD_HIP(c, launch_mlp_reduce(fr, D, s));
+        return DD_OK;
     }
-    for (int bi = 0; bi < nb; ++bi) {
-        const BlockW& w = m->blocks[bi];
-        const bool is_in = bi < m->half_depth, is_out = bi > m->half_depth;
-        if (ee) {
-            // output head and uncertainty probe on the INPUT of block bi (for out-blocks: before skip_linear, as the
-            // reference taps x before blk(x, skip)); both read the fp32 residual stream.  In- and mid-blocks: on the context's side
-            // stream, beside this block's norm1 / qkv / attention launches (which only read x); joined before the first launch that
-            // writes x (attn.proj).  Out-blocks start with skip_linear, which overwrites x: their heads stay in line.
-            const HeadW& hd = m->heads[bi];
-            // (the previous launch ran this block's skip_linear already: x holds its output, the tapped y is in ytap)
-            const float* xin = (skip_done && ws.ytap) ? ws.ytap : ws.x;
-            ee_side = !is_out && ch.ee_fork && c->side && s != c->side;
-            hipStream_t hs = ee_side ? c->side : s;
-            if (ee_side) {
-                DD_HIP(c, hipEventRecord(c->ev_ee_fork, s));
-                DD_HIP(c, hipStreamWaitEvent(c->side, c->ev_ee_fork, 0));
+    // split-K halves into the slabs, then the row pass that adds them (reduce_ln; under frag the extra-token rows' LayerNorm still goes to h)
+    int splitk_then_reduce_ln(GemmArgs<T> g, int resid, const float* ln_g, const float* ln_b, bool frag) {
+        g.partial = ws.mlp_partial; g.splits = 2;
+        DD_TIMED(DD_PROF_SPLITK, launch_gemm_splitk(g, s, ch.cus));
+        ReduceLnArgs ra{ws.x, ws.mlp_partial, (long long)M * D, 2, resid, g.bias, (bf16_t*)g.out, D, ln_g, ln_b, (bf16_t*)h,
+                        ln_g && frag ? ws.hfrag : nullptr, L, m->extras, M};
+        DD_HIP(c, launch_reduce_ln(ra, D, s));
+        return DD_OK;
+    }
+
+    int embed(const float* x_img, const float* t_vec, const int64_t* y_dev, Handoff& first) {
+        EmbedArgs ea{x_img, m->emb_wt, m->emb_b, m->pos, m->label, (const long long*)y_dev, t_vec, ch.st, ws.x,
+                     B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, D, L, m->extras,
+                     m->cfg.num_classes, m->cfg.normalize_timesteps, round_up(M, 256), (c->dev_flags & DD_DEV_GENERIC_EMBED) ? 1 : 0};
+        // the first block's norm1 of the patch rows from the embed launch's registers (where the attention launch computes attn.qkv itself and
+        // normalises the extra-token rows from the residual stream: the time_embed MLP below only rewrites such a row)
+        if constexpr (bf16) {
+            if (m->fused_qa && !(c->dev_flags & DD_DEV_NO_EMBED_LN) && embed_ln_supported(ea)) {
+                ea.ln_g = m->blocks[0].ln1_g; ea.ln_b = m->blocks[0].ln1_b; ea.ln_frag = ws.hfrag;
+                first.frag = true;
             }
-            // probe row: layer bi | timestep t | (t, layer): t is read from the step state inside the launch (a captured
-            // step replays for every t); dd_forward_early_exit has put int(t) there
-            const int t_mul = m->ee_type == DD_EE_MLP_PER_LAYER ? 0 : m->ee_type == DD_EE_MLP_PER_TIMESTEP ? 1 : nb;
-            const int add = m->ee_type == DD_EE_MLP_PER_TIMESTEP ? 0 : bi;
-            bool probe_done = false;
-            if (hd.wg) {   // the head's LayerNorm + decoder_pred in one exact-fp32 launch (the final head's kernel), patch rows only
-                HeadDecArgs ha{xin, hd.wg, hd.dc, ee_dec_all ? ee_dec_all + (size_t)bi * M * m->pd : ws.dec, M, m->pd, (L - m->extras) % 16 == 0 ? L : 0, m->extras};
-                if (hd.wsplit) { ha.wg = hd.wsplit; ha.c = hd.dcs; ha.split = 1; }      // (bf16 engine: the split-bf16 product, rowops.hip SPLIT)
-                if (ee_srow_all && m->ee_type != DD_EE_ATTENTION_PROBE && head_dec_probe_supported(D)) {   // ... and the MLP probe's per-token values of the same rows
-                    ha.srow = ee_srow_all + (size_t)bi * B * L; ha.pw_base = m->probe_w; ha.pb_base = m->probe_b; ha.st = ch.st; ha.t_mul = t_mul; ha.add = add;
-                    probe_done = true;
-                }
-                DD_HIP(c, launch_head_dec(ha, D, ch.cus, hs));
-            } else {
-                float* hf = (float*)ws.hid;   // the MLP hidden buffer is free between blocks
-                DD_HIP(c, launch_layernorm<float>(xin, hd.ng, hd.nb, hf, M, D, hs));
-                GemmArgs<float> g{hf, nullptr, hd.wdec, hd.bdec, ws.dec, nullptr, M, m->pd, D, D, D, 0, m->pd};
-                DD_HIP(c, launch_gemm<float>(g, EPI_BIAS_SET, hs, ch.cus));
+        }
+        DD_HIP(c, launch_embed(ea, s));
+        if (m->tm_w1t) {   // mlp_time_embed: the time token goes through Linear -> SiLU -> Linear (models/uvit.py:264-272, 358)
+            TimeMlpArgs ta{m->tm_w1t, m->tm_b1, m->tm_w2t, m->tm_b2, m->pos, t_vec, ch.st, ws.x, B, D, L, m->extras, m->cfg.normalize_timesteps};
+            DD_HIP(c, launch_time_mlp(ta, s));
+        }
+        return DD_OK;
+    }
+
+    // output head and uncertainty probe on the INPUT of block bi (for out-blocks: before skip_linear, as the reference taps x before
+    // blk(x, skip)); both read the fp32 residual stream.  In- and mid-blocks: on the context's side stream (side = true), beside this block's
+    // norm1 / qkv / attention launches (which only read x); the caller joins it before the first launch that writes x (attn.proj).
+    // Out-blocks start with skip_linear, which overwrites x: their heads stay in line.
+    int ee_taps(int bi, const Handoff& in, bool& side) {
+        if (!ee) return DD_OK;
+        const HeadW& hd = m->heads[bi];
+        const float* xin = (in.skip && ws.ytap) ? ws.ytap : ws.x;
+        side = bi <= m->half_depth && ch.ee_fork && c->side && s != c->side;
+        hipStream_t hs = side ? c->side : s;
+        if (side) {
+            DD_HIP(c, hipEventRecord(c->ev_ee_fork, s));
+            DD_HIP(c, hipStreamWaitEvent(c->side, c->ev_ee_fork, 0));
+        }
+        // probe row: layer bi | timestep t | (t, layer): t is read from the step state inside the launch (a captured
+        // step replays for every t); dd_forward_early_exit has put int(t) there
+        const int t_mul = m->ee_type == DD_EE_MLP_PER_LAYER ? 0 : m->ee_type == DD_EE_MLP_PER_TIMESTEP ? 1 : nb;
+        const int add = m->ee_type == DD_EE_MLP_PER_TIMESTEP ? 0 : bi;
+        bool probe_done = false;
+        if (hd.wg) {   // the head's LayerNorm + decoder_pred in one exact-fp32 launch (the final head's kernel), patch rows only
+            HeadDecArgs ha{xin, hd.wg, hd.dc, ee_dec_all ? ee_dec_all + (size_t)bi * M * m->pd : ws.dec, M, m->pd, (L - m->extras) % 16 == 0 ? L : 0, m->extras};
+            if (hd.wsplit) { ha.wg = hd.wsplit; ha.c = hd.dcs; ha.split = 1; }      // (bf16 engine: the split-bf16 product, rowops.hip SPLIT)
+            if (ee_srow_all && m->ee_type != DD_EE_ATTENTION_PROBE && head_dec_probe_supported(D)) {   // ... and the MLP probe's per-token values of the same rows
+                ha.srow = ee_srow_all + (size_t)bi * B * L; ha.pw_base = m->probe_w; ha.pb_base = m->probe_b; ha.st = ch.st; ha.t_mul = t_mul; ha.add = add;
+                probe_done = true;
             }
+            DD_HIP(c, launch_head_dec(ha, D, ch.cus, hs));
+        } else {
+            float* hf = (float*)ws.hid;   // the MLP hidden buffer is free between blocks
+            DD_HIP(c, launch_layernorm<float>(xin, hd.ng, hd.nb, hf, M, D, hs));
+            GemmArgs<float> g{hf, nullptr, hd.wdec, hd.bdec, ws.dec, nullptr, M, m->pd, D, D, D, 0, m->pd};
+            DD_HIP(c, launch_gemm<float>(g, EPI_BIAS_SET, hs, ch.cus));
+        }
+        if (!ee_dec_all) {
             const long long chw = (long long)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
-            if (!ee_dec_all) {
-                FinalArgs fa{ws.dec, hd.wconv, hd.bconv, nullptr, nullptr, ee->outs + (long long)bi * B * chw, nullptr, ch.st,
-                             c->coef, B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, DD_NOISE_NONE, 0, 0};
-                DD_HIP(c, launch_final(fa, hs));
-            }
-            if (m->ee_type == DD_EE_ATTENTION_PROBE) {
-                DD_HIP(c, launch_ee_attn_probe(xin, m->attn_probes[bi], ee->cls + (long long)bi * B, B, L, D, hs));
-            } else if (!probe_done) {
-                if (ee_srow_all) DD_HIP(c, launch_ee_probe(xin, m->probe_w, m->probe_b, nullptr, ee_srow_all + (size_t)bi * B * L, B, L, D, ch.st, t_mul, add, hs));   // rows only: reduced behind the last block
-                else DD_HIP(c, launch_ee_probe(xin, m->probe_w, m->probe_b, ee->cls + (long long)bi * B, (float*)ws.hid, B, L, D, ch.st, t_mul, add, hs));   // (the MLP hidden buffer is free between blocks)
-            }
-            if (ee_side) DD_HIP(c, hipEventRecord(c->ev_ee_join, c->side));
+            FinalArgs fa{ws.dec, hd.wconv, hd.bconv, nullptr, nullptr, ee->outs + (long long)bi * B * chw, nullptr, ch.st,
+                         c->coef, B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, L, m->extras, DD_NOISE_NONE, 0, 0};
+            DD_HIP(c, launch_final(fa, hs));
         }
-        if (is_out && !skip_done) {
-            const int oi = bi - m->half_depth - 1;
-            const T* skip = (const T*)ws.skips[m->half_depth - 1 - oi];  // LIFO (uvit.py:374-375)
-            GemmArgs<T> g{xb, skip, (const T*)w.skip_w, w.skip_b, ws.x, nullptr, M, D, 2 * D, D, D, D, D};
-            g.tile128 = tile128(D, 2 * D, D);
-            bool done = false;
-            if constexpr (sizeof(T) == 2) {
-                if (m->rowlin_skip) {     // (embed_dim 768) x = skip_linear(cat[x, skip]) and this block's norm1 in one row-resident launch
-                    RowLinArgs ra{};
-                    ra.A = (const bf16_t*)xb; ra.A2 = (const bf16_t*)skip; ra.k_split = D; ra.set_x = 1; ra.lda = D; ra.K = 2 * D;
-                    ra.wimg = w.rls_img; ra.bias = w.skip_b; ra.xres = ws.x; ra.partial = ws.mlp_partial; ra.ln_g = w.ln1_g; ra.ln_b = w.ln1_b;
-                    if (m->fused_qa) ra.h_frag = ws.hfrag; else ra.h_out = (bf16_t*)h;
-                    rowlin_plan(B, m->N, m->extras, L, 2 * D, ra);
-                    if (int rc = mark(DD_PROF_ROWLIN)) return rc;
-                    DD_HIP(c, launch_rowlin(ra, s));
-                    if (int rc = mark(DD_PROF_ROWLIN)) return rc;
-                    MlpFusedArgs fr{};
-                    fr.b2 = w.skip_b; fr.xres = ws.x; fr.partial = ws.mlp_partial; fr.ldo = D; fr.reduce_set = 1;
-                    fr.tok_n = ra.tok_n; fr.tok_e = ra.tok_e; fr.tok_l = ra.tok_l; fr.n_extra = ra.n_extra; fr.tiles_left = ra.tiles_extra;
-                    fr.groups = ra.groups; fr.prows = 128;
-                    if (!m->fused_qa) { fr.ln_out_g = w.ln1_g; fr.ln_out_b = w.ln1_b; fr.ln_out = (bf16_t*)h; }
-                    DD_HIP(c, launch_mlp_reduce(fr, D, s));
-                    h_ready = true; qa_ready = m->fused_qa; done = true;
-                }
-            }
-            if constexpr (sizeof(T) == 2) {
-                if (m->splitk && !done) {     // split-K halves -> slabs; x = bias + slabs and this block's norm1 in the row pass behind it
-                    g.partial = ws.mlp_partial; g.splits = 2;
-                    if (int rc = mark(DD_PROF_SPLITK)) return rc;
-                    DD_HIP(c, launch_gemm_splitk(g, s, ch.cus));
-                    if (int rc = mark(DD_PROF_SPLITK)) return rc;
-                    ReduceLnArgs ra{ws.x, ws.mlp_partial, (long long)M * D, 2, 0, w.skip_b, nullptr, D, w.ln1_g, w.ln1_b, (bf16_t*)h,
-                                    m->fused_qa ? ws.hfrag : nullptr, L, m->extras, M};
-                    DD_HIP(c, launch_reduce_ln(ra, D, s));
-                    h_ready = true; qa_ready = m->fused_qa; done = true;
-                }
-            }
-            if (!done) DD_HIP(c, launch_gemm<T>(g, EPI_BIAS_SET, s, ch.cus));
+        if (m->ee_type == DD_EE_ATTENTION_PROBE) {
+            DD_HIP(c, launch_ee_attn_probe(xin, m->attn_probes[bi], ee->cls + (long long)bi * B, B, L, D, hs));
+        } else if (!probe_done) {
+            if (ee_srow_all) DD_HIP(c, launch_ee_probe(xin, m->probe_w, m->probe_b, nullptr, ee_srow_all + (size_t)bi * B * L, B, L, D, ch.st, t_mul, add, hs));   // rows only: reduced behind the last block
+            else DD_HIP(c, launch_ee_probe(xin, m->probe_w, m->probe_b, ee->cls + (long long)bi * B, (float*)ws.hid, B, L, D, ch.st, t_mul, add, hs));   // (the MLP hidden buffer is free between blocks)
         }
-        skip_done = false;
-        if (!h_ready && !qkv_done) {     // else: written by the previous block's fused MLP
-            if (sizeof(T) == 2 && m->fused_qa) {
+        if (side) DD_HIP(c, hipEventRecord(c->ev_ee_join, c->side));
+        return DD_OK;
+    }
+
+    // out-blocks: x = skip_linear(cat[x, skip]), unless the previous block's fused launch ran it; the row-resident and split-K variants
+    // leave this block's norm1 behind
+    int skip_linear(int bi, Handoff& hand) {
+        if (bi <= m->half_depth || hand.skip) return DD_OK;
+        const BlockW& w = m->blocks[bi];
+        GemmArgs<T> g{xb, skip_of(bi), (const T*)w.skip_w, w.skip_b, ws.x, nullptr, M, D, 2 * D, D, D, D, D};
+        g.tile128 = tile128(D, 2 * D, D);
+        if constexpr (bf16) {
+            if (m->rowlin_skip || m->splitk) hand = norm1_written();
+            if (m->rowlin_skip) return rowlin_then_reduce(g, 0, w.rls_img, w.ln1_g, w.ln1_b, m->fused_qa);
+            if (m->splitk) return splitk_then_reduce_ln(g, 0, w.ln1_g, w.ln1_b, m->fused_qa);
+        }
+        DD_HIP(c, launch_gemm<T>(g, EPI_BIAS_SET, s, ch.cus));
+        return DD_OK;
+    }
+
+    // ao = attention(attn.qkv(norm1(x))), norm1 and qkv where the launches in front did not leave them
+    int norm1_attention(int bi, const Handoff& in) {
+        const BlockW& w = m->blocks[bi];
+        bool qa = in.frag;
+        if (!in.h && !in.frag && !in.qkv) {
+            if (bf16 && m->fused_qa) {
                 // (the first block; blocks behind a skip_linear GEMM when that fusion is off) norm1 straight into the order the
                 // attention launch loads it, so that these blocks take the same launch as the others
                 DD_HIP(c, launch_layernorm_frag(ws.x, w.ln1_g, w.ln1_b, (bf16_t*)h, ws.hfrag, M, D, L, m->extras, s));
-                qa_ready = true;
+                qa = true;
             } else {
                 DD_HIP(c, launch_layernorm<T>(ws.x, w.ln1_g, w.ln1_b, h, M, D, s));
             }
         }
-        h_ready = false;
-        if (qa_ready) {
-            if (int rc = mark(DD_PROF_QKV_ATTENTION)) return rc;
-            if constexpr (sizeof(T) == 2)
-                DD_HIP(c, launch_qkv_attention(ws.hfrag, w.qa_img, w.qkv_b, nullptr, ws.x, w.ln1_g, w.ln1_b, (bf16_t*)ao, B, L, m->H, D, m->extras, s));
-            if (int rc = mark(DD_PROF_QKV_ATTENTION)) return rc;
-        } else {
-            if (!qkv_done) {
-                GemmArgs<T> g{h, nullptr, (const T*)w.qkv_w, w.qkv_b, nullptr, qkv, M, 3 * D, D, D, D, 0, 3 * D};
-                g.hm = make_head_major(L, m->H);     // head-major: each (q | k | v, head) unit of an image is contiguous (attention.hip)
-                DD_HIP(c, launch_gemm<T>(g, w.qkv_b ? EPI_BIAS_STORE : EPI_STORE, s, ch.cus));
-            }
-            if (int rc = mark(DD_PROF_QKV_ATTENTION)) return rc;
-            DD_HIP(c, launch_attention<T>(qkv, ao, B, L, m->H, D, s));
-            if (int rc = mark(DD_PROF_QKV_ATTENTION)) return rc;
+        if (qa) {
+            if constexpr (bf16)
+                DD_TIMED(DD_PROF_QKV_ATTENTION, launch_qkv_attention(ws.hfrag, w.qa_img, w.qkv_b, nullptr, ws.x, w.ln1_g, w.ln1_b, (bf16_t*)ao, B, L, m->H, D, m->extras, s));
+            return DD_OK;
         }
-        qkv_done = false; qa_ready = false;
-        if (ee_side) {     // the head / probe launches have read x: from here on the block updates it
-            DD_HIP(c, hipStreamWaitEvent(s, c->ev_ee_join, 0));
-            ee_side = false;
+        if (!in.qkv) {
+            GemmArgs<T> g{h, nullptr, (const T*)w.qkv_w, w.qkv_b, nullptr, qkv, M, 3 * D, D, D, D, 0, 3 * D};
+            g.hm = make_head_major(L, m->H);     // head-major: each (q | k | v, head) unit of an image is contiguous (attention.hip)
+            DD_HIP(c, launch_gemm<T>(g, w.qkv_b ? EPI_BIAS_STORE : EPI_STORE, s, ch.cus));
         }
-        bool ln2_done = false;
-        if constexpr (sizeof(T) == 2) {
-            if (m->rowlin_proj) {
-                // (embed_dim 768) x += proj(ao) + b and norm2 of the updated rows in one row-resident launch (see mlp.fc2 below)
-                RowLinArgs ra{};
-                ra.A = (const bf16_t*)ao; ra.lda = D; ra.K = D; ra.wimg = w.rlp_img; ra.bias = w.proj_b; ra.xres = ws.x;
-                ra.partial = ws.mlp_partial; ra.ln_g = w.ln2_g; ra.ln_b = w.ln2_b; ra.h_out = (bf16_t*)h;
-                rowlin_plan(B, m->N, m->extras, L, D, ra);
-                if (int rc = mark(DD_PROF_ROWLIN)) return rc;
-                DD_HIP(c, launch_rowlin(ra, s));
-                if (int rc = mark(DD_PROF_ROWLIN)) return rc;
-                MlpFusedArgs fr{};
-                fr.b2 = w.proj_b; fr.xres = ws.x; fr.partial = ws.mlp_partial; fr.ldo = D;
-                fr.tok_n = ra.tok_n; fr.tok_e = ra.tok_e; fr.tok_l = ra.tok_l; fr.n_extra = ra.n_extra; fr.tiles_left = ra.tiles_extra;
-                fr.groups = ra.groups; fr.prows = 128;
-                fr.ln_out_g = w.ln2_g; fr.ln_out_b = w.ln2_b; fr.ln_out = (bf16_t*)h;
-                DD_HIP(c, launch_mlp_reduce(fr, D, s));
-                ln2_done = true;
-            }
-        }
-        if constexpr (sizeof(T) == 2) {
-            if (m->splitk && !ln2_done) {     // attn.proj as split-K halves; x += bias + slabs and norm2 in the row pass behind it
-                GemmArgs<T> g{ao, nullptr, (const T*)w.proj_w, nullptr, nullptr, nullptr, M, D, D, D, D, 0, D};
-                g.partial = ws.mlp_partial; g.splits = 2;
-                if (int rc = mark(DD_PROF_SPLITK)) return rc;
-                DD_HIP(c, launch_gemm_splitk(g, s, ch.cus));
-                if (int rc = mark(DD_PROF_SPLITK)) return rc;
-                ReduceLnArgs ra{ws.x, ws.mlp_partial, (long long)M * D, 2, 1, w.proj_b, nullptr, D, w.ln2_g, w.ln2_b, (bf16_t*)h, nullptr, L, m->extras, M};
-                DD_HIP(c, launch_reduce_ln(ra, D, s));
-                ln2_done = true;
-            }
-        }
-        if (!ln2_done && !(sizeof(T) == 2 && m->fused_proj)) {   // fused: x += proj(ao) + b happens inside the fused MLP launch below
-            GemmArgs<T> g{ao, nullptr, (const T*)w.proj_w, w.proj_b, ws.x, nullptr, M, D, D, D, D, 0, D};
-            g.tile128 = tile128(D, D, D);
-            DD_HIP(c, launch_gemm<T>(g, EPI_BIAS_RESID, s, ch.cus));
-        }
-        if (!ln2_done && !(sizeof(T) == 2 && m->fused_mlp)) DD_HIP(c, launch_layernorm<T>(ws.x, w.ln2_g, w.ln2_b, h, M, D, s));   // fused MLP: norm2 in its prologue
-        // the T-typed copy of the block output feeds a later skip_linear: as the `skip`
-        // operand (in-blocks) or as the `x` operand (mid / out blocks, except the last)
-        T* copy = is_in ? (T*)ws.skips[bi] : (bi + 1 < nb ? xb : nullptr);
-        if constexpr (sizeof(T) == 2) {
-            if (m->fused_mlp) {
-                MlpFusedArgs fa{};
-                fa.X = nullptr; fa.ldx = D; fa.wimg = w.mlp_img; fa.b1p = w.mlp_b1p; fa.b2 = w.fc2_b;
-                fa.ln_in_g = w.ln2_g; fa.ln_in_b = w.ln2_b;                       // norm2 of this block, in the prologue
-                if (bi + 1 < nb && bi + 1 <= m->half_depth) {                    // next block starts with norm1 (no skip_linear in between)
-                    fa.ln_out_g = m->blocks[bi + 1].ln1_g; fa.ln_out_b = m->blocks[bi + 1].ln1_b; fa.ln_out = (bf16_t*)h;
-                    h_ready = true;
-                }
-                fa.xres = ws.x; fa.out = (bf16_t*)copy; fa.ldo = D; fa.partial = ws.mlp_partial;
-                if (m->fused_proj) { fa.ao = (const bf16_t*)ao; fa.bproj = w.proj_b; fa.nproj = D / 32; }
-                const bool skip_next = m->fused_skip && bi >= m->half_depth && bi + 1 < nb;   // the next block starts with skip_linear
-                if (skip_next) {
-                    const BlockW& wn = m->blocks[bi + 1];
-                    const int oi = bi - m->half_depth;                                // index of the NEXT block among the out-blocks
-                    fa.skip = (const bf16_t*)ws.skips[m->half_depth - 1 - oi];      // LIFO (uvit.py:374-375)
-                    if (ee) fa.y_tap = ws.ytap;                                       // the next block's head / probe read y, which this launch consumes
-                    fa.bskip = wn.skip_b; fa.nskip = D / 16;
-                    fa.ln_out_g = wn.ln1_g; fa.ln_out_b = wn.ln1_b; fa.ln_out = (bf16_t*)h;
-                    h_ready = true; skip_done = true;
-                }
-                // the next block's attn.qkv last of all (where that block's skip_linear, if it has one, runs in here as well)
-                // the next block's attn.qkv: inside its attention launch (fused_qa), else last of all in this launch (fused_qkv) --
-                // wherever this launch leaves that block's norm1
-                const bool h_next = bi + 1 < nb && (bi < m->half_depth || skip_next);
-                const bool qa_next = m->fused_qa && h_next;
-                const bool qkv_next = !qa_next && m->fused_qkv && h_next;
-                if (qa_next) fa.ln_out_frag = ws.hfrag;      // the patch rows' norm1 in the order the attention launch loads it
-                if (qkv_next) {
-                    const BlockW& wn = m->blocks[bi + 1];
-                    fa.ln_out_g = wn.ln1_g; fa.ln_out_b = wn.ln1_b; fa.ln_out = (bf16_t*)h;   // (written for the extra-token rows only)
-                    fa.qkv_out = (bf16_t*)qkv; fa.qkv_dump = ws.qkv_dump; fa.hm = make_head_major(L, m->H); fa.nqkv = 3 * D / 32;
-                    h_ready = true; qkv_done = true;
-                }
-                mlp_fused_plan(B, m->N, m->extras, L, m->hidden, fa);
-                // The LAST block's projection / MLP of the extra-token rows feed nothing: the output head decodes the patch rows only
-                // (models/uvit.py:377-380 slices the extras off), and those rows' K / V went into this block's attention before.  No
-                // proj_rows / hidden-split workgroups / reduce launch for them.
-                if (bi + 1 == nb && m->fused_proj) { fa.n_extra = 0; fa.tiles_left = 0; }
-                if (m->fused_proj) fa.reduce_set = 1;   // the extra-token rows' projection runs in their hidden-split workgroups: the first group's slab carries x + proj(ao) + b
-                if (int rc = mark(DD_PROF_BLOCK_TAIL)) return rc;
-                DD_HIP(c, launch_mlp_fused(fa, D, s));
-                if (int rc = mark(DD_PROF_BLOCK_TAIL)) return rc;              // (the event pair brackets the fused kernel alone)
-                if (skip_next) {
-                    MlpFusedArgs fr = fa;                    // the reduce kernel finishes y of the extra-token rows (fp32 + the bf16
-                    fr.ln_out = nullptr;                     // copy in xb); their skip_linear + norm1 follow in one small launch
-                    DD_HIP(c, launch_mlp_reduce(fr, D, s));
-                    // (fused_qa: the attention launch normalises the extra-token rows itself, so the launch is split by columns)
-                    DD_HIP(c, launch_skip_rows_ln(fa, D, s, !qa_next));
-                } else if (qa_next) {
-                    MlpFusedArgs fr = fa;
-                    fr.ln_out = nullptr;                     // (ditto: no norm1 rows needed)
-                    DD_HIP(c, launch_mlp_reduce(fr, D, s));
-                } else {
-                    DD_HIP(c, launch_mlp_reduce(fa, D, s));
-                }
-                if (qkv_next) DD_HIP(c, launch_qkv_rows(fa, D, s));   // the extra-token rows' qkv, from the norm1 rows the launch above wrote
-                qa_ready = qa_next;    // (the extra-token rows reach the attention launch through the residual stream x)
-                continue;
-            }
-        }
-        {
-            GemmArgs<T> g{h, nullptr, (const T*)w.fc1_w, w.fc1_b, nullptr, hid, M, m->hidden, D, D, D, 0, m->hid_ld};
-            g.tile128 = tile128(m->hidden, D, D);
-            if (int rc = mark(DD_PROF_FC1)) return rc;
-            DD_HIP(c, launch_gemm<T>(g, EPI_BIAS_GELU, s, ch.cus));
-            if (int rc = mark(DD_PROF_FC1)) return rc;
-        }
-        if constexpr (sizeof(T) == 2) {
-            if (m->rowlin_fc2) {
-                // x += fc2(hid) + b with each wave's 32 residual rows resident in registers; where the next block starts with norm1 (in- and
-                // mid-blocks) that LayerNorm leaves from the same registers -- in the attention launch's fragment order under fused_qa
-                RowLinArgs ra{};
-                ra.A = (const bf16_t*)hid; ra.lda = m->hid_ld; ra.K = m->hidden; ra.wimg = w.rl_img; ra.bias = w.fc2_b; ra.xres = ws.x;
-                ra.x_copy = (bf16_t*)copy; ra.partial = ws.mlp_partial;
-                const bool ln_next = bi + 1 < nb && bi + 1 <= m->half_depth;
-                if (ln_next) {
-                    ra.ln_g = m->blocks[bi + 1].ln1_g; ra.ln_b = m->blocks[bi + 1].ln1_b;
-                    if (m->fused_qa) ra.h_frag = ws.hfrag; else ra.h_out = (bf16_t*)h;
-                }
-                rowlin_plan(B, m->N, m->extras, L, m->hidden, ra);
-                if (int rc = mark(DD_PROF_ROWLIN)) return rc;
-                DD_HIP(c, launch_rowlin(ra, s));
-                if (int rc = mark(DD_PROF_ROWLIN)) return rc;
-                MlpFusedArgs fr{};           // the extra-token rows: bias + residual + the K-split slabs in a fixed order (+ their norm1 rows)
-                fr.b2 = w.fc2_b; fr.xres = ws.x; fr.out = (bf16_t*)copy; fr.ldo = D; fr.partial = ws.mlp_partial;
-                fr.tok_n = ra.tok_n; fr.tok_e = ra.tok_e; fr.tok_l = ra.tok_l; fr.n_extra = ra.n_extra; fr.tiles_left = ra.tiles_extra;
-                fr.groups = ra.groups; fr.prows = 128;
-                if (ln_next && !m->fused_qa) { fr.ln_out_g = ra.ln_g; fr.ln_out_b = ra.ln_b; fr.ln_out = (bf16_t*)h; }
-                DD_HIP(c, launch_mlp_reduce(fr, D, s));
-                h_ready = ln_next;
-                qa_ready = ln_next && m->fused_qa;    // (the extra-token rows reach the attention launch through the residual stream x)
-                continue;
-            }
-        }
-        if constexpr (sizeof(T) == 2) {
-            if (m->splitk) {     // mlp.fc2 as split-K halves; x += bias + slabs, the bf16 copy and (in- / mid-blocks) the next block's norm1 in the row pass
-                GemmArgs<T> g{hid, nullptr, (const T*)w.fc2_w, nullptr, nullptr, nullptr, M, D, m->hidden, m->hidden, m->hid_ld, m->hid_ld, D};
-                g.partial = ws.mlp_partial; g.splits = 2;
-                if (int rc = mark(DD_PROF_SPLITK)) return rc;
-                DD_HIP(c, launch_gemm_splitk(g, s, ch.cus));
-                if (int rc = mark(DD_PROF_SPLITK)) return rc;
-                const bool ln_next = bi + 1 < nb && bi + 1 <= m->half_depth;
-                ReduceLnArgs ra{ws.x, ws.mlp_partial, (long long)M * D, 2, 1, w.fc2_b, (bf16_t*)copy, D,
-                                ln_next ? m->blocks[bi + 1].ln1_g : nullptr, ln_next ? m->blocks[bi + 1].ln1_b : nullptr, (bf16_t*)h,
-                                ln_next && m->fused_qa ? ws.hfrag : nullptr, L, m->extras, M};
-                DD_HIP(c, launch_reduce_ln(ra, D, s));
-                h_ready = ln_next;
-                qa_ready = ln_next && m->fused_qa;
-                continue;
-            }
-        }
-        {
-            GemmArgs<T> g{hid, nullptr, (const T*)w.fc2_w, w.fc2_b, ws.x, copy, M, D, m->hidden, m->hidden,
-                          m->hid_ld, m->hid_ld, D};
-            g.tile128 = tile128(D, m->hidden, m->hidden);
-            DD_HIP(c, launch_gemm<T>(g, EPI_BIAS_RESID, s, ch.cus));
-        }
+        DD_TIMED(DD_PROF_QKV_ATTENTION, launch_attention<T>(qkv, ao, B, L, m->H, D, s));
+        return DD_OK;
     }
-    if (ee_dec_all) {     // every layer's unpatchify + conv in one launch (layer i: images [i B, (i + 1) B) of nb B, its own conv weights), every MLP probe's mean in one
-        const long long chw = (long long)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
+
+    // x += attn.proj(ao) + b, then norm2 into h -- both in the fused block tail where the model has it (fused_proj; fused_mlp: norm2)
+    int proj(int bi) {
+        const BlockW& w = m->blocks[bi];
+        GemmArgs<T> g{ao, nullptr, (const T*)w.proj_w, w.proj_b, ws.x, nullptr, M, D, D, D, D, 0, D};
+        g.tile128 = tile128(D, D, D);
+        if constexpr (bf16) {
+            if (m->rowlin_proj) return rowlin_then_reduce(g, 1, w.rlp_img, w.ln2_g, w.ln2_b, false);
+            if (m->splitk) return splitk_then_reduce_ln(g, 1, w.ln2_g, w.ln2_b, false);
+            if (m->fused_proj) return DD_OK;
+        }
+        DD_HIP(c, launch_gemm<T>(g, EPI_BIAS_RESID, s, ch.cus));
+        if (!(bf16 && m->fused_mlp)) DD_HIP(c, launch_layernorm<T>(ws.x, w.ln2_g, w.ln2_b, h, M, D, s));   // fused MLP: norm2 in its prologue
+        return DD_OK;
+    }
+
+    // x += mlp.fc2(gelu(mlp.fc1(norm2))) + b and the T-typed copy of the block output, which feeds a later skip_linear: as the `skip` operand
+    // (in-blocks) or as the `x` operand (mid / out blocks, except the last).  Leaves `next`: what the next block finds done.
+    int mlp(int bi, Handoff& next) {
+        const BlockW& w = m->blocks[bi];
+        const bool is_in = bi < m->half_depth;   // the next block starts with norm1 (no skip_linear in between)
+        const BlockW* wn = bi + 1 < nb ? &m->blocks[bi + 1] : nullptr;
+        T* copy = is_in ? (T*)ws.skips[bi] : (wn ? xb : nullptr);
+        next = Handoff{};
+        if constexpr (bf16) {
+            if (m->fused_mlp) return block_tail(bi, copy, next);
+        }
+        GemmArgs<T> g1{h, nullptr, (const T*)w.fc1_w, w.fc1_b, nullptr, hid, M, m->hidden, D, D, D, 0, m->hid_ld};
+        g1.tile128 = tile128(m->hidden, D, D);
+        DD_TIMED(DD_PROF_FC1, launch_gemm<T>(g1, EPI_BIAS_GELU, s, ch.cus));
+        GemmArgs<T> g{hid, nullptr, (const T*)w.fc2_w, w.fc2_b, ws.x, copy, M, D, m->hidden, m->hidden, m->hid_ld, m->hid_ld, D};
+        g.tile128 = tile128(D, m->hidden, m->hidden);
+        if constexpr (bf16) {   // (the row passes write the next block's norm1 where it starts with one)
+            const float *ln_g = is_in ? wn->ln1_g : nullptr, *ln_b = is_in ? wn->ln1_b : nullptr;
+            if (is_in && (m->rowlin_fc2 || m->splitk)) next = norm1_written();
+            if (m->rowlin_fc2) return rowlin_then_reduce(g, 1, w.rl_img, ln_g, ln_b, m->fused_qa);
+            if (m->splitk) return splitk_then_reduce_ln(g, 1, ln_g, ln_b, m->fused_qa);
+        }
+        DD_HIP(c, launch_gemm<T>(g, EPI_BIAS_RESID, s, ch.cus));
+        return DD_OK;
+    }
+
+    // (bf16) the fused block tail: [attn.proj +] norm2 + the MLP in one launch (mlp_fused.hip), with whatever the next block starts with
+    // behind it -- its norm1; its skip_linear first (fused_skip); its attn.qkv last (fused_qkv), unless its attention launch computes that (fused_qa)
+    int block_tail(int bi, T* copy, Handoff& next) {
+        const BlockW& w = m->blocks[bi];
+        MlpFusedArgs fa{};
+        fa.X = nullptr; fa.ldx = D; fa.wimg = w.mlp_img; fa.b1p = w.mlp_b1p; fa.b2 = w.fc2_b;
+        fa.ln_in_g = w.ln2_g; fa.ln_in_b = w.ln2_b;                       // norm2 of this block, in the prologue
+        fa.xres = ws.x; fa.out = (bf16_t*)copy; fa.ldo = D; fa.partial = ws.mlp_partial;
+        if (m->fused_proj) { fa.ao = (const bf16_t*)ao; fa.bproj = w.proj_b; fa.nproj = D / 32; }
+        next.skip = m->fused_skip && bi >= m->half_depth && bi + 1 < nb;   // the next block starts with skip_linear
+        if (next.skip) {
+            fa.skip = (const bf16_t*)skip_of(bi + 1);
+            if (ee) fa.y_tap = ws.ytap;                                       // the next block's head / probe read y, which this launch consumes
+            fa.bskip = m->blocks[bi + 1].skip_b; fa.nskip = D / 16;
+        }
+        // the next block's norm1 where it starts with one (behind its skip_linear, if this launch runs that); its attn.qkv inside its attention
+        // launch (fused_qa), else last of all in this launch (fused_qkv) -- wherever this launch leaves that block's norm1
+        const bool h_next = bi < m->half_depth || next.skip;
+        next.frag = m->fused_qa && h_next;
+        next.qkv = !next.frag && m->fused_qkv && h_next;
+        next.h = h_next && !next.frag && !next.qkv;
+        if (h_next) { fa.ln_out_g = m->blocks[bi + 1].ln1_g; fa.ln_out_b = m->blocks[bi + 1].ln1_b; fa.ln_out = (bf16_t*)h; }
+        if (next.frag) fa.ln_out_frag = ws.hfrag;      // the patch rows' norm1 in the order the attention launch loads it
+        if (next.qkv) { fa.qkv_out = (bf16_t*)qkv; fa.qkv_dump = ws.qkv_dump; fa.hm = make_head_major(L, m->H); fa.nqkv = 3 * D / 32; }   // (norm1: the extra-token rows only)
+        mlp_fused_plan(B, m->N, m->extras, L, m->hidden, fa);
+        // The LAST block's projection / MLP of the extra-token rows feed nothing: the output head decodes the patch rows only
+        // (models/uvit.py:377-380 slices the extras off), and those rows' K / V went into this block's attention before.  No
+        // proj_rows / hidden-split workgroups / reduce launch for them.
+        if (bi + 1 == nb && m->fused_proj) { fa.n_extra = 0; fa.tiles_left = 0; }
+        if (m->fused_proj) fa.reduce_set = 1;   // the extra-token rows' projection runs in their hidden-split workgroups: the first group's slab carries x + proj(ao) + b
+        DD_TIMED(DD_PROF_BLOCK_TAIL, launch_mlp_fused(fa, D, s));   // (the event pair brackets the fused kernel alone)
+        // the reduce kernel finishes the extra-token rows (y in fp32 + the bf16 copy in xb); their skip_linear + norm1 follow in one small launch
+        // (fused_qa: the attention launch normalises the extra-token rows itself, so no norm1 rows, and that launch is split by columns)
+        MlpFusedArgs fr = fa;
+        if (next.skip || next.frag) fr.ln_out = nullptr;
+        DD_HIP(c, launch_mlp_reduce(fr, D, s));
+        if (next.skip) DD_HIP(c, launch_skip_rows_ln(fa, D, s, !next.frag));
+        if (next.qkv) DD_HIP(c, launch_qkv_rows(fa, D, s));   // the extra-token rows' qkv, from the norm1 rows the launch above wrote
+        return DD_OK;
+    }
+
+    // every layer's unpatchify + conv in one launch (layer i: images [i B, (i + 1) B) of nb B, its own conv weights), every MLP probe's mean in one
+    int ee_finish() {
+        if (!ee_dec_all) return DD_OK;
         FinalArgs fa{ee_dec_all, m->heads[0].wconv, m->heads[0].bconv, nullptr, nullptr, ee->outs, nullptr, ch.st,
-                     c->coef, nb * B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, DD_NOISE_NONE, 0, 0};
+                     c->coef, nb * B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, L, m->extras, DD_NOISE_NONE, 0, 0};
         fa.layer_B = B; fa.w_stride = m->ee_wconv_stride; fa.b_stride = m->ee_bconv_stride;
         DD_HIP(c, launch_final(fa, s));
         if (m->ee_type != DD_EE_ATTENTION_PROBE) DD_HIP(c, launch_ee_probe_reduce(ee_srow_all, ee->cls, nb * B, L, s));
-        (void)chw;
+        return DD_OK;
     }
+
     // output head (uvit.py:377-378): final LayerNorm in fp32 into scratch (the MLP hidden buffer is
     // free here), then decoder_pred as an exact-fp32 MFMA GEMM in BOTH precision modes, so eps is
     // never rounded to bf16.  dec holds all L tokens per image; the extras are skipped downstream.
-    if (m->wdec_g) {   // fused: rows read once, normalised rows never written
-        HeadDecArgs ha{ws.x, m->wdec_g, m->dec_c, ws.dec, M, m->pd, (L - m->extras) % 16 == 0 ? L : 0, m->extras};   // (only the patch rows)
-        DD_HIP(c, launch_head_dec(ha, D, ch.cus, s));
+    int head() {
+        if (m->wdec_g) {   // fused: rows read once, normalised rows never written
+            HeadDecArgs ha{ws.x, m->wdec_g, m->dec_c, ws.dec, M, m->pd, (L - m->extras) % 16 == 0 ? L : 0, m->extras};   // (only the patch rows)
+            DD_HIP(c, launch_head_dec(ha, D, ch.cus, s));
+            return DD_OK;
+        }
+        float* hf = (float*)ws.hid;
+        DD_HIP(c, launch_layernorm<float>(ws.x, m->norm_g, m->norm_b, hf, M, D, s));
+        GemmArgs<float> g{hf, nullptr, m->wdec, m->bdec, ws.dec, nullptr, M, m->pd, D, D, D, 0, m->pd};
+        DD_HIP(c, launch_gemm<float>(g, EPI_BIAS_SET, s, ch.cus));
         return DD_OK;
     }
-    float* hf = (float*)ws.hid;
-    DD_HIP(c, launch_layernorm<float>(ws.x, m->norm_g, m->norm_b, hf, M, D, s));
-    GemmArgs<float> g{hf, nullptr, m->wdec, m->bdec, ws.dec, nullptr, M, m->pd, D, D, D, 0, m->pd};
-    DD_HIP(c, launch_gemm<float>(g, EPI_BIAS_SET, s, ch.cus));
-    return DD_OK;
+#undef DD_TIMED
+};
+
+template <typename T>
+int run_backbone(dd_model* m, const Chain& ch, const float* x_img, const float* t_vec, const int64_t* y_dev, int B, hipStream_t s,
+                 const EeTaps* ee = nullptr) {
+    Backbone<T> f{m, ch, B, s, ee};
+    Handoff hand;
+    if (int rc = f.embed(x_img, t_vec, y_dev, hand)) return rc;
+    for (int bi = 0; bi < f.nb; ++bi) {
+        bool side = false;   // this block's early-exit head / probe launches are in flight on the side stream
+        if (int rc = f.ee_taps(bi, hand, side)) return rc;
+        if (int rc = f.skip_linear(bi, hand)) return rc;
+        if (int rc = f.norm1_attention(bi, hand)) return rc;
+        if (side) DD_HIP(m->ctx, hipStreamWaitEvent(s, m->ctx->ev_ee_join, 0));   // the head / probe launches have read x: from here on the block updates it
+        if (int rc = f.proj(bi)) return rc;
+        if (int rc = f.mlp(bi, hand)) return rc;
+    }
+    if (int rc = f.ee_finish()) return rc;
+    return f.head();
 }
 
 int run_model(dd_model* m, const Chain& ch, const float* x_img, const float* t_vec, const int64_t* y_dev, int B, hipStream_t s,
@@ -1574,6 +1540,13 @@ int dd_model_finalize(dd_model* m, int precision) {
         for (size_t i = 0; i < m->heads.size(); ++i)
             if (m->heads[i].wconv != m->heads[0].wconv + (long long)i * m->ee_wconv_stride || m->heads[i].bconv != m->heads[0].bconv + (long long)i * m->ee_bconv_stride) m->ee_conv_stride_ok = false;
     }
+    // the batched early-exit heads need nb B L (pd + 1) floats of the MLP hidden buffer: decided here for both chain workspaces (the need
+    // grows linearly in B, so it then fits every call) and never from a call's B, so that an image's probe value does not depend on its batch
+    auto ee_fits = [&](int b) {
+        return m->blocks.size() * b * L * (m->pd + 1) * sizeof(float) <= (size_t)round_up(b * L, 256) * m->hid_ld * m->esize;
+    };
+    m->ee_batched = m->ee_type >= 0 && precision == DD_PREC_BF16 && m->fused_mlp && m->ee_conv_stride_ok && m->heads[0].wg &&
+                    m->cfg.img_size >= 16 && ee_fits(m->cfg.max_batch) && ee_fits((m->cfg.max_batch + 1) / 2);
     if (m->ee_type >= 0 && m->ee_type != DD_EE_ATTENTION_PROBE) { m->probe_w = F(o_pw); m->probe_b = F(o_pb); }
     for (const AttnProbeOff& o : aoffs) m->attn_probes.push_back(AttnProbeW{F(o.u), F(o.wvt), F(o.bv), F(o.w0t), F(o.b0), F(o.w2), F(o.b2)});
     if (fused_head) { m->wdec_g = F(o_wg); m->dec_c = F(o_dc); }
@@ -2054,16 +2027,16 @@ int dd_dev_mlp(dd_ctx* c, int M, int D, int hidden, int extras, const float* x_h
     }
     a.X = (const bf16_t*)dX; a.ldx = D; a.wimg = (const char*)dI; a.b1p = (const float*)dB1; a.b2 = (const float*)dB2;
     a.xres = (float*)dXr; a.out = out_host ? (bf16_t*)dO : nullptr; a.ldo = D; a.partial = (float*)dP;
-    if (proj) {   // as run_backbone does it: patch rows in the main tiles, extra-token rows in their hidden-split workgroups
+    if (proj) {   // as Backbone::block_tail does it: patch rows in the main tiles, extra-token rows in their hidden-split workgroups
         std::vector<unsigned short> ah(Mp * D, 0);
         for (size_t i = 0; i < (size_t)M * D; ++i) ah[i] = host_f2bf(ao_host[i]);
         DD_TRY(hipMalloc(&dAo, ah.size() * 2)); DD_TRY(hipMalloc(&dBp, D * 4));
         DD_TRY(hipMemcpy(dAo, ah.data(), ah.size() * 2, hipMemcpyHostToDevice));
         DD_TRY(hipMemcpy(dBp, bproj, D * 4, hipMemcpyHostToDevice));
         a.ao = (const bf16_t*)dAo; a.bproj = (const float*)dBp; a.nproj = D / 32;
-        a.reduce_set = 1;        // (the extra-token rows' projection runs in their hidden-split workgroups, run_backbone)
+        a.reduce_set = 1;        // (the extra-token rows' projection runs in their hidden-split workgroups, Backbone::block_tail)
     }
-    MlpFusedArgs ar = a;       // (what the reduce launch gets: see run_backbone)
+    MlpFusedArgs ar = a;       // (what the reduce launch gets: see Backbone::block_tail)
     if (skp) {
         std::vector<unsigned short> sh(Mp * D, 0);
         for (size_t i = 0; i < (size_t)M * D; ++i) sh[i] = host_f2bf(skip_host[i]);

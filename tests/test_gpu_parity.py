@@ -628,8 +628,8 @@ def test_fused_branches_at_small_widths_vs_oracle(D, H, num_classes):
 
 @pytest.mark.parametrize("flags", [32, 64, 128, 32 | 128, 64 | 128, 1, 2, 4])
 def test_kernel_variant_flags_agree_with_the_default_path(flags):
-    """Every dd_dev_set_flags setting selects another launch sequence for the same arithmetic (run_backbone's h_ready /
-    skip_done / qkv_done / qa_ready state machine): on a 5-block class-conditional model at embed_dim 512 each variant must
+    """Every dd_dev_set_flags setting selects another launch sequence for the same arithmetic (what the Handoff record passes
+    from one block stage to the next in run_backbone): on a 5-block class-conditional model at embed_dim 512 each variant must
     stay within bf16 rounding of the oracle, like the default path (32 = no fused skip_linear, 64 = no qkv in the block tail,
     128 = no qkv inside the attention launch -> the QKV instantiation / the qkv GEMM, and their combinations)."""
     from duodiff_amd.engine import Context

@@ -534,7 +534,7 @@ __global__ void __launch_bounds__(512, 1) qkv_attention_kernel(const QkvAttnArgs
             const int pc = wave * 2 + i;
             const char* sb = wsrc + (size_t)bb * kQaBlk + pc * 1024;
             const unsigned lds = lds_addr_of(ring + (bb & 3) * kQaBlk + pc * 1024);
-            asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(lane16), "s"(sb) : "memory", "m0");
+            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(lane16), "s"(sb) : "memory", "m0");
         }
     };
     dma_block(0);

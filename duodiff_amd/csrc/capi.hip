@@ -473,6 +473,40 @@ WsOffsets ws_layout(const dd_model* m, int batch) {
     o.tap = o_tap; o.has_tap = has_tap;
     return o;
 }
+// Argument filling of the two row-pass variants of an N = D Linear g (Backbone::rowlin_then_reduce / splitk_then_reduce_ln, dd_dev_rowlin /
+// dd_dev_gemm): pure functions of the Linear, so that the development entry points launch exactly what the model launches.
+// (embed_dim 768) the row-resident launch: x = [x +] g + bias (resid), g's bf16 copy, LayerNorm ln_g / ln_b of the updated rows into h_out
+// (row-major) or h_frag (the patch rows in fragment order); rows planned as B images of n_patches patch tokens behind `extras` extra tokens, or
+// (n_patches == 0) the plain mode: rows [0, g.M) in tiles of 128
+RowLinArgs rowlin_args(const GemmArgs<bf16_t>& g, int resid, const char* wimg, float* partial, const float* ln_g, const float* ln_b,
+                       bf16_t* h_out, bf16_t* h_frag, int B, int n_patches, int extras) {
+    RowLinArgs ra{};
+    ra.A = g.A; ra.A2 = g.A2; ra.k_split = g.A2 ? g.K1 : 0; ra.set_x = !resid; ra.lda = g.lda; ra.K = g.K;
+    ra.wimg = wimg; ra.bias = g.bias; ra.xres = g.xres; ra.x_copy = g.out; ra.partial = partial;
+    if (ln_g) {
+        ra.ln_g = ln_g; ra.ln_b = ln_b;
+        if (h_frag) ra.h_frag = h_frag; else ra.h_out = h_out;
+    }
+    if (n_patches > 0) rowlin_plan(B, n_patches, extras, n_patches + extras, ra.K, ra);
+    else ra.M = g.M;
+    return ra;
+}
+// ... and the launch that finishes its extra-token rows from the K-split slabs (launch_mlp_reduce)
+MlpFusedArgs rowlin_reduce_args(const RowLinArgs& ra) {
+    MlpFusedArgs fr{};
+    fr.b2 = ra.bias; fr.xres = ra.xres; fr.partial = ra.partial; fr.out = ra.x_copy; fr.ldo = 768; fr.reduce_set = ra.set_x;
+    fr.tok_n = ra.tok_n; fr.tok_e = ra.tok_e; fr.tok_l = ra.tok_l; fr.n_extra = ra.n_extra; fr.tiles_left = ra.tiles_extra;
+    fr.groups = ra.groups; fr.prows = 128;
+    if (ra.h_out) { fr.ln_out_g = ra.ln_g; fr.ln_out_b = ra.ln_b; fr.ln_out = ra.h_out; }
+    return fr;
+}
+// the row pass behind a split-K launch of g (g.partial / g.splits): the slabs added in ascending order + bias [+ x], g's bf16 copy, LayerNorm into
+// h -- with frag, the patch rows of the tok_l-token images into frag and only the extra-token rows into h
+ReduceLnArgs splitk_reduce_args(const GemmArgs<bf16_t>& g, int resid, const float* ln_g, const float* ln_b, bf16_t* h, bf16_t* frag, int tok_l, int tok_e) {
+    return ReduceLnArgs{g.xres, g.partial, (long long)g.M * g.N, g.splits, resid, g.bias, g.out, g.ldo, ln_g, ln_b, h, ln_g ? frag : nullptr,
+                        tok_l, tok_e, g.M};
+}
+
 // What a step runs on: the launch sequence of a step is enqueued / captured for either half-batch chain by the same code, on the same
 // weights, with the chain's own workspace and step state.  cus: the CU count its persistent GEMM grids are sized for (halved for both
 // chains of a large GEMM-path batch, chain_gemm_cus); ee_fork: early-exit heads / probes may fork onto the context's side stream (not
@@ -546,31 +580,18 @@ struct Backbone {
     // The two row-pass variants of an N = D Linear g (skip_linear, attn.proj, mlp.fc2): x = [x +] g + bias (resid), g's bf16 copy (g.out), and
     // LayerNorm ln_g / ln_b of the updated rows into h -- under frag the patch rows into hfrag instead, in the order the attention launch loads them.
     // (embed_dim 768) the row-resident launch (rowlin.hip: W image wimg), then the launch that finishes its extra-token rows from the K-split slabs
-    int rowlin_then_reduce(const GemmArgs<T>& g, int resid, const char* wimg, const float* ln_g, const float* ln_b, bool frag) {
-        RowLinArgs ra{};
-        ra.A = (const bf16_t*)g.A; ra.A2 = (const bf16_t*)g.A2; ra.k_split = g.A2 ? g.K1 : 0; ra.set_x = !resid; ra.lda = g.lda; ra.K = g.K;
-        ra.wimg = wimg; ra.bias = g.bias; ra.xres = ws.x; ra.x_copy = (bf16_t*)g.out; ra.partial = ws.mlp_partial;
-        if (ln_g) {
-            ra.ln_g = ln_g; ra.ln_b = ln_b;
-            if (frag) ra.h_frag = ws.hfrag; else ra.h_out = (bf16_t*)h;
-        }
-        rowlin_plan(B, m->N, m->extras, L, ra.K, ra);
+    // (g.xres is the residual stream ws.x; g.ldo = D)
+    int rowlin_then_reduce(const GemmArgs<bf16_t>& g, int resid, const char* wimg, const float* ln_g, const float* ln_b, bool frag) {
+        const RowLinArgs ra = rowlin_args(g, resid, wimg, ws.mlp_partial, ln_g, ln_b, (bf16_t*)h, frag ? ws.hfrag : nullptr, B, m->N, m->extras);
         DD_TIMED(DD_PROF_ROWLIN, launch_rowlin(ra, s));
-        MlpFusedArgs fr{};
-        fr.b2 = ra.bias; fr.xres = ws.x; fr.partial = ws.mlp_partial; fr.out = ra.x_copy; fr.ldo = D; fr.reduce_set = ra.set_x;
-        fr.tok_n = ra.tok_n; fr.tok_e = ra.tok_e; fr.tok_l = ra.tok_l; fr.n_extra = ra.n_extra; fr.tiles_left = ra.tiles_extra;
-        fr.groups = ra.groups; fr.prows = 128;
-        if (ra.h_out) { fr.ln_out_g = ra.ln_g; fr.ln_out_b = ra.ln_b; fr.ln_out = ra.h_out; }
-        DD_HIP(c, launch_mlp_reduce(fr, D, s));
+        DD_HIP(c, launch_mlp_reduce(rowlin_reduce_args(ra), D, s));
         return DD_OK;
     }
     // split-K halves into the slabs, then the row pass that adds them (reduce_ln; under frag the extra-token rows' LayerNorm still goes to h)
-    int splitk_then_reduce_ln(GemmArgs<T> g, int resid, const float* ln_g, const float* ln_b, bool frag) {
+    int splitk_then_reduce_ln(GemmArgs<bf16_t> g, int resid, const float* ln_g, const float* ln_b, bool frag) {
         g.partial = ws.mlp_partial; g.splits = 2;
         DD_TIMED(DD_PROF_SPLITK, launch_gemm_splitk(g, s, ch.cus));
-        ReduceLnArgs ra{ws.x, ws.mlp_partial, (long long)M * D, 2, resid, g.bias, (bf16_t*)g.out, D, ln_g, ln_b, (bf16_t*)h,
-                        ln_g && frag ? ws.hfrag : nullptr, L, m->extras, M};
-        DD_HIP(c, launch_reduce_ln(ra, D, s));
+        DD_HIP(c, launch_reduce_ln(splitk_reduce_args(g, resid, ln_g, ln_b, (bf16_t*)h, frag ? ws.hfrag : nullptr, L, m->extras), D, s));
         return DD_OK;
     }
 
@@ -2171,6 +2192,181 @@ int dd_dev_head_dec(dd_ctx* c, int M, int D, int pd, int tok_l, int tok_e, const
         DD_TRY(hipEventCreate(&e0)); DD_TRY(hipEventCreate(&e1));
         DD_TRY(hipEventRecord(e0, s));
         for (int i = 0; i < iters; ++i) DD_TRY(launch_head_dec(ha, D, c->num_cus, s));
+        DD_TRY(hipEventRecord(e1, s));
+        DD_TRY(hipEventSynchronize(e1));
+        float ms = 0.f;
+        DD_TRY(hipEventElapsedTime(&ms, e0, e1));
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        *ms_out = ms / (float)iters;
+    }
+#undef DD_TRY
+    cleanup();
+    return DD_OK;
+}
+
+int dd_dev_gemm(dd_ctx* c, int precision, int M, int N, int K, int K1, const float* A, const float* A2, const float* W, const float* bias,
+                int epilogue, int tile128, int hm_L, int hm_H, int splits, int resid, const float* ln, int tok_l, int tok_e,
+                float* xres_host, void* out_host, int ldo, unsigned short* h_host, unsigned short* frag_host, float* slab_host,
+                int num_cus, int iters, void* stream, float* ms_out) {
+    const bool bf = precision == DD_PREC_BF16;
+    if (K1 == 0) K1 = K;
+    const int KT = bf ? 64 : 32;
+    if (!c || (!bf && precision != DD_PREC_FP32) || M < 1 || N < 4 || N % 4 || K < KT || K % KT || K1 < KT || K1 > K || K1 % KT || !A || !W ||
+        (K1 < K && !A2) || ldo < N || ldo % (bf ? 8 : 4) || iters < 0 || num_cus < 0 || (num_cus > 0 && num_cus < 8) || tile128 < -1 || tile128 > 1)
+        return DD_ERR_INVALID;
+    if (splits > 0 && (!bf || splits < 2 || !bias || hm_L || (ln && !h_host) || (frag_host && (!ln || tok_l <= tok_e))))
+        return fail(c, DD_ERR_INVALID, "split-K: bf16, splits >= 2, bias, no head-major map; LayerNorm output needs h (and frag tok_l > tok_e)");
+    if (splits == 0 && (epilogue < EPI_STORE || epilogue > EPI_BIAS_STORE || ((epilogue == EPI_BIAS_RESID || epilogue == EPI_BIAS_SET) && !xres_host) ||
+                        (epilogue != EPI_STORE && !bias) || (hm_L && (hm_H < 1 || M % hm_L || !out_host))))
+        return DD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t esz = bf ? 2 : 4, Mo = (size_t)round_up(M, 256) + 8;
+    const HeadMajor hm = hm_L ? make_head_major(hm_L, hm_H) : HeadMajor{};
+    const size_t out_elems = hm_L ? ((size_t)(M / hm_L) * 3 * hm_H * hm.Lp + 64) * 64 : Mo * ldo;
+    const int lda = K1, lda2 = K - K1;
+    // operands as the kernel reads them: bf16 (or fp32) rows; A / A2 padded to Mo rows of 0xFF bytes (NaN: a row read past M shows up as one)
+    auto pack = [&](const float* src, size_t rows, size_t cols, size_t alloc_rows) {
+        std::vector<unsigned char> v(alloc_rows * cols * esz, 0xFF);
+        for (size_t i = 0; i < rows * cols; ++i) {
+            if (bf) { const unsigned short b = host_f2bf(src[i]); std::memcpy(&v[i * 2], &b, 2); }
+            else std::memcpy(&v[i * 4], &src[i], 4);
+        }
+        return v;
+    };
+    const std::vector<unsigned char> ha = pack(A, M, lda, Mo), hw = pack(W, N, K, N);
+    std::vector<unsigned char> ha2;
+    if (K1 < K) ha2 = pack(A2, M, lda2, Mo);
+    void *dA = nullptr, *dA2 = nullptr, *dW = nullptr, *dBias = nullptr, *dX = nullptr, *dO = nullptr, *dLn = nullptr, *dH = nullptr, *dF = nullptr, *dP = nullptr;
+    auto cleanup = [&]() { for (void* p : {dA, dA2, dW, dBias, dX, dO, dLn, dH, dF, dP}) if (p) (void)hipFree(p); };
+#define DD_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail_hip(c, e_, #x); } } while (0)
+    auto upload = [&](void** d, const void* h, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(d, bytes);
+        return e == hipSuccess ? hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice) : e;
+    };
+    auto canary = [&](void** d, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(d, bytes);
+        return e == hipSuccess ? hipMemset(*d, 0xFF, bytes) : e;
+    };
+    DD_TRY(upload(&dA, ha.data(), ha.size()));
+    if (K1 < K) DD_TRY(upload(&dA2, ha2.data(), ha2.size()));
+    DD_TRY(upload(&dW, hw.data(), hw.size()));
+    if (bias) DD_TRY(upload(&dBias, bias, (size_t)N * 4));
+    // every output buffer: canary bytes (0xFF) everywhere, or the caller's bytes (xres, canary rows included), returned whole
+    if (xres_host) DD_TRY(upload(&dX, xres_host, Mo * N * 4));
+    if (out_host) DD_TRY(canary(&dO, out_elems * esz));
+    const size_t slab_elems = (size_t)(splits > 0 ? splits : 0) * Mo * N;
+    if (splits > 0) {
+        if (!dX) DD_TRY(canary(&dX, Mo * N * 4));      // (resid == 0: x = the Linear; the caller may not want it back)
+        DD_TRY(canary(&dP, slab_elems * 4));
+        if (ln) DD_TRY(upload(&dLn, ln, (size_t)2 * N * 4));
+        if (h_host) DD_TRY(canary(&dH, Mo * N * 2));
+        if (frag_host) DD_TRY(canary(&dF, Mo * N * 2));
+    }
+    auto once = [&]() -> hipError_t {
+        if (!bf) {
+            GemmArgs<float> g{(const float*)dA, (const float*)dA2, (const float*)dW, (const float*)dBias, (float*)dX, (float*)dO, M, N, K, K1, lda,
+                              K1 < K ? lda2 : lda, ldo};
+            g.hm = hm;
+            return launch_gemm<float>(g, epilogue, s, num_cus ? num_cus : c->num_cus);
+        }
+        GemmArgs<bf16_t> g{(const bf16_t*)dA, (const bf16_t*)dA2, (const bf16_t*)dW, (const float*)dBias, (float*)dX, (bf16_t*)dO, M, N, K, K1, lda,
+                           K1 < K ? lda2 : lda, ldo};
+        g.hm = hm;
+        g.tile128 = tile128;
+        if (splits == 0) return launch_gemm<bf16_t>(g, epilogue, s, num_cus ? num_cus : c->num_cus);
+        g.partial = (float*)dP; g.splits = splits;
+        hipError_t e = launch_gemm_splitk(g, s, num_cus ? num_cus : c->num_cus);
+        if (e != hipSuccess) return e;
+        const float* lg = ln ? (const float*)dLn : nullptr;
+        return launch_reduce_ln(splitk_reduce_args(g, resid, lg, lg ? lg + N : nullptr, (bf16_t*)dH, (bf16_t*)dF, tok_l, tok_e), N, s);
+    };
+    DD_TRY(once());
+    DD_TRY(hipStreamSynchronize(s));
+    if (xres_host) DD_TRY(hipMemcpy(xres_host, dX, Mo * N * 4, hipMemcpyDeviceToHost));
+    if (out_host) DD_TRY(hipMemcpy(out_host, dO, out_elems * esz, hipMemcpyDeviceToHost));
+    if (h_host && dH) DD_TRY(hipMemcpy(h_host, dH, Mo * N * 2, hipMemcpyDeviceToHost));
+    if (frag_host && dF) DD_TRY(hipMemcpy(frag_host, dF, Mo * N * 2, hipMemcpyDeviceToHost));
+    if (slab_host && dP) DD_TRY(hipMemcpy(slab_host, dP, slab_elems * 4, hipMemcpyDeviceToHost));
+    if (iters > 0 && ms_out) {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        DD_TRY(hipEventCreate(&e0)); DD_TRY(hipEventCreate(&e1));
+        DD_TRY(hipEventRecord(e0, s));
+        for (int i = 0; i < iters; ++i) DD_TRY(once());
+        DD_TRY(hipEventRecord(e1, s));
+        DD_TRY(hipEventSynchronize(e1));
+        float ms = 0.f;
+        DD_TRY(hipEventElapsedTime(&ms, e0, e1));
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        *ms_out = ms / (float)iters;
+    }
+#undef DD_TRY
+    cleanup();
+    return DD_OK;
+}
+
+int dd_dev_rowlin(dd_ctx* c, int B, int n_patches, int extras, int K, int k_split, int set_x, const float* A, const float* A2, const float* W,
+                  const float* bias, const float* ln, float* xres_host, unsigned short* x_copy_host, unsigned short* h_host, int frag,
+                  int iters, void* stream, float* ms_out) {
+    constexpr int D = 768;
+    const bool planned = n_patches > 0;
+    if (!c || B < 1 || n_patches < 0 || extras < 0 || (!planned && extras) || !A || !W || !bias || !xres_host || iters < 0 ||
+        (k_split && (2 * k_split != K || !A2)) || (h_host && !ln))
+        return DD_ERR_INVALID;
+    if (!rowlin_supported(D, K)) return fail(c, DD_ERR_UNSUPPORTED, "rowlin: K % 64 == 0, K >= 192");
+    hipStream_t s = (hipStream_t)stream;
+    const int M = planned ? B * (n_patches + extras) : B;
+    const size_t Mo = (size_t)round_up(M, 256) + 8;
+    const int lda = k_split ? k_split : K;
+    auto pack = [&](const float* src, size_t cols) {
+        std::vector<unsigned short> v(Mo * cols, 0xFFFF);
+        for (size_t i = 0; i < (size_t)M * cols; ++i) v[i] = host_f2bf(src[i]);
+        return v;
+    };
+    const std::vector<unsigned short> ha = pack(A, lda);
+    std::vector<unsigned short> ha2, img((size_t)K * D);
+    if (k_split) ha2 = pack(A2, lda);
+    rowlin_pack(K, W, host_f2bf, img.data());      // as finalize packs the model's rowlin images
+    void *dA = nullptr, *dA2 = nullptr, *dW = nullptr, *dBias = nullptr, *dX = nullptr, *dC = nullptr, *dLn = nullptr, *dH = nullptr, *dP = nullptr;
+    auto cleanup = [&]() { for (void* p : {dA, dA2, dW, dBias, dX, dC, dLn, dH, dP}) if (p) (void)hipFree(p); };
+#define DD_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail_hip(c, e_, #x); } } while (0)
+    auto upload = [&](void** d, const void* h, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(d, bytes);
+        return e == hipSuccess ? hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice) : e;
+    };
+    auto canary = [&](void** d, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(d, bytes);
+        return e == hipSuccess ? hipMemset(*d, 0xFF, bytes) : e;
+    };
+    DD_TRY(upload(&dA, ha.data(), ha.size() * 2));
+    if (k_split) DD_TRY(upload(&dA2, ha2.data(), ha2.size() * 2));
+    DD_TRY(upload(&dW, img.data(), img.size() * 2));
+    DD_TRY(upload(&dBias, bias, (size_t)D * 4));
+    DD_TRY(upload(&dX, xres_host, Mo * D * 4));
+    if (x_copy_host) DD_TRY(canary(&dC, Mo * D * 2));
+    if (ln) DD_TRY(upload(&dLn, ln, (size_t)2 * D * 4));
+    if (h_host) DD_TRY(canary(&dH, Mo * D * 2));
+    const size_t part = planned ? rowlin_partial_bytes(B, extras, K) : 0;
+    if (part) DD_TRY(canary(&dP, part));
+    GemmArgs<bf16_t> g{(const bf16_t*)dA, (const bf16_t*)dA2, nullptr, (const float*)dBias, (float*)dX, (bf16_t*)dC, M, D, K, k_split ? k_split : K,
+                       lda, lda, D};
+    const float* lg = ln ? (const float*)dLn : nullptr;
+    const RowLinArgs ra = rowlin_args(g, !set_x, (const char*)dW, (float*)dP, lg, lg ? lg + D : nullptr, frag ? nullptr : (bf16_t*)dH,
+                                      frag ? (bf16_t*)dH : nullptr, B, n_patches, extras);
+    const MlpFusedArgs fr = rowlin_reduce_args(ra);
+    auto once = [&]() -> hipError_t {
+        hipError_t e = launch_rowlin(ra, s);
+        return e == hipSuccess ? launch_mlp_reduce(fr, D, s) : e;
+    };
+    DD_TRY(once());
+    DD_TRY(hipStreamSynchronize(s));
+    DD_TRY(hipMemcpy(xres_host, dX, Mo * D * 4, hipMemcpyDeviceToHost));
+    if (x_copy_host) DD_TRY(hipMemcpy(x_copy_host, dC, Mo * D * 2, hipMemcpyDeviceToHost));
+    if (h_host) DD_TRY(hipMemcpy(h_host, dH, Mo * D * 2, hipMemcpyDeviceToHost));
+    if (iters > 0 && ms_out) {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        DD_TRY(hipEventCreate(&e0)); DD_TRY(hipEventCreate(&e1));
+        DD_TRY(hipEventRecord(e0, s));
+        for (int i = 0; i < iters; ++i) DD_TRY(once());
         DD_TRY(hipEventRecord(e1, s));
         DD_TRY(hipEventSynchronize(e1));
         float ms = 0.f;

@@ -40,7 +40,7 @@ __device__ __forceinline__ unsigned rl_lds(const void* p) { return (unsigned)(si
 // one 1 KB LDS-DMA piece in the scalar-base form: uniform 64-bit base (SGPRs) + a 32-bit lane offset, M0 = the piece's LDS address.  Written as asm: the
 // builtin turns base + offset into a 64-bit VGPR address pair, and that form serialises with the SIMD's MFMAs (profiles/r05/dma_mfma_probe_roles.txt).
 __device__ __forceinline__ void rl_dma(const char* sbase, unsigned voff, const void* lds_dst) {
-    asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(rl_lds(lds_dst)), "v"(voff), "s"(sbase) : "memory", "m0");
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(rl_lds(lds_dst)), "v"(voff), "s"(sbase) : "memory", "m0");
 }
 template <int OFF>
 __device__ __forceinline__ void rl_read(bf16x8& d, unsigned addr) {

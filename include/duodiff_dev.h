@@ -49,6 +49,34 @@ int dd_dev_head_dec(dd_ctx* ctx, int M, int D, int pd, int tok_l, int tok_e, con
                     const float* wdec, const float* bdec, float* dec_host, const float* probe_w, const float* probe_b, float* srow_host,
                     int split, int iters, void* stream, float* ms_out);
 
+/* Development harness for the GEMM path (gemm.hip; what the model's Linears launch): C = [A | A2] . W^T from host arrays -- A [M, K1]
+ * (K1 = 0: K), A2 [M, K - K1] or NULL (K1 == K), W [N, K], bias [N] or NULL; precision DD_PREC_BF16 (operands rounded to bf16: the persistent
+ * 256 x 256 kernel where the shape fits it, else the 128 x 128 one; tile128 -1 / 0 / 1 as GemmArgs::tile128) or DD_PREC_FP32 (the exact-f32 parity
+ * kernels, 128 x 128 or, N <= 64, 128 x 64).  splits == 0: ONE launch_gemm with `epilogue` (dd_internal.h GemmEpilogue EPI_STORE .. EPI_BIAS_STORE),
+ * hm_L > 0: out is written head-major (HeadMajor: images of hm_L rows, hm_H heads, N = 192 hm_H).  splits >= 2 (bf16): the split-K launch into
+ * `splits` fp32 slabs, then the reduce_ln row pass (N = 256 .. 1024): x = [x +] sum of slabs + bias (resid), the bf16 copy into out, ln [2, N]
+ * (gamma, beta) or NULL: LayerNorm of the updated rows into h_host row-major -- frag_host non-NULL: the patch rows of the tok_l-token images
+ * (behind tok_e extra tokens) into frag_host in fragment order (MlpFusedArgs::ln_out_frag) and only the extra-token rows into h_host.
+ * Every output array has Mo = round_up(M, 256) + 8 rows and comes back WHOLE: xres_host [Mo, N] fp32 in / out (the caller's bytes go in, canary
+ * rows included); out_host [Mo, ldo] (bf16 bits or fp32), head-major [(M / hm_L) 3 hm_H Lp + 64][64]; h_host / frag_host [Mo, N] bf16;
+ * slab_host [splits, Mo, N] fp32 (the kernel's slabs are the first splits M N elements) -- filled with 0xFF bytes (NaN) before the launch.
+ * num_cus: the CU count the persistent grid is sized for (0: the context's).  `iters` timed launch sequences -> ms_out. */
+int dd_dev_gemm(dd_ctx* ctx, int precision, int M, int N, int K, int K1, const float* A, const float* A2, const float* W, const float* bias,
+                int epilogue, int tile128, int hm_L, int hm_H, int splits, int resid, const float* ln, int tok_l, int tok_e,
+                float* xres_host, void* out_host, int ldo, unsigned short* h_host, unsigned short* frag_host, float* slab_host,
+                int num_cus, int iters, void* stream, float* ms_out);
+
+/* Development harness for the row-resident Linear of embed_dim 768 (rowlin.hip rowlin768_kernel, then mlp_reduce_kernel for the K-split
+ * extra-token tiles), filled as the model fills them: x = [x +] [A | A2] . W^T + bias (set_x: no residual), W [768, K] packed here as finalize packs
+ * it, A [M, lda] / A2 [M, lda] with lda = k_split (k_split > 0: K = 2 k_split, A2 holds k >= k_split) or K.  Rows: B images of n_patches patch
+ * tokens behind `extras` extra tokens (M = B (n_patches + extras)), or n_patches == 0: the plain mode over M = B rows.  ln [2, 768] or NULL:
+ * LayerNorm of the updated rows into h_host -- row-major, or (frag != 0) the patch rows in fragment order (MlpFusedArgs::ln_out_frag; the extra-token
+ * rows' LayerNorm is then not written).  xres_host [Mo, 768] fp32 in / out, x_copy_host (bf16 copy of the updated rows) and h_host [Mo, 768] or
+ * NULL, Mo = round_up(M, 256) + 8, returned whole (canary bytes 0xFF before the launch).  `iters` timed launch pairs -> ms_out. */
+int dd_dev_rowlin(dd_ctx* ctx, int B, int n_patches, int extras, int K, int k_split, int set_x, const float* A, const float* A2, const float* W,
+                  const float* bias, const float* ln, float* xres_host, unsigned short* x_copy_host, unsigned short* h_host, int frag,
+                  int iters, void* stream, float* ms_out);
+
 /* Kernel-variant switches for same-process A/B runs (tools/mlp_check.py, tools/all_configs.py).  They act on models
  * FINALIZED after the call (the first three) or on launches made after it; the product never sets them and the library
  * reads no environment variable. */

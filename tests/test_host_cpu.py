@@ -252,3 +252,21 @@ def test_hand_counted_loads_of_the_output_head_are_never_touched_in_flight():
     r = subprocess.run([sys.executable, str(REPO / "tools" / "isa_audit_head.py")], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.count(": OK") == 32
+
+
+def test_every_lds_dma_request_has_a_wait_state_behind_its_m0_write():
+    """An LDS-DMA request takes its LDS destination from M0, and gfx950 needs one wait state between an SALU write of M0 and the request that
+    reads it; hipcc pads the sites it emits itself but not the inside of an asm string (gemm.hip glds16s, rowlin.hip rl_dma, attention.hip's
+    weight ring).  tools/isa_audit_lds_dma.py compiles every translation unit for gfx950 and checks each kernel's instruction stream (across
+    labels and branches) for a request whose previous instruction writes M0.  Cross-compiles without a GPU."""
+    import shutil
+    import subprocess
+    import sys
+    if not shutil.which("/opt/rocm/bin/hipcc"):
+        pytest.skip("no hipcc")
+    r = subprocess.run([sys.executable, str(REPO / "tools" / "isa_audit_lds_dma.py")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    total = re.search(r"total: (\d+) LDS-DMA instructions, (\d+) findings", r.stdout)
+    assert total and int(total.group(1)) > 0 and total.group(2) == "0", r.stdout
+    for kernel in ("gemm256_kernel", "rowlin768_kernel", "qkv_attention_kernel", "mlp_fused_kernel"):
+        assert kernel in r.stdout, f"{kernel} issues no LDS-DMA any more: the audit no longer sees it"

@@ -7,6 +7,7 @@
 #include "../../include/duodiff.h"
 #include "../../include/duodiff_dev.h"
 #include "dd_internal.h"
+#include "host_arena.h"
 
 #include <algorithm>
 #include <cmath>
@@ -133,13 +134,12 @@ struct WsPtrs {
     bf16_t* hfrag = nullptr;              // fused_qa: norm1 of the patch rows in MFMA fragment order (MlpFusedArgs::ln_out_frag)
     float* ytap = nullptr;                // early-exit models with fused_skip: the block output y of the launches that run the next skip_linear (MlpFusedArgs::y_tap)
 };
-struct WsOffsets { size_t x, h, ao, qkv, hid, xb, dec, part, dump, hf, bytes; std::vector<size_t> sk; bool has_part, has_dump, has_hf; size_t tap = 0; bool has_tap = false; };
 
 struct dd_model {
     dd_ctx* ctx = nullptr;
     dd_config cfg{};
     int D = 0, L = 0, N = 0, extras = 0, pd = 0, pdp = 0, H = 0, hidden = 0, hid_ld = 0, half_depth = 0, Mp_max = 0;
-    std::map<std::string, HostParam> params;
+    std::map<std::string, HostParam> params;   // every state_dict name of the model (catalogue), its data once set (dropped by finalize)
     bool finalized = false;
     int prec = DD_PREC_BF16;
     size_t esize = 2;
@@ -147,8 +147,7 @@ struct dd_model {
     std::vector<BlockW> blocks;  // in.., mid, out..
     const float *emb_wt = nullptr, *emb_b = nullptr, *pos = nullptr, *label = nullptr;
     const float *tm_w1t = nullptr, *tm_b1 = nullptr, *tm_w2t = nullptr, *tm_b2 = nullptr;   // time_embed MLP (mlp_time_embed)
-    const float *norm_g = nullptr, *norm_b = nullptr, *wdec = nullptr, *bdec = nullptr, *wconv = nullptr, *bconv = nullptr;
-    const float *wdec_g = nullptr, *dec_c = nullptr;   // head_dec_kernel operands (decoder weight * norm gamma; bias + W . beta [pd], then the row sums of wdec_g [pd]) or null
+    HeadW head{};                         // the final head (uvit.py:377-380; no split-bf16 image)
     // early-exit baseline (models/early_exit.py:193-268): per-layer output heads + MLP probes; ee_type < 0: plain U-ViT
     int ee_type = -1, n_probe = 0;
     std::vector<HeadW> heads;             // head i is applied to the input of block i
@@ -169,7 +168,7 @@ struct dd_model {
     bool fused_qa = false;                // attn.qkv computed inside the attention launch (attention.hip qkv_attention_kernel): takes precedence over
                                           // fused_qkv wherever the previous block's fused launch leaves norm1 in h
     // each chain's activation workspace: [0] laid out for max_batch (dd_model_finalize), [1] for half of it (ensure_chain_ws, on the first chained call)
-    WsOffsets wsoff[2]{};
+    size_t ws_bytes[2] = {0, 0};
     char* wsarena[2] = {nullptr, nullptr};
     WsPtrs ws[2];
     hipGraphExec_t graph[GRAPH_KINDS][2] = {};                // each loop's captured step, per chain
@@ -255,36 +254,13 @@ const Schedule& schedule() {
     return s;
 }
 
-unsigned short host_f2bf(float f) {
-    unsigned u;
-    std::memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);  // NaN stays NaN
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
-// ModuleDict key of EarlyExitUViT.matrix -> row of the probe table (early_exit.py:194-204, 219-240); -1: not a key
-int probe_index(const dd_model* m, const std::string& key) {
-    auto num = [](const std::string& v, int& out) {
-        if (v.empty() || v.size() > 6) return false;
-        for (char ch : v) if (ch < '0' || ch > '9') return false;
-        out = std::atoi(v.c_str());
-        return true;
-    };
-    int i = 0, t = 0;
-    switch (m->ee_type) {
-        case DD_EE_MLP_PER_LAYER:
-        case DD_EE_ATTENTION_PROBE: return num(key, i) && i < m->cfg.depth ? i : -1;
-        case DD_EE_MLP_PER_TIMESTEP: return num(key, t) && t < 1000 ? t : -1;
-        case DD_EE_MLP_PER_LAYER_PER_TIMESTEP: {
-            const size_t cpos = key.find(", ");
-            if (cpos == std::string::npos) return -1;
-            if (!num(key.substr(0, cpos), i) || !num(key.substr(cpos + 2), t) || i >= m->cfg.depth || t >= 1000) return -1;
-            return t * m->cfg.depth + i;
-        }
-    }
-    return -1;
+// the probes of an early-exit model (EarlyExitUViT.matrix, early_exit.py:194-204, 219-240) form an nt x nl grid of (timestep, layer);
+// row t nl + layer of the probe table is probe (layer, t): per layer `layer`, per timestep `t`, per layer and timestep `t depth + layer`
+void probe_grid(const dd_model* m, int& nt, int& nl) {
+    nt = m->ee_type == DD_EE_MLP_PER_LAYER || m->ee_type == DD_EE_ATTENTION_PROBE ? 1 : 1000;
+    nl = m->ee_type == DD_EE_MLP_PER_TIMESTEP ? 1 : m->cfg.depth;
 }
 std::string probe_key(const dd_model* m, int layer, int t) {
     switch (m->ee_type) {
@@ -294,184 +270,237 @@ std::string probe_key(const dd_model* m, int layer, int t) {
         default: return std::to_string(layer) + ", " + std::to_string(t);
     }
 }
+std::string block_prefix(const dd_model* m, int bi) {
+    if (bi < m->half_depth) return "in_blocks." + std::to_string(bi) + ".";
+    if (bi == m->half_depth) return "mid_block.";
+    return "out_blocks." + std::to_string(bi - m->half_depth - 1) + ".";
+}
 std::string head_prefix(const dd_model* m, int layer) {
     if (layer < m->half_depth) return "in_blocks_heads." + std::to_string(layer) + ".";
     if (layer == m->half_depth) return "mid_block_head.";
     return "out_blocks_heads." + std::to_string(layer - m->half_depth - 1) + ".";
 }
-// "in_blocks_heads.<i>.<rest>" / "mid_block_head.<rest>" / "out_blocks_heads.<i>.<rest>" -> layer index, or -1
-int head_index(const dd_model* m, const std::string& name, std::string& rest) {
-    for (int layer = 0; layer < m->cfg.depth; ++layer) {
-        const std::string pre = head_prefix(m, layer);
-        if (name.compare(0, pre.size(), pre) == 0) { rest = name.substr(pre.size()); return layer; }
-    }
-    return -1;
-}
 
-// expected shapes by reference state_dict name (models/uvit.py:228-336)
-bool expected_shape(const dd_model* m, const std::string& name, std::vector<int64_t>& shp) {
+// every state_dict name of the model with its shape, nothing set (models/uvit.py:228-336; for ee_type >= 0 also the early-exit heads and
+// probes, early_exit.py:40-80, 193-268): what dd_model_set_param accepts and dd_model_finalize requires
+std::map<std::string, HostParam> catalogue(const dd_model* m) {
+    std::map<std::string, HostParam> c;
     const int64_t D = m->D, C = m->cfg.in_chans, P = m->cfg.patch_size, hid = m->hidden;
-    auto is = [&](const char* s) { return name == s; };
-    if (is("pos_embed")) { shp = {1, m->L, D}; return true; }
-    if (is("patch_embed.proj.weight")) { shp = {D, C, P, P}; return true; }
-    if (is("patch_embed.proj.bias")) { shp = {D}; return true; }
-    if (m->cfg.mlp_time_embed) {
-        if (is("time_embed.0.weight")) { shp = {4 * D, D}; return true; }
-        if (is("time_embed.0.bias")) { shp = {4 * D}; return true; }
-        if (is("time_embed.2.weight")) { shp = {D, 4 * D}; return true; }
-        if (is("time_embed.2.bias")) { shp = {D}; return true; }
-    }
-    if (is("label_emb.weight")) { if (m->cfg.num_classes <= 0) return false; shp = {m->cfg.num_classes, D}; return true; }
-    if (is("norm.weight") || is("norm.bias")) { shp = {D}; return true; }
-    if (is("decoder_pred.weight")) { shp = {m->pd, D}; return true; }
-    if (is("decoder_pred.bias")) { shp = {m->pd}; return true; }
-    if (is("final_layer.weight")) { shp = {C, C, 3, 3}; return true; }
-    if (is("final_layer.bias")) { shp = {C}; return true; }
-    std::string rest;
-    bool out_blk = false;
-    if (m->ee_type >= 0) {
-        if (name.compare(0, 7, "matrix.") == 0 && m->ee_type == DD_EE_ATTENTION_PROBE) {   // AttentionProbe, early_exit.py:46-58
-            const size_t e = name.find('.', 7);
-            if (e == std::string::npos || probe_index(m, name.substr(7, e - 7)) < 0) return false;
-            const std::string tail = name.substr(e + 1);
-            if (tail == "q") { shp = {1, 1, 1, D}; return true; }
-            if (tail == "weight_kv.weight") { shp = {2 * D, D}; return true; }
-            if (tail == "weight_kv.bias") { shp = {2 * D}; return true; }
-            if (tail == "classification.0.weight") { shp = {D, D}; return true; }
-            if (tail == "classification.0.bias") { shp = {D}; return true; }
-            if (tail == "classification.2.weight") { shp = {1, D}; return true; }
-            if (tail == "classification.2.bias") { shp = {1}; return true; }
-            return false;
-        }
-        if (name.compare(0, 7, "matrix.") == 0) {               // matrix.<key>.classifier.0.{weight,bias}
-            const size_t e = name.find(".classifier.0.");
-            if (e == std::string::npos || probe_index(m, name.substr(7, e - 7)) < 0) return false;
-            const std::string tail = name.substr(e + 14);
-            if (tail == "weight") { shp = {1, D}; return true; }
-            if (tail == "bias") { shp = {1}; return true; }
-            return false;
-        }
-        std::string hrest;
-        if (head_index(m, name, hrest) >= 0) {
-            if (hrest == "norm.weight" || hrest == "norm.bias") { shp = {D}; return true; }
-            if (hrest == "decoder_pred.weight") { shp = {m->pd, D}; return true; }
-            if (hrest == "decoder_pred.bias") { shp = {m->pd}; return true; }
-            if (hrest == "final_layer.weight") { shp = {C, C, 3, 3}; return true; }
-            if (hrest == "final_layer.bias") { shp = {C}; return true; }
-            return false;
-        }
-    }
-    auto strip = [&](const char* pre, bool indexed) -> bool {
-        const size_t n = std::strlen(pre);
-        if (name.compare(0, n, pre) != 0) return false;
-        size_t p = n;
-        if (indexed) {
-            size_t q = p;
-            while (q < name.size() && name[q] >= '0' && name[q] <= '9') ++q;
-            if (q == p || q >= name.size() || name[q] != '.') return false;
-            const int idx = std::atoi(name.substr(p, q - p).c_str());
-            if (idx >= m->half_depth) return false;
-            p = q + 1;
-        }
-        rest = name.substr(p);
-        return true;
+    auto add = [&](const std::string& n, std::vector<int64_t> shape) { c[n].shape = std::move(shape); };
+    auto linear = [&](const std::string& n, int64_t out, int64_t in) { add(n + ".weight", {out, in}); add(n + ".bias", {out}); };
+    auto head = [&](const std::string& p) {
+        add(p + "norm.weight", {D}); add(p + "norm.bias", {D});
+        linear(p + "decoder_pred", m->pd, D);
+        add(p + "final_layer.weight", {C, C, 3, 3}); add(p + "final_layer.bias", {C});
     };
-    if (strip("in_blocks.", true)) out_blk = false;
-    else if (strip("out_blocks.", true)) out_blk = true;
-    else if (strip("mid_block.", false)) out_blk = false;
-    else return false;
-    if (rest == "norm1.weight" || rest == "norm1.bias" || rest == "norm2.weight" || rest == "norm2.bias" ||
-        rest == "attn.proj.bias" || rest == "mlp.fc2.bias") { shp = {D}; return true; }
-    if (rest == "attn.qkv.weight") { shp = {3 * D, D}; return true; }
-    if (m->cfg.qkv_bias && rest == "attn.qkv.bias") { shp = {3 * D}; return true; }
-    if (rest == "attn.proj.weight") { shp = {D, D}; return true; }
-    if (rest == "mlp.fc1.weight") { shp = {hid, D}; return true; }
-    if (rest == "mlp.fc1.bias") { shp = {hid}; return true; }
-    if (rest == "mlp.fc2.weight") { shp = {D, hid}; return true; }
-    if (out_blk && rest == "skip_linear.weight") { shp = {D, 2 * D}; return true; }
-    if (out_blk && rest == "skip_linear.bias") { shp = {D}; return true; }
-    return false;
-}
-
-std::vector<std::string> required_names(const dd_model* m) {
-    std::vector<std::string> v = {"pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias", "norm.weight",
-                                  "norm.bias", "decoder_pred.weight", "decoder_pred.bias", "final_layer.weight",
-                                  "final_layer.bias"};
-    if (m->cfg.num_classes > 0) v.push_back("label_emb.weight");
-    if (m->cfg.mlp_time_embed)
-        for (const char* s : {"time_embed.0.weight", "time_embed.0.bias", "time_embed.2.weight", "time_embed.2.bias"}) v.push_back(s);
-    auto blk = [&](const std::string& p, bool skip) {
-        for (const char* s : {"norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.proj.weight", "attn.proj.bias",
-                              "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight",
-                              "mlp.fc2.bias"})
-            v.push_back(p + s);
-        if (skip) { v.push_back(p + "skip_linear.weight"); v.push_back(p + "skip_linear.bias"); }
-        if (m->cfg.qkv_bias) v.push_back(p + "attn.qkv.bias");
-    };
-    for (int i = 0; i < m->half_depth; ++i) blk("in_blocks." + std::to_string(i) + ".", false);
-    blk("mid_block.", false);
-    for (int i = 0; i < m->half_depth; ++i) blk("out_blocks." + std::to_string(i) + ".", true);
-    if (m->ee_type >= 0) {
-        for (int layer = 0; layer < m->cfg.depth; ++layer)
-            for (const char* s : {"norm.weight", "norm.bias", "decoder_pred.weight", "decoder_pred.bias",
-                                  "final_layer.weight", "final_layer.bias"})
-                v.push_back(head_prefix(m, layer) + s);
-        const bool per_layer_only = m->ee_type == DD_EE_MLP_PER_LAYER || m->ee_type == DD_EE_ATTENTION_PROBE;
-        const int nt = per_layer_only ? 1 : 1000, nl = m->ee_type == DD_EE_MLP_PER_TIMESTEP ? 1 : m->cfg.depth;
-        for (int t = 0; t < nt; ++t)
-            for (int layer = 0; layer < nl; ++layer) {
-                const std::string pre = "matrix." + probe_key(m, layer, t) + ".";
-                if (m->ee_type == DD_EE_ATTENTION_PROBE) {
-                    for (const char* s : {"q", "weight_kv.weight", "weight_kv.bias", "classification.0.weight", "classification.0.bias",
-                                          "classification.2.weight", "classification.2.bias"})
-                        v.push_back(pre + s);
-                } else {
-                    v.push_back(pre + "classifier.0.weight");
-                    v.push_back(pre + "classifier.0.bias");
-                }
+    add("pos_embed", {1, m->L, D});
+    add("patch_embed.proj.weight", {D, C, P, P}); add("patch_embed.proj.bias", {D});
+    if (m->cfg.mlp_time_embed) { linear("time_embed.0", 4 * D, D); linear("time_embed.2", D, 4 * D); }
+    if (m->cfg.num_classes > 0) add("label_emb.weight", {m->cfg.num_classes, D});
+    for (int bi = 0; bi < m->cfg.depth; ++bi) {
+        const std::string p = block_prefix(m, bi);
+        add(p + "norm1.weight", {D}); add(p + "norm1.bias", {D});
+        add(p + "attn.qkv.weight", {3 * D, D});
+        if (m->cfg.qkv_bias) add(p + "attn.qkv.bias", {3 * D});
+        linear(p + "attn.proj", D, D);
+        add(p + "norm2.weight", {D}); add(p + "norm2.bias", {D});
+        linear(p + "mlp.fc1", hid, D); linear(p + "mlp.fc2", D, hid);
+        if (bi > m->half_depth) linear(p + "skip_linear", D, 2 * D);
+    }
+    head("");
+    if (m->ee_type < 0) return c;
+    for (int layer = 0; layer < m->cfg.depth; ++layer) head(head_prefix(m, layer));
+    int nt, nl;
+    probe_grid(m, nt, nl);
+    for (int t = 0; t < nt; ++t)
+        for (int layer = 0; layer < nl; ++layer) {
+            const std::string p = "matrix." + probe_key(m, layer, t) + ".";
+            if (m->ee_type == DD_EE_ATTENTION_PROBE) {
+                add(p + "q", {1, 1, 1, D});
+                linear(p + "weight_kv", 2 * D, D); linear(p + "classification.0", D, D); linear(p + "classification.2", 1, D);
+            } else {
+                linear(p + "classifier.0", 1, D);
             }
-    }
-    return v;
+        }
+    return c;
 }
 
-void bind_ws(const WsOffsets& o, char* arena, WsPtrs& w) {
-    w.x = (float*)(arena + o.x); w.h = arena + o.h; w.ao = arena + o.ao; w.qkv = arena + o.qkv; w.hid = arena + o.hid; w.xb = arena + o.xb;
-    w.dec = (float*)(arena + o.dec);
-    w.skips.clear();
-    for (size_t v : o.sk) w.skips.push_back(arena + v);
-    w.mlp_partial = o.has_part ? (float*)(arena + o.part) : nullptr;
-    w.qkv_dump = o.has_dump ? (bf16_t*)(arena + o.dump) : nullptr;
-    w.hfrag = o.has_hf ? (bf16_t*)(arena + o.hf) : nullptr;
-    w.ytap = o.has_tap ? (float*)(arena + o.tap) : nullptr;
-}
 // Layout of one chain's activation workspace for batches up to `batch` (the model's max_batch; half of it, rounded up, for the second
-// half-batch chain of dd_sample, which never runs more).
-WsOffsets ws_layout(const dd_model* m, int batch) {
+// half-batch chain of dd_sample, which never runs more): the buffers of w as regions of a
+void ws_layout(const dd_model* m, int batch, WsPtrs& w, Arena& a) {
     const int D = m->D, L = m->L, hid = m->hidden;
     const size_t es = m->esize;
     const size_t Mp = (size_t)round_up(batch * L, 256);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
     // qkv is head-major: B * 3H units of Lp rows x 64 (rows [L, Lp) of a unit are never written: the bf16 attention launch that stages K / V
     // from this tensor zeroes them in its LDS images itself)
     const size_t qkv_elems = (size_t)batch * 3 * D * (size_t)make_head_major(L, m->H).Lp;
-    const size_t o_x = take(Mp * D * 4), o_h = take(Mp * D * es), o_ao = take(Mp * D * es), o_qkv = take(std::max(Mp * 3 * D, qkv_elems) * es);
-    const size_t o_hid = take(Mp * (size_t)m->hid_ld * es), o_xb = take(Mp * D * es);
-    std::vector<size_t> o_sk;
-    for (int i = 0; i < m->half_depth; ++i) o_sk.push_back(take(Mp * D * es));
-    const size_t o_dec = take(Mp * m->pd * 4);
+    a.space(w.x, Mp * D * 4); a.space(w.h, Mp * D * es); a.space(w.ao, Mp * D * es); a.space(w.qkv, std::max(Mp * 3 * D, qkv_elems) * es);
+    a.space(w.hid, Mp * (size_t)m->hid_ld * es); a.space(w.xb, Mp * D * es);
+    w.skips.assign(m->half_depth, nullptr);
+    for (void*& sk : w.skips) a.space(sk, Mp * D * es);
+    a.space(w.dec, Mp * m->pd * 4);
     const size_t part_bytes = m->fused_mlp ? mlp_fused_partial_bytes(batch, m->extras, D, hid)
                               : m->splitk ? (size_t)2 * Mp * D * 4
                               : m->rowlin_fc2 ? std::max(std::max(rowlin_partial_bytes(batch, m->extras, hid), rowlin_partial_bytes(batch, m->extras, 2 * D)), rowlin_partial_bytes(batch, m->extras, D)) : 0;
-    const size_t o_part = take(part_bytes);
-    const size_t o_dump = take(m->fused_qkv ? 16384 : 0);
-    const size_t o_hf = take(m->fused_qa ? (size_t)batch * m->N * D * 2 : 0);
-    const bool has_tap = m->ee_type >= 0 && m->fused_skip;
-    const size_t o_tap = take(has_tap ? Mp * D * 4 : 0);
-    WsOffsets o{o_x, o_h, o_ao, o_qkv, o_hid, o_xb, o_dec, o_part, o_dump, o_hf, off, o_sk, part_bytes != 0, m->fused_qkv, m->fused_qa};
-    o.bytes = off;
-    o.tap = o_tap; o.has_tap = has_tap;
-    return o;
+    if (part_bytes) a.space(w.mlp_partial, part_bytes);
+    if (m->fused_qkv) a.space(w.qkv_dump, 16384);
+    if (m->fused_qa) a.space(w.hfrag, (size_t)batch * m->N * D * 2);
+    if (m->ee_type >= 0 && m->fused_skip) a.space(w.ytap, Mp * D * 4);
+}
+// ---- dd_model_finalize: the kernel path of each stage, then every weight packed into one arena
+// (a function of the model, its precision and the development flags dd_dev_set_flags: never of a call's batch)
+void choose_paths(dd_model* m, int precision, unsigned flags) {
+    const int D = m->D, hid = m->hidden, L = m->L;
+    // fused block tail (mlp_fused.hip): bf16 mode only (development A/B runs can switch it off: dd_dev_set_flags)
+    m->fused_mlp = precision == DD_PREC_BF16 && mlp_fused_supported(D, hid) && !(flags & DD_DEV_NO_FUSED_MLP);
+    m->fused_proj = m->fused_mlp && D % 128 == 0 && !(flags & DD_DEV_NO_FUSED_PROJ);
+    m->fused_skip = m->fused_proj && (hid / 32) % 2 == 0 && !(flags & DD_DEV_NO_FUSED_SKIP);     // (early-exit models too: y leaves through MlpFusedArgs::y_tap)
+    m->fused_qkv = m->fused_proj && m->ee_type < 0 && (hid / 32) % 2 == 0 && !m->cfg.qkv_bias && !(flags & DD_DEV_NO_FUSED_QKV);
+    // (early-exit models too: their heads and probes read the residual stream between blocks, which this launch does not touch)
+    // (embed_dim 768 / 1024 too, which have no fused block tail: their norm1 launch writes the fragment order, the qkv tensor is gone)
+    m->fused_qa = precision == DD_PREC_BF16 && qkv_attention_supported(D, m->H, L, m->extras) && !(flags & DD_DEV_NO_FUSED_QA);
+    // (embed_dim 768, no fused block tail) mlp.fc2 with the residual rows resident in registers: x read and written once, the next norm1 from registers
+    m->rowlin_fc2 = precision == DD_PREC_BF16 && !m->fused_mlp && rowlin_supported(D, hid) && m->N % 32 == 0 && !(flags & DD_DEV_NO_ROWLIN);
+    m->rowlin_proj = m->rowlin_fc2 && !(flags & DD_DEV_NO_ROWLIN_PROJ);
+    m->rowlin_skip = m->rowlin_fc2 && rowlin_supported(D, 2 * D) && !(flags & DD_DEV_NO_ROWLIN_SKIP);
+    // split-K for the N = embed_dim Linears (skip_linear, attn.proj, mlp.fc2) where even max_batch leaves half of the CUs without a 256 x 256
+    // tile (ImageNet-256 latents: 32 x 4 tiles): a function of the model (max_batch), never of a call's batch
+    m->splitk = precision == DD_PREC_BF16 && !m->fused_mlp && !m->rowlin_fc2 && D % 256 == 0 && !(flags & DD_DEV_NO_SPLITK) &&
+                (long long)(m->cfg.max_batch * L / 256) * (D / 256) * 2 <= device_num_cus() &&
+                (hid / 64) % 2 == 0;
+    for (int b = 1; m->splitk && b <= m->cfg.max_batch; ++b)     // every batch this model can be called with must fit the kernel's row partition
+        m->splitk = gemm_splitk_supported(b * L, D, D, D, 2);
+}
+
+const std::vector<float>& param(const dd_model* m, const std::string& name) { return m->params.at(name).data; }
+
+// block bi into m->blocks[bi].  next_skip: prefix of the block whose skip_linear runs in THIS block's fused launch ("" = none);
+// next_qkv: prefix of the block whose attn.qkv runs in THIS block's fused launch ("" = none: the last block)
+void pack_block(dd_model* m, Arena& a, int bi, const std::string& next_skip, const std::string& next_qkv) {
+    const int D = m->D, hid = m->hidden;
+    const std::string p = block_prefix(m, bi);
+    auto P = [&](const std::string& n) -> const std::vector<float>& { return param(m, n); };
+    BlockW& w = m->blocks[bi];
+    a.f32(w.ln1_g, P(p + "norm1.weight")); a.f32(w.ln1_b, P(p + "norm1.bias"));
+    a.f32(w.ln2_g, P(p + "norm2.weight")); a.f32(w.ln2_b, P(p + "norm2.bias"));
+    a.f32(w.proj_b, P(p + "attn.proj.bias"));
+    a.f32(w.fc1_b, P(p + "mlp.fc1.bias")); a.f32(w.fc2_b, P(p + "mlp.fc2.bias"));
+    a.mat(w.qkv_w, P(p + "attn.qkv.weight")); a.mat(w.proj_w, P(p + "attn.proj.weight"));
+    if (m->cfg.qkv_bias) a.f32(w.qkv_b, P(p + "attn.qkv.bias"));
+    a.mat(w.fc1_w, P(p + "mlp.fc1.weight")); a.mat(w.fc2_w, P(p + "mlp.fc2.weight"));
+    const bool skip = bi > m->half_depth;
+    if (skip) { a.f32(w.skip_b, P(p + "skip_linear.bias")); a.mat(w.skip_w, P(p + "skip_linear.weight")); }
+    if (m->fused_mlp) {
+        const bool with_skip = m->fused_skip && !next_skip.empty();
+        // (an out-block's qkv needs its skip_linear in here too; with fused_qa the attention launch computes qkv and no section is packed)
+        const bool with_qkv = m->fused_qkv && !m->fused_qa && !next_qkv.empty() && (next_skip.empty() || with_skip);
+        char* img = a.raw(w.mlp_img, mlp_fused_image_bytes(D, hid, m->fused_proj, with_skip, with_qkv));
+        const size_t proj_bytes = m->fused_proj ? (size_t)D * D * 2 : 0;      // D/32 blocks of Wproj lead the stream
+        std::vector<float> b1p(hid);
+        if (m->fused_proj) mlp_fused_pack_proj(D, P(p + "attn.proj.weight").data(), host_f2bf, (unsigned short*)img);
+        mlp_fused_pack(D, hid, P(p + "mlp.fc1.weight").data(), P(p + "mlp.fc1.bias").data(), P(p + "mlp.fc2.weight").data(),
+                       true, host_f2bf, (unsigned short*)(img + proj_bytes), b1p.data());
+        if (with_skip)    // the next block's skip_linear: 2 D/32 blocks behind the MLP blocks
+            mlp_fused_pack_skip(D, P(next_skip + "skip_linear.weight").data(), host_f2bf,
+                                (unsigned short*)(img + proj_bytes + (size_t)(hid / 32) * 2 * (D / 16) * 1024));
+        if (with_qkv)     // the next block's attn.qkv: 3 D/32 blocks closing the image
+            mlp_fused_pack_rows(D, 3 * D, P(next_qkv + "attn.qkv.weight").data(), host_f2bf,
+                                (unsigned short*)(img + proj_bytes + ((size_t)(hid / 32) * 2 + (with_skip ? D / 16 : 0)) * (D / 16) * 1024));
+        a.f32(w.mlp_b1p, b1p);
+    }
+    if (m->fused_qa)
+        qkv_attention_pack(D, m->H, P(p + "attn.qkv.weight").data(), host_f2bf, (unsigned short*)a.raw(w.qa_img, (size_t)3 * D * D * 2));
+    if (m->rowlin_fc2) {
+        rowlin_pack(hid, P(p + "mlp.fc2.weight").data(), host_f2bf, (unsigned short*)a.raw(w.rl_img, (size_t)D * hid * 2));
+        rowlin_pack(D, P(p + "attn.proj.weight").data(), host_f2bf, (unsigned short*)a.raw(w.rlp_img, (size_t)D * D * 2));
+        if (skip) rowlin_pack(2 * D, P(p + "skip_linear.weight").data(), host_f2bf, (unsigned short*)a.raw(w.rls_img, (size_t)D * 2 * D * 2));
+    }
+}
+
+// patch, position and label embeddings and the time_embed MLP
+void pack_embed(dd_model* m, Arena& a) {
+    const int D = m->D, pd = m->pd;
+    auto P = [&](const std::string& n) -> const std::vector<float>& { return param(m, n); };
+    // patch-embed weight [D, pd] -> transposed [pd, D] (coalesced over D in the embed kernel)
+    std::vector<float> wt((size_t)pd * D);
+    const std::vector<float>& pe = P("patch_embed.proj.weight");
+    for (int d = 0; d < D; ++d) for (int k = 0; k < pd; ++k) wt[(size_t)k * D + d] = pe[(size_t)d * pd + k];
+    a.f32(m->emb_wt, wt); a.f32(m->emb_b, P("patch_embed.proj.bias")); a.f32(m->pos, P("pos_embed"));
+    if (m->cfg.num_classes > 0) a.f32(m->label, P("label_emb.weight"));
+    if (m->cfg.mlp_time_embed) {   // transposed: the kernel's threads run over the OUTPUT index
+        const std::vector<float>&w1 = P("time_embed.0.weight"), &w2 = P("time_embed.2.weight");
+        std::vector<float> w1t((size_t)D * 4 * D), w2t((size_t)4 * D * D);
+        for (int j = 0; j < 4 * D; ++j) for (int k = 0; k < D; ++k) w1t[(size_t)k * 4 * D + j] = w1[(size_t)j * D + k];
+        for (int d = 0; d < D; ++d) for (int k = 0; k < 4 * D; ++k) w2t[(size_t)k * D + d] = w2[(size_t)d * 4 * D + k];
+        a.f32(m->tm_w1t, w1t); a.f32(m->tm_b1, P("time_embed.0.bias"));
+        a.f32(m->tm_w2t, w2t); a.f32(m->tm_b2, P("time_embed.2.bias"));
+    }
+}
+
+// an output head (state_dict prefix p; "" = the final head) into h: LayerNorm, decoder_pred, final_layer.  fused: the head_dec_kernel
+// operands too, the norm folded into decoder_pred (dec = (W . diag(gamma)) xn + (b + W . beta)); split: and Wg as hi + lo bf16 halves in
+// the SPLIT kernel's fragment order
+void pack_head(const dd_model* m, Arena& a, const std::string& p, HeadW& h, bool fused, bool split) {
+    const int D = m->D, pd = m->pd;
+    auto P = [&](const std::string& n) -> const std::vector<float>& { return param(m, n); };
+    const std::vector<float>&ng = P(p + "norm.weight"), &nb = P(p + "norm.bias"), &wd = P(p + "decoder_pred.weight"), &bd = P(p + "decoder_pred.bias");
+    a.f32(h.ng, ng); a.f32(h.nb, nb); a.f32(h.wdec, wd); a.f32(h.bdec, bd);
+    a.f32(h.wconv, P(p + "final_layer.weight")); a.f32(h.bconv, P(p + "final_layer.bias"));
+    if (!fused) return;
+    std::vector<float> wg, dc;
+    fold_head_norm(D, pd, wd.data(), bd.data(), ng.data(), nb.data(), wg, dc);
+    a.f32(h.wg, wg); a.f32(h.dc, dc);
+    if (!split) return;
+    const size_t img_bytes = (size_t)(D / 32) * ((pd + 15) / 16) * 2 * 64 * 8 * 2;
+    std::vector<float> dcs(dc);
+    pack_head_split(D, pd, wg.data(), host_f2bf, (unsigned short*)a.raw(h.wsplit, img_bytes), dcs.data() + pd);
+    a.f32(h.dcs, dcs);
+}
+
+// the early-exit probes: one AttentionProbe per layer, or the [n_probe, D] / [n_probe] table of the MLP probes
+void pack_probes(dd_model* m, Arena& a) {
+    const int D = m->D;
+    auto P = [&](const std::string& n) -> const std::vector<float>& { return param(m, n); };
+    int nt, nl;
+    probe_grid(m, nt, nl);
+    if (m->ee_type == DD_EE_ATTENTION_PROBE) {
+        // AttentionProbe (early_exit.py:40-80), one learned query, one head.  q . (Wk x + bk) = (Wk^T q) . x + const, and the
+        // constant cancels in the softmax; sum_l p_l (Wv x_l + bv) = Wv (sum_l p_l x_l) + bv.  So the probe needs u = Wk^T q /
+        // sqrt(D) (folded here, in double), and Wv / classification.0 transposed for coalesced mat-vecs -- never the [L, 2D] kv.
+        m->attn_probes.resize(nl);
+        for (int layer = 0; layer < nl; ++layer) {
+            const std::string pre = "matrix." + probe_key(m, layer, 0) + ".";
+            const std::vector<float>&q = P(pre + "q"), &wkv = P(pre + "weight_kv.weight"), &bkv = P(pre + "weight_kv.bias"),
+                                    &w0 = P(pre + "classification.0.weight");
+            std::vector<float> u(D), wvt((size_t)D * D), w0t((size_t)D * D);
+            const double scale = 1.0 / std::sqrt((double)D);
+            for (int k = 0; k < D; ++k) {
+                double acc = 0.0;
+                for (int j = 0; j < D; ++j) acc += (double)q[j] * (double)wkv[(size_t)j * D + k];
+                u[k] = (float)(acc * scale);
+            }
+            for (int j = 0; j < D; ++j)
+                for (int k = 0; k < D; ++k) {
+                    wvt[(size_t)k * D + j] = wkv[(size_t)(D + j) * D + k];
+                    w0t[(size_t)k * D + j] = w0[(size_t)j * D + k];
+                }
+            AttnProbeW& w = m->attn_probes[layer];
+            a.f32(w.u, u); a.f32(w.wvt, wvt); a.f32(w.bv, bkv.data() + D, D);
+            a.f32(w.w0t, w0t); a.f32(w.b0, P(pre + "classification.0.bias"));
+            a.f32(w.w2, P(pre + "classification.2.weight")); a.f32(w.b2, P(pre + "classification.2.bias"));
+        }
+        return;
+    }
+    m->n_probe = nt * nl;
+    std::vector<float> pw((size_t)m->n_probe * D), pb(m->n_probe);
+    for (int t = 0; t < nt; ++t)
+        for (int layer = 0; layer < nl; ++layer) {
+            const std::string pre = "matrix." + probe_key(m, layer, t) + ".classifier.0.";
+            const int row = t * nl + layer;
+            std::memcpy(&pw[(size_t)row * D], P(pre + "weight").data(), (size_t)D * 4);
+            pb[row] = P(pre + "bias")[0];
+        }
+    a.f32(m->probe_w, pw); a.f32(m->probe_b, pb);
 }
 // Argument filling of the two row-pass variants of an N = D Linear g (Backbone::rowlin_then_reduce / splitk_then_reduce_ln, dd_dev_rowlin /
 // dd_dev_gemm): pure functions of the Linear, so that the development entry points launch exactly what the model launches.
@@ -805,14 +834,15 @@ struct Backbone {
     // free here), then decoder_pred as an exact-fp32 MFMA GEMM in BOTH precision modes, so eps is
     // never rounded to bf16.  dec holds all L tokens per image; the extras are skipped downstream.
     int head() {
-        if (m->wdec_g) {   // fused: rows read once, normalised rows never written
-            HeadDecArgs ha{ws.x, m->wdec_g, m->dec_c, ws.dec, M, m->pd, (L - m->extras) % 16 == 0 ? L : 0, m->extras};   // (only the patch rows)
+        const HeadW& hd = m->head;
+        if (hd.wg) {   // fused: rows read once, normalised rows never written
+            HeadDecArgs ha{ws.x, hd.wg, hd.dc, ws.dec, M, m->pd, (L - m->extras) % 16 == 0 ? L : 0, m->extras};   // (only the patch rows)
             DD_HIP(c, launch_head_dec(ha, D, ch.cus, s));
             return DD_OK;
         }
         float* hf = (float*)ws.hid;
-        DD_HIP(c, launch_layernorm<float>(ws.x, m->norm_g, m->norm_b, hf, M, D, s));
-        GemmArgs<float> g{hf, nullptr, m->wdec, m->bdec, ws.dec, nullptr, M, m->pd, D, D, D, 0, m->pd};
+        DD_HIP(c, launch_layernorm<float>(ws.x, hd.ng, hd.nb, hf, M, D, s));
+        GemmArgs<float> g{hf, nullptr, hd.wdec, hd.bdec, ws.dec, nullptr, M, m->pd, D, D, D, 0, m->pd};
         DD_HIP(c, launch_gemm<float>(g, EPI_BIAS_SET, s, ch.cus));
         return DD_OK;
     }
@@ -879,7 +909,7 @@ int enqueue_step(dd_ctx* c, dd_model* m, const Chain& ch, float* x_dev, const in
                  const dd_guidance* g = nullptr, const HistRow* htab = nullptr, float* h = nullptr) {
     int rc = run_model(m, ch, x_dev, nullptr, y_dev, g ? 2 * B : B, s);
     if (rc) return rc;
-    FinalArgs fa{ch.ws->dec, m->wconv, m->bconv, x_dev, z_dev, eps_out, x_dev, ch.st, c->coef,
+    FinalArgs fa{ch.ws->dec, m->head.wconv, m->head.bconv, x_dev, z_dev, eps_out, x_dev, ch.st, c->coef,
                  B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, noise_mode, variance, advance, atab, b0};
     if (g) { fa.pair_B = B; fa.guide_scale = g->scale; }
     fa.htab = htab;
@@ -895,7 +925,7 @@ int forward_eps(dd_ctx* c, dd_model* m, const Chain& ch, const float* t_set, con
     if (t_set) DD_HIP(c, launch_set_state_float(ch.st, *t_set, s));
     int rc = run_model(m, ch, x_dev, t_vec, y_dev, g ? 2 * B : B, s, ee);
     if (rc) return rc;
-    FinalArgs fa{ch.ws->dec, m->wconv, m->bconv, nullptr, nullptr, eps_dev, nullptr, ch.st, c->coef,
+    FinalArgs fa{ch.ws->dec, m->head.wconv, m->head.bconv, nullptr, nullptr, eps_dev, nullptr, ch.st, c->coef,
                  B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, DD_NOISE_NONE, 0, 0};
     if (g) { fa.pair_B = B; fa.guide_scale = g->scale; }
     DD_HIP(c, launch_final(fa, s));
@@ -977,10 +1007,12 @@ int chain_gemm_cus(dd_ctx* c, dd_model* m, int B) {
 // first chained call of a model, intermittently)
 int ensure_chain_ws(dd_ctx* c, dd_model* m, hipStream_t s) {
     if (m->wsarena[1]) return DD_OK;
-    m->wsoff[1] = ws_layout(m, (m->cfg.max_batch + 1) / 2);     // a chain never runs more than half of max_batch
-    DD_HIP(c, hipMalloc((void**)&m->wsarena[1], m->wsoff[1].bytes));
-    DD_HIP(c, hipMemsetAsync(m->wsarena[1], 0, m->wsoff[1].bytes, s));
-    bind_ws(m->wsoff[1], m->wsarena[1], m->ws[1]);
+    Arena a;
+    ws_layout(m, (m->cfg.max_batch + 1) / 2, m->ws[1], a);     // a chain never runs more than half of max_batch
+    m->ws_bytes[1] = a.bytes();
+    DD_HIP(c, hipMalloc((void**)&m->wsarena[1], m->ws_bytes[1]));
+    DD_HIP(c, hipMemsetAsync(m->wsarena[1], 0, m->ws_bytes[1], s));
+    a.bind(m->wsarena[1]);
     return DD_OK;
 }
 // a failure between the fork and the join of a chained call must not leave the side stream running on the second chain's buffers behind
@@ -1299,6 +1331,7 @@ int dd_model_create(dd_ctx* c, const dd_config* cfg, dd_model** out) {
     m->Mp_max = round_up(g.max_batch * m->L, 256);
     if (m->L > 288) { delete m; return fail(c, DD_ERR_UNSUPPORTED, "sequence length must be <= 288 tokens"); }
     if (m->pd > 64) { delete m; return fail(c, DD_ERR_UNSUPPORTED, "patch_size^2 * in_chans must be <= 64"); }
+    m->params = catalogue(m);
     *out = m;
     return DD_OK;
 }
@@ -1307,8 +1340,10 @@ int dd_model_set_param(dd_model* m, const char* name, const float* host, const i
     if (!m || !name || !host || !shape || ndim < 1) return DD_ERR_INVALID;
     dd_ctx* c = m->ctx;
     if (m->finalized) return fail(c, DD_ERR_STATE, "model already finalized");
-    std::vector<int64_t> want;
-    if (!expected_shape(m, name, want)) return fail(c, DD_ERR_NOT_FOUND, std::string("unexpected key in state_dict: ") + name);
+    auto it = m->params.find(name);
+    if (it == m->params.end()) return fail(c, DD_ERR_NOT_FOUND, std::string("unexpected key in state_dict: ") + name);
+    HostParam& p = it->second;
+    const std::vector<int64_t>& want = p.shape;
     std::vector<int64_t> got(shape, shape + ndim);
     if (got != want) {
         std::string msg = std::string("size mismatch for ") + name + ": expected [";
@@ -1319,9 +1354,7 @@ int dd_model_set_param(dd_model* m, const char* name, const float* host, const i
     }
     size_t n = 1;
     for (auto d : want) n *= (size_t)d;
-    HostParam& p = m->params[name];
     p.data.assign(host, host + n);
-    p.shape = want;
     p.set = true;
     return DD_OK;
 }
@@ -1338,223 +1371,34 @@ int dd_model_finalize(dd_model* m, int precision) {
     dd_ctx* c = m->ctx;
     if (m->finalized) return fail(c, DD_ERR_STATE, "model already finalized");
     if (precision != DD_PREC_BF16 && precision != DD_PREC_FP32) return fail(c, DD_ERR_INVALID, "unknown precision");
-    for (const std::string& nm : required_names(m)) {
-        auto it = m->params.find(nm);
-        if (it == m->params.end() || !it->second.set) return fail(c, DD_ERR_NOT_FOUND, "missing key in state_dict: " + nm);
-    }
+    for (const auto& kv : m->params)
+        if (!kv.second.set) return fail(c, DD_ERR_NOT_FOUND, "missing key in state_dict: " + kv.first);
     DD_HIP(c, hipSetDevice(c->device));
     m->prec = precision;
     m->esize = precision == DD_PREC_BF16 ? 2 : 4;
-    const size_t es = m->esize;
-    const int D = m->D, hid = m->hidden, L = m->L;
+    choose_paths(m, precision, c->dev_flags);
+    const int depth = m->cfg.depth, L = m->L;
 
     // ---- pack weights into one arena: fp32 vectors/tables + T-typed GEMM matrices
-    std::vector<char> host;
-    auto align = [&]() { host.resize((host.size() + 255) / 256 * 256); };
-    auto put_f32 = [&](const float* src, size_t n) -> size_t {
-        align(); const size_t off = host.size(); host.resize(off + n * 4); std::memcpy(&host[off], src, n * 4); return off;
-    };
-    auto put_mat = [&](const std::vector<float>& src) -> size_t {
-        align(); const size_t off = host.size(); host.resize(off + src.size() * es);
-        if (es == 4) std::memcpy(&host[off], src.data(), src.size() * 4);
-        else { unsigned short* d = (unsigned short*)&host[off]; for (size_t i = 0; i < src.size(); ++i) d[i] = host_f2bf(src[i]); }
-        return off;
-    };
-    auto P = [&](const std::string& nm) -> const std::vector<float>& { return m->params[nm].data; };
+    Arena w(m->esize);
+    m->blocks.resize(depth);   // (sized before any slot is taken: the arena binds their fields in place)
+    for (int bi = 0; bi < depth; ++bi) {
+        const std::string next = bi + 1 < depth ? block_prefix(m, bi + 1) : "";
+        pack_block(m, w, bi, bi + 1 > m->half_depth ? next : "", next);   // (only out-blocks have a skip_linear)
+    }
+    pack_embed(m, w);
+    const bool fused_head = head_dec_supported(m->D, m->pd) && !(c->dev_flags & DD_DEV_NO_FUSED_HEAD);
+    pack_head(m, w, "", m->head, fused_head, false);
+    if (m->ee_type >= 0) {   // the early-exit heads: identical consecutive records (ee_conv_stride_ok), split-bf16 in the bf16 engine
+        const bool split_heads = fused_head && m->esize == 2 && head_dec_probe_supported(m->D) && !(c->dev_flags & DD_DEV_NO_SPLIT_HEADS);
+        m->heads.resize(depth);
+        for (int layer = 0; layer < depth; ++layer) pack_head(m, w, head_prefix(m, layer), m->heads[layer], fused_head, split_heads);
+        pack_probes(m, w);
+    }
+    DD_HIP(c, hipMalloc((void**)&m->warena, w.bytes()));
+    DD_HIP(c, hipMemcpy(m->warena, w.image(), w.bytes(), hipMemcpyHostToDevice));
+    w.bind(m->warena);
 
-    // fused block tail (mlp_fused.hip): bf16 mode only (development A/B runs can switch it off: dd_dev_set_flags)
-    m->fused_mlp = precision == DD_PREC_BF16 && mlp_fused_supported(D, hid) && !(c->dev_flags & DD_DEV_NO_FUSED_MLP);
-    m->fused_proj = m->fused_mlp && D % 128 == 0 && !(c->dev_flags & DD_DEV_NO_FUSED_PROJ);
-    m->fused_skip = m->fused_proj && (hid / 32) % 2 == 0 && !(c->dev_flags & DD_DEV_NO_FUSED_SKIP);     // (early-exit models too: y leaves through MlpFusedArgs::y_tap)
-    m->fused_qkv = m->fused_proj && m->ee_type < 0 && (hid / 32) % 2 == 0 && !m->cfg.qkv_bias && !(c->dev_flags & DD_DEV_NO_FUSED_QKV);
-    // (early-exit models too: their heads and probes read the residual stream between blocks, which this launch does not touch)
-    // (embed_dim 768 / 1024 too, which have no fused block tail: their norm1 launch writes the fragment order, the qkv tensor is gone)
-    m->fused_qa = precision == DD_PREC_BF16 && qkv_attention_supported(D, m->H, L, m->extras) && !(c->dev_flags & DD_DEV_NO_FUSED_QA);
-    // (embed_dim 768, no fused block tail) mlp.fc2 with the residual rows resident in registers: x read and written once, the next norm1 from registers
-    m->rowlin_fc2 = precision == DD_PREC_BF16 && !m->fused_mlp && rowlin_supported(D, hid) && m->N % 32 == 0 && !(c->dev_flags & DD_DEV_NO_ROWLIN);
-    m->rowlin_proj = m->rowlin_fc2 && !(c->dev_flags & DD_DEV_NO_ROWLIN_PROJ);
-    m->rowlin_skip = m->rowlin_fc2 && rowlin_supported(D, 2 * D) && !(c->dev_flags & DD_DEV_NO_ROWLIN_SKIP);
-    // split-K for the N = embed_dim Linears (skip_linear, attn.proj, mlp.fc2) where even max_batch leaves half of the CUs without a 256 x 256
-    // tile (ImageNet-256 latents: 32 x 4 tiles): a function of the model (max_batch), never of a call's batch
-    m->splitk = precision == DD_PREC_BF16 && !m->fused_mlp && !m->rowlin_fc2 && D % 256 == 0 && !(c->dev_flags & DD_DEV_NO_SPLITK) &&
-                (long long)(m->cfg.max_batch * L / 256) * (D / 256) * 2 <= device_num_cus() &&
-                (hid / 64) % 2 == 0;
-    for (int b = 1; m->splitk && b <= m->cfg.max_batch; ++b)     // every batch this model can be called with must fit the kernel's row partition
-        m->splitk = gemm_splitk_supported(b * L, D, D, D, 2);
-    auto put_raw = [&](size_t bytes) -> size_t { align(); const size_t off = host.size(); host.resize(off + bytes, 0); return off; };
-    struct BlockOff { size_t ln1_g, ln1_b, ln2_g, ln2_b, proj_b, fc1_b, fc2_b, skip_b, qkv_w, proj_w, fc1_w, fc2_w, skip_w, mlp_img, mlp_b1p, qkv_b, qa_img, rl_img, rlp_img, rls_img; bool skip; };
-    std::vector<BlockOff> boffs;
-    // next_skip: prefix of the block whose skip_linear runs in THIS block's fused launch ("" = none)
-    // next_qkv: prefix of the block whose attn.qkv runs in THIS block's fused launch ("" = none: the last block)
-    auto pack_block = [&](const std::string& p, bool skip, const std::string& next_skip, const std::string& next_qkv) {
-        BlockOff o{};
-        o.skip = skip;
-        o.ln1_g = put_f32(P(p + "norm1.weight").data(), D); o.ln1_b = put_f32(P(p + "norm1.bias").data(), D);
-        o.ln2_g = put_f32(P(p + "norm2.weight").data(), D); o.ln2_b = put_f32(P(p + "norm2.bias").data(), D);
-        o.proj_b = put_f32(P(p + "attn.proj.bias").data(), D);
-        o.fc1_b = put_f32(P(p + "mlp.fc1.bias").data(), hid); o.fc2_b = put_f32(P(p + "mlp.fc2.bias").data(), D);
-        o.qkv_w = put_mat(P(p + "attn.qkv.weight")); o.proj_w = put_mat(P(p + "attn.proj.weight"));
-        if (m->cfg.qkv_bias) o.qkv_b = put_f32(P(p + "attn.qkv.bias").data(), 3 * (size_t)D);
-        o.fc1_w = put_mat(P(p + "mlp.fc1.weight")); o.fc2_w = put_mat(P(p + "mlp.fc2.weight"));
-        if (skip) { o.skip_b = put_f32(P(p + "skip_linear.bias").data(), D); o.skip_w = put_mat(P(p + "skip_linear.weight")); }
-        if (m->fused_mlp) {
-            const bool with_skip = m->fused_skip && !next_skip.empty();
-            // (an out-block's qkv needs its skip_linear in here too; with fused_qa the attention launch computes qkv and no section is packed)
-            const bool with_qkv = m->fused_qkv && !m->fused_qa && !next_qkv.empty() && (next_skip.empty() || with_skip);
-            o.mlp_img = put_raw(mlp_fused_image_bytes(D, hid, m->fused_proj, with_skip, with_qkv));
-            o.mlp_b1p = put_raw((size_t)hid * 4);
-            const size_t proj_bytes = m->fused_proj ? (size_t)D * D * 2 : 0;      // D/32 blocks of Wproj lead the stream
-            if (m->fused_proj) mlp_fused_pack_proj(D, P(p + "attn.proj.weight").data(), host_f2bf, (unsigned short*)&host[o.mlp_img]);
-            mlp_fused_pack(D, hid, P(p + "mlp.fc1.weight").data(), P(p + "mlp.fc1.bias").data(), P(p + "mlp.fc2.weight").data(),
-                           true, host_f2bf, (unsigned short*)&host[o.mlp_img + proj_bytes], (float*)&host[o.mlp_b1p]);
-            if (with_skip)    // the next block's skip_linear: 2 D/32 blocks behind the MLP blocks
-                mlp_fused_pack_skip(D, P(next_skip + "skip_linear.weight").data(), host_f2bf,
-                                    (unsigned short*)&host[o.mlp_img + proj_bytes + (size_t)(hid / 32) * 2 * (D / 16) * 1024]);
-            if (with_qkv)     // the next block's attn.qkv: 3 D/32 blocks closing the image
-                mlp_fused_pack_rows(D, 3 * D, P(next_qkv + "attn.qkv.weight").data(), host_f2bf,
-                                    (unsigned short*)&host[o.mlp_img + proj_bytes + ((size_t)(hid / 32) * 2 + (with_skip ? D / 16 : 0)) * (D / 16) * 1024]);
-        }
-        if (m->fused_qa) {
-            o.qa_img = put_raw((size_t)3 * D * D * 2);
-            qkv_attention_pack(D, m->H, P(p + "attn.qkv.weight").data(), host_f2bf, (unsigned short*)&host[o.qa_img]);
-        }
-        if (m->rowlin_fc2) {
-            o.rl_img = put_raw((size_t)D * hid * 2);
-            rowlin_pack(hid, P(p + "mlp.fc2.weight").data(), host_f2bf, (unsigned short*)&host[o.rl_img]);
-            o.rlp_img = put_raw((size_t)D * D * 2);
-            rowlin_pack(D, P(p + "attn.proj.weight").data(), host_f2bf, (unsigned short*)&host[o.rlp_img]);
-            if (skip) {
-                o.rls_img = put_raw((size_t)D * 2 * D * 2);
-                rowlin_pack(2 * D, P(p + "skip_linear.weight").data(), host_f2bf, (unsigned short*)&host[o.rls_img]);
-            }
-        }
-        boffs.push_back(o);
-    };
-    auto in_name = [&](int i) { return "in_blocks." + std::to_string(i) + "."; };
-    auto out_name = [&](int i) { return "out_blocks." + std::to_string(i) + "."; };
-    for (int i = 0; i < m->half_depth; ++i) pack_block(in_name(i), false, "", i + 1 < m->half_depth ? in_name(i + 1) : std::string("mid_block."));
-    pack_block("mid_block.", false, m->half_depth > 0 ? out_name(0) : "", m->half_depth > 0 ? out_name(0) : "");
-    for (int i = 0; i < m->half_depth; ++i)
-        pack_block(out_name(i), true, i + 1 < m->half_depth ? out_name(i + 1) : "", i + 1 < m->half_depth ? out_name(i + 1) : "");
-
-    // patch-embed weight [D, pd] -> transposed [pd, D] (coalesced over D in the embed kernel)
-    std::vector<float> wt((size_t)m->pd * D);
-    const std::vector<float>& pe = P("patch_embed.proj.weight");
-    for (int d = 0; d < D; ++d) for (int k = 0; k < m->pd; ++k) wt[(size_t)k * D + d] = pe[(size_t)d * m->pd + k];
-    const size_t o_wt = put_f32(wt.data(), wt.size()), o_eb = put_f32(P("patch_embed.proj.bias").data(), D);
-    const size_t o_pos = put_f32(P("pos_embed").data(), (size_t)L * D);
-    const size_t o_lab = m->cfg.num_classes > 0 ? put_f32(P("label_emb.weight").data(), (size_t)m->cfg.num_classes * D) : 0;
-    size_t o_tm[4] = {0, 0, 0, 0};
-    if (m->cfg.mlp_time_embed) {   // transposed: the kernel's threads run over the OUTPUT index
-        const std::vector<float>&w1 = P("time_embed.0.weight"), &w2 = P("time_embed.2.weight");
-        std::vector<float> w1t((size_t)D * 4 * D), w2t((size_t)4 * D * D);
-        for (int j = 0; j < 4 * D; ++j) for (int k = 0; k < D; ++k) w1t[(size_t)k * 4 * D + j] = w1[(size_t)j * D + k];
-        for (int d = 0; d < D; ++d) for (int k = 0; k < 4 * D; ++k) w2t[(size_t)k * D + d] = w2[(size_t)d * 4 * D + k];
-        o_tm[0] = put_f32(w1t.data(), w1t.size()); o_tm[1] = put_f32(P("time_embed.0.bias").data(), 4 * (size_t)D);
-        o_tm[2] = put_f32(w2t.data(), w2t.size()); o_tm[3] = put_f32(P("time_embed.2.bias").data(), D);
-    }
-    const size_t o_ng = put_f32(P("norm.weight").data(), D), o_nb = put_f32(P("norm.bias").data(), D);
-    // head_dec_kernel operands: the final norm's affine part folded into decoder_pred (dec = Wg . xn + c)
-    const bool fused_head = head_dec_supported(D, m->pd) && !(c->dev_flags & DD_DEV_NO_FUSED_HEAD);
-    size_t o_wg = 0, o_dc = 0;
-    if (fused_head) {
-        const std::vector<float>&wd = P("decoder_pred.weight"), &bd = P("decoder_pred.bias"), &ng = P("norm.weight"), &nbv = P("norm.bias");
-        std::vector<float> wg, dc;
-        fold_head_norm(D, m->pd, wd.data(), bd.data(), ng.data(), nbv.data(), wg, dc);
-        o_wg = put_f32(wg.data(), wg.size()); o_dc = put_f32(dc.data(), dc.size());
-    }
-    const size_t o_wdec = put_f32(P("decoder_pred.weight").data(), (size_t)m->pd * D), o_bd = put_f32(P("decoder_pred.bias").data(), m->pd);
-    const size_t o_wc = put_f32(P("final_layer.weight").data(), P("final_layer.weight").size());
-    const size_t o_bc = put_f32(P("final_layer.bias").data(), m->cfg.in_chans);
-    struct HeadOff { size_t ng, nb, wdec, bdec, wconv, bconv, wg, dc, ws, dcs; };
-    const bool split_heads = fused_head && es == 2 && head_dec_probe_supported(D) && !(c->dev_flags & DD_DEV_NO_SPLIT_HEADS);
-    struct AttnProbeOff { size_t u, wvt, bv, w0t, b0, w2, b2; };
-    std::vector<AttnProbeOff> aoffs;
-    std::vector<HeadOff> hoffs;
-    size_t o_pw = 0, o_pb = 0;
-    if (m->ee_type >= 0) {
-        for (int layer = 0; layer < m->cfg.depth; ++layer) {
-            const std::string p = head_prefix(m, layer);
-            HeadOff o{};
-            o.ng = put_f32(P(p + "norm.weight").data(), D); o.nb = put_f32(P(p + "norm.bias").data(), D);
-            o.wdec = put_f32(P(p + "decoder_pred.weight").data(), (size_t)m->pd * D); o.bdec = put_f32(P(p + "decoder_pred.bias").data(), m->pd);
-            o.wconv = put_f32(P(p + "final_layer.weight").data(), P(p + "final_layer.weight").size());
-            o.bconv = put_f32(P(p + "final_layer.bias").data(), m->cfg.in_chans);
-            if (fused_head) {   // as the final head: dec = (W . diag(gamma)) xn + (b + W . beta)
-                const std::vector<float>&wd = P(p + "decoder_pred.weight"), &bd = P(p + "decoder_pred.bias"), &ng = P(p + "norm.weight"), &nbv = P(p + "norm.bias");
-                std::vector<float> wg, dc;
-                fold_head_norm(D, m->pd, wd.data(), bd.data(), ng.data(), nbv.data(), wg, dc);
-                o.wg = put_f32(wg.data(), wg.size()); o.dc = put_f32(dc.data(), dc.size());
-                if (split_heads) {      // the early-exit heads of the bf16 engine: Wg as hi + lo bf16 halves in the SPLIT kernel's fragment order
-                    const int nt = (m->pd + 15) / 16;
-                    std::vector<unsigned short> img((size_t)(D / 32) * nt * 2 * 64 * 8);
-                    std::vector<float> dcs(dc);
-                    pack_head_split(D, m->pd, wg.data(), host_f2bf, img.data(), dcs.data() + m->pd);
-                    o.ws = put_f32(reinterpret_cast<const float*>(img.data()), img.size() / 2); o.dcs = put_f32(dcs.data(), dcs.size());
-                }
-            }
-            hoffs.push_back(o);
-        }
-        if (m->ee_type == DD_EE_ATTENTION_PROBE) {
-            // AttentionProbe (early_exit.py:40-80), one learned query, one head.  q . (Wk x + bk) = (Wk^T q) . x + const, and the
-            // constant cancels in the softmax; sum_l p_l (Wv x_l + bv) = Wv (sum_l p_l x_l) + bv.  So the probe needs u = Wk^T q /
-            // sqrt(D) (folded here, in double), and Wv / classification.0 transposed for coalesced mat-vecs -- never the [L, 2D] kv.
-            for (int layer = 0; layer < m->cfg.depth; ++layer) {
-                const std::string pre = "matrix." + std::to_string(layer) + ".";
-                const std::vector<float>&q = P(pre + "q"), &wkv = P(pre + "weight_kv.weight"), &bkv = P(pre + "weight_kv.bias"),
-                                        &w0 = P(pre + "classification.0.weight");
-                std::vector<float> u(D), wvt((size_t)D * D), w0t((size_t)D * D);
-                const double scale = 1.0 / std::sqrt((double)D);
-                for (int k = 0; k < D; ++k) {
-                    double acc = 0.0;
-                    for (int j = 0; j < D; ++j) acc += (double)q[j] * (double)wkv[(size_t)j * D + k];
-                    u[k] = (float)(acc * scale);
-                }
-                for (int j = 0; j < D; ++j)
-                    for (int k = 0; k < D; ++k) {
-                        wvt[(size_t)k * D + j] = wkv[(size_t)(D + j) * D + k];
-                        w0t[(size_t)k * D + j] = w0[(size_t)j * D + k];
-                    }
-                AttnProbeOff o{};
-                o.u = put_f32(u.data(), D); o.wvt = put_f32(wvt.data(), wvt.size()); o.bv = put_f32(bkv.data() + D, D);
-                o.w0t = put_f32(w0t.data(), w0t.size()); o.b0 = put_f32(P(pre + "classification.0.bias").data(), D);
-                o.w2 = put_f32(P(pre + "classification.2.weight").data(), D); o.b2 = put_f32(P(pre + "classification.2.bias").data(), 1);
-                aoffs.push_back(o);
-            }
-        } else {
-        const int nt = m->ee_type == DD_EE_MLP_PER_LAYER ? 1 : 1000, nl = m->ee_type == DD_EE_MLP_PER_TIMESTEP ? 1 : m->cfg.depth;
-        m->n_probe = nt * nl;
-        std::vector<float> pw((size_t)m->n_probe * D), pb(m->n_probe);
-        for (int t = 0; t < nt; ++t)
-            for (int layer = 0; layer < nl; ++layer) {
-                const std::string key = probe_key(m, layer, t);
-                const int row = probe_index(m, key);
-                std::memcpy(&pw[(size_t)row * D], P("matrix." + key + ".classifier.0.weight").data(), (size_t)D * 4);
-                pb[row] = P("matrix." + key + ".classifier.0.bias")[0];
-            }
-        o_pw = put_f32(pw.data(), pw.size());
-        o_pb = put_f32(pb.data(), pb.size());
-        }
-    }
-    align();
-
-    DD_HIP(c, hipMalloc((void**)&m->warena, host.size()));
-    DD_HIP(c, hipMemcpy(m->warena, host.data(), host.size(), hipMemcpyHostToDevice));
-    auto F = [&](size_t off) { return (const float*)(m->warena + off); };
-    auto V = [&](size_t off) { return (const void*)(m->warena + off); };
-    for (const BlockOff& o : boffs) {
-        BlockW w{F(o.ln1_g), F(o.ln1_b), F(o.ln2_g), F(o.ln2_b), F(o.proj_b), F(o.fc1_b), F(o.fc2_b),
-                 o.skip ? F(o.skip_b) : nullptr, m->cfg.qkv_bias ? F(o.qkv_b) : nullptr, V(o.qkv_w), V(o.proj_w), V(o.fc1_w), V(o.fc2_w),
-                 o.skip ? V(o.skip_w) : nullptr, m->fused_mlp ? (const char*)V(o.mlp_img) : nullptr,
-                 m->fused_mlp ? F(o.mlp_b1p) : nullptr, m->fused_qa ? (const bf16_t*)V(o.qa_img) : nullptr,
-                 m->rowlin_fc2 ? (const char*)V(o.rl_img) : nullptr, m->rowlin_fc2 ? (const char*)V(o.rlp_img) : nullptr,
-                 m->rowlin_fc2 && o.skip ? (const char*)V(o.rls_img) : nullptr};
-        m->blocks.push_back(w);
-    }
-    if (m->cfg.mlp_time_embed) { m->tm_w1t = F(o_tm[0]); m->tm_b1 = F(o_tm[1]); m->tm_w2t = F(o_tm[2]); m->tm_b2 = F(o_tm[3]); }
-    m->emb_wt = F(o_wt); m->emb_b = F(o_eb); m->pos = F(o_pos); m->label = m->cfg.num_classes > 0 ? F(o_lab) : nullptr;
-    for (const HeadOff& o : hoffs) m->heads.push_back(HeadW{F(o.ng), F(o.nb), F(o.wdec), F(o.bdec), F(o.wconv), F(o.bconv), fused_head ? F(o.wg) : nullptr, fused_head ? F(o.dc) : nullptr,
-                                                            split_heads ? F(o.ws) : nullptr, split_heads ? F(o.dcs) : nullptr});
     if (m->heads.size() >= 2) {
         m->ee_wconv_stride = m->heads[1].wconv - m->heads[0].wconv; m->ee_bconv_stride = m->heads[1].bconv - m->heads[0].bconv;
         m->ee_conv_stride_ok = true;
@@ -1568,17 +1412,15 @@ int dd_model_finalize(dd_model* m, int precision) {
     };
     m->ee_batched = m->ee_type >= 0 && precision == DD_PREC_BF16 && m->fused_mlp && m->ee_conv_stride_ok && m->heads[0].wg &&
                     m->cfg.img_size >= 16 && ee_fits(m->cfg.max_batch) && ee_fits((m->cfg.max_batch + 1) / 2);
-    if (m->ee_type >= 0 && m->ee_type != DD_EE_ATTENTION_PROBE) { m->probe_w = F(o_pw); m->probe_b = F(o_pb); }
-    for (const AttnProbeOff& o : aoffs) m->attn_probes.push_back(AttnProbeW{F(o.u), F(o.wvt), F(o.bv), F(o.w0t), F(o.b0), F(o.w2), F(o.b2)});
-    if (fused_head) { m->wdec_g = F(o_wg); m->dec_c = F(o_dc); }
-    m->norm_g = F(o_ng); m->norm_b = F(o_nb); m->wdec = F(o_wdec); m->bdec = F(o_bd); m->wconv = F(o_wc); m->bconv = F(o_bc);
 
     // ---- activation workspace (HBM-resident for the life of the model)
-    m->wsoff[0] = ws_layout(m, m->cfg.max_batch);
-    DD_HIP(c, hipMalloc((void**)&m->wsarena[0], m->wsoff[0].bytes));
-    DD_HIP(c, hipMemset(m->wsarena[0], 0, m->wsoff[0].bytes));
+    Arena a;
+    ws_layout(m, m->cfg.max_batch, m->ws[0], a);
+    m->ws_bytes[0] = a.bytes();
+    DD_HIP(c, hipMalloc((void**)&m->wsarena[0], m->ws_bytes[0]));
+    DD_HIP(c, hipMemset(m->wsarena[0], 0, m->ws_bytes[0]));
     DD_HIP(c, hipStreamSynchronize(nullptr));    // (callers run the model on non-blocking streams, which a null-stream memset does not order itself before)
-    bind_ws(m->wsoff[0], m->wsarena[0], m->ws[0]);
+    a.bind(m->wsarena[0]);
 
     // host copies are no longer needed
     for (auto& kv : m->params) { std::vector<float>().swap(kv.second.data); }
@@ -1609,10 +1451,12 @@ int dd_forward(dd_ctx* c, dd_model* m, const float* x_dev, float t, const float*
 int dd_model_enable_early_exit(dd_model* m, int classifier_type) {
     if (!m) return DD_ERR_INVALID;
     dd_ctx* c = m->ctx;
-    if (m->finalized || !m->params.empty()) return fail(c, DD_ERR_STATE, "enable early exit before any parameter is set");
+    const bool any_set = std::any_of(m->params.begin(), m->params.end(), [](const auto& kv) { return kv.second.set; });
+    if (m->finalized || any_set) return fail(c, DD_ERR_STATE, "enable early exit before any parameter is set");
     if (classifier_type < DD_EE_MLP_PER_LAYER || classifier_type > DD_EE_ATTENTION_PROBE)
         return fail(c, DD_ERR_UNSUPPORTED, "unknown classifier type");
     m->ee_type = classifier_type;
+    m->params = catalogue(m);   // the heads and probes of this classifier type
     return DD_OK;
 }
 
@@ -1928,7 +1772,7 @@ int dd_dev_poison_workspaces(dd_ctx* c, dd_model* m, void* stream) {
     if (!c || !m || m->ctx != c || !m->finalized) return DD_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     if (int rc = ensure_chain_ws(c, m, s)) return rc;
-    for (int k = 0; k < 2; ++k) DD_HIP(c, hipMemsetAsync(m->wsarena[k], 0xFF, m->wsoff[k].bytes, s));
+    for (int k = 0; k < 2; ++k) DD_HIP(c, hipMemsetAsync(m->wsarena[k], 0xFF, m->ws_bytes[k], s));
     return DD_OK;
 }
 

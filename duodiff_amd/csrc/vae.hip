@@ -7,6 +7,7 @@
 // image (0.5 % of the FLOPs of 1000 sampling steps), so the design goal is correctness on parity-proven kernels.
 #include "../../include/duodiff.h"
 #include "dd_internal.h"
+#include "host_arena.h"
 
 #include <cmath>
 #include <cstring>
@@ -86,13 +87,6 @@ std::map<std::string, std::vector<int64_t>> expected() {
     norm("decoder.norm_out", cin);
     conv("decoder.conv_out", 3, cin, 3);
     return m;
-}
-
-unsigned short h_f2bf(float f) {
-    unsigned u;
-    std::memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
 
 template <typename T>
@@ -226,17 +220,7 @@ int dd_vae_finalize(dd_vae* v, int precision) {
     const size_t es = v->es;
     const int kt = 128 / (int)es;   // GEMM k-tile in elements
 
-    std::vector<char> host;
-    auto align = [&]() { host.resize((host.size() + 255) / 256 * 256); };
-    auto put_f32 = [&](const std::vector<float>& a) { align(); const size_t o = host.size(); host.resize(o + a.size() * 4); std::memcpy(&host[o], a.data(), a.size() * 4); return o; };
-    auto put_mat = [&](const std::vector<float>& a) {
-        align(); const size_t o = host.size(); host.resize(o + a.size() * es);
-        if (es == 4) std::memcpy(&host[o], a.data(), a.size() * 4);
-        else { unsigned short* d = (unsigned short*)&host[o]; for (size_t i = 0; i < a.size(); ++i) d[i] = h_f2bf(a[i]); }
-        return o;
-    };
-    struct Pend { ConvW* cw; NormW* nw; size_t ow, ob; };
-    std::vector<Pend> pend;
+    Arena w(es);
     auto P = [&](const std::string& n) -> const std::vector<float>& { return v->params[n].d; };
     // conv weight [Cout, Cin, k, k] -> GEMM matrix [Cout(+pad), (ky, kx, ci) padded to the k-tile]
     auto conv = [&](const std::string& n, ConvW& cw) {
@@ -244,24 +228,24 @@ int dd_vae_finalize(dd_vae* v, int precision) {
         const int co = (int)shp[0], ci = (int)shp[1], k = (int)shp[2];
         const int K = k * k * ci, kpad = (K + kt - 1) / kt * kt, rows = co == 3 ? 4 : co;
         std::vector<float> m((size_t)rows * kpad, 0.f);
-        const auto& w = P(n + ".weight");
+        const auto& wt = P(n + ".weight");
         for (int o = 0; o < co; ++o)
             for (int c2 = 0; c2 < ci; ++c2)
-                for (int t = 0; t < k * k; ++t) m[(size_t)o * kpad + t * ci + c2] = w[((size_t)o * ci + c2) * k * k + t];
+                for (int t = 0; t < k * k; ++t) m[(size_t)o * kpad + t * ci + c2] = wt[((size_t)o * ci + c2) * k * k + t];
         std::vector<float> b(rows, 0.f);
         std::memcpy(b.data(), P(n + ".bias").data(), co * 4);
         cw.cin = ci; cw.cout = co; cw.k = k; cw.kpad = kpad;
-        pend.push_back({&cw, nullptr, put_mat(m), put_f32(b)});
+        w.mat(cw.w, m); w.f32(cw.b, b);
     };
     auto norm = [&](const std::string& n, NormW& nw) {
         nw.c = (int)P(n + ".weight").size();
-        pend.push_back({nullptr, &nw, put_f32(P(n + ".weight")), put_f32(P(n + ".bias"))});
+        w.f32(nw.g, P(n + ".weight")); w.f32(nw.b, P(n + ".bias"));
     };
     auto res = [&](const std::string& n, ResW& r) {
         norm(n + ".norm1", r.n1); conv(n + ".conv1", r.c1); norm(n + ".norm2", r.n2); conv(n + ".conv2", r.c2);
         if (v->params.count(n + ".nin_shortcut.weight")) conv(n + ".nin_shortcut", r.nin);
     };
-    const size_t o_pqw = put_f32(P("post_quant_conv.weight")), o_pqb = put_f32(P("post_quant_conv.bias"));
+    w.f32(v->pq_w, P("post_quant_conv.weight")); w.f32(v->pq_b, P("post_quant_conv.bias"));
     conv("decoder.conv_in", v->conv_in);
     res("decoder.mid.block_1", v->mid1);
     norm("decoder.mid.attn_1.norm", v->attn_norm);
@@ -274,35 +258,27 @@ int dd_vae_finalize(dd_vae* v, int precision) {
     }
     norm("decoder.norm_out", v->norm_out);
     conv("decoder.conv_out", v->conv_out);
-    align();
-    VHIP(c, hipMalloc((void**)&v->warena, host.size()));
-    VHIP(c, hipMemcpy(v->warena, host.data(), host.size(), hipMemcpyHostToDevice));
-    for (auto& p : pend) {
-        if (p.cw) { p.cw->w = v->warena + p.ow; p.cw->b = (const float*)(v->warena + p.ob); }
-        else { p.nw->g = (const float*)(v->warena + p.ow); p.nw->b = (const float*)(v->warena + p.ob); }
-    }
-    v->pq_w = (const float*)(v->warena + o_pqw); v->pq_b = (const float*)(v->warena + o_pqb);
+    VHIP(c, hipMalloc((void**)&v->warena, w.bytes()));
+    VHIP(c, hipMemcpy(v->warena, w.image(), w.bytes(), hipMemcpyHostToDevice));
+    w.bind(v->warena);
 
-    // workspace for one chunk of images at the largest resolution (8 * latent)
+    // workspace for one chunk of images at the largest resolution (8 * latent); every buffer with the same slack behind it
     const size_t Bc = v->max_chunk, HWmax = (size_t)(8 * v->max_latent) * (8 * v->max_latent), slack = 512 * 4608 * 4;
     const size_t stream_elems = Bc * HWmax * 256;            // the upsample conv at the last level keeps 256 channels
     const size_t col_elems = Bc * HWmax * 2304;              // widest im2col: 256 channels at full resolution
     const size_t HWm = (size_t)v->max_latent * v->max_latent, Cm = 512;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + slack + 255) / 256 * 256; return o; };
-    const size_t o_s0 = take(stream_elems * 4), o_s1 = take(stream_elems * 4), o_h1 = take(stream_elems * 4);
-    const size_t o_nb = take(stream_elems * es), o_col = take(col_elems * es);
-    const size_t o_part = take((size_t)groupnorm_partials((int)Bc, (int)HWmax) * 4);
-    const size_t o_q = take(std::max(Bc * HWm * Cm, stream_elems) * es), o_k = take(Bc * HWm * Cm * es);
-    const size_t o_vt = take(Cm * HWm * es), o_pp = take(HWm * HWm * es), o_sc = take(HWm * HWm * 4);
-    const size_t o_ao = take(Bc * HWm * Cm * 4), o_z4 = take(Bc * HWm * 4 * 4);
-    VHIP(c, hipMalloc((void**)&v->ws, off));
-    VHIP(c, hipMemset(v->ws, 0, off));
+    Arena a;
+    auto buf = [&](auto*& field, size_t bytes) { a.space(field, bytes + slack); };
+    buf(v->s0, stream_elems * 4); buf(v->s1, stream_elems * 4); buf(v->h1, stream_elems * 4);
+    buf(v->nb, stream_elems * es); buf(v->col, col_elems * es);
+    buf(v->part, (size_t)groupnorm_partials((int)Bc, (int)HWmax) * 4);
+    buf(v->q, std::max(Bc * HWm * Cm, stream_elems) * es); buf(v->kk, Bc * HWm * Cm * es);
+    buf(v->vt, Cm * HWm * es); buf(v->pp, HWm * HWm * es); buf(v->score, HWm * HWm * 4);
+    buf(v->ao, Bc * HWm * Cm * 4); buf(v->z4, Bc * HWm * 4 * 4);
+    VHIP(c, hipMalloc((void**)&v->ws, a.bytes()));
+    VHIP(c, hipMemset(v->ws, 0, a.bytes()));
     VHIP(c, hipStreamSynchronize(nullptr));      // (ditto capi.hip: ordered before any stream the decoder is later run on)
-    v->s0 = (float*)(v->ws + o_s0); v->s1 = (float*)(v->ws + o_s1); v->h1 = (float*)(v->ws + o_h1);
-    v->nb = v->ws + o_nb; v->col = v->ws + o_col; v->part = (float*)(v->ws + o_part);
-    v->q = v->ws + o_q; v->kk = v->ws + o_k; v->vt = v->ws + o_vt; v->pp = v->ws + o_pp;
-    v->score = (float*)(v->ws + o_sc); v->ao = (float*)(v->ws + o_ao); v->z4 = (float*)(v->ws + o_z4);
+    a.bind(v->ws);
     for (auto& kv : v->params) std::vector<float>().swap(kv.second.d);
     v->finalized = true;
     return DD_OK;

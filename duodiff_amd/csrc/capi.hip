@@ -548,6 +548,15 @@ struct Chain {
 };
 Chain whole_batch(dd_ctx* c, dd_model* m) { return Chain{&m->ws[0], c->st[0], c->num_cus, true}; }
 
+// the output head's arguments that the model and the chain determine, for B images whose decoder rows are in dec; a call site sets the rest by name
+FinalArgs final_args(const dd_model* m, const Chain& ch, const float* dec, const float* wconv, const float* bconv, int B) {
+    FinalArgs fa{};
+    fa.dec = dec; fa.wconv = wconv; fa.bconv = bconv;
+    fa.st = ch.st; fa.coef = m->ctx->coef;
+    fa.B = B; fa.C = m->cfg.in_chans; fa.S = m->cfg.img_size; fa.P = m->cfg.patch_size; fa.L = m->L; fa.extras = m->extras;
+    return fa;
+}
+
 // ---- the forward: tokens -> blocks -> decoder_pred patches (the chain's dec) -----------------------
 // early-exit taps of one forward (EarlyExitUViT.forward, early_exit.py:290-313): cls [depth, B], outs [depth, B, C, S, S]
 struct EeTaps { float* cls; float* outs; int t; };
@@ -679,8 +688,8 @@ struct Backbone {
         }
         if (!ee_dec_all) {
             const long long chw = (long long)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
-            FinalArgs fa{ws.dec, hd.wconv, hd.bconv, nullptr, nullptr, ee->outs + (long long)bi * B * chw, nullptr, ch.st,
-                         c->coef, B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, L, m->extras, DD_NOISE_NONE, 0, 0};
+            FinalArgs fa = final_args(m, ch, ws.dec, hd.wconv, hd.bconv, B);
+            fa.eps_out = ee->outs + (long long)bi * B * chw;
             DD_HIP(c, launch_final(fa, hs));
         }
         if (m->ee_type == DD_EE_ATTENTION_PROBE) {
@@ -822,8 +831,8 @@ struct Backbone {
     // every layer's unpatchify + conv in one launch (layer i: images [i B, (i + 1) B) of nb B, its own conv weights), every MLP probe's mean in one
     int ee_finish() {
         if (!ee_dec_all) return DD_OK;
-        FinalArgs fa{ee_dec_all, m->heads[0].wconv, m->heads[0].bconv, nullptr, nullptr, ee->outs, nullptr, ch.st,
-                     c->coef, nb * B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, L, m->extras, DD_NOISE_NONE, 0, 0};
+        FinalArgs fa = final_args(m, ch, ee_dec_all, m->heads[0].wconv, m->heads[0].bconv, nb * B);
+        fa.eps_out = ee->outs;
         fa.layer_B = B; fa.w_stride = m->ee_wconv_stride; fa.b_stride = m->ee_bconv_stride;
         DD_HIP(c, launch_final(fa, s));
         if (m->ee_type != DD_EE_ATTENTION_PROBE) DD_HIP(c, launch_ee_probe_reduce(ee_srow_all, ee->cls, nb * B, L, s));
@@ -909,8 +918,9 @@ int enqueue_step(dd_ctx* c, dd_model* m, const Chain& ch, float* x_dev, const in
                  const dd_guidance* g = nullptr, const HistRow* htab = nullptr, float* h = nullptr) {
     int rc = run_model(m, ch, x_dev, nullptr, y_dev, g ? 2 * B : B, s);
     if (rc) return rc;
-    FinalArgs fa{ch.ws->dec, m->head.wconv, m->head.bconv, x_dev, z_dev, eps_out, x_dev, ch.st, c->coef,
-                 B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, noise_mode, variance, advance, atab, b0};
+    FinalArgs fa = final_args(m, ch, ch.ws->dec, m->head.wconv, m->head.bconv, B);
+    fa.x_in = x_dev; fa.z = z_dev; fa.eps_out = eps_out; fa.x_out = x_dev;
+    fa.noise_mode = noise_mode; fa.variance = variance; fa.advance = advance; fa.atab = atab; fa.b0 = b0;
     if (g) { fa.pair_B = B; fa.guide_scale = g->scale; }
     fa.htab = htab;
     fa.h = h;
@@ -925,8 +935,8 @@ int forward_eps(dd_ctx* c, dd_model* m, const Chain& ch, const float* t_set, con
     if (t_set) DD_HIP(c, launch_set_state_float(ch.st, *t_set, s));
     int rc = run_model(m, ch, x_dev, t_vec, y_dev, g ? 2 * B : B, s, ee);
     if (rc) return rc;
-    FinalArgs fa{ch.ws->dec, m->head.wconv, m->head.bconv, nullptr, nullptr, eps_dev, nullptr, ch.st, c->coef,
-                 B, m->cfg.in_chans, m->cfg.img_size, m->cfg.patch_size, m->L, m->extras, DD_NOISE_NONE, 0, 0};
+    FinalArgs fa = final_args(m, ch, ch.ws->dec, m->head.wconv, m->head.bconv, B);
+    fa.eps_out = eps_dev;
     if (g) { fa.pair_B = B; fa.guide_scale = g->scale; }
     DD_HIP(c, launch_final(fa, s));
     return DD_OK;
@@ -1411,7 +1421,7 @@ int dd_model_finalize(dd_model* m, int precision) {
         return m->blocks.size() * b * L * (m->pd + 1) * sizeof(float) <= (size_t)round_up(b * L, 256) * m->hid_ld * m->esize;
     };
     m->ee_batched = m->ee_type >= 0 && precision == DD_PREC_BF16 && m->fused_mlp && m->ee_conv_stride_ok && m->heads[0].wg &&
-                    m->cfg.img_size >= 16 && ee_fits(m->cfg.max_batch) && ee_fits((m->cfg.max_batch + 1) / 2);
+                    ee_fits(m->cfg.max_batch) && ee_fits((m->cfg.max_batch + 1) / 2);
 
     // ---- activation workspace (HBM-resident for the life of the model)
     Arena a;
@@ -1479,7 +1489,7 @@ int dd_early_exit_select(dd_ctx* c, const float* outputs_dev, const float* eps_d
     if (!outputs_dev || !eps_dev || !classifier_dev || !model_output_dev) return fail(c, DD_ERR_INVALID, "null tensor");
     if (depth < 1 || B < 1 || chw < 1) return fail(c, DD_ERR_INVALID, "depth, B and chw must be positive");
     DD_HIP(c, launch_ee_select(outputs_dev, eps_dev, classifier_dev, threshold, depth, B, (long long)chw, model_output_dev,
-                               indices_dev, err_mean_dev, nullptr, (hipStream_t)stream));
+                               indices_dev, err_mean_dev, (hipStream_t)stream));
     return DD_OK;
 }
 

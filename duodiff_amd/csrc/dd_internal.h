@@ -273,7 +273,6 @@ struct FinalArgs {
                            // and advance hands row k + 1's timestep to the next step (the table holds one row more than steps)
     int b0 = 0;            // index of this launch's first image within the whole batch (a half-batch chain of dd_sample): only the
                            // Philox pixel ids depend on it, so that a chain draws the z the undivided batch would
-    // (the fields below are set by name, never positionally: the aggregate initialisers of the step launches end at b0)
     int layer_B = 0;       // > 0: the B "images" are layer_B images of B / layer_B early-exit layers, one after the other (dec, eps_out contiguous that way);
     long long w_stride = 0, b_stride = 0;   //   layer i convolves with wconv + i * w_stride / bconv + i * b_stride (floats): ONE launch for every layer's head
     // classifier-free guidance (pair_B > 0): dec holds 2 pair_B images, image b's conditional rows first and its unconditional rows at b + pair_B;
@@ -337,19 +336,16 @@ hipError_t launch_ee_attn_probe(const float* x, const AttnProbeW& w, float* out,
 hipError_t launch_ee_probe(const float* x, const float* w_base, const float* bias_base, float* out, float* srow, int B, int L, int D,
                            const StepState* st, int t_mul, int add, hipStream_t s);
 hipError_t launch_ee_probe_reduce(const float* srow, float* out, int rows, int L, hipStream_t s);   // out == nullptr above: the rows only; this finishes any number of (layer, image) rows
-// st != null: idx / err_mean are [1000, B] / [1000, depth] tables and row st->t_final is written
-// a half-batch chain (dd_sample_early_exit): B = the chain's images, idx rows are idx_stride = the whole batch wide and the chain writes from
-// column idx_col0 on; sums: err_mean receives the plain per-layer SUM over the chain's images (launch_ee_mean_combine joins the chains)
+// dd_early_exit_select: mo [B, chw] = the selected output, idx [B] (or null), err_mean [depth] = the per-layer mean of cls over the batch (or null)
 hipError_t launch_ee_select(const float* outs, const float* eps, const float* cls, float thr, int depth, int B, long long chw,
-                            float* mo, int* idx, float* err_mean, const StepState* st, hipStream_t s, int idx_stride = 0, int idx_col0 = 0, bool sums = false);
-// launch_ee_select + launch_ddpm_step_state in one launch (the device-resident loop; idx_col0 = the chain's first image within the whole batch)
+                            float* mo, int* idx, float* err_mean, hipStream_t s);
+// the selection and the DDPM update in one launch (the device-resident loop): idx / err_mean are [1000, idx_stride] / [1000, depth] tables and row
+// st->t_final is written.  A half-batch chain: B = the chain's images, idx_col0 = its first image within the whole batch (its idx columns,
+// its Philox pixel ids); sums: err_mean receives the plain per-layer SUM over the chain's images (launch_ee_mean_combine joins the chains)
 hipError_t launch_ee_select_step(float* x, const float* outs, const float* eps, const float* cls, float thr, int depth, int* idx, float* err_mean,
                                  int idx_stride, int idx_col0, bool sums, StepState* st, const StepCoef* coef, int B, int C, int S,
                                  int noise_mode, int advance, hipStream_t s);
 hipError_t launch_ee_mean_combine(const float* s0, const float* s1, float* err, int depth, int t_lo, int t_hi, int B, hipStream_t s);
-// b0: index of the launch's first image within the whole batch (only the Philox pixel ids depend on it)
-hipError_t launch_ddpm_step_state(float* x, const float* eps, StepState* st, const StepCoef* coef, int B, int C, int S,
-                                  int noise_mode, int advance, hipStream_t s, int b0 = 0);
 hipError_t launch_set_state(StepState* st, int t, unsigned long long seed, hipStream_t s);
 hipError_t launch_set_state_table(StepState* st, const AffineRow* atab, unsigned long long seed, hipStream_t s);   // step index 0
 hipError_t launch_set_state_float(StepState* st, float t, hipStream_t s);

@@ -1,5 +1,5 @@
 // Bandwidth-bound kernels around the GEMM/attention core (gfx950): token assembly,
-// LayerNorm, the output head, the 3x3 conv fused with the DDPM update, device noise.
+// LayerNorm, the early-exit probes, the final LayerNorm + decoder_pred launch (the step's tail lives in step.hip).
 // All arithmetic here is fp32 in both precision modes.
 #include "dd_internal.h"
 
@@ -466,408 +466,6 @@ __global__ void __launch_bounds__(256) reduce_ln_kernel(const ReduceLnArgs a) {
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// Device noise: Philox4x32-10 counter RNG + Box-Muller.  Counter = (element/4, t, 0, 0),
-// key = seed.  Statistically N(0,1); NOT the torch CPU mt19937 stream (that is DD_NOISE_BUFFER).
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox_round(unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3,
-                                             unsigned k0, unsigned k1) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-}
-
-// four N(0,1) values for one pixel (one per channel, C <= 4): counter = (pixel, t), key = seed
-__device__ __forceinline__ f32x4 philox_normal4(unsigned long long seed, unsigned long long pixel, int t) {
-    unsigned c0 = (unsigned)pixel, c1 = (unsigned)(pixel >> 32), c2 = (unsigned)t, c3 = 0x5eedu;
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c0, c1, c2, c3, k0, k1);
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    // Box-Muller on (c0,c1) and (c2,c3); hardware log/sin/cos (|error| ~1e-6) are ample for noise
-    const float ua = ((float)c0 + 1.0f) * 2.3283064365386963e-10f, ub = (float)c1 * 2.3283064365386963e-10f;
-    const float uc = ((float)c2 + 1.0f) * 2.3283064365386963e-10f, ud = (float)c3 * 2.3283064365386963e-10f;
-    const float ra = sqrtf(-2.0f * __logf(ua)), rc = sqrtf(-2.0f * __logf(uc));
-    const float aa = 6.283185307179586f * ub, ac = 6.283185307179586f * ud;
-    return f32x4{ra * __cosf(aa), ra * __sinf(aa), rc * __cosf(ac), rc * __sinf(ac)};
-}
-
-// ------------------------------------------------------------------------------------------
-// Output head (after final LayerNorm + decoder_pred GEMM) + DDPM update: unpatchify ("B (h w) (p1 p2 C) -> B C (h p1) (w p2)",
-// reference models/uvit.py:125-132), 3x3 conv pad 1 (:382), then
-//   x <- sqrt(1/a_t) (x - (1-a_t)/sqrt(1-abar_t) eps) + sigma_t z      (sampler.py:47-56)
-// One thread per pixel, all output channels; eps never goes to HBM unless asked for.
-// G (classifier-free guidance, FinalArgs::pair_B): the pixel's conv runs on the conditional decoder rows of image b and on the unconditional
-// rows of image b + pair_B, eps = eps_c + s (eps_c - eps_u) feeds the update, and x' is written to both images.
-// H (multistep loop, FinalArgs::htab): the table-driven update gains the history term of row t, x' = a x + b eps [+ d h] [+ c z], and
-// h' = p x + q eps goes back to h (image b's slot: guided, the conditional image only).  H = false compiles to the code it did before.
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void final_conv_pixel(const FinalArgs& a, int b, int y, int x, float (&acc)[4]) {
-    const int S = a.S, P = a.P, C = a.C;
-    const int g = S / P, pd = P * P * C;
-#pragma unroll
-    for (int co = 0; co < 4; ++co) acc[co] = co < C ? a.bconv[co] : 0.f;
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy) {
-        const int yy = y + dy - 1;
-        if (yy < 0 || yy >= S) continue;
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-            const int xx = x + dx - 1;
-            if (xx < 0 || xx >= S) continue;
-            const long long tok = (long long)b * a.L + a.extras + (yy / P) * g + (xx / P);
-            const float* u = a.dec + tok * pd + ((yy % P) * P + (xx % P)) * C;
-            for (int ci = 0; ci < C; ++ci) {
-                const float uv = u[ci];
-#pragma unroll
-                for (int co = 0; co < 4; ++co)
-                    if (co < C) acc[co] = fmaf(a.wconv[((co * C + ci) * 3 + dy) * 3 + dx], uv, acc[co]);
-            }
-        }
-    }
-}
-
-template <bool G, bool H>
-__global__ void __launch_bounds__(256) final_kernel(const FinalArgs a) {
-#pragma clang fp contract(off)  // the update must round like the reference: mul, sub, mul, add -- no FMA
-    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int S = a.S, C = a.C;
-    const long long npix = (long long)a.B * S * S;
-    if (pix >= npix) return;
-    const int b = (int)(pix / (S * S)), y = (int)((pix / S) % S), x = (int)(pix % S);
-
-    float acc[4];  // C <= 4
-    final_conv_pixel(a, b, y, x, acc);
-    const long long pair = G ? (long long)a.pair_B * C * S * S : 0;   // element offset of the unconditional twin of image b
-    if constexpr (G) {
-        float accu[4];
-        final_conv_pixel(a, b + a.pair_B, y, x, accu);
-#pragma unroll
-        for (int co = 0; co < 4; ++co) {
-            const float d = acc[co] - accu[co];
-            acc[co] = acc[co] + a.guide_scale * d;
-        }
-    }
-
-    const int t = a.st->t_final;
-    if (a.atab) {   // table-driven loop (dd_sample_affine): t is the step index
-        const AffineRow row = a.atab[t];
-        HistRow hr{0.f, 0.f, 0.f, 0};
-        if constexpr (H) hr = a.htab[t];
-        if (a.advance && pix == 0) { a.st->t = t + 1; a.st->t_model = a.atab[t + 1].t_model; }
-        const bool nz = row.noise != 0 && a.noise_mode == 2;
-        f32x4 zn = {0.f, 0.f, 0.f, 0.f};
-        if (a.x_out && nz) zn = philox_normal4(a.st->seed, (unsigned long long)(pix + (long long)a.b0 * S * S), row.ctr);
-        for (int co = 0; co < C; ++co) {
-            const long long e = (((long long)b * C + co) * S + y) * S + x;
-            const float eps = acc[co];
-            if (a.eps_out) a.eps_out[e] = eps;
-            if constexpr (H) {
-                const float xv = a.x_in[e];
-                float v = row.a * xv + row.b * eps;             // multistep_step_kernel's order and roundings
-                if (hr.hist) v = v + hr.d * a.h[e];
-                if (nz) v = v + row.c * zn[co];
-                a.h[e] = hr.p * xv + hr.q * eps;
-                a.x_out[e] = v;
-                if (G) a.x_out[e + pair] = v;
-            } else if (a.x_out) {
-                float v = row.a * a.x_in[e] + row.b * eps;      // affine_step_kernel's order and roundings
-                if (nz) v = v + row.c * zn[co];
-                a.x_out[e] = v;
-                if (G) a.x_out[e + pair] = v;
-            }
-        }
-        return;
-    }
-    if (a.advance && pix == 0) { a.st->t = t - 1; a.st->t_model = (float)(t - 1); }   // no block of this kernel reads t / t_model
-    const StepCoef cf = a.coef[t < 0 ? 0 : (t > 999 ? 999 : t)];
-    const float sigma = a.variance == 1 ? cf.sigma_beta : cf.sigma_tilde;
-    f32x4 zn = {0.f, 0.f, 0.f, 0.f};
-    if (a.x_out && t > 0 && a.noise_mode == 2) zn = philox_normal4(a.st->seed, (unsigned long long)(pix + (long long)a.b0 * S * S), t);
-    for (int co = 0; co < C; ++co) {
-        const long long e = (((long long)b * C + co) * S + y) * S + x;
-        const float eps = acc[co];
-        if (a.eps_out) a.eps_out[e] = eps;
-        if (a.x_out) {
-            // same operation order and roundings as the reference (no FMA contraction)
-            float v = cf.c1 * (a.x_in[e] - cf.c2 * eps);
-            if (t > 0) {
-                if (a.noise_mode == 1) v = v + sigma * a.z[e];
-                else if (a.noise_mode == 2) v = v + sigma * zn[co];
-            }
-            a.x_out[e] = v;
-            if (G) a.x_out[e + pair] = v;
-        }
-    }
-}
-
-// Tiled variant of final_kernel: a workgroup owns a 16x16 pixel tile of one image and first parks the
-// 18x18xC halo of the unpatchified decoder output in LDS, so every decoder value is fetched once
-// instead of up to nine times.  Same arithmetic, same rounding order (a tap outside the image multiplies a zero of the halo instead of
-// being skipped: fmaf(w, 0, acc) == acc).
-// CT = the channel count at compile time (3, 4; 0: a.C at run time): with it the 9 C^2 conv weights are unconditional scalar loads, one
-// output channel's 9 C at a time, PT = the patch size likewise (the halo gather divides by it) -- the run-time form tested co < C / ci < C around every one of 144 candidate loads (221 scalar branches,
-// 151 s_load_dword, the weights' SGPRs spilled to VGPR lanes: ~3 900 instructions for a kernel every sampling step waits for).
-// G (classifier-free guidance, FinalArgs::pair_B): the workgroup of image b parks TWO halos, the conditional decoder rows of image b and the
-// unconditional ones of image b + pair_B (2 x 13.8 KB of LDS), gathered by one loop so that both sets of loads are in flight together -- the
-// alternative, a second gather into the one halo behind the first conv, would put a second dependent global round trip on a kernel that is
-// a chain of them; then eps = eps_c + s (eps_c - eps_u), and x' goes to images b and b + pair_B.
-// H (multistep loop, FinalArgs::htab): as in final_kernel.  The h pixels are requested with x_in, ahead of the halo gather and without
-// waiting for row t's hist flag (a load behind the step state -> row chain would hold the gather back); a step without history loads
-// them but never lets them into x', so a NaN in h (the first step, an uninitialised buffer) cannot reach the result.
-template <int CT, int PT, bool G, bool H>
-__global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
-#pragma clang fp contract(off)
-    // (row pitch 48 = 16 mod 32 words: the two 16-pixel rows a 32-lane group reads fall into disjoint bank halves; pitch 19 gave every tap read
-    // a 2-way conflict on three banks -- 1.7 conflict cycles per LDS-active cycle in the round 2-4 profiles, for a kernel that is latency, not LDS)
-    constexpr int NH = G ? 2 : 1;     // halos: conditional (, unconditional)
-    __shared__ float u[NH][4][18][48];
-    const int S = a.S, P = PT ? PT : a.P, C = CT ? CT : a.C, g = S / P, pd = P * P * C;
-    const int tiles = (S + 15) / 16;
-    const int b = blockIdx.x / (tiles * tiles), ty = (blockIdx.x / tiles) % tiles, tx = blockIdx.x % tiles;
-    const int tid = threadIdx.x;
-    const int ly = tid >> 4, lx = tid & 15, y = ty * 16 + ly, x = tx * 16 + lx;
-    const bool inside = y < S && x < S;
-    // Everything that does not depend on the decoder output is requested / computed first, so that its latency (step
-    // state -> coefficient row, the x_t pixels, the Philox normals) overlaps the halo gather instead of following it:
-    // the kernel is a chain of dependent memory round trips, not bandwidth.
-    const int t = a.st->t_final;
-    const bool table = a.atab != nullptr;      // dd_sample_affine: t is a step index, the update a x + b eps + c z of row t
-    const AffineRow row = table ? a.atab[t] : AffineRow{0.f, 0.f, 0.f, 0.f, 0, 0, 0, 0};
-    const float t_next = (table && a.advance) ? a.atab[t + 1].t_model : 0.f;
-    const StepCoef cf = a.coef[table ? 0 : (t < 0 ? 0 : (t > 999 ? 999 : t))];
-    const bool draw = table ? (row.noise != 0) : (t > 0);
-    float xin[4] = {0.f, 0.f, 0.f, 0.f}, zin[4] = {0.f, 0.f, 0.f, 0.f};
-    HistRow hr{0.f, 0.f, 0.f, 0};
-    float hin[4] = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (H) hr = a.htab[t];
-    if (inside && a.x_out) {
-#pragma unroll
-        for (int co = 0; co < 4; ++co) {
-            if (co < C) {
-                const long long e = (((long long)b * C + co) * S + y) * S + x;
-                xin[co] = a.x_in[e];
-                if (draw && a.noise_mode == 1) zin[co] = a.z[e];
-                if constexpr (H) hin[co] = a.h[e];     // (not behind the row: used only where hr.hist is set)
-            }
-        }
-    }
-    const int layer = a.layer_B > 0 ? b / a.layer_B : 0;      // (early-exit heads batched into one launch: this image's layer)
-    const float* wconv = a.wconv + layer * a.w_stride;
-    const float* bconv = a.bconv + layer * a.b_stride;
-    for (int idx = tid; idx < NH * 18 * 18; idx += 256) {
-        const int hh = NH == 1 ? 0 : idx / (18 * 18), hi = NH == 1 ? idx : idx - hh * (18 * 18);
-        const int hy = hi / 18, hx = hi % 18;
-        const int yy = ty * 16 + hy - 1, xx = tx * 16 + hx - 1;
-        const bool in = yy >= 0 && yy < S && xx >= 0 && xx < S;
-        const float* src = a.dec + ((long long)(b + hh * a.pair_B) * a.L + a.extras + (in ? (yy / P) * g + (xx / P) : 0)) * pd +
-                           (in ? ((yy % P) * P + (xx % P)) * C : 0);
-        for (int ci = 0; ci < C; ++ci) u[hh][ci][hy][hx] = in ? src[ci] : 0.f;
-    }
-    f32x4 zn = {0.f, 0.f, 0.f, 0.f};
-    if (inside && a.x_out && draw && a.noise_mode == 2)
-        zn = philox_normal4(a.st->seed, ((unsigned long long)(b + a.b0) * S + y) * S + x, table ? row.ctr : t);   // same pixel id as the untiled kernel (b0: this launch's first image within the whole batch)
-    __syncthreads();
-    if (a.advance && blockIdx.x == 0 && tid == 0) {   // no block of this kernel reads t / t_model
-        const int tn = table ? t + 1 : t - 1;
-        a.st->t = tn;
-        a.st->t_model = table ? t_next : (float)tn;
-    }
-    if (!inside) return;
-    constexpr int CM = CT ? CT : 4;
-    float acc[NH][4] = {};
-#pragma unroll
-    for (int hh = 0; hh < NH; ++hh) {
-        float uu[CM][9];
-#pragma unroll
-        for (int ci = 0; ci < CM; ++ci)
-#pragma unroll
-            for (int k = 0; k < 9; ++k) uu[ci][k] = ci < C ? u[hh][ci][ly + k / 3][lx + k % 3] : 0.f;
-#pragma unroll
-        for (int co = 0; co < CM; ++co) {
-            if (co < C) {
-                // uniform address, constant address space: scalar loads (s_load_dwordx8 ...), one output channel's 9 C weights live at a time
-                const __attribute__((address_space(4))) float* wp = (const __attribute__((address_space(4))) float*)(wconv + co * C * 9);
-                float v = bconv[co];
-#pragma unroll
-                for (int k = 0; k < 9; ++k)
-#pragma unroll
-                    for (int ci = 0; ci < CM; ++ci)
-                        if (ci < C) v = fmaf(wp[ci * 9 + k], uu[ci][k], v);
-                acc[hh][co] = v;
-            }
-        }
-    }
-    if constexpr (G) {
-#pragma unroll
-        for (int co = 0; co < 4; ++co) {
-            const float d = acc[0][co] - acc[1][co];
-            acc[0][co] = acc[0][co] + a.guide_scale * d;
-        }
-    }
-    const long long pair = G ? (long long)a.pair_B * C * S * S : 0;   // element offset of the unconditional twin of image b
-    const float sigma = a.variance == 1 ? cf.sigma_beta : cf.sigma_tilde;
-#pragma unroll
-    for (int co = 0; co < 4; ++co) {
-        if (co < C) {
-            const long long e = (((long long)b * C + co) * S + y) * S + x;
-            const float eps = acc[0][co];
-            if (a.eps_out) a.eps_out[e] = eps;
-            if (a.x_out) {
-                float v;
-                if (table) {
-                    v = row.a * xin[co] + row.b * eps;                  // affine_step_kernel's order and roundings
-                    if constexpr (H) {                                  // multistep_step_kernel's
-                        if (hr.hist) v = v + hr.d * hin[co];
-                        a.h[e] = hr.p * xin[co] + hr.q * eps;
-                    }
-                    if (draw && a.noise_mode == 1) v = v + row.c * zin[co];
-                    else if (draw && a.noise_mode == 2) v = v + row.c * zn[co];
-                } else {
-                    v = cf.c1 * (xin[co] - cf.c2 * eps);
-                    if (t > 0) {
-                        if (a.noise_mode == 1) v = v + sigma * zin[co];
-                        else if (a.noise_mode == 2) v = v + sigma * zn[co];
-                    }
-                }
-                a.x_out[e] = v;
-                if (G) a.x_out[e + pair] = v;
-            }
-        }
-    }
-}
-
-__global__ void ddpm_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
-                                 const float* __restrict__ z, float* __restrict__ out, StepCoef c,
-                                 int use_noise, int variance_beta, long long n) {
-#pragma clang fp contract(off)
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float v = c.c1 * (x[i] - c.c2 * eps[i]);
-    if (use_noise) v = v + (variance_beta ? c.sigma_beta : c.sigma_tilde) * z[i];
-    out[i] = v;
-}
-
-// The same update driven by the device-resident step state (dd_sample_early_exit): t = st->t_final, coefficients from the
-// context's table, z from the Philox generator of the fused step (same counter: pixel, t); advance: one thread hands t - 1
-// to the next step.  x [B, C, S, S] in place; one thread per pixel.
-__global__ void __launch_bounds__(256) ddpm_step_state_kernel(float* __restrict__ x, const float* __restrict__ eps, StepState* st,
-                                                              const StepCoef* __restrict__ coef, int B, int C, int S,
-                                                              int noise_mode, int advance, long long pix0) {
-#pragma clang fp contract(off)
-    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long hw = (long long)S * S;
-    const int t = st->t_final;
-    if (advance && pix == 0) { st->t = t - 1; st->t_model = (float)(t - 1); }   // no block of this kernel reads t / t_model
-    if (pix >= (long long)B * hw) return;
-    const StepCoef cf = coef[t < 0 ? 0 : (t > 999 ? 999 : t)];
-    f32x4 zn = {0.f, 0.f, 0.f, 0.f};
-    if (t > 0 && noise_mode == 2) zn = philox_normal4(st->seed, (unsigned long long)(pix + pix0), t);     // pix0: a half-batch chain's first pixel within the whole batch
-    const long long b = pix / hw, p = pix - b * hw;
-    for (int c = 0; c < C; ++c) {
-        const long long e = (b * C + c) * hw + p;
-        float v = cf.c1 * (x[e] - cf.c2 * eps[e]);
-        if (t > 0 && noise_mode == 2) v = v + cf.sigma_tilde * zn[c];
-        x[e] = v;
-    }
-}
-
-// ee_select_kernel and the update above in one launch (the device-resident early-exit loop: two launches less on every step's serial tail,
-// and the selected model output never travels through HBM): per pixel, the image's exit layer from cls (ee_select_kernel's rule), then the
-// update on (outputs ++ [eps])[idx] -- the same operations in the same order as the two kernels.
-__global__ void __launch_bounds__(256) ee_select_step_kernel(float* __restrict__ x, const float* __restrict__ outs, const float* __restrict__ eps,
-                                                             const float* __restrict__ cls, float thr, int depth, int* __restrict__ idx_out,
-                                                             int idx_stride, int idx_col0, StepState* st, const StepCoef* __restrict__ coef,
-                                                             int B, int C, int S, int noise_mode, int advance, long long pix0) {
-#pragma clang fp contract(off)
-    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long hw = (long long)S * S;
-    const int t = st->t_final;
-    if (advance && pix == 0) { st->t = t - 1; st->t_model = (float)(t - 1); }   // no block of this kernel reads t / t_model
-    if (pix >= (long long)B * hw) return;
-    const StepCoef cf = coef[t < 0 ? 0 : (t > 999 ? 999 : t)];
-    f32x4 zn = {0.f, 0.f, 0.f, 0.f};
-    if (t > 0 && noise_mode == 2) zn = philox_normal4(st->seed, (unsigned long long)(pix + pix0), t);
-    const long long b = pix / hw, p = pix - b * hw;
-    int idx = -1;
-    for (int k = 0; k < depth && idx < 0; ++k)
-        if (cls[(long long)k * B + b] <= thr) idx = k;
-    if (idx < 0) idx = (0.0f <= thr) ? depth : 0;
-    if (idx_out && p == 0) idx_out[(long long)t * idx_stride + idx_col0 + b] = idx;     // row t of indices_by_timestep (eesampler.py:71)
-    const float* src = idx == depth ? eps : outs + (long long)idx * B * C * hw;
-    for (int c = 0; c < C; ++c) {
-        const long long e = (b * C + c) * hw + p;
-        float v = cf.c1 * (x[e] - cf.c2 * src[e]);
-        if (t > 0 && noise_mode == 2) v = v + cf.sigma_tilde * zn[c];
-        x[e] = v;
-    }
-}
-
-// out = a*x + b*m + c*z, each product rounded (no FMA contraction): the common form of the reference's
-// predict_original / predict_previous post-processing (sampler.py:59-79) and of a DDIM step (:112-120).
-__global__ void affine_step_kernel(const float* __restrict__ x, const float* __restrict__ m,
-                                   const float* __restrict__ z, float* __restrict__ out, float a, float b, float c,
-                                   long long n) {
-#pragma clang fp contract(off)
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float v = a * x[i] + b * m[i];
-    if (z) v = v + c * z[i];
-    out[i] = v;
-}
-
-// out = a*x + b*m [+ d*h if use_hist] [+ c*z if z], then h = p*x + q*m, each product rounded, the terms added in this order: the
-// multistep row (dd_multistep_step, DPM-Solver++), the update the multistep final kernels fuse.  h is not read when use_hist is 0;
-// x and out may alias (in place), h must alias neither.
-__global__ void multistep_step_kernel(const float* x, const float* __restrict__ m, const float* __restrict__ z, float* h, float* out,
-                                      float a, float b, float c, float d, float p, float q, int use_hist, long long n) {
-#pragma clang fp contract(off)
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float xv = x[i], mv = m[i];
-    float v = a * xv + b * mv;
-    if (use_hist) v = v + d * h[i];
-    if (z) v = v + c * z[i];
-    h[i] = p * xv + q * mv;
-    out[i] = v;
-}
-
-__global__ void set_state_kernel(StepState* st, int t, unsigned long long seed) {
-    st->t = t;
-    st->t_final = t;
-    st->t_model = (float)t;
-    st->seed = seed;
-}
-__global__ void set_state_table_kernel(StepState* st, const AffineRow* atab, unsigned long long seed) {
-    st->t = 0;
-    st->t_final = 0;
-    st->t_model = atab[0].t_model;
-    st->seed = seed;
-}
-// the label rows of one guided chain: [y [0, B) | null_label x B]
-__global__ void __launch_bounds__(256) guided_labels_kernel(const long long* __restrict__ y, long long* __restrict__ out, int B, long long null_label) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < 2 * B) out[i] = i < B ? y[i] : null_label;
-}
-__global__ void set_state_float_kernel(StepState* st, float t) {
-    st->t = (int)t;
-    st->t_final = (int)t;
-    st->t_model = t;
-}
-
-// reference sampler.py:145-146: samples = rearrange((x + 1) / 2, "b c h w -> b h w c").  One thread per pixel: the NCHW
-// reads are coalesced per channel plane, the NHWC writes are C contiguous floats per thread.
-__global__ void __launch_bounds__(256) to_images_kernel(const float* __restrict__ x, float* __restrict__ out, int B, int C, int S) {
-    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long hw = (long long)S * S;
-    if (pix >= (long long)B * hw) return;
-    const long long b = pix / hw, p = pix - b * hw;
-    for (int c = 0; c < C; ++c) out[pix * C + c] = (x[(b * C + c) * hw + p] + 1.0f) / 2.0f;
-}
-
 // ---- early-exit baseline (reference models/early_exit.py, eesampler.py) --------------------------------------
 // MLPProbe (early_exit.py:31-37): u[b] = mean over the L tokens of sigmoid(x[b,l,:] . w + bias).  One workgroup per
 // image, one wave per token row (coalesced 256 B segments), fixed-order reductions (deterministic per image).
@@ -976,45 +574,6 @@ __global__ void __launch_bounds__(256) ee_attn_probe_kernel(const float* __restr
     }
     part = block_reduce(part, false);
     if (tid == 0) out[b] = part + w.b2[0];
-}
-
-// eesampler.py:61-67: idx[b] = first layer i in [0, depth] with c[i][b] <= threshold, where c[depth][b] = 0 closes the
-// list (torch.argmax of an all-False column is 0); model_output[b] = (outputs ++ [eps])[idx[b]][b].
-__global__ void ee_select_kernel(const float* __restrict__ outs, const float* __restrict__ eps, const float* __restrict__ cls,
-                                 float thr, int depth, int B, long long chw, float* __restrict__ mo, int* __restrict__ idx_out,
-                                 const StepState* __restrict__ st, int idx_stride, int idx_col0) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)B * chw) return;
-    // row t of indices_by_timestep (eesampler.py:71); a half-batch chain writes its columns [idx_col0, idx_col0 + B) of the whole batch's row
-    if (st && idx_out) idx_out += (long long)st->t_final * idx_stride + idx_col0;
-    const int b = (int)(i / chw);
-    int idx = -1;
-    for (int k = 0; k < depth && idx < 0; ++k)
-        if (cls[(long long)k * B + b] <= thr) idx = k;
-    if (idx < 0) idx = (0.0f <= thr) ? depth : 0;
-    mo[i] = idx == depth ? eps[i] : outs[(long long)idx * B * chw + i];
-    if (idx_out && i == (long long)b * chw) idx_out[b] = idx;
-}
-
-// eesampler.py:70: per-layer mean over the batch of the predicted errors (logging)
-// (scale = 1 / B: the mean; scale = 1: the plain sum -- a half-batch chain's share, ee_mean_combine_kernel divides)
-__global__ void __launch_bounds__(64) ee_batch_mean_kernel(const float* __restrict__ cls, float* __restrict__ err, int B,
-                                                           const StepState* __restrict__ st, float scale) {
-    const int k = blockIdx.x, lane = threadIdx.x;
-    if (st) err += (long long)st->t_final * gridDim.x;            // row t of error_prediction_by_timestep (eesampler.py:70)
-    float a = 0.f;
-    for (int b = lane; b < B; b += 64) a += cls[(long long)k * B + b];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o);
-    if (lane == 0) err[k] = scale == 1.0f ? a : a / (float)B;
-}
-
-// rows [t_lo, t_hi] of error_prediction_by_timestep from the two chains' per-step sums, in a fixed order: (chain 0 + chain 1) / B
-__global__ void ee_mean_combine_kernel(const float* __restrict__ s0, const float* __restrict__ s1, float* __restrict__ err, int depth, int t_lo, int t_hi, int B) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x, n = (t_hi - t_lo + 1) * depth;
-    if (i >= n) return;
-    const long long e = (long long)t_lo * depth + i;
-    err[e] = (s0[e] + s1[e]) / (float)B;
 }
 
 }  // namespace
@@ -1444,60 +1003,6 @@ hipError_t launch_fill_random(T* p, long long n, unsigned seed, float scale, hip
 template hipError_t launch_fill_random<bf16_t>(bf16_t*, long long, unsigned, float, hipStream_t);
 template hipError_t launch_fill_random<float>(float*, long long, unsigned, float, hipStream_t);
 
-template <bool H>
-static void launch_final_kind(const FinalArgs& a, hipStream_t s) {
-    if (a.S >= 16) {
-        const int tiles = (a.S + 15) / 16;
-        const dim3 grid(a.B * tiles * tiles);
-        if (a.pair_B > 0) {   // classifier-free guidance: a.B images, 2 a.B decoder images
-            if (a.C == 3 && a.P == 4) hipLaunchKernelGGL((final_tiled_kernel<3, 4, true, H>), grid, dim3(256), 0, s, a);
-            else if (a.C == 3 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<3, 2, true, H>), grid, dim3(256), 0, s, a);
-            else if (a.C == 4 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<4, 2, true, H>), grid, dim3(256), 0, s, a);   // ImageNet-256 latents
-            else hipLaunchKernelGGL((final_tiled_kernel<0, 0, true, H>), grid, dim3(256), 0, s, a);
-            return;
-        }
-        if (a.C == 3 && a.P == 4) hipLaunchKernelGGL((final_tiled_kernel<3, 4, false, H>), grid, dim3(256), 0, s, a);          // CelebA-64, ImageNet-64
-        else if (a.C == 3 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<3, 2, false, H>), grid, dim3(256), 0, s, a);     // CIFAR-10
-        else if (a.C == 4 && a.P == 2) hipLaunchKernelGGL((final_tiled_kernel<4, 2, false, H>), grid, dim3(256), 0, s, a);     // latent 32 x 32 x 4
-        else hipLaunchKernelGGL((final_tiled_kernel<0, 0, false, H>), grid, dim3(256), 0, s, a);
-        return;
-    }
-    const long long npix = (long long)a.B * a.S * a.S;
-    if (a.pair_B > 0) hipLaunchKernelGGL((final_kernel<true, H>), dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((final_kernel<false, H>), dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, a);
-}
-
-hipError_t launch_final(const FinalArgs& a, hipStream_t s) {
-    if (a.pair_B > 0 && (a.pair_B != a.B || a.layer_B > 0)) return hipErrorInvalidValue;
-    if (a.htab) {         // the multistep loop: a table-driven step that writes x and h
-        if (!a.atab || !a.h || !a.x_in || !a.x_out || a.layer_B > 0) return hipErrorInvalidValue;
-        launch_final_kind<true>(a, s);
-    } else {
-        launch_final_kind<false>(a, s);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_ddpm_step(const float* x, const float* eps, const float* z, float* out, StepCoef c,
-                            int use_noise, long long n, hipStream_t s) {
-    // variance selection is folded by the caller into c.sigma_tilde
-    hipLaunchKernelGGL(ddpm_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, eps, z, out, c,
-                       use_noise, 0, n);
-    return hipGetLastError();
-}
-
-hipError_t launch_affine_step(const float* x, const float* m, const float* z, float* out, float a, float b, float c,
-                              long long n, hipStream_t s) {
-    hipLaunchKernelGGL(affine_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, m, z, out, a, b, c, n);
-    return hipGetLastError();
-}
-
-hipError_t launch_multistep_step(const float* x, const float* m, const float* z, float* h, float* out, float a, float b, float c, float d,
-                                 float p, float q, int use_hist, long long n, hipStream_t s) {
-    hipLaunchKernelGGL(multistep_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, m, z, h, out, a, b, c, d, p, q, use_hist, n);
-    return hipGetLastError();
-}
-
 hipError_t launch_ee_probe(const float* x, const float* w_base, const float* bias_base, float* out, float* srow, int B, int L, int D,
                            const StepState* st, int t_mul, int add, hipStream_t s) {
     hipLaunchKernelGGL(ee_probe_rows_kernel, dim3(B, 8), dim3(256), 0, s, x, w_base, bias_base, srow, L, D, st, t_mul, add);
@@ -1511,57 +1016,6 @@ hipError_t launch_ee_probe_reduce(const float* srow, float* out, int rows, int L
 }
 hipError_t launch_ee_attn_probe(const float* x, const AttnProbeW& w, float* out, int B, int L, int D, hipStream_t s) {
     hipLaunchKernelGGL(ee_attn_probe_kernel, dim3(B), dim3(256), (size_t)(L + 3 * D) * sizeof(float), s, x, w, out, L, D);
-    return hipGetLastError();
-}
-hipError_t launch_ee_select(const float* outs, const float* eps, const float* cls, float thr, int depth, int B, long long chw,
-                            float* mo, int* idx, float* err_mean, const StepState* st, hipStream_t s, int idx_stride, int idx_col0, bool sums) {
-    const long long n = (long long)B * chw;
-    hipLaunchKernelGGL(ee_select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, outs, eps, cls, thr, depth, B, chw, mo, idx, st,
-                       idx_stride > 0 ? idx_stride : B, idx_col0);
-    if (err_mean) hipLaunchKernelGGL(ee_batch_mean_kernel, dim3(depth), dim3(64), 0, s, cls, err_mean, B, st, sums ? 1.0f : 0.0f);
-    return hipGetLastError();
-}
-hipError_t launch_ee_select_step(float* x, const float* outs, const float* eps, const float* cls, float thr, int depth, int* idx, float* err_mean,
-                                 int idx_stride, int idx_col0, bool sums, StepState* st, const StepCoef* coef, int B, int C, int S,
-                                 int noise_mode, int advance, hipStream_t s) {
-    const long long npix = (long long)B * S * S;
-    if (err_mean) hipLaunchKernelGGL(ee_batch_mean_kernel, dim3(depth), dim3(64), 0, s, cls, err_mean, B, st, sums ? 1.0f : 0.0f);
-    hipLaunchKernelGGL(ee_select_step_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, x, outs, eps, cls, thr, depth, idx,
-                       idx_stride > 0 ? idx_stride : B, idx_col0, st, coef, B, C, S, noise_mode, advance, (long long)idx_col0 * S * S);
-    return hipGetLastError();
-}
-hipError_t launch_ee_mean_combine(const float* s0, const float* s1, float* err, int depth, int t_lo, int t_hi, int B, hipStream_t s) {
-    const int n = (t_hi - t_lo + 1) * depth;
-    hipLaunchKernelGGL(ee_mean_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, s0, s1, err, depth, t_lo, t_hi, B);
-    return hipGetLastError();
-}
-hipError_t launch_ddpm_step_state(float* x, const float* eps, StepState* st, const StepCoef* coef, int B, int C, int S,
-                                  int noise_mode, int advance, hipStream_t s, int b0) {
-    const long long npix = (long long)B * S * S;
-    hipLaunchKernelGGL(ddpm_step_state_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, x, eps, st, coef, B, C, S,
-                       noise_mode, advance, (long long)b0 * S * S);
-    return hipGetLastError();
-}
-
-hipError_t launch_set_state(StepState* st, int t, unsigned long long seed, hipStream_t s) {
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, s, st, t, seed);
-    return hipGetLastError();
-}
-hipError_t launch_set_state_table(StepState* st, const AffineRow* atab, unsigned long long seed, hipStream_t s) {
-    hipLaunchKernelGGL(set_state_table_kernel, dim3(1), dim3(1), 0, s, st, atab, seed);
-    return hipGetLastError();
-}
-hipError_t launch_guided_labels(const long long* y, long long* out, int B, long long null_label, hipStream_t s) {
-    hipLaunchKernelGGL(guided_labels_kernel, dim3((unsigned)((2 * B + 255) / 256)), dim3(256), 0, s, y, out, B, null_label);
-    return hipGetLastError();
-}
-hipError_t launch_set_state_float(StepState* st, float t, hipStream_t s) {
-    hipLaunchKernelGGL(set_state_float_kernel, dim3(1), dim3(1), 0, s, st, t);
-    return hipGetLastError();
-}
-hipError_t launch_to_images(const float* x, float* out, int B, int C, int S, hipStream_t s) {
-    const long long npix = (long long)B * S * S;
-    hipLaunchKernelGGL(to_images_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, x, out, B, C, S);
     return hipGetLastError();
 }
 

@@ -1,0 +1,339 @@
+// The tail of a sampling step (gfx950): the output head (unpatchify + 3x3 conv) fused with the update, the unfused step kernels, the
+// early-exit selection, the step-state setters and the image conversion.  The update itself is defined once, in step_update.h.
+// All arithmetic here is fp32 in both precision modes.
+#include "dd_internal.h"
+#include "step_update.h"
+
+namespace dd {
+namespace {
+
+// ------------------------------------------------------------------------------------------
+// Output head (after final LayerNorm + decoder_pred GEMM) + the step update: unpatchify ("B (h w) (p1 p2 C) -> B C (h p1) (w p2)",
+// reference models/uvit.py:125-132), 3x3 conv pad 1 (:382), then the update of step_update.h on the pixel; eps never goes to HBM
+// unless asked for.  A workgroup owns a 16x16 pixel tile of one image and first parks the 18x18xC halo of the unpatchified decoder
+// output in LDS, so every decoder value is fetched once instead of up to nine times (a tap outside the image multiplies a zero of the
+// halo: fmaf(w, 0, acc) == acc).  An image smaller than a tile (the test models' 8x8) is one tile with 64 live lanes.
+// CT = the channel count at compile time (3, 4; 0: a.C at run time): with it the 9 C^2 conv weights are unconditional scalar loads, one
+// output channel's 9 C at a time, PT = the patch size likewise (the halo gather divides by it) -- the run-time form tested co < C / ci < C around every one of 144 candidate loads (221 scalar branches,
+// 151 s_load_dword, the weights' SGPRs spilled to VGPR lanes: ~3 900 instructions for a kernel every sampling step waits for).
+// G (classifier-free guidance, FinalArgs::pair_B): the workgroup of image b parks TWO halos, the conditional decoder rows of image b and the
+// unconditional ones of image b + pair_B (2 x 13.8 KB of LDS), gathered by one loop so that both sets of loads are in flight together -- the
+// alternative, a second gather into the one halo behind the first conv, would put a second dependent global round trip on a kernel that is
+// a chain of them; then eps = eps_c + s (eps_c - eps_u) feeds the update, and x' goes to images b and b + pair_B.
+// H (multistep loop, FinalArgs::htab): the table-driven update gains the history term of row t, and h' goes back to h (image b's slot:
+// guided, the conditional image only); H = false compiles to the code without it.  The h pixels are requested with x_in, ahead of the halo
+// gather and without waiting for row t's hist flag (a load behind the step state -> row chain would hold the gather back); a step without
+// history loads them but never lets them into x', so a NaN in h (the first step, an uninitialised buffer) cannot reach the result.
+// ------------------------------------------------------------------------------------------
+template <int CT, int PT, bool G, bool H>
+__global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
+#pragma clang fp contract(off)
+    // (row pitch 48 = 16 mod 32 words: the two 16-pixel rows a 32-lane group reads fall into disjoint bank halves; pitch 19 gave every tap read
+    // a 2-way conflict on three banks -- 1.7 conflict cycles per LDS-active cycle in the round 2-4 profiles, for a kernel that is latency, not LDS)
+    constexpr int NH = G ? 2 : 1;     // halos: conditional (, unconditional)
+    __shared__ float u[NH][4][18][48];
+    const int S = a.S, P = PT ? PT : a.P, C = CT ? CT : a.C, g = S / P, pd = P * P * C;
+    const int tiles = (S + 15) / 16;
+    const int b = blockIdx.x / (tiles * tiles), ty = (blockIdx.x / tiles) % tiles, tx = blockIdx.x % tiles;
+    const int tid = threadIdx.x;
+    const int ly = tid >> 4, lx = tid & 15, y = ty * 16 + ly, x = tx * 16 + lx;
+    const bool inside = y < S && x < S;
+    // Everything that does not depend on the decoder output is requested / computed first, so that its latency (step
+    // state -> coefficient row, the x_t pixels, the Philox normals) overlaps the halo gather instead of following it:
+    // the kernel is a chain of dependent memory round trips, not bandwidth.
+    const StepRule<H> rule(a.st, a.coef, a.atab, a.htab, a.noise_mode, a.variance, a.advance);
+    float xin[4] = {0.f, 0.f, 0.f, 0.f}, zin[4] = {0.f, 0.f, 0.f, 0.f}, hin[4] = {0.f, 0.f, 0.f, 0.f};
+    if (inside && a.x_out) {
+#pragma unroll
+        for (int co = 0; co < 4; ++co) {
+            if (co < C) {
+                const long long e = (((long long)b * C + co) * S + y) * S + x;
+                xin[co] = a.x_in[e];
+                if (rule.reads_z()) zin[co] = a.z[e];
+                if constexpr (H) hin[co] = a.h[e];     // (not behind the row: used only where hr.hist is set)
+            }
+        }
+    }
+    const int layer = a.layer_B > 0 ? b / a.layer_B : 0;      // (early-exit heads batched into one launch: this image's layer)
+    const float* wconv = a.wconv + layer * a.w_stride;
+    const float* bconv = a.bconv + layer * a.b_stride;
+    for (int idx = tid; idx < NH * 18 * 18; idx += 256) {
+        const int hh = NH == 1 ? 0 : idx / (18 * 18), hi = NH == 1 ? idx : idx - hh * (18 * 18);
+        const int hy = hi / 18, hx = hi % 18;
+        const int yy = ty * 16 + hy - 1, xx = tx * 16 + hx - 1;
+        const bool in = yy >= 0 && yy < S && xx >= 0 && xx < S;
+        const float* src = a.dec + ((long long)(b + hh * a.pair_B) * a.L + a.extras + (in ? (yy / P) * g + (xx / P) : 0)) * pd +
+                           (in ? ((yy % P) * P + (xx % P)) * C : 0);
+        for (int ci = 0; ci < C; ++ci) u[hh][ci][hy][hx] = in ? src[ci] : 0.f;
+    }
+    if (inside && a.x_out && rule.draws()) {   // pixel id within the WHOLE batch (b0: this launch's first image): a half-batch chain draws the z the undivided batch would
+        const f32x4 zn = philox_normal4(a.st->seed, ((unsigned long long)(b + a.b0) * S + y) * S + x, rule.ctr);
+#pragma unroll
+        for (int co = 0; co < 4; ++co) zin[co] = zn[co];
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && tid == 0) rule.advance(a.st);
+    if (!inside) return;
+    constexpr int CM = CT ? CT : 4;
+    float acc[NH][4] = {};
+#pragma unroll
+    for (int hh = 0; hh < NH; ++hh) {
+        float uu[CM][9];
+#pragma unroll
+        for (int ci = 0; ci < CM; ++ci)
+#pragma unroll
+            for (int k = 0; k < 9; ++k) uu[ci][k] = ci < C ? u[hh][ci][ly + k / 3][lx + k % 3] : 0.f;
+#pragma unroll
+        for (int co = 0; co < CM; ++co) {
+            if (co < C) {
+                // uniform address, constant address space: scalar loads (s_load_dwordx8 ...), one output channel's 9 C weights live at a time
+                const __attribute__((address_space(4))) float* wp = (const __attribute__((address_space(4))) float*)(wconv + co * C * 9);
+                float v = bconv[co];
+#pragma unroll
+                for (int k = 0; k < 9; ++k)
+#pragma unroll
+                    for (int ci = 0; ci < CM; ++ci)
+                        if (ci < C) v = fmaf(wp[ci * 9 + k], uu[ci][k], v);
+                acc[hh][co] = v;
+            }
+        }
+    }
+    if constexpr (G) {
+#pragma unroll
+        for (int co = 0; co < 4; ++co) {
+            const float d = acc[0][co] - acc[1][co];
+            acc[0][co] = acc[0][co] + a.guide_scale * d;
+        }
+    }
+    const long long pair = G ? (long long)a.pair_B * C * S * S : 0;   // element offset of the unconditional twin of image b
+#pragma unroll
+    for (int co = 0; co < 4; ++co) {
+        if (co < C) {
+            const long long e = (((long long)b * C + co) * S + y) * S + x;
+            const float eps = acc[0][co];
+            if (a.eps_out) a.eps_out[e] = eps;
+            if (a.x_out) {
+                const float v = rule.apply(xin[co], eps, zin[co], hin[co]);
+                if constexpr (H) a.h[e] = rule.history(xin[co], eps);
+                a.x_out[e] = v;
+                if (G) a.x_out[e + pair] = v;
+            }
+        }
+    }
+}
+
+// the unfused update on n elements from coefficients passed by value (dd_ddpm_step / dd_ddpm_step_coef)
+__global__ void ddpm_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                 const float* __restrict__ z, float* __restrict__ out, StepCoef c,
+                                 int use_noise, int variance_beta, long long n) {
+#pragma clang fp contract(off)
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const StepRule<false> rule(c, variance_beta != 0, use_noise != 0);
+    out[i] = rule.apply(x[i], eps[i], rule.reads_z() ? z[i] : 0.f, 0.f);
+}
+
+// Exit selection and the update in one launch (the device-resident early-exit loop: two launches less on every step's serial tail,
+// and the selected model output never travels through HBM): per pixel, the image's exit layer from cls, then the update on
+// (outputs ++ [eps])[idx], z from the Philox generator of the fused step (same counter: pixel, t).  x [B, C, S, S] in place; pix0: a
+// half-batch chain's first pixel within the whole batch.
+__global__ void __launch_bounds__(256) ee_select_step_kernel(float* __restrict__ x, const float* __restrict__ outs, const float* __restrict__ eps,
+                                                             const float* __restrict__ cls, float thr, int depth, int* __restrict__ idx_out,
+                                                             int idx_stride, int idx_col0, StepState* st, const StepCoef* __restrict__ coef,
+                                                             int B, int C, int S, int noise_mode, int advance, long long pix0) {
+#pragma clang fp contract(off)
+    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long hw = (long long)S * S;
+    const StepRule<false> rule(st, coef, nullptr, nullptr, noise_mode == 2 ? 2 : 0, 0, advance);   // (this loop draws on the device or not at all)
+    if (pix == 0) rule.advance(st);
+    if (pix >= (long long)B * hw) return;
+    f32x4 zn = {0.f, 0.f, 0.f, 0.f};
+    if (rule.draws()) zn = philox_normal4(st->seed, (unsigned long long)(pix + pix0), rule.ctr);
+    const long long b = pix / hw, p = pix - b * hw;
+    const int idx = ee_exit_layer(cls, thr, depth, B, (int)b);
+    if (idx_out && p == 0) idx_out[(long long)rule.t * idx_stride + idx_col0 + b] = idx;     // row t of indices_by_timestep (eesampler.py:71)
+    const float* src = idx == depth ? eps : outs + (long long)idx * B * C * hw;
+    for (int c = 0; c < C; ++c) {
+        const long long e = (b * C + c) * hw + p;
+        x[e] = rule.apply(x[e], src[e], zn[c], 0.f);
+    }
+}
+
+// out = a*x + b*m + c*z, each product rounded (no FMA contraction): the common form of the reference's
+// predict_original / predict_previous post-processing (sampler.py:59-79) and of a DDIM step (:112-120).
+__global__ void affine_step_kernel(const float* __restrict__ x, const float* __restrict__ m,
+                                   const float* __restrict__ z, float* __restrict__ out, float a, float b, float c,
+                                   long long n) {
+#pragma clang fp contract(off)
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const StepRule<false> rule(a, b, c, HistRow{0.f, 0.f, 0.f, 0}, z != nullptr);
+    out[i] = rule.apply(x[i], m[i], rule.reads_z() ? z[i] : 0.f, 0.f);
+}
+
+// out = a*x + b*m [+ d*h if use_hist] [+ c*z if z], then h = p*x + q*m: the multistep row (dd_multistep_step, DPM-Solver++), the update the
+// multistep output head fuses.  h is not read when use_hist is 0; x and out may alias (in place), h must alias neither.
+__global__ void multistep_step_kernel(const float* x, const float* __restrict__ m, const float* __restrict__ z, float* h, float* out,
+                                      float a, float b, float c, float d, float p, float q, int use_hist, long long n) {
+#pragma clang fp contract(off)
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const StepRule<true> rule(a, b, c, HistRow{d, p, q, use_hist}, z != nullptr);
+    const float xv = x[i], mv = m[i];
+    const float v = rule.apply(xv, mv, rule.reads_z() ? z[i] : 0.f, rule.hr.hist ? h[i] : 0.f);
+    h[i] = rule.history(xv, mv);
+    out[i] = v;
+}
+
+__global__ void set_state_kernel(StepState* st, int t, unsigned long long seed) {
+    st->t = t;
+    st->t_final = t;
+    st->t_model = (float)t;
+    st->seed = seed;
+}
+__global__ void set_state_table_kernel(StepState* st, const AffineRow* atab, unsigned long long seed) {
+    st->t = 0;
+    st->t_final = 0;
+    st->t_model = atab[0].t_model;
+    st->seed = seed;
+}
+// the label rows of one guided chain: [y [0, B) | null_label x B]
+__global__ void __launch_bounds__(256) guided_labels_kernel(const long long* __restrict__ y, long long* __restrict__ out, int B, long long null_label) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < 2 * B) out[i] = i < B ? y[i] : null_label;
+}
+__global__ void set_state_float_kernel(StepState* st, float t) {
+    st->t = (int)t;
+    st->t_final = (int)t;
+    st->t_model = t;
+}
+
+// reference sampler.py:145-146: samples = rearrange((x + 1) / 2, "b c h w -> b h w c").  One thread per pixel: the NCHW
+// reads are coalesced per channel plane, the NHWC writes are C contiguous floats per thread.
+__global__ void __launch_bounds__(256) to_images_kernel(const float* __restrict__ x, float* __restrict__ out, int B, int C, int S) {
+    const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long hw = (long long)S * S;
+    if (pix >= (long long)B * hw) return;
+    const long long b = pix / hw, p = pix - b * hw;
+    for (int c = 0; c < C; ++c) out[pix * C + c] = (x[(b * C + c) * hw + p] + 1.0f) / 2.0f;
+}
+
+// dd_early_exit_select: model_output[b] = (outputs ++ [eps])[idx[b]][b] with idx[b] = the image's exit layer (ee_exit_layer)
+__global__ void ee_select_kernel(const float* __restrict__ outs, const float* __restrict__ eps, const float* __restrict__ cls,
+                                 float thr, int depth, int B, long long chw, float* __restrict__ mo, int* __restrict__ idx_out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)B * chw) return;
+    const int b = (int)(i / chw);
+    const int idx = ee_exit_layer(cls, thr, depth, B, b);
+    mo[i] = idx == depth ? eps[i] : outs[(long long)idx * B * chw + i];
+    if (idx_out && i == (long long)b * chw) idx_out[b] = idx;
+}
+
+// eesampler.py:70: per-layer mean over the batch of the predicted errors (logging)
+// (scale = 1 / B: the mean; scale = 1: the plain sum -- a half-batch chain's share, ee_mean_combine_kernel divides)
+__global__ void __launch_bounds__(64) ee_batch_mean_kernel(const float* __restrict__ cls, float* __restrict__ err, int B,
+                                                           const StepState* __restrict__ st, float scale) {
+    const int k = blockIdx.x, lane = threadIdx.x;
+    if (st) err += (long long)st->t_final * gridDim.x;            // row t of error_prediction_by_timestep (eesampler.py:70)
+    float a = 0.f;
+    for (int b = lane; b < B; b += 64) a += cls[(long long)k * B + b];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o);
+    if (lane == 0) err[k] = scale == 1.0f ? a : a / (float)B;
+}
+
+// rows [t_lo, t_hi] of error_prediction_by_timestep from the two chains' per-step sums, in a fixed order: (chain 0 + chain 1) / B
+__global__ void ee_mean_combine_kernel(const float* __restrict__ s0, const float* __restrict__ s1, float* __restrict__ err, int depth, int t_lo, int t_hi, int B) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, n = (t_hi - t_lo + 1) * depth;
+    if (i >= n) return;
+    const long long e = (long long)t_lo * depth + i;
+    err[e] = (s0[e] + s1[e]) / (float)B;
+}
+
+}  // namespace
+
+// one instantiation per (C, P) specialisation x guidance x history: (3, 4) CelebA-64 / ImageNet-64, (3, 2) CIFAR-10, (4, 2) 32 x 32 x 4
+// latents (ImageNet-256), anything else the run-time form
+template <int CT, int PT>
+static void launch_final_cp(const FinalArgs& a, hipStream_t s) {
+    const int tiles = (a.S + 15) / 16;
+    const dim3 grid(a.B * tiles * tiles);       // guided (pair_B > 0): a.B images, 2 a.B decoder images
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, a); };
+    if (a.pair_B > 0) a.htab ? go(final_tiled_kernel<CT, PT, true, true>) : go(final_tiled_kernel<CT, PT, true, false>);
+    else a.htab ? go(final_tiled_kernel<CT, PT, false, true>) : go(final_tiled_kernel<CT, PT, false, false>);
+}
+
+hipError_t launch_final(const FinalArgs& a, hipStream_t s) {
+    if (a.pair_B > 0 && (a.pair_B != a.B || a.layer_B > 0)) return hipErrorInvalidValue;
+    // the multistep loop: a table-driven step that writes x and h
+    if (a.htab && (!a.atab || !a.h || !a.x_in || !a.x_out || a.layer_B > 0)) return hipErrorInvalidValue;
+    if (a.C == 3 && a.P == 4) launch_final_cp<3, 4>(a, s);
+    else if (a.C == 3 && a.P == 2) launch_final_cp<3, 2>(a, s);
+    else if (a.C == 4 && a.P == 2) launch_final_cp<4, 2>(a, s);
+    else launch_final_cp<0, 0>(a, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_ddpm_step(const float* x, const float* eps, const float* z, float* out, StepCoef c,
+                            int use_noise, long long n, hipStream_t s) {
+    // variance selection is folded by the caller into c.sigma_tilde
+    hipLaunchKernelGGL(ddpm_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, eps, z, out, c,
+                       use_noise, 0, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_affine_step(const float* x, const float* m, const float* z, float* out, float a, float b, float c,
+                              long long n, hipStream_t s) {
+    hipLaunchKernelGGL(affine_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, m, z, out, a, b, c, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_multistep_step(const float* x, const float* m, const float* z, float* h, float* out, float a, float b, float c, float d,
+                                 float p, float q, int use_hist, long long n, hipStream_t s) {
+    hipLaunchKernelGGL(multistep_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, m, z, h, out, a, b, c, d, p, q, use_hist, n);
+    return hipGetLastError();
+}
+hipError_t launch_ee_select(const float* outs, const float* eps, const float* cls, float thr, int depth, int B, long long chw,
+                            float* mo, int* idx, float* err_mean, hipStream_t s) {
+    const long long n = (long long)B * chw;
+    hipLaunchKernelGGL(ee_select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, outs, eps, cls, thr, depth, B, chw, mo, idx);
+    if (err_mean) hipLaunchKernelGGL(ee_batch_mean_kernel, dim3(depth), dim3(64), 0, s, cls, err_mean, B, (const StepState*)nullptr, 0.0f);
+    return hipGetLastError();
+}
+hipError_t launch_ee_select_step(float* x, const float* outs, const float* eps, const float* cls, float thr, int depth, int* idx, float* err_mean,
+                                 int idx_stride, int idx_col0, bool sums, StepState* st, const StepCoef* coef, int B, int C, int S,
+                                 int noise_mode, int advance, hipStream_t s) {
+    const long long npix = (long long)B * S * S;
+    if (err_mean) hipLaunchKernelGGL(ee_batch_mean_kernel, dim3(depth), dim3(64), 0, s, cls, err_mean, B, st, sums ? 1.0f : 0.0f);
+    hipLaunchKernelGGL(ee_select_step_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, x, outs, eps, cls, thr, depth, idx,
+                       idx_stride > 0 ? idx_stride : B, idx_col0, st, coef, B, C, S, noise_mode, advance, (long long)idx_col0 * S * S);
+    return hipGetLastError();
+}
+hipError_t launch_ee_mean_combine(const float* s0, const float* s1, float* err, int depth, int t_lo, int t_hi, int B, hipStream_t s) {
+    const int n = (t_hi - t_lo + 1) * depth;
+    hipLaunchKernelGGL(ee_mean_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, s0, s1, err, depth, t_lo, t_hi, B);
+    return hipGetLastError();
+}
+hipError_t launch_set_state(StepState* st, int t, unsigned long long seed, hipStream_t s) {
+    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, s, st, t, seed);
+    return hipGetLastError();
+}
+hipError_t launch_set_state_table(StepState* st, const AffineRow* atab, unsigned long long seed, hipStream_t s) {
+    hipLaunchKernelGGL(set_state_table_kernel, dim3(1), dim3(1), 0, s, st, atab, seed);
+    return hipGetLastError();
+}
+hipError_t launch_guided_labels(const long long* y, long long* out, int B, long long null_label, hipStream_t s) {
+    hipLaunchKernelGGL(guided_labels_kernel, dim3((unsigned)((2 * B + 255) / 256)), dim3(256), 0, s, y, out, B, null_label);
+    return hipGetLastError();
+}
+hipError_t launch_set_state_float(StepState* st, float t, hipStream_t s) {
+    hipLaunchKernelGGL(set_state_float_kernel, dim3(1), dim3(1), 0, s, st, t);
+    return hipGetLastError();
+}
+hipError_t launch_to_images(const float* x, float* out, int B, int C, int S, hipStream_t s) {
+    const long long npix = (long long)B * S * S;
+    hipLaunchKernelGGL(to_images_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, x, out, B, C, S);
+    return hipGetLastError();
+}
+
+}  // namespace dd

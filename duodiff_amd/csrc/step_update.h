@@ -1,0 +1,122 @@
+// The sampling-step update, defined once (device only).  Loops, chains, cut loops and manual steps are compared bit for bit, so the
+// operation order and the roundings below are a contract: every step kernel (step.hip) applies these functions and holds no update
+// arithmetic of its own.  Each function that rounds carries the fp-contract pragma in its own body (at file scope it would leak into the
+// including unit): mul, sub, mul, add -- no FMA, as the reference rounds.
+#pragma once
+#include "dd_internal.h"
+
+namespace dd {
+
+// ------------------------------------------------------------------------------------------
+// Device noise: Philox4x32-10 counter RNG + Box-Muller.  Counter = (element/4, t, 0, 0),
+// key = seed.  Statistically N(0,1); NOT the torch CPU mt19937 stream (that is DD_NOISE_BUFFER).
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void philox_round(unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3,
+                                             unsigned k0, unsigned k1) {
+    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
+    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+}
+
+// four N(0,1) values for one pixel (one per channel, C <= 4): counter = (pixel, t), key = seed
+__device__ __forceinline__ f32x4 philox_normal4(unsigned long long seed, unsigned long long pixel, int t) {
+    unsigned c0 = (unsigned)pixel, c1 = (unsigned)(pixel >> 32), c2 = (unsigned)t, c3 = 0x5eedu;
+    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c0, c1, c2, c3, k0, k1);
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    // Box-Muller on (c0,c1) and (c2,c3); hardware log/sin/cos (|error| ~1e-6) are ample for noise
+    const float ua = ((float)c0 + 1.0f) * 2.3283064365386963e-10f, ub = (float)c1 * 2.3283064365386963e-10f;
+    const float uc = ((float)c2 + 1.0f) * 2.3283064365386963e-10f, ud = (float)c3 * 2.3283064365386963e-10f;
+    const float ra = sqrtf(-2.0f * __logf(ua)), rc = sqrtf(-2.0f * __logf(uc));
+    const float aa = 6.283185307179586f * ub, ac = 6.283185307179586f * ud;
+    return f32x4{ra * __cosf(aa), ra * __sinf(aa), rc * __cosf(ac), rc * __sinf(ac)};
+}
+
+// One step's rule, built once per thread:
+//   DDPM   x' = c1 (x - c2 eps) + sigma z                      (reference sampler.py:47-56)
+//   table  x' = a x + b eps [+ d h if hist] [+ c z if drawn],  h' = p x + q eps   (AffineRow / HistRow of step k)
+// H: the rule carries a history part (the multistep loop); H = false compiles to the code without it.
+// noise_mode: 0 none, 1 a z buffer the caller reads where reads_z(), 2 Philox where draws() with counter ctr.
+template <bool H>
+struct StepRule {
+    int t;                        // st->t_final as read: the timestep (DDPM) or the step index (table)
+    bool table, draw;             // draw: this step adds noise at all (t > 0, or row.noise)
+    int noise_mode, ctr;
+    StepCoef cf;
+    float sigma;
+    AffineRow row;
+    HistRow hr;
+    bool adv;
+    float t_next;                 // table && adv: the next row's t_model
+
+    // From the device-resident step state.  Every load is issued here, so a kernel builds the rule ahead of its own long-latency work;
+    // none waits for another beyond the step state -> row chain (the caller likewise requests h without waiting for hr.hist).
+    __device__ __forceinline__ StepRule(const StepState* st, const StepCoef* coef, const AffineRow* atab, const HistRow* htab,
+                                        int noise_mode_, int variance, int advance)
+        : t(st->t_final), table(atab != nullptr), noise_mode(noise_mode_), hr{0.f, 0.f, 0.f, 0}, adv(advance != 0) {
+        row = table ? atab[t] : AffineRow{0.f, 0.f, 0.f, 0.f, 0, 0, 0, 0};
+        t_next = (table && adv) ? atab[t + 1].t_model : 0.f;
+        cf = coef[table ? 0 : (t < 0 ? 0 : (t > 999 ? 999 : t))];
+        draw = table ? (row.noise != 0) : (t > 0);
+        if constexpr (H) hr = htab[t];
+        ctr = table ? row.ctr : t;
+        sigma = variance == 1 ? cf.sigma_beta : cf.sigma_tilde;
+    }
+    // From plain coefficients (the unfused step kernels): the same rule, nothing loaded and no step state to advance.
+    __device__ __forceinline__ StepRule(StepCoef c, bool variance_beta, bool use_z)      // DDPM
+        : t(0), table(false), draw(use_z), noise_mode(1), ctr(0), cf(c), sigma(variance_beta ? c.sigma_beta : c.sigma_tilde),
+          row{0.f, 0.f, 0.f, 0.f, 0, 0, 0, 0}, hr{0.f, 0.f, 0.f, 0}, adv(false), t_next(0.f) {}
+    __device__ __forceinline__ StepRule(float a, float b, float c, HistRow h, bool use_z)   // table row
+        : t(0), table(true), draw(use_z), noise_mode(1), ctr(0), cf{0.f, 0.f, 0.f, 0.f}, sigma(0.f),
+          row{0.f, a, b, c, use_z, 0, 0, 0}, hr(h), adv(false), t_next(0.f) {}
+
+    __device__ __forceinline__ bool reads_z() const { return draw && noise_mode == 1; }
+    __device__ __forceinline__ bool draws() const { return draw && noise_mode == 2; }
+    __device__ __forceinline__ bool noisy() const { return reads_z() || draws(); }
+
+    // x' from x, the model output, this element's z (read only where reads_z() / draws()) and its history h (read only where hr.hist:
+    // a step without history never lets h into x' -- the first step's h may be an uninitialised buffer, and 0 * NaN is NaN)
+    __device__ __forceinline__ float apply(float x, float eps, float z, float h) const {
+#pragma clang fp contract(off)
+        float v;
+        if (table) {
+            v = row.a * x + row.b * eps;
+            if constexpr (H) {
+                if (hr.hist) v = v + hr.d * h;
+            }
+            if (noisy()) v = v + row.c * z;
+        } else {
+            v = cf.c1 * (x - cf.c2 * eps);
+            if (noisy()) v = v + sigma * z;
+        }
+        return v;
+    }
+    // h' of the multistep row, written on every step
+    __device__ __forceinline__ float history(float x, float eps) const {
+#pragma clang fp contract(off)
+        return hr.p * x + hr.q * eps;
+    }
+    // hands the next step its t / t_model; ONE thread of the step's last kernel calls it (no block of that kernel reads t / t_model)
+    __device__ __forceinline__ void advance(StepState* st) const {
+        if (!adv) return;
+        const int tn = table ? t + 1 : t - 1;
+        st->t = tn;
+        st->t_model = table ? t_next : (float)tn;
+    }
+};
+
+// eesampler.py:61-67: idx[b] = first layer i in [0, depth] with c[i][b] <= threshold, where c[depth][b] = 0 closes the
+// list (torch.argmax of an all-False column is 0)
+__device__ __forceinline__ int ee_exit_layer(const float* __restrict__ cls, float thr, int depth, int B, int b) {
+    int idx = -1;
+    for (int k = 0; k < depth && idx < 0; ++k)
+        if (cls[(long long)k * B + b] <= thr) idx = k;
+    if (idx < 0) idx = (0.0f <= thr) ? depth : 0;
+    return idx;
+}
+
+}  // namespace dd

@@ -121,11 +121,11 @@ def _labels(B, ncls, seed):
 
 
 @gpu
-@pytest.mark.parametrize("case", ["tiny_final_kernel", "tiled_32x32"])
+@pytest.mark.parametrize("case", ["tiny_one_tile", "tiled_32x32"])
 def test_forward_guided_vs_oracle(case):
     """dd_forward_guided against the unchanged numpy oracle run twice (labels, then the null label), combined in float64."""
     import oracle
-    if case == "tiny_final_kernel":
+    if case == "tiny_one_tile":
         cfg, B, S, Cc = dict(TINY_COND), 5, 8, 3
     else:
         cfg = dict(img_size=32, patch_size=2, in_chans=4, embed_dim=256, depth=3, num_heads=4, mlp_ratio=4, qkv_bias=False,

@@ -400,7 +400,7 @@ def test_cut_loop_equals_the_uncut_loop(case, request):
 @gpu
 @pytest.mark.parametrize("S", [8, 16])
 def test_guided_multistep(S):
-    """Class-conditional TINY pair (S = 8: final_kernel, S = 16: the tiled kernel), chains forced: scale 0 == the unguided loop with the
+    """Class-conditional TINY pair (S = 8: one tile of 64 live lanes, S = 16: a full tile), chains forced: scale 0 == the unguided loop with the
     same labels (SDE, Philox noise); scale 0.4 ODE == forward_guided + multistep_step, bit for bit."""
     B = 6
     es, ef, _ = _tiny_pair(max_batch=2 * B, num_classes=11, img_size=S)

@@ -144,7 +144,7 @@ def summarize_trace(d):
     for f in trace:
         for r in csv.DictReader(open(f)):
             n = r["Kernel_Name"]
-            if "final_tiled_kernel" in n or "final_kernel" in n:
+            if "final_tiled_kernel" in n:
                 durs.setdefault(n, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     out = {"_build_id": _lib.load().dd_build_id().decode(),
            "source": "rocprofv3 --kernel-trace --stats of tools/multistep_bench.py (its own run); durations in microseconds",

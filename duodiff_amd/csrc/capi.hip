@@ -7,7 +7,9 @@
 #include "../../include/duodiff.h"
 #include "../../include/duodiff_dev.h"
 #include "dd_internal.h"
+#include "dev_scope.h"
 #include "host_arena.h"
+#include "launch_args.h"
 
 #include <algorithm>
 #include <cmath>
@@ -81,23 +83,6 @@ struct BlockW {
     const char* rlp_img = nullptr;  // attn.proj weight, ditto
     const char* rls_img = nullptr;  // skip_linear weight [D, 2 D], ditto (out-blocks)
 };
-
-// head_dec_kernel operands from a head's LayerNorm (gamma, beta) and decoder_pred (W [pd, D], b): wg = W diag(gamma); dc = c [pd] = b + W . beta,
-// then the row sums of wg [pd] (the kernel multiplies the un-normalised rows: dec = rstd (wg . d - mean_d wsum) + c, rowops.hip)
-static void fold_head_norm(int D, int pd, const float* wd, const float* bd, const float* ng, const float* nb, std::vector<float>& wg, std::vector<float>& dc) {
-    wg.assign((size_t)pd * D, 0.f);
-    dc.assign(2 * (size_t)pd, 0.f);
-    for (int r = 0; r < pd; ++r) {
-        double acc = bd[r], wsum = 0.0;
-        for (int k = 0; k < D; ++k) {
-            wg[(size_t)r * D + k] = wd[(size_t)r * D + k] * ng[k];
-            acc += (double)wd[(size_t)r * D + k] * (double)nb[k];
-            wsum += (double)wg[(size_t)r * D + k];
-        }
-        dc[r] = (float)acc;
-        dc[pd + r] = (float)wsum;
-    }
-}
 
 struct HeadW { const float *ng, *nb, *wdec, *bdec, *wconv, *bconv; const float *wg = nullptr, *dc = nullptr; const float *wsplit = nullptr, *dcs = nullptr; };   // wg / dc: head_dec_kernel operands (norm folded into decoder_pred; dc = c [pd], row sums of wg [pd]) or null; wsplit / dcs: the same for the split-bf16 product (bf16 engine, embed_dim 256 / 512) or null
 
@@ -182,24 +167,18 @@ struct dd_model {
 };
 
 namespace dd {
-// shared with vae.hip (dd_ctx is defined in this translation unit)
+// declared in dev_scope.h for vae.hip and dev_harness.hip (dd_ctx is defined in this translation unit)
 int ctx_fail(dd_ctx* c, int code, const std::string& msg) {
     if (c) c->err = msg;
     return code;
 }
 int ctx_device(dd_ctx* c) { return c->device; }
 int ctx_num_cus(dd_ctx* c) { return c->num_cus; }
+unsigned ctx_dev_flags(dd_ctx* c) { return c->dev_flags; }
 }  // namespace dd
 
 namespace {
 
-int fail(dd_ctx* c, int code, const std::string& msg) {
-    if (c) c->err = msg;
-    return code;
-}
-int fail_hip(dd_ctx* c, hipError_t e, const char* what) {
-    return fail(c, DD_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
 #define DD_HIP(c, expr)                                          \
     do {                                                         \
         hipError_t _e = (expr);                                  \
@@ -253,8 +232,6 @@ const Schedule& schedule() {
     static const Schedule s;
     return s;
 }
-
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // the probes of an early-exit model (EarlyExitUViT.matrix, early_exit.py:194-204, 219-240) form an nt x nl grid of (timestep, layer);
 // row t nl + layer of the probe table is probe (layer, t): per layer `layer`, per timestep `t`, per layer and timestep `t depth + layer`
@@ -501,39 +478,6 @@ void pack_probes(dd_model* m, Arena& a) {
             pb[row] = P(pre + "bias")[0];
         }
     a.f32(m->probe_w, pw); a.f32(m->probe_b, pb);
-}
-// Argument filling of the two row-pass variants of an N = D Linear g (Backbone::rowlin_then_reduce / splitk_then_reduce_ln, dd_dev_rowlin /
-// dd_dev_gemm): pure functions of the Linear, so that the development entry points launch exactly what the model launches.
-// (embed_dim 768) the row-resident launch: x = [x +] g + bias (resid), g's bf16 copy, LayerNorm ln_g / ln_b of the updated rows into h_out
-// (row-major) or h_frag (the patch rows in fragment order); rows planned as B images of n_patches patch tokens behind `extras` extra tokens, or
-// (n_patches == 0) the plain mode: rows [0, g.M) in tiles of 128
-RowLinArgs rowlin_args(const GemmArgs<bf16_t>& g, int resid, const char* wimg, float* partial, const float* ln_g, const float* ln_b,
-                       bf16_t* h_out, bf16_t* h_frag, int B, int n_patches, int extras) {
-    RowLinArgs ra{};
-    ra.A = g.A; ra.A2 = g.A2; ra.k_split = g.A2 ? g.K1 : 0; ra.set_x = !resid; ra.lda = g.lda; ra.K = g.K;
-    ra.wimg = wimg; ra.bias = g.bias; ra.xres = g.xres; ra.x_copy = g.out; ra.partial = partial;
-    if (ln_g) {
-        ra.ln_g = ln_g; ra.ln_b = ln_b;
-        if (h_frag) ra.h_frag = h_frag; else ra.h_out = h_out;
-    }
-    if (n_patches > 0) rowlin_plan(B, n_patches, extras, n_patches + extras, ra.K, ra);
-    else ra.M = g.M;
-    return ra;
-}
-// ... and the launch that finishes its extra-token rows from the K-split slabs (launch_mlp_reduce)
-MlpFusedArgs rowlin_reduce_args(const RowLinArgs& ra) {
-    MlpFusedArgs fr{};
-    fr.b2 = ra.bias; fr.xres = ra.xres; fr.partial = ra.partial; fr.out = ra.x_copy; fr.ldo = 768; fr.reduce_set = ra.set_x;
-    fr.tok_n = ra.tok_n; fr.tok_e = ra.tok_e; fr.tok_l = ra.tok_l; fr.n_extra = ra.n_extra; fr.tiles_left = ra.tiles_extra;
-    fr.groups = ra.groups; fr.prows = 128;
-    if (ra.h_out) { fr.ln_out_g = ra.ln_g; fr.ln_out_b = ra.ln_b; fr.ln_out = ra.h_out; }
-    return fr;
-}
-// the row pass behind a split-K launch of g (g.partial / g.splits): the slabs added in ascending order + bias [+ x], g's bf16 copy, LayerNorm into
-// h -- with frag, the patch rows of the tok_l-token images into frag and only the extra-token rows into h
-ReduceLnArgs splitk_reduce_args(const GemmArgs<bf16_t>& g, int resid, const float* ln_g, const float* ln_b, bf16_t* h, bf16_t* frag, int tok_l, int tok_e) {
-    return ReduceLnArgs{g.xres, g.partial, (long long)g.M * g.N, g.splits, resid, g.bias, g.out, g.ldo, ln_g, ln_b, h, ln_g ? frag : nullptr,
-                        tok_l, tok_e, g.M};
 }
 
 // What a step runs on: the launch sequence of a step is enqueued / captured for either half-batch chain by the same code, on the same
@@ -885,27 +829,27 @@ int run_model(dd_model* m, const Chain& ch, const float* x_img, const float* t_v
 
 int check_call(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev) {
     if (!c || !m) return DD_ERR_INVALID;
-    if (m->ctx != c) return fail(c, DD_ERR_INVALID, "model belongs to another context");
-    if (!m->finalized) return fail(c, DD_ERR_STATE, "dd_model_finalize has not been called");
-    if (B < 1 || B > m->cfg.max_batch) return fail(c, DD_ERR_INVALID, "batch size outside [1, max_batch]");
+    if (m->ctx != c) return ctx_fail(c, DD_ERR_INVALID, "model belongs to another context");
+    if (!m->finalized) return ctx_fail(c, DD_ERR_STATE, "dd_model_finalize has not been called");
+    if (B < 1 || B > m->cfg.max_batch) return ctx_fail(c, DD_ERR_INVALID, "batch size outside [1, max_batch]");
     if (m->cfg.num_classes > 0 && !y_dev)
-        return fail(c, DD_ERR_INVALID, "class-conditional model called without labels (pos_embed has L=extras+N rows)");
+        return ctx_fail(c, DD_ERR_INVALID, "class-conditional model called without labels (pos_embed has L=extras+N rows)");
     if (m->cfg.num_classes <= 0 && y_dev)
-        return fail(c, DD_ERR_INVALID, "unconditional model called with labels");
+        return ctx_fail(c, DD_ERR_INVALID, "unconditional model called with labels");
     return DD_OK;
 }
 
 // a guided call of B images on m (include/duodiff.h dd_guidance): every check before anything is enqueued
 int check_guided(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev, const dd_guidance* g) {
     if (!c || !m) return DD_ERR_INVALID;
-    if (!g) return fail(c, DD_ERR_INVALID, "null dd_guidance");
-    if (m->cfg.num_classes <= 0) return fail(c, DD_ERR_INVALID, "classifier-free guidance needs a class-conditional model");
-    if (m->ee_type >= 0) return fail(c, DD_ERR_INVALID, "classifier-free guidance is not supported for early-exit models");
+    if (!g) return ctx_fail(c, DD_ERR_INVALID, "null dd_guidance");
+    if (m->cfg.num_classes <= 0) return ctx_fail(c, DD_ERR_INVALID, "classifier-free guidance needs a class-conditional model");
+    if (m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, "classifier-free guidance is not supported for early-exit models");
     if (g->null_label < 0 || g->null_label >= m->cfg.num_classes)
-        return fail(c, DD_ERR_INVALID, "guidance null_label outside [0, num_classes) of the model");
-    if (!std::isfinite(g->scale)) return fail(c, DD_ERR_INVALID, "guidance scale is not finite");
+        return ctx_fail(c, DD_ERR_INVALID, "guidance null_label outside [0, num_classes) of the model");
+    if (!std::isfinite(g->scale)) return ctx_fail(c, DD_ERR_INVALID, "guidance scale is not finite");
     if (B < 1 || 2LL * B > m->cfg.max_batch)
-        return fail(c, DD_ERR_INVALID, "a guided batch of B images runs 2 B backbone rows: need 1 <= B and 2 B <= max_batch");
+        return ctx_fail(c, DD_ERR_INVALID, "a guided batch of B images runs 2 B backbone rows: need 1 <= B and 2 B <= max_batch");
     return check_call(c, m, 2 * B, y_dev);
 }
 
@@ -1165,7 +1109,7 @@ int profile_steps(dd_ctx* c, dd_model* m, float* x_dev, const int64_t* y_dev, in
     if (rc) return rc;
     const bool chained = chains == 2;
     if (!x_dev || !ms_out || steps < 1 || t_start > 999 || t_start - steps + 1 < 0 || (chained && ((B & 1) || B < 2)))
-        return fail(c, DD_ERR_INVALID, "bad arguments");
+        return ctx_fail(c, DD_ERR_INVALID, "bad arguments");
     hipStream_t s = (hipStream_t)stream;
     const hipStream_t cs[2] = {s, c->side};
     if (chained && (rc = ensure_chain_ws(c, m, s))) return rc;
@@ -1320,14 +1264,14 @@ int dd_model_create(dd_ctx* c, const dd_config* cfg, dd_model** out) {
     if (!c || !cfg || !out) return DD_ERR_INVALID;
     *out = nullptr;
     const dd_config& g = *cfg;
-    if (g.img_size <= 0 || g.patch_size <= 0 || g.img_size % g.patch_size) return fail(c, DD_ERR_INVALID, "img_size must be a positive multiple of patch_size");
-    if (g.num_heads <= 0 || g.embed_dim != g.num_heads * 64) return fail(c, DD_ERR_UNSUPPORTED, "kernels require head_dim == 64 (all shipped configs)");
-    if (g.depth < 1 || g.depth % 2 != 1) return fail(c, DD_ERR_INVALID, "depth must be odd");
-    if (g.in_chans < 1 || g.in_chans > 4) return fail(c, DD_ERR_UNSUPPORTED, "in_chans must be 1..4");
-    if (g.embed_dim > 1024) return fail(c, DD_ERR_UNSUPPORTED, "embed_dim must be <= 1024");
-    if (g.max_batch < 1) return fail(c, DD_ERR_INVALID, "max_batch must be >= 1");
+    if (g.img_size <= 0 || g.patch_size <= 0 || g.img_size % g.patch_size) return ctx_fail(c, DD_ERR_INVALID, "img_size must be a positive multiple of patch_size");
+    if (g.num_heads <= 0 || g.embed_dim != g.num_heads * 64) return ctx_fail(c, DD_ERR_UNSUPPORTED, "kernels require head_dim == 64 (all shipped configs)");
+    if (g.depth < 1 || g.depth % 2 != 1) return ctx_fail(c, DD_ERR_INVALID, "depth must be odd");
+    if (g.in_chans < 1 || g.in_chans > 4) return ctx_fail(c, DD_ERR_UNSUPPORTED, "in_chans must be 1..4");
+    if (g.embed_dim > 1024) return ctx_fail(c, DD_ERR_UNSUPPORTED, "embed_dim must be <= 1024");
+    if (g.max_batch < 1) return ctx_fail(c, DD_ERR_INVALID, "max_batch must be >= 1");
     dd_model* m = new (std::nothrow) dd_model();
-    if (!m) return fail(c, DD_ERR_NOMEM, "out of host memory");
+    if (!m) return ctx_fail(c, DD_ERR_NOMEM, "out of host memory");
     m->ctx = c; m->cfg = g;
     m->D = g.embed_dim; m->H = g.num_heads;
     m->N = (g.img_size / g.patch_size) * (g.img_size / g.patch_size);
@@ -1339,8 +1283,8 @@ int dd_model_create(dd_ctx* c, const dd_config* cfg, dd_model** out) {
     m->hid_ld = m->hidden;   // row stride of the MLP hidden activation (a +64 pad against power-of-two strides measured no gain)
     m->half_depth = g.depth / 2;
     m->Mp_max = round_up(g.max_batch * m->L, 256);
-    if (m->L > 288) { delete m; return fail(c, DD_ERR_UNSUPPORTED, "sequence length must be <= 288 tokens"); }
-    if (m->pd > 64) { delete m; return fail(c, DD_ERR_UNSUPPORTED, "patch_size^2 * in_chans must be <= 64"); }
+    if (m->L > 288) { delete m; return ctx_fail(c, DD_ERR_UNSUPPORTED, "sequence length must be <= 288 tokens"); }
+    if (m->pd > 64) { delete m; return ctx_fail(c, DD_ERR_UNSUPPORTED, "patch_size^2 * in_chans must be <= 64"); }
     m->params = catalogue(m);
     *out = m;
     return DD_OK;
@@ -1349,9 +1293,9 @@ int dd_model_create(dd_ctx* c, const dd_config* cfg, dd_model** out) {
 int dd_model_set_param(dd_model* m, const char* name, const float* host, const int64_t* shape, int ndim) {
     if (!m || !name || !host || !shape || ndim < 1) return DD_ERR_INVALID;
     dd_ctx* c = m->ctx;
-    if (m->finalized) return fail(c, DD_ERR_STATE, "model already finalized");
+    if (m->finalized) return ctx_fail(c, DD_ERR_STATE, "model already finalized");
     auto it = m->params.find(name);
-    if (it == m->params.end()) return fail(c, DD_ERR_NOT_FOUND, std::string("unexpected key in state_dict: ") + name);
+    if (it == m->params.end()) return ctx_fail(c, DD_ERR_NOT_FOUND, std::string("unexpected key in state_dict: ") + name);
     HostParam& p = it->second;
     const std::vector<int64_t>& want = p.shape;
     std::vector<int64_t> got(shape, shape + ndim);
@@ -1360,7 +1304,7 @@ int dd_model_set_param(dd_model* m, const char* name, const float* host, const i
         for (size_t i = 0; i < want.size(); ++i) msg += (i ? "," : "") + std::to_string(want[i]);
         msg += "], got [";
         for (size_t i = 0; i < got.size(); ++i) msg += (i ? "," : "") + std::to_string(got[i]);
-        return fail(c, DD_ERR_INVALID, msg + "]");
+        return ctx_fail(c, DD_ERR_INVALID, msg + "]");
     }
     size_t n = 1;
     for (auto d : want) n *= (size_t)d;
@@ -1379,10 +1323,10 @@ int64_t dd_model_num_params(const dd_model* m) {
 int dd_model_finalize(dd_model* m, int precision) {
     if (!m) return DD_ERR_INVALID;
     dd_ctx* c = m->ctx;
-    if (m->finalized) return fail(c, DD_ERR_STATE, "model already finalized");
-    if (precision != DD_PREC_BF16 && precision != DD_PREC_FP32) return fail(c, DD_ERR_INVALID, "unknown precision");
+    if (m->finalized) return ctx_fail(c, DD_ERR_STATE, "model already finalized");
+    if (precision != DD_PREC_BF16 && precision != DD_PREC_FP32) return ctx_fail(c, DD_ERR_INVALID, "unknown precision");
     for (const auto& kv : m->params)
-        if (!kv.second.set) return fail(c, DD_ERR_NOT_FOUND, "missing key in state_dict: " + kv.first);
+        if (!kv.second.set) return ctx_fail(c, DD_ERR_NOT_FOUND, "missing key in state_dict: " + kv.first);
     DD_HIP(c, hipSetDevice(c->device));
     m->prec = precision;
     m->esize = precision == DD_PREC_BF16 ? 2 : 4;
@@ -1454,7 +1398,7 @@ int dd_forward(dd_ctx* c, dd_model* m, const float* x_dev, float t, const float*
                float* eps_dev, int B, void* stream) {
     int rc = check_call(c, m, B, y_dev);
     if (rc) return rc;
-    if (!x_dev || !eps_dev) return fail(c, DD_ERR_INVALID, "null tensor");
+    if (!x_dev || !eps_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
     return forward_eps(c, m, whole_batch(c, m), &t, x_dev, t_dev, y_dev, eps_dev, B, (hipStream_t)stream);
 }
 
@@ -1462,9 +1406,9 @@ int dd_model_enable_early_exit(dd_model* m, int classifier_type) {
     if (!m) return DD_ERR_INVALID;
     dd_ctx* c = m->ctx;
     const bool any_set = std::any_of(m->params.begin(), m->params.end(), [](const auto& kv) { return kv.second.set; });
-    if (m->finalized || any_set) return fail(c, DD_ERR_STATE, "enable early exit before any parameter is set");
+    if (m->finalized || any_set) return ctx_fail(c, DD_ERR_STATE, "enable early exit before any parameter is set");
     if (classifier_type < DD_EE_MLP_PER_LAYER || classifier_type > DD_EE_ATTENTION_PROBE)
-        return fail(c, DD_ERR_UNSUPPORTED, "unknown classifier type");
+        return ctx_fail(c, DD_ERR_UNSUPPORTED, "unknown classifier type");
     m->ee_type = classifier_type;
     m->params = catalogue(m);   // the heads and probes of this classifier type
     return DD_OK;
@@ -1474,10 +1418,10 @@ int dd_forward_early_exit(dd_ctx* c, dd_model* m, const float* x_dev, float t, c
                           float* eps_dev, float* classifier_dev, float* outputs_dev, int B, void* stream) {
     int rc = check_call(c, m, B, y_dev);
     if (rc) return rc;
-    if (m->ee_type < 0) return fail(c, DD_ERR_STATE, "model was not created with dd_model_enable_early_exit");
-    if (!x_dev || !eps_dev || !classifier_dev || !outputs_dev) return fail(c, DD_ERR_INVALID, "null tensor");
+    if (m->ee_type < 0) return ctx_fail(c, DD_ERR_STATE, "model was not created with dd_model_enable_early_exit");
+    if (!x_dev || !eps_dev || !classifier_dev || !outputs_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
     const int ti = (int)t;                                   // t = int(timesteps[0]) (early_exit.py:271)
-    if (m->ee_type != DD_EE_MLP_PER_LAYER && m->ee_type != DD_EE_ATTENTION_PROBE && (ti < 0 || ti > 999)) return fail(c, DD_ERR_NOT_FOUND, "no probe for this timestep (KeyError in the reference)");
+    if (m->ee_type != DD_EE_MLP_PER_LAYER && m->ee_type != DD_EE_ATTENTION_PROBE && (ti < 0 || ti > 999)) return ctx_fail(c, DD_ERR_NOT_FOUND, "no probe for this timestep (KeyError in the reference)");
     const EeTaps ee{classifier_dev, outputs_dev, ti};
     return forward_eps(c, m, whole_batch(c, m), &t, x_dev, t_dev, y_dev, eps_dev, B, (hipStream_t)stream, &ee);
 }
@@ -1486,8 +1430,8 @@ int dd_early_exit_select(dd_ctx* c, const float* outputs_dev, const float* eps_d
                          float threshold, int depth, int B, int64_t chw, float* model_output_dev, int32_t* indices_dev,
                          float* err_mean_dev, void* stream) {
     if (!c) return DD_ERR_INVALID;
-    if (!outputs_dev || !eps_dev || !classifier_dev || !model_output_dev) return fail(c, DD_ERR_INVALID, "null tensor");
-    if (depth < 1 || B < 1 || chw < 1) return fail(c, DD_ERR_INVALID, "depth, B and chw must be positive");
+    if (!outputs_dev || !eps_dev || !classifier_dev || !model_output_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    if (depth < 1 || B < 1 || chw < 1) return ctx_fail(c, DD_ERR_INVALID, "depth, B and chw must be positive");
     DD_HIP(c, launch_ee_select(outputs_dev, eps_dev, classifier_dev, threshold, depth, B, (long long)chw, model_output_dev,
                                indices_dev, err_mean_dev, (hipStream_t)stream));
     return DD_OK;
@@ -1496,8 +1440,8 @@ int dd_early_exit_select(dd_ctx* c, const float* outputs_dev, const float* eps_d
 int dd_ddpm_step(dd_ctx* c, const float* x_dev, const float* eps_dev, const float* z_dev, int t, int variance,
                  float* x_out_dev, int64_t n, void* stream) {
     if (!c) return DD_ERR_INVALID;
-    if (!x_dev || !eps_dev || !x_out_dev || n < 0) return fail(c, DD_ERR_INVALID, "null tensor");
-    if (t < 0 || t > 999) return fail(c, DD_ERR_INVALID, "timestep outside [0, 999]");
+    if (!x_dev || !eps_dev || !x_out_dev || n < 0) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    if (t < 0 || t > 999) return ctx_fail(c, DD_ERR_INVALID, "timestep outside [0, 999]");
     StepCoef cf = c->coef_host[t];
     if (variance == DD_VAR_BETA) cf.sigma_tilde = cf.sigma_beta;
     const int use_noise = (t > 0 && z_dev) ? 1 : 0;
@@ -1509,7 +1453,7 @@ int dd_ddpm_step(dd_ctx* c, const float* x_dev, const float* eps_dev, const floa
 int dd_ddpm_step_coef(dd_ctx* c, const float* x_dev, const float* eps_dev, const float* z_dev, float c1, float c2,
                       float sigma, float* x_out_dev, int64_t n, void* stream) {
     if (!c) return DD_ERR_INVALID;
-    if (!x_dev || !eps_dev || !x_out_dev || n < 0) return fail(c, DD_ERR_INVALID, "null tensor");
+    if (!x_dev || !eps_dev || !x_out_dev || n < 0) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
     if (n == 0) return DD_OK;
     const StepCoef cf{c1, c2, sigma, sigma};
     DD_HIP(c, launch_ddpm_step(x_dev, eps_dev, z_dev, x_out_dev, cf, z_dev ? 1 : 0, (long long)n, (hipStream_t)stream));
@@ -1519,7 +1463,7 @@ int dd_ddpm_step_coef(dd_ctx* c, const float* x_dev, const float* eps_dev, const
 int dd_affine_step(dd_ctx* c, const float* x_dev, const float* m_dev, const float* z_dev, float a, float b, float cc,
                    float* out_dev, int64_t n, void* stream) {
     if (!c) return DD_ERR_INVALID;
-    if (!x_dev || !m_dev || !out_dev || n < 0) return fail(c, DD_ERR_INVALID, "null tensor");
+    if (!x_dev || !m_dev || !out_dev || n < 0) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
     if (n == 0) return DD_OK;
     DD_HIP(c, launch_affine_step(x_dev, m_dev, z_dev, out_dev, a, b, cc, (long long)n, (hipStream_t)stream));
     return DD_OK;
@@ -1528,8 +1472,8 @@ int dd_affine_step(dd_ctx* c, const float* x_dev, const float* m_dev, const floa
 int dd_multistep_step(dd_ctx* c, const float* x_dev, const float* m_dev, const float* z_dev, float* h_dev, float a, float b, float cc,
                       float d, float p, float q, int use_hist, float* out_dev, int64_t n, void* stream) {
     if (!c) return DD_ERR_INVALID;
-    if (!x_dev || !m_dev || !h_dev || !out_dev || n < 0) return fail(c, DD_ERR_INVALID, "null tensor");
-    if (h_dev == x_dev || h_dev == out_dev || h_dev == m_dev) return fail(c, DD_ERR_INVALID, "h_dev must not alias x, m or out");
+    if (!x_dev || !m_dev || !h_dev || !out_dev || n < 0) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    if (h_dev == x_dev || h_dev == out_dev || h_dev == m_dev) return ctx_fail(c, DD_ERR_INVALID, "h_dev must not alias x, m or out");
     if (n == 0) return DD_OK;
     DD_HIP(c, launch_multistep_step(x_dev, m_dev, z_dev, h_dev, out_dev, a, b, cc, d, p, q, use_hist ? 1 : 0, (long long)n, (hipStream_t)stream));
     return DD_OK;
@@ -1537,8 +1481,8 @@ int dd_multistep_step(dd_ctx* c, const float* x_dev, const float* m_dev, const f
 
 int dd_to_images(dd_ctx* c, const float* x_dev, float* images_dev, int B, int C, int S, void* stream) {
     if (!c) return DD_ERR_INVALID;
-    if (!x_dev || !images_dev) return fail(c, DD_ERR_INVALID, "null tensor");
-    if (B < 0 || C < 1 || S < 1) return fail(c, DD_ERR_INVALID, "bad image shape");
+    if (!x_dev || !images_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    if (B < 0 || C < 1 || S < 1) return ctx_fail(c, DD_ERR_INVALID, "bad image shape");
     if (B == 0) return DD_OK;
     DD_HIP(c, launch_to_images(x_dev, images_dev, B, C, S, (hipStream_t)stream));
     return DD_OK;
@@ -1547,7 +1491,7 @@ int dd_forward_guided(dd_ctx* c, dd_model* m, const float* x_dev, float t, const
                       float* eps_dev, int B, void* stream) {
     int rc = check_guided(c, m, B, y_dev, g);
     if (rc) return rc;
-    if (!x_dev || !eps_dev) return fail(c, DD_ERR_INVALID, "null tensor");
+    if (!x_dev || !eps_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
     hipStream_t s = (hipStream_t)stream;
     const size_t chw = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
     float* x_run = nullptr;
@@ -1560,9 +1504,9 @@ int dd_sample_step(dd_ctx* c, dd_model* m, float* x_dev, int t, const int64_t* y
                    uint64_t seed, int variance, float* eps_out_dev, int B, void* stream) {
     int rc = check_call(c, m, B, y_dev);
     if (rc) return rc;
-    if (!x_dev) return fail(c, DD_ERR_INVALID, "null tensor");
-    if (t < 0 || t > 999) return fail(c, DD_ERR_INVALID, "timestep outside [0, 999]");
-    if (noise_mode == DD_NOISE_BUFFER && !z_dev && t > 0) return fail(c, DD_ERR_INVALID, "DD_NOISE_BUFFER needs z_dev");
+    if (!x_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    if (t < 0 || t > 999) return ctx_fail(c, DD_ERR_INVALID, "timestep outside [0, 999]");
+    if (noise_mode == DD_NOISE_BUFFER && !z_dev && t > 0) return ctx_fail(c, DD_ERR_INVALID, "DD_NOISE_BUFFER needs z_dev");
     hipStream_t s = (hipStream_t)stream;
     DD_HIP(c, launch_set_state(c->st[0], t, (unsigned long long)seed, s));
     return enqueue_step(c, m, whole_batch(c, m), x_dev, y_dev, noise_mode, z_dev, variance, eps_out_dev, B, s);
@@ -1578,13 +1522,13 @@ int sample_ddpm(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* 
     int rc = check(a->first);
     if (rc) return rc;
     if (a->late && (rc = check(a->late))) return rc;
-    if (!a->x_dev) return fail(c, DD_ERR_INVALID, "null tensor");
-    if (a->t_start > 999 || a->t_end < 0 || a->t_end > a->t_start) return fail(c, DD_ERR_INVALID, "need 999 >= t_start >= t_end >= 0");
+    if (!a->x_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    if (a->t_start > 999 || a->t_end < 0 || a->t_end > a->t_start) return ctx_fail(c, DD_ERR_INVALID, "need 999 >= t_start >= t_end >= 0");
     if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE)
-        return fail(c, DD_ERR_INVALID, "dd_sample generates noise on the device; for host noise drive dd_sample_step");
+        return ctx_fail(c, DD_ERR_INVALID, "dd_sample generates noise on the device; for host noise drive dd_sample_step");
     if (a->late) {
         const dd_config &f = a->first->cfg, &l = a->late->cfg;
-        if (f.img_size != l.img_size || f.in_chans != l.in_chans) return fail(c, DD_ERR_INVALID, "first and late model disagree on image shape");
+        if (f.img_size != l.img_size || f.in_chans != l.in_chans) return ctx_fail(c, DD_ERR_INVALID, "first and late model disagree on image shape");
     }
     const bool switching = a->late && a->t_switch > 0 && a->t_switch <= 1000;
     const int t_sw = 1000 - a->t_switch;  // the late model takes over AFTER this step (sampler.py:135-136)
@@ -1623,13 +1567,13 @@ int check_table_loop(dd_ctx* c, const Args* a, const dd_guidance* g, const char*
     int rc = check(a->first);
     if (rc) return rc;
     if (a->late && (rc = check(a->late))) return rc;
-    if (!a->x_dev || !a->t || !a->a || !a->b || !a->c || !a->noise) return fail(c, DD_ERR_INVALID, "null tensor / table");
-    if (a->n_steps < 1 || a->n_steps > (1 << 20)) return fail(c, DD_ERR_INVALID, "n_steps outside [1, 2^20]");
-    if (a->counter_base < 0 || a->counter_base > (1 << 20)) return fail(c, DD_ERR_INVALID, "counter_base outside [0, 2^20]");
-    if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE) return fail(c, DD_ERR_INVALID, host_noise);
+    if (!a->x_dev || !a->t || !a->a || !a->b || !a->c || !a->noise) return ctx_fail(c, DD_ERR_INVALID, "null tensor / table");
+    if (a->n_steps < 1 || a->n_steps > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "n_steps outside [1, 2^20]");
+    if (a->counter_base < 0 || a->counter_base > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "counter_base outside [0, 2^20]");
+    if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE) return ctx_fail(c, DD_ERR_INVALID, host_noise);
     if (a->late) {
         const dd_config &f = a->first->cfg, &l = a->late->cfg;
-        if (f.img_size != l.img_size || f.in_chans != l.in_chans) return fail(c, DD_ERR_INVALID, "first and late model disagree on image shape");
+        if (f.img_size != l.img_size || f.in_chans != l.in_chans) return ctx_fail(c, DD_ERR_INVALID, "first and late model disagree on image shape");
     }
     return DD_OK;
 }
@@ -1660,11 +1604,11 @@ int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* 
 int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, void* stream) {
     if (!c || !a) return DD_ERR_INVALID;
     for (dd_model* m : {a->first, a->late})
-        if (m && m->ee_type >= 0) return fail(c, DD_ERR_INVALID, "the multistep loop is not supported for early-exit models");
+        if (m && m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, "the multistep loop is not supported for early-exit models");
     int rc = check_table_loop(c, a, g, "dd_sample_multistep generates noise on the device; for host noise drive dd_forward + dd_multistep_step");
     if (rc) return rc;
-    if (!a->d || !a->p || !a->q || !a->hist) return fail(c, DD_ERR_INVALID, "null tensor / table");
-    if (!a->h_dev) return fail(c, DD_ERR_INVALID, "null h_dev: the multistep loop needs its history register");
+    if (!a->d || !a->p || !a->q || !a->hist) return ctx_fail(c, DD_ERR_INVALID, "null tensor / table");
+    if (!a->h_dev) return ctx_fail(c, DD_ERR_INVALID, "null h_dev: the multistep loop needs its history register");
     hipStream_t s = (hipStream_t)stream;
     const int n = a->n_steps;
     const bool switching = a->late && a->switch_after >= 0 && a->switch_after < n;
@@ -1707,17 +1651,17 @@ extern "C" {
 
 int dd_sample(dd_ctx* c, const dd_sample_args* a, void* stream) { return sample_ddpm(c, a, nullptr, stream); }
 int dd_sample_guided(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* stream) {
-    if (c && !g) return fail(c, DD_ERR_INVALID, "null dd_guidance");
+    if (c && !g) return ctx_fail(c, DD_ERR_INVALID, "null dd_guidance");
     return sample_ddpm(c, a, g, stream);
 }
 int dd_sample_affine(dd_ctx* c, const dd_affine_sample_args* a, void* stream) { return sample_affine(c, a, nullptr, stream); }
 int dd_sample_affine_guided(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, void* stream) {
-    if (c && !g) return fail(c, DD_ERR_INVALID, "null dd_guidance");
+    if (c && !g) return ctx_fail(c, DD_ERR_INVALID, "null dd_guidance");
     return sample_affine(c, a, g, stream);
 }
 int dd_sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, void* stream) { return sample_multistep(c, a, nullptr, stream); }
 int dd_sample_multistep_guided(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, void* stream) {
-    if (c && !g) return fail(c, DD_ERR_INVALID, "null dd_guidance");
+    if (c && !g) return ctx_fail(c, DD_ERR_INVALID, "null dd_guidance");
     return sample_multistep(c, a, g, stream);
 }
 
@@ -1745,11 +1689,11 @@ int dd_sample_early_exit(dd_ctx* c, const dd_ee_sample_args* a, void* stream) {
     dd_model* m = a->model;
     int rc = check_call(c, m, a->B, a->y_dev);
     if (rc) return rc;
-    if (m->ee_type < 0) return fail(c, DD_ERR_STATE, "model was not created with dd_model_enable_early_exit");
-    if (!a->x_dev) return fail(c, DD_ERR_INVALID, "null tensor");
-    if (a->t_start > 999 || a->t_end < 0 || a->t_end > a->t_start) return fail(c, DD_ERR_INVALID, "need 999 >= t_start >= t_end >= 0");
+    if (m->ee_type < 0) return ctx_fail(c, DD_ERR_STATE, "model was not created with dd_model_enable_early_exit");
+    if (!a->x_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    if (a->t_start > 999 || a->t_end < 0 || a->t_end > a->t_start) return ctx_fail(c, DD_ERR_INVALID, "need 999 >= t_start >= t_end >= 0");
     if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE)
-        return fail(c, DD_ERR_INVALID, "dd_sample_early_exit generates noise on the device; for host noise drive dd_forward_early_exit");
+        return ctx_fail(c, DD_ERR_INVALID, "dd_sample_early_exit generates noise on the device; for host noise drive dd_forward_early_exit");
     // Two half-batch chains, as dd_sample: the samples are independent (every exit decision is per sample); the one quantity over the whole
     // batch -- the logged per-layer mean of the predicted errors, eesampler.py:70 -- becomes per-chain sums that one small launch joins
     // behind the loop, (chain 0 + chain 1) / B.  Heads and probes stay on each chain's own stream (measured: the 13 forks as parallel
@@ -1819,7 +1763,7 @@ int dd_profile_steps_chained(dd_ctx* c, dd_model* m, float* x_dev, const int64_t
 int dd_bench_gemm(dd_ctx* c, dd_model* m, int B, int iters, void* stream, float* ms_out, double* flops_out) {
     int rc = check_call(c, m, B, m && m->cfg.num_classes > 0 ? (const int64_t*)1 : nullptr);
     if (rc) return rc;
-    if (iters < 1 || !ms_out) return fail(c, DD_ERR_INVALID, "bad arguments");
+    if (iters < 1 || !ms_out) return ctx_fail(c, DD_ERR_INVALID, "bad arguments");
     hipStream_t s = (hipStream_t)stream;
     const int M = B * m->L, D = m->D;
     const BlockW& w = m->blocks[0];
@@ -1834,402 +1778,8 @@ int dd_bench_gemm(dd_ctx* c, dd_model* m, int B, int iters, void* stream, float*
         return launch_gemm<float>(g, EPI_BIAS_GELU, s, c->num_cus);
     };
     DD_HIP(c, once());
-    hipEvent_t e0, e1;
-    DD_HIP(c, hipEventCreate(&e0));
-    DD_HIP(c, hipEventCreate(&e1));
-    DD_HIP(c, hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) DD_HIP(c, once());
-    DD_HIP(c, hipEventRecord(e1, s));
-    DD_HIP(c, hipEventSynchronize(e1));
-    float ms = 0.f;
-    DD_HIP(c, hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    *ms_out = ms / (float)iters;
+    DD_HIP(c, time_launches(s, iters, once, ms_out));
     if (flops_out) *flops_out = 2.0 * (double)M * (double)m->hidden * (double)D;
-    return DD_OK;
-}
-
-int dd_dev_mlp(dd_ctx* c, int M, int D, int hidden, int extras, const float* x_host, const float* w1, const float* b1, const float* w2,
-               const float* b2, float* xres_host, unsigned short* out_host, const float* ln_in, const float* ln_out,
-               unsigned short* ln_out_host, int iters, void* stream, float* ms_out, const float* ao_host, const float* wproj,
-               const float* bproj, const float* skip_host, const float* wskip, const float* bskip, const float* wqkv,
-               unsigned short* qkv_out_host) {
-    const bool proj = ao_host && wproj && bproj;
-    const bool skp = skip_host && wskip && bskip;
-    const bool qk = wqkv && qkv_out_host;
-    if (qk && (!proj || !ln_out || (hidden / 32) % 2)) return DD_ERR_INVALID;   // the qkv phases ride on the proj-fused launch, behind norm1
-    if (proj && (!ln_in || D % 128)) return DD_ERR_INVALID;   // the projection rides in the LayerNorm-in kernel only
-    if (skp && (!proj || !ln_out || !ln_out_host || (hidden / 32) % 2)) return DD_ERR_INVALID;   // the skip phases ride on the proj-fused launch and end in norm1
-    if (!c || !x_host || !w1 || !b1 || !w2 || !b2 || !xres_host || M < 1 || iters < 0 || extras < 0 || (extras > 0 && M % (1 + extras))) return DD_ERR_INVALID;
-    if (!mlp_fused_supported(D, hidden)) return fail(c, DD_ERR_UNSUPPORTED, "fused MLP: D in {64,128,256,512}, hidden % 64 == 0");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t Mp = (size_t)round_up(M, 256);
-    std::vector<unsigned short> xh(Mp * D, 0), img(mlp_fused_image_bytes(D, hidden, proj, skp, qk) / 2, 0);
-    std::vector<float> b1p(hidden), xr(Mp * D, 0.f);
-    for (size_t i = 0; i < (size_t)M * D; ++i) { xh[i] = host_f2bf(x_host[i]); xr[i] = xres_host[i]; }
-    if (proj) mlp_fused_pack_proj(D, wproj, host_f2bf, img.data());
-    mlp_fused_pack(D, hidden, w1, b1, w2, ln_in != nullptr, host_f2bf, img.data() + (proj ? (size_t)D * D : 0), b1p.data());
-    if (skp) mlp_fused_pack_skip(D, wskip, host_f2bf, img.data() + (proj ? (size_t)D * D : 0) + (size_t)(hidden / 32) * 2 * (D / 16) * 512);
-    if (qk) mlp_fused_pack_rows(D, 3 * D, wqkv, host_f2bf, img.data() + (proj ? (size_t)D * D : 0) + ((size_t)(hidden / 32) * 2 + (skp ? D / 16 : 0)) * (D / 16) * 512);
-    // extras > 0: the M rows are `M / (1 + extras)` images of one patch token each (drives the hidden-split path);
-    // extras == 0: one image of M patch tokens (main tiles only)
-    MlpFusedArgs a{};
-    if (extras > 0) mlp_fused_plan(M / (1 + extras), 1, extras, 1 + extras, hidden, a);
-    else mlp_fused_plan(1, M, 0, M, hidden, a);
-    if (c->dev_flags & DD_DEV_MLP_EXTRAS_ONLY) { a.tiles_main = 0; a.n_main = 0; }   // time the hidden-split workgroups alone
-    const size_t part = (size_t)a.tiles_left * a.groups * 128 * D * sizeof(float);
-    void *dX = nullptr, *dI = nullptr, *dB1 = nullptr, *dB2 = nullptr, *dXr = nullptr, *dO = nullptr, *dP = nullptr, *dLn = nullptr, *dH = nullptr;
-    void *dAo = nullptr, *dBp = nullptr, *dSk = nullptr, *dBs = nullptr, *dQ = nullptr, *dQd = nullptr;
-    auto cleanup = [&]() { for (void* p : {dX, dI, dB1, dB2, dXr, dO, dP, dLn, dH, dAo, dBp, dSk, dBs, dQ, dQd}) if (p) (void)hipFree(p); };
-#define DD_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { cleanup(); return fail_hip(c, _e, #expr); } } while (0)
-    DD_TRY(hipMalloc(&dX, xh.size() * 2)); DD_TRY(hipMalloc(&dI, img.size() * 2)); DD_TRY(hipMalloc(&dB1, hidden * 4));
-    DD_TRY(hipMalloc(&dB2, D * 4)); DD_TRY(hipMalloc(&dXr, xr.size() * 4)); DD_TRY(hipMalloc(&dO, xh.size() * 2));
-    if (part) DD_TRY(hipMalloc(&dP, part));
-    DD_TRY(hipMemcpy(dX, xh.data(), xh.size() * 2, hipMemcpyHostToDevice));
-    DD_TRY(hipMemcpy(dI, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-    DD_TRY(hipMemcpy(dB1, b1p.data(), hidden * 4, hipMemcpyHostToDevice));
-    DD_TRY(hipMemcpy(dB2, b2, D * 4, hipMemcpyHostToDevice));
-    DD_TRY(hipMemcpy(dXr, xr.data(), xr.size() * 4, hipMemcpyHostToDevice));
-    DD_TRY(hipMemset(dO, 0, xh.size() * 2));
-    // ln_in / ln_out: [2, D] gamma then beta of the LayerNorm fused into the prologue / epilogue (or NULL)
-    DD_TRY(hipMalloc(&dLn, (size_t)4 * D * 4));
-    DD_TRY(hipMalloc(&dH, xh.size() * 2));
-    DD_TRY(hipMemset(dH, 0, xh.size() * 2));
-    if (ln_in) { DD_TRY(hipMemcpy(dLn, ln_in, (size_t)2 * D * 4, hipMemcpyHostToDevice)); a.ln_in_g = (const float*)dLn; a.ln_in_b = (const float*)dLn + D; }
-    if (ln_out && ln_out_host) {
-        DD_TRY(hipMemcpy((float*)dLn + 2 * D, ln_out, (size_t)2 * D * 4, hipMemcpyHostToDevice));
-        a.ln_out_g = (const float*)dLn + 2 * D; a.ln_out_b = (const float*)dLn + 3 * D; a.ln_out = (bf16_t*)dH;
-    }
-    a.X = (const bf16_t*)dX; a.ldx = D; a.wimg = (const char*)dI; a.b1p = (const float*)dB1; a.b2 = (const float*)dB2;
-    a.xres = (float*)dXr; a.out = out_host ? (bf16_t*)dO : nullptr; a.ldo = D; a.partial = (float*)dP;
-    if (proj) {   // as Backbone::block_tail does it: patch rows in the main tiles, extra-token rows in their hidden-split workgroups
-        std::vector<unsigned short> ah(Mp * D, 0);
-        for (size_t i = 0; i < (size_t)M * D; ++i) ah[i] = host_f2bf(ao_host[i]);
-        DD_TRY(hipMalloc(&dAo, ah.size() * 2)); DD_TRY(hipMalloc(&dBp, D * 4));
-        DD_TRY(hipMemcpy(dAo, ah.data(), ah.size() * 2, hipMemcpyHostToDevice));
-        DD_TRY(hipMemcpy(dBp, bproj, D * 4, hipMemcpyHostToDevice));
-        a.ao = (const bf16_t*)dAo; a.bproj = (const float*)dBp; a.nproj = D / 32;
-        a.reduce_set = 1;        // (the extra-token rows' projection runs in their hidden-split workgroups, Backbone::block_tail)
-    }
-    MlpFusedArgs ar = a;       // (what the reduce launch gets: see Backbone::block_tail)
-    if (skp) {
-        std::vector<unsigned short> sh(Mp * D, 0);
-        for (size_t i = 0; i < (size_t)M * D; ++i) sh[i] = host_f2bf(skip_host[i]);
-        DD_TRY(hipMalloc(&dSk, sh.size() * 2)); DD_TRY(hipMalloc(&dBs, D * 4));
-        DD_TRY(hipMemcpy(dSk, sh.data(), sh.size() * 2, hipMemcpyHostToDevice));
-        DD_TRY(hipMemcpy(dBs, bskip, D * 4, hipMemcpyHostToDevice));
-        a.skip = (const bf16_t*)dSk; a.bskip = (const float*)dBs; a.nskip = D / 16;
-        a.out = (bf16_t*)dO;   // y of the extra-token rows travels through the bf16 copy
-        ar = a; ar.ln_out = nullptr;
-    }
-    size_t qkv_elems = 0;
-    if (qk) {   // head-major qkv of the rows as images of a.tok_l tokens (HeadMajor, dd_internal.h): [images][3 D / 64 units][Lp][64]
-        a.hm = make_head_major(a.tok_l, D / 64);
-        const size_t images = (size_t)(M / a.tok_l);
-        qkv_elems = images * 3 * D * (size_t)a.hm.Lp;
-        DD_TRY(hipMalloc(&dQ, qkv_elems * 2)); DD_TRY(hipMalloc(&dQd, 16384));
-        DD_TRY(hipMemset(dQ, 0, qkv_elems * 2));
-        a.qkv_out = (bf16_t*)dQ; a.qkv_dump = (bf16_t*)dQd; a.nqkv = 3 * D / 32;
-        ar.qkv_out = a.qkv_out; ar.qkv_dump = a.qkv_dump; ar.nqkv = a.nqkv; ar.hm = a.hm;
-        if (!skp) ar = a;
-    }
-    DD_TRY(launch_mlp_fused(a, D, s));
-    DD_TRY(launch_mlp_reduce(ar, D, s));
-    DD_TRY(launch_skip_rows_ln(a, D, s));
-    DD_TRY(launch_qkv_rows(a, D, s));
-    DD_TRY(hipStreamSynchronize(s));
-    if (qk) DD_TRY(hipMemcpy(qkv_out_host, dQ, qkv_elems * 2, hipMemcpyDeviceToHost));
-    DD_TRY(hipMemcpy(xres_host, dXr, (size_t)M * D * 4, hipMemcpyDeviceToHost));
-    if (out_host) DD_TRY(hipMemcpy(out_host, dO, (size_t)M * D * 2, hipMemcpyDeviceToHost));
-    if (a.ln_out) DD_TRY(hipMemcpy(ln_out_host, dH, (size_t)M * D * 2, hipMemcpyDeviceToHost));
-    if (iters > 0 && ms_out) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        DD_TRY(hipEventCreate(&e0)); DD_TRY(hipEventCreate(&e1));
-        DD_TRY(hipEventRecord(e0, s));
-        for (int i = 0; i < iters; ++i) { DD_TRY(launch_mlp_fused(a, D, s)); DD_TRY(launch_mlp_reduce(ar, D, s)); DD_TRY(launch_skip_rows_ln(a, D, s)); DD_TRY(launch_qkv_rows(a, D, s)); }
-        DD_TRY(hipEventRecord(e1, s));
-        DD_TRY(hipEventSynchronize(e1));
-        float ms = 0.f;
-        DD_TRY(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        *ms_out = ms / (float)iters;
-    }
-#undef DD_TRY
-    cleanup();
-    return DD_OK;
-}
-
-int dd_dev_qkv_attention(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
-                         unsigned short* out_host, int iters, void* stream, float* ms_out) {
-    if (!c || !h_host || !wqkv || !out_host) return DD_ERR_INVALID;
-    const int D = 64 * H;
-    if (!qkv_attention_supported(D, H, L, extras)) return fail(c, DD_ERR_UNSUPPORTED, "qkv_attention: D = 512 / 768 / 1024, L = 256 + 1 or 2 extra tokens only");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t M = (size_t)B * L;
-    std::vector<unsigned short> hb(M * D), hf((size_t)B * 256 * D), img((size_t)3 * D * D);
-    for (size_t i = 0; i < hb.size(); ++i) hb[i] = host_f2bf(h_host[i]);
-    for (int b = 0; b < B; ++b)          // the patch rows in fragment order (what the fused block tail writes: MlpFusedArgs::ln_out_frag)
-        for (int n = 0; n < 256; ++n)
-            for (int k = 0; k < D; ++k)
-                hf[((((size_t)b * 8 + n / 32) * (D / 16) + k / 16) * 64 + (n % 32) + 32 * ((k % 16) / 8)) * 8 + k % 8] = hb[((size_t)b * L + extras + n) * D + k];
-    qkv_attention_pack(D, H, wqkv, host_f2bf, img.data());
-    void *dH = nullptr, *dW = nullptr, *dB = nullptr, *dQ = nullptr, *dO = nullptr;
-    auto cleanup = [&]() { for (void* p : {dH, dW, dB, dQ, dO}) if (p) (void)hipFree(p); };
-#define DD_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail(c, DD_ERR_HIP, hipGetErrorString(e_)); } } while (0)
-    DD_TRY(hipMalloc(&dH, hf.size() * 2)); DD_TRY(hipMalloc(&dW, img.size() * 2)); DD_TRY(hipMalloc(&dQ, hb.size() * 2)); DD_TRY(hipMalloc(&dO, M * D * 2));
-    DD_TRY(hipMemcpy(dH, hf.data(), hf.size() * 2, hipMemcpyHostToDevice));
-    DD_TRY(hipMemcpy(dW, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-    DD_TRY(hipMemcpy(dQ, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));     // row-major norm1 rows: the kernel reads the extra-token rows of it
-    DD_TRY(hipMemset(dO, 0, M * D * 2));
-    if (bqkv) { DD_TRY(hipMalloc(&dB, (size_t)3 * D * 4)); DD_TRY(hipMemcpy(dB, bqkv, (size_t)3 * D * 4, hipMemcpyHostToDevice)); }
-    DD_TRY(launch_qkv_attention((const bf16_t*)dH, (const bf16_t*)dW, (const float*)dB, (const bf16_t*)dQ, nullptr, nullptr, nullptr, (bf16_t*)dO, B, L, H, D, extras, s));
-    DD_TRY(hipStreamSynchronize(s));
-    DD_TRY(hipMemcpy(out_host, dO, M * D * 2, hipMemcpyDeviceToHost));
-    if (iters > 0 && ms_out) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        DD_TRY(hipEventCreate(&e0)); DD_TRY(hipEventCreate(&e1));
-        DD_TRY(hipEventRecord(e0, s));
-        for (int i = 0; i < iters; ++i) DD_TRY(launch_qkv_attention((const bf16_t*)dH, (const bf16_t*)dW, (const float*)dB, (const bf16_t*)dQ, nullptr, nullptr, nullptr, (bf16_t*)dO, B, L, H, D, extras, s));
-        DD_TRY(hipEventRecord(e1, s));
-        DD_TRY(hipEventSynchronize(e1));
-        float ms = 0.f;
-        DD_TRY(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        *ms_out = ms / (float)iters;
-    }
-#undef DD_TRY
-    cleanup();
-    return DD_OK;
-}
-
-int dd_dev_head_dec(dd_ctx* c, int M, int D, int pd, int tok_l, int tok_e, const float* x_host, const float* norm_g, const float* norm_b,
-                    const float* wdec, const float* bdec, float* dec_host, const float* probe_w, const float* probe_b, float* srow_host,
-                    int split, int iters, void* stream, float* ms_out) {
-    if (!c || !x_host || !norm_g || !norm_b || !wdec || !bdec || !dec_host || M < 1 || iters < 0) return DD_ERR_INVALID;
-    if (!head_dec_supported(D, pd)) return fail(c, DD_ERR_UNSUPPORTED, "head_dec: D in {256, 512, 768, 1024}, pd % 4 == 0, pd <= 64");
-    const bool probe = probe_w && probe_b && srow_host;
-    if (probe && !head_dec_probe_supported(D)) return fail(c, DD_ERR_UNSUPPORTED, "head_dec with the probe: D in {256, 512}");
-    hipStream_t s = (hipStream_t)stream;
-    if (split && !head_dec_probe_supported(D)) return fail(c, DD_ERR_UNSUPPORTED, "head_dec as a split-bf16 product: D in {256, 512}");
-    std::vector<float> wg, dc;
-    fold_head_norm(D, pd, wdec, bdec, norm_g, norm_b, wg, dc);
-    if (split) {      // wg becomes the packed image (as floats: two bf16 each), dc's second half the row sums of hi + lo
-        const int nt = (pd + 15) / 16;
-        std::vector<unsigned short> img((size_t)(D / 32) * nt * 2 * 64 * 8);
-        pack_head_split(D, pd, wg.data(), host_f2bf, img.data(), dc.data() + pd);
-        wg.assign(img.size() / 2, 0.f);
-        std::memcpy(wg.data(), img.data(), img.size() * 2);
-    }
-    void *dX = nullptr, *dW = nullptr, *dC = nullptr, *dO = nullptr, *dP = nullptr, *dPb = nullptr, *dS = nullptr;
-    auto cleanup = [&]() { for (void* p : {dX, dW, dC, dO, dP, dPb, dS}) if (p) (void)hipFree(p); };
-#define DD_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail(c, DD_ERR_HIP, hipGetErrorString(e_)); } } while (0)
-    DD_TRY(hipMalloc(&dX, (size_t)M * D * 4)); DD_TRY(hipMalloc(&dW, wg.size() * 4)); DD_TRY(hipMalloc(&dC, dc.size() * 4)); DD_TRY(hipMalloc(&dO, (size_t)M * pd * 4));
-    DD_TRY(hipMemcpy(dX, x_host, (size_t)M * D * 4, hipMemcpyHostToDevice));
-    DD_TRY(hipMemcpy(dW, wg.data(), wg.size() * 4, hipMemcpyHostToDevice));
-    DD_TRY(hipMemcpy(dC, dc.data(), dc.size() * 4, hipMemcpyHostToDevice));
-    DD_TRY(hipMemset(dO, 0xFF, (size_t)M * pd * 4));      // NaN: rows the launch does not decode stay recognisable
-    HeadDecArgs ha{(const float*)dX, (const float*)dW, (const float*)dC, (float*)dO, M, pd, tok_l, tok_e};
-    ha.split = split ? 1 : 0;
-    if (probe) {
-        DD_TRY(hipMalloc(&dP, (size_t)D * 4)); DD_TRY(hipMalloc(&dPb, 4)); DD_TRY(hipMalloc(&dS, (size_t)M * 4));
-        DD_TRY(hipMemcpy(dP, probe_w, (size_t)D * 4, hipMemcpyHostToDevice));
-        DD_TRY(hipMemcpy(dPb, probe_b, 4, hipMemcpyHostToDevice));
-        DD_TRY(hipMemset(dS, 0xFF, (size_t)M * 4));
-        ha.srow = (float*)dS; ha.pw_base = (const float*)dP; ha.pb_base = (const float*)dPb;     // (probe row 0: t_mul = add = 0, the step state is not read)
-    }
-    DD_TRY(launch_head_dec(ha, D, c->num_cus, s));
-    DD_TRY(hipStreamSynchronize(s));
-    DD_TRY(hipMemcpy(dec_host, dO, (size_t)M * pd * 4, hipMemcpyDeviceToHost));
-    if (probe) DD_TRY(hipMemcpy(srow_host, dS, (size_t)M * 4, hipMemcpyDeviceToHost));
-    if (iters > 0 && ms_out) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        DD_TRY(hipEventCreate(&e0)); DD_TRY(hipEventCreate(&e1));
-        DD_TRY(hipEventRecord(e0, s));
-        for (int i = 0; i < iters; ++i) DD_TRY(launch_head_dec(ha, D, c->num_cus, s));
-        DD_TRY(hipEventRecord(e1, s));
-        DD_TRY(hipEventSynchronize(e1));
-        float ms = 0.f;
-        DD_TRY(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        *ms_out = ms / (float)iters;
-    }
-#undef DD_TRY
-    cleanup();
-    return DD_OK;
-}
-
-int dd_dev_gemm(dd_ctx* c, int precision, int M, int N, int K, int K1, const float* A, const float* A2, const float* W, const float* bias,
-                int epilogue, int tile128, int hm_L, int hm_H, int splits, int resid, const float* ln, int tok_l, int tok_e,
-                float* xres_host, void* out_host, int ldo, unsigned short* h_host, unsigned short* frag_host, float* slab_host,
-                int num_cus, int iters, void* stream, float* ms_out) {
-    const bool bf = precision == DD_PREC_BF16;
-    if (K1 == 0) K1 = K;
-    const int KT = bf ? 64 : 32;
-    if (!c || (!bf && precision != DD_PREC_FP32) || M < 1 || N < 4 || N % 4 || K < KT || K % KT || K1 < KT || K1 > K || K1 % KT || !A || !W ||
-        (K1 < K && !A2) || ldo < N || ldo % (bf ? 8 : 4) || iters < 0 || num_cus < 0 || (num_cus > 0 && num_cus < 8) || tile128 < -1 || tile128 > 1)
-        return DD_ERR_INVALID;
-    if (splits > 0 && (!bf || splits < 2 || !bias || hm_L || (ln && !h_host) || (frag_host && (!ln || tok_l <= tok_e))))
-        return fail(c, DD_ERR_INVALID, "split-K: bf16, splits >= 2, bias, no head-major map; LayerNorm output needs h (and frag tok_l > tok_e)");
-    if (splits == 0 && (epilogue < EPI_STORE || epilogue > EPI_BIAS_STORE || ((epilogue == EPI_BIAS_RESID || epilogue == EPI_BIAS_SET) && !xres_host) ||
-                        (epilogue != EPI_STORE && !bias) || (hm_L && (hm_H < 1 || M % hm_L || !out_host))))
-        return DD_ERR_INVALID;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t esz = bf ? 2 : 4, Mo = (size_t)round_up(M, 256) + 8;
-    const HeadMajor hm = hm_L ? make_head_major(hm_L, hm_H) : HeadMajor{};
-    const size_t out_elems = hm_L ? ((size_t)(M / hm_L) * 3 * hm_H * hm.Lp + 64) * 64 : Mo * ldo;
-    const int lda = K1, lda2 = K - K1;
-    // operands as the kernel reads them: bf16 (or fp32) rows; A / A2 padded to Mo rows of 0xFF bytes (NaN: a row read past M shows up as one)
-    auto pack = [&](const float* src, size_t rows, size_t cols, size_t alloc_rows) {
-        std::vector<unsigned char> v(alloc_rows * cols * esz, 0xFF);
-        for (size_t i = 0; i < rows * cols; ++i) {
-            if (bf) { const unsigned short b = host_f2bf(src[i]); std::memcpy(&v[i * 2], &b, 2); }
-            else std::memcpy(&v[i * 4], &src[i], 4);
-        }
-        return v;
-    };
-    const std::vector<unsigned char> ha = pack(A, M, lda, Mo), hw = pack(W, N, K, N);
-    std::vector<unsigned char> ha2;
-    if (K1 < K) ha2 = pack(A2, M, lda2, Mo);
-    void *dA = nullptr, *dA2 = nullptr, *dW = nullptr, *dBias = nullptr, *dX = nullptr, *dO = nullptr, *dLn = nullptr, *dH = nullptr, *dF = nullptr, *dP = nullptr;
-    auto cleanup = [&]() { for (void* p : {dA, dA2, dW, dBias, dX, dO, dLn, dH, dF, dP}) if (p) (void)hipFree(p); };
-#define DD_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail_hip(c, e_, #x); } } while (0)
-    auto upload = [&](void** d, const void* h, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(d, bytes);
-        return e == hipSuccess ? hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice) : e;
-    };
-    auto canary = [&](void** d, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(d, bytes);
-        return e == hipSuccess ? hipMemset(*d, 0xFF, bytes) : e;
-    };
-    DD_TRY(upload(&dA, ha.data(), ha.size()));
-    if (K1 < K) DD_TRY(upload(&dA2, ha2.data(), ha2.size()));
-    DD_TRY(upload(&dW, hw.data(), hw.size()));
-    if (bias) DD_TRY(upload(&dBias, bias, (size_t)N * 4));
-    // every output buffer: canary bytes (0xFF) everywhere, or the caller's bytes (xres, canary rows included), returned whole
-    if (xres_host) DD_TRY(upload(&dX, xres_host, Mo * N * 4));
-    if (out_host) DD_TRY(canary(&dO, out_elems * esz));
-    const size_t slab_elems = (size_t)(splits > 0 ? splits : 0) * Mo * N;
-    if (splits > 0) {
-        if (!dX) DD_TRY(canary(&dX, Mo * N * 4));      // (resid == 0: x = the Linear; the caller may not want it back)
-        DD_TRY(canary(&dP, slab_elems * 4));
-        if (ln) DD_TRY(upload(&dLn, ln, (size_t)2 * N * 4));
-        if (h_host) DD_TRY(canary(&dH, Mo * N * 2));
-        if (frag_host) DD_TRY(canary(&dF, Mo * N * 2));
-    }
-    auto once = [&]() -> hipError_t {
-        if (!bf) {
-            GemmArgs<float> g{(const float*)dA, (const float*)dA2, (const float*)dW, (const float*)dBias, (float*)dX, (float*)dO, M, N, K, K1, lda,
-                              K1 < K ? lda2 : lda, ldo};
-            g.hm = hm;
-            return launch_gemm<float>(g, epilogue, s, num_cus ? num_cus : c->num_cus);
-        }
-        GemmArgs<bf16_t> g{(const bf16_t*)dA, (const bf16_t*)dA2, (const bf16_t*)dW, (const float*)dBias, (float*)dX, (bf16_t*)dO, M, N, K, K1, lda,
-                           K1 < K ? lda2 : lda, ldo};
-        g.hm = hm;
-        g.tile128 = tile128;
-        if (splits == 0) return launch_gemm<bf16_t>(g, epilogue, s, num_cus ? num_cus : c->num_cus);
-        g.partial = (float*)dP; g.splits = splits;
-        hipError_t e = launch_gemm_splitk(g, s, num_cus ? num_cus : c->num_cus);
-        if (e != hipSuccess) return e;
-        const float* lg = ln ? (const float*)dLn : nullptr;
-        return launch_reduce_ln(splitk_reduce_args(g, resid, lg, lg ? lg + N : nullptr, (bf16_t*)dH, (bf16_t*)dF, tok_l, tok_e), N, s);
-    };
-    DD_TRY(once());
-    DD_TRY(hipStreamSynchronize(s));
-    if (xres_host) DD_TRY(hipMemcpy(xres_host, dX, Mo * N * 4, hipMemcpyDeviceToHost));
-    if (out_host) DD_TRY(hipMemcpy(out_host, dO, out_elems * esz, hipMemcpyDeviceToHost));
-    if (h_host && dH) DD_TRY(hipMemcpy(h_host, dH, Mo * N * 2, hipMemcpyDeviceToHost));
-    if (frag_host && dF) DD_TRY(hipMemcpy(frag_host, dF, Mo * N * 2, hipMemcpyDeviceToHost));
-    if (slab_host && dP) DD_TRY(hipMemcpy(slab_host, dP, slab_elems * 4, hipMemcpyDeviceToHost));
-    if (iters > 0 && ms_out) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        DD_TRY(hipEventCreate(&e0)); DD_TRY(hipEventCreate(&e1));
-        DD_TRY(hipEventRecord(e0, s));
-        for (int i = 0; i < iters; ++i) DD_TRY(once());
-        DD_TRY(hipEventRecord(e1, s));
-        DD_TRY(hipEventSynchronize(e1));
-        float ms = 0.f;
-        DD_TRY(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        *ms_out = ms / (float)iters;
-    }
-#undef DD_TRY
-    cleanup();
-    return DD_OK;
-}
-
-int dd_dev_rowlin(dd_ctx* c, int B, int n_patches, int extras, int K, int k_split, int set_x, const float* A, const float* A2, const float* W,
-                  const float* bias, const float* ln, float* xres_host, unsigned short* x_copy_host, unsigned short* h_host, int frag,
-                  int iters, void* stream, float* ms_out) {
-    constexpr int D = 768;
-    const bool planned = n_patches > 0;
-    if (!c || B < 1 || n_patches < 0 || extras < 0 || (!planned && extras) || !A || !W || !bias || !xres_host || iters < 0 ||
-        (k_split && (2 * k_split != K || !A2)) || (h_host && !ln))
-        return DD_ERR_INVALID;
-    if (!rowlin_supported(D, K)) return fail(c, DD_ERR_UNSUPPORTED, "rowlin: K % 64 == 0, K >= 192");
-    hipStream_t s = (hipStream_t)stream;
-    const int M = planned ? B * (n_patches + extras) : B;
-    const size_t Mo = (size_t)round_up(M, 256) + 8;
-    const int lda = k_split ? k_split : K;
-    auto pack = [&](const float* src, size_t cols) {
-        std::vector<unsigned short> v(Mo * cols, 0xFFFF);
-        for (size_t i = 0; i < (size_t)M * cols; ++i) v[i] = host_f2bf(src[i]);
-        return v;
-    };
-    const std::vector<unsigned short> ha = pack(A, lda);
-    std::vector<unsigned short> ha2, img((size_t)K * D);
-    if (k_split) ha2 = pack(A2, lda);
-    rowlin_pack(K, W, host_f2bf, img.data());      // as finalize packs the model's rowlin images
-    void *dA = nullptr, *dA2 = nullptr, *dW = nullptr, *dBias = nullptr, *dX = nullptr, *dC = nullptr, *dLn = nullptr, *dH = nullptr, *dP = nullptr;
-    auto cleanup = [&]() { for (void* p : {dA, dA2, dW, dBias, dX, dC, dLn, dH, dP}) if (p) (void)hipFree(p); };
-#define DD_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail_hip(c, e_, #x); } } while (0)
-    auto upload = [&](void** d, const void* h, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(d, bytes);
-        return e == hipSuccess ? hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice) : e;
-    };
-    auto canary = [&](void** d, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(d, bytes);
-        return e == hipSuccess ? hipMemset(*d, 0xFF, bytes) : e;
-    };
-    DD_TRY(upload(&dA, ha.data(), ha.size() * 2));
-    if (k_split) DD_TRY(upload(&dA2, ha2.data(), ha2.size() * 2));
-    DD_TRY(upload(&dW, img.data(), img.size() * 2));
-    DD_TRY(upload(&dBias, bias, (size_t)D * 4));
-    DD_TRY(upload(&dX, xres_host, Mo * D * 4));
-    if (x_copy_host) DD_TRY(canary(&dC, Mo * D * 2));
-    if (ln) DD_TRY(upload(&dLn, ln, (size_t)2 * D * 4));
-    if (h_host) DD_TRY(canary(&dH, Mo * D * 2));
-    const size_t part = planned ? rowlin_partial_bytes(B, extras, K) : 0;
-    if (part) DD_TRY(canary(&dP, part));
-    GemmArgs<bf16_t> g{(const bf16_t*)dA, (const bf16_t*)dA2, nullptr, (const float*)dBias, (float*)dX, (bf16_t*)dC, M, D, K, k_split ? k_split : K,
-                       lda, lda, D};
-    const float* lg = ln ? (const float*)dLn : nullptr;
-    const RowLinArgs ra = rowlin_args(g, !set_x, (const char*)dW, (float*)dP, lg, lg ? lg + D : nullptr, frag ? nullptr : (bf16_t*)dH,
-                                      frag ? (bf16_t*)dH : nullptr, B, n_patches, extras);
-    const MlpFusedArgs fr = rowlin_reduce_args(ra);
-    auto once = [&]() -> hipError_t {
-        hipError_t e = launch_rowlin(ra, s);
-        return e == hipSuccess ? launch_mlp_reduce(fr, D, s) : e;
-    };
-    DD_TRY(once());
-    DD_TRY(hipStreamSynchronize(s));
-    DD_TRY(hipMemcpy(xres_host, dX, Mo * D * 4, hipMemcpyDeviceToHost));
-    if (x_copy_host) DD_TRY(hipMemcpy(x_copy_host, dC, Mo * D * 2, hipMemcpyDeviceToHost));
-    if (h_host) DD_TRY(hipMemcpy(h_host, dH, Mo * D * 2, hipMemcpyDeviceToHost));
-    if (iters > 0 && ms_out) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        DD_TRY(hipEventCreate(&e0)); DD_TRY(hipEventCreate(&e1));
-        DD_TRY(hipEventRecord(e0, s));
-        for (int i = 0; i < iters; ++i) DD_TRY(once());
-        DD_TRY(hipEventRecord(e1, s));
-        DD_TRY(hipEventSynchronize(e1));
-        float ms = 0.f;
-        DD_TRY(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        *ms_out = ms / (float)iters;
-    }
-#undef DD_TRY
-    cleanup();
     return DD_OK;
 }
 
@@ -2240,7 +1790,7 @@ int dd_plan_rows(int M, int N, int K, int num_cus, int* q_out, int* e_out) {
 
 int dd_set_num_cus(dd_ctx* c, int n) {
     if (!c) return DD_ERR_INVALID;
-    if (n < 8) return fail(c, DD_ERR_INVALID, "need at least 8 CUs");
+    if (n < 8) return ctx_fail(c, DD_ERR_INVALID, "need at least 8 CUs");
     c->num_cus = n / 8 * 8;      // the persistent kernels deal tiles to workgroups in groups of 8 (one per XCD)
     return DD_OK;
 }

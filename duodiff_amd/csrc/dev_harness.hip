@@ -1,0 +1,278 @@
+// The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_qkv_attention, dd_dev_head_dec, dd_dev_gemm,
+// dd_dev_rowlin): test scaffolding, not product.  Each one packs host operands as finalize packs a model's, launches what the model launches
+// (launch_args.h), returns the outputs and times `iters` further launch sequences.  Buffers, transfers, timing and HIP errors go through
+// one DevScope (dev_scope.h); the context is reached through its accessors only.
+#include "../../include/duodiff.h"
+#include "../../include/duodiff_dev.h"
+#include "dd_internal.h"
+#include "dev_scope.h"
+#include "launch_args.h"
+
+#include <cstring>
+#include <vector>
+
+using namespace dd;
+
+extern "C" {
+
+int dd_dev_mlp(dd_ctx* c, int M, int D, int hidden, int extras, const float* x_host, const float* w1, const float* b1, const float* w2,
+               const float* b2, float* xres_host, unsigned short* out_host, const float* ln_in, const float* ln_out,
+               unsigned short* ln_out_host, int iters, void* stream, float* ms_out, const float* ao_host, const float* wproj,
+               const float* bproj, const float* skip_host, const float* wskip, const float* bskip, const float* wqkv,
+               unsigned short* qkv_out_host) {
+    const bool proj = ao_host && wproj && bproj;
+    const bool skp = skip_host && wskip && bskip;
+    const bool qk = wqkv && qkv_out_host;
+    if (qk && (!proj || !ln_out || (hidden / 32) % 2)) return DD_ERR_INVALID;   // the qkv phases ride on the proj-fused launch, behind norm1
+    if (proj && (!ln_in || D % 128)) return DD_ERR_INVALID;   // the projection rides in the LayerNorm-in kernel only
+    if (skp && (!proj || !ln_out || !ln_out_host || (hidden / 32) % 2)) return DD_ERR_INVALID;   // the skip phases ride on the proj-fused launch and end in norm1
+    if (!c || !x_host || !w1 || !b1 || !w2 || !b2 || !xres_host || M < 1 || iters < 0 || extras < 0 || (extras > 0 && M % (1 + extras))) return DD_ERR_INVALID;
+    if (!mlp_fused_supported(D, hidden)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "fused MLP: D in {64,128,256,512}, hidden % 64 == 0");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t Mp = (size_t)round_up(M, 256), row_bytes = Mp * D * 2;      // (every bf16 row buffer: Mp rows, zero padding)
+    std::vector<unsigned short> img(mlp_fused_image_bytes(D, hidden, proj, skp, qk) / 2, 0);
+    std::vector<float> b1p(hidden), xr(Mp * D, 0.f);
+    std::memcpy(xr.data(), xres_host, (size_t)M * D * 4);
+    if (proj) mlp_fused_pack_proj(D, wproj, host_f2bf, img.data());
+    mlp_fused_pack(D, hidden, w1, b1, w2, ln_in != nullptr, host_f2bf, img.data() + (proj ? (size_t)D * D : 0), b1p.data());
+    if (skp) mlp_fused_pack_skip(D, wskip, host_f2bf, img.data() + (proj ? (size_t)D * D : 0) + (size_t)(hidden / 32) * 2 * (D / 16) * 512);
+    if (qk) mlp_fused_pack_rows(D, 3 * D, wqkv, host_f2bf, img.data() + (proj ? (size_t)D * D : 0) + ((size_t)(hidden / 32) * 2 + (skp ? D / 16 : 0)) * (D / 16) * 512);
+    // extras > 0: the M rows are `M / (1 + extras)` images of one patch token each (drives the hidden-split path);
+    // extras == 0: one image of M patch tokens (main tiles only)
+    MlpFusedArgs a{};
+    if (extras > 0) mlp_fused_plan(M / (1 + extras), 1, extras, 1 + extras, hidden, a);
+    else mlp_fused_plan(1, M, 0, M, hidden, a);
+    if (ctx_dev_flags(c) & DD_DEV_MLP_EXTRAS_ONLY) { a.tiles_main = 0; a.n_main = 0; }   // time the hidden-split workgroups alone
+    const size_t part = (size_t)a.tiles_left * a.groups * 128 * D * sizeof(float);
+    DevScope dev(c);
+    a.X = dev.upload(bf16_rows(x_host, M, D, Mp, 0).data(), row_bytes); a.ldx = D;
+    a.wimg = (const char*)dev.upload(img.data(), img.size() * 2);
+    a.b1p = dev.upload(b1p.data(), (size_t)hidden * 4); a.b2 = dev.upload(b2, (size_t)D * 4);
+    a.xres = dev.upload(xr.data(), xr.size() * 4);
+    bf16_t* dO = dev.filled<bf16_t>(row_bytes, 0);
+    a.out = out_host ? dO : nullptr; a.ldo = D;
+    a.partial = part ? dev.alloc<float>(part) : nullptr;
+    // ln_in / ln_out: [2, D] gamma then beta of the LayerNorm fused into the prologue / epilogue (or NULL)
+    bf16_t* dH = dev.filled<bf16_t>(row_bytes, 0);
+    if (ln_in) { a.ln_in_g = dev.upload(ln_in, (size_t)2 * D * 4); a.ln_in_b = a.ln_in_g + D; }
+    if (ln_out && ln_out_host) { a.ln_out_g = dev.upload(ln_out, (size_t)2 * D * 4); a.ln_out_b = a.ln_out_g + D; a.ln_out = dH; }
+    if (proj) {   // as Backbone::block_tail does it: patch rows in the main tiles, extra-token rows in their hidden-split workgroups
+        a.ao = dev.upload(bf16_rows(ao_host, M, D, Mp, 0).data(), row_bytes); a.bproj = dev.upload(bproj, (size_t)D * 4); a.nproj = D / 32;
+        a.reduce_set = 1;        // (the extra-token rows' projection runs in their hidden-split workgroups, Backbone::block_tail)
+    }
+    MlpFusedArgs ar = a;       // (what the reduce launch gets: see Backbone::block_tail)
+    if (skp) {
+        a.skip = dev.upload(bf16_rows(skip_host, M, D, Mp, 0).data(), row_bytes); a.bskip = dev.upload(bskip, (size_t)D * 4); a.nskip = D / 16;
+        a.out = dO;   // y of the extra-token rows travels through the bf16 copy
+        ar = a; ar.ln_out = nullptr;
+    }
+    size_t qkv_elems = 0;
+    if (qk) {   // head-major qkv of the rows as images of a.tok_l tokens (HeadMajor, dd_internal.h): [images][3 D / 64 units][Lp][64]
+        a.hm = make_head_major(a.tok_l, D / 64);
+        const size_t images = (size_t)(M / a.tok_l);
+        qkv_elems = images * 3 * D * (size_t)a.hm.Lp;
+        a.qkv_out = dev.filled<bf16_t>(qkv_elems * 2, 0); a.qkv_dump = dev.alloc<bf16_t>(16384); a.nqkv = 3 * D / 32;
+        ar.qkv_out = a.qkv_out; ar.qkv_dump = a.qkv_dump; ar.nqkv = a.nqkv; ar.hm = a.hm;
+        if (!skp) ar = a;
+    }
+    auto once = [&]() -> hipError_t {
+        hipError_t e = launch_mlp_fused(a, D, s);
+        if (e == hipSuccess) e = launch_mlp_reduce(ar, D, s);
+        if (e == hipSuccess) e = launch_skip_rows_ln(a, D, s);
+        return e == hipSuccess ? launch_qkv_rows(a, D, s) : e;
+    };
+    DEV_HIP(dev, once());
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    if (qk) dev.download(qkv_out_host, a.qkv_out, qkv_elems * 2);
+    dev.download(xres_host, a.xres, (size_t)M * D * 4);
+    if (out_host) dev.download(out_host, dO, (size_t)M * D * 2);
+    if (a.ln_out) dev.download(ln_out_host, dH, (size_t)M * D * 2);
+    DEV_HIP(dev, time_launches(s, iters, once, ms_out));
+    return dev.status();
+}
+
+int dd_dev_qkv_attention(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
+                         unsigned short* out_host, int iters, void* stream, float* ms_out) {
+    if (!c || !h_host || !wqkv || !out_host) return DD_ERR_INVALID;
+    const int D = 64 * H;
+    if (!qkv_attention_supported(D, H, L, extras)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "qkv_attention: D = 512 / 768 / 1024, L = 256 + 1 or 2 extra tokens only");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t M = (size_t)B * L;
+    const std::vector<unsigned short> hb = bf16_rows(h_host, M, D, M, 0);
+    std::vector<unsigned short> hf((size_t)B * 256 * D), img((size_t)3 * D * D);
+    for (int b = 0; b < B; ++b)          // the patch rows in fragment order (what the fused block tail writes: MlpFusedArgs::ln_out_frag)
+        for (int n = 0; n < 256; ++n)
+            for (int k = 0; k < D; ++k)
+                hf[((((size_t)b * 8 + n / 32) * (D / 16) + k / 16) * 64 + (n % 32) + 32 * ((k % 16) / 8)) * 8 + k % 8] = hb[((size_t)b * L + extras + n) * D + k];
+    qkv_attention_pack(D, H, wqkv, host_f2bf, img.data());
+    DevScope dev(c);
+    const bf16_t* dH = dev.upload(hf.data(), hf.size() * 2);
+    const bf16_t* dW = dev.upload(img.data(), img.size() * 2);
+    const bf16_t* dQ = dev.upload(hb.data(), hb.size() * 2);     // row-major norm1 rows: the kernel reads the extra-token rows of it
+    bf16_t* dO = dev.filled<bf16_t>(M * D * 2, 0);
+    const float* dB = bqkv ? dev.upload(bqkv, (size_t)3 * D * 4) : nullptr;
+    auto once = [&]() { return launch_qkv_attention(dH, dW, dB, dQ, nullptr, nullptr, nullptr, dO, B, L, H, D, extras, s); };
+    DEV_HIP(dev, once());
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(out_host, dO, M * D * 2);
+    DEV_HIP(dev, time_launches(s, iters, once, ms_out));
+    return dev.status();
+}
+
+int dd_dev_head_dec(dd_ctx* c, int M, int D, int pd, int tok_l, int tok_e, const float* x_host, const float* norm_g, const float* norm_b,
+                    const float* wdec, const float* bdec, float* dec_host, const float* probe_w, const float* probe_b, float* srow_host,
+                    int split, int iters, void* stream, float* ms_out) {
+    if (!c || !x_host || !norm_g || !norm_b || !wdec || !bdec || !dec_host || M < 1 || iters < 0) return DD_ERR_INVALID;
+    if (!head_dec_supported(D, pd)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "head_dec: D in {256, 512, 768, 1024}, pd % 4 == 0, pd <= 64");
+    const bool probe = probe_w && probe_b && srow_host;
+    if (probe && !head_dec_probe_supported(D)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "head_dec with the probe: D in {256, 512}");
+    hipStream_t s = (hipStream_t)stream;
+    if (split && !head_dec_probe_supported(D)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "head_dec as a split-bf16 product: D in {256, 512}");
+    std::vector<float> wg, dc;
+    fold_head_norm(D, pd, wdec, bdec, norm_g, norm_b, wg, dc);
+    if (split) {      // wg becomes the packed image (as floats: two bf16 each), dc's second half the row sums of hi + lo
+        const int nt = (pd + 15) / 16;
+        std::vector<unsigned short> img((size_t)(D / 32) * nt * 2 * 64 * 8);
+        pack_head_split(D, pd, wg.data(), host_f2bf, img.data(), dc.data() + pd);
+        wg.assign(img.size() / 2, 0.f);
+        std::memcpy(wg.data(), img.data(), img.size() * 2);
+    }
+    DevScope dev(c);
+    const float* dX = dev.upload(x_host, (size_t)M * D * 4);
+    const float* dW = dev.upload(wg.data(), wg.size() * 4);
+    const float* dC = dev.upload(dc.data(), dc.size() * 4);
+    float* dO = dev.filled<float>((size_t)M * pd * 4, 0xFF);      // NaN: rows the launch does not decode stay recognisable
+    HeadDecArgs ha{dX, dW, dC, dO, M, pd, tok_l, tok_e};
+    ha.split = split ? 1 : 0;
+    if (probe) {
+        ha.pw_base = dev.upload(probe_w, (size_t)D * 4); ha.pb_base = dev.upload(probe_b, 4);
+        ha.srow = dev.filled<float>((size_t)M * 4, 0xFF);     // (probe row 0: t_mul = add = 0, the step state is not read)
+    }
+    auto once = [&]() { return launch_head_dec(ha, D, ctx_num_cus(c), s); };
+    DEV_HIP(dev, once());
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(dec_host, dO, (size_t)M * pd * 4);
+    if (probe) dev.download(srow_host, ha.srow, (size_t)M * 4);
+    DEV_HIP(dev, time_launches(s, iters, once, ms_out));
+    return dev.status();
+}
+
+int dd_dev_gemm(dd_ctx* c, int precision, int M, int N, int K, int K1, const float* A, const float* A2, const float* W, const float* bias,
+                int epilogue, int tile128, int hm_L, int hm_H, int splits, int resid, const float* ln, int tok_l, int tok_e,
+                float* xres_host, void* out_host, int ldo, unsigned short* h_host, unsigned short* frag_host, float* slab_host,
+                int num_cus, int iters, void* stream, float* ms_out) {
+    const bool bf = precision == DD_PREC_BF16;
+    if (K1 == 0) K1 = K;
+    const int KT = bf ? 64 : 32;
+    if (!c || (!bf && precision != DD_PREC_FP32) || M < 1 || N < 4 || N % 4 || K < KT || K % KT || K1 < KT || K1 > K || K1 % KT || !A || !W ||
+        (K1 < K && !A2) || ldo < N || ldo % (bf ? 8 : 4) || iters < 0 || num_cus < 0 || (num_cus > 0 && num_cus < 8) || tile128 < -1 || tile128 > 1)
+        return DD_ERR_INVALID;
+    if (splits > 0 && (!bf || splits < 2 || !bias || hm_L || (ln && !h_host) || (frag_host && (!ln || tok_l <= tok_e))))
+        return ctx_fail(c, DD_ERR_INVALID, "split-K: bf16, splits >= 2, bias, no head-major map; LayerNorm output needs h (and frag tok_l > tok_e)");
+    if (splits == 0 && (epilogue < EPI_STORE || epilogue > EPI_BIAS_STORE || ((epilogue == EPI_BIAS_RESID || epilogue == EPI_BIAS_SET) && !xres_host) ||
+                        (epilogue != EPI_STORE && !bias) || (hm_L && (hm_H < 1 || M % hm_L || !out_host))))
+        return DD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t esz = bf ? 2 : 4, Mo = (size_t)round_up(M, 256) + 8;
+    const HeadMajor hm = hm_L ? make_head_major(hm_L, hm_H) : HeadMajor{};
+    const size_t out_elems = hm_L ? ((size_t)(M / hm_L) * 3 * hm_H * hm.Lp + 64) * 64 : Mo * ldo;
+    const int lda = K1, lda2 = K - K1;
+    DevScope dev(c);
+    // operands as the kernel reads them: bf16 (or fp32) rows; A / A2 padded to Mo rows of 0xFF bytes (NaN: a row read past M shows up as one)
+    auto operand = [&](const float* src, size_t rows, size_t cols, size_t alloc_rows) -> const void* {
+        if (bf) return dev.upload(bf16_rows(src, rows, cols, alloc_rows, 0xFF).data(), alloc_rows * cols * 2);
+        std::vector<unsigned char> v(alloc_rows * cols * 4, 0xFF);
+        std::memcpy(v.data(), src, rows * cols * 4);
+        return dev.upload(v.data(), v.size());
+    };
+    const void* dA = operand(A, M, lda, Mo);
+    const void* dA2 = K1 < K ? operand(A2, M, lda2, Mo) : nullptr;
+    const void* dW = operand(W, N, K, N);
+    const float* dBias = bias ? dev.upload(bias, (size_t)N * 4) : nullptr;
+    // every output buffer: canary bytes (0xFF) everywhere, or the caller's bytes (xres, canary rows included), returned whole
+    float* dX = xres_host ? dev.upload(xres_host, Mo * N * 4) : nullptr;
+    void* dO = out_host ? dev.filled(out_elems * esz, 0xFF) : nullptr;
+    const size_t slab_elems = (size_t)(splits > 0 ? splits : 0) * Mo * N;
+    float *dP = nullptr, *dLn = nullptr;
+    bf16_t *dH = nullptr, *dF = nullptr;
+    if (splits > 0) {
+        if (!dX) dX = dev.filled<float>(Mo * N * 4, 0xFF);      // (resid == 0: x = the Linear; the caller may not want it back)
+        dP = dev.filled<float>(slab_elems * 4, 0xFF);
+        if (ln) dLn = dev.upload(ln, (size_t)2 * N * 4);
+        if (h_host) dH = dev.filled<bf16_t>(Mo * N * 2, 0xFF);
+        if (frag_host) dF = dev.filled<bf16_t>(Mo * N * 2, 0xFF);
+    }
+    auto once = [&]() -> hipError_t {
+        if (!bf) {
+            GemmArgs<float> g{(const float*)dA, (const float*)dA2, (const float*)dW, dBias, dX, (float*)dO, M, N, K, K1, lda,
+                              K1 < K ? lda2 : lda, ldo};
+            g.hm = hm;
+            return launch_gemm<float>(g, epilogue, s, num_cus ? num_cus : ctx_num_cus(c));
+        }
+        GemmArgs<bf16_t> g{(const bf16_t*)dA, (const bf16_t*)dA2, (const bf16_t*)dW, dBias, dX, (bf16_t*)dO, M, N, K, K1, lda,
+                           K1 < K ? lda2 : lda, ldo};
+        g.hm = hm;
+        g.tile128 = tile128;
+        if (splits == 0) return launch_gemm<bf16_t>(g, epilogue, s, num_cus ? num_cus : ctx_num_cus(c));
+        g.partial = dP; g.splits = splits;
+        hipError_t e = launch_gemm_splitk(g, s, num_cus ? num_cus : ctx_num_cus(c));
+        if (e != hipSuccess) return e;
+        const float* lg = ln ? dLn : nullptr;
+        return launch_reduce_ln(splitk_reduce_args(g, resid, lg, lg ? lg + N : nullptr, dH, dF, tok_l, tok_e), N, s);
+    };
+    DEV_HIP(dev, once());
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    if (xres_host) dev.download(xres_host, dX, Mo * N * 4);
+    if (out_host) dev.download(out_host, dO, out_elems * esz);
+    if (h_host && dH) dev.download(h_host, dH, Mo * N * 2);
+    if (frag_host && dF) dev.download(frag_host, dF, Mo * N * 2);
+    if (slab_host && dP) dev.download(slab_host, dP, slab_elems * 4);
+    DEV_HIP(dev, time_launches(s, iters, once, ms_out));
+    return dev.status();
+}
+
+int dd_dev_rowlin(dd_ctx* c, int B, int n_patches, int extras, int K, int k_split, int set_x, const float* A, const float* A2, const float* W,
+                  const float* bias, const float* ln, float* xres_host, unsigned short* x_copy_host, unsigned short* h_host, int frag,
+                  int iters, void* stream, float* ms_out) {
+    constexpr int D = 768;
+    const bool planned = n_patches > 0;
+    if (!c || B < 1 || n_patches < 0 || extras < 0 || (!planned && extras) || !A || !W || !bias || !xres_host || iters < 0 ||
+        (k_split && (2 * k_split != K || !A2)) || (h_host && !ln))
+        return DD_ERR_INVALID;
+    if (!rowlin_supported(D, K)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "rowlin: K % 64 == 0, K >= 192");
+    hipStream_t s = (hipStream_t)stream;
+    const int M = planned ? B * (n_patches + extras) : B;
+    const size_t Mo = (size_t)round_up(M, 256) + 8;
+    const int lda = k_split ? k_split : K;
+    std::vector<unsigned short> img((size_t)K * D);
+    rowlin_pack(K, W, host_f2bf, img.data());      // as finalize packs the model's rowlin images
+    DevScope dev(c);
+    // A / A2 padded to Mo rows of 0xFF bytes; every output buffer: canary bytes (0xFF) everywhere, or the caller's bytes (xres)
+    const bf16_t* dA = dev.upload(bf16_rows(A, M, lda, Mo, 0xFF).data(), Mo * lda * 2);
+    const bf16_t* dA2 = k_split ? dev.upload(bf16_rows(A2, M, lda, Mo, 0xFF).data(), Mo * lda * 2) : nullptr;
+    const bf16_t* dW = dev.upload(img.data(), img.size() * 2);
+    const float* dBias = dev.upload(bias, (size_t)D * 4);
+    float* dX = dev.upload(xres_host, Mo * D * 4);
+    bf16_t* dC = x_copy_host ? dev.filled<bf16_t>(Mo * D * 2, 0xFF) : nullptr;
+    const float* lg = ln ? dev.upload(ln, (size_t)2 * D * 4) : nullptr;
+    bf16_t* dH = h_host ? dev.filled<bf16_t>(Mo * D * 2, 0xFF) : nullptr;
+    const size_t part = planned ? rowlin_partial_bytes(B, extras, K) : 0;
+    float* dP = part ? dev.filled<float>(part, 0xFF) : nullptr;
+    GemmArgs<bf16_t> g{dA, dA2, nullptr, dBias, dX, dC, M, D, K, k_split ? k_split : K, lda, lda, D};
+    const RowLinArgs ra = rowlin_args(g, !set_x, (const char*)dW, dP, lg, lg ? lg + D : nullptr, frag ? nullptr : dH, frag ? dH : nullptr,
+                                      B, n_patches, extras);
+    const MlpFusedArgs fr = rowlin_reduce_args(ra);
+    auto once = [&]() -> hipError_t {
+        hipError_t e = launch_rowlin(ra, s);
+        return e == hipSuccess ? launch_mlp_reduce(fr, D, s) : e;
+    };
+    DEV_HIP(dev, once());
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(xres_host, dX, Mo * D * 4);
+    if (x_copy_host) dev.download(x_copy_host, dC, Mo * D * 2);
+    if (h_host) dev.download(h_host, dH, Mo * D * 2);
+    DEV_HIP(dev, time_launches(s, iters, once, ms_out));
+    return dev.status();
+}
+
+}  // extern "C"

@@ -7,6 +7,7 @@
 // image (0.5 % of the FLOPs of 1000 sampling steps), so the design goal is correctness on parity-proven kernels.
 #include "../../include/duodiff.h"
 #include "dd_internal.h"
+#include "dev_scope.h"
 #include "host_arena.h"
 
 #include <cmath>
@@ -18,9 +19,6 @@
 
 using namespace dd;
 
-struct dd_ctx;
-extern "C" const char* dd_last_error(dd_ctx*);
-namespace dd { int ctx_fail(dd_ctx* c, int code, const std::string& msg); int ctx_device(dd_ctx* c); int ctx_num_cus(dd_ctx* c); }
 
 namespace {
 

@@ -32,10 +32,10 @@ int dd_dev_mlp(dd_ctx* ctx, int M, int D, int hidden, int extras, const float* h
                const float* ao_host, const float* wproj, const float* bproj, const float* skip_host, const float* wskip,
                const float* bskip, const float* wqkv, unsigned short* qkv_out_host);
 
-/* Development harness for the attention launch that computes attn.qkv itself (attention.hip qkv_attention_kernel; bf16, 8 heads
- * of 64, L = 256 patches + `extras` = 1 or 2 leading extra tokens): out = softmax(q k^T / 8) v per (image, head) with
- * q, k, v = split(h . wqkv^T + bqkv), from host arrays h [B L, 512] (rounded to bf16), wqkv [1536, 512], bqkv [1536] or NULL;
- * out_host bf16 [B L, 512].  `iters` timed launches -> ms_out. */
+/* Development harness for the attention launch that computes attn.qkv itself (attention.hip qkv_attention_kernel; bf16, H heads
+ * of 64 with D = 64 H = 512, 768 or 1024, L = 256 patches + `extras` = 1 or 2 leading extra tokens -- qkv_attention_supported; anything else
+ * is DD_ERR_UNSUPPORTED): out = softmax(q k^T / 8) v per (image, head) with q, k, v = split(h . wqkv^T + bqkv), from host arrays
+ * h [B L, D] (rounded to bf16), wqkv [3 D, D], bqkv [3 D] or NULL; out_host bf16 [B L, D].  `iters` timed launches -> ms_out. */
 int dd_dev_qkv_attention(dd_ctx* ctx, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
                          unsigned short* out_host, int iters, void* stream, float* ms_out);
 

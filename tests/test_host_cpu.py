@@ -199,6 +199,11 @@ def test_bench_roofline_leg_follows_the_committed_kernel_table():
             assert kind in Model.PROFILE_KINDS and 0 < b.cu_share_half_batch(kind, mp, B) <= 1.0
     lib = _lib.load()
     assert lib.dd_profile_select(None, 0) == _lib.DD_ERR_INVALID      # (a null context is refused: the symbol exists and checks its arguments)
+    # ... and so is it by the single-kernel development entry points (csrc/dev_harness.hip), called through their bound signatures with every
+    # pointer null and every integer 0: they check the context before anything touches the GPU
+    for name in ("dd_dev_mlp", "dd_dev_qkv_attention", "dd_dev_head_dec", "dd_dev_gemm", "dd_dev_rowlin"):
+        args = [0 if t is ctypes.c_int else None for t in _lib.SIGNATURES[name][1]]
+        assert getattr(lib, name)(*args) == _lib.DD_ERR_INVALID, name
 
 
 def test_bench_steps_and_output_dump(tmp_path):

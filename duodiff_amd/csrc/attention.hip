@@ -18,6 +18,7 @@
 // The L x L score matrix is never written anywhere (reference: 270 MB per layer at B=128).
 // Works in bf16 (v_mfma_f32_32x32x16_bf16) and in the fp32 parity mode (v_mfma_f32_32x32x2_f32).
 #include "dd_internal.h"
+#include "wave_prims.h"
 
 #include <type_traits>
 #include <utility>
@@ -29,17 +30,6 @@ constexpr int kMaxKeyTiles = 9;          // 9 x 32 = 288 >= 258
 constexpr int kLP = kMaxKeyTiles * 32;   // padded key count held in LDS
 constexpr int kHD = 64;
 constexpr int kPartBytes = 4 * 2 * 66 * 4;   // split last query chunk: [4 waves][2 queries][64 d, max, sum] fp32
-
-__device__ __forceinline__ unsigned pack2_bf16(float lo, float hi) {   // one v_cvt_pk_bf16_f32 (round to nearest even, as f2bf)
-    typedef __bf16 bf16v2 __attribute__((ext_vector_type(2)));
-    typedef float f32v2 __attribute__((ext_vector_type(2)));
-    const f32v2 q = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(q, bf16v2));
-}
-
-__device__ __forceinline__ unsigned lds_addr_of(const void* p) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
-}
 
 // XOR swizzles of the bf16 K / V images in LDS (128-byte rows of eight 16-byte chunks; chunk ch of row r is stored at chunk ch ^ swz(r)).
 // Each serves the image's READ pattern and its WRITE pattern without a bank conflict (MI355X_MICROARCH.md, LDS: a ds_read_b128 serves 4 groups of
@@ -203,8 +193,8 @@ __device__ __forceinline__ void attend_tiles(const char* Ks, const char* Vt, int
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
                     const char* vr = vbd[dt] + (t * 32 + 16 * st) * Lay::kRowV;
-                    f.lo[st][dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(size_t)lds_addr_of(vr));
-                    f.hi[st][dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(size_t)lds_addr_of(vr + 8 * Lay::kRowV));
+                    f.lo[st][dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(size_t)lds_offset(vr));
+                    f.hi[st][dt] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(size_t)lds_offset(vr + 8 * Lay::kRowV));
                 }
         };
         VF va, vb;
@@ -298,8 +288,6 @@ attention_kernel(const T* __restrict__ qkv, T* __restrict__ out, int B, int L, i
         // LDS-DMA, 1 KB pieces of 8 rows x 128 B: piece p of K, then piece p of V; lane = (row 8p + (lane >> 3), slot lane & 7)
         // fetches the chunk that belongs in its slot (source-side swizzle).  Rows [L, Lp) of the images receive a copy of row L - 1 (masked keys);
         // rows [Lp, 32 nkt) of the LDS images are zeroed here (V: 0 x garbage must not be NaN).
-        typedef const __attribute__((address_space(1))) void* gptr_t;
-        typedef __attribute__((address_space(3))) void* lptr_t;
         const int np = Lp >> 3;                                        // pieces per operand (33 for L = 257 / 258)
         const int wv = __builtin_amdgcn_readfirstlane(wave);
         const int lr = lane >> 3, slot = lane & 7;
@@ -315,14 +303,14 @@ attention_kernel(const T* __restrict__ qkv, T* __restrict__ out, int B, int L, i
                 // that the softmax masks; nothing may depend on what the workspace held before this call)
                 const T* src = (isv ? vbase : kbase) + (long long)(r < L ? r : L - 1) * kHD + ch * 8;
                 char* dst = (isv ? Vt : Ks) + p * 1024;
-                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
+                lds_dma16(src, dst);
             }
         }
         for (int i = tid; i < (nkt * 32 - Lp) * 16; i += 256) {       // 8 chunks per row, K and V
             const int rr = Lp + (i >> 4), c = i & 15;
             *reinterpret_cast<f32x4*>((c < 8 ? Ks : Vt) + rr * 128 + (c & 7) * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // this wave's pieces have landed (hipcc does not track LDS-DMA writes)
+        waitcnt_vm<0>();                                               // this wave's pieces have landed (hipcc does not track LDS-DMA writes)
     } else {
         for (int idx = tid; idx < nkt * 32 * CPR; idx += 256) {
             const int key = idx / CPR, ch = idx % CPR;
@@ -475,9 +463,6 @@ constexpr int kQaBlk = 2 * kQaKQ * 1024;             // one weight block = (slic
 constexpr int kQaRing = 4 * kQaBlk;
 static_assert(8 * 2 * 66 * 4 <= kQaPxBytes, "the split chunk's partials reuse the px area");
 
-typedef const __attribute__((address_space(1))) void* qa_gptr_t;
-typedef __attribute__((address_space(3))) void* qa_lptr_t;
-
 // Phase A since round 4 -- the k range in SLICES of 8 k-steps, all six accumulators resident, the rows double-buffered:
 //   for slice q: [rows of h, k-steps 8 q .. 8 q + 7, as 32 VGPRs of B fragments; slice q + 1 is requested into the other 32 now]
 //       for tile pair (q0 q1), (k0 k1), (v0 v1):  acc[t] += W(q, t) . h_q^T      (one 16 KB weight block = 2 tiles x 8 k-steps, 16 MFMAs per wave)
@@ -524,17 +509,14 @@ __global__ void __launch_bounds__(512, 1) qkv_attention_kernel(const QkvAttnArgs
     const int half = lane >> 5, r32 = lane & 31;
     const int L = a.L, E = a.E;
 
-    // LDS-DMA in the scalar-base form (uniform 64-bit base in SGPRs + one 32-bit lane offset), written as asm: the builtin makes a 64-bit VGPR address
-    // pair of it, and that form serialises with the MFMAs of BOTH waves of the SIMD (75 cycles per request, profiles/r05/dma_mfma_probe_roles.txt)
+    // LDS-DMA in the scalar-base form: the VGPR-pair form serialises with the MFMAs of BOTH waves of the SIMD (75 cycles per request, profiles/r05/dma_mfma_probe_roles.txt)
     const char* wsrc = reinterpret_cast<const char*>(a.wimg) + (size_t)hh * NB * kQaBlk;
     const unsigned lane16 = lane * 16;
     auto dma_block = [&](int bb) {      // block bb -> ring slot bb & 3: two 1 KB pieces per wave
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int pc = wave * 2 + i;
-            const char* sb = wsrc + (size_t)bb * kQaBlk + pc * 1024;
-            const unsigned lds = lds_addr_of(ring + (bb & 3) * kQaBlk + pc * 1024);
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(lane16), "s"(sb) : "memory", "m0");
+            lds_dma16s(wsrc + (size_t)bb * kQaBlk + pc * 1024, lane16, ring + (bb & 3) * kQaBlk + pc * 1024);
         }
     };
     dma_block(0);
@@ -566,23 +548,19 @@ __global__ void __launch_bounds__(512, 1) qkv_attention_kernel(const QkvAttnArgs
             xv[v] = *reinterpret_cast<const f32x4*>(xr + 4 * v);
             s1 += (xv[v][0] + xv[v][1]) + (xv[v][2] + xv[v][3]);
         }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) s1 += __shfl_xor(s1, o);
-        const float mean = s1 / (float)D;
+        const float mean = wave_reduce_add(s1) / (float)D;
         float s2 = 0.f;
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
             xv[v] = xv[v] - mean;
             s2 += (xv[v][0] * xv[v][0] + xv[v][1] * xv[v][1]) + (xv[v][2] * xv[v][2] + xv[v][3] * xv[v][3]);
         }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) s2 += __shfl_xor(s2, o);
-        const float rstd = 1.0f / sqrtf(s2 / (float)D + 1e-5f);
+        const float rstd = 1.0f / sqrtf(wave_reduce_add(s2) / (float)D + 1e-5f);
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
             const f32x4 g = *reinterpret_cast<const f32x4*>(a.ln_g + lane * (D / 64) + 4 * v), c0 = *reinterpret_cast<const f32x4*>(a.ln_b + lane * (D / 64) + 4 * v);
             const f32x4 y = xv[v] * rstd * g + c0;
-            *reinterpret_cast<uint2*>(hxl + wave * (D * 2 + kQaHxPad) + (lane * (D / 64) + 4 * v) * 2) = uint2{pack2_bf16(y[0], y[1]), pack2_bf16(y[2], y[3])};
+            *reinterpret_cast<uint2*>(hxl + wave * (D * 2 + kQaHxPad) + (lane * (D / 64) + 4 * v) * 2) = uint2{cvt_pk_bf16(y[0], y[1]), cvt_pk_bf16(y[2], y[3])};
         }
     }
     for (int i = tid; i < (kLP - 256 - E) * 16; i += 512) {
@@ -677,7 +655,7 @@ __global__ void __launch_bounds__(512, 1) qkv_attention_kernel(const QkvAttnArgs
         }
         unsigned pk[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) pk[i] = pack2_bf16(acc[j][2 * i], acc[j][2 * i + 1]);
+        for (int i = 0; i < 8; ++i) pk[i] = cvt_pk_bf16(acc[j][2 * i], acc[j][2 * i + 1]);
         const int T = j & 1;
         if (j < 2) {            // q: registers 8 eh .. 8 eh + 7 of d tile T are k-step 2 T + eh of S^T = K Q^T
             qcur[2 * T] = __builtin_bit_cast(f32x4, uint4{pk[0], pk[1], pk[2], pk[3]});
@@ -800,20 +778,16 @@ hipError_t launch_attention(const T* qkv, T* out, int B, int L, int H, int D, hi
 }
 
 // attn.qkv weight [3 D, D] (nn.Linear layout) -> per head the weight blocks the kernel streams, in stream order: [slice q of the k range:
-// 8 k-steps][tile pair jj][tile t of the pair][k-step][lane] x 16 bytes (tiles j = 2 jj + t = q0 q1 k0 k1 v0 v1), each 1 KB fragment in
-// MFMA A-operand order:
-// img[(((((head * NS + q) * 3 + jj) * 2 + t) * 8 + ks) * 64 + lane) * 8 + i] = W[(j >> 1) D + 64 head + 32 (j & 1) + (lane & 31)][16 (8 q + ks) + 8 (lane >> 5) + i]
+// 8 k-steps][tile pair jj][tile t of the pair][k-step] x 1 KB fragment in natural k order (tiles j = 2 jj + t = q0 q1 k0 k1 v0 v1): tile j of head hh =
+// rows (j >> 1) D + 64 hh + 32 (j & 1) .. + 31 of W
 void qkv_attention_pack(int D, int H, const float* w, unsigned short (*to_bf16)(float), unsigned short* img) {
     const int NS = D / 16 / kQaKQ;
     for (int hh = 0; hh < H; ++hh)
         for (int q = 0; q < NS; ++q)
             for (int j = 0; j < 6; ++j)
                 for (int ks = 0; ks < kQaKQ; ++ks)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const float* src = w + ((size_t)(j >> 1) * D + 64 * hh + 32 * (j & 1) + (lane & 31)) * D + 16 * (q * kQaKQ + ks) + 8 * (lane >> 5);
-                        unsigned short* dst = img + (((((size_t)hh * NS + q) * 6 + j) * kQaKQ + ks) * 64 + lane) * 8;
-                        for (int i = 0; i < 8; ++i) dst[i] = to_bf16(src[i]);
-                    }
+                    pack_fragment(w, D, (j >> 1) * D + 64 * hh + 32 * (j & 1), 16 * (q * kQaKQ + ks), FRAG_K_NATURAL, to_bf16,
+                                  img + ((((size_t)hh * NS + q) * 6 + j) * kQaKQ + ks) * 512);
 }
 
 bool qkv_attention_supported(int D, int H, int L, int extras) {

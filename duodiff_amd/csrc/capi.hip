@@ -371,18 +371,15 @@ void pack_block(dd_model* m, Arena& a, int bi, const std::string& next_skip, con
         const bool with_skip = m->fused_skip && !next_skip.empty();
         // (an out-block's qkv needs its skip_linear in here too; with fused_qa the attention launch computes qkv and no section is packed)
         const bool with_qkv = m->fused_qkv && !m->fused_qa && !next_qkv.empty() && (next_skip.empty() || with_skip);
-        char* img = a.raw(w.mlp_img, mlp_fused_image_bytes(D, hid, m->fused_proj, with_skip, with_qkv));
-        const size_t proj_bytes = m->fused_proj ? (size_t)D * D * 2 : 0;      // D/32 blocks of Wproj lead the stream
+        const MlpImage im = MlpImage::of(D, hid, m->fused_proj, with_skip, with_qkv);
+        char* img = a.raw(w.mlp_img, im.bytes());
+        auto section = [&](size_t block) { return (unsigned short*)(img + im.at(block)); };
         std::vector<float> b1p(hid);
-        if (m->fused_proj) mlp_fused_pack_proj(D, P(p + "attn.proj.weight").data(), host_f2bf, (unsigned short*)img);
-        mlp_fused_pack(D, hid, P(p + "mlp.fc1.weight").data(), P(p + "mlp.fc1.bias").data(), P(p + "mlp.fc2.weight").data(),
-                       true, host_f2bf, (unsigned short*)(img + proj_bytes), b1p.data());
-        if (with_skip)    // the next block's skip_linear: 2 D/32 blocks behind the MLP blocks
-            mlp_fused_pack_skip(D, P(next_skip + "skip_linear.weight").data(), host_f2bf,
-                                (unsigned short*)(img + proj_bytes + (size_t)(hid / 32) * 2 * (D / 16) * 1024));
-        if (with_qkv)     // the next block's attn.qkv: 3 D/32 blocks closing the image
-            mlp_fused_pack_rows(D, 3 * D, P(next_qkv + "attn.qkv.weight").data(), host_f2bf,
-                                (unsigned short*)(img + proj_bytes + ((size_t)(hid / 32) * 2 + (with_skip ? D / 16 : 0)) * (D / 16) * 1024));
+        if (m->fused_proj) mlp_fused_pack_proj(D, P(p + "attn.proj.weight").data(), host_f2bf, section(0));
+        mlp_fused_pack(D, hid, P(p + "mlp.fc1.weight").data(), P(p + "mlp.fc1.bias").data(), P(p + "mlp.fc2.weight").data(), true, host_f2bf,
+                       section(im.mlp), b1p.data());
+        if (with_skip) mlp_fused_pack_skip(D, P(next_skip + "skip_linear.weight").data(), host_f2bf, section(im.skip));      // the next block's skip_linear
+        if (with_qkv) mlp_fused_pack_rows(D, 3 * D, P(next_qkv + "attn.qkv.weight").data(), host_f2bf, section(im.qkv));     // the next block's attn.qkv
         a.f32(w.mlp_b1p, b1p);
     }
     if (m->fused_qa)

@@ -10,6 +10,8 @@ typedef unsigned short bf16_t;  // raw bf16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ bf16_t f2bf(float f) {
     __bf16 b = (__bf16)f;  // v_cvt_pk_bf16_f32: round-to-nearest-even, NaN stays NaN
@@ -150,8 +152,38 @@ struct MlpFusedArgs {
     int reduce_set = 0;    // launch_mlp_reduce: x = b2 + slabs instead of x += (the extra-token rows of a row-resident skip_linear; of a block tail with the
                            // projection in front: the first hidden group's slab carries x + proj(ao) + b)
 };
+// One 1 KB MFMA operand fragment of a row-major weight W (row stride ld): 64 lanes x 8 bf16 of the 32-row x 16-k piece at (row0, k0), lane = (row
+// lane & 31, half h = lane >> 5) -- what one ds_read_b128 / 16-byte load per lane puts in front of a v_mfma_f32_32x32x16_bf16.  Element j of half h holds
+// k0 + k(h, j), in one of two k orders: natural (the other operand is rows as loaded: 8 consecutive k per lane) or accumulator order (the other operand
+// is converted from 32x32 accumulator registers: quads 2 kq, 2 kq + 1 of a tile, columns 8 g + 4 h .. + 3 each).  Every weight image of the library
+// (mlp_fused_pack*, rowlin_pack, qkv_attention_pack) is a sequence of these.
+enum FragK { FRAG_K_NATURAL = 0, FRAG_K_ACC = 1 };
+__host__ __device__ constexpr int frag_k_natural(int h, int j) { return 8 * h + j; }
+__host__ __device__ constexpr int frag_k_acc(int h, int j) { return 8 * (j >> 2) + 4 * h + (j & 3); }
+inline void pack_fragment(const float* w, size_t ld, int row0, int k0, FragK order, unsigned short (*to_bf16)(float), unsigned short* dst) {
+    for (int lane = 0; lane < 64; ++lane)
+        for (int j = 0; j < 8; ++j) {
+            const int h = lane >> 5, k = order == FRAG_K_ACC ? frag_k_acc(h, j) : frag_k_natural(h, j);
+            dst[lane * 8 + j] = to_bf16(w[(size_t)(row0 + (lane & 31)) * ld + k0 + k]);
+        }
+}
+
+// Layout of the fused block tail's weight image: blocks of D / 16 fragments (one ring slot of the kernel), four sections in stream order
+//     [attn.proj: nproj blocks][fc1 / fc2 chunk pairs: 2 nchunks][next skip_linear: nskip][next attn.qkv: nqkv] + four run-off blocks
+// (the kernel's DMA runs up to three blocks past the last one -- branch-free pipeline; never used as data).  The projection's section starts the image.
+struct MlpImage {
+    size_t blk;               // bytes per block
+    size_t mlp, skip, qkv;    // first block of the section
+    size_t end;               // blocks of data
+    __host__ __device__ constexpr MlpImage(int D, int nproj, int nchunks, int nskip, int nqkv)
+        : blk((size_t)(D / 16) * 1024), mlp((size_t)nproj), skip(mlp + 2 * (size_t)nchunks), qkv(skip + (size_t)nskip), end(qkv + (size_t)nqkv) {}
+    static MlpImage of(int D, int hidden, bool with_proj, bool with_skip, bool with_qkv) {
+        return MlpImage(D, with_proj ? D / 32 : 0, hidden / 32, with_skip ? D / 16 : 0, with_qkv ? 3 * D / 32 : 0);
+    }
+    __host__ __device__ constexpr size_t at(size_t block) const { return block * blk; }     // byte offset of a block
+    constexpr size_t bytes() const { return at(end + 4); }
+};
 bool mlp_fused_supported(int D, int hidden);
-size_t mlp_fused_image_bytes(int D, int hidden, bool with_proj, bool with_skip, bool with_qkv);
 // nn.Linear weight [nrows, D] -> nrows / 32 blocks (one 32-row tile each, fragment f = k-step f, k index in accumulator order)
 void mlp_fused_pack_rows(int D, int nrows, const float* w, unsigned short (*to_bf16)(float), unsigned short* img);
 // qkv of the extra-token rows of a QKV launch (from a.ln_out, which the reduce / skip_rows launch has written for them)

@@ -30,13 +30,15 @@ int dd_dev_mlp(dd_ctx* c, int M, int D, int hidden, int extras, const float* x_h
     if (!mlp_fused_supported(D, hidden)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "fused MLP: D in {64,128,256,512}, hidden % 64 == 0");
     hipStream_t s = (hipStream_t)stream;
     const size_t Mp = (size_t)round_up(M, 256), row_bytes = Mp * D * 2;      // (every bf16 row buffer: Mp rows, zero padding)
-    std::vector<unsigned short> img(mlp_fused_image_bytes(D, hidden, proj, skp, qk) / 2, 0);
+    const MlpImage im = MlpImage::of(D, hidden, proj, skp, qk);
+    std::vector<unsigned short> img(im.bytes() / 2, 0);
+    auto section = [&](size_t block) { return img.data() + im.at(block) / 2; };
     std::vector<float> b1p(hidden), xr(Mp * D, 0.f);
     std::memcpy(xr.data(), xres_host, (size_t)M * D * 4);
-    if (proj) mlp_fused_pack_proj(D, wproj, host_f2bf, img.data());
-    mlp_fused_pack(D, hidden, w1, b1, w2, ln_in != nullptr, host_f2bf, img.data() + (proj ? (size_t)D * D : 0), b1p.data());
-    if (skp) mlp_fused_pack_skip(D, wskip, host_f2bf, img.data() + (proj ? (size_t)D * D : 0) + (size_t)(hidden / 32) * 2 * (D / 16) * 512);
-    if (qk) mlp_fused_pack_rows(D, 3 * D, wqkv, host_f2bf, img.data() + (proj ? (size_t)D * D : 0) + ((size_t)(hidden / 32) * 2 + (skp ? D / 16 : 0)) * (D / 16) * 512);
+    if (proj) mlp_fused_pack_proj(D, wproj, host_f2bf, section(0));
+    mlp_fused_pack(D, hidden, w1, b1, w2, ln_in != nullptr, host_f2bf, section(im.mlp), b1p.data());
+    if (skp) mlp_fused_pack_skip(D, wskip, host_f2bf, section(im.skip));
+    if (qk) mlp_fused_pack_rows(D, 3 * D, wqkv, host_f2bf, section(im.qkv));
     // extras > 0: the M rows are `M / (1 + extras)` images of one patch token each (drives the hidden-split path);
     // extras == 0: one image of M patch tokens (main tiles only)
     MlpFusedArgs a{};

@@ -16,6 +16,7 @@
 // Replaces the ATen addmm/mm + gelu + add sequence of reference models/uvit.py:86-92,
 // 155-168, 203-208.
 #include "dd_internal.h"
+#include "wave_prims.h"
 
 #include <type_traits>
 
@@ -23,22 +24,8 @@ namespace dd {
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __forceinline__ void glds16(const void* src, void* lds_dst) {
-    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)lds_dst, 16, 0, 0);
-}
-
 // exact-erf GELU (nn.GELU default), fp32 parity mode: libm erff.  (The bf16 mode uses the polynomial of gelu_erf4.)
 __device__ __forceinline__ float gelu_erf_f32(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
-
-// The same piece in the scalar-base form: uniform 64-bit base (SGPRs) + a 32-bit lane offset, M0 = the piece's LDS address.  Written as asm: the builtin turns
-// base + offset into a 64-bit VGPR address pair (checked in the ISA), and that form serialises with the SIMD's MFMAs (profiles/r05/dma_mfma_probe_roles.txt).
-__device__ __forceinline__ void glds16s(const char* sbase, unsigned voff, const void* lds_dst) {
-    const unsigned lds = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)lds_dst;
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(voff), "s"(sbase) : "memory", "m0");
-}
 
 // Stage ROWS x 128 B into a lane-linear LDS tile with the source-side chunk swizzle.
 // `g` points at (row 0, this k-tile's first byte); rows >= row_limit are clamped (N guard).
@@ -52,7 +39,7 @@ __device__ __forceinline__ void stage_tile(const char* g, long long row_stride, 
         int r = inst * 8 + (lane >> 3);
         const int c = (lane & 7) ^ ((r >> 1) & 7);
         r = r < row_limit ? r : row_limit - 1;
-        glds16(g + (long long)r * row_stride + c * 16, lds_tile + inst * 1024);
+        lds_dma16(g + (long long)r * row_stride + c * 16, lds_tile + inst * 1024);
     }
 }
 
@@ -104,11 +91,6 @@ template <>
 __device__ __forceinline__ void mma_chunk<float>(f32x16& acc, const f32x4& a, const f32x4& b) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b[e], acc, 0, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
 }
 
 // BM x BN output tile, WM x WN waves, each wave (BM/WM) x (BN/WN) as TM x TN MFMA 32x32 tiles.
@@ -214,9 +196,9 @@ gemm_kernel(const GemmArgs<T> a) {
         int rd = 0, wrb = STAGES - 1;  // ring slots: read slot of tile kt, write slot of tile kt+STAGES-1
         for (int kt = 0; kt < nk; ++kt) {
             const int ahead = nk - 1 - kt;  // tiles issued after kt that may stay in flight (capped)
-            if (STAGES >= 4 && ahead >= 2) wait_vmcnt<2 * G>();
-            else if (ahead >= 1) wait_vmcnt<G>();
-            else wait_vmcnt<0>();
+            if (STAGES >= 4 && ahead >= 2) waitcnt_vm<2 * G>();
+            else if (ahead >= 1) waitcnt_vm<G>();
+            else waitcnt_vm<0>();
             __builtin_amdgcn_s_barrier();
             if (kt + STAGES - 1 < nk) stage(kt + STAGES - 1, wrb);
             compute(rd);
@@ -321,9 +303,6 @@ struct Part256 {  // host-computed row partition
     int tail_base;  // = 256 * q
 };
 
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
-}
 // four 16-byte LDS reads at addr + {0, 32, 64, 96} bytes, one wait
 __device__ __forceinline__ void asm_ds_read_4x_b128_wait(unsigned addr, f32x4 (&r)[4]) {
     asm volatile(
@@ -382,7 +361,7 @@ gemm256_kernel(const GemmArgs<bf16_t> a, const Part256 part) {
         const unsigned voff_w = lr * (unsigned)sw + swz;
         char* at = smem + buf * k256Stage;
         if (kt == 0 && wave == 1 && EPI != EPI_STORE && !PARTIAL && a.bias)   // this tile's 256 bias values -> LDS
-            glds16(a.bias + tn * 256 + lane * 4, at - buf * k256Stage + k256BiasOff + parity * 1024);
+            lds_dma16(a.bias + tn * 256 + lane * 4, at - buf * k256Stage + k256BiasOff + parity * 1024);
         const char* Ab = kt < nk1 ? reinterpret_cast<const char*>(a.A) + (long long)kt * 128
                                   : reinterpret_cast<const char*>(a.A2) + (long long)(kt - nk1) * 128;
         const char* a_rows = Ab + ((long long)tm * 256 + wave * 32) * sa1;     // sa1 == sa2 (checked on host)
@@ -390,18 +369,18 @@ gemm256_kernel(const GemmArgs<bf16_t> a, const Part256 part) {
 #pragma unroll
         for (int inst = 0; inst < 4; ++inst) {
             const unsigned x = (inst & 1) ? 64u : 0u;
-            glds16s(a_rows + (long long)(inst * 8) * sa1, voff_a ^ x, at + (wave * 4 + inst) * 1024);
+            lds_dma16s(a_rows + (long long)(inst * 8) * sa1, voff_a ^ x, at + (wave * 4 + inst) * 1024);
         }
         if (wave == 0 && part.e > 0) {
             // 8 tail rows of this tile -> LDS rows 256..263 (row index 256 + lr: even-inst swizzle)
             long long row = (long long)part.tail_base + (long long)tm * part.e + ((int)lr < part.e ? (int)lr : part.e - 1);
             row = row < a.M ? row : a.M - 1;
-            glds16(Ab + row * sa1 + swz, at + 256 * 128);
+            lds_dma16(Ab + row * sa1 + swz, at + 256 * 128);
         }
 #pragma unroll
         for (int inst = 0; inst < 4; ++inst) {
             const unsigned x = (inst & 1) ? 64u : 0u;
-            glds16s(w_rows + (long long)(inst * 8) * sw, voff_w ^ x, at + A_BYTES + (wave * 4 + inst) * 1024);
+            lds_dma16s(w_rows + (long long)(inst * 8) * sw, voff_w ^ x, at + A_BYTES + (wave * 4 + inst) * 1024);
         }
     };
 
@@ -428,7 +407,7 @@ gemm256_kernel(const GemmArgs<bf16_t> a, const Part256 part) {
         const int tr = 256 + r32;  // tail rows; rows >= 264 read the W tile's bytes: finite or not, they
         x_off = tr * 128 + ((h ^ ((tr >> 1) & 7)) << 4);  // only reach dropped output columns
     }
-    const unsigned smem_lds = lds_addr(smem);
+    const unsigned smem_lds = lds_offset(smem);
     typedef const __attribute__((address_space(3))) f32x4* lds_f32x4_ptr;
     // Called once per k-tile: makes the 7 offsets opaque to the optimiser so that it cannot hoist the
     // 28 (offset ^ step) values out of the k-loop again (they would be spilled to scratch).
@@ -509,7 +488,7 @@ gemm256_kernel(const GemmArgs<bf16_t> a, const Part256 part) {
         const bool use_out = EPI != EPI_BIAS_SET && !PARTIAL && a.out != nullptr;
         const bool has_bias = HAS_BIAS && a.bias != nullptr;
         const int col0 = tn * 256 + wc * 64;
-        const unsigned bias_lds = lds_addr(smem + k256BiasOff + parity * 1024) + (wc * 64 + 4 * h) * 4;
+        const unsigned bias_lds = lds_offset(smem + k256BiasOff + parity * 1024) + (wc * 64 + 4 * h) * 4;
         // bias quads of column tile j: columns j*32 + 8g + 4h.., i.e. LDS bytes +32 per g
         auto load_bias = [&](int j, f32x4 (&b)[4]) {
             if (has_bias) asm_ds_read_4x_b128_wait(bias_lds + j * 128, b);
@@ -622,8 +601,8 @@ gemm256_kernel(const GemmArgs<bf16_t> a, const Part256 part) {
         for (int e = 0; e < 16; ++e) accx[e] = 0.f;
         for (int kt = cur.kb; kt < cur.ke; ++kt) {
             // the k-tile about to be read must have landed; only an epilogue's stores may be younger
-            if (kt == cur.kb && stores_in_flight) wait_vmcnt<N_EPI_STORES>();
-            else wait_vmcnt<0>();
+            if (kt == cur.kb && stores_in_flight) waitcnt_vm<N_EPI_STORES>();
+            else waitcnt_vm<0>();
             __builtin_amdgcn_s_barrier();
             compute(buf, [&]() {
                 if (kt + 1 < cur.ke) stage(cur.tm, cur.tn, kt + 1, buf ^ 1, i & 1);

@@ -28,6 +28,7 @@
 // fixed order (deterministic, no atomics).  Which path a row takes depends only on its token index, never on the batch
 // size, so an image computes bit-identically alone and inside any batch.
 #include "dd_internal.h"
+#include "wave_prims.h"
 
 #include <type_traits>
 #include <utility>
@@ -39,17 +40,10 @@ constexpr int kMaxHidden = 4096;   // bias table in LDS next to the 128 KB ring
 constexpr int kProjRowsLds = 4 * 32 * (1024 + 32);   // proj_rows_kernel: one padded 1 KB strip per LDS-DMA instruction
 constexpr int kGroups = 16;        // hidden-split ways of an extra-token tile (32 measured slower: more slab traffic, same fixed costs)
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __forceinline__ void glds16(const void* src, void* lds_dst) {
-    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)lds_dst, 16, 0, 0);
-}
-
-// Same, addressed as (uniform base) + (32-bit lane offset): the base is made opaque so that hipcc does not hoist one 64-bit VGPR pointer per
+// An LDS-DMA piece (lds_dma16) addressed as (uniform base) + (32-bit lane offset): the base is made opaque so that hipcc does not hoist one 64-bit VGPR pointer per
 // request out of the hot loop (16 pairs live across it otherwise -- the registers the loop does not have).  What it emits is still the VGPR-pair
-// form `global_load_lds_dwordx4 v[n:n+1], off offset:imm` (one address computation per four requests through the immediate offset); the true
-// scalar-base form `voff, s[base:base+1]` needs asm (rowlin.hip, gemm.hip, attention.hip use it) and measured neutral HERE (2 281 vs 2 246 cycles
+// form of the request, `v[n:n+1], off offset:imm` (one address computation per four requests through the immediate offset); the true
+// scalar-base form `voff, s[base:base+1]` needs asm (lds_dma16s) and measured neutral HERE (2 281 vs 2 246 cycles
 // per chunk, 156.1 vs 156.3 us per launch, profiles/r05/ab_round5.txt): this loop hides its request issue already.
 __device__ __forceinline__ const char* uniform_ptr(const char* p) {
     asm volatile("" : "+s"(p));
@@ -67,13 +61,6 @@ __device__ __forceinline__ void glds16u_j(const char* ublock, unsigned voff, cha
     __builtin_amdgcn_global_load_lds((gptr_t)(ublock + HI + voff), (lptr_t)(lds_block + HI), 16, IMM, 0);
 }
 
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {   // v_cvt_pk_bf16_f32
-    typedef __bf16 bf16v2 __attribute__((ext_vector_type(2)));
-    typedef float f32v2 __attribute__((ext_vector_type(2)));
-    const f32v2 q = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(q, bf16v2));
-}
-
 // The hot loop is written as a sequence of small asm volatile statements -- one MFMA, one LDS fragment read, or one half
 // of a GELU evaluation each.  Volatile asm statements keep their program order, so the interleave written in the source
 // IS the instruction stream (hipcc sinks or hoists plain C++ VALU code around asm MFMAs as it likes, and drains
@@ -86,14 +73,6 @@ __device__ __forceinline__ unsigned pack2(float lo, float hi) {   // v_cvt_pk_bf
 // Accumulators: Y tiles "+a" (AGPR half of the register file: 256 registers at D = 512, resident for the whole kernel),
 // hidden-chunk accumulators "+v" (the GELU reads them with VALU instructions).
 __device__ __forceinline__ void mfma_drain() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
-template <int OFF>
-__device__ __forceinline__ void lds_frag(bf16x8& dst, unsigned addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(OFF));
-}
-template <int OFF>
-__device__ __forceinline__ void lds_quad(f32x4& dst, unsigned addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(OFF));
-}
 
 // exact-erf GELU for a bf16-rounded result: gelu(v) = v * (0.5 + s * P'(s^2)), s = med3(v, +-3.8), P' = P / 2 with P the degree-6
 // minimax polynomial of erf(s/sqrt2)/s (same coefficients as the GEMM epilogue in gemm.hip: |erf error| <= 1.3e-4, GELU
@@ -109,9 +88,8 @@ struct GeluPair { float sa, s2a, pa, ha, sb, s2b, pb, hb; };
 //     ; [piece K of the GELU pair (va, vb)]
 // KIND 0: S^T += W1 fragment . X^T, accumulator in VGPRs;  KIND 1: Y^T tile += W2 fragment . P^T, accumulator in AGPRs.
 // Every operand is declared for every variant (unused ones cost nothing); the GELU registers are read-write throughout.
-#define DD_S_MFMA_W "s_waitcnt lgkmcnt(%[lg])\n\tv_mfma_f32_32x32x16_bf16 %[acc], %[wa], %[xb], %[acc]"
-#define DD_S_MFMA_N "v_mfma_f32_32x32x16_bf16 %[acc], %[wa], %[xb], %[acc]"     // LG < 0: the gap in front already waited for this fragment
-#define DD_S_READ "\n\tds_read_b128 %[wa], %[la] offset:%[lo]"
+// (DD_S_MFMA_W / DD_S_MFMA_N / DD_S_READ: the strings of mfma_gap, wave_prims.h -- the gap without a GELU piece, with only the operands it uses: the
+// SKIP phases' 2 NT F statements and the QKV phases'; the statement here declares the GELU constants, an SGPR float among them, whether it uses them or not)
 #define DD_S_G0 "\n\tv_med3_f32 %[sa], %[va], %[kn], %[kh]\n\tv_med3_f32 %[sb], %[vb], %[kn], %[kh]\n\tv_mul_f32 %[s2a], %[sa], %[sa]"
 #define DD_S_G1 "\n\tv_mul_f32 %[s2b], %[sb], %[sb]\n\tv_fmamk_f32 %[pa], %[s2a], 0x331d7172, %[kc]\n\tv_fmamk_f32 %[pb], %[s2b], 0x331d7172, %[kc]"
 #define DD_S_G2 "\n\tv_fmaak_f32 %[pa], %[pa], %[s2a], 0x387e87ac\n\tv_fmaak_f32 %[pb], %[pb], %[s2b], 0x387e87ac\n\tv_fmaak_f32 %[pa], %[pa], %[s2a], 0xba743309"
@@ -146,31 +124,6 @@ __device__ __forceinline__ void gap_stmt(f32x16& acc, bf16x8& wa, const bf16x8& 
         if constexpr (K < 0) { DD_GAP_SEL("", "+a") }
         DD_GAP_K(0, DD_S_G0, "+a") DD_GAP_K(1, DD_S_G1, "+a") DD_GAP_K(2, DD_S_G2, "+a") DD_GAP_K(3, DD_S_G3, "+a")
         DD_GAP_K(4, DD_S_G4, "+a") DD_GAP_K(5, DD_S_G5, "+a") DD_GAP_K(6, DD_S_G6, "+a") DD_GAP_K(7, DD_S_G7, "+a")
-    }
-}
-
-// A gap without a GELU piece, accumulator in AGPRs, with only the operands it uses (the SKIP phases: 2 NT F statements; the
-// generic statement above declares the GELU constants as operands -- an SGPR float among them -- whether it uses them or not)
-template <int LG, bool READ, int LO>
-__device__ __forceinline__ void gap_plain(f32x16& acc, bf16x8& wa, const bf16x8& xb, unsigned la) {
-    if constexpr (LG >= 0) {
-        if constexpr (READ) asm volatile(DD_S_MFMA_W DD_S_READ : [acc] "+a"(acc), [wa] "+v"(wa) : [xb] "v"(xb), [la] "v"(la), [lg] "i"(LG), [lo] "i"(LO));
-        else asm volatile(DD_S_MFMA_W : [acc] "+a"(acc), [wa] "+v"(wa) : [xb] "v"(xb), [lg] "i"(LG));
-    } else {
-        if constexpr (READ) asm volatile(DD_S_MFMA_N DD_S_READ : [acc] "+a"(acc), [wa] "+v"(wa) : [xb] "v"(xb), [la] "v"(la), [lo] "i"(LO));
-        else asm volatile(DD_S_MFMA_N : [acc] "+a"(acc), [wa] "+v"(wa) : [xb] "v"(xb));
-    }
-}
-
-// the same with the accumulator in VGPRs (the QKV phases: the tile is converted and stored by VALU code)
-template <int LG, bool READ, int LO>
-__device__ __forceinline__ void gap_plain_v(f32x16& acc, bf16x8& wa, const bf16x8& xb, unsigned la) {
-    if constexpr (LG >= 0) {
-        if constexpr (READ) asm volatile(DD_S_MFMA_W DD_S_READ : [acc] "+v"(acc), [wa] "+v"(wa) : [xb] "v"(xb), [la] "v"(la), [lg] "i"(LG), [lo] "i"(LO));
-        else asm volatile(DD_S_MFMA_W : [acc] "+v"(acc), [wa] "+v"(wa) : [xb] "v"(xb), [lg] "i"(LG));
-    } else {
-        if constexpr (READ) asm volatile(DD_S_MFMA_N DD_S_READ : [acc] "+v"(acc), [wa] "+v"(wa) : [xb] "v"(xb), [la] "v"(la), [lo] "i"(LO));
-        else asm volatile(DD_S_MFMA_N : [acc] "+v"(acc), [wa] "+v"(wa) : [xb] "v"(xb));
     }
 }
 
@@ -211,9 +164,6 @@ __device__ __forceinline__ void pin_tiles(f32x16 (&y)[NT]) {
         asm volatile("" : "+a"(y[0]), "+a"(y[1]), "+a"(y[2]), "+a"(y[3]), "+a"(y[4]), "+a"(y[5]), "+a"(y[6]), "+a"(y[7]), "+a"(y[8]),
                      "+a"(y[9]), "+a"(y[10]), "+a"(y[11]), "+a"(y[12]), "+a"(y[13]), "+a"(y[14]), "+a"(y[15]));
 }
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory"); }
 
 // LayerNorm statistics of a row that is spread over the two lane halves (lane, lane ^ 32), D / 2 columns each, from ONE
 // pass over the registers -- without the cancellation of E[x^2] - mean^2: every lane accumulates s = sum(x - c) and
@@ -279,6 +229,8 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
     float* vecs = b1s + (a.nchunks + 1) * 32;                        // 7 x [D]: ln_in gamma, beta | ln_out gamma, beta | b2 | bproj | bskip
     // weight stream: [nproj blocks of Wproj][W1(0) W2(0) W1(1) W2(1) ...]; stream position p lives in ring slot p & 3
     // (nproj % 4 == 0), so the MLP part keeps "block b in slot b & 3" with or without the projection in front
+    // (MlpImage, dd_internal.h, is the layout; the section starts are spelled out here, relative to wmlp, because the SKIP / QKV instantiations'
+    // register allocation follows the form of these expressions: see the identical-ISA rule in wave_prims.h)
     const char* const wproj = a.wimg;
     const char* const wmlp = a.wimg + (size_t)a.nproj * C::BLK;
 
@@ -368,7 +320,6 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
 
     bf16x8 xf[C::KS];
     f32x16 Y[C::NT];
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     if constexpr (!LNIN) {
         const bf16_t* xr = a.X + row_pro * a.ldx + 8 * h;
 #pragma unroll
@@ -432,7 +383,7 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
             // below).  In the middle of phase t: block t+1 landed (in-order groups, one younger one may be outstanding) |
             // barrier | request block t+3 into the slot block t-1 has left.  The queue first touches block t+1 after that
             // point (PDp <= F/2).  The last three requests are the MLP's first blocks.
-            const unsigned lds_lo_p = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)smem + lane * 16;
+            const unsigned lds_lo_p = lds_offset(smem) + lane * 16;
             const unsigned lds_hi_p = lds_lo_p + 65536u;
             constexpr int PDp = C::F / 2 < 8 ? C::F / 2 : 8;
             constexpr int NGp = C::NT * C::F;
@@ -441,13 +392,13 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
             const GeluConst gk0{0.f, 0.f};
             unsigned none = 0;
             [&]<int... J>(std::integer_sequence<int, J...>) {
-                (lds_frag<J * 1024>(wp[J], lds_lo_p), ...);
+                (ds_read16<J * 1024>(wp[J], lds_lo_p), ...);
             }(std::make_integer_sequence<int, PDp>{});
             [&]<int... GI>(std::integer_sequence<int, GI...>) {
                 ([&] {
                     constexpr int g = GI, t = g / C::F, f = g % C::F;
                     if constexpr (f == C::F / 2) {
-                        wait_vmcnt<C::FPW>();
+                        waitcnt_vm<C::FPW>();
                         __builtin_amdgcn_s_barrier();
                         // stream position t + 3: Wproj block, or (t + 3 >= NT) block 2 c0 + t + 3 - NT of the MLP part (c0 = 0 for main tiles;
                         // a hidden-split workgroup continues with ITS hidden range: c0 is even, so the ring slot parity holds)
@@ -504,8 +455,8 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
                     const f32x4 q = {yt[4 * g], yt[4 * g + 1], yt[4 * g + 2], yt[4 * g + 3]};
                     const f32x4 gv = *reinterpret_cast<const f32x4*>(lg_in + col), bv = *reinterpret_cast<const f32x4*>(lb_in + col);
                     const f32x4 v = (q * rstd + shift) * gv + bv;
-                    u[2 * gq] = pack2(v[0], v[1]);
-                    u[2 * gq + 1] = pack2(v[2], v[3]);
+                    u[2 * gq] = cvt_pk_bf16(v[0], v[1]);
+                    u[2 * gq + 1] = cvt_pk_bf16(v[2], v[3]);
                 }
                 xf[ks] = __builtin_bit_cast(bf16x8, u32x4{u[0], u[1], u[2], u[3]});
             }
@@ -527,9 +478,9 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
     }
 
     // LDS addressing: one per-lane base (+ a second one 64 KB up: ds offsets are 16 bits), compile-time offsets
-    const unsigned lds_lo = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)smem + lane * 16;
+    const unsigned lds_lo = lds_offset(smem) + lane * 16;
     const unsigned lds_hi = lds_lo + 65536u;
-    const unsigned bias_lo = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)smem + C::RING + h * 64;
+    const unsigned bias_lo = lds_offset(smem) + C::RING + h * 64;
     constexpr int PD = C::F < 8 ? C::F : 8;    // fragment reads in flight ahead of their MFMA: covers ~250 cycles of LDS latency
     const GeluConst gk{3.8f, 0.5f * -4.544908101e-06f};     // (the polynomial's coefficients are halved: 0.5 * erf(s / sqrt2) / s)
 
@@ -537,14 +488,14 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
     auto frag_off = [](int slot, int f) constexpr { return slot * C::BLK + f * 1024; };
     auto frag = [&](auto off_tag, bf16x8& q) {
         constexpr int OFF = decltype(off_tag)::value;
-        if constexpr (OFF < 65536) lds_frag<OFF>(q, lds_lo);
-        else lds_frag<OFF - 65536>(q, lds_hi);
+        if constexpr (OFF < 65536) ds_read16<OFF>(q, lds_lo);
+        else ds_read16<OFF - 65536>(q, lds_hi);
     };
     // S accumulator of chunk c initialised with its fc1 bias (register e of lane half h = hidden 32c + (e&3) + 8(e>>2) + 4h)
     auto bias_init = [&](int c, f32x16& sacc) {
         f32x4 q0, q1, q2, q3;
         const unsigned ba = bias_lo + c * 128;
-        lds_quad<0>(q0, ba); lds_quad<16>(q1, ba); lds_quad<32>(q2, ba); lds_quad<48>(q3, ba);
+        ds_read16<0>(q0, ba); ds_read16<16>(q1, ba); ds_read16<32>(q2, ba); ds_read16<48>(q3, ba);
         sacc = f32x16{q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3],
                       q2[0], q2[1], q2[2], q2[3], q3[0], q3[1], q3[2], q3[3]};
     };
@@ -601,7 +552,7 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
             ([&] {
                 constexpr int g = GI;
                 if constexpr (g == 0 || g == C::F) {
-                    wait_vmcnt<C::FPW>();
+                    waitcnt_vm<C::FPW>();
                     __builtin_amdgcn_s_barrier();
                 }
                 // fragment read PD gaps ahead: this iteration's slots, or the next iteration's first block
@@ -639,7 +590,6 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
                 }
             }(), ...);
         }(std::make_integer_sequence<int, NG>{});
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         p_out[0] = __builtin_bit_cast(bf16x8, u32x4{pw[0], pw[1], pw[2], pw[3]});
         p_out[1] = __builtin_bit_cast(bf16x8, u32x4{pw[4], pw[5], pw[6], pw[7]});
     };
@@ -671,7 +621,7 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
             gap_stmt<1, LG, RD, LOA, -1>(Y[f >> 1], wq[f % PD], pA[f & 1], LO < 65536 ? lds_lo : lds_hi, 0.f, 0.f, gk, gr, pw_none);
         }(), ...);
     }(std::make_integer_sequence<int, C::F>{});
-    wait_vmcnt<0>();     // the run-ahead DMA of the padded blocks must not outlive the workgroup's LDS allocation
+    waitcnt_vm<0>();     // the run-ahead DMA of the padded blocks must not outlive the workgroup's LDS allocation
     // hipcc does not know that the asm statements are MFMAs: left alone it schedules its own reads of the accumulators
     // (v_accvgpr_read, AGPR spills) directly behind the last MFMA, inside its 12-wait-state shadow.  The drain, then one
     // empty asm per tile that "rewrites" it: every compiler read of Y is ordered behind the drain.
@@ -682,7 +632,7 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
     if constexpr (SKIP) {
         // ---- (a) y = Y + b2 as the B fragments of the y half (accumulator k order: the image's y blocks are packed to match),
         //      (b) the accumulators restart from bskip
-        __builtin_amdgcn_s_barrier();     // every wave's pieces of the first three skip blocks have landed (wait_vmcnt<0> above)
+        __builtin_amdgcn_s_barrier();     // every wave's pieces of the first three skip blocks have landed (waitcnt_vm<0> above)
         {
             const int hs = half_of();
             const float* lb2s = vecs + 4 * D + 4 * hs;
@@ -706,8 +656,8 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
                         f32x4 q = {yt[4 * g], yt[4 * g + 1], yt[4 * g + 2], yt[4 * g + 3]};
                         q += *reinterpret_cast<const f32x4*>(lb2s + col);
                         if constexpr (TAP) { if (tap_ok) *reinterpret_cast<f32x4*>(tap + col) = q; }
-                        u[2 * gq] = pack2(q[0], q[1]);
-                        u[2 * gq + 1] = pack2(q[2], q[3]);
+                        u[2 * gq] = cvt_pk_bf16(q[0], q[1]);
+                        u[2 * gq + 1] = cvt_pk_bf16(q[2], q[3]);
                     }
                     xf[ks] = __builtin_bit_cast(bf16x8, u32x4{u[0], u[1], u[2], u[3]});
                 }
@@ -729,13 +679,13 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
         // In the middle of phase p: block p+1 landed | barrier | request block p+3 (as the projection phases do).  The 16-byte
         // loads of the second half sit right behind the requests of phase NT: the two waits that follow count them in.
         const char* const wskip = wmlp + (size_t)(2 * a.nchunks) * C::BLK;
-        const unsigned lds_lo_s = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)smem + lane * 16;
+        const unsigned lds_lo_s = lds_offset(smem) + lane * 16;
         const unsigned lds_hi_s = lds_lo_s + 65536u;
         constexpr int PDs = C::F / 2 < 8 ? C::F / 2 : 8;
         constexpr int NPs = 2 * C::NT, NGs = NPs * C::F, H2 = C::F / 2;
         bf16x8 ws[PDs];
         [&]<int... J>(std::integer_sequence<int, J...>) {
-            (lds_frag<J * 1024>(ws[J], lds_lo_s), ...);
+            (ds_read16<J * 1024>(ws[J], lds_lo_s), ...);
         }(std::make_integer_sequence<int, PDs>{});
         [&]<int... GI>(std::integer_sequence<int, GI...>) {
             ([&] {
@@ -743,7 +693,7 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
                 if constexpr (f == C::F / 2) {
                     // younger than block p+1's requests at this point: block p+2's, plus (p = NT+1, NT+2) the H2 operand loads
                     constexpr int extra = (p == C::NT + 1 || p == C::NT + 2) ? H2 : 0;
-                    wait_vmcnt<C::FPW + extra>();
+                    waitcnt_vm<C::FPW + extra>();
                     __builtin_amdgcn_s_barrier();
                     const char* src = uniform_ptr(wskip + (size_t)(p + 3) * C::BLK);
                     char* dst = smem + ((p + 3) & 3) * C::BLK + (wave * C::FPW) * 1024;
@@ -765,14 +715,14 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
                 constexpr int LOA = LO < 65536 ? LO : LO - 65536;
                 constexpr int tile = p < C::NT ? p : 2 * ((p - C::NT) % (C::NT / 2)) + (f >= H2 ? 1 : 0);
                 if constexpr (p < C::NT)
-                    gap_plain<LG, RD, LOA>(Y[tile], ws[g % PDs], xf[f], LO < 65536 ? lds_lo_s : lds_hi_s);
+                    mfma_gap<true, LG, RD, LOA>(Y[tile], ws[g % PDs], xf[f], LO < 65536 ? lds_lo_s : lds_hi_s);
                 else if constexpr (p < C::NT + C::NT / 2)
-                    gap_plain<LG, RD, LOA>(Y[tile], ws[g % PDs], sk[f % H2], LO < 65536 ? lds_lo_s : lds_hi_s);
+                    mfma_gap<true, LG, RD, LOA>(Y[tile], ws[g % PDs], sk[f % H2], LO < 65536 ? lds_lo_s : lds_hi_s);
                 else
-                    gap_plain<LG, RD, LOA>(Y[tile], ws[g % PDs], xf[f % H2], LO < 65536 ? lds_lo_s : lds_hi_s);
+                    mfma_gap<true, LG, RD, LOA>(Y[tile], ws[g % PDs], xf[f % H2], LO < 65536 ? lds_lo_s : lds_hi_s);
             }(), ...);
         }(std::make_integer_sequence<int, NGs>{});
-        wait_vmcnt<0>();     // the run-ahead requests of the padded blocks
+        waitcnt_vm<0>();     // the run-ahead requests of the padded blocks
         mfma_drain();
 #pragma unroll
         for (int t = 0; t < C::NT; ++t) asm volatile("" : "+a"(Y[t]));
@@ -826,7 +776,7 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
                 if constexpr (!SKIP) q += *reinterpret_cast<const f32x4*>(lb2 + 32 * t + 8 * g);
                 if constexpr (!LNIN) q = xl[t & 1][g] + q;
                 *reinterpret_cast<f32x4*>(xrow + 32 * t + 8 * g) = q;
-                v[g] = uint2{pack2(q[0], q[1]), pack2(q[2], q[3])};
+                v[g] = uint2{cvt_pk_bf16(q[0], q[1]), cvt_pk_bf16(q[2], q[3])};
                 if (t == 0 && g == 0) cshift = q[0];
                 const f32x4 dq = q - cshift;
                 s4 += dq;
@@ -875,7 +825,7 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
                     if constexpr (!SKIP) q += *reinterpret_cast<const f32x4*>(lb2r + 32 * t + 8 * g);
                     const f32x4 gv = *reinterpret_cast<const f32x4*>(lg_out + 32 * t + 8 * g), bv = *reinterpret_cast<const f32x4*>(lb_out + 32 * t + 8 * g);
                     const f32x4 w = (q * rstd + shift) * gv + bv;
-                    v[g] = uint2{pack2(w[0], w[1]), pack2(w[2], w[3])};
+                    v[g] = uint2{cvt_pk_bf16(w[0], w[1]), cvt_pk_bf16(w[2], w[3])};
                 }
                 if constexpr (QKV) {
                     // k-step 2t + kq of the qkv product = quads 2kq, 2kq + 1 of tile t (as norm2 feeds fc1 in the prologue)
@@ -901,9 +851,9 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
             // ---- the qkv phases.  The row accumulators are dead from here on (x has been stored above: its stores drain under the
             // first phases -- vmcnt is in order, so the first request that must be confirmed behind them waits for them).  Stream
             // position of qkv block t: behind the MLP (and skip) blocks, slot t & 3; blocks 0..2 were requested by the run-ahead of the
-            // loop before and have landed (wait_vmcnt<0> + the barrier here).
+            // loop before and have landed (waitcnt_vm<0> + the barrier here).
             const char* const wqkv = wmlp + ((size_t)2 * a.nchunks + (SKIP ? 2 * C::NT : 0)) * C::BLK;
-            const unsigned lds_lo_q = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)smem + lane * 16;
+            const unsigned lds_lo_q = lds_offset(smem) + lane * 16;
             const unsigned lds_hi_q = lds_lo_q + 65536u;
             constexpr int PDq = C::F / 2 < 8 ? C::F / 2 : 8;
             constexpr int NQ = 3 * C::NT, NGq = NQ * C::F;
@@ -919,7 +869,7 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
             __builtin_amdgcn_s_barrier();
             bf16x8 wq2[PDq];
             [&]<int... J>(std::integer_sequence<int, J...>) {
-                (lds_frag<J * 1024>(wq2[J], lds_lo_q), ...);
+                (ds_read16<J * 1024>(wq2[J], lds_lo_q), ...);
             }(std::make_integer_sequence<int, PDq>{});
             f32x16 qa, qb;
 #pragma unroll
@@ -929,7 +879,7 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
             auto flush_tile = [&](int tt, f32x16& acc) {
                 uint2 v[4];
 #pragma unroll
-                for (int g = 0; g < 4; ++g) v[g] = uint2{pack2(acc[4 * g], acc[4 * g + 1]), pack2(acc[4 * g + 2], acc[4 * g + 3])};
+                for (int g = 0; g < 4; ++g) v[g] = uint2{cvt_pk_bf16(acc[4 * g], acc[4 * g + 1]), cvt_pk_bf16(acc[4 * g + 2], acc[4 * g + 3])};
                 char* dst = qrow + (long long)(tt >> 1) * ustride + (tt & 1) * tstride;
 #pragma unroll
                 for (int gp = 0; gp < 4; gp += 2) {
@@ -948,7 +898,7 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
                         // younger than block t+1's requests (issued in the middle of phase t-2): the two stores of phase t-2 (tile t-3, if
                         // any), block t+2's requests, the two stores of phase t-1 (tile t-2, if any)
                         constexpr int younger = C::FPW + (t - 2 >= 1 ? 2 : 0) + (t - 1 >= 1 ? 2 : 0);
-                        if constexpr (t >= 2) wait_vmcnt<younger>();
+                        if constexpr (t >= 2) waitcnt_vm<younger>();
                         __builtin_amdgcn_s_barrier();
                         const char* src = uniform_ptr(wqkv + (size_t)(t + 3) * C::BLK);
                         char* dst = smem + ((t + 3) & 3) * C::BLK + (wave * C::FPW) * 1024;
@@ -969,15 +919,15 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
                     constexpr bool RD = gn < NGq;
                     constexpr int LO = RD ? ((gn / C::F) & 3) * C::BLK + (gn % C::F) * 1024 : 0;
                     constexpr int LOA = LO < 65536 ? LO : LO - 65536;
-                    if constexpr (t & 1) gap_plain<LG, RD, LOA>(qb, wq2[g % PDq], xf[f], LO < 65536 ? lds_lo_q : lds_hi_q);
-                    else gap_plain<LG, RD, LOA>(qa, wq2[g % PDq], xf[f], LO < 65536 ? lds_lo_q : lds_hi_q);
+                    if constexpr (t & 1) mfma_gap<true, LG, RD, LOA>(qb, wq2[g % PDq], xf[f], LO < 65536 ? lds_lo_q : lds_hi_q);
+                    else mfma_gap<true, LG, RD, LOA>(qa, wq2[g % PDq], xf[f], LO < 65536 ? lds_lo_q : lds_hi_q);
                 }(), ...);
             }(std::make_integer_sequence<int, NGq>{});
             mfma_drain();
             if constexpr ((NQ - 1) & 1) { asm volatile("" : "+a"(qb)); flush_tile(NQ - 1, qb); }
             else { asm volatile("" : "+a"(qa)); flush_tile(NQ - 1, qa); }
             asm volatile("" : "+a"(qa), "+a"(qb));
-            wait_vmcnt<0>();     // the run-ahead requests of the padded blocks must not outlive the workgroup's LDS allocation
+            waitcnt_vm<0>();     // the run-ahead requests of the padded blocks must not outlive the workgroup's LDS allocation
         }
     }
 }
@@ -1055,7 +1005,7 @@ __global__ void __launch_bounds__(256) mlp_reduce_kernel(const MlpFusedArgs a) {
     }
     if (a.ln_out) {
 #pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o);
+        for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o);      // (not wave_reduce_add: the call form changes this kernel's instructions)
         const float mean = sum / (float)D;
         float q2 = 0.f;
 #pragma unroll
@@ -1089,10 +1039,7 @@ __global__ void __launch_bounds__(WPG * 64) skip_rows_ln_kernel(const MlpFusedAr
     char* sbuf = srl + 32 * PITCH;          // [32][PITCH]
     float* red = reinterpret_cast<float*>(srl + 64 * PITCH);   // [2][NW][32]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, r32 = lane & 31;
-    auto row_of = [&](int i) -> long long {
-        const int q = i < a.n_extra ? i : a.n_extra - 1, b = q / a.tok_e;
-        return (long long)b * a.tok_l + (q - b * a.tok_e);
-    };
+    auto row_of = [&](int idx) { return extra_token_row(idx, a.n_extra, a.tok_e, a.tok_l); };
     // ---- park the operand rows: 32 rows x D bf16 each, 16-byte chunks
     constexpr int CPR = D / 8, ITEMS = 2 * 32 * CPR, PER_ALL = (ITEMS + NTHR - 1) / NTHR, PER = PER_ALL < 8 ? PER_ALL : 8, ROUNDS = (PER_ALL + PER - 1) / PER;
     f32x4 stg[PER];
@@ -1118,15 +1065,16 @@ __global__ void __launch_bounds__(WPG * 64) skip_rows_ln_kernel(const MlpFusedAr
         for (int i = 0; i < 32 / WPG; ++i) {
             const int r = wave + i * WPG;
             const long long row = row_of(blockIdx.x * 32 + r);
-            glds16(a.out + row * a.ldo + lane * 8, ybuf + r * PITCH);
-            glds16(a.skip + row * D + lane * 8, sbuf + r * PITCH);
+            lds_dma16(a.out + row * a.ldo + lane * 8, ybuf + r * PITCH);
+            lds_dma16(a.skip + row * D + lane * 8, sbuf + r * PITCH);
         }
     } else {
         stage_load(0);
     }
     // this wave's column tile: weights of the y half (block t), first fragments requested before the operands are parked
     const int t = blockIdx.y * WPG + wave;
-    const char* const wskip = a.wimg + ((size_t)a.nproj + 2 * (size_t)a.nchunks) * C::BLK;
+    const MlpImage im(D, a.nproj, a.nchunks, a.nskip, a.nqkv);
+    const char* const wskip = a.wimg + im.at(im.skip);
     const bf16x8* wy = reinterpret_cast<const bf16x8*>(wskip + (size_t)t * C::BLK) + lane;
     const bf16x8* ws0 = reinterpret_cast<const bf16x8*>(wskip + (size_t)(C::NT + t / 2) * C::BLK) + (t & 1) * H2 * 64 + lane;
     const bf16x8* ws1 = reinterpret_cast<const bf16x8*>(wskip + (size_t)(C::NT + C::NT / 2 + t / 2) * C::BLK) + (t & 1) * H2 * 64 + lane;
@@ -1139,7 +1087,7 @@ __global__ void __launch_bounds__(WPG * 64) skip_rows_ln_kernel(const MlpFusedAr
 #pragma unroll
     for (int f = 0; f < G; ++f) wf[f] = wfrag(f);
     if constexpr (DMA_PARK) {
-        wait_vmcnt<0>();
+        waitcnt_vm<0>();
     } else {
         stage_store(0);
 #pragma unroll
@@ -1153,9 +1101,7 @@ __global__ void __launch_bounds__(WPG * 64) skip_rows_ln_kernel(const MlpFusedAr
 #pragma unroll
         for (int e = 0; e < 4; ++e) { acc0[4 * g + e] = bq[e]; acc1[4 * g + e] = 0.f; }
     }
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const char* yrow = ybuf + r32 * PITCH + 8 * h;       // accumulator k order: columns 16 ks + 4 h .. +3 and 16 ks + 8 + 4 h .. +3
+    const char* yrow = ybuf + r32 * PITCH + 8 * h;       // accumulator k order (frag_k_acc, dd_internal.h): two 8-byte pieces per k-step
     const char* srow = sbuf + r32 * PITCH + 16 * h;      // natural k order: columns 16 ks + 8 h .. +7
 #pragma unroll
     for (int kk = 0; kk < 2 * C::F; ++kk) {
@@ -1211,7 +1157,7 @@ __global__ void __launch_bounds__(WPG * 64) skip_rows_ln_kernel(const MlpFusedAr
         *reinterpret_cast<f32x4*>(a.xres + row * D + col) = v;
         const f32x4 gv = *reinterpret_cast<const f32x4*>(a.ln_out_g + col), bv = *reinterpret_cast<const f32x4*>(a.ln_out_b + col);
         const f32x4 w = (v - mean) * rstd * gv + bv;
-        *reinterpret_cast<uint2*>(a.ln_out + row * D + col) = uint2{pack2(w[0], w[1]), pack2(w[2], w[3])};
+        *reinterpret_cast<uint2*>(a.ln_out + row * D + col) = uint2{cvt_pk_bf16(w[0], w[1]), cvt_pk_bf16(w[2], w[3])};
     }
 }
 
@@ -1227,25 +1173,21 @@ __global__ void __launch_bounds__(256) qkv_rows_kernel(const MlpFusedArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
     const int t = blockIdx.x, idx0 = blockIdx.y * 128 + wave * 32;
     char* strip = strip_lds + wave * (NI * IPITCH);
-    auto row_of = [&](int idx) -> long long {
-        const int q = idx < a.n_extra ? idx : a.n_extra - 1, b = q / a.tok_e;
-        return (long long)b * a.tok_l + (q - b * a.tok_e);
-    };
+    auto row_of = [&](int idx) { return extra_token_row(idx, a.n_extra, a.tok_e, a.tok_l); };
 #pragma unroll
     for (int i = 0; i < NI; ++i)
-        glds16(a.ln_out + row_of(idx0 + i * RPI + lane / LPR) * D + (lane % LPR) * 8, strip + i * IPITCH);
+        lds_dma16(a.ln_out + row_of(idx0 + i * RPI + lane / LPR) * D + (lane % LPR) * 8, strip + i * IPITCH);
     __builtin_amdgcn_sched_barrier(0);
     const int idx = idx0 + (lane & 31);
     const bool ok = idx < a.n_extra;
     const long long row = row_of(idx);
-    const size_t pos = (size_t)a.nproj + 2 * (size_t)a.nchunks + (size_t)a.nskip;
-    const bf16x8* wb = reinterpret_cast<const bf16x8*>(a.wimg + (pos + t) * C::BLK) + lane;
+    const MlpImage im(D, a.nproj, a.nchunks, a.nskip, a.nqkv);
+    const bf16x8* wb = reinterpret_cast<const bf16x8*>(a.wimg + im.at(im.qkv + t)) + lane;
     bf16x8 wf[C::F];
 #pragma unroll
     for (int ks = 0; ks < C::F; ++ks) wf[ks] = wb[ks * 64];
-    wait_vmcnt<0>();
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    waitcnt_vm<0>();
+    // (accumulator k order, frag_k_acc in dd_internal.h: the row fragment of a k-step is two 8-byte pieces 16 bytes apart)
     const char* my = strip + ((lane & 31) / RPI) * IPITCH + ((lane & 31) % RPI) * (D * 2) + 8 * h;
     f32x16 acc, acc1;
 #pragma unroll
@@ -1262,7 +1204,7 @@ __global__ void __launch_bounds__(256) qkv_rows_kernel(const MlpFusedArgs a) {
     bf16_t* dst = a.qkv_out + hm_offset(a.hm, (int)row, 32 * t) + 4 * h;
 #pragma unroll
     for (int g = 0; g < 4; ++g)
-        *reinterpret_cast<uint2*>(dst + 8 * g) = uint2{pack2(acc[4 * g], acc[4 * g + 1]), pack2(acc[4 * g + 2], acc[4 * g + 3])};
+        *reinterpret_cast<uint2*>(dst + 8 * g) = uint2{cvt_pk_bf16(acc[4 * g], acc[4 * g + 1]), cvt_pk_bf16(acc[4 * g + 2], acc[4 * g + 3])};
 }
 
 template <int D>
@@ -1310,20 +1252,10 @@ bool mlp_fused_supported(int D, int hidden) {
     return (D == 64 || D == 128 || D == 256 || D == 512) && hidden % 64 == 0 && hidden >= 64 && hidden <= kMaxHidden;
 }
 
-// + four blocks: the kernel's DMA runs up to three blocks past the last chunk (branch-free pipeline); never used as data
-size_t mlp_fused_image_bytes(int D, int hidden, bool with_proj, bool with_skip, bool with_qkv) {
-    return ((size_t)(hidden / 32 + 2) * 2 + (with_proj ? D / 32 : 0) + (with_skip ? D / 16 : 0) + (with_qkv ? 3 * D / 32 : 0)) * (D / 16) * 1024;
-}
-
 void mlp_fused_pack_rows(int D, int nrows, const float* w, unsigned short (*to_bf16)(float), unsigned short* img) {
     const int F = D / 16;
     for (int t = 0; t < nrows / 32; ++t)
-        for (int f = 0; f < F; ++f)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int r = lane & 31, h = lane >> 5;
-                for (int j = 0; j < 8; ++j)
-                    img[((size_t)t * F + f) * 512 + lane * 8 + j] = to_bf16(w[(size_t)(32 * t + r) * D + 16 * f + 8 * (j >> 2) + 4 * h + (j & 3)]);
-            }
+        for (int f = 0; f < F; ++f) pack_fragment(w, D, 32 * t, 16 * f, FRAG_K_ACC, to_bf16, img + ((size_t)t * F + f) * 512);
 }
 
 // skip_linear weight [D, 2D] (nn.Linear layout; input = cat([x, skip]), reference models/uvit.py:199) -> the 2 NT blocks the
@@ -1336,22 +1268,15 @@ void mlp_fused_pack_rows(int D, int nrows, const float* w, unsigned short (*to_b
 void mlp_fused_pack_skip(int D, const float* ws, unsigned short (*to_bf16)(float), unsigned short* img) {
     const int F = D / 16, NT = D / 32, H2 = F / 2;
     for (int p = 0; p < 2 * NT; ++p)
-        for (int f = 0; f < F; ++f)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int r = lane & 31, h = lane >> 5;
-                for (int j = 0; j < 8; ++j) {
-                    int row, k;
-                    if (p < NT) {
-                        row = 32 * p + r;
-                        k = 16 * f + 8 * (j >> 2) + 4 * h + (j & 3);
-                    } else {
-                        const int q = p - NT, pass = q / (NT / 2), jj = q % (NT / 2);
-                        row = 32 * (2 * jj + (f >= H2 ? 1 : 0)) + r;
-                        k = D + 16 * (pass * H2 + f % H2) + 8 * h + j;
-                    }
-                    img[((size_t)p * F + f) * 512 + lane * 8 + j] = to_bf16(ws[(size_t)row * 2 * D + k]);
-                }
+        for (int f = 0; f < F; ++f) {
+            unsigned short* dst = img + ((size_t)p * F + f) * 512;
+            if (p < NT) {
+                pack_fragment(ws, 2 * D, 32 * p, 16 * f, FRAG_K_ACC, to_bf16, dst);
+            } else {
+                const int q = p - NT, pass = q / (NT / 2), jj = q % (NT / 2);
+                pack_fragment(ws, 2 * D, 32 * (2 * jj + (f >= H2 ? 1 : 0)), D + 16 * (pass * H2 + f % H2), FRAG_K_NATURAL, to_bf16, dst);
             }
+        }
 }
 
 // Wproj [D, D] (nn.Linear layout) -> D/32 blocks in front of the MLP image: block t = output columns 32t .. 32t+31 as the
@@ -1359,10 +1284,7 @@ void mlp_fused_pack_skip(int D, const float* ws, unsigned short (*to_bf16)(float
 void mlp_fused_pack_proj(int D, const float* wp, unsigned short (*to_bf16)(float), unsigned short* img) {
     const int F = D / 16;
     for (int t = 0; t < D / 32; ++t)
-        for (int ks = 0; ks < F; ++ks)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j)
-                    img[((size_t)t * F + ks) * 512 + lane * 8 + j] = to_bf16(wp[(size_t)(32 * t + (lane & 31)) * D + 16 * ks + 8 * (lane >> 5) + j]);
+        for (int ks = 0; ks < F; ++ks) pack_fragment(wp, D, 32 * t, 16 * ks, FRAG_K_NATURAL, to_bf16, img + ((size_t)t * F + ks) * 512);
 }
 
 // Row plan (see the header): patch rows in 128-row main tiles, extra rows in tiles split `groups` ways along hidden.
@@ -1396,24 +1318,13 @@ size_t mlp_fused_partial_bytes(int max_batch, int extras, int D, int hidden) {
 // fc1 B fragments from accumulator registers); W2's k index always is.
 void mlp_fused_pack(int D, int hidden, const float* w1, const float* b1, const float* w2, bool kperm,
                     unsigned short (*to_bf16)(float), unsigned short* img, float* b1p) {
-    const int F = D / 16, NT = D / 32, KS = D / 16, nchunks = hidden / 32;
+    const int F = D / 16, NT = D / 32, nchunks = hidden / 32;
     for (int c = 0; c < nchunks; ++c) {
         unsigned short* blk1 = img + (size_t)(2 * c) * F * 512;
         unsigned short* blk2 = img + (size_t)(2 * c + 1) * F * 512;
-        for (int lane = 0; lane < 64; ++lane) {
-            const int r = lane & 31, h = lane >> 5;
-            for (int ks = 0; ks < KS; ++ks)
-                for (int j = 0; j < 8; ++j) {
-                    const int k = 16 * ks + (kperm ? 8 * (j >> 2) + 4 * h + (j & 3) : 8 * h + j);
-                    blk1[(size_t)ks * 512 + lane * 8 + j] = to_bf16(w1[(size_t)(32 * c + r) * D + k]);
-                }
-            for (int t = 0; t < NT; ++t)
-                for (int s = 0; s < 2; ++s)
-                    for (int j = 0; j < 8; ++j) {
-                        const int k = 32 * c + 16 * s + 8 * (j >> 2) + 4 * h + (j & 3);   // accumulator row order
-                        blk2[(size_t)(2 * t + s) * 512 + lane * 8 + j] = to_bf16(w2[(size_t)(32 * t + r) * hidden + k]);
-                    }
-        }
+        for (int ks = 0; ks < F; ++ks) pack_fragment(w1, D, 32 * c, 16 * ks, kperm ? FRAG_K_ACC : FRAG_K_NATURAL, to_bf16, blk1 + (size_t)ks * 512);
+        for (int t = 0; t < NT; ++t)       // fragment 2 t + s: output tile t, k = hidden units 32 c + 16 s .. + 15 (the GELU output leaves the accumulators)
+            for (int s = 0; s < 2; ++s) pack_fragment(w2, hidden, 32 * t, 32 * c + 16 * s, FRAG_K_ACC, to_bf16, blk2 + (size_t)(2 * t + s) * 512);
         for (int h = 0; h < 2; ++h)
             for (int e = 0; e < 16; ++e) b1p[c * 32 + h * 16 + e] = b1[32 * c + (e & 3) + 8 * (e >> 2) + 4 * h];
     }

@@ -15,49 +15,18 @@
 //     tiles of their own, each split along K over `groups` workgroups that write partial sums to slabs -- mlp_reduce_kernel folds the slabs
 //     into x in a fixed order (deterministic; which path a row takes depends only on its token index, never on the batch size).
 #include "dd_internal.h"
+#include "wave_prims.h"
 
 #include <utility>
 
 namespace dd {
 namespace {
 
-typedef const __attribute__((address_space(1))) void* rl_gptr_t;
-typedef __attribute__((address_space(3))) void* rl_lptr_t;
-
 constexpr int kRlD = 768, kRlNT = kRlD / 32, kRlBlk = kRlNT * 1024;      // one k-step of weights: 24 fragments
 constexpr int kRlRing = 4 * kRlBlk;                                       // 96 KB
 constexpr int kRlABuf = 128 * 128;                                        // 128 rows x 64 k (4 k-steps) bf16
 constexpr int kRlLds = kRlRing + 3 * kRlABuf;                             // 144 KB
-
-__device__ __forceinline__ unsigned rl_pack2(float lo, float hi) {
-    typedef __bf16 bf16v2 __attribute__((ext_vector_type(2)));
-    typedef float f32v2 __attribute__((ext_vector_type(2)));
-    const f32v2 q = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(q, bf16v2));
-}
-
-__device__ __forceinline__ unsigned rl_lds(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p; }
-// one 1 KB LDS-DMA piece in the scalar-base form: uniform 64-bit base (SGPRs) + a 32-bit lane offset, M0 = the piece's LDS address.  Written as asm: the
-// builtin turns base + offset into a 64-bit VGPR address pair, and that form serialises with the SIMD's MFMAs (profiles/r05/dma_mfma_probe_roles.txt).
-__device__ __forceinline__ void rl_dma(const char* sbase, unsigned voff, const void* lds_dst) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(rl_lds(lds_dst)), "v"(voff), "s"(sbase) : "memory", "m0");
-}
-template <int OFF>
-__device__ __forceinline__ void rl_read(bf16x8& d, unsigned addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "i"(OFF));
-}
-// one MFMA gap: [wait: at most LG LDS reads younger than this MFMA's fragment] MFMA [read the fragment PD gaps ahead into the register just read]
-// (AGPR: the accumulator lives in the AGPR half of the register file -- 256 registers = 16 of the 24 output tiles; the other 8 tiles' in VGPRs)
-template <int LG, int LO, bool AGPR>
-__device__ __forceinline__ void rl_gap(f32x16& acc, bf16x8& wa, const bf16x8& xb, unsigned la) {
-    if constexpr (AGPR)
-        asm volatile("s_waitcnt lgkmcnt(%4)\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0\n\tds_read_b128 %1, %3 offset:%5"
-                     : "+a"(acc), "+v"(wa) : "v"(xb), "v"(la), "i"(LG), "i"(LO));
-    else
-        asm volatile("s_waitcnt lgkmcnt(%4)\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0\n\tds_read_b128 %1, %3 offset:%5"
-                     : "+v"(acc), "+v"(wa) : "v"(xb), "v"(la), "i"(LG), "i"(LO));
-}
-constexpr int kRlNA = 16;        // output tiles whose accumulators are AGPRs
+constexpr int kRlNA = 16;        // output tiles whose accumulators are AGPRs (256 registers, the AGPR half of the register file; the other 8 tiles' are VGPRs)
 template <int T>
 __device__ __forceinline__ void rl_pin(f32x16& y) {
     if constexpr (T < kRlNA) asm volatile("" : "+a"(y));
@@ -99,7 +68,7 @@ __global__ void __launch_bounds__(256) rowlin768_kernel(const RowLinArgs a) {
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
             const int pc = wave * 6 + i;
-            rl_dma(wsrc + (size_t)ks * kRlBlk + pc * 1024, lane16, ring + (ks & 3) * kRlBlk + pc * 1024);
+            lds_dma16s(wsrc + (size_t)ks * kRlBlk + pc * 1024, lane16, ring + (ks & 3) * kRlBlk + pc * 1024);
         }
     };
     // LDS-DMA of the rows' operand, group g (k = 64 g .. 64 g + 63) -> A buffer g % 3: 16 pieces of 8 rows x 128 B, 4 per wave; the lane
@@ -120,18 +89,18 @@ __global__ void __launch_bounds__(256) rowlin768_kernel(const RowLinArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int pc = wave * 4 + i;
-            rl_dma(g < g_split ? abase_1 : abase_2, arows[i] + (unsigned)g * 128u, abuf + (g % 3) * kRlABuf + pc * 1024);
+            lds_dma16s(g < g_split ? abase_1 : abase_2, arows[i] + (unsigned)g * 128u, abuf + (g % 3) * kRlABuf + pc * 1024);
         }
     };
     // ... and one piece at a time (the loop spreads a k-step's requests over its MFMA gaps: an LDS-DMA instruction costs 60-185 cycles of
     // issue, a burst of 10 stalls the wave for a whole k-step's worth of MFMA time)
     auto dma_w1 = [&](int ks, int j) {
         const int pc = wave * 6 + j;
-        rl_dma(wsrc + (size_t)ks * kRlBlk + pc * 1024, lane16, ring + (ks & 3) * kRlBlk + pc * 1024);
+        lds_dma16s(wsrc + (size_t)ks * kRlBlk + pc * 1024, lane16, ring + (ks & 3) * kRlBlk + pc * 1024);
     };
     auto dma_a1 = [&](int g, int j) {
         const int pc = wave * 4 + j;
-        rl_dma(g < g_split ? abase_1 : abase_2, arows[j] + (unsigned)g * 128u, abuf + (g % 3) * kRlABuf + pc * 1024);
+        lds_dma16s(g < g_split ? abase_1 : abase_2, arows[j] + (unsigned)g * 128u, abuf + (g % 3) * kRlABuf + pc * 1024);
     };
     // prologue: A groups 0, 1; weights of k-steps 0, 1, 2
     dma_a(0);
@@ -150,15 +119,15 @@ __global__ void __launch_bounds__(256) rowlin768_kernel(const RowLinArgs a) {
 
     // fragment read of the rows: lane (r32, h) wants chunk 2 s + h of row 32 wave + r32 (s = k-step within the group)
     const int arow = 32 * wave + r32;
-    const unsigned afr = rl_lds(abuf) + arow * 128;
+    const unsigned afr = lds_offset(abuf) + arow * 128;
     const int asw = (arow >> 1) & 7;
-    const unsigned wlo = rl_lds(ring) + lane * 16, whi = wlo + 65536u;   // ds offsets are 16 bits
+    const unsigned wlo = lds_offset(ring) + lane * 16, whi = wlo + 65536u;   // ds offsets are 16 bits
 
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");      // A groups 0, 1 and the weights of k-steps 0, 1, 2 have landed
     constexpr int PD = 8;                                                // fragment reads in flight ahead of their MFMA
     bf16x8 wa[PD], xf[2];
-    rl_read<0>(xf[0], afr + ((h ^ asw) << 4));                          // k-step 0 (A buffer 0): chunk h of the row
-    [&]<int... J>(std::integer_sequence<int, J...>) { (rl_read<J * 1024>(wa[J], wlo), ...); }(std::make_integer_sequence<int, PD>{});
+    ds_read16<0>(xf[0], afr + ((h ^ asw) << 4));                          // k-step 0 (A buffer 0): chunk h of the row
+    [&]<int... J>(std::integer_sequence<int, J...>) { (ds_read16<J * 1024>(wa[J], wlo), ...); }(std::make_integer_sequence<int, PD>{});
     for (int g = 0; g < NG; ++g) {
         const bool more_a = g + 2 < NG;
         const unsigned abase = afr + (unsigned)(g % 3) * kRlABuf, anext = afr + (unsigned)((g + 1) % 3) * kRlABuf;
@@ -181,12 +150,12 @@ __global__ void __launch_bounds__(256) rowlin768_kernel(const RowLinArgs a) {
                 if constexpr (t == kRlNT / 2) {
                     // the rows' fragment of the next k-step (its group landed long ago: requested 8 k-steps before its first use)
                     const unsigned na = (i < 3 ? abase : anext) + ((((2 * ((i + 1) & 3)) + h) ^ asw) << 4);
-                    rl_read<0>(xf[(i + 1) & 1], na);
+                    ds_read16<0>(xf[(i + 1) & 1], na);
                 }
                 // fragment PD gaps ahead: this k-step's slot, or the next k-step's (confirmed at the barrier above: t + PD >= 24 > 2)
                 constexpr int tn = t + PD, sl = tn < kRlNT ? i : ((i + 1) & 3), tt = tn < kRlNT ? tn : tn - kRlNT;
                 constexpr int LO = sl * kRlBlk + tt * 1024;
-                rl_gap<PD - 1, (LO < 65536 ? LO : LO - 65536), (t < kRlNA)>(Y[t], wa[gi % PD], xf[i & 1], LO < 65536 ? wlo : whi);
+                mfma_gap<(t < kRlNA), PD - 1, true, (LO < 65536 ? LO : LO - 65536)>(Y[t], wa[gi % PD], xf[i & 1], LO < 65536 ? wlo : whi);
             }(), ...);
         }(std::make_integer_sequence<int, 4 * kRlNT>{});
     }
@@ -223,10 +192,10 @@ __global__ void __launch_bounds__(256) rowlin768_kernel(const RowLinArgs a) {
             const char* src = reinterpret_cast<const char*>(a.xres + 256 * p);
             for (int i = 0; i < nvalid; ++i) {
                 const long long ri = row0w + i < rows_all ? row0w + i : rows_all - 1;
-                rl_dma(src + ri * (kRlD * 4), lane * 16, strip + i * kPitch);
+                lds_dma16s(src + ri * (kRlD * 4), lane * 16, strip + i * kPitch);
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        waitcnt_vm<0>();
 #pragma unroll
         for (int tt = 0; tt < 8; ++tt) {
             const int t = 8 * p + tt;
@@ -256,7 +225,7 @@ __global__ void __launch_bounds__(256) rowlin768_kernel(const RowLinArgs a) {
                 if (i < nvalid) {
                     const f32x4 v = *reinterpret_cast<const f32x4*>(strip + i * kPitch + lane * 16);
                     *reinterpret_cast<f32x4*>(dst + (long long)i * kRlD) = v;
-                    if (cp) *reinterpret_cast<uint2*>(cp + (long long)i * kRlD) = uint2{rl_pack2(v[0], v[1]), rl_pack2(v[2], v[3])};
+                    if (cp) *reinterpret_cast<uint2*>(cp + (long long)i * kRlD) = uint2{cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3])};
                 }
             }
         }
@@ -290,7 +259,7 @@ __global__ void __launch_bounds__(256) rowlin768_kernel(const RowLinArgs a) {
                 const f32x4 gv = *reinterpret_cast<const f32x4*>(a.ln_g + 32 * t + 8 * q + 4 * h), bv = *reinterpret_cast<const f32x4*>(a.ln_b + 32 * t + 8 * q + 4 * h);
                 const f32x4 yv = {Y[t][4 * q], Y[t][4 * q + 1], Y[t][4 * q + 2], Y[t][4 * q + 3]};
                 const f32x4 w = (yv * rstd + shift) * gv + bv;
-                v[q] = uint2{rl_pack2(w[0], w[1]), rl_pack2(w[2], w[3])};
+                v[q] = uint2{cvt_pk_bf16(w[0], w[1]), cvt_pk_bf16(w[2], w[3])};
             }
 #pragma unroll
             for (int qp = 0; qp < 4; qp += 2) {      // 16-byte row segments (v_permlane32_swap pairs the lane halves)
@@ -314,16 +283,10 @@ __global__ void __launch_bounds__(256) rowlin768_kernel(const RowLinArgs a) {
 
 bool rowlin_supported(int D, int K) { return D == kRlD && K % 64 == 0 && K >= 192; }
 
-// nn.Linear weight [768, K] -> the stream the kernel reads: [k-step][output tile t][lane] x 16 bytes, each 1 KB fragment in MFMA A-operand
-// order: img[((ks * 24 + t) * 64 + lane) * 8 + i] = W[32 t + (lane & 31)][16 ks + 8 (lane >> 5) + i]
+// nn.Linear weight [768, K] -> the stream the kernel reads: [k-step][output tile t] x 1 KB fragment, natural k order (the rows' operand is loaded as stored)
 void rowlin_pack(int K, const float* w, unsigned short (*to_bf16)(float), unsigned short* img) {
     for (int ks = 0; ks < K / 16; ++ks)
-        for (int t = 0; t < kRlNT; ++t)
-            for (int lane = 0; lane < 64; ++lane) {
-                const float* src = w + (size_t)(32 * t + (lane & 31)) * K + 16 * ks + 8 * (lane >> 5);
-                unsigned short* dst = img + (((size_t)ks * kRlNT + t) * 64 + lane) * 8;
-                for (int i = 0; i < 8; ++i) dst[i] = to_bf16(src[i]);
-            }
+        for (int t = 0; t < kRlNT; ++t) pack_fragment(w, K, 32 * t, 16 * ks, FRAG_K_NATURAL, to_bf16, img + ((size_t)ks * kRlNT + t) * 512);
 }
 
 // Row plan: patch rows in 128-row main tiles, extra-token rows in 128-row tiles split `groups` ways along K (a function of K alone -- never of

@@ -2,6 +2,7 @@
 // LayerNorm, the early-exit probes, the final LayerNorm + decoder_pred launch (the step's tail lives in step.hip).
 // All arithmetic here is fp32 in both precision modes.
 #include "dd_internal.h"
+#include "wave_prims.h"
 
 #include <cstring>
 #include <utility>
@@ -308,12 +309,6 @@ __global__ void __launch_bounds__(256) time_mlp_kernel(const TimeMlpArgs a) {
 // ------------------------------------------------------------------------------------------
 constexpr int kLnMaxPerLane = 16;  // D <= 1024
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // frag != nullptr (bf16, D % 256 == 0, tok_n % 32 == 0): the patch rows (token l >= tok_e of every tok_l-row image) are written
 // THERE in MFMA B-fragment order -- [32-row group of patch rows][D / 16 k-steps][64 lanes] x 16 bytes, what the attention launch
 // that computes attn.qkv itself loads (MlpFusedArgs::ln_out_frag) -- instead of row-major; the extra-token rows still go to `out`.
@@ -343,12 +338,12 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict_
         for (int j = 0; j < kLnMaxPerLane; ++j)
             if (j < per) { v[j] = xr[j * 64 + lane]; s += v[j]; }
     }
-    const float mean = wave_sum(s) / (float)D;
+    const float mean = wave_reduce_add(s) / (float)D;
     float q2 = 0.f;
 #pragma unroll
     for (int j = 0; j < kLnMaxPerLane; ++j)
         if (j < per) { const float dlt = v[j] - mean; q2 += dlt * dlt; }
-    const float rstd = 1.0f / sqrtf(wave_sum(q2) / (float)D + 1e-5f);
+    const float rstd = 1.0f / sqrtf(wave_reduce_add(q2) / (float)D + 1e-5f);
     T* orow = out + (long long)row * D;
     bool to_frag = false;
     if constexpr (sizeof(T) == 2) {
@@ -437,13 +432,13 @@ __global__ void __launch_bounds__(256) reduce_ln_kernel(const ReduceLnArgs a) {
     float sum = 0.f;
 #pragma unroll
     for (int j = 0; j < NQ; ++j) sum += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
-    const float mean = wave_sum(sum) / (float)D;
+    const float mean = wave_reduce_add(sum) / (float)D;
     float q2 = 0.f;
 #pragma unroll
     for (int j = 0; j < NQ; ++j)
 #pragma unroll
         for (int e = 0; e < 4; ++e) { const float d = v[j][e] - mean; q2 += d * d; }
-    const float rstd = 1.0f / sqrtf(wave_sum(q2) / (float)D + 1e-5f);
+    const float rstd = 1.0f / sqrtf(wave_reduce_add(q2) / (float)D + 1e-5f);
     bf16_t* orow = a.h + (long long)row * D;
     bool to_frag = false;
     if (a.frag) {
@@ -690,13 +685,6 @@ __device__ __forceinline__ void landed_at_vmcnt(f32x4& v) {
 // orders below the bf16 roundings of the backbone that feeds these heads -- 9 MFMAs of 16 cycles per 32 k instead of 24 of 32 cycles (a fifth
 // of the matrix-pipe time, and of its energy).  Lane (row l & 15, k-group l >> 4) holds k = 32 jj + 8 (l >> 4) .. + 7 as TWO quads per jj;
 // a.wg is the host-packed image [jj][ct][hi, lo][64 lanes] x 8 bf16 in A-operand order (capi.hip: pack_head_split).
-__device__ __forceinline__ unsigned head_pack2_bf16(float lo, float hi) {   // one v_cvt_pk_bf16_f32 (round to nearest even)
-    typedef __bf16 bf16v2 __attribute__((ext_vector_type(2)));
-    typedef float f32v2 __attribute__((ext_vector_type(2)));
-    const f32v2 q = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(q, bf16v2));
-}
-
 template <int D, int NT, int NW = 8, bool PROBE = false, bool SPLIT = false>
 __global__ void __launch_bounds__(NW * 64) head_dec_kernel(const HeadDecArgs a) {
     constexpr int J = D / 16;
@@ -804,14 +792,13 @@ __global__ void __launch_bounds__(NW * 64) head_dec_kernel(const HeadDecArgs a) 
                         for (int ct = 0; ct < NT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[ct][e], xv[j][e], acc[ct], 0, 0, 0);
                 } else if constexpr (j % 2 == 1) {      // both quads of k-block jj = j / 2 are here: split, then 3 NT MFMAs
                     constexpr int jj = j / 2;
-                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                     u32x4 hi, lo;
 #pragma unroll
                     for (int p2 = 0; p2 < 4; ++p2) {
                         const float d0 = p2 < 2 ? xv[j - 1][2 * p2] : xv[j][2 * p2 - 4], d1 = p2 < 2 ? xv[j - 1][2 * p2 + 1] : xv[j][2 * p2 - 3];
-                        const unsigned h = head_pack2_bf16(d0, d1);
+                        const unsigned h = cvt_pk_bf16(d0, d1);
                         hi[p2] = h;
-                        lo[p2] = head_pack2_bf16(d0 - __builtin_bit_cast(float, h << 16), d1 - __builtin_bit_cast(float, h & 0xffff0000u));
+                        lo[p2] = cvt_pk_bf16(d0 - __builtin_bit_cast(float, h << 16), d1 - __builtin_bit_cast(float, h & 0xffff0000u));
                     }
                     const bf16x8 dh = __builtin_bit_cast(bf16x8, hi), dl = __builtin_bit_cast(bf16x8, lo);
 #pragma unroll

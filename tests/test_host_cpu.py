@@ -261,8 +261,8 @@ def test_hand_counted_loads_of_the_output_head_are_never_touched_in_flight():
 
 def test_every_lds_dma_request_has_a_wait_state_behind_its_m0_write():
     """An LDS-DMA request takes its LDS destination from M0, and gfx950 needs one wait state between an SALU write of M0 and the request that
-    reads it; hipcc pads the sites it emits itself but not the inside of an asm string (gemm.hip glds16s, rowlin.hip rl_dma, attention.hip's
-    weight ring).  tools/isa_audit_lds_dma.py compiles every translation unit for gfx950 and checks each kernel's instruction stream (across
+    reads it; hipcc pads the sites it emits itself but not the inside of an asm string (wave_prims.h lds_dma16s, which gemm.hip, rowlin.hip and
+    attention.hip's weight ring call).  tools/isa_audit_lds_dma.py compiles every translation unit for gfx950 and checks each kernel's instruction stream (across
     labels and branches) for a request whose previous instruction writes M0.  Cross-compiles without a GPU."""
     import shutil
     import subprocess

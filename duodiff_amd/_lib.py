@@ -53,6 +53,11 @@ class dd_guidance(C.Structure):
     _fields_ = [("scale", C.c_float), ("null_label", C.c_int32)]
 
 
+class dd_autoguidance(C.Structure):
+    """autoguidance: eps = eps_main + scale * (eps_main - eps_guide), guide = the weaker dd_model of the same image geometry"""
+    _fields_ = [("guide", C.c_void_p), ("scale", C.c_float)]
+
+
 class dd_ee_sample_args(C.Structure):
     _fields_ = [("model", C.c_void_p), ("threshold", C.c_float), ("t_start", C.c_int32), ("t_end", C.c_int32),
                 ("noise_mode", C.c_int32), ("use_graph", C.c_int32), ("B", C.c_int32), ("seed", C.c_uint64),
@@ -99,6 +104,11 @@ SIGNATURES = {
                           [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "dd_sample_multistep": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.c_void_p]),
     "dd_sample_multistep_guided": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_guidance), C.c_void_p]),
+    "dd_forward_autoguided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.POINTER(dd_autoguidance), C.c_void_p,
+                                        C.c_int, C.c_void_p]),
+    "dd_sample_autoguided": (C.c_int, [C.c_void_p, C.POINTER(dd_sample_args), C.POINTER(dd_autoguidance), C.c_void_p]),
+    "dd_sample_affine_autoguided": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.POINTER(dd_autoguidance), C.c_void_p]),
+    "dd_sample_multistep_autoguided": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_autoguidance), C.c_void_p]),
     "dd_bench_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
     "dd_vae_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "dd_vae_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),

@@ -12,6 +12,7 @@
 #include "launch_args.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -94,9 +95,12 @@ struct GraphKey {
     int b0 = 0;                                                      // first image of a half-batch chain within the whole batch
     int gnull = -1;                                                  // classifier-free guidance: the null label (-1: unguided)
     unsigned gscale = 0;                                             //   and the bits of the scale (+0 and -0 round differently)
+    const void* aguide = nullptr;                                    // autoguidance: the guide model of a two-model step (null: CFG / unguided; gscale: the scale's bits)
+    unsigned long long aserial = 0;                                  //   and its serial: an address can come back with another model behind it
     bool operator==(const GraphKey& o) const {
         return x == o.x && y == o.y && B == o.B && noise == o.noise && variance == o.variance && num_cus == o.num_cus &&
-               atab == o.atab && aux0 == o.aux0 && aux1 == o.aux1 && thr == o.thr && b0 == o.b0 && gnull == o.gnull && gscale == o.gscale;
+               atab == o.atab && aux0 == o.aux0 && aux1 == o.aux1 && thr == o.thr && b0 == o.b0 && gnull == o.gnull && gscale == o.gscale &&
+               aguide == o.aguide && aserial == o.aserial;
     }
     void guide(const dd_guidance* g) {
         if (g) { gnull = g->null_label; gscale = __builtin_bit_cast(unsigned, g->scale); }
@@ -122,6 +126,7 @@ struct WsPtrs {
 
 struct dd_model {
     dd_ctx* ctx = nullptr;
+    unsigned long long serial = 0;   // unique per dd_model_create of the process (graph keys that name another model: autoguidance)
     dd_config cfg{};
     int D = 0, L = 0, N = 0, extras = 0, pd = 0, pdp = 0, H = 0, hidden = 0, hid_ld = 0, half_depth = 0, Mp_max = 0;
     std::map<std::string, HostParam> params;   // every state_dict name of the model (catalogue), its data once set (dropped by finalize)
@@ -824,11 +829,16 @@ int run_model(dd_model* m, const Chain& ch, const float* x_img, const float* t_v
                                    : run_backbone<float>(m, ch, x_img, t_vec, y_dev, B, s, ee);
 }
 
-int check_call(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev) {
+// the checks of a call that do not concern labels
+int check_model(dd_ctx* c, dd_model* m, int B) {
     if (!c || !m) return DD_ERR_INVALID;
     if (m->ctx != c) return ctx_fail(c, DD_ERR_INVALID, "model belongs to another context");
     if (!m->finalized) return ctx_fail(c, DD_ERR_STATE, "dd_model_finalize has not been called");
     if (B < 1 || B > m->cfg.max_batch) return ctx_fail(c, DD_ERR_INVALID, "batch size outside [1, max_batch]");
+    return DD_OK;
+}
+int check_call(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev) {
+    if (int rc = check_model(c, m, B)) return rc;
     if (m->cfg.num_classes > 0 && !y_dev)
         return ctx_fail(c, DD_ERR_INVALID, "class-conditional model called without labels (pos_embed has L=extras+N rows)");
     if (m->cfg.num_classes <= 0 && y_dev)
@@ -850,16 +860,64 @@ int check_guided(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev, const dd_g
     return check_call(c, m, 2 * B, y_dev);
 }
 
+// an autoguided call of B images (include/duodiff.h dd_autoguidance) on first (and late, or null): every check before anything is enqueued
+int check_autoguided(dd_ctx* c, dd_model* first, dd_model* late, int B, const int64_t* y_dev, const dd_autoguidance* ag) {
+    if (!c || !first) return DD_ERR_INVALID;
+    if (!ag) return ctx_fail(c, DD_ERR_INVALID, "null dd_autoguidance");
+    dd_model* gm = ag->guide;
+    if (!gm) return ctx_fail(c, DD_ERR_INVALID, "null guide model");
+    if (gm->ctx != c) return ctx_fail(c, DD_ERR_INVALID, "guide model belongs to another context");
+    if (gm->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, "autoguidance is not supported for early-exit models (the guide carries heads)");
+    if (!gm->finalized) return ctx_fail(c, DD_ERR_INVALID, "guide model: dd_model_finalize has not been called");
+    if (!std::isfinite(ag->scale)) return ctx_fail(c, DD_ERR_INVALID, "autoguidance scale is not finite");
+    bool conditional = gm->cfg.num_classes > 0;
+    for (dd_model* m : {first, late}) {
+        if (!m) continue;
+        if (m->ctx == c && m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, "autoguidance is not supported for early-exit models");
+        if (int rc = check_model(c, m, B)) return rc;
+        if (m->cfg.img_size != gm->cfg.img_size || m->cfg.patch_size != gm->cfg.patch_size || m->cfg.in_chans != gm->cfg.in_chans)
+            return ctx_fail(c, DD_ERR_INVALID, "guide model disagrees with the guided model on image geometry (img_size, patch_size, in_chans)");
+        conditional = conditional || m->cfg.num_classes > 0;
+    }
+    if (B > gm->cfg.max_batch) return ctx_fail(c, DD_ERR_INVALID, "batch size outside [1, max_batch] of the guide model");
+    if (conditional && !y_dev) return ctx_fail(c, DD_ERR_INVALID, "autoguidance with a class-conditional model called without labels");
+    if (!conditional && y_dev) return ctx_fail(c, DD_ERR_INVALID, "autoguidance of unconditional models called with labels");
+    return DD_OK;
+}
+// the guide's side of chain ch of model m: the same chain of the guide's own workspaces, the same step state and grids
+Chain guide_chain(const Chain& ch, const dd_model* m, const dd_model* guide) {
+    Chain g = ch;
+    g.ws = &guide->ws[ch.ws == &m->ws[1] ? 1 : 0];
+    return g;
+}
+// Under autoguidance the running model m is guided unless it is the guide model itself (the plain unguided step).  Runs the guide's
+// forward in line on the chain's stream (no fork inside a captured step: parallel branches in a chain's graph cost more than they hide,
+// and the other chain already fills the chip) and points the output head's second halo at its decoder rows.  Both embed launches copy
+// the same t into the step state (rowops.hip: t_final = t); only the output head advances it.
+int run_guide(dd_ctx* c, dd_model* m, const Chain& ch, const dd_autoguidance* ag, const float* x_dev, const int64_t* y_dev, int B,
+              hipStream_t s, FinalArgs& fa) {
+    dd_model* gm = ag->guide;
+    const Chain gch = guide_chain(ch, m, gm);
+    if (int rc = run_model(gm, gch, x_dev, nullptr, gm->cfg.num_classes > 0 ? y_dev : nullptr, B, s)) return rc;
+    fa.dec2 = gch.ws->dec; fa.wconv2 = gm->head.wconv; fa.bconv2 = gm->head.bconv; fa.L2 = gm->L; fa.extras2 = gm->extras;
+    fa.guide_scale = ag->scale;
+    return DD_OK;
+}
+
 // one sampling step of chain ch enqueued on s: x <- update(x, model(x, t)) ; t comes from ch.st
 // advance != 0: the step's last kernel also decrements the device-resident timestep (graph replays / dd_sample)
 // g != null (classifier-free guidance): B images, the backbone runs the 2 B rows [x | x] with labels [y | null] (stage_guided's layout)
 // htab != null (the multistep loop, atab set): the update adds row k's history term and writes h' to h [B, C, S, S]
+// ag != null (autoguidance; never with g): each model takes y_dev iff it is class-conditional; m != ag->guide: the guide runs the same B rows first
 int enqueue_step(dd_ctx* c, dd_model* m, const Chain& ch, float* x_dev, const int64_t* y_dev, int noise_mode, const float* z_dev,
                  int variance, float* eps_out, int B, hipStream_t s, int advance = 0, const AffineRow* atab = nullptr, int b0 = 0,
-                 const dd_guidance* g = nullptr, const HistRow* htab = nullptr, float* h = nullptr) {
-    int rc = run_model(m, ch, x_dev, nullptr, y_dev, g ? 2 * B : B, s);
-    if (rc) return rc;
+                 const dd_guidance* g = nullptr, const HistRow* htab = nullptr, float* h = nullptr, const dd_autoguidance* ag = nullptr) {
     FinalArgs fa = final_args(m, ch, ch.ws->dec, m->head.wconv, m->head.bconv, B);
+    int rc = DD_OK;
+    if (ag && ag->guide != m && (rc = run_guide(c, m, ch, ag, x_dev, y_dev, B, s, fa))) return rc;
+    if (ag && m->cfg.num_classes <= 0) y_dev = nullptr;
+    rc = run_model(m, ch, x_dev, nullptr, y_dev, g ? 2 * B : B, s);
+    if (rc) return rc;
     fa.x_in = x_dev; fa.z = z_dev; fa.eps_out = eps_out; fa.x_out = x_dev;
     fa.noise_mode = noise_mode; fa.variance = variance; fa.advance = advance; fa.atab = atab; fa.b0 = b0;
     if (g) { fa.pair_B = B; fa.guide_scale = g->scale; }
@@ -871,12 +929,17 @@ int enqueue_step(dd_ctx* c, dd_model* m, const Chain& ch, float* x_dev, const in
 
 // eps = model(x, t) and nothing else (dd_forward*, the early-exit step): t_set != null first puts that timestep into the chain's step
 // state; g != null: the backbone runs the 2 B rows of stage_guided's layout and the output head combines them into B guided images
+// ag != null (autoguidance; t_vec null): as enqueue_step
 int forward_eps(dd_ctx* c, dd_model* m, const Chain& ch, const float* t_set, const float* x_dev, const float* t_vec, const int64_t* y_dev,
-                float* eps_dev, int B, hipStream_t s, const EeTaps* ee = nullptr, const dd_guidance* g = nullptr) {
+                float* eps_dev, int B, hipStream_t s, const EeTaps* ee = nullptr, const dd_guidance* g = nullptr,
+                const dd_autoguidance* ag = nullptr) {
     if (t_set) DD_HIP(c, launch_set_state_float(ch.st, *t_set, s));
-    int rc = run_model(m, ch, x_dev, t_vec, y_dev, g ? 2 * B : B, s, ee);
-    if (rc) return rc;
     FinalArgs fa = final_args(m, ch, ch.ws->dec, m->head.wconv, m->head.bconv, B);
+    int rc = DD_OK;
+    if (ag && ag->guide != m && (rc = run_guide(c, m, ch, ag, x_dev, y_dev, B, s, fa))) return rc;
+    if (ag && m->cfg.num_classes <= 0) y_dev = nullptr;
+    rc = run_model(m, ch, x_dev, t_vec, y_dev, g ? 2 * B : B, s, ee);
+    if (rc) return rc;
     fa.eps_out = eps_dev;
     if (g) { fa.pair_B = B; fa.guide_scale = g->scale; }
     DD_HIP(c, launch_final(fa, s));
@@ -1012,6 +1075,7 @@ struct Loop {
     std::function<void(GraphKey&, const Slice&)> key;                                // the loop's own fields of a chain's graph key
     std::function<int(dd_model*, const Chain&, const Slice&, hipStream_t)> step;     // one step of one chain
     std::function<int(int chains, hipStream_t)> tail = nullptr;                      // behind the join of the chains
+    const dd_autoguidance* ag = nullptr;     // autoguidance (never with g): the steps of a model other than ag->guide run the guide too
 };
 
 // dd_sample, dd_sample_affine (both also guided) and dd_sample_early_exit: staging, the half-batch chains, graph capture and replay, timing
@@ -1029,7 +1093,8 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
     const int B0 = chained ? (L.g ? (L.B + 1) / 2 : L.B / 2) : L.B;
     c->last_chains = chains;
     // the captured persistent GEMM grids: halved for both chains of a large GEMM-path batch (the early-exit loop keeps the full grids)
-    const int cus = chained && !ee ? std::min(chain_gemm_cus(c, L.first, rows), L.late ? chain_gemm_cus(c, L.late, rows) : c->num_cus) : c->num_cus;
+    int cus = chained && !ee ? std::min(chain_gemm_cus(c, L.first, rows), L.late ? chain_gemm_cus(c, L.late, rows) : c->num_cus) : c->num_cus;
+    if (chained && L.ag) cus = std::min(cus, chain_gemm_cus(c, L.ag->guide, rows));
     // the loop runs on x_run / y_run: guided, or with graphs, the context's staging buffers (copied in here, copied back at the end)
     const size_t chw = (size_t)L.first->cfg.in_chans * L.first->cfg.img_size * L.first->cfg.img_size;
     float* x_run = L.x_dev;
@@ -1053,7 +1118,15 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
             for (dd_model* m : {L.first, L.late}) {
                 if (!m) continue;
                 if (k && (rc = ensure_chain_ws(c, m, s))) return rc;
-                if ((rc = get_graph(c, m, L.kind, k, key, s, [&] { return L.step(m, chain(m, k), sl, s); }))) return rc;
+                GraphKey mkey = key;
+                if (L.ag) {   // the step of the guide model itself is the unguided loop's step, under the unguided loop's key
+                    if (m->cfg.num_classes <= 0) mkey.y = nullptr;
+                    if (m != L.ag->guide) {
+                        if (k && (rc = ensure_chain_ws(c, L.ag->guide, s))) return rc;
+                        mkey.aguide = L.ag->guide; mkey.aserial = L.ag->guide->serial; mkey.gscale = __builtin_bit_cast(unsigned, L.ag->scale);
+                    }
+                }
+                if ((rc = get_graph(c, m, L.kind, k, mkey, s, [&] { return L.step(m, chain(m, k), sl, s); }))) return rc;
             }
         }
     }
@@ -1283,6 +1356,8 @@ int dd_model_create(dd_ctx* c, const dd_config* cfg, dd_model** out) {
     if (m->L > 288) { delete m; return ctx_fail(c, DD_ERR_UNSUPPORTED, "sequence length must be <= 288 tokens"); }
     if (m->pd > 64) { delete m; return ctx_fail(c, DD_ERR_UNSUPPORTED, "patch_size^2 * in_chans must be <= 64"); }
     m->params = catalogue(m);
+    static std::atomic<unsigned long long> serials{0};
+    m->serial = ++serials;
     *out = m;
     return DD_OK;
 }
@@ -1497,6 +1572,14 @@ int dd_forward_guided(dd_ctx* c, dd_model* m, const float* x_dev, float t, const
     return forward_eps(c, m, whole_batch(c, m), &t, x_run, nullptr, y_run, eps_dev, B, s, nullptr, g);
 }
 
+int dd_forward_autoguided(dd_ctx* c, dd_model* m, const float* x_dev, float t, const int64_t* y_dev, const dd_autoguidance* g,
+                          float* eps_dev, int B, void* stream) {
+    int rc = check_autoguided(c, m, nullptr, B, y_dev, g);
+    if (rc) return rc;
+    if (!x_dev || !eps_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    return forward_eps(c, m, whole_batch(c, m), &t, x_dev, nullptr, y_dev, eps_dev, B, (hipStream_t)stream, nullptr, nullptr, g);
+}
+
 int dd_sample_step(dd_ctx* c, dd_model* m, float* x_dev, int t, const int64_t* y_dev, int noise_mode, const float* z_dev,
                    uint64_t seed, int variance, float* eps_out_dev, int B, void* stream) {
     int rc = check_call(c, m, B, y_dev);
@@ -1512,13 +1595,13 @@ int dd_sample_step(dd_ctx* c, dd_model* m, float* x_dev, int t, const int64_t* y
 }  // extern "C"
 
 namespace {
-// dd_sample (g == nullptr) and dd_sample_guided: one path
-int sample_ddpm(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* stream) {
+// dd_sample (g == nullptr, ag == nullptr), dd_sample_guided (g) and dd_sample_autoguided (ag): one path
+int sample_ddpm(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* stream, const dd_autoguidance* ag = nullptr) {
     if (!c || !a) return DD_ERR_INVALID;
     auto check = [&](dd_model* m) { return g ? check_guided(c, m, a->B, a->y_dev, g) : check_call(c, m, a->B, a->y_dev); };
-    int rc = check(a->first);
+    int rc = ag ? check_autoguided(c, a->first, a->late, a->B, a->y_dev, ag) : check(a->first);
     if (rc) return rc;
-    if (a->late && (rc = check(a->late))) return rc;
+    if (!ag && a->late && (rc = check(a->late))) return rc;
     if (!a->x_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
     if (a->t_start > 999 || a->t_end < 0 || a->t_end > a->t_start) return ctx_fail(c, DD_ERR_INVALID, "need 999 >= t_start >= t_end >= 0");
     if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE)
@@ -1535,8 +1618,9 @@ int sample_ddpm(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* 
     L.set_state = [&](StepState* st, hipStream_t s) { return launch_set_state(st, a->t_start, (unsigned long long)a->seed, s); };
     L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.variance = a->variance; };
     L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t s) {
-        return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, a->variance, nullptr, sl.B, s, 1, nullptr, sl.b0, g);
+        return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, a->variance, nullptr, sl.B, s, 1, nullptr, sl.b0, g, nullptr, nullptr, ag);
     };
+    L.ag = ag;
     return run_loop(c, L, (hipStream_t)stream);
 }
 
@@ -1559,11 +1643,11 @@ int upload_atab(dd_ctx* c, int n, const float* t, const float* a, const float* b
 // the checks of a table-driven loop (dd_sample_affine, dd_sample_multistep: a's fields are dd_affine_sample_args'), before anything is
 // enqueued; host_noise: the message for a host noise mode
 template <typename Args>
-int check_table_loop(dd_ctx* c, const Args* a, const dd_guidance* g, const char* host_noise) {
+int check_table_loop(dd_ctx* c, const Args* a, const dd_guidance* g, const dd_autoguidance* ag, const char* host_noise) {
     auto check = [&](dd_model* m) { return g ? check_guided(c, m, a->B, a->y_dev, g) : check_call(c, m, a->B, a->y_dev); };
-    int rc = check(a->first);
+    int rc = ag ? check_autoguided(c, a->first, a->late, a->B, a->y_dev, ag) : check(a->first);
     if (rc) return rc;
-    if (a->late && (rc = check(a->late))) return rc;
+    if (!ag && a->late && (rc = check(a->late))) return rc;
     if (!a->x_dev || !a->t || !a->a || !a->b || !a->c || !a->noise) return ctx_fail(c, DD_ERR_INVALID, "null tensor / table");
     if (a->n_steps < 1 || a->n_steps > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "n_steps outside [1, 2^20]");
     if (a->counter_base < 0 || a->counter_base > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "counter_base outside [0, 2^20]");
@@ -1575,10 +1659,10 @@ int check_table_loop(dd_ctx* c, const Args* a, const dd_guidance* g, const char*
     return DD_OK;
 }
 
-// dd_sample_affine (g == nullptr) and dd_sample_affine_guided: one path
-int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, void* stream) {
+// dd_sample_affine (g == nullptr, ag == nullptr), dd_sample_affine_guided (g) and dd_sample_affine_autoguided (ag): one path
+int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, void* stream, const dd_autoguidance* ag = nullptr) {
     if (!c || !a) return DD_ERR_INVALID;
-    int rc = check_table_loop(c, a, g, "dd_sample_affine generates noise on the device; for host noise drive dd_forward + dd_affine_step");
+    int rc = check_table_loop(c, a, g, ag, "dd_sample_affine generates noise on the device; for host noise drive dd_forward + dd_affine_step");
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int n = a->n_steps;
@@ -1590,19 +1674,20 @@ int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* 
     L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_table(st, c->atab, (unsigned long long)a->seed, ss); };
     L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.atab = c->atab; };
     L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
-        return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, 0, nullptr, sl.B, ss, 1, c->atab, sl.b0, g);
+        return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, 0, nullptr, sl.B, ss, 1, c->atab, sl.b0, g, nullptr, nullptr, ag);
     };
+    L.ag = ag;
     return run_loop(c, L, s);
 }
 
 // dd_sample_multistep (g == nullptr) and dd_sample_multistep_guided: dd_sample_affine's loop with the history register.  h is staged
 // like x: copied into the context's h_stage before the loop, chain k's images at h_stage + o_k chw (guided too: h holds B images,
 // not 2 B), and copied back behind the join of the chains.
-int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, void* stream) {
+int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, void* stream, const dd_autoguidance* ag = nullptr) {
     if (!c || !a) return DD_ERR_INVALID;
     for (dd_model* m : {a->first, a->late})
         if (m && m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, "the multistep loop is not supported for early-exit models");
-    int rc = check_table_loop(c, a, g, "dd_sample_multistep generates noise on the device; for host noise drive dd_forward + dd_multistep_step");
+    int rc = check_table_loop(c, a, g, ag, "dd_sample_multistep generates noise on the device; for host noise drive dd_forward + dd_multistep_step");
     if (rc) return rc;
     if (!a->d || !a->p || !a->q || !a->hist) return ctx_fail(c, DD_ERR_INVALID, "null tensor / table");
     if (!a->h_dev) return ctx_fail(c, DD_ERR_INVALID, "null h_dev: the multistep loop needs its history register");
@@ -1634,8 +1719,9 @@ int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guid
     L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.atab = c->atab; k.aux0 = c->htab; k.aux1 = c->h_stage; };
     L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
         return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, 0, nullptr, sl.B, ss, 1, c->atab, sl.b0, g, c->htab,
-                            c->h_stage + (size_t)sl.b0 * chw);
+                            c->h_stage + (size_t)sl.b0 * chw, ag);
     };
+    L.ag = ag;
     L.tail = [&](int, hipStream_t ss) -> int {
         DD_HIP(c, hipMemcpyAsync(a->h_dev, c->h_stage, h_elems * sizeof(float), hipMemcpyDeviceToDevice, ss));
         return DD_OK;
@@ -1660,6 +1746,18 @@ int dd_sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, void* stre
 int dd_sample_multistep_guided(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, void* stream) {
     if (c && !g) return ctx_fail(c, DD_ERR_INVALID, "null dd_guidance");
     return sample_multistep(c, a, g, stream);
+}
+int dd_sample_autoguided(dd_ctx* c, const dd_sample_args* a, const dd_autoguidance* g, void* stream) {
+    if (c && !g) return ctx_fail(c, DD_ERR_INVALID, "null dd_autoguidance");
+    return sample_ddpm(c, a, nullptr, stream, g);
+}
+int dd_sample_affine_autoguided(dd_ctx* c, const dd_affine_sample_args* a, const dd_autoguidance* g, void* stream) {
+    if (c && !g) return ctx_fail(c, DD_ERR_INVALID, "null dd_autoguidance");
+    return sample_affine(c, a, nullptr, stream, g);
+}
+int dd_sample_multistep_autoguided(dd_ctx* c, const dd_multistep_sample_args* a, const dd_autoguidance* g, void* stream) {
+    if (c && !g) return ctx_fail(c, DD_ERR_INVALID, "null dd_autoguidance");
+    return sample_multistep(c, a, nullptr, stream, g);
 }
 
 // One early-exit sampling step on the device (reference eesampler.py:56-81): EarlyExitUViT.forward with every head and

@@ -316,6 +316,14 @@ struct FinalArgs {
     // written on every step; h [B, C, S, S] holds this launch's B images (guided: the conditional images only), x_out must be set
     const HistRow* htab = nullptr;
     float* h = nullptr;
+    // the second halo's own source (guided launches).  Classifier-free guidance leaves these unset: launch_final derives them from dec,
+    // pair_B and the one conv.  Autoguidance (pair_B == 0, dec2 set): dec2 [B * L2, pd] is the GUIDE model's decoder output for the same B
+    // images (its own token count L2 / extras2, the same patch grid), convolved with the guide's wconv2 / bconv2;
+    // eps = eps_main + guide_scale * (eps_main - eps_guide) goes through the update and x_out [b] alone is written; layer_B must be 0
+    const float* dec2 = nullptr;
+    const float* wconv2 = nullptr;
+    const float* bconv2 = nullptr;
+    int L2 = 0, extras2 = 0;
 };
 hipError_t launch_final(const FinalArgs& a, hipStream_t s);
 

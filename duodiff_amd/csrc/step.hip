@@ -20,6 +20,9 @@ namespace {
 // unconditional ones of image b + pair_B (2 x 13.8 KB of LDS), gathered by one loop so that both sets of loads are in flight together -- the
 // alternative, a second gather into the one halo behind the first conv, would put a second dependent global round trip on a kernel that is
 // a chain of them; then eps = eps_c + s (eps_c - eps_u) feeds the update, and x' goes to images b and b + pair_B.
+// The second halo is a source of its own (FinalArgs::dec2, L2, extras2, wconv2, bconv2): for classifier-free guidance launch_final points
+// it at the twin rows of dec and at the same conv; for autoguidance (pair_B == 0) it is the GUIDE model's decoder buffer of the same chain
+// -- its own token count and its own 3x3 conv, a different layer -- and eps = eps_main + s (eps_main - eps_guide); nothing is written twice.
 // H (multistep loop, FinalArgs::htab): the table-driven update gains the history term of row t, and h' goes back to h (image b's slot:
 // guided, the conditional image only); H = false compiles to the code without it.  The h pixels are requested with x_in, ahead of the halo
 // gather and without waiting for row t's hist flag (a load behind the step state -> row chain would hold the gather back); a step without
@@ -62,7 +65,8 @@ __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
         const int hy = hi / 18, hx = hi % 18;
         const int yy = ty * 16 + hy - 1, xx = tx * 16 + hx - 1;
         const bool in = yy >= 0 && yy < S && xx >= 0 && xx < S;
-        const float* src = a.dec + ((long long)(b + hh * a.pair_B) * a.L + a.extras + (in ? (yy / P) * g + (xx / P) : 0)) * pd +
+        const bool second = NH == 2 && hh == 1;   // the second halo's own source
+        const float* src = (second ? a.dec2 : a.dec) + ((long long)b * (second ? a.L2 : a.L) + (second ? a.extras2 : a.extras) + (in ? (yy / P) * g + (xx / P) : 0)) * pd +
                            (in ? ((yy % P) * P + (xx % P)) * C : 0);
         for (int ci = 0; ci < C; ++ci) u[hh][ci][hy][hx] = in ? src[ci] : 0.f;
     }
@@ -87,8 +91,8 @@ __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
         for (int co = 0; co < CM; ++co) {
             if (co < C) {
                 // uniform address, constant address space: scalar loads (s_load_dwordx8 ...), one output channel's 9 C weights live at a time
-                const __attribute__((address_space(4))) float* wp = (const __attribute__((address_space(4))) float*)(wconv + co * C * 9);
-                float v = bconv[co];
+                const __attribute__((address_space(4))) float* wp = (const __attribute__((address_space(4))) float*)((G && hh == 1 ? a.wconv2 : wconv) + co * C * 9);
+                float v = (G && hh == 1 ? a.bconv2 : bconv)[co];
 #pragma unroll
                 for (int k = 0; k < 9; ++k)
 #pragma unroll
@@ -116,7 +120,7 @@ __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
                 const float v = rule.apply(xin[co], eps, zin[co], hin[co]);
                 if constexpr (H) a.h[e] = rule.history(xin[co], eps);
                 a.x_out[e] = v;
-                if (G) a.x_out[e + pair] = v;
+                if (G && a.pair_B > 0) a.x_out[e + pair] = v;     // (the twin exists under classifier-free guidance only)
             }
         }
     }
@@ -257,14 +261,21 @@ __global__ void ee_mean_combine_kernel(const float* __restrict__ s0, const float
 template <int CT, int PT>
 static void launch_final_cp(const FinalArgs& a, hipStream_t s) {
     const int tiles = (a.S + 15) / 16;
-    const dim3 grid(a.B * tiles * tiles);       // guided (pair_B > 0): a.B images, 2 a.B decoder images
+    const dim3 grid(a.B * tiles * tiles);       // guided (dec2 set): a.B images, each with a second decoder image
     auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, a); };
-    if (a.pair_B > 0) a.htab ? go(final_tiled_kernel<CT, PT, true, true>) : go(final_tiled_kernel<CT, PT, true, false>);
+    if (a.dec2) a.htab ? go(final_tiled_kernel<CT, PT, true, true>) : go(final_tiled_kernel<CT, PT, true, false>);
     else a.htab ? go(final_tiled_kernel<CT, PT, false, true>) : go(final_tiled_kernel<CT, PT, false, false>);
 }
 
-hipError_t launch_final(const FinalArgs& a, hipStream_t s) {
-    if (a.pair_B > 0 && (a.pair_B != a.B || a.layer_B > 0)) return hipErrorInvalidValue;
+hipError_t launch_final(const FinalArgs& args, hipStream_t s) {
+    FinalArgs a = args;
+    if (a.pair_B > 0) {   // classifier-free guidance: the second halo is image b + pair_B of the same decoder buffer, under the same conv
+        if (a.pair_B != a.B || a.layer_B > 0 || a.dec2) return hipErrorInvalidValue;
+        a.dec2 = a.dec + (long long)a.pair_B * a.L * a.P * a.P * a.C;
+        a.wconv2 = a.wconv; a.bconv2 = a.bconv; a.L2 = a.L; a.extras2 = a.extras;
+    } else if (a.dec2 && (a.layer_B > 0 || !a.wconv2 || !a.bconv2 || a.L2 - a.extras2 != a.L - a.extras)) {   // autoguidance: same patch grid
+        return hipErrorInvalidValue;
+    }
     // the multistep loop: a table-driven step that writes x and h
     if (a.htab && (!a.atab || !a.h || !a.x_in || !a.x_out || a.layer_B > 0)) return hipErrorInvalidValue;
     if (a.C == 3 && a.P == 4) launch_final_cp<3, 4>(a, s);

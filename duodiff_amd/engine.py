@@ -2,6 +2,7 @@
 reference-style state_dict.  torch tensors are containers for device memory and streams only.
 """
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -232,6 +233,17 @@ class Model:
                                                       _ptr(out), B, _stream_ptr(stream)))
         return out
 
+    def forward_autoguided(self, x, t, y, guide, scale, out=None, stream=None):
+        """Autoguided eps = eps_main + scale * (eps_main - eps_guide) at timestep t (dd_forward_autoguided): `guide` (a Model of the same
+        image geometry) and this model run the same B rows; y is required iff either model is class-conditional, and each model takes it
+        iff it is.  guide is this model itself: the plain forward."""
+        B = x.shape[0]
+        out = torch.empty_like(x) if out is None else out
+        g = L.dd_autoguidance(guide.handle, float(scale))
+        self.ctx.check(self.ctx.lib.dd_forward_autoguided(self.ctx.handle, self.handle, _ptr(x), float(t), _ptr(y), C.byref(g),
+                                                          _ptr(out), B, _stream_ptr(stream)))
+        return out
+
     def sample_step(self, x, t, y=None, z=None, noise="buffer", seed=0, variance="beta_tilde", eps_out=None,
                     stream=None):
         mode = {"none": L.DD_NOISE_NONE, "buffer": L.DD_NOISE_BUFFER, "philox": L.DD_NOISE_PHILOX}[noise]
@@ -285,6 +297,25 @@ def guidance_struct(guidance):
     return L.dd_guidance(float(scale), int(null_label))
 
 
+class Autoguidance(NamedTuple):
+    """A loop's `guidance` argument for autoguidance: every step of a model other than `guide` (a Model of the same image geometry) also
+    runs `guide` on the same rows and uses eps_main + scale * (eps_main - eps_guide); a step `guide` itself runs is the unguided step."""
+    guide: "Model"
+    scale: float
+
+
+def _loop_call(ctx, args, plain, guidance):
+    """The loop entry of this argument struct: `plain` (guidance None), its _guided form (guidance = (scale, null_label): classifier-free)
+    or its _autoguided form (guidance = Autoguidance(guide, scale)).  One argument: the C ABI has no entry that takes both."""
+    if guidance is None:
+        return lambda st: getattr(ctx.lib, plain)(ctx.handle, C.byref(args), st)
+    if isinstance(guidance, Autoguidance):
+        g, fn = L.dd_autoguidance(guidance.guide.handle, float(guidance.scale)), getattr(ctx.lib, plain + "_autoguided")
+    else:
+        g, fn = guidance_struct(guidance), getattr(ctx.lib, plain + "_guided")
+    return lambda st: fn(ctx.handle, C.byref(args), C.byref(g), st)
+
+
 def _run_loop(ctx: Context, args, x, y, seed, noise, use_graph, stream, call):
     """Fill the fields every loop's argument struct shares (x in place, y, the device noise) and run call(stream) on the caller's stream."""
     args.noise_mode = {"none": L.DD_NOISE_NONE, "philox": L.DD_NOISE_PHILOX}[noise]
@@ -310,18 +341,15 @@ def _run_loop(ctx: Context, args, x, y, seed, noise, use_graph, stream, call):
 def sample_loop(ctx: Context, first: Model, late, x, *, t_switch=0, t_start=999, t_end=0, y=None, seed=0,
                 noise="philox", variance="beta_tilde", use_graph=True, stream=None, guidance=None):
     """dd_sample: the whole DDPM loop on the device (hipGraph replay per backbone), in place on x.
-    guidance = (scale, null_label): classifier-free guidance (dd_sample_guided; labels y required, max_batch >= 2 B)."""
+    guidance = (scale, null_label): classifier-free guidance (dd_sample_guided; labels y required, max_batch >= 2 B);
+    guidance = Autoguidance(guide_model, scale): autoguidance (dd_sample_autoguided)."""
     args = L.dd_sample_args()
     args.first = first.handle
     args.late = late.handle if late is not None else None
     args.t_switch = int(t_switch) if t_switch and np.isfinite(t_switch) else 0
     args.t_start, args.t_end = int(t_start), int(t_end)
     args.variance = L.DD_VAR_BETA if variance == "beta" else L.DD_VAR_BETA_TILDE
-    if guidance is None:
-        call = lambda st: ctx.lib.dd_sample(ctx.handle, C.byref(args), st)
-    else:
-        g = guidance_struct(guidance)
-        call = lambda st: ctx.lib.dd_sample_guided(ctx.handle, C.byref(args), C.byref(g), st)
+    call = _loop_call(ctx, args, "dd_sample", guidance)
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
 
@@ -349,15 +377,12 @@ def sample_affine_loop(ctx: Context, first: Model, late, x, t, a, b, c, noise_fl
     x <- a[k] x + b[k] model(x, t[k]) + c[k] z for k = 0 .. len(t) - 1; the late model runs from step switch_after on.
     Step k draws z from Philox(key = seed, counter = counter_base + k): a loop cut into several calls passes the number
     of steps already done as counter_base and draws exactly the z of the uncut loop.
-    guidance = (scale, null_label): classifier-free guidance of the model output (dd_sample_affine_guided)."""
+    guidance = (scale, null_label): classifier-free guidance of the model output (dd_sample_affine_guided);
+    guidance = Autoguidance(guide_model, scale): autoguidance of it (dd_sample_affine_autoguided)."""
     args = L.dd_affine_sample_args()
     tab = _step_table(args, first, late, dict(t=t, a=a, b=b, c=c, noise=noise_flags), "tabc", ("noise",), switch_after,  # noqa: F841
                       counter_base)
-    if guidance is None:
-        call = lambda st: ctx.lib.dd_sample_affine(ctx.handle, C.byref(args), st)
-    else:
-        g = guidance_struct(guidance)
-        call = lambda st: ctx.lib.dd_sample_affine_guided(ctx.handle, C.byref(args), C.byref(g), st)
+    call = _loop_call(ctx, args, "dd_sample_affine", guidance)
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
 
@@ -367,16 +392,13 @@ def sample_multistep_loop(ctx: Context, first: Model, late, x, h, rows, *, switc
     x <- a[k] x + b[k] m_k [+ d[k] h if hist[k]] [+ c[k] z if noise[k]], h <- p[k] x + q[k] m_k for k = 0 .. len(t) - 1, m_k the
     model output at t[k].  rows: a dict with t, a, b, c, d, p, q, noise, hist (sampler.multistep_coefficients, or any slice of it).
     The late model runs from step switch_after on; Philox counters as sample_affine_loop.  A loop cut into several calls passes h on.
-    guidance = (scale, null_label): classifier-free guidance of the model output (dd_sample_multistep_guided)."""
+    guidance = (scale, null_label): classifier-free guidance of the model output (dd_sample_multistep_guided);
+    guidance = Autoguidance(guide_model, scale): autoguidance of it (dd_sample_multistep_autoguided)."""
     args = L.dd_multistep_sample_args()
     tab = _step_table(args, first, late, rows, "tabcdpq", ("noise", "hist"), switch_after, counter_base)  # noqa: F841
     assert h.is_cuda and h.dtype == torch.float32 and h.is_contiguous() and h.shape == x.shape
     args.h_dev = h.data_ptr()
-    if guidance is None:
-        call = lambda st: ctx.lib.dd_sample_multistep(ctx.handle, C.byref(args), st)
-    else:
-        g = guidance_struct(guidance)
-        call = lambda st: ctx.lib.dd_sample_multistep_guided(ctx.handle, C.byref(args), C.byref(g), st)
+    call = _loop_call(ctx, args, "dd_sample_multistep", guidance)
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
 

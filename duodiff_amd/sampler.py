@@ -18,6 +18,11 @@ Classifier-free guidance (engine option, not in the reference): ``--cfg_scale 0.
 model with eps = eps_c + s (eps_c - eps_u), the unconditional rows labelled ``--cfg_null_label`` (U-ViT's null class 1000), the
 combination fused into the step kernel of every loop.
 
+Autoguidance (engine option, not in the reference): ``--autoguidance_scale 1.0`` on a DuoDiff run (``--checkpoint_path_late``) guides
+every step of the full model with the shallow one, eps = eps_full + s (eps_full - eps_shallow), both backbones on the same rows and the
+combination fused into the step kernel; the shallow model's own steps stay unguided.  ``--guide_config_path`` / ``--guide_checkpoint_path``
+name an explicit guide for a single-backbone run.  No labels are needed: unconditional models can be guided.
+
 DPM-Solver++ (engine option, not in the reference): ``--dpm_solver ode --dpm_solver_steps 20`` samples with the second-order multistep
 solver (``sde``: its SDE variant) in 20 model evaluations; the table-driven loop with one history register per image.
 """
@@ -33,7 +38,7 @@ import torch
 
 from .config import ModelParams, load_config
 from .autoencoder import get_autoencoder
-from .engine import Context, sample_affine_loop, sample_loop, sample_multistep_loop, schedule_tables
+from .engine import Autoguidance, Context, sample_affine_loop, sample_loop, sample_multistep_loop, schedule_tables
 from .uvit import UViT
 
 
@@ -278,12 +283,16 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
                 ddim_eta: float = 0.0, timesteps_save: List[int] = (), y=None, autoencoder=None,
                 late_model=None, t_switch=np.inf, *, noise: str = "torch_cpu", use_graph: bool = True,
                 num_steps: int = 1000, return_device_tensor: bool = False, cfg_scale=None, cfg_null_label: int = 1000,
-                solver=None, solver_steps: int = 20, solver_order: int = 2):
+                solver=None, solver_steps: int = 20, solver_order: int = 2, autoguidance_scale=None, guide_model=None):
     """reference sampler.py:82-155.  Returns (samples[B,H,W,C] float32 numpy = (x+1)/2, intermediates).
 
     cfg_scale (None: the unguided loops, unchanged): classifier-free guidance of every step's model output,
         eps_c + cfg_scale * (eps_c - eps_u) with the unconditional rows labelled cfg_null_label; needs labels y.  The backbones run
         2 * batch_size rows (their max_batch grows to that).
+
+    autoguidance_scale (None: off; exclusive with cfg_scale): autoguidance of every step's model output with guide_model (a UViT of the
+        same image geometry; default: `model` when a late_model is given, the DuoDiff pair), eps_m + s * (eps_m - eps_guide).  A step
+        that guide_model itself runs is the unguided step.  Labels y go to whichever models are class-conditional.
 
     noise="torch_cpu": x_T and every z come from the torch CPU generator after seed_everything(seed),
         in the reference's order -> identical random numbers to a CPU reference run.
@@ -297,6 +306,17 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
     """
     if noise not in ("torch_cpu", "device"):
         raise ValueError("noise must be 'torch_cpu' or 'device'")
+    if autoguidance_scale is not None:
+        if cfg_scale is not None:
+            raise ValueError("classifier-free guidance and autoguidance are exclusive")
+        if not math.isfinite(float(autoguidance_scale)):
+            raise ValueError("autoguidance_scale must be finite")
+        if guide_model is None:
+            guide_model = model if late_model is not None else None
+        if guide_model is None:
+            raise ValueError("autoguidance needs a guide model: pass guide_model, or a late_model (the first model then guides it)")
+    elif guide_model is not None:
+        raise ValueError("guide_model without autoguidance_scale")
     plan = step_plan(_PARAMETRIZATIONS.get(postprocessing), timesteps_save, late_model is not None, t_switch, num_steps, use_ddim,
                      ddim_steps, ddim_eta, solver, solver_steps, solver_order)
     device = model.device
@@ -311,6 +331,10 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
     first = model.engine_model(rows)
     late = late_model.engine_model(rows) if late_model is not None else None
     ctx = first.ctx
+    guide = None
+    if autoguidance_scale is not None:
+        guide = first if guide_model is model else late if guide_model is late_model else guide_model.engine_model(rows)
+    autoguidance = None if guide is None else Autoguidance(guide, float(autoguidance_scale))
     tab, n = plan.rows, len(plan.rows["t"])
     h = torch.zeros_like(x) if plan.kind == "multistep" else None          # the solver's history, carried across save points
     intermediate = []
@@ -319,7 +343,7 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
         # step's index as the Philox counter base: the final samples do not depend on where the loop is cut.
         for k0, k1 in _segments(plan.save_after):
             sw = None if plan.switch_after is None else min(max(plan.switch_after - k0, 0), k1 - k0)
-            kw = dict(y=y, seed=seed, noise="philox", use_graph=use_graph, guidance=guidance)
+            kw = dict(y=y, seed=seed, noise="philox", use_graph=use_graph, guidance=autoguidance or guidance)
             if plan.kind == "ddpm":                                          # dd_sample counts t_switch from t = 999, as switch_after
                 sample_loop(ctx, late if sw == 0 else first, None if sw == 0 else late, x, t_switch=plan.switch_after if sw else 0,
                             t_start=int(tab["t"][k0]), t_end=int(tab["t"][k1 - 1]), **kw)
@@ -340,13 +364,16 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
                 cur = late
             t = tab["t"][k]
             z = torch.randn(x.shape).to(device) if tab["noise"][k] else None  # randn_like on the torch CPU stream (:52, :67, :119)
-            if plan.kind == "ddpm" and guidance is None:
-                cur.sample_step(x, int(t), y=y, z=z, noise="buffer")          # :130-133, fused
+            y_cur = y if guide is None or cur.mp.num_classes > 0 else None    # (autoguidance: y may be there for the other model only)
+            if plan.kind == "ddpm" and guidance is None and (guide is None or guide is cur):
+                cur.sample_step(x, int(t), y=y_cur, z=z, noise="buffer")      # :130-133, fused
             else:
-                if guidance is None:
-                    cur.forward(x, float(t), y, out=eps)
-                else:
+                if guidance is not None:
                     cur.forward_guided(x, float(t), y, guidance[0], guidance[1], out=eps)
+                elif guide is not None:
+                    cur.forward_autoguided(x, float(t), y, guide, autoguidance.scale, out=eps)
+                else:
+                    cur.forward(x, float(t), y, out=eps)
                 if plan.kind == "ddpm":
                     ctx.ddpm_step(x, eps, z, int(t), out=x)
                 elif plan.kind == "affine":
@@ -398,6 +425,34 @@ def validate_guidance(args, num_classes: int, num_classes_late=None):
             raise ValueError("--cfg_scale must be finite")
         if args.class_id is None and args.class_label is None:
             raise ValueError("--cfg_scale needs class labels: --class_id or --class_label")
+
+
+def validate_autoguidance(args, config, config_late=None, config_guide=None):
+    """The autoguidance options against the YAML configs (the first, the late and the explicit guide's model_params), before any GPU
+    work: ValueError on a bad combination."""
+    explicit = args.guide_config_path is not None or args.guide_checkpoint_path is not None
+    if args.autoguidance_scale is None:
+        if explicit:
+            raise ValueError("--guide_config_path / --guide_checkpoint_path need --autoguidance_scale")
+        return
+    if not math.isfinite(args.autoguidance_scale):
+        raise ValueError("--autoguidance_scale must be finite")
+    if args.cfg_scale is not None:
+        raise ValueError("--autoguidance_scale and --cfg_scale are exclusive")
+    if explicit and (args.guide_config_path is None or args.guide_checkpoint_path is None):
+        raise ValueError("an explicit guide needs both --guide_config_path and --guide_checkpoint_path")
+    if not explicit and config_late is None:
+        raise ValueError("--autoguidance_scale needs a guide: --checkpoint_path_late (the first model then guides the late one) or "
+                         "--guide_config_path / --guide_checkpoint_path")
+    guide = ModelParams.from_dict(config_guide if explicit else config)
+    for name, cfg in (("--config_path", config), ("--config_path_late", config_late)):
+        if cfg is None:
+            continue
+        mp = ModelParams.from_dict(cfg)
+        if (mp.img_size, mp.patch_size, mp.in_chans) != (guide.img_size, guide.patch_size, guide.in_chans):
+            raise ValueError(f"autoguidance: the guide's image geometry (img_size, patch_size, in_chans) = "
+                             f"{(guide.img_size, guide.patch_size, guide.in_chans)} differs from {name}'s "
+                             f"{(mp.img_size, mp.patch_size, mp.in_chans)}")
 
 
 SOLVERS = {"ode": "dpmsolver++", "sde": "sde-dpmsolver++"}
@@ -489,6 +544,13 @@ def get_args(argv=None):
                         "--class_id; an image whose drawn --class_id label equals the null label is sampled unguided")
     p.add_argument("--cfg_null_label", type=int, default=1000,
                    help="(engine option) label of the unconditional rows (default 1000: U-ViT's null class)")
+    p.add_argument("--autoguidance_scale", type=float, default=None,
+                   help="(engine option) autoguidance eps = eps_m + S (eps_m - eps_guide): every step of a model other than the guide runs "
+                        "the guide on the same rows; any value, 0 included, selects it (default: off).  Without an explicit guide the first "
+                        "(shallow) model guides the late one and --checkpoint_path_late is required.  Exclusive with --cfg_scale")
+    p.add_argument("--guide_config_path", type=str, default=None,
+                   help="(engine option) yaml config of an explicit guide model (same img_size, patch_size, in_chans)")
+    p.add_argument("--guide_checkpoint_path", type=str, default=None, help="(engine option) checkpoint of the explicit guide model")
     p.add_argument("--dpm_solver", choices=sorted(SOLVERS), default=None,
                    help="(engine option) DPM-Solver++ multistep sampling: ode = DPM-Solver++(2M), sde = SDE-DPM-Solver++(2M) "
                         "(default: the reference's loops).  Exclusive with --use_ddim; predict_noise / predict_original models")
@@ -522,12 +584,18 @@ def main(argv=None):
     config_late = load_config(args.config_path_late) if args.checkpoint_path_late else None
     validate_guidance(args, ModelParams.from_dict(config).num_classes,
                       ModelParams.from_dict(config_late).num_classes if config_late is not None else None)
+    config_guide = load_config(args.guide_config_path) if args.guide_config_path else None
+    validate_autoguidance(args, config, config_late, config_guide)
     rows = 2 * args.batch_size if args.cfg_scale is not None else args.batch_size
     model, mp = build_model(config, args.checkpoint_path, args.precision, rows)
     model_late = None
     if config_late is not None:
         config = config_late
         model_late, _ = build_model(config, args.checkpoint_path_late, args.precision, rows)
+
+    model_guide = None
+    if config_guide is not None:
+        model_guide, _ = build_model(config_guide, args.guide_checkpoint_path, args.precision, rows)
 
     seed_everything(args.seed)
     y = labels_from_args(args, args.batch_size, mp.num_classes)
@@ -542,7 +610,8 @@ def main(argv=None):
                                  use_ddim=args.use_ddim, ddim_steps=args.ddim_steps, ddim_eta=args.ddim_eta,
                                  y=y, autoencoder=autoencoder, late_model=model_late, t_switch=args.t_switch,
                                  timesteps_save=args.timesteps_save, noise=args.noise, use_graph=not args.no_graph,
-                                 cfg_scale=args.cfg_scale, cfg_null_label=args.cfg_null_label, **solver_kwargs(args))
+                                 cfg_scale=args.cfg_scale, cfg_null_label=args.cfg_null_label, **solver_kwargs(args),
+                                 autoguidance_scale=args.autoguidance_scale, guide_model=model_guide)
     tac = time.time()
     dump_statistics(tac - tic, out, args.batch_size)
     if args.no_png:

@@ -102,6 +102,15 @@ class UViT:
             self._model = m
         return self._model
 
+    def forward_autoguided(self, x, t, y, guide, scale, out=None):
+        """eps_main + scale * (eps_main - eps_guide) at the common timestep t (engine option: dd_forward_autoguided): `guide` is the weaker
+        UViT of the same image geometry; y goes to whichever of the two models is class-conditional."""
+        x = x.to(self.device, torch.float32).contiguous()
+        B = x.shape[0]
+        if y is not None:
+            y = torch.as_tensor(y).to(self.device, torch.int64).contiguous()
+        return self.engine_model(B).forward_autoguided(x, float(t), y, guide.engine_model(B), scale, out=out)
+
     def __call__(self, x, timesteps, y=None):
         """eps = model(x, time_tensor, y) (reference models/uvit.py:351-383)."""
         self.calls += 1

@@ -276,6 +276,40 @@ typedef struct dd_multistep_sample_args {
 int dd_sample_multistep(dd_ctx* ctx, const dd_multistep_sample_args* args, void* stream);
 int dd_sample_multistep_guided(dd_ctx* ctx, const dd_multistep_sample_args* args, const dd_guidance* g, void* stream);
 
+/* ---- autoguidance (Karras et al. 2024): the main model guided by a weaker model of the same image geometry -------------- */
+/* A DuoDiff user holds the pair already: the full U-ViT and the independently trained shallow one.  An autoguided step runs the guide
+ * and then the main model on the SAME B rows of x at the same t (nothing is duplicated: B <= max_batch of each model is all that is
+ * needed), and the step's last kernel reads both decoder outputs and uses
+ *     eps = eps_main + scale * (eps_main - eps_guide)     in fp32, contraction off, in that order: d = eps_main - eps_guide;
+ *                                                         eps = eps_main + scale * d   (the rule of dd_guidance)
+ * It needs no labels, so unconditional models (CelebA, CIFAR-10) can be guided.  Each model receives labels if and only if it is
+ * class-conditional: y_dev is required when either model is conditional (an unconditional guide under a conditional main model simply
+ * gets none) and must be NULL when neither is.
+ * A step whose running model is the guide model itself (the same dd_model*) is the plain unguided step: the launches and the bits of
+ * dd_sample / dd_sample_affine / dd_sample_multistep.  So the DuoDiff call first = shallow, late = full, guide = shallow runs the first
+ * t_switch steps unguided -- x up to the switch is byte-identical to the unguided loop's -- and guides the rest with the model that
+ * is the "bad version" exactly there.  The guide's identity decides, not its weights: a second dd_model with the same weights goes through
+ * the two-model path (and yields the same bits, d being exactly 0).
+ * Philox ids, counters, counter_base and the history register h are exactly the unguided loop's (multistep: m in h' = p x + q m is the
+ * guided output, as with classifier-free guidance); scale 0 reproduces the unguided loop.  Two half-batch chains are decided on B rows,
+ * chain k running on each model's chain-k workspace; captured graphs are keyed on the guide and the bits of the scale.
+ * Embed width, depth, head count, num_classes, mlp_time_embed and precision may differ between the two models.
+ * Every entry returns DD_ERR_INVALID (with dd_last_error) before anything is enqueued when g or g->guide is NULL, the guide belongs to
+ * another context or is not finalized, img_size / patch_size / in_chans differ between the guide and first or late, any of the models
+ * carries early-exit heads, scale is not finite, B is outside a model's max_batch, labels are missing or superfluous under the rule
+ * above, or (the loops) the noise mode is host noise.  There is no entry point that takes a dd_guidance as well. */
+typedef struct dd_autoguidance {
+    dd_model* guide;        /* the weaker model; same context, finalized */
+    float scale;            /* d = eps_main - eps_guide; eps = eps_main + scale * d, fp32, in that order */
+} dd_autoguidance;
+/* x_dev [B,C,S,S], y_dev [B] int64 or NULL (rule above), eps_dev [B,C,S,S]: the autoguided eps at timestep t (host-noise loops, parity) */
+int dd_forward_autoguided(dd_ctx* ctx, dd_model* m, const float* x_dev, float t, const int64_t* y_dev, const dd_autoguidance* g,
+                          float* eps_dev, int B, void* stream);
+/* dd_sample / dd_sample_affine / dd_sample_multistep with autoguidance */
+int dd_sample_autoguided(dd_ctx* ctx, const dd_sample_args* args, const dd_autoguidance* g, void* stream);
+int dd_sample_affine_autoguided(dd_ctx* ctx, const dd_affine_sample_args* args, const dd_autoguidance* g, void* stream);
+int dd_sample_multistep_autoguided(dd_ctx* ctx, const dd_multistep_sample_args* args, const dd_autoguidance* g, void* stream);
+
 /* The early-exit baseline's loop (reference eesampler.py:40-89) as a device-resident loop: per step EarlyExitUViT.forward
  * (all heads and probes), the per-sample exit selection with the global threshold, the DDPM update (sigma^2 = beta-tilde)
  * with the selected output; row t of err_dev [1000, depth] (batch-mean predicted error per layer, :70) and of idx_dev

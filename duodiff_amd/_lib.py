@@ -58,6 +58,11 @@ class dd_autoguidance(C.Structure):
     _fields_ = [("guide", C.c_void_p), ("scale", C.c_float)]
 
 
+class dd_known_region(C.Structure):
+    """a known region: x' is finished as m * (ka x0 + kb z2) + (1 - m) x' from the known image x0, the mask m and per-step rows ka, kb"""
+    _fields_ = [("x0_dev", C.c_void_p), ("mask_dev", C.c_void_p), ("ka", C.POINTER(C.c_float)), ("kb", C.POINTER(C.c_float))]
+
+
 class dd_ee_sample_args(C.Structure):
     _fields_ = [("model", C.c_void_p), ("threshold", C.c_float), ("t_start", C.c_int32), ("t_end", C.c_int32),
                 ("noise_mode", C.c_int32), ("use_graph", C.c_int32), ("B", C.c_int32), ("seed", C.c_uint64),
@@ -109,6 +114,13 @@ SIGNATURES = {
     "dd_sample_autoguided": (C.c_int, [C.c_void_p, C.POINTER(dd_sample_args), C.POINTER(dd_autoguidance), C.c_void_p]),
     "dd_sample_affine_autoguided": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.POINTER(dd_autoguidance), C.c_void_p]),
     "dd_sample_multistep_autoguided": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_autoguidance), C.c_void_p]),
+    "dd_known_blend": (C.c_int, [C.c_void_p] * 5 + [C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "dd_sample_region": (C.c_int, [C.c_void_p, C.POINTER(dd_sample_args), C.POINTER(dd_guidance), C.POINTER(dd_autoguidance),
+                                   C.POINTER(dd_known_region), C.c_void_p]),
+    "dd_sample_affine_region": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.POINTER(dd_guidance), C.POINTER(dd_autoguidance),
+                                          C.POINTER(dd_known_region), C.c_void_p]),
+    "dd_sample_multistep_region": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_guidance),
+                                             C.POINTER(dd_autoguidance), C.POINTER(dd_known_region), C.c_void_p]),
     "dd_bench_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
     "dd_vae_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "dd_vae_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),

@@ -62,6 +62,12 @@ struct dd_ctx {
     std::vector<HistRow> htab_host;
     float* h_stage = nullptr;
     size_t h_stage_elems = 0;
+    // the *_region loops: the known-region half of the rows, and the known image and mask the loop reads (x0 [B, C, S, S] | mask [B, 1, S, S], staged like x)
+    KnownRow* ktab = nullptr;
+    size_t ktab_rows = 0;
+    std::vector<KnownRow> ktab_host;
+    float* k_stage = nullptr;
+    size_t k_stage_elems = 0;
     int prof_kind = 0;           // dd_profile_select: which launches dd_profile_steps brackets (DD_PROF_*)
     unsigned dev_flags = 0;      // dd_dev_set_flags (include/duodiff_dev.h): kernel-variant switches of the development harness
 };
@@ -97,10 +103,11 @@ struct GraphKey {
     unsigned gscale = 0;                                             //   and the bits of the scale (+0 and -0 round differently)
     const void* aguide = nullptr;                                    // autoguidance: the guide model of a two-model step (null: CFG / unguided; gscale: the scale's bits)
     unsigned long long aserial = 0;                                  //   and its serial: an address can come back with another model behind it
+    const void *kx0 = nullptr, *kmask = nullptr, *ktab = nullptr;    // known region: the chain's staged x0 / mask and the rows (null: none)
     bool operator==(const GraphKey& o) const {
         return x == o.x && y == o.y && B == o.B && noise == o.noise && variance == o.variance && num_cus == o.num_cus &&
                atab == o.atab && aux0 == o.aux0 && aux1 == o.aux1 && thr == o.thr && b0 == o.b0 && gnull == o.gnull && gscale == o.gscale &&
-               aguide == o.aguide && aserial == o.aserial;
+               aguide == o.aguide && aserial == o.aserial && kx0 == o.kx0 && kmask == o.kmask && ktab == o.ktab;
     }
     void guide(const dd_guidance* g) {
         if (g) { gnull = g->null_label; gscale = __builtin_bit_cast(unsigned, g->scale); }
@@ -493,6 +500,18 @@ struct Chain {
     bool ee_fork;
 };
 Chain whole_batch(dd_ctx* c, dd_model* m) { return Chain{&m->ws[0], c->st[0], c->num_cus, true}; }
+
+// A loop's known region as a step sees it: the context's staged known image and mask at the step's first image, and the device rows
+struct Known {
+    const float* x0;
+    const float* mask;
+    const KnownRow* ktab;
+    Known at(int b0, const dd_model* m) const {      // a chain's share: images [b0, ...)
+        const size_t hw = (size_t)m->cfg.img_size * m->cfg.img_size;
+        return Known{x0 + (size_t)b0 * hw * m->cfg.in_chans, mask + (size_t)b0 * hw, ktab};
+    }
+    void key(GraphKey& k) const { k.kx0 = x0; k.kmask = mask; k.ktab = ktab; }
+};
 
 // the output head's arguments that the model and the chain determine, for B images whose decoder rows are in dec; a call site sets the rest by name
 FinalArgs final_args(const dd_model* m, const Chain& ch, const float* dec, const float* wconv, const float* bconv, int B) {
@@ -909,9 +928,11 @@ int run_guide(dd_ctx* c, dd_model* m, const Chain& ch, const dd_autoguidance* ag
 // g != null (classifier-free guidance): B images, the backbone runs the 2 B rows [x | x] with labels [y | null] (stage_guided's layout)
 // htab != null (the multistep loop, atab set): the update adds row k's history term and writes h' to h [B, C, S, S]
 // ag != null (autoguidance; never with g): each model takes y_dev iff it is class-conditional; m != ag->guide: the guide runs the same B rows first
+// kn != null (a *_region loop): the known region of these B images finishes x'
 int enqueue_step(dd_ctx* c, dd_model* m, const Chain& ch, float* x_dev, const int64_t* y_dev, int noise_mode, const float* z_dev,
                  int variance, float* eps_out, int B, hipStream_t s, int advance = 0, const AffineRow* atab = nullptr, int b0 = 0,
-                 const dd_guidance* g = nullptr, const HistRow* htab = nullptr, float* h = nullptr, const dd_autoguidance* ag = nullptr) {
+                 const dd_guidance* g = nullptr, const HistRow* htab = nullptr, float* h = nullptr, const dd_autoguidance* ag = nullptr,
+                 const Known* kn = nullptr) {
     FinalArgs fa = final_args(m, ch, ch.ws->dec, m->head.wconv, m->head.bconv, B);
     int rc = DD_OK;
     if (ag && ag->guide != m && (rc = run_guide(c, m, ch, ag, x_dev, y_dev, B, s, fa))) return rc;
@@ -923,6 +944,7 @@ int enqueue_step(dd_ctx* c, dd_model* m, const Chain& ch, float* x_dev, const in
     if (g) { fa.pair_B = B; fa.guide_scale = g->scale; }
     fa.htab = htab;
     fa.h = h;
+    if (kn) { fa.kx0 = kn->x0; fa.kmask = kn->mask; fa.ktab = kn->ktab; }
     DD_HIP(c, launch_final(fa, s));
     return DD_OK;
 }
@@ -1318,6 +1340,8 @@ void dd_ctx_destroy(dd_ctx* c) {
     if (c->atab) (void)hipFree(c->atab);
     if (c->htab) (void)hipFree(c->htab);
     if (c->h_stage) (void)hipFree(c->h_stage);
+    if (c->ktab) (void)hipFree(c->ktab);
+    if (c->k_stage) (void)hipFree(c->k_stage);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     delete c;
 }
@@ -1551,6 +1575,16 @@ int dd_multistep_step(dd_ctx* c, const float* x_dev, const float* m_dev, const f
     return DD_OK;
 }
 
+int dd_known_blend(dd_ctx* c, const float* x_dev, const float* x0_dev, const float* mask_dev, const float* z2_dev, float ka, float kb,
+                   float* out_dev, int B, int C, int S, void* stream) {
+    if (!c) return DD_ERR_INVALID;
+    if (!x_dev || !x0_dev || !mask_dev || !out_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    if (B < 0 || C < 1 || S < 1) return ctx_fail(c, DD_ERR_INVALID, "bad image shape");
+    if (B == 0) return DD_OK;
+    DD_HIP(c, launch_known_blend(x_dev, x0_dev, mask_dev, z2_dev, ka, kb, out_dev, B, C, S, (hipStream_t)stream));
+    return DD_OK;
+}
+
 int dd_to_images(dd_ctx* c, const float* x_dev, float* images_dev, int B, int C, int S, void* stream) {
     if (!c) return DD_ERR_INVALID;
     if (!x_dev || !images_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
@@ -1595,9 +1629,56 @@ int dd_sample_step(dd_ctx* c, dd_model* m, float* x_dev, int t, const int64_t* y
 }  // extern "C"
 
 namespace {
+// What a *_region entry checks beyond the loop's own checks (include/duodiff.h dd_known_region), before anything is enqueued
+int check_region(dd_ctx* c, dd_model* first, dd_model* late, const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr,
+                 int noise_mode) {
+    if (!kr) return ctx_fail(c, DD_ERR_INVALID, "null dd_known_region");
+    if (!kr->x0_dev || !kr->mask_dev || !kr->ka || !kr->kb) return ctx_fail(c, DD_ERR_INVALID, "null member of dd_known_region");
+    if (g && ag) return ctx_fail(c, DD_ERR_INVALID, "classifier-free guidance and autoguidance are exclusive");
+    if (noise_mode == DD_NOISE_BUFFER)
+        return ctx_fail(c, DD_ERR_INVALID, "a known region draws its noise on the device; for host noise drive dd_forward, the step and dd_known_blend");
+    for (dd_model* m : {first, late})
+        if (m && m->ctx == c && m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, "a known region is not supported for early-exit models");
+    return DD_OK;
+}
+
+// The known region of a checked *_region call on the device: x0 | mask copied into the context's k_stage (a later call with other tensors of
+// the same shape replays the same graphs, as with x / y / h) and `rows` rows uploaded, row(i) each.
+int stage_known(dd_ctx* c, const dd_known_region* kr, const dd_model* m, int B, size_t rows, const std::function<KnownRow(size_t)>& row,
+                hipStream_t s, Known* out) {
+    const size_t hw = (size_t)m->cfg.img_size * m->cfg.img_size, x_elems = (size_t)B * hw * m->cfg.in_chans, m_elems = (size_t)B * hw;
+    if (c->k_stage_elems < x_elems + m_elems) {       // grows only: graphs keyed on the old address are re-captured once
+        if (c->k_stage) (void)hipFree(c->k_stage);
+        c->k_stage = nullptr; c->k_stage_elems = 0;
+        DD_HIP(c, hipMalloc((void**)&c->k_stage, (x_elems + m_elems) * sizeof(float)));
+        c->k_stage_elems = x_elems + m_elems;
+    }
+    if (c->ktab_rows < rows) {
+        if (c->ktab) (void)hipFree(c->ktab);
+        c->ktab = nullptr; c->ktab_rows = 0;
+        DD_HIP(c, hipMalloc((void**)&c->ktab, rows * sizeof(KnownRow)));
+        c->ktab_rows = rows;
+    }
+    DD_HIP(c, hipStreamSynchronize(s));            // a previous call's upload may still read the host staging copy
+    c->ktab_host.resize(rows);
+    for (size_t i = 0; i < rows; ++i) c->ktab_host[i] = row(i);
+    DD_HIP(c, hipMemcpyAsync(c->ktab, c->ktab_host.data(), rows * sizeof(KnownRow), hipMemcpyHostToDevice, s));
+    DD_HIP(c, hipMemcpyAsync(c->k_stage, kr->x0_dev, x_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    DD_HIP(c, hipMemcpyAsync(c->k_stage + x_elems, kr->mask_dev, m_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    *out = Known{c->k_stage, c->k_stage + x_elems, c->ktab};
+    return DD_OK;
+}
+// the rows of a table-driven loop of n steps: row k beside AffineRow k, one more (never used) as there
+std::function<KnownRow(size_t)> table_known_row(const dd_known_region* kr, int n) {
+    return [kr, n](size_t k) { return k < (size_t)n ? KnownRow{kr->ka[k], kr->kb[k]} : KnownRow{0.f, 0.f}; };
+}
+
 // dd_sample (g == nullptr, ag == nullptr), dd_sample_guided (g) and dd_sample_autoguided (ag): one path
-int sample_ddpm(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* stream, const dd_autoguidance* ag = nullptr) {
+int sample_ddpm(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* stream, const dd_autoguidance* ag = nullptr,
+                const dd_known_region* kr = nullptr, bool region = false) {
     if (!c || !a) return DD_ERR_INVALID;
+    if (region)
+        if (int rc0 = check_region(c, a->first, a->late, g, ag, kr, a->noise_mode)) return rc0;
     auto check = [&](dd_model* m) { return g ? check_guided(c, m, a->B, a->y_dev, g) : check_call(c, m, a->B, a->y_dev); };
     int rc = ag ? check_autoguided(c, a->first, a->late, a->B, a->y_dev, ag) : check(a->first);
     if (rc) return rc;
@@ -1613,12 +1694,23 @@ int sample_ddpm(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* 
     const bool switching = a->late && a->t_switch > 0 && a->t_switch <= 1000;
     const int t_sw = 1000 - a->t_switch;  // the late model takes over AFTER this step (sampler.py:135-136)
     const bool switch_here = switching && t_sw <= a->t_start && t_sw >= a->t_end;
+    Known kn{};
+    if (kr) {      // the rows by timestep, as the DDPM rule reads its own: row k of the call is the step at t_start - k
+        const int t0 = a->t_start, n = a->t_start - a->t_end + 1;
+        auto row = [&](size_t t) { const long long k = t0 - (long long)t; return k >= 0 && k < n ? KnownRow{kr->ka[k], kr->kb[k]} : KnownRow{0.f, 0.f}; };
+        if ((rc = stage_known(c, kr, a->first, a->B, 1000, row, (hipStream_t)stream, &kn))) return rc;
+    }
     Loop L{GRAPH_DDPM, a->first, switching ? a->late : nullptr, a->t_start - a->t_end + 1, switch_here ? a->t_start - t_sw + 1 : -1,
            a->x_dev, a->y_dev, a->B, g, a->use_graph != 0};
     L.set_state = [&](StepState* st, hipStream_t s) { return launch_set_state(st, a->t_start, (unsigned long long)a->seed, s); };
-    L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.variance = a->variance; };
+    L.key = [&](GraphKey& k, const Slice& sl) {
+        k.noise = a->noise_mode; k.variance = a->variance;
+        if (kr) kn.at(sl.b0, a->first).key(k);
+    };
     L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t s) {
-        return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, a->variance, nullptr, sl.B, s, 1, nullptr, sl.b0, g, nullptr, nullptr, ag);
+        const Known ks = kr ? kn.at(sl.b0, m) : kn;
+        return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, a->variance, nullptr, sl.B, s, 1, nullptr, sl.b0, g, nullptr, nullptr, ag,
+                            kr ? &ks : nullptr);
     };
     L.ag = ag;
     return run_loop(c, L, (hipStream_t)stream);
@@ -1660,21 +1752,31 @@ int check_table_loop(dd_ctx* c, const Args* a, const dd_guidance* g, const dd_au
 }
 
 // dd_sample_affine (g == nullptr, ag == nullptr), dd_sample_affine_guided (g) and dd_sample_affine_autoguided (ag): one path
-int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, void* stream, const dd_autoguidance* ag = nullptr) {
+int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, void* stream, const dd_autoguidance* ag = nullptr,
+                  const dd_known_region* kr = nullptr, bool region = false) {
     if (!c || !a) return DD_ERR_INVALID;
+    if (region)
+        if (int rc0 = check_region(c, a->first, a->late, g, ag, kr, a->noise_mode)) return rc0;
     int rc = check_table_loop(c, a, g, ag, "dd_sample_affine generates noise on the device; for host noise drive dd_forward + dd_affine_step");
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int n = a->n_steps;
     const bool switching = a->late && a->switch_after >= 0 && a->switch_after < n;
     if ((rc = upload_atab(c, n, a->t, a->a, a->b, a->c, a->noise, a->counter_base, s))) return rc;
+    Known kn{};
+    if (kr && (rc = stage_known(c, kr, a->first, a->B, (size_t)n + 1, table_known_row(kr, n), s, &kn))) return rc;
     // (two half-batch chains, as dd_sample: both read the one step table; each has its own step index and Philox image offset)
     Loop L{GRAPH_AFFINE, a->first, switching ? a->late : nullptr, n, switching ? a->switch_after : -1, a->x_dev, a->y_dev, a->B, g,
            a->use_graph != 0};
     L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_table(st, c->atab, (unsigned long long)a->seed, ss); };
-    L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.atab = c->atab; };
+    L.key = [&](GraphKey& k, const Slice& sl) {
+        k.noise = a->noise_mode; k.atab = c->atab;
+        if (kr) kn.at(sl.b0, a->first).key(k);
+    };
     L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
-        return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, 0, nullptr, sl.B, ss, 1, c->atab, sl.b0, g, nullptr, nullptr, ag);
+        const Known ks = kr ? kn.at(sl.b0, m) : kn;
+        return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, 0, nullptr, sl.B, ss, 1, c->atab, sl.b0, g, nullptr, nullptr, ag,
+                            kr ? &ks : nullptr);
     };
     L.ag = ag;
     return run_loop(c, L, s);
@@ -1683,8 +1785,11 @@ int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* 
 // dd_sample_multistep (g == nullptr) and dd_sample_multistep_guided: dd_sample_affine's loop with the history register.  h is staged
 // like x: copied into the context's h_stage before the loop, chain k's images at h_stage + o_k chw (guided too: h holds B images,
 // not 2 B), and copied back behind the join of the chains.
-int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, void* stream, const dd_autoguidance* ag = nullptr) {
+int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, void* stream, const dd_autoguidance* ag = nullptr,
+                     const dd_known_region* kr = nullptr, bool region = false) {
     if (!c || !a) return DD_ERR_INVALID;
+    if (region)
+        if (int rc0 = check_region(c, a->first, a->late, g, ag, kr, a->noise_mode)) return rc0;
     for (dd_model* m : {a->first, a->late})
         if (m && m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, "the multistep loop is not supported for early-exit models");
     int rc = check_table_loop(c, a, g, ag, "dd_sample_multistep generates noise on the device; for host noise drive dd_forward + dd_multistep_step");
@@ -1713,13 +1818,19 @@ int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guid
         c->h_stage_elems = h_elems;
     }
     DD_HIP(c, hipMemcpyAsync(c->h_stage, a->h_dev, h_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    Known kn{};
+    if (kr && (rc = stage_known(c, kr, a->first, a->B, (size_t)n + 1, table_known_row(kr, n), s, &kn))) return rc;
     Loop L{GRAPH_MULTISTEP, a->first, switching ? a->late : nullptr, n, switching ? a->switch_after : -1, a->x_dev, a->y_dev, a->B, g,
            a->use_graph != 0};
     L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_table(st, c->atab, (unsigned long long)a->seed, ss); };
-    L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.atab = c->atab; k.aux0 = c->htab; k.aux1 = c->h_stage; };
+    L.key = [&](GraphKey& k, const Slice& sl) {
+        k.noise = a->noise_mode; k.atab = c->atab; k.aux0 = c->htab; k.aux1 = c->h_stage;
+        if (kr) kn.at(sl.b0, a->first).key(k);
+    };
     L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
+        const Known ks = kr ? kn.at(sl.b0, m) : kn;
         return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, 0, nullptr, sl.B, ss, 1, c->atab, sl.b0, g, c->htab,
-                            c->h_stage + (size_t)sl.b0 * chw, ag);
+                            c->h_stage + (size_t)sl.b0 * chw, ag, kr ? &ks : nullptr);
     };
     L.ag = ag;
     L.tail = [&](int, hipStream_t ss) -> int {
@@ -1758,6 +1869,18 @@ int dd_sample_affine_autoguided(dd_ctx* c, const dd_affine_sample_args* a, const
 int dd_sample_multistep_autoguided(dd_ctx* c, const dd_multistep_sample_args* a, const dd_autoguidance* g, void* stream) {
     if (c && !g) return ctx_fail(c, DD_ERR_INVALID, "null dd_autoguidance");
     return sample_multistep(c, a, nullptr, stream, g);
+}
+
+int dd_sample_region(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr, void* stream) {
+    return sample_ddpm(c, a, g, stream, ag, kr, true);
+}
+int dd_sample_affine_region(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr,
+                            void* stream) {
+    return sample_affine(c, a, g, stream, ag, kr, true);
+}
+int dd_sample_multistep_region(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag,
+                               const dd_known_region* kr, void* stream) {
+    return sample_multistep(c, a, g, stream, ag, kr, true);
 }
 
 // One early-exit sampling step on the device (reference eesampler.py:56-81): EarlyExitUViT.forward with every head and

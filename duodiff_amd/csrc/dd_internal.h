@@ -60,6 +60,11 @@ struct HistRow {
     int hist;                     // 0: h does not enter the update at all (0 * NaN is NaN: the first step, a caller's uninitialised buffer)
 };
 
+// the known-region half of step k's row (dd_known_region): the known pixels land on ka x0 + kb z2
+struct KnownRow {
+    float ka, kb;
+};
+
 enum GemmEpilogue {
     EPI_STORE = 0,        // out = T(acc)                                  (qkv)
     EPI_BIAS_GELU = 1,    // out = T(gelu_erf(acc + bias))                 (fc1)
@@ -324,6 +329,12 @@ struct FinalArgs {
     const float* wconv2 = nullptr;
     const float* bconv2 = nullptr;
     int L2 = 0, extras2 = 0;
+    // known region (kx0 != null; x_out set, layer_B == 0): x' is finished by step_update.h known() before it is stored, from the known image
+    // kx0 [B, C, S, S], the mask kmask [B, 1, S, S] of this launch's B images and row t of ktab (the DDPM loop: 1000 rows by timestep; a
+    // table-driven loop: beside atab); z2 is a Philox draw of its own (noise_mode 2), no other noise mode adds one.  Guided, the twin gets x'' too.
+    const float* kx0 = nullptr;
+    const float* kmask = nullptr;
+    const KnownRow* ktab = nullptr;
 };
 hipError_t launch_final(const FinalArgs& a, hipStream_t s);
 
@@ -369,6 +380,9 @@ hipError_t launch_affine_step(const float* x, const float* m, const float* z, fl
 // out = a x + b m [+ d h if use_hist] [+ c z if z], h = p x + q m (read before it is written): the multistep row, elementwise
 hipError_t launch_multistep_step(const float* x, const float* m, const float* z, float* h, float* out, float a, float b, float c, float d,
                                  float p, float q, int use_hist, long long n, hipStream_t s);
+// out = known(x, x0, mask, ka, kb, z2) elementwise on [B, C, S, S] (mask [B, 1, S, S]; z2 null: none): the unfused known-region rule
+hipError_t launch_known_blend(const float* x, const float* x0, const float* mask, const float* z2, float ka, float kb, float* out, int B, int C,
+                              int S, hipStream_t s);
 // AttentionProbe operands of one layer (capi.hip finalize folds them): u [D], Wv^T [D, D], bv [D], W0^T [D, D], b0 [D], w2 [D], b2 [1]
 struct AttnProbeW { const float *u, *wvt, *bv, *w0t, *b0, *w2, *b2; };
 hipError_t launch_ee_attn_probe(const float* x, const AttnProbeW& w, float* out, int B, int L, int D, hipStream_t s);

@@ -27,8 +27,12 @@ namespace {
 // guided, the conditional image only); H = false compiles to the code without it.  The h pixels are requested with x_in, ahead of the halo
 // gather and without waiting for row t's hist flag (a load behind the step state -> row chain would hold the gather back); a step without
 // history loads them but never lets them into x', so a NaN in h (the first step, an uninitialised buffer) cannot reach the result.
+// K (known region, FinalArgs::kx0): x' is finished by known() of step_update.h in front of the x_out store.  The x0 and mask pixels are requested with
+// x_in for the same reason as h, row t of ktab rides behind the step state beside the rule's own row, and the second Philox draw (z2, its own
+// stream word) is issued beside the first: nothing is added to the chain of dependent round trips.  Guided, the twin image gets x'' too.
+// K = false compiles to the code without any of it.
 // ------------------------------------------------------------------------------------------
-template <int CT, int PT, bool G, bool H>
+template <int CT, int PT, bool G, bool H, bool K>
 __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
 #pragma clang fp contract(off)
     // (row pitch 48 = 16 mod 32 words: the two 16-pixel rows a 32-lane group reads fall into disjoint bank halves; pitch 19 gave every tap read
@@ -46,7 +50,10 @@ __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
     // the kernel is a chain of dependent memory round trips, not bandwidth.
     const StepRule<H> rule(a.st, a.coef, a.atab, a.htab, a.noise_mode, a.variance, a.advance);
     float xin[4] = {0.f, 0.f, 0.f, 0.f}, zin[4] = {0.f, 0.f, 0.f, 0.f}, hin[4] = {0.f, 0.f, 0.f, 0.f};
+    float kin[4] = {0.f, 0.f, 0.f, 0.f}, z2in[4] = {0.f, 0.f, 0.f, 0.f}, km = 0.f;
+    const KnownRule krule(K ? a.ktab : nullptr, rule.table, rule.t, a.noise_mode);
     if (inside && a.x_out) {
+        if constexpr (K) km = a.kmask[((long long)b * S + y) * S + x];
 #pragma unroll
         for (int co = 0; co < 4; ++co) {
             if (co < C) {
@@ -54,6 +61,7 @@ __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
                 xin[co] = a.x_in[e];
                 if (rule.reads_z()) zin[co] = a.z[e];
                 if constexpr (H) hin[co] = a.h[e];     // (not behind the row: used only where hr.hist is set)
+                if constexpr (K) kin[co] = a.kx0[e];
             }
         }
     }
@@ -74,6 +82,13 @@ __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
         const f32x4 zn = philox_normal4(a.st->seed, ((unsigned long long)(b + a.b0) * S + y) * S + x, rule.ctr);
 #pragma unroll
         for (int co = 0; co < 4; ++co) zin[co] = zn[co];
+    }
+    if constexpr (K) {
+        if (inside && a.x_out && krule.draws()) {   // z2: the same key, pixel id and counter as z, the known region's stream word
+            const f32x4 zn = philox_normal4(a.st->seed, ((unsigned long long)(b + a.b0) * S + y) * S + x, rule.ctr, PHILOX_KNOWN);
+#pragma unroll
+            for (int co = 0; co < 4; ++co) z2in[co] = zn[co];
+        }
     }
     __syncthreads();
     if (blockIdx.x == 0 && tid == 0) rule.advance(a.st);
@@ -117,13 +132,24 @@ __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
             const float eps = acc[0][co];
             if (a.eps_out) a.eps_out[e] = eps;
             if (a.x_out) {
-                const float v = rule.apply(xin[co], eps, zin[co], hin[co]);
+                float v = rule.apply(xin[co], eps, zin[co], hin[co]);
                 if constexpr (H) a.h[e] = rule.history(xin[co], eps);
+                if constexpr (K) v = krule.apply(v, kin[co], km, z2in[co]);
                 a.x_out[e] = v;
                 if (G && a.pair_B > 0) a.x_out[e + pair] = v;     // (the twin exists under classifier-free guidance only)
             }
         }
     }
+}
+
+// the unfused known-region rule on [B, C, S, S] (dd_known_blend): the mask is shared by a pixel's channels; x and out may alias
+__global__ void known_blend_kernel(const float* x, const float* __restrict__ x0, const float* __restrict__ mask, const float* __restrict__ z2,
+                                   float* out, float ka, float kb, long long chw, long long hw, long long n) {
+#pragma clang fp contract(off)
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool use_z2 = z2 != nullptr && kb != 0.f;
+    out[i] = known(x[i], x0[i], mask[(i / chw) * hw + i % hw], ka, kb, use_z2 ? z2[i] : 0.f, use_z2);
 }
 
 // the unfused update on n elements from coefficients passed by value (dd_ddpm_step / dd_ddpm_step_coef)
@@ -256,15 +282,20 @@ __global__ void ee_mean_combine_kernel(const float* __restrict__ s0, const float
 
 }  // namespace
 
-// one instantiation per (C, P) specialisation x guidance x history: (3, 4) CelebA-64 / ImageNet-64, (3, 2) CIFAR-10, (4, 2) 32 x 32 x 4
+// one instantiation per (C, P) specialisation x guidance x history x known region: (3, 4) CelebA-64 / ImageNet-64, (3, 2) CIFAR-10, (4, 2) 32 x 32 x 4
 // latents (ImageNet-256), anything else the run-time form
 template <int CT, int PT>
 static void launch_final_cp(const FinalArgs& a, hipStream_t s) {
     const int tiles = (a.S + 15) / 16;
     const dim3 grid(a.B * tiles * tiles);       // guided (dec2 set): a.B images, each with a second decoder image
     auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, a); };
-    if (a.dec2) a.htab ? go(final_tiled_kernel<CT, PT, true, true>) : go(final_tiled_kernel<CT, PT, true, false>);
-    else a.htab ? go(final_tiled_kernel<CT, PT, false, true>) : go(final_tiled_kernel<CT, PT, false, false>);
+    if (a.kx0) {
+        if (a.dec2) a.htab ? go(final_tiled_kernel<CT, PT, true, true, true>) : go(final_tiled_kernel<CT, PT, true, false, true>);
+        else a.htab ? go(final_tiled_kernel<CT, PT, false, true, true>) : go(final_tiled_kernel<CT, PT, false, false, true>);
+        return;
+    }
+    if (a.dec2) a.htab ? go(final_tiled_kernel<CT, PT, true, true, false>) : go(final_tiled_kernel<CT, PT, true, false, false>);
+    else a.htab ? go(final_tiled_kernel<CT, PT, false, true, false>) : go(final_tiled_kernel<CT, PT, false, false, false>);
 }
 
 hipError_t launch_final(const FinalArgs& args, hipStream_t s) {
@@ -278,6 +309,8 @@ hipError_t launch_final(const FinalArgs& args, hipStream_t s) {
     }
     // the multistep loop: a table-driven step that writes x and h
     if (a.htab && (!a.atab || !a.h || !a.x_in || !a.x_out || a.layer_B > 0)) return hipErrorInvalidValue;
+    // a known region finishes a step's x'
+    if (a.kx0 && (!a.kmask || !a.ktab || !a.x_in || !a.x_out || a.layer_B > 0)) return hipErrorInvalidValue;
     if (a.C == 3 && a.P == 4) launch_final_cp<3, 4>(a, s);
     else if (a.C == 3 && a.P == 2) launch_final_cp<3, 2>(a, s);
     else if (a.C == 4 && a.P == 2) launch_final_cp<4, 2>(a, s);
@@ -290,6 +323,13 @@ hipError_t launch_ddpm_step(const float* x, const float* eps, const float* z, fl
     // variance selection is folded by the caller into c.sigma_tilde
     hipLaunchKernelGGL(ddpm_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, eps, z, out, c,
                        use_noise, 0, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_known_blend(const float* x, const float* x0, const float* mask, const float* z2, float ka, float kb, float* out, int B, int C,
+                              int S, hipStream_t s) {
+    const long long hw = (long long)S * S, chw = hw * C, n = chw * B;
+    hipLaunchKernelGGL(known_blend_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, x0, mask, z2, out, ka, kb, chw, hw, n);
     return hipGetLastError();
 }
 

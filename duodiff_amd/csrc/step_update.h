@@ -10,7 +10,10 @@ namespace dd {
 // ------------------------------------------------------------------------------------------
 // Device noise: Philox4x32-10 counter RNG + Box-Muller.  Counter = (element/4, t, 0, 0),
 // key = seed.  Statistically N(0,1); NOT the torch CPU mt19937 stream (that is DD_NOISE_BUFFER).
+// The fourth counter word names the stream: PHILOX_STEP for the update's z, PHILOX_KNOWN for the z2 of a known region --
+// the same key, pixel and counter give two independent draws.
 // ------------------------------------------------------------------------------------------
+constexpr unsigned PHILOX_STEP = 0x5eedu, PHILOX_KNOWN = 0x6b6e6f77u;
 __device__ __forceinline__ void philox_round(unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3,
                                              unsigned k0, unsigned k1) {
     const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
@@ -20,8 +23,8 @@ __device__ __forceinline__ void philox_round(unsigned& c0, unsigned& c1, unsigne
 }
 
 // four N(0,1) values for one pixel (one per channel, C <= 4): counter = (pixel, t), key = seed
-__device__ __forceinline__ f32x4 philox_normal4(unsigned long long seed, unsigned long long pixel, int t) {
-    unsigned c0 = (unsigned)pixel, c1 = (unsigned)(pixel >> 32), c2 = (unsigned)t, c3 = 0x5eedu;
+__device__ __forceinline__ f32x4 philox_normal4(unsigned long long seed, unsigned long long pixel, int t, unsigned stream = PHILOX_STEP) {
+    unsigned c0 = (unsigned)pixel, c1 = (unsigned)(pixel >> 32), c2 = (unsigned)t, c3 = stream;
     unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
@@ -107,6 +110,29 @@ struct StepRule {
         st->t = tn;
         st->t_model = table ? t_next : (float)tn;
     }
+};
+
+// The known region of a step (inpainting, the RePaint replacement rule without resampling): after the step has produced x', a pixel
+// with mask m is finished from the known image x0 re-noised to the level the step lands on,
+//     kn = ka x0 [+ kb z2  if kb != 0 and a z2 is there]        x'' = x' if m == 0, else m kn + (1 - m) x'
+// each product rounded on its own, in that order.  m == 0 keeps x' bit for bit whatever x0 holds; m == 1 with finite x' gives kn
+// (kn + 0: the value, a -0 becoming +0).  h' of the multistep rule is none of its business.
+__device__ __forceinline__ float known(float xp, float x0, float m, float ka, float kb, float z2, bool use_z2) {
+#pragma clang fp contract(off)
+    if (m == 0.f) return xp;
+    float kn = ka * x0;
+    if (use_z2 && kb != 0.f) kn = kn + kb * z2;
+    return m * kn + (1.f - m) * xp;
+}
+// row t of a loop's known-region table (t as StepRule reads it: the timestep of the DDPM loop, the step index of a table-driven one),
+// loaded behind the step state like the rule's own row
+struct KnownRule {
+    KnownRow row;
+    bool philox;
+    __device__ __forceinline__ KnownRule(const KnownRow* ktab, bool table, int t, int noise_mode)
+        : row(ktab ? ktab[table ? t : (t < 0 ? 0 : (t > 999 ? 999 : t))] : KnownRow{0.f, 0.f}), philox(noise_mode == 2) {}   // (null: no known region)
+    __device__ __forceinline__ bool draws() const { return philox && row.kb != 0.f; }
+    __device__ __forceinline__ float apply(float xp, float x0, float m, float z2) const { return known(xp, x0, m, row.ka, row.kb, z2, philox); }
 };
 
 // eesampler.py:61-67: idx[b] = first layer i in [0, depth] with c[i][b] <= threshold, where c[depth][b] = 0 closes the

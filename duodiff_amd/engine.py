@@ -127,6 +127,18 @@ class Context:
                                               float(d), float(p), float(q), int(bool(use_hist)), _ptr(out), x.numel(), _stream_ptr(stream)))
         return out
 
+    def known_blend(self, x, x0, mask, z2, ka, kb, out=None, stream=None):
+        """The known-region rule on device tensors (dd_known_blend): kn = ka*x0 [+ kb*z2 if kb != 0 and z2 is not None];
+        out = x where mask == 0, else mask*kn + (1 - mask)*x.  x, x0 [B,C,S,S], mask [B,1,S,S]; out may be x."""
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[2] == x.shape[3]
+        B, Cc, S, _ = x.shape
+        for v, shape in ((x0, (B, Cc, S, S)), (mask, (B, 1, S, S))) + (((z2, (B, Cc, S, S)),) if z2 is not None else ()):
+            assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and tuple(v.shape) == shape
+        out = torch.empty_like(x) if out is None else out
+        self.check(self.lib.dd_known_blend(self.handle, _ptr(x), _ptr(x0), _ptr(mask), _ptr(z2), float(ka), float(kb), _ptr(out),
+                                           B, Cc, S, _stream_ptr(stream)))
+        return out
+
     def set_num_cus(self, n):
         """CU count this context's persistent GEMM grids are sized for (CU-masked streams)."""
         self.check(self.lib.dd_set_num_cus(self.handle, int(n)))
@@ -304,6 +316,34 @@ class Autoguidance(NamedTuple):
     scale: float
 
 
+class KnownRegion(NamedTuple):
+    """A loop's `region` argument: after every step, x' is finished as mask * (ka[k] x0 + kb[k] z2) + (1 - mask) x' (x' kept bit for bit
+    where mask == 0).  x0 [B,C,S,S] and mask [B,1,S,S] are fp32 device tensors, ka / kb one value per step of the call
+    (sampler.known_rows)."""
+    x0: torch.Tensor
+    mask: torch.Tensor
+    ka: np.ndarray
+    kb: np.ndarray
+
+
+def _region_call(ctx, args, plain, guidance, region, x, n_steps):
+    """The _region entry of `plain` (dd_known_region): either kind of guidance, or none, goes in beside the region"""
+    B, Cc, S, _ = x.shape
+    for v, shape in ((region.x0, (B, Cc, S, S)), (region.mask, (B, 1, S, S))):
+        assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and tuple(v.shape) == shape
+    ka, kb = (np.ascontiguousarray(v, np.float32) for v in (region.ka, region.kb))
+    assert ka.shape == kb.shape == (n_steps,)
+    kr = L.dd_known_region(region.x0.data_ptr(), region.mask.data_ptr(), ka.ctypes.data_as(C.POINTER(C.c_float)),
+                           kb.ctypes.data_as(C.POINTER(C.c_float)))
+    g = ag = None
+    if isinstance(guidance, Autoguidance):
+        ag = C.byref(L.dd_autoguidance(guidance.guide.handle, float(guidance.scale)))
+    elif guidance is not None:
+        g = C.byref(guidance_struct(guidance))
+    fn = getattr(ctx.lib, plain + "_region")
+    return lambda st, keep=(ka, kb): fn(ctx.handle, C.byref(args), g, ag, C.byref(kr), st)
+
+
 def _loop_call(ctx, args, plain, guidance):
     """The loop entry of this argument struct: `plain` (guidance None), its _guided form (guidance = (scale, null_label): classifier-free)
     or its _autoguided form (guidance = Autoguidance(guide, scale)).  One argument: the C ABI has no entry that takes both."""
@@ -343,13 +383,26 @@ def sample_loop(ctx: Context, first: Model, late, x, *, t_switch=0, t_start=999,
     """dd_sample: the whole DDPM loop on the device (hipGraph replay per backbone), in place on x.
     guidance = (scale, null_label): classifier-free guidance (dd_sample_guided; labels y required, max_batch >= 2 B);
     guidance = Autoguidance(guide_model, scale): autoguidance (dd_sample_autoguided)."""
+    return _sample_loop(ctx, first, late, x, None, t_switch, t_start, t_end, y, seed, noise, variance, use_graph, stream, guidance)
+
+
+def sample_region_loop(ctx: Context, first: Model, late, x, region: KnownRegion, *, t_switch=0, t_start=999, t_end=0, y=None, seed=0,
+                       noise="philox", variance="beta_tilde", use_graph=True, stream=None, guidance=None):
+    """dd_sample_region: sample_loop with a known region; region.ka / kb hold t_start - t_end + 1 rows, row k the step at t_start - k."""
+    return _sample_loop(ctx, first, late, x, region, t_switch, t_start, t_end, y, seed, noise, variance, use_graph, stream, guidance)
+
+
+def _sample_loop(ctx, first, late, x, region, t_switch, t_start, t_end, y, seed, noise, variance, use_graph, stream, guidance):
     args = L.dd_sample_args()
     args.first = first.handle
     args.late = late.handle if late is not None else None
     args.t_switch = int(t_switch) if t_switch and np.isfinite(t_switch) else 0
     args.t_start, args.t_end = int(t_start), int(t_end)
     args.variance = L.DD_VAR_BETA if variance == "beta" else L.DD_VAR_BETA_TILDE
-    call = _loop_call(ctx, args, "dd_sample", guidance)
+    if region is None:
+        call = _loop_call(ctx, args, "dd_sample", guidance)
+    else:
+        call = _region_call(ctx, args, "dd_sample", guidance, region, x, int(t_start) - int(t_end) + 1)
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
 
@@ -379,10 +432,26 @@ def sample_affine_loop(ctx: Context, first: Model, late, x, t, a, b, c, noise_fl
     of steps already done as counter_base and draws exactly the z of the uncut loop.
     guidance = (scale, null_label): classifier-free guidance of the model output (dd_sample_affine_guided);
     guidance = Autoguidance(guide_model, scale): autoguidance of it (dd_sample_affine_autoguided)."""
+    return _sample_affine_loop(ctx, first, late, x, None, t, a, b, c, noise_flags, switch_after, y, seed, counter_base, noise, use_graph,
+                               stream, guidance)
+
+
+def sample_affine_region_loop(ctx: Context, first: Model, late, x, region: KnownRegion, t, a, b, c, noise_flags, *, switch_after=None,
+                              y=None, seed=0, counter_base=0, noise="philox", use_graph=True, stream=None, guidance=None):
+    """dd_sample_affine_region: sample_affine_loop with a known region; region.ka / kb hold one row per step of the call."""
+    return _sample_affine_loop(ctx, first, late, x, region, t, a, b, c, noise_flags, switch_after, y, seed, counter_base, noise,
+                               use_graph, stream, guidance)
+
+
+def _sample_affine_loop(ctx, first, late, x, region, t, a, b, c, noise_flags, switch_after, y, seed, counter_base, noise, use_graph,
+                        stream, guidance):
     args = L.dd_affine_sample_args()
     tab = _step_table(args, first, late, dict(t=t, a=a, b=b, c=c, noise=noise_flags), "tabc", ("noise",), switch_after,  # noqa: F841
                       counter_base)
-    call = _loop_call(ctx, args, "dd_sample_affine", guidance)
+    if region is None:
+        call = _loop_call(ctx, args, "dd_sample_affine", guidance)
+    else:
+        call = _region_call(ctx, args, "dd_sample_affine", guidance, region, x, args.n_steps)
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
 
@@ -394,11 +463,27 @@ def sample_multistep_loop(ctx: Context, first: Model, late, x, h, rows, *, switc
     The late model runs from step switch_after on; Philox counters as sample_affine_loop.  A loop cut into several calls passes h on.
     guidance = (scale, null_label): classifier-free guidance of the model output (dd_sample_multistep_guided);
     guidance = Autoguidance(guide_model, scale): autoguidance of it (dd_sample_multistep_autoguided)."""
+    return _sample_multistep_loop(ctx, first, late, x, None, h, rows, switch_after, y, seed, counter_base, noise, use_graph, stream,
+                                  guidance)
+
+
+def sample_multistep_region_loop(ctx: Context, first: Model, late, x, region: KnownRegion, h, rows, *, switch_after=None, y=None,
+                                 seed=0, counter_base=0, noise="philox", use_graph=True, stream=None, guidance=None):
+    """dd_sample_multistep_region: sample_multistep_loop with a known region (h is not touched by it); region.ka / kb hold one row per
+    step of the call."""
+    return _sample_multistep_loop(ctx, first, late, x, region, h, rows, switch_after, y, seed, counter_base, noise, use_graph, stream,
+                                  guidance)
+
+
+def _sample_multistep_loop(ctx, first, late, x, region, h, rows, switch_after, y, seed, counter_base, noise, use_graph, stream, guidance):
     args = L.dd_multistep_sample_args()
     tab = _step_table(args, first, late, rows, "tabcdpq", ("noise", "hist"), switch_after, counter_base)  # noqa: F841
     assert h.is_cuda and h.dtype == torch.float32 and h.is_contiguous() and h.shape == x.shape
     args.h_dev = h.data_ptr()
-    call = _loop_call(ctx, args, "dd_sample_multistep", guidance)
+    if region is None:
+        call = _loop_call(ctx, args, "dd_sample_multistep", guidance)
+    else:
+        call = _region_call(ctx, args, "dd_sample_multistep", guidance, region, x, args.n_steps)
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
 

@@ -23,6 +23,10 @@ every step of the full model with the shallow one, eps = eps_full + s (eps_full 
 combination fused into the step kernel; the shallow model's own steps stay unguided.  ``--guide_config_path`` / ``--guide_checkpoint_path``
 name an explicit guide for a single-backbone run.  No labels are needed: unconditional models can be guided.
 
+Image-to-image and inpainting (engine options, not in the reference): ``--init_image x.npy --strength 0.5`` starts every loop from the
+given image noised to t = round(999 * 0.5) instead of from pure noise (SDEdit); ``--known_image x.npy --known_mask m.npy`` keeps the
+masked region of the image fixed while the rest is generated (RePaint's replacement rule without resampling), fused into the step kernel.
+
 DPM-Solver++ (engine option, not in the reference): ``--dpm_solver ode --dpm_solver_steps 20`` samples with the second-order multistep
 solver (``sde``: its SDE variant) in 20 model evaluations; the table-driven loop with one history register per image.
 """
@@ -38,7 +42,8 @@ import torch
 
 from .config import ModelParams, load_config
 from .autoencoder import get_autoencoder
-from .engine import Autoguidance, Context, sample_affine_loop, sample_loop, sample_multistep_loop, schedule_tables
+from .engine import (Autoguidance, Context, KnownRegion, sample_affine_loop, sample_affine_region_loop, sample_loop,
+                     sample_multistep_loop, sample_multistep_region_loop, sample_region_loop, schedule_tables)
 from .uvit import UViT
 
 
@@ -168,12 +173,15 @@ def multistep_rows(kind, alphas_bar, order=2, parametrization="predict_noise", l
     return rows
 
 
-def multistep_grid(n_steps):
-    """The integer timestep grid of an N-evaluation DPM-Solver++ run: N + 1 points from 999 down to 0; the model sees the first N."""
+def multistep_grid(n_steps, t0=999):
+    """The integer timestep grid of an N-evaluation DPM-Solver++ run: N + 1 points from t0 (999; lower: an image-to-image start) down
+    to 0; the model sees the first N."""
     n = int(n_steps)
     if not 1 <= n <= 999:
         raise ValueError(f"DPM-Solver++ steps must be in [1, 999], not {n}")
-    return np.linspace(999, 0, n + 1).round().astype(int)
+    if n > t0:
+        raise ValueError(f"{n} DPM-Solver++ steps do not fit a start at t = {t0}: lower the steps or raise the strength")
+    return np.linspace(t0, 0, n + 1).round().astype(int)
 
 
 def multistep_coefficients(kind, ts, order=2, parametrization="predict_noise"):
@@ -215,52 +223,93 @@ class StepPlan(NamedTuple):
     """What get_samples runs, step by step.  kind: "ddpm" (dd_sample / ddpm_step: the update follows from t), "affine" (rows a, b, c)
     or "multistep" (rows a, b, c, d, p, q, hist: multistep_coefficients).  rows: per-step arrays, always with t (the model timestep,
     float32) and noise (int32: the step draws z).  save_after[k]: x is saved after step k.  switch_after: the first step the late model
-    runs, or None; it may lie past the last step (a DDPM switch beyond num_steps), where it only hands the late model to dd_sample."""
+    runs, or None; it may lie past the last step (a DDPM switch beyond num_steps), where it only hands the late model to dd_sample.
+    lands[k]: the timestep whose noise level x has after step k, -1 for the final image (known_rows)."""
     kind: str
     rows: dict
     save_after: list
     switch_after: Optional[int]
+    lands: tuple = ()
 
 
 _PARAMETRIZATIONS = {predict_noise_postprocessing: "predict_noise", predict_original_postprocessing: "predict_original",
                      predict_previous_postprocessing: "predict_previous"}
 
 
+def start_timestep(strength=None):
+    """The timestep a loop starts at: 999, or round(999 * strength) for an image-to-image start of strength in (0, 1]."""
+    if strength is None:
+        return 999
+    if not (isinstance(strength, (int, float, np.number)) and 0 < float(strength) <= 1):
+        raise ValueError(f"strength must be in (0, 1], not {strength!r}")
+    return int(round(999 * float(strength)))
+
+
 def step_plan(parametrization, timesteps_save=(), has_late=False, t_switch=np.inf, num_steps=1000, use_ddim=False, ddim_steps=50,
-              ddim_eta=0.0, solver=None, solver_steps=20, solver_order=2):
+              ddim_eta=0.0, solver=None, solver_steps=20, solver_order=2, strength=None):
     """The StepPlan of get_samples' arguments (parametrization: "predict_noise" | "predict_original" | "predict_previous", or None
-    for a postprocessing function of elsewhere; has_late: a late model is given).  Host arithmetic only, no torch."""
+    for a postprocessing function of elsewhere; has_late: a late model is given).  Host arithmetic only, no torch.
+    strength (None or 1: the start at t = 999): the loops start at t0 = start_timestep(strength) -- DDPM at t0, the DDIM and solver grids
+    built from t0 down with the same spacing rule and step count; the late model's rule is unchanged (by timestep)."""
+    t0 = start_timestep(strength)
     # the DDPM loop switches AFTER the step at t == 1000 - t_switch (sampler.py:135-136): a t_switch outside [1, 1000] (0, negative,
     # > 1000, inf) never matches a t in 999..0, i.e. the first model runs every step
     in_range = has_late and np.isfinite(t_switch) and 1 <= int(t_switch) <= 1000
     if solver is not None:
         if use_ddim:
             raise ValueError("DPM-Solver++ and DDIM are exclusive")
-        grid = multistep_grid(solver_steps)                                   # range check first
+        grid = multistep_grid(solver_steps, t0)                               # range check first
         if parametrization is None:
             raise ValueError("postprocessing must be one of this module's predict_*_postprocessing functions")
         kind, rows = "multistep", multistep_coefficients(solver, grid, solver_order, parametrization)
         switch_after = next((k for k, t in enumerate(rows["t"]) if t < 1000 - int(t_switch)), None) if in_range else None
+        lands = [int(s) if s > 0 else -1 for s in grid[1:]]
     elif use_ddim:
         # reference sampler.py:103-126; z is drawn (:119) whenever s > 0, also at eta = 0
-        ts = np.linspace(0, 999, ddim_steps).astype(int)[::-1]
+        ts = np.linspace(0, t0, ddim_steps).astype(int)[::-1]
+        if (np.diff(ts) >= 0).any():
+            raise ValueError(f"{ddim_steps} DDIM steps do not fit a start at t = {t0}: lower the steps or raise the strength")
         pairs = [(int(t), int(s)) for t, s in zip(ts[:-1], ts[1:])]
         kind, rows = "affine", _affine_rows([t for t, _ in pairs], [affine_coefficients("ddim", t, s, ddim_eta) for t, s in pairs],
                                             [s > 0 for _, s in pairs])
         # :122-123: the late model from the step after the first t < 1000 - t_switch (raw t_switch: <= 0 switches after step 0)
         switch_after = next((k + 1 for k, (t, _) in enumerate(pairs) if t < 1000 - t_switch), None) if has_late else None
+        lands = [s if s > 0 else -1 for _, s in pairs]
     else:
         # sampler.py:129-139: t = 999 .. 1000 - num_steps; predict_original / predict_previous (:59-79) as affine rows
-        ts = list(range(999, 999 - int(num_steps), -1))
+        ts = list(range(t0, max(t0 - int(num_steps), -1), -1))
         if parametrization == "predict_noise":
             kind, rows = "ddpm", {"t": np.array(ts, np.float32), "noise": np.array([t > 0 for t in ts], np.int32)}
         elif parametrization in ("predict_original", "predict_previous"):
             kind, rows = "affine", _affine_rows(ts, [affine_coefficients(parametrization, t) for t in ts], [t > 0 for t in ts])
         else:
             raise ValueError("postprocessing must be one of this module's predict_*_postprocessing functions")
-        switch_after = int(t_switch) if in_range else None                    # the step after t == 1000 - t_switch
+        switch_after = max(int(t_switch) - (999 - t0), 0) if in_range else None   # the step after t == 1000 - t_switch
+        lands = [t - 1 for t in ts]
     saves = set(int(v) for v in timesteps_save)
-    return StepPlan(kind, rows, [(1000 - int(t)) in saves for t in rows["t"]], switch_after)
+    return StepPlan(kind, rows, [(1000 - int(t)) in saves for t in rows["t"]], switch_after, tuple(lands))
+
+
+def known_rows(plan):
+    """The known-region rows (ka, kb) of a plan, float32, one per step: a step that lands on timestep s puts its known pixels at
+    ka x0 + kb z2 with ka = sqrt(alphas_bar[s]), kb = sqrt(1 - alphas_bar[s]) from the engine's bit-exact tables, each rounded once;
+    a step that lands on the final image (the DDPM step at t = 0, the last DDIM pair, the solver grid's last point) has (1, 0), so the
+    known pixels of the result are x0 itself.  Host arithmetic only."""
+    ab = schedule_tables()["alphas_bar"].astype(np.float64)
+    s = np.asarray(plan.lands, np.int64)
+    final = s < 0
+    abs_ = ab[np.where(final, 0, s)]
+    ka = np.where(final, 1.0, np.sqrt(abs_)).astype(np.float32)
+    kb = np.where(final, 0.0, np.sqrt(1.0 - abs_)).astype(np.float32)
+    return ka, kb
+
+
+def _batch_tensor(v, name, batch_size, shape, device):
+    """An image argument of get_samples as a contiguous fp32 device tensor [B, *shape]; a leading 1 is repeated over the batch"""
+    t = torch.as_tensor(np.asarray(v.detach().cpu()) if isinstance(v, torch.Tensor) else np.asarray(v), dtype=torch.float32)
+    if t.dim() != 4 or t.shape[0] not in (1, batch_size) or tuple(t.shape[1:]) != tuple(shape):
+        raise ValueError(f"{name} must have shape [1 or {batch_size}, {', '.join(map(str, shape))}], not {list(t.shape)}")
+    return t.expand(batch_size, *shape).contiguous().to(device)
 
 
 def _affine_rows(ts, coefficients, noise):
@@ -283,7 +332,8 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
                 ddim_eta: float = 0.0, timesteps_save: List[int] = (), y=None, autoencoder=None,
                 late_model=None, t_switch=np.inf, *, noise: str = "torch_cpu", use_graph: bool = True,
                 num_steps: int = 1000, return_device_tensor: bool = False, cfg_scale=None, cfg_null_label: int = 1000,
-                solver=None, solver_steps: int = 20, solver_order: int = 2, autoguidance_scale=None, guide_model=None):
+                solver=None, solver_steps: int = 20, solver_order: int = 2, autoguidance_scale=None, guide_model=None,
+                init_image=None, strength=None, known_image=None, known_mask=None):
     """reference sampler.py:82-155.  Returns (samples[B,H,W,C] float32 numpy = (x+1)/2, intermediates).
 
     cfg_scale (None: the unguided loops, unchanged): classifier-free guidance of every step's model output,
@@ -303,6 +353,14 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
         solver_steps model evaluations on the grid multistep_grid(solver_steps) and order solver_order (multistep_coefficients);
         predict_noise or predict_original models.  Step k runs the late model iff t_k < 1000 - t_switch (the DDPM loop's rule).
         Intermediate saves: after the step whose model timestep t has 1000 - t in timesteps_save.
+
+    init_image [1 or B, C, H, W] in the model's own space with strength in (0, 1] (engine option, SDEdit): every loop starts at
+        t0 = round(999 * strength) from sqrt(abar[t0]) init_image + sqrt(1 - abar[t0]) z, z the draw x_T is today; strength 1 is the
+        present start from z alone.
+    known_image [1 or B, C, H, W] with known_mask [1 or B, 1, H, W] in [0, 1] (engine option, inpainting): after every step the pixels
+        are finished as mask * (ka known_image + kb z2) + (1 - mask) x' at the noise level the step lands on (known_rows), so the
+        result equals known_image where mask == 1.  noise="device": fused into the loops, z2 from the device generator;
+        noise="torch_cpu": step by step, z2 drawn from the torch CPU stream after the step's z.
     """
     if noise not in ("torch_cpu", "device"):
         raise ValueError("noise must be 'torch_cpu' or 'device'")
@@ -317,8 +375,12 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
             raise ValueError("autoguidance needs a guide model: pass guide_model, or a late_model (the first model then guides it)")
     elif guide_model is not None:
         raise ValueError("guide_model without autoguidance_scale")
+    if (init_image is None) != (strength is None):
+        raise ValueError("init_image and strength go together")
+    if (known_image is None) != (known_mask is None):
+        raise ValueError("known_image and known_mask go together")
     plan = step_plan(_PARAMETRIZATIONS.get(postprocessing), timesteps_save, late_model is not None, t_switch, num_steps, use_ddim,
-                     ddim_steps, ddim_eta, solver, solver_steps, solver_order)
+                     ddim_steps, ddim_eta, solver, solver_steps, solver_order, strength)
     device = model.device
     guidance = None if cfg_scale is None else (float(cfg_scale), int(cfg_null_label))
     if guidance is not None and y is None:
@@ -328,9 +390,21 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
     x = torch.randn(batch_size, num_channels, sample_height, sample_width).to(device).contiguous()  # :100
     if y is not None:
         y = torch.as_tensor(y).to(device, torch.int64).contiguous()
+    image_shape = (num_channels, sample_height, sample_width)
+    t0 = start_timestep(strength)
+    init = None if init_image is None else _batch_tensor(init_image, "init_image", batch_size, image_shape, device)
+    region = None
+    if known_image is not None:
+        mask = _batch_tensor(known_mask, "known_mask", batch_size, (1, sample_height, sample_width), device)
+        if not bool(((mask >= 0) & (mask <= 1)).all()):
+            raise ValueError("known_mask must lie in [0, 1]")
+        region = KnownRegion(_batch_tensor(known_image, "known_image", batch_size, image_shape, device), mask, *known_rows(plan))
     first = model.engine_model(rows)
     late = late_model.engine_model(rows) if late_model is not None else None
     ctx = first.ctx
+    if t0 < 999:                                                             # x_t0 = sqrt(abar) x0 + sqrt(1 - abar) z; strength 1: z alone, as today
+        ab0 = schedule_tables()["alphas_bar"].astype(np.float64)[t0]
+        ctx.affine_step(x, init, None, _f32(np.sqrt(1.0 - ab0)), _f32(np.sqrt(ab0)), 0.0, out=x)
     guide = None
     if autoguidance_scale is not None:
         guide = first if guide_model is model else late if guide_model is late_model else guide_model.engine_model(rows)
@@ -344,17 +418,21 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
         for k0, k1 in _segments(plan.save_after):
             sw = None if plan.switch_after is None else min(max(plan.switch_after - k0, 0), k1 - k0)
             kw = dict(y=y, seed=seed, noise="philox", use_graph=use_graph, guidance=autoguidance or guidance)
-            if plan.kind == "ddpm":                                          # dd_sample counts t_switch from t = 999, as switch_after
-                sample_loop(ctx, late if sw == 0 else first, None if sw == 0 else late, x, t_switch=plan.switch_after if sw else 0,
-                            t_start=int(tab["t"][k0]), t_end=int(tab["t"][k1 - 1]), **kw)
+            # with a known region: the same loop's _region form, the region's rows cut like the loop's
+            known = () if region is None else (region._replace(ka=region.ka[k0:k1], kb=region.kb[k0:k1]),)
+            if plan.kind == "ddpm":                                          # dd_sample counts t_switch from t = 999, switch_after from the start
+                (sample_region_loop if known else sample_loop)(
+                    ctx, late if sw == 0 else first, None if sw == 0 else late, x, *known,
+                    t_switch=plan.switch_after + 999 - t0 if sw else 0, t_start=int(tab["t"][k0]), t_end=int(tab["t"][k1 - 1]), **kw)
             else:
                 seg = {key: v[k0:k1] for key, v in tab.items()}
                 m0, m1 = late if sw == 0 else first, late if sw and sw < k1 - k0 else None
                 if plan.kind == "affine":
-                    sample_affine_loop(ctx, m0, m1, x, seg["t"], seg["a"], seg["b"], seg["c"], seg["noise"], switch_after=sw,
-                                       counter_base=k0, **kw)
+                    (sample_affine_region_loop if known else sample_affine_loop)(
+                        ctx, m0, m1, x, *known, seg["t"], seg["a"], seg["b"], seg["c"], seg["noise"], switch_after=sw, counter_base=k0, **kw)
                 else:
-                    sample_multistep_loop(ctx, m0, m1, x, h, seg, switch_after=sw, counter_base=k0, **kw)
+                    (sample_multistep_region_loop if known else sample_multistep_loop)(
+                        ctx, m0, m1, x, *known, h, seg, switch_after=sw, counter_base=k0, **kw)
             if plan.save_after[k1 - 1]:
                 intermediate.append(x.clone())
     else:
@@ -380,6 +458,9 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
                     ctx.affine_step(x, eps, z, tab["a"][k], tab["b"][k], tab["c"][k], out=x)
                 else:
                     ctx.multistep_step(x, eps, z, h, *(tab[key][k] for key in "abcdpq"), tab["hist"][k], out=x)
+            if region is not None:                                           # z2: its own draw, after the step's z
+                z2 = torch.randn(x.shape).to(device) if region.kb[k] != 0 else None
+                ctx.known_blend(x, region.x0, region.mask, z2, region.ka[k], region.kb[k], out=x)
             if plan.save_after[k]:
                 intermediate.append(x.clone())
 
@@ -453,6 +534,52 @@ def validate_autoguidance(args, config, config_late=None, config_guide=None):
             raise ValueError(f"autoguidance: the guide's image geometry (img_size, patch_size, in_chans) = "
                              f"{(guide.img_size, guide.patch_size, guide.in_chans)} differs from {name}'s "
                              f"{(mp.img_size, mp.patch_size, mp.in_chans)}")
+
+
+def _load_image_file(path, what, mp, latent):
+    """--init_image / --known_image / --known_mask: a .npy in the model's own space, or (pixel-space RGB models) a .png mapped through
+    2 v - 1 (the mask: its first channel, unmapped) -> float32 [N, C, S, S]"""
+    path = Path(path)
+    mask = what == "--known_mask"
+    if path.suffix.lower() == ".npy":
+        a = np.asarray(np.load(path), np.float32)
+    elif path.suffix.lower() == ".png":
+        if latent:
+            raise ValueError(f"{what} {path.name}: a latent model takes .npy latents only (there is no encoder)")
+        if mp.in_chans != 3:
+            raise ValueError(f"{what} {path.name}: .png needs an in_chans = 3 config, this one has in_chans = {mp.in_chans}")
+        from matplotlib import pyplot as plt
+        a = np.asarray(plt.imread(path), np.float32)
+        a = a[..., None] if a.ndim == 2 else a
+        a = a[..., :1] if mask else 2.0 * (a[..., :3] if a.shape[-1] >= 3 else np.repeat(a[..., :1], 3, -1)) - 1.0
+        a = np.ascontiguousarray(a.transpose(2, 0, 1))[None]
+    else:
+        raise ValueError(f"{what} {path.name}: .npy or .png")
+    return a
+
+
+def validate_region(args, config):
+    """The image-to-image and inpainting options against the config, before any GPU work: ValueError on a bad combination.  Returns
+    get_samples' init_image / strength / known_image / known_mask arguments, the files loaded."""
+    mp = ModelParams.from_dict(config)
+    if (args.known_image is None) != (args.known_mask is None):
+        raise ValueError("--known_image and --known_mask go together")
+    if (args.init_image is None) != (args.strength is None):
+        raise ValueError("--init_image and --strength go together")
+    if args.strength is not None and not 0 < args.strength <= 1:
+        raise ValueError(f"--strength {args.strength} outside (0, 1]")
+    out = dict(init_image=None, strength=args.strength, known_image=None, known_mask=None)
+    for key, chans in (("init_image", mp.in_chans), ("known_image", mp.in_chans), ("known_mask", 1)):
+        path = getattr(args, key)
+        if path is None:
+            continue
+        a = _load_image_file(path, "--" + key, mp, "autoencoder" in config)
+        if a.ndim != 4 or a.shape[0] not in (1, args.batch_size) or a.shape[1:] != (chans, mp.img_size, mp.img_size):
+            raise ValueError(f"--{key}: shape {list(a.shape)} does not match [1 or {args.batch_size}, {chans}, {mp.img_size}, {mp.img_size}]")
+        if not np.isfinite(a).all() or (key == "known_mask" and ((a < 0) | (a > 1)).any()):
+            raise ValueError(f"--{key}: " + ("values outside [0, 1]" if key == "known_mask" else "non-finite values"))
+        out[key] = a
+    return out
 
 
 SOLVERS = {"ode": "dpmsolver++", "sde": "sde-dpmsolver++"}
@@ -556,6 +683,14 @@ def get_args(argv=None):
                         "(default: the reference's loops).  Exclusive with --use_ddim; predict_noise / predict_original models")
     p.add_argument("--dpm_solver_steps", type=int, default=20, help="(engine option) DPM-Solver++ model evaluations, 1 .. 999")
     p.add_argument("--dpm_solver_order", type=int, choices=[1, 2], default=2, help="(engine option) DPM-Solver++ order")
+    p.add_argument("--init_image", type=str, default=None,
+                   help="(engine option) image-to-image: start from this image (.npy in the model's space [1 or B, C, S, S], or .png for "
+                        "RGB pixel models) noised to t = round(999 * --strength)")
+    p.add_argument("--strength", type=float, default=None, help="(engine option) in (0, 1]: how far --init_image is noised; 1 = pure noise")
+    p.add_argument("--known_image", type=str, default=None,
+                   help="(engine option) inpainting: the image whose --known_mask region stays fixed (.npy / .png as --init_image)")
+    p.add_argument("--known_mask", type=str, default=None,
+                   help="(engine option) inpainting mask in [0, 1], 1 = keep (.npy [1 or B, 1, S, S], or the first channel of a .png)")
     return p.parse_args(argv)
 
 
@@ -586,6 +721,7 @@ def main(argv=None):
                       ModelParams.from_dict(config_late).num_classes if config_late is not None else None)
     config_guide = load_config(args.guide_config_path) if args.guide_config_path else None
     validate_autoguidance(args, config, config_late, config_guide)
+    region_kwargs = validate_region(args, config_late if config_late is not None else config)
     rows = 2 * args.batch_size if args.cfg_scale is not None else args.batch_size
     model, mp = build_model(config, args.checkpoint_path, args.precision, rows)
     model_late = None
@@ -611,7 +747,7 @@ def main(argv=None):
                                  y=y, autoencoder=autoencoder, late_model=model_late, t_switch=args.t_switch,
                                  timesteps_save=args.timesteps_save, noise=args.noise, use_graph=not args.no_graph,
                                  cfg_scale=args.cfg_scale, cfg_null_label=args.cfg_null_label, **solver_kwargs(args),
-                                 autoguidance_scale=args.autoguidance_scale, guide_model=model_guide)
+                                 autoguidance_scale=args.autoguidance_scale, guide_model=model_guide, **region_kwargs)
     tac = time.time()
     dump_statistics(tac - tic, out, args.batch_size)
     if args.no_png:

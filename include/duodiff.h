@@ -310,6 +310,41 @@ int dd_sample_autoguided(dd_ctx* ctx, const dd_sample_args* args, const dd_autog
 int dd_sample_affine_autoguided(dd_ctx* ctx, const dd_affine_sample_args* args, const dd_autoguidance* g, void* stream);
 int dd_sample_multistep_autoguided(dd_ctx* ctx, const dd_multistep_sample_args* args, const dd_autoguidance* g, void* stream);
 
+/* ---- known regions: inpainting and image-to-image starts (RePaint's replacement rule, Lugmayr et al. 2022, without resampling) ---- */
+/* After a step has produced x' (at the noise level the step lands on), every pixel is finished from a known image x0 and a mask m:
+ *     kn  = ka * x0                      ka, kb: fp32 scalars of the step
+ *     if kb != 0:  kn = kn + kb * z2     z2 ~ N(0,1), a draw of its own
+ *     x'' = x'                           if m == 0
+ *     x'' = m * kn + (1 - m) * x'        otherwise
+ * in fp32, contraction off, each product rounded on its own, in exactly that order.  So m == 0 leaves x' bit for bit (whatever x0 holds)
+ * and m == 1 with finite x' gives kn.  The mask is shared by a pixel's channels.  The history register of the multistep rule is not
+ * touched: h' = p x + q m comes from the step's inputs.
+ * For a step that lands on timestep s the host passes ka = sqrt(alphas_bar[s]), kb = sqrt(1 - alphas_bar[s]), and ka = 1, kb = 0 for
+ * a step that lands on the final image (duodiff_amd.sampler known_rows): where m == 1 the result then equals x0 exactly.
+ * z2 comes from the device Philox generator with the step's key, batch-wide pixel id and counter (counter_base included), exactly as
+ * z is drawn, under another stream word: independent of z, and the same for chained, cut and uncut runs.  DD_NOISE_NONE adds no z2.
+ * An image-to-image start needs no entry of its own: the caller noises x0 to the first timestep (dd_affine_step) and starts there. */
+typedef struct dd_known_region {
+    const float* x0_dev;    /* [B,C,S,S] fp32: the known image, in the model's own space */
+    const float* mask_dev;  /* [B,1,S,S] fp32 in [0,1]: 1 = known, 0 = generated */
+    const float* ka;        /* host [n_steps] (dd_sample: t_start - t_end + 1 rows, row k = step at t_start - k) */
+    const float* kb;        /* host [n_steps]; 0: no noise on that step's known pixels */
+} dd_known_region;
+/* the rule alone, elementwise: out = x'' of x = x'.  z2_dev [B,C,S,S] or NULL (no z2 term); x_dev and out_dev may alias */
+int dd_known_blend(dd_ctx* ctx, const float* x_dev, const float* x0_dev, const float* mask_dev, const float* z2_dev, float ka, float kb,
+                   float* out_dev, int B, int C, int S, void* stream);
+/* dd_sample / dd_sample_affine / dd_sample_multistep with a known region, fused into the step's last kernel.  g and ag are optional
+ * (NULL) and exclusive: the loop is then the guided / autoguided one, and under classifier-free guidance both rows of an image get x''.
+ * x0 and the mask are copied into the context at every call, so captured graphs are reused across calls with other tensors of the
+ * same shape.  DD_ERR_INVALID (with dd_last_error) before anything is enqueued when kr or one of its members is NULL, both g and ag
+ * are given, the noise mode is host noise, a model carries early-exit heads, or a check of the plain / guided entry fails. */
+int dd_sample_region(dd_ctx* ctx, const dd_sample_args* args, const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr,
+                     void* stream);
+int dd_sample_affine_region(dd_ctx* ctx, const dd_affine_sample_args* args, const dd_guidance* g, const dd_autoguidance* ag,
+                            const dd_known_region* kr, void* stream);
+int dd_sample_multistep_region(dd_ctx* ctx, const dd_multistep_sample_args* args, const dd_guidance* g, const dd_autoguidance* ag,
+                               const dd_known_region* kr, void* stream);
+
 /* The early-exit baseline's loop (reference eesampler.py:40-89) as a device-resident loop: per step EarlyExitUViT.forward
  * (all heads and probes), the per-sample exit selection with the global threshold, the DDPM update (sigma^2 = beta-tilde)
  * with the selected output; row t of err_dev [1000, depth] (batch-mean predicted error per layer, :70) and of idx_dev

@@ -32,6 +32,44 @@ hipError_t init_rowops_kernels();
 int device_num_cus();
 }  // namespace dd
 
+#define DD_HIP(c, expr)                                          \
+    do {                                                         \
+        hipError_t _e = (expr);                                  \
+        if (_e != hipSuccess) return fail_hip((c), _e, #expr);   \
+    } while (0)
+
+namespace {
+// A device buffer of the context that only grows: a captured step is keyed on its address, so graphs are re-captured once after it grew
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;        // elements
+    int grow(dd_ctx* c, size_t need) {       // the old block is freed first; a failed allocation leaves the buffer empty
+        if (n >= need) return DD_OK;
+        release();
+        DD_HIP(c, hipMalloc((void**)&p, need * sizeof(T)));
+        n = need;
+        return DD_OK;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr; n = 0;
+    }
+};
+// A table of per-step rows on the device with the host copy it is uploaded from (upload_rows)
+template <typename Row>
+struct RowTable {
+    DevBuf<Row> dev;
+    std::vector<Row> host;
+    hipEvent_t uploaded = nullptr;      // behind the last upload: the host copy is not rewritten before it has been read
+    void release() {
+        dev.release();
+        if (uploaded) (void)hipEventDestroy(uploaded);
+        uploaded = nullptr;
+    }
+};
+}  // namespace
+
 // ------------------------------------------------------------------------------------------
 struct dd_ctx {
     int device = 0;
@@ -47,27 +85,15 @@ struct dd_ctx {
     int num_cus = 256;           // CU count the persistent GEMM grids are sized for (dd_set_num_cus), a multiple of 8
     // dd_sample's graphs run on context-owned staging copies of x / y, so a captured step does not depend on the caller's
     // tensor addresses (reference get_samples allocates a fresh x per call: the graphs would be re-captured every time)
-    float* x_stage = nullptr;
-    int64_t* y_stage = nullptr;
-    size_t x_stage_elems = 0, y_stage_elems = 0;
+    DevBuf<float> x_stage;
+    DevBuf<int64_t> y_stage;
     long long graph_captures = 0;
     int last_chains = 1;         // chains the last dd_sample call ran (dd_dev_last_sample_chains)
-    // dd_sample_affine: the step table on the device (+ its host staging copy, which must outlive the async upload)
-    AffineRow* atab = nullptr;
-    size_t atab_rows = 0;
-    std::vector<AffineRow> atab_host;
-    // dd_sample_multistep: the history half of the rows beside atab, and the history register the loop runs on ([B, C, S, S], staged like x)
-    HistRow* htab = nullptr;
-    size_t htab_rows = 0;
-    std::vector<HistRow> htab_host;
-    float* h_stage = nullptr;
-    size_t h_stage_elems = 0;
-    // the *_region loops: the known-region half of the rows, and the known image and mask the loop reads (x0 [B, C, S, S] | mask [B, 1, S, S], staged like x)
-    KnownRow* ktab = nullptr;
-    size_t ktab_rows = 0;
-    std::vector<KnownRow> ktab_host;
-    float* k_stage = nullptr;
-    size_t k_stage_elems = 0;
+    RowTable<AffineRow> atab;    // dd_sample_affine: the step table
+    RowTable<HistRow> htab;      // dd_sample_multistep: the history half of the rows beside atab,
+    DevBuf<float> h_stage;       //   and the history register the loop runs on ([B, C, S, S], staged like x)
+    RowTable<KnownRow> ktab;     // the *_region loops: the known-region half of the rows,
+    DevBuf<float> k_stage;       //   and the known image and mask the loop reads (x0 [B, C, S, S] | mask [B, 1, S, S], staged like x)
     int prof_kind = 0;           // dd_profile_select: which launches dd_profile_steps brackets (DD_PROF_*)
     unsigned dev_flags = 0;      // dd_dev_set_flags (include/duodiff_dev.h): kernel-variant switches of the development harness
 };
@@ -190,12 +216,6 @@ unsigned ctx_dev_flags(dd_ctx* c) { return c->dev_flags; }
 }  // namespace dd
 
 namespace {
-
-#define DD_HIP(c, expr)                                          \
-    do {                                                         \
-        hipError_t _e = (expr);                                  \
-        if (_e != hipSuccess) return fail_hip((c), _e, #expr);   \
-    } while (0)
 
 // ---- schedule: bit-for-bit the fp32 tables of sampler.py:40-44 / ddpm_core.py:64-70 (see oracle/schedule_oracle.py)
 // betas = torch.linspace(beta_init, beta_final, n): ATen rounds once per element, forward from start in the first half,
@@ -502,16 +522,30 @@ struct Chain {
 Chain whole_batch(dd_ctx* c, dd_model* m) { return Chain{&m->ws[0], c->st[0], c->num_cus, true}; }
 
 // A loop's known region as a step sees it: the context's staged known image and mask at the step's first image, and the device rows
+// (all null: none)
 struct Known {
-    const float* x0;
-    const float* mask;
-    const KnownRow* ktab;
+    const float* x0 = nullptr;
+    const float* mask = nullptr;
+    const KnownRow* ktab = nullptr;
     Known at(int b0, const dd_model* m) const {      // a chain's share: images [b0, ...)
+        if (!x0) return *this;
         const size_t hw = (size_t)m->cfg.img_size * m->cfg.img_size;
         return Known{x0 + (size_t)b0 * hw * m->cfg.in_chans, mask + (size_t)b0 * hw, ktab};
     }
-    void key(GraphKey& k) const { k.kx0 = x0; k.kmask = mask; k.ktab = ktab; }
 };
+
+// What modifies a sampling loop, from its public entry down to the output head of each step
+struct Mods {
+    const dd_guidance* g = nullptr;           // classifier-free guidance: B images run as the 2 B backbone rows [x | x] with labels [y | null]
+    const dd_autoguidance* ag = nullptr;      // autoguidance (never with g): a step of a model other than ag->guide runs the guide on the same rows first
+    const dd_known_region* kr = nullptr;      // a *_region entry's known region as the caller passed it,
+    bool region = false;                      //   which such an entry requires;
+    Known kn{};                               //   staged on the device (stage_known) -- in a Slice, the chain's share of it
+    const char* missing = nullptr;            // a _guided / _autoguided entry called without its struct: the rejection
+};
+Mods guided(const dd_guidance* g) { return Mods{.g = g, .missing = g ? nullptr : "null dd_guidance"}; }
+Mods autoguided(const dd_autoguidance* ag) { return Mods{.ag = ag, .missing = ag ? nullptr : "null dd_autoguidance"}; }
+Mods in_region(const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr) { return Mods{.g = g, .ag = ag, .kr = kr, .region = true}; }
 
 // the output head's arguments that the model and the chain determine, for B images whose decoder rows are in dec; a call site sets the rest by name
 FinalArgs final_args(const dd_model* m, const Chain& ch, const float* dec, const float* wconv, const float* bconv, int B) {
@@ -923,47 +957,59 @@ int run_guide(dd_ctx* c, dd_model* m, const Chain& ch, const dd_autoguidance* ag
     return DD_OK;
 }
 
-// one sampling step of chain ch enqueued on s: x <- update(x, model(x, t)) ; t comes from ch.st
-// advance != 0: the step's last kernel also decrements the device-resident timestep (graph replays / dd_sample)
-// g != null (classifier-free guidance): B images, the backbone runs the 2 B rows [x | x] with labels [y | null] (stage_guided's layout)
-// htab != null (the multistep loop, atab set): the update adds row k's history term and writes h' to h [B, C, S, S]
-// ag != null (autoguidance; never with g): each model takes y_dev iff it is class-conditional; m != ag->guide: the guide runs the same B rows first
-// kn != null (a *_region loop): the known region of these B images finishes x'
-int enqueue_step(dd_ctx* c, dd_model* m, const Chain& ch, float* x_dev, const int64_t* y_dev, int noise_mode, const float* z_dev,
-                 int variance, float* eps_out, int B, hipStream_t s, int advance = 0, const AffineRow* atab = nullptr, int b0 = 0,
-                 const dd_guidance* g = nullptr, const HistRow* htab = nullptr, float* h = nullptr, const dd_autoguidance* ag = nullptr,
-                 const Known* kn = nullptr) {
-    FinalArgs fa = final_args(m, ch, ch.ws->dec, m->head.wconv, m->head.bconv, B);
+// The options of one model evaluation (forward_eps) or one sampling step (enqueue_step), set by name at the call site
+struct StepOpts {
+    const float* t_set = nullptr;      // put this timestep into the chain's step state first (else the state holds it)
+    const float* t_vec = nullptr;      // per-image timesteps on the device (dd_forward*)
+    const EeTaps* ee = nullptr;        // early-exit heads and probes of the forward
+    Mods mods{};                       // g, ag; and (a step) kn: the known region of these B images finishes x'
+    // a step only
+    int noise_mode = DD_NOISE_NONE;
+    const float* z = nullptr;          // DD_NOISE_BUFFER: the step's noise
+    int variance = 0;
+    float* eps_out = nullptr;          // the model output of the step, or null
+    int advance = 0;                   // != 0: the step's last kernel also moves the device-resident timestep on (graph replays / the loops)
+    const AffineRow* atab = nullptr;   // a table-driven loop: the step state holds a step index into these rows (null: the DDPM update)
+    int b0 = 0;                        // first image of a half-batch chain within the whole batch
+    const HistRow* htab = nullptr;     // the multistep loop (atab set): the update adds row k's history term and writes h' to h [B, C, S, S]
+    float* h = nullptr;
+};
+
+// eps = model(x, t) of B images of chain ch enqueued on s, up to the output head: the guide's forward (autoguidance; each model takes
+// y_dev iff it is class-conditional), the model's (classifier-free guidance: 2 B rows in stage_guided's layout) and the head's arguments
+// that combine them.  The caller sets what the head writes and launches it.
+int model_eps(dd_ctx* c, dd_model* m, const Chain& ch, const float* x_dev, const int64_t* y_dev, int B, hipStream_t s, const StepOpts& o,
+              FinalArgs& fa) {
+    const dd_guidance* g = o.mods.g;
+    const dd_autoguidance* ag = o.mods.ag;
+    if (o.t_set) DD_HIP(c, launch_set_state_float(ch.st, *o.t_set, s));
+    fa = final_args(m, ch, ch.ws->dec, m->head.wconv, m->head.bconv, B);
     int rc = DD_OK;
     if (ag && ag->guide != m && (rc = run_guide(c, m, ch, ag, x_dev, y_dev, B, s, fa))) return rc;
     if (ag && m->cfg.num_classes <= 0) y_dev = nullptr;
-    rc = run_model(m, ch, x_dev, nullptr, y_dev, g ? 2 * B : B, s);
-    if (rc) return rc;
-    fa.x_in = x_dev; fa.z = z_dev; fa.eps_out = eps_out; fa.x_out = x_dev;
-    fa.noise_mode = noise_mode; fa.variance = variance; fa.advance = advance; fa.atab = atab; fa.b0 = b0;
+    if ((rc = run_model(m, ch, x_dev, o.t_vec, y_dev, g ? 2 * B : B, s, o.ee))) return rc;
     if (g) { fa.pair_B = B; fa.guide_scale = g->scale; }
-    fa.htab = htab;
-    fa.h = h;
-    if (kn) { fa.kx0 = kn->x0; fa.kmask = kn->mask; fa.ktab = kn->ktab; }
+    return DD_OK;
+}
+
+// one sampling step of chain ch enqueued on s: x <- update(x, model(x, t)); t comes from ch.st
+int enqueue_step(dd_ctx* c, dd_model* m, const Chain& ch, float* x_dev, const int64_t* y_dev, int B, hipStream_t s, const StepOpts& o) {
+    FinalArgs fa;
+    if (int rc = model_eps(c, m, ch, x_dev, y_dev, B, s, o, fa)) return rc;
+    fa.x_in = x_dev; fa.z = o.z; fa.eps_out = o.eps_out; fa.x_out = x_dev;
+    fa.noise_mode = o.noise_mode; fa.variance = o.variance; fa.advance = o.advance; fa.atab = o.atab; fa.b0 = o.b0;
+    fa.htab = o.htab; fa.h = o.h;
+    fa.kx0 = o.mods.kn.x0; fa.kmask = o.mods.kn.mask; fa.ktab = o.mods.kn.ktab;
     DD_HIP(c, launch_final(fa, s));
     return DD_OK;
 }
 
-// eps = model(x, t) and nothing else (dd_forward*, the early-exit step): t_set != null first puts that timestep into the chain's step
-// state; g != null: the backbone runs the 2 B rows of stage_guided's layout and the output head combines them into B guided images
-// ag != null (autoguidance; t_vec null): as enqueue_step
-int forward_eps(dd_ctx* c, dd_model* m, const Chain& ch, const float* t_set, const float* x_dev, const float* t_vec, const int64_t* y_dev,
-                float* eps_dev, int B, hipStream_t s, const EeTaps* ee = nullptr, const dd_guidance* g = nullptr,
-                const dd_autoguidance* ag = nullptr) {
-    if (t_set) DD_HIP(c, launch_set_state_float(ch.st, *t_set, s));
-    FinalArgs fa = final_args(m, ch, ch.ws->dec, m->head.wconv, m->head.bconv, B);
-    int rc = DD_OK;
-    if (ag && ag->guide != m && (rc = run_guide(c, m, ch, ag, x_dev, y_dev, B, s, fa))) return rc;
-    if (ag && m->cfg.num_classes <= 0) y_dev = nullptr;
-    rc = run_model(m, ch, x_dev, t_vec, y_dev, g ? 2 * B : B, s, ee);
-    if (rc) return rc;
+// eps = model(x, t) and nothing else (dd_forward*, the early-exit step): the step-only options are not read
+int forward_eps(dd_ctx* c, dd_model* m, const Chain& ch, const float* x_dev, const int64_t* y_dev, float* eps_dev, int B, hipStream_t s,
+                const StepOpts& o) {
+    FinalArgs fa;
+    if (int rc = model_eps(c, m, ch, x_dev, y_dev, B, s, o, fa)) return rc;
     fa.eps_out = eps_dev;
-    if (g) { fa.pair_B = B; fa.guide_scale = g->scale; }
     DD_HIP(c, launch_final(fa, s));
     return DD_OK;
 }
@@ -971,27 +1017,16 @@ int forward_eps(dd_ctx* c, dd_model* m, const Chain& ch, const float* t_set, con
 // dd_sample / dd_sample_affine with graphs: the loop runs on context-owned staging copies of x / y, so the captured step
 // does not depend on the caller's tensor addresses
 int grow_stage(dd_ctx* c, size_t x_elems, size_t y_elems) {
-    if (c->x_stage_elems < x_elems) {       // grows only: model graphs keyed on the old address are re-captured once
-        if (c->x_stage) (void)hipFree(c->x_stage);
-        c->x_stage = nullptr; c->x_stage_elems = 0;
-        DD_HIP(c, hipMalloc((void**)&c->x_stage, x_elems * sizeof(float)));
-        c->x_stage_elems = x_elems;
-    }
-    if (c->y_stage_elems < y_elems) {
-        if (c->y_stage) (void)hipFree(c->y_stage);
-        c->y_stage = nullptr; c->y_stage_elems = 0;
-        DD_HIP(c, hipMalloc((void**)&c->y_stage, y_elems * sizeof(int64_t)));
-        c->y_stage_elems = y_elems;
-    }
-    return DD_OK;
+    if (int rc = c->x_stage.grow(c, x_elems)) return rc;
+    return c->y_stage.grow(c, y_elems);
 }
 int stage_inputs(dd_ctx* c, const float* x_dev, const int64_t* y_dev, int B, size_t x_elems, hipStream_t s, float** x_run,
                  const int64_t** y_run) {
     if (int rc = grow_stage(c, x_elems, y_dev ? (size_t)B : 0)) return rc;
-    DD_HIP(c, hipMemcpyAsync(c->x_stage, x_dev, x_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (y_dev) DD_HIP(c, hipMemcpyAsync(c->y_stage, y_dev, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    *x_run = c->x_stage;
-    *y_run = y_dev ? c->y_stage : nullptr;
+    DD_HIP(c, hipMemcpyAsync(c->x_stage.p, x_dev, x_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (y_dev) DD_HIP(c, hipMemcpyAsync(c->y_stage.p, y_dev, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    *x_run = c->x_stage.p;
+    *y_run = y_dev ? c->y_stage.p : nullptr;
     return DD_OK;
 }
 
@@ -1004,13 +1039,13 @@ int stage_guided(dd_ctx* c, const float* x_dev, const int64_t* y_dev, int B, int
     for (int k = 0; k < 2; ++k) {
         const int o = k ? B0 : 0, Bk = k ? B - B0 : B0;
         if (Bk == 0) continue;
-        float* xs = c->x_stage + 2 * (size_t)o * chw;
+        float* xs = c->x_stage.p + 2 * (size_t)o * chw;
         DD_HIP(c, hipMemcpyAsync(xs, x_dev + (size_t)o * chw, (size_t)Bk * chw * sizeof(float), hipMemcpyDeviceToDevice, s));
         DD_HIP(c, hipMemcpyAsync(xs + (size_t)Bk * chw, x_dev + (size_t)o * chw, (size_t)Bk * chw * sizeof(float), hipMemcpyDeviceToDevice, s));
-        DD_HIP(c, launch_guided_labels((const long long*)y_dev + o, (long long*)c->y_stage + 2 * (size_t)o, Bk, null_label, s));
+        DD_HIP(c, launch_guided_labels((const long long*)y_dev + o, (long long*)c->y_stage.p + 2 * (size_t)o, Bk, null_label, s));
     }
-    *x_run = c->x_stage;
-    *y_run = c->y_stage;
+    *x_run = c->x_stage.p;
+    *y_run = c->y_stage.p;
     return DD_OK;
 }
 // ... and the first half of each chain's block back to the caller's images
@@ -1079,7 +1114,8 @@ int get_graph(dd_ctx* c, dd_model* m, GraphKind kind, int chain, const GraphKey&
 }
 
 // One chain's share of a sampling loop's batch: the caller's images [b0, b0 + B), at x / y in the buffers the loop runs on
-struct Slice { int chain, chains; float* x; const int64_t* y; int B, b0; };
+// (mods: the loop's, with the chain's share of the known region)
+struct Slice { int chain, chains; float* x; const int64_t* y; int B, b0; Mods mods; };
 
 // A sampling loop as run_loop drives it: the entry point has run its checks and supplies what differs between the loops
 struct Loop {
@@ -1091,17 +1127,18 @@ struct Loop {
     float* x_dev;
     const int64_t* y_dev;
     int B;
-    const dd_guidance* g;
+    Mods mods;           // (the early-exit loop: none)
     bool use_graph;
     std::function<hipError_t(StepState*, hipStream_t)> set_state;                   // a chain's step state at the start of the loop
     std::function<void(GraphKey&, const Slice&)> key;                                // the loop's own fields of a chain's graph key
     std::function<int(dd_model*, const Chain&, const Slice&, hipStream_t)> step;     // one step of one chain
     std::function<int(int chains, hipStream_t)> tail = nullptr;                      // behind the join of the chains
-    const dd_autoguidance* ag = nullptr;     // autoguidance (never with g): the steps of a model other than ag->guide run the guide too
 };
 
 // dd_sample, dd_sample_affine (both also guided) and dd_sample_early_exit: staging, the half-batch chains, graph capture and replay, timing
 int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
+    const dd_guidance* g = L.mods.g;
+    const dd_autoguidance* ag = L.mods.ag;
     // Two half-batch chains (graph replays only).  Images are independent and a row's path through the kernels does not depend on the
     // batch size, so chain 0 = images [0, B0) on the caller's stream and chain 1 = images [B0, B) on the context's side stream compute
     // bit for bit what the undivided batch computes (Philox pixel ids carry the image offset) -- with the two chains free to drift apart,
@@ -1109,25 +1146,27 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
     // Guided: the decisions are made on the 2 B backbone rows and the split is by image (chain 0 takes the larger half, on the workspace
     // sized for max_batch >= 2 B rows; the second chain's workspace holds (max_batch + 1) / 2 rows >= 2 * floor(B / 2)).
     const bool ee = L.kind == GRAPH_EARLY_EXIT;
-    const int rows = L.g ? 2 * L.B : L.B;
-    const bool chained = L.use_graph && use_chains(c, L.first, rows, ee) && (!L.late || use_chains(c, L.late, rows, ee)) && (!L.g || L.B >= 2);
+    const int rows = g ? 2 * L.B : L.B;
+    const bool chained = L.use_graph && use_chains(c, L.first, rows, ee) && (!L.late || use_chains(c, L.late, rows, ee)) && (!g || L.B >= 2);
     const int chains = chained ? 2 : 1;
-    const int B0 = chained ? (L.g ? (L.B + 1) / 2 : L.B / 2) : L.B;
+    const int B0 = chained ? (g ? (L.B + 1) / 2 : L.B / 2) : L.B;
     c->last_chains = chains;
     // the captured persistent GEMM grids: halved for both chains of a large GEMM-path batch (the early-exit loop keeps the full grids)
     int cus = chained && !ee ? std::min(chain_gemm_cus(c, L.first, rows), L.late ? chain_gemm_cus(c, L.late, rows) : c->num_cus) : c->num_cus;
-    if (chained && L.ag) cus = std::min(cus, chain_gemm_cus(c, L.ag->guide, rows));
+    if (chained && ag) cus = std::min(cus, chain_gemm_cus(c, ag->guide, rows));
     // the loop runs on x_run / y_run: guided, or with graphs, the context's staging buffers (copied in here, copied back at the end)
     const size_t chw = (size_t)L.first->cfg.in_chans * L.first->cfg.img_size * L.first->cfg.img_size;
     float* x_run = L.x_dev;
     const int64_t* y_run = L.y_dev;
     int rc = DD_OK;
-    if (L.g) rc = stage_guided(c, L.x_dev, L.y_dev, L.B, B0, chw, L.g->null_label, s, &x_run, &y_run);
+    if (g) rc = stage_guided(c, L.x_dev, L.y_dev, L.B, B0, chw, g->null_label, s, &x_run, &y_run);
     else if (L.use_graph) rc = stage_inputs(c, L.x_dev, L.y_dev, L.B, (size_t)L.B * chw, s, &x_run, &y_run);
     if (rc) return rc;
     auto slice = [&](int k) {
-        const size_t row = k ? (L.g ? 2 * (size_t)B0 : (size_t)B0) : 0;     // the chain's first row in x_run / y_run
-        return Slice{k, chains, x_run + row * chw, y_run ? y_run + row : nullptr, k ? L.B - B0 : B0, k ? B0 : 0};
+        const size_t row = k ? (g ? 2 * (size_t)B0 : (size_t)B0) : 0;     // the chain's first row in x_run / y_run
+        Slice sl{k, chains, x_run + row * chw, y_run ? y_run + row : nullptr, k ? L.B - B0 : B0, k ? B0 : 0, L.mods};
+        sl.mods.kn = L.mods.kn.at(sl.b0, L.first);
+        return sl;
     };
     auto chain = [&](dd_model* m, int k) { return Chain{&m->ws[k], c->st[k], cus, !chained}; };
     if (L.use_graph) {
@@ -1135,17 +1174,18 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
             const Slice sl = slice(k);
             GraphKey key{sl.x, sl.y, sl.B, 0, 0, cus, nullptr};
             key.b0 = sl.b0;
-            key.guide(L.g);
+            key.guide(g);
+            key.kx0 = sl.mods.kn.x0; key.kmask = sl.mods.kn.mask; key.ktab = sl.mods.kn.ktab;
             L.key(key, sl);
             for (dd_model* m : {L.first, L.late}) {
                 if (!m) continue;
                 if (k && (rc = ensure_chain_ws(c, m, s))) return rc;
                 GraphKey mkey = key;
-                if (L.ag) {   // the step of the guide model itself is the unguided loop's step, under the unguided loop's key
+                if (ag) {   // the step of the guide model itself is the unguided loop's step, under the unguided loop's key
                     if (m->cfg.num_classes <= 0) mkey.y = nullptr;
-                    if (m != L.ag->guide) {
-                        if (k && (rc = ensure_chain_ws(c, L.ag->guide, s))) return rc;
-                        mkey.aguide = L.ag->guide; mkey.aserial = L.ag->guide->serial; mkey.gscale = __builtin_bit_cast(unsigned, L.ag->scale);
+                    if (m != ag->guide) {
+                        if (k && (rc = ensure_chain_ws(c, ag->guide, s))) return rc;
+                        mkey.aguide = ag->guide; mkey.aserial = ag->guide->serial; mkey.gscale = __builtin_bit_cast(unsigned, ag->scale);
                     }
                 }
                 if ((rc = get_graph(c, m, L.kind, k, mkey, s, [&] { return L.step(m, chain(m, k), sl, s); }))) return rc;
@@ -1181,7 +1221,7 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
     if (L.tail && (rc = L.tail(chains, s))) return rc;
     if (L.switch_at < 0) DD_HIP(c, hipEventRecord(c->ev[1], s));
     DD_HIP(c, hipEventRecord(c->ev[2], s));
-    if (L.g) return unstage_guided(c, L.x_dev, x_run, L.B, B0, chw, s);
+    if (g) return unstage_guided(c, L.x_dev, x_run, L.B, B0, chw, s);
     if (x_run != L.x_dev) DD_HIP(c, hipMemcpyAsync(L.x_dev, x_run, (size_t)L.B * chw * sizeof(float), hipMemcpyDeviceToDevice, s));
     return DD_OK;
 }
@@ -1222,7 +1262,7 @@ int profile_steps(dd_ctx* c, dd_model* m, float* x_dev, const int64_t* y_dev, in
         for (int k = 0; k < chains && !rc; ++k) {
             const int b0 = k ? B0 : 0;
             rc = enqueue_step(c, m, Chain{&m->ws[k], c->st[k], cus, !chained}, x_dev + (size_t)b0 * chw, y_dev ? y_dev + b0 : nullptr,
-                              DD_NOISE_PHILOX, nullptr, DD_VAR_BETA_TILDE, nullptr, k ? B - B0 : B0, cs[k], 0, nullptr, b0);
+                              k ? B - B0 : B0, cs[k], {.noise_mode = DD_NOISE_PHILOX, .variance = DD_VAR_BETA_TILDE, .b0 = b0});
         }
     }
     m->time_fc1 = false;
@@ -1335,13 +1375,8 @@ void dd_ctx_destroy(dd_ctx* c) {
     if (c->ev_ee_join) (void)hipEventDestroy(c->ev_ee_join);
     for (StepState* st : c->st) if (st) (void)hipFree(st);
     if (c->coef) (void)hipFree(c->coef);
-    if (c->x_stage) (void)hipFree(c->x_stage);
-    if (c->y_stage) (void)hipFree(c->y_stage);
-    if (c->atab) (void)hipFree(c->atab);
-    if (c->htab) (void)hipFree(c->htab);
-    if (c->h_stage) (void)hipFree(c->h_stage);
-    if (c->ktab) (void)hipFree(c->ktab);
-    if (c->k_stage) (void)hipFree(c->k_stage);
+    c->x_stage.release(); c->y_stage.release(); c->h_stage.release(); c->k_stage.release();
+    c->atab.release(); c->htab.release(); c->ktab.release();
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     delete c;
 }
@@ -1495,7 +1530,7 @@ int dd_forward(dd_ctx* c, dd_model* m, const float* x_dev, float t, const float*
     int rc = check_call(c, m, B, y_dev);
     if (rc) return rc;
     if (!x_dev || !eps_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
-    return forward_eps(c, m, whole_batch(c, m), &t, x_dev, t_dev, y_dev, eps_dev, B, (hipStream_t)stream);
+    return forward_eps(c, m, whole_batch(c, m), x_dev, y_dev, eps_dev, B, (hipStream_t)stream, {.t_set = &t, .t_vec = t_dev});
 }
 
 int dd_model_enable_early_exit(dd_model* m, int classifier_type) {
@@ -1519,7 +1554,7 @@ int dd_forward_early_exit(dd_ctx* c, dd_model* m, const float* x_dev, float t, c
     const int ti = (int)t;                                   // t = int(timesteps[0]) (early_exit.py:271)
     if (m->ee_type != DD_EE_MLP_PER_LAYER && m->ee_type != DD_EE_ATTENTION_PROBE && (ti < 0 || ti > 999)) return ctx_fail(c, DD_ERR_NOT_FOUND, "no probe for this timestep (KeyError in the reference)");
     const EeTaps ee{classifier_dev, outputs_dev, ti};
-    return forward_eps(c, m, whole_batch(c, m), &t, x_dev, t_dev, y_dev, eps_dev, B, (hipStream_t)stream, &ee);
+    return forward_eps(c, m, whole_batch(c, m), x_dev, y_dev, eps_dev, B, (hipStream_t)stream, {.t_set = &t, .t_vec = t_dev, .ee = &ee});
 }
 
 int dd_early_exit_select(dd_ctx* c, const float* outputs_dev, const float* eps_dev, const float* classifier_dev,
@@ -1603,7 +1638,7 @@ int dd_forward_guided(dd_ctx* c, dd_model* m, const float* x_dev, float t, const
     float* x_run = nullptr;
     const int64_t* y_run = nullptr;
     if ((rc = stage_guided(c, x_dev, y_dev, B, B, chw, g->null_label, s, &x_run, &y_run))) return rc;
-    return forward_eps(c, m, whole_batch(c, m), &t, x_run, nullptr, y_run, eps_dev, B, s, nullptr, g);
+    return forward_eps(c, m, whole_batch(c, m), x_run, y_run, eps_dev, B, s, {.t_set = &t, .mods = {.g = g}});
 }
 
 int dd_forward_autoguided(dd_ctx* c, dd_model* m, const float* x_dev, float t, const int64_t* y_dev, const dd_autoguidance* g,
@@ -1611,7 +1646,7 @@ int dd_forward_autoguided(dd_ctx* c, dd_model* m, const float* x_dev, float t, c
     int rc = check_autoguided(c, m, nullptr, B, y_dev, g);
     if (rc) return rc;
     if (!x_dev || !eps_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
-    return forward_eps(c, m, whole_batch(c, m), &t, x_dev, nullptr, y_dev, eps_dev, B, (hipStream_t)stream, nullptr, nullptr, g);
+    return forward_eps(c, m, whole_batch(c, m), x_dev, y_dev, eps_dev, B, (hipStream_t)stream, {.t_set = &t, .mods = {.ag = g}});
 }
 
 int dd_sample_step(dd_ctx* c, dd_model* m, float* x_dev, int t, const int64_t* y_dev, int noise_mode, const float* z_dev,
@@ -1623,126 +1658,38 @@ int dd_sample_step(dd_ctx* c, dd_model* m, float* x_dev, int t, const int64_t* y
     if (noise_mode == DD_NOISE_BUFFER && !z_dev && t > 0) return ctx_fail(c, DD_ERR_INVALID, "DD_NOISE_BUFFER needs z_dev");
     hipStream_t s = (hipStream_t)stream;
     DD_HIP(c, launch_set_state(c->st[0], t, (unsigned long long)seed, s));
-    return enqueue_step(c, m, whole_batch(c, m), x_dev, y_dev, noise_mode, z_dev, variance, eps_out_dev, B, s);
+    return enqueue_step(c, m, whole_batch(c, m), x_dev, y_dev, B, s,
+                        {.noise_mode = noise_mode, .z = z_dev, .variance = variance, .eps_out = eps_out_dev});
 }
 
 }  // extern "C"
 
 namespace {
-// What a *_region entry checks beyond the loop's own checks (include/duodiff.h dd_known_region), before anything is enqueued
-int check_region(dd_ctx* c, dd_model* first, dd_model* late, const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr,
-                 int noise_mode) {
-    if (!kr) return ctx_fail(c, DD_ERR_INVALID, "null dd_known_region");
-    if (!kr->x0_dev || !kr->mask_dev || !kr->ka || !kr->kb) return ctx_fail(c, DD_ERR_INVALID, "null member of dd_known_region");
-    if (g && ag) return ctx_fail(c, DD_ERR_INVALID, "classifier-free guidance and autoguidance are exclusive");
-    if (noise_mode == DD_NOISE_BUFFER)
-        return ctx_fail(c, DD_ERR_INVALID, "a known region draws its noise on the device; for host noise drive dd_forward, the step and dd_known_blend");
-    for (dd_model* m : {first, late})
-        if (m && m->ctx == c && m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, "a known region is not supported for early-exit models");
-    return DD_OK;
-}
-
-// The known region of a checked *_region call on the device: x0 | mask copied into the context's k_stage (a later call with other tensors of
-// the same shape replays the same graphs, as with x / y / h) and `rows` rows uploaded, row(i) each.
-int stage_known(dd_ctx* c, const dd_known_region* kr, const dd_model* m, int B, size_t rows, const std::function<KnownRow(size_t)>& row,
-                hipStream_t s, Known* out) {
-    const size_t hw = (size_t)m->cfg.img_size * m->cfg.img_size, x_elems = (size_t)B * hw * m->cfg.in_chans, m_elems = (size_t)B * hw;
-    if (c->k_stage_elems < x_elems + m_elems) {       // grows only: graphs keyed on the old address are re-captured once
-        if (c->k_stage) (void)hipFree(c->k_stage);
-        c->k_stage = nullptr; c->k_stage_elems = 0;
-        DD_HIP(c, hipMalloc((void**)&c->k_stage, (x_elems + m_elems) * sizeof(float)));
-        c->k_stage_elems = x_elems + m_elems;
-    }
-    if (c->ktab_rows < rows) {
-        if (c->ktab) (void)hipFree(c->ktab);
-        c->ktab = nullptr; c->ktab_rows = 0;
-        DD_HIP(c, hipMalloc((void**)&c->ktab, rows * sizeof(KnownRow)));
-        c->ktab_rows = rows;
-    }
-    DD_HIP(c, hipStreamSynchronize(s));            // a previous call's upload may still read the host staging copy
-    c->ktab_host.resize(rows);
-    for (size_t i = 0; i < rows; ++i) c->ktab_host[i] = row(i);
-    DD_HIP(c, hipMemcpyAsync(c->ktab, c->ktab_host.data(), rows * sizeof(KnownRow), hipMemcpyHostToDevice, s));
-    DD_HIP(c, hipMemcpyAsync(c->k_stage, kr->x0_dev, x_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
-    DD_HIP(c, hipMemcpyAsync(c->k_stage + x_elems, kr->mask_dev, m_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
-    *out = Known{c->k_stage, c->k_stage + x_elems, c->ktab};
-    return DD_OK;
-}
-// the rows of a table-driven loop of n steps: row k beside AffineRow k, one more (never used) as there
-std::function<KnownRow(size_t)> table_known_row(const dd_known_region* kr, int n) {
-    return [kr, n](size_t k) { return k < (size_t)n ? KnownRow{kr->ka[k], kr->kb[k]} : KnownRow{0.f, 0.f}; };
-}
-
-// dd_sample (g == nullptr, ag == nullptr), dd_sample_guided (g) and dd_sample_autoguided (ag): one path
-int sample_ddpm(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* stream, const dd_autoguidance* ag = nullptr,
-                const dd_known_region* kr = nullptr, bool region = false) {
+// Every check the model-driven loops share, before anything is enqueued and in this order (a: any of their argument structs): the entry's
+// own struct, the known region (include/duodiff.h dd_known_region), the loop's exclusion of early-exit models (no_early_exit: the
+// rejection, or null), the models under the guidance in use, the loop's own arguments (own_checks), the noise mode (host_noise: the
+// rejection of a host noise mode) and the image shape of the two models
+template <typename Args, typename Own>
+int check_loop(dd_ctx* c, const Args* a, const Mods& mo, const char* no_early_exit, const char* host_noise, Own&& own_checks) {
+    if (c && mo.missing) return ctx_fail(c, DD_ERR_INVALID, mo.missing);
     if (!c || !a) return DD_ERR_INVALID;
-    if (region)
-        if (int rc0 = check_region(c, a->first, a->late, g, ag, kr, a->noise_mode)) return rc0;
-    auto check = [&](dd_model* m) { return g ? check_guided(c, m, a->B, a->y_dev, g) : check_call(c, m, a->B, a->y_dev); };
-    int rc = ag ? check_autoguided(c, a->first, a->late, a->B, a->y_dev, ag) : check(a->first);
+    const dd_known_region* kr = mo.kr;
+    if (mo.region) {
+        if (!kr) return ctx_fail(c, DD_ERR_INVALID, "null dd_known_region");
+        if (!kr->x0_dev || !kr->mask_dev || !kr->ka || !kr->kb) return ctx_fail(c, DD_ERR_INVALID, "null member of dd_known_region");
+        if (mo.g && mo.ag) return ctx_fail(c, DD_ERR_INVALID, "classifier-free guidance and autoguidance are exclusive");
+        if (a->noise_mode == DD_NOISE_BUFFER)
+            return ctx_fail(c, DD_ERR_INVALID, "a known region draws its noise on the device; for host noise drive dd_forward, the step and dd_known_blend");
+        for (dd_model* m : {a->first, a->late})
+            if (m && m->ctx == c && m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, "a known region is not supported for early-exit models");
+    }
+    for (dd_model* m : {a->first, a->late})
+        if (no_early_exit && m && m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, no_early_exit);
+    auto check = [&](dd_model* m) { return mo.g ? check_guided(c, m, a->B, a->y_dev, mo.g) : check_call(c, m, a->B, a->y_dev); };
+    int rc = mo.ag ? check_autoguided(c, a->first, a->late, a->B, a->y_dev, mo.ag) : check(a->first);
     if (rc) return rc;
-    if (!ag && a->late && (rc = check(a->late))) return rc;
-    if (!a->x_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
-    if (a->t_start > 999 || a->t_end < 0 || a->t_end > a->t_start) return ctx_fail(c, DD_ERR_INVALID, "need 999 >= t_start >= t_end >= 0");
-    if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE)
-        return ctx_fail(c, DD_ERR_INVALID, "dd_sample generates noise on the device; for host noise drive dd_sample_step");
-    if (a->late) {
-        const dd_config &f = a->first->cfg, &l = a->late->cfg;
-        if (f.img_size != l.img_size || f.in_chans != l.in_chans) return ctx_fail(c, DD_ERR_INVALID, "first and late model disagree on image shape");
-    }
-    const bool switching = a->late && a->t_switch > 0 && a->t_switch <= 1000;
-    const int t_sw = 1000 - a->t_switch;  // the late model takes over AFTER this step (sampler.py:135-136)
-    const bool switch_here = switching && t_sw <= a->t_start && t_sw >= a->t_end;
-    Known kn{};
-    if (kr) {      // the rows by timestep, as the DDPM rule reads its own: row k of the call is the step at t_start - k
-        const int t0 = a->t_start, n = a->t_start - a->t_end + 1;
-        auto row = [&](size_t t) { const long long k = t0 - (long long)t; return k >= 0 && k < n ? KnownRow{kr->ka[k], kr->kb[k]} : KnownRow{0.f, 0.f}; };
-        if ((rc = stage_known(c, kr, a->first, a->B, 1000, row, (hipStream_t)stream, &kn))) return rc;
-    }
-    Loop L{GRAPH_DDPM, a->first, switching ? a->late : nullptr, a->t_start - a->t_end + 1, switch_here ? a->t_start - t_sw + 1 : -1,
-           a->x_dev, a->y_dev, a->B, g, a->use_graph != 0};
-    L.set_state = [&](StepState* st, hipStream_t s) { return launch_set_state(st, a->t_start, (unsigned long long)a->seed, s); };
-    L.key = [&](GraphKey& k, const Slice& sl) {
-        k.noise = a->noise_mode; k.variance = a->variance;
-        if (kr) kn.at(sl.b0, a->first).key(k);
-    };
-    L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t s) {
-        const Known ks = kr ? kn.at(sl.b0, m) : kn;
-        return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, a->variance, nullptr, sl.B, s, 1, nullptr, sl.b0, g, nullptr, nullptr, ag,
-                            kr ? &ks : nullptr);
-    };
-    L.ag = ag;
-    return run_loop(c, L, (hipStream_t)stream);
-}
-
-// the step table of dd_sample_affine / dd_sample_multistep on the device: n rows + one more whose timestep the last step hands on (never used)
-int upload_atab(dd_ctx* c, int n, const float* t, const float* a, const float* b, const float* cc, const int32_t* noise, int counter_base,
-                hipStream_t s) {
-    if (c->atab_rows < (size_t)n + 1) {
-        if (c->atab) (void)hipFree(c->atab);
-        c->atab = nullptr; c->atab_rows = 0;
-        DD_HIP(c, hipMalloc((void**)&c->atab, ((size_t)n + 1) * sizeof(AffineRow)));
-        c->atab_rows = (size_t)n + 1;
-    }
-    DD_HIP(c, hipStreamSynchronize(s));            // a previous call's upload may still read the host staging copy
-    c->atab_host.assign((size_t)n + 1, AffineRow{0.f, 0.f, 0.f, 0.f, 0, 0, 0, 0});
-    for (int k = 0; k < n; ++k) c->atab_host[k] = AffineRow{t[k], a[k], b[k], cc[k], noise[k] ? 1 : 0, counter_base + k, 0, 0};
-    DD_HIP(c, hipMemcpyAsync(c->atab, c->atab_host.data(), ((size_t)n + 1) * sizeof(AffineRow), hipMemcpyHostToDevice, s));
-    return DD_OK;
-}
-
-// the checks of a table-driven loop (dd_sample_affine, dd_sample_multistep: a's fields are dd_affine_sample_args'), before anything is
-// enqueued; host_noise: the message for a host noise mode
-template <typename Args>
-int check_table_loop(dd_ctx* c, const Args* a, const dd_guidance* g, const dd_autoguidance* ag, const char* host_noise) {
-    auto check = [&](dd_model* m) { return g ? check_guided(c, m, a->B, a->y_dev, g) : check_call(c, m, a->B, a->y_dev); };
-    int rc = ag ? check_autoguided(c, a->first, a->late, a->B, a->y_dev, ag) : check(a->first);
-    if (rc) return rc;
-    if (!ag && a->late && (rc = check(a->late))) return rc;
-    if (!a->x_dev || !a->t || !a->a || !a->b || !a->c || !a->noise) return ctx_fail(c, DD_ERR_INVALID, "null tensor / table");
-    if (a->n_steps < 1 || a->n_steps > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "n_steps outside [1, 2^20]");
-    if (a->counter_base < 0 || a->counter_base > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "counter_base outside [0, 2^20]");
+    if (!mo.ag && a->late && (rc = check(a->late))) return rc;
+    if ((rc = own_checks())) return rc;
     if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE) return ctx_fail(c, DD_ERR_INVALID, host_noise);
     if (a->late) {
         const dd_config &f = a->first->cfg, &l = a->late->cfg;
@@ -1750,91 +1697,143 @@ int check_table_loop(dd_ctx* c, const Args* a, const dd_guidance* g, const dd_au
     }
     return DD_OK;
 }
+// the own checks of a table-driven loop (dd_sample_affine, dd_sample_multistep: a's fields are dd_affine_sample_args')
+template <typename Args>
+int check_table(dd_ctx* c, const Args* a) {
+    if (!a->x_dev || !a->t || !a->a || !a->b || !a->c || !a->noise) return ctx_fail(c, DD_ERR_INVALID, "null tensor / table");
+    if (a->n_steps < 1 || a->n_steps > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "n_steps outside [1, 2^20]");
+    if (a->counter_base < 0 || a->counter_base > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "counter_base outside [0, 2^20]");
+    return DD_OK;
+}
 
-// dd_sample_affine (g == nullptr, ag == nullptr), dd_sample_affine_guided (g) and dd_sample_affine_autoguided (ag): one path
-int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, void* stream, const dd_autoguidance* ag = nullptr,
-                  const dd_known_region* kr = nullptr, bool region = false) {
-    if (!c || !a) return DD_ERR_INVALID;
-    if (region)
-        if (int rc0 = check_region(c, a->first, a->late, g, ag, kr, a->noise_mode)) return rc0;
-    int rc = check_table_loop(c, a, g, ag, "dd_sample_affine generates noise on the device; for host noise drive dd_forward + dd_affine_step");
+// `rows` rows, row(i) each, into the table's device buffer on s.  The host copy an earlier upload may still be reading is left alone
+// until that upload has finished.
+template <typename Row, typename F>
+int upload_rows(dd_ctx* c, RowTable<Row>& t, size_t rows, hipStream_t s, F&& row) {
+    if (int rc = t.dev.grow(c, rows)) return rc;
+    if (t.uploaded) DD_HIP(c, hipEventSynchronize(t.uploaded));
+    else DD_HIP(c, hipEventCreateWithFlags(&t.uploaded, hipEventDisableTiming));
+    t.host.resize(rows);
+    for (size_t i = 0; i < rows; ++i) t.host[i] = row(i);
+    DD_HIP(c, hipMemcpyAsync(t.dev.p, t.host.data(), rows * sizeof(Row), hipMemcpyHostToDevice, s));
+    DD_HIP(c, hipEventRecord(t.uploaded, s));
+    return DD_OK;
+}
+// the step table of dd_sample_affine / dd_sample_multistep on the device: n rows + one more whose timestep the last step hands on (never used)
+template <typename Args>
+int upload_atab(dd_ctx* c, const Args* a, hipStream_t s) {
+    return upload_rows(c, c->atab, (size_t)a->n_steps + 1, s, [a](size_t k) {
+        return k < (size_t)a->n_steps ? AffineRow{a->t[k], a->a[k], a->b[k], a->c[k], a->noise[k] ? 1 : 0, a->counter_base + (int)k, 0, 0}
+                                      : AffineRow{0.f, 0.f, 0.f, 0.f, 0, 0, 0, 0};
+    });
+}
+
+// The known region of a checked *_region call on the device (mo.kr null: nothing to do): x0 | mask copied into the context's k_stage (a
+// later call with other tensors of the same shape replays the same graphs, as with x / y / h) and `rows` rows uploaded, row(i) each.
+template <typename F>
+int stage_known(dd_ctx* c, Mods& mo, const dd_model* m, int B, size_t rows, hipStream_t s, F&& row) {
+    if (!mo.kr) return DD_OK;
+    const size_t hw = (size_t)m->cfg.img_size * m->cfg.img_size, x_elems = (size_t)B * hw * m->cfg.in_chans, m_elems = (size_t)B * hw;
+    if (int rc = c->k_stage.grow(c, x_elems + m_elems)) return rc;
+    if (int rc = upload_rows(c, c->ktab, rows, s, row)) return rc;
+    DD_HIP(c, hipMemcpyAsync(c->k_stage.p, mo.kr->x0_dev, x_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    DD_HIP(c, hipMemcpyAsync(c->k_stage.p + x_elems, mo.kr->mask_dev, m_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    mo.kn = Known{c->k_stage.p, c->k_stage.p + x_elems, c->ktab.dev.p};
+    return DD_OK;
+}
+// ... of a table-driven loop of n steps: row k beside AffineRow k, one more (never used) as there
+int stage_table_known(dd_ctx* c, Mods& mo, const dd_model* m, int B, int n, hipStream_t s) {
+    const dd_known_region* kr = mo.kr;
+    return stage_known(c, mo, m, B, (size_t)n + 1, s, [kr, n](size_t k) { return k < (size_t)n ? KnownRow{kr->ka[k], kr->kb[k]} : KnownRow{0.f, 0.f}; });
+}
+
+// dd_sample and its _guided, _autoguided and _region forms: one path
+int sample_ddpm(dd_ctx* c, const dd_sample_args* a, Mods mo, void* stream) {
+    int rc = check_loop(c, a, mo, nullptr, "dd_sample generates noise on the device; for host noise drive dd_sample_step", [&]() -> int {
+        if (!a->x_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+        if (a->t_start > 999 || a->t_end < 0 || a->t_end > a->t_start) return ctx_fail(c, DD_ERR_INVALID, "need 999 >= t_start >= t_end >= 0");
+        return DD_OK;
+    });
+    if (rc) return rc;
+    const int n = a->t_start - a->t_end + 1;
+    const bool switching = a->late && a->t_switch > 0 && a->t_switch <= 1000;
+    const int t_sw = 1000 - a->t_switch;  // the late model takes over AFTER this step (sampler.py:135-136)
+    const bool switch_here = switching && t_sw <= a->t_start && t_sw >= a->t_end;
+    // the known rows by timestep, as the DDPM rule reads its own: row k of the call is the step at t_start - k
+    auto known_row = [kr = mo.kr, t0 = a->t_start, n](size_t t) {
+        const long long k = t0 - (long long)t;
+        return k >= 0 && k < n ? KnownRow{kr->ka[k], kr->kb[k]} : KnownRow{0.f, 0.f};
+    };
+    if ((rc = stage_known(c, mo, a->first, a->B, 1000, (hipStream_t)stream, known_row))) return rc;
+    Loop L{GRAPH_DDPM, a->first, switching ? a->late : nullptr, n, switch_here ? a->t_start - t_sw + 1 : -1, a->x_dev, a->y_dev, a->B, mo,
+           a->use_graph != 0};
+    L.set_state = [&](StepState* st, hipStream_t s) { return launch_set_state(st, a->t_start, (unsigned long long)a->seed, s); };
+    L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.variance = a->variance; };
+    L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t s) {
+        return enqueue_step(c, m, ch, sl.x, sl.y, sl.B, s,
+                            {.mods = sl.mods, .noise_mode = a->noise_mode, .variance = a->variance, .advance = 1, .b0 = sl.b0});
+    };
+    return run_loop(c, L, (hipStream_t)stream);
+}
+
+// dd_sample_affine and its _guided, _autoguided and _region forms: one path
+int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, Mods mo, void* stream) {
+    int rc = check_loop(c, a, mo, nullptr, "dd_sample_affine generates noise on the device; for host noise drive dd_forward + dd_affine_step",
+                        [&] { return check_table(c, a); });
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int n = a->n_steps;
     const bool switching = a->late && a->switch_after >= 0 && a->switch_after < n;
-    if ((rc = upload_atab(c, n, a->t, a->a, a->b, a->c, a->noise, a->counter_base, s))) return rc;
-    Known kn{};
-    if (kr && (rc = stage_known(c, kr, a->first, a->B, (size_t)n + 1, table_known_row(kr, n), s, &kn))) return rc;
+    if ((rc = upload_atab(c, a, s))) return rc;
+    if ((rc = stage_table_known(c, mo, a->first, a->B, n, s))) return rc;
+    const AffineRow* atab = c->atab.dev.p;
     // (two half-batch chains, as dd_sample: both read the one step table; each has its own step index and Philox image offset)
-    Loop L{GRAPH_AFFINE, a->first, switching ? a->late : nullptr, n, switching ? a->switch_after : -1, a->x_dev, a->y_dev, a->B, g,
+    Loop L{GRAPH_AFFINE, a->first, switching ? a->late : nullptr, n, switching ? a->switch_after : -1, a->x_dev, a->y_dev, a->B, mo,
            a->use_graph != 0};
-    L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_table(st, c->atab, (unsigned long long)a->seed, ss); };
-    L.key = [&](GraphKey& k, const Slice& sl) {
-        k.noise = a->noise_mode; k.atab = c->atab;
-        if (kr) kn.at(sl.b0, a->first).key(k);
-    };
+    L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_table(st, atab, (unsigned long long)a->seed, ss); };
+    L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.atab = atab; };
     L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
-        const Known ks = kr ? kn.at(sl.b0, m) : kn;
-        return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, 0, nullptr, sl.B, ss, 1, c->atab, sl.b0, g, nullptr, nullptr, ag,
-                            kr ? &ks : nullptr);
+        return enqueue_step(c, m, ch, sl.x, sl.y, sl.B, ss, {.mods = sl.mods, .noise_mode = a->noise_mode, .advance = 1, .atab = atab, .b0 = sl.b0});
     };
-    L.ag = ag;
     return run_loop(c, L, s);
 }
 
-// dd_sample_multistep (g == nullptr) and dd_sample_multistep_guided: dd_sample_affine's loop with the history register.  h is staged
-// like x: copied into the context's h_stage before the loop, chain k's images at h_stage + o_k chw (guided too: h holds B images,
-// not 2 B), and copied back behind the join of the chains.
-int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, void* stream, const dd_autoguidance* ag = nullptr,
-                     const dd_known_region* kr = nullptr, bool region = false) {
-    if (!c || !a) return DD_ERR_INVALID;
-    if (region)
-        if (int rc0 = check_region(c, a->first, a->late, g, ag, kr, a->noise_mode)) return rc0;
-    for (dd_model* m : {a->first, a->late})
-        if (m && m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, "the multistep loop is not supported for early-exit models");
-    int rc = check_table_loop(c, a, g, ag, "dd_sample_multistep generates noise on the device; for host noise drive dd_forward + dd_multistep_step");
+// dd_sample_multistep and its forms: dd_sample_affine's loop with the history register.  h is staged like x: copied into the context's
+// h_stage before the loop, chain k's images at h_stage + o_k chw (guided too: h holds B images, not 2 B), and copied back behind the
+// join of the chains.
+int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, Mods mo, void* stream) {
+    int rc = check_loop(c, a, mo, "the multistep loop is not supported for early-exit models",
+                        "dd_sample_multistep generates noise on the device; for host noise drive dd_forward + dd_multistep_step",
+                        [&] { return check_table(c, a); });
     if (rc) return rc;
     if (!a->d || !a->p || !a->q || !a->hist) return ctx_fail(c, DD_ERR_INVALID, "null tensor / table");
     if (!a->h_dev) return ctx_fail(c, DD_ERR_INVALID, "null h_dev: the multistep loop needs its history register");
     hipStream_t s = (hipStream_t)stream;
     const int n = a->n_steps;
     const bool switching = a->late && a->switch_after >= 0 && a->switch_after < n;
-    if ((rc = upload_atab(c, n, a->t, a->a, a->b, a->c, a->noise, a->counter_base, s))) return rc;
-    if (c->htab_rows < (size_t)n + 1) {
-        if (c->htab) (void)hipFree(c->htab);
-        c->htab = nullptr; c->htab_rows = 0;
-        DD_HIP(c, hipMalloc((void**)&c->htab, ((size_t)n + 1) * sizeof(HistRow)));
-        c->htab_rows = (size_t)n + 1;
-    }
-    c->htab_host.assign((size_t)n + 1, HistRow{0.f, 0.f, 0.f, 0});     // (upload_atab synchronised s: no upload still reads it)
-    for (int k = 0; k < n; ++k) c->htab_host[k] = HistRow{a->d[k], a->p[k], a->q[k], a->hist[k] ? 1 : 0};
-    DD_HIP(c, hipMemcpyAsync(c->htab, c->htab_host.data(), ((size_t)n + 1) * sizeof(HistRow), hipMemcpyHostToDevice, s));
+    if ((rc = upload_atab(c, a, s))) return rc;
+    rc = upload_rows(c, c->htab, (size_t)n + 1, s, [a, n](size_t k) {
+        return k < (size_t)n ? HistRow{a->d[k], a->p[k], a->q[k], a->hist[k] ? 1 : 0} : HistRow{0.f, 0.f, 0.f, 0};
+    });
+    if (rc) return rc;
     const size_t chw = (size_t)a->first->cfg.in_chans * a->first->cfg.img_size * a->first->cfg.img_size;
     const size_t h_elems = (size_t)a->B * chw;
-    if (c->h_stage_elems < h_elems) {       // grows only: graphs keyed on the old address are re-captured once
-        if (c->h_stage) (void)hipFree(c->h_stage);
-        c->h_stage = nullptr; c->h_stage_elems = 0;
-        DD_HIP(c, hipMalloc((void**)&c->h_stage, h_elems * sizeof(float)));
-        c->h_stage_elems = h_elems;
-    }
-    DD_HIP(c, hipMemcpyAsync(c->h_stage, a->h_dev, h_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
-    Known kn{};
-    if (kr && (rc = stage_known(c, kr, a->first, a->B, (size_t)n + 1, table_known_row(kr, n), s, &kn))) return rc;
-    Loop L{GRAPH_MULTISTEP, a->first, switching ? a->late : nullptr, n, switching ? a->switch_after : -1, a->x_dev, a->y_dev, a->B, g,
+    if ((rc = c->h_stage.grow(c, h_elems))) return rc;
+    float* h_run = c->h_stage.p;
+    DD_HIP(c, hipMemcpyAsync(h_run, a->h_dev, h_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if ((rc = stage_table_known(c, mo, a->first, a->B, n, s))) return rc;
+    const AffineRow* atab = c->atab.dev.p;
+    const HistRow* htab = c->htab.dev.p;
+    Loop L{GRAPH_MULTISTEP, a->first, switching ? a->late : nullptr, n, switching ? a->switch_after : -1, a->x_dev, a->y_dev, a->B, mo,
            a->use_graph != 0};
-    L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_table(st, c->atab, (unsigned long long)a->seed, ss); };
-    L.key = [&](GraphKey& k, const Slice& sl) {
-        k.noise = a->noise_mode; k.atab = c->atab; k.aux0 = c->htab; k.aux1 = c->h_stage;
-        if (kr) kn.at(sl.b0, a->first).key(k);
-    };
+    L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_table(st, atab, (unsigned long long)a->seed, ss); };
+    L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.atab = atab; k.aux0 = htab; k.aux1 = h_run; };
     L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
-        const Known ks = kr ? kn.at(sl.b0, m) : kn;
-        return enqueue_step(c, m, ch, sl.x, sl.y, a->noise_mode, nullptr, 0, nullptr, sl.B, ss, 1, c->atab, sl.b0, g, c->htab,
-                            c->h_stage + (size_t)sl.b0 * chw, ag, kr ? &ks : nullptr);
+        return enqueue_step(c, m, ch, sl.x, sl.y, sl.B, ss, {.mods = sl.mods, .noise_mode = a->noise_mode, .advance = 1, .atab = atab, .b0 = sl.b0,
+                                                             .htab = htab, .h = h_run + (size_t)sl.b0 * chw});
     };
-    L.ag = ag;
     L.tail = [&](int, hipStream_t ss) -> int {
-        DD_HIP(c, hipMemcpyAsync(a->h_dev, c->h_stage, h_elems * sizeof(float), hipMemcpyDeviceToDevice, ss));
+        DD_HIP(c, hipMemcpyAsync(a->h_dev, h_run, h_elems * sizeof(float), hipMemcpyDeviceToDevice, ss));
         return DD_OK;
     };
     return run_loop(c, L, s);
@@ -1843,44 +1842,31 @@ int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guid
 
 extern "C" {
 
-int dd_sample(dd_ctx* c, const dd_sample_args* a, void* stream) { return sample_ddpm(c, a, nullptr, stream); }
-int dd_sample_guided(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* stream) {
-    if (c && !g) return ctx_fail(c, DD_ERR_INVALID, "null dd_guidance");
-    return sample_ddpm(c, a, g, stream);
-}
-int dd_sample_affine(dd_ctx* c, const dd_affine_sample_args* a, void* stream) { return sample_affine(c, a, nullptr, stream); }
-int dd_sample_affine_guided(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, void* stream) {
-    if (c && !g) return ctx_fail(c, DD_ERR_INVALID, "null dd_guidance");
-    return sample_affine(c, a, g, stream);
-}
-int dd_sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, void* stream) { return sample_multistep(c, a, nullptr, stream); }
-int dd_sample_multistep_guided(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, void* stream) {
-    if (c && !g) return ctx_fail(c, DD_ERR_INVALID, "null dd_guidance");
-    return sample_multistep(c, a, g, stream);
-}
-int dd_sample_autoguided(dd_ctx* c, const dd_sample_args* a, const dd_autoguidance* g, void* stream) {
-    if (c && !g) return ctx_fail(c, DD_ERR_INVALID, "null dd_autoguidance");
-    return sample_ddpm(c, a, nullptr, stream, g);
-}
-int dd_sample_affine_autoguided(dd_ctx* c, const dd_affine_sample_args* a, const dd_autoguidance* g, void* stream) {
-    if (c && !g) return ctx_fail(c, DD_ERR_INVALID, "null dd_autoguidance");
-    return sample_affine(c, a, nullptr, stream, g);
-}
-int dd_sample_multistep_autoguided(dd_ctx* c, const dd_multistep_sample_args* a, const dd_autoguidance* g, void* stream) {
-    if (c && !g) return ctx_fail(c, DD_ERR_INVALID, "null dd_autoguidance");
-    return sample_multistep(c, a, nullptr, stream, g);
-}
-
+int dd_sample(dd_ctx* c, const dd_sample_args* a, void* stream) { return sample_ddpm(c, a, Mods{}, stream); }
+int dd_sample_guided(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* stream) { return sample_ddpm(c, a, guided(g), stream); }
+int dd_sample_autoguided(dd_ctx* c, const dd_sample_args* a, const dd_autoguidance* g, void* stream) { return sample_ddpm(c, a, autoguided(g), stream); }
 int dd_sample_region(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr, void* stream) {
-    return sample_ddpm(c, a, g, stream, ag, kr, true);
+    return sample_ddpm(c, a, in_region(g, ag, kr), stream);
+}
+int dd_sample_affine(dd_ctx* c, const dd_affine_sample_args* a, void* stream) { return sample_affine(c, a, Mods{}, stream); }
+int dd_sample_affine_guided(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, void* stream) { return sample_affine(c, a, guided(g), stream); }
+int dd_sample_affine_autoguided(dd_ctx* c, const dd_affine_sample_args* a, const dd_autoguidance* g, void* stream) {
+    return sample_affine(c, a, autoguided(g), stream);
 }
 int dd_sample_affine_region(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr,
                             void* stream) {
-    return sample_affine(c, a, g, stream, ag, kr, true);
+    return sample_affine(c, a, in_region(g, ag, kr), stream);
+}
+int dd_sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, void* stream) { return sample_multistep(c, a, Mods{}, stream); }
+int dd_sample_multistep_guided(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, void* stream) {
+    return sample_multistep(c, a, guided(g), stream);
+}
+int dd_sample_multistep_autoguided(dd_ctx* c, const dd_multistep_sample_args* a, const dd_autoguidance* g, void* stream) {
+    return sample_multistep(c, a, autoguided(g), stream);
 }
 int dd_sample_multistep_region(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag,
                                const dd_known_region* kr, void* stream) {
-    return sample_multistep(c, a, g, stream, ag, kr, true);
+    return sample_multistep(c, a, in_region(g, ag, kr), stream);
 }
 
 // One early-exit sampling step on the device (reference eesampler.py:56-81): EarlyExitUViT.forward with every head and
@@ -1895,7 +1881,7 @@ static int enqueue_ee_step(dd_ctx* c, dd_model* m, const Chain& ch, float* ws, f
     float* cls = eps + (size_t)B * chw;
     float* outs = cls + (size_t)depth * B;
     const EeTaps ee{cls, outs, 0};
-    if (int rc = forward_eps(c, m, ch, nullptr, x, nullptr, y, eps, B, s, &ee)) return rc;
+    if (int rc = forward_eps(c, m, ch, x, y, eps, B, s, {.ee = &ee})) return rc;
     // exit layer per image, the selected output and the DDPM update in one launch (dd_early_exit_select + the step kernel, fused: same arithmetic)
     DD_HIP(c, launch_ee_select_step(x, outs, eps, cls, thr, depth, idx_tab, err_tab, B_all, b0, sums, ch.st, c->coef, B,
                                     m->cfg.in_chans, m->cfg.img_size, noise_mode, 1, s));
@@ -1920,7 +1906,7 @@ int dd_sample_early_exit(dd_ctx* c, const dd_ee_sample_args* a, void* stream) {
     if (!m->ee_ws) DD_HIP(c, hipMalloc((void**)&m->ee_ws, (ee_scratch_elems(m, m->cfg.max_batch) + 2 * tab) * sizeof(float)));
     float* sums = m->ee_ws + ee_scratch_elems(m, m->cfg.max_batch);
     auto err_tab = [&](const Slice& sl) { return sl.chains == 1 || !a->err_dev ? a->err_dev : sums + sl.chain * tab; };
-    Loop L{GRAPH_EARLY_EXIT, m, nullptr, a->t_start - a->t_end + 1, -1, a->x_dev, a->y_dev, a->B, nullptr, a->use_graph != 0};
+    Loop L{GRAPH_EARLY_EXIT, m, nullptr, a->t_start - a->t_end + 1, -1, a->x_dev, a->y_dev, a->B, Mods{}, a->use_graph != 0};
     L.set_state = [&](StepState* st, hipStream_t s) { return launch_set_state(st, a->t_start, (unsigned long long)a->seed, s); };
     L.key = [&](GraphKey& k, const Slice& sl) {
         k.noise = a->noise_mode; k.aux0 = err_tab(sl); k.aux1 = a->idx_dev; k.thr = a->threshold;

@@ -326,34 +326,29 @@ class KnownRegion(NamedTuple):
     kb: np.ndarray
 
 
-def _region_call(ctx, args, plain, guidance, region, x, n_steps):
-    """The _region entry of `plain` (dd_known_region): either kind of guidance, or none, goes in beside the region"""
-    B, Cc, S, _ = x.shape
-    for v, shape in ((region.x0, (B, Cc, S, S)), (region.mask, (B, 1, S, S))):
-        assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and tuple(v.shape) == shape
-    ka, kb = (np.ascontiguousarray(v, np.float32) for v in (region.ka, region.kb))
-    assert ka.shape == kb.shape == (n_steps,)
-    kr = L.dd_known_region(region.x0.data_ptr(), region.mask.data_ptr(), ka.ctypes.data_as(C.POINTER(C.c_float)),
-                           kb.ctypes.data_as(C.POINTER(C.c_float)))
+def _loop_call(ctx, args, plain, guidance, region, x):
+    """The loop entry of this argument struct as call(stream): `plain` (guidance None), its _guided form (guidance = (scale, null_label):
+    classifier-free), its _autoguided form (guidance = Autoguidance(guide, scale)) or, with a KnownRegion, its _region form, which
+    takes either kind of guidance, or none, beside the dd_known_region.  No entry takes both kinds of guidance."""
     g = ag = None
     if isinstance(guidance, Autoguidance):
         ag = C.byref(L.dd_autoguidance(guidance.guide.handle, float(guidance.scale)))
     elif guidance is not None:
         g = C.byref(guidance_struct(guidance))
-    fn = getattr(ctx.lib, plain + "_region")
-    return lambda st, keep=(ka, kb): fn(ctx.handle, C.byref(args), g, ag, C.byref(kr), st)
-
-
-def _loop_call(ctx, args, plain, guidance):
-    """The loop entry of this argument struct: `plain` (guidance None), its _guided form (guidance = (scale, null_label): classifier-free)
-    or its _autoguided form (guidance = Autoguidance(guide, scale)).  One argument: the C ABI has no entry that takes both."""
-    if guidance is None:
-        return lambda st: getattr(ctx.lib, plain)(ctx.handle, C.byref(args), st)
-    if isinstance(guidance, Autoguidance):
-        g, fn = L.dd_autoguidance(guidance.guide.handle, float(guidance.scale)), getattr(ctx.lib, plain + "_autoguided")
+    if region is None:
+        keep = None
+        name, extra = plain + ("" if guidance is None else "_autoguided" if g is None else "_guided"), [r for r in (g, ag) if r is not None]
     else:
-        g, fn = guidance_struct(guidance), getattr(ctx.lib, plain + "_guided")
-    return lambda st: fn(ctx.handle, C.byref(args), C.byref(g), st)
+        B, Cc, S, _ = x.shape
+        n_steps = args.n_steps if hasattr(args, "n_steps") else args.t_start - args.t_end + 1
+        for v, shape in ((region.x0, (B, Cc, S, S)), (region.mask, (B, 1, S, S))):
+            assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and tuple(v.shape) == shape
+        keep = ka, kb = [np.ascontiguousarray(v, np.float32) for v in (region.ka, region.kb)]
+        assert ka.shape == kb.shape == (n_steps,)
+        kr = L.dd_known_region(region.x0.data_ptr(), region.mask.data_ptr(), *(v.ctypes.data_as(C.POINTER(C.c_float)) for v in keep))
+        name, extra = plain + "_region", [g, ag, C.byref(kr)]
+    fn = getattr(ctx.lib, name)
+    return lambda st, keep=keep: fn(ctx.handle, C.byref(args), *extra, st)     # (a byref keeps its struct alive, the closure the arrays)
 
 
 def _run_loop(ctx: Context, args, x, y, seed, noise, use_graph, stream, call):
@@ -399,11 +394,7 @@ def _sample_loop(ctx, first, late, x, region, t_switch, t_start, t_end, y, seed,
     args.t_switch = int(t_switch) if t_switch and np.isfinite(t_switch) else 0
     args.t_start, args.t_end = int(t_start), int(t_end)
     args.variance = L.DD_VAR_BETA if variance == "beta" else L.DD_VAR_BETA_TILDE
-    if region is None:
-        call = _loop_call(ctx, args, "dd_sample", guidance)
-    else:
-        call = _region_call(ctx, args, "dd_sample", guidance, region, x, int(t_start) - int(t_end) + 1)
-    return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
+    return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, _loop_call(ctx, args, "dd_sample", guidance, region, x))
 
 
 def _step_table(args, first, late, rows, floats, ints, switch_after, counter_base):
@@ -448,11 +439,7 @@ def _sample_affine_loop(ctx, first, late, x, region, t, a, b, c, noise_flags, sw
     args = L.dd_affine_sample_args()
     tab = _step_table(args, first, late, dict(t=t, a=a, b=b, c=c, noise=noise_flags), "tabc", ("noise",), switch_after,  # noqa: F841
                       counter_base)
-    if region is None:
-        call = _loop_call(ctx, args, "dd_sample_affine", guidance)
-    else:
-        call = _region_call(ctx, args, "dd_sample_affine", guidance, region, x, args.n_steps)
-    return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
+    return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, _loop_call(ctx, args, "dd_sample_affine", guidance, region, x))
 
 
 def sample_multistep_loop(ctx: Context, first: Model, late, x, h, rows, *, switch_after=None, y=None, seed=0, counter_base=0,
@@ -480,11 +467,7 @@ def _sample_multistep_loop(ctx, first, late, x, region, h, rows, switch_after, y
     tab = _step_table(args, first, late, rows, "tabcdpq", ("noise", "hist"), switch_after, counter_base)  # noqa: F841
     assert h.is_cuda and h.dtype == torch.float32 and h.is_contiguous() and h.shape == x.shape
     args.h_dev = h.data_ptr()
-    if region is None:
-        call = _loop_call(ctx, args, "dd_sample_multistep", guidance)
-    else:
-        call = _region_call(ctx, args, "dd_sample_multistep", guidance, region, x, args.n_steps)
-    return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
+    return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, _loop_call(ctx, args, "dd_sample_multistep", guidance, region, x))
 
 
 def sample_early_exit_loop(ctx: Context, model: Model, x, threshold, *, t_start=999, t_end=0, y=None, seed=0, noise="philox",

@@ -607,6 +607,61 @@ def test_invalid_region_calls_are_rejected_before_anything_is_enqueued(kind):
 
 
 @gpu
+def test_loop_rejections_keep_their_order():
+    """Calls that break two rules at once fail on the rule the loops check first (the texts in the order of the checks in capi.hip: the
+    region's own rules, the multistep loop's early-exit exclusion, the models, the loop's tensors and ranges, the noise mode)."""
+    from duodiff_amd.engine import Model
+    B = 2
+    m, guide = _model(B), _model(B, seed=41, depth=1)
+    ctx, lib = m.ctx, m.ctx.lib
+    ee = Model(ctx, ModelParams.from_dict(dict(TINY)), B)
+    ee.enable_early_exit("mlp_probe_per_layer")
+    x_in, x0, mask = _inputs(B, 43)
+    x, h, st = x_in.clone(), torch.zeros_like(x_in), _stream()
+    tab = {k: np.ascontiguousarray(v, np.int32 if k in ("noise", "hist") else np.float32) for k, v in _plan("multistep", n=3).rows.items()}
+    ka, kb = np.ones(3, np.float32), np.zeros(3, np.float32)
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    kr = L.dd_known_region(x0.data_ptr(), mask.data_ptr(), fp(ka), fp(kb))
+    g, ag = L.dd_guidance(0.5, NULL), L.dd_autoguidance(guide.handle, 0.5)
+
+    def args(kind, first=m, **fields):
+        if kind == "ddpm":
+            a = L.dd_sample_args()
+            a.t_start, a.t_end = 2, 0
+        else:
+            a = L.dd_affine_sample_args() if kind == "affine" else L.dd_multistep_sample_args()
+            a.n_steps, a.switch_after = 3, 3
+            for k in "tabc" + ("dpq" if kind == "multistep" else ""):
+                setattr(a, k, fp(tab[k]))
+            for k in ("noise",) + (("hist",) if kind == "multistep" else ()):
+                setattr(a, k, tab[k].ctypes.data_as(C.POINTER(C.c_int32)))
+            if kind == "multistep":
+                a.h_dev = h.data_ptr()
+        a.first, a.late, a.y_dev, a.x_dev = first.handle, None, None, x.data_ptr()
+        a.noise_mode, a.use_graph, a.seed, a.B = L.DD_NOISE_PHILOX, 1, 1, B
+        for k, v in fields.items():
+            setattr(a, k, v)
+        return a
+
+    both = (C.byref(g), C.byref(ag), C.byref(kr))
+    cases = [(f"dd_sample{k}_region", args(kind, noise_mode=L.DD_NOISE_BUFFER), both, "classifier-free guidance and autoguidance are exclusive")
+             for k, kind in (("", "ddpm"), ("_affine", "affine"), ("_multistep", "multistep"))]
+    cases += [("dd_sample_multistep_region", args("multistep", ee), (None, None, None), "null dd_known_region"),
+              ("dd_sample_multistep", args("multistep", ee, h_dev=None), (), "the multistep loop is not supported for early-exit models"),
+              ("dd_sample_affine", args("affine", x_dev=None, n_steps=0), (), "null tensor / table"),
+              ("dd_sample", args("ddpm", t_start=1, t_end=2, noise_mode=L.DD_NOISE_BUFFER), (), "need 999 >= t_start >= t_end >= 0")]
+    n0 = lib.dd_dev_graph_captures(ctx.handle)
+    for name, a, extra, msg in cases:
+        with torch.cuda.stream(st):
+            rc = getattr(lib, name)(ctx.handle, C.byref(a), *extra, C.c_void_p(st.cuda_stream))
+        err = lib.dd_last_error(ctx.handle).decode()
+        print(f"{name}: rc {rc}, {err!r}")
+        assert rc == L.DD_ERR_INVALID and err == msg, (name, rc, err)
+    st.synchronize()
+    assert torch.equal(x, x_in) and not h.any() and lib.dd_dev_graph_captures(ctx.handle) == n0, "something was enqueued"
+
+
+@gpu
 def test_fp32_engine_matches_the_oracle_with_a_half_image_mask():
     """8 DDIM steps with the left half of the image known: the fp32 engine (device loop) against the numpy oracle driven by the
     extracted z / z2 and a numpy restatement of the rule in float64 (max abs <= 1e-3, the multistep rollout's tolerance: the blend is a

@@ -139,6 +139,10 @@ SIGNATURES = {
     "dd_dev_gemm": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p] + [C.c_int] * 2 + [C.c_void_p] * 2 +
                     [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_rowlin": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 5 + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
+    "dd_dev_attention": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
+    "dd_dev_layernorm": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.POINTER(C.c_float)]),
+    "dd_dev_embed": (C.c_int, [C.c_void_p] + [C.c_int] * 9 + [C.c_void_p] * 7 + [C.c_float] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
+    "dd_dev_time_mlp": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 6 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_poison_workspaces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "dd_dev_graph_captures": (C.c_longlong, [C.c_void_p]),
     "dd_dev_last_sample_chains": (C.c_int, [C.c_void_p]),

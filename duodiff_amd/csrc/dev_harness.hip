@@ -1,5 +1,5 @@
 // The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_qkv_attention, dd_dev_head_dec, dd_dev_gemm,
-// dd_dev_rowlin): test scaffolding, not product.  Each one packs host operands as finalize packs a model's, launches what the model launches
+// dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp): test scaffolding, not product.  Each one packs host operands as finalize packs a model's, launches what the model launches
 // (launch_args.h), returns the outputs and times `iters` further launch sequences.  Buffers, transfers, timing and HIP errors go through
 // one DevScope (dev_scope.h); the context is reached through its accessors only.
 #include "../../include/duodiff.h"
@@ -273,6 +273,134 @@ int dd_dev_rowlin(dd_ctx* c, int B, int n_patches, int extras, int K, int k_spli
     dev.download(xres_host, dX, Mo * D * 4);
     if (x_copy_host) dev.download(x_copy_host, dC, Mo * D * 2);
     if (h_host) dev.download(h_host, dH, Mo * D * 2);
+    DEV_HIP(dev, time_launches(s, iters, once, ms_out));
+    return dev.status();
+}
+
+int dd_dev_attention(dd_ctx* c, int precision, int B, int L, int H, const float* q, const float* k, const float* v, void* out_host,
+                     int iters, void* stream, float* ms_out) {
+    const bool bf = precision == DD_PREC_BF16;
+    if (!c || (!bf && precision != DD_PREC_FP32) || B < 1 || L < 1 || H < 1 || !q || !k || !v || !out_host || iters < 0) return DD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const int D = 64 * H;
+    const size_t esz = bf ? 2 : 4, Lp = (size_t)make_head_major(L, H).Lp;
+    const size_t qkv_elems = ((size_t)B * 3 * H * Lp + 64) * 64, out_elems = ((size_t)B * L + 8) * D;
+    // head-major image (HeadMajor): 0xFF bytes (NaN) everywhere, then the rows l < L only -- the pad rows [L, Lp) of every unit, which the qkv
+    // Linear never writes, and the 64 trailing rows stay NaN
+    std::vector<unsigned char> img(qkv_elems * esz, 0xFF);
+    const float* src[3] = {q, k, v};
+    for (int b = 0; b < B; ++b)
+        for (int j = 0; j < 3; ++j)
+            for (int hh = 0; hh < H; ++hh)
+                for (int l = 0; l < L; ++l) {
+                    const float* row = src[j] + (((size_t)b * H + hh) * L + l) * 64;
+                    const size_t at = ((((size_t)b * 3 + j) * H + hh) * Lp + l) * 64;
+                    if (bf) for (int d = 0; d < 64; ++d) reinterpret_cast<unsigned short*>(img.data())[at + d] = host_f2bf(row[d]);
+                    else std::memcpy(img.data() + at * 4, row, 64 * 4);
+                }
+    DevScope dev(c);
+    const void* dQ = dev.upload(img.data(), img.size());
+    void* dO = dev.filled(out_elems * esz, 0xFF);
+    auto once = [&]() {
+        return bf ? launch_attention<bf16_t>((const bf16_t*)dQ, (bf16_t*)dO, B, L, H, D, s) : launch_attention<float>((const float*)dQ, (float*)dO, B, L, H, D, s);
+    };
+    const hipError_t first = dev.ok() ? once() : hipSuccess;
+    if (first == hipErrorInvalidValue) return ctx_fail(c, DD_ERR_UNSUPPORTED, "attention: 1 <= L <= 288, heads of 64");      // (refused before any launch)
+    DEV_HIP(dev, first);
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(out_host, dO, out_elems * esz);
+    DEV_HIP(dev, time_launches(s, iters, once, ms_out));
+    return dev.status();
+}
+
+int dd_dev_layernorm(dd_ctx* c, int precision, int rows, int D, const float* x_host, const float* gamma_beta, void* out_host,
+                     unsigned short* frag_host, int tok_l, int tok_e, int iters, void* stream, float* ms_out) {
+    const bool bf = precision == DD_PREC_BF16;
+    if (!c || (!bf && precision != DD_PREC_FP32) || rows < 1 || D < 1 || !x_host || !gamma_beta || !out_host || iters < 0) return DD_ERR_INVALID;
+    if (frag_host && !bf) return ctx_fail(c, DD_ERR_UNSUPPORTED, "layernorm: fragment order is a bf16 output");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n_out = ((size_t)rows + 8) * D;
+    DevScope dev(c);
+    const float* dX = dev.upload(x_host, (size_t)rows * D * 4);
+    const float* dG = dev.upload(gamma_beta, (size_t)2 * D * 4);
+    void* dO = dev.filled(n_out * (bf ? 2 : 4), 0xFF);
+    bf16_t* dF = frag_host ? dev.filled<bf16_t>(n_out * 2, 0xFF) : nullptr;
+    auto once = [&]() {
+        if (frag_host) return launch_layernorm_frag(dX, dG, dG + D, (bf16_t*)dO, dF, rows, D, tok_l, tok_e, s);
+        return bf ? launch_layernorm<bf16_t>(dX, dG, dG + D, (bf16_t*)dO, rows, D, s) : launch_layernorm<float>(dX, dG, dG + D, (float*)dO, rows, D, s);
+    };
+    const hipError_t first = dev.ok() ? once() : hipSuccess;
+    if (first == hipErrorInvalidValue)      // (refused before any launch)
+        return ctx_fail(c, DD_ERR_UNSUPPORTED, "layernorm: D % 64 == 0, D <= 1024; fragment order: D % 256 == 0, (tok_l - tok_e) % 32 == 0, rows % tok_l == 0");
+    DEV_HIP(dev, first);
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(out_host, dO, n_out * (bf ? 2 : 4));
+    if (frag_host) dev.download(frag_host, dF, n_out * 2);
+    DEV_HIP(dev, time_launches(s, iters, once, ms_out));
+    return dev.status();
+}
+
+int dd_dev_embed(dd_ctx* c, int B, int C, int S, int P, int D, int extras, int num_classes, int normalize, int generic, const float* x_img,
+                 const float* w, const float* bias, const float* pos, const float* label_emb, const long long* y, const float* t_vec,
+                 float t_state, const float* ln, float* x_tok_host, unsigned short* ln_frag_host, int iters, void* stream, float* ms_out) {
+    if (!c || B < 1 || C < 1 || P < 1 || S < P || S % P || D < 2 || extras < 1 || extras > 2 || !x_img || !w || !bias || !pos || !x_tok_host ||
+        (extras == 2 && (!label_emb || !y || num_classes < 1)) || (ln && !ln_frag_host) || iters < 0)
+        return DD_ERR_INVALID;
+    const int pd = C * P * P, L = extras + (S / P) * (S / P), Mp = round_up(B * L, 256);
+    if (pd > 64) return ctx_fail(c, DD_ERR_UNSUPPORTED, "embed: patch_dim <= 64");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<float> wt((size_t)pd * D);      // [D, pd] -> [pd, D], as finalize packs it (pack_embed)
+    for (int d = 0; d < D; ++d) for (int k = 0; k < pd; ++k) wt[(size_t)k * D + d] = w[(size_t)d * pd + k];
+    const size_t n_tok = ((size_t)Mp + 8) * D;
+    EmbedArgs a{};
+    a.B = B; a.C = C; a.S = S; a.P = P; a.D = D; a.L = L; a.extras = extras; a.num_classes = num_classes; a.normalize = normalize; a.Mp = Mp;
+    a.generic = generic;
+    if (ln && !embed_ln_supported(a)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "embed with norm1: the MFMA kernel at patch 4, 3 channels, embed_dim 512");
+    DevScope dev(c);
+    a.x_img = dev.upload(x_img, (size_t)B * C * S * S * 4);
+    a.wt = dev.upload(wt.data(), wt.size() * 4);
+    a.bias = dev.upload(bias, (size_t)D * 4);
+    a.pos = dev.upload(pos, (size_t)L * D * 4);
+    if (extras == 2) { a.label_emb = dev.upload(label_emb, (size_t)num_classes * D * 4); a.y = dev.upload(y, (size_t)B * 8); }
+    if (t_vec) a.t_vec = dev.upload(t_vec, (size_t)B * 4);
+    a.st = dev.alloc<StepState>(sizeof(StepState));
+    a.x_tok = dev.filled<float>(n_tok * 4, 0xFF);
+    if (ln) {
+        a.ln_g = dev.upload(ln, (size_t)2 * D * 4); a.ln_b = a.ln_g + D;
+        a.ln_frag = dev.filled<bf16_t>(n_tok * 2, 0xFF);
+    }
+    DEV_HIP(dev, launch_set_state_float(a.st, t_state, s));      // t_vec NULL: the kernel's timestep; always: t, which it copies to t_final
+    auto once = [&]() { return launch_embed(a, s); };
+    DEV_HIP(dev, once());
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(x_tok_host, a.x_tok, n_tok * 4);
+    if (ln) dev.download(ln_frag_host, a.ln_frag, n_tok * 2);
+    DEV_HIP(dev, time_launches(s, iters, once, ms_out));
+    return dev.status();
+}
+
+int dd_dev_time_mlp(dd_ctx* c, int B, int D, int L, int extras, int normalize, const float* w1, const float* b1, const float* w2,
+                    const float* b2, const float* pos, const float* t_vec, float t_state, float* x_tok_host, int iters, void* stream,
+                    float* ms_out) {
+    if (!c || B < 1 || D < 2 || extras < 1 || L < extras || !w1 || !b1 || !w2 || !b2 || !pos || !x_tok_host || iters < 0) return DD_ERR_INVALID;
+    if ((size_t)5 * D * 4 > 64 * 1024) return ctx_fail(c, DD_ERR_UNSUPPORTED, "time_mlp: 5 D floats of LDS");
+    hipStream_t s = (hipStream_t)stream;
+    const int H4 = 4 * D;
+    std::vector<float> w1t((size_t)D * H4), w2t((size_t)H4 * D);      // transposed as finalize packs them (pack_embed)
+    for (int j = 0; j < H4; ++j) for (int k = 0; k < D; ++k) w1t[(size_t)k * H4 + j] = w1[(size_t)j * D + k];
+    for (int d = 0; d < D; ++d) for (int k = 0; k < H4; ++k) w2t[(size_t)k * D + d] = w2[(size_t)d * H4 + k];
+    const size_t n_tok = (size_t)B * L * D;
+    DevScope dev(c);
+    StepState* st = dev.alloc<StepState>(sizeof(StepState));
+    float* dX = dev.upload(x_tok_host, n_tok * 4);
+    const TimeMlpArgs a{dev.upload(w1t.data(), w1t.size() * 4), dev.upload(b1, (size_t)H4 * 4), dev.upload(w2t.data(), w2t.size() * 4),
+                        dev.upload(b2, (size_t)D * 4), dev.upload(pos, (size_t)L * D * 4), t_vec ? dev.upload(t_vec, (size_t)B * 4) : nullptr,
+                        st, dX, B, D, L, extras, normalize};
+    DEV_HIP(dev, launch_set_state_float(st, t_state, s));
+    auto once = [&]() { return launch_time_mlp(a, s); };
+    DEV_HIP(dev, once());
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(x_tok_host, dX, n_tok * 4);
     DEV_HIP(dev, time_launches(s, iters, once, ms_out));
     return dev.status();
 }

@@ -77,6 +77,43 @@ int dd_dev_rowlin(dd_ctx* ctx, int B, int n_patches, int extras, int K, int k_sp
                   const float* bias, const float* ln, float* xres_host, unsigned short* x_copy_host, unsigned short* h_host, int frag,
                   int iters, void* stream, float* ms_out);
 
+/* Development harness for the plain attention launch (attention.hip attention_kernel<T, 9> for L = 257 / 258, <T, 0> for any other L <= 288;
+ * reference models/uvit.py:155-164): out = softmax(q k^T / 8) v per (image, head) from host fp32 q, k, v [B, H, L, 64] (precision DD_PREC_BF16:
+ * rounded to bf16 here, so they are exact operands).  The head-major qkv buffer the launch reads ([B][3 H][Lp = L rounded up to 8][64] + 64
+ * trailing rows) is filled with 0xFF bytes and only its rows l < L are written: the pad rows [L, Lp), which the qkv Linear never writes, hold
+ * NaN.  out_host [B L + 8, 64 H] of bf16 bits / fp32 is filled with 0xFF bytes before the launch and comes back WHOLE.  A shape the launcher
+ * refuses (L > 288) is DD_ERR_UNSUPPORTED, L < 1 DD_ERR_INVALID; nothing is launched.  `iters` timed launches -> ms_out. */
+int dd_dev_attention(dd_ctx* ctx, int precision, int B, int L, int H, const float* q, const float* k, const float* v, void* out_host,
+                     int iters, void* stream, float* ms_out);
+
+/* Development harness for the LayerNorm launches (rowops.hip layernorm_kernel<T>): out = LayerNorm(x) gamma + beta (eps 1e-5, biased variance)
+ * of host fp32 rows x [rows, D], gamma_beta [2, D].  frag_host NULL: launch_layernorm<T> (T by precision) into out_host, row-major.
+ * frag_host non-NULL (bf16 only): launch_layernorm_frag -- the patch rows of the tok_l-token images (behind tok_e extra tokens) go to frag_host in
+ * fragment order ([32-row group][D / 16 k-steps][64 lanes] x 8 bf16, MlpFusedArgs::ln_out_frag), only the extra-token rows to out_host.
+ * out_host (bf16 bits / fp32) and frag_host have rows + 8 rows of D, are filled with 0xFF bytes before the launch and come back WHOLE.
+ * A shape the launcher refuses is DD_ERR_UNSUPPORTED.  `iters` timed launches -> ms_out. */
+int dd_dev_layernorm(dd_ctx* ctx, int precision, int rows, int D, const float* x_host, const float* gamma_beta, void* out_host,
+                     unsigned short* frag_host, int tok_l, int tok_e, int iters, void* stream, float* ms_out);
+
+/* Development harness for token assembly (rowops.hip embed_kernel / embed_mfma_kernel through launch_embed; reference models/uvit.py:352-365):
+ * rows of every image = [label_emb[y],] time sinusoid, (S / P)^2 patch tokens, + pos; L = extras + (S / P)^2, extras = 1 (time) or 2 (label + time).
+ * x_img [B, C, S, S], w [D, C, P, P] (transposed here as finalize does), bias [D], pos [L, D], label_emb [num_classes, D] + y [B] (extras == 2),
+ * t_vec [B] or NULL: the timestep comes from a device StepState set to t_state (which is set either way).  generic != 0: the VALU kernel even where
+ * the MFMA kernel fits.  ln [2, D] (gamma, beta) + ln_frag_host or NULL: the MFMA kernel's variant that also writes the first block's norm1 of the
+ * patch rows in fragment order (patch 4, 3 channels, embed_dim 512, not generic; anything else is DD_ERR_UNSUPPORTED).
+ * x_tok_host fp32 and ln_frag_host bf16: [Mp + 8, D], Mp = round_up(B L, 256), filled with 0xFF bytes before the launch, returned WHOLE (the
+ * launch zeroes rows [B L, Mp)).  `iters` timed launches -> ms_out. */
+int dd_dev_embed(dd_ctx* ctx, int B, int C, int S, int P, int D, int extras, int num_classes, int normalize, int generic, const float* x_img,
+                 const float* w, const float* bias, const float* pos, const float* label_emb, const long long* y, const float* t_vec,
+                 float t_state, const float* ln, float* x_tok_host, unsigned short* ln_frag_host, int iters, void* stream, float* ms_out);
+
+/* Development harness for the time_embed MLP (rowops.hip time_mlp_kernel; reference models/uvit.py:264-272, 358): row extras - 1 of every image of
+ * x_tok_host [B L, D] (in / out, returned whole) = w2 . SiLU(w1 . sinusoid(t) + b1) + b2 + pos[extras - 1]; nn.Linear weights w1 [4 D, D], w2 [D, 4 D]
+ * (transposed here as finalize does), pos [L, D], t_vec [B] or NULL (the StepState set to t_state).  `iters` timed launches -> ms_out. */
+int dd_dev_time_mlp(dd_ctx* ctx, int B, int D, int L, int extras, int normalize, const float* w1, const float* b1, const float* w2,
+                    const float* b2, const float* pos, const float* t_vec, float t_state, float* x_tok_host, int iters, void* stream,
+                    float* ms_out);
+
 /* Kernel-variant switches for same-process A/B runs (tools/mlp_check.py, tools/all_configs.py).  They act on models
  * FINALIZED after the call (the first three) or on launches made after it; the product never sets them and the library
  * reads no environment variable. */

@@ -127,6 +127,9 @@ SIGNATURES = {
     "dd_vae_finalize": (C.c_int, [C.c_void_p, C.c_int]),
     "dd_vae_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dd_vae_destroy": (None, [C.c_void_p]),
+    "dd_vae_has_encoder": (C.c_int, [C.c_void_p]),
+    "dd_vae_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dd_vae_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dd_profile_steps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                    C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "dd_profile_steps_chained": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -143,6 +146,7 @@ SIGNATURES = {
     "dd_dev_layernorm": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_embed": (C.c_int, [C.c_void_p] + [C.c_int] * 9 + [C.c_void_p] * 7 + [C.c_float] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_time_mlp": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 6 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
+    "dd_dev_vae_gather": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dd_dev_poison_workspaces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "dd_dev_graph_captures": (C.c_longlong, [C.c_void_p]),
     "dd_dev_last_sample_chains": (C.c_int, [C.c_void_p]),

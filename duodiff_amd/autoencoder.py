@@ -1,8 +1,10 @@
-"""Host-side mirror of the reference's frozen KL-VAE, decode side only (models/utils/autoencoder.py:452-516).
+"""Host-side mirror of the reference's frozen KL-VAE (models/utils/autoencoder.py:452-516).
 
 ``get_autoencoder(path)`` / ``FrozenAutoencoderKL.decode(z)`` keep the reference's call surface
 (``sampler.py:141-143,320-325``); the arithmetic runs in libduodiff.so (``dd_vae_*``): z/0.18215 -> post_quant_conv ->
-Decoder (ResNet / attention / upsample stack) as im2col + MFMA GEMMs.  The encoder is training-only and not built.
+Decoder (ResNet / attention / upsample stack) as im2col + MFMA GEMMs.  ``encode_moments`` / ``sample`` / ``encode``
+(:468-484) run the Encoder + quant_conv the same way when the state_dict carries every encode-side tensor; a checkpoint
+without them gives a decode-only object whose encode methods raise NotImplementedError.
 """
 import ctypes as C
 from collections import OrderedDict
@@ -53,12 +55,47 @@ def vae_param_shapes() -> "OrderedDict[str, tuple]":
     return s
 
 
-def synthetic_vae_state_dict(seed: int = 4321) -> "OrderedDict[str, torch.Tensor]":
-    """Seeded fp32 decode-side weights (no checkpoint exists offline): conv W ~ N(0, 1/fan_in), b ~ N(0, 0.02^2),
-    GroupNorm gamma ~ 1 + N(0, 0.1^2), beta ~ N(0, 0.02^2)."""
+def vae_encoder_param_shapes() -> "OrderedDict[str, tuple]":
+    """Encode-side tensors of the reference state_dict (encoder.* and quant_conv.*), name -> shape, in the modules' order."""
+    s = OrderedDict()
+
+    def conv(n, co, ci, k):
+        s[n + ".weight"] = (co, ci, k, k)
+        s[n + ".bias"] = (co,)
+
+    def norm(n, c):
+        s[n + ".weight"] = (c,)
+        s[n + ".bias"] = (c,)
+
+    def res(n, ci, co):
+        norm(n + ".norm1", ci); conv(n + ".conv1", co, ci, 3); norm(n + ".norm2", co); conv(n + ".conv2", co, co, 3)
+        if ci != co:
+            conv(n + ".nin_shortcut", co, ci, 1)
+
+    conv("encoder.conv_in", CH, 3, 3)
+    cin = CH
+    for lv in range(4):
+        cout = CH * CH_MULT[lv]
+        for j in range(2):
+            res(f"encoder.down.{lv}.block.{j}", cin, cout)
+            cin = cout
+        if lv != 3:
+            conv(f"encoder.down.{lv}.downsample.conv", cin, cin, 3)
+    res("encoder.mid.block_1", cin, cin)
+    norm("encoder.mid.attn_1.norm", cin)
+    for n in ("q", "k", "v", "proj_out"):
+        conv(f"encoder.mid.attn_1.{n}", cin, cin, 1)
+    res("encoder.mid.block_2", cin, cin)
+    norm("encoder.norm_out", cin)
+    conv("encoder.conv_out", 2 * Z_CH, cin, 3)
+    conv("quant_conv", 2 * Z_CH, 2 * Z_CH, 1)
+    return s
+
+
+def _synthetic(shapes, seed):
     g = torch.Generator(device="cpu").manual_seed(int(seed))
     sd = OrderedDict()
-    for name, shp in vae_param_shapes().items():
+    for name, shp in shapes.items():
         if name.endswith(".bias"):
             t = 0.02 * torch.randn(shp, generator=g)
         elif len(shp) == 1:
@@ -70,8 +107,21 @@ def synthetic_vae_state_dict(seed: int = 4321) -> "OrderedDict[str, torch.Tensor
     return sd
 
 
+def synthetic_vae_encoder_state_dict(seed: int = 8765) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded fp32 encode-side weights, drawn as synthetic_vae_state_dict draws the decode side but from a generator of their own
+    (the decode-side weights of a seed do not depend on whether the encoder's are asked for)."""
+    return _synthetic(vae_encoder_param_shapes(), seed)
+
+
+def synthetic_vae_state_dict(seed: int = 4321) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded fp32 decode-side weights (no checkpoint exists offline): conv W ~ N(0, 1/fan_in), b ~ N(0, 0.02^2),
+    GroupNorm gamma ~ 1 + N(0, 0.1^2), beta ~ N(0, 0.02^2)."""
+    return _synthetic(vae_param_shapes(), seed)
+
+
 class FrozenAutoencoderKL:
-    """decode-only mirror; ``scale_factor`` is fixed to the reference's 0.18215 in the engine."""
+    """``scale_factor`` is fixed to the reference's 0.18215 in the engine.  ``has_encoder``: the state_dict carried every encode-side
+    tensor (vae_encoder_param_shapes); otherwise the object decodes only."""
 
     def __init__(self, state_dict=None, scale_factor=0.18215, precision="bf16", max_chunk=4, max_latent=32):
         if abs(scale_factor - 0.18215) > 1e-12:
@@ -80,6 +130,7 @@ class FrozenAutoencoderKL:
         self.max_chunk, self.max_latent = int(max_chunk), int(max_latent)
         self.embed_dim = 4
         self._state, self._handle, self._ctx, self._device = None, None, None, None
+        self.has_encoder = False
         if state_dict is not None:
             self.load_state_dict(state_dict)
 
@@ -88,6 +139,10 @@ class FrozenAutoencoderKL:
         missing = [k for k in want if k not in state_dict]
         if strict and missing:
             raise RuntimeError(f"Error(s) in loading state_dict for FrozenAutoencoderKL: missing keys {missing}")
+        enc = vae_encoder_param_shapes()
+        self.has_encoder = all(k in state_dict for k in enc)      # all of them or none: a partial set loads decode-only
+        if self.has_encoder:
+            want.update(enc)
         sd = OrderedDict()
         for k, shp in want.items():
             t = torch.as_tensor(state_dict[k]).detach().to("cpu", torch.float32)
@@ -139,10 +194,59 @@ class FrozenAutoencoderKL:
         ctx.check(ctx.lib.dd_vae_decode(ctx.handle, h, _ptr(z), _ptr(out), B, hh, _stream_ptr(stream)))
         return out
 
+    def _need_encoder(self):
+        if not self.has_encoder:
+            raise NotImplementedError("this autoencoder was loaded without the encoder tensors (encoder.*, quant_conv.*): decode only")
+
+    def _eps(self, shape, generator):
+        """the reference's torch.randn_like(mean) (autoencoder.py:477), drawn on the CPU and copied over"""
+        return torch.randn(shape, generator=generator).to(self.device, torch.float32).contiguous()
+
+    def _encode(self, x, eps, want_moments, want_z, stream):
+        self._need_encoder()
+        ctx, h = self._engine()
+        x = x.to(self.device, torch.float32).contiguous()
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+            raise RuntimeError(f"expected images [B,3,H,H], got {tuple(x.shape)}")
+        B, hw = x.shape[0], x.shape[2]
+        moments = torch.empty(B, 2 * Z_CH, hw // 8, hw // 8, device=x.device, dtype=torch.float32) if want_moments else None
+        z = torch.empty(B, Z_CH, hw // 8, hw // 8, device=x.device, dtype=torch.float32) if want_z else None
+        if B > 0:
+            e = eps(z.shape) if (want_z and eps is not None) else None
+            ctx.check(ctx.lib.dd_vae_encode(ctx.handle, h, _ptr(x), _ptr(e), _ptr(moments), _ptr(z), B, hw, _stream_ptr(stream)))
+        return moments, z
+
+    def encode_moments(self, x, stream=None):
+        """reference autoencoder.py:468-471: [B,3,8h,8h] images in [-1, 1] -> [B,8,h,h] (mean | logvar), fp32 on the device."""
+        return self._encode(x, None, True, False, stream)[0]
+
+    def sample(self, moments, generator=None, stream=None):
+        """reference autoencoder.py:473-479: z = 0.18215 (mean + exp(0.5 clamp(logvar, -30, 20)) eps), eps = randn_like(mean)
+        from `generator` (None: the global CPU generator, as the reference draws)."""
+        self._need_encoder()
+        ctx, _ = self._engine()
+        moments = moments.to(self.device, torch.float32).contiguous()
+        if moments.dim() != 4 or moments.shape[1] != 2 * Z_CH or moments.shape[2] != moments.shape[3]:
+            raise RuntimeError(f"expected moments [B,8,h,h], got {tuple(moments.shape)}")
+        B, hh = moments.shape[0], moments.shape[2]
+        z = torch.empty(B, Z_CH, hh, hh, device=moments.device, dtype=torch.float32)
+        if B > 0 and hh > 0:
+            e = self._eps(z.shape, generator)
+            ctx.check(ctx.lib.dd_vae_sample(ctx.handle, _ptr(moments), _ptr(e), _ptr(z), B, hh, _stream_ptr(stream)))
+        return z
+
+    def encode(self, x, generator=None, sample=True, stream=None):
+        """reference autoencoder.py:481-484: sample(encode_moments(x)) in one engine call; sample=False: the mode, 0.18215 mean."""
+        return self._encode(x, (lambda shp: self._eps(shp, generator)) if sample else None, False, True, stream)[1]
+
     def __call__(self, inputs, fn="decode"):
-        if fn != "decode":
-            raise NotImplementedError("only decode is on the sampling path (encode is training-only)")
-        return self.decode(inputs)
+        if fn == "decode":
+            return self.decode(inputs)
+        if fn == "encode":
+            return self.encode(inputs)
+        if fn == "encode_moments":
+            return self.encode_moments(inputs)
+        raise NotImplementedError(fn)
 
     def __del__(self):
         try:
@@ -154,6 +258,7 @@ class FrozenAutoencoderKL:
 
 
 def get_autoencoder(pretrained_path, scale_factor=0.18215, precision="bf16"):
-    """reference autoencoder.py:503-516: build the fixed-config KL-VAE and load its checkpoint (decode side)."""
+    """reference autoencoder.py:503-516: build the fixed-config KL-VAE and load its checkpoint (the encoder too when the
+    checkpoint carries every one of its tensors)."""
     sd = torch.load(pretrained_path, map_location="cpu")
     return FrozenAutoencoderKL(sd, scale_factor, precision=precision)

@@ -365,10 +365,17 @@ hipError_t launch_head_dec(const HeadDecArgs& a, int D, int num_cus, hipStream_t
 hipError_t launch_ddpm_step(const float* x, const float* eps, const float* z, float* out,
                             StepCoef c, int use_noise, long long n, hipStream_t s);
 template <typename T> hipError_t launch_fill_random(T* p, long long n, unsigned seed, float scale, hipStream_t s);
-// ---- KL-VAE decoder bandwidth kernels (vae_kernels.hip)
+// ---- KL-VAE decoder / encoder bandwidth kernels (vae_kernels.hip)
 hipError_t launch_vae_input(const float* z, const float* w, const float* b, float inv_scale, float* out, int B, int HW, hipStream_t s);
 hipError_t launch_vae_output(const float* in, float* out, int B, int C, int HW, int ldc, hipStream_t s);
 template <typename T> hipError_t launch_im2col3x3(const T* src, T* dst, int B, int H, int W, int C, int up, int Kpad, hipStream_t s);
+// Downsample's gather: src [B, 2H, 2W, C] -> rows of the H x W output, pad on the bottom / right only
+template <typename T> hipError_t launch_im2col3x3_s2(const T* src, T* dst, int B, int H, int W, int C, int Kpad, hipStream_t s);
+hipError_t launch_vae_image(const float* x, float* out, int B, int HW, hipStream_t s);      // [B,3,HW] NCHW -> [B*HW, 4], channel 3 zero
+// h [B*HW, 8] -> quant_conv (w [8, 8], b [8]) -> moments [B,8,HW] and / or z [B,4,HW] (either may be null; eps null: z = scale * mean)
+hipError_t launch_vae_moments(const float* h, const float* w, const float* b, const float* eps, float* moments, float* z, int B, int HW,
+                              hipStream_t s);
+hipError_t launch_vae_sample(const float* moments, const float* eps, float* z, int B, int HW, hipStream_t s);
 template <typename T> hipError_t launch_im2col3x3_c4(const float* src, T* dst, int B, int H, int W, int Kpad, hipStream_t s);
 template <typename T> hipError_t launch_groupnorm(const float* x, float* part, const float* gamma, const float* beta, T* out, int B, int HW, int C, int swish, hipStream_t s);
 int groupnorm_partials(int B, int HW);

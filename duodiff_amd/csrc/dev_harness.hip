@@ -1,5 +1,5 @@
 // The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_qkv_attention, dd_dev_head_dec, dd_dev_gemm,
-// dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp): test scaffolding, not product.  Each one packs host operands as finalize packs a model's, launches what the model launches
+// dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather): test scaffolding, not product.  Each one packs host operands as finalize packs a model's, launches what the model launches
 // (launch_args.h), returns the outputs and times `iters` further launch sequences.  Buffers, transfers, timing and HIP errors go through
 // one DevScope (dev_scope.h); the context is reached through its accessors only.
 #include "../../include/duodiff.h"
@@ -402,6 +402,35 @@ int dd_dev_time_mlp(dd_ctx* c, int B, int D, int L, int extras, int normalize, c
     DEV_HIP(dev, hipStreamSynchronize(s));
     dev.download(x_tok_host, dX, n_tok * 4);
     DEV_HIP(dev, time_launches(s, iters, once, ms_out));
+    return dev.status();
+}
+
+int dd_dev_vae_gather(dd_ctx* c, int kind, int precision, int B, int H, int W, int Cn, const void* src_host, void* dst_host, size_t dst_bytes,
+                      void* stream) {
+    const bool bf = precision == DD_PREC_BF16;
+    if (!c || (!bf && precision != DD_PREC_FP32) || (kind != 0 && kind != 1) || B < 1 || H < 1 || W < 1 || !src_host || !dst_host) return DD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t esz = bf ? 2 : 4, kt = 128 / esz;
+    const int C = kind == 0 ? Cn : 4;
+    if (C < 1) return DD_ERR_INVALID;
+    const int Kpad = (int)((9 * (size_t)C + kt - 1) / kt * kt);          // as dd_vae_finalize pads a conv's K to the GEMM k-tile
+    const size_t rows = (size_t)B * H * W, need = rows * Kpad * esz;
+    if (dst_bytes < need) return ctx_fail(c, DD_ERR_INVALID, "vae_gather: dst_bytes below B H W Kpad elements");
+    if (kind == 0 && C % (16 / (int)esz)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "vae_gather: C must fill 16-byte vectors");
+    DevScope dev(c);
+    void* dD = dev.filled(dst_bytes, 0xFF);
+    if (kind == 0) {
+        const void* dS = dev.upload((const char*)src_host, rows * 4 * C * esz);
+        DEV_HIP(dev, bf ? launch_im2col3x3_s2<bf16_t>((const bf16_t*)dS, (bf16_t*)dD, B, H, W, C, Kpad, s)
+                        : launch_im2col3x3_s2<float>((const float*)dS, (float*)dD, B, H, W, C, Kpad, s));
+    } else {
+        const float* dS = dev.upload((const float*)src_host, rows * 3 * 4);
+        float* dI = dev.filled<float>(rows * 4 * 4, 0xFF);
+        DEV_HIP(dev, launch_vae_image(dS, dI, B, H * W, s));
+        DEV_HIP(dev, bf ? launch_im2col3x3_c4<bf16_t>(dI, (bf16_t*)dD, B, H, W, Kpad, s) : launch_im2col3x3_c4<float>(dI, (float*)dD, B, H, W, Kpad, s));
+    }
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(dst_host, dD, dst_bytes);
     return dev.status();
 }
 

@@ -1,7 +1,8 @@
-// Bandwidth kernels of the KL-VAE decoder (reference models/utils/autoencoder.py:320-449): layout
-// changes, im2col for the 3x3 convolutions (optionally through a nearest-2x upsample), GroupNorm(32)
-// + swish, row softmax of the single-head attention block.  All convolutions themselves run as
-// GEMMs on the MFMA kernels of gemm.hip (NHWC activations: a pixel is a GEMM row).
+// Bandwidth kernels of the KL-VAE decoder and encoder (reference models/utils/autoencoder.py:203-449): layout
+// changes, im2col for the 3x3 convolutions (optionally through a nearest-2x upsample, or with the stride 2 of
+// Downsample), GroupNorm(32) + swish, row softmax of the single-head attention block, quant_conv + the
+// posterior sample.  All convolutions themselves run as GEMMs on the MFMA kernels of gemm.hip (NHWC
+// activations: a pixel is a GEMM row).
 #include "dd_internal.h"
 
 namespace dd {
@@ -69,6 +70,90 @@ __global__ void im2col3x3_kernel(const T* __restrict__ src, T* __restrict__ dst,
         }
     }
     *reinterpret_cast<f32x4*>(dst + row * Kpad + (long long)kc * V) = val;
+}
+
+// im2col of Downsample (autoencoder.py:69-73): pad (0, 1, 0, 1) + 3x3 stride-2 convolution over NHWC `src` [B, 2H, 2W, C].  Row = output
+// pixel (y, x) of the H x W result, which reads input rows 2y .. 2y + 2 and columns 2x .. 2x + 2; row 2H / column 2W is the zero pad and
+// there is none on the top / left.  Columns as im2col3x3_kernel: (ky, kx, c), [9C, Kpad) zero, 16 B per thread.
+template <typename T>
+__global__ void im2col3x3_s2_kernel(const T* __restrict__ src, T* __restrict__ dst, int B, int H, int W, int C, int Kpad) {
+    constexpr int V = 16 / (int)sizeof(T);
+    const int cv = C / V;
+    const long long per_row = (long long)Kpad / V;
+    const long long total = (long long)B * H * W * per_row;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long long row = i / per_row;
+    const int kc = (int)(i % per_row);
+    f32x4 val = {0.f, 0.f, 0.f, 0.f};
+    const int tap = kc / cv, c0 = (kc % cv) * V;
+    if (tap < 9) {
+        const int x = (int)(row % W), y = (int)((row / W) % H), bi = (int)(row / ((long long)W * H));
+        const int yy = 2 * y + tap / 3, xx = 2 * x + tap % 3;
+        if (yy < 2 * H && xx < 2 * W)
+            val = *reinterpret_cast<const f32x4*>(src + (((long long)bi * 2 * H + yy) * 2 * W + xx) * C + c0);
+    }
+    *reinterpret_cast<f32x4*>(dst + row * Kpad + (long long)kc * V) = val;
+}
+
+// x [B,3,H,W] fp32 NCHW (an image in [-1, 1]) -> NHWC fp32 [B*H*W, 4], the fourth channel zero: the encoder's conv_in then gathers it
+// with im2col3x3_c4_kernel (K = 36, the weight's fourth-channel columns zero)
+__global__ void vae_image_kernel(const float* __restrict__ x, float* __restrict__ out, int B, int HW) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)B * HW) return;
+    const int bi = (int)(i / HW), p = (int)(i % HW);
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = x[((long long)bi * 3 + c) * HW + p];
+    reinterpret_cast<f32x4*>(out)[i] = v;
+}
+
+// FrozenAutoencoderKL.sample (autoencoder.py:473-479) for one element: scale * (mean + exp(0.5 clamp(logvar, -30, 20)) eps), each
+// product rounded on its own; exp is evaluated in double and rounded once (the correctly rounded fp32 exp).  use_eps false: the mode.
+__device__ __forceinline__ float vae_sample_one(float mean, float logvar, float eps, bool use_eps) {
+#pragma clang fp contract(off)
+    if (!use_eps) return 0.18215f * mean;
+    const float lv = fminf(fmaxf(logvar, -30.0f), 20.0f);
+    const float sd = (float)exp(0.5 * (double)lv);
+    return 0.18215f * (mean + sd * eps);
+}
+
+// conv_out rows [B*HW, 8] fp32 -> quant_conv 1x1 (8 -> 8, autoencoder.py:468-471) -> moments [B,8,HW] NCHW and / or z [B,4,HW]
+__global__ void vae_moments_kernel(const float* __restrict__ h, const float* __restrict__ w, const float* __restrict__ b,
+                                   const float* __restrict__ eps, float* __restrict__ moments, float* __restrict__ z, int B, int HW) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)B * HW) return;
+    const int bi = (int)(i / HW), p = (int)(i % HW);
+    float v[8], m[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v[c] = h[i * 8 + c];
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+        float a = b[o];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) a = fmaf(w[o * 8 + c], v[c], a);
+        m[o] = a;
+    }
+    if (moments) {
+#pragma unroll
+        for (int o = 0; o < 8; ++o) moments[((long long)bi * 8 + o) * HW + p] = m[o];
+    }
+    if (z) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const long long at = ((long long)bi * 4 + c) * HW + p;
+            z[at] = vae_sample_one(m[c], m[4 + c], eps ? eps[at] : 0.f, eps != nullptr);
+        }
+    }
+}
+
+// z = sample(moments [B,8,HW]) alone, elementwise over [B,4,HW]
+__global__ void vae_sample_kernel(const float* __restrict__ moments, const float* __restrict__ eps, float* __restrict__ z, int B, int HW) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)B * 4 * HW) return;
+    const long long per = 4LL * HW;
+    const long long bi = i / per, r = i % per;
+    z[i] = vae_sample_one(moments[bi * 2 * per + r], moments[bi * 2 * per + per + r], eps ? eps[i] : 0.f, eps != nullptr);
 }
 
 // conv_in has C = 4 input channels: K = 36, padded to Kpad; scalar gather
@@ -225,6 +310,27 @@ hipError_t launch_im2col3x3(const T* src, T* dst, int B, int H, int W, int C, in
     return hipGetLastError();
 }
 template <typename T>
+hipError_t launch_im2col3x3_s2(const T* src, T* dst, int B, int H, int W, int C, int Kpad, hipStream_t s) {
+    constexpr int V = 16 / (int)sizeof(T);
+    if (C % V || Kpad % V || Kpad < 9 * C || H < 1 || W < 1) return hipErrorInvalidValue;
+    const long long total = (long long)B * H * W * (Kpad / V);
+    hipLaunchKernelGGL(im2col3x3_s2_kernel<T>, grid1d(total), dim3(256), 0, s, src, dst, B, H, W, C, Kpad);
+    return hipGetLastError();
+}
+hipError_t launch_vae_image(const float* x, float* out, int B, int HW, hipStream_t s) {
+    hipLaunchKernelGGL(vae_image_kernel, grid1d((long long)B * HW), dim3(256), 0, s, x, out, B, HW);
+    return hipGetLastError();
+}
+hipError_t launch_vae_moments(const float* h, const float* w, const float* b, const float* eps, float* moments, float* z, int B, int HW,
+                              hipStream_t s) {
+    hipLaunchKernelGGL(vae_moments_kernel, grid1d((long long)B * HW), dim3(256), 0, s, h, w, b, eps, moments, z, B, HW);
+    return hipGetLastError();
+}
+hipError_t launch_vae_sample(const float* moments, const float* eps, float* z, int B, int HW, hipStream_t s) {
+    hipLaunchKernelGGL(vae_sample_kernel, grid1d((long long)B * 4 * HW), dim3(256), 0, s, moments, eps, z, B, HW);
+    return hipGetLastError();
+}
+template <typename T>
 hipError_t launch_im2col3x3_c4(const float* src, T* dst, int B, int H, int W, int Kpad, hipStream_t s) {
     hipLaunchKernelGGL(im2col3x3_c4_kernel<T>, grid1d((long long)B * H * W * Kpad), dim3(256), 0, s, src, dst, B, H, W, Kpad);
     return hipGetLastError();
@@ -256,6 +362,7 @@ hipError_t launch_cast(const float* x, T* out, long long n, hipStream_t s) {
 
 #define DD_INST(T)                                                                                                     \
     template hipError_t launch_im2col3x3<T>(const T*, T*, int, int, int, int, int, int, hipStream_t);                 \
+    template hipError_t launch_im2col3x3_s2<T>(const T*, T*, int, int, int, int, int, hipStream_t);                   \
     template hipError_t launch_im2col3x3_c4<T>(const float*, T*, int, int, int, int, hipStream_t);                    \
     template hipError_t launch_groupnorm<T>(const float*, float*, const float*, const float*, T*, int, int, int, int, \
                                             hipStream_t);                                                             \

@@ -95,8 +95,8 @@ def main(argv=None):
     from . import sampler
     args = sampler.get_args(argv)
     sampler.validate_solver(args)
-    if any(v is not None for v in (args.init_image, args.strength, args.known_image, args.known_mask)):
-        raise ValueError("--init_image / --strength / --known_image / --known_mask belong to the single-GPU sampler (duodiff_amd.sampler)")
+    if any(v is not None for v in (args.init_image, args.strength, args.known_image, args.known_mask)) or args.encode_images:
+        raise ValueError("--init_image / --strength / --known_image / --known_mask / --encode_images belong to the single-GPU sampler (duodiff_amd.sampler)")
     rank, world, local_rank = init()
     if torch.cuda.is_available():
         torch.cuda.set_device(local_rank % torch.cuda.device_count())   # (ranks may share a GPU when rehearsed on one)

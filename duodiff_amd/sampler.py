@@ -24,7 +24,8 @@ combination fused into the step kernel; the shallow model's own steps stay ungui
 name an explicit guide for a single-backbone run.  No labels are needed: unconditional models can be guided.
 
 Image-to-image and inpainting (engine options, not in the reference): ``--init_image x.npy --strength 0.5`` starts every loop from the
-given image noised to t = round(999 * 0.5) instead of from pure noise (SDEdit); ``--known_image x.npy --known_mask m.npy`` keeps the
+given image noised to t = round(999 * 0.5) instead of from pure noise (SDEdit; latent models: .npy latents, or pixel-space files with
+``--encode_images``, which the KL-VAE encoder of the engine turns into latents); ``--known_image x.npy --known_mask m.npy`` keeps the
 masked region of the image fixed while the rest is generated (RePaint's replacement rule without resampling), fused into the step kernel.
 
 DPM-Solver++ (engine option, not in the reference): ``--dpm_solver ode --dpm_solver_steps 20`` samples with the second-order multistep
@@ -536,17 +537,17 @@ def validate_autoguidance(args, config, config_late=None, config_guide=None):
                              f"{(mp.img_size, mp.patch_size, mp.in_chans)}")
 
 
-def _load_image_file(path, what, mp, latent):
-    """--init_image / --known_image / --known_mask: a .npy in the model's own space, or (pixel-space RGB models) a .png mapped through
-    2 v - 1 (the mask: its first channel, unmapped) -> float32 [N, C, S, S]"""
+def _load_image_file(path, what, mp, latent, pixels=False):
+    """--init_image / --known_image / --known_mask: a .npy in the model's own space, or (pixel-space RGB models, and latent models under
+    --encode_images: pixels) a .png mapped through 2 v - 1 (the mask: its first channel, unmapped) -> float32 [N, C, S, S]"""
     path = Path(path)
     mask = what == "--known_mask"
     if path.suffix.lower() == ".npy":
         a = np.asarray(np.load(path), np.float32)
     elif path.suffix.lower() == ".png":
-        if latent:
-            raise ValueError(f"{what} {path.name}: a latent model takes .npy latents only (there is no encoder)")
-        if mp.in_chans != 3:
+        if latent and not pixels:
+            raise ValueError(f"{what} {path.name}: a latent model takes .npy latents only, or pixel-space files with --encode_images")
+        if mp.in_chans != 3 and not pixels:
             raise ValueError(f"{what} {path.name}: .png needs an in_chans = 3 config, this one has in_chans = {mp.in_chans}")
         from matplotlib import pyplot as plt
         a = np.asarray(plt.imread(path), np.float32)
@@ -560,8 +561,22 @@ def _load_image_file(path, what, mp, latent):
 
 def validate_region(args, config):
     """The image-to-image and inpainting options against the config, before any GPU work: ValueError on a bad combination.  Returns
-    get_samples' init_image / strength / known_image / known_mask arguments, the files loaded."""
+    get_samples' init_image / strength / known_image / known_mask arguments, the files loaded.  With --encode_images the files are in
+    pixel space ([.., 3, 8 S, 8 S] images in [-1, 1], a [.., 1, 8 S, 8 S] mask) and main() passes the result through encode_region once
+    the autoencoder is loaded."""
     mp = ModelParams.from_dict(config)
+    pixels = bool(getattr(args, "encode_images", False))
+    if pixels:
+        if "autoencoder" not in config:
+            raise ValueError("--encode_images needs a latent model (a config with an autoencoder block); a pixel-space model takes its images as they are")
+        if args.init_image is None and args.known_image is None:
+            raise ValueError("--encode_images needs --init_image or --known_image")
+        if mp.in_chans != 4 or mp.img_size % 8 or mp.img_size > 32:
+            raise ValueError(f"--encode_images: the KL-VAE encoder gives 4-channel latents of a size that is a multiple of 8, at most 32; "
+                             f"this config has in_chans = {mp.in_chans}, img_size = {mp.img_size}")
+    elif getattr(args, "encode_mean", False):
+        raise ValueError("--encode_mean goes with --encode_images")
+    size = 8 * mp.img_size if pixels else mp.img_size
     if (args.known_image is None) != (args.known_mask is None):
         raise ValueError("--known_image and --known_mask go together")
     if (args.init_image is None) != (args.strength is None):
@@ -569,16 +584,38 @@ def validate_region(args, config):
     if args.strength is not None and not 0 < args.strength <= 1:
         raise ValueError(f"--strength {args.strength} outside (0, 1]")
     out = dict(init_image=None, strength=args.strength, known_image=None, known_mask=None)
-    for key, chans in (("init_image", mp.in_chans), ("known_image", mp.in_chans), ("known_mask", 1)):
+    for key, chans in (("init_image", 3 if pixels else mp.in_chans), ("known_image", 3 if pixels else mp.in_chans), ("known_mask", 1)):
         path = getattr(args, key)
         if path is None:
             continue
-        a = _load_image_file(path, "--" + key, mp, "autoencoder" in config)
-        if a.ndim != 4 or a.shape[0] not in (1, args.batch_size) or a.shape[1:] != (chans, mp.img_size, mp.img_size):
-            raise ValueError(f"--{key}: shape {list(a.shape)} does not match [1 or {args.batch_size}, {chans}, {mp.img_size}, {mp.img_size}]")
+        a = _load_image_file(path, "--" + key, mp, "autoencoder" in config, pixels)
+        if a.ndim != 4 or a.shape[0] not in (1, args.batch_size) or a.shape[1:] != (chans, size, size):
+            raise ValueError(f"--{key}: shape {list(a.shape)} does not match [1 or {args.batch_size}, {chans}, {size}, {size}]")
         if not np.isfinite(a).all() or (key == "known_mask" and ((a < 0) | (a > 1)).any()):
             raise ValueError(f"--{key}: " + ("values outside [0, 1]" if key == "known_mask" else "non-finite values"))
         out[key] = a
+    return out
+
+
+def reduce_mask_8x8(mask):
+    """A pixel-space mask [N, 1, 8 S, 8 S] at latent resolution [N, 1, S, S]: the minimum over every 8 x 8 block.  A latent pixel counts
+    as known only if every pixel under it is, so the generated region never shrinks, and a binary mask stays binary."""
+    m = np.asarray(mask, np.float32)
+    n, c, h, w = m.shape
+    return np.ascontiguousarray(m.reshape(n, c, h // 8, 8, w // 8, 8).min(axis=(3, 5)))
+
+
+def encode_region(region_kwargs, autoencoder, seed, mean=False):
+    """--encode_images: validate_region's pixel-space files -> what get_samples takes.  Each image goes through autoencoder.encode with a
+    generator of its own seeded with `seed` (the loop's noise streams are what they are without the flag), or its mode (mean); the mask
+    through reduce_mask_8x8."""
+    out = dict(region_kwargs)
+    for key in ("init_image", "known_image"):
+        if out[key] is not None:
+            z = autoencoder.encode(torch.from_numpy(out[key]), generator=torch.Generator().manual_seed(int(seed)), sample=not mean)
+            out[key] = z.cpu().numpy()
+    if out["known_mask"] is not None:
+        out["known_mask"] = reduce_mask_8x8(out["known_mask"])
     return out
 
 
@@ -691,6 +728,12 @@ def get_args(argv=None):
                    help="(engine option) inpainting: the image whose --known_mask region stays fixed (.npy / .png as --init_image)")
     p.add_argument("--known_mask", type=str, default=None,
                    help="(engine option) inpainting mask in [0, 1], 1 = keep (.npy [1 or B, 1, S, S], or the first channel of a .png)")
+    p.add_argument("--encode_images", action="store_true",
+                   help="(engine option) latent models: --init_image / --known_image / --known_mask are in pixel space (.png or .npy "
+                        "[1 or B, 3, 8S, 8S] in [-1, 1]; mask [1 or B, 1, 8S, 8S]); the images go through the KL-VAE encoder, the mask "
+                        "through an 8x8 minimum")
+    p.add_argument("--encode_mean", action="store_true",
+                   help="(engine option) with --encode_images: the posterior's mode 0.18215 mean instead of a sample")
     return p.parse_args(argv)
 
 
@@ -739,6 +782,9 @@ def main(argv=None):
     if "autoencoder" in config:                                              # reference sampler.py:320-325
         ae_path = args.autoencoder_checkpoint_path or config["autoencoder"]["autoencoder_checkpoint_path"]
         autoencoder = get_autoencoder(ae_path, precision=args.precision).to(model.device)
+    if args.encode_images:
+        print("Encode the images...")
+        region_kwargs = encode_region(region_kwargs, autoencoder, args.seed, mean=args.encode_mean)
 
     tic = time.time()
     samples, inter = get_samples(model=model, batch_size=args.batch_size, postprocessing=post, seed=args.seed,

@@ -368,13 +368,31 @@ int dd_sample_early_exit(dd_ctx* ctx, const dd_ee_sample_args* args, void* strea
 /* ---- KL-VAE decode: autoencoder.decode(x) at sampler.py:141-143 ---------------- */
 /* Replaces FrozenAutoencoderKL.decode (models/utils/autoencoder.py:486-490, Decoder :320-449) for the fixed ddconfig of
  * get_autoencoder (:503-516).  Parameters are set by the reference state_dict keys ("decoder.*", "post_quant_conv.*";
- * "encoder.*" / "quant_conv.*" are accepted and ignored).  z_dev [B,4,h,h] fp32 latents -> out_dev [B,3,8h,8h] fp32. */
+ * "encoder.*" / "quant_conv.*" feed the encoder below).  z_dev [B,4,h,h] fp32 latents -> out_dev [B,3,8h,8h] fp32. */
 typedef struct dd_vae dd_vae;
 int dd_vae_create(dd_ctx* ctx, int max_chunk, int max_latent, dd_vae** out);
 int dd_vae_set_param(dd_vae* v, const char* name, const float* host_data, const int64_t* shape, int ndim);
 int dd_vae_finalize(dd_vae* v, int precision);
 int dd_vae_decode(dd_ctx* ctx, dd_vae* v, const float* z_dev, float* out_dev, int B, int latent_hw, void* stream);
 void dd_vae_destroy(dd_vae* v);
+
+/* ---- KL-VAE encode (version 6 addition): pixel images for latent image-to-image and inpainting ---- */
+/* Replaces FrozenAutoencoderKL.encode_moments / sample / encode (models/utils/autoencoder.py:468-484, Encoder :203-317).
+ * The encoder is built by dd_vae_finalize iff EVERY "encoder.*" / "quant_conv.*" tensor (108 of them) was set; otherwise the
+ * object is decode-only and dd_vae_has_encoder returns 0.  An unknown encode-side name or a wrong shape is an error.
+ * dd_vae_encode: x_dev [B,3,8h,8h] fp32 in [-1, 1] -> moments_dev [B,8,h,h] (mean | logvar) and / or
+ * z_dev [B,4,h,h] = 0.18215 (mean + exp(0.5 clamp(logvar, -30, 20)) eps); either output may be NULL, not both.  eps_dev [B,4,h,h]
+ * is the caller's normal draw; NULL selects the mode, z = 0.18215 mean.  B is chunked by max_chunk as in dd_vae_decode.
+ * Rejected before anything is enqueued: a decode-only object (DD_ERR_UNSUPPORTED), image_hw not a multiple of 64
+ * (DD_ERR_UNSUPPORTED: the latent pixel count must be a multiple of 64, as for decode), image_hw > 8 max_latent, both outputs
+ * NULL, B < 1, NULL input (DD_ERR_INVALID).
+ * dd_vae_sample: the sample rule alone on moments_dev [B,8,h,h]; bit-identical to what dd_vae_encode writes for the same moments.
+ * Encode and decode of one dd_vae share ONE workspace: calls are ordered by the stream they are given; calls on different
+ * streams must be ordered by the caller. */
+int dd_vae_has_encoder(const dd_vae* v);
+int dd_vae_encode(dd_ctx* ctx, dd_vae* v, const float* x_dev, const float* eps_dev, float* moments_dev, float* z_dev, int B,
+                  int image_hw, void* stream);
+int dd_vae_sample(dd_ctx* ctx, const float* moments_dev, const float* eps_dev, float* z_dev, int B, int latent_hw, void* stream);
 
 /* ---- measurement support ------------------------------------------------------------ */
 /* Time `iters` back-to-back launches of the fc1 GEMM (fused bias+GELU epilogue) of model m at batch B with hipEvents

@@ -6,6 +6,7 @@
 #define DUODIFF_DEV_H
 
 #include "duodiff.h"
+#include <stddef.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -113,6 +114,16 @@ int dd_dev_embed(dd_ctx* ctx, int B, int C, int S, int P, int D, int extras, int
 int dd_dev_time_mlp(dd_ctx* ctx, int B, int D, int L, int extras, int normalize, const float* w1, const float* b1, const float* w2,
                     const float* b2, const float* pos, const float* t_vec, float t_state, float* x_tok_host, int iters, void* stream,
                     float* ms_out);
+
+/* Development harness for the two gathers of the KL-VAE encoder (vae_kernels.hip), alone on host arrays.
+ * kind 0: Downsample's stride-2 im2col (launch_im2col3x3_s2): src_host = NHWC [B, 2H, 2W, C] elements of `precision` (bf16 bits / fp32),
+ *         dst rows = the B H W output pixels, Kpad columns in order (ky, kx, c), columns [9 C, Kpad) zero.
+ * kind 1: the encoder's input path (launch_vae_image + launch_im2col3x3_c4): src_host = NCHW fp32 [B, 3, H, W], C is ignored;
+ *         dst rows = the B H W pixels, Kpad columns (ky, kx, c of 4) with c = 3 and columns [36, Kpad) zero.
+ * dst_host holds dst_bytes >= B H W Kpad elements of `precision`; it is filled with 0xFF bytes before the launch and comes back WHOLE, so
+ * the bytes behind the last row keep the canary.  A shape the launcher refuses is DD_ERR_UNSUPPORTED; nothing is launched. */
+int dd_dev_vae_gather(dd_ctx* ctx, int kind, int precision, int B, int H, int W, int C, const void* src_host, void* dst_host,
+                      size_t dst_bytes, void* stream);
 
 /* Kernel-variant switches for same-process A/B runs (tools/mlp_check.py, tools/all_configs.py).  They act on models
  * FINALIZED after the call (the first three) or on launches made after it; the product never sets them and the library

@@ -11,6 +11,7 @@ DD_ERR_INVALID, DD_ERR_NOT_FOUND, DD_ERR_STATE, DD_ERR_HIP, DD_ERR_NOMEM, DD_ERR
 DD_PREC_BF16, DD_PREC_FP32 = 0, 1
 DD_VAR_BETA_TILDE, DD_VAR_BETA = 0, 1
 DD_NOISE_NONE, DD_NOISE_BUFFER, DD_NOISE_PHILOX = 0, 1, 2
+DD_X0_STATIC, DD_X0_DYNAMIC = 0, 1
 DD_EE_MLP_PER_LAYER, DD_EE_MLP_PER_TIMESTEP, DD_EE_MLP_PER_LAYER_PER_TIMESTEP, DD_EE_ATTENTION_PROBE = 0, 1, 2, 3
 ABI_VERSION = 6
 DD_DEV_NO_FUSED_MLP, DD_DEV_NO_FUSED_PROJ, DD_DEV_NO_FUSED_HEAD, DD_DEV_GENERIC_EMBED, DD_DEV_MLP_EXTRAS_ONLY = 1, 2, 4, 8, 16
@@ -61,6 +62,11 @@ class dd_autoguidance(C.Structure):
 class dd_known_region(C.Structure):
     """a known region: x' is finished as m * (ka x0 + kb z2) + (1 - m) x' from the known image x0, the mask m and per-step rows ka, kb"""
     _fields_ = [("x0_dev", C.c_void_p), ("mask_dev", C.c_void_p), ("ka", C.POINTER(C.c_float)), ("kb", C.POINTER(C.c_float))]
+
+
+class dd_x0_threshold(C.Structure):
+    """x0 thresholding of the multistep loop: static (clamp to +-range) or dynamic (the image's own quantile scale, at most s_max)"""
+    _fields_ = [("mode", C.c_int32), ("quantile", C.c_float), ("range", C.c_float), ("s_max", C.c_float)]
 
 
 class dd_ee_sample_args(C.Structure):
@@ -121,6 +127,10 @@ SIGNATURES = {
                                           C.POINTER(dd_known_region), C.c_void_p]),
     "dd_sample_multistep_region": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_guidance),
                                              C.POINTER(dd_autoguidance), C.POINTER(dd_known_region), C.c_void_p]),
+    "dd_threshold_step": (C.c_int, [C.c_void_p] * 5 + [C.POINTER(dd_x0_threshold)] + [C.c_float] * 6 +
+                          [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "dd_sample_multistep_threshold": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_guidance),
+                                                C.POINTER(dd_autoguidance), C.POINTER(dd_known_region), C.POINTER(dd_x0_threshold), C.c_void_p]),
     "dd_bench_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
     "dd_vae_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "dd_vae_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),

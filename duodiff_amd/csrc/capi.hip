@@ -94,6 +94,8 @@ struct dd_ctx {
     DevBuf<float> h_stage;       //   and the history register the loop runs on ([B, C, S, S], staged like x)
     RowTable<KnownRow> ktab;     // the *_region loops: the known-region half of the rows,
     DevBuf<float> k_stage;       //   and the known image and mask the loop reads (x0 [B, C, S, S] | mask [B, 1, S, S], staged like x)
+    DevBuf<float> m_stage;       // dd_sample_multistep_threshold: the step's (guided) model output [B, C, S, S], chain k's images at its first image:
+                                 //   written by the output head and read by threshold_step_kernel within one step, never across steps
     int prof_kind = 0;           // dd_profile_select: which launches dd_profile_steps brackets (DD_PROF_*)
     unsigned dev_flags = 0;      // dd_dev_set_flags (include/duodiff_dev.h): kernel-variant switches of the development harness
 };
@@ -130,10 +132,14 @@ struct GraphKey {
     const void* aguide = nullptr;                                    // autoguidance: the guide model of a two-model step (null: CFG / unguided; gscale: the scale's bits)
     unsigned long long aserial = 0;                                  //   and its serial: an address can come back with another model behind it
     const void *kx0 = nullptr, *kmask = nullptr, *ktab = nullptr;    // known region: the chain's staged x0 / mask and the rows (null: none)
+    int tmode = -1;                                                  // x0 thresholding: the mode (-1: none), the bits of quantile, range and s_max,
+    unsigned tq = 0, tr = 0, ts = 0;                                 //   and the model-output scratch the step goes through
+    const void* tscratch = nullptr;
     bool operator==(const GraphKey& o) const {
         return x == o.x && y == o.y && B == o.B && noise == o.noise && variance == o.variance && num_cus == o.num_cus &&
                atab == o.atab && aux0 == o.aux0 && aux1 == o.aux1 && thr == o.thr && b0 == o.b0 && gnull == o.gnull && gscale == o.gscale &&
-               aguide == o.aguide && aserial == o.aserial && kx0 == o.kx0 && kmask == o.kmask && ktab == o.ktab;
+               aguide == o.aguide && aserial == o.aserial && kx0 == o.kx0 && kmask == o.kmask && ktab == o.ktab && tmode == o.tmode &&
+               tq == o.tq && tr == o.tr && ts == o.ts && tscratch == o.tscratch;
     }
     void guide(const dd_guidance* g) {
         if (g) { gnull = g->null_label; gscale = __builtin_bit_cast(unsigned, g->scale); }
@@ -542,10 +548,31 @@ struct Mods {
     bool region = false;                      //   which such an entry requires;
     Known kn{};                               //   staged on the device (stage_known) -- in a Slice, the chain's share of it
     const char* missing = nullptr;            // a _guided / _autoguided entry called without its struct: the rejection
+    const dd_x0_threshold* thr = nullptr;     // dd_sample_multistep_threshold's thresholding as the caller passed it,
+    bool thresholded = false;                 //   which that entry requires
 };
 Mods guided(const dd_guidance* g) { return Mods{.g = g, .missing = g ? nullptr : "null dd_guidance"}; }
 Mods autoguided(const dd_autoguidance* ag) { return Mods{.ag = ag, .missing = ag ? nullptr : "null dd_autoguidance"}; }
 Mods in_region(const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr) { return Mods{.g = g, .ag = ag, .kr = kr, .region = true}; }
+Mods thresholding(const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr, const dd_x0_threshold* thr) {
+    return Mods{.g = g, .ag = ag, .kr = kr, .region = kr != nullptr, .thr = thr, .thresholded = true};
+}
+
+// dd_x0_threshold's checks (null: ok) and the kernel's form of it for images of n elements
+const char* check_threshold(const dd_x0_threshold* t) {
+    if (!t) return "null dd_x0_threshold";
+    if (t->mode == DD_X0_STATIC) return t->range > 0.f && std::isfinite(t->range) ? nullptr : "dd_x0_threshold: range must be positive and finite";
+    if (t->mode != DD_X0_DYNAMIC) return "dd_x0_threshold: unknown mode";
+    if (!(t->quantile > 0.f && t->quantile <= 1.f)) return "dd_x0_threshold: quantile outside (0, 1]";
+    if (!(t->s_max >= 1.f)) return "dd_x0_threshold: s_max must be at least 1 (it may be +inf)";
+    return nullptr;
+}
+X0Threshold kernel_threshold(const dd_x0_threshold* t, long long n) {
+    if (t->mode == DD_X0_STATIC) return X0Threshold{0, 0, 0.f, t->range, 0.f};
+    const double pos = (double)t->quantile * (double)(n - 1);
+    const double i = std::floor(pos);
+    return X0Threshold{1, (int)i, (float)(pos - i), 0.f, t->s_max};
+}
 
 // the output head's arguments that the model and the chain determine, for B images whose decoder rows are in dec; a call site sets the rest by name
 FinalArgs final_args(const dd_model* m, const Chain& ch, const float* dec, const float* wconv, const float* bconv, int B) {
@@ -973,6 +1000,8 @@ struct StepOpts {
     int b0 = 0;                        // first image of a half-batch chain within the whole batch
     const HistRow* htab = nullptr;     // the multistep loop (atab set): the update adds row k's history term and writes h' to h [B, C, S, S]
     float* h = nullptr;
+    const X0Threshold* thr = nullptr;  // the thresholded multistep loop (htab set): the output head writes the model output to m_scratch [B, C, S, S]
+    float* m_scratch = nullptr;        //   and threshold_step_kernel finishes the step
 };
 
 // eps = model(x, t) of B images of chain ch enqueued on s, up to the output head: the guide's forward (autoguidance; each model takes
@@ -996,6 +1025,17 @@ int model_eps(dd_ctx* c, dd_model* m, const Chain& ch, const float* x_dev, const
 int enqueue_step(dd_ctx* c, dd_model* m, const Chain& ch, float* x_dev, const int64_t* y_dev, int B, hipStream_t s, const StepOpts& o) {
     FinalArgs fa;
     if (int rc = model_eps(c, m, ch, x_dev, y_dev, B, s, o, fa)) return rc;
+    if (o.thr) {   // the head writes the (guided) m and nothing else; the step's rule, its noise, the known region and the advance are the second launch's
+        fa.eps_out = o.m_scratch; fa.atab = o.atab; fa.b0 = o.b0;
+        DD_HIP(c, launch_final(fa, s));
+        ThresholdArgs ta{x_dev, o.m_scratch, nullptr, o.h, x_dev};
+        ta.st = ch.st; ta.coef = c->coef; ta.atab = o.atab; ta.htab = o.htab;
+        ta.noise_mode = o.noise_mode; ta.advance = o.advance; ta.b0 = o.b0; ta.pair_B = fa.pair_B;
+        ta.kx0 = o.mods.kn.x0; ta.kmask = o.mods.kn.mask; ta.ktab = o.mods.kn.ktab;
+        ta.thr = *o.thr; ta.B = B; ta.C = m->cfg.in_chans; ta.S = m->cfg.img_size;
+        DD_HIP(c, launch_threshold_step(ta, s));
+        return DD_OK;
+    }
     fa.x_in = x_dev; fa.z = o.z; fa.eps_out = o.eps_out; fa.x_out = x_dev;
     fa.noise_mode = o.noise_mode; fa.variance = o.variance; fa.advance = o.advance; fa.atab = o.atab; fa.b0 = o.b0;
     fa.htab = o.htab; fa.h = o.h;
@@ -1375,7 +1415,7 @@ void dd_ctx_destroy(dd_ctx* c) {
     if (c->ev_ee_join) (void)hipEventDestroy(c->ev_ee_join);
     for (StepState* st : c->st) if (st) (void)hipFree(st);
     if (c->coef) (void)hipFree(c->coef);
-    c->x_stage.release(); c->y_stage.release(); c->h_stage.release(); c->k_stage.release();
+    c->x_stage.release(); c->y_stage.release(); c->h_stage.release(); c->k_stage.release(); c->m_stage.release();
     c->atab.release(); c->htab.release(); c->ktab.release();
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     delete c;
@@ -1610,6 +1650,24 @@ int dd_multistep_step(dd_ctx* c, const float* x_dev, const float* m_dev, const f
     return DD_OK;
 }
 
+int dd_threshold_step(dd_ctx* c, const float* x_dev, const float* m_dev, const float* z_dev, float* h_dev, const dd_x0_threshold* thr, float a,
+                      float b, float cc, float d, float p, float q, int use_hist, float* out_dev, int B, int C, int S, void* stream) {
+    if (!c) return DD_ERR_INVALID;
+    if (!x_dev || !m_dev || !h_dev || !out_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    if (h_dev == x_dev || h_dev == out_dev || h_dev == m_dev) return ctx_fail(c, DD_ERR_INVALID, "h_dev must not alias x, m or out");
+    if (const char* bad = check_threshold(thr)) return ctx_fail(c, DD_ERR_INVALID, bad);
+    if (B < 0 || C < 1 || S < 1) return ctx_fail(c, DD_ERR_INVALID, "bad image shape");
+    const long long n = (long long)C * S * S;
+    if (n > THRESHOLD_MAX_ELEMS) return ctx_fail(c, DD_ERR_UNSUPPORTED, "x0 thresholding holds one image in LDS: at most 16384 elements per image");
+    if (B == 0) return DD_OK;
+    ThresholdArgs ta{x_dev, m_dev, z_dev, h_dev, out_dev};
+    ta.row = AffineRow{0.f, a, b, cc, z_dev ? 1 : 0, 0, 0, 0};
+    ta.hr = HistRow{d, p, q, use_hist ? 1 : 0};
+    ta.thr = kernel_threshold(thr, n); ta.B = B; ta.C = C; ta.S = S;
+    DD_HIP(c, launch_threshold_step(ta, (hipStream_t)stream));
+    return DD_OK;
+}
+
 int dd_known_blend(dd_ctx* c, const float* x_dev, const float* x0_dev, const float* mask_dev, const float* z2_dev, float ka, float kb,
                    float* out_dev, int B, int C, int S, void* stream) {
     if (!c) return DD_ERR_INVALID;
@@ -1808,6 +1866,13 @@ int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, Mods mo, void
     if (rc) return rc;
     if (!a->d || !a->p || !a->q || !a->hist) return ctx_fail(c, DD_ERR_INVALID, "null tensor / table");
     if (!a->h_dev) return ctx_fail(c, DD_ERR_INVALID, "null h_dev: the multistep loop needs its history register");
+    X0Threshold thr{};
+    if (mo.thresholded) {
+        if (const char* bad = check_threshold(mo.thr)) return ctx_fail(c, DD_ERR_INVALID, bad);
+        const long long n_img = (long long)a->first->cfg.in_chans * a->first->cfg.img_size * a->first->cfg.img_size;
+        if (n_img > THRESHOLD_MAX_ELEMS) return ctx_fail(c, DD_ERR_UNSUPPORTED, "x0 thresholding holds one image in LDS: at most 16384 elements per image");
+        thr = kernel_threshold(mo.thr, n_img);
+    }
     hipStream_t s = (hipStream_t)stream;
     const int n = a->n_steps;
     const bool switching = a->late && a->switch_after >= 0 && a->switch_after < n;
@@ -1820,6 +1885,9 @@ int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, Mods mo, void
     const size_t h_elems = (size_t)a->B * chw;
     if ((rc = c->h_stage.grow(c, h_elems))) return rc;
     float* h_run = c->h_stage.p;
+    if (mo.thresholded && (rc = c->m_stage.grow(c, h_elems))) return rc;      // (with h_stage: never on the launch path)
+    float* m_run = mo.thresholded ? c->m_stage.p : nullptr;
+    const X0Threshold* thr_p = mo.thresholded ? &thr : nullptr;
     DD_HIP(c, hipMemcpyAsync(h_run, a->h_dev, h_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
     if ((rc = stage_table_known(c, mo, a->first, a->B, n, s))) return rc;
     const AffineRow* atab = c->atab.dev.p;
@@ -1827,10 +1895,18 @@ int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, Mods mo, void
     Loop L{GRAPH_MULTISTEP, a->first, switching ? a->late : nullptr, n, switching ? a->switch_after : -1, a->x_dev, a->y_dev, a->B, mo,
            a->use_graph != 0};
     L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_table(st, atab, (unsigned long long)a->seed, ss); };
-    L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.atab = atab; k.aux0 = htab; k.aux1 = h_run; };
+    L.key = [&](GraphKey& k, const Slice&) {
+        k.noise = a->noise_mode; k.atab = atab; k.aux0 = htab; k.aux1 = h_run;
+        if (mo.thresholded) {
+            k.tmode = mo.thr->mode; k.tscratch = m_run;
+            k.tq = __builtin_bit_cast(unsigned, mo.thr->quantile); k.tr = __builtin_bit_cast(unsigned, mo.thr->range);
+            k.ts = __builtin_bit_cast(unsigned, mo.thr->s_max);
+        }
+    };
     L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
         return enqueue_step(c, m, ch, sl.x, sl.y, sl.B, ss, {.mods = sl.mods, .noise_mode = a->noise_mode, .advance = 1, .atab = atab, .b0 = sl.b0,
-                                                             .htab = htab, .h = h_run + (size_t)sl.b0 * chw});
+                                                             .htab = htab, .h = h_run + (size_t)sl.b0 * chw, .thr = thr_p,
+                                                             .m_scratch = m_run ? m_run + (size_t)sl.b0 * chw : nullptr});
     };
     L.tail = [&](int, hipStream_t ss) -> int {
         DD_HIP(c, hipMemcpyAsync(a->h_dev, h_run, h_elems * sizeof(float), hipMemcpyDeviceToDevice, ss));
@@ -1867,6 +1943,11 @@ int dd_sample_multistep_autoguided(dd_ctx* c, const dd_multistep_sample_args* a,
 int dd_sample_multistep_region(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag,
                                const dd_known_region* kr, void* stream) {
     return sample_multistep(c, a, in_region(g, ag, kr), stream);
+}
+int dd_sample_multistep_threshold(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag,
+                                  const dd_known_region* kr, const dd_x0_threshold* thr, void* stream) {
+    if (c && g && ag) return ctx_fail(c, DD_ERR_INVALID, "classifier-free guidance and autoguidance are exclusive");
+    return sample_multistep(c, a, thresholding(g, ag, kr, thr), stream);
 }
 
 // One early-exit sampling step on the device (reference eesampler.py:56-81): EarlyExitUViT.forward with every head and
@@ -1931,6 +2012,9 @@ int dd_dev_poison_workspaces(dd_ctx* c, dd_model* m, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (int rc = ensure_chain_ws(c, m, s)) return rc;
     for (int k = 0; k < 2; ++k) DD_HIP(c, hipMemsetAsync(m->wsarena[k], 0xFF, m->ws_bytes[k], s));
+    // the context's model-output scratch of the thresholded loop, sized for this model's largest batch (it only grows)
+    if (int rc = c->m_stage.grow(c, (size_t)m->cfg.max_batch * m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size)) return rc;
+    DD_HIP(c, hipMemsetAsync(c->m_stage.p, 0xFF, c->m_stage.n * sizeof(float), s));
     return DD_OK;
 }
 

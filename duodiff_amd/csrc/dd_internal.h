@@ -390,6 +390,36 @@ hipError_t launch_multistep_step(const float* x, const float* m, const float* z,
 // out = known(x, x0, mask, ka, kb, z2) elementwise on [B, C, S, S] (mask [B, 1, S, S]; z2 null: none): the unfused known-region rule
 hipError_t launch_known_blend(const float* x, const float* x0, const float* mask, const float* z2, float ka, float kb, float* out, int B, int C,
                               int S, hipStream_t s);
+// x0 thresholding of a multistep step (step_update.h; include/duodiff.h dd_x0_threshold) as the kernel takes it
+struct X0Threshold {
+    int dynamic;            // 0: static, xh = clamp(x0, +-range); 1: dynamic, the image's own scale s
+    int i;                  // dynamic: floor(quantile (n - 1)) in double on the host, n = C S S
+    float f;                //          and (float)(quantile (n - 1) - i)
+    float range, s_max;
+};
+constexpr int THRESHOLD_MAX_ELEMS = 16384;    // one image's x0 lives in LDS (64 KB)
+// The thresholded multistep step on B images [B, C, S, S], one workgroup per image: x0 = p x + q m, the image's scale, xh, then
+// x' = a x + b xh [+ d h] [+ c z], h' = xh, x' finished by the known region where one is given.  Two ways to name the row:
+//   st set:  the loop -- row st->t_final of atab / htab (/ ktab), noise_mode 0 / 2 (Philox: batch-wide pixel ids from b0), advance as
+//            FinalArgs::advance; pair_B > 0 stores x' to image b + pair_B too (classifier-free guidance)
+//   st null: dd_threshold_step -- the row by value (row, hr), z a buffer or null
+struct ThresholdArgs {
+    const float* x; const float* m; const float* z; float* h; float* out;
+    StepState* st = nullptr;
+    const StepCoef* coef = nullptr;
+    const AffineRow* atab = nullptr;
+    const HistRow* htab = nullptr;
+    AffineRow row{};
+    HistRow hr{};
+    int noise_mode = 0, advance = 0, b0 = 0, pair_B = 0;
+    const float* kx0 = nullptr;
+    const float* kmask = nullptr;
+    const KnownRow* ktab = nullptr;
+    X0Threshold thr{};
+    int B = 0, C = 0, S = 0;
+};
+hipError_t launch_threshold_step(const ThresholdArgs& a, hipStream_t s);
+
 // AttentionProbe operands of one layer (capi.hip finalize folds them): u [D], Wv^T [D, D], bv [D], W0^T [D, D], b0 [D], w2 [D], b2 [1]
 struct AttnProbeW { const float *u, *wvt, *bv, *w0t, *b0, *w2, *b2; };
 hipError_t launch_ee_attn_probe(const float* x, const AttnProbeW& w, float* out, int B, int L, int D, hipStream_t s);

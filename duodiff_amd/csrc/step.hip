@@ -215,6 +215,199 @@ __global__ void multistep_step_kernel(const float* x, const float* __restrict__ 
     out[i] = v;
 }
 
+// ------------------------------------------------------------------------------------------
+// The thresholded multistep step (step_update.h: x0 thresholding; ThresholdArgs), one workgroup of 1024 threads per image.  It needs an
+// order statistic of the image's |x0| inside the step, so it cannot ride in the output head: that launch writes the (guided) m of the step
+// and this one finishes it.  Like the head it is a chain of dependent round trips, so every global load is issued up front -- x, m, h, and
+// where used z, the known image and the mask, W = 4 elements (16 bytes) per access -- and the Philox draws and the known region's
+// ka x0 + kb z2 are computed in their shadow; a thread keeps its 16 elements' operands in registers across the selection.
+//   1. x0 = p x + q m goes to LDS (at most 16 384 floats, 64 KB).
+//   2. dynamic: v[i] by a radix select on the keys bits(|x0|), which order as unsigned integers: four passes of 8-bit digits from the top,
+//      each a 256-bin LDS histogram (integer LDS adds) of the keys that match the digits chosen so far, scanned by the first wave for the
+//      bin that holds rank i.  One more pass counts the keys <= v[i] and takes the smallest key above: v[i + 1] is that key if exactly
+//      i + 1 keys are <= v[i] (and i + 1 < n), else v[i].  Exact, deterministic (integer adds commute), five passes for any bits.
+//   3. s, xh = clamp(x0, +-s) / s (static: clamp alone), the update, the known region, the stores: x' (guided: the twin image too), h' = xh.
+// x and out may alias: a thread reads its own elements before it writes them, and no workgroup reads another image (the twin is only written).
+// W = 1: the same with scalar accesses (S * S no multiple of 4, or a pointer not 16-byte aligned).
+// ------------------------------------------------------------------------------------------
+template <int W>
+__device__ __forceinline__ void load_w(float (&d)[W], const float* p) {
+    if constexpr (W == 4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+        d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
+    } else {
+        d[0] = *p;
+    }
+}
+template <int W>
+__device__ __forceinline__ void store_w(float* p, const float (&d)[W]) {
+    if constexpr (W == 4) *reinterpret_cast<f32x4*>(p) = f32x4{d[0], d[1], d[2], d[3]};
+    else *p = d[0];
+}
+__device__ __forceinline__ float pick(const f32x4& v, int c) { return c == 0 ? v[0] : c == 1 ? v[1] : c == 2 ? v[2] : v[3]; }
+
+template <int W>
+__global__ void __launch_bounds__(1024) threshold_step_kernel(const ThresholdArgs a) {
+#pragma clang fp contract(off)
+    constexpr int NT = 1024, SLOTS = THRESHOLD_MAX_ELEMS / NT / W;     // a thread's share: 16 elements, in SLOTS accesses
+    __shared__ __attribute__((aligned(16))) float x0s[THRESHOLD_MAX_ELEMS];
+    __shared__ unsigned hist[256];
+    __shared__ unsigned sel[4];      // the pass's digit, the rank within it; keys <= v[i], the smallest key above v[i]
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int hw = a.S * a.S, n = a.C * hw;
+    const long long base = (long long)b * n;
+    const bool loop = a.st != nullptr;
+    const StepRule<true> rule = loop ? StepRule<true>(a.st, a.coef, a.atab, a.htab, a.noise_mode, 0, a.advance)
+                                     : StepRule<true>(a.row.a, a.row.b, a.row.c, a.hr, a.z != nullptr);
+    const bool kn_on = a.kx0 != nullptr;
+    const KnownRule krule(kn_on ? a.ktab : nullptr, true, rule.t, a.noise_mode);
+    float xv[SLOTS][W], hv[SLOTS][W], zv[SLOTS][W], kv[SLOTS][W], km[SLOTS][W];
+    // ---- 1. every load, x0 to LDS
+#pragma unroll
+    for (int j = 0; j < SLOTS; ++j) {
+        const int e0 = (tid + j * NT) * W;
+#pragma unroll
+        for (int w = 0; w < W; ++w) { xv[j][w] = 0.f; hv[j][w] = 0.f; zv[j][w] = 0.f; kv[j][w] = 0.f; km[j][w] = 0.f; }
+        if (e0 < n) {
+            float mv[W];
+            load_w<W>(xv[j], a.x + base + e0);
+            load_w<W>(mv, a.m + base + e0);
+            load_w<W>(hv[j], a.h + base + e0);            // (not behind the row: used only where hr.hist is set)
+            if (rule.reads_z()) load_w<W>(zv[j], a.z + base + e0);
+            if (kn_on) {
+                load_w<W>(kv[j], a.kx0 + base + e0);
+                load_w<W>(km[j], a.kmask + (long long)b * hw + e0 % hw);
+            }
+            float x0[W];
+#pragma unroll
+            for (int w = 0; w < W; ++w) x0[w] = rule.history(xv[j][w], mv[w]);
+            store_w<W>(&x0s[e0], x0);
+        }
+    }
+    // Philox z (and the known region's z2): the batch-wide pixel id, the step's counter, the two stream words, as final_tiled_kernel draws
+    // them -- one draw serves a pixel's channels, so a slot reuses the previous slot's draws where it holds the same pixels of the next channel
+    const bool zdraw = rule.draws(), z2draw = kn_on && krule.draws();
+    if (zdraw || z2draw) {
+        const unsigned long long seed = a.st->seed;
+        f32x4 zc[W], z2c[W];
+        int drawn = -1;
+#pragma unroll
+        for (int j = 0; j < SLOTS; ++j) {
+            const int e0 = (tid + j * NT) * W;
+            if (e0 < n) {
+                const int c = e0 / hw, pix = e0 - c * hw;
+                if (pix != drawn) {
+#pragma unroll
+                    for (int w = 0; w < W; ++w) {
+                        const unsigned long long id = (unsigned long long)(b + a.b0) * hw + pix + w;
+                        if (zdraw) zc[w] = philox_normal4(seed, id, rule.ctr);
+                        if (z2draw) z2c[w] = philox_normal4(seed, id, rule.ctr, PHILOX_KNOWN);
+                    }
+                    drawn = pix;
+                }
+#pragma unroll
+                for (int w = 0; w < W; ++w) {
+                    if (zdraw) zv[j][w] = pick(zc[w], c);
+                    if (kn_on) kv[j][w] = krule.value(kv[j][w], z2draw ? pick(z2c[w], c) : 0.f);
+                }
+            }
+        }
+    } else if (kn_on) {
+#pragma unroll
+        for (int j = 0; j < SLOTS; ++j)
+#pragma unroll
+            for (int w = 0; w < W; ++w) kv[j][w] = krule.value(kv[j][w], 0.f);
+    }
+    __syncthreads();
+    if (b == 0 && tid == 0) rule.advance(a.st);      // (no workgroup reads t / t_model)
+    // ---- 2. the image's scale
+    float s = a.thr.range;
+    if (a.thr.dynamic) {
+        unsigned prefix = 0, pmask = 0, rank = (unsigned)a.thr.i;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) hist[tid] = 0;
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < SLOTS; ++j) {
+                const int e0 = (tid + j * NT) * W;
+                if (e0 < n) {
+                    float v[W];
+                    load_w<W>(v, &x0s[e0]);
+#pragma unroll
+                    for (int w = 0; w < W; ++w) {
+                        const unsigned key = __float_as_uint(v[w]) & 0x7fffffffu;
+                        if ((key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+                    }
+                }
+            }
+            __syncthreads();
+            if (tid < 64) {      // bins 4 tid .. 4 tid + 3; the lane whose bins hold the rank names the digit
+                const unsigned c0 = hist[4 * tid], c1 = hist[4 * tid + 1], c2 = hist[4 * tid + 2], c3 = hist[4 * tid + 3];
+                const unsigned sum = c0 + c1 + c2 + c3;
+                unsigned inc = sum;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const unsigned up = __shfl_up(inc, o);
+                    if (tid >= o) inc += up;
+                }
+                const unsigned exc = inc - sum;
+                if (rank >= exc && rank < inc) {
+                    unsigned r = rank - exc, dg = 0;
+                    if (r >= c0) { r -= c0; dg = 1; if (r >= c1) { r -= c1; dg = 2; if (r >= c2) { r -= c2; dg = 3; } } }
+                    sel[0] = 4 * tid + dg; sel[1] = r;
+                }
+            }
+            __syncthreads();
+            prefix |= sel[0] << shift; pmask |= 0xffu << shift; rank = sel[1];
+        }
+        if (tid == 0) { sel[2] = 0; sel[3] = 0xffffffffu; }
+        __syncthreads();
+        unsigned le = 0, above = 0xffffffffu;
+#pragma unroll
+        for (int j = 0; j < SLOTS; ++j) {
+            const int e0 = (tid + j * NT) * W;
+            if (e0 < n) {
+                float v[W];
+                load_w<W>(v, &x0s[e0]);
+#pragma unroll
+                for (int w = 0; w < W; ++w) {
+                    const unsigned key = __float_as_uint(v[w]) & 0x7fffffffu;
+                    if (key <= prefix) ++le;
+                    else above = min(above, key);
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            le += __shfl_xor(le, o);
+            above = min(above, (unsigned)__shfl_xor(above, o));
+        }
+        if ((tid & 63) == 0) { atomicAdd(&sel[2], le); atomicMin(&sel[3], above); }
+        __syncthreads();
+        const bool next = sel[2] == (unsigned)a.thr.i + 1u && a.thr.i + 1 < n;
+        s = threshold_scale(__uint_as_float(prefix), __uint_as_float(next ? sel[3] : prefix), a.thr.f, a.thr.s_max);
+    }
+    // ---- 3. xh, the update, the known region, the stores
+    const long long pair = (long long)a.pair_B * n;
+#pragma unroll
+    for (int j = 0; j < SLOTS; ++j) {
+        const int e0 = (tid + j * NT) * W;
+        if (e0 < n) {
+            float x0[W], xh[W], out[W];
+            load_w<W>(x0, &x0s[e0]);
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+                xh[w] = threshold_clip(x0[w], s, a.thr.dynamic != 0);
+                out[w] = rule.apply(xv[j][w], xh[w], zv[j][w], hv[j][w]);
+                if (kn_on) out[w] = known_mix(out[w], kv[j][w], km[j][w]);
+            }
+            store_w<W>(a.h + base + e0, xh);
+            store_w<W>(a.out + base + e0, out);
+            if (a.pair_B > 0) store_w<W>(a.out + base + pair + e0, out);
+        }
+    }
+}
+
 __global__ void set_state_kernel(StepState* st, int t, unsigned long long seed) {
     st->t = t;
     st->t_final = t;
@@ -344,6 +537,21 @@ hipError_t launch_multistep_step(const float* x, const float* m, const float* z,
     hipLaunchKernelGGL(multistep_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, m, z, h, out, a, b, c, d, p, q, use_hist, n);
     return hipGetLastError();
 }
+hipError_t launch_threshold_step(const ThresholdArgs& a, hipStream_t s) {
+    const long long hw = (long long)a.S * a.S, n = hw * a.C;
+    if (a.B < 1 || n < 1 || n > THRESHOLD_MAX_ELEMS || !a.x || !a.m || !a.h || !a.out) return hipErrorInvalidValue;
+    if (a.thr.dynamic && (a.thr.i < 0 || a.thr.i >= n)) return hipErrorInvalidValue;
+    if (a.st ? (!a.atab || !a.htab || !a.coef || a.z) : (a.kx0 || a.pair_B > 0)) return hipErrorInvalidValue;
+    if (a.kx0 && (!a.kmask || !a.ktab)) return hipErrorInvalidValue;
+    bool vec = hw % 4 == 0;      // 16-byte accesses: every image then starts on a 16-byte boundary of an aligned buffer
+    for (const void* p : {(const void*)a.x, (const void*)a.m, (const void*)a.z, (const void*)a.h, (const void*)a.out, (const void*)a.kx0,
+                          (const void*)a.kmask})
+        vec = vec && (uintptr_t)p % 16 == 0;
+    if (vec) hipLaunchKernelGGL(threshold_step_kernel<4>, dim3(a.B), dim3(1024), 0, s, a);
+    else hipLaunchKernelGGL(threshold_step_kernel<1>, dim3(a.B), dim3(1024), 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_ee_select(const float* outs, const float* eps, const float* cls, float thr, int depth, int B, long long chw,
                             float* mo, int* idx, float* err_mean, hipStream_t s) {
     const long long n = (long long)B * chw;

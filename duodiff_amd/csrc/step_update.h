@@ -124,6 +124,19 @@ __device__ __forceinline__ float known(float xp, float x0, float m, float ka, fl
     if (use_z2 && kb != 0.f) kn = kn + kb * z2;
     return m * kn + (1.f - m) * xp;
 }
+// known() in two halves, for a kernel that has x0 and z2 long before x' (threshold_step_kernel holds one register per element instead
+// of two): known(xp, x0, m, ...) == known_mix(xp, known_value(x0, ...), m), the same products and sums in the same order
+__device__ __forceinline__ float known_value(float x0, float ka, float kb, float z2, bool use_z2) {
+#pragma clang fp contract(off)
+    float kn = ka * x0;
+    if (use_z2 && kb != 0.f) kn = kn + kb * z2;
+    return kn;
+}
+__device__ __forceinline__ float known_mix(float xp, float kn, float m) {
+#pragma clang fp contract(off)
+    if (m == 0.f) return xp;
+    return m * kn + (1.f - m) * xp;
+}
 // row t of a loop's known-region table (t as StepRule reads it: the timestep of the DDPM loop, the step index of a table-driven one),
 // loaded behind the step state like the rule's own row
 struct KnownRule {
@@ -133,7 +146,26 @@ struct KnownRule {
         : row(ktab ? ktab[table ? t : (t < 0 ? 0 : (t > 999 ? 999 : t))] : KnownRow{0.f, 0.f}), philox(noise_mode == 2) {}   // (null: no known region)
     __device__ __forceinline__ bool draws() const { return philox && row.kb != 0.f; }
     __device__ __forceinline__ float apply(float xp, float x0, float m, float z2) const { return known(xp, x0, m, row.ka, row.kb, z2, philox); }
+    __device__ __forceinline__ float value(float x0, float z2) const { return known_value(x0, row.ka, row.kb, z2, philox); }
 };
+
+// x0 thresholding of a multistep step (dd_x0_threshold): the step's data prediction x0 = p x + q m (StepRule::history) is pulled back
+// before it drives the update, and the update then takes it in m's place -- a and b are the UNFOLDED row, b multiplying xh:
+//     static   xh = min(max(x0, -r), r)
+//     dynamic  s  = v[i] + f (v[i1] - v[i]),  v = |x0| of ONE image ascending (sub, mul, add);  s = min(max(s, 1), smax)
+//              xh = min(max(x0, -s), s) / s          (correctly rounded division)
+//     x' = StepRule<true>::apply(x, xh, z, h)        h' = xh
+// v[i], v[i1] come from an exact selection on the bit patterns of |x0| (threshold_step_kernel), never from an approximation; i and f
+// from the host (dd_internal.h X0Threshold).
+__device__ __forceinline__ float threshold_scale(float vi, float vi1, float f, float s_max) {
+#pragma clang fp contract(off)
+    const float s = vi + f * (vi1 - vi);
+    return fminf(fmaxf(s, 1.f), s_max);
+}
+__device__ __forceinline__ float threshold_clip(float x0, float s, bool divide) {
+    const float v = fminf(fmaxf(x0, -s), s);
+    return divide ? __fdiv_rn(v, s) : v;
+}
 
 // eesampler.py:61-67: idx[b] = first layer i in [0, depth] with c[i][b] <= threshold, where c[depth][b] = 0 closes the
 // list (torch.argmax of an all-False column is 0)

@@ -127,6 +127,19 @@ class Context:
                                               float(d), float(p), float(q), int(bool(use_hist)), _ptr(out), x.numel(), _stream_ptr(stream)))
         return out
 
+    def threshold_step(self, x, m, z, h, threshold, a, b, c, d, p, q, use_hist, out=None, stream=None):
+        """The thresholded multistep row on device tensors [B,C,S,S] (dd_threshold_step): x0 = p*x + q*m, xh = x0 clipped (threshold:
+        an X0Threshold), out = a*x + b*xh [+ d*h if use_hist] [+ c*z if z is not None], then h <- xh.  a, b: the UNFOLDED row.  out may be x."""
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[2] == x.shape[3]
+        B, Cc, S, _ = x.shape
+        for v in (m, h) + ((z,) if z is not None else ()):
+            assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == x.shape
+        out = torch.empty_like(x) if out is None else out
+        thr = threshold_struct(threshold)
+        self.check(self.lib.dd_threshold_step(self.handle, _ptr(x), _ptr(m), _ptr(z), _ptr(h), C.byref(thr), float(a), float(b), float(c),
+                                              float(d), float(p), float(q), int(bool(use_hist)), _ptr(out), B, Cc, S, _stream_ptr(stream)))
+        return out
+
     def known_blend(self, x, x0, mask, z2, ka, kb, out=None, stream=None):
         """The known-region rule on device tensors (dd_known_blend): kn = ka*x0 [+ kb*z2 if kb != 0 and z2 is not None];
         out = x where mask == 0, else mask*kn + (1 - mask)*x.  x, x0 [B,C,S,S], mask [B,1,S,S]; out may be x."""
@@ -326,7 +339,24 @@ class KnownRegion(NamedTuple):
     kb: np.ndarray
 
 
-def _loop_call(ctx, args, plain, guidance, region, x):
+class X0Threshold(NamedTuple):
+    """A thresholded loop's `threshold` argument.  mode "static": x0 is clamped to [-range, range]; mode "dynamic": each image's x0 is
+    clamped to +-s and divided by s, s = the `quantile` of its |x0| (linear interpolation), at least 1 and at most s_max."""
+    mode: str
+    quantile: float = 0.995
+    range: float = 1.0
+    s_max: float = float("inf")
+
+
+def threshold_struct(threshold):
+    """X0Threshold -> the C ABI's dd_x0_threshold (the engine checks the values)"""
+    if threshold.mode not in ("static", "dynamic"):
+        raise ValueError(f"threshold mode must be 'static' or 'dynamic', not {threshold.mode!r}")
+    return L.dd_x0_threshold(L.DD_X0_DYNAMIC if threshold.mode == "dynamic" else L.DD_X0_STATIC, float(threshold.quantile),
+                             float(threshold.range), float(threshold.s_max))
+
+
+def _loop_call(ctx, args, plain, guidance, region, x, threshold=None):
     """The loop entry of this argument struct as call(stream): `plain` (guidance None), its _guided form (guidance = (scale, null_label):
     classifier-free), its _autoguided form (guidance = Autoguidance(guide, scale)) or, with a KnownRegion, its _region form, which
     takes either kind of guidance, or none, beside the dd_known_region.  No entry takes both kinds of guidance."""
@@ -335,9 +365,12 @@ def _loop_call(ctx, args, plain, guidance, region, x):
         ag = C.byref(L.dd_autoguidance(guidance.guide.handle, float(guidance.scale)))
     elif guidance is not None:
         g = C.byref(guidance_struct(guidance))
-    if region is None:
+    if region is None and threshold is None:
         keep = None
         name, extra = plain + ("" if guidance is None else "_autoguided" if g is None else "_guided"), [r for r in (g, ag) if r is not None]
+    elif region is None:
+        keep = None
+        name, extra = plain + "_threshold", [g, ag, None, C.byref(threshold_struct(threshold))]
     else:
         B, Cc, S, _ = x.shape
         n_steps = args.n_steps if hasattr(args, "n_steps") else args.t_start - args.t_end + 1
@@ -347,6 +380,8 @@ def _loop_call(ctx, args, plain, guidance, region, x):
         assert ka.shape == kb.shape == (n_steps,)
         kr = L.dd_known_region(region.x0.data_ptr(), region.mask.data_ptr(), *(v.ctypes.data_as(C.POINTER(C.c_float)) for v in keep))
         name, extra = plain + "_region", [g, ag, C.byref(kr)]
+        if threshold is not None:
+            name, extra = plain + "_threshold", extra + [C.byref(threshold_struct(threshold))]
     fn = getattr(ctx.lib, name)
     return lambda st, keep=keep: fn(ctx.handle, C.byref(args), *extra, st)     # (a byref keeps its struct alive, the closure the arrays)
 
@@ -462,12 +497,22 @@ def sample_multistep_region_loop(ctx: Context, first: Model, late, x, region: Kn
                                   guidance)
 
 
-def _sample_multistep_loop(ctx, first, late, x, region, h, rows, switch_after, y, seed, counter_base, noise, use_graph, stream, guidance):
+def sample_multistep_threshold_loop(ctx: Context, first: Model, late, x, h, rows, threshold: X0Threshold, *, region=None, switch_after=None,
+                                    y=None, seed=0, counter_base=0, noise="philox", use_graph=True, stream=None, guidance=None):
+    """dd_sample_multistep_threshold: sample_multistep_loop on UNFOLDED rows (sampler.multistep_coefficients(..., unfolded=True) and its
+    DDIM / DDPM forms) with every step's data prediction x0 = p[k] x + q[k] m_k thresholded: x <- a[k] x + b[k] xh [+ d[k] h] [+ c[k] z],
+    h <- xh.  region (a KnownRegion) and guidance are optional, as in the other loops."""
+    return _sample_multistep_loop(ctx, first, late, x, region, h, rows, switch_after, y, seed, counter_base, noise, use_graph, stream,
+                                  guidance, threshold)
+
+
+def _sample_multistep_loop(ctx, first, late, x, region, h, rows, switch_after, y, seed, counter_base, noise, use_graph, stream, guidance,
+                           threshold=None):
     args = L.dd_multistep_sample_args()
     tab = _step_table(args, first, late, rows, "tabcdpq", ("noise", "hist"), switch_after, counter_base)  # noqa: F841
     assert h.is_cuda and h.dtype == torch.float32 and h.is_contiguous() and h.shape == x.shape
     args.h_dev = h.data_ptr()
-    return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, _loop_call(ctx, args, "dd_sample_multistep", guidance, region, x))
+    return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, _loop_call(ctx, args, "dd_sample_multistep", guidance, region, x, threshold))
 
 
 def sample_early_exit_loop(ctx: Context, model: Model, x, threshold, *, t_start=999, t_end=0, y=None, seed=0, noise="philox",

@@ -43,8 +43,9 @@ import torch
 
 from .config import ModelParams, load_config
 from .autoencoder import get_autoencoder
-from .engine import (Autoguidance, Context, KnownRegion, sample_affine_loop, sample_affine_region_loop, sample_loop,
-                     sample_multistep_loop, sample_multistep_region_loop, sample_region_loop, schedule_tables)
+from .engine import (Autoguidance, Context, KnownRegion, X0Threshold, sample_affine_loop, sample_affine_region_loop, sample_loop,
+                     sample_multistep_loop, sample_multistep_region_loop, sample_multistep_threshold_loop, sample_region_loop,
+                     schedule_tables, threshold_struct)
 from .uvit import UViT
 
 
@@ -122,7 +123,7 @@ def affine_coefficients(kind, t, s=None, eta=0.0):
 MULTISTEP_KINDS = ("dpmsolver++", "sde-dpmsolver++")
 
 
-def multistep_rows(kind, alphas_bar, order=2, parametrization="predict_noise", lower_order_final=True):
+def multistep_rows(kind, alphas_bar, order=2, parametrization="predict_noise", lower_order_final=True, unfolded=False):
     """float64 DPM-Solver++ (Lu et al., 2022) rows of the multistep update, for the steps alphas_bar[k] -> alphas_bar[k + 1]
     (len(alphas_bar) = N + 1 values of abar along the grid; the model sees the first N):
 
@@ -132,6 +133,8 @@ def multistep_rows(kind, alphas_bar, order=2, parametrization="predict_noise", l
     or "sde-dpmsolver++" (the midpoint 2M SDE: every row here has noise = 1; multistep_coefficients drops the z of a step landing on
     t = 0).  order 2: step 0 is first order (no history yet), and with lower_order_final the last step too (on the product grid it
     lands on t = 0, where lambda jumps: a second-order step there extrapolates with r ~ 0.2 and overshoots).
+    unfolded: the rows of the thresholded loop, x' = a x + b xh + ..., xh = the thresholded data prediction p x + q m: a = A,
+    b = phi w0 (the default folds x0 into them: a = A + phi w0 p, b = phi w0 q).
     Returns a dict of float64 arrays a, b, c, d, p, q and int32 arrays hist, noise."""
     if kind not in MULTISTEP_KINDS:
         raise ValueError(f"solver must be one of {MULTISTEP_KINDS}, not {kind!r}")
@@ -168,6 +171,8 @@ def multistep_rows(kind, alphas_bar, order=2, parametrization="predict_noise", l
             A, phi = sigma[k + 1] / sigma[k] * np.exp(-h[k]), alpha[k + 1] * -np.expm1(-2.0 * h[k])
             c = sigma[k + 1] * np.sqrt(-np.expm1(-2.0 * h[k]))
         rows["a"][k], rows["b"][k], rows["c"][k], rows["d"][k] = A + phi * w0 * p, phi * w0 * q, c, phi * w1
+        if unfolded:
+            rows["a"][k], rows["b"][k] = A, phi * w0
         rows["p"][k], rows["q"][k] = p, q
         rows["hist"][k] = int(w1 != 0.0)
         rows["noise"][k] = int(kind == "sde-dpmsolver++")
@@ -185,7 +190,64 @@ def multistep_grid(n_steps, t0=999):
     return np.linspace(t0, 0, n + 1).round().astype(int)
 
 
-def multistep_coefficients(kind, ts, order=2, parametrization="predict_noise"):
+def _data_prediction(parametrization, ab_t):
+    """(p, q) of x0 = p x + q m in float64 at alphas_bar ab_t: the model predicts the noise or the data"""
+    if parametrization == "predict_previous":
+        raise ValueError("x0 thresholding needs a model that predicts the noise or the data (predict_noise / predict_original), "
+                         "not predict_previous: there is no x0")
+    if parametrization == "predict_original":
+        return 0.0, 1.0
+    if parametrization != "predict_noise":
+        raise ValueError(parametrization)
+    return 1.0 / np.sqrt(ab_t), -np.sqrt(1.0 - ab_t) / np.sqrt(ab_t)
+
+
+def unfolded_rows(kind, ts, eta=0.0, parametrization="predict_noise"):
+    """The reference's own samplers as float64 UNFOLDED rows of the thresholded loop (x' = a x + b xh + c z, xh the thresholded
+    x0 = p x + q m, no history), from the engine's bit-exact tables:
+      "ddim"  over the descending grid ts (N + 1 timesteps), step t -> s: a = dir / sigma_t, b = alpha_s - a alpha_t with
+              dir = sqrt(1 - abar_s - sig2), sig2 = betas_tilde[t] eta and c = sig2 (the reference scales its noise by sigma^2,
+              sampler.py:112-120, and reads the model output as the noise whatever the parametrization: so does (p, q) here)
+      "ddpm"  the ancestral steps at the timesteps ts (t -> t - 1): the posterior mean's coefficients on x and x0 (sampler.py:59-72)
+              and c = sqrt(betas_tilde[t]); (p, q) from the parametrization
+    Returns a dict of float64 arrays a, b, c, d, p, q and int32 arrays hist (0), noise (the step does not land on the final image)."""
+    tb = {k: v.astype(np.float64) for k, v in schedule_tables().items()}
+    ab = tb["alphas_bar"]
+    ts = np.asarray(ts, np.int64)
+    if kind == "ddim":
+        t, s_ = ts[:-1], ts[1:]
+        sig2 = tb["betas_tilde"][t] * float(eta)
+        with np.errstate(invalid="ignore"):     # (a large eta on the step onto t = 0: the reference's direction term is NaN, sampler.py:116)
+            a = np.sqrt(1.0 - ab[s_] - sig2) / np.sqrt(1.0 - ab[t])
+        b = np.sqrt(ab[s_]) - a * np.sqrt(ab[t])
+        c, noise = sig2, s_ > 0
+        pq = [_data_prediction("predict_noise", v) for v in ab[t]]
+        if parametrization == "predict_previous":
+            _data_prediction(parametrization, 0.5)
+    elif kind == "ddpm":
+        t = ts
+        a = np.sqrt(tb["alphas"][t]) * (1.0 - tb["alphas_bar_previous"][t]) / (1.0 - ab[t])
+        b = np.sqrt(tb["alphas_bar_previous"][t]) * tb["betas"][t] / (1.0 - ab[t])
+        c, noise = np.sqrt(tb["betas_tilde"][t]), t > 0
+        pq = [_data_prediction(parametrization, v) for v in ab[t]]
+    else:
+        raise ValueError(kind)
+    n = len(t)
+    return {"a": a, "b": b, "c": np.asarray(c, np.float64), "d": np.zeros(n), "p": np.array([v[0] for v in pq]).reshape(n),
+            "q": np.array([v[1] for v in pq]).reshape(n), "hist": np.zeros(n, np.int32), "noise": noise.astype(np.int32)}
+
+
+def unfolded_coefficients(kind, ts, eta=0.0, parametrization="predict_noise"):
+    """unfolded_rows as the fp32 rows a loop takes (each coefficient rounded once), with t: the model timesteps"""
+    ts = np.asarray(ts, np.int64)
+    r = unfolded_rows(kind, ts, eta, parametrization)
+    out = {k: r[k].astype(np.float32) for k in "abcdpq"}
+    out["t"] = (ts[:-1] if kind == "ddim" else ts).astype(np.float32)
+    out["hist"], out["noise"] = r["hist"], r["noise"]
+    return out
+
+
+def multistep_coefficients(kind, ts, order=2, parametrization="predict_noise", unfolded=False):
     """The fp32 rows of a DPM-Solver++ run over the integer grid ts (descending, N + 1 timesteps, the last one usually 0), from the
     engine's bit-exact schedule tables: multistep_rows in float64, each coefficient rounded once.  Returns a dict of per-step arrays
     t (float32 model timesteps t_0 .. t_{N-1}), a, b, c, d, p, q (float32), hist, noise (int32).  The SDE draws z on every step but
@@ -194,7 +256,7 @@ def multistep_coefficients(kind, ts, order=2, parametrization="predict_noise"):
     if ts.ndim != 1 or len(ts) < 2 or (ts < 0).any() or (ts > 999).any() or (np.diff(ts) >= 0).any():
         raise ValueError("ts must be a strictly decreasing grid of timesteps in [0, 999] with at least two points")
     ab = schedule_tables()["alphas_bar"].astype(np.float64)[ts]
-    r = multistep_rows(kind, ab, order, parametrization)
+    r = multistep_rows(kind, ab, order, parametrization, unfolded=unfolded)
     out = {k: r[k].astype(np.float32) for k in "abcdpq"}
     out["t"] = ts[:-1].astype(np.float32)
     out["hist"] = r["hist"]
@@ -247,12 +309,16 @@ def start_timestep(strength=None):
 
 
 def step_plan(parametrization, timesteps_save=(), has_late=False, t_switch=np.inf, num_steps=1000, use_ddim=False, ddim_steps=50,
-              ddim_eta=0.0, solver=None, solver_steps=20, solver_order=2, strength=None):
+              ddim_eta=0.0, solver=None, solver_steps=20, solver_order=2, strength=None, threshold=None):
     """The StepPlan of get_samples' arguments (parametrization: "predict_noise" | "predict_original" | "predict_previous", or None
     for a postprocessing function of elsewhere; has_late: a late model is given).  Host arithmetic only, no torch.
     strength (None or 1: the start at t = 999): the loops start at t0 = start_timestep(strength) -- DDPM at t0, the DDIM and solver grids
-    built from t0 down with the same spacing rule and step count; the late model's rule is unchanged (by timestep)."""
+    built from t0 down with the same spacing rule and step count; the late model's rule is unchanged (by timestep).
+    threshold (anything but None): the plan of the thresholded loop -- kind "multistep" on UNFOLDED rows for all three samplers
+    (multistep_coefficients(..., unfolded=True), unfolded_coefficients); predict_previous has no x0 and is rejected."""
     t0 = start_timestep(strength)
+    if threshold is not None:
+        _data_prediction(parametrization if parametrization is not None else "predict_noise", 0.5)
     # the DDPM loop switches AFTER the step at t == 1000 - t_switch (sampler.py:135-136): a t_switch outside [1, 1000] (0, negative,
     # > 1000, inf) never matches a t in 999..0, i.e. the first model runs every step
     in_range = has_late and np.isfinite(t_switch) and 1 <= int(t_switch) <= 1000
@@ -262,7 +328,7 @@ def step_plan(parametrization, timesteps_save=(), has_late=False, t_switch=np.in
         grid = multistep_grid(solver_steps, t0)                               # range check first
         if parametrization is None:
             raise ValueError("postprocessing must be one of this module's predict_*_postprocessing functions")
-        kind, rows = "multistep", multistep_coefficients(solver, grid, solver_order, parametrization)
+        kind, rows = "multistep", multistep_coefficients(solver, grid, solver_order, parametrization, unfolded=threshold is not None)
         switch_after = next((k for k, t in enumerate(rows["t"]) if t < 1000 - int(t_switch)), None) if in_range else None
         lands = [int(s) if s > 0 else -1 for s in grid[1:]]
     elif use_ddim:
@@ -271,15 +337,22 @@ def step_plan(parametrization, timesteps_save=(), has_late=False, t_switch=np.in
         if (np.diff(ts) >= 0).any():
             raise ValueError(f"{ddim_steps} DDIM steps do not fit a start at t = {t0}: lower the steps or raise the strength")
         pairs = [(int(t), int(s)) for t, s in zip(ts[:-1], ts[1:])]
-        kind, rows = "affine", _affine_rows([t for t, _ in pairs], [affine_coefficients("ddim", t, s, ddim_eta) for t, s in pairs],
-                                            [s > 0 for _, s in pairs])
+        if threshold is not None:
+            if parametrization is None:
+                raise ValueError("postprocessing must be one of this module's predict_*_postprocessing functions")
+            kind, rows = "multistep", unfolded_coefficients("ddim", ts, ddim_eta, parametrization)
+        else:
+            kind, rows = "affine", _affine_rows([t for t, _ in pairs], [affine_coefficients("ddim", t, s, ddim_eta) for t, s in pairs],
+                                                [s > 0 for _, s in pairs])
         # :122-123: the late model from the step after the first t < 1000 - t_switch (raw t_switch: <= 0 switches after step 0)
         switch_after = next((k + 1 for k, (t, _) in enumerate(pairs) if t < 1000 - t_switch), None) if has_late else None
         lands = [s if s > 0 else -1 for _, s in pairs]
     else:
         # sampler.py:129-139: t = 999 .. 1000 - num_steps; predict_original / predict_previous (:59-79) as affine rows
         ts = list(range(t0, max(t0 - int(num_steps), -1), -1))
-        if parametrization == "predict_noise":
+        if threshold is not None and parametrization in ("predict_noise", "predict_original"):
+            kind, rows = "multistep", unfolded_coefficients("ddpm", ts, 0.0, parametrization)
+        elif parametrization == "predict_noise":
             kind, rows = "ddpm", {"t": np.array(ts, np.float32), "noise": np.array([t > 0 for t in ts], np.int32)}
         elif parametrization in ("predict_original", "predict_previous"):
             kind, rows = "affine", _affine_rows(ts, [affine_coefficients(parametrization, t) for t in ts], [t > 0 for t in ts])
@@ -334,7 +407,7 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
                 late_model=None, t_switch=np.inf, *, noise: str = "torch_cpu", use_graph: bool = True,
                 num_steps: int = 1000, return_device_tensor: bool = False, cfg_scale=None, cfg_null_label: int = 1000,
                 solver=None, solver_steps: int = 20, solver_order: int = 2, autoguidance_scale=None, guide_model=None,
-                init_image=None, strength=None, known_image=None, known_mask=None):
+                init_image=None, strength=None, known_image=None, known_mask=None, threshold=None):
     """reference sampler.py:82-155.  Returns (samples[B,H,W,C] float32 numpy = (x+1)/2, intermediates).
 
     cfg_scale (None: the unguided loops, unchanged): classifier-free guidance of every step's model output,
@@ -362,6 +435,9 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
         are finished as mask * (ka known_image + kb z2) + (1 - mask) x' at the noise level the step lands on (known_rows), so the
         result equals known_image where mask == 1.  noise="device": fused into the loops, z2 from the device generator;
         noise="torch_cpu": step by step, z2 drawn from the torch CPU stream after the step's z.
+    threshold (an engine.X0Threshold; engine option): every step's predicted image x0 is clipped to a fixed range (mode "static") or to
+        its own quantile scale and rescaled (mode "dynamic", Imagen's dynamic thresholding) before it drives the update; all three
+        samplers then run as the thresholded multistep loop on unfolded rows.  predict_noise / predict_original models, pixel space.
     """
     if noise not in ("torch_cpu", "device"):
         raise ValueError("noise must be 'torch_cpu' or 'device'")
@@ -381,7 +457,11 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
     if (known_image is None) != (known_mask is None):
         raise ValueError("known_image and known_mask go together")
     plan = step_plan(_PARAMETRIZATIONS.get(postprocessing), timesteps_save, late_model is not None, t_switch, num_steps, use_ddim,
-                     ddim_steps, ddim_eta, solver, solver_steps, solver_order, strength)
+                     ddim_steps, ddim_eta, solver, solver_steps, solver_order, strength, threshold)
+    if threshold is not None:
+        if autoencoder is not None:
+            raise ValueError("x0 thresholding is for pixel-space models: a latent model's x0 is a latent, not an image in [-1, 1]")
+        threshold_struct(threshold)
     device = model.device
     guidance = None if cfg_scale is None else (float(cfg_scale), int(cfg_null_label))
     if guidance is not None and y is None:
@@ -431,6 +511,9 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
                 if plan.kind == "affine":
                     (sample_affine_region_loop if known else sample_affine_loop)(
                         ctx, m0, m1, x, *known, seg["t"], seg["a"], seg["b"], seg["c"], seg["noise"], switch_after=sw, counter_base=k0, **kw)
+                elif threshold is not None:
+                    sample_multistep_threshold_loop(ctx, m0, m1, x, h, seg, threshold, region=known[0] if known else None, switch_after=sw,
+                                                    counter_base=k0, **kw)
                 else:
                     (sample_multistep_region_loop if known else sample_multistep_loop)(
                         ctx, m0, m1, x, *known, h, seg, switch_after=sw, counter_base=k0, **kw)
@@ -457,6 +540,8 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
                     ctx.ddpm_step(x, eps, z, int(t), out=x)
                 elif plan.kind == "affine":
                     ctx.affine_step(x, eps, z, tab["a"][k], tab["b"][k], tab["c"][k], out=x)
+                elif threshold is not None:
+                    ctx.threshold_step(x, eps, z, h, threshold, *(tab[key][k] for key in "abcdpq"), tab["hist"][k], out=x)
                 else:
                     ctx.multistep_step(x, eps, z, h, *(tab[key][k] for key in "abcdpq"), tab["hist"][k], out=x)
             if region is not None:                                           # z2: its own draw, after the step's z
@@ -634,6 +719,36 @@ def validate_solver(args):
         raise ValueError(f"--dpm_solver_steps {args.dpm_solver_steps} outside [1, 999]")
 
 
+def validate_threshold(args, config):
+    """The x0 thresholding options against the config, before any GPU work: ValueError on a bad combination.  Returns get_samples'
+    threshold argument (None: off)."""
+    clip, dyn, smax = args.clip_x0, args.dynamic_threshold, args.threshold_max
+    if clip is None and dyn is None:
+        if smax is not None:
+            raise ValueError("--threshold_max goes with --dynamic_threshold")
+        return None
+    if clip is not None and dyn is not None:
+        raise ValueError("--clip_x0 and --dynamic_threshold are exclusive")
+    if "autoencoder" in config:
+        raise ValueError("--clip_x0 / --dynamic_threshold are for pixel-space models: with an autoencoder block x0 is a latent, not an image in [-1, 1]")
+    if args.parametrization == "predict_previous":
+        raise ValueError("--clip_x0 / --dynamic_threshold need --parametrization predict_noise or predict_original: predict_previous has no x0")
+    if args.noise == "torch_cpu":
+        raise ValueError("--clip_x0 / --dynamic_threshold run in the device-resident loops: --noise device")
+    if clip is not None:
+        if smax is not None:
+            raise ValueError("--threshold_max goes with --dynamic_threshold")
+        if not (clip > 0 and math.isfinite(clip)):
+            raise ValueError(f"--clip_x0 {clip} must be positive and finite")
+        return X0Threshold("static", range=float(clip))
+    if not 0 < dyn <= 1:
+        raise ValueError(f"--dynamic_threshold {dyn} outside (0, 1]")
+    smax = float("inf") if smax is None else float(smax)
+    if not smax >= 1:
+        raise ValueError(f"--threshold_max {smax} must be at least 1")
+    return X0Threshold("dynamic", quantile=float(dyn), s_max=smax)
+
+
 def solver_kwargs(args):
     """get_samples' solver arguments from the command line"""
     return dict(solver=SOLVERS[args.dpm_solver] if args.dpm_solver is not None else None, solver_steps=args.dpm_solver_steps,
@@ -734,6 +849,12 @@ def get_args(argv=None):
                         "through an 8x8 minimum")
     p.add_argument("--encode_mean", action="store_true",
                    help="(engine option) with --encode_images: the posterior's mode 0.18215 mean instead of a sample")
+    p.add_argument("--clip_x0", type=float, nargs="?", const=1.0, default=None, metavar="R",
+                   help="(engine option) clip every step's predicted image x0 to [-R, R] (default R = 1) before it drives the update")
+    p.add_argument("--dynamic_threshold", type=float, default=None, metavar="Q",
+                   help="(engine option) dynamic thresholding (Imagen): per image, s = the Q-quantile of |x0| (at least 1), x0 clipped to "
+                        "[-s, s] and divided by s.  Exclusive with --clip_x0; pixel-space predict_noise / predict_original models, --noise device")
+    p.add_argument("--threshold_max", type=float, default=None, metavar="S", help="(engine option) with --dynamic_threshold: s is at most S (>= 1)")
     return p.parse_args(argv)
 
 
@@ -765,6 +886,7 @@ def main(argv=None):
     config_guide = load_config(args.guide_config_path) if args.guide_config_path else None
     validate_autoguidance(args, config, config_late, config_guide)
     region_kwargs = validate_region(args, config_late if config_late is not None else config)
+    threshold = validate_threshold(args, config_late if config_late is not None else config)
     rows = 2 * args.batch_size if args.cfg_scale is not None else args.batch_size
     model, mp = build_model(config, args.checkpoint_path, args.precision, rows)
     model_late = None
@@ -793,7 +915,7 @@ def main(argv=None):
                                  y=y, autoencoder=autoencoder, late_model=model_late, t_switch=args.t_switch,
                                  timesteps_save=args.timesteps_save, noise=args.noise, use_graph=not args.no_graph,
                                  cfg_scale=args.cfg_scale, cfg_null_label=args.cfg_null_label, **solver_kwargs(args),
-                                 autoguidance_scale=args.autoguidance_scale, guide_model=model_guide, **region_kwargs)
+                                 autoguidance_scale=args.autoguidance_scale, guide_model=model_guide, threshold=threshold, **region_kwargs)
     tac = time.time()
     dump_statistics(tac - tic, out, args.batch_size)
     if args.no_png:

@@ -345,6 +345,40 @@ int dd_sample_affine_region(dd_ctx* ctx, const dd_affine_sample_args* args, cons
 int dd_sample_multistep_region(dd_ctx* ctx, const dd_multistep_sample_args* args, const dd_guidance* g, const dd_autoguidance* ag,
                                const dd_known_region* kr, void* stream);
 
+/* ---- x0 clipping and dynamic thresholding (Ho et al. 2020; Saharia et al. 2022, Imagen; Lu et al. 2022) of the multistep loop ---------- */
+/* The multistep row's data prediction x0 = p*x + q*m (its history expression) is pulled back before it drives the update, and the update
+ * takes the result xh in m's place: the rows a, b are UNFOLDED (b multiplies xh, not m; duodiff_amd.sampler multistep_coefficients(...,
+ * unfolded=True)).  fp32, contraction off, each product rounded on its own, in the order written:
+ *     static  (range r > 0):   xh = min(max(x0, -r), r)
+ *     dynamic (quantile qt in (0, 1], ceiling s_max >= 1, may be +inf):
+ *         v[0 .. n-1] = |x0| of ONE image's n = C*S*S elements, ascending
+ *         pos = qt * (n - 1) in double; i = floor(pos); f = (float)(pos - i)
+ *         s  = v[i] + f * (v[min(i+1, n-1)] - v[i]);   s = min(max(s, 1), s_max)
+ *         xh = min(max(x0, -s), s) / s                  (correctly rounded division)
+ *     out = a*x + b*xh [+ d*h if use_hist] [+ c*z if drawn]            h = xh
+ * The order statistic is an exact, deterministic selection on the bit patterns of |x0| (+-inf and denormals are ordinary values; results
+ * for NaN inputs are unspecified, the call terminates for any bits).  One image is at most 16384 elements (DD_ERR_UNSUPPORTED beyond).
+ * A known region finishes out afterwards, unchanged. */
+enum { DD_X0_STATIC = 0, DD_X0_DYNAMIC = 1 };
+typedef struct dd_x0_threshold {
+    int32_t mode;           /* DD_X0_STATIC | DD_X0_DYNAMIC                     */
+    float quantile;         /* dynamic: in (0, 1]                               */
+    float range;            /* static: > 0, finite                              */
+    float s_max;            /* dynamic: >= 1, may be +inf                       */
+} dd_x0_threshold;
+/* the rule alone on caller buffers [B,C,S,S]: x_dev and out_dev may alias; h_dev (aliasing neither x, m nor out) is read iff use_hist
+ * and always written; z_dev NULL: no c*z term */
+int dd_threshold_step(dd_ctx* ctx, const float* x_dev, const float* m_dev, const float* z_dev, float* h_dev, const dd_x0_threshold* thr,
+                      float a, float b, float c, float d, float p, float q, int use_hist, float* out_dev, int B, int C, int S,
+                      void* stream);
+/* dd_sample_multistep_region plus thr, on unfolded rows: g, ag and kr are optional (NULL), g and ag exclusive.  Every step's output head
+ * writes the (guided) model output to a context-owned scratch image and a second launch, one workgroup per image, finishes the step.
+ * Captured graphs are keyed on the mode and the bits of quantile, range and s_max.  DD_ERR_INVALID (with dd_last_error) before anything
+ * is enqueued for a NULL thr, an unknown mode, quantile outside (0, 1], range <= 0 or not finite, s_max < 1 or NaN, host noise, an
+ * early-exit model, and every check dd_sample_multistep_region makes. */
+int dd_sample_multistep_threshold(dd_ctx* ctx, const dd_multistep_sample_args* args, const dd_guidance* g, const dd_autoguidance* ag,
+                                  const dd_known_region* kr, const dd_x0_threshold* thr, void* stream);
+
 /* The early-exit baseline's loop (reference eesampler.py:40-89) as a device-resident loop: per step EarlyExitUViT.forward
  * (all heads and probes), the per-sample exit selection with the global threshold, the DDPM update (sigma^2 = beta-tilde)
  * with the selected output; row t of err_dev [1000, depth] (batch-mean predicted error per layer, :70) and of idx_dev

@@ -147,6 +147,7 @@ SIGNATURES = {
     "dd_profile_select": (C.c_int, [C.c_void_p, C.c_int]),
     "dd_dev_qkv_attention": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
+    "dd_dev_qkv_attention_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_mlp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)] + [C.c_void_p] * 8),
     "dd_dev_head_dec": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_gemm": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p] + [C.c_int] * 2 + [C.c_void_p] * 2 +

@@ -288,7 +288,7 @@ hipError_t launch_attention(const T* qkv, T* out, int B, int L, int H, int D, hi
 // attn.qkv + attention in one launch (attention.hip qkv_attention_kernel): h = norm1 of the patch rows in fragment order
 // (MlpFusedArgs::ln_out_frag); the extra-token rows: hx = norm1 row-major [B L, D], or hx = nullptr and xres / ln_g / ln_b = the fp32
 // residual stream and this block's norm1 parameters (the kernel normalises the rows itself); wimg from qkv_attention_pack;
-// bf16, D = 512, L = 256 + extras only
+// bf16, D = 512 / 768 / 1024 (heads of 64), L = 256 + extras, extras = 1 or 2 only (qkv_attention_supported)
 bool qkv_attention_supported(int D, int H, int L, int extras);
 void qkv_attention_pack(int D, int H, const float* w, unsigned short (*to_bf16)(float), unsigned short* img);
 hipError_t launch_qkv_attention(const bf16_t* h, const bf16_t* wimg, const float* bias, const bf16_t* hx, const float* xres,

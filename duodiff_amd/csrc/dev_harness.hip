@@ -1,4 +1,4 @@
-// The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_qkv_attention, dd_dev_head_dec, dd_dev_gemm,
+// The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_qkv_attention, dd_dev_qkv_attention_rows, dd_dev_head_dec, dd_dev_gemm,
 // dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather): test scaffolding, not product.  Each one packs host operands as finalize packs a model's, launches what the model launches
 // (launch_args.h), returns the outputs and times `iters` further launch sequences.  Buffers, transfers, timing and HIP errors go through
 // one DevScope (dev_scope.h); the context is reached through its accessors only.
@@ -93,32 +93,53 @@ int dd_dev_mlp(dd_ctx* c, int M, int D, int hidden, int extras, const float* x_h
     return dev.status();
 }
 
-int dd_dev_qkv_attention(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
-                         unsigned short* out_host, int iters, void* stream, float* ms_out) {
-    if (!c || !h_host || !wqkv || !out_host) return DD_ERR_INVALID;
+int dd_dev_qkv_attention_rows(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
+                              const float* xres_host, const float* ln, unsigned short* out_host, int iters, void* stream, float* ms_out) {
+    if (!c || !h_host || !wqkv || !out_host || (xres_host && !ln) || B < 1 || iters < 0) return DD_ERR_INVALID;
     const int D = 64 * H;
     if (!qkv_attention_supported(D, H, L, extras)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "qkv_attention: D = 512 / 768 / 1024, L = 256 + 1 or 2 extra tokens only");
     hipStream_t s = (hipStream_t)stream;
     const size_t M = (size_t)B * L;
-    const std::vector<unsigned short> hb = bf16_rows(h_host, M, D, M, 0);
+    std::vector<unsigned short> hb = bf16_rows(h_host, M, D, M, 0);
     std::vector<unsigned short> hf((size_t)B * 256 * D), img((size_t)3 * D * D);
     for (int b = 0; b < B; ++b)          // the patch rows in fragment order (what the fused block tail writes: MlpFusedArgs::ln_out_frag)
         for (int n = 0; n < 256; ++n)
             for (int k = 0; k < D; ++k)
                 hf[((((size_t)b * 8 + n / 32) * (D / 16) + k / 16) * 64 + (n % 32) + 32 * ((k % 16) / 8)) * 8 + k % 8] = hb[((size_t)b * L + extras + n) * D + k];
     qkv_attention_pack(D, H, wqkv, host_f2bf, img.data());
+    // the extra-token rows, row-major: norm1 rows as bf16 (hx), or the fp32 residual stream the kernel normalises itself; the patch rows of
+    // either, which the kernel must never read, hold 0xFF bytes (NaN)
+    std::vector<float> xr;
+    if (xres_host) {
+        xr.resize(M * D);
+        std::memset(xr.data(), 0xFF, xr.size() * 4);
+        for (int b = 0; b < B; ++b) std::memcpy(xr.data() + (size_t)b * L * D, xres_host + (size_t)b * L * D, (size_t)extras * D * 4);
+    } else {
+        for (int b = 0; b < B; ++b) std::memset(hb.data() + ((size_t)b * L + extras) * D, 0xFF, (size_t)256 * D * 2);
+    }
     DevScope dev(c);
     const bf16_t* dH = dev.upload(hf.data(), hf.size() * 2);
     const bf16_t* dW = dev.upload(img.data(), img.size() * 2);
-    const bf16_t* dQ = dev.upload(hb.data(), hb.size() * 2);     // row-major norm1 rows: the kernel reads the extra-token rows of it
-    bf16_t* dO = dev.filled<bf16_t>(M * D * 2, 0);
+    const bf16_t* dQ = xres_host ? nullptr : dev.upload(hb.data(), hb.size() * 2);
+    const float* dX = xres_host ? dev.upload(xr.data(), xr.size() * 4) : nullptr;
+    const float* dL = xres_host ? dev.upload(ln, (size_t)2 * D * 4) : nullptr;
+    bf16_t* dO = dev.filled<bf16_t>((M + 8) * D * 2, 0xFF);      // 8 canary rows behind the output
     const float* dB = bqkv ? dev.upload(bqkv, (size_t)3 * D * 4) : nullptr;
-    auto once = [&]() { return launch_qkv_attention(dH, dW, dB, dQ, nullptr, nullptr, nullptr, dO, B, L, H, D, extras, s); };
+    auto once = [&]() { return launch_qkv_attention(dH, dW, dB, dQ, dX, dL, dL ? dL + D : nullptr, dO, B, L, H, D, extras, s); };
     DEV_HIP(dev, once());
     DEV_HIP(dev, hipStreamSynchronize(s));
-    dev.download(out_host, dO, M * D * 2);
+    dev.download(out_host, dO, (M + 8) * D * 2);
     DEV_HIP(dev, time_launches(s, iters, once, ms_out));
     return dev.status();
+}
+
+int dd_dev_qkv_attention(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
+                         unsigned short* out_host, int iters, void* stream, float* ms_out) {
+    if (!out_host) return DD_ERR_INVALID;
+    std::vector<unsigned short> whole(B > 0 && L > 0 && H > 0 ? ((size_t)B * L + 8) * 64 * H : 0);      // (a refused shape does not touch it)
+    const int st = dd_dev_qkv_attention_rows(c, B, L, H, extras, h_host, wqkv, bqkv, nullptr, nullptr, whole.data(), iters, stream, ms_out);
+    if (st == DD_OK) std::memcpy(out_host, whole.data(), (size_t)B * L * 64 * H * 2);
+    return st;
 }
 
 int dd_dev_head_dec(dd_ctx* c, int M, int D, int pd, int tok_l, int tok_e, const float* x_host, const float* norm_g, const float* norm_b,

@@ -40,6 +40,16 @@ int dd_dev_mlp(dd_ctx* ctx, int M, int D, int hidden, int extras, const float* h
 int dd_dev_qkv_attention(dd_ctx* ctx, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
                          unsigned short* out_host, int iters, void* stream, float* ms_out);
 
+/* The same launch with the extra-token rows under the caller's control and every buffer the kernel must leave alone poisoned.
+ * xres_host NULL (the hx mode): as dd_dev_qkv_attention, but the patch rows (l >= extras) of the row-major norm1 buffer hold 0xFFFF -- the
+ * kernel may read only its rows l < extras.  xres_host [B L, D] fp32 + ln [2, D] (gamma, beta) (the production mode, what the model
+ * launches): hx = nullptr, the kernel normalises the extra-token rows itself from the residual stream (norm1, eps 1e-5); only the rows
+ * l < extras of xres_host are used, the patch rows of the device copy hold 0xFF bytes (NaN); h_host still supplies the patch rows (its
+ * extra-token rows are ignored).  out_host [B L + 8, D] of bf16 bits is filled with 0xFF bytes before the launch and comes back WHOLE.
+ * A refused shape is DD_ERR_UNSUPPORTED; nothing is launched and out_host is not written. */
+int dd_dev_qkv_attention_rows(dd_ctx* ctx, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
+                              const float* xres_host, const float* ln, unsigned short* out_host, int iters, void* stream, float* ms_out);
+
 /* Development harness for the output head's first launch (rowops.hip head_dec_kernel; reference models/uvit.py:377-378):
  * dec = decoder_pred(LayerNorm(x)) in exact fp32 from host arrays x [M, D], norm gamma / beta [D], decoder_pred weight [pd, D] / bias [pd];
  * dec_host [M, pd] (rows the launch does not decode -- the first tok_e rows of every tok_l-row image when tok_l > 0 -- come back as NaN).

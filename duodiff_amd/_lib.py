@@ -59,6 +59,11 @@ class dd_autoguidance(C.Structure):
     _fields_ = [("guide", C.c_void_p), ("scale", C.c_float)]
 
 
+class dd_pag(C.Structure):
+    """perturbed-attention guidance: eps = eps + scale * (eps - eps_perturbed), identity attention in the blocks of the model's mask"""
+    _fields_ = [("scale", C.c_float), ("layers_first", C.c_uint32), ("layers_late", C.c_uint32)]
+
+
 class dd_known_region(C.Structure):
     """a known region: x' is finished as m * (ka x0 + kb z2) + (1 - m) x' from the known image x0, the mask m and per-step rows ka, kb"""
     _fields_ = [("x0_dev", C.c_void_p), ("mask_dev", C.c_void_p), ("ka", C.POINTER(C.c_float)), ("kb", C.POINTER(C.c_float))]
@@ -120,6 +125,11 @@ SIGNATURES = {
     "dd_sample_autoguided": (C.c_int, [C.c_void_p, C.POINTER(dd_sample_args), C.POINTER(dd_autoguidance), C.c_void_p]),
     "dd_sample_affine_autoguided": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.POINTER(dd_autoguidance), C.c_void_p]),
     "dd_sample_multistep_autoguided": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_autoguidance), C.c_void_p]),
+    "dd_forward_perturbed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.POINTER(dd_pag), C.c_void_p,
+                                       C.c_int, C.c_void_p]),
+    "dd_sample_perturbed": (C.c_int, [C.c_void_p, C.POINTER(dd_sample_args), C.POINTER(dd_pag), C.c_void_p]),
+    "dd_sample_affine_perturbed": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.POINTER(dd_pag), C.c_void_p]),
+    "dd_sample_multistep_perturbed": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_pag), C.c_void_p]),
     "dd_known_blend": (C.c_int, [C.c_void_p] * 5 + [C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dd_sample_region": (C.c_int, [C.c_void_p, C.POINTER(dd_sample_args), C.POINTER(dd_guidance), C.POINTER(dd_autoguidance),
                                    C.POINTER(dd_known_region), C.c_void_p]),
@@ -148,6 +158,8 @@ SIGNATURES = {
     "dd_dev_qkv_attention": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_qkv_attention_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
+    "dd_dev_v_identity": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
+    "dd_dev_v_copy": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_mlp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)] + [C.c_void_p] * 8),
     "dd_dev_head_dec": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_gemm": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p] + [C.c_int] * 2 + [C.c_void_p] * 2 +

@@ -763,6 +763,174 @@ __global__ void __launch_bounds__(512, 1) qkv_attention_kernel(const QkvAttnArgs
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Identity attention (perturbed-attention guidance): the attention map of a block is replaced by the identity, every
+// token attends to itself and attention(q, k, v) = v.  The companion of launch_qkv_attention for the images whose attention is the identity:
+// the same operands (the patch rows' norm1 in fragment order, the per-head weight image of qkv_attention_pack, the extra-token rows normalised
+// here from the fp32 residual stream), a third of phase A's product and no phase B:
+//     out[b L + l, 64 hh + c] = bf16(sum_k h[l, k] Wv[64 hh + c, k] + bv[64 hh + c])
+// The launch is bound by HBM (rows in + rows out), so the map is by ROWS, not by (image, head): one workgroup = 64 rows (two 32-row fragment
+// groups), copied to LDS once -- each fragment of h leaves HBM once -- and multiplied against ALL D / 32 column tiles of Wv, which the 8 waves
+// share out (wave w: tiles w, w + 8, ..).  The weight fragments come straight from L2 (Wv is 0.5 .. 2 MB, every workgroup reads the same
+// bytes), 1 KB per load, one slice of 8 k-steps ahead of the MFMAs that use it; a fragment serves both row groups.
+// Workgroups [0, 4 B): patch rows (image row r = token E + r).  Workgroups behind them: 64 extra-token rows each (row q = image q / E, token
+// q % E), normalised into the same fragment order in LDS, then the same product.
+struct VIdentityArgs {
+    const bf16_t* h;       // norm1 of the patch rows in fragment order: [B * 8 groups of 32 rows][D / 16][64 lanes][8]
+    const bf16_t* wimg;    // qkv_attention_pack: per head and slice of 8 k-steps the tiles q0 q1 k0 k1 v0 v1; only v0 v1 are read
+    const float* bias;     // [3 D] or nullptr; only [2 D, 3 D) is read
+    const float* xres;     // fp32 residual stream [B L, D]: only the extra-token rows (l < E) are read
+    const float* ln_g;     // norm1 weight
+    const float* ln_b;     // and bias (eps 1e-5, two-pass statistics in fp32, as qkv_attention_kernel normalises those rows)
+    bf16_t* out;           // [B L, D]
+    int B, L, E;
+};
+
+template <int D>
+__global__ void __launch_bounds__(512, 1) v_identity_kernel(const VIdentityArgs a) {
+    constexpr int KS = D / 16, NS = KS / kQaKQ, NT = D / 256;     // k-steps, slices of 8 k-steps, column tiles per wave
+    static_assert(D % 256 == 0 && D >= 512 && D <= 1024, "8 waves share D / 32 column tiles; a lane normalises D / 64 columns in float4s");
+    extern __shared__ __attribute__((aligned(16))) char smem[];    // h of the 64 rows: [2 groups][KS k-steps][64 lanes] x 16 bytes
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int half = lane >> 5, r32 = lane & 31;
+    const int L = a.L, E = a.E, n_extra = a.B * E;
+    const int wg_patch = a.B * 4;
+    const bool extra_wg = (int)blockIdx.x >= wg_patch;
+    const int q0 = ((int)blockIdx.x - wg_patch) * 64;              // extra_wg: the first extra-token row of this workgroup
+
+    if (!extra_wg) {
+        const f32x4* src = reinterpret_cast<const f32x4*>(a.h) + (size_t)blockIdx.x * (2 * KS * 64);
+        for (int i = tid; i < 2 * KS * 64; i += 512) reinterpret_cast<f32x4*>(smem)[i] = src[i];
+    } else {
+        // wave w normalises rows w, w + 8, ..: D / 64 columns per lane, the arithmetic of qkv_attention_kernel's own rows; rows past the last
+        // extra token are zero (their results are dropped at the store)
+        constexpr int NV = D / 256;
+        for (int i = wave; i < 64; i += 8) {
+            const int q = q0 + i;
+            f32x4 y[NV];
+#pragma unroll
+            for (int v = 0; v < NV; ++v) y[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (q < n_extra) {
+                const int b = q / E, l = q - b * E;
+                const float* xr = a.xres + ((long long)b * L + l) * D + lane * (D / 64);
+                f32x4 xv[NV];
+                float s1 = 0.f;
+#pragma unroll
+                for (int v = 0; v < NV; ++v) {
+                    xv[v] = *reinterpret_cast<const f32x4*>(xr + 4 * v);
+                    s1 += (xv[v][0] + xv[v][1]) + (xv[v][2] + xv[v][3]);
+                }
+                const float mean = wave_reduce_add(s1) / (float)D;
+                float s2 = 0.f;
+#pragma unroll
+                for (int v = 0; v < NV; ++v) {
+                    xv[v] = xv[v] - mean;
+                    s2 += (xv[v][0] * xv[v][0] + xv[v][1] * xv[v][1]) + (xv[v][2] * xv[v][2] + xv[v][3] * xv[v][3]);
+                }
+                const float rstd = 1.0f / sqrtf(wave_reduce_add(s2) / (float)D + 1e-5f);
+#pragma unroll
+                for (int v = 0; v < NV; ++v) {
+                    const f32x4 g = *reinterpret_cast<const f32x4*>(a.ln_g + lane * (D / 64) + 4 * v), c0 = *reinterpret_cast<const f32x4*>(a.ln_b + lane * (D / 64) + 4 * v);
+                    y[v] = xv[v] * rstd * g + c0;
+                }
+            }
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {     // columns k .. k + 3 (k % 4 == 0): k-step k / 16, lane half (k / 8) & 1, elements k % 8 ..
+                const int k = lane * (D / 64) + 4 * v;
+                char* dst = smem + ((((i >> 5) * KS + (k >> 4)) * 64 + (i & 31) + 32 * ((k >> 3) & 1)) << 4) + (k & 7) * 2;
+                *reinterpret_cast<uint2*>(dst) = uint2{cvt_pk_bf16(y[v][0], y[v][1]), cvt_pk_bf16(y[v][2], y[v][3])};
+            }
+        }
+    }
+    __syncthreads();
+
+    // this lane's output row in either group (the lane owns a row of out^T = Wv . h^T)
+    long long orow[2];
+    bool valid[2];
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        if (!extra_wg) {
+            const int gg = (int)blockIdx.x * 2 + g;                 // fragment group: image gg / 8, rows 32 (gg % 8) ..
+            orow[g] = (long long)(gg >> 3) * L + E + 32 * (gg & 7) + r32;
+            valid[g] = true;
+        } else {
+            const int q = q0 + 32 * g + r32, qc = q < n_extra ? q : n_extra - 1, b = qc / E;
+            orow[g] = (long long)b * L + (qc - b * E);
+            valid[g] = q < n_extra;
+        }
+    }
+
+    // unit idx = (tile i of this wave, slice q): the weight block of 8 k-steps of column tile T = wave + 8 i (head T / 2, tile v0 / v1 = T % 2)
+    auto load_w = [&](int idx, bf16x8 (&w)[kQaKQ]) {
+        const int T = wave + 8 * (idx / NS), q = idx % NS;
+        const bf16x8* wp = reinterpret_cast<const bf16x8*>(a.wimg) + ((size_t)((T >> 1) * NS + q) * 6 + 4 + (T & 1)) * (kQaKQ * 64) + lane;
+#pragma unroll
+        for (int ks = 0; ks < kQaKQ; ++ks) w[ks] = wp[ks * 64];
+    };
+    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const bf16x8* hl = reinterpret_cast<const bf16x8*>(smem) + lane;
+    bf16x8 wb[2][kQaKQ];
+    f32x16 acc[2];
+    load_w(0, wb[0]);
+#pragma unroll
+    for (int idx = 0; idx < NT * NS; ++idx) {
+        const int q = idx % NS;
+        if (idx + 1 < NT * NS) load_w(idx + 1, wb[(idx + 1) & 1]);     // the next block is in flight under this block's MFMAs
+        if (q == 0) { acc[0] = zero16; acc[1] = zero16; }
+#pragma unroll
+        for (int ks = 0; ks < kQaKQ; ++ks) {
+            const bf16x8 h0 = hl[(q * kQaKQ + ks) * 64], h1 = hl[(KS + q * kQaKQ + ks) * 64];
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wb[idx & 1][ks], h0, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wb[idx & 1][ks], h1, acc[1], 0, 0, 0);
+        }
+        if (q == NS - 1) {
+            // register e of a tile: column (e & 3) + 8 (e >> 2) + 4 half; v_permlane32_swap pairs the lane halves into 16-byte row segments
+            // (as the attention launches store their rows); every lane takes part in the swap, rows past the end are dropped at the store
+            const int T = wave + 8 * (idx / NS), col0 = 32 * T;        // = 64 hh + 32 t
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {
+                if (a.bias) {
+                    const float* bj = a.bias + 2 * D + col0 + 4 * half;
+#pragma unroll
+                    for (int gq = 0; gq < 4; ++gq) {
+                        const f32x4 bv = *reinterpret_cast<const f32x4*>(bj + 8 * gq);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) acc[g][4 * gq + e] += bv[e];
+                    }
+                }
+                unsigned pk[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) pk[i] = cvt_pk_bf16(acc[g][2 * i], acc[g][2 * i + 1]);
+                bf16_t* op = a.out + orow[g] * D + col0 + 8 * half;
+#pragma unroll
+                for (int gp = 0; gp < 4; gp += 2) {
+                    const auto s0 = __builtin_amdgcn_permlane32_swap(pk[2 * gp], pk[2 * gp + 2], false, false);
+                    const auto s1 = __builtin_amdgcn_permlane32_swap(pk[2 * gp + 1], pk[2 * gp + 3], false, false);
+                    if (valid[g]) *reinterpret_cast<uint4*>(op + 8 * gp) = uint4{s0[0], s1[0], s0[1], s1[1]};
+                }
+            }
+        }
+    }
+}
+
+// ... where the head-major qkv tensor exists (fp32 mode, widths the fused launch does not cover, attn.qkv run by a GEMM or by the block tail):
+// out[b L + l, 64 hh + c] = qkv[b][v][hh][l][c], a bit-exact copy, 16 bytes per lane in output order.  The pad rows [L, Lp) are never read.
+template <typename T>
+__global__ void __launch_bounds__(256) v_copy_kernel(const T* __restrict__ qkv, T* __restrict__ out, long long n_chunks, int L, int H, int Lp) {
+    constexpr int EPC = 16 / (int)sizeof(T), CPR = kHD / EPC;      // elements per 16-byte chunk, chunks per (row, head)
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n_chunks) return;
+    const int ch = (int)(idx % CPR);
+    long long r = idx / CPR;
+    const int hh = (int)(r % H);
+    r /= H;
+    const int l = (int)(r % L);
+    const long long b = r / L;
+    const T* src = qkv + (((b * 3 + 2) * H + hh) * Lp + l) * kHD + ch * EPC;
+    *reinterpret_cast<f32x4*>(out + idx * EPC) = *reinterpret_cast<const f32x4*>(src);
+}
+
 }  // namespace
 
 template <typename T>
@@ -794,6 +962,7 @@ bool qkv_attention_supported(int D, int H, int L, int extras) {
     return (D == 512 || D == 768 || D == 1024) && H * kHD == D && (extras == 1 || extras == 2) && L == 256 + extras;
 }
 
+static size_t v_identity_lds(int D) { return (size_t)2 * (D / 16) * 1024; }     // 64 rows of h in fragment order
 static size_t qkv_attention_lds() { return (size_t)kLP * AttnLayout<bf16_t>::kRowK + AttnLayout<bf16_t>::kVBytes + kQaAuxBytes + kQaRing; }
 
 hipError_t launch_qkv_attention(const bf16_t* h, const bf16_t* wimg, const float* bias, const bf16_t* hx, const float* xres,
@@ -808,9 +977,35 @@ hipError_t launch_qkv_attention(const bf16_t* h, const bf16_t* wimg, const float
     return hipGetLastError();
 }
 
+// identity attention of images whose attention map is the identity (v_identity_kernel): launch_qkv_attention's operands without the hx mode
+hipError_t launch_v_identity(const bf16_t* h, const bf16_t* wimg, const float* bias, const float* xres, const float* ln_g, const float* ln_b,
+                             bf16_t* out, int B, int L, int H, int D, int extras, hipStream_t s) {
+    if (!qkv_attention_supported(D, H, L, extras) || !h || !wimg || !xres || !ln_g || !ln_b || !out || B < 1) return hipErrorInvalidValue;
+    const VIdentityArgs a{h, wimg, bias, xres, ln_g, ln_b, out, B, L, extras};
+    const dim3 grid(B * 4 + (B * extras + 63) / 64);
+    switch (D) {
+        case 512: hipLaunchKernelGGL((v_identity_kernel<512>), grid, dim3(512), v_identity_lds(512), s, a); break;
+        case 768: hipLaunchKernelGGL((v_identity_kernel<768>), grid, dim3(512), v_identity_lds(768), s, a); break;
+        default: hipLaunchKernelGGL((v_identity_kernel<1024>), grid, dim3(512), v_identity_lds(1024), s, a); break;
+    }
+    return hipGetLastError();
+}
+
+// ... from the head-major qkv tensor (make_head_major(L, H)): out [B L, D] rows = the v rows
+template <typename T>
+hipError_t launch_v_copy(const T* qkv, T* out, int B, int L, int H, int D, hipStream_t s) {
+    if (!qkv || !out || B < 1 || L < 1 || L > kLP || H < 1 || D != H * kHD) return hipErrorInvalidValue;
+    const long long n_chunks = (long long)B * L * D / (16 / (int)sizeof(T));
+    hipLaunchKernelGGL((v_copy_kernel<T>), dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, s, qkv, out, n_chunks, L, H, make_head_major(L, H).Lp);
+    return hipGetLastError();
+}
+
 hipError_t init_attention_kernels() {
     for (const void* f : {(const void*)qkv_attention_kernel<512>, (const void*)qkv_attention_kernel<768>, (const void*)qkv_attention_kernel<1024>})
         if (hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)qkv_attention_lds()); e != hipSuccess) return e;
+    if (hipError_t e = hipFuncSetAttribute((const void*)v_identity_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v_identity_lds(512)); e != hipSuccess) return e;
+    if (hipError_t e = hipFuncSetAttribute((const void*)v_identity_kernel<768>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v_identity_lds(768)); e != hipSuccess) return e;
+    if (hipError_t e = hipFuncSetAttribute((const void*)v_identity_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v_identity_lds(1024)); e != hipSuccess) return e;
     const int lb = kLP * AttnLayout<bf16_t>::kRowK + AttnLayout<bf16_t>::kVBytes + kPartBytes;
     const int lf = kLP * AttnLayout<float>::kRowK + AttnLayout<float>::kVBytes + kPartBytes;
     hipError_t e = hipFuncSetAttribute((const void*)attention_kernel<bf16_t, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, lb);
@@ -822,5 +1017,7 @@ hipError_t init_attention_kernels() {
 
 template hipError_t launch_attention<bf16_t>(const bf16_t*, bf16_t*, int, int, int, int, hipStream_t);
 template hipError_t launch_attention<float>(const float*, float*, int, int, int, int, hipStream_t);
+template hipError_t launch_v_copy<bf16_t>(const bf16_t*, bf16_t*, int, int, int, int, hipStream_t);
+template hipError_t launch_v_copy<float>(const float*, float*, int, int, int, int, hipStream_t);
 
 }  // namespace dd

@@ -135,11 +135,16 @@ struct GraphKey {
     int tmode = -1;                                                  // x0 thresholding: the mode (-1: none), the bits of quantile, range and s_max,
     unsigned tq = 0, tr = 0, ts = 0;                                 //   and the model-output scratch the step goes through
     const void* tscratch = nullptr;
+    int pag = 0;                                                     // perturbed-attention guidance: set (gscale: the scale's bits), and the
+    unsigned pfirst = 0, plate = 0;                                  //   masks of the loop's two models
     bool operator==(const GraphKey& o) const {
         return x == o.x && y == o.y && B == o.B && noise == o.noise && variance == o.variance && num_cus == o.num_cus &&
                atab == o.atab && aux0 == o.aux0 && aux1 == o.aux1 && thr == o.thr && b0 == o.b0 && gnull == o.gnull && gscale == o.gscale &&
                aguide == o.aguide && aserial == o.aserial && kx0 == o.kx0 && kmask == o.kmask && ktab == o.ktab && tmode == o.tmode &&
-               tq == o.tq && tr == o.tr && ts == o.ts && tscratch == o.tscratch;
+               tq == o.tq && tr == o.tr && ts == o.ts && tscratch == o.tscratch && pag == o.pag && pfirst == o.pfirst && plate == o.plate;
+    }
+    void perturb(const dd_pag* p) {
+        if (p) { pag = 1; gscale = __builtin_bit_cast(unsigned, p->scale); pfirst = p->layers_first; plate = p->layers_late; }
     }
     void guide(const dd_guidance* g) {
         if (g) { gnull = g->null_label; gscale = __builtin_bit_cast(unsigned, g->scale); }
@@ -550,8 +555,17 @@ struct Mods {
     const char* missing = nullptr;            // a _guided / _autoguided entry called without its struct: the rejection
     const dd_x0_threshold* thr = nullptr;     // dd_sample_multistep_threshold's thresholding as the caller passed it,
     bool thresholded = false;                 //   which that entry requires
+    const dd_pag* pag = nullptr;              // perturbed-attention guidance (never with g, ag, kr or thr): B images run as the 2 B backbone rows [x | x]
+    const dd_model* pag_late = nullptr;       //   with the labels [y | y]; the second half's attention is the identity in the running model's masked
+                                              //   blocks: layers_late where that model is pag_late, else layers_first
+    unsigned pag_mask(const dd_model* m) const { return !pag ? 0u : (pag_late && m == pag_late) ? pag->layers_late : pag->layers_first; }
 };
 Mods guided(const dd_guidance* g) { return Mods{.g = g, .missing = g ? nullptr : "null dd_guidance"}; }
+Mods perturbed(const dd_pag* p, const dd_model* late) {
+    Mods mo{};
+    mo.pag = p; mo.pag_late = late; mo.missing = p ? nullptr : "null dd_pag";
+    return mo;
+}
 Mods autoguided(const dd_autoguidance* ag) { return Mods{.ag = ag, .missing = ag ? nullptr : "null dd_autoguidance"}; }
 Mods in_region(const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr) { return Mods{.g = g, .ag = ag, .kr = kr, .region = true}; }
 Mods thresholding(const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr, const dd_x0_threshold* thr) {
@@ -607,6 +621,10 @@ struct Backbone {
     int B;
     hipStream_t s;
     const EeTaps* ee;
+    // perturbation record (perturbed-attention guidance): images [pert_first, B) of this forward take the identity for their attention map in
+    // the blocks of pert_mask (bit i = block i in forward order); 0: no block, the launches of an unperturbed forward
+    int pert_first = 0;
+    unsigned pert_mask = 0;
     dd_ctx* c = m->ctx;
     const WsPtrs& ws = *ch.ws;
     const int D = m->D, L = m->L, M = B * L, nb = (int)m->blocks.size();
@@ -758,9 +776,17 @@ struct Backbone {
                 DD_HIP(c, launch_layernorm<T>(ws.x, w.ln1_g, w.ln1_b, h, M, D, s));
             }
         }
+        // a masked block: the attention launch on images [0, Bn), the identity launch on the Bi images behind them (operands offset by image)
+        const bool masked = (pert_mask >> bi) & 1u;
+        const int Bn = masked ? pert_first : B, Bi = B - Bn;
         if (qa) {
-            if constexpr (bf16)
-                DD_TIMED(DD_PROF_QKV_ATTENTION, launch_qkv_attention(ws.hfrag, w.qa_img, w.qkv_b, nullptr, ws.x, w.ln1_g, w.ln1_b, (bf16_t*)ao, B, L, m->H, D, m->extras, s));
+            if constexpr (bf16) {
+                if (Bn > 0)
+                    DD_TIMED(DD_PROF_QKV_ATTENTION, launch_qkv_attention(ws.hfrag, w.qa_img, w.qkv_b, nullptr, ws.x, w.ln1_g, w.ln1_b, (bf16_t*)ao, Bn, L, m->H, D, m->extras, s));
+                if (Bi > 0)
+                    DD_HIP(c, launch_v_identity(ws.hfrag + (size_t)Bn * m->N * D, w.qa_img, w.qkv_b, ws.x + (size_t)Bn * L * D, w.ln1_g, w.ln1_b,
+                                                (bf16_t*)ao + (size_t)Bn * L * D, Bi, L, m->H, D, m->extras, s));
+            }
             return DD_OK;
         }
         if (!in.qkv) {
@@ -768,7 +794,9 @@ struct Backbone {
             g.hm = make_head_major(L, m->H);     // head-major: each (q | k | v, head) unit of an image is contiguous (attention.hip)
             DD_HIP(c, launch_gemm<T>(g, w.qkv_b ? EPI_BIAS_STORE : EPI_STORE, s, ch.cus));
         }
-        DD_TIMED(DD_PROF_QKV_ATTENTION, launch_attention<T>(qkv, ao, B, L, m->H, D, s));
+        if (Bn > 0) DD_TIMED(DD_PROF_QKV_ATTENTION, launch_attention<T>(qkv, ao, Bn, L, m->H, D, s));
+        if (Bi > 0)
+            DD_HIP(c, launch_v_copy<T>(qkv + (size_t)Bn * 3 * D * make_head_major(L, m->H).Lp, ao + (size_t)Bn * L * D, Bi, L, m->H, D, s));
         return DD_OK;
     }
 
@@ -884,10 +912,13 @@ struct Backbone {
 #undef DD_TIMED
 };
 
+// what a forward's perturbation record is made from (Backbone::pert_first / pert_mask)
+struct Perturb { int first = 0; unsigned mask = 0; };
+
 template <typename T>
 int run_backbone(dd_model* m, const Chain& ch, const float* x_img, const float* t_vec, const int64_t* y_dev, int B, hipStream_t s,
-                 const EeTaps* ee = nullptr) {
-    Backbone<T> f{m, ch, B, s, ee};
+                 const EeTaps* ee = nullptr, Perturb pert = {}) {
+    Backbone<T> f{m, ch, B, s, ee, pert.first, pert.mask};
     Handoff hand;
     if (int rc = f.embed(x_img, t_vec, y_dev, hand)) return rc;
     for (int bi = 0; bi < f.nb; ++bi) {
@@ -904,9 +935,9 @@ int run_backbone(dd_model* m, const Chain& ch, const float* x_img, const float* 
 }
 
 int run_model(dd_model* m, const Chain& ch, const float* x_img, const float* t_vec, const int64_t* y_dev, int B, hipStream_t s,
-              const EeTaps* ee = nullptr) {
-    return m->prec == DD_PREC_BF16 ? run_backbone<bf16_t>(m, ch, x_img, t_vec, y_dev, B, s, ee)
-                                   : run_backbone<float>(m, ch, x_img, t_vec, y_dev, B, s, ee);
+              const EeTaps* ee = nullptr, Perturb pert = {}) {
+    return m->prec == DD_PREC_BF16 ? run_backbone<bf16_t>(m, ch, x_img, t_vec, y_dev, B, s, ee, pert)
+                                   : run_backbone<float>(m, ch, x_img, t_vec, y_dev, B, s, ee, pert);
 }
 
 // the checks of a call that do not concern labels
@@ -937,6 +968,18 @@ int check_guided(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev, const dd_g
     if (!std::isfinite(g->scale)) return ctx_fail(c, DD_ERR_INVALID, "guidance scale is not finite");
     if (B < 1 || 2LL * B > m->cfg.max_batch)
         return ctx_fail(c, DD_ERR_INVALID, "a guided batch of B images runs 2 B backbone rows: need 1 <= B and 2 B <= max_batch");
+    return check_call(c, m, 2 * B, y_dev);
+}
+
+// a perturbed call of B images on m with the blocks of `mask` perturbed (include/duodiff.h dd_pag): every check before anything is enqueued
+int check_perturbed(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev, const dd_pag* p, unsigned mask) {
+    if (!c || !m) return DD_ERR_INVALID;
+    if (!p) return ctx_fail(c, DD_ERR_INVALID, "null dd_pag");
+    if (!std::isfinite(p->scale)) return ctx_fail(c, DD_ERR_INVALID, "perturbed-attention guidance scale is not finite");
+    if (m->cfg.depth < 32 && (mask >> m->cfg.depth)) return ctx_fail(c, DD_ERR_INVALID, "perturbed-attention mask names a block at or above the depth of the model");
+    if (B < 1 || 2LL * B > m->cfg.max_batch)
+        return ctx_fail(c, DD_ERR_INVALID, "a perturbed batch of B images runs 2 B backbone rows: need 1 <= B and 2 B <= max_batch");
+    if (m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, "perturbed-attention guidance is not supported for early-exit models");
     return check_call(c, m, 2 * B, y_dev);
 }
 
@@ -1016,8 +1059,11 @@ int model_eps(dd_ctx* c, dd_model* m, const Chain& ch, const float* x_dev, const
     int rc = DD_OK;
     if (ag && ag->guide != m && (rc = run_guide(c, m, ch, ag, x_dev, y_dev, B, s, fa))) return rc;
     if (ag && m->cfg.num_classes <= 0) y_dev = nullptr;
-    if ((rc = run_model(m, ch, x_dev, o.t_vec, y_dev, g ? 2 * B : B, s, o.ee))) return rc;
+    const dd_pag* pag = o.mods.pag;
+    const Perturb pert = pag ? Perturb{B, o.mods.pag_mask(m)} : Perturb{};
+    if ((rc = run_model(m, ch, x_dev, o.t_vec, y_dev, g || pag ? 2 * B : B, s, o.ee, pert))) return rc;
     if (g) { fa.pair_B = B; fa.guide_scale = g->scale; }
+    if (pag) { fa.pair_B = B; fa.guide_scale = pag->scale; }
     return DD_OK;
 }
 
@@ -1071,21 +1117,27 @@ int stage_inputs(dd_ctx* c, const float* x_dev, const int64_t* y_dev, int B, siz
 }
 
 // A guided call (eager or graph-replayed) always runs on the staging buffers, 2 B images: chain k (images [o_k, o_k + B_k), o_0 = 0,
-// o_1 = B0) owns images [2 o_k, 2 o_k + 2 B_k) of them -- its B_k images, then the same images again -- and labels [y_k | null x B_k].
+// o_1 = B0) owns images [2 o_k, 2 o_k + 2 B_k) of them -- its B_k images, then the same images again -- and labels [y_k | null x B_k];
+// null_label < 0 (perturbed-attention guidance): the second half's labels are the first half's, [y_k | y_k], or none (y_dev null).
 // B0 == B: one chain.
 int stage_guided(dd_ctx* c, const float* x_dev, const int64_t* y_dev, int B, int B0, size_t chw, int null_label, hipStream_t s,
                  float** x_run, const int64_t** y_run) {
-    if (int rc = grow_stage(c, 2 * (size_t)B * chw, 2 * (size_t)B)) return rc;
+    if (int rc = grow_stage(c, 2 * (size_t)B * chw, y_dev ? 2 * (size_t)B : 0)) return rc;
     for (int k = 0; k < 2; ++k) {
         const int o = k ? B0 : 0, Bk = k ? B - B0 : B0;
         if (Bk == 0) continue;
         float* xs = c->x_stage.p + 2 * (size_t)o * chw;
         DD_HIP(c, hipMemcpyAsync(xs, x_dev + (size_t)o * chw, (size_t)Bk * chw * sizeof(float), hipMemcpyDeviceToDevice, s));
         DD_HIP(c, hipMemcpyAsync(xs + (size_t)Bk * chw, x_dev + (size_t)o * chw, (size_t)Bk * chw * sizeof(float), hipMemcpyDeviceToDevice, s));
-        DD_HIP(c, launch_guided_labels((const long long*)y_dev + o, (long long*)c->y_stage.p + 2 * (size_t)o, Bk, null_label, s));
+        if (null_label >= 0) {
+            DD_HIP(c, launch_guided_labels((const long long*)y_dev + o, (long long*)c->y_stage.p + 2 * (size_t)o, Bk, null_label, s));
+        } else if (y_dev) {
+            for (int half = 0; half < 2; ++half)
+                DD_HIP(c, hipMemcpyAsync(c->y_stage.p + 2 * (size_t)o + (size_t)half * Bk, y_dev + o, (size_t)Bk * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        }
     }
     *x_run = c->x_stage.p;
-    *y_run = c->y_stage.p;
+    *y_run = y_dev ? c->y_stage.p : nullptr;
     return DD_OK;
 }
 // ... and the first half of each chain's block back to the caller's images
@@ -1186,10 +1238,12 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
     // Guided: the decisions are made on the 2 B backbone rows and the split is by image (chain 0 takes the larger half, on the workspace
     // sized for max_batch >= 2 B rows; the second chain's workspace holds (max_batch + 1) / 2 rows >= 2 * floor(B / 2)).
     const bool ee = L.kind == GRAPH_EARLY_EXIT;
-    const int rows = g ? 2 * L.B : L.B;
-    const bool chained = L.use_graph && use_chains(c, L.first, rows, ee) && (!L.late || use_chains(c, L.late, rows, ee)) && (!g || L.B >= 2);
+    const dd_pag* pag = L.mods.pag;
+    const bool paired = g || pag;        // B images as 2 B backbone rows (stage_guided's layout): classifier-free or perturbed-attention guidance
+    const int rows = paired ? 2 * L.B : L.B;
+    const bool chained = L.use_graph && use_chains(c, L.first, rows, ee) && (!L.late || use_chains(c, L.late, rows, ee)) && (!paired || L.B >= 2);
     const int chains = chained ? 2 : 1;
-    const int B0 = chained ? (g ? (L.B + 1) / 2 : L.B / 2) : L.B;
+    const int B0 = chained ? (paired ? (L.B + 1) / 2 : L.B / 2) : L.B;
     c->last_chains = chains;
     // the captured persistent GEMM grids: halved for both chains of a large GEMM-path batch (the early-exit loop keeps the full grids)
     int cus = chained && !ee ? std::min(chain_gemm_cus(c, L.first, rows), L.late ? chain_gemm_cus(c, L.late, rows) : c->num_cus) : c->num_cus;
@@ -1199,11 +1253,11 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
     float* x_run = L.x_dev;
     const int64_t* y_run = L.y_dev;
     int rc = DD_OK;
-    if (g) rc = stage_guided(c, L.x_dev, L.y_dev, L.B, B0, chw, g->null_label, s, &x_run, &y_run);
+    if (paired) rc = stage_guided(c, L.x_dev, L.y_dev, L.B, B0, chw, g ? g->null_label : -1, s, &x_run, &y_run);
     else if (L.use_graph) rc = stage_inputs(c, L.x_dev, L.y_dev, L.B, (size_t)L.B * chw, s, &x_run, &y_run);
     if (rc) return rc;
     auto slice = [&](int k) {
-        const size_t row = k ? (g ? 2 * (size_t)B0 : (size_t)B0) : 0;     // the chain's first row in x_run / y_run
+        const size_t row = k ? (paired ? 2 * (size_t)B0 : (size_t)B0) : 0;     // the chain's first row in x_run / y_run
         Slice sl{k, chains, x_run + row * chw, y_run ? y_run + row : nullptr, k ? L.B - B0 : B0, k ? B0 : 0, L.mods};
         sl.mods.kn = L.mods.kn.at(sl.b0, L.first);
         return sl;
@@ -1215,6 +1269,7 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
             GraphKey key{sl.x, sl.y, sl.B, 0, 0, cus, nullptr};
             key.b0 = sl.b0;
             key.guide(g);
+            key.perturb(pag);
             key.kx0 = sl.mods.kn.x0; key.kmask = sl.mods.kn.mask; key.ktab = sl.mods.kn.ktab;
             L.key(key, sl);
             for (dd_model* m : {L.first, L.late}) {
@@ -1261,7 +1316,7 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
     if (L.tail && (rc = L.tail(chains, s))) return rc;
     if (L.switch_at < 0) DD_HIP(c, hipEventRecord(c->ev[1], s));
     DD_HIP(c, hipEventRecord(c->ev[2], s));
-    if (g) return unstage_guided(c, L.x_dev, x_run, L.B, B0, chw, s);
+    if (paired) return unstage_guided(c, L.x_dev, x_run, L.B, B0, chw, s);
     if (x_run != L.x_dev) DD_HIP(c, hipMemcpyAsync(L.x_dev, x_run, (size_t)L.B * chw * sizeof(float), hipMemcpyDeviceToDevice, s));
     return DD_OK;
 }
@@ -1707,6 +1762,19 @@ int dd_forward_autoguided(dd_ctx* c, dd_model* m, const float* x_dev, float t, c
     return forward_eps(c, m, whole_batch(c, m), x_dev, y_dev, eps_dev, B, (hipStream_t)stream, {.t_set = &t, .mods = {.ag = g}});
 }
 
+int dd_forward_perturbed(dd_ctx* c, dd_model* m, const float* x_dev, float t, const int64_t* y_dev, const dd_pag* p, float* eps_dev, int B,
+                         void* stream) {
+    int rc = check_perturbed(c, m, B, y_dev, p, p ? p->layers_first : 0);
+    if (rc) return rc;
+    if (!x_dev || !eps_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t chw = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
+    float* x_run = nullptr;
+    const int64_t* y_run = nullptr;
+    if ((rc = stage_guided(c, x_dev, y_dev, B, B, chw, -1, s, &x_run, &y_run))) return rc;
+    return forward_eps(c, m, whole_batch(c, m), x_run, y_run, eps_dev, B, s, {.t_set = &t, .mods = perturbed(p, nullptr)});
+}
+
 int dd_sample_step(dd_ctx* c, dd_model* m, float* x_dev, int t, const int64_t* y_dev, int noise_mode, const float* z_dev,
                    uint64_t seed, int variance, float* eps_out_dev, int B, void* stream) {
     int rc = check_call(c, m, B, y_dev);
@@ -1743,7 +1811,12 @@ int check_loop(dd_ctx* c, const Args* a, const Mods& mo, const char* no_early_ex
     }
     for (dd_model* m : {a->first, a->late})
         if (no_early_exit && m && m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, no_early_exit);
-    auto check = [&](dd_model* m) { return mo.g ? check_guided(c, m, a->B, a->y_dev, mo.g) : check_call(c, m, a->B, a->y_dev); };
+    if (mo.pag && a->first && a->late == a->first && mo.pag->layers_first != mo.pag->layers_late)
+        return ctx_fail(c, DD_ERR_INVALID, "first and late are one model: its two perturbed-attention masks must agree");
+    auto check = [&](dd_model* m) {
+        if (mo.pag) return check_perturbed(c, m, a->B, a->y_dev, mo.pag, m && m == a->late ? mo.pag->layers_late : mo.pag->layers_first);
+        return mo.g ? check_guided(c, m, a->B, a->y_dev, mo.g) : check_call(c, m, a->B, a->y_dev);
+    };
     int rc = mo.ag ? check_autoguided(c, a->first, a->late, a->B, a->y_dev, mo.ag) : check(a->first);
     if (rc) return rc;
     if (!mo.ag && a->late && (rc = check(a->late))) return rc;
@@ -1939,6 +2012,15 @@ int dd_sample_multistep_guided(dd_ctx* c, const dd_multistep_sample_args* a, con
 }
 int dd_sample_multistep_autoguided(dd_ctx* c, const dd_multistep_sample_args* a, const dd_autoguidance* g, void* stream) {
     return sample_multistep(c, a, autoguided(g), stream);
+}
+int dd_sample_perturbed(dd_ctx* c, const dd_sample_args* a, const dd_pag* p, void* stream) {
+    return sample_ddpm(c, a, perturbed(p, a ? a->late : nullptr), stream);
+}
+int dd_sample_affine_perturbed(dd_ctx* c, const dd_affine_sample_args* a, const dd_pag* p, void* stream) {
+    return sample_affine(c, a, perturbed(p, a ? a->late : nullptr), stream);
+}
+int dd_sample_multistep_perturbed(dd_ctx* c, const dd_multistep_sample_args* a, const dd_pag* p, void* stream) {
+    return sample_multistep(c, a, perturbed(p, a ? a->late : nullptr), stream);
 }
 int dd_sample_multistep_region(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag,
                                const dd_known_region* kr, void* stream) {

@@ -294,6 +294,15 @@ void qkv_attention_pack(int D, int H, const float* w, unsigned short (*to_bf16)(
 hipError_t launch_qkv_attention(const bf16_t* h, const bf16_t* wimg, const float* bias, const bf16_t* hx, const float* xres,
                                 const float* ln_g, const float* ln_b, bf16_t* out, int B, int L, int H, int D, int extras, hipStream_t s);
 
+// Identity attention (perturbed-attention guidance): attention(q, k, v) = v for the B images given.  launch_v_identity is the companion of
+// launch_qkv_attention (the same operands, xres / ln_g / ln_b mode only; qkv_attention_supported shapes): v is computed from norm1 and the
+// v tiles of the weight image.  launch_v_copy is the companion of launch_attention: out [B L, D] rows = the v rows of the head-major qkv
+// tensor, copied bit for bit (rows [L, Lp) of a unit are never read).
+hipError_t launch_v_identity(const bf16_t* h, const bf16_t* wimg, const float* bias, const float* xres, const float* ln_g, const float* ln_b,
+                             bf16_t* out, int B, int L, int H, int D, int extras, hipStream_t s);
+template <typename T>
+hipError_t launch_v_copy(const T* qkv, T* out, int B, int L, int H, int D, hipStream_t s);
+
 struct FinalArgs {
     const float* dec;      // [B*L, pd] decoder_pred output for every token (extras included)
     const float* wconv;    // [C, C, 3, 3]

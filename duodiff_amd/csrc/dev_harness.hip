@@ -1,4 +1,4 @@
-// The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_qkv_attention, dd_dev_qkv_attention_rows, dd_dev_head_dec, dd_dev_gemm,
+// The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_qkv_attention, dd_dev_qkv_attention_rows, dd_dev_v_identity, dd_dev_v_copy, dd_dev_head_dec, dd_dev_gemm,
 // dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather): test scaffolding, not product.  Each one packs host operands as finalize packs a model's, launches what the model launches
 // (launch_args.h), returns the outputs and times `iters` further launch sequences.  Buffers, transfers, timing and HIP errors go through
 // one DevScope (dev_scope.h); the context is reached through its accessors only.
@@ -129,6 +129,70 @@ int dd_dev_qkv_attention_rows(dd_ctx* c, int B, int L, int H, int extras, const 
     DEV_HIP(dev, once());
     DEV_HIP(dev, hipStreamSynchronize(s));
     dev.download(out_host, dO, (M + 8) * D * 2);
+    DEV_HIP(dev, time_launches(s, iters, once, ms_out));
+    return dev.status();
+}
+
+int dd_dev_v_identity(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
+                      const float* xres_host, const float* ln, unsigned short* out_host, int iters, void* stream, float* ms_out) {
+    if (!c || !h_host || !wqkv || !out_host || !xres_host || !ln || B < 1 || iters < 0) return DD_ERR_INVALID;
+    const int D = 64 * H;
+    if (!qkv_attention_supported(D, H, L, extras)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "v_identity: D = 512 / 768 / 1024, L = 256 + 1 or 2 extra tokens only");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t M = (size_t)B * L;
+    std::vector<unsigned short> hb = bf16_rows(h_host, M, D, M, 0);
+    std::vector<unsigned short> hf((size_t)B * 256 * D), img((size_t)3 * D * D);
+    for (int b = 0; b < B; ++b)          // the patch rows in fragment order (MlpFusedArgs::ln_out_frag)
+        for (int n = 0; n < 256; ++n)
+            for (int k = 0; k < D; ++k)
+                hf[((((size_t)b * 8 + n / 32) * (D / 16) + k / 16) * 64 + (n % 32) + 32 * ((k % 16) / 8)) * 8 + k % 8] = hb[((size_t)b * L + extras + n) * D + k];
+    qkv_attention_pack(D, H, wqkv, host_f2bf, img.data());
+    // the fp32 residual stream: the extra-token rows only; the patch rows, which the kernel must never read, hold 0xFF bytes (NaN)
+    std::vector<float> xr(M * D);
+    std::memset(xr.data(), 0xFF, xr.size() * 4);
+    for (int b = 0; b < B; ++b) std::memcpy(xr.data() + (size_t)b * L * D, xres_host + (size_t)b * L * D, (size_t)extras * D * 4);
+    DevScope dev(c);
+    const bf16_t* dH = dev.upload(hf.data(), hf.size() * 2);
+    const bf16_t* dW = dev.upload(img.data(), img.size() * 2);
+    const float* dX = dev.upload(xr.data(), xr.size() * 4);
+    const float* dL = dev.upload(ln, (size_t)2 * D * 4);
+    bf16_t* dO = dev.filled<bf16_t>((M + 8) * D * 2, 0xFF);      // 8 canary rows behind the output
+    const float* dB = bqkv ? dev.upload(bqkv, (size_t)3 * D * 4) : nullptr;
+    auto once = [&]() { return launch_v_identity(dH, dW, dB, dX, dL, dL ? dL + D : nullptr, dO, B, L, H, D, extras, s); };
+    DEV_HIP(dev, once());
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(out_host, dO, (M + 8) * D * 2);
+    DEV_HIP(dev, time_launches(s, iters, once, ms_out));
+    return dev.status();
+}
+
+int dd_dev_v_copy(dd_ctx* c, int precision, int B, int L, int H, const float* qkv_host, void* out_host, int iters, void* stream, float* ms_out) {
+    const bool bf = precision == DD_PREC_BF16;
+    if (!c || (!bf && precision != DD_PREC_FP32) || B < 1 || L < 1 || H < 1 || !qkv_host || !out_host || iters < 0) return DD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const int D = 64 * H;
+    const size_t esz = bf ? 2 : 4, Lp = (size_t)make_head_major(L, H).Lp;
+    const size_t qkv_elems = ((size_t)B * 3 * H * Lp + 64) * 64, out_elems = ((size_t)B * L + 8) * D;
+    // head-major image (HeadMajor): 0xFF bytes (NaN) everywhere, then the rows l < L only
+    std::vector<unsigned char> img(qkv_elems * esz, 0xFF);
+    for (size_t u = 0; u < (size_t)B * 3 * H; ++u)
+        for (int l = 0; l < L; ++l) {
+            const float* row = qkv_host + (u * L + l) * 64;
+            const size_t at = (u * Lp + l) * 64;
+            if (bf) for (int d = 0; d < 64; ++d) reinterpret_cast<unsigned short*>(img.data())[at + d] = host_f2bf(row[d]);
+            else std::memcpy(img.data() + at * 4, row, 64 * 4);
+        }
+    DevScope dev(c);
+    const void* dQ = dev.upload(img.data(), img.size());
+    void* dO = dev.filled(out_elems * esz, 0xFF);
+    auto once = [&]() {
+        return bf ? launch_v_copy<bf16_t>((const bf16_t*)dQ, (bf16_t*)dO, B, L, H, D, s) : launch_v_copy<float>((const float*)dQ, (float*)dO, B, L, H, D, s);
+    };
+    const hipError_t first = dev.ok() ? once() : hipSuccess;
+    if (first == hipErrorInvalidValue) return ctx_fail(c, DD_ERR_UNSUPPORTED, "v_copy: 1 <= L <= 288, heads of 64");      // (refused before any launch)
+    DEV_HIP(dev, first);
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(out_host, dO, out_elems * esz);
     DEV_HIP(dev, time_launches(s, iters, once, ms_out));
     return dev.status();
 }

@@ -269,6 +269,17 @@ class Model:
                                                           _ptr(out), B, _stream_ptr(stream)))
         return out
 
+    def forward_perturbed(self, x, t, y, scale, layers, out=None, stream=None):
+        """Perturbed-attention guided eps = eps + scale * (eps - eps_perturbed) at timestep t (dd_forward_perturbed): the backbone runs
+        2 B rows, x as it is, then x with identity attention in the blocks of `layers` (block indices in forward order, or their bit
+        mask); max_batch must hold them.  y as in forward: labels of a class-conditional model, else None."""
+        B = x.shape[0]
+        out = torch.empty_like(x) if out is None else out
+        p = L.dd_pag(float(scale), layer_mask(layers), 0)
+        self.ctx.check(self.ctx.lib.dd_forward_perturbed(self.ctx.handle, self.handle, _ptr(x), float(t), _ptr(y), C.byref(p),
+                                                         _ptr(out), B, _stream_ptr(stream)))
+        return out
+
     def sample_step(self, x, t, y=None, z=None, noise="buffer", seed=0, variance="beta_tilde", eps_out=None,
                     stream=None):
         mode = {"none": L.DD_NOISE_NONE, "buffer": L.DD_NOISE_BUFFER, "philox": L.DD_NOISE_PHILOX}[noise]
@@ -329,6 +340,30 @@ class Autoguidance(NamedTuple):
     scale: float
 
 
+def layer_mask(layers):
+    """Block indices in forward order (in_blocks, mid_block, out_blocks), or their bit mask as an int -> the bit mask"""
+    if isinstance(layers, (int, np.integer)):
+        mask = int(layers)
+    else:
+        mask = 0
+        for i in layers:
+            if not 0 <= int(i) < 32:
+                raise ValueError(f"block index {i} outside [0, 32)")
+            mask |= 1 << int(i)
+    if not 0 <= mask < 1 << 32:
+        raise ValueError("block mask outside 32 bits")
+    return mask
+
+
+class Perturbed(NamedTuple):
+    """A loop's `guidance` argument for perturbed-attention guidance: every step runs its 2 B rows [x | x], the second half with identity
+    attention in the masked blocks of the running model (layers_first for the loop's first model, layers_late for its late model: block
+    indices or bit masks), and uses eps + scale * (eps - eps_perturbed).  Not with a known region or x0 thresholding."""
+    scale: float
+    layers_first: object
+    layers_late: object = 0
+
+
 class KnownRegion(NamedTuple):
     """A loop's `region` argument: after every step, x' is finished as mask * (ka[k] x0 + kb[k] z2) + (1 - mask) x' (x' kept bit for bit
     where mask == 0).  x0 [B,C,S,S] and mask [B,1,S,S] are fp32 device tensors, ka / kb one value per step of the call
@@ -359,8 +394,15 @@ def threshold_struct(threshold):
 def _loop_call(ctx, args, plain, guidance, region, x, threshold=None):
     """The loop entry of this argument struct as call(stream): `plain` (guidance None), its _guided form (guidance = (scale, null_label):
     classifier-free), its _autoguided form (guidance = Autoguidance(guide, scale)) or, with a KnownRegion, its _region form, which
-    takes either kind of guidance, or none, beside the dd_known_region.  No entry takes both kinds of guidance."""
+    takes either kind of guidance, or none, beside the dd_known_region.  guidance = Perturbed(scale, layers_first, layers_late): its
+    _perturbed form, alone.  No entry takes two kinds of guidance."""
     g = ag = None
+    if isinstance(guidance, Perturbed):
+        if region is not None or threshold is not None:
+            raise ValueError("perturbed-attention guidance does not combine with a known region or x0 thresholding")
+        pag = L.dd_pag(float(guidance.scale), layer_mask(guidance.layers_first), layer_mask(guidance.layers_late))
+        fn = getattr(ctx.lib, plain + "_perturbed")
+        return lambda st: fn(ctx.handle, C.byref(args), C.byref(pag), st)
     if isinstance(guidance, Autoguidance):
         ag = C.byref(L.dd_autoguidance(guidance.guide.handle, float(guidance.scale)))
     elif guidance is not None:

@@ -23,6 +23,10 @@ every step of the full model with the shallow one, eps = eps_full + s (eps_full 
 combination fused into the step kernel; the shallow model's own steps stay unguided.  ``--guide_config_path`` / ``--guide_checkpoint_path``
 name an explicit guide for a single-backbone run.  No labels are needed: unconditional models can be guided.
 
+Perturbed-attention guidance (engine option, not in the reference; Ahn et al. 2024): ``--pag_scale 3.0`` guides ONE model, unconditional
+ones included, with itself: every step also evaluates it with the self-attention map of the blocks ``--pag_layers`` (default: the middle
+block) replaced by the identity and uses eps = eps + s (eps - eps_perturbed), fused into the step kernel of every loop.
+
 Image-to-image and inpainting (engine options, not in the reference): ``--init_image x.npy --strength 0.5`` starts every loop from the
 given image noised to t = round(999 * 0.5) instead of from pure noise (SDEdit; latent models: .npy latents, or pixel-space files with
 ``--encode_images``, which the KL-VAE encoder of the engine turns into latents); ``--known_image x.npy --known_mask m.npy`` keeps the
@@ -43,7 +47,7 @@ import torch
 
 from .config import ModelParams, load_config
 from .autoencoder import get_autoencoder
-from .engine import (Autoguidance, Context, KnownRegion, X0Threshold, sample_affine_loop, sample_affine_region_loop, sample_loop,
+from .engine import (Autoguidance, Context, KnownRegion, Perturbed, X0Threshold, layer_mask, sample_affine_loop, sample_affine_region_loop, sample_loop,
                      sample_multistep_loop, sample_multistep_region_loop, sample_multistep_threshold_loop, sample_region_loop,
                      schedule_tables, threshold_struct)
 from .uvit import UViT
@@ -407,7 +411,7 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
                 late_model=None, t_switch=np.inf, *, noise: str = "torch_cpu", use_graph: bool = True,
                 num_steps: int = 1000, return_device_tensor: bool = False, cfg_scale=None, cfg_null_label: int = 1000,
                 solver=None, solver_steps: int = 20, solver_order: int = 2, autoguidance_scale=None, guide_model=None,
-                init_image=None, strength=None, known_image=None, known_mask=None, threshold=None):
+                init_image=None, strength=None, known_image=None, known_mask=None, threshold=None, pag=None):
     """reference sampler.py:82-155.  Returns (samples[B,H,W,C] float32 numpy = (x+1)/2, intermediates).
 
     cfg_scale (None: the unguided loops, unchanged): classifier-free guidance of every step's model output,
@@ -417,6 +421,11 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
     autoguidance_scale (None: off; exclusive with cfg_scale): autoguidance of every step's model output with guide_model (a UViT of the
         same image geometry; default: `model` when a late_model is given, the DuoDiff pair), eps_m + s * (eps_m - eps_guide).  A step
         that guide_model itself runs is the unguided step.  Labels y go to whichever models are class-conditional.
+
+    pag = (scale, layers_first, layers_late) (None: off; exclusive with cfg_scale, autoguidance_scale, known_image, init_image and
+        threshold): perturbed-attention guidance of every step's model output, eps + scale * (eps - eps_perturbed), eps_perturbed the
+        running model's output with identity attention in its blocks -- layers_first for `model`, layers_late for late_model (block
+        indices in forward order, or bit masks).  The backbones run 2 * batch_size rows.  No labels are needed.
 
     noise="torch_cpu": x_T and every z come from the torch CPU generator after seed_everything(seed),
         in the reference's order -> identical random numbers to a CPU reference run.
@@ -452,6 +461,16 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
             raise ValueError("autoguidance needs a guide model: pass guide_model, or a late_model (the first model then guides it)")
     elif guide_model is not None:
         raise ValueError("guide_model without autoguidance_scale")
+    if pag is not None:
+        if cfg_scale is not None or autoguidance_scale is not None or known_image is not None or init_image is not None or threshold is not None:
+            raise ValueError("perturbed-attention guidance does not combine with classifier-free guidance, autoguidance, a known region, "
+                             "an init image or x0 thresholding")
+        pag_scale, pag_first, pag_late = float(pag[0]), layer_mask(pag[1]), layer_mask(pag[2] if len(pag) > 2 else 0)
+        if not math.isfinite(pag_scale):
+            raise ValueError("pag scale must be finite")
+        for mdl, mask, what in ((model, pag_first, "layers_first"), (late_model, pag_late, "layers_late")):
+            if mdl is not None and mask >> mdl.depth:
+                raise ValueError(f"pag {what} names a block at or above the model's depth {mdl.depth}")
     if (init_image is None) != (strength is None):
         raise ValueError("init_image and strength go together")
     if (known_image is None) != (known_mask is None):
@@ -466,7 +485,7 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
     guidance = None if cfg_scale is None else (float(cfg_scale), int(cfg_null_label))
     if guidance is not None and y is None:
         raise ValueError("classifier-free guidance needs class labels")
-    rows = 2 * batch_size if guidance is not None else batch_size           # backbone rows per step
+    rows = 2 * batch_size if guidance is not None or pag is not None else batch_size    # backbone rows per step
     seed_everything(seed)                                                    # sampler.py:99
     x = torch.randn(batch_size, num_channels, sample_height, sample_width).to(device).contiguous()  # :100
     if y is not None:
@@ -499,6 +518,8 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
         for k0, k1 in _segments(plan.save_after):
             sw = None if plan.switch_after is None else min(max(plan.switch_after - k0, 0), k1 - k0)
             kw = dict(y=y, seed=seed, noise="philox", use_graph=use_graph, guidance=autoguidance or guidance)
+            if pag is not None:      # (a segment that starts behind the switch runs the late model as the loop's first)
+                kw["guidance"] = Perturbed(pag_scale, pag_late if sw == 0 else pag_first, pag_late)
             # with a known region: the same loop's _region form, the region's rows cut like the loop's
             known = () if region is None else (region._replace(ka=region.ka[k0:k1], kb=region.kb[k0:k1]),)
             if plan.kind == "ddpm":                                          # dd_sample counts t_switch from t = 999, switch_after from the start
@@ -527,13 +548,15 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
             t = tab["t"][k]
             z = torch.randn(x.shape).to(device) if tab["noise"][k] else None  # randn_like on the torch CPU stream (:52, :67, :119)
             y_cur = y if guide is None or cur.mp.num_classes > 0 else None    # (autoguidance: y may be there for the other model only)
-            if plan.kind == "ddpm" and guidance is None and (guide is None or guide is cur):
+            if plan.kind == "ddpm" and guidance is None and pag is None and (guide is None or guide is cur):
                 cur.sample_step(x, int(t), y=y_cur, z=z, noise="buffer")      # :130-133, fused
             else:
                 if guidance is not None:
                     cur.forward_guided(x, float(t), y, guidance[0], guidance[1], out=eps)
                 elif guide is not None:
                     cur.forward_autoguided(x, float(t), y, guide, autoguidance.scale, out=eps)
+                elif pag is not None:
+                    cur.forward_perturbed(x, float(t), y, pag_scale, pag_late if cur is late else pag_first, out=eps)
                 else:
                     cur.forward(x, float(t), y, out=eps)
                 if plan.kind == "ddpm":
@@ -620,6 +643,47 @@ def validate_autoguidance(args, config, config_late=None, config_guide=None):
             raise ValueError(f"autoguidance: the guide's image geometry (img_size, patch_size, in_chans) = "
                              f"{(guide.img_size, guide.patch_size, guide.in_chans)} differs from {name}'s "
                              f"{(mp.img_size, mp.patch_size, mp.in_chans)}")
+
+
+def pag_layers(spec, depth, what):
+    """--pag_layers / --pag_layers_first values (None: the default) -> block indices: "mid" is block depth // 2"""
+    spec = ["mid"] if spec is None else spec
+    out = []
+    for v in spec:
+        if v == "mid":
+            out.append(depth // 2)
+            continue
+        try:
+            i = int(v)
+        except ValueError:
+            raise ValueError(f"{what}: 'mid' or block indices, not {v!r}") from None
+        if not 0 <= i < depth:
+            raise ValueError(f"{what}: block {i} outside [0, {depth}) of the model")
+        out.append(i)
+    return out
+
+
+def validate_pag(args, config, config_late=None):
+    """The perturbed-attention options against the YAML configs, before any GPU work: ValueError on a bad combination.  Returns
+    get_samples' pag = (scale, layers_first, layers_late) or None.  --pag_layers names the blocks of the only model, or of the late model
+    of a pair; --pag_layers_first those of the first model of a pair."""
+    if args.pag_scale is None:
+        if args.pag_layers is not None or args.pag_layers_first is not None:
+            raise ValueError("--pag_layers / --pag_layers_first need --pag_scale")
+        return None
+    if not math.isfinite(args.pag_scale):
+        raise ValueError("--pag_scale must be finite")
+    for name in ("cfg_scale", "autoguidance_scale", "known_image", "init_image", "clip_x0", "dynamic_threshold"):
+        if getattr(args, name, None) is not None:
+            raise ValueError(f"--pag_scale and --{name} are exclusive")
+    depth = ModelParams.from_dict(config).depth
+    if config_late is None:
+        if args.pag_layers_first is not None:
+            raise ValueError("--pag_layers_first is for the first model of a pair (--checkpoint_path_late); use --pag_layers")
+        return args.pag_scale, pag_layers(args.pag_layers, depth, "--pag_layers"), []
+    depth_late = ModelParams.from_dict(config_late).depth
+    return (args.pag_scale, pag_layers(args.pag_layers_first, depth, "--pag_layers_first"),
+            pag_layers(args.pag_layers, depth_late, "--pag_layers"))
 
 
 def _load_image_file(path, what, mp, latent, pixels=False):
@@ -827,6 +891,16 @@ def get_args(argv=None):
                    help="(engine option) autoguidance eps = eps_m + S (eps_m - eps_guide): every step of a model other than the guide runs "
                         "the guide on the same rows; any value, 0 included, selects it (default: off).  Without an explicit guide the first "
                         "(shallow) model guides the late one and --checkpoint_path_late is required.  Exclusive with --cfg_scale")
+    p.add_argument("--pag_scale", type=float, default=None,
+                   help="(engine option) perturbed-attention guidance eps = eps + S (eps - eps_perturbed), eps_perturbed the same model with "
+                        "identity self-attention in the blocks of --pag_layers; any value, 0 included, selects the path (2 B backbone rows). "
+                        "Needs no labels and no second model.  Exclusive with --cfg_scale, --autoguidance_scale, --known_image, --init_image, "
+                        "--clip_x0 and --dynamic_threshold")
+    p.add_argument("--pag_layers", type=str, nargs="+", default=None, metavar="mid|I",
+                   help="(engine option) blocks with identity attention, by index in forward order (in_blocks, mid_block, out_blocks), of the "
+                        "only model or of the late model of a pair; default: mid = block depth // 2")
+    p.add_argument("--pag_layers_first", type=str, nargs="+", default=None, metavar="mid|I",
+                   help="(engine option) the same for the first model of a pair; default: mid")
     p.add_argument("--guide_config_path", type=str, default=None,
                    help="(engine option) yaml config of an explicit guide model (same img_size, patch_size, in_chans)")
     p.add_argument("--guide_checkpoint_path", type=str, default=None, help="(engine option) checkpoint of the explicit guide model")
@@ -887,7 +961,8 @@ def main(argv=None):
     validate_autoguidance(args, config, config_late, config_guide)
     region_kwargs = validate_region(args, config_late if config_late is not None else config)
     threshold = validate_threshold(args, config_late if config_late is not None else config)
-    rows = 2 * args.batch_size if args.cfg_scale is not None else args.batch_size
+    pag = validate_pag(args, config, config_late)
+    rows = 2 * args.batch_size if args.cfg_scale is not None or pag is not None else args.batch_size
     model, mp = build_model(config, args.checkpoint_path, args.precision, rows)
     model_late = None
     if config_late is not None:
@@ -915,7 +990,7 @@ def main(argv=None):
                                  y=y, autoencoder=autoencoder, late_model=model_late, t_switch=args.t_switch,
                                  timesteps_save=args.timesteps_save, noise=args.noise, use_graph=not args.no_graph,
                                  cfg_scale=args.cfg_scale, cfg_null_label=args.cfg_null_label, **solver_kwargs(args),
-                                 autoguidance_scale=args.autoguidance_scale, guide_model=model_guide, threshold=threshold, **region_kwargs)
+                                 autoguidance_scale=args.autoguidance_scale, guide_model=model_guide, threshold=threshold, pag=pag, **region_kwargs)
     tac = time.time()
     dump_statistics(tac - tic, out, args.batch_size)
     if args.no_png:

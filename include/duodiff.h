@@ -310,6 +310,35 @@ int dd_sample_autoguided(dd_ctx* ctx, const dd_sample_args* args, const dd_autog
 int dd_sample_affine_autoguided(dd_ctx* ctx, const dd_affine_sample_args* args, const dd_autoguidance* g, void* stream);
 int dd_sample_multistep_autoguided(dd_ctx* ctx, const dd_multistep_sample_args* args, const dd_autoguidance* g, void* stream);
 
+/* ---- perturbed-attention guidance (PAG; Ahn et al. 2024): one model, no labels, no second model ------------------------------ */
+/* A perturbed step runs the backbone on 2 B rows of the same x_t: the B images as they are (eps), then the same images with the
+ * self-attention map of the chosen blocks replaced by the identity -- every token attends only to itself, attention(q, k, v) = v
+ * (eps_perturbed) -- and the step's last kernel uses
+ *     eps = eps + scale * (eps - eps_perturbed)     in fp32, in that order: d = eps - eps_perturbed; eps = eps + scale * d
+ *                                                   (the rule of dd_guidance)
+ * A mask names blocks by bit: bit i is block i in forward order (in_blocks, mid_block, out_blocks).  Everything but the attention of a
+ * masked block (norm1, attn.qkv, attn.proj, the MLP, the long skips) runs unchanged on all 2 B rows; a block that is not masked runs
+ * the launches of the unguided forward.  A class-conditional model sees the labels on both halves ([y | y]); an unconditional model
+ * takes none.  Mask 0 makes both halves equal (d is exactly 0: the bits of the unguided entry), scale 0 reproduces the unguided loop.
+ * Philox ids, counters, counter_base and the multistep history are the unguided loop's; two half-batch chains are decided on the 2 B
+ * rows and split by image as under dd_guidance; captured graphs are keyed on both masks and the bits of the scale.
+ * Every entry returns DD_ERR_INVALID (with dd_last_error) before anything is enqueued when the struct is NULL, scale is not finite,
+ * a mask names a block at or above the depth of its model, 2 B > max_batch, a model carries early-exit heads, first and late are one
+ * model with two different masks, labels are missing or superfluous (as the unguided entries), or (the loops) the noise mode is host
+ * noise.  There is no entry point that also takes a dd_guidance, dd_autoguidance, dd_known_region or dd_x0_threshold. */
+typedef struct dd_pag {
+    float scale;             /* d = eps - eps_perturbed; eps = eps + scale * d (the rule of dd_guidance) */
+    uint32_t layers_first;   /* blocks of args->first with identity attention */
+    uint32_t layers_late;    /* blocks of args->late with identity attention */
+} dd_pag;
+/* x_dev [B,C,S,S], y_dev [B] int64 or NULL (as dd_forward), eps_dev [B,C,S,S]: the guided eps at timestep t; uses p->layers_first */
+int dd_forward_perturbed(dd_ctx* ctx, dd_model* m, const float* x_dev, float t, const int64_t* y_dev, const dd_pag* p, float* eps_dev,
+                         int B, void* stream);
+/* dd_sample / dd_sample_affine / dd_sample_multistep with perturbed-attention guidance (multistep: h holds the B images) */
+int dd_sample_perturbed(dd_ctx* ctx, const dd_sample_args* args, const dd_pag* p, void* stream);
+int dd_sample_affine_perturbed(dd_ctx* ctx, const dd_affine_sample_args* args, const dd_pag* p, void* stream);
+int dd_sample_multistep_perturbed(dd_ctx* ctx, const dd_multistep_sample_args* args, const dd_pag* p, void* stream);
+
 /* ---- known regions: inpainting and image-to-image starts (RePaint's replacement rule, Lugmayr et al. 2022, without resampling) ---- */
 /* After a step has produced x' (at the noise level the step lands on), every pixel is finished from a known image x0 and a mask m:
  *     kn  = ka * x0                      ka, kb: fp32 scalars of the step

@@ -50,6 +50,23 @@ int dd_dev_qkv_attention(dd_ctx* ctx, int B, int L, int H, int extras, const flo
 int dd_dev_qkv_attention_rows(dd_ctx* ctx, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
                               const float* xres_host, const float* ln, unsigned short* out_host, int iters, void* stream, float* ms_out);
 
+/* Development harness for the identity-attention launch (attention.hip v_identity_kernel; perturbed-attention guidance): the companion of the
+ * launch above for images whose attention map is the identity, out = v = h . Wv^T + bv with Wv / bv the last third of wqkv / bqkv.  Operands as
+ * dd_dev_qkv_attention_rows in its production mode, which is the only one: h_host [B L, D] supplies the patch rows (rounded to bf16; its
+ * extra-token rows are ignored), xres_host [B L, D] fp32 + ln [2, D] (gamma, beta) the extra-token rows, which the kernel normalises itself
+ * (norm1, eps 1e-5); the patch rows of the device copy of xres hold 0xFF bytes (NaN).  out_host [B L + 8, D] of bf16 bits is filled with 0xFF
+ * bytes before the launch and comes back WHOLE.  A refused shape is DD_ERR_UNSUPPORTED; nothing is launched and out_host is not written. */
+int dd_dev_v_identity(dd_ctx* ctx, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
+                      const float* xres_host, const float* ln, unsigned short* out_host, int iters, void* stream, float* ms_out);
+
+/* Development harness for the identity-attention launch of the paths that hold the qkv tensor (attention.hip v_copy_kernel<T>): out = the v
+ * rows, bit for bit.  qkv_host: fp32 [B, 3, H, L, 64] (q | k | v per image; precision DD_PREC_BF16: rounded to bf16 here).  The head-major
+ * device tensor ([B][3 H][Lp = L rounded up to 8][64] + 64 trailing rows) is filled with 0xFF bytes and only its rows l < L are written: the
+ * pad rows hold NaN.  out_host [B L + 8, 64 H] of bf16 bits / fp32 is filled with 0xFF bytes before the launch and comes back WHOLE.  A shape
+ * the launcher refuses (L > 288) is DD_ERR_UNSUPPORTED; nothing is launched.  `iters` timed launches -> ms_out. */
+int dd_dev_v_copy(dd_ctx* ctx, int precision, int B, int L, int H, const float* qkv_host, void* out_host, int iters, void* stream,
+                  float* ms_out);
+
 /* Development harness for the output head's first launch (rowops.hip head_dec_kernel; reference models/uvit.py:377-378):
  * dec = decoder_pred(LayerNorm(x)) in exact fp32 from host arrays x [M, D], norm gamma / beta [D], decoder_pred weight [pd, D] / bias [pd];
  * dec_host [M, pd] (rows the launch does not decode -- the first tok_e rows of every tok_l-row image when tok_l > 0 -- come back as NaN).

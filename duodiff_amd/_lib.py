@@ -161,6 +161,7 @@ SIGNATURES = {
     "dd_dev_v_identity": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_v_copy": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_mlp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)] + [C.c_void_p] * 8),
+    "dd_dev_block_tail": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 21 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_head_dec": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_gemm": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p] + [C.c_int] * 2 + [C.c_void_p] * 2 +
                     [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),

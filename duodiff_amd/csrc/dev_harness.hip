@@ -1,4 +1,4 @@
-// The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_qkv_attention, dd_dev_qkv_attention_rows, dd_dev_v_identity, dd_dev_v_copy, dd_dev_head_dec, dd_dev_gemm,
+// The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_block_tail, dd_dev_qkv_attention, dd_dev_qkv_attention_rows, dd_dev_v_identity, dd_dev_v_copy, dd_dev_head_dec, dd_dev_gemm,
 // dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather): test scaffolding, not product.  Each one packs host operands as finalize packs a model's, launches what the model launches
 // (launch_args.h), returns the outputs and times `iters` further launch sequences.  Buffers, transfers, timing and HIP errors go through
 // one DevScope (dev_scope.h); the context is reached through its accessors only.
@@ -89,6 +89,92 @@ int dd_dev_mlp(dd_ctx* c, int M, int D, int hidden, int extras, const float* x_h
     dev.download(xres_host, a.xres, (size_t)M * D * 4);
     if (out_host) dev.download(out_host, dO, (size_t)M * D * 2);
     if (a.ln_out) dev.download(ln_out_host, dH, (size_t)M * D * 2);
+    DEV_HIP(dev, time_launches(s, iters, once, ms_out));
+    return dev.status();
+}
+
+int dd_dev_block_tail(dd_ctx* c, int B, int n_patches, int extras, int D, int hidden, int last, int poison, const float* h_host,
+                      const float* w1, const float* b1, const float* w2, const float* b2, const float* ln_in, const float* ao_host,
+                      const float* wproj, const float* bproj, const float* ln_out, const float* skip_host, const float* wskip,
+                      const float* bskip, const float* wqkv, float* xres_host, unsigned short* out_host, unsigned short* ln_out_host,
+                      unsigned short* frag_host, float* tap_host, unsigned short* qkv_host, float* slab_host, int slab_rows, int* plan_out,
+                      int iters, void* stream, float* ms_out) {
+    const bool proj = ao_host && wproj && bproj;
+    const bool skp = skip_host && wskip && bskip;
+    const bool qk = wqkv && qkv_host;
+    const bool lnout = ln_out && ln_out_host;
+    const bool frag = frag_host != nullptr, tap = tap_host != nullptr;
+    if (!c || B < 1 || n_patches < 1 || extras < 0 || extras > 2 || D < 1 || hidden < 1 || !w1 || !b1 || !w2 || !b2 || !xres_host || iters < 0 ||
+        poison < 0 || poison > 255 || slab_rows < 0 || (slab_rows > 0) != (slab_host != nullptr) || (ln_in != nullptr) == (h_host != nullptr))
+        return DD_ERR_INVALID;
+    if ((proj && !ln_in) || (lnout && !ln_in) || (frag && !lnout) || (skp && (!proj || !lnout || !out_host)) || (tap && !skp) ||
+        (qk && (!proj || !lnout)) || (last && (!proj || lnout || skp || qk)))
+        return DD_ERR_INVALID;
+    if (!mlp_fused_supported(D, hidden)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "fused MLP: D in {64,128,256,512}, hidden % 64 == 0");
+    if (frag && skp && extras > 0 && D != 512) return ctx_fail(c, DD_ERR_UNSUPPORTED, "block tail: skip rows without their LayerNorm at D = 512 only");
+    hipStream_t s = (hipStream_t)stream;
+    const int L = extras + n_patches, M = B * L;
+    const size_t Mo = (size_t)round_up(M, 256) + 8, n16 = Mo * D * 2, n32 = Mo * D * 4;
+    const MlpImage im = MlpImage::of(D, hidden, proj, skp, qk);
+    std::vector<unsigned short> img(im.bytes() / 2, 0);
+    auto section = [&](size_t block) { return img.data() + im.at(block) / 2; };
+    std::vector<float> b1p(hidden);
+    if (proj) mlp_fused_pack_proj(D, wproj, host_f2bf, section(0));
+    mlp_fused_pack(D, hidden, w1, b1, w2, ln_in != nullptr, host_f2bf, section(im.mlp), b1p.data());
+    if (skp) mlp_fused_pack_skip(D, wskip, host_f2bf, section(im.skip));
+    if (qk) mlp_fused_pack_rows(D, 3 * D, wqkv, host_f2bf, section(im.qkv));
+    // the arguments, field by field as Backbone::block_tail fills them
+    MlpFusedArgs a{};
+    mlp_fused_plan(B, n_patches, extras, L, hidden, a);
+    if (last) { a.n_extra = 0; a.tiles_left = 0; }
+    if ((size_t)slab_rows < (size_t)a.tiles_left * a.groups * a.prows) return DD_ERR_INVALID;
+    if (plan_out) { plan_out[0] = a.tiles_main; plan_out[1] = a.tiles_left; plan_out[2] = a.groups; plan_out[3] = a.prows; }
+    DevScope dev(c);
+    // operands: Mo rows, the rows [M, Mo) hold `poison` bytes; X = nullptr in LayerNorm-in mode, as in the model
+    a.X = h_host ? dev.upload(bf16_rows(h_host, M, D, Mo, (unsigned char)poison).data(), n16) : nullptr; a.ldx = D;
+    a.wimg = (const char*)dev.upload(img.data(), img.size() * 2);
+    a.b1p = dev.upload(b1p.data(), (size_t)hidden * 4); a.b2 = dev.upload(b2, (size_t)D * 4);
+    if (ln_in) { a.ln_in_g = dev.upload(ln_in, (size_t)2 * D * 4); a.ln_in_b = a.ln_in_g + D; }
+    a.xres = dev.upload(xres_host, n32);
+    a.out = out_host ? dev.filled<bf16_t>(n16, 0xFF) : nullptr; a.ldo = D;
+    a.partial = slab_rows ? dev.filled<float>((size_t)slab_rows * D * 4, poison) : nullptr;
+    if (proj) {
+        a.ao = dev.upload(bf16_rows(ao_host, M, D, Mo, (unsigned char)poison).data(), n16); a.bproj = dev.upload(bproj, (size_t)D * 4); a.nproj = D / 32;
+        a.reduce_set = 1;
+    }
+    if (skp) {
+        a.skip = dev.upload(bf16_rows(skip_host, M, D, Mo, (unsigned char)poison).data(), n16);
+        if (tap) a.y_tap = dev.filled<float>(n32, 0xFF);
+        a.bskip = dev.upload(bskip, (size_t)D * 4); a.nskip = D / 16;
+    }
+    if (lnout) { a.ln_out_g = dev.upload(ln_out, (size_t)2 * D * 4); a.ln_out_b = a.ln_out_g + D; a.ln_out = dev.filled<bf16_t>(n16, 0xFF); }
+    if (frag) a.ln_out_frag = dev.filled<bf16_t>(n16, 0xFF);
+    const size_t qkv_elems = qk ? ((size_t)B * 3 * (D / 64) * make_head_major(L, D / 64).Lp + 64) * 64 : 0;
+    if (qk) { a.qkv_out = dev.filled<bf16_t>(qkv_elems * 2, 0xFF); a.qkv_dump = dev.alloc<bf16_t>(16384); a.hm = make_head_major(L, D / 64); a.nqkv = 3 * D / 32; }
+    MlpFusedArgs fr = a;      // the reduce launch's: no norm1 rows where a skip_linear follows or the consumer normalises them itself
+    if (skp || frag) fr.ln_out = nullptr;
+    auto rest = [&]() -> hipError_t {
+        hipError_t e = launch_mlp_reduce(fr, D, s);
+        if (e == hipSuccess && skp) e = launch_skip_rows_ln(a, D, s, !frag);
+        if (e == hipSuccess && qk) e = launch_qkv_rows(a, D, s);
+        return e;
+    };
+    auto once = [&]() -> hipError_t {
+        const hipError_t e = launch_mlp_fused(a, D, s);
+        return e == hipSuccess ? rest() : e;
+    };
+    const hipError_t first = dev.ok() ? launch_mlp_fused(a, D, s) : hipSuccess;
+    if (first == hipErrorInvalidValue) return ctx_fail(c, DD_ERR_UNSUPPORTED, "block tail: a combination of modes launch_mlp_fused refuses");      // (refused before any launch)
+    DEV_HIP(dev, first);
+    DEV_HIP(dev, rest());
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(xres_host, a.xres, n32);
+    if (out_host) dev.download(out_host, a.out, n16);
+    if (lnout) dev.download(ln_out_host, a.ln_out, n16);
+    if (frag) dev.download(frag_host, a.ln_out_frag, n16);
+    if (tap) dev.download(tap_host, a.y_tap, n32);
+    if (qk) dev.download(qkv_host, a.qkv_out, qkv_elems * 2);
+    if (slab_rows) dev.download(slab_host, a.partial, (size_t)slab_rows * D * 4);
     DEV_HIP(dev, time_launches(s, iters, once, ms_out));
     return dev.status();
 }

@@ -33,6 +33,31 @@ int dd_dev_mlp(dd_ctx* ctx, int M, int D, int hidden, int extras, const float* h
                const float* ao_host, const float* wproj, const float* bproj, const float* skip_host, const float* wskip,
                const float* bskip, const float* wqkv, unsigned short* qkv_out_host);
 
+/* The block tail as the model launches it (Backbone::block_tail: the fused launch, the reduce launch of the extra-token rows, their skip_linear
+ * rows, their qkv rows) on B images of n_patches patch tokens behind `extras` (0, 1 or 2) extra tokens: M = B (extras + n_patches) rows, row plan
+ * mlp_fused_plan(B, n_patches, extras, extras + n_patches, hidden).  Modes, each set as the model sets it:
+ *   ln_in [2, D] (gamma, beta): norm2 in the prologue, X = nullptr (h_host must be NULL); ln_in NULL: h_host [M, D] is the normalised input;
+ *   ao_host [M, D] + wproj [D, D] + bproj [D] (needs ln_in): attn.proj in front, reduce_set = 1;
+ *   ln_out [2, D] + ln_out_host (needs ln_in): the next block's norm1 row-major; + frag_host: the patch rows go to frag_host in fragment order
+ *     (MlpFusedArgs::ln_out_frag), the reduce launch gets ln_out = nullptr and the skip rows run without their LayerNorm (D = 512);
+ *   skip_host [M, D] + wskip [D, 2 D] + bskip [D] (needs the projection, ln_out and out_host): the next block's skip_linear behind the MLP;
+ *   tap_host (needs skip): y of every row goes to y_tap before skip_linear replaces it;
+ *   wqkv [3 D, D] + qkv_host (needs the projection and ln_out): the next block's attn.qkv last, head-major (images of extras + n_patches rows);
+ *   last != 0 (needs the projection; no ln_out / skip / qkv): the last block's launch, n_extra = 0 and tiles_left = 0 after the plan.
+ * A combination the launcher refuses is DD_ERR_UNSUPPORTED with nothing launched.
+ * Every output array has Mo = round_up(M, 256) + 8 rows of D, is filled with 0xFF bytes before the launch and comes back WHOLE: out_host (the bf16
+ * copy), ln_out_host, frag_host (bf16), tap_host (fp32); xres_host [Mo, D] fp32 in / out carries the caller's bytes, canary rows included;
+ * qkv_host [(B 3 (D / 64) Lp + 64) 64] bf16; slab_host [slab_rows, D] fp32 or NULL is the kernel's partial-sum buffer, filled with `poison` bytes
+ * (slab_rows >= tiles_left groups prows, else DD_ERR_INVALID).  The rows [M, Mo) of the device copies of ao, skip and h hold `poison` in every
+ * byte too (0xFF: NaN): the kernel clamps out-of-range rows to row 0 and must never read them.  plan_out[4] (or NULL) receives tiles_main,
+ * tiles_left, groups, prows of the launch.  `iters` timed launch sequences -> ms_out. */
+int dd_dev_block_tail(dd_ctx* ctx, int B, int n_patches, int extras, int D, int hidden, int last, int poison, const float* h_host,
+                      const float* w1, const float* b1, const float* w2, const float* b2, const float* ln_in, const float* ao_host,
+                      const float* wproj, const float* bproj, const float* ln_out, const float* skip_host, const float* wskip,
+                      const float* bskip, const float* wqkv, float* xres_host, unsigned short* out_host, unsigned short* ln_out_host,
+                      unsigned short* frag_host, float* tap_host, unsigned short* qkv_host, float* slab_host, int slab_rows, int* plan_out,
+                      int iters, void* stream, float* ms_out);
+
 /* Development harness for the attention launch that computes attn.qkv itself (attention.hip qkv_attention_kernel; bf16, H heads
  * of 64 with D = 64 H = 512, 768 or 1024, L = 256 patches + `extras` = 1 or 2 leading extra tokens -- qkv_attention_supported; anything else
  * is DD_ERR_UNSUPPORTED): out = softmax(q k^T / 8) v per (image, head) with q, k, v = split(h . wqkv^T + bqkv), from host arrays

@@ -19,6 +19,7 @@ DD_DEV_NO_FUSED_SKIP, DD_DEV_NO_FUSED_QKV, DD_DEV_NO_FUSED_QA = 32, 64, 128
 DD_PROF_DOMINANT, DD_PROF_BLOCK_TAIL, DD_PROF_FC1, DD_PROF_ROWLIN, DD_PROF_QKV_ATTENTION, DD_PROF_SPLITK = 0, 1, 2, 3, 4, 5
 DD_DEV_NO_CHAINS, DD_DEV_FORCE_CHAINS, DD_DEV_NO_ROWLIN, DD_DEV_NO_ROWLIN_PROJ, DD_DEV_NO_EMBED_LN, DD_DEV_NO_SPLITK, DD_DEV_NO_ROWLIN_SKIP = 256, 512, 1024, 2048, 4096, 8192, 16384
 DD_DEV_NO_SPLIT_HEADS = 32768
+DD_DEV_NO_FRAG_AO, DD_DEV_NO_FRAG_SKIP, DD_DEV_NO_FRAG_X = 65536, 131072, 262144
 
 
 class dd_config(C.Structure):
@@ -162,6 +163,8 @@ SIGNATURES = {
     "dd_dev_v_copy": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_mlp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)] + [C.c_void_p] * 8),
     "dd_dev_block_tail": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 21 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
+    "dd_dev_block_tail_frag": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 21 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)] + [C.c_void_p] * 5),
+    "dd_dev_qkv_attention_frag": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_head_dec": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_gemm": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p] + [C.c_int] * 2 + [C.c_void_p] * 2 +
                     [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),

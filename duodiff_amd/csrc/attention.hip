@@ -450,6 +450,8 @@ struct QkvAttnArgs {
     const float* ln_b;     //   and bias (reference models/uvit.py:206, eps 1e-5, two-pass statistics in fp32)
     bf16_t* out;           // [B L, D]
     int B, L, H, Lp, E;
+    bf16_t* out_frag = nullptr;   // or null: the PATCH rows' output goes here instead of out, in the fragment order the block tail's projection loads
+                           // ([B * 8 groups of 32 rows][D / 16 k-steps][64 lanes][8], natural k order: MlpFusedArgs::ao_frag); the extra-token rows still go to out
 };
 
 // LDS behind the K / V images: px = the extra rows' partial q / k / v sums [8 waves][6 tiles][2 rows][32 columns] fp32 (the split
@@ -710,7 +712,12 @@ __global__ void __launch_bounds__(512, 1) qkv_attention_kernel(const QkvAttnArgs
         float mx, sum;
         attend_tiles<bf16_t, 9, kMaxKeyTiles, true>(Ks, Vt, L, kMaxKeyTiles, lane, [&](int k) { return k; }, qcur, o, mx, sum);
         const float inv = 1.0f / sum;
-        bf16_t* orow = a.out + ((long long)b * L + E + row) * D + hh * kHD;
+        // where the 16-byte piece of k-step 4 hh + 2 dt + gp / 2 of the block tail's projection goes (after the swap a lane holds head dims
+        // 32 dt + 8 gp + 8 half .. + 7 of its row: that k-step's natural-k B fragment): row-major rows, or (out_frag) the order the tail loads
+        // straight into registers -- [32-row group = 8 b + wave][k-step][lane] x 16 bytes, a wave's store = 1 KB contiguous
+        bf16_t* orow = a.out + ((long long)b * L + E + row) * D + hh * kHD + 8 * half;
+        long long ostride = 16;
+        if (a.out_frag) { orow = a.out_frag + ((((long long)b * 8 + wave) * KS + 4 * hh) * 64 + lane) * 8; ostride = 512; }
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
             uint2 v[4];
@@ -725,7 +732,7 @@ __global__ void __launch_bounds__(512, 1) qkv_attention_kernel(const QkvAttnArgs
             for (int gp = 0; gp < 4; gp += 2) {
                 const auto s0 = __builtin_amdgcn_permlane32_swap(v[gp].x, v[gp + 1].x, false, false);
                 const auto s1 = __builtin_amdgcn_permlane32_swap(v[gp].y, v[gp + 1].y, false, false);
-                *reinterpret_cast<uint4*>(orow + dt * 32 + 8 * gp + 8 * half) = uint4{s0[0], s1[0], s0[1], s1[1]};
+                *reinterpret_cast<uint4*>(orow + (2 * dt + gp / 2) * ostride) = uint4{s0[0], s1[0], s0[1], s1[1]};
             }
         }
     }
@@ -966,9 +973,9 @@ static size_t v_identity_lds(int D) { return (size_t)2 * (D / 16) * 1024; }     
 static size_t qkv_attention_lds() { return (size_t)kLP * AttnLayout<bf16_t>::kRowK + AttnLayout<bf16_t>::kVBytes + kQaAuxBytes + kQaRing; }
 
 hipError_t launch_qkv_attention(const bf16_t* h, const bf16_t* wimg, const float* bias, const bf16_t* hx, const float* xres,
-                                const float* ln_g, const float* ln_b, bf16_t* out, int B, int L, int H, int D, int extras, hipStream_t s) {
+                                const float* ln_g, const float* ln_b, bf16_t* out, int B, int L, int H, int D, int extras, hipStream_t s, bf16_t* out_frag) {
     if (!qkv_attention_supported(D, H, L, extras) || !h || !wimg || (!hx && (!xres || !ln_g || !ln_b)) || !out || B < 1) return hipErrorInvalidValue;
-    const QkvAttnArgs a{h, wimg, bias, hx, xres, ln_g, ln_b, out, B, L, H, make_head_major(L, H).Lp, extras};
+    const QkvAttnArgs a{h, wimg, bias, hx, xres, ln_g, ln_b, out, B, L, H, make_head_major(L, H).Lp, extras, out_frag};
     switch (D) {
         case 512: hipLaunchKernelGGL((qkv_attention_kernel<512>), dim3(B * H), dim3(512), qkv_attention_lds(), s, a); break;
         case 768: hipLaunchKernelGGL((qkv_attention_kernel<768>), dim3(B * H), dim3(512), qkv_attention_lds(), s, a); break;

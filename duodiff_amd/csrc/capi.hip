@@ -165,6 +165,10 @@ struct WsPtrs {
     float* mlp_partial = nullptr;         // partial slabs of hidden-split leftover tiles (mlp_fused_plan)
     bf16_t* qkv_dump = nullptr;           // scratch for the qkv stores of rows past the end of a ragged tile
     bf16_t* hfrag = nullptr;              // fused_qa: norm1 of the patch rows in MFMA fragment order (MlpFusedArgs::ln_out_frag)
+    // the patch rows' hand-offs in MFMA fragment order (dd_model::frag_ao / frag_skip / frag_x): each buffer holds batch * N * D elements
+    bf16_t* aofrag = nullptr;             // attention output -> the tail's projection (QkvAttnArgs::out_frag -> MlpFusedArgs::ao_frag)
+    std::vector<bf16_t*> skipfrags;       // in-block bi's bf16 copy -> the SKIP phases of its out-block's tail (out_frag -> skip_frag)
+    float* xfrag = nullptr;               // the fp32 residual rows from one tail to the next (x_out_frag -> x_in_frag)
     float* ytap = nullptr;                // early-exit models with fused_skip: the block output y of the launches that run the next skip_linear (MlpFusedArgs::y_tap)
 };
 
@@ -199,6 +203,11 @@ struct dd_model {
     bool rowlin_skip = false;             // ... and the out-blocks' skip_linear + norm1
     bool rowlin_proj = false;             // ... and attn.proj + residual + norm2 likewise
     bool rowlin_fc2 = false;              // embed_dim 768 on the GEMM path: mlp.fc2 + residual + the next block's norm1 in one row-resident launch (rowlin.hip)
+    // fused_qa + fused_proj at embed_dim 512: the patch rows travel between the attention launch and the block tails in fragment order, 1 KB per wave
+    // instruction on both sides; the extra-token rows stay row-major in ao / skips / x
+    bool frag_ao = false;                 // attention output -> projection
+    bool frag_skip = false;               // in-block output -> the out-block's skip_linear (fused_skip)
+    bool frag_x = false;                  // residual rows between consecutive tails (not for early-exit models, whose heads read x every block)
     bool fused_qa = false;                // attn.qkv computed inside the attention launch (attention.hip qkv_attention_kernel): takes precedence over
                                           // fused_qkv wherever the previous block's fused launch leaves norm1 in h
     // each chain's activation workspace: [0] laid out for max_batch (dd_model_finalize), [1] for half of it (ensure_chain_ws, on the first chained call)
@@ -366,6 +375,11 @@ void ws_layout(const dd_model* m, int batch, WsPtrs& w, Arena& a) {
     if (m->fused_qkv) a.space(w.qkv_dump, 16384);
     if (m->fused_qa) a.space(w.hfrag, (size_t)batch * m->N * D * 2);
     if (m->ee_type >= 0 && m->fused_skip) a.space(w.ytap, Mp * D * 4);
+    const size_t patch_elems = (size_t)batch * m->N * D;
+    if (m->frag_ao) a.space(w.aofrag, patch_elems * 2);
+    w.skipfrags.assign(m->frag_skip ? m->half_depth : 0, nullptr);
+    for (bf16_t*& sf : w.skipfrags) a.space(sf, patch_elems * 2);
+    if (m->frag_x) a.space(w.xfrag, patch_elems * 4);
 }
 // ---- dd_model_finalize: the kernel path of each stage, then every weight packed into one arena
 // (a function of the model, its precision and the development flags dd_dev_set_flags: never of a call's batch)
@@ -379,6 +393,11 @@ void choose_paths(dd_model* m, int precision, unsigned flags) {
     // (early-exit models too: their heads and probes read the residual stream between blocks, which this launch does not touch)
     // (embed_dim 768 / 1024 too, which have no fused block tail: their norm1 launch writes the fragment order, the qkv tensor is gone)
     m->fused_qa = precision == DD_PREC_BF16 && qkv_attention_supported(D, m->H, L, m->extras) && !(flags & DD_DEV_NO_FUSED_QA);
+    // the patch rows' hand-offs in fragment order ride on that launch and the proj-fused tail (mlp_fused.hip FRAG: D = 512)
+    const bool frag = m->fused_qa && m->fused_proj && D == 512 && m->N % 32 == 0;
+    m->frag_ao = frag && !(flags & DD_DEV_NO_FRAG_AO);
+    m->frag_skip = frag && m->fused_skip && !(flags & DD_DEV_NO_FRAG_SKIP);
+    m->frag_x = frag && m->ee_type < 0 && !(flags & DD_DEV_NO_FRAG_X);
     // (embed_dim 768, no fused block tail) mlp.fc2 with the residual rows resident in registers: x read and written once, the next norm1 from registers
     m->rowlin_fc2 = precision == DD_PREC_BF16 && !m->fused_mlp && rowlin_supported(D, hid) && m->N % 32 == 0 && !(flags & DD_DEV_NO_ROWLIN);
     m->rowlin_proj = m->rowlin_fc2 && !(flags & DD_DEV_NO_ROWLIN_PROJ);
@@ -609,6 +628,7 @@ struct Handoff {
                          // normalises the extra-token rows itself, from x)
     bool qkv = false;    // its attn.qkv is in qkv
     bool skip = false;   // its skip_linear has run: x holds the output, ytap the block input y that its early-exit heads read
+    bool xfrag = false;  // the patch rows of the residual stream are in xfrag, in the order the block tail loads them (x holds the extra-token rows only)
 };
 
 // one forward of B rows of chain ch, enqueued on s (Backbone<T>{m, ch, B, s, ee}): the stages of a block each enqueue their launches and
@@ -636,6 +656,7 @@ struct Backbone {
     // buffer, which the fused block tail never touches.
     float* ee_dec_all = ee && m->ee_batched ? (float*)ws.hid : nullptr;
     float* ee_srow_all = ee_dec_all ? ee_dec_all + (size_t)nb * M * m->pd : nullptr;
+    bool ao_in_frag = false;     // norm1_attention -> block_tail of the same block: the patch rows of the attention output are in aofrag
 
     // in-context timing (dd_profile_steps): an event on s in front of and behind every launch of the selected kind (DD_TIMED)
     int mark(int kind) {
@@ -779,10 +800,14 @@ struct Backbone {
         // a masked block: the attention launch on images [0, Bn), the identity launch on the Bi images behind them (operands offset by image)
         const bool masked = (pert_mask >> bi) & 1u;
         const int Bn = masked ? pert_first : B, Bi = B - Bn;
+        // the patch rows' output in the order the tail's projection loads it -- not in a block where the identity launch runs: that block takes the
+        // row-major ao on both sides
+        ao_in_frag = qa && m->frag_ao && Bi == 0;
         if (qa) {
             if constexpr (bf16) {
                 if (Bn > 0)
-                    DD_TIMED(DD_PROF_QKV_ATTENTION, launch_qkv_attention(ws.hfrag, w.qa_img, w.qkv_b, nullptr, ws.x, w.ln1_g, w.ln1_b, (bf16_t*)ao, Bn, L, m->H, D, m->extras, s));
+                    DD_TIMED(DD_PROF_QKV_ATTENTION, launch_qkv_attention(ws.hfrag, w.qa_img, w.qkv_b, nullptr, ws.x, w.ln1_g, w.ln1_b, (bf16_t*)ao, Bn, L, m->H, D, m->extras, s,
+                                                                         ao_in_frag ? ws.aofrag : nullptr));
                 if (Bi > 0)
                     DD_HIP(c, launch_v_identity(ws.hfrag + (size_t)Bn * m->N * D, w.qa_img, w.qkv_b, ws.x + (size_t)Bn * L * D, w.ln1_g, w.ln1_b,
                                                 (bf16_t*)ao + (size_t)Bn * L * D, Bi, L, m->H, D, m->extras, s));
@@ -822,9 +847,10 @@ struct Backbone {
         const bool is_in = bi < m->half_depth;   // the next block starts with norm1 (no skip_linear in between)
         const BlockW* wn = bi + 1 < nb ? &m->blocks[bi + 1] : nullptr;
         T* copy = is_in ? (T*)ws.skips[bi] : (wn ? xb : nullptr);
+        const Handoff in = next;     // (what this block found: the residual rows' form is this stage's to read)
         next = Handoff{};
         if constexpr (bf16) {
-            if (m->fused_mlp) return block_tail(bi, copy, next);
+            if (m->fused_mlp) return block_tail(bi, copy, in, next);
         }
         GemmArgs<T> g1{h, nullptr, (const T*)w.fc1_w, w.fc1_b, nullptr, hid, M, m->hidden, D, D, D, 0, m->hid_ld};
         g1.tile128 = tile128(m->hidden, D, D);
@@ -843,22 +869,31 @@ struct Backbone {
 
     // (bf16) the fused block tail: [attn.proj +] norm2 + the MLP in one launch (mlp_fused.hip), with whatever the next block starts with
     // behind it -- its norm1; its skip_linear first (fused_skip); its attn.qkv last (fused_qkv), unless its attention launch computes that (fused_qa)
-    int block_tail(int bi, T* copy, Handoff& next) {
+    int block_tail(int bi, T* copy, const Handoff in, Handoff& next) {
         const BlockW& w = m->blocks[bi];
         MlpFusedArgs fa{};
         fa.X = nullptr; fa.ldx = D; fa.wimg = w.mlp_img; fa.b1p = w.mlp_b1p; fa.b2 = w.fc2_b;
         fa.ln_in_g = w.ln2_g; fa.ln_in_b = w.ln2_b;                       // norm2 of this block, in the prologue
         fa.xres = ws.x; fa.out = (bf16_t*)copy; fa.ldo = D; fa.partial = ws.mlp_partial;
         if (m->fused_proj) { fa.ao = (const bf16_t*)ao; fa.bproj = w.proj_b; fa.nproj = D / 32; }
+        if (ao_in_frag) fa.ao_frag = ws.aofrag;
+        // the long-skip operand's patch rows: in-block bi's copy into its fragment buffer, read back by the tail that runs out-block nb - 1 - bi's skip_linear
+        if (m->frag_skip && bi < m->half_depth) fa.out_frag = ws.skipfrags[bi];
         next.skip = m->fused_skip && bi >= m->half_depth && bi + 1 < nb;   // the next block starts with skip_linear
         if (next.skip) {
             fa.skip = (const bf16_t*)skip_of(bi + 1);
+            if (m->frag_skip) fa.skip_frag = ws.skipfrags[nb - 1 - (bi + 1)];
             if (ee) fa.y_tap = ws.ytap;                                       // the next block's head / probe read y, which this launch consumes
             fa.bskip = m->blocks[bi + 1].skip_b; fa.nskip = D / 16;
         }
         // the next block's norm1 where it starts with one (behind its skip_linear, if this launch runs that); its attn.qkv inside its attention
         // launch (fused_qa), else last of all in this launch (fused_qkv) -- wherever this launch leaves that block's norm1
         const bool h_next = bi < m->half_depth || next.skip;
+        // the residual patch rows: from xfrag where the previous tail left them there, into xfrag where the next launch to touch them is another tail
+        // (h_next: no skip_linear launch in between); the last tail writes x for the output head -- fragment order lives between tails only
+        if (in.xfrag) fa.x_in_frag = ws.xfrag;
+        next.xfrag = m->frag_x && h_next;
+        if (next.xfrag) fa.x_out_frag = ws.xfrag;
         next.frag = m->fused_qa && h_next;
         next.qkv = !next.frag && m->fused_qkv && h_next;
         next.h = h_next && !next.frag && !next.qkv;

@@ -156,6 +156,17 @@ struct MlpFusedArgs {
                            // patch rows by the main tiles, the extra-token rows by the reduce launch (the next block's output head and probe read y)
     int reduce_set = 0;    // launch_mlp_reduce: x = b2 + slabs instead of x += (the extra-token rows of a row-resident skip_linear; of a block tail with the
                            // projection in front: the first hidden group's slab carries x + proj(ao) + b)
+    const bf16_t* ao_frag = nullptr;   // nproj > 0, or null: the main tiles read the attention output of the PATCH rows here instead of ao, in MFMA fragment
+                           // order ([32-row group of patch rows][D / 16 k-steps][64 lanes] x 16 bytes, natural k order: launch_qkv_attention's out_frag);
+                           // the extra-token rows still come from ao; needs tok_n % 32 == 0
+    bf16_t* out_frag = nullptr;        // or null (launches without skip phases): the main tiles write the bf16 copy of the PATCH rows here instead of out, in
+                           // the same fragment order (k-step ks = columns 16 ks .. 16 ks + 15); the reduce launch still writes the extra-token rows to out
+    const bf16_t* skip_frag = nullptr; // nskip > 0, or null: the SKIP phases read the long-skip operand's PATCH rows here (an in-block's out_frag) instead of
+                           // skip; the extra-token rows (launch_skip_rows_ln) still come from skip
+    const float* x_in_frag = nullptr;  // or null: the main tiles read the fp32 residual PATCH rows here instead of xres, as the previous tail left them:
+                           // [32-row group][D / 32 tiles t][4 quads g][64 lanes] x 16 bytes, lane (r, h) of (t, g) = columns 32 t + 8 g + 4 h .. + 3 of row r
+    float* x_out_frag = nullptr;       // or null: ... and write the updated rows here instead of xres, in that order.  Extra-token rows: always xres.
+                           // The five hand-offs above: D = 512 with the projection in front, no qkv phases; x_*_frag not together with y_tap
 };
 // One 1 KB MFMA operand fragment of a row-major weight W (row stride ld): 64 lanes x 8 bf16 of the 32-row x 16-k piece at (row0, k0), lane = (row
 // lane & 31, half h = lane >> 5) -- what one ds_read_b128 / 16-byte load per lane puts in front of a v_mfma_f32_32x32x16_bf16.  Element j of half h holds
@@ -288,11 +299,13 @@ hipError_t launch_attention(const T* qkv, T* out, int B, int L, int H, int D, hi
 // attn.qkv + attention in one launch (attention.hip qkv_attention_kernel): h = norm1 of the patch rows in fragment order
 // (MlpFusedArgs::ln_out_frag); the extra-token rows: hx = norm1 row-major [B L, D], or hx = nullptr and xres / ln_g / ln_b = the fp32
 // residual stream and this block's norm1 parameters (the kernel normalises the rows itself); wimg from qkv_attention_pack;
-// bf16, D = 512 / 768 / 1024 (heads of 64), L = 256 + extras, extras = 1 or 2 only (qkv_attention_supported)
+// bf16, D = 512 / 768 / 1024 (heads of 64), L = 256 + extras, extras = 1 or 2 only (qkv_attention_supported); out_frag or null: the patch rows'
+// output goes there in fragment order (MlpFusedArgs::ao_frag, B * 256 * D elements) instead of out, which then receives the extra-token rows only
 bool qkv_attention_supported(int D, int H, int L, int extras);
 void qkv_attention_pack(int D, int H, const float* w, unsigned short (*to_bf16)(float), unsigned short* img);
 hipError_t launch_qkv_attention(const bf16_t* h, const bf16_t* wimg, const float* bias, const bf16_t* hx, const float* xres,
-                                const float* ln_g, const float* ln_b, bf16_t* out, int B, int L, int H, int D, int extras, hipStream_t s);
+                                const float* ln_g, const float* ln_b, bf16_t* out, int B, int L, int H, int D, int extras, hipStream_t s,
+                                bf16_t* out_frag = nullptr);
 
 // Identity attention (perturbed-attention guidance): attention(q, k, v) = v for the B images given.  launch_v_identity is the companion of
 // launch_qkv_attention (the same operands, xres / ln_g / ln_b mode only; qkv_attention_supported shapes): v is computed from norm1 and the

@@ -1,4 +1,4 @@
-// The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_block_tail, dd_dev_qkv_attention, dd_dev_qkv_attention_rows, dd_dev_v_identity, dd_dev_v_copy, dd_dev_head_dec, dd_dev_gemm,
+// The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_block_tail, dd_dev_block_tail_frag, dd_dev_qkv_attention, dd_dev_qkv_attention_rows, dd_dev_qkv_attention_frag, dd_dev_v_identity, dd_dev_v_copy, dd_dev_head_dec, dd_dev_gemm,
 // dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather): test scaffolding, not product.  Each one packs host operands as finalize packs a model's, launches what the model launches
 // (launch_args.h), returns the outputs and times `iters` further launch sequences.  Buffers, transfers, timing and HIP errors go through
 // one DevScope (dev_scope.h); the context is reached through its accessors only.
@@ -93,12 +93,16 @@ int dd_dev_mlp(dd_ctx* c, int M, int D, int hidden, int extras, const float* x_h
     return dev.status();
 }
 
-int dd_dev_block_tail(dd_ctx* c, int B, int n_patches, int extras, int D, int hidden, int last, int poison, const float* h_host,
-                      const float* w1, const float* b1, const float* w2, const float* b2, const float* ln_in, const float* ao_host,
-                      const float* wproj, const float* bproj, const float* ln_out, const float* skip_host, const float* wskip,
-                      const float* bskip, const float* wqkv, float* xres_host, unsigned short* out_host, unsigned short* ln_out_host,
-                      unsigned short* frag_host, float* tap_host, unsigned short* qkv_host, float* slab_host, int slab_rows, int* plan_out,
-                      int iters, void* stream, float* ms_out) {
+}  // extern "C"
+
+// dd_dev_block_tail and dd_dev_block_tail_frag: the second adds the patch rows' hand-offs in fragment order (all null: the first)
+static int block_tail_run(dd_ctx* c, int B, int n_patches, int extras, int D, int hidden, int last, int poison, const float* h_host,
+                          const float* w1, const float* b1, const float* w2, const float* b2, const float* ln_in, const float* ao_host,
+                          const float* wproj, const float* bproj, const float* ln_out, const float* skip_host, const float* wskip,
+                          const float* bskip, const float* wqkv, float* xres_host, unsigned short* out_host, unsigned short* ln_out_host,
+                          unsigned short* frag_host, float* tap_host, unsigned short* qkv_host, float* slab_host, int slab_rows, int* plan_out,
+                          int iters, void* stream, float* ms_out, const unsigned short* ao_frag_host, const unsigned short* skip_frag_host,
+                          const float* xin_frag_host, unsigned short* out_frag_host, float* xout_frag_host) {
     const bool proj = ao_host && wproj && bproj;
     const bool skp = skip_host && wskip && bskip;
     const bool qk = wqkv && qkv_host;
@@ -112,8 +116,17 @@ int dd_dev_block_tail(dd_ctx* c, int B, int n_patches, int extras, int D, int hi
         return DD_ERR_INVALID;
     if (!mlp_fused_supported(D, hidden)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "fused MLP: D in {64,128,256,512}, hidden % 64 == 0");
     if (frag && skp && extras > 0 && D != 512) return ctx_fail(c, DD_ERR_UNSUPPORTED, "block tail: skip rows without their LayerNorm at D = 512 only");
+    if ((ao_frag_host && !proj) || (skip_frag_host && !skp) || (out_frag_host && !out_host)) return DD_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const int L = extras + n_patches, M = B * L;
+    // the fragment-order buffers hold the B n_patches patch rows; the output ones carry 8 canary rows (0xFF bytes) in front and behind.  The patch
+    // rows of the row-major device buffer a fragment operand stands in for hold `poison` bytes: the main tiles must not read them
+    const size_t pe = (size_t)B * n_patches * D, guard = (size_t)8 * D;
+    auto rows_patch_poisoned = [&](const float* src) {
+        std::vector<unsigned short> r = bf16_rows(src, M, D, (size_t)round_up(M, 256) + 8, (unsigned char)poison);
+        for (int b = 0; b < B; ++b) std::memset(r.data() + ((size_t)b * L + extras) * D, poison, (size_t)n_patches * D * 2);
+        return r;
+    };
     const size_t Mo = (size_t)round_up(M, 256) + 8, n16 = Mo * D * 2, n32 = Mo * D * 4;
     const MlpImage im = MlpImage::of(D, hidden, proj, skp, qk);
     std::vector<unsigned short> img(im.bytes() / 2, 0);
@@ -135,15 +148,27 @@ int dd_dev_block_tail(dd_ctx* c, int B, int n_patches, int extras, int D, int hi
     a.wimg = (const char*)dev.upload(img.data(), img.size() * 2);
     a.b1p = dev.upload(b1p.data(), (size_t)hidden * 4); a.b2 = dev.upload(b2, (size_t)D * 4);
     if (ln_in) { a.ln_in_g = dev.upload(ln_in, (size_t)2 * D * 4); a.ln_in_b = a.ln_in_g + D; }
-    a.xres = dev.upload(xres_host, n32);
+    if (xin_frag_host) {      // the patch rows come from the fragment buffer: their row-major copies hold `poison`
+        std::vector<float> xr(xres_host, xres_host + Mo * D);
+        for (int b = 0; b < B; ++b) std::memset(xr.data() + ((size_t)b * L + extras) * D, poison, (size_t)n_patches * D * 4);
+        a.xres = dev.upload(xr.data(), n32);
+        a.x_in_frag = dev.upload(xin_frag_host, pe * 4);
+    } else {
+        a.xres = dev.upload(xres_host, n32);
+    }
+    if (xout_frag_host) a.x_out_frag = dev.filled<float>((pe + 2 * guard) * 4, 0xFF) + guard;
+    if (out_frag_host) a.out_frag = dev.filled<bf16_t>((pe + 2 * guard) * 2, 0xFF) + guard;
     a.out = out_host ? dev.filled<bf16_t>(n16, 0xFF) : nullptr; a.ldo = D;
     a.partial = slab_rows ? dev.filled<float>((size_t)slab_rows * D * 4, poison) : nullptr;
     if (proj) {
-        a.ao = dev.upload(bf16_rows(ao_host, M, D, Mo, (unsigned char)poison).data(), n16); a.bproj = dev.upload(bproj, (size_t)D * 4); a.nproj = D / 32;
+        a.ao = dev.upload((ao_frag_host ? rows_patch_poisoned(ao_host) : bf16_rows(ao_host, M, D, Mo, (unsigned char)poison)).data(), n16);
+        a.bproj = dev.upload(bproj, (size_t)D * 4); a.nproj = D / 32;
+        if (ao_frag_host) a.ao_frag = dev.upload(ao_frag_host, pe * 2);
         a.reduce_set = 1;
     }
     if (skp) {
-        a.skip = dev.upload(bf16_rows(skip_host, M, D, Mo, (unsigned char)poison).data(), n16);
+        a.skip = dev.upload((skip_frag_host ? rows_patch_poisoned(skip_host) : bf16_rows(skip_host, M, D, Mo, (unsigned char)poison)).data(), n16);
+        if (skip_frag_host) a.skip_frag = dev.upload(skip_frag_host, pe * 2);
         if (tap) a.y_tap = dev.filled<float>(n32, 0xFF);
         a.bskip = dev.upload(bskip, (size_t)D * 4); a.nskip = D / 16;
     }
@@ -175,12 +200,43 @@ int dd_dev_block_tail(dd_ctx* c, int B, int n_patches, int extras, int D, int hi
     if (tap) dev.download(tap_host, a.y_tap, n32);
     if (qk) dev.download(qkv_host, a.qkv_out, qkv_elems * 2);
     if (slab_rows) dev.download(slab_host, a.partial, (size_t)slab_rows * D * 4);
+    if (xout_frag_host) dev.download(xout_frag_host, a.x_out_frag - guard, (pe + 2 * guard) * 4);
+    if (out_frag_host) dev.download(out_frag_host, a.out_frag - guard, (pe + 2 * guard) * 2);
     DEV_HIP(dev, time_launches(s, iters, once, ms_out));
     return dev.status();
 }
 
-int dd_dev_qkv_attention_rows(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
-                              const float* xres_host, const float* ln, unsigned short* out_host, int iters, void* stream, float* ms_out) {
+extern "C" {
+
+int dd_dev_block_tail(dd_ctx* c, int B, int n_patches, int extras, int D, int hidden, int last, int poison, const float* h_host,
+                      const float* w1, const float* b1, const float* w2, const float* b2, const float* ln_in, const float* ao_host,
+                      const float* wproj, const float* bproj, const float* ln_out, const float* skip_host, const float* wskip,
+                      const float* bskip, const float* wqkv, float* xres_host, unsigned short* out_host, unsigned short* ln_out_host,
+                      unsigned short* frag_host, float* tap_host, unsigned short* qkv_host, float* slab_host, int slab_rows, int* plan_out,
+                      int iters, void* stream, float* ms_out) {
+    return block_tail_run(c, B, n_patches, extras, D, hidden, last, poison, h_host, w1, b1, w2, b2, ln_in, ao_host, wproj, bproj, ln_out, skip_host, wskip,
+                          bskip, wqkv, xres_host, out_host, ln_out_host, frag_host, tap_host, qkv_host, slab_host, slab_rows, plan_out, iters, stream,
+                          ms_out, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int dd_dev_block_tail_frag(dd_ctx* c, int B, int n_patches, int extras, int D, int hidden, int last, int poison, const float* h_host,
+                           const float* w1, const float* b1, const float* w2, const float* b2, const float* ln_in, const float* ao_host,
+                           const float* wproj, const float* bproj, const float* ln_out, const float* skip_host, const float* wskip,
+                           const float* bskip, const float* wqkv, float* xres_host, unsigned short* out_host, unsigned short* ln_out_host,
+                           unsigned short* frag_host, float* tap_host, unsigned short* qkv_host, float* slab_host, int slab_rows, int* plan_out,
+                           int iters, void* stream, float* ms_out, const unsigned short* ao_frag_host, const unsigned short* skip_frag_host,
+                           const float* xin_frag_host, unsigned short* out_frag_host, float* xout_frag_host) {
+    return block_tail_run(c, B, n_patches, extras, D, hidden, last, poison, h_host, w1, b1, w2, b2, ln_in, ao_host, wproj, bproj, ln_out, skip_host, wskip,
+                          bskip, wqkv, xres_host, out_host, ln_out_host, frag_host, tap_host, qkv_host, slab_host, slab_rows, plan_out, iters, stream,
+                          ms_out, ao_frag_host, skip_frag_host, xin_frag_host, out_frag_host, xout_frag_host);
+}
+
+}  // extern "C"
+
+// dd_dev_qkv_attention_rows and dd_dev_qkv_attention_frag (out_frag_host non-null: the patch rows' output in fragment order)
+static int qkv_attention_run(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
+                             const float* xres_host, const float* ln, unsigned short* out_host, unsigned short* out_frag_host, int iters, void* stream,
+                             float* ms_out) {
     if (!c || !h_host || !wqkv || !out_host || (xres_host && !ln) || B < 1 || iters < 0) return DD_ERR_INVALID;
     const int D = 64 * H;
     if (!qkv_attention_supported(D, H, L, extras)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "qkv_attention: D = 512 / 768 / 1024, L = 256 + 1 or 2 extra tokens only");
@@ -210,13 +266,30 @@ int dd_dev_qkv_attention_rows(dd_ctx* c, int B, int L, int H, int extras, const 
     const float* dX = xres_host ? dev.upload(xr.data(), xr.size() * 4) : nullptr;
     const float* dL = xres_host ? dev.upload(ln, (size_t)2 * D * 4) : nullptr;
     bf16_t* dO = dev.filled<bf16_t>((M + 8) * D * 2, 0xFF);      // 8 canary rows behind the output
+    const size_t pe = (size_t)B * 256 * D, guard = (size_t)8 * D;          // the fragment-order output: 8 canary rows in front and behind
+    bf16_t* dF = out_frag_host ? dev.filled<bf16_t>((pe + 2 * guard) * 2, 0xFF) + guard : nullptr;
     const float* dB = bqkv ? dev.upload(bqkv, (size_t)3 * D * 4) : nullptr;
-    auto once = [&]() { return launch_qkv_attention(dH, dW, dB, dQ, dX, dL, dL ? dL + D : nullptr, dO, B, L, H, D, extras, s); };
+    auto once = [&]() { return launch_qkv_attention(dH, dW, dB, dQ, dX, dL, dL ? dL + D : nullptr, dO, B, L, H, D, extras, s, dF); };
     DEV_HIP(dev, once());
     DEV_HIP(dev, hipStreamSynchronize(s));
     dev.download(out_host, dO, (M + 8) * D * 2);
+    if (out_frag_host) dev.download(out_frag_host, dF - guard, (pe + 2 * guard) * 2);
     DEV_HIP(dev, time_launches(s, iters, once, ms_out));
     return dev.status();
+}
+
+extern "C" {
+
+int dd_dev_qkv_attention_rows(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
+                              const float* xres_host, const float* ln, unsigned short* out_host, int iters, void* stream, float* ms_out) {
+    return qkv_attention_run(c, B, L, H, extras, h_host, wqkv, bqkv, xres_host, ln, out_host, nullptr, iters, stream, ms_out);
+}
+
+int dd_dev_qkv_attention_frag(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
+                              const float* xres_host, const float* ln, unsigned short* out_host, unsigned short* out_frag_host, int iters,
+                              void* stream, float* ms_out) {
+    if (!out_frag_host) return DD_ERR_INVALID;
+    return qkv_attention_run(c, B, L, H, extras, h_host, wqkv, bqkv, xres_host, ln, out_host, out_frag_host, iters, stream, ms_out);
 }
 
 int dd_dev_v_identity(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,

@@ -222,6 +222,10 @@ struct MlpCfg {
 template <int D, bool LNIN, bool PARTIAL, bool PROJ, bool SKIP = false, bool QKV = false, bool TAP = false>
 __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, const int tile_idx, const int c0, int c1, const int slab) {
     using C = MlpCfg<D>;
+    // the fragment-order hand-offs of the patch rows (ao_frag, x_in_frag / x_out_frag, out_frag / skip_frag) exist in the product's instantiations only:
+    // main tiles of the proj-fused launches at D = 512; everywhere else the row-major offsets stay compile-time constants
+    constexpr bool FRAG = PROJ && !PARTIAL && !QKV && D == 512;
+    constexpr bool FRAGX = FRAG && !TAP;          // (early-exit models read x between blocks: row-major throughout)
     static_assert(!PROJ || (LNIN && C::NT % 4 == 0), "proj fusion: the LayerNorm-in kernel, D % 128 == 0");
     static_assert(!SKIP || (PROJ && !PARTIAL), "skip fusion rides on the proj-fused main tiles");
     static_assert(!QKV || (PROJ && !PARTIAL), "qkv fusion rides on the proj-fused main tiles");
@@ -334,7 +338,16 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
         // Main tiles keep x in the accumulators (the MLP output is added on top: no second read of x); hidden-split
         // tiles zero them after the normalisation (x is added once, by the reduce kernel).
         // This code runs at one wave per SIMD with nothing to hide latency behind: its length is its cost.
+        // (x_in_frag, main tiles: the rows as the previous tail's epilogue left them -- [32-row group][tile t][quad g][lane] x 16 bytes, the same
+        // (t, g, lane) -> column map, one load instruction = 1 KB contiguous; xts / xgs = floats between tiles / quads, wave-uniform)
         const float* xr = a.xres + row_pro * D + 4 * h;
+        int xts = 32, xgs = 8;
+        if constexpr (FRAGX) {
+            const bool xfr = a.x_in_frag != nullptr;
+            const int grp = row_ok_pro ? tile_idx * 4 + wave : 0;
+            const float* const xfp = a.x_in_frag + ((long long)grp * (C::NT * 4) * 64 + lane) * 4;
+            xr = xfr ? xfp : xr; xts = xfr ? 1024 : 32; xgs = xfr ? 256 : 8;
+        }
         f32x4 s4 = {0.f, 0.f, 0.f, 0.f}, q4 = {0.f, 0.f, 0.f, 0.f};
         float cshift = 0.f;      // shift of the one-pass statistics: the lane's first element (ln_stats_shifted)
         // LA tiles of loads in flight, no more: sched_barrier keeps hipcc from hoisting all 64 loads (256 registers)
@@ -344,21 +357,30 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
         const float* lbp = vecs + 5 * D + 4 * h;     // (PROJ) attn.proj bias
         if constexpr (PROJ) {
             // attention output rows of this wave as B fragments (natural k order; they live in the registers the
-            // normalised rows take over afterwards)
-            const bf16_t* ar = a.ao + row_pro * D + 8 * h;
+            // normalised rows take over afterwards): row-major rows, or (ao_frag, main tiles) the fragments as the attention
+            // launch stored them -- [32-row group][k-step][lane] x 16 bytes, one load instruction = 1 KB contiguous
+            if (FRAG && a.ao_frag) {          // (a kernel argument: a scalar branch, constant offsets on either side)
+                const int grp = row_ok_pro ? tile_idx * 4 + wave : 0;      // whole groups are in range or not: tok_n % 32 == 0
+                const bf16_t* af = a.ao_frag + ((long long)grp * C::KS * 64 + lane) * 8;
 #pragma unroll
-            for (int ks = 0; ks < C::KS; ++ks) xf[ks] = *reinterpret_cast<const bf16x8*>(ar + 16 * ks);
-            __syncthreads();                          // the bias vector is in LDS (and the first Wproj blocks have landed)
+                for (int ks = 0; ks < C::KS; ++ks) xf[ks] = *reinterpret_cast<const bf16x8*>(af + 512 * ks);
+            } else {
+                const bf16_t* ar = a.ao + row_pro * D + 8 * h;
+#pragma unroll
+                for (int ks = 0; ks < C::KS; ++ks) xf[ks] = *reinterpret_cast<const bf16x8*>(ar + 16 * ks);
+            }
         }
+        // the first LA - 1 tiles of x are requested in front of the barrier that drains the attention rows: one round trip, not two
 #pragma unroll
         for (int t = 0; t < LA - 1; ++t)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) xq[t][g] = *reinterpret_cast<const f32x4*>(xr + 32 * t + 8 * g);
+            for (int g = 0; g < 4; ++g) xq[t][g] = *reinterpret_cast<const f32x4*>(xr + (FRAGX ? xts * t + xgs * g : 32 * t + 8 * g));
+        if constexpr (PROJ) __syncthreads();          // the bias vector is in LDS (and the first Wproj blocks have landed)
 #pragma unroll
         for (int t = 0; t < C::NT; ++t) {
             if (t + LA - 1 < C::NT) {
 #pragma unroll
-                for (int g = 0; g < 4; ++g) xq[(t + LA - 1) % LA][g] = *reinterpret_cast<const f32x4*>(xr + 32 * (t + LA - 1) + 8 * g);
+                for (int g = 0; g < 4; ++g) xq[(t + LA - 1) % LA][g] = *reinterpret_cast<const f32x4*>(xr + (FRAGX ? xts * (t + LA - 1) + xgs * g : 32 * (t + LA - 1) + 8 * g));
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -606,9 +628,18 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
     const bf16_t* sr = nullptr;        // this lane's long-skip row (kept across the first skip phases for the second half's loads:
     if constexpr (SKIP) {              // no address arithmetic -- compiler VALU code -- between the hand-placed MFMAs)
         bool ok_s;
-        sr = a.skip + row_of(ok_s) * D + 8 * half_of();
+        const long long row_s = row_of(ok_s);
+        if (FRAG && a.skip_frag) {     // the in-block tail's bf16 copy in fragment order (out_frag): [32-row group][k-step][lane] x 16 bytes, 1 KB per load instruction
+            unsigned l = (unsigned)threadIdx.x;
+            asm volatile("" : "+v"(l));
+            sr = a.skip_frag + ((long long)(ok_s ? tile_idx * 4 + (int)(l >> 6) : 0) * C::F * 64 + (l & 63)) * 8;
 #pragma unroll
-        for (int ks = 0; ks < C::F / 2; ++ks) sk[ks] = *reinterpret_cast<const bf16x8*>(sr + 16 * ks);
+            for (int ks = 0; ks < C::F / 2; ++ks) sk[ks] = *reinterpret_cast<const bf16x8*>(sr + 512 * ks);
+        } else {
+            sr = a.skip + row_s * D + 8 * half_of();
+#pragma unroll
+            for (int ks = 0; ks < C::F / 2; ++ks) sk[ks] = *reinterpret_cast<const bf16x8*>(sr + 16 * ks);
+        }
     }
     // tail: GEMM2 of the last chunk; its block W2(c1-1) (slot 3) was confirmed at the last M barrier and the first PD
     // fragments are already in flight
@@ -701,8 +732,13 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
                     if constexpr (p == C::NT) {       // second half of the long-skip rows -> the registers the y fragments have left
                         asm volatile("" ::: "memory");
                         __builtin_amdgcn_sched_barrier(0);
+                        if (FRAG && a.skip_frag) {
 #pragma unroll
-                        for (int ks = 0; ks < H2; ++ks) xf[ks] = *reinterpret_cast<const bf16x8*>(sr + 16 * (H2 + ks));
+                            for (int ks = 0; ks < H2; ++ks) xf[ks] = *reinterpret_cast<const bf16x8*>(sr + 512 * (H2 + ks));
+                        } else {
+#pragma unroll
+                            for (int ks = 0; ks < H2; ++ks) xf[ks] = *reinterpret_cast<const bf16x8*>(sr + 16 * (H2 + ks));
+                        }
                         __builtin_amdgcn_sched_barrier(0);
                         asm volatile("" ::: "memory");
                     }
@@ -753,6 +789,22 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
         // QKV: every wave runs the phases below, so rows past the end of a ragged tile store into the dump area instead of leaving
         float* xrow = (!QKV || row_ok) ? a.xres + row * D + 4 * he : reinterpret_cast<float*>(reinterpret_cast<char*>(a.qkv_dump) + 8192) + 4 * he;
         bf16_t* orow = (!QKV || row_ok) ? a.out + row * a.ldo + 8 * he : reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(a.qkv_dump) + 12288) + 8 * he;
+        // fragment-order hand-offs of the patch rows (pure re-addressing of the same registers; a wave's store instruction = 1 KB contiguous):
+        //   x_out_frag: the fp32 rows for the next tail's prologue, [32-row group][tile t][quad g][lane] x 16 bytes;
+        //   out_frag:   the bf16 copy for the SKIP phases of the out-block's tail, [32-row group][k-step 2 t + gp / 2][lane] x 16 bytes (natural k order)
+        int xts = 32, xgs = 8;
+        long long ostride = 16;
+        if constexpr (FRAG) {
+            unsigned l = (unsigned)threadIdx.x;
+            asm volatile("" : "+v"(l));
+            const long long grp = (long long)tile_idx * 4 + (l >> 6);
+            // (selects, not branches: a branch here made hipcc spill an accumulator tile around it)
+            const bool xfr = FRAGX && a.x_out_frag != nullptr, ofr = !SKIP && a.out_frag != nullptr;
+            float* const xfp = a.x_out_frag + (grp * (C::NT * 4) * 64 + (l & 63)) * 4;
+            bf16_t* const ofp = a.out_frag + (grp * C::F * 64 + (l & 63)) * 8;
+            xrow = xfr ? xfp : xrow; xts = xfr ? 1024 : 32; xgs = xfr ? 256 : 8;
+            orow = ofr ? ofp : orow; ostride = ofr ? 512 : 16;
+        }
         f32x4 xl[2][4];   // !LNIN: residual quads of tile t, loaded one tile ahead of the stores (vmcnt retires in order)
         if constexpr (!LNIN) {
 #pragma unroll
@@ -775,21 +827,21 @@ __device__ __forceinline__ void mlp_body(const MlpFusedArgs& a, char* smem, cons
                 f32x4 q = {yt[4 * g], yt[4 * g + 1], yt[4 * g + 2], yt[4 * g + 3]};
                 if constexpr (!SKIP) q += *reinterpret_cast<const f32x4*>(lb2 + 32 * t + 8 * g);
                 if constexpr (!LNIN) q = xl[t & 1][g] + q;
-                *reinterpret_cast<f32x4*>(xrow + 32 * t + 8 * g) = q;
+                *reinterpret_cast<f32x4*>(xrow + (FRAGX ? xts * t + xgs * g : 32 * t + 8 * g)) = q;
                 v[g] = uint2{cvt_pk_bf16(q[0], q[1]), cvt_pk_bf16(q[2], q[3])};
                 if (t == 0 && g == 0) cshift = q[0];
                 const f32x4 dq = q - cshift;
                 s4 += dq;
                 q4 += dq * dq;
             }
-            if (!SKIP && a.out) {
+            if (!SKIP && (a.out || (FRAG && a.out_frag))) {
                 // bf16 copy as 16-byte row segments: v_permlane32_swap joins the two lane halves (see gemm.hip)
 #pragma unroll
                 for (int gp = 0; gp < 4; gp += 2) {
                     const auto s0 = __builtin_amdgcn_permlane32_swap(v[gp].x, v[gp + 1].x, false, false);
                     const auto s1 = __builtin_amdgcn_permlane32_swap(v[gp].y, v[gp + 1].y, false, false);
                     const uint4 o = {s0[0], s1[0], s0[1], s1[1]};
-                    *reinterpret_cast<uint4*>(orow + 32 * t + 8 * gp) = o;
+                    *reinterpret_cast<uint4*>(orow + (FRAG && !SKIP ? (2 * t + gp / 2) * ostride : (long long)(32 * t + 8 * gp))) = o;
                 }
             }
             acc_pin(Y[t]);                       // the copy dies here: the LayerNorm pass below re-reads the accumulators instead of a spill slot
@@ -1215,6 +1267,13 @@ hipError_t launch_d(const MlpFusedArgs& a, hipStream_t s) {
     if (a.nqkv > 0 && a.nproj <= 0) return hipErrorInvalidValue;
     if (a.y_tap && (a.nskip <= 0 || a.nqkv > 0)) return hipErrorInvalidValue;      // (the tap rides on the SKIP launches of early-exit models)
     if (a.ln_out_frag && (!a.ln_out || a.nqkv > 0 || a.tok_n % 32)) return hipErrorInvalidValue;   // (whole 32-row groups of patch rows per wave)
+    // the fragment-order hand-offs: the proj-fused launches at D = 512, whole 32-row groups of patch rows per wave, no qkv phases; the residual rows not
+    // where a y_tap exists (early-exit models keep x row-major); out_frag from the launches that write the bf16 copy, skip_frag into the SKIP phases
+    if (a.ao_frag || a.x_in_frag || a.x_out_frag || a.out_frag || a.skip_frag) {
+        if (D != 512 || a.nproj <= 0 || a.nqkv > 0 || a.tok_n % 32) return hipErrorInvalidValue;
+        if ((a.x_in_frag || a.x_out_frag) && a.y_tap) return hipErrorInvalidValue;
+        if ((a.out_frag && a.nskip > 0) || (a.skip_frag && a.nskip <= 0)) return hipErrorInvalidValue;
+    }
     if (a.nproj > 0) {
         if constexpr (D % 128 == 0) {
             if (!a.ln_in_g || !a.ao || !a.bproj || a.nproj != D / 32) return hipErrorInvalidValue;

@@ -58,6 +58,24 @@ int dd_dev_block_tail(dd_ctx* ctx, int B, int n_patches, int extras, int D, int 
                       unsigned short* frag_host, float* tap_host, unsigned short* qkv_host, float* slab_host, int slab_rows, int* plan_out,
                       int iters, void* stream, float* ms_out);
 
+/* dd_dev_block_tail with the patch rows' hand-offs in MFMA fragment order (embed_dim 512 with the projection in front: MlpFusedArgs::ao_frag,
+ * skip_frag, x_in_frag, out_frag, x_out_frag); each of the five is optional, all NULL is dd_dev_block_tail.  A fragment buffer holds the
+ * B n_patches patch rows (no extra-token rows, no padding), group = patch row / 32 counted over all images:
+ *   bf16 buffers: element ((group (D / 16) + ks) 64 + lane) 8 + j = column 16 ks + 8 (lane >> 5) + j of patch row 32 group + (lane & 31);
+ *   fp32 buffers: element (((group (D / 32) + t) 4 + g) 64 + lane) 4 + e = column 32 t + 8 g + 4 (lane >> 5) + e of that row.
+ * ao_frag_host / skip_frag_host (bf16 bits) / xin_frag_host (fp32) [B n_patches D]: the main tiles read the patch rows of ao / skip / x from
+ * these; the patch rows of the row-major device copies of ao_host / skip_host / xres_host then hold `poison` bytes (the extra-token rows still
+ * come from them).  out_frag_host (bf16 bits, needs out_host) / xout_frag_host (fp32) [(B n_patches + 16) D]: the bf16 copy / the updated
+ * residual rows of the patch rows go here instead of out_host / xres_host, whose patch rows then keep the bytes they had; both are filled with
+ * 0xFF bytes before the launch and come back WHOLE, the data behind 8 canary rows and in front of 8 more. */
+int dd_dev_block_tail_frag(dd_ctx* ctx, int B, int n_patches, int extras, int D, int hidden, int last, int poison, const float* h_host,
+                           const float* w1, const float* b1, const float* w2, const float* b2, const float* ln_in, const float* ao_host,
+                           const float* wproj, const float* bproj, const float* ln_out, const float* skip_host, const float* wskip,
+                           const float* bskip, const float* wqkv, float* xres_host, unsigned short* out_host, unsigned short* ln_out_host,
+                           unsigned short* frag_host, float* tap_host, unsigned short* qkv_host, float* slab_host, int slab_rows, int* plan_out,
+                           int iters, void* stream, float* ms_out, const unsigned short* ao_frag_host, const unsigned short* skip_frag_host,
+                           const float* xin_frag_host, unsigned short* out_frag_host, float* xout_frag_host);
+
 /* Development harness for the attention launch that computes attn.qkv itself (attention.hip qkv_attention_kernel; bf16, H heads
  * of 64 with D = 64 H = 512, 768 or 1024, L = 256 patches + `extras` = 1 or 2 leading extra tokens -- qkv_attention_supported; anything else
  * is DD_ERR_UNSUPPORTED): out = softmax(q k^T / 8) v per (image, head) with q, k, v = split(h . wqkv^T + bqkv), from host arrays
@@ -74,6 +92,13 @@ int dd_dev_qkv_attention(dd_ctx* ctx, int B, int L, int H, int extras, const flo
  * A refused shape is DD_ERR_UNSUPPORTED; nothing is launched and out_host is not written. */
 int dd_dev_qkv_attention_rows(dd_ctx* ctx, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
                               const float* xres_host, const float* ln, unsigned short* out_host, int iters, void* stream, float* ms_out);
+
+/* dd_dev_qkv_attention_rows with the patch rows' output in fragment order (QkvAttnArgs::out_frag, the layout of the bf16 buffers of
+ * dd_dev_block_tail_frag with n_patches = 256): out_frag_host [(B 256 + 16) D] of bf16 bits is filled with 0xFF bytes before the launch and comes
+ * back WHOLE, the data behind 8 canary rows and in front of 8 more; out_host [B L + 8, D] then receives the extra-token rows only. */
+int dd_dev_qkv_attention_frag(dd_ctx* ctx, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
+                              const float* xres_host, const float* ln, unsigned short* out_host, unsigned short* out_frag_host, int iters,
+                              void* stream, float* ms_out);
 
 /* Development harness for the identity-attention launch (attention.hip v_identity_kernel; perturbed-attention guidance): the companion of the
  * launch above for images whose attention map is the identity, out = v = h . Wv^T + bv with Wv / bv the last third of wqkv / bqkv.  Operands as
@@ -178,7 +203,7 @@ int dd_dev_vae_gather(dd_ctx* ctx, int kind, int precision, int B, int H, int W,
                       size_t dst_bytes, void* stream);
 
 /* Kernel-variant switches for same-process A/B runs (tools/mlp_check.py, tools/all_configs.py).  They act on models
- * FINALIZED after the call (the first three) or on launches made after it; the product never sets them and the library
+ * FINALIZED after the call (the kernel paths a model takes, the DD_DEV_NO_FRAG_* hand-offs among them) or on launches made after it; the product never sets them and the library
  * reads no environment variable. */
 #define DD_DEV_NO_FUSED_MLP 1u      /* keep the fc1 / fc2 GEMM pair + LayerNorm launches instead of the fused block tail */
 #define DD_DEV_NO_FUSED_PROJ 2u     /* keep attn.proj as its own GEMM */
@@ -195,6 +220,9 @@ int dd_dev_vae_gather(dd_ctx* ctx, int kind, int precision, int B, int H, int W,
 #define DD_DEV_NO_SPLITK 8192u       /* small-batch GEMM-path models: keep skip_linear / attn.proj / mlp.fc2 as whole-K GEMMs + LayerNorm launches */
 #define DD_DEV_NO_ROWLIN_SKIP 16384u /* embed_dim 768: keep the out-blocks' skip_linear as a GEMM + LayerNorm launch pair */
 #define DD_DEV_NO_SPLIT_HEADS 32768u /* early-exit heads of the bf16 engine: keep the exact-fp32 decoder product (default: the split-bf16 product at embed_dim 256 / 512) */
+#define DD_DEV_NO_FRAG_AO 65536u     /* embed_dim 512: keep the attention output of the patch rows row-major between the attention launch and the block tail */
+#define DD_DEV_NO_FRAG_SKIP 131072u  /* embed_dim 512: keep the long-skip copy of the patch rows row-major between the in-block and the out-block tails */
+#define DD_DEV_NO_FRAG_X 262144u     /* embed_dim 512: keep the fp32 residual patch rows row-major between consecutive block tails */
 #define DD_DEV_FORCE_CHAINS 512u    /* dd_sample: two half-batch chains for ANY even batch (tests at small batches) */
 int dd_dev_set_flags(dd_ctx* ctx, unsigned flags);
 

@@ -22,9 +22,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from kernel_support import PREC_BF16, PREC_FP32, bf16, from_bf16_bits, gate
+
 gpu = pytest.mark.gpu
 
-PREC_BF16, PREC_FP32 = 0, 1
 PREC_NAME = {PREC_BF16: "bf16", PREC_FP32: "fp32"}
 BF16_UNIT = 2.0 ** -8          # bf16 P in the P . V product + the bf16 output rounding, relative to A
 BF16_MARGIN = 1.75             # the two roundings at the lower end of a binade (at most 2), v_exp_f32, accumulation order
@@ -33,16 +34,6 @@ FP32_FLOOR = 2.0 ** -20
 
 
 # ---------------------------------------------------------------------------------------------------------------- host helpers
-def bf16(a):
-    """fp32 -> bf16 (round to nearest even) -> fp32, as host_f2bf"""
-    u = np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)
-    return (((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint32) << 16).view(np.float32)
-
-
-def from_bf16_bits(b):
-    return (np.ascontiguousarray(b, np.uint16).astype(np.uint32) << 16).view(np.float32)
-
-
 def operands(B, H, L, sigma, seed, prec, big_keys=()):
     """q, k [B, H, L, 64] of standard deviation sigma (scores q . k / 8 of standard deviation sigma^2: 1.5 spreads them over a few units, 4 makes
     the softmax nearly one-hot), v of 1; big_keys: key rows made 3 x larger.  bf16 mode: rounded, so the kernel's operands are exact."""
@@ -94,18 +85,6 @@ def tolerance(prec, q, k, v, want, A):
         return BF16_MARGIN * BF16_UNIT * A, None
     e32 = float((np.abs(emulate_fp32(q, k, v).astype(np.float64) - want) / A).max())
     return max(FP32_MARGIN * e32, FP32_FLOOR) * A, e32
-
-
-def gate(got, want, tol, what):
-    """elementwise |got - want| <= tol; NaN fails.  Returns the largest error / bound ratio."""
-    got = np.asarray(got, np.float64)
-    err = np.abs(got - want)
-    bad = ~(err <= tol)
-    if bad.any():
-        i = tuple(np.argwhere(bad)[0])
-        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.size} elements out of bound; first at {i}: got {got[i]!r}, want {want[i]!r}, "
-                             f"bound {tol[i]!r}; largest error / bound {np.nanmax(err / tol):.3f}")
-    return float((err / tol).max())
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU call

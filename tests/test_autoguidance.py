@@ -19,6 +19,7 @@ from duodiff_amd import _lib as L
 from duodiff_amd.config import ModelParams, load_config
 from duodiff_amd.engine import Autoguidance
 from duodiff_amd.weights import synthetic_state_dict
+from loop_support import cli_argv, engine_pair, eps_rms_bound, side_stream, uvit
 
 gpu = pytest.mark.gpu
 
@@ -27,19 +28,14 @@ F32 = np.float32
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
-def _argv(config, *extra):
-    return ["--checkpoint_path", "/nonexistent.pth", "--batch_size", "2", "--parametrization", "predict_noise",
-            "--output_folder", "/tmp/unused", "--config_path", str(config), *extra]
-
-
 def test_cli_autoguidance_options_and_defaults():
     from duodiff_amd import sampler
-    a = sampler.get_args(_argv(CONFIGS / "uvit_celeba_3.yaml"))
+    a = sampler.get_args(cli_argv(CONFIGS / "uvit_celeba_3.yaml"))
     assert a.autoguidance_scale is None and a.guide_config_path is None and a.guide_checkpoint_path is None
-    a = sampler.get_args(_argv(CONFIGS / "uvit_celeba_3.yaml", "--autoguidance_scale", "1.5", "--guide_config_path", "g.yaml",
+    a = sampler.get_args(cli_argv(CONFIGS / "uvit_celeba_3.yaml", "--autoguidance_scale", "1.5", "--guide_config_path", "g.yaml",
                                "--guide_checkpoint_path", "g.pth"))
     assert a.autoguidance_scale == pytest.approx(1.5) and a.guide_config_path == "g.yaml" and a.guide_checkpoint_path == "g.pth"
-    a = sampler.get_args(_argv(CONFIGS / "uvit_celeba_3.yaml", "--autoguidance_scale", "0"))
+    a = sampler.get_args(cli_argv(CONFIGS / "uvit_celeba_3.yaml", "--autoguidance_scale", "0"))
     assert a.autoguidance_scale == 0.0 and a.autoguidance_scale is not None       # 0 selects the autoguided path too
     assert a.cfg_scale is None
 
@@ -63,7 +59,7 @@ _LATE = ["--checkpoint_path_late", "/nonexistent.pth", "--config_path_late"]
 def test_cli_rejects_invalid_autoguidance_before_any_gpu_work(tmp_path, config, extra, match):
     """main() validates the options against the YAMLs before it builds a model: no GPU is touched and no checkpoint is opened."""
     from duodiff_amd import sampler
-    argv = _argv(CONFIGS / config, *extra)
+    argv = cli_argv(CONFIGS / config, *extra)
     argv[argv.index("--output_folder") + 1] = str(tmp_path / "out")
     with pytest.raises(ValueError, match=match):
         sampler.main(argv)
@@ -102,24 +98,9 @@ TINY_G = dict(TINY, depth=1)                                   # the guide: 1 bl
 TINY_M = dict(TINY, depth=3, embed_dim=128, num_heads=2)       # the main model: 3 blocks, embed_dim 128
 
 
-def eps_rms_bound(depth):
-    """test_gpu_parity's error model of the bf16 engine (rms(eps - oracle) / sigma), margin 1.5"""
-    return 1.5 * 2.0 ** -9 / np.sqrt(3.0) * np.sqrt(6.0 * depth)
-
-
-def _uvit(cfg, seed, precision, max_batch):
-    from duodiff_amd.uvit import UViT
-    mp = ModelParams.from_dict(cfg)
-    m = UViT(**mp.as_dict(), precision=precision, max_batch=max_batch)
-    m.load_state_dict(synthetic_state_dict(mp, seed))
-    return m.eval().to("cuda"), mp
-
-
 def _pair(cfg_g, cfg_m, seeds, max_batch, precision="bf16"):
     """(guide, main) engine models"""
-    g, _ = _uvit(cfg_g, seeds[0], precision, max_batch)
-    m, _ = _uvit(cfg_m, seeds[1], precision, max_batch)
-    return g.engine_model(max_batch), m.engine_model(max_batch)
+    return engine_pair(cfg_g, cfg_m, seeds, max_batch, precision)[:2]
 
 
 def _tiny_pair(seeds=(41, 42), max_batch=12, precision="bf16"):
@@ -136,12 +117,6 @@ def _imagenet256_pair(max_batch=32):
 
 def _x0(B, Cc, S, seed):
     return torch.randn(B, Cc, S, S, generator=torch.Generator().manual_seed(seed)).cuda()
-
-
-def _stream():
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    return s
 
 
 class _flags:
@@ -251,7 +226,7 @@ def test_scale_zero_equals_the_unguided_loop(case, kind):
     else:
         B, S, n, flags = 128, 64, 3, 0
         eg, em = _celeba_pair(B)
-    ctx, x0, stream = em.ctx, _x0(B, 3, S, 7), _stream()
+    ctx, x0, stream = em.ctx, _x0(B, 3, S, 7), side_stream()
     with _flags(ctx, flags):
         want = _run(kind, ctx, em, None, x0, stream, switch=0, n=n, seed=21)
         chains = ctx.lib.dd_dev_last_sample_chains(ctx.handle)
@@ -270,7 +245,7 @@ def test_the_guides_identity_decides_the_launch_not_its_weights(kind):
     B = 4
     _, em = _tiny_pair(max_batch=B)
     _, twin = _tiny_pair(max_batch=B)                # the same seeds: the same weights, another dd_model
-    ctx, x0, stream = em.ctx, _x0(B, 3, 8, 9), _stream()
+    ctx, x0, stream = em.ctx, _x0(B, 3, 8, 9), side_stream()
     want = _run(kind, ctx, em, None, x0, stream, switch=0, seed=22)
     n0 = ctx.lib.dd_dev_graph_captures(ctx.handle)
     same = _run(kind, ctx, em, None, x0, stream, switch=0, seed=22, guidance=Autoguidance(em, 1.7))
@@ -290,7 +265,7 @@ def test_the_duodiff_call():
     from duodiff_amd.engine import sample_loop
     B, s = 4, 1.7
     eg, em = _tiny_pair(max_batch=B)
-    ctx, x0, stream = em.ctx, _x0(B, 3, 8, 10), _stream()
+    ctx, x0, stream = em.ctx, _x0(B, 3, 8, 10), side_stream()
     out = {}
     with torch.cuda.stream(stream):
         for name, ag in (("unguided", None), ("auto", Autoguidance(eg, s))):
@@ -324,7 +299,7 @@ def test_autoguided_loops_equal_manual_steps(kind):
     from duodiff_amd.engine import sample_affine_loop, sample_multistep_loop
     B, s, n, sw = 4, 1.7, 8, 3
     eg, em = _tiny_pair(max_batch=B)
-    ctx, x0, stream = em.ctx, _x0(B, 3, 8, 11), _stream()
+    ctx, x0, stream = em.ctx, _x0(B, 3, 8, 11), side_stream()
     ag = Autoguidance(eg, s)
     loops = [_run(kind, ctx, eg, em, x0, stream, switch=sw, n=n, noise="none", use_graph=ug, guidance=ag) for ug in (True, False)]
     rows = None if kind == "ddpm" else _affine_rows(n) if kind == "affine" else _ms_rows(n)
@@ -380,7 +355,7 @@ def test_autoguided_two_chains_equal_one_chain(case):
         B, S, Cc, n, sw, force = 32, 32, 4, 3, 1, 0
         eg, em = _imagenet256_pair(B)
         y = torch.randint(0, 1000, (B,), generator=torch.Generator().manual_seed(12)).cuda()
-    ctx, x0, stream = em.ctx, _x0(B, Cc, S, 12), _stream()
+    ctx, x0, stream = em.ctx, _x0(B, Cc, S, 12), side_stream()
     outs = {}
     try:
         for name, flags in (("chained", force), ("single", L.DD_DEV_NO_CHAINS)):
@@ -400,12 +375,12 @@ def test_no_stale_graph():
     autoguided and unguided calls alternated on one (class-conditional) pair each reproduce their own first result."""
     B = 4
     cfg_g, cfg_m = dict(TINY_G, num_classes=11), dict(TINY_M, num_classes=11)
-    x0, stream = _x0(B, 3, 8, 13), _stream()
+    x0, stream = _x0(B, 3, 8, 13), side_stream()
     y = torch.randint(0, 10, (B,), generator=torch.Generator().manual_seed(14)).cuda()
 
     def models():
         eg, em = _pair(cfg_g, cfg_m, (41, 42), 2 * B)
-        g2, _ = _uvit(cfg_g, 43, "bf16", 2 * B)
+        g2, _ = uvit(cfg_g, 43, "bf16", 2 * B)
         return eg, em, g2.engine_model(2 * B)
 
     def run(ms, what):
@@ -444,7 +419,7 @@ def test_no_stale_graph():
 def test_autoguided_loop_reads_no_stale_workspace_bytes():
     """Both chains' workspaces of both models poisoned (NaN bytes) in front of the first autoguided dd_sample == fresh models."""
     B = 6
-    x0, stream = _x0(B, 3, 8, 15), _stream()
+    x0, stream = _x0(B, 3, 8, 15), side_stream()
     outs = []
     for poison in (False, True):
         eg, em = _tiny_pair(seeds=(71, 72), max_batch=B)
@@ -469,7 +444,7 @@ def test_invalid_autoguided_calls_are_rejected_before_anything_is_enqueued():
     B = 4
     eg, em = _tiny_pair(max_batch=B)
     ctx, lib = em.ctx, em.ctx.lib
-    mk = lambda cfg, seed, mb=B: _uvit(cfg, seed, "bf16", mb)[0].engine_model(mb)
+    mk = lambda cfg, seed, mb=B: uvit(cfg, seed, "bf16", mb)[0].engine_model(mb)
     g_img, g_patch, g_chan = mk(dict(TINY_G, img_size=16), 81), mk(dict(TINY_G, patch_size=4), 82), mk(dict(TINY_G, in_chans=4), 83)
     g_small, m_small = mk(TINY_G, 84, B - 1), mk(TINY_M, 85, B - 1)
     g_cond, m_cond = mk(dict(TINY_G, num_classes=11), 86), mk(dict(TINY_M, num_classes=11), 87)
@@ -485,7 +460,7 @@ def test_invalid_autoguided_calls_are_rejected_before_anything_is_enqueued():
     for k, v in synthetic_state_dict(ModelParams.from_dict(TINY_G), 90).items():
         g_other.set_param(k, v)
     g_other.finalize("bf16")
-    x0, stream = _x0(B, 3, 8, 17), _stream()
+    x0, stream = _x0(B, 3, 8, 17), side_stream()
     y = torch.randint(0, 10, (B,), generator=torch.Generator().manual_seed(18)).cuda()
     NULLG = object()
     #        first  late   guide    scale          y     message

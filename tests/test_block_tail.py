@@ -13,7 +13,7 @@ pre-activations cover the GELU polynomial, its +-3.8 clamp and both tails.  fc2 
 sigma(4 j + i) with weights +-2^-e -- so that every hidden unit (every chunk, every accumulator slot) is seen through exactly one output element
 and the bound is sharp; one dense-W2 case per mode family keeps the aggregate gates of tests/test_mlp_fused.py.
 
-Gates, all elementwise (gate() of tests/test_gemm_path.py), s = the float64 pre-activation of the exact operands:
+Gates, all elementwise (gate() of tests/kernel_support.py), s = the float64 pre-activation of the exact operands:
   * hidden activation   Eg = ulp_bf16(gelu(s)) + GELU_POLY + GELU_SLOPE FP32_REL (|h2| |W1|^T + |b1|)
   * y (xres; y_tap)     |got - ref| <= Eg |W2|^T + FP32_REL (|gelu(s)| |W2|^T + |b2| + |x1|)        (the reference leaves the activation unrounded)
   * bf16 copy           bit-equal to bf16() of the fp32 rows that came back
@@ -39,91 +39,14 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from duodiff_amd._lib import DD_ERR_UNSUPPORTED
+from kernel_support import (FP32_REL, GELU_POLY, GELU_SLOPE, NAN16, NAN32, P, bf16, bf16_bits, from_bf16_bits, gate, gelu_exact, ln_ref_and_tol,
+                            round_up, to_frag, unfrag, untouched, ulp_bf16)
 from oracle.uvit_oracle import layer_norm
 
 gpu = pytest.mark.gpu
 
-FP32_REL = 2.0 ** -16          # fp32 accumulation of bf16 products (tests/test_gemm_path.py)
-GELU_POLY = 2.41e-4            # |polynomial - exact GELU| for |v| <= 16 (mlp_fused.hip: "GELU abs error <= 2.4e-4, same coefficients as the GEMM epilogue")
-GELU_SLOPE = 1.13              # max |d gelu / dv|
-NAN32, NAN16 = 0xFFFFFFFF, 0xFFFF
-DD_ERR_UNSUPPORTED = -6       # include/duodiff.h
 REPO = Path(__file__).resolve().parents[1]
-
-
-# ---------------------------------------------------------------------------------------------------------------- host helpers (tests/test_gemm_path.py)
-def bf16(a):
-    """fp32 -> bf16 (round to nearest even) -> fp32, as host_f2bf"""
-    u = np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)
-    return (((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint32) << 16).view(np.float32)
-
-
-def bf16_bits(a):
-    return (bf16(a).view(np.uint32) >> 16).astype(np.uint16)
-
-
-def from_bf16_bits(b):
-    return (np.ascontiguousarray(b, np.uint16).astype(np.uint32) << 16).view(np.float32)
-
-
-def ulp_bf16(y):
-    """one bf16 ulp at bf16(y) (0 at 0: the fp32 term covers it)"""
-    yb = np.abs(bf16(np.asarray(y, np.float32))).astype(np.float64)
-    _, e = np.frexp(yb)
-    return np.where(yb == 0, 0.0, np.ldexp(1.0, e - 8))
-
-
-def gelu_exact(v):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(v, np.float64))
-    return (0.5 * t * (1.0 + torch.special.erf(t / np.sqrt(2.0)))).numpy()
-
-
-def gate(got, ref, tol, what):
-    """elementwise |got - ref| <= tol; NaN fails.  Returns the largest error / bound ratio."""
-    got = np.asarray(got, np.float64)
-    if got.size == 0:
-        return 0.0
-    err = np.abs(got - ref)
-    bad = ~(err <= tol)
-    if bad.any():
-        i = tuple(np.argwhere(bad)[0])
-        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.size} elements out of bound; first at {i}: got {got[i]!r}, "
-                             f"ref {ref[i]!r}, bound {tol[i] if np.ndim(tol) else tol!r}")
-    return float((err / np.maximum(tol, 1e-300)).max())
-
-
-def ln_ref_and_tol(x, g, b):
-    """LayerNorm of fp32 rows x (the kernel's own) and the bf16 bound: one ulp + 2^-16 of the rows' scale in units of their spread"""
-    want = layer_norm(x.astype(np.float32), g, b).astype(np.float64)
-    x64 = x.astype(np.float64)
-    rstd = 1.0 / np.sqrt(x64.var(-1, keepdims=True) + 1e-5)
-    scale = np.abs(x64).max(-1, keepdims=True) * rstd
-    return want, ulp_bf16(want) + FP32_REL * (scale * np.abs(g) + np.abs(b)) + 1e-30
-
-
-def unfrag(fr, groups, D):
-    """[32-row group][D / 16 k-steps][64 lanes] x 8 bf16 (MlpFusedArgs::ln_out_frag) -> [groups 32, D] rows"""
-    f = fr[: groups * (D // 16) * 64 * 8].reshape(groups, D // 16, 2, 32, 8)       # [grp][ks][lane >> 5][lane & 31][i]
-    return f.transpose(0, 3, 1, 2, 4).reshape(groups * 32, D)
-
-
-def to_frag(rows_, D, swap_halves=False):
-    """the inverse of unfrag (tests/test_row_kernels.py); swap_halves: the bug of a store that exchanges the two lane halves"""
-    groups = rows_.shape[0] // 32
-    f = rows_.reshape(groups, 32, D // 16, 2, 8).transpose(0, 2, 3, 1, 4)
-    if swap_halves:
-        f = f[:, :, ::-1]
-    return np.ascontiguousarray(f).reshape(-1)
-
-
-def round_up(v, m):
-    return (v + m - 1) // m * m
-
-
-def untouched(a):
-    a = np.ascontiguousarray(a)
-    return bool(np.all(a.view(np.uint8) == 0xFF))
 
 
 # ---------------------------------------------------------------------------------------------------------------- the kernel's GELU polynomial
@@ -239,10 +162,6 @@ def slab_rows_for(o, sw):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the GPU call
-def P(a):
-    return None if a is None else a.ctypes.data
-
-
 def run(o, mode, poison=0xFF):
     """dd_dev_block_tail; every buffer whole.  poison: the byte the padding rows of the operands (xres included) and the slab buffer hold"""
     from duodiff_amd.engine import Context

@@ -3,8 +3,8 @@ copy -> the out-block's skip_linear (out_frag / skip_frag), residual rows from o
 
 All three are pure re-addressing: a kernel moves the same registers to other addresses, so every comparison here is exact equality of bits.
   * kernel level: each launch once row-major (dd_dev_qkv_attention_rows, dd_dev_block_tail) and once in fragment form (dd_dev_qkv_attention_frag,
-    dd_dev_block_tail_frag) on the same seeded operands; the fragment buffers are un-permuted with the index maps below, which are written from
-    the layout definitions alone; the canary rows around every fragment output and every row a launch must leave alone keep their bytes.
+    dd_dev_block_tail_frag) on the same seeded operands; the fragment buffers are un-permuted with the index maps of tests/kernel_support.py, which are
+    written from the layout definitions alone; the canary rows around every fragment output and every row a launch must leave alone keep their bytes.
   * model level: a depth-3 width-512 model (in-block: row-major -> fragment, mid block: fragment -> fragment with the skip read, out block:
     fragment -> row-major) with each stage switched off by its development flag, in one chain and in two.
 """
@@ -14,9 +14,11 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_support
 from duodiff_amd import _lib as L
-from test_autoguidance import _flags, _run, _stream, _uvit, _x0
-from test_block_tail import to_frag, unfrag
+from kernel_support import P, bf16, bf16_bits, frag16_index, frag32_index, round_up, to_frag, unfrag
+from loop_support import side_stream, uvit
+from test_autoguidance import _flags, _run, _x0
 
 gpu = pytest.mark.gpu
 
@@ -26,38 +28,17 @@ POISON = 0xFF
 ALL_OFF = L.DD_DEV_NO_FRAG_AO | L.DD_DEV_NO_FRAG_SKIP | L.DD_DEV_NO_FRAG_X
 
 
-# ---------------------------------------------------------------------------------------------------------------- the layouts, from their definitions
-def idx16(rows):
-    """bf16 fragment buffers: [32-row group][D / 16 k-steps][64 lanes] x 8 elements; lane (r, h) of k-step ks holds columns 16 ks + 8 h .. + 7 of
-    row 32 group + r.  Returns the flat element index of (patch row p, column c)."""
-    p, c = np.arange(rows)[:, None], np.arange(D)[None, :]
-    group, r, ks, h, j = p // 32, p % 32, c // 16, (c % 16) // 8, c % 8
-    return ((group * (D // 16) + ks) * 64 + (r + 32 * h)) * 8 + j
-
-
-def idx32(rows):
-    """fp32 fragment buffer: [32-row group][D / 32 tiles t][4 quads g][64 lanes] x 4 elements; lane (r, h) of (t, g) holds columns
-    32 t + 8 g + 4 h .. + 3 of row 32 group + r."""
-    p, c = np.arange(rows)[:, None], np.arange(D)[None, :]
-    group, r, t, g, h, e = p // 32, p % 32, c // 32, (c % 32) // 8, (c % 8) // 4, c % 4
-    return (((group * (D // 32) + t) * 4 + g) * 64 + (r + 32 * h)) * 4 + e
-
-
-def permute(rows_, idx):
-    out = np.empty(rows_.size, rows_.dtype)
-    out[idx] = rows_
-    return out
-
-
+# ---------------------------------------------------------------------------------------------------------------- the layouts
 def test_index_maps_are_bijections_and_agree_with_the_norm1_fragment_order():
     rows = 96
-    for idx in (idx16(rows), idx32(rows)):
+    for idx in (frag16_index(rows, D), frag32_index(rows, D)):
         assert np.array_equal(np.sort(idx.reshape(-1)), np.arange(rows * D))
     a = np.arange(rows * D, dtype=np.uint16).reshape(rows, D)
-    assert np.array_equal(permute(a, idx16(rows)), to_frag(a, D))               # MlpFusedArgs::ln_out_frag's order (tests/test_block_tail.py)
-    assert np.array_equal(unfrag(permute(a, idx16(rows)), rows // 32, D), a)
+    f = a.reshape(rows // 32, 32, D // 16, 2, 8).transpose(0, 2, 3, 1, 4).reshape(-1)      # MlpFusedArgs::ln_out_frag: [grp][ks][lane >> 5][lane & 31][i]
+    assert np.array_equal(to_frag(a, D), f)
+    assert np.array_equal(unfrag(f, rows // 32, D), a)
     # one wave instruction (fixed group, k-step or (t, g)) covers 1 KB contiguous
-    i16, i32 = idx16(32), idx32(32)
+    i16, i32 = frag16_index(32, D), frag32_index(32, D)
     assert set((i16[:, 16:32].reshape(-1) * 2) // 1024) == {1} and set((i32[:, 40:48].reshape(-1) * 4) // 1024) == {5}
 
 
@@ -70,37 +51,15 @@ def test_lib_binds_the_fragment_entry_points_and_flags():
 
 
 # ---------------------------------------------------------------------------------------------------------------- helpers
-def P(a):
-    return None if a is None else a.ctypes.data
-
-
-def bits16(a):
-    u = np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)
-    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
-
-
-def bf16f(a):
-    return (bits16(a).astype(np.uint32) << 16).view(np.float32)
-
-
 def all_bytes(a, byte):
     return bool(np.all(np.ascontiguousarray(a).view(np.uint8) == byte))
-
-
-def _ctx():
-    from duodiff_amd.engine import Context
-    return Context.get()
-
-
-def round_up(v, m):
-    return (v + m - 1) // m * m
 
 
 # ---------------------------------------------------------------------------------------------------------------- the attention launch
 @gpu
 @pytest.mark.parametrize("B,E", [(2, 1), (3, 2)])
 def test_attention_output_in_fragment_order(B, E):
-    ctx = _ctx()
+    ctx = kernel_support.ctx()
     Lt, M = N + E, B * (N + E)
     r = np.random.default_rng([B, E, 1])
     h = r.standard_normal((M, D)).astype(np.float32)
@@ -114,7 +73,7 @@ def test_attention_output_in_fragment_order(B, E):
     ctx.check(ctx.lib.dd_dev_qkv_attention_frag(ctx.handle, B, Lt, H, E, P(h), P(w), None, P(xres), P(ln), P(got), P(frag), 0, None, C.byref(C.c_float(0))))
     patch = (np.arange(M) % Lt) >= E
     assert np.isfinite((want[:M].astype(np.uint32) << 16).view(np.float32)).all()
-    assert np.array_equal(frag[8 * D: 8 * D + B * N * D][idx16(B * N)], want[:M][patch]), "patch rows: the fragment buffer un-permuted differs from the row-major launch"
+    assert np.array_equal(unfrag(frag[8 * D:], B * N // 32, D), want[:M][patch]), "patch rows: the fragment buffer un-permuted differs from the row-major launch"
     assert all_bytes(frag[: 8 * D], 0xFF) and all_bytes(frag[8 * D + B * N * D:], 0xFF), "canary rows around out_frag"
     assert np.array_equal(got[:M][~patch], want[:M][~patch]), "extra-token rows still go to the row-major buffer"
     assert all_bytes(got[:M][patch], 0xFF), "the row-major patch rows must not be written"
@@ -128,8 +87,8 @@ class TailOps:
         r = np.random.default_rng([B, E, 2])
         M = self.M
         self.x = r.standard_normal((M, D)).astype(np.float32)
-        self.ao = bf16f(r.standard_normal((M, D)))
-        self.skip = bf16f(r.standard_normal((M, D)))
+        self.ao = bf16(r.standard_normal((M, D)))
+        self.skip = bf16(r.standard_normal((M, D)))
         self.w1 = (0.05 * r.standard_normal((HIDDEN, D))).astype(np.float32)
         self.b1 = r.standard_normal(HIDDEN).astype(np.float32)
         self.w2 = (0.1 * r.standard_normal((D, HIDDEN))).astype(np.float32)
@@ -160,7 +119,7 @@ _REF = {}
 def run_tail(o, role, frags):
     """one block tail: the fused launch + the launches of its extra-token rows.  frags = the hand-offs taken in fragment order (empty: the row-major
     launch through dd_dev_block_tail).  Every buffer comes back whole."""
-    ctx = _ctx()
+    ctx = kernel_support.ctx()
     skp, last, _ = ROLES[role]
     M, B, E = o.M, o.B, o.E
     Mo = round_up(M, 256) + 8
@@ -182,9 +141,9 @@ def run_tail(o, role, frags):
     if not frags:
         ctx.check(ctx.lib.dd_dev_block_tail(*common))
         return res
-    ins = {"ao": permute(bits16(o.ao[o.patch]), idx16(B * N)) if "ao" in frags else None,
-           "skip": permute(bits16(o.skip[o.patch]), idx16(B * N)) if "skip" in frags else None,
-           "xin": permute(o.x[o.patch], idx32(B * N)) if "xin" in frags else None}
+    ins = {"ao": to_frag(bf16_bits(o.ao[o.patch]), D) if "ao" in frags else None,
+           "skip": to_frag(bf16_bits(o.skip[o.patch]), D) if "skip" in frags else None,
+           "xin": to_frag(o.x[o.patch], D, index=frag32_index) if "xin" in frags else None}
     res["out_frag"] = np.zeros(pe + 16 * D, np.uint16) if "out" in frags else None
     res["xout_frag"] = np.zeros(pe + 16 * D, np.float32) if "xout" in frags else None
     ctx.check(ctx.lib.dd_dev_block_tail_frag(*common, P(ins["ao"]), P(ins["skip"]), P(ins["xin"]), P(res["out_frag"]), P(res["xout_frag"])))
@@ -212,7 +171,7 @@ def check_tail(o, role, frags):
     # the residual rows
     if "xout" in frags:
         xf = got["xout_frag"]
-        assert same(xf[8 * D: 8 * D + pe][idx32(o.B * N)], want["xres"][:M][pr]), f"{role} {frags}: x_out_frag un-permuted differs from the row-major rows"
+        assert same(unfrag(xf[8 * D:], o.B * N // 32, D, index=frag32_index), want["xres"][:M][pr]), f"{role} {frags}: x_out_frag un-permuted differs from the row-major rows"
         assert all_bytes(xf[: 8 * D], 0xFF) and all_bytes(xf[8 * D + pe:], 0xFF), "canary rows around x_out_frag"
         if "xin" in frags:       # (the harness poisons the row-major patch rows that x_in_frag stands in for)
             assert all_bytes(got["xres"][:M][pr], POISON), "the row-major patch rows of x must keep their poison bytes"
@@ -225,7 +184,7 @@ def check_tail(o, role, frags):
     if want["out"] is not None:
         if "out" in frags:
             of = got["out_frag"]
-            assert same(of[8 * D: 8 * D + pe][idx16(o.B * N)], want["out"][:M][pr]), f"{role} {frags}: out_frag un-permuted differs from the row-major copy"
+            assert same(unfrag(of[8 * D:], o.B * N // 32, D), want["out"][:M][pr]), f"{role} {frags}: out_frag un-permuted differs from the row-major copy"
             assert all_bytes(of[: 8 * D], 0xFF) and all_bytes(of[8 * D + pe:], 0xFF), "canary rows around out_frag"
             assert all_bytes(got["out"][:M][pr], 0xFF), "the row-major patch rows of the copy must not be written"
         else:
@@ -262,8 +221,8 @@ STAGES = {"all_frag": 0, "no_ao": L.DD_DEV_NO_FRAG_AO, "no_skip": L.DD_DEV_NO_FR
 
 def _model(flags, B):
     """an engine model finalized under `flags` (the hand-offs are a property of the model, chosen in dd_model_finalize)"""
-    m, _ = _uvit(QA512, 71, "bf16", max_batch=B)
-    with _flags(_ctx(), flags):
+    m, _ = uvit(QA512, 71, "bf16", max_batch=B)
+    with _flags(kernel_support.ctx(), flags):
         em = m.engine_model(B)
     return m, em
 
@@ -271,14 +230,14 @@ def _model(flags, B):
 @gpu
 def test_model_outputs_do_not_depend_on_the_form_of_the_hand_offs():
     B = 4
-    ctx = _ctx()
+    ctx = kernel_support.ctx()
     x = _x0(B, 3, 64, 5)
     outs = {}
     for name, flags in STAGES.items():
         m, em = _model(flags, B)
         fwd = em.forward(x, 417.0, None).clone()
         pag = em.forward_perturbed(x[:2], 417.0, None, 0.7, [1]).clone() if name in ("all_frag", "row_major") else None   # identity attention in the mid block
-        s = _stream()
+        s = side_stream()
         loops = {}
         for chains, cf in (("two", L.DD_DEV_FORCE_CHAINS), ("one", L.DD_DEV_NO_CHAINS)):
             with _flags(ctx, cf):
@@ -301,7 +260,7 @@ def test_model_outputs_do_not_depend_on_the_form_of_the_hand_offs():
 def test_stale_workspace_bytes_do_not_reach_the_outputs():
     """every fragment buffer is written before it is read: a forward on poisoned workspaces equals the first forward of the model"""
     B = 4
-    ctx = _ctx()
+    ctx = kernel_support.ctx()
     m, em = _model(0, B)
     x = _x0(B, 3, 64, 6)
     first = em.forward(x, 100.0, None).clone()
@@ -321,7 +280,7 @@ def test_early_exit_model_keeps_the_residual_rows_row_major():
     x = torch.randn(B, 3, 64, 64, generator=torch.Generator().manual_seed(9))
     got = {}
     for name, flags in (("frag", 0), ("row_major", ALL_OFF)):
-        with _flags(_ctx(), flags):
+        with _flags(kernel_support.ctx(), flags):
             m, mp = _engine(QA512, 73, "mlp_probe_per_layer", "bf16", max_batch=B)
             eps, cls, outs = m(x, torch.full((B,), 300.0), None)
             got[name] = (eps.clone(), torch.stack(cls).clone(), torch.stack(outs).clone())

@@ -16,77 +16,18 @@ import ctypes as C
 
 import numpy as np
 import pytest
-import torch
 
-from oracle.uvit_oracle import layer_norm
+import kernel_support
+from kernel_support import (FP32_REL, GELU_POLY, GELU_SLOPE, NAN32, PARITY_REL, PREC_BF16, PREC_FP32, P, bf16, from_bf16_bits, gate, gelu_exact,
+                            ln_ref_and_tol, round_up, unfrag, untouched, ulp_bf16)
 
 gpu = pytest.mark.gpu
 
 EPI_STORE, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_SET, EPI_BIAS_STORE = range(5)
 EPI_NAME = {EPI_STORE: "store", EPI_BIAS_GELU: "bias_gelu", EPI_BIAS_RESID: "bias_resid", EPI_BIAS_SET: "bias_set", EPI_BIAS_STORE: "bias_store"}
-PREC_BF16, PREC_FP32 = 0, 1
-FP32_REL = 2.0 ** -16          # fp32 accumulation of bf16 products (K / 16 MFMA partial sums, + bias, + x)
-PARITY_REL = 2.0 ** -20        # fp32 parity mode
-GELU_POLY = 2.41e-4            # |gelu_erf4 (bf16 mode) - exact GELU| for |v| <= 16 (gemm.hip)
-GELU_SLOPE = 1.13              # max |d gelu / dv|
-NAN32, NAN16 = 0xFFFFFFFF, 0xFFFF
 
 
-# ---------------------------------------------------------------------------------------------------------------- host helpers
-def bf16(a):
-    """fp32 -> bf16 (round to nearest even) -> fp32, as host_f2bf"""
-    u = np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)
-    return (((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint32) << 16).view(np.float32)
-
-
-def from_bf16_bits(b):
-    return (np.ascontiguousarray(b, np.uint16).astype(np.uint32) << 16).view(np.float32)
-
-
-def ulp_bf16(y):
-    """one bf16 ulp at bf16(y) (0 at 0: the fp32 term covers it)"""
-    yb = np.abs(bf16(np.asarray(y, np.float32))).astype(np.float64)
-    _, e = np.frexp(yb)
-    return np.where(yb == 0, 0.0, np.ldexp(1.0, e - 8))
-
-
-def gelu_exact(v):
-    t = torch.from_numpy(np.ascontiguousarray(v, np.float64))
-    return (0.5 * t * (1.0 + torch.special.erf(t / np.sqrt(2.0)))).numpy()
-
-
-def gate(got, ref, tol, what):
-    """elementwise |got - ref| <= tol; NaN fails.  Returns the largest error / bound ratio."""
-    got = np.asarray(got, np.float64)
-    err = np.abs(got - ref)
-    bad = ~(err <= tol)
-    if bad.any():
-        i = tuple(np.argwhere(bad)[0])
-        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.size} elements out of bound; first at {i}: got {got[i]!r}, "
-                             f"ref {ref[i]!r}, bound {tol[i] if np.ndim(tol) else tol!r}")
-    return float((err / np.maximum(tol, 1e-300)).max())
-
-
-def ln_ref_and_tol(x, g, b):
-    """LayerNorm of fp32 rows x (the kernel's own) and the bf16 bound: one ulp + 2^-16 of the rows' scale in units of their spread"""
-    want = layer_norm(x.astype(np.float32), g, b).astype(np.float64)
-    x64 = x.astype(np.float64)
-    rstd = 1.0 / np.sqrt(x64.var(-1, keepdims=True) + 1e-5)
-    scale = np.abs(x64).max(-1, keepdims=True) * rstd
-    return want, ulp_bf16(want) + FP32_REL * (scale * np.abs(g) + np.abs(b)) + 1e-30
-
-
-def unfrag(fr, groups, D):
-    """[32-row group][D / 16 k-steps][64 lanes] x 8 bf16 (MlpFusedArgs::ln_out_frag) -> [groups 32, D] rows: lane -> row lane & 31,
-    k = 16 ks + 8 (lane >> 5) + i (rowlin_pack's fragment order)"""
-    f = fr[: groups * (D // 16) * 64 * 8].reshape(groups, D // 16, 2, 32, 8)       # [grp][ks][lane >> 5][lane & 31][i]
-    return f.transpose(0, 3, 1, 2, 4).reshape(groups * 32, D)
-
-
-def round_up(v, m):
-    return (v + m - 1) // m * m
-
-
+# ---------------------------------------------------------------------------------------------------------------- operands
 def operands(M, N, K, seed, bias_span=None, x_offset=0.0):
     r = np.random.default_rng(seed)
     A = r.standard_normal((M, K), dtype=np.float32)
@@ -108,19 +49,10 @@ def linear_ref(A, W, prec=PREC_BF16, k0=0, k1=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU calls
-def _ctx():
-    from duodiff_amd.engine import Context
-    return Context.get()
-
-
-def P(a):
-    return None if a is None else a.ctypes.data
-
-
 def run_gemm(A, W, bias, x_in, epi, K1=0, prec=PREC_BF16, tile128=-1, hm=None, splits=0, resid=1, ln=None, tok=(0, 0), frag=False,
              ldo=None, with_out=True, num_cus=0):
     """dd_dev_gemm; returns (xres [Mo, N], out, h, frag, slabs) as the whole buffers"""
-    ctx = _ctx()
+    ctx = kernel_support.ctx()
     M, K = A.shape
     N = W.shape[0]
     K1 = K1 or K
@@ -148,7 +80,7 @@ def run_gemm(A, W, bias, x_in, epi, K1=0, prec=PREC_BF16, tile128=-1, hm=None, s
 
 
 def run_rowlin(A, W, bias, x_in, B, n_patches, extras, k_split=0, set_x=0, ln=None, frag=False, copy=True):
-    ctx = _ctx()
+    ctx = kernel_support.ctx()
     M, K = A.shape
     Mo = round_up(M, 256) + 8
     a1 = np.ascontiguousarray(A[:, :k_split] if k_split else A)
@@ -162,14 +94,6 @@ def run_rowlin(A, W, bias, x_in, B, n_patches, extras, k_split=0, set_x=0, ln=No
                                     P(np.ascontiguousarray(W)), P(bias), P(lnp), P(xres), P(xc), P(h), 1 if frag else 0, 0, None,
                                     C.byref(C.c_float(0))))
     return xres, xc, h
-
-
-def untouched32(a):
-    return np.all(np.ascontiguousarray(a).view(np.uint32) == NAN32)
-
-
-def untouched16(a):
-    return np.all(np.ascontiguousarray(a) == NAN16)
 
 
 def ln_params(D, seed):
@@ -200,17 +124,17 @@ def check_linear(name, M, N, K, epi, K1=0, prec=PREC_BF16, tile128=-1, ldo=None,
             tout = GELU_SLOPE * t32 + (GELU_POLY + 2.0 ** -22 * np.abs(pre) if prec == PREC_BF16 else 4 * 2.0 ** -24 * np.abs(oref))
         else:
             oref, tout = pre, t32
-    assert untouched32(xres[M:]), f"{name}: x rows >= M written"
+    assert untouched(xres[M:]), f"{name}: x rows >= M written"
     if out is not None and epi != EPI_BIAS_SET:
         if prec == PREC_BF16:
             got = from_bf16_bits(out[:M, :N])
             ratios["out"] = gate(got, oref, ulp_bf16(oref) + tout, f"{name}: out")
-            assert untouched16(out[M:]) and untouched16(out[:, N:]), f"{name}: out written outside [M, N)"
+            assert untouched(out[M:]) and untouched(out[:, N:]), f"{name}: out written outside [M, N)"
         else:
             ratios["out"] = gate(out[:M, :N], oref, tout + 1e-30, f"{name}: out")
-            assert untouched32(out[M:]) and untouched32(out[:, N:]), f"{name}: out written outside [M, N)"
+            assert untouched(out[M:]) and untouched(out[:, N:]), f"{name}: out written outside [M, N)"
     elif out is not None:
-        assert (untouched16 if prec == PREC_BF16 else untouched32)(out), f"{name}: EPI_BIAS_SET wrote out"
+        assert untouched(out), f"{name}: EPI_BIAS_SET wrote out"
     print(f"{name}: M={M} N={N} K={K} K1={K1 or K} {EPI_NAME[epi]} tile128={tile128} ldo={ldo or N}: max err/bound "
           + ", ".join(f"{k} {v:.3f}" for k, v in ratios.items()))
     return xres, out
@@ -236,7 +160,7 @@ GEMM256 = [
 @gpu
 @pytest.mark.parametrize("M,N,K,K1,epi", GEMM256)
 def test_gemm256_against_float64_reference(M, N, K, K1, epi):
-    lib = _ctx().lib
+    lib = kernel_support.ctx().lib
     q, e = C.c_int(), C.c_int()
     if lib.dd_plan_rows(M, N, K, 256, C.byref(q), C.byref(e)) == 0:
         print(f"  plan256 at 256 CUs: q={q.value} e={e.value}")
@@ -283,8 +207,8 @@ def test_head_major_qkv_store(D, L, B, bias):
     img = out[: B * 3 * H * Lp * 64].reshape(B, 3 * H, Lp, 64)
     got = from_bf16_bits(img[:, :, :L, :]).transpose(0, 2, 1, 3).reshape(M, N)
     r = gate(got, ref, tol, "head-major qkv")
-    assert untouched16(img[:, :, L:, :]), "rows [L, Lp) of a head-major unit written"
-    assert untouched16(out[B * 3 * H * Lp * 64:]), "bytes behind the head-major image written"
+    assert untouched(img[:, :, L:, :]), "rows [L, Lp) of a head-major unit written"
+    assert untouched(out[B * 3 * H * Lp * 64:]), "bytes behind the head-major image written"
     print(f"head-major D={D} L={L} B={B} bias={bias}: max err/bound {r:.3f}")
 
 
@@ -316,14 +240,14 @@ def test_split_k_and_reduce_ln_against_float64_reference(D, K, K1, splits, resid
         k0, k1 = sp * nk // splits * 64, (sp + 1) * nk // splits * 64
         acc, absum = linear_ref(A, W, k0=k0, k1=k1)
         gate(slab.reshape(-1)[sp * M * D: (sp + 1) * M * D].reshape(M, D), acc, FP32_REL * absum, f"slab {sp}")     # (slab sp at sp M N)
-    assert untouched32(slab.reshape(-1)[splits * M * D:]), "slab area past M N splits written"
+    assert untouched(slab.reshape(-1)[splits * M * D:]), "slab area past M N splits written"
     acc, absum = linear_ref(A, W)
     xref = acc + bias + (x_in.astype(np.float64) if resid else 0.0)
     tx = FP32_REL * (absum + np.abs(bias) + (np.abs(x_in) if resid else 0.0))
     rx = gate(xres[:M], xref, tx, "x")
-    assert untouched32(xres[M:]), "x rows >= M written"
+    assert untouched(xres[M:]), "x rows >= M written"
     ro = gate(from_bf16_bits(out[:M]), xref, ulp_bf16(xref) + tx, "bf16 copy")
-    assert untouched16(out[M:]), "copy rows >= M written"
+    assert untouched(out[M:]), "copy rows >= M written"
     msg = f"split-K D={D} K={K} K1={K1 or K} splits={splits} resid={resid} ln={with_ln} frag={frag} L={L} B={B}: max err/bound x {rx:.3f}, copy {ro:.3f}"
     if with_ln:
         want, tol = ln_ref_and_tol(xres[:M], *ln)
@@ -332,13 +256,13 @@ def test_split_k_and_reduce_ln_against_float64_reference(D, K, K1, splits, resid
             groups = B * 256 // 32
             got_p = unfrag(fr.reshape(-1), groups, D)
             rh = gate(from_bf16_bits(got_p), want[patch], tol[patch], "LayerNorm (fragment order)")
-            assert untouched16(fr.reshape(-1)[groups * 32 * D:]), "fragment buffer written past the patch rows"
+            assert untouched(fr.reshape(-1)[groups * 32 * D:]), "fragment buffer written past the patch rows"
             rows = ~patch
-            assert untouched16(h[:M][patch]), "patch rows' LayerNorm written row-major too"
+            assert untouched(h[:M][patch]), "patch rows' LayerNorm written row-major too"
         else:
             rows = np.ones(M, bool)
         rh2 = gate(from_bf16_bits(h[:M][rows]), want[rows], tol[rows], "LayerNorm (row-major)")
-        assert untouched16(h[M:]), "LayerNorm rows >= M written"
+        assert untouched(h[M:]), "LayerNorm rows >= M written"
         msg += f", LayerNorm row-major {rh2:.3f}" + (f", fragment order {rh:.3f}" if frag else "")
     print(msg)
 
@@ -364,11 +288,11 @@ def check_rowlin(name, B, P_, E, K, k_split, set_x, frag, copy, with_ln, x_offse
     xref = acc + bias + (0.0 if set_x else x_in.astype(np.float64))
     tx = FP32_REL * (absum + np.abs(bias) + (0.0 if set_x else np.abs(x_in)))
     rx = gate(xres[:M], xref, tx, f"{name}: x")
-    assert untouched32(xres[M:]), f"{name}: x rows >= M written"
+    assert untouched(xres[M:]), f"{name}: x rows >= M written"
     msg = f"{name} B={B} patches={P_} extras={E} M={M} K={K} k_split={k_split} set_x={set_x} frag={frag}: max err/bound x {rx:.3f}"
     if copy:
         msg += f", copy {gate(from_bf16_bits(xc[:M]), xref, ulp_bf16(xref) + tx, f'{name}: x copy'):.3f}"
-        assert untouched16(xc[M:]), f"{name}: copy rows >= M written"
+        assert untouched(xc[M:]), f"{name}: copy rows >= M written"
     if with_ln:
         want, tol = ln_ref_and_tol(xres[:M], *ln)
         if frag:
@@ -376,10 +300,10 @@ def check_rowlin(name, B, P_, E, K, k_split, set_x, frag, copy, with_ln, x_offse
             groups = int(patch.sum()) // 32
             got = unfrag(h.reshape(-1), groups, 768)
             msg += f", LayerNorm fragment order {gate(from_bf16_bits(got), want[patch], tol[patch], f'{name}: LayerNorm (fragment order)'):.3f}"
-            assert untouched16(h.reshape(-1)[groups * 32 * 768:]), f"{name}: fragment buffer written past the patch rows"
+            assert untouched(h.reshape(-1)[groups * 32 * 768:]), f"{name}: fragment buffer written past the patch rows"
         else:
             msg += f", LayerNorm {gate(from_bf16_bits(h[:M]), want, tol, f'{name}: LayerNorm'):.3f}"
-            assert untouched16(h[M:]), f"{name}: LayerNorm rows >= M written"
+            assert untouched(h[M:]), f"{name}: LayerNorm rows >= M written"
     print(msg)
     return xres, xc, h
 

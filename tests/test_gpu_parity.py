@@ -18,6 +18,7 @@ import oracle
 from conftest import FULL_NAMES, REPO, TINY, tiny_cfg_from_fixture
 from duodiff_amd.config import ModelParams, load_config
 from duodiff_amd.weights import synthetic_state_dict
+from loop_support import eps_rms_bound, uvit
 
 pytestmark = pytest.mark.gpu
 
@@ -30,26 +31,6 @@ def eps_tol(precision, ref, full_size=False):
     1536-value slice moves by +-5 % with every change of accumulation order in a kernel, so it is not the regression gate).
     The gate is the rms error against the error model of eps_rms_bound (fixed margin, no per-config constants)."""
     return 1e-4 if precision == "fp32" else (5e-2 if full_size else 3e-2) * float(np.asarray(ref, np.float64).std())
-
-
-# bf16 engine vs the reference: the gate on rms(eps - ref) / sigma(ref) is an ERROR MODEL, not a fit to the last run.  Every block rounds
-# ~6 GEMM operands to bf16 (norm1 rows, the attention output, norm2 rows, the GELU'd hidden rows, the long-skip copy, P of the attention
-# core), each with relative rms 2^-9 / sqrt(3) (uniform rounding error of an 8-bit significand), and the roundings of the `depth` blocks
-# add in quadrature on a residual stream of spread ~sigma:  model = 2^-9 / sqrt(3) * sqrt(6 depth)  =  4.8e-3 (depth 3) .. 9.9e-3 (13)
-# .. 1.27e-2 (21).  Observed on MI355X (profiles/r05/parity_numbers.txt): 0.47 .. 0.96 of the model.  The bound is the model x 1.5, fixed.
-EPS_RMS_MODEL_MARGIN = 1.5
-
-
-def eps_rms_bound(depth):
-    return EPS_RMS_MODEL_MARGIN * 2.0 ** -9 / np.sqrt(3.0) * np.sqrt(6.0 * depth)
-
-
-def _uvit(cfg, seed, precision, max_batch=None):
-    from duodiff_amd.uvit import UViT
-    mp = ModelParams.from_dict(cfg)
-    m = UViT(**mp.as_dict(), precision=precision, max_batch=max_batch)
-    m.load_state_dict(synthetic_state_dict(mp, seed))
-    return m.eval().to("cuda"), mp
 
 
 def _oracle(cfg, seed):
@@ -68,7 +49,7 @@ def test_library_loaded_in_tree():
 def test_forward_tiny_vs_reference(golden, name, precision):
     fx = golden(f"uvit_tiny_{name}.npz")
     cfg = tiny_cfg_from_fixture(fx)
-    m, mp = _uvit(cfg, int(fx["seed"]), precision)
+    m, mp = uvit(cfg, int(fx["seed"]), precision)
     y = torch.from_numpy(fx["y"]) if "y" in fx.files else None
     eps = m(torch.from_numpy(fx["x"]), torch.from_numpy(fx["t"]), y).cpu().numpy()
     err = np.abs(eps - fx["eps"]).max()
@@ -81,7 +62,7 @@ def test_forward_tiny_vs_reference(golden, name, precision):
 def test_forward_full_size_vs_reference(golden, name, precision):
     fx = golden(f"uvit_full_{name}.npz")
     cfg = load_config(REPO / "configs" / f"{name}.yaml")
-    m, mp = _uvit(cfg, int(fx["seed"]), precision)
+    m, mp = uvit(cfg, int(fx["seed"]), precision)
     B = fx["x"].shape[0]
     t = torch.full((B,), float(fx["t"]))
     y = torch.from_numpy(fx["y"]) if fx["y"].size else None
@@ -124,7 +105,7 @@ def test_teacher_forced_step_within_1e3(golden, name, precision):
     fx = golden(f"uvit_full_{name}.npz")
     cfg = load_config(REPO / "configs" / f"{name}.yaml")
     seed = int(fx["seed"])
-    m, mp = _uvit(cfg, seed, precision)
+    m, mp = uvit(cfg, seed, precision)
     orc = _oracle(cfg, seed)
     B = 2
     x = fx["x"]
@@ -147,8 +128,8 @@ def test_rollout_tiny_fp32_vs_reference(golden):
     """get_samples with late_model, t_switch=300, seed 0, B=2 against the reference's own rollout."""
     from duodiff_amd import sampler
     fx = golden("rollout_tiny.npz")
-    m_s, _ = _uvit(dict(TINY, depth=1), int(fx["seed_first"]), "fp32")
-    m_f, _ = _uvit(dict(TINY, depth=3), int(fx["seed_late"]), "fp32")
+    m_s, _ = uvit(dict(TINY, depth=1), int(fx["seed_first"]), "fp32")
+    m_f, _ = uvit(dict(TINY, depth=3), int(fx["seed_late"]), "fp32")
     samples, inter = sampler.get_samples(m_s, 2, sampler.predict_noise_postprocessing, 0, 3, 8, 8,
                                          timesteps_save=[1, 2, 301], late_model=m_f, t_switch=300,
                                          noise="torch_cpu")
@@ -168,8 +149,8 @@ def test_switch_and_graph_replay_match_manual_steps():
     one by one through dd_sample_step: bit-exact, and the switch happens AFTER t == 1000 - t_switch."""
     from duodiff_amd.engine import sample_loop
     cfg_s, cfg_f = dict(TINY, depth=1), dict(TINY, depth=3)
-    m_s, _ = _uvit(cfg_s, 11, "bf16")
-    m_f, _ = _uvit(cfg_f, 12, "bf16")
+    m_s, _ = uvit(cfg_s, 11, "bf16")
+    m_f, _ = uvit(cfg_f, 12, "bf16")
     B = 4
     es, ef = m_s.engine_model(B), m_f.engine_model(B)
     x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(3)).cuda()
@@ -211,8 +192,8 @@ def test_half_batch_chains_equal_the_single_chain(case):
         B, S, C_, steps, tsw, force = 6, 8, 3, 12, 5, L.DD_DEV_FORCE_CHAINS
         nc = 10 if case == "tiny_cond_forced" else -1
         cfg_s, cfg_f = dict(TINY, depth=1, num_classes=nc), dict(TINY, depth=3, num_classes=nc)
-    m_s, _ = _uvit(cfg_s, 31, "bf16", max_batch=B)
-    m_f, mp_f = _uvit(cfg_f, 32, "bf16", max_batch=B)
+    m_s, _ = uvit(cfg_s, 31, "bf16", max_batch=B)
+    m_f, mp_f = uvit(cfg_f, 32, "bf16", max_batch=B)
     es, ef = m_s.engine_model(B), m_f.engine_model(B)
     ctx = es.ctx
     x0 = torch.randn(B, C_, S, S, generator=torch.Generator().manual_seed(4)).cuda()
@@ -266,8 +247,8 @@ def test_no_kernel_depends_on_stale_workspace_bytes(case):
     stream.wait_stream(torch.cuda.current_stream())
     outs = []
     for poison in (False, True):
-        m_s, _ = _uvit(cfg_s, 131, prec, max_batch=B)
-        m_f, mp_f = _uvit(cfg_f, 132, prec, max_batch=B)
+        m_s, _ = uvit(cfg_s, 131, prec, max_batch=B)
+        m_f, mp_f = uvit(cfg_f, 132, prec, max_batch=B)
         es, ef = m_s.engine_model(B), m_f.engine_model(B)
         ctx = es.ctx
         ncls = int(mp_f.num_classes)
@@ -295,7 +276,7 @@ def test_profile_steps_chained_counts_and_grid():
     """dd_profile_steps_chained (bench.py's `chained` roofline leg) brackets every launch of the selected kernel in BOTH chains:
     2 x steps x depth event pairs for the block tail, and it runs on the chain-sized GEMM grids dd_sample uses."""
     cfg = load_config(REPO / "configs" / "uvit_celeba_3.yaml")
-    m, mp = _uvit(cfg, 7, "bf16", max_batch=64)
+    m, mp = uvit(cfg, 7, "bf16", max_batch=64)
     em = m.engine_model(64)
     x = torch.randn(64, 3, 64, 64, generator=torch.Generator().manual_seed(3)).cuda()
     stream = torch.cuda.Stream()
@@ -315,8 +296,8 @@ def test_half_batch_chains_in_the_table_driven_loops():
     image offset)."""
     from duodiff_amd import _lib as L
     from duodiff_amd import sampler
-    m_s, _ = _uvit(dict(TINY, depth=1), 300, "bf16", max_batch=6)
-    m_f, _ = _uvit(dict(TINY, depth=3), 301, "bf16", max_batch=6)
+    m_s, _ = uvit(dict(TINY, depth=1), 300, "bf16", max_batch=6)
+    m_f, _ = uvit(dict(TINY, depth=3), 301, "bf16", max_batch=6)
     ctx = m_s.engine_model(6).ctx
     run = lambda **kw: sampler.get_samples(m_s, 6, kw.pop("post", sampler.predict_noise_postprocessing), 5, 3, 8, 8,
                                            late_model=m_f, noise="device", **kw)
@@ -341,8 +322,8 @@ def test_graphs_are_not_recaptured_for_new_tensors():
     buffers, so a second call with other tensors of the same shape replays the captured graphs (and still writes its
     result into the caller's tensor)."""
     from duodiff_amd.engine import sample_loop
-    m_s, _ = _uvit(dict(TINY, depth=1), 21, "bf16")
-    m_f, _ = _uvit(dict(TINY, depth=3), 22, "bf16")
+    m_s, _ = uvit(dict(TINY, depth=1), 21, "bf16")
+    m_f, _ = uvit(dict(TINY, depth=3), 22, "bf16")
     B = 3
     es, ef = m_s.engine_model(B), m_f.engine_model(B)
     lib, h = es.ctx.lib, es.ctx.handle
@@ -366,7 +347,7 @@ def test_graphs_are_not_recaptured_for_new_tensors():
 
 
 def test_philox_noise_is_standard_normal():
-    m, mp = _uvit(dict(TINY), 21, "bf16")
+    m, mp = uvit(dict(TINY), 21, "bf16")
     B = 64
     em = m.engine_model(B)
     x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(1)).cuda()
@@ -389,7 +370,7 @@ def test_batch_independence_at_full_size():
     """Images are independent (no cross-sample op on the path): image i of a B=128 CelebA batch
     equals the same image run at B=2, bit for bit.  Also exercises the BASELINE batch size."""
     cfg = load_config(REPO / "configs" / "uvit_celeba_3.yaml")
-    m, mp = _uvit(cfg, 1237, "bf16", max_batch=128)
+    m, mp = uvit(cfg, 1237, "bf16", max_batch=128)
     x = torch.randn(128, 3, 64, 64, generator=torch.Generator().manual_seed(8)).cuda()
     t = torch.full((128,), 640.0)
     eps_big = m(x, t)
@@ -402,12 +383,12 @@ def test_batch_independence_at_full_size():
 
 def test_full_size_bf16_close_to_fp32_at_batch_128():
     cfg = load_config(REPO / "configs" / "uvit_celeba.yaml")
-    mb, _ = _uvit(cfg, 1236, "bf16", max_batch=128)
+    mb, _ = uvit(cfg, 1236, "bf16", max_batch=128)
     x = torch.randn(128, 3, 64, 64, generator=torch.Generator().manual_seed(9)).cuda()
     t = torch.full((128,), 123.0)
     eb = mb(x, t)
     del mb
-    mf, _ = _uvit(cfg, 1236, "fp32", max_batch=128)
+    mf, _ = uvit(cfg, 1236, "fp32", max_batch=128)
     ef = mf(x, t)
     err = (eb - ef).abs().max().item()
     rms, sd = ((eb - ef) ** 2).mean().sqrt().item(), ef.std().item()
@@ -439,7 +420,7 @@ def test_class_conditional_width_512_vs_oracle(B, qkv_bias):
     want = _oracle(cfg, 4242)(x.numpy(), t.numpy(), y.numpy())
     sigma = float(want.std())
     for prec in ("fp32", "bf16"):
-        m, _ = _uvit(cfg, 4242, prec, max_batch=B)
+        m, _ = uvit(cfg, 4242, prec, max_batch=B)
         got = m(x, t, y).cpu().numpy()
         del m
         assert np.isfinite(got).all()
@@ -467,8 +448,8 @@ def test_benchmarked_path_drift_bf16_vs_fp32(K):
     k_switch = max(1, round(0.3 * K))
     out = {}
     for prec in ("bf16", "fp32"):
-        ms, _ = _uvit(cfg_s, 1237, prec, max_batch=B)
-        mf, _ = _uvit(cfg_f, 1236, prec, max_batch=B)
+        ms, _ = uvit(cfg_s, 1237, prec, max_batch=B)
+        mf, _ = uvit(cfg_f, 1236, prec, max_batch=B)
         es, ef = ms.engine_model(B), mf.engine_model(B)
         x = x_T.clone()
         stream = torch.cuda.Stream()
@@ -490,7 +471,7 @@ def test_benchmarked_path_drift_bf16_vs_fp32(K):
 def test_error_behaviour_matches_reference_classes():
     from duodiff_amd.uvit import UViT
     cfg = dict(TINY, num_classes=10)
-    m, mp = _uvit(cfg, 5, "fp32")
+    m, mp = uvit(cfg, 5, "fp32")
     x = torch.zeros(2, 3, 8, 8)
     with pytest.raises(RuntimeError):          # quirk Q5: conditional model without y
         m(x, torch.zeros(2))
@@ -508,8 +489,8 @@ def test_ddim_and_other_parametrizations_vs_reference(golden):
     own outputs, and the predict_original / predict_previous updates against the reference."""
     from duodiff_amd import sampler
     fd = golden("ddim_tiny.npz")
-    m_s, _ = _uvit(dict(TINY, depth=1), 300, "fp32")
-    m_f, _ = _uvit(dict(TINY, depth=3), 301, "fp32")
+    m_s, _ = uvit(dict(TINY, depth=1), 300, "fp32")
+    m_f, _ = uvit(dict(TINY, depth=3), 301, "fp32")
     for tag in ("a", "b", "c", "nan"):
         steps, eta, tsw = fd[f"cfg_{tag}"]
         with np.errstate(invalid="ignore"):
@@ -535,7 +516,7 @@ def test_ddim_and_other_parametrizations_vs_reference(golden):
         got = sampler.predict_previous_postprocessing(m, x, t, z).cpu().numpy()
         np.testing.assert_allclose(got, fx[f"prev_{t}"], rtol=0, atol=1e-6)
     # a short predict_previous loop runs end to end through get_samples
-    m_s, _ = _uvit(dict(TINY, depth=1), 300, "bf16")
+    m_s, _ = uvit(dict(TINY, depth=1), 300, "bf16")
     s, _ = sampler.get_samples(m_s, 2, sampler.predict_previous_postprocessing, 0, 3, 8, 8, num_steps=5, noise="torch_cpu")
     assert s.shape == (2, 8, 8, 3) and np.isfinite(s).all()
 
@@ -548,8 +529,8 @@ def test_device_resident_ddim_and_parametrization_loops(precision):
     loop equals the step-by-step Python loop (dd_forward + dd_affine_step, the path the reference fixtures pin) bit for bit,
     save points included; (3) the noisy DDIM / predict_* runs are finite and differ from the noise-free ones."""
     from duodiff_amd import sampler
-    m_s, _ = _uvit(dict(TINY, depth=1), 300, precision)
-    m_f, _ = _uvit(dict(TINY, depth=3), 301, precision)
+    m_s, _ = uvit(dict(TINY, depth=1), 300, precision)
+    m_f, _ = uvit(dict(TINY, depth=3), 301, precision)
     run = lambda **kw: sampler.get_samples(m_s, 3, kw.pop("post", sampler.predict_noise_postprocessing), 3, 3, 8, 8,
                                            late_model=m_f, **kw)
     # (2) DDIM eta = 0, switch inside the run, one save point: device loop == Python loop
@@ -579,8 +560,8 @@ def test_save_points_do_not_change_the_final_samples():
     so step k draws the same z whether or not the loop was cut before it.  Noisy DDIM (eta > 0), predict_original and
     predict_previous with a backbone switch; and the DDPM loop (dd_sample: counter = t) for completeness."""
     from duodiff_amd import sampler
-    m_s, _ = _uvit(dict(TINY, depth=1), 300, "fp32")
-    m_f, _ = _uvit(dict(TINY, depth=3), 301, "fp32")
+    m_s, _ = uvit(dict(TINY, depth=1), 300, "fp32")
+    m_f, _ = uvit(dict(TINY, depth=3), 301, "fp32")
     run = lambda **kw: sampler.get_samples(m_s, 3, kw.pop("post", sampler.predict_noise_postprocessing), 7, 3, 8, 8,
                                            late_model=m_f, noise="device", **kw)
     # (DDIM visits t = linspace(0, 999, 40).astype(int) reversed: 1000 - t takes the values 1, 27, ..., 258, ..., 642, ...)
@@ -617,7 +598,7 @@ def test_fused_branches_at_small_widths_vs_oracle(D, H, num_classes):
     want = _oracle(cfg, 99)(x.numpy(), t.numpy(), y.numpy() if y is not None else None)
     sigma = float(want.std())
     for prec in ("fp32", "bf16"):
-        m, _ = _uvit(cfg, 99, prec, max_batch=B)
+        m, _ = uvit(cfg, 99, prec, max_batch=B)
         got = m(x, t, y).cpu().numpy()
         del m
         err, rms = float(np.abs(got - want).max()), float(np.sqrt(((got - want).astype(np.float64) ** 2).mean()))
@@ -645,7 +626,7 @@ def test_kernel_variant_flags_agree_with_the_default_path(flags):
     ctx = Context.get()
     try:
         ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
-        m, _ = _uvit(cfg, 4243, "bf16", max_batch=B)
+        m, _ = uvit(cfg, 4243, "bf16", max_batch=B)
         got = m(x, t, y).cpu().numpy()
         del m
     finally:
@@ -674,7 +655,7 @@ def test_row_resident_fc2_at_embed_dim_768(img, B, flags, ncls):
     ctx = Context.get()
     try:
         ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
-        m, _ = _uvit(cfg, 4244, "bf16", max_batch=B)
+        m, _ = uvit(cfg, 4244, "bf16", max_batch=B)
         got = m(x, t, y).cpu().numpy()
         alone = m(x[B - 1:].contiguous(), t[:1], y[B - 1:].contiguous() if y is not None else None).cpu().numpy()
         del m
@@ -705,7 +686,7 @@ def test_split_k_linears_at_embed_dim_1024(img, B, flags, ncls):
     ctx = Context.get()
     try:
         ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
-        m, _ = _uvit(cfg, 4245, "bf16", max_batch=B)
+        m, _ = uvit(cfg, 4245, "bf16", max_batch=B)
         got = m(x, t, y).cpu().numpy()
         alone = m(x[B - 1:].contiguous(), t[:1], y[B - 1:].contiguous() if y is not None else None).cpu().numpy()
         del m
@@ -751,7 +732,7 @@ def test_ragged_batch_sizes_row_partition(B):
     B = 1 is a single 256-row tile + 1 tail row).  bf16 engine vs the oracle on image 0 and B-1, and every image
     bit-identical to the same image computed alone (B = 1)."""
     cfg = load_config(REPO / "configs" / "uvit_celeba_3.yaml")
-    m, mp = _uvit(cfg, 1237, "bf16", max_batch=64)
+    m, mp = uvit(cfg, 1237, "bf16", max_batch=64)
     orc = _oracle(cfg, 1237)
     x = torch.randn(B, 3, 64, 64, generator=torch.Generator().manual_seed(100 + B))
     t = torch.full((B,), 321.0)
@@ -767,7 +748,7 @@ def test_ragged_batch_sizes_row_partition(B):
 def test_conditional_model_full_size_labels():
     """Class-conditional path at full size (ImageNet-64 shallow, L = 258: two tail rows per tile) with distinct labels."""
     cfg = load_config(REPO / "configs" / "uvit_imagenet64_3.yaml")
-    m, mp = _uvit(cfg, 1239, "bf16", max_batch=8)
+    m, mp = uvit(cfg, 1239, "bf16", max_batch=8)
     orc = _oracle(cfg, 1239)
     B = 6
     x = torch.randn(B, 3, 64, 64, generator=torch.Generator().manual_seed(7))
@@ -788,8 +769,8 @@ def test_get_samples_device_noise_on_default_stream():
     """noise="device" replays hipGraphs; called from the default stream (as the CLI does) the loop moves to a side stream
     instead of failing in hipStreamBeginCapture.  Same seeds -> identical images; intermediate saves split the loop."""
     from duodiff_amd import sampler
-    m_s, _ = _uvit(dict(TINY, depth=1), 300, "fp32")
-    m_f, _ = _uvit(dict(TINY, depth=3), 301, "fp32")
+    m_s, _ = uvit(dict(TINY, depth=1), 300, "fp32")
+    m_f, _ = uvit(dict(TINY, depth=3), 301, "fp32")
     kw = dict(late_model=m_f, t_switch=300, noise="device", num_steps=40)
     a, _ = sampler.get_samples(m_s, 3, sampler.predict_noise_postprocessing, 7, 3, 8, 8, **kw)
     b, inter = sampler.get_samples(m_s, 3, sampler.predict_noise_postprocessing, 7, 3, 8, 8, timesteps_save=[20], **kw)
@@ -816,7 +797,7 @@ def test_sharded_cli_single_rank(tmp_path):
 def test_workspace_grows_with_batch():
     """No max_batch given: the engine model is rebuilt when a later call brings a larger batch; results do not depend on it."""
     cfg = dict(TINY)
-    m, _ = _uvit(cfg, 77, "fp32")
+    m, _ = uvit(cfg, 77, "fp32")
     g = torch.Generator().manual_seed(4)
     x = torch.randn(9, 3, 8, 8, generator=g)
     t = torch.full((9,), 123.0)
@@ -836,7 +817,7 @@ def test_noise_scheduler_sample_vs_reference(golden):
     and the default 1000-step schedule with sigma^2 = beta through the FUSED sampling step (DD_VAR_BETA)."""
     from duodiff_amd.ddpm_core import NoiseScheduler
     fx = golden("scheduler_tiny.npz")
-    m, _ = _uvit(dict(TINY, depth=1), int(fx["seed"]), "fp32")
+    m, _ = uvit(dict(TINY, depth=1), int(fx["seed"]), "fp32")
     for tag, steps, mode in (("", 50, "beta"), ("_bt50", 50, "beta_tilde"), ("_b1000", 1000, "beta")):
         sch = NoiseScheduler(beta_steps=steps, variance_mode=mode)
         x0, log = sch.sample(m, num_steps=steps, data_shape=(3, 8, 8), num_samples=2, seed=5, model_type="uvit")
@@ -861,8 +842,8 @@ def test_backbone_per_step_matches_reference_rule(t_switch):
     """Which backbone runs each step: the reference switches AFTER the step at t == 1000 - t_switch (sampler.py:135-136),
     so a t_switch outside [1, 1000] never switches.  Both noise paths of get_samples against manual stepping."""
     from duodiff_amd import sampler
-    m_s, _ = _uvit(dict(TINY, depth=1), 300, "fp32")
-    m_f, _ = _uvit(dict(TINY, depth=3), 301, "fp32")
+    m_s, _ = uvit(dict(TINY, depth=1), 300, "fp32")
+    m_f, _ = uvit(dict(TINY, depth=3), 301, "fp32")
     n, B, seed = 4, 2, 9
     sw = 1000 - t_switch if np.isfinite(t_switch) else None
     pick = lambda t: (m_s if (sw is None or not (0 <= sw <= 999) or t >= sw) else m_f).engine_model(B)
@@ -901,7 +882,7 @@ def test_full_batch_vs_oracle(name, B):
     oracle on image 0 and the last image, bf16 engine; every other image must at least be finite."""
     cfg = load_config(REPO / "configs" / f"{name}.yaml")
     seed = 1234 + FULL_NAMES.index(name)
-    m, mp = _uvit(cfg, seed, "bf16", max_batch=B)
+    m, mp = uvit(cfg, seed, "bf16", max_batch=B)
     orc = _oracle(cfg, seed)
     g = torch.Generator().manual_seed(4242)
     x = torch.randn(B, mp.in_chans, mp.img_size, mp.img_size, generator=g)
@@ -945,8 +926,8 @@ def test_two_ranks_equal_two_single_rank_runs(tmp_path):
         assert p.returncode == 0, se[-2000:]
     got = np.load(out / "samples.npy")
     assert got.shape == (2 * B, 16, 16, 3) and np.isfinite(got).all()
-    m_s, _ = _uvit(cfg_s, 21, "bf16")
-    m_f, _ = _uvit(cfg_f, 22, "bf16")
+    m_s, _ = uvit(cfg_s, 21, "bf16")
+    m_f, _ = uvit(cfg_f, 22, "bf16")
     for r in range(2):
         want, _ = sampler.get_samples(m_s, B, sampler.predict_noise_postprocessing, base + r, 3, 16, 16, late_model=m_f,
                                       t_switch=300, noise="device")

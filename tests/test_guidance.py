@@ -16,6 +16,7 @@ from conftest import REPO, TINY
 from duodiff_amd import _lib as L
 from duodiff_amd.config import ModelParams, load_config
 from duodiff_amd.weights import synthetic_state_dict
+from loop_support import cli_argv, engine_pair, eps_rms_bound, uvit
 
 gpu = pytest.mark.gpu
 
@@ -24,22 +25,17 @@ IMAGENET256_3 = REPO / "configs" / "uvit_imagenet256_3.yaml"
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
-def _argv(config, *extra):
-    return ["--checkpoint_path", "/nonexistent.pth", "--batch_size", "2", "--parametrization", "predict_noise",
-            "--output_folder", "/tmp/unused", "--config_path", str(config), *extra]
-
-
 def test_cli_guidance_options_and_defaults():
     from duodiff_amd import sampler
-    a = sampler.get_args(_argv(IMAGENET256))
+    a = sampler.get_args(cli_argv(IMAGENET256))
     assert a.cfg_scale is None and a.cfg_null_label == 1000 and a.class_label is None and a.class_id is None
-    a = sampler.get_args(_argv(IMAGENET256, "--cfg_scale", "0.4", "--class_label", "207", "--cfg_null_label", "999"))
+    a = sampler.get_args(cli_argv(IMAGENET256, "--cfg_scale", "0.4", "--class_label", "207", "--cfg_null_label", "999"))
     assert a.cfg_scale == pytest.approx(0.4) and a.class_label == 207 and a.cfg_null_label == 999
-    a = sampler.get_args(_argv(IMAGENET256, "--cfg_scale", "0"))
+    a = sampler.get_args(cli_argv(IMAGENET256, "--cfg_scale", "0"))
     assert a.cfg_scale == 0.0 and a.cfg_scale is not None       # 0 selects the guided path too
-    y = sampler.labels_from_args(sampler.get_args(_argv(IMAGENET256, "--class_label", "207")), 3, 1001)
+    y = sampler.labels_from_args(sampler.get_args(cli_argv(IMAGENET256, "--class_label", "207")), 3, 1001)
     assert y.dtype == torch.int64 and y.tolist() == [207, 207, 207]
-    assert sampler.labels_from_args(sampler.get_args(_argv(IMAGENET256)), 3, 1001) is None
+    assert sampler.labels_from_args(sampler.get_args(cli_argv(IMAGENET256)), 3, 1001) is None
 
 
 @pytest.mark.parametrize("config,extra,match", [
@@ -55,7 +51,7 @@ def test_cli_guidance_options_and_defaults():
 def test_cli_rejects_invalid_guidance_before_any_gpu_work(tmp_path, config, extra, match):
     """main() validates the options against the YAML before it builds a model: no GPU is touched (this runs on the CPU box)."""
     from duodiff_amd import sampler
-    argv = _argv(REPO / "configs" / config, *extra)
+    argv = cli_argv(REPO / "configs" / config, *extra)
     argv[argv.index("--output_folder") + 1] = str(tmp_path / "out")
     with pytest.raises(ValueError, match=match):
         sampler.main(argv)
@@ -63,7 +59,7 @@ def test_cli_rejects_invalid_guidance_before_any_gpu_work(tmp_path, config, extr
 
 def test_cli_rejects_a_late_config_without_the_null_row(tmp_path):
     from duodiff_amd import sampler
-    argv = _argv(IMAGENET256_3, "--cfg_scale", "0.4", "--class_label", "3", "--checkpoint_path_late", "/nonexistent.pth",
+    argv = cli_argv(IMAGENET256_3, "--cfg_scale", "0.4", "--class_label", "3", "--checkpoint_path_late", "/nonexistent.pth",
                  "--config_path_late", str(REPO / "configs" / "uvit_imagenet64.yaml"), "--output_folder", str(tmp_path / "out"))
     with pytest.raises(ValueError, match="null"):
         sampler.main(argv)
@@ -89,31 +85,12 @@ NULL = 10
 TINY_COND = dict(TINY, num_classes=11)     # 10 classes + the null row
 
 
-def eps_rms_bound(depth):
-    """test_gpu_parity's error model of the bf16 engine (rms(eps - oracle) / sigma), margin 1.5"""
-    return 1.5 * 2.0 ** -9 / np.sqrt(3.0) * np.sqrt(6.0 * depth)
-
-
-def _uvit(cfg, seed, precision, max_batch):
-    from duodiff_amd.uvit import UViT
-    mp = ModelParams.from_dict(cfg)
-    m = UViT(**mp.as_dict(), precision=precision, max_batch=max_batch)
-    m.load_state_dict(synthetic_state_dict(mp, seed))
-    return m.eval().to("cuda"), mp
-
-
-def _pair(cfg_s, cfg_f, seeds, max_batch, precision="bf16"):
-    m_s, _ = _uvit(cfg_s, seeds[0], precision, max_batch)
-    m_f, mp = _uvit(cfg_f, seeds[1], precision, max_batch)
-    return m_s.engine_model(max_batch), m_f.engine_model(max_batch), mp
-
-
 def _tiny_pair(seeds=(41, 42), max_batch=12, precision="bf16"):
-    return _pair(dict(TINY_COND, depth=1), dict(TINY_COND, depth=3), seeds, max_batch, precision)
+    return engine_pair(dict(TINY_COND, depth=1), dict(TINY_COND, depth=3), seeds, max_batch, precision)
 
 
 def _imagenet256_pair(max_batch=64):
-    return _pair(load_config(IMAGENET256_3), load_config(IMAGENET256), (51, 52), max_batch)
+    return engine_pair(load_config(IMAGENET256_3), load_config(IMAGENET256), (51, 52), max_batch)
 
 
 def _labels(B, ncls, seed):
@@ -143,7 +120,7 @@ def test_forward_guided_vs_oracle(case):
     want = ec + s * (ec - eu)
     sigma = float(ec.std())
     for prec in ("fp32", "bf16"):
-        m, _ = _uvit(cfg, 61, prec, max_batch=2 * B)
+        m, _ = uvit(cfg, 61, prec, max_batch=2 * B)
         em = m.engine_model(2 * B)
         got = em.forward_guided(x.cuda(), t, y.cuda(), s, NULL).cpu().numpy().astype(np.float64)
         torch.cuda.synchronize()
@@ -340,11 +317,11 @@ def test_invalid_guided_calls_are_rejected_before_anything_is_enqueued():
     B = 4
     es, ef, _ = _tiny_pair(max_batch=2 * B)
     ctx, lib = es.ctx, es.ctx.lib
-    small, _ = _uvit(dict(TINY_COND, depth=1), 81, "bf16", max_batch=B)          # room for B rows only
+    small, _ = uvit(dict(TINY_COND, depth=1), 81, "bf16", max_batch=B)          # room for B rows only
     es_small = small.engine_model(B)
-    late10, _ = _uvit(dict(TINY, depth=1, num_classes=10), 82, "bf16", 2 * B)   # no row for label 10
+    late10, _ = uvit(dict(TINY, depth=1, num_classes=10), 82, "bf16", 2 * B)   # no row for label 10
     el10 = late10.engine_model(2 * B)
-    unc, _ = _uvit(dict(TINY, depth=1), 83, "bf16", 2 * B)
+    unc, _ = uvit(dict(TINY, depth=1), 83, "bf16", 2 * B)
     eu = unc.engine_model(2 * B)
     ee = Model(ctx, ModelParams.from_dict(TINY_COND), 2 * B)
     ee.enable_early_exit("mlp_probe_per_layer")

@@ -14,6 +14,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import kernel_support
+from kernel_support import P
+
 pytestmark = pytest.mark.gpu
 
 
@@ -26,8 +29,7 @@ def _reference(x, g, b, w, bias):
 
 
 def _run(M, D, pd, tok_l, tok_e, x, probe, split=0):
-    from duodiff_amd.engine import Context
-    ctx = Context.get()
+    ctx = kernel_support.ctx()
     r = np.random.default_rng(D + pd)
     g = (1.0 + 0.2 * r.standard_normal(D)).astype(np.float32)
     b = (0.1 * r.standard_normal(D)).astype(np.float32)
@@ -38,7 +40,6 @@ def _run(M, D, pd, tok_l, tok_e, x, probe, split=0):
     dec = np.zeros((M, pd), np.float32)
     srow = np.zeros(M, np.float32)
     ms = C.c_float(0)
-    P = lambda a: a.ctypes.data
     ctx.check(ctx.lib.dd_dev_head_dec(ctx.handle, M, D, pd, tok_l, tok_e, P(x), P(g), P(b), P(w), P(bias), P(dec),
                                       P(pw) if probe else None, P(pb) if probe else None, P(srow) if probe else None, split, 3, None, C.byref(ms)))
     want = _reference(x, g, b, w, bias)

@@ -18,6 +18,7 @@ from conftest import REPO, TINY
 from duodiff_amd import _lib as L
 from duodiff_amd.config import ModelParams, load_config
 from duodiff_amd.weights import synthetic_state_dict
+from loop_support import known_region, philox_z, philox_z2, side_stream, uvit
 
 gpu = pytest.mark.gpu
 CELEBA_3 = REPO / "configs" / "uvit_celeba_3.yaml"
@@ -192,22 +193,8 @@ def test_lib_binds_the_region_entry_points():
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
-def _uvit(cfg, seed, precision, max_batch):
-    from duodiff_amd.uvit import UViT
-    mp = ModelParams.from_dict(cfg)
-    m = UViT(**mp.as_dict(), precision=precision, max_batch=max_batch)
-    m.load_state_dict(synthetic_state_dict(mp, seed))
-    return m.eval().to("cuda")
-
-
 def _model(max_batch, seed=42, precision="bf16", **kw):
-    return _uvit(dict(TINY, **kw), seed, precision, max_batch).engine_model(max_batch)
-
-
-def _stream():
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    return s
+    return uvit(dict(TINY, **kw), seed, precision, max_batch)[0].engine_model(max_batch)
 
 
 def _inputs(B, seed, C_=3, S=8, mask="checker"):
@@ -227,13 +214,6 @@ def _inputs(B, seed, C_=3, S=8, mask="checker"):
     return x.cuda(), x0.cuda(), m.cuda()
 
 
-def _region(plan, x0, mask, k0=0, k1=None):
-    from duodiff_amd import sampler
-    from duodiff_amd.engine import KnownRegion
-    ka, kb = sampler.known_rows(plan)
-    return KnownRegion(x0, mask, ka[k0:k1], kb[k0:k1])
-
-
 def _loop(kind, plan, m, x_in, stream, *, region=None, seed=5, use_graph=True, guidance=None, y=None, flags=0, cuts=(), noise="philox"):
     """the device loop of the plan's kind on model m, cut after the steps in cuts (h and the Philox counter carried); region: (x0, mask)
     -> (x, h, chains of the last call)"""
@@ -246,7 +226,7 @@ def _loop(kind, plan, m, x_in, stream, *, region=None, seed=5, use_graph=True, g
         with torch.cuda.stream(stream):
             for k0, k1 in zip(bounds[:-1], bounds[1:]):
                 kw = dict(y=y, seed=seed, noise=noise, use_graph=use_graph, stream=stream, guidance=guidance)
-                known = () if region is None else (_region(plan, *region, k0, k1),)
+                known = () if region is None else (known_region(plan, *region, k0, k1),)
                 seg = {k: v[k0:k1] for k, v in tab.items()}
                 if kind == "ddpm":
                     (engine.sample_region_loop if known else engine.sample_loop)(
@@ -269,30 +249,6 @@ def _counter(kind, plan, k):
     return int(plan.rows["t"][k]) if kind == "ddpm" else k
 
 
-def _philox_z(m, like, counter, seed, stream, y=None):
-    """the z of a step: a one-step dd_sample_affine with the row (0, 0, 1) returns 0 + 0 + 1 * z"""
-    from duodiff_amd.engine import sample_affine_loop
-    z = like.clone()
-    with torch.cuda.stream(stream):
-        sample_affine_loop(m.ctx, m, None, z, [500.0], [0.0], [0.0], [1.0], [1], y=y, seed=seed, counter_base=counter, noise="philox",
-                           use_graph=False, stream=stream)
-    stream.synchronize()
-    return z
-
-
-def _philox_z2(m, like, counter, seed, stream, y=None):
-    """the z2 of a step: a one-step region call with m = 1, x0 = 0, ka = 0, kb = 1 on the row (0, 0, 0) returns 1 * (0 + 1 * z2) + 0 * 0"""
-    from duodiff_amd.engine import KnownRegion, sample_affine_region_loop
-    z = like.clone()
-    B, _, S, _ = like.shape
-    reg = KnownRegion(torch.zeros_like(like), torch.ones(B, 1, S, S, device="cuda"), np.zeros(1, np.float32), np.ones(1, np.float32))
-    with torch.cuda.stream(stream):
-        sample_affine_region_loop(m.ctx, m, None, z, reg, [500.0], [0.0], [0.0], [0.0], [0], y=y, seed=seed, counter_base=counter,
-                                  noise="philox", use_graph=False, stream=stream)
-    stream.synchronize()
-    return z
-
-
 def _step_by_step(kind, plan, m, x_in, stream, region, *, seed=5, guidance=None, y=None, with_z2=True):
     """forward[_guided | _autoguided] + the existing unfused step + known_blend, z and z2 as the device loop draws them"""
     from duodiff_amd.engine import Autoguidance
@@ -302,8 +258,8 @@ def _step_by_step(kind, plan, m, x_in, stream, region, *, seed=5, guidance=None,
     x, h, eps = x_in.clone(), torch.zeros_like(x_in), torch.empty_like(x_in)
     for k in range(len(tab["t"])):
         t, ctr = float(tab["t"][k]), _counter(kind, plan, k)
-        z = _philox_z(m, x_in, ctr, seed, stream, y if m.mp.num_classes > 0 else None) if tab["noise"][k] else None
-        z2 = _philox_z2(m, x_in, ctr, seed, stream, y if m.mp.num_classes > 0 else None) if kb[k] != 0 and with_z2 else None
+        z = philox_z(m, x_in, ctr, seed, stream, y if m.mp.num_classes > 0 else None) if tab["noise"][k] else None
+        z2 = philox_z2(m, x_in, ctr, seed, stream, y if m.mp.num_classes > 0 else None) if kb[k] != 0 and with_z2 else None
         with torch.cuda.stream(stream):
             if isinstance(guidance, Autoguidance):
                 m.forward_autoguided(x, t, y, guidance.guide, guidance.scale, out=eps, stream=stream)
@@ -384,7 +340,7 @@ def test_zero_mask_equals_the_plain_loop(kind, guided):
     x0.fill_(float("nan"))
     y = torch.tensor([3, 7]).cuda() if guided else None
     guidance = (0.6, NULL) if guided else None
-    plan, st = _plan(kind), _stream()
+    plan, st = _plan(kind), side_stream()
     xp, hp, _ = _loop(kind, plan, m, x, st, y=y, guidance=guidance)
     xr, hr, _ = _loop(kind, plan, m, x, st, y=y, guidance=guidance, region=(x0, mask))
     assert torch.isfinite(xp).all() and not torch.equal(xp, x)
@@ -399,7 +355,7 @@ def test_one_mask_gives_the_known_image(kind):
     B = 2
     m = _model(B)
     x, x0, mask = _inputs(B, 32, mask=1.0)
-    st = _stream()
+    st = side_stream()
     plan = _plan(kind)
     xr, _, _ = _loop(kind, plan, m, x, st, region=(x0, mask))
     assert torch.equal(xr, x0), "the known pixels of the result are not x0"
@@ -408,7 +364,7 @@ def test_one_mask_gives_the_known_image(kind):
     ka, kb = sampler.known_rows(short)
     k = len(ka) - 1
     assert kb[k] > 0 and ka[k] < 1
-    z2 = _philox_z2(m, x, _counter(kind, short, k), 5, st)
+    z2 = philox_z2(m, x, _counter(kind, short, k), 5, st)
     want = ka[k] * x0.cpu().numpy() + kb[k] * z2.cpu().numpy()
     assert want.dtype == np.float32 and np.array_equal(xs.cpu().numpy(), want)
 
@@ -421,7 +377,7 @@ def test_loop_forms_agree(kind):
     m = _model(B)
     x, x0, mask = _inputs(B, 33)
     assert set(mask.unique().tolist()) == {0.0, 0.5, 1.0}
-    plan, st = _plan(kind), _stream()
+    plan, st = _plan(kind), side_stream()
     xg, hg, _ = _loop(kind, plan, m, x, st, region=(x0, mask), use_graph=True)
     xe, he, _ = _loop(kind, plan, m, x, st, region=(x0, mask), use_graph=False)
     xs, hs = _step_by_step(kind, plan, m, x, st, (x0, mask))
@@ -447,7 +403,7 @@ def test_two_chains_and_cut_loops(kind):
     B = 6
     m = _model(B)
     x, x0, mask = _inputs(B, 34)
-    plan, st = _plan(kind, n=7), _stream()
+    plan, st = _plan(kind, n=7), side_stream()
     x2, h2, c2 = _loop(kind, plan, m, x, st, region=(x0, mask), flags=L.DD_DEV_FORCE_CHAINS)
     x1, h1, c1 = _loop(kind, plan, m, x, st, region=(x0, mask), flags=L.DD_DEV_NO_CHAINS)
     assert (c2, c1) == (2, 1)
@@ -464,7 +420,7 @@ def test_guided_region_equals_the_steps(kind):
     m = _model(2 * B, num_classes=11)
     x, x0, mask = _inputs(B, 35)
     y = torch.randint(0, NULL, (B,), generator=torch.Generator().manual_seed(6)).cuda()
-    plan, st = _plan(kind, n=5), _stream()
+    plan, st = _plan(kind, n=5), side_stream()
     xg, hg, c = _loop(kind, plan, m, x, st, region=(x0, mask), y=y, guidance=(0.4, NULL), flags=L.DD_DEV_FORCE_CHAINS)
     xs, hs = _step_by_step(kind, plan, m, x, st, (x0, mask), y=y, guidance=(0.4, NULL))
     assert c == 2 and torch.isfinite(xg).all()
@@ -479,7 +435,7 @@ def test_autoguided_region_equals_the_steps(kind):
     B = 6
     guide, m = _model(B, seed=41, depth=1), _model(B, seed=42)
     x, x0, mask = _inputs(B, 36)
-    plan, st = _plan(kind, n=5), _stream()
+    plan, st = _plan(kind, n=5), side_stream()
     ag = Autoguidance(guide, 0.7)
     xg, hg, c = _loop(kind, plan, m, x, st, region=(x0, mask), guidance=ag, flags=L.DD_DEV_FORCE_CHAINS)
     xs, hs = _step_by_step(kind, plan, m, x, st, (x0, mask), guidance=ag)
@@ -495,10 +451,10 @@ def test_z2_is_independent_of_z():
     B = 2
     m = _model(B)
     x, _, _ = _inputs(B, 37)
-    st = _stream()
+    st = side_stream()
     zs, z2s = [], []
     for k in range(8):
-        z, z2 = _philox_z(m, x, k, 9, st), _philox_z2(m, x, k, 9, st)
+        z, z2 = philox_z(m, x, k, 9, st), philox_z2(m, x, k, 9, st)
         assert not torch.equal(z, z2)
         zs.append(z.cpu().numpy().ravel())
         z2s.append(z2.cpu().numpy().ravel())
@@ -509,7 +465,7 @@ def test_z2_is_independent_of_z():
     print(f"corr(z, z2) over {n} values: {r:.4f} (bound {5 / np.sqrt(n):.4f}); z2 mean {b.mean():.3f} std {b.std():.3f}")
     assert abs(r) < 5 / np.sqrt(n)
     assert abs(b.mean()) < 5 / np.sqrt(n) and abs(b.std() - 1) < 5 / np.sqrt(2 * n)     # N(0, 1): the mean's and the deviation's own spread
-    assert np.array_equal(_philox_z2(m, x, 3, 9, st).cpu().numpy().ravel(), z2s[3])     # a pure function of (seed, pixel, counter)
+    assert np.array_equal(philox_z2(m, x, 3, 9, st).cpu().numpy().ravel(), z2s[3])     # a pure function of (seed, pixel, counter)
 
 
 @gpu
@@ -517,7 +473,7 @@ def test_second_call_with_other_tensors():
     """A second call with another x0 / mask of the same shape gives that call's own step-by-step result, replaying the graphs of the first."""
     B = 2
     m = _model(B)
-    plan, st = _plan("affine"), _stream()
+    plan, st = _plan("affine"), side_stream()
     x, x0a, ma = _inputs(B, 38)
     _, x0b, _ = _inputs(B, 39)
     mb = (1 - ma).contiguous()
@@ -543,7 +499,7 @@ def test_poisoned_workspaces_and_history_with_a_region():
     """Both chains' workspaces NaN-poisoned before the call, on fresh models: == the clean run (multistep, chains forced)."""
     B = 6
     x, x0, mask = _inputs(B, 40)
-    plan, st = _plan("multistep", n=8), _stream()
+    plan, st = _plan("multistep", n=8), side_stream()
     outs = []
     for poison in (False, True):
         m = _model(B, seed=71)
@@ -566,7 +522,7 @@ def test_invalid_region_calls_are_rejected_before_anything_is_enqueued(kind):
     ee = Model(ctx, ModelParams.from_dict(dict(TINY)), B)
     ee.enable_early_exit("mlp_probe_per_layer")
     x_in, x0, mask = _inputs(B, 41)
-    plan, st = _plan(kind, n=3), _stream()
+    plan, st = _plan(kind, n=3), side_stream()
     tab = {k: np.ascontiguousarray(v, np.int32 if k in ("noise", "hist") else np.float32) for k, v in plan.rows.items()}
     ka, kb = np.ones(3, np.float32), np.zeros(3, np.float32)
     fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
@@ -617,7 +573,7 @@ def test_loop_rejections_keep_their_order():
     ee = Model(ctx, ModelParams.from_dict(dict(TINY)), B)
     ee.enable_early_exit("mlp_probe_per_layer")
     x_in, x0, mask = _inputs(B, 43)
-    x, h, st = x_in.clone(), torch.zeros_like(x_in), _stream()
+    x, h, st = x_in.clone(), torch.zeros_like(x_in), side_stream()
     tab = {k: np.ascontiguousarray(v, np.int32 if k in ("noise", "hist") else np.float32) for k, v in _plan("multistep", n=3).rows.items()}
     ka, kb = np.ones(3, np.float32), np.zeros(3, np.float32)
     fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
@@ -672,23 +628,23 @@ def test_fp32_engine_matches_the_oracle_with_a_half_image_mask():
     mp = ModelParams.from_dict(cfg)
     sd = synthetic_state_dict(mp, 61)
     orc = oracle.UViTOracle(mp.as_dict(), {k: v.numpy() for k, v in sd.items()})
-    em = _uvit(cfg, 61, "fp32", B).engine_model(B)
+    em = uvit(cfg, 61, "fp32", B)[0].engine_model(B)
     from duodiff_amd import sampler
     plan = sampler.step_plan(None, use_ddim=True, ddim_steps=9, ddim_eta=0.01)
     assert len(plan.rows["t"]) == 8
     ka, kb = sampler.known_rows(plan)
     xd, x0, mask = _inputs(B, 62, mask="half")
-    st = _stream()
+    st = side_stream()
     x, k0, mk = xd.cpu().numpy().astype(np.float64), x0.cpu().numpy().astype(np.float64), mask.cpu().numpy().astype(np.float64)
     r = plan.rows
     for k in range(8):
         eps = orc(x.astype(np.float32), np.full((B,), float(r["t"][k]), np.float32)).astype(np.float64)
         v = float(r["a"][k]) * x + float(r["b"][k]) * eps
         if r["noise"][k]:
-            v = v + float(r["c"][k]) * _philox_z(em, xd, k, 5, st).cpu().numpy().astype(np.float64)
+            v = v + float(r["c"][k]) * philox_z(em, xd, k, 5, st).cpu().numpy().astype(np.float64)
         kn = float(ka[k]) * k0
         if kb[k] != 0:
-            kn = kn + float(kb[k]) * _philox_z2(em, xd, k, 5, st).cpu().numpy().astype(np.float64)
+            kn = kn + float(kb[k]) * philox_z2(em, xd, k, 5, st).cpu().numpy().astype(np.float64)
         x = np.where(mk == 0, v, mk * kn + (1 - mk) * v)
     got, _, _ = _loop("affine", plan, em, xd, st, region=(x0, mask))
     err = float(np.abs(got.cpu().numpy() - x).max())
@@ -702,9 +658,9 @@ def test_celeba_width_two_real_chains():
     """embed_dim 512, depth 3, 64 x 64, B = 32 (two real chains), 3 DDPM steps in bf16 == forward + ddpm_step + known_blend."""
     from duodiff_amd import sampler
     B = 32
-    m = _uvit(load_config(CELEBA_3), 51, "bf16", B).engine_model(B)
+    m = uvit(load_config(CELEBA_3), 51, "bf16", B)[0].engine_model(B)
     x, x0, mask = _inputs(B, 42, S=64)
-    plan, st = sampler.step_plan("predict_noise", num_steps=3), _stream()
+    plan, st = sampler.step_plan("predict_noise", num_steps=3), side_stream()
     xg, _, chains = _loop("ddpm", plan, m, x, st, region=(x0, mask))
     xs, _ = _step_by_step("ddpm", plan, m, x, st, (x0, mask))
     xp, _, _ = _loop("ddpm", plan, m, x, st)
@@ -754,7 +710,7 @@ def test_cli_strength_equals_get_samples(tmp_path):
     x0 = rng.uniform(-1, 1, (3, 3, 8, 8)).astype(np.float32)
     np.save(tmp_path / "x0.npy", x0)
     s = _cli(tmp_path, "--use_ddim", "--ddim_steps", "8", "--init_image", str(tmp_path / "x0.npy"), "--strength", "0.5")
-    model = _uvit(dict(TINY), 91, "bf16", 3)
+    model = uvit(dict(TINY), 91, "bf16", 3)[0]
     kw = dict(model=model, batch_size=3, postprocessing=sampler.predict_noise_postprocessing, seed=5, num_channels=3, sample_height=8,
               sample_width=8, use_ddim=True, ddim_steps=8, noise="device")
     direct, _ = sampler.get_samples(**kw, init_image=x0, strength=0.5)

@@ -12,11 +12,9 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_support import bf16
+
 pytestmark = pytest.mark.gpu
-
-
-def _bf16(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(torch.bfloat16).to(torch.float32).numpy()
 
 
 def _layernorm(x, gb):
@@ -28,9 +26,9 @@ def _layernorm(x, gb):
 
 def _reference(h, w1, b1, w2, b2, x):
     from scipy.special import erf
-    s = _bf16(h).astype(np.float64) @ _bf16(w1).astype(np.float64).T + b1.astype(np.float64)
+    s = bf16(h).astype(np.float64) @ bf16(w1).astype(np.float64).T + b1.astype(np.float64)
     g = 0.5 * s * (1.0 + erf(s / np.sqrt(2.0)))                      # nn.GELU() default: exact erf
-    return x.astype(np.float64) + _bf16(g.astype(np.float32)).astype(np.float64) @ _bf16(w2).astype(np.float64).T + b2.astype(np.float64)
+    return x.astype(np.float64) + bf16(g.astype(np.float32)).astype(np.float64) @ bf16(w2).astype(np.float64).T + b2.astype(np.float64)
 
 
 @pytest.mark.parametrize("M,D,extras,ln,proj", [
@@ -56,7 +54,7 @@ def test_fused_mlp_against_float64_reference(M, D, extras, ln, proj):
     bp = (g.standard_normal(D, dtype=np.float32) * 0.2).astype(np.float32)
     x1 = x
     if proj:                                          # x1 = x + attn.proj(ao): what the MLP then normalises and adds to
-        x1 = (x.astype(np.float64) + _bf16(ao).astype(np.float64) @ _bf16(wp).astype(np.float64).T + bp.astype(np.float64)).astype(np.float32)
+        x1 = (x.astype(np.float64) + bf16(ao).astype(np.float64) @ bf16(wp).astype(np.float64).T + bp.astype(np.float64)).astype(np.float32)
     if ln:
         h = _layernorm(x1, ln_in)                     # what the kernel's prologue computes itself from x
     want = _reference(h, w1, b1, w2, b2, x1)
@@ -73,7 +71,7 @@ def test_fused_mlp_against_float64_reference(M, D, extras, ln, proj):
     assert np.isfinite(got).all()
     assert err.max() <= 1.5e-2 * max(scale, 0.1) and np.sqrt((err ** 2).mean()) <= 2e-3 * max(scale, 0.1)
     as_f32 = lambda u: torch.from_numpy(u.view(np.int16)).view(torch.bfloat16).to(torch.float32).numpy()
-    assert np.array_equal(as_f32(out), _bf16(got))    # the bf16 copy is the rounding of what was stored
+    assert np.array_equal(as_f32(out), bf16(got))    # the bf16 copy is the rounding of what was stored
     if ln:                                            # next block's norm1 of the updated rows, bf16
         assert np.abs(as_f32(hout) - _layernorm(got, ln_out)).max() <= 4e-2
 
@@ -103,7 +101,7 @@ def test_fused_layernorms_on_rows_with_a_large_common_offset(offset, sigma, proj
     bp = (g.standard_normal(D, dtype=np.float32) * 0.2).astype(np.float32)
     x1 = x
     if proj:
-        x1 = (x.astype(np.float64) + _bf16(ao).astype(np.float64) @ _bf16(wp).astype(np.float64).T + bp.astype(np.float64)).astype(np.float32)
+        x1 = (x.astype(np.float64) + bf16(ao).astype(np.float64) @ bf16(wp).astype(np.float64).T + bp.astype(np.float64)).astype(np.float32)
     h = _layernorm(x1, ln_in)
     want = _reference(h, w1, b1, w2, b2, x1)
     got, out, hout = x.copy(), np.zeros((M, D), np.uint16), np.zeros((M, D), np.uint16)
@@ -153,10 +151,10 @@ def test_fused_tail_with_next_skip_linear(M, D, extras):
     skip = (g.standard_normal((M, D), dtype=np.float32) * 1.2).astype(np.float32)
     ws = (g.standard_normal((D, 2 * D), dtype=np.float32) * 0.04).astype(np.float32)
     bs = (g.standard_normal(D, dtype=np.float32) * 0.2).astype(np.float32)
-    x1 = (x.astype(np.float64) + _bf16(ao).astype(np.float64) @ _bf16(wp).astype(np.float64).T + bp.astype(np.float64)).astype(np.float32)
+    x1 = (x.astype(np.float64) + bf16(ao).astype(np.float64) @ bf16(wp).astype(np.float64).T + bp.astype(np.float64)).astype(np.float32)
     y = _reference(_layernorm(x1, ln_in), w1, b1, w2, b2, x1)                      # float64
-    cat = np.concatenate([_bf16(y.astype(np.float32)), _bf16(skip)], axis=1).astype(np.float64)
-    want = cat @ _bf16(ws).astype(np.float64).T + bs.astype(np.float64)
+    cat = np.concatenate([bf16(y.astype(np.float32)), bf16(skip)], axis=1).astype(np.float64)
+    want = cat @ bf16(ws).astype(np.float64).T + bs.astype(np.float64)
     got, out, hout = x.copy(), np.zeros((M, D), np.uint16), np.zeros((M, D), np.uint16)
     P = lambda a: a.ctypes.data_as(C.c_void_p)
     ms = C.c_float(0)
@@ -212,8 +210,8 @@ def test_fused_tail_with_next_qkv(M, D, extras, skip):
                                  P(ao), P(wp), P(bp), P(sk) if skip else None, P(ws) if skip else None, P(bs) if skip else None, P(wq), P(qkv)))
     assert np.isfinite(got).all()
     as_f32 = lambda u: torch.from_numpy(u.view(np.int16)).view(torch.bfloat16).to(torch.float32).numpy()
-    h = _bf16(_layernorm(got, ln_out)).astype(np.float64)                        # norm1 of the rows the launch stored, rounded as the operand is
-    want = h @ _bf16(wq).astype(np.float64).T                                    # [M, 3D]
+    h = bf16(_layernorm(got, ln_out)).astype(np.float64)                        # norm1 of the rows the launch stored, rounded as the operand is
+    want = h @ bf16(wq).astype(np.float64).T                                    # [M, 3D]
     q = as_f32(qkv).reshape(B, 3 * H, Lp, 64)                                    # head-major -> [M, 3D]
     have = q[:, :, :L, :].transpose(0, 2, 1, 3).reshape(M, 3 * D)
     err = np.abs(have - want)

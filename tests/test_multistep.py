@@ -18,6 +18,7 @@ from conftest import REPO, TINY
 from duodiff_amd import _lib as L
 from duodiff_amd.config import ModelParams, load_config
 from duodiff_amd.weights import synthetic_state_dict
+from loop_support import cli_argv, engine_pair, philox_z, side_stream, uvit
 
 gpu = pytest.mark.gpu
 CELEBA, CELEBA_3 = REPO / "configs" / "uvit_celeba.yaml", REPO / "configs" / "uvit_celeba_3.yaml"
@@ -169,8 +170,7 @@ def test_rows_grid_and_flags():
 
 
 def _argv(*extra):
-    return ["--checkpoint_path", "/nonexistent.pth", "--batch_size", "2", "--parametrization", "predict_noise",
-            "--output_folder", "/tmp/unused", "--config_path", str(CELEBA), *extra]
+    return cli_argv(CELEBA, *extra)
 
 
 def test_cli_solver_options_and_defaults():
@@ -220,39 +220,19 @@ NULL = 10
 TINY_COND = dict(TINY, num_classes=11)
 
 
-def _uvit(cfg, seed, precision, max_batch):
-    from duodiff_amd.uvit import UViT
-    mp = ModelParams.from_dict(cfg)
-    m = UViT(**mp.as_dict(), precision=precision, max_batch=max_batch)
-    m.load_state_dict(synthetic_state_dict(mp, seed))
-    return m.eval().to("cuda"), mp
-
-
-def _pair(cfg_s, cfg_f, seeds, max_batch, precision="bf16"):
-    m_s, _ = _uvit(cfg_s, seeds[0], precision, max_batch)
-    m_f, mp = _uvit(cfg_f, seeds[1], precision, max_batch)
-    return m_s.engine_model(max_batch), m_f.engine_model(max_batch), mp
-
-
 def _tiny_pair(max_batch, seeds=(41, 42), **kw):
-    return _pair(dict(TINY, depth=1, **kw), dict(TINY, depth=3, **kw), seeds, max_batch)
+    return engine_pair(dict(TINY, depth=1, **kw), dict(TINY, depth=3, **kw), seeds, max_batch)
 
 
 @pytest.fixture(scope="module")
 def celeba_pair():
-    return _pair(load_config(CELEBA_3), load_config(CELEBA), (51, 52), 32)
+    return engine_pair(load_config(CELEBA_3), load_config(CELEBA), (51, 52), 32)
 
 
 def _rows(kind="sde-dpmsolver++", n=20, order=2, steps=None):
     from duodiff_amd import sampler
     r = sampler.multistep_coefficients(kind, sampler.multistep_grid(n), order)
     return r if steps is None else {k: v[:steps] for k, v in r.items()}
-
-
-def _stream():
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    return s
 
 
 def _loop(es, ef, x0, rows, stream, *, switch_after=None, seed=5, use_graph=True, guidance=None, y=None, h0=None, flags=0, cuts=()):
@@ -279,24 +259,13 @@ def _loop(es, ef, x0, rows, stream, *, switch_after=None, seed=5, use_graph=True
     return x, h, chains
 
 
-def _philox_z(es, x0, t, k, seed, stream, y=None):
-    """the z the device loop draws at step k: a one-step dd_sample_affine with the row (0, 0, 1) returns exactly 0 + 0 + 1 * z"""
-    from duodiff_amd.engine import sample_affine_loop
-    z = x0.clone()
-    with torch.cuda.stream(stream):
-        sample_affine_loop(es.ctx, es, None, z, [t], [0.0], [0.0], [1.0], [1], y=y, seed=seed, counter_base=k, noise="philox",
-                           use_graph=False, stream=stream)
-    stream.synchronize()
-    return z
-
-
 def _host_loop(es, ef, x0, rows, stream, *, switch_after=None, seed=5, guidance=None, y=None):
     """step by step: dd_forward[_guided] + dd_multistep_step, z from _philox_z"""
     ctx = es.ctx
     x, h, eps = x0.clone(), torch.zeros_like(x0), torch.empty_like(x0)
     for k in range(len(rows["t"])):
         t = float(rows["t"][k])
-        z = _philox_z(es, x0, t, k, seed, stream, y) if rows["noise"][k] else None
+        z = philox_z(es, x0, k, seed, stream, y, t=t) if rows["noise"][k] else None
         m = ef if (switch_after is not None and k >= switch_after) else es
         with torch.cuda.stream(stream):
             if guidance is None:
@@ -351,7 +320,7 @@ def test_loop_forms_agree(kind):
     es, ef, _ = _tiny_pair(max_batch=B)
     x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(2)).cuda()
     rows = _rows(kind, n=10)
-    st = _stream()
+    st = side_stream()
     xg, hg, _ = _loop(es, ef, x0, rows, st, switch_after=4, use_graph=True)
     xe, he, _ = _loop(es, ef, x0, rows, st, switch_after=4, use_graph=False)
     xm, hm = _host_loop(es, ef, x0, rows, st, switch_after=4)
@@ -371,7 +340,7 @@ def test_two_chains_equal_one_chain(case, request):
         es, ef, _ = request.getfixturevalue("celeba_pair")
     x0 = torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(3)).cuda()
     rows = _rows("sde-dpmsolver++", n=20, steps=8)
-    st = _stream()
+    st = side_stream()
     x2, h2, c2 = _loop(es, ef, x0, rows, st, switch_after=5, flags=force)
     x1, h1, c1 = _loop(es, ef, x0, rows, st, switch_after=5, flags=L.DD_DEV_NO_CHAINS)
     assert (c2, c1) == (2, 1)
@@ -391,7 +360,7 @@ def test_cut_loop_equals_the_uncut_loop(case, request):
         es, ef, _ = request.getfixturevalue("celeba_pair")
     x0 = torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(4)).cuda()
     rows = _rows("sde-dpmsolver++", n=12)
-    st = _stream()
+    st = side_stream()
     xu, hu, _ = _loop(es, ef, x0, rows, st, switch_after=6, flags=force)
     xc, hc, _ = _loop(es, ef, x0, rows, st, switch_after=6, flags=force, cuts=(3, 6, 7))
     assert torch.isfinite(xu).all() and torch.equal(xu, xc) and torch.equal(hu, hc), "a cut loop differs from the uncut loop"
@@ -406,7 +375,7 @@ def test_guided_multistep(S):
     es, ef, _ = _tiny_pair(max_batch=2 * B, num_classes=11, img_size=S)
     x0 = torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(5)).cuda()
     y = torch.randint(0, NULL, (B,), generator=torch.Generator().manual_seed(6)).cuda()
-    st = _stream()
+    st = side_stream()
     rows = _rows("sde-dpmsolver++", n=10)
     xu, hu, cu = _loop(es, ef, x0, rows, st, switch_after=3, y=y, flags=L.DD_DEV_FORCE_CHAINS)
     x0g, h0g, cg = _loop(es, ef, x0, rows, st, switch_after=3, y=y, guidance=(0.0, NULL), flags=L.DD_DEV_FORCE_CHAINS)
@@ -438,7 +407,7 @@ def test_ddim_rows_reproduce_the_affine_loop(case, request):
     tables = {"ddim": ([float(t) for t, _ in pairs], [sampler.affine_coefficients("ddim", t, s, 0.0) for t, s in pairs], [0] * 10),
               "predict_original": ([float(t) for t in range(999, 989, -1)],
                                    [sampler.affine_coefficients("predict_original", t) for t in range(999, 989, -1)], [1] * 10)}
-    st = _stream()
+    st = side_stream()
     for name, (t, co, nz) in tables.items():
         n = len(t)
         rows = dict(t=t, a=[c[0] for c in co], b=[c[1] for c in co], c=[c[2] for c in co], noise=nz, d=np.zeros(n), p=np.zeros(n),
@@ -469,7 +438,7 @@ def test_affine_and_multistep_calls_do_not_share_graphs():
     rows = _rows("dpmsolver++", n=10)
     co = [sampler.affine_coefficients("ddim", int(t), int(s), 0.0)
           for t, s in zip(sampler.multistep_grid(10)[:-1], sampler.multistep_grid(10)[1:])]
-    st = _stream()
+    st = side_stream()
 
     def affine(es, ef):
         x = x0.clone()
@@ -500,7 +469,7 @@ def test_poisoned_workspaces_and_history():
     B = 6
     x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(10)).cuda()
     rows = _rows("sde-dpmsolver++", n=10)
-    st = _stream()
+    st = side_stream()
     outs = []
     for poison in (False, True):
         es, ef, _ = _tiny_pair(max_batch=B, seeds=(71, 72))
@@ -526,7 +495,7 @@ def test_invalid_multistep_calls_are_rejected_before_anything_is_enqueued():
     ee.enable_early_exit("mlp_probe_per_layer")
     x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(11)).cuda()
     rows = _rows("dpmsolver++", n=3)
-    st = _stream()
+    st = side_stream()
     n0 = lib.dd_dev_graph_captures(ctx.handle)
     f = lambda k: np.ascontiguousarray(rows[k], np.float32)
     i = lambda k: np.ascontiguousarray(rows[k], np.int32)
@@ -571,7 +540,7 @@ def test_fp32_engine_matches_the_oracle_driven_by_the_float64_solver():
         m = orc(x.astype(np.float32), np.full((B,), float(ts[k]), np.float32)).astype(np.float64)
         v = r64["a"][k] * x + r64["b"][k] * m + (r64["d"][k] * h if r64["hist"][k] else 0.0)
         h, x = r64["p"][k] * x + r64["q"][k] * m, v
-    m32, _ = _uvit(cfg, 61, "fp32", B)
+    m32, _ = uvit(cfg, 61, "fp32", B)
     em = m32.engine_model(B)
     xd, hd = x0.cuda(), torch.zeros(B, 3, 8, 8, device="cuda")
     sample_multistep_loop(em.ctx, em, None, xd, hd, sampler.multistep_coefficients("dpmsolver++", ts, 2), noise="none")

@@ -24,12 +24,14 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_support
 from conftest import REPO, TINY
 from duodiff_amd import _lib as L
 from duodiff_amd.config import ModelParams, load_config
 from duodiff_amd.weights import synthetic_state_dict
-from test_autoguidance import KINDS, _affine_rows, _flags, _ms_rows, _run, _stream, _uvit, _x0, eps_rms_bound
-from test_gemm_path import FP32_REL, bf16, from_bf16_bits, gate, ulp_bf16
+from kernel_support import FP32_REL, NAN16, P, bf16, from_bf16_bits, gate, ulp_bf16
+from loop_support import cli_argv, engine_pair, eps_rms_bound, side_stream, uvit
+from test_autoguidance import KINDS, _affine_rows, _flags, _ms_rows, _run, _x0
 from test_row_kernels import ln_rows, ln_tolerances
 
 gpu = pytest.mark.gpu
@@ -37,33 +39,27 @@ gpu = pytest.mark.gpu
 CONFIGS = REPO / "configs"
 CELEBA = CONFIGS / "uvit_celeba.yaml"
 CELEBA_3 = CONFIGS / "uvit_celeba_3.yaml"
-NAN16 = 0xFFFF
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
-def _argv(config, *extra):
-    return ["--checkpoint_path", "/nonexistent.pth", "--batch_size", "2", "--parametrization", "predict_noise",
-            "--output_folder", "/tmp/unused", "--config_path", str(config), *extra]
-
-
 def test_cli_pag_options_and_defaults():
     from duodiff_amd import sampler
     cfg, cfg3 = load_config(CELEBA), load_config(CELEBA_3)
-    a = sampler.get_args(_argv(CELEBA))
+    a = sampler.get_args(cli_argv(CELEBA))
     assert a.pag_scale is None and a.pag_layers is None and a.pag_layers_first is None
     assert sampler.validate_pag(a, cfg) is None
-    a = sampler.get_args(_argv(CELEBA, "--pag_scale", "3"))
+    a = sampler.get_args(cli_argv(CELEBA, "--pag_scale", "3"))
     assert a.pag_scale == 3.0
     assert sampler.validate_pag(a, cfg) == (3.0, [6], [])                      # depth 13: mid = block 6
-    a = sampler.get_args(_argv(CELEBA, "--pag_scale", "0"))
+    a = sampler.get_args(cli_argv(CELEBA, "--pag_scale", "0"))
     assert a.pag_scale == 0.0 and a.pag_scale is not None                      # 0 selects the path too
     assert sampler.validate_pag(a, cfg)[0] == 0.0
-    a = sampler.get_args(_argv(CELEBA, "--pag_scale", "1.5", "--pag_layers", "5", "mid", "7"))
+    a = sampler.get_args(cli_argv(CELEBA, "--pag_scale", "1.5", "--pag_layers", "5", "mid", "7"))
     assert sampler.validate_pag(a, cfg) == (1.5, [5, 6, 7], [])
     # a pair: --pag_layers is the late model's, --pag_layers_first the first model's, both default to their own mid
-    a = sampler.get_args(_argv(CELEBA_3, "--pag_scale", "2"))
+    a = sampler.get_args(cli_argv(CELEBA_3, "--pag_scale", "2"))
     assert sampler.validate_pag(a, cfg3, cfg) == (2.0, [1], [6])
-    a = sampler.get_args(_argv(CELEBA_3, "--pag_scale", "2", "--pag_layers", "0", "12", "--pag_layers_first", "2"))
+    a = sampler.get_args(cli_argv(CELEBA_3, "--pag_scale", "2", "--pag_layers", "0", "12", "--pag_layers_first", "2"))
     assert sampler.validate_pag(a, cfg3, cfg) == (2.0, [2], [0, 12])
     from duodiff_amd.engine import layer_mask
     assert layer_mask([0, 12]) == 0x1001 and layer_mask([]) == 0 and layer_mask(5) == 5
@@ -88,7 +84,7 @@ def test_cli_pag_options_and_defaults():
 def test_validate_pag_rejects_before_any_gpu_work(config, extra, match):
     """validate_pag against the YAML alone: no model is built, no GPU is touched (this runs on the CPU box)."""
     from duodiff_amd import sampler
-    args = sampler.get_args(_argv(CONFIGS / config, *extra))
+    args = sampler.get_args(cli_argv(CONFIGS / config, *extra))
     with pytest.raises(ValueError, match=match):
         sampler.validate_pag(args, load_config(CONFIGS / config))
 
@@ -100,14 +96,14 @@ def test_validate_pag_rejects_before_any_gpu_work(config, extra, match):
 ])
 def test_validate_pag_rejects_a_pair(extra, match):
     from duodiff_amd import sampler
-    args = sampler.get_args(_argv(CELEBA_3, "--checkpoint_path_late", "/nonexistent.pth", "--config_path_late", str(CELEBA), *extra))
+    args = sampler.get_args(cli_argv(CELEBA_3, "--checkpoint_path_late", "/nonexistent.pth", "--config_path_late", str(CELEBA), *extra))
     with pytest.raises(ValueError, match=match):
         sampler.validate_pag(args, load_config(CELEBA_3), load_config(CELEBA))
 
 
 def test_cli_main_rejects_pag_options_before_it_builds_a_model(tmp_path):
     from duodiff_amd import sampler
-    argv = _argv(CELEBA, "--pag_scale", "1", "--pag_layers", "13")
+    argv = cli_argv(CELEBA, "--pag_scale", "1", "--pag_layers", "13")
     argv[argv.index("--output_folder") + 1] = str(tmp_path / "out")
     with pytest.raises(ValueError, match="outside"):
         sampler.main(argv)
@@ -155,15 +151,6 @@ def test_the_kernel_gates_reject_a_wrong_v():
 
 
 # ---- GPU, kernels -----------------------------------------------------------------------------------------------------------
-def _ctx():
-    from duodiff_amd.engine import Context
-    return Context.get()
-
-
-def P(a):
-    return None if a is None else a.ctypes.data
-
-
 def _v_ref(h, w, bias, D):
     """float64 v = h . Wv^T + bv of operands that are already bf16 values, and the bound of its bf16 result: half an ulp + 2^-16 of the sum
     of magnitudes"""
@@ -189,7 +176,7 @@ def _v_case(D, B, E, with_bias, seed, offset=0.0):
 
 
 def _run_v_identity(B, E, H, h, w, bias, xres, ln):
-    ctx = _ctx()
+    ctx = kernel_support.ctx()
     D, L_ = 64 * H, 256 + E
     out = np.full((B * L_ + 8, D), 0xA5A5, np.uint16)
     st = ctx.lib.dd_dev_v_identity(ctx.handle, B, L_, H, E, P(h), P(w), P(bias), P(xres), P(ln), P(out), 0, None, C.byref(C.c_float(0)))
@@ -200,7 +187,7 @@ def _check_v_identity(D, B, E, with_bias, seed, offset=0.0):
     H, L_ = D // 64, 256 + E
     h, w, bias, xres, ln = _v_case(D, B, E, with_bias, seed, offset)
     st, out = _run_v_identity(B, E, H, h, w, bias, xres, ln)
-    assert st == L.DD_OK, _ctx().lib.dd_last_error(_ctx().handle).decode()
+    assert st == L.DD_OK, kernel_support.ctx().lib.dd_last_error(kernel_support.ctx().handle).decode()
     assert (out[B * L_:] == NAN16).all(), "canary rows behind the output were written"
     got = from_bf16_bits(out[:B * L_]).astype(np.float64)
     assert np.isfinite(got).all(), "a row the kernel must not read (NaN on the device) reached the output"
@@ -250,7 +237,7 @@ def test_v_identity_an_image_does_not_depend_on_its_batch():
 
 @gpu
 def test_v_identity_refuses_what_it_does_not_support():
-    ctx = _ctx()
+    ctx = kernel_support.ctx()
     h, w, bias, xres, ln = _v_case(512, 1, 1, False, 3)
     for B, L_, H, E in ((1, 257, 4, 1), (1, 256, 8, 1), (1, 259, 8, 3), (1, 258, 8, 1)):
         out = np.full((B * L_ + 8, 64 * H), 0xA5A5, np.uint16)
@@ -266,7 +253,7 @@ def test_v_identity_refuses_what_it_does_not_support():
 @pytest.mark.parametrize("L_", [17, 18, 257, 258])
 @pytest.mark.parametrize("prec", ["bf16", "fp32"])
 def test_v_copy_is_bit_equal_to_v(prec, L_, B, H):
-    ctx = _ctx()
+    ctx = kernel_support.ctx()
     D = 64 * H
     r = np.random.default_rng(7 * L_ + B + H)
     qkv = r.standard_normal((B, 3, H, L_, 64), dtype=np.float32)
@@ -286,7 +273,7 @@ def test_v_copy_is_bit_equal_to_v(prec, L_, B, H):
 
 @gpu
 def test_v_copy_refuses_a_long_sequence():
-    ctx = _ctx()
+    ctx = kernel_support.ctx()
     qkv = np.zeros((1, 3, 1, 289, 64), np.float32)
     out = np.full((289 + 8, 64), 0xA5A5, np.uint16)
     st = ctx.lib.dd_dev_v_copy(ctx.handle, 0, 1, 289, 1, P(qkv), P(out), 0, None, C.byref(C.c_float(0)))
@@ -354,8 +341,8 @@ def test_forward_perturbed_vs_oracle(monkeypatch, case, mask):
     moved = float(np.sqrt(((pert - plain) ** 2).mean())) / sigma
     assert moved >= 0.05, "the oracle's own perturbation is too small to test anything"
     for prec in ("fp32", "bf16"):
-        m, _ = _uvit(cfg, 61, prec, max_batch=2 * B)
-        with _flags(_ctx(), flags):
+        m, _ = uvit(cfg, 61, prec, max_batch=2 * B)
+        with _flags(kernel_support.ctx(), flags):
             em = m.engine_model(2 * B)
         yd = None if y is None else y.cuda()
         got = em.forward_perturbed(x.cuda(), t, yd, s, layers).cpu().numpy().astype(np.float64)
@@ -384,7 +371,7 @@ def test_mask_zero_equals_dd_forward(case):
     x = torch.randn(B, mp.in_chans, mp.img_size, mp.img_size, generator=g).cuda()
     y = torch.randint(0, 11, (B,), generator=g).cuda() if mp.num_classes > 0 else None
     for prec in ("bf16", "fp32"):
-        m, _ = _uvit(cfg, 63, prec, max_batch=2 * B)
+        m, _ = uvit(cfg, 63, prec, max_batch=2 * B)
         em = m.engine_model(2 * B)
         base = em.forward(x, 400.0, y)
         for s in (0.0, 1.7, -3.0):
@@ -393,18 +380,12 @@ def test_mask_zero_equals_dd_forward(case):
         del em, m
 
 
-def _pair(cfg_s, cfg_f, seeds, max_batch, precision="bf16"):
-    ms, _ = _uvit(cfg_s, seeds[0], precision, max_batch)
-    mf, _ = _uvit(cfg_f, seeds[1], precision, max_batch)
-    return ms.engine_model(max_batch), mf.engine_model(max_batch)
-
-
 def _tiny_pair(seeds=(41, 42), max_batch=12):
-    return _pair(dict(TINY, depth=1), dict(TINY, depth=3), seeds, max_batch)
+    return engine_pair(dict(TINY, depth=1), dict(TINY, depth=3), seeds, max_batch)[:2]
 
 
 def _celeba_pair(max_batch):
-    return _pair(load_config(CELEBA_3), load_config(CELEBA), (51, 52), max_batch)
+    return engine_pair(load_config(CELEBA_3), load_config(CELEBA), (51, 52), max_batch)[:2]
 
 
 @gpu
@@ -422,7 +403,7 @@ def test_scale_zero_equals_the_unguided_loop(case, kind):
         B, S, n, sw, flags = 32, 64, 3, 1, 0
         es, ef = _celeba_pair(max_batch=2 * B)
         full = Perturbed(0.0, [0, 1, 2], list(range(13)))
-    ctx, x0, stream = es.ctx, _x0(B, 3, S, 7), _stream()
+    ctx, x0, stream = es.ctx, _x0(B, 3, S, 7), side_stream()
     outs = {}
     with _flags(ctx, flags):
         for name, guidance in (("unguided", None), ("scale0", full)):
@@ -441,7 +422,7 @@ def test_perturbed_loops_equal_manual_steps(kind):
     from duodiff_amd.engine import Perturbed
     B, s, n, sw = 4, 1.7, 8, 3
     es, ef = _tiny_pair(max_batch=2 * B)
-    ctx, x0, stream = ef.ctx, _x0(B, 3, 8, 11), _stream()
+    ctx, x0, stream = ef.ctx, _x0(B, 3, 8, 11), side_stream()
     pag = Perturbed(s, [0], [1, 2])
     loops = [_run(kind, ctx, es, ef, x0, stream, switch=sw, n=n, noise="none", use_graph=ug, guidance=pag) for ug in (True, False)]
     plain = _run(kind, ctx, es, ef, x0, stream, switch=sw, n=n, noise="none", guidance=None)
@@ -475,7 +456,7 @@ def test_perturbed_two_chains_equal_one_chain(kind):
     from duodiff_amd.engine import Perturbed
     B = 6
     es, ef = _tiny_pair(max_batch=2 * B)
-    ctx, x0, stream = es.ctx, _x0(B, 3, 8, 13), _stream()
+    ctx, x0, stream = es.ctx, _x0(B, 3, 8, 13), side_stream()
     pag = Perturbed(0.4, [0], [1])
     outs = {}
     for name, flags in (("chained", L.DD_DEV_FORCE_CHAINS), ("single", L.DD_DEV_NO_CHAINS)):
@@ -492,7 +473,7 @@ def test_a_new_mask_or_scale_is_not_a_stale_graph():
     """Calls with (scale, first mask, late mask) changing one at a time on the same models: each equals a run of freshly built models"""
     from duodiff_amd.engine import Perturbed
     B = 4
-    x0, stream = _x0(B, 3, 8, 15), _stream()
+    x0, stream = _x0(B, 3, 8, 15), side_stream()
     settings = [Perturbed(0.4, [0], [1]), Perturbed(1.0, [0], [1]), Perturbed(1.0, [0], [2]), Perturbed(1.0, [], [2]), Perturbed(0.4, [0], [1])]
 
     def run(es, ef, pag):
@@ -518,10 +499,10 @@ def test_perturbed_loop_reads_no_stale_workspace_bytes():
     path that reads the qkv tensor (tiny) and on the one that reads norm1 in fragment order (embed_dim 512)"""
     from duodiff_amd.engine import Perturbed
     for cfg_s, cfg_f, B, S, n in ((dict(TINY, depth=1), dict(TINY, depth=3), 6, 8, 6), (dict(QA512, depth=1), QA512, 2, 64, 2)):
-        x0, stream = _x0(B, 3, S, 17), _stream()
+        x0, stream = _x0(B, 3, S, 17), side_stream()
         outs = []
         for poison in (False, True):
-            es, ef = _pair(cfg_s, cfg_f, (71, 72), 2 * B)
+            es, ef, _ = engine_pair(cfg_s, cfg_f, (71, 72), 2 * B)
             ctx = es.ctx
             with _flags(ctx, L.DD_DEV_FORCE_CHAINS):
                 if poison:
@@ -544,15 +525,15 @@ def test_invalid_perturbed_calls_are_rejected_before_anything_is_enqueued():
     B = 4
     es, ef = _tiny_pair(max_batch=2 * B)                        # depths 1 and 3
     ctx, lib = es.ctx, es.ctx.lib
-    small, _ = _uvit(dict(TINY, depth=1), 81, "bf16", max_batch=B)          # room for B rows only
+    small, _ = uvit(dict(TINY, depth=1), 81, "bf16", max_batch=B)          # room for B rows only
     es_small = small.engine_model(B)
-    cond, _ = _uvit(dict(TINY_COND, depth=1), 82, "bf16", 2 * B)
+    cond, _ = uvit(dict(TINY_COND, depth=1), 82, "bf16", 2 * B)
     ec = cond.engine_model(2 * B)
     ee = Model(ctx, ModelParams.from_dict(TINY), 2 * B)
     ee.enable_early_exit("mlp_probe_per_layer")
     x0 = _x0(B, 3, 8, 19)
     y = torch.randint(0, 10, (B,), generator=torch.Generator().manual_seed(20)).cuda()
-    stream = _stream()
+    stream = side_stream()
     # (first, late, (scale, first mask, late mask) or None, labels, message)
     cases = [(es, None, None, None, "null dd_pag"), (es, None, (float("inf"), 1, 0), None, "finite"), (es, None, (float("nan"), 1, 0), None, "finite"),
              (es, None, (0.4, 2, 0), None, "depth"), (es, ef, (0.4, 1, 8), None, "depth"), (es_small, None, (0.4, 1, 0), None, "max_batch"),
@@ -609,8 +590,8 @@ def test_get_samples_with_pag_runs_every_sampler():
     """get_samples(pag=...) through the one step plan: DDPM (cut short), DDIM and DPM-Solver++ on a pair, device noise and the step-by-step
     torch_cpu path; scale 0 equals the run without the option (device noise), a scale moves the samples"""
     from duodiff_amd import sampler
-    ms, _ = _uvit(dict(TINY, depth=1), 91, "bf16", None)
-    mf, _ = _uvit(dict(TINY, depth=3), 92, "bf16", None)
+    ms, _ = uvit(dict(TINY, depth=1), 91, "bf16", None)
+    mf, _ = uvit(dict(TINY, depth=3), 92, "bf16", None)
     common = dict(batch_size=3, postprocessing=sampler.predict_noise_postprocessing, seed=3, num_channels=3, sample_height=8, sample_width=8,
                   late_model=mf, t_switch=4)
     for kw in (dict(num_steps=8), dict(use_ddim=True, ddim_steps=6), dict(solver="dpmsolver++", solver_steps=6)):

@@ -42,9 +42,9 @@ import ctypes as C
 
 import numpy as np
 import pytest
-import torch
 
-from test_attention import BF16_MARGIN, BF16_UNIT, bf16, emulate_bf16, from_bf16_bits, gate, reference, rows
+from kernel_support import bf16, from_bf16_bits, gate
+from test_attention import BF16_MARGIN, BF16_UNIT, emulate_bf16, reference, rows
 
 gpu = pytest.mark.gpu
 MARGIN = 2.0          # the two bf16 roundings' analytic bound, in units of 2^-8 A (the docstring: why BF16_MARGIN = 1.75 cannot hold on these cases)
@@ -59,16 +59,12 @@ def tolerance(A):
     return np.maximum(MARGIN * BF16_UNIT * A, FLOOR)
 
 
-def _bf16(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(torch.bfloat16).to(torch.float32).numpy()
-
-
 def _reference(h, w, bias, B, L, H):
     D = 64 * H
-    qkv = _bf16(h).astype(np.float64) @ _bf16(w).astype(np.float64).T
+    qkv = bf16(h).astype(np.float64) @ bf16(w).astype(np.float64).T
     if bias is not None:
         qkv = qkv + bias.astype(np.float64)
-    qkv = _bf16(qkv.astype(np.float32)).astype(np.float64).reshape(B, L, 3, H, 64)     # "B L (K H D) -> K B H L D"
+    qkv = bf16(qkv.astype(np.float32)).astype(np.float64).reshape(B, L, 3, H, 64)     # "B L (K H D) -> K B H L D"
     q, k, v = (qkv[:, :, i].transpose(0, 2, 1, 3) for i in range(3))
     s = q @ k.transpose(0, 1, 3, 2) * 0.125
     p = np.exp(s - s.max(-1, keepdims=True))

@@ -19,48 +19,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import kernel_support
+from kernel_support import NAN16, NAN32, PREC_BF16, PREC_FP32, P, bf16, from_bf16_bits, gate, round_up, to_frag, unfrag
+
 gpu = pytest.mark.gpu
 
-PREC_BF16, PREC_FP32 = 0, 1
-NAN32, NAN16 = 0xFFFFFFFF, 0xFFFF
 LN_OFFSETS = [(0.0, 1.0), (100.0, 1.0), (-1000.0, 2.0), (2000.0, 0.5)]
-
-
-# ---------------------------------------------------------------------------------------------------------------- host helpers
-def bf16(a):
-    """fp32 -> bf16 (round to nearest even) -> fp32, as host_f2bf"""
-    u = np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)
-    return (((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint32) << 16).view(np.float32)
-
-
-def from_bf16_bits(b):
-    return (np.ascontiguousarray(b, np.uint16).astype(np.uint32) << 16).view(np.float32)
-
-
-def round_up(v, m):
-    return (v + m - 1) // m * m
-
-
-def gate(got, want, tol, what):
-    """elementwise |got - want| <= tol; NaN fails.  Returns the largest error / bound ratio."""
-    got = np.asarray(got, np.float64)
-    tol = np.broadcast_to(np.asarray(tol, np.float64), want.shape)
-    err = np.abs(got - want)
-    bad = ~(err <= tol)
-    if bad.any():
-        i = tuple(np.argwhere(bad)[0])
-        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.size} elements out of bound; first at {i}: got {got[i]!r}, want {want[i]!r}, "
-                             f"bound {tol[i]!r}")
-    return float((err / np.maximum(tol, 1e-300)).max())
-
-
-def _ctx():
-    from duodiff_amd.engine import Context
-    return Context.get()
-
-
-def P(a):
-    return None if a is None else a.ctypes.data
 
 
 # ---------------------------------------------------------------------------------------------------------------- LayerNorm
@@ -95,7 +59,7 @@ def ln_rows(rows, D, offset, sigma, seed):
 
 def run_layernorm(prec, x, g, b, frag=False, tok=(0, 0)):
     """dd_dev_layernorm; returns (status, out [rows + 8, D] as stored, frag [rows + 8, D] bf16 bits or None)"""
-    ctx = _ctx()
+    ctx = kernel_support.ctx()
     rows, D = x.shape
     out = np.full((rows + 8, D), 0xA5A5 if prec == PREC_BF16 else 0xA5A5A5A5, np.uint16 if prec == PREC_BF16 else np.uint32)
     fr = np.full((rows + 8, D), 0xA5A5, np.uint16) if frag else None
@@ -103,22 +67,6 @@ def run_layernorm(prec, x, g, b, frag=False, tok=(0, 0)):
     st = ctx.lib.dd_dev_layernorm(ctx.handle, prec, rows, D, P(np.ascontiguousarray(x)), P(gb), P(out), P(fr), tok[0], tok[1], 0, None,
                                   C.byref(C.c_float(0)))
     return st, out, fr
-
-
-def unfrag(fr, groups, D):
-    """the permutation of layernorm_kernel's comment undone: [32-row group][D / 16 k-steps][64 lanes] x 8 bf16 -> [groups 32, D] rows; column c of
-    row n of a group sits at k-step c / 16, lane (n & 31) + 32 ((c / 8) & 1), element c & 7"""
-    f = fr.reshape(-1)[: groups * (D // 16) * 64 * 8].reshape(groups, D // 16, 2, 32, 8)       # [grp][ks][lane >> 5][lane & 31][i]
-    return f.transpose(0, 3, 1, 2, 4).reshape(groups * 32, D)
-
-
-def to_frag(rows_, D, swap_halves=False):
-    """the inverse of unfrag (rows [groups 32, D] -> fragment order); swap_halves: the bug of a store that exchanges the two lane halves"""
-    groups = rows_.shape[0] // 32
-    f = rows_.reshape(groups, 32, D // 16, 2, 8).transpose(0, 2, 3, 1, 4)
-    if swap_halves:
-        f = f[:, :, ::-1]
-    return np.ascontiguousarray(f).reshape(-1)
 
 
 @gpu
@@ -133,7 +81,7 @@ def test_layernorm_against_float64_reference(prec, D):
             x = x_many[516 - rows:]
             want, t32, t16 = ln_tolerances(x, g, b, x_many)
             st, out, _ = run_layernorm(prec, x, g, b)
-            _ctx().check(st)
+            kernel_support.ctx().check(st)
             assert np.all(out[rows:] == (NAN16 if prec == PREC_BF16 else NAN32)), "the rows behind the output were written"
             got = from_bf16_bits(out[:rows]) if prec == PREC_BF16 else out[:rows].view(np.float32)
             what = f"layernorm {'bf16' if prec == PREC_BF16 else 'fp32'} D={D} rows={rows} offset={offset} sigma={sigma}"
@@ -151,7 +99,7 @@ def test_layernorm_in_fragment_order(D, tok_l, tok_e):
         x, g, b = ln_rows(rows, D, offset, sigma, seed=D + tok_l)
         want, _, t16 = ln_tolerances(x, g, b)
         st, out, fr = run_layernorm(PREC_BF16, x, g, b, frag=True, tok=(tok_l, tok_e))
-        _ctx().check(st)
+        kernel_support.ctx().check(st)
         is_patch = (np.arange(rows) % tok_l) >= tok_e
         groups = nimg * tok_n // 32
         what = f"layernorm frag D={D} tok_l={tok_l} tok_e={tok_e} offset={offset}"
@@ -232,7 +180,7 @@ def embed_ref(x, w, bias, pos, label, y, t, extras, normalize, pos_shift=0):
 
 def run_embed(x, w, bias, pos, label, y, extras, normalize, generic, t_vec=None, t_state=0.0, ln=None):
     """dd_dev_embed; returns (x_tok [Mp + 8, D] fp32 as uint32 bits, ln_frag [Mp + 8, D] bf16 bits or None)"""
-    ctx = _ctx()
+    ctx = kernel_support.ctx()
     B, Cn, S, _ = x.shape
     D, _, Pz, _ = w.shape
     L = extras + (S // Pz) ** 2
@@ -341,7 +289,7 @@ def time_mlp_tolerance(t, D, normalize, w1, b1, w2, b2, pos_row):
 @gpu
 @pytest.mark.parametrize("D", [64, 256, 512])
 def test_time_mlp_against_float64_reference(D):
-    ctx = _ctx()
+    ctx = kernel_support.ctx()
     L = 9
     for B in (1, 5):
         for extras in (1, 2):

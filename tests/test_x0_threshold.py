@@ -12,6 +12,7 @@ from conftest import REPO, TINY
 from duodiff_amd import _lib as L
 from duodiff_amd.config import ModelParams
 from duodiff_amd.weights import synthetic_state_dict
+from loop_support import cli_argv, known_region, philox_z, philox_z2, side_stream, uvit
 
 gpu = pytest.mark.gpu
 CELEBA, IMAGENET256 = REPO / "configs" / "uvit_celeba.yaml", REPO / "configs" / "uvit_imagenet256.yaml"
@@ -160,8 +161,7 @@ def test_restated_scale_against_numpy_quantile(qt):
 
 
 def _argv(*extra, config=CELEBA, par="predict_noise"):
-    return ["--checkpoint_path", "/nonexistent.pth", "--batch_size", "2", "--parametrization", par,
-            "--output_folder", "/tmp/unused", "--config_path", str(config), *extra]
+    return cli_argv(config, *extra, par=par)
 
 
 def test_cli_threshold_options():
@@ -370,24 +370,10 @@ def test_threshold_step_images_are_independent_canaries_and_aliasing():
 NULL = 10
 
 
-def _uvit(cfg, seed, precision, max_batch):
-    from duodiff_amd.uvit import UViT
-    mp = ModelParams.from_dict(cfg)
-    m = UViT(**mp.as_dict(), precision=precision, max_batch=max_batch)
-    m.load_state_dict(synthetic_state_dict(mp, seed))
-    return m.eval().to("cuda"), mp
-
-
 def _model(S=8, cond=False, precision="bf16", depth=3, seed=42, max_batch=12):
     cfg = dict(TINY, img_size=S, depth=depth, num_classes=11 if cond else TINY.get("num_classes", -1))
-    m, _ = _uvit(cfg, seed, precision, max_batch)
+    m, _ = uvit(cfg, seed, precision, max_batch)
     return m.engine_model(max_batch)
-
-
-def _stream():
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    return s
 
 
 def _plan(sampler_kind, par="predict_noise"):
@@ -395,13 +381,6 @@ def _plan(sampler_kind, par="predict_noise"):
     kw = {"ode": dict(solver="dpmsolver++", solver_steps=6), "sde": dict(solver="sde-dpmsolver++", solver_steps=6),
           "ddim": dict(use_ddim=True, ddim_steps=7, ddim_eta=0.02), "ddpm": dict(num_steps=12)}[sampler_kind]
     return sampler.step_plan(par, threshold=_thr("static"), **kw)
-
-
-def _region(plan, x0, mask, k0=0, k1=None):
-    from duodiff_amd import sampler
-    from duodiff_amd.engine import KnownRegion
-    ka, kb = sampler.known_rows(plan)
-    return KnownRegion(x0, mask, ka[k0:k1], kb[k0:k1])
 
 
 def _loop(em, x_in, plan, thr, stream, *, region=None, seed=5, use_graph=True, guidance=None, y=None, flags=0, cuts=(), h0=None):
@@ -416,7 +395,7 @@ def _loop(em, x_in, plan, thr, stream, *, region=None, seed=5, use_graph=True, g
             for k0, k1 in zip(bounds[:-1], bounds[1:]):
                 seg = {k: v[k0:k1] for k, v in tab.items()}
                 kw = dict(y=y, seed=seed, counter_base=k0, noise="philox", use_graph=use_graph, stream=stream, guidance=guidance)
-                reg = None if region is None else _region(plan, *region, k0, k1)
+                reg = None if region is None else known_region(plan, *region, k0, k1)
                 if thr is not None:
                     engine.sample_multistep_threshold_loop(ctx, em, None, x, h, seg, thr, region=reg, **kw)
                 elif reg is not None:
@@ -430,30 +409,6 @@ def _loop(em, x_in, plan, thr, stream, *, region=None, seed=5, use_graph=True, g
     return x, h, chains
 
 
-def _philox_z(em, like, t, k, seed, stream, y=None):
-    """the z of step k: a one-step dd_sample_affine with the row (0, 0, 1) returns 0 + 0 + 1 * z"""
-    from duodiff_amd.engine import sample_affine_loop
-    z = like.clone()
-    with torch.cuda.stream(stream):
-        sample_affine_loop(em.ctx, em, None, z, [t], [0.0], [0.0], [1.0], [1], y=y, seed=seed, counter_base=k, noise="philox",
-                           use_graph=False, stream=stream)
-    stream.synchronize()
-    return z
-
-
-def _philox_z2(em, like, k, seed, stream, y=None):
-    """the z2 of step k: a one-step region call with m = 1, x0 = 0, ka = 0, kb = 1 on the row (0, 0, 0) returns z2"""
-    from duodiff_amd.engine import KnownRegion, sample_affine_region_loop
-    z = like.clone()
-    B, _, S, _ = like.shape
-    reg = KnownRegion(torch.zeros_like(like), torch.ones(B, 1, S, S, device="cuda"), np.zeros(1, F), np.ones(1, F))
-    with torch.cuda.stream(stream):
-        sample_affine_region_loop(em.ctx, em, None, z, reg, [500.0], [0.0], [0.0], [0.0], [0], y=y, seed=seed, counter_base=k,
-                                  noise="philox", use_graph=False, stream=stream)
-    stream.synchronize()
-    return z
-
-
 def _composition(em, x_in, plan, thr, stream, *, region=None, seed=5, guidance=None, y=None):
     """dd_forward[_guided | _autoguided], dd_threshold_step, dd_known_blend, fed the loop's z and z2"""
     from duodiff_amd import sampler
@@ -464,8 +419,8 @@ def _composition(em, x_in, plan, thr, stream, *, region=None, seed=5, guidance=N
     yz = y if em.mp.num_classes > 0 else None
     for k in range(len(tab["t"])):
         t = float(tab["t"][k])
-        z = _philox_z(em, x_in, t, k, seed, stream, yz) if tab["noise"][k] else None
-        z2 = _philox_z2(em, x_in, k, seed, stream, yz) if region is not None and kb[k] != 0 else None
+        z = philox_z(em, x_in, k, seed, stream, yz, t=t) if tab["noise"][k] else None
+        z2 = philox_z2(em, x_in, k, seed, stream, yz) if region is not None and kb[k] != 0 else None
         with torch.cuda.stream(stream):
             if isinstance(guidance, Autoguidance):
                 em.forward_autoguided(x, t, y, guidance.guide, guidance.scale, out=eps, stream=stream)
@@ -510,7 +465,7 @@ def test_loop_equals_the_composition_of_its_parts(kind, S, prec, mode, mods):
         kw = dict(guidance=Autoguidance(_model(S, precision=prec, depth=1, seed=41), 1.3))
     elif mods == "known":
         kw = dict(region=_known(B, S))
-    plan, thr, st = _plan(kind), _thr(mode, **THR[mode]), _stream()
+    plan, thr, st = _plan(kind), _thr(mode, **THR[mode]), side_stream()
     x_in = _start(B, S)
     xc, hc = _composition(em, x_in, plan, thr, st, **kw)
     assert torch.isfinite(xc).all() and not torch.equal(xc, x_in)
@@ -526,7 +481,7 @@ def test_loop_equals_the_composition_of_its_parts(kind, S, prec, mode, mods):
 @pytest.mark.parametrize("kind", ["sde", "ddpm"])
 def test_cut_loop_resumes_to_the_bits_of_the_uncut_loop(kind):
     B, S = 6, 8
-    em, st = _model(S), _stream()
+    em, st = _model(S), side_stream()
     plan, thr, x_in = _plan(kind), _thr("dynamic", quantile=0.995), _start(B, S)
     n = len(plan.rows["t"])
     whole = _loop(em, x_in, plan, thr, st, flags=L.DD_DEV_FORCE_CHAINS, region=_known(B, S))
@@ -541,14 +496,14 @@ def test_graph_keys_separate_thresholded_and_plain_calls():
     from duodiff_amd import sampler
     from duodiff_amd.engine import sample_loop
     B, S = 6, 8
-    em, st = _model(S), _stream()
+    em, st = _model(S), side_stream()
     plan, x_in = _plan("sde"), _start(B, S)
     variants = [None, _thr("dynamic", quantile=0.995), _thr("dynamic", quantile=0.9), _thr("dynamic", quantile=0.995, s_max=2.0),
                 _thr("static", range=1.0), _thr("static", range=0.5)]
     alone = []
     for thr in variants:
         fresh = _model(S)
-        alone.append(_loop(fresh, x_in, plan, thr, _stream())[0])
+        alone.append(_loop(fresh, x_in, plan, thr, side_stream())[0])
         del fresh
     assert len({a.cpu().numpy().tobytes() for a in alone}) == len(variants)
 
@@ -590,7 +545,7 @@ def test_invalid_threshold_calls_are_rejected_before_anything_is_enqueued():
     rows = _plan("ode").rows
     keep = {k: np.ascontiguousarray(rows[k], F) for k in "tabcdpq"}
     keep.update({k: np.ascontiguousarray(rows[k], np.int32) for k in ("noise", "hist")})
-    st = _stream()
+    st = side_stream()
     n0 = lib.dd_dev_graph_captures(ctx.handle)
     ok = (L.DD_X0_DYNAMIC, 0.995, 1.0, float("inf"))
     cases = [("null", None, "dd_x0_threshold"), ("mode", (5, 0.5, 1.0, 1.0), "mode"), ("q0", (1, 0.0, 1.0, 1.0), "quantile"),
@@ -667,7 +622,7 @@ def test_fp32_engine_matches_the_float64_thresholded_solver_on_the_oracle():
     B = 3
     x0, ts, x, gap = _float64_reference(B)
     assert gap > 1e-3
-    m32, _ = _uvit(dict(TINY), NUM_SEED, "fp32", B)
+    m32, _ = uvit(dict(TINY), NUM_SEED, "fp32", B)
     em = m32.engine_model(B)
     xd, hd = x0.cuda(), torch.zeros(B, 3, 8, 8, device="cuda")
     sample_multistep_threshold_loop(em.ctx, em, None, xd, hd, sampler.multistep_coefficients("dpmsolver++", ts, 2, unfolded=True),
@@ -683,7 +638,7 @@ def test_no_kernel_of_a_thresholded_call_depends_on_stale_bytes():
     """Both chains' workspaces and the context's model-output scratch are filled with NaN bytes on the launch stream before a model's
     first thresholded call (h NaN-filled too: step 0 has no history); the samples equal those of a fresh model, bit for bit."""
     B, S = 6, 8
-    plan, thr, x_in, st = _plan("sde"), _thr("dynamic", quantile=0.995), _start(B, S), _stream()
+    plan, thr, x_in, st = _plan("sde"), _thr("dynamic", quantile=0.995), _start(B, S), side_stream()
     outs = []
     for poison in (False, True):
         em = _model(S, cond=True, seed=73)

@@ -28,31 +28,20 @@ from pathlib import Path
 REPO = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(REPO))
 
+from loop_bench_support import LoopTimer, spread, synthetic_pair  # noqa: E402
+
 OUT = REPO / "profiles" / "autoguidance"
 SCALE = 1.0
 PAIRS = {"celeba": ("uvit_celeba_3", "uvit_celeba", 128), "imagenet256": ("uvit_imagenet256_3", "uvit_imagenet256", 32)}
 
 
-def spread(v):
-    med = statistics.median(v)
-    return {"runs": v, "median": med, "min": min(v), "max": max(v), "spread_frac": (max(v) - min(v)) / med if med else None}
-
-
 def build_pair(name, max_batch):
-    import torch
-    from duodiff_amd.config import ModelParams, load_config
-    from duodiff_amd.uvit import UViT
-    from duodiff_amd.weights import synthetic_state_dict
     cfg_g, cfg_m, _ = PAIRS[name]
-    mp_g = ModelParams.from_dict(load_config(REPO / "configs" / f"{cfg_g}.yaml"))
-    mp_m = ModelParams.from_dict(load_config(REPO / "configs" / f"{cfg_m}.yaml"))
-    guide = UViT(**mp_g.as_dict(), precision="bf16", max_batch=max_batch).load_state_dict(synthetic_state_dict(mp_g, 1237)).to("cuda:0")
-    main = UViT(**mp_m.as_dict(), precision="bf16", max_batch=max_batch).load_state_dict(synthetic_state_dict(mp_m, 1236)).to("cuda:0")
-    torch.cuda.synchronize()
-    return guide.engine_model(max_batch), main.engine_model(max_batch), mp_m
+    eg, em, _, mp_m = synthetic_pair(f"{cfg_g}.yaml", f"{cfg_m}.yaml", (1237, 1236), max_batch)
+    return eg, em, mp_m
 
 
-def runner(eg, em, mp, B, stream):
+def runner(eg, em, mp, B):
     """run(case, k) -> (ms of the loop's replays, chains); cases: autoguided_late, unguided_late, unguided_shallow, cfg_late"""
     import torch
     from duodiff_amd.engine import Autoguidance, sample_loop
@@ -61,16 +50,14 @@ def runner(eg, em, mp, B, stream):
     y = torch.randint(0, 1000, (B,), generator=g).to("cuda:0") if mp.num_classes > 0 else None
     x = x_T.clone()
     ctx = em.ctx
+    timer = LoopTimer(ctx)
 
     def run(case, k):
         model = eg if case == "unguided_shallow" else em
         kw = {"autoguided_late": dict(guidance=Autoguidance(eg, SCALE)), "cfg_late": dict(guidance=(SCALE, 1000))}.get(case, {})
-        with torch.cuda.stream(stream):
-            x.copy_(x_T, non_blocking=True)
-            sample_loop(ctx, model, None, x, t_start=999, t_end=1000 - k, y=y, seed=0, noise="philox", use_graph=True, stream=stream, **kw)
-        stream.synchronize()
-        assert torch.isfinite(x).all(), case
-        return ctx.last_sample_timing()[0], ctx.lib.dd_dev_last_sample_chains(ctx.handle)
+        _, chains = timer.run(lambda stream: sample_loop(ctx, model, None, x, t_start=999, t_end=1000 - k, y=y, seed=0, noise="philox",
+                                                         use_graph=True, stream=stream, **kw), x, x_T, case, timed=False)
+        return ctx.last_sample_timing()[0], chains      # the loop's own timing: graph capture is outside
     return run
 
 
@@ -80,8 +67,6 @@ def bench(a):
     if not torch.cuda.is_available():
         raise SystemExit("autoguidance_bench.py needs an MI355X: the engine has no CPU path")
     torch.cuda.set_device(0)
-    stream = torch.cuda.Stream(device="cuda:0")
-    stream.wait_stream(torch.cuda.current_stream())
     K, W = a.steps, a.warmup
     cases = ("autoguided_late", "unguided_late", "unguided_shallow")
     out = {"_build_id": _lib.load().dd_build_id().decode(),
@@ -91,7 +76,7 @@ def bench(a):
                       "date": time.strftime("%Y-%m-%d")}}
     for pair, (_, _, B) in PAIRS.items():
         eg, em, mp = build_pair(pair, B)
-        run = runner(eg, em, mp, B, stream)
+        run = runner(eg, em, mp, B)
         for c in cases:
             if W > 0:
                 run(c, W)
@@ -132,10 +117,8 @@ def trace_case(a):
     sized alike), B = 32 in two chains: an output-head launch covers 16 images, autoguided or classifier-free guided."""
     import torch
     torch.cuda.set_device(0)
-    stream = torch.cuda.Stream(device="cuda:0")
-    stream.wait_stream(torch.cuda.current_stream())
     eg, em, mp = build_pair("imagenet256", 64)
-    run = runner(eg, em, mp, 32, stream)
+    run = runner(eg, em, mp, 32)
     case = {"auto": "autoguided_late", "cfg": "cfg_late"}[a.trace_case]
     _, chains = run(case, a.warmup)
     ms, chains = run(case, a.steps)

@@ -25,33 +25,23 @@ from pathlib import Path
 REPO = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(REPO))
 
+from loop_bench_support import LoopTimer, spread, synthetic_pair  # noqa: E402
+
 OUT = REPO / "profiles" / "guidance"
 SCALE, NULL = 0.4, 1000
-
-
-def spread(v):
-    med = statistics.median(v)
-    return {"runs": v, "median": med, "min": min(v), "max": max(v), "spread_frac": (max(v) - min(v)) / med if med else None}
 
 
 def bench(a):
     import torch
     from duodiff_amd import _lib
-    from duodiff_amd.config import ModelParams, load_config
     from duodiff_amd.engine import sample_loop
-    from duodiff_amd.uvit import UViT
-    from duodiff_amd.weights import synthetic_state_dict
 
     if not torch.cuda.is_available():
         raise SystemExit("guidance_bench.py needs an MI355X: the engine has no CPU path")
     dev = "cuda:0"
     torch.cuda.set_device(0)
-    mp_s = ModelParams.from_dict(load_config(REPO / "configs" / "uvit_imagenet256_3.yaml"))
-    mp_f = ModelParams.from_dict(load_config(REPO / "configs" / "uvit_imagenet256.yaml"))
     rows = 64
-    shallow = UViT(**mp_s.as_dict(), precision="bf16", max_batch=rows).load_state_dict(synthetic_state_dict(mp_s, 1237)).to(dev)
-    full = UViT(**mp_f.as_dict(), precision="bf16", max_batch=rows).load_state_dict(synthetic_state_dict(mp_f, 1236)).to(dev)
-    es, ef = shallow.engine_model(rows), full.engine_model(rows)
+    es, ef, _, mp_f = synthetic_pair("uvit_imagenet256_3.yaml", "uvit_imagenet256.yaml", (1237, 1236), rows)
     ctx = es.ctx
     K, W = a.steps, a.warmup
     k_sw = max(1, round(0.3 * K))          # the 30 / 70 mix: the switch after 30 % of the steps
@@ -66,24 +56,12 @@ def bench(a):
         x_T = torch.randn(c["B"], Cc, S, S, generator=g).to(dev)
         y = torch.randint(0, 1000, (c["B"],), generator=g).to(dev)       # every image guided (no label equals the null label)
         state[name] = (x_T, x_T.clone(), y)
-    stream = torch.cuda.Stream(device=dev)
-    stream.wait_stream(torch.cuda.current_stream())
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    timer = LoopTimer(ctx)
 
     def run(name, k, ksw, timed):
         x_T, x, y = state[name]
-        with torch.cuda.stream(stream):
-            x.copy_(x_T, non_blocking=True)
-            if timed:
-                e0.record(stream)
-            sample_loop(ctx, es, ef, x, t_switch=ksw, t_start=999, t_end=1000 - k, y=y, seed=0, noise="philox", use_graph=True,
-                        stream=stream, guidance=cases[name]["guidance"])
-            if timed:
-                e1.record(stream)
-        stream.synchronize()
-        assert torch.isfinite(x).all(), name
-        chains = ctx.lib.dd_dev_last_sample_chains(ctx.handle)
-        return (e0.elapsed_time(e1) if timed else None), chains
+        return timer.run(lambda stream: sample_loop(ctx, es, ef, x, t_switch=ksw, t_start=999, t_end=1000 - k, y=y, seed=0, noise="philox",
+                                                    use_graph=True, stream=stream, guidance=cases[name]["guidance"]), x, x_T, name, timed=timed)
 
     for name in cases:                     # warm-up: both backbones of both cases (graph captures, code-object loads)
         if W > 0:

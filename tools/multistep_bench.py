@@ -27,6 +27,8 @@ import numpy as np
 REPO = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(REPO))
 
+from loop_bench_support import LoopTimer, spread, synthetic_pair  # noqa: E402
+
 OUT = REPO / "profiles" / "multistep"
 SCALE, NULL = 0.4, 1000
 PAIRS = {
@@ -35,27 +37,15 @@ PAIRS = {
 }
 
 
-def spread(v):
-    med = statistics.median(v)
-    return {"runs": v, "median": med, "min": min(v), "max": max(v), "spread_frac": (max(v) - min(v)) / med if med else None}
-
-
 def bench_pair(name, spec, a):
     import torch
     from duodiff_amd import sampler
-    from duodiff_amd.config import ModelParams, load_config
     from duodiff_amd.engine import sample_affine_loop, sample_multistep_loop
-    from duodiff_amd.uvit import UViT
-    from duodiff_amd.weights import synthetic_state_dict
 
     dev = "cuda:0"
-    mp_s = ModelParams.from_dict(load_config(REPO / "configs" / spec["first"]))
-    mp_f = ModelParams.from_dict(load_config(REPO / "configs" / spec["late"]))
     B, guidance = spec["B"], spec["guidance"]
     rows = 2 * B if guidance else B
-    shallow = UViT(**mp_s.as_dict(), precision="bf16", max_batch=rows).load_state_dict(synthetic_state_dict(mp_s, spec["seeds"][0])).to(dev)
-    full = UViT(**mp_f.as_dict(), precision="bf16", max_batch=rows).load_state_dict(synthetic_state_dict(mp_f, spec["seeds"][1])).to(dev)
-    es, ef = shallow.engine_model(rows), full.engine_model(rows)
+    es, ef, _, mp_f = synthetic_pair(spec["first"], spec["late"], spec["seeds"], rows)
     ctx = es.ctx
     N = a.evals
     k_sw = max(1, round(0.3 * N))
@@ -67,27 +57,17 @@ def bench_pair(name, spec, a):
     x_T = torch.randn(B, Cc, S, S, generator=g).to(dev)
     y = torch.randint(0, 1000, (B,), generator=g).to(dev) if mp_f.num_classes > 0 else None
     x, h = x_T.clone(), torch.zeros_like(x_T)
-    stream = torch.cuda.Stream(device=dev)
-    stream.wait_stream(torch.cuda.current_stream())
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    timer = LoopTimer(ctx)
 
     def run(kind, timed):
-        with torch.cuda.stream(stream):
-            x.copy_(x_T, non_blocking=True)
-            h.zero_()
-            if timed:
-                e0.record(stream)
+        def loop(stream):
             if kind == "dpmsolver++":
                 sample_multistep_loop(ctx, es, ef, x, h, ms_rows, switch_after=k_sw, y=y, seed=0, noise="philox", stream=stream,
                                       guidance=guidance)
             else:
                 sample_affine_loop(ctx, es, ef, x, [float(t) for t in ts[:-1]], [c[0] for c in co], [c[1] for c in co], [c[2] for c in co],
                                    [0] * N, switch_after=k_sw, y=y, seed=0, noise="philox", stream=stream, guidance=guidance)
-            if timed:
-                e1.record(stream)
-        stream.synchronize()
-        assert torch.isfinite(x).all(), (name, kind)
-        return (e0.elapsed_time(e1) if timed else None), ctx.lib.dd_dev_last_sample_chains(ctx.handle)
+        return timer.run(loop, x, x_T, (name, kind), h=h, timed=timed)
 
     kinds = ("dpmsolver++", "ddim")
     for _ in range(a.warmup):
@@ -107,7 +87,7 @@ def bench_pair(name, spec, a):
         out[kind] = {"chains": chains[kind], "ms_per_step": spread(res[kind]["ms_per_step"]), "images_per_s": spread(res[kind]["images_per_s"])}
     out["dpm_over_ddim_ms_per_step"] = out["dpmsolver++"]["ms_per_step"]["median"] / out["ddim"]["ms_per_step"]["median"]
     out["target_met"] = out["dpm_over_ddim_ms_per_step"] <= 1.01
-    del es, ef, shallow, full
+    del es, ef
     torch.cuda.empty_cache()
     return out
 

@@ -19,7 +19,6 @@ the alternated unguided runs.
 import argparse
 import ctypes as C
 import json
-import statistics
 import sys
 import time
 from pathlib import Path
@@ -27,42 +26,24 @@ from pathlib import Path
 REPO = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(REPO))
 
+from loop_bench_support import LoopTimer, merge_json, spread, synthetic_pair  # noqa: E402
+
 OUT = REPO / "profiles" / "pag"
 SCALE = 3.0
 HBM_ACHIEVABLE_TBS = 6.3        # a float4 copy on the MI355X (8.0 TB/s spec)
 
 
-def spread(v):
-    med = statistics.median(v)
-    return {"runs": v, "median": med, "min": min(v), "max": max(v), "spread_frac": (max(v) - min(v)) / med if med else None}
-
-
-def merge_json(update):
-    path = OUT / "pag_bench.json"
-    OUT.mkdir(parents=True, exist_ok=True)
-    out = json.loads(path.read_text()) if path.exists() else {}
-    out.update(update)
-    path.write_text(json.dumps(out, indent=1) + "\n")
-
-
 def bench(a):
     import torch
     from duodiff_amd import _lib
-    from duodiff_amd.config import ModelParams, load_config
     from duodiff_amd.engine import Perturbed, sample_loop
-    from duodiff_amd.uvit import UViT
-    from duodiff_amd.weights import synthetic_state_dict
 
     if not torch.cuda.is_available():
         raise SystemExit("pag_bench.py needs an MI355X: the engine has no CPU path")
     dev = "cuda:0"
     torch.cuda.set_device(0)
-    mp_s = ModelParams.from_dict(load_config(REPO / "configs" / "uvit_celeba_3.yaml"))
-    mp_f = ModelParams.from_dict(load_config(REPO / "configs" / "uvit_celeba.yaml"))
     rows = 128
-    shallow = UViT(**mp_s.as_dict(), precision="bf16", max_batch=rows).load_state_dict(synthetic_state_dict(mp_s, 1237)).to(dev)
-    full = UViT(**mp_f.as_dict(), precision="bf16", max_batch=rows).load_state_dict(synthetic_state_dict(mp_f, 1236)).to(dev)
-    es, ef = shallow.engine_model(rows), full.engine_model(rows)
+    es, ef, mp_s, mp_f = synthetic_pair("uvit_celeba_3.yaml", "uvit_celeba.yaml", (1237, 1236), rows)
     ctx = es.ctx
     K, W = a.steps, a.warmup
     k_sw = max(1, round(0.3 * K))          # the 30 / 70 mix: the switch after 30 % of the steps
@@ -77,24 +58,12 @@ def bench(a):
     for name, c in cases.items():
         x_T = torch.randn(c["B"], Cc, S, S, generator=g).to(dev)
         state[name] = (x_T, x_T.clone())
-    stream = torch.cuda.Stream(device=dev)
-    stream.wait_stream(torch.cuda.current_stream())
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    timer = LoopTimer(ctx)
 
     def run(name, k, ksw, timed):
         x_T, x = state[name]
-        with torch.cuda.stream(stream):
-            x.copy_(x_T, non_blocking=True)
-            if timed:
-                e0.record(stream)
-            sample_loop(ctx, es, ef, x, t_switch=ksw, t_start=999, t_end=1000 - k, seed=0, noise="philox", use_graph=True,
-                        stream=stream, guidance=cases[name]["guidance"])
-            if timed:
-                e1.record(stream)
-        stream.synchronize()
-        assert torch.isfinite(x).all(), name
-        chains = ctx.lib.dd_dev_last_sample_chains(ctx.handle)
-        return (e0.elapsed_time(e1) if timed else None), chains
+        return timer.run(lambda stream: sample_loop(ctx, es, ef, x, t_switch=ksw, t_start=999, t_end=1000 - k, seed=0, noise="philox",
+                                                    use_graph=True, stream=stream, guidance=cases[name]["guidance"]), x, x_T, name, timed=timed)
 
     for name in cases:                     # warm-up: both backbones of every case (graph captures, code-object loads)
         if W > 0:
@@ -122,7 +91,7 @@ def bench(a):
     out["target"] = "PAG B=64 ms/step <= unguided B=128 ms/step + the min-max spread of the alternated unguided runs"
     print(json.dumps(out, indent=1))
     if not a.no_json:
-        merge_json({"loop": out})
+        merge_json(OUT / "pag_bench.json", {"loop": out})
 
 
 def kernel(a):
@@ -167,7 +136,7 @@ def kernel(a):
     res["v_identity_over_qkv_attention"] = med / res["qkv_attention_us"]["median"]
     print(json.dumps(res, indent=1))
     if not a.no_json:
-        merge_json({"kernel": res})
+        merge_json(OUT / "pag_bench.json", {"kernel": res})
 
 
 def main(argv=None):

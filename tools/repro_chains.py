@@ -1,13 +1,14 @@
 """Dev tool: repeat the half-batch-chains comparison on the ImageNet-64-width model and report which runs differ (run-to-run determinism of each mode too)."""
 import sys, torch
 sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
-from test_gpu_parity import _uvit, load_config, REPO
+from test_gpu_parity import load_config, REPO
+from loop_support import uvit
 from duodiff_amd import _lib as L
 from duodiff_amd.engine import sample_loop
 B, S, C_, steps, tsw = 256, 64, 3, 4, 2
 cfg = load_config(REPO / "configs" / "uvit_imagenet64_3.yaml")
-m_s, _ = _uvit(cfg, 31, "bf16", max_batch=B)
-m_f, mp_f = _uvit(cfg, 32, "bf16", max_batch=B)
+m_s, _ = uvit(cfg, 31, "bf16", max_batch=B)
+m_f, mp_f = uvit(cfg, 32, "bf16", max_batch=B)
 es, ef = m_s.engine_model(B), m_f.engine_model(B)
 ctx = es.ctx
 x0 = torch.randn(B, C_, S, S, generator=torch.Generator().manual_seed(4)).cuda()

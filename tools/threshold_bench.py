@@ -23,31 +23,21 @@ from pathlib import Path
 REPO = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(REPO))
 
+from loop_bench_support import LoopTimer, spread, synthetic_pair  # noqa: E402
+
 OUT = REPO / "profiles" / "threshold"
 FIRST, LATE, B, SEEDS = "uvit_celeba_3.yaml", "uvit_celeba.yaml", 128, (1235, 1234)
-
-
-def spread(v):
-    med = statistics.median(v)
-    return {"runs": v, "median": med, "min": min(v), "max": max(v), "spread_frac": (max(v) - min(v)) / med if med else None}
 
 
 def bench(a):
     import torch
     from duodiff_amd import _lib, sampler
-    from duodiff_amd.config import ModelParams, load_config
     from duodiff_amd.engine import X0Threshold, sample_multistep_loop, sample_multistep_threshold_loop
-    from duodiff_amd.uvit import UViT
-    from duodiff_amd.weights import synthetic_state_dict
     if not torch.cuda.is_available():
         raise SystemExit("threshold_bench.py needs an MI355X: the engine has no CPU path")
     torch.cuda.set_device(0)
     dev = "cuda:0"
-    mp_s = ModelParams.from_dict(load_config(REPO / "configs" / FIRST))
-    mp_f = ModelParams.from_dict(load_config(REPO / "configs" / LATE))
-    shallow = UViT(**mp_s.as_dict(), precision="bf16", max_batch=B).load_state_dict(synthetic_state_dict(mp_s, SEEDS[0])).to(dev)
-    full = UViT(**mp_f.as_dict(), precision="bf16", max_batch=B).load_state_dict(synthetic_state_dict(mp_f, SEEDS[1])).to(dev)
-    es, ef = shallow.engine_model(B), full.engine_model(B)
+    es, ef, _, mp_f = synthetic_pair(FIRST, LATE, SEEDS, B)
     ctx = es.ctx
     N = a.evals
     k_sw = max(1, round(0.3 * N))
@@ -57,26 +47,16 @@ def bench(a):
     modes = {"plain": None, "static": X0Threshold("static", range=1.0), "dynamic": X0Threshold("dynamic", quantile=0.995)}
     x_T = torch.randn(B, mp_f.in_chans, mp_f.img_size, mp_f.img_size, generator=torch.Generator().manual_seed(0)).to(dev)
     x, h = x_T.clone(), torch.zeros_like(x_T)
-    stream = torch.cuda.Stream(device=dev)
-    stream.wait_stream(torch.cuda.current_stream())
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    timer = LoopTimer(ctx)
 
     def run(mode, timed):
-        with torch.cuda.stream(stream):
-            x.copy_(x_T, non_blocking=True)
-            h.zero_()
-            if timed:
-                e0.record(stream)
+        def loop(stream):
             kw = dict(switch_after=k_sw, seed=0, noise="philox", stream=stream)
             if modes[mode] is None:
                 sample_multistep_loop(ctx, es, ef, x, h, folded, **kw)
             else:
                 sample_multistep_threshold_loop(ctx, es, ef, x, h, unfolded, modes[mode], **kw)
-            if timed:
-                e1.record(stream)
-        stream.synchronize()
-        assert torch.isfinite(x).all(), mode
-        return (e0.elapsed_time(e1) if timed else None), ctx.lib.dd_dev_last_sample_chains(ctx.handle)
+        return timer.run(loop, x, x_T, mode, h=h, timed=timed)
 
     for _ in range(a.warmup):
         for mode in modes:

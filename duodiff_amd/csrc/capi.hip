@@ -433,16 +433,12 @@ void pack_block(dd_model* m, Arena& a, int bi, const std::string& next_skip, con
         const bool with_skip = m->fused_skip && !next_skip.empty();
         // (an out-block's qkv needs its skip_linear in here too; with fused_qa the attention launch computes qkv and no section is packed)
         const bool with_qkv = m->fused_qkv && !m->fused_qa && !next_qkv.empty() && (next_skip.empty() || with_skip);
-        const MlpImage im = MlpImage::of(D, hid, m->fused_proj, with_skip, with_qkv);
-        char* img = a.raw(w.mlp_img, im.bytes());
-        auto section = [&](size_t block) { return (unsigned short*)(img + im.at(block)); };
-        std::vector<float> b1p(hid);
-        if (m->fused_proj) mlp_fused_pack_proj(D, P(p + "attn.proj.weight").data(), host_f2bf, section(0));
-        mlp_fused_pack(D, hid, P(p + "mlp.fc1.weight").data(), P(p + "mlp.fc1.bias").data(), P(p + "mlp.fc2.weight").data(), true, host_f2bf,
-                       section(im.mlp), b1p.data());
-        if (with_skip) mlp_fused_pack_skip(D, P(next_skip + "skip_linear.weight").data(), host_f2bf, section(im.skip));      // the next block's skip_linear
-        if (with_qkv) mlp_fused_pack_rows(D, 3 * D, P(next_qkv + "attn.qkv.weight").data(), host_f2bf, section(im.qkv));     // the next block's attn.qkv
-        a.f32(w.mlp_b1p, b1p);
+        const TailImage t = pack_tail_image(D, hid, m->fused_proj ? P(p + "attn.proj.weight").data() : nullptr, P(p + "mlp.fc1.weight").data(),
+                                            P(p + "mlp.fc1.bias").data(), P(p + "mlp.fc2.weight").data(), true,
+                                            with_skip ? P(next_skip + "skip_linear.weight").data() : nullptr,      // the next block's skip_linear
+                                            with_qkv ? P(next_qkv + "attn.qkv.weight").data() : nullptr);          // the next block's attn.qkv
+        std::memcpy(a.raw(w.mlp_img, t.img.size() * 2), t.img.data(), t.img.size() * 2);
+        a.f32(w.mlp_b1p, t.b1p);
     }
     if (m->fused_qa)
         qkv_attention_pack(D, m->H, P(p + "attn.qkv.weight").data(), host_f2bf, (unsigned short*)a.raw(w.qa_img, (size_t)3 * D * D * 2));
@@ -458,18 +454,11 @@ void pack_embed(dd_model* m, Arena& a) {
     const int D = m->D, pd = m->pd;
     auto P = [&](const std::string& n) -> const std::vector<float>& { return param(m, n); };
     // patch-embed weight [D, pd] -> transposed [pd, D] (coalesced over D in the embed kernel)
-    std::vector<float> wt((size_t)pd * D);
-    const std::vector<float>& pe = P("patch_embed.proj.weight");
-    for (int d = 0; d < D; ++d) for (int k = 0; k < pd; ++k) wt[(size_t)k * D + d] = pe[(size_t)d * pd + k];
-    a.f32(m->emb_wt, wt); a.f32(m->emb_b, P("patch_embed.proj.bias")); a.f32(m->pos, P("pos_embed"));
+    a.f32(m->emb_wt, transposed(P("patch_embed.proj.weight").data(), D, pd)); a.f32(m->emb_b, P("patch_embed.proj.bias")); a.f32(m->pos, P("pos_embed"));
     if (m->cfg.num_classes > 0) a.f32(m->label, P("label_emb.weight"));
     if (m->cfg.mlp_time_embed) {   // transposed: the kernel's threads run over the OUTPUT index
-        const std::vector<float>&w1 = P("time_embed.0.weight"), &w2 = P("time_embed.2.weight");
-        std::vector<float> w1t((size_t)D * 4 * D), w2t((size_t)4 * D * D);
-        for (int j = 0; j < 4 * D; ++j) for (int k = 0; k < D; ++k) w1t[(size_t)k * 4 * D + j] = w1[(size_t)j * D + k];
-        for (int d = 0; d < D; ++d) for (int k = 0; k < 4 * D; ++k) w2t[(size_t)k * D + d] = w2[(size_t)d * 4 * D + k];
-        a.f32(m->tm_w1t, w1t); a.f32(m->tm_b1, P("time_embed.0.bias"));
-        a.f32(m->tm_w2t, w2t); a.f32(m->tm_b2, P("time_embed.2.bias"));
+        a.f32(m->tm_w1t, transposed(P("time_embed.0.weight").data(), 4 * D, D)); a.f32(m->tm_b1, P("time_embed.0.bias"));
+        a.f32(m->tm_w2t, transposed(P("time_embed.2.weight").data(), D, 4 * D)); a.f32(m->tm_b2, P("time_embed.2.bias"));
     }
 }
 
@@ -483,14 +472,11 @@ void pack_head(const dd_model* m, Arena& a, const std::string& p, HeadW& h, bool
     a.f32(h.ng, ng); a.f32(h.nb, nb); a.f32(h.wdec, wd); a.f32(h.bdec, bd);
     a.f32(h.wconv, P(p + "final_layer.weight")); a.f32(h.bconv, P(p + "final_layer.bias"));
     if (!fused) return;
-    std::vector<float> wg, dc;
-    fold_head_norm(D, pd, wd.data(), bd.data(), ng.data(), nb.data(), wg, dc);
-    a.f32(h.wg, wg); a.f32(h.dc, dc);
+    const HeadImage hi = pack_head_image(D, pd, wd.data(), bd.data(), ng.data(), nb.data(), split);
+    a.f32(h.wg, hi.wg); a.f32(h.dc, hi.dc);
     if (!split) return;
-    const size_t img_bytes = (size_t)(D / 32) * ((pd + 15) / 16) * 2 * 64 * 8 * 2;
-    std::vector<float> dcs(dc);
-    pack_head_split(D, pd, wg.data(), host_f2bf, (unsigned short*)a.raw(h.wsplit, img_bytes), dcs.data() + pd);
-    a.f32(h.dcs, dcs);
+    std::memcpy(a.raw(h.wsplit, hi.wsplit.size() * 2), hi.wsplit.data(), hi.wsplit.size() * 2);
+    a.f32(h.dcs, hi.dcs);
 }
 
 // the early-exit probes: one AttentionProbe per layer, or the [n_probe, D] / [n_probe] table of the MLP probes
@@ -872,10 +858,10 @@ struct Backbone {
     int block_tail(int bi, T* copy, const Handoff in, Handoff& next) {
         const BlockW& w = m->blocks[bi];
         MlpFusedArgs fa{};
-        fa.X = nullptr; fa.ldx = D; fa.wimg = w.mlp_img; fa.b1p = w.mlp_b1p; fa.b2 = w.fc2_b;
+        fa.wimg = w.mlp_img; fa.b1p = w.mlp_b1p; fa.b2 = w.fc2_b;
         fa.ln_in_g = w.ln2_g; fa.ln_in_b = w.ln2_b;                       // norm2 of this block, in the prologue
-        fa.xres = ws.x; fa.out = (bf16_t*)copy; fa.ldo = D; fa.partial = ws.mlp_partial;
-        if (m->fused_proj) { fa.ao = (const bf16_t*)ao; fa.bproj = w.proj_b; fa.nproj = D / 32; }
+        fa.xres = ws.x; fa.out = (bf16_t*)copy; fa.partial = ws.mlp_partial;
+        if (m->fused_proj) { fa.ao = (const bf16_t*)ao; fa.bproj = w.proj_b; }
         if (ao_in_frag) fa.ao_frag = ws.aofrag;
         // the long-skip operand's patch rows: in-block bi's copy into its fragment buffer, read back by the tail that runs out-block nb - 1 - bi's skip_linear
         if (m->frag_skip && bi < m->half_depth) fa.out_frag = ws.skipfrags[bi];
@@ -884,7 +870,7 @@ struct Backbone {
             fa.skip = (const bf16_t*)skip_of(bi + 1);
             if (m->frag_skip) fa.skip_frag = ws.skipfrags[nb - 1 - (bi + 1)];
             if (ee) fa.y_tap = ws.ytap;                                       // the next block's head / probe read y, which this launch consumes
-            fa.bskip = m->blocks[bi + 1].skip_b; fa.nskip = D / 16;
+            fa.bskip = m->blocks[bi + 1].skip_b;
         }
         // the next block's norm1 where it starts with one (behind its skip_linear, if this launch runs that); its attn.qkv inside its attention
         // launch (fused_qa), else last of all in this launch (fused_qkv) -- wherever this launch leaves that block's norm1
@@ -899,21 +885,10 @@ struct Backbone {
         next.h = h_next && !next.frag && !next.qkv;
         if (h_next) { fa.ln_out_g = m->blocks[bi + 1].ln1_g; fa.ln_out_b = m->blocks[bi + 1].ln1_b; fa.ln_out = (bf16_t*)h; }
         if (next.frag) fa.ln_out_frag = ws.hfrag;      // the patch rows' norm1 in the order the attention launch loads it
-        if (next.qkv) { fa.qkv_out = (bf16_t*)qkv; fa.qkv_dump = ws.qkv_dump; fa.hm = make_head_major(L, m->H); fa.nqkv = 3 * D / 32; }   // (norm1: the extra-token rows only)
-        mlp_fused_plan(B, m->N, m->extras, L, m->hidden, fa);
-        // The LAST block's projection / MLP of the extra-token rows feed nothing: the output head decodes the patch rows only
-        // (models/uvit.py:377-380 slices the extras off), and those rows' K / V went into this block's attention before.  No
-        // proj_rows / hidden-split workgroups / reduce launch for them.
-        if (bi + 1 == nb && m->fused_proj) { fa.n_extra = 0; fa.tiles_left = 0; }
-        if (m->fused_proj) fa.reduce_set = 1;   // the extra-token rows' projection runs in their hidden-split workgroups: the first group's slab carries x + proj(ao) + b
+        if (next.qkv) { fa.qkv_out = (bf16_t*)qkv; fa.qkv_dump = ws.qkv_dump; }   // (norm1: the extra-token rows only)
+        block_tail_plan(fa, B, m->N, m->extras, D, m->H, m->hidden, bi + 1 == nb);
         DD_TIMED(DD_PROF_BLOCK_TAIL, launch_mlp_fused(fa, D, s));   // (the event pair brackets the fused kernel alone)
-        // the reduce kernel finishes the extra-token rows (y in fp32 + the bf16 copy in xb); their skip_linear + norm1 follow in one small launch
-        // (fused_qa: the attention launch normalises the extra-token rows itself, so no norm1 rows, and that launch is split by columns)
-        MlpFusedArgs fr = fa;
-        if (next.skip || next.frag) fr.ln_out = nullptr;
-        DD_HIP(c, launch_mlp_reduce(fr, D, s));
-        if (next.skip) DD_HIP(c, launch_skip_rows_ln(fa, D, s, !next.frag));
-        if (next.qkv) DD_HIP(c, launch_qkv_rows(fa, D, s));   // the extra-token rows' qkv, from the norm1 rows the launch above wrote
+        DD_HIP(c, block_tail_finish(fa, D, s));
         return DD_OK;
     }
 

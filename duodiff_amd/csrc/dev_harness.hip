@@ -1,7 +1,8 @@
 // The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_block_tail, dd_dev_block_tail_frag, dd_dev_qkv_attention, dd_dev_qkv_attention_rows, dd_dev_qkv_attention_frag, dd_dev_v_identity, dd_dev_v_copy, dd_dev_head_dec, dd_dev_gemm,
-// dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather): test scaffolding, not product.  Each one packs host operands as finalize packs a model's, launches what the model launches
-// (launch_args.h), returns the outputs and times `iters` further launch sequences.  Buffers, transfers, timing and HIP errors go through
-// one DevScope (dev_scope.h); the context is reached through its accessors only.
+// dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather): test scaffolding, not product.  Each one owns its host operands, device buffers, canaries and
+// downloads, and nothing of the launch: the weight images come from finalize's packers and the launch arguments from the model's builders (launch_args.h:
+// dd_dev_mlp and dd_dev_block_tail* run block_tail_plan / block_tail_finish exactly as Backbone::block_tail does), then `iters` further launch sequences
+// are timed.  Buffers, transfers, timing and HIP errors go through one DevScope (dev_scope.h); the context is reached through its accessors only.
 #include "../../include/duodiff.h"
 #include "../../include/duodiff_dev.h"
 #include "dd_internal.h"
@@ -30,58 +31,36 @@ int dd_dev_mlp(dd_ctx* c, int M, int D, int hidden, int extras, const float* x_h
     if (!mlp_fused_supported(D, hidden)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "fused MLP: D in {64,128,256,512}, hidden % 64 == 0");
     hipStream_t s = (hipStream_t)stream;
     const size_t Mp = (size_t)round_up(M, 256), row_bytes = Mp * D * 2;      // (every bf16 row buffer: Mp rows, zero padding)
-    const MlpImage im = MlpImage::of(D, hidden, proj, skp, qk);
-    std::vector<unsigned short> img(im.bytes() / 2, 0);
-    auto section = [&](size_t block) { return img.data() + im.at(block) / 2; };
-    std::vector<float> b1p(hidden), xr(Mp * D, 0.f);
+    const TailImage t = pack_tail_image(D, hidden, proj ? wproj : nullptr, w1, b1, w2, ln_in != nullptr, skp ? wskip : nullptr, qk ? wqkv : nullptr);
+    std::vector<float> xr(Mp * D, 0.f);
     std::memcpy(xr.data(), xres_host, (size_t)M * D * 4);
-    if (proj) mlp_fused_pack_proj(D, wproj, host_f2bf, section(0));
-    mlp_fused_pack(D, hidden, w1, b1, w2, ln_in != nullptr, host_f2bf, section(im.mlp), b1p.data());
-    if (skp) mlp_fused_pack_skip(D, wskip, host_f2bf, section(im.skip));
-    if (qk) mlp_fused_pack_rows(D, 3 * D, wqkv, host_f2bf, section(im.qkv));
     // extras > 0: the M rows are `M / (1 + extras)` images of one patch token each (drives the hidden-split path);
     // extras == 0: one image of M patch tokens (main tiles only)
-    MlpFusedArgs a{};
-    if (extras > 0) mlp_fused_plan(M / (1 + extras), 1, extras, 1 + extras, hidden, a);
-    else mlp_fused_plan(1, M, 0, M, hidden, a);
-    if (ctx_dev_flags(c) & DD_DEV_MLP_EXTRAS_ONLY) { a.tiles_main = 0; a.n_main = 0; }   // time the hidden-split workgroups alone
-    const size_t part = (size_t)a.tiles_left * a.groups * 128 * D * sizeof(float);
+    const int B = extras > 0 ? M / (1 + extras) : 1, n_patches = extras > 0 ? 1 : M;
     DevScope dev(c);
-    a.X = dev.upload(bf16_rows(x_host, M, D, Mp, 0).data(), row_bytes); a.ldx = D;
-    a.wimg = (const char*)dev.upload(img.data(), img.size() * 2);
-    a.b1p = dev.upload(b1p.data(), (size_t)hidden * 4); a.b2 = dev.upload(b2, (size_t)D * 4);
+    MlpFusedArgs a{};
+    a.X = dev.upload(bf16_rows(x_host, M, D, Mp, 0).data(), row_bytes);
+    a.wimg = (const char*)dev.upload(t.img.data(), t.img.size() * 2);
+    a.b1p = dev.upload(t.b1p.data(), (size_t)hidden * 4); a.b2 = dev.upload(b2, (size_t)D * 4);
     a.xres = dev.upload(xr.data(), xr.size() * 4);
     bf16_t* dO = dev.filled<bf16_t>(row_bytes, 0);
-    a.out = out_host ? dO : nullptr; a.ldo = D;
-    a.partial = part ? dev.alloc<float>(part) : nullptr;
+    a.out = out_host || skp ? dO : nullptr;      // (a SKIP launch: y of the extra-token rows travels through the bf16 copy)
     // ln_in / ln_out: [2, D] gamma then beta of the LayerNorm fused into the prologue / epilogue (or NULL)
     bf16_t* dH = dev.filled<bf16_t>(row_bytes, 0);
     if (ln_in) { a.ln_in_g = dev.upload(ln_in, (size_t)2 * D * 4); a.ln_in_b = a.ln_in_g + D; }
     if (ln_out && ln_out_host) { a.ln_out_g = dev.upload(ln_out, (size_t)2 * D * 4); a.ln_out_b = a.ln_out_g + D; a.ln_out = dH; }
-    if (proj) {   // as Backbone::block_tail does it: patch rows in the main tiles, extra-token rows in their hidden-split workgroups
-        a.ao = dev.upload(bf16_rows(ao_host, M, D, Mp, 0).data(), row_bytes); a.bproj = dev.upload(bproj, (size_t)D * 4); a.nproj = D / 32;
-        a.reduce_set = 1;        // (the extra-token rows' projection runs in their hidden-split workgroups, Backbone::block_tail)
-    }
-    MlpFusedArgs ar = a;       // (what the reduce launch gets: see Backbone::block_tail)
-    if (skp) {
-        a.skip = dev.upload(bf16_rows(skip_host, M, D, Mp, 0).data(), row_bytes); a.bskip = dev.upload(bskip, (size_t)D * 4); a.nskip = D / 16;
-        a.out = dO;   // y of the extra-token rows travels through the bf16 copy
-        ar = a; ar.ln_out = nullptr;
-    }
-    size_t qkv_elems = 0;
-    if (qk) {   // head-major qkv of the rows as images of a.tok_l tokens (HeadMajor, dd_internal.h): [images][3 D / 64 units][Lp][64]
-        a.hm = make_head_major(a.tok_l, D / 64);
-        const size_t images = (size_t)(M / a.tok_l);
-        qkv_elems = images * 3 * D * (size_t)a.hm.Lp;
-        a.qkv_out = dev.filled<bf16_t>(qkv_elems * 2, 0); a.qkv_dump = dev.alloc<bf16_t>(16384); a.nqkv = 3 * D / 32;
-        ar.qkv_out = a.qkv_out; ar.qkv_dump = a.qkv_dump; ar.nqkv = a.nqkv; ar.hm = a.hm;
-        if (!skp) ar = a;
-    }
+    if (proj) { a.ao = dev.upload(bf16_rows(ao_host, M, D, Mp, 0).data(), row_bytes); a.bproj = dev.upload(bproj, (size_t)D * 4); }
+    if (skp) { a.skip = dev.upload(bf16_rows(skip_host, M, D, Mp, 0).data(), row_bytes); a.bskip = dev.upload(bskip, (size_t)D * 4); }
+    // head-major qkv of the rows as images of n_patches + extras tokens (HeadMajor, dd_internal.h): [images][3 D / 64 units][Lp][64]
+    const size_t qkv_elems = qk ? (size_t)B * 3 * D * make_head_major(n_patches + extras, D / 64).Lp : 0;
+    if (qk) { a.qkv_out = dev.filled<bf16_t>(qkv_elems * 2, 0); a.qkv_dump = dev.alloc<bf16_t>(16384); }
+    block_tail_plan(a, B, n_patches, extras, D, D / 64, hidden, false);
+    if (ctx_dev_flags(c) & DD_DEV_MLP_EXTRAS_ONLY) { a.tiles_main = 0; a.n_main = 0; }   // time the hidden-split workgroups alone
+    const size_t part = (size_t)a.tiles_left * a.groups * 128 * D * sizeof(float);
+    a.partial = part ? dev.alloc<float>(part) : nullptr;
     auto once = [&]() -> hipError_t {
-        hipError_t e = launch_mlp_fused(a, D, s);
-        if (e == hipSuccess) e = launch_mlp_reduce(ar, D, s);
-        if (e == hipSuccess) e = launch_skip_rows_ln(a, D, s);
-        return e == hipSuccess ? launch_qkv_rows(a, D, s) : e;
+        const hipError_t e = launch_mlp_fused(a, D, s);
+        return e == hipSuccess ? block_tail_finish(a, D, s) : e;
     };
     DEV_HIP(dev, once());
     DEV_HIP(dev, hipStreamSynchronize(s));
@@ -128,25 +107,13 @@ static int block_tail_run(dd_ctx* c, int B, int n_patches, int extras, int D, in
         return r;
     };
     const size_t Mo = (size_t)round_up(M, 256) + 8, n16 = Mo * D * 2, n32 = Mo * D * 4;
-    const MlpImage im = MlpImage::of(D, hidden, proj, skp, qk);
-    std::vector<unsigned short> img(im.bytes() / 2, 0);
-    auto section = [&](size_t block) { return img.data() + im.at(block) / 2; };
-    std::vector<float> b1p(hidden);
-    if (proj) mlp_fused_pack_proj(D, wproj, host_f2bf, section(0));
-    mlp_fused_pack(D, hidden, w1, b1, w2, ln_in != nullptr, host_f2bf, section(im.mlp), b1p.data());
-    if (skp) mlp_fused_pack_skip(D, wskip, host_f2bf, section(im.skip));
-    if (qk) mlp_fused_pack_rows(D, 3 * D, wqkv, host_f2bf, section(im.qkv));
-    // the arguments, field by field as Backbone::block_tail fills them
-    MlpFusedArgs a{};
-    mlp_fused_plan(B, n_patches, extras, L, hidden, a);
-    if (last) { a.n_extra = 0; a.tiles_left = 0; }
-    if ((size_t)slab_rows < (size_t)a.tiles_left * a.groups * a.prows) return DD_ERR_INVALID;
-    if (plan_out) { plan_out[0] = a.tiles_main; plan_out[1] = a.tiles_left; plan_out[2] = a.groups; plan_out[3] = a.prows; }
+    const TailImage t = pack_tail_image(D, hidden, proj ? wproj : nullptr, w1, b1, w2, ln_in != nullptr, skp ? wskip : nullptr, qk ? wqkv : nullptr);
     DevScope dev(c);
+    MlpFusedArgs a{};
     // operands: Mo rows, the rows [M, Mo) hold `poison` bytes; X = nullptr in LayerNorm-in mode, as in the model
-    a.X = h_host ? dev.upload(bf16_rows(h_host, M, D, Mo, (unsigned char)poison).data(), n16) : nullptr; a.ldx = D;
-    a.wimg = (const char*)dev.upload(img.data(), img.size() * 2);
-    a.b1p = dev.upload(b1p.data(), (size_t)hidden * 4); a.b2 = dev.upload(b2, (size_t)D * 4);
+    a.X = h_host ? dev.upload(bf16_rows(h_host, M, D, Mo, (unsigned char)poison).data(), n16) : nullptr;
+    a.wimg = (const char*)dev.upload(t.img.data(), t.img.size() * 2);
+    a.b1p = dev.upload(t.b1p.data(), (size_t)hidden * 4); a.b2 = dev.upload(b2, (size_t)D * 4);
     if (ln_in) { a.ln_in_g = dev.upload(ln_in, (size_t)2 * D * 4); a.ln_in_b = a.ln_in_g + D; }
     if (xin_frag_host) {      // the patch rows come from the fragment buffer: their row-major copies hold `poison`
         std::vector<float> xr(xres_host, xres_host + Mo * D);
@@ -158,40 +125,34 @@ static int block_tail_run(dd_ctx* c, int B, int n_patches, int extras, int D, in
     }
     if (xout_frag_host) a.x_out_frag = dev.filled<float>((pe + 2 * guard) * 4, 0xFF) + guard;
     if (out_frag_host) a.out_frag = dev.filled<bf16_t>((pe + 2 * guard) * 2, 0xFF) + guard;
-    a.out = out_host ? dev.filled<bf16_t>(n16, 0xFF) : nullptr; a.ldo = D;
-    a.partial = slab_rows ? dev.filled<float>((size_t)slab_rows * D * 4, poison) : nullptr;
+    a.out = out_host ? dev.filled<bf16_t>(n16, 0xFF) : nullptr;
     if (proj) {
         a.ao = dev.upload((ao_frag_host ? rows_patch_poisoned(ao_host) : bf16_rows(ao_host, M, D, Mo, (unsigned char)poison)).data(), n16);
-        a.bproj = dev.upload(bproj, (size_t)D * 4); a.nproj = D / 32;
+        a.bproj = dev.upload(bproj, (size_t)D * 4);
         if (ao_frag_host) a.ao_frag = dev.upload(ao_frag_host, pe * 2);
-        a.reduce_set = 1;
     }
     if (skp) {
         a.skip = dev.upload((skip_frag_host ? rows_patch_poisoned(skip_host) : bf16_rows(skip_host, M, D, Mo, (unsigned char)poison)).data(), n16);
         if (skip_frag_host) a.skip_frag = dev.upload(skip_frag_host, pe * 2);
         if (tap) a.y_tap = dev.filled<float>(n32, 0xFF);
-        a.bskip = dev.upload(bskip, (size_t)D * 4); a.nskip = D / 16;
+        a.bskip = dev.upload(bskip, (size_t)D * 4);
     }
     if (lnout) { a.ln_out_g = dev.upload(ln_out, (size_t)2 * D * 4); a.ln_out_b = a.ln_out_g + D; a.ln_out = dev.filled<bf16_t>(n16, 0xFF); }
     if (frag) a.ln_out_frag = dev.filled<bf16_t>(n16, 0xFF);
     const size_t qkv_elems = qk ? ((size_t)B * 3 * (D / 64) * make_head_major(L, D / 64).Lp + 64) * 64 : 0;
-    if (qk) { a.qkv_out = dev.filled<bf16_t>(qkv_elems * 2, 0xFF); a.qkv_dump = dev.alloc<bf16_t>(16384); a.hm = make_head_major(L, D / 64); a.nqkv = 3 * D / 32; }
-    MlpFusedArgs fr = a;      // the reduce launch's: no norm1 rows where a skip_linear follows or the consumer normalises them itself
-    if (skp || frag) fr.ln_out = nullptr;
-    auto rest = [&]() -> hipError_t {
-        hipError_t e = launch_mlp_reduce(fr, D, s);
-        if (e == hipSuccess && skp) e = launch_skip_rows_ln(a, D, s, !frag);
-        if (e == hipSuccess && qk) e = launch_qkv_rows(a, D, s);
-        return e;
-    };
+    if (qk) { a.qkv_out = dev.filled<bf16_t>(qkv_elems * 2, 0xFF); a.qkv_dump = dev.alloc<bf16_t>(16384); }
+    block_tail_plan(a, B, n_patches, extras, D, D / 64, hidden, last != 0);
+    if ((size_t)slab_rows < (size_t)a.tiles_left * a.groups * a.prows) return DD_ERR_INVALID;
+    if (plan_out) { plan_out[0] = a.tiles_main; plan_out[1] = a.tiles_left; plan_out[2] = a.groups; plan_out[3] = a.prows; }
+    a.partial = slab_rows ? dev.filled<float>((size_t)slab_rows * D * 4, poison) : nullptr;
     auto once = [&]() -> hipError_t {
         const hipError_t e = launch_mlp_fused(a, D, s);
-        return e == hipSuccess ? rest() : e;
+        return e == hipSuccess ? block_tail_finish(a, D, s) : e;
     };
     const hipError_t first = dev.ok() ? launch_mlp_fused(a, D, s) : hipSuccess;
     if (first == hipErrorInvalidValue) return ctx_fail(c, DD_ERR_UNSUPPORTED, "block tail: a combination of modes launch_mlp_fused refuses");      // (refused before any launch)
     DEV_HIP(dev, first);
-    DEV_HIP(dev, rest());
+    DEV_HIP(dev, block_tail_finish(a, D, s));
     DEV_HIP(dev, hipStreamSynchronize(s));
     dev.download(xres_host, a.xres, n32);
     if (out_host) dev.download(out_host, a.out, n16);
@@ -233,43 +194,79 @@ int dd_dev_block_tail_frag(dd_ctx* c, int B, int n_patches, int extras, int D, i
 
 }  // extern "C"
 
-// dd_dev_qkv_attention_rows and dd_dev_qkv_attention_frag (out_frag_host non-null: the patch rows' output in fragment order)
-static int qkv_attention_run(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
-                             const float* xres_host, const float* ln, unsigned short* out_host, unsigned short* out_frag_host, int iters, void* stream,
-                             float* ms_out) {
-    if (!c || !h_host || !wqkv || !out_host || (xres_host && !ln) || B < 1 || iters < 0) return DD_ERR_INVALID;
+// The head-major qkv image of B images (HeadMajor: B 3 H units of Lp rows, 64 trailing rows) as launch_attention / launch_v_copy read it, from
+// row(u, l), the 64 floats of token l of unit u: 0xFF bytes (NaN) everywhere, then the rows l < L only -- the pad rows [L, Lp) of every unit, which the
+// qkv Linear never writes, and the trailing rows stay NaN
+template <typename Row>
+static std::vector<unsigned char> head_major_image(bool bf, int B, int L, int H, Row row) {
+    const size_t units = (size_t)B * 3 * H, Lp = (size_t)make_head_major(L, H).Lp;
+    std::vector<unsigned char> img((units * Lp + 64) * 64 * (bf ? 2 : 4), 0xFF);
+    for (size_t u = 0; u < units; ++u)
+        for (int l = 0; l < L; ++l) {
+            const float* r = row(u, l);
+            const size_t at = (u * Lp + l) * 64;
+            if (bf) for (int d = 0; d < 64; ++d) reinterpret_cast<unsigned short*>(img.data())[at + d] = host_f2bf(r[d]);
+            else std::memcpy(img.data() + at * 4, r, 64 * 4);
+        }
+    return img;
+}
+
+// The device operands of launch_qkv_attention / launch_v_identity on B images of 256 patch tokens behind `extras` extra tokens, from the norm1 rows
+// h_host [B L, D]: the patch rows in fragment order (what the fused block tail writes: MlpFusedArgs::ln_out_frag), the weight image, and the
+// extra-token rows row-major -- norm1 as bf16 (hx), or (xres_host) the fp32 residual stream the kernel normalises itself with ln.  The patch rows of
+// either, which the kernel must never read, hold 0xFF bytes (NaN)
+struct QkvOperands {
+    const bf16_t *hf, *img, *hx = nullptr;
+    const float *xres = nullptr, *ln_g = nullptr, *ln_b = nullptr, *bias = nullptr;
+};
+static QkvOperands qkv_operands(DevScope& dev, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
+                                const float* xres_host, const float* ln) {
     const int D = 64 * H;
-    if (!qkv_attention_supported(D, H, L, extras)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "qkv_attention: D = 512 / 768 / 1024, L = 256 + 1 or 2 extra tokens only");
-    hipStream_t s = (hipStream_t)stream;
     const size_t M = (size_t)B * L;
     std::vector<unsigned short> hb = bf16_rows(h_host, M, D, M, 0);
     std::vector<unsigned short> hf((size_t)B * 256 * D), img((size_t)3 * D * D);
-    for (int b = 0; b < B; ++b)          // the patch rows in fragment order (what the fused block tail writes: MlpFusedArgs::ln_out_frag)
+    for (int b = 0; b < B; ++b)
         for (int n = 0; n < 256; ++n)
             for (int k = 0; k < D; ++k)
                 hf[((((size_t)b * 8 + n / 32) * (D / 16) + k / 16) * 64 + (n % 32) + 32 * ((k % 16) / 8)) * 8 + k % 8] = hb[((size_t)b * L + extras + n) * D + k];
     qkv_attention_pack(D, H, wqkv, host_f2bf, img.data());
-    // the extra-token rows, row-major: norm1 rows as bf16 (hx), or the fp32 residual stream the kernel normalises itself; the patch rows of
-    // either, which the kernel must never read, hold 0xFF bytes (NaN)
-    std::vector<float> xr;
+    QkvOperands q;
+    q.hf = (const bf16_t*)dev.upload(hf.data(), hf.size() * 2);
+    q.img = (const bf16_t*)dev.upload(img.data(), img.size() * 2);
     if (xres_host) {
-        xr.resize(M * D);
+        std::vector<float> xr(M * D);
         std::memset(xr.data(), 0xFF, xr.size() * 4);
         for (int b = 0; b < B; ++b) std::memcpy(xr.data() + (size_t)b * L * D, xres_host + (size_t)b * L * D, (size_t)extras * D * 4);
+        q.xres = dev.upload(xr.data(), xr.size() * 4);
+        q.ln_g = dev.upload(ln, (size_t)2 * D * 4); q.ln_b = q.ln_g + D;
     } else {
         for (int b = 0; b < B; ++b) std::memset(hb.data() + ((size_t)b * L + extras) * D, 0xFF, (size_t)256 * D * 2);
+        q.hx = (const bf16_t*)dev.upload(hb.data(), hb.size() * 2);
     }
+    if (bqkv) q.bias = dev.upload(bqkv, (size_t)3 * D * 4);
+    return q;
+}
+
+// dd_dev_qkv_attention_rows, dd_dev_qkv_attention_frag (out_frag_host non-null: the patch rows' output in fragment order) and dd_dev_v_identity
+// (identity: launch_v_identity on the same operands, the extra-token rows from the residual stream)
+static int qkv_attention_run(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
+                             const float* xres_host, const float* ln, unsigned short* out_host, unsigned short* out_frag_host, bool identity, int iters,
+                             void* stream, float* ms_out) {
+    if (!c || !h_host || !wqkv || !out_host || (identity ? !xres_host || !ln : xres_host && !ln) || B < 1 || iters < 0) return DD_ERR_INVALID;
+    const int D = 64 * H;
+    if (!qkv_attention_supported(D, H, L, extras))
+        return ctx_fail(c, DD_ERR_UNSUPPORTED, std::string(identity ? "v_identity" : "qkv_attention") + ": D = 512 / 768 / 1024, L = 256 + 1 or 2 extra tokens only");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t M = (size_t)B * L;
     DevScope dev(c);
-    const bf16_t* dH = dev.upload(hf.data(), hf.size() * 2);
-    const bf16_t* dW = dev.upload(img.data(), img.size() * 2);
-    const bf16_t* dQ = xres_host ? nullptr : dev.upload(hb.data(), hb.size() * 2);
-    const float* dX = xres_host ? dev.upload(xr.data(), xr.size() * 4) : nullptr;
-    const float* dL = xres_host ? dev.upload(ln, (size_t)2 * D * 4) : nullptr;
+    const QkvOperands q = qkv_operands(dev, B, L, H, extras, h_host, wqkv, bqkv, xres_host, ln);
     bf16_t* dO = dev.filled<bf16_t>((M + 8) * D * 2, 0xFF);      // 8 canary rows behind the output
     const size_t pe = (size_t)B * 256 * D, guard = (size_t)8 * D;          // the fragment-order output: 8 canary rows in front and behind
     bf16_t* dF = out_frag_host ? dev.filled<bf16_t>((pe + 2 * guard) * 2, 0xFF) + guard : nullptr;
-    const float* dB = bqkv ? dev.upload(bqkv, (size_t)3 * D * 4) : nullptr;
-    auto once = [&]() { return launch_qkv_attention(dH, dW, dB, dQ, dX, dL, dL ? dL + D : nullptr, dO, B, L, H, D, extras, s, dF); };
+    auto once = [&]() {
+        return identity ? launch_v_identity(q.hf, q.img, q.bias, q.xres, q.ln_g, q.ln_b, dO, B, L, H, D, extras, s)
+                        : launch_qkv_attention(q.hf, q.img, q.bias, q.hx, q.xres, q.ln_g, q.ln_b, dO, B, L, H, D, extras, s, dF);
+    };
     DEV_HIP(dev, once());
     DEV_HIP(dev, hipStreamSynchronize(s));
     dev.download(out_host, dO, (M + 8) * D * 2);
@@ -282,47 +279,19 @@ extern "C" {
 
 int dd_dev_qkv_attention_rows(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
                               const float* xres_host, const float* ln, unsigned short* out_host, int iters, void* stream, float* ms_out) {
-    return qkv_attention_run(c, B, L, H, extras, h_host, wqkv, bqkv, xres_host, ln, out_host, nullptr, iters, stream, ms_out);
+    return qkv_attention_run(c, B, L, H, extras, h_host, wqkv, bqkv, xres_host, ln, out_host, nullptr, false, iters, stream, ms_out);
 }
 
 int dd_dev_qkv_attention_frag(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
                               const float* xres_host, const float* ln, unsigned short* out_host, unsigned short* out_frag_host, int iters,
                               void* stream, float* ms_out) {
     if (!out_frag_host) return DD_ERR_INVALID;
-    return qkv_attention_run(c, B, L, H, extras, h_host, wqkv, bqkv, xres_host, ln, out_host, out_frag_host, iters, stream, ms_out);
+    return qkv_attention_run(c, B, L, H, extras, h_host, wqkv, bqkv, xres_host, ln, out_host, out_frag_host, false, iters, stream, ms_out);
 }
 
 int dd_dev_v_identity(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
                       const float* xres_host, const float* ln, unsigned short* out_host, int iters, void* stream, float* ms_out) {
-    if (!c || !h_host || !wqkv || !out_host || !xres_host || !ln || B < 1 || iters < 0) return DD_ERR_INVALID;
-    const int D = 64 * H;
-    if (!qkv_attention_supported(D, H, L, extras)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "v_identity: D = 512 / 768 / 1024, L = 256 + 1 or 2 extra tokens only");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t M = (size_t)B * L;
-    std::vector<unsigned short> hb = bf16_rows(h_host, M, D, M, 0);
-    std::vector<unsigned short> hf((size_t)B * 256 * D), img((size_t)3 * D * D);
-    for (int b = 0; b < B; ++b)          // the patch rows in fragment order (MlpFusedArgs::ln_out_frag)
-        for (int n = 0; n < 256; ++n)
-            for (int k = 0; k < D; ++k)
-                hf[((((size_t)b * 8 + n / 32) * (D / 16) + k / 16) * 64 + (n % 32) + 32 * ((k % 16) / 8)) * 8 + k % 8] = hb[((size_t)b * L + extras + n) * D + k];
-    qkv_attention_pack(D, H, wqkv, host_f2bf, img.data());
-    // the fp32 residual stream: the extra-token rows only; the patch rows, which the kernel must never read, hold 0xFF bytes (NaN)
-    std::vector<float> xr(M * D);
-    std::memset(xr.data(), 0xFF, xr.size() * 4);
-    for (int b = 0; b < B; ++b) std::memcpy(xr.data() + (size_t)b * L * D, xres_host + (size_t)b * L * D, (size_t)extras * D * 4);
-    DevScope dev(c);
-    const bf16_t* dH = dev.upload(hf.data(), hf.size() * 2);
-    const bf16_t* dW = dev.upload(img.data(), img.size() * 2);
-    const float* dX = dev.upload(xr.data(), xr.size() * 4);
-    const float* dL = dev.upload(ln, (size_t)2 * D * 4);
-    bf16_t* dO = dev.filled<bf16_t>((M + 8) * D * 2, 0xFF);      // 8 canary rows behind the output
-    const float* dB = bqkv ? dev.upload(bqkv, (size_t)3 * D * 4) : nullptr;
-    auto once = [&]() { return launch_v_identity(dH, dW, dB, dX, dL, dL ? dL + D : nullptr, dO, B, L, H, D, extras, s); };
-    DEV_HIP(dev, once());
-    DEV_HIP(dev, hipStreamSynchronize(s));
-    dev.download(out_host, dO, (M + 8) * D * 2);
-    DEV_HIP(dev, time_launches(s, iters, once, ms_out));
-    return dev.status();
+    return qkv_attention_run(c, B, L, H, extras, h_host, wqkv, bqkv, xres_host, ln, out_host, nullptr, true, iters, stream, ms_out);
 }
 
 int dd_dev_v_copy(dd_ctx* c, int precision, int B, int L, int H, const float* qkv_host, void* out_host, int iters, void* stream, float* ms_out) {
@@ -330,17 +299,8 @@ int dd_dev_v_copy(dd_ctx* c, int precision, int B, int L, int H, const float* qk
     if (!c || (!bf && precision != DD_PREC_FP32) || B < 1 || L < 1 || H < 1 || !qkv_host || !out_host || iters < 0) return DD_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const int D = 64 * H;
-    const size_t esz = bf ? 2 : 4, Lp = (size_t)make_head_major(L, H).Lp;
-    const size_t qkv_elems = ((size_t)B * 3 * H * Lp + 64) * 64, out_elems = ((size_t)B * L + 8) * D;
-    // head-major image (HeadMajor): 0xFF bytes (NaN) everywhere, then the rows l < L only
-    std::vector<unsigned char> img(qkv_elems * esz, 0xFF);
-    for (size_t u = 0; u < (size_t)B * 3 * H; ++u)
-        for (int l = 0; l < L; ++l) {
-            const float* row = qkv_host + (u * L + l) * 64;
-            const size_t at = (u * Lp + l) * 64;
-            if (bf) for (int d = 0; d < 64; ++d) reinterpret_cast<unsigned short*>(img.data())[at + d] = host_f2bf(row[d]);
-            else std::memcpy(img.data() + at * 4, row, 64 * 4);
-        }
+    const size_t esz = bf ? 2 : 4, out_elems = ((size_t)B * L + 8) * D;
+    const std::vector<unsigned char> img = head_major_image(bf, B, L, H, [&](size_t u, int l) { return qkv_host + (u * L + l) * 64; });
     DevScope dev(c);
     const void* dQ = dev.upload(img.data(), img.size());
     void* dO = dev.filled(out_elems * esz, 0xFF);
@@ -374,19 +334,12 @@ int dd_dev_head_dec(dd_ctx* c, int M, int D, int pd, int tok_l, int tok_e, const
     if (probe && !head_dec_probe_supported(D)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "head_dec with the probe: D in {256, 512}");
     hipStream_t s = (hipStream_t)stream;
     if (split && !head_dec_probe_supported(D)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "head_dec as a split-bf16 product: D in {256, 512}");
-    std::vector<float> wg, dc;
-    fold_head_norm(D, pd, wdec, bdec, norm_g, norm_b, wg, dc);
-    if (split) {      // wg becomes the packed image (as floats: two bf16 each), dc's second half the row sums of hi + lo
-        const int nt = (pd + 15) / 16;
-        std::vector<unsigned short> img((size_t)(D / 32) * nt * 2 * 64 * 8);
-        pack_head_split(D, pd, wg.data(), host_f2bf, img.data(), dc.data() + pd);
-        wg.assign(img.size() / 2, 0.f);
-        std::memcpy(wg.data(), img.data(), img.size() * 2);
-    }
+    const HeadImage hi = pack_head_image(D, pd, wdec, bdec, norm_g, norm_b, split != 0);
     DevScope dev(c);
     const float* dX = dev.upload(x_host, (size_t)M * D * 4);
-    const float* dW = dev.upload(wg.data(), wg.size() * 4);
-    const float* dC = dev.upload(dc.data(), dc.size() * 4);
+    // split: the packed image in wg's place, and the constants whose second half are the row sums of hi + lo (HeadDecArgs::split)
+    const float* dW = split ? (const float*)dev.upload(hi.wsplit.data(), hi.wsplit.size() * 2) : dev.upload(hi.wg.data(), hi.wg.size() * 4);
+    const float* dC = dev.upload((split ? hi.dcs : hi.dc).data(), hi.dc.size() * 4);
     float* dO = dev.filled<float>((size_t)M * pd * 4, 0xFF);      // NaN: rows the launch does not decode stay recognisable
     HeadDecArgs ha{dX, dW, dC, dO, M, pd, tok_l, tok_e};
     ha.split = split ? 1 : 0;
@@ -527,21 +480,11 @@ int dd_dev_attention(dd_ctx* c, int precision, int B, int L, int H, const float*
     if (!c || (!bf && precision != DD_PREC_FP32) || B < 1 || L < 1 || H < 1 || !q || !k || !v || !out_host || iters < 0) return DD_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const int D = 64 * H;
-    const size_t esz = bf ? 2 : 4, Lp = (size_t)make_head_major(L, H).Lp;
-    const size_t qkv_elems = ((size_t)B * 3 * H * Lp + 64) * 64, out_elems = ((size_t)B * L + 8) * D;
-    // head-major image (HeadMajor): 0xFF bytes (NaN) everywhere, then the rows l < L only -- the pad rows [L, Lp) of every unit, which the qkv
-    // Linear never writes, and the 64 trailing rows stay NaN
-    std::vector<unsigned char> img(qkv_elems * esz, 0xFF);
-    const float* src[3] = {q, k, v};
-    for (int b = 0; b < B; ++b)
-        for (int j = 0; j < 3; ++j)
-            for (int hh = 0; hh < H; ++hh)
-                for (int l = 0; l < L; ++l) {
-                    const float* row = src[j] + (((size_t)b * H + hh) * L + l) * 64;
-                    const size_t at = ((((size_t)b * 3 + j) * H + hh) * Lp + l) * 64;
-                    if (bf) for (int d = 0; d < 64; ++d) reinterpret_cast<unsigned short*>(img.data())[at + d] = host_f2bf(row[d]);
-                    else std::memcpy(img.data() + at * 4, row, 64 * 4);
-                }
+    const size_t esz = bf ? 2 : 4, out_elems = ((size_t)B * L + 8) * D;
+    const float* src[3] = {q, k, v};      // unit u = (b 3 + j) H + head: q | k | v [B, H, L, 64]
+    const std::vector<unsigned char> img = head_major_image(bf, B, L, H, [&](size_t u, int l) {
+        return src[u / H % 3] + ((u / (3 * (size_t)H) * H + u % H) * L + l) * 64;
+    });
     DevScope dev(c);
     const void* dQ = dev.upload(img.data(), img.size());
     void* dO = dev.filled(out_elems * esz, 0xFF);
@@ -593,8 +536,7 @@ int dd_dev_embed(dd_ctx* c, int B, int C, int S, int P, int D, int extras, int n
     const int pd = C * P * P, L = extras + (S / P) * (S / P), Mp = round_up(B * L, 256);
     if (pd > 64) return ctx_fail(c, DD_ERR_UNSUPPORTED, "embed: patch_dim <= 64");
     hipStream_t s = (hipStream_t)stream;
-    std::vector<float> wt((size_t)pd * D);      // [D, pd] -> [pd, D], as finalize packs it (pack_embed)
-    for (int d = 0; d < D; ++d) for (int k = 0; k < pd; ++k) wt[(size_t)k * D + d] = w[(size_t)d * pd + k];
+    const std::vector<float> wt = transposed(w, D, pd);
     const size_t n_tok = ((size_t)Mp + 8) * D;
     EmbedArgs a{};
     a.B = B; a.C = C; a.S = S; a.P = P; a.D = D; a.L = L; a.extras = extras; a.num_classes = num_classes; a.normalize = normalize; a.Mp = Mp;
@@ -630,9 +572,7 @@ int dd_dev_time_mlp(dd_ctx* c, int B, int D, int L, int extras, int normalize, c
     if ((size_t)5 * D * 4 > 64 * 1024) return ctx_fail(c, DD_ERR_UNSUPPORTED, "time_mlp: 5 D floats of LDS");
     hipStream_t s = (hipStream_t)stream;
     const int H4 = 4 * D;
-    std::vector<float> w1t((size_t)D * H4), w2t((size_t)H4 * D);      // transposed as finalize packs them (pack_embed)
-    for (int j = 0; j < H4; ++j) for (int k = 0; k < D; ++k) w1t[(size_t)k * H4 + j] = w1[(size_t)j * D + k];
-    for (int d = 0; d < D; ++d) for (int k = 0; k < H4; ++k) w2t[(size_t)k * D + d] = w2[(size_t)d * H4 + k];
+    const std::vector<float> w1t = transposed(w1, H4, D), w2t = transposed(w2, D, H4);
     const size_t n_tok = (size_t)B * L * D;
     DevScope dev(c);
     StepState* st = dev.alloc<StepState>(sizeof(StepState));

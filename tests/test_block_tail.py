@@ -549,3 +549,49 @@ def test_poison_does_not_reach_an_output(mode):
         if a[k] is not None:
             assert same_bytes(a[k], b[k]), (mode, k)
     check(o, b)
+
+
+@gpu
+@pytest.mark.parametrize("M,extras,geom,skip", [(130, 0, (1, 130, 0), False), (10, 1, (5, 1, 1), False), (10, 1, (5, 1, 1), True)],
+                         ids=["M130-E0", "M10-E1", "M10-E1-skip"])
+def test_dd_dev_mlp_and_dd_dev_block_tail_return_the_same_bytes(M, extras, geom, skip):
+    """the two entry points take their launch arguments from one plan (csrc/launch_args.h), so the same rows come back bit for bit: two main tiles,
+    the second ragged; the hidden-split tiles and the reduce launch; those again with the next skip_linear.  D = 128, hidden = 256, norm2 in the
+    prologue, the projection in front, norm1 behind.  Only the padding differs (dd_dev_mlp: zero rows up to a multiple of 256; dd_dev_block_tail:
+    0xFF bytes), so the rows [0, M) are compared; a SKIP launch writes the bf16 copy of the extra-token rows only, and the patch rows of each
+    entry's buffer keep what it was filled with"""
+    from duodiff_amd.engine import Context
+    ctx = Context.get()
+    B, N, E = geom
+    D, hidden = 128, 256
+    assert B * (N + E) == M and E == extras
+    r = np.random.default_rng([M, extras, int(skip)])
+    f = lambda *shape, s=1.0: (s * r.standard_normal(shape)).astype(np.float32)
+    w1, b1, w2, b2 = f(hidden, D, s=0.05), f(hidden, s=0.2), f(D, hidden, s=0.05), f(D, s=0.2)
+    x, ao, wp, bp = f(M, D, s=1.5) + np.float32(0.3), f(M, D), f(D, D, s=0.05), f(D, s=0.2)
+    ln_in, ln_out = (np.stack([1 + 0.1 * r.standard_normal(D), 0.05 * r.standard_normal(D)]).astype(np.float32) for _ in range(2))
+    sk, ws, bs = (f(M, D, s=1.2), f(D, 2 * D, s=0.04), f(D, s=0.2)) if skip else (None, None, None)
+    ms = C.c_float(0)
+    # dd_dev_mlp: extras > 0: M / (1 + extras) images of one patch token; extras == 0: one image of M patch tokens
+    got, out, hout = x.copy(), np.zeros((M, D), np.uint16), np.zeros((M, D), np.uint16)
+    ctx.check(ctx.lib.dd_dev_mlp(ctx.handle, M, D, hidden, extras, P(x), P(w1), P(b1), P(w2), P(b2), P(got), P(out), P(ln_in), P(ln_out), P(hout), 0,
+                                 None, C.byref(ms), P(ao), P(wp), P(bp), P(sk), P(ws), P(bs), None, None))
+    # dd_dev_block_tail: the same rows as B images of N patch tokens behind E extra tokens
+    Mo = round_up(M, 256) + 8
+    xres = np.full((Mo, D), NAN32, np.uint32).view(np.float32)
+    xres[:M] = x
+    tout, tln = np.zeros((Mo, D), np.uint16), np.zeros((Mo, D), np.uint16)
+    srows = (B * E + 31) // 32 * 16 * 32 + 8
+    slab = np.zeros((srows, D), np.float32)
+    ctx.check(ctx.lib.dd_dev_block_tail(ctx.handle, B, N, E, D, hidden, 0, 0xFF, None, P(w1), P(b1), P(w2), P(b2), P(ln_in), P(ao), P(wp), P(bp),
+                                        P(ln_out), P(sk), P(ws), P(bs), None, P(xres), P(tout), P(tln), None, None, None, P(slab), srows, None, 0,
+                                        None, C.byref(ms)))
+    patch = (np.arange(M) % (N + E)) >= E
+    assert np.isfinite(got).all()
+    assert same_bytes(got, xres[:M]), "xres"
+    assert same_bytes(hout, tln[:M]), "ln_out"
+    written = ~patch if skip else np.ones(M, bool)
+    assert same_bytes(out[written], tout[:M][written]), "bf16 copy"
+    assert not out[~written].any() and untouched(tout[:M][~written]), "a SKIP launch wrote the bf16 copy of patch rows"
+    if E:
+        assert not np.array_equal(out[~patch], np.zeros_like(out[~patch])), "the extra-token rows' bf16 copy was not written"

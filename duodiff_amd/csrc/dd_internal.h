@@ -117,6 +117,7 @@ bool gemm_prefers_128(int M, int N, int K, int K1, int num_cus);   // the 256 x 
 bool gemm_splitk_supported(int M, int N, int K, int K1, int splits);
 hipError_t launch_gemm_splitk(const GemmArgs<bf16_t>& a, hipStream_t s, int num_cus);
 int device_num_cus();
+hipError_t init_gemm_kernels();
 
 // ---- fused MLP (mlp_fused.hip): x += fc2(gelu(fc1(h) + b1)) + b2 in one launch
 struct MlpFusedArgs {
@@ -296,6 +297,7 @@ hipError_t launch_layernorm_frag(const float* x, const float* gamma, const float
 // qkv: head-major (HeadMajor, make_head_major(L, H)); out: [B * L, D] rows
 template <typename T>
 hipError_t launch_attention(const T* qkv, T* out, int B, int L, int H, int D, hipStream_t s);
+hipError_t init_attention_kernels();
 // attn.qkv + attention in one launch (attention.hip qkv_attention_kernel): h = norm1 of the patch rows in fragment order
 // (MlpFusedArgs::ln_out_frag); the extra-token rows: hx = norm1 row-major [B L, D], or hx = nullptr and xres / ln_g / ln_b = the fp32
 // residual stream and this block's norm1 parameters (the kernel normalises the rows itself); wimg from qkv_attention_pack;
@@ -359,6 +361,7 @@ struct FinalArgs {
     const KnownRow* ktab = nullptr;
 };
 hipError_t launch_final(const FinalArgs& a, hipStream_t s);
+hipError_t init_rowops_kernels();
 
 // final LayerNorm + decoder_pred in one launch (rowops.hip); wg = decoder weight * norm gamma [pd, D], c = decoder bias + W . norm beta
 struct HeadDecArgs {
@@ -442,7 +445,7 @@ struct ThresholdArgs {
 };
 hipError_t launch_threshold_step(const ThresholdArgs& a, hipStream_t s);
 
-// AttentionProbe operands of one layer (capi.hip finalize folds them): u [D], Wv^T [D, D], bv [D], W0^T [D, D], b0 [D], w2 [D], b2 [1]
+// AttentionProbe operands of one layer (model.hip finalize folds them): u [D], Wv^T [D, D], bv [D], W0^T [D, D], b0 [D], w2 [D], b2 [1]
 struct AttnProbeW { const float *u, *wvt, *bv, *w0t, *b0, *w2, *b2; };
 hipError_t launch_ee_attn_probe(const float* x, const AttnProbeW& w, float* out, int B, int L, int D, hipStream_t s);
 // probe row = (t_mul ? st->t_final * t_mul : 0) + add of the [n_probe, D] / [n_probe] tables; srow: [B, L] fp32 scratch (the rows' sigmoids)

@@ -2,11 +2,10 @@
 // dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather): test scaffolding, not product.  Each one owns its host operands, device buffers, canaries and
 // downloads, and nothing of the launch: the weight images come from finalize's packers and the launch arguments from the model's builders (launch_args.h:
 // dd_dev_mlp and dd_dev_block_tail* run block_tail_plan / block_tail_finish exactly as Backbone::block_tail does), then `iters` further launch sequences
-// are timed.  Buffers, transfers, timing and HIP errors go through one DevScope (dev_scope.h); the context is reached through its accessors only.
+// are timed.  Buffers, transfers, timing and HIP errors go through one DevScope (dev_scope.h); of the context it reads num_cus and dev_flags (engine_state.h).
 #include "../../include/duodiff.h"
 #include "../../include/duodiff_dev.h"
-#include "dd_internal.h"
-#include "dev_scope.h"
+#include "engine_state.h"
 #include "launch_args.h"
 
 #include <cstring>
@@ -55,7 +54,7 @@ int dd_dev_mlp(dd_ctx* c, int M, int D, int hidden, int extras, const float* x_h
     const size_t qkv_elems = qk ? (size_t)B * 3 * D * make_head_major(n_patches + extras, D / 64).Lp : 0;
     if (qk) { a.qkv_out = dev.filled<bf16_t>(qkv_elems * 2, 0); a.qkv_dump = dev.alloc<bf16_t>(16384); }
     block_tail_plan(a, B, n_patches, extras, D, D / 64, hidden, false);
-    if (ctx_dev_flags(c) & DD_DEV_MLP_EXTRAS_ONLY) { a.tiles_main = 0; a.n_main = 0; }   // time the hidden-split workgroups alone
+    if (c->dev_flags & DD_DEV_MLP_EXTRAS_ONLY) { a.tiles_main = 0; a.n_main = 0; }   // time the hidden-split workgroups alone
     const size_t part = (size_t)a.tiles_left * a.groups * 128 * D * sizeof(float);
     a.partial = part ? dev.alloc<float>(part) : nullptr;
     auto once = [&]() -> hipError_t {
@@ -347,7 +346,7 @@ int dd_dev_head_dec(dd_ctx* c, int M, int D, int pd, int tok_l, int tok_e, const
         ha.pw_base = dev.upload(probe_w, (size_t)D * 4); ha.pb_base = dev.upload(probe_b, 4);
         ha.srow = dev.filled<float>((size_t)M * 4, 0xFF);     // (probe row 0: t_mul = add = 0, the step state is not read)
     }
-    auto once = [&]() { return launch_head_dec(ha, D, ctx_num_cus(c), s); };
+    auto once = [&]() { return launch_head_dec(ha, D, c->num_cus, s); };
     DEV_HIP(dev, once());
     DEV_HIP(dev, hipStreamSynchronize(s));
     dev.download(dec_host, dO, (size_t)M * pd * 4);
@@ -406,15 +405,15 @@ int dd_dev_gemm(dd_ctx* c, int precision, int M, int N, int K, int K1, const flo
             GemmArgs<float> g{(const float*)dA, (const float*)dA2, (const float*)dW, dBias, dX, (float*)dO, M, N, K, K1, lda,
                               K1 < K ? lda2 : lda, ldo};
             g.hm = hm;
-            return launch_gemm<float>(g, epilogue, s, num_cus ? num_cus : ctx_num_cus(c));
+            return launch_gemm<float>(g, epilogue, s, num_cus ? num_cus : c->num_cus);
         }
         GemmArgs<bf16_t> g{(const bf16_t*)dA, (const bf16_t*)dA2, (const bf16_t*)dW, dBias, dX, (bf16_t*)dO, M, N, K, K1, lda,
                            K1 < K ? lda2 : lda, ldo};
         g.hm = hm;
         g.tile128 = tile128;
-        if (splits == 0) return launch_gemm<bf16_t>(g, epilogue, s, num_cus ? num_cus : ctx_num_cus(c));
+        if (splits == 0) return launch_gemm<bf16_t>(g, epilogue, s, num_cus ? num_cus : c->num_cus);
         g.partial = dP; g.splits = splits;
-        hipError_t e = launch_gemm_splitk(g, s, num_cus ? num_cus : ctx_num_cus(c));
+        hipError_t e = launch_gemm_splitk(g, s, num_cus ? num_cus : c->num_cus);
         if (e != hipSuccess) return e;
         const float* lg = ln ? dLn : nullptr;
         return launch_reduce_ln(splitk_reduce_args(g, resid, lg, lg ? lg + N : nullptr, dH, dF, tok_l, tok_e), N, s);

@@ -1,6 +1,6 @@
 // Host-side scope of one call that owns device buffers and times launches for its own duration (dev_harness.hip: the single-kernel development
-// entry points of include/duodiff_dev.h; capi.hip: dd_bench_gemm), and the context accessors of the translation units that do not define dd_ctx.
-// Not included by any kernel translation unit.
+// entry points of include/duodiff_dev.h; capi.hip: dd_bench_gemm), and the one function through which every host unit reports an error on the
+// context (dd_ctx itself: engine_state.h, which includes this header).  Not included by any kernel translation unit.
 #pragma once
 #include "../../include/duodiff.h"
 #include "host_arena.h"
@@ -13,13 +13,9 @@ struct dd_ctx;
 
 namespace dd {
 
-// dd_ctx is defined in capi.hip only
-int ctx_fail(dd_ctx* c, int code, const std::string& msg);   // sets the context's error string, returns code
-int ctx_device(dd_ctx* c);
-int ctx_num_cus(dd_ctx* c);
+int ctx_fail(dd_ctx* c, int code, const std::string& msg);   // sets the context's error string, returns code (model.hip)
 
 #pragma GCC visibility push(hidden)   // what follows stays out of the library's dynamic symbol table
-unsigned ctx_dev_flags(dd_ctx* c);    // dd_dev_set_flags
 
 inline int fail_hip(dd_ctx* c, hipError_t e, const char* what) {
     return ctx_fail(c, DD_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));

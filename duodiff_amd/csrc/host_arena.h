@@ -1,4 +1,4 @@
-// Host-side layout of one device allocation (capi.hip, vae.hip: model weights and activation workspaces).  Regions are taken in order,
+// Host-side layout of one device allocation (model.hip, vae.hip: model weights and activation workspaces).  Regions are taken in order,
 // each 256-byte aligned; a region names the pointer field it will be bound to, and bind() sets every such field once the allocation
 // exists.  A region that is not taken leaves its field null.  Not included by any kernel translation unit.
 #pragma once

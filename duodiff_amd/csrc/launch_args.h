@@ -1,4 +1,4 @@
-// What the model (capi.hip: Backbone, finalize) and the single-kernel development entry points (dev_harness.hip) share on the host side, each
+// What the model (forward.hip: Backbone; model.hip: finalize) and the single-kernel development entry points (dev_harness.hip) share on the host side, each
 // defined once, so that a development entry point packs what finalize packs and launches what the model launches: the weight-image packers (the
 // fused block tail's image, the transposed embed / time_embed weights, an output head's folded operands) and the launch plans (the block tail's
 // derived arguments, reduce arguments and follow-up launches; the row-resident and split-K row passes).  Callers own operands and buffers only.

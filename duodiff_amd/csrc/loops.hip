@@ -1,0 +1,558 @@
+// The device-resident sampling loops: the half-batch chains, the captured step of each loop and its replay, staging of the loops' tables and
+// known regions, in-context launch timing; every dd_sample* entry point except dd_sample_step, and dd_profile_steps*.  Above forward.hip, below
+// capi.hip (engine_state.h).
+//
+// Host-side restatement of: get_samples DDPM branch and backbone switch (reference sampler.py:128-139), the early-exit sampler (eesampler.py:56-81).
+#include "../../include/duodiff.h"
+#include "../../include/duodiff_dev.h"
+#include "engine_state.h"
+
+#include <algorithm>
+#include <functional>
+
+using namespace dd;
+
+namespace {
+
+Mods guided(const dd_guidance* g) { return Mods{.g = g, .missing = g ? nullptr : "null dd_guidance"}; }
+Mods autoguided(const dd_autoguidance* ag) { return Mods{.ag = ag, .missing = ag ? nullptr : "null dd_autoguidance"}; }
+Mods in_region(const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr) { return Mods{.g = g, .ag = ag, .kr = kr, .region = true}; }
+Mods thresholding(const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr, const dd_x0_threshold* thr) {
+    return Mods{.g = g, .ag = ag, .kr = kr, .region = kr != nullptr, .thr = thr, .thresholded = true};
+}
+
+// dd_sample splits an even batch of at least 32 images into two half-batch chains (same-box A/B, profiles/r04/ab_chains.txt): the
+// fused-path models (their kernels have strong MFMA / HBM phase structure and one tile per CU at the benchmark batch: CelebA B = 128
+// +10.5 %) and GEMM-path models whose launches leave CUs idle (ImageNet-256 latents, B = 32: +9 %) as they are; GEMM-path models at
+// large batches (ImageNet-64, B = 256) with the persistent GEMM grids of both chains sized for HALF the CUs (chain_gemm_cus): a full-size
+// grid holds every CU's LDS, two of them only queue behind each other (-4.7 %), two half-size ones run side by side (+4.7 %).
+// Development flags force the split on for any even batch, or switch it off.
+bool use_chains(dd_ctx* c, dd_model* m, int B, bool early_exit_loop) {
+    if ((c->dev_flags & DD_DEV_NO_CHAINS) || (B & 1) || B < 2 || ((m->ee_type >= 0) != early_exit_loop)) return false;
+    return B >= 32 || (c->dev_flags & DD_DEV_FORCE_CHAINS);
+}
+int chain_gemm_cus(dd_ctx* c, dd_model* m, int B) {
+    const bool fused = m->prec == DD_PREC_BF16 && m->fused_mlp;
+    if (fused || (long long)B * m->L <= 32768) return c->num_cus;
+    const int half = c->num_cus / 2 / 8 * 8;
+    return half >= 8 ? half : c->num_cus;
+}
+// a failure between the fork and the join of a chained call must not leave the side stream running on the second chain's buffers behind
+// the caller's back: armed after the fork, disarmed by the regular join
+struct SideJoin {
+    dd_ctx* c; bool armed;
+    ~SideJoin() { if (armed && c->side) (void)hipStreamSynchronize(c->side); }
+};
+
+// the model's captured step of this kind for this chain and key: reused, or captured now from enqueue()
+template <typename F>
+int get_graph(dd_ctx* c, dd_model* m, GraphKind kind, int chain, const GraphKey& key, hipStream_t s, F&& enqueue) {
+    hipGraphExec_t& exec = m->graph[kind][chain];
+    if (exec && m->gkey[kind][chain] == key) return DD_OK;
+    if (exec) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
+    hipGraph_t g = nullptr;
+    DD_HIP(c, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    const int r = enqueue();
+    const hipError_t e2 = hipStreamEndCapture(s, &g);
+    if (r) { if (g) (void)hipGraphDestroy(g); return r; }
+    if (e2 != hipSuccess) return fail_hip(c, e2, "hipStreamEndCapture");
+    const hipError_t e3 = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    if (e3 != hipSuccess) { exec = nullptr; return fail_hip(c, e3, "hipGraphInstantiate"); }
+    m->gkey[kind][chain] = key;
+    ++c->graph_captures;
+    return DD_OK;
+}
+
+// One chain's share of a sampling loop's batch: the caller's images [b0, b0 + B), at x / y in the buffers the loop runs on
+// (mods: the loop's, with the chain's share of the known region)
+struct Slice { int chain, chains; float* x; const int64_t* y; int B, b0; Mods mods; };
+
+// A sampling loop as run_loop drives it: the entry point has run its checks and supplies what differs between the loops
+struct Loop {
+    GraphKind kind;
+    dd_model* first;
+    dd_model* late;      // the model the loop may switch to (its graphs are captured along with first's), or null
+    int steps;
+    int switch_at;       // late runs steps [switch_at, steps), ev[1] is recorded in front of step switch_at; -1: ev[1] behind the join and the tail
+    float* x_dev;
+    const int64_t* y_dev;
+    int B;
+    Mods mods;           // (the early-exit loop: none)
+    bool use_graph;
+    std::function<hipError_t(StepState*, hipStream_t)> set_state;                   // a chain's step state at the start of the loop
+    std::function<void(GraphKey&, const Slice&)> key;                                // the loop's own fields of a chain's graph key
+    std::function<int(dd_model*, const Chain&, const Slice&, hipStream_t)> step;     // one step of one chain
+    std::function<int(int chains, hipStream_t)> tail = nullptr;                      // behind the join of the chains
+};
+
+// dd_sample, dd_sample_affine (both also guided) and dd_sample_early_exit: staging, the half-batch chains, graph capture and replay, timing
+int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
+    const dd_guidance* g = L.mods.g;
+    const dd_autoguidance* ag = L.mods.ag;
+    // Two half-batch chains (graph replays only).  Images are independent and a row's path through the kernels does not depend on the
+    // batch size, so chain 0 = images [0, B0) on the caller's stream and chain 1 = images [B0, B) on the context's side stream compute
+    // bit for bit what the undivided batch computes (Philox pixel ids carry the image offset) -- with the two chains free to drift apart,
+    // so that one's HBM-bound phases (row prologues / epilogues, attention row fetch) run under the other's MFMA phases.
+    // Guided: the decisions are made on the 2 B backbone rows and the split is by image (chain 0 takes the larger half, on the workspace
+    // sized for max_batch >= 2 B rows; the second chain's workspace holds (max_batch + 1) / 2 rows >= 2 * floor(B / 2)).
+    const bool ee = L.kind == GRAPH_EARLY_EXIT;
+    const dd_pag* pag = L.mods.pag;
+    const bool paired = g || pag;        // B images as 2 B backbone rows (stage_guided's layout): classifier-free or perturbed-attention guidance
+    const int rows = paired ? 2 * L.B : L.B;
+    const bool chained = L.use_graph && use_chains(c, L.first, rows, ee) && (!L.late || use_chains(c, L.late, rows, ee)) && (!paired || L.B >= 2);
+    const int chains = chained ? 2 : 1;
+    const int B0 = chained ? (paired ? (L.B + 1) / 2 : L.B / 2) : L.B;
+    c->last_chains = chains;
+    // the captured persistent GEMM grids: halved for both chains of a large GEMM-path batch (the early-exit loop keeps the full grids)
+    int cus = chained && !ee ? std::min(chain_gemm_cus(c, L.first, rows), L.late ? chain_gemm_cus(c, L.late, rows) : c->num_cus) : c->num_cus;
+    if (chained && ag) cus = std::min(cus, chain_gemm_cus(c, ag->guide, rows));
+    // the loop runs on x_run / y_run: guided, or with graphs, the context's staging buffers (copied in here, copied back at the end)
+    const size_t chw = (size_t)L.first->cfg.in_chans * L.first->cfg.img_size * L.first->cfg.img_size;
+    float* x_run = L.x_dev;
+    const int64_t* y_run = L.y_dev;
+    int rc = DD_OK;
+    if (paired) rc = stage_guided(c, L.x_dev, L.y_dev, L.B, B0, chw, g ? g->null_label : -1, s, &x_run, &y_run);
+    else if (L.use_graph) rc = stage_inputs(c, L.x_dev, L.y_dev, L.B, (size_t)L.B * chw, s, &x_run, &y_run);
+    if (rc) return rc;
+    auto slice = [&](int k) {
+        const size_t row = k ? (paired ? 2 * (size_t)B0 : (size_t)B0) : 0;     // the chain's first row in x_run / y_run
+        Slice sl{k, chains, x_run + row * chw, y_run ? y_run + row : nullptr, k ? L.B - B0 : B0, k ? B0 : 0, L.mods};
+        sl.mods.kn = L.mods.kn.at(sl.b0, L.first);
+        return sl;
+    };
+    auto chain = [&](dd_model* m, int k) { return Chain{&m->ws[k], c->st[k], cus, !chained}; };
+    if (L.use_graph) {
+        for (int k = 0; k < chains; ++k) {
+            const Slice sl = slice(k);
+            GraphKey key{sl.x, sl.y, sl.B, 0, 0, cus, nullptr};
+            key.b0 = sl.b0;
+            key.guide(g);
+            key.perturb(pag);
+            key.kx0 = sl.mods.kn.x0; key.kmask = sl.mods.kn.mask; key.ktab = sl.mods.kn.ktab;
+            L.key(key, sl);
+            for (dd_model* m : {L.first, L.late}) {
+                if (!m) continue;
+                if (k && (rc = ensure_chain_ws(c, m, s))) return rc;
+                GraphKey mkey = key;
+                if (ag) {   // the step of the guide model itself is the unguided loop's step, under the unguided loop's key
+                    if (m->cfg.num_classes <= 0) mkey.y = nullptr;
+                    if (m != ag->guide) {
+                        if (k && (rc = ensure_chain_ws(c, ag->guide, s))) return rc;
+                        mkey.aguide = ag->guide; mkey.aserial = ag->guide->serial; mkey.gscale = __builtin_bit_cast(unsigned, ag->scale);
+                    }
+                }
+                if ((rc = get_graph(c, m, L.kind, k, mkey, s, [&] { return L.step(m, chain(m, k), sl, s); }))) return rc;
+            }
+        }
+    }
+    for (int k = 0; k < chains; ++k) DD_HIP(c, L.set_state(c->st[k], s));
+    if (chained) {
+        DD_HIP(c, hipEventRecord(c->ev_fork, s));                 // the side stream starts behind the staging copies and the state
+        DD_HIP(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
+    }
+    SideJoin side_join{c, chained};
+    DD_HIP(c, hipEventRecord(c->ev[0], s));
+    dd_model* cur = L.first;
+    for (int k = 0; k < L.steps; ++k) {
+        if (k == L.switch_at) {
+            cur = L.late;
+            DD_HIP(c, hipEventRecord(c->ev[1], s));
+        }
+        if (L.use_graph) {
+            DD_HIP(c, hipGraphLaunch(cur->graph[L.kind][0], s));
+            if (chained) DD_HIP(c, hipGraphLaunch(cur->graph[L.kind][1], c->side));
+        } else if ((rc = L.step(cur, chain(cur, 0), slice(0), s))) {
+            return rc;
+        }
+    }
+    if (L.switch_at == L.steps) DD_HIP(c, hipEventRecord(c->ev[1], s));
+    if (chained) {
+        DD_HIP(c, hipEventRecord(c->ev_join, c->side));
+        DD_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0));
+        side_join.armed = false;
+    }
+    if (L.tail && (rc = L.tail(chains, s))) return rc;
+    if (L.switch_at < 0) DD_HIP(c, hipEventRecord(c->ev[1], s));
+    DD_HIP(c, hipEventRecord(c->ev[2], s));
+    if (paired) return unstage_guided(c, L.x_dev, x_run, L.B, B0, chw, s);
+    if (x_run != L.x_dev) DD_HIP(c, hipMemcpyAsync(L.x_dev, x_run, (size_t)L.B * chw * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return DD_OK;
+}
+
+// dd_sample_early_exit's scratch for B images: eps | cls | outs.  Linear in B: chain 1's block starts behind chain 0's B0 images.
+size_t ee_scratch_elems(const dd_model* m, int B) {
+    const size_t chw = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
+    return (size_t)B * ((1 + m->cfg.depth) * chw + m->cfg.depth);
+}
+
+// dd_profile_steps (chains == 1) and dd_profile_steps_chained (chains == 2: dd_sample's two half-batch chains enqueued eagerly on `stream`
+// and on the context's side stream, step by step -- the launches overlap the other chain's kernels exactly as the graph replays of the
+// timed loop do): an event pair around every launch of the selected kind in every chain; out: the average ms of one such launch
+int profile_steps(dd_ctx* c, dd_model* m, float* x_dev, const int64_t* y_dev, int t_start, int steps, int B, int chains, void* stream,
+                  float* ms_out, int* launches_out) {
+    int rc = check_call(c, m, B, y_dev);
+    if (rc) return rc;
+    const bool chained = chains == 2;
+    if (!x_dev || !ms_out || steps < 1 || t_start > 999 || t_start - steps + 1 < 0 || (chained && ((B & 1) || B < 2)))
+        return ctx_fail(c, DD_ERR_INVALID, "bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    const hipStream_t cs[2] = {s, c->side};
+    if (chained && (rc = ensure_chain_ws(c, m, s))) return rc;
+    const int B0 = B / chains;
+    const size_t chw = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
+    const int cus = chained ? chain_gemm_cus(c, m, B) : c->num_cus;     // (both chains' persistent GEMM grids sized as dd_sample sizes them)
+    if (chained) {
+        DD_HIP(c, hipEventRecord(c->ev_fork, s));
+        DD_HIP(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
+    }
+    SideJoin side_join{c, chained};
+    m->time_fc1 = true;
+    m->fc1_used = 0;
+    for (int i = 0; i < steps && !rc; ++i) {
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < chains && e == hipSuccess; ++k) e = launch_set_state(c->st[k], t_start - i, 12345ull, cs[k]);
+        if (e != hipSuccess) { m->time_fc1 = false; return fail_hip(c, e, "set_state"); }
+        for (int k = 0; k < chains && !rc; ++k) {
+            const int b0 = k ? B0 : 0;
+            rc = enqueue_step(c, m, Chain{&m->ws[k], c->st[k], cus, !chained}, x_dev + (size_t)b0 * chw, y_dev ? y_dev + b0 : nullptr,
+                              k ? B - B0 : B0, cs[k], {.noise_mode = DD_NOISE_PHILOX, .variance = DD_VAR_BETA_TILDE, .b0 = b0});
+        }
+    }
+    m->time_fc1 = false;
+    if (rc) return rc;
+    if (chained) {
+        DD_HIP(c, hipEventRecord(c->ev_join, c->side));
+        DD_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0));
+        side_join.armed = false;
+    }
+    DD_HIP(c, hipStreamSynchronize(s));
+    double total = 0.0;
+    for (size_t i = 0; i + 1 < m->fc1_used; i += 2) {
+        float ms = 0.f;
+        DD_HIP(c, hipEventElapsedTime(&ms, m->fc1_events[i], m->fc1_events[i + 1]));
+        total += ms;
+    }
+    const int n = (int)(m->fc1_used / 2);
+    *ms_out = n ? (float)(total / n) : 0.f;
+    if (launches_out) *launches_out = n;
+    return DD_OK;
+}
+
+// Every check the model-driven loops share, before anything is enqueued and in this order (a: any of their argument structs): the entry's
+// own struct, the known region (include/duodiff.h dd_known_region), the loop's exclusion of early-exit models (no_early_exit: the
+// rejection, or null), the models under the guidance in use, the loop's own arguments (own_checks), the noise mode (host_noise: the
+// rejection of a host noise mode) and the image shape of the two models
+template <typename Args, typename Own>
+int check_loop(dd_ctx* c, const Args* a, const Mods& mo, const char* no_early_exit, const char* host_noise, Own&& own_checks) {
+    if (c && mo.missing) return ctx_fail(c, DD_ERR_INVALID, mo.missing);
+    if (!c || !a) return DD_ERR_INVALID;
+    const dd_known_region* kr = mo.kr;
+    if (mo.region) {
+        if (!kr) return ctx_fail(c, DD_ERR_INVALID, "null dd_known_region");
+        if (!kr->x0_dev || !kr->mask_dev || !kr->ka || !kr->kb) return ctx_fail(c, DD_ERR_INVALID, "null member of dd_known_region");
+        if (mo.g && mo.ag) return ctx_fail(c, DD_ERR_INVALID, "classifier-free guidance and autoguidance are exclusive");
+        if (a->noise_mode == DD_NOISE_BUFFER)
+            return ctx_fail(c, DD_ERR_INVALID, "a known region draws its noise on the device; for host noise drive dd_forward, the step and dd_known_blend");
+        for (dd_model* m : {a->first, a->late})
+            if (m && m->ctx == c && m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, "a known region is not supported for early-exit models");
+    }
+    for (dd_model* m : {a->first, a->late})
+        if (no_early_exit && m && m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, no_early_exit);
+    if (mo.pag && a->first && a->late == a->first && mo.pag->layers_first != mo.pag->layers_late)
+        return ctx_fail(c, DD_ERR_INVALID, "first and late are one model: its two perturbed-attention masks must agree");
+    auto check = [&](dd_model* m) {
+        if (mo.pag) return check_perturbed(c, m, a->B, a->y_dev, mo.pag, m && m == a->late ? mo.pag->layers_late : mo.pag->layers_first);
+        return mo.g ? check_guided(c, m, a->B, a->y_dev, mo.g) : check_call(c, m, a->B, a->y_dev);
+    };
+    int rc = mo.ag ? check_autoguided(c, a->first, a->late, a->B, a->y_dev, mo.ag) : check(a->first);
+    if (rc) return rc;
+    if (!mo.ag && a->late && (rc = check(a->late))) return rc;
+    if ((rc = own_checks())) return rc;
+    if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE) return ctx_fail(c, DD_ERR_INVALID, host_noise);
+    if (a->late) {
+        const dd_config &f = a->first->cfg, &l = a->late->cfg;
+        if (f.img_size != l.img_size || f.in_chans != l.in_chans) return ctx_fail(c, DD_ERR_INVALID, "first and late model disagree on image shape");
+    }
+    return DD_OK;
+}
+// the own checks of a table-driven loop (dd_sample_affine, dd_sample_multistep: a's fields are dd_affine_sample_args')
+template <typename Args>
+int check_table(dd_ctx* c, const Args* a) {
+    if (!a->x_dev || !a->t || !a->a || !a->b || !a->c || !a->noise) return ctx_fail(c, DD_ERR_INVALID, "null tensor / table");
+    if (a->n_steps < 1 || a->n_steps > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "n_steps outside [1, 2^20]");
+    if (a->counter_base < 0 || a->counter_base > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "counter_base outside [0, 2^20]");
+    return DD_OK;
+}
+
+// `rows` rows, row(i) each, into the table's device buffer on s.  The host copy an earlier upload may still be reading is left alone
+// until that upload has finished.
+template <typename Row, typename F>
+int upload_rows(dd_ctx* c, RowTable<Row>& t, size_t rows, hipStream_t s, F&& row) {
+    if (int rc = t.dev.grow(c, rows)) return rc;
+    if (t.uploaded) DD_HIP(c, hipEventSynchronize(t.uploaded));
+    else DD_HIP(c, hipEventCreateWithFlags(&t.uploaded, hipEventDisableTiming));
+    t.host.resize(rows);
+    for (size_t i = 0; i < rows; ++i) t.host[i] = row(i);
+    DD_HIP(c, hipMemcpyAsync(t.dev.p, t.host.data(), rows * sizeof(Row), hipMemcpyHostToDevice, s));
+    DD_HIP(c, hipEventRecord(t.uploaded, s));
+    return DD_OK;
+}
+// the step table of dd_sample_affine / dd_sample_multistep on the device: n rows + one more whose timestep the last step hands on (never used)
+template <typename Args>
+int upload_atab(dd_ctx* c, const Args* a, hipStream_t s) {
+    return upload_rows(c, c->atab, (size_t)a->n_steps + 1, s, [a](size_t k) {
+        return k < (size_t)a->n_steps ? AffineRow{a->t[k], a->a[k], a->b[k], a->c[k], a->noise[k] ? 1 : 0, a->counter_base + (int)k, 0, 0}
+                                      : AffineRow{0.f, 0.f, 0.f, 0.f, 0, 0, 0, 0};
+    });
+}
+
+// The known region of a checked *_region call on the device (mo.kr null: nothing to do): x0 | mask copied into the context's k_stage (a
+// later call with other tensors of the same shape replays the same graphs, as with x / y / h) and `rows` rows uploaded, row(i) each.
+template <typename F>
+int stage_known(dd_ctx* c, Mods& mo, const dd_model* m, int B, size_t rows, hipStream_t s, F&& row) {
+    if (!mo.kr) return DD_OK;
+    const size_t hw = (size_t)m->cfg.img_size * m->cfg.img_size, x_elems = (size_t)B * hw * m->cfg.in_chans, m_elems = (size_t)B * hw;
+    if (int rc = c->k_stage.grow(c, x_elems + m_elems)) return rc;
+    if (int rc = upload_rows(c, c->ktab, rows, s, row)) return rc;
+    DD_HIP(c, hipMemcpyAsync(c->k_stage.p, mo.kr->x0_dev, x_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    DD_HIP(c, hipMemcpyAsync(c->k_stage.p + x_elems, mo.kr->mask_dev, m_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    mo.kn = Known{c->k_stage.p, c->k_stage.p + x_elems, c->ktab.dev.p};
+    return DD_OK;
+}
+// ... of a table-driven loop of n steps: row k beside AffineRow k, one more (never used) as there
+int stage_table_known(dd_ctx* c, Mods& mo, const dd_model* m, int B, int n, hipStream_t s) {
+    const dd_known_region* kr = mo.kr;
+    return stage_known(c, mo, m, B, (size_t)n + 1, s, [kr, n](size_t k) { return k < (size_t)n ? KnownRow{kr->ka[k], kr->kb[k]} : KnownRow{0.f, 0.f}; });
+}
+
+// dd_sample and its _guided, _autoguided and _region forms: one path
+int sample_ddpm(dd_ctx* c, const dd_sample_args* a, Mods mo, void* stream) {
+    int rc = check_loop(c, a, mo, nullptr, "dd_sample generates noise on the device; for host noise drive dd_sample_step", [&]() -> int {
+        if (!a->x_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+        if (a->t_start > 999 || a->t_end < 0 || a->t_end > a->t_start) return ctx_fail(c, DD_ERR_INVALID, "need 999 >= t_start >= t_end >= 0");
+        return DD_OK;
+    });
+    if (rc) return rc;
+    const int n = a->t_start - a->t_end + 1;
+    const bool switching = a->late && a->t_switch > 0 && a->t_switch <= 1000;
+    const int t_sw = 1000 - a->t_switch;  // the late model takes over AFTER this step (sampler.py:135-136)
+    const bool switch_here = switching && t_sw <= a->t_start && t_sw >= a->t_end;
+    // the known rows by timestep, as the DDPM rule reads its own: row k of the call is the step at t_start - k
+    auto known_row = [kr = mo.kr, t0 = a->t_start, n](size_t t) {
+        const long long k = t0 - (long long)t;
+        return k >= 0 && k < n ? KnownRow{kr->ka[k], kr->kb[k]} : KnownRow{0.f, 0.f};
+    };
+    if ((rc = stage_known(c, mo, a->first, a->B, 1000, (hipStream_t)stream, known_row))) return rc;
+    Loop L{GRAPH_DDPM, a->first, switching ? a->late : nullptr, n, switch_here ? a->t_start - t_sw + 1 : -1, a->x_dev, a->y_dev, a->B, mo,
+           a->use_graph != 0};
+    L.set_state = [&](StepState* st, hipStream_t s) { return launch_set_state(st, a->t_start, (unsigned long long)a->seed, s); };
+    L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.variance = a->variance; };
+    L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t s) {
+        return enqueue_step(c, m, ch, sl.x, sl.y, sl.B, s,
+                            {.mods = sl.mods, .noise_mode = a->noise_mode, .variance = a->variance, .advance = 1, .b0 = sl.b0});
+    };
+    return run_loop(c, L, (hipStream_t)stream);
+}
+
+// dd_sample_affine and its _guided, _autoguided and _region forms: one path
+int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, Mods mo, void* stream) {
+    int rc = check_loop(c, a, mo, nullptr, "dd_sample_affine generates noise on the device; for host noise drive dd_forward + dd_affine_step",
+                        [&] { return check_table(c, a); });
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int n = a->n_steps;
+    const bool switching = a->late && a->switch_after >= 0 && a->switch_after < n;
+    if ((rc = upload_atab(c, a, s))) return rc;
+    if ((rc = stage_table_known(c, mo, a->first, a->B, n, s))) return rc;
+    const AffineRow* atab = c->atab.dev.p;
+    // (two half-batch chains, as dd_sample: both read the one step table; each has its own step index and Philox image offset)
+    Loop L{GRAPH_AFFINE, a->first, switching ? a->late : nullptr, n, switching ? a->switch_after : -1, a->x_dev, a->y_dev, a->B, mo,
+           a->use_graph != 0};
+    L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_table(st, atab, (unsigned long long)a->seed, ss); };
+    L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.atab = atab; };
+    L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
+        return enqueue_step(c, m, ch, sl.x, sl.y, sl.B, ss, {.mods = sl.mods, .noise_mode = a->noise_mode, .advance = 1, .atab = atab, .b0 = sl.b0});
+    };
+    return run_loop(c, L, s);
+}
+
+// dd_sample_multistep and its forms: dd_sample_affine's loop with the history register.  h is staged like x: copied into the context's
+// h_stage before the loop, chain k's images at h_stage + o_k chw (guided too: h holds B images, not 2 B), and copied back behind the
+// join of the chains.
+int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, Mods mo, void* stream) {
+    int rc = check_loop(c, a, mo, "the multistep loop is not supported for early-exit models",
+                        "dd_sample_multistep generates noise on the device; for host noise drive dd_forward + dd_multistep_step",
+                        [&] { return check_table(c, a); });
+    if (rc) return rc;
+    if (!a->d || !a->p || !a->q || !a->hist) return ctx_fail(c, DD_ERR_INVALID, "null tensor / table");
+    if (!a->h_dev) return ctx_fail(c, DD_ERR_INVALID, "null h_dev: the multistep loop needs its history register");
+    X0Threshold thr{};
+    if (mo.thresholded) {
+        if (const char* bad = check_threshold(mo.thr)) return ctx_fail(c, DD_ERR_INVALID, bad);
+        const long long n_img = (long long)a->first->cfg.in_chans * a->first->cfg.img_size * a->first->cfg.img_size;
+        if (n_img > THRESHOLD_MAX_ELEMS) return ctx_fail(c, DD_ERR_UNSUPPORTED, "x0 thresholding holds one image in LDS: at most 16384 elements per image");
+        thr = kernel_threshold(mo.thr, n_img);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int n = a->n_steps;
+    const bool switching = a->late && a->switch_after >= 0 && a->switch_after < n;
+    if ((rc = upload_atab(c, a, s))) return rc;
+    rc = upload_rows(c, c->htab, (size_t)n + 1, s, [a, n](size_t k) {
+        return k < (size_t)n ? HistRow{a->d[k], a->p[k], a->q[k], a->hist[k] ? 1 : 0} : HistRow{0.f, 0.f, 0.f, 0};
+    });
+    if (rc) return rc;
+    const size_t chw = (size_t)a->first->cfg.in_chans * a->first->cfg.img_size * a->first->cfg.img_size;
+    const size_t h_elems = (size_t)a->B * chw;
+    if ((rc = c->h_stage.grow(c, h_elems))) return rc;
+    float* h_run = c->h_stage.p;
+    if (mo.thresholded && (rc = c->m_stage.grow(c, h_elems))) return rc;      // (with h_stage: never on the launch path)
+    float* m_run = mo.thresholded ? c->m_stage.p : nullptr;
+    const X0Threshold* thr_p = mo.thresholded ? &thr : nullptr;
+    DD_HIP(c, hipMemcpyAsync(h_run, a->h_dev, h_elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if ((rc = stage_table_known(c, mo, a->first, a->B, n, s))) return rc;
+    const AffineRow* atab = c->atab.dev.p;
+    const HistRow* htab = c->htab.dev.p;
+    Loop L{GRAPH_MULTISTEP, a->first, switching ? a->late : nullptr, n, switching ? a->switch_after : -1, a->x_dev, a->y_dev, a->B, mo,
+           a->use_graph != 0};
+    L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_table(st, atab, (unsigned long long)a->seed, ss); };
+    L.key = [&](GraphKey& k, const Slice&) {
+        k.noise = a->noise_mode; k.atab = atab; k.aux0 = htab; k.aux1 = h_run;
+        if (mo.thresholded) {
+            k.tmode = mo.thr->mode; k.tscratch = m_run;
+            k.tq = __builtin_bit_cast(unsigned, mo.thr->quantile); k.tr = __builtin_bit_cast(unsigned, mo.thr->range);
+            k.ts = __builtin_bit_cast(unsigned, mo.thr->s_max);
+        }
+    };
+    L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
+        return enqueue_step(c, m, ch, sl.x, sl.y, sl.B, ss, {.mods = sl.mods, .noise_mode = a->noise_mode, .advance = 1, .atab = atab, .b0 = sl.b0,
+                                                             .htab = htab, .h = h_run + (size_t)sl.b0 * chw, .thr = thr_p,
+                                                             .m_scratch = m_run ? m_run + (size_t)sl.b0 * chw : nullptr});
+    };
+    L.tail = [&](int, hipStream_t ss) -> int {
+        DD_HIP(c, hipMemcpyAsync(a->h_dev, h_run, h_elems * sizeof(float), hipMemcpyDeviceToDevice, ss));
+        return DD_OK;
+    };
+    return run_loop(c, L, s);
+}
+}  // namespace
+
+extern "C" {
+
+int dd_sample(dd_ctx* c, const dd_sample_args* a, void* stream) { return sample_ddpm(c, a, Mods{}, stream); }
+int dd_sample_guided(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* stream) { return sample_ddpm(c, a, guided(g), stream); }
+int dd_sample_autoguided(dd_ctx* c, const dd_sample_args* a, const dd_autoguidance* g, void* stream) { return sample_ddpm(c, a, autoguided(g), stream); }
+int dd_sample_region(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr, void* stream) {
+    return sample_ddpm(c, a, in_region(g, ag, kr), stream);
+}
+int dd_sample_affine(dd_ctx* c, const dd_affine_sample_args* a, void* stream) { return sample_affine(c, a, Mods{}, stream); }
+int dd_sample_affine_guided(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, void* stream) { return sample_affine(c, a, guided(g), stream); }
+int dd_sample_affine_autoguided(dd_ctx* c, const dd_affine_sample_args* a, const dd_autoguidance* g, void* stream) {
+    return sample_affine(c, a, autoguided(g), stream);
+}
+int dd_sample_affine_region(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr,
+                            void* stream) {
+    return sample_affine(c, a, in_region(g, ag, kr), stream);
+}
+int dd_sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, void* stream) { return sample_multistep(c, a, Mods{}, stream); }
+int dd_sample_multistep_guided(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, void* stream) {
+    return sample_multistep(c, a, guided(g), stream);
+}
+int dd_sample_multistep_autoguided(dd_ctx* c, const dd_multistep_sample_args* a, const dd_autoguidance* g, void* stream) {
+    return sample_multistep(c, a, autoguided(g), stream);
+}
+int dd_sample_perturbed(dd_ctx* c, const dd_sample_args* a, const dd_pag* p, void* stream) {
+    return sample_ddpm(c, a, perturbed(p, a ? a->late : nullptr), stream);
+}
+int dd_sample_affine_perturbed(dd_ctx* c, const dd_affine_sample_args* a, const dd_pag* p, void* stream) {
+    return sample_affine(c, a, perturbed(p, a ? a->late : nullptr), stream);
+}
+int dd_sample_multistep_perturbed(dd_ctx* c, const dd_multistep_sample_args* a, const dd_pag* p, void* stream) {
+    return sample_multistep(c, a, perturbed(p, a ? a->late : nullptr), stream);
+}
+int dd_sample_multistep_region(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag,
+                               const dd_known_region* kr, void* stream) {
+    return sample_multistep(c, a, in_region(g, ag, kr), stream);
+}
+int dd_sample_multistep_threshold(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag,
+                                  const dd_known_region* kr, const dd_x0_threshold* thr, void* stream) {
+    if (c && g && ag) return ctx_fail(c, DD_ERR_INVALID, "classifier-free guidance and autoguidance are exclusive");
+    return sample_multistep(c, a, thresholding(g, ag, kr, thr), stream);
+}
+
+// One early-exit sampling step on the device (reference eesampler.py:56-81): EarlyExitUViT.forward with every head and
+// probe -> per-sample exit selection -> DDPM update with the selected output; rows t of the two log tables are written.
+// ws: the chain's scratch block (eps | cls | outs for B images, ee_scratch_elems); b0 / B_all: the chain's first image within the whole batch
+// and the whole batch (idx_tab rows are B_all wide); sums: err_tab is the chain's table of per-layer SUMS (launch_ee_mean_combine joins the chains)
+static int enqueue_ee_step(dd_ctx* c, dd_model* m, const Chain& ch, float* ws, float* x, const int64_t* y, float thr, float* err_tab,
+                           int32_t* idx_tab, int noise_mode, int B, hipStream_t s, int b0, int B_all, bool sums) {
+    const long long chw = (long long)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
+    const int depth = m->cfg.depth;
+    float* eps = ws;
+    float* cls = eps + (size_t)B * chw;
+    float* outs = cls + (size_t)depth * B;
+    const EeTaps ee{cls, outs, 0};
+    if (int rc = forward_eps(c, m, ch, x, y, eps, B, s, {.ee = &ee})) return rc;
+    // exit layer per image, the selected output and the DDPM update in one launch (dd_early_exit_select + the step kernel, fused: same arithmetic)
+    DD_HIP(c, launch_ee_select_step(x, outs, eps, cls, thr, depth, idx_tab, err_tab, B_all, b0, sums, ch.st, c->coef, B,
+                                    m->cfg.in_chans, m->cfg.img_size, noise_mode, 1, s));
+    return DD_OK;
+}
+
+int dd_sample_early_exit(dd_ctx* c, const dd_ee_sample_args* a, void* stream) {
+    if (!c || !a) return DD_ERR_INVALID;
+    dd_model* m = a->model;
+    int rc = check_call(c, m, a->B, a->y_dev);
+    if (rc) return rc;
+    if (m->ee_type < 0) return ctx_fail(c, DD_ERR_STATE, "model was not created with dd_model_enable_early_exit");
+    if (!a->x_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    if (a->t_start > 999 || a->t_end < 0 || a->t_end > a->t_start) return ctx_fail(c, DD_ERR_INVALID, "need 999 >= t_start >= t_end >= 0");
+    if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE)
+        return ctx_fail(c, DD_ERR_INVALID, "dd_sample_early_exit generates noise on the device; for host noise drive dd_forward_early_exit");
+    // Two half-batch chains, as dd_sample: the samples are independent (every exit decision is per sample); the one quantity over the whole
+    // batch -- the logged per-layer mean of the predicted errors, eesampler.py:70 -- becomes per-chain sums that one small launch joins
+    // behind the loop, (chain 0 + chain 1) / B.  Heads and probes stay on each chain's own stream (measured: the 13 forks as parallel
+    // branches of each chain's graph cost +0.9 ms per step -- 5.22 against 4.23 ms; profiles/r05/ab_round5.txt).
+    const size_t tab = (size_t)1000 * m->cfg.depth;
+    if (!m->ee_ws) DD_HIP(c, hipMalloc((void**)&m->ee_ws, (ee_scratch_elems(m, m->cfg.max_batch) + 2 * tab) * sizeof(float)));
+    float* sums = m->ee_ws + ee_scratch_elems(m, m->cfg.max_batch);
+    auto err_tab = [&](const Slice& sl) { return sl.chains == 1 || !a->err_dev ? a->err_dev : sums + sl.chain * tab; };
+    Loop L{GRAPH_EARLY_EXIT, m, nullptr, a->t_start - a->t_end + 1, -1, a->x_dev, a->y_dev, a->B, Mods{}, a->use_graph != 0};
+    L.set_state = [&](StepState* st, hipStream_t s) { return launch_set_state(st, a->t_start, (unsigned long long)a->seed, s); };
+    L.key = [&](GraphKey& k, const Slice& sl) {
+        k.noise = a->noise_mode; k.aux0 = err_tab(sl); k.aux1 = a->idx_dev; k.thr = a->threshold;
+        if (sl.chains == 2 && sl.chain == 0) k.b0 = -1;     // (chain 0 of two -- not the whole batch's graph)
+    };
+    L.step = [&](dd_model* mm, const Chain& ch, const Slice& sl, hipStream_t s) {
+        return enqueue_ee_step(c, mm, ch, mm->ee_ws + ee_scratch_elems(mm, sl.b0), sl.x, sl.y, a->threshold, err_tab(sl), a->idx_dev,
+                               a->noise_mode, sl.B, s, sl.b0, a->B, sl.chains == 2);
+    };
+    L.tail = [&](int chains, hipStream_t s) -> int {
+        if (chains == 2 && a->err_dev) DD_HIP(c, launch_ee_mean_combine(sums, sums + tab, a->err_dev, m->cfg.depth, a->t_end, a->t_start, a->B, s));
+        return DD_OK;
+    };
+    return run_loop(c, L, (hipStream_t)stream);
+}
+
+long long dd_dev_graph_captures(dd_ctx* c) { return c ? c->graph_captures : -1; }
+int dd_dev_last_sample_chains(dd_ctx* c) { return c ? c->last_chains : -1; }
+
+int dd_last_sample_timing(dd_ctx* c, float out3[3]) {
+    if (!c || !out3) return DD_ERR_INVALID;
+    DD_HIP(c, hipEventSynchronize(c->ev[2]));
+    DD_HIP(c, hipEventElapsedTime(&out3[0], c->ev[0], c->ev[2]));
+    DD_HIP(c, hipEventElapsedTime(&out3[1], c->ev[0], c->ev[1]));
+    DD_HIP(c, hipEventElapsedTime(&out3[2], c->ev[1], c->ev[2]));
+    return DD_OK;
+}
+
+int dd_profile_steps(dd_ctx* c, dd_model* m, float* x_dev, const int64_t* y_dev, int t_start, int steps, int B,
+                     void* stream, float* fc1_ms_out, int* launches_out) {
+    return profile_steps(c, m, x_dev, y_dev, t_start, steps, B, 1, stream, fc1_ms_out, launches_out);
+}
+int dd_profile_steps_chained(dd_ctx* c, dd_model* m, float* x_dev, const int64_t* y_dev, int t_start, int steps, int B,
+                             void* stream, float* ms_out, int* launches_out) {
+    return profile_steps(c, m, x_dev, y_dev, t_start, steps, B, 2, stream, ms_out, launches_out);
+}
+
+}  // extern "C"

@@ -684,7 +684,7 @@ __device__ __forceinline__ void landed_at_vmcnt(f32x4& v) {
 // Wh.dh + Wh.dl + Wl.dh accumulated in fp32; the dropped Wl.dl term and the low halves' own rounding are 2^-16 .. 2^-17 of a product, two
 // orders below the bf16 roundings of the backbone that feeds these heads -- 9 MFMAs of 16 cycles per 32 k instead of 24 of 32 cycles (a fifth
 // of the matrix-pipe time, and of its energy).  Lane (row l & 15, k-group l >> 4) holds k = 32 jj + 8 (l >> 4) .. + 7 as TWO quads per jj;
-// a.wg is the host-packed image [jj][ct][hi, lo][64 lanes] x 8 bf16 in A-operand order (capi.hip: pack_head_split).
+// a.wg is the host-packed image [jj][ct][hi, lo][64 lanes] x 8 bf16 in A-operand order (launch_args.h: pack_head_image).
 template <int D, int NT, int NW = 8, bool PROBE = false, bool SPLIT = false>
 __global__ void __launch_bounds__(NW * 64) head_dec_kernel(const HeadDecArgs a) {
     constexpr int J = D / 16;

@@ -12,7 +12,7 @@
 //   they are given, and two calls on different streams must be ordered by the caller.
 #include "../../include/duodiff.h"
 #include "dd_internal.h"
-#include "dev_scope.h"
+#include "engine_state.h"
 #include "host_arena.h"
 
 #include <cmath>
@@ -141,7 +141,7 @@ struct Net {
 
     int gemm(const T* A, int M, int K, const ConvW& w, int epi, float* xres, T* o, int ldo) {
         GemmArgs<T> g{A, nullptr, (const T*)w.w, w.b, xres, o, M, w.cout == 3 ? 4 : w.cout, K, K, K, 0, ldo};
-        VHIP(c, launch_gemm<T>(g, epi, s, ctx_num_cus(c)));
+        VHIP(c, launch_gemm<T>(g, epi, s, c->num_cus));
         return DD_OK;
     }
     // 3x3 conv of the T-typed NHWC image `src` (C channels at Hs x Hs, optionally upsampled 2x first)
@@ -182,16 +182,16 @@ struct Net {
             const T* hb = nb + (long long)b * HW * C;
             // V^T[c][tok] = Wv[c][:] . h[tok][:]  (bias of v is added after P.V: softmax rows sum to 1)
             GemmArgs<T> gv{(const T*)wv.w, nullptr, hb, nullptr, nullptr, (T*)v->vt, C, HW, C, C, C, 0, HW};
-            VHIP(c, launch_gemm<T>(gv, EPI_STORE, s, ctx_num_cus(c)));
+            VHIP(c, launch_gemm<T>(gv, EPI_STORE, s, c->num_cus));
             // S[i][j] = q_i . k_j  -> fp32
             GemmArgs<T> gs{(const T*)v->q + (long long)b * HW * C, nullptr, (const T*)v->kk + (long long)b * HW * C, nullptr,
                            v->score, nullptr, HW, HW, C, C, C, 0, 0};
-            VHIP(c, launch_gemm<T>(gs, EPI_BIAS_SET, s, ctx_num_cus(c)));
+            VHIP(c, launch_gemm<T>(gs, EPI_BIAS_SET, s, c->num_cus));
             VHIP(c, launch_softmax_rows<T>(v->score, (T*)v->pp, HW, HW, 1.0f / sqrtf((float)C), s));
             // O[i][c] = sum_j P[i][j] V^T[c][j] + b_v[c]
             GemmArgs<T> go{(const T*)v->pp, nullptr, (const T*)v->vt, wv.b, v->ao + (long long)b * HW * C, nullptr,
                            HW, C, HW, HW, HW, 0, 0};
-            VHIP(c, launch_gemm<T>(go, EPI_BIAS_SET, s, ctx_num_cus(c)));
+            VHIP(c, launch_gemm<T>(go, EPI_BIAS_SET, s, c->num_cus));
         }
         VHIP(c, launch_cast<T>(v->ao, (T*)v->q, (long long)M * C, s));
         return gemm((const T*)v->q, M, C, wproj, EPI_BIAS_RESID, cur, nullptr, 0);  // x + proj_out(h_)
@@ -297,7 +297,7 @@ int dd_vae_finalize(dd_vae* v, int precision) {
     if (precision != DD_PREC_BF16 && precision != DD_PREC_FP32) return ctx_fail(c, DD_ERR_INVALID, "unknown precision");
     for (auto& kv : expected())
         if (!v->params.count(kv.first)) return ctx_fail(c, DD_ERR_NOT_FOUND, "missing key in autoencoder state_dict: " + kv.first);
-    VHIP(c, hipSetDevice(ctx_device(c)));
+    VHIP(c, hipSetDevice(c->device));
     v->prec = precision;
     v->es = precision == DD_PREC_BF16 ? 2 : 4;
     const size_t es = v->es;
@@ -381,7 +381,7 @@ int dd_vae_finalize(dd_vae* v, int precision) {
     buf(v->ao, Bc * HWm * Cm * 4); buf(v->z4, Bc * HWm * 4 * 4);
     VHIP(c, hipMalloc((void**)&v->ws, a.bytes()));
     VHIP(c, hipMemset(v->ws, 0, a.bytes()));
-    VHIP(c, hipStreamSynchronize(nullptr));      // (ditto capi.hip: ordered before any stream the decoder is later run on)
+    VHIP(c, hipStreamSynchronize(nullptr));      // (ditto model.hip: ordered before any stream the decoder is later run on)
     a.bind(v->ws);
     for (auto& kv : v->params) std::vector<float>().swap(kv.second.d);
     v->finalized = true;

@@ -564,7 +564,7 @@ def test_invalid_region_calls_are_rejected_before_anything_is_enqueued(kind):
 
 @gpu
 def test_loop_rejections_keep_their_order():
-    """Calls that break two rules at once fail on the rule the loops check first (the texts in the order of the checks in capi.hip: the
+    """Calls that break two rules at once fail on the rule the loops check first (the texts in the order of the checks in loops.hip: the
     region's own rules, the multistep loop's early-exit exclusion, the models, the loop's tensors and ranges, the noise mode)."""
     from duodiff_amd.engine import Model
     B = 2

@@ -81,6 +81,24 @@ class dd_ee_sample_args(C.Structure):
                 ("y_dev", C.c_void_p), ("x_dev", C.c_void_p), ("err_dev", C.c_void_p), ("idx_dev", C.c_void_p)]
 
 
+class dd_dev_final_args(C.Structure):
+    """the operands of dd_dev_final (include/duodiff_dev.h), field for field"""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "C", "S", "P", "L", "extras", "b0", "images")] +
+                [(n, C.c_void_p) for n in ("dec", "wconv", "bconv", "dec2", "wconv2", "bconv2")] +
+                [(n, C.c_int32) for n in ("L2", "extras2", "pair_B", "layer_B")] +
+                [("w_stride", C.c_int64), ("b_stride", C.c_int64), ("guide_scale", C.c_float)] +
+                [(n, C.c_int32) for n in ("write_eps", "write_x", "x_alias")] +
+                [(n, C.c_void_p) for n in ("eps_out", "x_out", "x_in", "z")] +
+                [(n, C.c_int32) for n in ("t", "advance", "noise_mode", "variance")] +
+                [("seed", C.c_uint64), ("table", C.c_int32)] +
+                [(n, C.c_float) for n in ("c1", "c2", "sigma_tilde", "sigma_beta", "row_t_model", "row_a", "row_b", "row_c")] +
+                [("row_noise", C.c_int32), ("row_ctr", C.c_int32), ("next_t_model", C.c_float), ("hist_row", C.c_int32)] +
+                [(n, C.c_float) for n in ("hist_d", "hist_p", "hist_q")] +
+                [("hist", C.c_int32), ("h", C.c_void_p), ("known", C.c_int32), ("known_ka", C.c_float), ("known_kb", C.c_float),
+                 ("kx0", C.c_void_p), ("kmask", C.c_void_p), ("t_out", C.c_int32), ("t_final_out", C.c_int32), ("t_model_out", C.c_float),
+                 ("seed_out", C.c_uint64)])
+
+
 # every symbol include/duodiff.h (and include/duodiff_dev.h: dd_dev_*) declares: name -> (restype, argtypes)
 SIGNATURES = {
     "dd_abi_version": (C.c_int, []),
@@ -174,6 +192,7 @@ SIGNATURES = {
     "dd_dev_embed": (C.c_int, [C.c_void_p] + [C.c_int] * 9 + [C.c_void_p] * 7 + [C.c_float] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_time_mlp": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 6 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_vae_gather": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dd_dev_final": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_final_args), C.c_void_p]),
     "dd_dev_poison_workspaces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "dd_dev_graph_captures": (C.c_longlong, [C.c_void_p]),
     "dd_dev_last_sample_chains": (C.c_int, [C.c_void_p]),

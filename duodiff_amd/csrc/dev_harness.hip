@@ -1,5 +1,5 @@
 // The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_block_tail, dd_dev_block_tail_frag, dd_dev_qkv_attention, dd_dev_qkv_attention_rows, dd_dev_qkv_attention_frag, dd_dev_v_identity, dd_dev_v_copy, dd_dev_head_dec, dd_dev_gemm,
-// dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather): test scaffolding, not product.  Each one owns its host operands, device buffers, canaries and
+// dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather, dd_dev_final): test scaffolding, not product.  Each one owns its host operands, device buffers, canaries and
 // downloads, and nothing of the launch: the weight images come from finalize's packers and the launch arguments from the model's builders (launch_args.h:
 // dd_dev_mlp and dd_dev_block_tail* run block_tail_plan / block_tail_finish exactly as Backbone::block_tail does), then `iters` further launch sequences
 // are timed.  Buffers, transfers, timing and HIP errors go through one DevScope (dev_scope.h); of the context it reads num_cus and dev_flags (engine_state.h).
@@ -614,6 +614,101 @@ int dd_dev_vae_gather(dd_ctx* c, int kind, int precision, int B, int H, int W, i
     }
     DEV_HIP(dev, hipStreamSynchronize(s));
     dev.download(dst_host, dD, dst_bytes);
+    return dev.status();
+}
+
+int dd_dev_final(dd_ctx* c, dd_dev_final_args* p, void* stream) {
+    if (!c || !p) return DD_ERR_INVALID;
+    const dd_dev_final_args& q = *p;
+    // ---- everything the selected instantiation dereferences, before anything touches the GPU
+    if (q.B < 1 || q.B > 4096 || q.C < 1 || q.C > 4 || q.P < 1 || q.P * q.P * q.C > 64 || q.S < q.P || q.S > 1024 || q.S % q.P || q.extras < 0 ||
+        q.extras > 64 || q.b0 < 0 || q.images < q.B || q.images > 2 * q.B + 64 || !q.dec || !q.wconv || !q.bconv)
+        return DD_ERR_INVALID;
+    const int g = q.S / q.P, pd = q.P * q.P * q.C;
+    if (q.L - q.extras != g * g || (long long)q.images * q.C * q.S * q.S > (1ll << 26)) return DD_ERR_INVALID;
+    const bool cfg = q.pair_B > 0, ag = q.dec2 != nullptr, layered = q.layer_B > 0;
+    if (q.pair_B < 0 || q.layer_B < 0 || (cfg && (q.pair_B != q.B || ag || q.images < 2 * q.pair_B))) return DD_ERR_INVALID;
+    if (ag && (!q.wconv2 || !q.bconv2 || q.extras2 < 0 || q.extras2 > 64 || q.L2 - q.extras2 != g * g)) return DD_ERR_INVALID;
+    if (layered && (cfg || ag || q.hist_row || q.known || q.B % q.layer_B || q.w_stride < 0 || q.b_stride < 0 || q.w_stride > (1 << 20) ||
+                    q.b_stride > (1 << 20)))
+        return DD_ERR_INVALID;
+    if (q.noise_mode < DD_NOISE_NONE || q.noise_mode > DD_NOISE_PHILOX || (q.variance != DD_VAR_BETA_TILDE && q.variance != DD_VAR_BETA)) return DD_ERR_INVALID;
+    if (q.t < 0 || q.t > (q.table ? 65535 : 999)) return DD_ERR_INVALID;
+    if ((q.write_eps && !q.eps_out) || (q.write_x && (!q.x_in || !q.x_out)) || (q.write_x && q.noise_mode == DD_NOISE_BUFFER && !q.z)) return DD_ERR_INVALID;
+    if (q.hist_row && (!q.table || !q.write_x || !q.h)) return DD_ERR_INVALID;
+    if (q.known && (!q.write_x || !q.kx0 || !q.kmask)) return DD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t img = (size_t)q.C * q.S * q.S, n_in = (size_t)q.B * img, n_out = (size_t)q.images * img + 8;
+    const int layers = layered ? q.B / q.layer_B : 1;
+    const size_t t_rows = (size_t)q.t + 2;
+    DevScope dev(c);
+    FinalArgs fa{};
+    // the head's arguments that the model and the chain determine (forward.hip final_args)
+    fa.dec = dev.upload(q.dec, (size_t)(cfg ? 2 * q.pair_B : q.B) * q.L * pd * 4);
+    fa.wconv = dev.upload(q.wconv, ((size_t)(layers - 1) * q.w_stride + (size_t)q.C * q.C * 9) * 4);
+    fa.bconv = dev.upload(q.bconv, ((size_t)(layers - 1) * q.b_stride + q.C) * 4);
+    fa.B = q.B; fa.C = q.C; fa.S = q.S; fa.P = q.P; fa.L = q.L; fa.extras = q.extras;
+    // the step state and the context's coefficient table: row t alone holds the caller's coefficients
+    const StepState st0{q.t, q.table ? q.row_t_model : (float)q.t, q.seed, q.t, 0};
+    fa.st = dev.upload(&st0, sizeof st0);
+    StepCoef* coef = dev.filled<StepCoef>(1000 * sizeof(StepCoef), 0xFF);
+    if (!q.table && dev.ok()) {
+        const StepCoef cf{q.c1, q.c2, q.sigma_tilde, q.sigma_beta};
+        dev.ok(hipMemcpy(coef + q.t, &cf, sizeof cf, hipMemcpyHostToDevice), "hipMemcpy to the device");
+    }
+    fa.coef = coef;
+    // the guidance of model_eps / run_guide, the batched early-exit heads of ee_finish
+    if (cfg) { fa.pair_B = q.pair_B; fa.guide_scale = q.guide_scale; }
+    if (ag) {
+        fa.dec2 = dev.upload(q.dec2, (size_t)q.B * q.L2 * pd * 4);
+        fa.wconv2 = dev.upload(q.wconv2, (size_t)q.C * q.C * 9 * 4); fa.bconv2 = dev.upload(q.bconv2, (size_t)q.C * 4);
+        fa.L2 = q.L2; fa.extras2 = q.extras2; fa.guide_scale = q.guide_scale;
+    }
+    if (layered) { fa.layer_B = q.layer_B; fa.w_stride = q.w_stride; fa.b_stride = q.b_stride; }
+    // what the launch writes (enqueue_step / forward_eps): canary bytes everywhere, or the caller's bytes (x aliased, h)
+    float* dE = q.eps_out ? dev.filled<float>(n_out * 4, 0xFF) : nullptr;
+    float* dX = nullptr;
+    if (q.x_out) {
+        dX = dev.filled<float>(n_out * 4, 0xFF);
+        if (q.write_x && q.x_alias && dev.ok()) dev.ok(hipMemcpy(dX, q.x_in, (size_t)q.images * img * 4, hipMemcpyHostToDevice), "hipMemcpy to the device");
+    }
+    if (q.write_eps) fa.eps_out = dE;
+    if (q.write_x) {
+        fa.x_in = q.x_alias ? dX : dev.upload(q.x_in, (size_t)q.images * img * 4);
+        fa.x_out = dX;
+        if (q.noise_mode == DD_NOISE_BUFFER) fa.z = dev.upload(q.z, n_in * 4);
+    }
+    fa.noise_mode = q.noise_mode; fa.variance = q.variance; fa.advance = q.advance; fa.b0 = q.b0;
+    if (q.table) {
+        AffineRow* atab = dev.filled<AffineRow>(t_rows * sizeof(AffineRow), 0xFF);
+        const AffineRow rows[2] = {{q.row_t_model, q.row_a, q.row_b, q.row_c, q.row_noise, q.row_ctr, 0, 0}, {q.next_t_model, 0.f, 0.f, 0.f, 0, 0, 0, 0}};
+        if (dev.ok()) dev.ok(hipMemcpy(atab + q.t, rows, sizeof rows[0], hipMemcpyHostToDevice), "hipMemcpy to the device");
+        if (dev.ok()) dev.ok(hipMemcpy(&atab[q.t + 1].t_model, &rows[1].t_model, sizeof(float), hipMemcpyHostToDevice), "hipMemcpy to the device");
+        fa.atab = atab;
+    }
+    if (q.h) fa.h = dev.upload(q.h, n_out * 4);
+    if (q.hist_row) {
+        HistRow* htab = dev.filled<HistRow>(t_rows * sizeof(HistRow), 0xFF);
+        const HistRow hr{q.hist_d, q.hist_p, q.hist_q, q.hist};
+        if (dev.ok()) dev.ok(hipMemcpy(htab + q.t, &hr, sizeof hr, hipMemcpyHostToDevice), "hipMemcpy to the device");
+        fa.htab = htab;
+    }
+    if (q.known) {
+        KnownRow* ktab = dev.filled<KnownRow>((q.table ? t_rows : (size_t)1000) * sizeof(KnownRow), 0xFF);
+        const KnownRow kr{q.known_ka, q.known_kb};
+        if (dev.ok()) dev.ok(hipMemcpy(ktab + q.t, &kr, sizeof kr, hipMemcpyHostToDevice), "hipMemcpy to the device");
+        fa.kx0 = dev.upload(q.kx0, n_in * 4); fa.kmask = dev.upload(q.kmask, (size_t)q.B * q.S * q.S * 4); fa.ktab = ktab;
+    }
+    const hipError_t first = dev.ok() ? launch_final(fa, s) : hipSuccess;
+    if (first == hipErrorInvalidValue) return ctx_fail(c, DD_ERR_INVALID, "final: a combination of operands launch_final refuses");      // (refused before any launch)
+    DEV_HIP(dev, first);
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    if (q.eps_out) dev.download(q.eps_out, dE, n_out * 4);
+    if (q.x_out) dev.download(q.x_out, dX, n_out * 4);
+    if (q.h) dev.download(q.h, fa.h, n_out * 4);
+    StepState st1{};
+    dev.download(&st1, fa.st, sizeof st1);
+    if (dev.ok()) { p->t_out = st1.t; p->t_final_out = st1.t_final; p->t_model_out = st1.t_model; p->seed_out = st1.seed; }
     return dev.status();
 }
 

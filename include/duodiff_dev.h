@@ -202,6 +202,57 @@ int dd_dev_time_mlp(dd_ctx* ctx, int B, int D, int L, int extras, int normalize,
 int dd_dev_vae_gather(dd_ctx* ctx, int kind, int precision, int B, int H, int W, int C, const void* src_host, void* dst_host,
                       size_t dst_bytes, void* stream);
 
+/* Development harness for the launch that ends every sampling step and every forward (step.hip final_tiled_kernel through launch_final:
+ * unpatchify, the 3x3 conv, guidance, the step update of step_update.h): ONE launch, from a FinalArgs filled the way forward.hip fills it.
+ * All arrays are host fp32.  Geometry: B images of C x S x S (the grid), patches of P, L = extras + (S / P)^2 decoder rows per image, b0 the
+ * launch's first image within the whole batch (Philox pixel ids only); `images` >= B (>= 2 pair_B): how many images eps_out, x_in / x_out and h hold.
+ * Sources: dec [B L, P P C] ([2 pair_B L, ...] under classifier-free guidance, pair_B == B: image b's unconditional rows at b + pair_B), wconv / bconv
+ * (layer_B > 0: the B images are B / layer_B early-exit layers of layer_B images, layer i convolving with wconv + i w_stride / bconv + i b_stride);
+ * autoguidance (pair_B == 0): dec2 [B L2, P P C] with its own L2 / extras2 and conv wconv2 / bconv2; guide_scale for either guidance.
+ * What the launch is handed: write_eps -> eps_out, write_x -> x_in and x_out (x_alias != 0: the one buffer, as in production; else two), hist_row -> h,
+ * known -> kx0 [B, C, S, S] and kmask [B, 1, S, S], noise_mode 1 -> z [B, C, S, S].  eps_out, x_out: [images C S S + 8]; h: [images C S S + 8] in / out
+ * (the caller's bytes go in, the 8 trailing elements included; h given without hist_row is handed to the launch beside a null table).  Every output
+ * buffer is filled with 0xFF bytes before the launch (x_alias: x_in's `images` images, then 8 canary elements) and comes back WHOLE; a buffer the
+ * launch is not handed (write_eps / write_x clear) comes back as the 0xFF it was filled with.
+ * The step state is created on the device with t (= t_final), seed and t_model = (float)t or the row's; t_out, t_model_out, t_final_out and seed_out
+ * are read back after the launch.  The rule: table == 0, DDPM -- coef at row t of a 1000-row table whose other rows are NaN, `variance`
+ * (DD_VAR_*); table != 0 -- the AffineRow of step k = t (row_*) in a table of k + 2 rows, row k + 1 holding next_t_model, every other row and
+ * field 0xFF bytes; hist_row: the HistRow of step k (hist_d, hist_p, hist_q, hist) likewise (needs table, write_x and h); known: the KnownRow
+ * (known_ka, known_kb) at the row the rule reads (needs write_x).  noise_mode DD_NOISE_*; advance as FinalArgs::advance.
+ * Everything the selected instantiation dereferences is checked first -- C in 1..4, P P C <= 64, S % P == 0, L - extras == (S / P)^2 (and of L2 /
+ * extras2), t in 0..999 (DDPM) or 0..65535 (table), B % layer_B == 0, no guidance / history / known region beside layer_B, a buffer for every
+ * flag, sizes a test has use for (B <= 4096, S <= 1024, extras <= 64, images <= 2 B + 64 and images C S S <= 2^26, strides <= 2^20) -- and a call
+ * that fails a check is DD_ERR_INVALID with nothing launched.  No timing loop: the launch mutates x, h and the step state. */
+typedef struct dd_dev_final_args {
+    int B, C, S, P, L, extras, b0, images;
+    const float *dec, *wconv, *bconv;
+    const float *dec2, *wconv2, *bconv2;
+    int L2, extras2, pair_B, layer_B;
+    long long w_stride, b_stride;
+    float guide_scale;
+    int write_eps, write_x, x_alias;
+    float *eps_out, *x_out;
+    const float *x_in, *z;
+    int t, advance, noise_mode, variance;
+    unsigned long long seed;
+    int table;
+    float c1, c2, sigma_tilde, sigma_beta;
+    float row_t_model, row_a, row_b, row_c;
+    int row_noise, row_ctr;
+    float next_t_model;
+    int hist_row;
+    float hist_d, hist_p, hist_q;
+    int hist;
+    float* h;
+    int known;
+    float known_ka, known_kb;
+    const float *kx0, *kmask;
+    int t_out, t_final_out;
+    float t_model_out;
+    unsigned long long seed_out;
+} dd_dev_final_args;
+int dd_dev_final(dd_ctx* ctx, dd_dev_final_args* args, void* stream);
+
 /* Kernel-variant switches for same-process A/B runs (tools/mlp_check.py, tools/all_configs.py).  They act on models
  * FINALIZED after the call (the kernel paths a model takes, the DD_DEV_NO_FRAG_* hand-offs among them) or on launches made after it; the product never sets them and the library
  * reads no environment variable. */

@@ -1,10 +1,16 @@
 """CPU tests of tests/kernel_support.py, the one copy of what every per-element kernel test rests on: the host's bf16 rounding against torch's,
 the bf16 ulp, the gate's predicate at and around its bound, and the two fragment orders against a literal element-by-element evaluation of the
-formulas in include/duodiff_dev.h (dd_dev_block_tail_frag)."""
+formulas in include/duodiff_dev.h (dd_dev_block_tail_frag); and the references of the output head + step launch (tests/test_final_step.py):
+the float64 head against torch's conv2d on a rearrange written out index by index, the float32 restatement of step_update.h against a
+scalar evaluation with explicit roundings, Philox4x32-10 against the published Random123 vectors, the Box-Muller reference against a scalar
+one, and -- on the very inputs the GPU tests use -- that each deliberate error of the reference exceeds the bound the kernel is held to."""
+import math
+
 import numpy as np
 import pytest
 import torch
 
+import kernel_support as ks
 from kernel_support import bf16, bf16_bits, from_bf16_bits, frag16_index, frag32_index, gate, to_frag, ulp_bf16, unfrag
 
 
@@ -96,3 +102,169 @@ def test_fragment_orders_are_the_header_formulas(D):
     good, swapped = to_frag(x, D).reshape(-1, 8), to_frag(x, D, swap_halves=True).reshape(-1, 8)
     assert (good != swapped).any(1).all(), "a 16-byte piece survives the exchange of the lane halves"
     assert np.array_equal(swapped.reshape(-1, 2, 32, 8)[:, ::-1].reshape(-1, 8), good)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the output head + step launch
+def _rearranged(dec, B, L, extras, C, P, S):
+    """ "B (h w) (p1 p2 C) -> B C (h p1) (w p2)" index by index"""
+    g = S // P
+    d = np.asarray(dec, np.float64).reshape(B, L, P * P * C)
+    img = np.zeros((B, C, S, S))
+    for h in range(g):
+        for w in range(g):
+            for p1 in range(P):
+                for p2 in range(P):
+                    for c in range(C):
+                        img[:, c, h * P + p1, w * P + p2] = d[:, extras + h * g + w, (p1 * P + p2) * C + c]
+    return torch.from_numpy(img)
+
+
+def _conv64(img, w, b, C):
+    w, b = torch.from_numpy(np.asarray(w, np.float64).reshape(C, C, 3, 3)), torch.from_numpy(np.asarray(b, np.float64))
+    return torch.nn.functional.conv2d(img, w, b, padding=1), torch.nn.functional.conv2d(img.abs(), w.abs(), b.abs(), padding=1)
+
+
+@pytest.mark.parametrize("C,P,S,guided,layers", [(3, 4, 24, None, 1), (4, 2, 8, "cfg", 1), (2, 2, 24, "auto", 1), (1, 8, 16, "auto", 1),
+                                                 (3, 2, 16, None, 3), (3, 1, 8, "cfg", 1)])
+def test_final_eps64_against_torch_conv2d(C, P, S, guided, layers):
+    B = 6 if layers > 1 else 3
+    a = ks.final_inputs(C, P, S, B, 2, 11 * S + C, guided, layers=layers)
+    got, tol = ks.final_eps64(**a)
+    L, e, n = a["L"], a["extras"], 9 * C * C
+    if layers > 1:
+        lb = a["layer_B"]
+        parts = [_conv64(_rearranged(a["dec"][i * lb * L:(i + 1) * lb * L], lb, L, e, C, P, S), a["wconv"][i * a["w_stride"]:][:n],
+                         a["bconv"][i * a["b_stride"]:][:C], C) for i in range(layers)]
+        c, mc = (torch.cat(v).numpy() for v in zip(*parts))
+    else:
+        c, mc = (v.numpy() for v in _conv64(_rearranged(a["dec"][:B * L], B, L, e, C, P, S), a["wconv"], a["bconv"], C))
+    assert np.isfinite(got).all() and got.shape == (B, C, S, S)
+    if guided is None:
+        np.testing.assert_allclose(got, c, rtol=0, atol=1e-13 * mc.max())
+        np.testing.assert_allclose(tol, (9 * C + 2) * 2.0 ** -24 * mc, rtol=1e-12)
+        return
+    s = float(np.float32(a["scale"]))
+    if guided == "cfg":
+        u, mu = (v.numpy() for v in _conv64(_rearranged(a["dec"][B * L:], B, L, e, C, P, S), a["wconv"], a["bconv"], C))
+    else:
+        u, mu = (v.numpy() for v in _conv64(_rearranged(a["dec2"], B, a["L2"], a["extras2"], C, P, S), a["wconv2"], a["bconv2"], C))
+        assert a["extras2"] != e
+    np.testing.assert_allclose(got, c + s * (c - u), rtol=0, atol=1e-13 * (mc.max() + mu.max()) * (1 + abs(s)))
+    lin = (9 * C + 2) * 2.0 ** -24 * ((1 + abs(s)) * mc + abs(s) * mu)
+    assert (tol >= lin).all() and (tol <= 1.2 * lin + 2.0 ** -22 * (np.abs(got) + abs(s) * np.abs(c - u))).all()
+
+
+def test_philox4x32_10_known_answers():
+    """the published Random123 vectors of philox4x32_10 (kat_vectors)"""
+    kat = [((0, 0, 0, 0), (0, 0), (0x6627E8D5, 0xE169C58D, 0xBC57AC4C, 0x9B00DBD8)),
+           ((0xFFFFFFFF,) * 4, (0xFFFFFFFF,) * 2, (0x408F276D, 0x41C83B0E, 0xA20BC7C6, 0x6D5451FD)),
+           ((0x243F6A88, 0x85A308D3, 0x13198A2E, 0x03707344), (0xA4093822, 0x299F31D0), (0xD16CFE09, 0x94FDCCEB, 0x5001E420, 0x24126EA1))]
+    for ctr, key, want in kat:
+        assert tuple(int(v) for v in ks.philox4x32_10(np.array(ctr, np.uint32), np.array(key, np.uint32))) == want
+    got = ks.philox4x32_10(np.array([k[0] for k in kat], np.uint32), np.array([k[1] for k in kat], np.uint32))      # vectorised, a key per row
+    assert got.dtype == np.uint32 and np.array_equal(got, np.array([k[2] for k in kat], np.uint32))
+
+
+def test_philox_normal4_ref_against_a_scalar_box_muller():
+    """the words of counter and key (a 64-bit id and a 64-bit seed use both halves), the float32 uniforms, and the float64 functions"""
+    seed, ctr = (0xDEADBEEF << 32) | 0x12345678, 941
+    pix = np.array([0, 1, 4095, (1 << 32) + 7, (5 << 32) | 0xFFFFFFFF], np.uint64)
+    for stream in (ks.PHILOX_STEP, ks.PHILOX_KNOWN):
+        z, ulog = ks.philox_normal4_ref(seed, pix, ctr, stream)
+        assert z.shape == (5, 4) and z.dtype == np.float64 and ulog.dtype == np.float32
+        for i, p in enumerate(int(v) for v in pix):
+            c = [int(v) for v in ks.philox4x32_10(np.array([p & 0xFFFFFFFF, p >> 32, ctr, stream], np.uint32),
+                                                  np.array([seed & 0xFFFFFFFF, seed >> 32], np.uint32))]
+            f = [torch.tensor(v, dtype=torch.int64).to(torch.float32) for v in c]                  # int -> float32, round to nearest even
+            sc = torch.tensor(2.0 ** -32, dtype=torch.float32)
+            for j in (0, 2):
+                u = float((f[j] + 1.0) * sc)
+                ang = float(torch.tensor(6.283185307179586, dtype=torch.float32) * (f[j + 1] * sc))
+                r = math.sqrt(-2.0 * math.log(u))
+                assert ulog[i, j // 2] == np.float32(u)
+                assert abs(z[i, j] - r * math.cos(ang)) <= 1e-14 and abs(z[i, j + 1] - r * math.sin(ang)) <= 1e-14
+    assert not np.array_equal(ks.philox_normal4_ref(seed, pix, ctr)[0], ks.philox_normal4_ref(seed, pix, ctr, ks.PHILOX_KNOWN)[0])
+    # uint32 -> float32 rounds to nearest even: 2^32 - 129 is a tie between 2^32 - 256 and 2^32, and the even neighbour is 2^32
+    assert np.uint32(0xFFFFFF7F).astype(np.float32) == np.float32(2.0 ** 32 - 256) and np.uint32(0xFFFFFF80).astype(np.float32) == np.float32(2.0 ** 32)
+    zz = ks.philox_normal4_ref(3, np.arange(1 << 16, dtype=np.uint64), 0)[0]
+    assert abs(zz.mean()) < 0.01 and abs(zz.std() - 1.0) < 0.01 and np.isfinite(zz).all()
+    ids = ks.final_pixel_ids(2, 4, 5)
+    assert ids.shape == (2, 4, 4) and int(ids[1, 2, 3]) == ((1 + 5) * 4 + 2) * 4 + 3 and int(ks.final_pixel_ids(2, 4, 5, True)[1, 2, 3]) == ((1 + 5) * 4 + 3) * 4 + 2
+    assert int(ks.final_pixel_ids(1, 64, (1 << 20) + 5)[0, 0, 0]) == ((1 << 20) + 5) * 4096 > 1 << 32
+
+
+def _r32(v):
+    """a Python float (exact: sums and products of two float32 of nearby exponents fit float64) rounded to float32"""
+    return float(np.float32(v))
+
+
+def test_step_restatement_rounds_every_operation_once():
+    r = np.random.default_rng(8)
+    x, e, z, h, x0, z2 = (r.standard_normal(512).astype(np.float32) for _ in range(6))
+    m = r.choice(np.array([0.0, 1.0, 0.25, 0.7], np.float32), 512)
+    a, b, c, d, p, q, ka, kb = (float(np.float32(v)) for v in (0.9731, -0.2173, 0.3337, 0.1291, 1.0413, -0.3127, 0.8125, 0.5829))
+    X, E, Z, H, X0, Z2, M = ([float(v) for v in arr] for arr in (x, e, z, h, x0, z2, m))
+    f = lambda v: np.array(v, np.float32)
+    want = [_r32(_r32(a * _r32(xi - _r32(b * ei))) + _r32(c * zi)) for xi, ei, zi in zip(X, E, Z)]
+    assert np.array_equal(ks.step_ddpm(x, e, z, a, b, c), f(want))
+    assert np.array_equal(ks.step_ddpm(x, e, None, a, b, c), f([_r32(a * _r32(xi - _r32(b * ei))) for xi, ei in zip(X, E)]))
+    ab = [_r32(_r32(a * xi) + _r32(b * ei)) for xi, ei in zip(X, E)]
+    abd = [_r32(v + _r32(d * hi)) for v, hi in zip(ab, H)]
+    assert np.array_equal(ks.step_table(x, e, None, h, a, b, c, d, 0), f(ab))
+    assert np.array_equal(ks.step_table(x, e, None, np.full(512, np.nan, np.float32), a, b, c, d, 0), f(ab)), "h must not enter without hist"
+    assert np.array_equal(ks.step_table(x, e, z, h, a, b, c, d, 1), f([_r32(v + _r32(c * zi)) for v, zi in zip(abd, Z)]))
+    assert np.array_equal(ks.step_table(x, e, z, h, a, b, c, d, 0), f([_r32(v + _r32(c * zi)) for v, zi in zip(ab, Z)]))
+    assert np.array_equal(ks.step_history(x, e, p, q), f([_r32(_r32(p * xi) + _r32(q * ei)) for xi, ei in zip(X, E)]))
+    # an FMA would differ: some element of a x + b e must change when the product is not rounded on its own
+    assert any(_r32(a * xi + _r32(b * ei)) != v for xi, ei, v in zip(X, E, ab))
+    xp = np.array(abd, np.float32)
+    for use_z2, kbv in ((True, kb), (False, kb), (True, 0.0)):
+        kn = [_r32(ka * v) if not use_z2 or kbv == 0.0 else _r32(_r32(ka * v) + _r32(kbv * w)) for v, w in zip(X0, Z2)]
+        want = [xi if mi == 0.0 else _r32(_r32(mi * k) + _r32(_r32(1.0 - mi) * xi)) for xi, k, mi in zip(abd, kn, M)]
+        x0n = np.where(m == 0, np.float32(np.nan), x0)                   # NaN in the known image wherever the mask is 0
+        got = ks.step_known(xp, x0n, m, ka, kbv, z2 if use_z2 else None)
+        assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), f(want).view(np.uint32))
+    assert np.array_equal(ks.step_known(xp, x0, np.zeros(512, np.float32), ka, kb, z2).view(np.uint32), xp.view(np.uint32))
+    # float64: the same expressions without the float32 roundings
+    assert np.array_equal(ks.step_table(x, e, z, h, a, b, c, d, 1, np.float64), a * x.astype(np.float64) + b * e.astype(np.float64) + d * h.astype(np.float64) + c * z.astype(np.float64))
+
+
+MUTANTS = [(C, P, S, mut, guided) for C, P in ks.FINAL_FORMS for S in ks.FINAL_SIZES
+           for mut, guided in (("taps", None), ("chan_first", None), ("edge_shift", "cfg"), ("same_weights", "auto"))
+           if not (mut == "chan_first" and (C == 1 or P == 1)) and not (mut == "edge_shift" and S <= 16)]
+
+
+@pytest.mark.parametrize("C,P,S,mut,guided", MUTANTS)
+def test_a_mutant_head_exceeds_the_bound_on_the_test_inputs(C, P, S, mut, guided):
+    """the reference with one deliberate error, against the bound the kernel is held to, on the inputs tests/test_final_step.py uses"""
+    a = ks.final_head_inputs(C, P, S, guided)
+    want, tol = ks.final_eps64(**a)
+    bad, _ = ks.final_eps64(**a, mutant=mut)
+    over = np.abs(bad - want) > tol
+    if mut == "edge_shift":                   # only the last column of a tile that has a right-hand neighbour reads the shifted halo
+        hit = np.zeros(S, bool)
+        hit[15:S - 1:16] = True
+        assert hit.any() and not over[..., ~hit].any() and np.array_equal(bad[..., ~hit], want[..., ~hit])
+        assert over[..., hit].mean() > 0.9
+    else:
+        assert over.mean() > 0.9, over.mean()
+
+
+@pytest.mark.parametrize("case", ks.PHILOX_CASES, ids=lambda c: f"S{c['S']}-C{c['C']}-b{c['b0']}-k{c['ctr']}-{'z2' if c['z2'] else 'z'}")
+def test_philox_cases_near_one_cap_and_the_transposed_id(case):
+    """at most 1 % of a case's draws may be judged at the looser bound of log near 0; the pixel id built as x S + y is off by order 1"""
+    stream = ks.PHILOX_KNOWN if case["z2"] else ks.PHILOX_STEP
+    z, near = ks.final_philox_ref(case["seed"], case["B"], case["C"], case["S"], case["b0"], case["ctr"], stream)
+    assert z.shape == near.shape == (case["B"], case["C"], case["S"], case["S"]) and np.isfinite(z).all()
+    assert near.mean() <= 0.01, near.mean()
+    bad, _ = ks.final_philox_ref(case["seed"], case["B"], case["C"], case["S"], case["b0"], case["ctr"], stream, transposed=True)
+    diag = np.eye(case["S"], dtype=bool)
+    assert np.array_equal(bad[..., diag], z[..., diag]) and (np.abs(bad - z)[..., ~diag] > 1e-4).mean() > 0.99
+    # every other mix-up the test exists for: the other stream word, counter, seed half, image
+    for other in (ks.final_philox_ref(case["seed"], case["B"], case["C"], case["S"], case["b0"], case["ctr"], stream ^ 1)[0],
+                  ks.final_philox_ref(case["seed"], case["B"], case["C"], case["S"], case["b0"], case["ctr"] + 1, stream)[0],
+                  ks.final_philox_ref(case["seed"] ^ (1 << 32), case["B"], case["C"], case["S"], case["b0"], case["ctr"], stream)[0],
+                  ks.final_philox_ref(case["seed"], case["B"], case["C"], case["S"], case["b0"] + 1, case["ctr"], stream)[0],
+                  ks.final_philox_ref(case["seed"], case["B"], case["C"], case["S"], case["b0"] & 0xFFFFF, case["ctr"], stream)[0]
+                  if case["b0"] >> 20 else None):
+        assert other is None or (np.abs(other - z) > 1e-4).mean() > 0.99

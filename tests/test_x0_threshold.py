@@ -12,6 +12,7 @@ from conftest import REPO, TINY
 from duodiff_amd import _lib as L
 from duodiff_amd.config import ModelParams
 from duodiff_amd.weights import synthetic_state_dict
+from kernel_support import step_history, step_table
 from loop_support import cli_argv, known_region, philox_z, philox_z2, side_stream, uvit
 
 gpu = pytest.mark.gpu
@@ -24,7 +25,8 @@ def _thr(mode, **kw):
     return X0Threshold(mode, **kw)
 
 
-# ---- the rule, restated in numpy: every product and sum rounded to float32 on its own, in the order of include/duodiff.h ----------
+# ---- the rule, restated in numpy: every product and sum rounded to float32 on its own, in the order of include/duodiff.h; the update and
+# the history are kernel_support's restatement of step_update.h, shared with tests/test_final_step.py ----------
 def _scale(x0_image, qt, smax, dtype=F):
     """s of one image; dtype float64: the same expression without the float32 roundings"""
     v = np.sort(np.abs(x0_image).ravel())
@@ -41,7 +43,7 @@ def _restate(x, m, z, h, thr, a, b, c, d, p, q, use_hist, dtype=F):
     x, m = np.asarray(x, dtype), np.asarray(m, dtype)
     a, b, c, d, p, q = (dtype(v) for v in (a, b, c, d, p, q))
     with np.errstate(invalid="ignore", over="ignore"):
-        x0 = p * x + q * m
+        x0 = step_history(x, m, p, q, dtype)
         if thr.mode == "static":
             r = dtype(F(thr.range))
             xh = np.minimum(np.maximum(x0, -r), r)
@@ -50,12 +52,7 @@ def _restate(x, m, z, h, thr, a, b, c, d, p, q, use_hist, dtype=F):
             for i in range(len(x0)):
                 s = _scale(x0[i], thr.quantile, F(thr.s_max), dtype)
                 xh[i] = np.minimum(np.maximum(x0[i], -s), s) / s
-        out = a * x + b * xh
-        if use_hist:
-            out = out + d * np.asarray(h, dtype)
-        if z is not None:
-            out = out + c * np.asarray(z, dtype)
-    return out, xh
+    return step_table(x, xh, z, h, a, b, c, d, use_hist, dtype), xh
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------------

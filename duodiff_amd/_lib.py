@@ -160,6 +160,8 @@ SIGNATURES = {
                           [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dd_sample_multistep_threshold": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_guidance),
                                                 C.POINTER(dd_autoguidance), C.POINTER(dd_known_region), C.POINTER(dd_x0_threshold), C.c_void_p]),
+    "dd_set_image_seeds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "dd_noise_images": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dd_bench_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
     "dd_vae_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "dd_vae_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
@@ -193,6 +195,7 @@ SIGNATURES = {
     "dd_dev_time_mlp": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 6 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_vae_gather": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dd_dev_final": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_final_args), C.c_void_p]),
+    "dd_dev_final_seeded": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_final_args), C.c_void_p, C.c_int, C.c_void_p]),
     "dd_dev_poison_workspaces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "dd_dev_graph_captures": (C.c_longlong, [C.c_void_p]),
     "dd_dev_last_sample_chains": (C.c_int, [C.c_void_p]),

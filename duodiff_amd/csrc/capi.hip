@@ -65,7 +65,7 @@ void dd_ctx_destroy(dd_ctx* c) {
     for (StepState* st : c->st) if (st) (void)hipFree(st);
     if (c->coef) (void)hipFree(c->coef);
     c->x_stage.release(); c->y_stage.release(); c->h_stage.release(); c->k_stage.release(); c->m_stage.release();
-    c->atab.release(); c->htab.release(); c->ktab.release();
+    c->atab.release(); c->htab.release(); c->ktab.release(); c->seeds_stage.release();
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     delete c;
 }
@@ -165,6 +165,26 @@ int dd_to_images(dd_ctx* c, const float* x_dev, float* images_dev, int B, int C,
     if (B < 0 || C < 1 || S < 1) return ctx_fail(c, DD_ERR_INVALID, "bad image shape");
     if (B == 0) return DD_OK;
     DD_HIP(c, launch_to_images(x_dev, images_dev, B, C, S, (hipStream_t)stream));
+    return DD_OK;
+}
+
+int dd_set_image_seeds(dd_ctx* c, const uint64_t* seeds_dev, int n) {
+    if (!c) return DD_ERR_INVALID;
+    if (n < 0 || (seeds_dev == nullptr) != (n == 0)) return ctx_fail(c, DD_ERR_INVALID, "dd_set_image_seeds: n seeds on the device, or NULL and 0 to clear");
+    c->seeds_user = seeds_dev;
+    c->seeds_n = n;
+    return DD_OK;
+}
+
+int dd_noise_images(dd_ctx* c, uint64_t seed, const uint64_t* seeds_dev, int counter, float* out_dev, int B, int C, int S, void* stream) {
+    if (!c) return DD_ERR_INVALID;
+    if (!out_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    if (B < 0 || C < 1 || C > 4 || S < 1 || S > 32768) return ctx_fail(c, DD_ERR_INVALID, "bad image shape: B >= 0, C in 1..4, S in 1..32768");
+    if (counter < 0) return ctx_fail(c, DD_ERR_INVALID, "counter must not be negative");
+    if (B == 0) return DD_OK;
+    const hipError_t e = launch_noise_images(out_dev, (const unsigned long long*)seeds_dev, (unsigned long long)seed, counter, B, C, S, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue) return ctx_fail(c, DD_ERR_INVALID, "dd_noise_images: a batch this launch cannot cover");
+    DD_HIP(c, e);
     return DD_OK;
 }
 

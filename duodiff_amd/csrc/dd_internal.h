@@ -359,6 +359,9 @@ struct FinalArgs {
     const float* kx0 = nullptr;
     const float* kmask = nullptr;
     const KnownRow* ktab = nullptr;
+    // per-image seeds (dd_set_image_seeds) of the WHOLE batch, or null: image b of this launch draws z / z2 under seeds[b0 + b] with
+    // image-local pixel ids (step_update.h draw_site); null: st->seed and the batch-wide pixel ids
+    const unsigned long long* seeds = nullptr;
 };
 hipError_t launch_final(const FinalArgs& a, hipStream_t s);
 hipError_t init_rowops_kernels();
@@ -442,6 +445,7 @@ struct ThresholdArgs {
     const KnownRow* ktab = nullptr;
     X0Threshold thr{};
     int B = 0, C = 0, S = 0;
+    const unsigned long long* seeds = nullptr;     // as FinalArgs::seeds (the loop only)
 };
 hipError_t launch_threshold_step(const ThresholdArgs& a, hipStream_t s);
 
@@ -457,10 +461,14 @@ hipError_t launch_ee_select(const float* outs, const float* eps, const float* cl
                             float* mo, int* idx, float* err_mean, hipStream_t s);
 // the selection and the DDPM update in one launch (the device-resident loop): idx / err_mean are [1000, idx_stride] / [1000, depth] tables and row
 // st->t_final is written.  A half-batch chain: B = the chain's images, idx_col0 = its first image within the whole batch (its idx columns,
-// its Philox pixel ids); sums: err_mean receives the plain per-layer SUM over the chain's images (launch_ee_mean_combine joins the chains)
+// its Philox pixel ids); sums: err_mean receives the plain per-layer SUM over the chain's images (launch_ee_mean_combine joins the chains);
+// seeds: the whole batch's per-image seeds (FinalArgs::seeds) or null
 hipError_t launch_ee_select_step(float* x, const float* outs, const float* eps, const float* cls, float thr, int depth, int* idx, float* err_mean,
                                  int idx_stride, int idx_col0, bool sums, StepState* st, const StepCoef* coef, int B, int C, int S,
-                                 int noise_mode, int advance, hipStream_t s);
+                                 int noise_mode, int advance, hipStream_t s, const unsigned long long* seeds = nullptr);
+// out [B, C, S, S] = the x_T draw of step_update.h (PHILOX_START) under `seed` (seeds null) or the per-image seeds [B]; C in 1..4; a bad
+// argument is hipErrorInvalidValue with nothing launched
+hipError_t launch_noise_images(float* out, const unsigned long long* seeds, unsigned long long seed, int ctr, int B, int C, int S, hipStream_t s);
 hipError_t launch_ee_mean_combine(const float* s0, const float* s1, float* err, int depth, int t_lo, int t_hi, int B, hipStream_t s);
 hipError_t launch_set_state(StepState* st, int t, unsigned long long seed, hipStream_t s);
 hipError_t launch_set_state_table(StepState* st, const AffineRow* atab, unsigned long long seed, hipStream_t s);   // step index 0

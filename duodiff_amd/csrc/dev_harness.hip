@@ -617,9 +617,13 @@ int dd_dev_vae_gather(dd_ctx* c, int kind, int precision, int B, int H, int W, i
     return dev.status();
 }
 
-int dd_dev_final(dd_ctx* c, dd_dev_final_args* p, void* stream) {
+}  // extern "C"
+
+// dd_dev_final, and dd_dev_final_seeded with the n per-image seeds of the whole batch (seeds_host null: none)
+static int dev_final(dd_ctx* c, dd_dev_final_args* p, const uint64_t* seeds_host, int n_seeds, void* stream) {
     if (!c || !p) return DD_ERR_INVALID;
     const dd_dev_final_args& q = *p;
+    if (seeds_host && (q.b0 < 0 || q.B < 1 || n_seeds > (1 << 22) || (long long)n_seeds < (long long)q.b0 + q.B)) return DD_ERR_INVALID;
     // ---- everything the selected instantiation dereferences, before anything touches the GPU
     if (q.B < 1 || q.B > 4096 || q.C < 1 || q.C > 4 || q.P < 1 || q.P * q.P * q.C > 64 || q.S < q.P || q.S > 1024 || q.S % q.P || q.extras < 0 ||
         q.extras > 64 || q.b0 < 0 || q.images < q.B || q.images > 2 * q.B + 64 || !q.dec || !q.wconv || !q.bconv)
@@ -699,6 +703,7 @@ int dd_dev_final(dd_ctx* c, dd_dev_final_args* p, void* stream) {
         if (dev.ok()) dev.ok(hipMemcpy(ktab + q.t, &kr, sizeof kr, hipMemcpyHostToDevice), "hipMemcpy to the device");
         fa.kx0 = dev.upload(q.kx0, n_in * 4); fa.kmask = dev.upload(q.kmask, (size_t)q.B * q.S * q.S * 4); fa.ktab = ktab;
     }
+    if (seeds_host) fa.seeds = (const unsigned long long*)dev.upload(seeds_host, (size_t)n_seeds * sizeof(uint64_t));
     const hipError_t first = dev.ok() ? launch_final(fa, s) : hipSuccess;
     if (first == hipErrorInvalidValue) return ctx_fail(c, DD_ERR_INVALID, "final: a combination of operands launch_final refuses");      // (refused before any launch)
     DEV_HIP(dev, first);
@@ -710,6 +715,15 @@ int dd_dev_final(dd_ctx* c, dd_dev_final_args* p, void* stream) {
     dev.download(&st1, fa.st, sizeof st1);
     if (dev.ok()) { p->t_out = st1.t; p->t_final_out = st1.t_final; p->t_model_out = st1.t_model; p->seed_out = st1.seed; }
     return dev.status();
+}
+
+extern "C" {
+
+int dd_dev_final(dd_ctx* c, dd_dev_final_args* p, void* stream) { return dev_final(c, p, nullptr, 0, stream); }
+
+int dd_dev_final_seeded(dd_ctx* c, dd_dev_final_args* p, const uint64_t* seeds_host, int n, void* stream) {
+    if (!seeds_host || n < 1) return DD_ERR_INVALID;
+    return dev_final(c, p, seeds_host, n, stream);
 }
 
 }  // extern "C"

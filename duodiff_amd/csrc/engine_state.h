@@ -79,6 +79,11 @@ struct dd_ctx {
     dd::DevBuf<float> k_stage;       //   and the known image and mask the loop reads (x0 [B, C, S, S] | mask [B, 1, S, S], staged like x)
     dd::DevBuf<float> m_stage;       // dd_sample_multistep_threshold: the step's (guided) model output [B, C, S, S], chain k's images at its first image:
                                  //   written by the output head and read by threshold_step_kernel within one step, never across steps
+    // dd_set_image_seeds: the caller's per-image seeds (device, seeds_n of them; null: the plain noise), and the context's own copy that
+    // the kernels read -- copied at every call that draws device noise (stage_image_seeds), so a captured step is reused across seeds
+    const uint64_t* seeds_user = nullptr;
+    int seeds_n = 0;
+    dd::DevBuf<unsigned long long> seeds_stage;
     int prof_kind = 0;           // dd_profile_select: which launches dd_profile_steps brackets (DD_PROF_*)
     unsigned dev_flags = 0;      // dd_dev_set_flags (include/duodiff_dev.h): kernel-variant switches of the development harness
 };
@@ -121,6 +126,7 @@ struct GraphKey {
     const void* tscratch = nullptr;
     int pag = 0;                                                     // perturbed-attention guidance: set (gscale: the scale's bits), and the
     unsigned pfirst = 0, plate = 0;                                  //   masks of the loop's two models
+    const void* seeds = nullptr;                                     // per-image seeds: the context's staged copy (null: the plain noise)
     bool operator==(const GraphKey&) const = default;
     void perturb(const dd_pag* p) {
         if (p) { pag = 1; gscale = __builtin_bit_cast(unsigned, p->scale); pfirst = p->layers_first; plate = p->layers_late; }
@@ -244,6 +250,8 @@ struct Mods {
     const dd_pag* pag = nullptr;              // perturbed-attention guidance (never with g, ag, kr or thr): B images run as the 2 B backbone rows [x | x]
     const dd_model* pag_late = nullptr;       //   with the labels [y | y]; the second half's attention is the identity in the running model's masked
                                               //   blocks: layers_late where that model is pag_late, else layers_first
+    const unsigned long long* seeds = nullptr;   // per-image seeds of the WHOLE batch, staged (stage_image_seeds), or null: in a Slice too -- the
+                                              //   kernels index them by b0 + b, the image, under either guidance that doubles the rows
     unsigned pag_mask(const dd_model* m) const { return !pag ? 0u : (pag_late && m == pag_late) ? pag->layers_late : pag->layers_first; }
 };
 
@@ -299,6 +307,11 @@ int stage_inputs(dd_ctx* c, const float* x_dev, const int64_t* y_dev, int B, siz
 int stage_guided(dd_ctx* c, const float* x_dev, const int64_t* y_dev, int B, int B0, size_t chw, int null_label, hipStream_t s,
                  float** x_run, const int64_t** y_run);
 int unstage_guided(dd_ctx* c, float* x_dev, const float* x_run, int B, int B0, size_t chw, hipStream_t s);
+// The context's per-image seeds for a call of B images in this noise mode.  check: DD_ERR_INVALID where they are set, the call draws device
+// noise and n != B -- before anything is enqueued.  stage: *seeds = the context's copy, refreshed from the caller's array on s (null where
+// none are set or the call draws no device noise: DD_NOISE_BUFFER and DD_NOISE_NONE calls are what they are without them).
+int check_image_seeds(dd_ctx* c, int noise_mode, int B);
+int stage_image_seeds(dd_ctx* c, int noise_mode, hipStream_t s, const unsigned long long** seeds);
 
 }  // namespace dd
 #pragma GCC visibility pop

@@ -516,7 +516,7 @@ int enqueue_step(dd_ctx* c, dd_model* m, const Chain& ch, float* x_dev, const in
         ta.st = ch.st; ta.coef = c->coef; ta.atab = o.atab; ta.htab = o.htab;
         ta.noise_mode = o.noise_mode; ta.advance = o.advance; ta.b0 = o.b0; ta.pair_B = fa.pair_B;
         ta.kx0 = o.mods.kn.x0; ta.kmask = o.mods.kn.mask; ta.ktab = o.mods.kn.ktab;
-        ta.thr = *o.thr; ta.B = B; ta.C = m->cfg.in_chans; ta.S = m->cfg.img_size;
+        ta.thr = *o.thr; ta.B = B; ta.C = m->cfg.in_chans; ta.S = m->cfg.img_size; ta.seeds = o.mods.seeds;
         DD_HIP(c, launch_threshold_step(ta, s));
         return DD_OK;
     }
@@ -524,7 +524,22 @@ int enqueue_step(dd_ctx* c, dd_model* m, const Chain& ch, float* x_dev, const in
     fa.noise_mode = o.noise_mode; fa.variance = o.variance; fa.advance = o.advance; fa.atab = o.atab; fa.b0 = o.b0;
     fa.htab = o.htab; fa.h = o.h;
     fa.kx0 = o.mods.kn.x0; fa.kmask = o.mods.kn.mask; fa.ktab = o.mods.kn.ktab;
+    fa.seeds = o.mods.seeds;
     DD_HIP(c, launch_final(fa, s));
+    return DD_OK;
+}
+
+int check_image_seeds(dd_ctx* c, int noise_mode, int B) {
+    if (c->seeds_user && noise_mode == DD_NOISE_PHILOX && c->seeds_n != B)
+        return ctx_fail(c, DD_ERR_INVALID, "dd_set_image_seeds holds " + std::to_string(c->seeds_n) + " seeds, the call has " + std::to_string(B) + " images");
+    return DD_OK;
+}
+int stage_image_seeds(dd_ctx* c, int noise_mode, hipStream_t s, const unsigned long long** seeds) {
+    *seeds = nullptr;
+    if (!c->seeds_user || noise_mode != DD_NOISE_PHILOX) return DD_OK;
+    if (int rc = c->seeds_stage.grow(c, (size_t)c->seeds_n)) return rc;
+    DD_HIP(c, hipMemcpyAsync(c->seeds_stage.p, c->seeds_user, (size_t)c->seeds_n * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+    *seeds = c->seeds_stage.p;
     return DD_OK;
 }
 
@@ -657,10 +672,13 @@ int dd_sample_step(dd_ctx* c, dd_model* m, float* x_dev, int t, const int64_t* y
     if (!x_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
     if (t < 0 || t > 999) return ctx_fail(c, DD_ERR_INVALID, "timestep outside [0, 999]");
     if (noise_mode == DD_NOISE_BUFFER && !z_dev && t > 0) return ctx_fail(c, DD_ERR_INVALID, "DD_NOISE_BUFFER needs z_dev");
+    if ((rc = check_image_seeds(c, noise_mode, B))) return rc;
     hipStream_t s = (hipStream_t)stream;
+    const unsigned long long* seeds = nullptr;
+    if ((rc = stage_image_seeds(c, noise_mode, s, &seeds))) return rc;
     DD_HIP(c, launch_set_state(c->st[0], t, (unsigned long long)seed, s));
     return enqueue_step(c, m, whole_batch(c, m), x_dev, y_dev, B, s,
-                        {.noise_mode = noise_mode, .z = z_dev, .variance = variance, .eps_out = eps_out_dev});
+                        {.mods = {.seeds = seeds}, .noise_mode = noise_mode, .z = z_dev, .variance = variance, .eps_out = eps_out_dev});
 }
 
 }  // extern "C"

@@ -130,6 +130,7 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
             key.guide(g);
             key.perturb(pag);
             key.kx0 = sl.mods.kn.x0; key.kmask = sl.mods.kn.mask; key.ktab = sl.mods.kn.ktab;
+            key.seeds = L.mods.seeds;
             L.key(key, sl);
             for (dd_model* m : {L.first, L.late}) {
                 if (!m) continue;
@@ -270,6 +271,7 @@ int check_loop(dd_ctx* c, const Args* a, const Mods& mo, const char* no_early_ex
     if (!mo.ag && a->late && (rc = check(a->late))) return rc;
     if ((rc = own_checks())) return rc;
     if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE) return ctx_fail(c, DD_ERR_INVALID, host_noise);
+    if ((rc = check_image_seeds(c, a->noise_mode, a->B))) return rc;
     if (a->late) {
         const dd_config &f = a->first->cfg, &l = a->late->cfg;
         if (f.img_size != l.img_size || f.in_chans != l.in_chans) return ctx_fail(c, DD_ERR_INVALID, "first and late model disagree on image shape");
@@ -343,6 +345,7 @@ int sample_ddpm(dd_ctx* c, const dd_sample_args* a, Mods mo, void* stream) {
         const long long k = t0 - (long long)t;
         return k >= 0 && k < n ? KnownRow{kr->ka[k], kr->kb[k]} : KnownRow{0.f, 0.f};
     };
+    if ((rc = stage_image_seeds(c, a->noise_mode, (hipStream_t)stream, &mo.seeds))) return rc;
     if ((rc = stage_known(c, mo, a->first, a->B, 1000, (hipStream_t)stream, known_row))) return rc;
     Loop L{GRAPH_DDPM, a->first, switching ? a->late : nullptr, n, switch_here ? a->t_start - t_sw + 1 : -1, a->x_dev, a->y_dev, a->B, mo,
            a->use_graph != 0};
@@ -363,6 +366,7 @@ int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, Mods mo, void* stre
     hipStream_t s = (hipStream_t)stream;
     const int n = a->n_steps;
     const bool switching = a->late && a->switch_after >= 0 && a->switch_after < n;
+    if ((rc = stage_image_seeds(c, a->noise_mode, s, &mo.seeds))) return rc;
     if ((rc = upload_atab(c, a, s))) return rc;
     if ((rc = stage_table_known(c, mo, a->first, a->B, n, s))) return rc;
     const AffineRow* atab = c->atab.dev.p;
@@ -397,6 +401,7 @@ int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, Mods mo, void
     hipStream_t s = (hipStream_t)stream;
     const int n = a->n_steps;
     const bool switching = a->late && a->switch_after >= 0 && a->switch_after < n;
+    if ((rc = stage_image_seeds(c, a->noise_mode, s, &mo.seeds))) return rc;
     if ((rc = upload_atab(c, a, s))) return rc;
     rc = upload_rows(c, c->htab, (size_t)n + 1, s, [a, n](size_t k) {
         return k < (size_t)n ? HistRow{a->d[k], a->p[k], a->q[k], a->hist[k] ? 1 : 0} : HistRow{0.f, 0.f, 0.f, 0};
@@ -483,9 +488,9 @@ int dd_sample_multistep_threshold(dd_ctx* c, const dd_multistep_sample_args* a, 
 // One early-exit sampling step on the device (reference eesampler.py:56-81): EarlyExitUViT.forward with every head and
 // probe -> per-sample exit selection -> DDPM update with the selected output; rows t of the two log tables are written.
 // ws: the chain's scratch block (eps | cls | outs for B images, ee_scratch_elems); b0 / B_all: the chain's first image within the whole batch
-// and the whole batch (idx_tab rows are B_all wide); sums: err_tab is the chain's table of per-layer SUMS (launch_ee_mean_combine joins the chains)
+// and the whole batch (idx_tab rows are B_all wide); seeds: the whole batch's staged per-image seeds or null; sums: err_tab is the chain's table of per-layer SUMS (launch_ee_mean_combine joins the chains)
 static int enqueue_ee_step(dd_ctx* c, dd_model* m, const Chain& ch, float* ws, float* x, const int64_t* y, float thr, float* err_tab,
-                           int32_t* idx_tab, int noise_mode, int B, hipStream_t s, int b0, int B_all, bool sums) {
+                           int32_t* idx_tab, int noise_mode, int B, hipStream_t s, int b0, int B_all, bool sums, const unsigned long long* seeds) {
     const long long chw = (long long)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
     const int depth = m->cfg.depth;
     float* eps = ws;
@@ -495,7 +500,7 @@ static int enqueue_ee_step(dd_ctx* c, dd_model* m, const Chain& ch, float* ws, f
     if (int rc = forward_eps(c, m, ch, x, y, eps, B, s, {.ee = &ee})) return rc;
     // exit layer per image, the selected output and the DDPM update in one launch (dd_early_exit_select + the step kernel, fused: same arithmetic)
     DD_HIP(c, launch_ee_select_step(x, outs, eps, cls, thr, depth, idx_tab, err_tab, B_all, b0, sums, ch.st, c->coef, B,
-                                    m->cfg.in_chans, m->cfg.img_size, noise_mode, 1, s));
+                                    m->cfg.in_chans, m->cfg.img_size, noise_mode, 1, s, seeds));
     return DD_OK;
 }
 
@@ -509,6 +514,9 @@ int dd_sample_early_exit(dd_ctx* c, const dd_ee_sample_args* a, void* stream) {
     if (a->t_start > 999 || a->t_end < 0 || a->t_end > a->t_start) return ctx_fail(c, DD_ERR_INVALID, "need 999 >= t_start >= t_end >= 0");
     if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE)
         return ctx_fail(c, DD_ERR_INVALID, "dd_sample_early_exit generates noise on the device; for host noise drive dd_forward_early_exit");
+    if ((rc = check_image_seeds(c, a->noise_mode, a->B))) return rc;
+    const unsigned long long* seeds = nullptr;
+    if ((rc = stage_image_seeds(c, a->noise_mode, (hipStream_t)stream, &seeds))) return rc;
     // Two half-batch chains, as dd_sample: the samples are independent (every exit decision is per sample); the one quantity over the whole
     // batch -- the logged per-layer mean of the predicted errors, eesampler.py:70 -- becomes per-chain sums that one small launch joins
     // behind the loop, (chain 0 + chain 1) / B.  Heads and probes stay on each chain's own stream (measured: the 13 forks as parallel
@@ -517,7 +525,7 @@ int dd_sample_early_exit(dd_ctx* c, const dd_ee_sample_args* a, void* stream) {
     if (!m->ee_ws) DD_HIP(c, hipMalloc((void**)&m->ee_ws, (ee_scratch_elems(m, m->cfg.max_batch) + 2 * tab) * sizeof(float)));
     float* sums = m->ee_ws + ee_scratch_elems(m, m->cfg.max_batch);
     auto err_tab = [&](const Slice& sl) { return sl.chains == 1 || !a->err_dev ? a->err_dev : sums + sl.chain * tab; };
-    Loop L{GRAPH_EARLY_EXIT, m, nullptr, a->t_start - a->t_end + 1, -1, a->x_dev, a->y_dev, a->B, Mods{}, a->use_graph != 0};
+    Loop L{GRAPH_EARLY_EXIT, m, nullptr, a->t_start - a->t_end + 1, -1, a->x_dev, a->y_dev, a->B, Mods{.seeds = seeds}, a->use_graph != 0};
     L.set_state = [&](StepState* st, hipStream_t s) { return launch_set_state(st, a->t_start, (unsigned long long)a->seed, s); };
     L.key = [&](GraphKey& k, const Slice& sl) {
         k.noise = a->noise_mode; k.aux0 = err_tab(sl); k.aux1 = a->idx_dev; k.thr = a->threshold;
@@ -525,7 +533,7 @@ int dd_sample_early_exit(dd_ctx* c, const dd_ee_sample_args* a, void* stream) {
     };
     L.step = [&](dd_model* mm, const Chain& ch, const Slice& sl, hipStream_t s) {
         return enqueue_ee_step(c, mm, ch, mm->ee_ws + ee_scratch_elems(mm, sl.b0), sl.x, sl.y, a->threshold, err_tab(sl), a->idx_dev,
-                               a->noise_mode, sl.B, s, sl.b0, a->B, sl.chains == 2);
+                               a->noise_mode, sl.B, s, sl.b0, a->B, sl.chains == 2, sl.mods.seeds);
     };
     L.tail = [&](int chains, hipStream_t s) -> int {
         if (chains == 2 && a->err_dev) DD_HIP(c, launch_ee_mean_combine(sums, sums + tab, a->err_dev, m->cfg.depth, a->t_end, a->t_start, a->B, s));

@@ -78,14 +78,16 @@ __global__ void __launch_bounds__(256) final_tiled_kernel(const FinalArgs a) {
                            (in ? ((yy % P) * P + (xx % P)) * C : 0);
         for (int ci = 0; ci < C; ++ci) u[hh][ci][hy][hx] = in ? src[ci] : 0.f;
     }
-    if (inside && a.x_out && rule.draws()) {   // pixel id within the WHOLE batch (b0: this launch's first image): a half-batch chain draws the z the undivided batch would
-        const f32x4 zn = philox_normal4(a.st->seed, ((unsigned long long)(b + a.b0) * S + y) * S + x, rule.ctr);
+    if (inside && a.x_out && rule.draws()) {   // (key, id) of the pixel within the WHOLE batch (b0: this launch's first image), or under the image's own seed: draw_site
+        const DrawSite ds = draw_site(a.seeds, a.st->seed, (unsigned long long)(b + a.b0), (unsigned long long)(y * S + x), (unsigned long long)S * S);
+        const f32x4 zn = philox_normal4(ds.key, ds.id, rule.ctr);
 #pragma unroll
         for (int co = 0; co < 4; ++co) zin[co] = zn[co];
     }
     if constexpr (K) {
         if (inside && a.x_out && krule.draws()) {   // z2: the same key, pixel id and counter as z, the known region's stream word
-            const f32x4 zn = philox_normal4(a.st->seed, ((unsigned long long)(b + a.b0) * S + y) * S + x, rule.ctr, PHILOX_KNOWN);
+            const DrawSite ds = draw_site(a.seeds, a.st->seed, (unsigned long long)(b + a.b0), (unsigned long long)(y * S + x), (unsigned long long)S * S);
+            const f32x4 zn = philox_normal4(ds.key, ds.id, rule.ctr, PHILOX_KNOWN);
 #pragma unroll
             for (int co = 0; co < 4; ++co) z2in[co] = zn[co];
         }
@@ -165,21 +167,25 @@ __global__ void ddpm_step_kernel(const float* __restrict__ x, const float* __res
 
 // Exit selection and the update in one launch (the device-resident early-exit loop: two launches less on every step's serial tail,
 // and the selected model output never travels through HBM): per pixel, the image's exit layer from cls, then the update on
-// (outputs ++ [eps])[idx], z from the Philox generator of the fused step (same counter: pixel, t).  x [B, C, S, S] in place; pix0: a
-// half-batch chain's first pixel within the whole batch.
+// (outputs ++ [eps])[idx], z from the Philox generator of the fused step (same counter: pixel, t).  x [B, C, S, S] in place; b0: a
+// half-batch chain's first image within the whole batch; seeds: the whole batch's per-image seeds or null (draw_site).
 __global__ void __launch_bounds__(256) ee_select_step_kernel(float* __restrict__ x, const float* __restrict__ outs, const float* __restrict__ eps,
                                                              const float* __restrict__ cls, float thr, int depth, int* __restrict__ idx_out,
                                                              int idx_stride, int idx_col0, StepState* st, const StepCoef* __restrict__ coef,
-                                                             int B, int C, int S, int noise_mode, int advance, long long pix0) {
+                                                             int B, int C, int S, int noise_mode, int advance, int b0,
+                                                             const unsigned long long* __restrict__ seeds) {
 #pragma clang fp contract(off)
     const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long hw = (long long)S * S;
     const StepRule<false> rule(st, coef, nullptr, nullptr, noise_mode == 2 ? 2 : 0, 0, advance);   // (this loop draws on the device or not at all)
     if (pix == 0) rule.advance(st);
     if (pix >= (long long)B * hw) return;
-    f32x4 zn = {0.f, 0.f, 0.f, 0.f};
-    if (rule.draws()) zn = philox_normal4(st->seed, (unsigned long long)(pix + pix0), rule.ctr);
     const long long b = pix / hw, p = pix - b * hw;
+    f32x4 zn = {0.f, 0.f, 0.f, 0.f};
+    if (rule.draws()) {
+        const DrawSite ds = draw_site(seeds, st->seed, (unsigned long long)(b + b0), (unsigned long long)p, (unsigned long long)hw);
+        zn = philox_normal4(ds.key, ds.id, rule.ctr);
+    }
     const int idx = ee_exit_layer(cls, thr, depth, B, (int)b);
     if (idx_out && p == 0) idx_out[(long long)rule.t * idx_stride + idx_col0 + b] = idx;     // row t of indices_by_timestep (eesampler.py:71)
     const float* src = idx == depth ? eps : outs + (long long)idx * B * C * hw;
@@ -284,7 +290,7 @@ __global__ void __launch_bounds__(1024) threshold_step_kernel(const ThresholdArg
             store_w<W>(&x0s[e0], x0);
         }
     }
-    // Philox z (and the known region's z2): the batch-wide pixel id, the step's counter, the two stream words, as final_tiled_kernel draws
+    // Philox z (and the known region's z2): the (key, id) of draw_site, the step's counter, the two stream words, as final_tiled_kernel draws
     // them -- one draw serves a pixel's channels, so a slot reuses the previous slot's draws where it holds the same pixels of the next channel
     const bool zdraw = rule.draws(), z2draw = kn_on && krule.draws();
     if (zdraw || z2draw) {
@@ -299,9 +305,9 @@ __global__ void __launch_bounds__(1024) threshold_step_kernel(const ThresholdArg
                 if (pix != drawn) {
 #pragma unroll
                     for (int w = 0; w < W; ++w) {
-                        const unsigned long long id = (unsigned long long)(b + a.b0) * hw + pix + w;
-                        if (zdraw) zc[w] = philox_normal4(seed, id, rule.ctr);
-                        if (z2draw) z2c[w] = philox_normal4(seed, id, rule.ctr, PHILOX_KNOWN);
+                        const DrawSite ds = draw_site(a.seeds, seed, (unsigned long long)(b + a.b0), (unsigned long long)(pix + w), (unsigned long long)hw);
+                        if (zdraw) zc[w] = philox_normal4(ds.key, ds.id, rule.ctr);
+                        if (z2draw) z2c[w] = philox_normal4(ds.key, ds.id, rule.ctr, PHILOX_KNOWN);
                     }
                     drawn = pix;
                 }
@@ -405,6 +411,32 @@ __global__ void __launch_bounds__(1024) threshold_step_kernel(const ThresholdArg
             store_w<W>(a.out + base + e0, out);
             if (a.pair_B > 0) store_w<W>(a.out + base + pair + e0, out);
         }
+    }
+}
+
+// x_T on the device (dd_noise_images): out [B, C, S, S], channel c of pixel p of image b = component c of philox_normal4 at draw_site's (key, id)
+// (b0 = 0), counter ctr, the stream word PHILOX_START -- independent of every step's z and z2 under the same key.  One draw serves a pixel's
+// channels.  A thread owns W consecutive pixels of one image: W = 4 where hw % 4 == 0 and out is 16-byte aligned (one 16-byte store per
+// channel), else W = 1 with plain stores.
+template <int W>
+__global__ void __launch_bounds__(256) noise_images_kernel(float* __restrict__ out, const unsigned long long* __restrict__ seeds, unsigned long long seed,
+                                                           int ctr, int B, int C, int hw) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int per_image = hw / W;
+    if (i >= (long long)B * per_image) return;
+    const long long b = i / per_image;
+    const int p0 = (int)(i - b * per_image) * W;
+    f32x4 zn[W];
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        const DrawSite ds = draw_site(seeds, seed, (unsigned long long)b, (unsigned long long)(p0 + w), (unsigned long long)hw);
+        zn[w] = philox_normal4(ds.key, ds.id, ctr, PHILOX_START);
+    }
+    for (int c = 0; c < C; ++c) {
+        float v[W];
+#pragma unroll
+        for (int w = 0; w < W; ++w) v[w] = pick(zn[w], c);
+        store_w<W>(out + (b * C + c) * hw + p0, v);
     }
 }
 
@@ -561,11 +593,21 @@ hipError_t launch_ee_select(const float* outs, const float* eps, const float* cl
 }
 hipError_t launch_ee_select_step(float* x, const float* outs, const float* eps, const float* cls, float thr, int depth, int* idx, float* err_mean,
                                  int idx_stride, int idx_col0, bool sums, StepState* st, const StepCoef* coef, int B, int C, int S,
-                                 int noise_mode, int advance, hipStream_t s) {
+                                 int noise_mode, int advance, hipStream_t s, const unsigned long long* seeds) {
     const long long npix = (long long)B * S * S;
     if (err_mean) hipLaunchKernelGGL(ee_batch_mean_kernel, dim3(depth), dim3(64), 0, s, cls, err_mean, B, st, sums ? 1.0f : 0.0f);
     hipLaunchKernelGGL(ee_select_step_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, x, outs, eps, cls, thr, depth, idx,
-                       idx_stride > 0 ? idx_stride : B, idx_col0, st, coef, B, C, S, noise_mode, advance, (long long)idx_col0 * S * S);
+                       idx_stride > 0 ? idx_stride : B, idx_col0, st, coef, B, C, S, noise_mode, advance, idx_col0, seeds);
+    return hipGetLastError();
+}
+hipError_t launch_noise_images(float* out, const unsigned long long* seeds, unsigned long long seed, int ctr, int B, int C, int S, hipStream_t s) {
+    const long long hw = (long long)S * S;
+    if (!out || B < 1 || C < 1 || C > 4 || S < 1 || hw > (1ll << 30) || ctr < 0) return hipErrorInvalidValue;
+    const bool vec = hw % 4 == 0 && (uintptr_t)out % 16 == 0;
+    const long long threads = (long long)B * (vec ? hw / 4 : hw), blocks = (threads + 255) / 256;
+    if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+    if (vec) hipLaunchKernelGGL(noise_images_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, out, seeds, seed, ctr, B, C, (int)hw);
+    else hipLaunchKernelGGL(noise_images_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, out, seeds, seed, ctr, B, C, (int)hw);
     return hipGetLastError();
 }
 hipError_t launch_ee_mean_combine(const float* s0, const float* s1, float* err, int depth, int t_lo, int t_hi, int B, hipStream_t s) {

@@ -11,9 +11,22 @@ namespace dd {
 // Device noise: Philox4x32-10 counter RNG + Box-Muller.  Counter = (element/4, t, 0, 0),
 // key = seed.  Statistically N(0,1); NOT the torch CPU mt19937 stream (that is DD_NOISE_BUFFER).
 // The fourth counter word names the stream: PHILOX_STEP for the update's z, PHILOX_KNOWN for the z2 of a known region --
-// the same key, pixel and counter give two independent draws.
+// the same key, pixel and counter give two independent draws.  PHILOX_START is the stream of x_T (dd_noise_images).
 // ------------------------------------------------------------------------------------------
-constexpr unsigned PHILOX_STEP = 0x5eedu, PHILOX_KNOWN = 0x6b6e6f77u;
+constexpr unsigned PHILOX_STEP = 0x5eedu, PHILOX_KNOWN = 0x6b6e6f77u, PHILOX_START = 0x78545f30u;
+
+// The draw site, defined once: the Philox key and pixel id of pixel p = y S + x (hw = S S pixels per image) of image bg of the WHOLE batch
+// (bg = the launch's first image b0 + the launch's image b: a half-batch chain draws what the undivided batch would).
+//   plain  (seeds == null)  key = seed,       id = bg hw + p    -- the batch-wide pixel id: an image's noise depends on where it sits
+//   seeded                  key = seeds[bg],  id = p            -- per-image seeds (dd_set_image_seeds): it depends on its seed alone
+// so a seeded image with seed s draws exactly what the plain call with B = 1 and seed = s draws.  `seeds` is a launch argument: the
+// branch is uniform.  Every drawing kernel takes (key, id) from here and holds no id arithmetic of its own.
+struct DrawSite { unsigned long long key, id; };
+__device__ __forceinline__ DrawSite draw_site(const unsigned long long* __restrict__ seeds, unsigned long long seed, unsigned long long bg,
+                                              unsigned long long p, unsigned long long hw) {
+    if (seeds) return DrawSite{seeds[bg], p};
+    return DrawSite{seed, bg * hw + p};
+}
 __device__ __forceinline__ void philox_round(unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3,
                                              unsigned k0, unsigned k1) {
     const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;

@@ -7,6 +7,10 @@ with ``seed = base_seed + r``, which is bit-for-bit what the r-th independent re
 batch).  Exactly ONE collective closes a run: the gather of the finished images
 (RCCL over xGMI when the backend is "nccl", gloo on CPU for tests).
 
+With ``--image_seeds`` the run is instead ONE set of pictures, image i under seed ``base_seed + first_image + i``: every rank keeps
+the base seed and rank r samples images ``first_image + r B ...``, so the gathered W x B images equal one rank's run of W B images, and
+any image can be regenerated alone (``--first_image i --batch_size 1``).
+
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m duodiff_amd.dist --config_path ... (same flags as sampler)
 """
 import os
@@ -43,6 +47,11 @@ def rank_seed(base_seed: int, rank: int) -> int:
     return int(base_seed) + int(rank)
 
 
+def rank_first_image(first_image: int, rank: int, batch_size: int) -> int:
+    """--image_seeds: the first image of rank r's shard within the whole run"""
+    return int(first_image) + int(rank) * int(batch_size)
+
+
 def gather_images(local: torch.Tensor, world: int, dst: Optional[int] = None):
     """The single collective: all ranks' [B,H,W,C] images, in rank order.
 
@@ -70,16 +79,17 @@ def gather_images(local: torch.Tensor, world: int, dst: Optional[int] = None):
 
 
 def sample_sharded(sample_fn: Callable[[int], torch.Tensor], base_seed: int, dst: Optional[int] = None,
-                   barrier: bool = True):
+                   barrier: bool = True, rank_seeds: bool = True):
     """Run ``sample_fn(seed)`` (one rank's whole sampling loop, returning [B,H,W,C] images) on every
     rank with its own seed, then gather.  No communication happens inside ``sample_fn``.
+    rank_seeds=False (per-image seeds): every rank gets the base seed; ``sample_fn`` names its shard by its first image.
 
     Returns (gathered images or None on non-destination ranks, this rank's local images).
     """
     rank, world, _ = env_rank()
     if world > 1 and not dist.is_initialized():
         raise RuntimeError("call duodiff_amd.dist.init() first")
-    local = sample_fn(rank_seed(base_seed, rank))
+    local = sample_fn(rank_seed(base_seed, rank) if rank_seeds else int(base_seed))
     if not torch.is_tensor(local):
         local = torch.from_numpy(np.asarray(local))
     if world > 1 and barrier:
@@ -95,6 +105,7 @@ def main(argv=None):
     from . import sampler
     args = sampler.get_args(argv)
     sampler.validate_solver(args)
+    sampler.validate_image_seeds(args)
     if any(v is not None for v in (args.init_image, args.strength, args.known_image, args.known_mask)) or args.encode_images:
         raise ValueError("--init_image / --strength / --known_image / --known_mask / --encode_images belong to the single-GPU sampler (duodiff_amd.sampler)")
     rank, world, local_rank = init()
@@ -119,18 +130,21 @@ def main(argv=None):
 
     def one_rank(seed):
         y = None
+        # --image_seeds: `seed` is the base seed on every rank (below) and the shard is named by its first image
+        image_seeds = sampler.image_seed_list(args, args.batch_size, rank_first_image(args.first_image, rank, args.batch_size))
         if args.class_id is not None or args.class_label is not None:
             sampler.seed_everything(seed)
-            y = sampler.labels_from_args(args, args.batch_size, mp.num_classes)   # same range check as the single-GPU CLI
+            y = sampler.labels_from_args(args, args.batch_size, mp.num_classes, image_seeds)   # same range check as the single-GPU CLI
         s, _ = sampler.get_samples(model, args.batch_size, post, seed, mp.in_chans, mp.img_size, mp.img_size,
                                    use_ddim=args.use_ddim, ddim_steps=args.ddim_steps, ddim_eta=args.ddim_eta,
                                    timesteps_save=[], y=y, autoencoder=autoencoder, late_model=late, t_switch=args.t_switch,
                                    noise=args.noise, use_graph=not args.no_graph, return_device_tensor=True,
-                                   cfg_scale=args.cfg_scale, cfg_null_label=args.cfg_null_label, **sampler.solver_kwargs(args))
+                                   cfg_scale=args.cfg_scale, cfg_null_label=args.cfg_null_label, **sampler.solver_kwargs(args),
+                                   image_seeds=image_seeds)
         return s
 
     tic = time.time()
-    allimgs, _ = sample_sharded(one_rank, args.seed, dst=0)
+    allimgs, _ = sample_sharded(one_rank, args.seed, dst=0, rank_seeds=not args.image_seeds)
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     tac = time.time()

@@ -20,19 +20,30 @@ from .autoencoder import get_autoencoder
 from .config import load_config
 from .early_exit import EarlyExitUViT
 from .engine import Context
-from .sampler import dump_samples, load_checkpoint, seed_everything
+from .sampler import (add_image_seed_args, draw_labels_per_image, dump_samples, image_seed_list, load_checkpoint, seed_everything,
+                      validate_image_seeds)
 from .uvit import UViT
 
 
 def get_samples(model, batch_size: int, seed: int, num_channels: int, sample_height: int, sample_width: int,
                 threshold: float, depth: int, y=None, autoencoder=None, *, noise: str = "torch_cpu",
-                num_steps: int = 1000):
+                num_steps: int = 1000, image_seeds=None):
     """reference eesampler.py:40-89 -> (samples [B,H,W,C] numpy, error_prediction_by_timestep [1000,depth],
-    indices_by_timestep [1000,B]) (the last two as torch CPU tensors, like the reference)."""
+    indices_by_timestep [1000,B]) (the last two as torch CPU tensors, like the reference).
+    image_seeds (None: unchanged; batch_size ints, a device noise mode): image i -- its x_T and every z -- depends on image_seeds[i]
+    alone (sampler.get_samples); the logged batch means are of course the batch's."""
     device = model.device
     ctx = Context.get(device)
     seed_everything(seed)
-    x = torch.randn(batch_size, num_channels, sample_height, sample_width).to(device).contiguous()
+    if image_seeds is None:
+        x = torch.randn(batch_size, num_channels, sample_height, sample_width).to(device).contiguous()
+    else:
+        if noise not in ("device", "device_eager", "device_none"):
+            raise ValueError("image_seeds need noise='device': the torch CPU stream is sequential in the batch")
+        image_seeds = [int(v) for v in image_seeds]
+        if len(image_seeds) != batch_size or sample_height != sample_width:
+            raise ValueError(f"image_seeds: {len(image_seeds)} seeds for batch_size {batch_size} (square images only)")
+        x = ctx.noise_images(batch_size, num_channels, sample_height, image_seeds=image_seeds, counter=0)
     if y is not None:
         y = torch.as_tensor(y).to(device, torch.int64).contiguous()
     err_dev = torch.zeros(1000, depth, device=device)
@@ -41,9 +52,10 @@ def get_samples(model, batch_size: int, seed: int, num_channels: int, sample_hei
         # the whole loop on the device (dd_sample_early_exit): one hipGraph replay per step, z from the device Philox
         # generator ("device_none": no noise term, "device_eager": the same launches without the graph -- tests / timing)
         from .engine import sample_early_exit_loop
-        sample_early_exit_loop(ctx, model.engine_model(batch_size), x, threshold, t_start=999, t_end=1000 - int(num_steps), y=y,
-                               seed=seed, noise="none" if noise == "device_none" else "philox", err=err_dev, idx=ind_dev,
-                               use_graph=noise != "device_eager")
+        with ctx.image_seeds(image_seeds):
+            sample_early_exit_loop(ctx, model.engine_model(batch_size), x, threshold, t_start=999, t_end=1000 - int(num_steps), y=y,
+                                   seed=seed, noise="none" if noise == "device_none" else "philox", err=err_dev, idx=ind_dev,
+                                   use_graph=noise != "device_eager")
     else:
         for t in range(999, 999 - int(num_steps), -1):
             time_tensor = t * torch.ones(batch_size, device=device)
@@ -83,11 +95,13 @@ def get_args(argv=None):
     p.add_argument("--noise", choices=["torch_cpu", "device"], default="torch_cpu")
     p.add_argument("--autoencoder_checkpoint_path", type=str, default=None)
     p.add_argument("--no_png", action="store_true", help="write samples.npy instead of PNG files")
+    add_image_seed_args(p)
     return p.parse_args(argv)
 
 
 def main(argv=None):
     args = get_args(argv)
+    validate_image_seeds(args)
     out = Path(args.output_folder)
     out.mkdir(parents=True, exist_ok=True)
     config = load_config(args.config_path)
@@ -98,9 +112,13 @@ def main(argv=None):
     model.load_state_dict(load_checkpoint(args.checkpoint_path))
     model = model.eval().to("cuda")
     seed_everything(args.seed)
-    y = torch.randint(1, 1001, (args.batch_size,)) if args.class_id is not None else None   # :177-181
-    if y is not None and int(y.max()) >= base.num_classes:
-        raise IndexError("index out of range in self")
+    image_seeds = image_seed_list(args, args.batch_size)
+    if image_seeds is not None and args.class_id is not None:
+        y = draw_labels_per_image(image_seeds, base.num_classes)
+    else:
+        y = torch.randint(1, 1001, (args.batch_size,)) if args.class_id is not None else None   # :177-181
+        if y is not None and int(y.max()) >= base.num_classes:
+            raise IndexError("index out of range in self")
     autoencoder = None
     if "autoencoder" in config:
         path = args.autoencoder_checkpoint_path or config["autoencoder"]["autoencoder_checkpoint_path"]
@@ -108,7 +126,7 @@ def main(argv=None):
     tic = time.time()
     samples, err, ind = get_samples(model, args.batch_size, args.seed, base.in_chans, base.params.img_size,
                                     base.params.img_size, args.threshold, base.depth, y=y, autoencoder=autoencoder,
-                                    noise=args.noise)
+                                    noise=args.noise, image_seeds=image_seeds)
     tac = time.time()
     dump_statistics(tac - tic, err, ind, out)
     if args.no_png:

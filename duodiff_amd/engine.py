@@ -1,6 +1,7 @@
 """Thin object layer over the C ABI: one Context per (process, GPU), Models built from a
 reference-style state_dict.  torch tensors are containers for device memory and streams only.
 """
+import contextlib
 import ctypes as C
 from typing import NamedTuple
 
@@ -150,6 +151,65 @@ class Context:
         out = torch.empty_like(x) if out is None else out
         self.check(self.lib.dd_known_blend(self.handle, _ptr(x), _ptr(x0), _ptr(mask), _ptr(z2), float(ka), float(kb), _ptr(out),
                                            B, Cc, S, _stream_ptr(stream)))
+        return out
+
+    def _seeds_tensor(self, seeds, device=None):
+        """a sequence of ints in [0, 2^64) -> the uint64 seeds on the device (an int64 tensor of the same bits)"""
+        seeds = [int(s) for s in seeds]
+        if any(not 0 <= s < 1 << 64 for s in seeds):
+            raise ValueError("image seeds must lie in [0, 2^64)")
+        host = torch.from_numpy(np.array(seeds, np.uint64).view(np.int64))
+        return host.to(torch.device("cuda", self.device) if device is None else device)
+
+    def set_image_seeds(self, seeds):
+        """dd_set_image_seeds: while set, image i of every call that draws device noise (the sample_*_loop functions, Model.sample_step
+        with noise="philox") draws under seeds[i] (a sequence of ints, one per image of the call) with image-local pixel ids -- exactly
+        what the plain call with B = 1 and seed = seeds[i] draws; the call's own seed is unused.  None clears.  For one call or a few:
+        `with ctx.image_seeds(seeds): ...`."""
+        if seeds is None:
+            self.check(self.lib.dd_set_image_seeds(self.handle, None, 0))
+            self._image_seeds = None
+            return
+        t = self._seeds_tensor(seeds)
+        if t.numel() == 0:
+            raise ValueError("image seeds: an empty sequence (None clears)")
+        self.check(self.lib.dd_set_image_seeds(self.handle, _ptr(t), t.numel()))
+        self._image_seeds = t               # (the engine reads the array at every call while it is set)
+
+    @contextlib.contextmanager
+    def image_seeds(self, seeds, stream=None):
+        """Per-image seeds for the calls inside the block: set before it, cleared behind it whatever happens (seeds None: a plain block).
+        stream: the stream those calls are given, where it is not the current one."""
+        if seeds is None:
+            yield
+            return
+        self.set_image_seeds(seeds)
+        try:
+            yield
+        finally:
+            t = self._image_seeds
+            dev = torch.device("cuda", self.device)
+            for s in (stream, torch.cuda.current_stream(dev), getattr(self, "_side", None)):     # the streams a call may have read them on
+                if s is not None:
+                    t.record_stream(s)
+            self.set_image_seeds(None)
+
+    def noise_images(self, B, C, S, seed=0, image_seeds=None, counter=0, out=None, stream=None):
+        """dd_noise_images: x_T [B, C, S, S] drawn on the device under `seed` with batch-wide pixel ids, or (image_seeds: B ints) image i
+        under image_seeds[i] with image-local ids -- then image i is what the B = 1 call with seed = image_seeds[i] returns.  The draw has a
+        stream word of its own: independent of every step's noise under the same seeds."""
+        dev = torch.device("cuda", self.device)
+        out = torch.empty(int(B), int(C), int(S), int(S), device=dev, dtype=torch.float32) if out is None else out
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, C, S, S)
+        sd = None
+        if image_seeds is not None:
+            sd = self._seeds_tensor(image_seeds, out.device)
+            if sd.numel() != B:
+                raise ValueError(f"{sd.numel()} image seeds for {B} images")
+        self.check(self.lib.dd_noise_images(self.handle, int(seed) & (2 ** 64 - 1), _ptr(sd), int(counter), _ptr(out), int(B), int(C), int(S),
+                                            _stream_ptr(stream)))
+        if sd is not None:
+            sd.record_stream(stream if stream is not None else torch.cuda.current_stream(out.device))
         return out
 
     def set_num_cus(self, n):

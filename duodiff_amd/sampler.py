@@ -35,6 +35,7 @@ masked region of the image fixed while the rest is generated (RePaint's replacem
 DPM-Solver++ (engine option, not in the reference): ``--dpm_solver ode --dpm_solver_steps 20`` samples with the second-order multistep
 solver (``sde``: its SDE variant) in 20 model evaluations; the table-driven loop with one history register per image.
 """
+import contextlib
 import math
 import random
 import time
@@ -411,7 +412,7 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
                 late_model=None, t_switch=np.inf, *, noise: str = "torch_cpu", use_graph: bool = True,
                 num_steps: int = 1000, return_device_tensor: bool = False, cfg_scale=None, cfg_null_label: int = 1000,
                 solver=None, solver_steps: int = 20, solver_order: int = 2, autoguidance_scale=None, guide_model=None,
-                init_image=None, strength=None, known_image=None, known_mask=None, threshold=None, pag=None):
+                init_image=None, strength=None, known_image=None, known_mask=None, threshold=None, pag=None, image_seeds=None):
     """reference sampler.py:82-155.  Returns (samples[B,H,W,C] float32 numpy = (x+1)/2, intermediates).
 
     cfg_scale (None: the unguided loops, unchanged): classifier-free guidance of every step's model output,
@@ -431,6 +432,11 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
         in the reference's order -> identical random numbers to a CPU reference run.
     noise="device": x_T as above, z from the device Philox generator inside the graph-replayed loop.
     num_steps < 1000 runs only the first steps (t = 999 ...), for bounded benchmarks.
+    image_seeds (None: as above, unchanged; a sequence of batch_size ints; engine option, needs noise="device"): image i depends on
+        image_seeds[i] alone, not on its batch -- x_T is drawn on the device (Context.noise_images) and every z and z2 of the loops
+        under the image's own seed, so image i equals the batch_size = 1 run with image_seeds = [image_seeds[i]], and a batch equals
+        the concatenation of any split of it.  `seed` is then unused by the draws.  (The KL-VAE decode of a latent model is per image
+        by construction; nothing is claimed or tested about it here.)
 
     solver ("dpmsolver++" | "sde-dpmsolver++", engine option, not in the reference): DPM-Solver++ multistep sampling with
         solver_steps model evaluations on the grid multistep_grid(solver_steps) and order solver_order (multistep_coefficients);
@@ -471,6 +477,12 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
         for mdl, mask, what in ((model, pag_first, "layers_first"), (late_model, pag_late, "layers_late")):
             if mdl is not None and mask >> mdl.depth:
                 raise ValueError(f"pag {what} names a block at or above the model's depth {mdl.depth}")
+    if image_seeds is not None:
+        if noise != "device":
+            raise ValueError("image_seeds need noise='device': the torch CPU stream is sequential in the batch")
+        image_seeds = [int(v) for v in image_seeds]
+        if len(image_seeds) != batch_size:
+            raise ValueError(f"image_seeds holds {len(image_seeds)} seeds for batch_size {batch_size}")
     if (init_image is None) != (strength is None):
         raise ValueError("init_image and strength go together")
     if (known_image is None) != (known_mask is None):
@@ -487,7 +499,8 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
         raise ValueError("classifier-free guidance needs class labels")
     rows = 2 * batch_size if guidance is not None or pag is not None else batch_size    # backbone rows per step
     seed_everything(seed)                                                    # sampler.py:99
-    x = torch.randn(batch_size, num_channels, sample_height, sample_width).to(device).contiguous()  # :100
+    if image_seeds is None:
+        x = torch.randn(batch_size, num_channels, sample_height, sample_width).to(device).contiguous()  # :100
     if y is not None:
         y = torch.as_tensor(y).to(device, torch.int64).contiguous()
     image_shape = (num_channels, sample_height, sample_width)
@@ -502,6 +515,10 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
     first = model.engine_model(rows)
     late = late_model.engine_model(rows) if late_model is not None else None
     ctx = first.ctx
+    if image_seeds is not None:                                              # x_T on the device, image i under its own seed
+        if sample_height != sample_width:
+            raise ValueError("image_seeds: square images only")
+        x = ctx.noise_images(batch_size, num_channels, sample_height, image_seeds=image_seeds, counter=0)
     if t0 < 999:                                                             # x_t0 = sqrt(abar) x0 + sqrt(1 - abar) z; strength 1: z alone, as today
         ab0 = schedule_tables()["alphas_bar"].astype(np.float64)[t0]
         ctx.affine_step(x, init, None, _f32(np.sqrt(1.0 - ab0)), _f32(np.sqrt(ab0)), 0.0, out=x)
@@ -522,22 +539,24 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
                 kw["guidance"] = Perturbed(pag_scale, pag_late if sw == 0 else pag_first, pag_late)
             # with a known region: the same loop's _region form, the region's rows cut like the loop's
             known = () if region is None else (region._replace(ka=region.ka[k0:k1], kb=region.kb[k0:k1]),)
-            if plan.kind == "ddpm":                                          # dd_sample counts t_switch from t = 999, switch_after from the start
-                (sample_region_loop if known else sample_loop)(
-                    ctx, late if sw == 0 else first, None if sw == 0 else late, x, *known,
-                    t_switch=plan.switch_after + 999 - t0 if sw else 0, t_start=int(tab["t"][k0]), t_end=int(tab["t"][k1 - 1]), **kw)
-            else:
-                seg = {key: v[k0:k1] for key, v in tab.items()}
-                m0, m1 = late if sw == 0 else first, late if sw and sw < k1 - k0 else None
-                if plan.kind == "affine":
-                    (sample_affine_region_loop if known else sample_affine_loop)(
-                        ctx, m0, m1, x, *known, seg["t"], seg["a"], seg["b"], seg["c"], seg["noise"], switch_after=sw, counter_base=k0, **kw)
-                elif threshold is not None:
-                    sample_multistep_threshold_loop(ctx, m0, m1, x, h, seg, threshold, region=known[0] if known else None, switch_after=sw,
-                                                    counter_base=k0, **kw)
+            # per-image seeds: set on the context around the segment's call (its counter base keeps the cut invisible, as with one seed)
+            with ctx.image_seeds(image_seeds) if image_seeds is not None else contextlib.nullcontext():
+                if plan.kind == "ddpm":                                      # dd_sample counts t_switch from t = 999, switch_after from the start
+                    (sample_region_loop if known else sample_loop)(
+                        ctx, late if sw == 0 else first, None if sw == 0 else late, x, *known,
+                        t_switch=plan.switch_after + 999 - t0 if sw else 0, t_start=int(tab["t"][k0]), t_end=int(tab["t"][k1 - 1]), **kw)
                 else:
-                    (sample_multistep_region_loop if known else sample_multistep_loop)(
-                        ctx, m0, m1, x, *known, h, seg, switch_after=sw, counter_base=k0, **kw)
+                    seg = {key: v[k0:k1] for key, v in tab.items()}
+                    m0, m1 = late if sw == 0 else first, late if sw and sw < k1 - k0 else None
+                    if plan.kind == "affine":
+                        (sample_affine_region_loop if known else sample_affine_loop)(
+                            ctx, m0, m1, x, *known, seg["t"], seg["a"], seg["b"], seg["c"], seg["noise"], switch_after=sw, counter_base=k0, **kw)
+                    elif threshold is not None:
+                        sample_multistep_threshold_loop(ctx, m0, m1, x, h, seg, threshold, region=known[0] if known else None,
+                                                        switch_after=sw, counter_base=k0, **kw)
+                    else:
+                        (sample_multistep_region_loop if known else sample_multistep_loop)(
+                            ctx, m0, m1, x, *known, h, seg, switch_after=sw, counter_base=k0, **kw)
             if plan.save_after[k1 - 1]:
                 intermediate.append(x.clone())
     else:
@@ -819,12 +838,43 @@ def solver_kwargs(args):
                 solver_order=args.dpm_solver_order)
 
 
-def labels_from_args(args, batch_size: int, num_classes: int):
-    """y of a run: --class_label K for every image, --class_id's reference draw (quirk Q4), or None."""
+def image_seed_list(args, batch_size: int, first_image=None):
+    """--image_seeds: image i of the run (i counted from --first_image, or from first_image) gets seed --seed + i; None without the flag"""
+    if not getattr(args, "image_seeds", False):
+        return None
+    first = int(args.first_image if first_image is None else first_image)
+    if first < 0:
+        raise ValueError("--first_image must not be negative")
+    return [int(args.seed) + first + i for i in range(int(batch_size))]
+
+
+def validate_image_seeds(args):
+    """--image_seeds / --first_image against the noise mode, before any GPU work"""
+    if getattr(args, "first_image", 0) < 0:
+        raise ValueError("--first_image must not be negative")
+    if not getattr(args, "image_seeds", False):
+        if getattr(args, "first_image", 0):
+            raise ValueError("--first_image needs --image_seeds")
+        return
+    if args.noise != "device":
+        raise ValueError("--image_seeds needs --noise device: the torch CPU stream is sequential in the batch")
+
+
+def draw_labels_per_image(seeds, num_classes: int):
+    """--class_id's draw (quirk Q4: randint(1, 1001) whatever the id) per image: label i is a function of seeds[i] alone"""
+    y = torch.cat([torch.randint(1, 1001, (1,), generator=torch.Generator().manual_seed(int(s))) for s in seeds])
+    if int(y.max()) >= num_classes or int(y.min()) < 0:
+        raise IndexError("index out of range in self")
+    return y
+
+
+def labels_from_args(args, batch_size: int, num_classes: int, image_seeds=None):
+    """y of a run: --class_label K for every image, --class_id's reference draw (quirk Q4; with image_seeds: drawn per image from
+    the image's own seed), or None."""
     if args.class_label is not None:
         return torch.full((batch_size,), int(args.class_label), dtype=torch.int64)
     if args.class_id is not None:
-        return draw_labels(batch_size, num_classes)
+        return draw_labels(batch_size, num_classes) if image_seeds is None else draw_labels_per_image(image_seeds, num_classes)
     return None
 
 
@@ -849,6 +899,16 @@ def dump_statistics(elapsed_time, output_folder: Path, batch_size=None):
         f.write(f"Elapsed time: {elapsed_time} s\n")                          # reference sampler.py:187-189
         if batch_size:
             f.write(f"Images per second: {batch_size / elapsed_time}\n")
+
+
+def add_image_seed_args(p):
+    """the per-image seed flags the three command lines share (sampler, dist, eesampler)"""
+    p.add_argument("--image_seeds", action="store_true",
+                   help="(engine option) image i of the run gets its own seed, --seed + --first_image + i, and depends on nothing else: the "
+                        "same pictures at any --batch_size and on any number of GPUs.  Needs --noise device")
+    p.add_argument("--first_image", type=int, default=0, metavar="N",
+                   help="(engine option) with --image_seeds: the run's first image is image N (regenerate image i alone with "
+                        "--first_image i --batch_size 1)")
 
 
 def get_args(argv=None):
@@ -929,6 +989,7 @@ def get_args(argv=None):
                    help="(engine option) dynamic thresholding (Imagen): per image, s = the Q-quantile of |x0| (at least 1), x0 clipped to "
                         "[-s, s] and divided by s.  Exclusive with --clip_x0; pixel-space predict_noise / predict_original models, --noise device")
     p.add_argument("--threshold_max", type=float, default=None, metavar="S", help="(engine option) with --dynamic_threshold: s is at most S (>= 1)")
+    add_image_seed_args(p)
     return p.parse_args(argv)
 
 
@@ -953,6 +1014,7 @@ def main(argv=None):
             "predict_previous": predict_previous_postprocessing}[args.parametrization]
 
     validate_solver(args)
+    validate_image_seeds(args)
     config = load_config(args.config_path)
     config_late = load_config(args.config_path_late) if args.checkpoint_path_late else None
     validate_guidance(args, ModelParams.from_dict(config).num_classes,
@@ -974,7 +1036,8 @@ def main(argv=None):
         model_guide, _ = build_model(config_guide, args.guide_checkpoint_path, args.precision, rows)
 
     seed_everything(args.seed)
-    y = labels_from_args(args, args.batch_size, mp.num_classes)
+    image_seeds = image_seed_list(args, args.batch_size)
+    y = labels_from_args(args, args.batch_size, mp.num_classes, image_seeds)
     autoencoder = None
     if "autoencoder" in config:                                              # reference sampler.py:320-325
         ae_path = args.autoencoder_checkpoint_path or config["autoencoder"]["autoencoder_checkpoint_path"]
@@ -990,7 +1053,8 @@ def main(argv=None):
                                  y=y, autoencoder=autoencoder, late_model=model_late, t_switch=args.t_switch,
                                  timesteps_save=args.timesteps_save, noise=args.noise, use_graph=not args.no_graph,
                                  cfg_scale=args.cfg_scale, cfg_null_label=args.cfg_null_label, **solver_kwargs(args),
-                                 autoguidance_scale=args.autoguidance_scale, guide_model=model_guide, threshold=threshold, pag=pag, **region_kwargs)
+                                 autoguidance_scale=args.autoguidance_scale, guide_model=model_guide, threshold=threshold, pag=pag, image_seeds=image_seeds,
+                                 **region_kwargs)
     tac = time.time()
     dump_statistics(tac - tic, out, args.batch_size)
     if args.no_png:

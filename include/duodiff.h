@@ -428,6 +428,28 @@ typedef struct dd_ee_sample_args {
 } dd_ee_sample_args;
 int dd_sample_early_exit(dd_ctx* ctx, const dd_ee_sample_args* args, void* stream);
 
+/* ---- per-image seeds (version 6 additions: new symbols, no struct changes): image i = f(seed_i), whatever its batch ---- */
+/* Plain (the default, every bit as before): the device noise of a call is Philox with key = the call's seed and a pixel id that runs
+ * over the WHOLE batch, id = (i S S + y S + x) for pixel (y, x) of image i -- an image's noise depends on where it sits in its batch.
+ * Seeded: key = seeds[i], id = y S + x.  The counter word (the DDPM timestep, or counter_base + k of a table-driven loop) and the
+ * stream word (z, the known region's z2, x_T) are the same in both.  So image i of a seeded call with seed s draws exactly what the
+ * plain call with B = 1 and seed = s draws: any image of a run can be regenerated alone, and a run does not depend on how it was cut
+ * into batches or shared among GPUs.
+ *
+ * dd_set_image_seeds: seeds_dev [n] uint64 on the device stay with the context until cleared (NULL, 0) -- like dd_set_num_cus.  While
+ * set, every entry that draws device noise (every dd_sample* loop, dd_sample_early_exit, dd_sample_step with DD_NOISE_PHILOX) takes
+ * image i's draws from seeds_dev[i]; the call's own seed is unused; a call with B != n is DD_ERR_INVALID before anything is enqueued.
+ * DD_NOISE_BUFFER and DD_NOISE_NONE calls are unaffected.  Under classifier-free and perturbed-attention guidance the seed is the
+ * image's, not the backbone row's.  The array is read at every such call (copied on the call's stream into a buffer of the context,
+ * which the captured steps read: calls with other seeds replay the same graphs), so it must stay valid while set.
+ * NULL with n != 0, a pointer with n == 0 or n < 0: DD_ERR_INVALID. */
+int dd_set_image_seeds(dd_ctx* ctx, const uint64_t* seeds_dev, int n);
+/* x_T on the device: out_dev [B, C, S, S] (C in 1..4, S in 1..32768), out[b, c, y, x] = component c of the pixel's four normals under
+ * (key, id) as above -- seeds_dev [B] given: seeded, else plain under `seed` -- with counter word `counter` (>= 0) and a stream word of
+ * its own: independent of every step's z and z2 under the same key.  Independent of dd_set_image_seeds.  A bad argument is
+ * DD_ERR_INVALID with nothing launched; B == 0 does nothing. */
+int dd_noise_images(dd_ctx* ctx, uint64_t seed, const uint64_t* seeds_dev, int counter, float* out_dev, int B, int C, int S, void* stream);
+
 /* ---- KL-VAE decode: autoencoder.decode(x) at sampler.py:141-143 ---------------- */
 /* Replaces FrozenAutoencoderKL.decode (models/utils/autoencoder.py:486-490, Decoder :320-449) for the fixed ddconfig of
  * get_autoencoder (:503-516).  Parameters are set by the reference state_dict keys ("decoder.*", "post_quant_conv.*";

@@ -252,6 +252,10 @@ typedef struct dd_dev_final_args {
     unsigned long long seed_out;
 } dd_dev_final_args;
 int dd_dev_final(dd_ctx* ctx, dd_dev_final_args* args, void* stream);
+/* dd_dev_final with per-image seeds (include/duodiff.h dd_set_image_seeds; FinalArgs::seeds): seeds_host [n] uint64 are the seeds of the
+ * WHOLE batch, n >= b0 + B, so image b of the launch draws under seeds_host[b0 + b] with image-local pixel ids; args->seed is unused by
+ * the draw.  NULL, n < 1, n < b0 + B or n > 2^22: DD_ERR_INVALID, nothing launched. */
+int dd_dev_final_seeded(dd_ctx* ctx, dd_dev_final_args* args, const uint64_t* seeds_host, int n, void* stream);
 
 /* Kernel-variant switches for same-process A/B runs (tools/mlp_check.py, tools/all_configs.py).  They act on models
  * FINALIZED after the call (the kernel paths a model takes, the DD_DEV_NO_FRAG_* hand-offs among them) or on launches made after it; the product never sets them and the library

@@ -69,12 +69,8 @@ def gather_images(local: torch.Tensor, world: int, dst: Optional[int] = None):
         dist.all_gather(out, local)
         return torch.cat(out, dim=0)
     rank = dist.get_rank()
-    if dist.get_backend() == "nccl":
-        out = [torch.empty_like(local) for _ in range(world)] if rank == dst else None
-        dist.gather(local, out, dst=dst)
-    else:
-        out = [torch.empty_like(local) for _ in range(world)] if rank == dst else None
-        dist.gather(local, gather_list=out, dst=dst)
+    out = [torch.empty_like(local) for _ in range(world)] if rank == dst else None
+    dist.gather(local, gather_list=out, dst=dst)
     return torch.cat(out, dim=0) if rank == dst else None
 
 
@@ -98,50 +94,28 @@ def sample_sharded(sample_fn: Callable[[int], torch.Tensor], base_seed: int, dst
 
 
 def main(argv=None):
-    """Sharded version of the sampler CLI: same flags; --batch_size is per GPU; rank 0 writes the output."""
+    """Sharded version of the sampler CLI: its flags and its run setup (sampler.setup_run); --batch_size is per GPU; rank 0 writes the
+    output.  Not taken: the image-to-image and inpainting flags, and --timesteps_save (intermediates are not gathered)."""
     import time
     from pathlib import Path
 
     from . import sampler
     args = sampler.get_args(argv)
-    sampler.validate_solver(args)
-    sampler.validate_image_seeds(args)
     if any(v is not None for v in (args.init_image, args.strength, args.known_image, args.known_mask)) or args.encode_images:
         raise ValueError("--init_image / --strength / --known_image / --known_mask / --encode_images belong to the single-GPU sampler (duodiff_amd.sampler)")
+    if args.timesteps_save:
+        raise ValueError("--timesteps_save belongs to the single-GPU sampler (duodiff_amd.sampler): intermediates are not gathered")
     rank, world, local_rank = init()
     if torch.cuda.is_available():
         torch.cuda.set_device(local_rank % torch.cuda.device_count())   # (ranks may share a GPU when rehearsed on one)
-    config = sampler.load_config(args.config_path)
-    config_late = sampler.load_config(args.config_path_late) if args.checkpoint_path_late else None
-    sampler.validate_guidance(args, sampler.ModelParams.from_dict(config).num_classes,
-                              sampler.ModelParams.from_dict(config_late).num_classes if config_late is not None else None)
-    rows = 2 * args.batch_size if args.cfg_scale is not None else args.batch_size    # guided: 2 B backbone rows
-    model, mp = sampler.build_model(config, args.checkpoint_path, args.precision, rows)
-    late = None
-    if config_late is not None:
-        late, _ = sampler.build_model(config_late, args.checkpoint_path_late, args.precision, rows)
-    post = {"predict_noise": sampler.predict_noise_postprocessing, "predict_original": sampler.predict_original_postprocessing,
-            "predict_previous": sampler.predict_previous_postprocessing}[args.parametrization]
-    autoencoder = None
-    if "autoencoder" in config:
-        from .autoencoder import get_autoencoder
-        path = args.autoencoder_checkpoint_path or config["autoencoder"]["autoencoder_checkpoint_path"]
-        autoencoder = get_autoencoder(path, precision=args.precision).to(model.device)
+    setup = sampler.setup_run(args)
 
     def one_rank(seed):
-        y = None
         # --image_seeds: `seed` is the base seed on every rank (below) and the shard is named by its first image
         image_seeds = sampler.image_seed_list(args, args.batch_size, rank_first_image(args.first_image, rank, args.batch_size))
-        if args.class_id is not None or args.class_label is not None:
-            sampler.seed_everything(seed)
-            y = sampler.labels_from_args(args, args.batch_size, mp.num_classes, image_seeds)   # same range check as the single-GPU CLI
-        s, _ = sampler.get_samples(model, args.batch_size, post, seed, mp.in_chans, mp.img_size, mp.img_size,
-                                   use_ddim=args.use_ddim, ddim_steps=args.ddim_steps, ddim_eta=args.ddim_eta,
-                                   timesteps_save=[], y=y, autoencoder=autoencoder, late_model=late, t_switch=args.t_switch,
-                                   noise=args.noise, use_graph=not args.no_graph, return_device_tensor=True,
-                                   cfg_scale=args.cfg_scale, cfg_null_label=args.cfg_null_label, **sampler.solver_kwargs(args),
-                                   image_seeds=image_seeds)
-        return s
+        sampler.seed_everything(seed)               # (get_samples seeds again: a run without labels is what it was)
+        y = sampler.labels_from_args(args, args.batch_size, setup.mp.num_classes, image_seeds)   # same draw and range check as the single-GPU CLI
+        return sampler.get_samples(**setup.kwargs, seed=seed, image_seeds=image_seeds, y=y, timesteps_save=[], return_device_tensor=True)[0]
 
     tic = time.time()
     allimgs, _ = sample_sharded(one_rank, args.seed, dst=0, rank_seeds=not args.image_seeds)

@@ -16,12 +16,11 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from .autoencoder import get_autoencoder
 from .config import load_config
 from .early_exit import EarlyExitUViT
 from .engine import Context
-from .sampler import (add_image_seed_args, draw_labels_per_image, dump_samples, image_seed_list, load_checkpoint, seed_everything,
-                      validate_image_seeds)
+from .sampler import (add_image_seed_args, dump_samples, image_seed_list, labels_from_args, load_autoencoder, load_checkpoint,
+                      seed_everything, validate_image_seeds)
 from .uvit import UViT
 
 
@@ -113,16 +112,8 @@ def main(argv=None):
     model = model.eval().to("cuda")
     seed_everything(args.seed)
     image_seeds = image_seed_list(args, args.batch_size)
-    if image_seeds is not None and args.class_id is not None:
-        y = draw_labels_per_image(image_seeds, base.num_classes)
-    else:
-        y = torch.randint(1, 1001, (args.batch_size,)) if args.class_id is not None else None   # :177-181
-        if y is not None and int(y.max()) >= base.num_classes:
-            raise IndexError("index out of range in self")
-    autoencoder = None
-    if "autoencoder" in config:
-        path = args.autoencoder_checkpoint_path or config["autoencoder"]["autoencoder_checkpoint_path"]
-        autoencoder = get_autoencoder(path, precision=args.precision).to(model.device)
+    y = labels_from_args(args, args.batch_size, base.num_classes, image_seeds)              # :177-181: the randint right behind the seeding
+    autoencoder = load_autoencoder(args, config, model.device)
     tic = time.time()
     samples, err, ind = get_samples(model, args.batch_size, args.seed, base.in_chans, base.params.img_size,
                                     base.params.img_size, args.threshold, base.depth, y=y, autoencoder=autoencoder,

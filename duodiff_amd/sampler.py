@@ -40,8 +40,9 @@ import math
 import random
 import time
 from argparse import ArgumentParser
+from collections import namedtuple
 from pathlib import Path
-from typing import List, NamedTuple, Optional
+from typing import List
 
 import numpy as np
 import torch
@@ -51,6 +52,8 @@ from .autoencoder import get_autoencoder
 from .engine import (Autoguidance, Context, KnownRegion, Perturbed, X0Threshold, layer_mask, sample_affine_loop, sample_affine_region_loop, sample_loop,
                      sample_multistep_loop, sample_multistep_region_loop, sample_multistep_threshold_loop, sample_region_loop,
                      schedule_tables, threshold_struct)
+from .step_plan import (MULTISTEP_KINDS, StepPlan, _affine_rows, _data_prediction, _f32, _segments, affine_coefficients, known_rows,  # noqa: F401
+                        multistep_coefficients, multistep_grid, multistep_rows, start_timestep, step_plan, unfolded_coefficients, unfolded_rows)
 from .uvit import UViT
 
 
@@ -97,178 +100,6 @@ def predict_noise_postprocessing(model_output, x, t, z=None):
     return ctx.ddpm_step(x.contiguous(), model_output, z if t > 0 else None, t)
 
 
-def _f32(v):
-    return np.float32(v)
-
-
-def affine_coefficients(kind, t, s=None, eta=0.0):
-    """Scalar (a, b, c) with x' = a*x + b*model_output + c*z for the reference's other updates, in fp32
-    from the engine's (bit-exact) tables:
-      "predict_original"  sampler.py:59-72      "predict_previous"  sampler.py:75-79
-      "ddim" (t -> s)     sampler.py:112-120 (noise scaled by sigma^2 = betas_tilde[t]*eta, as the reference does)
-    """
-    tb = schedule_tables()
-    one = _f32(1)
-    if kind == "predict_previous":
-        return _f32(0), one, np.sqrt(tb["betas_tilde"][t])
-    if kind == "predict_original":
-        a_t, ab_t, ab_p, b_t = tb["alphas"][t], tb["alphas_bar"][t], tb["alphas_bar_previous"][t], tb["betas"][t]
-        a = _f32(np.sqrt(a_t) * (one - ab_p)) / (one - ab_t)
-        b = _f32(np.sqrt(ab_p) * b_t) / (one - ab_t)
-        return _f32(a), _f32(b), np.sqrt(tb["betas_tilde"][t])
-    if kind == "ddim":
-        ab = tb["alphas_bar"]
-        sig2 = _f32(tb["betas_tilde"][t] * _f32(eta))
-        a = np.sqrt(_f32(ab[s] / ab[t]))
-        b = _f32(np.sqrt(_f32(one - ab[s] - sig2)) - _f32(a * np.sqrt(_f32(one - ab[t]))))
-        return _f32(a), b, sig2
-    raise ValueError(kind)
-
-
-MULTISTEP_KINDS = ("dpmsolver++", "sde-dpmsolver++")
-
-
-def multistep_rows(kind, alphas_bar, order=2, parametrization="predict_noise", lower_order_final=True, unfolded=False):
-    """float64 DPM-Solver++ (Lu et al., 2022) rows of the multistep update, for the steps alphas_bar[k] -> alphas_bar[k + 1]
-    (len(alphas_bar) = N + 1 values of abar along the grid; the model sees the first N):
-
-        x' = a x + b m [+ d h  if hist]  [+ c z  if noise]        h' = p x + q m
-
-    m: the model output at step k, h: the previous step's data prediction x0 = p x + q m.  kind: "dpmsolver++" (ODE, no noise)
-    or "sde-dpmsolver++" (the midpoint 2M SDE: every row here has noise = 1; multistep_coefficients drops the z of a step landing on
-    t = 0).  order 2: step 0 is first order (no history yet), and with lower_order_final the last step too (on the product grid it
-    lands on t = 0, where lambda jumps: a second-order step there extrapolates with r ~ 0.2 and overshoots).
-    unfolded: the rows of the thresholded loop, x' = a x + b xh + ..., xh = the thresholded data prediction p x + q m: a = A,
-    b = phi w0 (the default folds x0 into them: a = A + phi w0 p, b = phi w0 q).
-    Returns a dict of float64 arrays a, b, c, d, p, q and int32 arrays hist, noise."""
-    if kind not in MULTISTEP_KINDS:
-        raise ValueError(f"solver must be one of {MULTISTEP_KINDS}, not {kind!r}")
-    if order not in (1, 2):
-        raise ValueError("solver order must be 1 or 2")
-    if parametrization == "predict_previous":
-        raise ValueError("DPM-Solver++ needs a model that predicts the noise or the data (predict_noise / predict_original), "
-                         "not predict_previous")
-    if parametrization not in ("predict_noise", "predict_original"):
-        raise ValueError(parametrization)
-    ab = np.asarray(alphas_bar, np.float64)
-    n = len(ab) - 1
-    if n < 1:
-        raise ValueError("need at least one step")
-    alpha, sigma = np.sqrt(ab), np.sqrt(1.0 - ab)
-    lam = np.log(alpha) - np.log(sigma)
-    h = lam[1:] - lam[:-1]
-    rows = {k: np.zeros(n) for k in "abcdpq"}
-    rows["hist"], rows["noise"] = np.zeros(n, np.int32), np.zeros(n, np.int32)
-    for k in range(n):
-        if parametrization == "predict_noise":
-            p, q = 1.0 / alpha[k], -sigma[k] / alpha[k]
-        else:
-            p, q = 0.0, 1.0
-        second = order == 2 and k > 0 and not (lower_order_final and k == n - 1)
-        if second:
-            r = h[k - 1] / h[k]
-            w0, w1 = 1.0 + 1.0 / (2.0 * r), -1.0 / (2.0 * r)
-        else:
-            w0, w1 = 1.0, 0.0
-        if kind == "dpmsolver++":
-            A, phi, c = sigma[k + 1] / sigma[k], alpha[k + 1] * -np.expm1(-h[k]), 0.0
-        else:
-            A, phi = sigma[k + 1] / sigma[k] * np.exp(-h[k]), alpha[k + 1] * -np.expm1(-2.0 * h[k])
-            c = sigma[k + 1] * np.sqrt(-np.expm1(-2.0 * h[k]))
-        rows["a"][k], rows["b"][k], rows["c"][k], rows["d"][k] = A + phi * w0 * p, phi * w0 * q, c, phi * w1
-        if unfolded:
-            rows["a"][k], rows["b"][k] = A, phi * w0
-        rows["p"][k], rows["q"][k] = p, q
-        rows["hist"][k] = int(w1 != 0.0)
-        rows["noise"][k] = int(kind == "sde-dpmsolver++")
-    return rows
-
-
-def multistep_grid(n_steps, t0=999):
-    """The integer timestep grid of an N-evaluation DPM-Solver++ run: N + 1 points from t0 (999; lower: an image-to-image start) down
-    to 0; the model sees the first N."""
-    n = int(n_steps)
-    if not 1 <= n <= 999:
-        raise ValueError(f"DPM-Solver++ steps must be in [1, 999], not {n}")
-    if n > t0:
-        raise ValueError(f"{n} DPM-Solver++ steps do not fit a start at t = {t0}: lower the steps or raise the strength")
-    return np.linspace(t0, 0, n + 1).round().astype(int)
-
-
-def _data_prediction(parametrization, ab_t):
-    """(p, q) of x0 = p x + q m in float64 at alphas_bar ab_t: the model predicts the noise or the data"""
-    if parametrization == "predict_previous":
-        raise ValueError("x0 thresholding needs a model that predicts the noise or the data (predict_noise / predict_original), "
-                         "not predict_previous: there is no x0")
-    if parametrization == "predict_original":
-        return 0.0, 1.0
-    if parametrization != "predict_noise":
-        raise ValueError(parametrization)
-    return 1.0 / np.sqrt(ab_t), -np.sqrt(1.0 - ab_t) / np.sqrt(ab_t)
-
-
-def unfolded_rows(kind, ts, eta=0.0, parametrization="predict_noise"):
-    """The reference's own samplers as float64 UNFOLDED rows of the thresholded loop (x' = a x + b xh + c z, xh the thresholded
-    x0 = p x + q m, no history), from the engine's bit-exact tables:
-      "ddim"  over the descending grid ts (N + 1 timesteps), step t -> s: a = dir / sigma_t, b = alpha_s - a alpha_t with
-              dir = sqrt(1 - abar_s - sig2), sig2 = betas_tilde[t] eta and c = sig2 (the reference scales its noise by sigma^2,
-              sampler.py:112-120, and reads the model output as the noise whatever the parametrization: so does (p, q) here)
-      "ddpm"  the ancestral steps at the timesteps ts (t -> t - 1): the posterior mean's coefficients on x and x0 (sampler.py:59-72)
-              and c = sqrt(betas_tilde[t]); (p, q) from the parametrization
-    Returns a dict of float64 arrays a, b, c, d, p, q and int32 arrays hist (0), noise (the step does not land on the final image)."""
-    tb = {k: v.astype(np.float64) for k, v in schedule_tables().items()}
-    ab = tb["alphas_bar"]
-    ts = np.asarray(ts, np.int64)
-    if kind == "ddim":
-        t, s_ = ts[:-1], ts[1:]
-        sig2 = tb["betas_tilde"][t] * float(eta)
-        with np.errstate(invalid="ignore"):     # (a large eta on the step onto t = 0: the reference's direction term is NaN, sampler.py:116)
-            a = np.sqrt(1.0 - ab[s_] - sig2) / np.sqrt(1.0 - ab[t])
-        b = np.sqrt(ab[s_]) - a * np.sqrt(ab[t])
-        c, noise = sig2, s_ > 0
-        pq = [_data_prediction("predict_noise", v) for v in ab[t]]
-        if parametrization == "predict_previous":
-            _data_prediction(parametrization, 0.5)
-    elif kind == "ddpm":
-        t = ts
-        a = np.sqrt(tb["alphas"][t]) * (1.0 - tb["alphas_bar_previous"][t]) / (1.0 - ab[t])
-        b = np.sqrt(tb["alphas_bar_previous"][t]) * tb["betas"][t] / (1.0 - ab[t])
-        c, noise = np.sqrt(tb["betas_tilde"][t]), t > 0
-        pq = [_data_prediction(parametrization, v) for v in ab[t]]
-    else:
-        raise ValueError(kind)
-    n = len(t)
-    return {"a": a, "b": b, "c": np.asarray(c, np.float64), "d": np.zeros(n), "p": np.array([v[0] for v in pq]).reshape(n),
-            "q": np.array([v[1] for v in pq]).reshape(n), "hist": np.zeros(n, np.int32), "noise": noise.astype(np.int32)}
-
-
-def unfolded_coefficients(kind, ts, eta=0.0, parametrization="predict_noise"):
-    """unfolded_rows as the fp32 rows a loop takes (each coefficient rounded once), with t: the model timesteps"""
-    ts = np.asarray(ts, np.int64)
-    r = unfolded_rows(kind, ts, eta, parametrization)
-    out = {k: r[k].astype(np.float32) for k in "abcdpq"}
-    out["t"] = (ts[:-1] if kind == "ddim" else ts).astype(np.float32)
-    out["hist"], out["noise"] = r["hist"], r["noise"]
-    return out
-
-
-def multistep_coefficients(kind, ts, order=2, parametrization="predict_noise", unfolded=False):
-    """The fp32 rows of a DPM-Solver++ run over the integer grid ts (descending, N + 1 timesteps, the last one usually 0), from the
-    engine's bit-exact schedule tables: multistep_rows in float64, each coefficient rounded once.  Returns a dict of per-step arrays
-    t (float32 model timesteps t_0 .. t_{N-1}), a, b, c, d, p, q (float32), hist, noise (int32).  The SDE draws z on every step but
-    one landing on t = 0 (the reference's DDPM / DDIM convention)."""
-    ts = np.asarray(ts, np.int64)
-    if ts.ndim != 1 or len(ts) < 2 or (ts < 0).any() or (ts > 999).any() or (np.diff(ts) >= 0).any():
-        raise ValueError("ts must be a strictly decreasing grid of timesteps in [0, 999] with at least two points")
-    ab = schedule_tables()["alphas_bar"].astype(np.float64)[ts]
-    r = multistep_rows(kind, ab, order, parametrization, unfolded=unfolded)
-    out = {k: r[k].astype(np.float32) for k in "abcdpq"}
-    out["t"] = ts[:-1].astype(np.float32)
-    out["hist"] = r["hist"]
-    out["noise"] = (r["noise"] * (ts[1:] > 0)).astype(np.int32)
-    return out
-
-
 def _affine_post(kind, model_output, x, t, z=None):
     ctx = Context.get(x.device)
     a, b, c = affine_coefficients(kind, t)
@@ -287,100 +118,8 @@ def predict_previous_postprocessing(model_output, x, t, z=None):
     return _affine_post("predict_previous", model_output, x, t, z)
 
 
-class StepPlan(NamedTuple):
-    """What get_samples runs, step by step.  kind: "ddpm" (dd_sample / ddpm_step: the update follows from t), "affine" (rows a, b, c)
-    or "multistep" (rows a, b, c, d, p, q, hist: multistep_coefficients).  rows: per-step arrays, always with t (the model timestep,
-    float32) and noise (int32: the step draws z).  save_after[k]: x is saved after step k.  switch_after: the first step the late model
-    runs, or None; it may lie past the last step (a DDPM switch beyond num_steps), where it only hands the late model to dd_sample.
-    lands[k]: the timestep whose noise level x has after step k, -1 for the final image (known_rows)."""
-    kind: str
-    rows: dict
-    save_after: list
-    switch_after: Optional[int]
-    lands: tuple = ()
-
-
 _PARAMETRIZATIONS = {predict_noise_postprocessing: "predict_noise", predict_original_postprocessing: "predict_original",
                      predict_previous_postprocessing: "predict_previous"}
-
-
-def start_timestep(strength=None):
-    """The timestep a loop starts at: 999, or round(999 * strength) for an image-to-image start of strength in (0, 1]."""
-    if strength is None:
-        return 999
-    if not (isinstance(strength, (int, float, np.number)) and 0 < float(strength) <= 1):
-        raise ValueError(f"strength must be in (0, 1], not {strength!r}")
-    return int(round(999 * float(strength)))
-
-
-def step_plan(parametrization, timesteps_save=(), has_late=False, t_switch=np.inf, num_steps=1000, use_ddim=False, ddim_steps=50,
-              ddim_eta=0.0, solver=None, solver_steps=20, solver_order=2, strength=None, threshold=None):
-    """The StepPlan of get_samples' arguments (parametrization: "predict_noise" | "predict_original" | "predict_previous", or None
-    for a postprocessing function of elsewhere; has_late: a late model is given).  Host arithmetic only, no torch.
-    strength (None or 1: the start at t = 999): the loops start at t0 = start_timestep(strength) -- DDPM at t0, the DDIM and solver grids
-    built from t0 down with the same spacing rule and step count; the late model's rule is unchanged (by timestep).
-    threshold (anything but None): the plan of the thresholded loop -- kind "multistep" on UNFOLDED rows for all three samplers
-    (multistep_coefficients(..., unfolded=True), unfolded_coefficients); predict_previous has no x0 and is rejected."""
-    t0 = start_timestep(strength)
-    if threshold is not None:
-        _data_prediction(parametrization if parametrization is not None else "predict_noise", 0.5)
-    # the DDPM loop switches AFTER the step at t == 1000 - t_switch (sampler.py:135-136): a t_switch outside [1, 1000] (0, negative,
-    # > 1000, inf) never matches a t in 999..0, i.e. the first model runs every step
-    in_range = has_late and np.isfinite(t_switch) and 1 <= int(t_switch) <= 1000
-    if solver is not None:
-        if use_ddim:
-            raise ValueError("DPM-Solver++ and DDIM are exclusive")
-        grid = multistep_grid(solver_steps, t0)                               # range check first
-        if parametrization is None:
-            raise ValueError("postprocessing must be one of this module's predict_*_postprocessing functions")
-        kind, rows = "multistep", multistep_coefficients(solver, grid, solver_order, parametrization, unfolded=threshold is not None)
-        switch_after = next((k for k, t in enumerate(rows["t"]) if t < 1000 - int(t_switch)), None) if in_range else None
-        lands = [int(s) if s > 0 else -1 for s in grid[1:]]
-    elif use_ddim:
-        # reference sampler.py:103-126; z is drawn (:119) whenever s > 0, also at eta = 0
-        ts = np.linspace(0, t0, ddim_steps).astype(int)[::-1]
-        if (np.diff(ts) >= 0).any():
-            raise ValueError(f"{ddim_steps} DDIM steps do not fit a start at t = {t0}: lower the steps or raise the strength")
-        pairs = [(int(t), int(s)) for t, s in zip(ts[:-1], ts[1:])]
-        if threshold is not None:
-            if parametrization is None:
-                raise ValueError("postprocessing must be one of this module's predict_*_postprocessing functions")
-            kind, rows = "multistep", unfolded_coefficients("ddim", ts, ddim_eta, parametrization)
-        else:
-            kind, rows = "affine", _affine_rows([t for t, _ in pairs], [affine_coefficients("ddim", t, s, ddim_eta) for t, s in pairs],
-                                                [s > 0 for _, s in pairs])
-        # :122-123: the late model from the step after the first t < 1000 - t_switch (raw t_switch: <= 0 switches after step 0)
-        switch_after = next((k + 1 for k, (t, _) in enumerate(pairs) if t < 1000 - t_switch), None) if has_late else None
-        lands = [s if s > 0 else -1 for _, s in pairs]
-    else:
-        # sampler.py:129-139: t = 999 .. 1000 - num_steps; predict_original / predict_previous (:59-79) as affine rows
-        ts = list(range(t0, max(t0 - int(num_steps), -1), -1))
-        if threshold is not None and parametrization in ("predict_noise", "predict_original"):
-            kind, rows = "multistep", unfolded_coefficients("ddpm", ts, 0.0, parametrization)
-        elif parametrization == "predict_noise":
-            kind, rows = "ddpm", {"t": np.array(ts, np.float32), "noise": np.array([t > 0 for t in ts], np.int32)}
-        elif parametrization in ("predict_original", "predict_previous"):
-            kind, rows = "affine", _affine_rows(ts, [affine_coefficients(parametrization, t) for t in ts], [t > 0 for t in ts])
-        else:
-            raise ValueError("postprocessing must be one of this module's predict_*_postprocessing functions")
-        switch_after = max(int(t_switch) - (999 - t0), 0) if in_range else None   # the step after t == 1000 - t_switch
-        lands = [t - 1 for t in ts]
-    saves = set(int(v) for v in timesteps_save)
-    return StepPlan(kind, rows, [(1000 - int(t)) in saves for t in rows["t"]], switch_after, tuple(lands))
-
-
-def known_rows(plan):
-    """The known-region rows (ka, kb) of a plan, float32, one per step: a step that lands on timestep s puts its known pixels at
-    ka x0 + kb z2 with ka = sqrt(alphas_bar[s]), kb = sqrt(1 - alphas_bar[s]) from the engine's bit-exact tables, each rounded once;
-    a step that lands on the final image (the DDPM step at t = 0, the last DDIM pair, the solver grid's last point) has (1, 0), so the
-    known pixels of the result are x0 itself.  Host arithmetic only."""
-    ab = schedule_tables()["alphas_bar"].astype(np.float64)
-    s = np.asarray(plan.lands, np.int64)
-    final = s < 0
-    abs_ = ab[np.where(final, 0, s)]
-    ka = np.where(final, 1.0, np.sqrt(abs_)).astype(np.float32)
-    kb = np.where(final, 0.0, np.sqrt(1.0 - abs_)).astype(np.float32)
-    return ka, kb
 
 
 def _batch_tensor(v, name, batch_size, shape, device):
@@ -391,19 +130,148 @@ def _batch_tensor(v, name, batch_size, shape, device):
     return t.expand(batch_size, *shape).contiguous().to(device)
 
 
-def _affine_rows(ts, coefficients, noise):
-    a, b, c = zip(*coefficients) if coefficients else ((), (), ())
-    return {"t": np.array(ts, np.float32), "a": np.array(a, np.float32), "b": np.array(b, np.float32), "c": np.array(c, np.float32),
-            "noise": np.array(noise, np.int32)}
+def backbone_rows(batch_size, cfg_scale=None, pag=None):
+    """Backbone rows per step (a model's max_batch): 2 B with the unconditional / perturbed half of CFG or PAG, else B (autoguidance too)"""
+    return 2 * batch_size if cfg_scale is not None or pag is not None else batch_size
 
 
-def _segments(save_after):
-    """(k0, k1) of the device loop cut after every save step"""
-    k0 = 0
-    for k, save in enumerate(save_after):
-        if save or k == len(save_after) - 1:
-            yield k0, k + 1
-            k0 = k + 1
+def _resolve_options(model, late_model, batch_size, image_shape, plan_args, noise, y, autoencoder, cfg_scale, cfg_null_label,
+                     autoguidance_scale, guide_model, pag, image_seeds, init_image, strength, known_image, known_mask, threshold):
+    """get_samples' one options check, before any engine call: every ValueError it raises, in a fixed order.  Returns the StepPlan of
+    plan_args; the run's ONE guidance, which the device loops take and the host step picks its forward call by -- None, (scale, null_label),
+    Autoguidance(the guide's UViT, scale) or Perturbed(scale, mask_first, mask_late); the seeds as ints; the init image and KnownRegion."""
+    if noise not in ("torch_cpu", "device"):
+        raise ValueError("noise must be 'torch_cpu' or 'device'")
+    guidance = None
+    if autoguidance_scale is not None:
+        if cfg_scale is not None:
+            raise ValueError("classifier-free guidance and autoguidance are exclusive")
+        if not math.isfinite(float(autoguidance_scale)):
+            raise ValueError("autoguidance_scale must be finite")
+        if guide_model is None and late_model is None:
+            raise ValueError("autoguidance needs a guide model: pass guide_model, or a late_model (the first model then guides it)")
+        guidance = Autoguidance(model if guide_model is None else guide_model, float(autoguidance_scale))
+    elif guide_model is not None:
+        raise ValueError("guide_model without autoguidance_scale")
+    if pag is not None:
+        if cfg_scale is not None or autoguidance_scale is not None or known_image is not None or init_image is not None or threshold is not None:
+            raise ValueError("perturbed-attention guidance does not combine with classifier-free guidance, autoguidance, a known region, "
+                             "an init image or x0 thresholding")
+        guidance = Perturbed(float(pag[0]), layer_mask(pag[1]), layer_mask(pag[2] if len(pag) > 2 else 0))
+        if not math.isfinite(guidance.scale):
+            raise ValueError("pag scale must be finite")
+        for mdl, mask, what in ((model, guidance.layers_first, "layers_first"), (late_model, guidance.layers_late, "layers_late")):
+            if mdl is not None and mask >> mdl.depth:
+                raise ValueError(f"pag {what} names a block at or above the model's depth {mdl.depth}")
+    if image_seeds is not None:
+        if noise != "device":
+            raise ValueError("image_seeds need noise='device': the torch CPU stream is sequential in the batch")
+        image_seeds = [int(v) for v in image_seeds]
+        if len(image_seeds) != batch_size:
+            raise ValueError(f"image_seeds holds {len(image_seeds)} seeds for batch_size {batch_size}")
+    if (init_image is None) != (strength is None):
+        raise ValueError("init_image and strength go together")
+    if (known_image is None) != (known_mask is None):
+        raise ValueError("known_image and known_mask go together")
+    plan = step_plan(*plan_args)
+    if threshold is not None:
+        if autoencoder is not None:
+            raise ValueError("x0 thresholding is for pixel-space models: a latent model's x0 is a latent, not an image in [-1, 1]")
+        threshold_struct(threshold)
+    if cfg_scale is not None:
+        guidance = (float(cfg_scale), int(cfg_null_label))
+        if y is None:
+            raise ValueError("classifier-free guidance needs class labels")
+    init = None if init_image is None else _batch_tensor(init_image, "init_image", batch_size, image_shape, model.device)
+    region = None
+    if known_image is not None:
+        mask = _batch_tensor(known_mask, "known_mask", batch_size, (1,) + image_shape[1:], model.device)
+        if not bool(((mask >= 0) & (mask <= 1)).all()):
+            raise ValueError("known_mask must lie in [0, 1]")
+        region = KnownRegion(_batch_tensor(known_image, "known_image", batch_size, image_shape, model.device), mask, *known_rows(plan))
+    return plan, guidance, image_seeds, init, region
+
+
+def _start(ctx, device, batch_size, image_shape, seed, image_seeds, init, t0):
+    """x_T from the torch CPU stream after seed_everything(seed) (sampler.py:99-100), or image i on the device under image_seeds[i];
+    with an init image (t0 < 999): x_t0 = sqrt(abar) init + sqrt(1 - abar) x_T."""
+    seed_everything(seed)
+    if image_seeds is None:
+        x = torch.randn(batch_size, *image_shape).to(device).contiguous()
+    elif image_shape[1] != image_shape[2]:
+        raise ValueError("image_seeds: square images only")
+    else:
+        x = ctx.noise_images(batch_size, image_shape[0], image_shape[1], image_seeds=image_seeds, counter=0)
+    if t0 < 999:                                                             # (strength 1: t0 = 999, x_T alone)
+        ab0 = schedule_tables()["alphas_bar"].astype(np.float64)[t0]
+        ctx.affine_step(x, init, None, _f32(np.sqrt(1.0 - ab0)), _f32(np.sqrt(ab0)), 0.0, out=x)
+    return x
+
+
+# what a segment of get_samples works on: the models, x and the solver's history h (updated in place), the host step's eps buffer, the options
+_Run = namedtuple("_Run", "ctx plan first late x h eps y guidance threshold region seed use_graph image_seeds")
+
+
+def _segment_models(plan, k0, k1, first, late):
+    """Who runs the steps [k0, k1) of any plan kind: (the model that starts the segment, the one it switches to inside it or None, the
+    first step of that one counted from k0 -- 0: the segment starts behind the switch, k1 - k0: the switch comes later, None: never)"""
+    sw = None if plan.switch_after is None else min(max(plan.switch_after - k0, 0), k1 - k0)
+    return late if sw == 0 else first, late if sw and sw < k1 - k0 else None, sw
+
+
+def _device_segment(run, k0, k1):
+    """Steps [k0, k1) as one device loop call (hipGraph replays, Philox z) under the run's seed and the Philox counter base k0: cuts do not show"""
+    ctx, plan, x, h, tab = run.ctx, run.plan, run.x, run.h, run.plan.rows
+    m0, m1, sw = _segment_models(plan, k0, k1, run.first, run.late)
+    guidance = run.guidance
+    if isinstance(guidance, Perturbed) and sw == 0:                         # m0 is the late model: its blocks are the loop's layers_first
+        guidance = guidance._replace(layers_first=guidance.layers_late)
+    kw = dict(y=run.y, seed=run.seed, noise="philox", use_graph=run.use_graph, guidance=guidance)
+    known = () if run.region is None else (run.region._replace(ka=run.region.ka[k0:k1], kb=run.region.kb[k0:k1]),)   # -> the loop's _region form
+    seg = {key: v[k0:k1] for key, v in tab.items()}
+    with ctx.image_seeds(run.image_seeds) if run.image_seeds is not None else contextlib.nullcontext():   # (set around the segment's call)
+        if plan.kind == "ddpm":     # dd_sample: the late model unless the segment starts on it; t_switch counted from t = 999, not from t[0]
+            (sample_region_loop if known else sample_loop)(
+                ctx, m0, None if sw == 0 else run.late, x, *known, t_switch=plan.switch_after + 999 - int(tab["t"][0]) if sw else 0,
+                t_start=int(seg["t"][0]), t_end=int(seg["t"][-1]), **kw)
+        elif plan.kind == "affine":
+            (sample_affine_region_loop if known else sample_affine_loop)(
+                ctx, m0, m1, x, *known, seg["t"], seg["a"], seg["b"], seg["c"], seg["noise"], switch_after=sw, counter_base=k0, **kw)
+        elif run.threshold is not None:
+            sample_multistep_threshold_loop(ctx, m0, m1, x, h, seg, run.threshold, region=known[0] if known else None,
+                                            switch_after=sw, counter_base=k0, **kw)
+        else:
+            (sample_multistep_region_loop if known else sample_multistep_loop)(
+                ctx, m0, m1, x, *known, h, seg, switch_after=sw, counter_base=k0, **kw)
+
+
+def _host_step(run, k, k1=None):
+    """Step k, the segment [k, k + 1): z, then the known region's z2, from the torch CPU stream in the reference's order (sampler.py:103-139)"""
+    ctx, plan, x, h, y, g, eps, tab = run.ctx, run.plan, run.x, run.h, run.y, run.guidance, run.eps, run.plan.rows
+    cur, t = _segment_models(plan, k, k + 1, run.first, run.late)[0], tab["t"][k]
+    z = torch.randn(x.shape).to(x.device) if tab["noise"][k] else None
+    auto = isinstance(g, Autoguidance)
+    if plan.kind == "ddpm" and (g is None or auto and g.guide is cur):      # :130-133, fused; the guide's own steps: unguided, y only if it takes one
+        cur.sample_step(x, int(t), y=y if not auto or cur.mp.num_classes > 0 else None, z=z, noise="buffer")
+    else:
+        if g is None:
+            cur.forward(x, float(t), y, out=eps)
+        elif auto:
+            cur.forward_autoguided(x, float(t), y, g.guide, g.scale, out=eps)
+        elif isinstance(g, Perturbed):
+            cur.forward_perturbed(x, float(t), y, g.scale, g.layers_late if cur is run.late else g.layers_first, out=eps)
+        else:
+            cur.forward_guided(x, float(t), y, g[0], g[1], out=eps)
+        if plan.kind == "ddpm":
+            ctx.ddpm_step(x, eps, z, int(t), out=x)
+        elif plan.kind == "affine":
+            ctx.affine_step(x, eps, z, tab["a"][k], tab["b"][k], tab["c"][k], out=x)
+        else:
+            thr = () if run.threshold is None else (run.threshold,)
+            (ctx.threshold_step if thr else ctx.multistep_step)(x, eps, z, h, *thr, *(tab[key][k] for key in "abcdpq"), tab["hist"][k], out=x)
+    if run.region is not None:                                               # z2: its own draw, after the step's z
+        z2 = torch.randn(x.shape).to(x.device) if run.region.kb[k] != 0 else None
+        ctx.known_blend(x, run.region.x0, run.region.mask, z2, run.region.ka[k], run.region.kb[k], out=x)
 
 
 def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num_channels: int,
@@ -454,159 +322,43 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
         its own quantile scale and rescaled (mode "dynamic", Imagen's dynamic thresholding) before it drives the update; all three
         samplers then run as the thresholded multistep loop on unfolded rows.  predict_noise / predict_original models, pixel space.
     """
-    if noise not in ("torch_cpu", "device"):
-        raise ValueError("noise must be 'torch_cpu' or 'device'")
-    if autoguidance_scale is not None:
-        if cfg_scale is not None:
-            raise ValueError("classifier-free guidance and autoguidance are exclusive")
-        if not math.isfinite(float(autoguidance_scale)):
-            raise ValueError("autoguidance_scale must be finite")
-        if guide_model is None:
-            guide_model = model if late_model is not None else None
-        if guide_model is None:
-            raise ValueError("autoguidance needs a guide model: pass guide_model, or a late_model (the first model then guides it)")
-    elif guide_model is not None:
-        raise ValueError("guide_model without autoguidance_scale")
-    if pag is not None:
-        if cfg_scale is not None or autoguidance_scale is not None or known_image is not None or init_image is not None or threshold is not None:
-            raise ValueError("perturbed-attention guidance does not combine with classifier-free guidance, autoguidance, a known region, "
-                             "an init image or x0 thresholding")
-        pag_scale, pag_first, pag_late = float(pag[0]), layer_mask(pag[1]), layer_mask(pag[2] if len(pag) > 2 else 0)
-        if not math.isfinite(pag_scale):
-            raise ValueError("pag scale must be finite")
-        for mdl, mask, what in ((model, pag_first, "layers_first"), (late_model, pag_late, "layers_late")):
-            if mdl is not None and mask >> mdl.depth:
-                raise ValueError(f"pag {what} names a block at or above the model's depth {mdl.depth}")
-    if image_seeds is not None:
-        if noise != "device":
-            raise ValueError("image_seeds need noise='device': the torch CPU stream is sequential in the batch")
-        image_seeds = [int(v) for v in image_seeds]
-        if len(image_seeds) != batch_size:
-            raise ValueError(f"image_seeds holds {len(image_seeds)} seeds for batch_size {batch_size}")
-    if (init_image is None) != (strength is None):
-        raise ValueError("init_image and strength go together")
-    if (known_image is None) != (known_mask is None):
-        raise ValueError("known_image and known_mask go together")
-    plan = step_plan(_PARAMETRIZATIONS.get(postprocessing), timesteps_save, late_model is not None, t_switch, num_steps, use_ddim,
-                     ddim_steps, ddim_eta, solver, solver_steps, solver_order, strength, threshold)
-    if threshold is not None:
-        if autoencoder is not None:
-            raise ValueError("x0 thresholding is for pixel-space models: a latent model's x0 is a latent, not an image in [-1, 1]")
-        threshold_struct(threshold)
-    device = model.device
-    guidance = None if cfg_scale is None else (float(cfg_scale), int(cfg_null_label))
-    if guidance is not None and y is None:
-        raise ValueError("classifier-free guidance needs class labels")
-    rows = 2 * batch_size if guidance is not None or pag is not None else batch_size    # backbone rows per step
-    seed_everything(seed)                                                    # sampler.py:99
-    if image_seeds is None:
-        x = torch.randn(batch_size, num_channels, sample_height, sample_width).to(device).contiguous()  # :100
-    if y is not None:
-        y = torch.as_tensor(y).to(device, torch.int64).contiguous()
     image_shape = (num_channels, sample_height, sample_width)
-    t0 = start_timestep(strength)
-    init = None if init_image is None else _batch_tensor(init_image, "init_image", batch_size, image_shape, device)
-    region = None
-    if known_image is not None:
-        mask = _batch_tensor(known_mask, "known_mask", batch_size, (1, sample_height, sample_width), device)
-        if not bool(((mask >= 0) & (mask <= 1)).all()):
-            raise ValueError("known_mask must lie in [0, 1]")
-        region = KnownRegion(_batch_tensor(known_image, "known_image", batch_size, image_shape, device), mask, *known_rows(plan))
-    first = model.engine_model(rows)
-    late = late_model.engine_model(rows) if late_model is not None else None
+    plan_args = (_PARAMETRIZATIONS.get(postprocessing), timesteps_save, late_model is not None, t_switch, num_steps, use_ddim, ddim_steps,
+                 ddim_eta, solver, solver_steps, solver_order, strength, threshold)
+    plan, guidance, image_seeds, init, region = _resolve_options(
+        model, late_model, batch_size, image_shape, plan_args, noise, y, autoencoder, cfg_scale, cfg_null_label, autoguidance_scale,
+        guide_model, pag, image_seeds, init_image, strength, known_image, known_mask, threshold)
+    rows = backbone_rows(batch_size, cfg_scale, pag)
+    y = None if y is None else torch.as_tensor(y).to(model.device, torch.int64).contiguous()
+    first, late = model.engine_model(rows), late_model.engine_model(rows) if late_model is not None else None
     ctx = first.ctx
-    if image_seeds is not None:                                              # x_T on the device, image i under its own seed
-        if sample_height != sample_width:
-            raise ValueError("image_seeds: square images only")
-        x = ctx.noise_images(batch_size, num_channels, sample_height, image_seeds=image_seeds, counter=0)
-    if t0 < 999:                                                             # x_t0 = sqrt(abar) x0 + sqrt(1 - abar) z; strength 1: z alone, as today
-        ab0 = schedule_tables()["alphas_bar"].astype(np.float64)[t0]
-        ctx.affine_step(x, init, None, _f32(np.sqrt(1.0 - ab0)), _f32(np.sqrt(ab0)), 0.0, out=x)
-    guide = None
-    if autoguidance_scale is not None:
-        guide = first if guide_model is model else late if guide_model is late_model else guide_model.engine_model(rows)
-    autoguidance = None if guide is None else Autoguidance(guide, float(autoguidance_scale))
-    tab, n = plan.rows, len(plan.rows["t"])
+    x = _start(ctx, model.device, batch_size, image_shape, seed, image_seeds, init, start_timestep(strength))
+    if isinstance(guidance, Autoguidance):                                   # the guide's engine model: one of the run's two, or its own
+        g = guidance.guide
+        guidance = guidance._replace(guide=first if g is model else late if g is late_model else g.engine_model(rows))
     h = torch.zeros_like(x) if plan.kind == "multistep" else None          # the solver's history, carried across save points
-    intermediate = []
-    if noise == "device":
-        # one loop call per segment between save points (hipGraph replays, Philox z).  Every segment keeps the seed and passes its first
-        # step's index as the Philox counter base: the final samples do not depend on where the loop is cut.
-        for k0, k1 in _segments(plan.save_after):
-            sw = None if plan.switch_after is None else min(max(plan.switch_after - k0, 0), k1 - k0)
-            kw = dict(y=y, seed=seed, noise="philox", use_graph=use_graph, guidance=autoguidance or guidance)
-            if pag is not None:      # (a segment that starts behind the switch runs the late model as the loop's first)
-                kw["guidance"] = Perturbed(pag_scale, pag_late if sw == 0 else pag_first, pag_late)
-            # with a known region: the same loop's _region form, the region's rows cut like the loop's
-            known = () if region is None else (region._replace(ka=region.ka[k0:k1], kb=region.kb[k0:k1]),)
-            # per-image seeds: set on the context around the segment's call (its counter base keeps the cut invisible, as with one seed)
-            with ctx.image_seeds(image_seeds) if image_seeds is not None else contextlib.nullcontext():
-                if plan.kind == "ddpm":                                      # dd_sample counts t_switch from t = 999, switch_after from the start
-                    (sample_region_loop if known else sample_loop)(
-                        ctx, late if sw == 0 else first, None if sw == 0 else late, x, *known,
-                        t_switch=plan.switch_after + 999 - t0 if sw else 0, t_start=int(tab["t"][k0]), t_end=int(tab["t"][k1 - 1]), **kw)
-                else:
-                    seg = {key: v[k0:k1] for key, v in tab.items()}
-                    m0, m1 = late if sw == 0 else first, late if sw and sw < k1 - k0 else None
-                    if plan.kind == "affine":
-                        (sample_affine_region_loop if known else sample_affine_loop)(
-                            ctx, m0, m1, x, *known, seg["t"], seg["a"], seg["b"], seg["c"], seg["noise"], switch_after=sw, counter_base=k0, **kw)
-                    elif threshold is not None:
-                        sample_multistep_threshold_loop(ctx, m0, m1, x, h, seg, threshold, region=known[0] if known else None,
-                                                        switch_after=sw, counter_base=k0, **kw)
-                    else:
-                        (sample_multistep_region_loop if known else sample_multistep_loop)(
-                            ctx, m0, m1, x, *known, h, seg, switch_after=sw, counter_base=k0, **kw)
-            if plan.save_after[k1 - 1]:
-                intermediate.append(x.clone())
-    else:
-        eps, cur = torch.empty_like(x), first
-        for k in range(n):                                                   # sampler.py:129-139 / :103-126
-            if k == plan.switch_after:
-                cur = late
-            t = tab["t"][k]
-            z = torch.randn(x.shape).to(device) if tab["noise"][k] else None  # randn_like on the torch CPU stream (:52, :67, :119)
-            y_cur = y if guide is None or cur.mp.num_classes > 0 else None    # (autoguidance: y may be there for the other model only)
-            if plan.kind == "ddpm" and guidance is None and pag is None and (guide is None or guide is cur):
-                cur.sample_step(x, int(t), y=y_cur, z=z, noise="buffer")      # :130-133, fused
-            else:
-                if guidance is not None:
-                    cur.forward_guided(x, float(t), y, guidance[0], guidance[1], out=eps)
-                elif guide is not None:
-                    cur.forward_autoguided(x, float(t), y, guide, autoguidance.scale, out=eps)
-                elif pag is not None:
-                    cur.forward_perturbed(x, float(t), y, pag_scale, pag_late if cur is late else pag_first, out=eps)
-                else:
-                    cur.forward(x, float(t), y, out=eps)
-                if plan.kind == "ddpm":
-                    ctx.ddpm_step(x, eps, z, int(t), out=x)
-                elif plan.kind == "affine":
-                    ctx.affine_step(x, eps, z, tab["a"][k], tab["b"][k], tab["c"][k], out=x)
-                elif threshold is not None:
-                    ctx.threshold_step(x, eps, z, h, threshold, *(tab[key][k] for key in "abcdpq"), tab["hist"][k], out=x)
-                else:
-                    ctx.multistep_step(x, eps, z, h, *(tab[key][k] for key in "abcdpq"), tab["hist"][k], out=x)
-            if region is not None:                                           # z2: its own draw, after the step's z
-                z2 = torch.randn(x.shape).to(device) if region.kb[k] != 0 else None
-                ctx.known_blend(x, region.x0, region.mask, z2, region.ka[k], region.kb[k], out=x)
-            if plan.save_after[k]:
-                intermediate.append(x.clone())
-
-    if autoencoder is not None:                                              # :141-143, :149-150
+    device = noise == "device"
+    run = _Run(ctx, plan, first, late, x, h, None if device else torch.empty_like(x), y, guidance, threshold, region, seed, use_graph, image_seeds)
+    intermediate = []                                                        # (on the host every step is a segment of its own)
+    for k0, k1 in _segments(plan.save_after) if device else ((k, k + 1) for k in range(len(plan.save_after))):
+        (_device_segment if device else _host_step)(run, k0, k1)
+        if plan.save_after[k1 - 1]:
+            intermediate.append(x.clone())
+    if autoencoder is not None:                                              # the finish: decode (:141-143, :149-150), then the images
         print("Decode the images...")
         x = autoencoder.decode(x)
         intermediate = [autoencoder.decode(v) for v in intermediate]
     samples = ctx.to_images(x.contiguous())                                  # :145-146, library kernel
     inter = [ctx.to_images(v.contiguous()).cpu().numpy() for v in intermediate]
-    if return_device_tensor:
-        return samples, inter
-    return samples.cpu().numpy(), inter                                      # :155 (D2H boundary)
+    return (samples if return_device_tensor else samples.cpu().numpy()), inter       # :155 (the D2H boundary)
 
 
-def draw_labels(batch_size: int, num_classes: int):
+def draw_labels(batch_size: int, num_classes: int, seeds=None):
     """reference sampler.py:314-318: labels are randint(1, 1001) whatever --class_id says (quirk Q4); a label the embedding
-    table does not hold raises the IndexError nn.Embedding raises there (the engine would read past label_emb)."""
-    y = torch.randint(1, 1001, (batch_size,))
+    table does not hold raises the IndexError nn.Embedding raises there (the engine would read past label_emb).
+    seeds (per-image seeds): label i is drawn from a generator of its own under seeds[i]."""
+    y = torch.randint(1, 1001, (batch_size,)) if seeds is None else torch.cat(
+        [torch.randint(1, 1001, (1,), generator=torch.Generator().manual_seed(int(s))) for s in seeds])
     if int(y.max()) >= num_classes or int(y.min()) < 0:
         raise IndexError("index out of range in self")
     return y
@@ -842,9 +594,7 @@ def image_seed_list(args, batch_size: int, first_image=None):
     """--image_seeds: image i of the run (i counted from --first_image, or from first_image) gets seed --seed + i; None without the flag"""
     if not getattr(args, "image_seeds", False):
         return None
-    first = int(args.first_image if first_image is None else first_image)
-    if first < 0:
-        raise ValueError("--first_image must not be negative")
+    first = int(args.first_image if first_image is None else first_image)       # (validate_image_seeds: not negative)
     return [int(args.seed) + first + i for i in range(int(batch_size))]
 
 
@@ -862,19 +612,15 @@ def validate_image_seeds(args):
 
 def draw_labels_per_image(seeds, num_classes: int):
     """--class_id's draw (quirk Q4: randint(1, 1001) whatever the id) per image: label i is a function of seeds[i] alone"""
-    y = torch.cat([torch.randint(1, 1001, (1,), generator=torch.Generator().manual_seed(int(s))) for s in seeds])
-    if int(y.max()) >= num_classes or int(y.min()) < 0:
-        raise IndexError("index out of range in self")
-    return y
+    return draw_labels(len(seeds), num_classes, seeds)
 
 
 def labels_from_args(args, batch_size: int, num_classes: int, image_seeds=None):
-    """y of a run: --class_label K for every image, --class_id's reference draw (quirk Q4; with image_seeds: drawn per image from
-    the image's own seed), or None."""
-    if args.class_label is not None:
+    """y of a run: --class_label K for every image, --class_id's reference draw (quirk Q4; with image_seeds: per image), or None."""
+    if getattr(args, "class_label", None) is not None:                      # (eesampler has --class_id only)
         return torch.full((batch_size,), int(args.class_label), dtype=torch.int64)
     if args.class_id is not None:
-        return draw_labels(batch_size, num_classes) if image_seeds is None else draw_labels_per_image(image_seeds, num_classes)
+        return draw_labels(batch_size, num_classes, image_seeds)
     return None
 
 
@@ -1006,55 +752,58 @@ def build_model(config, checkpoint_path, precision, max_batch):
     return m.eval().to(get_device()), mp
 
 
-def main(argv=None):
-    args = get_args(argv)
-    out = Path(args.output_folder)
-    out.mkdir(parents=True, exist_ok=True)
-    post = {"predict_noise": predict_noise_postprocessing, "predict_original": predict_original_postprocessing,
-            "predict_previous": predict_previous_postprocessing}[args.parametrization]
+def load_autoencoder(args, config, device):
+    """The KL-VAE a latent model's config names (reference sampler.py:320-325; --autoencoder_checkpoint_path overrides), or None"""
+    if "autoencoder" in config:
+        path = args.autoencoder_checkpoint_path or config["autoencoder"]["autoencoder_checkpoint_path"]
+        return get_autoencoder(path, precision=args.precision).to(device)
 
+
+RunSetup = namedtuple("RunSetup", "mp kwargs")
+
+
+def setup_run(args):
+    """Everything between get_args and get_samples, for sampler.main and dist.main alike: every validate_* (all before the first model is
+    built), the configs, the models on backbone_rows rows (an explicit guide included), the autoencoder, --encode_images.  -> RunSetup(mp:
+    the first model's ModelParams; kwargs: get_samples' arguments but seed, image_seeds, y, timesteps_save and return_device_tensor)"""
     validate_solver(args)
     validate_image_seeds(args)
     config = load_config(args.config_path)
     config_late = load_config(args.config_path_late) if args.checkpoint_path_late else None
-    validate_guidance(args, ModelParams.from_dict(config).num_classes,
-                      ModelParams.from_dict(config_late).num_classes if config_late is not None else None)
+    validate_guidance(args, ModelParams.from_dict(config).num_classes, config_late and ModelParams.from_dict(config_late).num_classes)
     config_guide = load_config(args.guide_config_path) if args.guide_config_path else None
     validate_autoguidance(args, config, config_late, config_guide)
-    region_kwargs = validate_region(args, config_late if config_late is not None else config)
-    threshold = validate_threshold(args, config_late if config_late is not None else config)
+    config_last = config_late if config_late is not None else config        # (the model that finishes the images)
+    region_kwargs = validate_region(args, config_last)
+    threshold = validate_threshold(args, config_last)
     pag = validate_pag(args, config, config_late)
-    rows = 2 * args.batch_size if args.cfg_scale is not None or pag is not None else args.batch_size
+    rows = backbone_rows(args.batch_size, args.cfg_scale, pag)
     model, mp = build_model(config, args.checkpoint_path, args.precision, rows)
-    model_late = None
-    if config_late is not None:
-        config = config_late
-        model_late, _ = build_model(config, args.checkpoint_path_late, args.precision, rows)
-
-    model_guide = None
-    if config_guide is not None:
-        model_guide, _ = build_model(config_guide, args.guide_checkpoint_path, args.precision, rows)
-
-    seed_everything(args.seed)
-    image_seeds = image_seed_list(args, args.batch_size)
-    y = labels_from_args(args, args.batch_size, mp.num_classes, image_seeds)
-    autoencoder = None
-    if "autoencoder" in config:                                              # reference sampler.py:320-325
-        ae_path = args.autoencoder_checkpoint_path or config["autoencoder"]["autoencoder_checkpoint_path"]
-        autoencoder = get_autoencoder(ae_path, precision=args.precision).to(model.device)
+    late = build_model(config_late, args.checkpoint_path_late, args.precision, rows)[0] if config_late is not None else None
+    guide = build_model(config_guide, args.guide_checkpoint_path, args.precision, rows)[0] if config_guide is not None else None
+    autoencoder = load_autoencoder(args, config_last, model.device)
     if args.encode_images:
         print("Encode the images...")
         region_kwargs = encode_region(region_kwargs, autoencoder, args.seed, mean=args.encode_mean)
+    post = {name: fn for fn, name in _PARAMETRIZATIONS.items()}[args.parametrization]
+    return RunSetup(mp, dict(
+        model=model, batch_size=args.batch_size, postprocessing=post, num_channels=mp.in_chans, sample_height=mp.img_size,
+        sample_width=mp.img_size, use_ddim=args.use_ddim, ddim_steps=args.ddim_steps, ddim_eta=args.ddim_eta, autoencoder=autoencoder,
+        late_model=late, t_switch=args.t_switch, noise=args.noise, use_graph=not args.no_graph, cfg_scale=args.cfg_scale,
+        cfg_null_label=args.cfg_null_label, **solver_kwargs(args), autoguidance_scale=args.autoguidance_scale, guide_model=guide,
+        threshold=threshold, pag=pag, **region_kwargs))
 
+
+def main(argv=None):
+    args = get_args(argv)
+    out = Path(args.output_folder)
+    out.mkdir(parents=True, exist_ok=True)
+    setup = setup_run(args)
+    seed_everything(args.seed)
+    image_seeds = image_seed_list(args, args.batch_size)
+    y = labels_from_args(args, args.batch_size, setup.mp.num_classes, image_seeds)
     tic = time.time()
-    samples, inter = get_samples(model=model, batch_size=args.batch_size, postprocessing=post, seed=args.seed,
-                                 num_channels=mp.in_chans, sample_height=mp.img_size, sample_width=mp.img_size,
-                                 use_ddim=args.use_ddim, ddim_steps=args.ddim_steps, ddim_eta=args.ddim_eta,
-                                 y=y, autoencoder=autoencoder, late_model=model_late, t_switch=args.t_switch,
-                                 timesteps_save=args.timesteps_save, noise=args.noise, use_graph=not args.no_graph,
-                                 cfg_scale=args.cfg_scale, cfg_null_label=args.cfg_null_label, **solver_kwargs(args),
-                                 autoguidance_scale=args.autoguidance_scale, guide_model=model_guide, threshold=threshold, pag=pag, image_seeds=image_seeds,
-                                 **region_kwargs)
+    samples, inter = get_samples(**setup.kwargs, seed=args.seed, image_seeds=image_seeds, y=y, timesteps_save=args.timesteps_save)
     tac = time.time()
     dump_statistics(tac - tic, out, args.batch_size)
     if args.no_png:

@@ -1,0 +1,286 @@
+"""The host arithmetic of sampling: each sampler's update as per-step coefficient rows, and the StepPlan get_samples runs (timesteps,
+rows, noise flags, save points, the late model's first step).  numpy and the engine's bit-exact schedule tables only: no torch, no GPU."""
+from typing import NamedTuple, Optional
+
+import numpy as np
+
+from .engine import schedule_tables
+
+
+def _f32(v):
+    return np.float32(v)
+
+
+def affine_coefficients(kind, t, s=None, eta=0.0):
+    """Scalar (a, b, c) with x' = a*x + b*model_output + c*z for the reference's other updates, in fp32
+    from the engine's (bit-exact) tables:
+      "predict_original"  sampler.py:59-72      "predict_previous"  sampler.py:75-79
+      "ddim" (t -> s)     sampler.py:112-120 (noise scaled by sigma^2 = betas_tilde[t]*eta, as the reference does)
+    """
+    tb = schedule_tables()
+    one = _f32(1)
+    if kind == "predict_previous":
+        return _f32(0), one, np.sqrt(tb["betas_tilde"][t])
+    if kind == "predict_original":
+        a_t, ab_t, ab_p, b_t = tb["alphas"][t], tb["alphas_bar"][t], tb["alphas_bar_previous"][t], tb["betas"][t]
+        a = _f32(np.sqrt(a_t) * (one - ab_p)) / (one - ab_t)
+        b = _f32(np.sqrt(ab_p) * b_t) / (one - ab_t)
+        return _f32(a), _f32(b), np.sqrt(tb["betas_tilde"][t])
+    if kind == "ddim":
+        ab = tb["alphas_bar"]
+        sig2 = _f32(tb["betas_tilde"][t] * _f32(eta))
+        a = np.sqrt(_f32(ab[s] / ab[t]))
+        b = _f32(np.sqrt(_f32(one - ab[s] - sig2)) - _f32(a * np.sqrt(_f32(one - ab[t]))))
+        return _f32(a), b, sig2
+    raise ValueError(kind)
+
+
+MULTISTEP_KINDS = ("dpmsolver++", "sde-dpmsolver++")
+
+
+def multistep_rows(kind, alphas_bar, order=2, parametrization="predict_noise", lower_order_final=True, unfolded=False):
+    """float64 DPM-Solver++ (Lu et al., 2022) rows of the multistep update, for the steps alphas_bar[k] -> alphas_bar[k + 1]
+    (len(alphas_bar) = N + 1 values of abar along the grid; the model sees the first N):
+
+        x' = a x + b m [+ d h  if hist]  [+ c z  if noise]        h' = p x + q m
+
+    m: the model output at step k, h: the previous step's data prediction x0 = p x + q m.  kind: "dpmsolver++" (ODE, no noise)
+    or "sde-dpmsolver++" (the midpoint 2M SDE: every row here has noise = 1; multistep_coefficients drops the z of a step landing on
+    t = 0).  order 2: step 0 is first order (no history yet), and with lower_order_final the last step too (on the product grid it
+    lands on t = 0, where lambda jumps: a second-order step there extrapolates with r ~ 0.2 and overshoots).
+    unfolded: the rows of the thresholded loop, x' = a x + b xh + ..., xh = the thresholded data prediction p x + q m: a = A,
+    b = phi w0 (the default folds x0 into them: a = A + phi w0 p, b = phi w0 q).
+    Returns a dict of float64 arrays a, b, c, d, p, q and int32 arrays hist, noise."""
+    if kind not in MULTISTEP_KINDS:
+        raise ValueError(f"solver must be one of {MULTISTEP_KINDS}, not {kind!r}")
+    if order not in (1, 2):
+        raise ValueError("solver order must be 1 or 2")
+    if parametrization == "predict_previous":
+        raise ValueError("DPM-Solver++ needs a model that predicts the noise or the data (predict_noise / predict_original), "
+                         "not predict_previous")
+    if parametrization not in ("predict_noise", "predict_original"):
+        raise ValueError(parametrization)
+    ab = np.asarray(alphas_bar, np.float64)
+    n = len(ab) - 1
+    if n < 1:
+        raise ValueError("need at least one step")
+    alpha, sigma = np.sqrt(ab), np.sqrt(1.0 - ab)
+    lam = np.log(alpha) - np.log(sigma)
+    h = lam[1:] - lam[:-1]
+    rows = {k: np.zeros(n) for k in "abcdpq"}
+    rows["hist"], rows["noise"] = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    for k in range(n):
+        if parametrization == "predict_noise":
+            p, q = 1.0 / alpha[k], -sigma[k] / alpha[k]
+        else:
+            p, q = 0.0, 1.0
+        second = order == 2 and k > 0 and not (lower_order_final and k == n - 1)
+        if second:
+            r = h[k - 1] / h[k]
+            w0, w1 = 1.0 + 1.0 / (2.0 * r), -1.0 / (2.0 * r)
+        else:
+            w0, w1 = 1.0, 0.0
+        if kind == "dpmsolver++":
+            A, phi, c = sigma[k + 1] / sigma[k], alpha[k + 1] * -np.expm1(-h[k]), 0.0
+        else:
+            A, phi = sigma[k + 1] / sigma[k] * np.exp(-h[k]), alpha[k + 1] * -np.expm1(-2.0 * h[k])
+            c = sigma[k + 1] * np.sqrt(-np.expm1(-2.0 * h[k]))
+        rows["a"][k], rows["b"][k], rows["c"][k], rows["d"][k] = A + phi * w0 * p, phi * w0 * q, c, phi * w1
+        if unfolded:
+            rows["a"][k], rows["b"][k] = A, phi * w0
+        rows["p"][k], rows["q"][k] = p, q
+        rows["hist"][k] = int(w1 != 0.0)
+        rows["noise"][k] = int(kind == "sde-dpmsolver++")
+    return rows
+
+
+def multistep_grid(n_steps, t0=999):
+    """The integer timestep grid of an N-evaluation DPM-Solver++ run: N + 1 points from t0 (999; lower: an image-to-image start) down
+    to 0; the model sees the first N."""
+    n = int(n_steps)
+    if not 1 <= n <= 999:
+        raise ValueError(f"DPM-Solver++ steps must be in [1, 999], not {n}")
+    if n > t0:
+        raise ValueError(f"{n} DPM-Solver++ steps do not fit a start at t = {t0}: lower the steps or raise the strength")
+    return np.linspace(t0, 0, n + 1).round().astype(int)
+
+
+def _data_prediction(parametrization, ab_t):
+    """(p, q) of x0 = p x + q m in float64 at alphas_bar ab_t: the model predicts the noise or the data"""
+    if parametrization == "predict_previous":
+        raise ValueError("x0 thresholding needs a model that predicts the noise or the data (predict_noise / predict_original), "
+                         "not predict_previous: there is no x0")
+    if parametrization == "predict_original":
+        return 0.0, 1.0
+    if parametrization != "predict_noise":
+        raise ValueError(parametrization)
+    return 1.0 / np.sqrt(ab_t), -np.sqrt(1.0 - ab_t) / np.sqrt(ab_t)
+
+
+def unfolded_rows(kind, ts, eta=0.0, parametrization="predict_noise"):
+    """The reference's own samplers as float64 UNFOLDED rows of the thresholded loop (x' = a x + b xh + c z, xh the thresholded
+    x0 = p x + q m, no history), from the engine's bit-exact tables:
+      "ddim"  over the descending grid ts (N + 1 timesteps), step t -> s: a = dir / sigma_t, b = alpha_s - a alpha_t with
+              dir = sqrt(1 - abar_s - sig2), sig2 = betas_tilde[t] eta and c = sig2 (the reference scales its noise by sigma^2,
+              sampler.py:112-120, and reads the model output as the noise whatever the parametrization: so does (p, q) here)
+      "ddpm"  the ancestral steps at the timesteps ts (t -> t - 1): the posterior mean's coefficients on x and x0 (sampler.py:59-72)
+              and c = sqrt(betas_tilde[t]); (p, q) from the parametrization
+    Returns a dict of float64 arrays a, b, c, d, p, q and int32 arrays hist (0), noise (the step does not land on the final image)."""
+    tb = {k: v.astype(np.float64) for k, v in schedule_tables().items()}
+    ab = tb["alphas_bar"]
+    ts = np.asarray(ts, np.int64)
+    if kind == "ddim":
+        t, s_ = ts[:-1], ts[1:]
+        sig2 = tb["betas_tilde"][t] * float(eta)
+        with np.errstate(invalid="ignore"):     # (a large eta on the step onto t = 0: the reference's direction term is NaN, sampler.py:116)
+            a = np.sqrt(1.0 - ab[s_] - sig2) / np.sqrt(1.0 - ab[t])
+        b = np.sqrt(ab[s_]) - a * np.sqrt(ab[t])
+        c, noise = sig2, s_ > 0
+        pq = [_data_prediction("predict_noise", v) for v in ab[t]]
+        if parametrization == "predict_previous":
+            _data_prediction(parametrization, 0.5)
+    elif kind == "ddpm":
+        t = ts
+        a = np.sqrt(tb["alphas"][t]) * (1.0 - tb["alphas_bar_previous"][t]) / (1.0 - ab[t])
+        b = np.sqrt(tb["alphas_bar_previous"][t]) * tb["betas"][t] / (1.0 - ab[t])
+        c, noise = np.sqrt(tb["betas_tilde"][t]), t > 0
+        pq = [_data_prediction(parametrization, v) for v in ab[t]]
+    else:
+        raise ValueError(kind)
+    n = len(t)
+    return {"a": a, "b": b, "c": np.asarray(c, np.float64), "d": np.zeros(n), "p": np.array([v[0] for v in pq]).reshape(n),
+            "q": np.array([v[1] for v in pq]).reshape(n), "hist": np.zeros(n, np.int32), "noise": noise.astype(np.int32)}
+
+
+def unfolded_coefficients(kind, ts, eta=0.0, parametrization="predict_noise"):
+    """unfolded_rows as the fp32 rows a loop takes (each coefficient rounded once), with t: the model timesteps"""
+    ts = np.asarray(ts, np.int64)
+    r = unfolded_rows(kind, ts, eta, parametrization)
+    out = {k: r[k].astype(np.float32) for k in "abcdpq"}
+    out["t"] = (ts[:-1] if kind == "ddim" else ts).astype(np.float32)
+    out["hist"], out["noise"] = r["hist"], r["noise"]
+    return out
+
+
+def multistep_coefficients(kind, ts, order=2, parametrization="predict_noise", unfolded=False):
+    """The fp32 rows of a DPM-Solver++ run over the integer grid ts (descending, N + 1 timesteps, the last one usually 0), from the
+    engine's bit-exact schedule tables: multistep_rows in float64, each coefficient rounded once.  Returns a dict of per-step arrays
+    t (float32 model timesteps t_0 .. t_{N-1}), a, b, c, d, p, q (float32), hist, noise (int32).  The SDE draws z on every step but
+    one landing on t = 0 (the reference's DDPM / DDIM convention)."""
+    ts = np.asarray(ts, np.int64)
+    if ts.ndim != 1 or len(ts) < 2 or (ts < 0).any() or (ts > 999).any() or (np.diff(ts) >= 0).any():
+        raise ValueError("ts must be a strictly decreasing grid of timesteps in [0, 999] with at least two points")
+    ab = schedule_tables()["alphas_bar"].astype(np.float64)[ts]
+    r = multistep_rows(kind, ab, order, parametrization, unfolded=unfolded)
+    out = {k: r[k].astype(np.float32) for k in "abcdpq"}
+    out["t"] = ts[:-1].astype(np.float32)
+    out["hist"] = r["hist"]
+    out["noise"] = (r["noise"] * (ts[1:] > 0)).astype(np.int32)
+    return out
+
+
+class StepPlan(NamedTuple):
+    """What get_samples runs, step by step.  kind: "ddpm" (dd_sample / ddpm_step: the update follows from t), "affine" (rows a, b, c)
+    or "multistep" (rows a, b, c, d, p, q, hist: multistep_coefficients).  rows: per-step arrays, always with t (the model timestep,
+    float32) and noise (int32: the step draws z).  save_after[k]: x is saved after step k.  switch_after: the first step the late model
+    runs, or None; it may lie past the last step (a DDPM switch beyond num_steps), where it only hands the late model to dd_sample.
+    lands[k]: the timestep whose noise level x has after step k, -1 for the final image (known_rows)."""
+    kind: str
+    rows: dict
+    save_after: list
+    switch_after: Optional[int]
+    lands: tuple = ()
+
+
+def start_timestep(strength=None):
+    """The timestep a loop starts at: 999, or round(999 * strength) for an image-to-image start of strength in (0, 1]."""
+    if strength is None:
+        return 999
+    if not (isinstance(strength, (int, float, np.number)) and 0 < float(strength) <= 1):
+        raise ValueError(f"strength must be in (0, 1], not {strength!r}")
+    return int(round(999 * float(strength)))
+
+
+def step_plan(parametrization, timesteps_save=(), has_late=False, t_switch=np.inf, num_steps=1000, use_ddim=False, ddim_steps=50,
+              ddim_eta=0.0, solver=None, solver_steps=20, solver_order=2, strength=None, threshold=None):
+    """The StepPlan of get_samples' arguments (parametrization: "predict_noise" | "predict_original" | "predict_previous", or None
+    for a postprocessing function of elsewhere; has_late: a late model is given).  Host arithmetic only, no torch.
+    strength (None or 1: the start at t = 999): the loops start at t0 = start_timestep(strength) -- DDPM at t0, the DDIM and solver grids
+    built from t0 down with the same spacing rule and step count; the late model's rule is unchanged (by timestep).
+    threshold (anything but None): the plan of the thresholded loop -- kind "multistep" on UNFOLDED rows for all three samplers
+    (multistep_coefficients(..., unfolded=True), unfolded_coefficients); predict_previous has no x0 and is rejected."""
+    t0 = start_timestep(strength)
+    if threshold is not None:
+        _data_prediction(parametrization if parametrization is not None else "predict_noise", 0.5)
+    # the DDPM loop switches AFTER the step at t == 1000 - t_switch (sampler.py:135-136): a t_switch outside [1, 1000] (0, negative,
+    # > 1000, inf) never matches a t in 999..0, i.e. the first model runs every step
+    in_range = has_late and np.isfinite(t_switch) and 1 <= int(t_switch) <= 1000
+    if solver is not None:
+        if use_ddim:
+            raise ValueError("DPM-Solver++ and DDIM are exclusive")
+        grid = multistep_grid(solver_steps, t0)                               # range check first
+        if parametrization is None:
+            raise ValueError("postprocessing must be one of this module's predict_*_postprocessing functions")
+        kind, rows = "multistep", multistep_coefficients(solver, grid, solver_order, parametrization, unfolded=threshold is not None)
+        switch_after = next((k for k, t in enumerate(rows["t"]) if t < 1000 - int(t_switch)), None) if in_range else None
+        lands = [int(s) if s > 0 else -1 for s in grid[1:]]
+    elif use_ddim:
+        # reference sampler.py:103-126; z is drawn (:119) whenever s > 0, also at eta = 0
+        ts = np.linspace(0, t0, ddim_steps).astype(int)[::-1]
+        if (np.diff(ts) >= 0).any():
+            raise ValueError(f"{ddim_steps} DDIM steps do not fit a start at t = {t0}: lower the steps or raise the strength")
+        pairs = [(int(t), int(s)) for t, s in zip(ts[:-1], ts[1:])]
+        if threshold is not None:
+            if parametrization is None:
+                raise ValueError("postprocessing must be one of this module's predict_*_postprocessing functions")
+            kind, rows = "multistep", unfolded_coefficients("ddim", ts, ddim_eta, parametrization)
+        else:
+            kind, rows = "affine", _affine_rows([t for t, _ in pairs], [affine_coefficients("ddim", t, s, ddim_eta) for t, s in pairs],
+                                                [s > 0 for _, s in pairs])
+        # :122-123: the late model from the step after the first t < 1000 - t_switch (raw t_switch: <= 0 switches after step 0)
+        switch_after = next((k + 1 for k, (t, _) in enumerate(pairs) if t < 1000 - t_switch), None) if has_late else None
+        lands = [s if s > 0 else -1 for _, s in pairs]
+    else:
+        # sampler.py:129-139: t = 999 .. 1000 - num_steps; predict_original / predict_previous (:59-79) as affine rows
+        ts = list(range(t0, max(t0 - int(num_steps), -1), -1))
+        if threshold is not None and parametrization in ("predict_noise", "predict_original"):
+            kind, rows = "multistep", unfolded_coefficients("ddpm", ts, 0.0, parametrization)
+        elif parametrization == "predict_noise":
+            kind, rows = "ddpm", {"t": np.array(ts, np.float32), "noise": np.array([t > 0 for t in ts], np.int32)}
+        elif parametrization in ("predict_original", "predict_previous"):
+            kind, rows = "affine", _affine_rows(ts, [affine_coefficients(parametrization, t) for t in ts], [t > 0 for t in ts])
+        else:
+            raise ValueError("postprocessing must be one of this module's predict_*_postprocessing functions")
+        switch_after = max(int(t_switch) - (999 - t0), 0) if in_range else None   # the step after t == 1000 - t_switch
+        lands = [t - 1 for t in ts]
+    saves = set(int(v) for v in timesteps_save)
+    return StepPlan(kind, rows, [(1000 - int(t)) in saves for t in rows["t"]], switch_after, tuple(lands))
+
+
+def known_rows(plan):
+    """The known-region rows (ka, kb) of a plan, float32, one per step: a step that lands on timestep s puts its known pixels at
+    ka x0 + kb z2 with ka = sqrt(alphas_bar[s]), kb = sqrt(1 - alphas_bar[s]) from the engine's bit-exact tables, each rounded once;
+    a step that lands on the final image (the DDPM step at t = 0, the last DDIM pair, the solver grid's last point) has (1, 0), so the
+    known pixels of the result are x0 itself.  Host arithmetic only."""
+    ab = schedule_tables()["alphas_bar"].astype(np.float64)
+    s = np.asarray(plan.lands, np.int64)
+    final = s < 0
+    abs_ = ab[np.where(final, 0, s)]
+    ka = np.where(final, 1.0, np.sqrt(abs_)).astype(np.float32)
+    kb = np.where(final, 0.0, np.sqrt(1.0 - abs_)).astype(np.float32)
+    return ka, kb
+
+
+def _affine_rows(ts, coefficients, noise):
+    a, b, c = zip(*coefficients) if coefficients else ((), (), ())
+    return {"t": np.array(ts, np.float32), "a": np.array(a, np.float32), "b": np.array(b, np.float32), "c": np.array(c, np.float32),
+            "noise": np.array(noise, np.int32)}
+
+
+def _segments(save_after):
+    """(k0, k1) of the device loop cut after every save step"""
+    k0 = 0
+    for k, save in enumerate(save_after):
+        if save or k == len(save_after) - 1:
+            yield k0, k + 1
+            k0 = k + 1

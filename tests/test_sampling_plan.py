@@ -2,18 +2,22 @@
 
 The plan tests pin each sampler's rules: timesteps, update rows, which steps draw z, the save points and the step the late model
 takes over.  The call-log tests run get_samples on the CPU with recording fakes for the models, the context, the autoencoder and the
-three device loops, and compare every call with a log recorded once from the sampler before the plan existed
-(tests/golden/sampler_calls.json.gz).  Floats are logged as float32 bit patterns and tensors as their exact float64 sums, so the
-logs pin the coefficient rounding and the order of the torch CPU noise draws.  A loop call without a late model drops switch_after /
-t_switch from its log: the engine ignores them there.
+device loops, and compare every call with a log recorded from the sampler as it was before get_samples was last restructured
+(tests/golden/sampler_calls.json.gz): the matrix of samplers, noise modes, saves, switches, labels and classifier-free guidance, and
+on top of it known regions, init images, x0 thresholds, autoguidance, perturbed-attention guidance and per-image seeds.  Floats are
+logged as float32 bit patterns and tensors as their exact float64 sums, so the logs pin the coefficient rounding and the order of the
+torch CPU noise draws.  A loop call without a late model drops switch_after / t_switch from its log: the engine ignores them there.
+Every option get_samples rejects is rejected before the first call.
 
 Regenerate the fixture (only when the intended behaviour changes): python tests/test_sampling_plan.py --write
 """
+import contextlib
 import gzip
 import inspect
 import json
 import math
 import sys
+import types
 from pathlib import Path
 
 import numpy as np
@@ -131,6 +135,8 @@ def _norm(v):
         return [type(v).__name__, getattr(v, "name", "")]
     if isinstance(v, dict):
         return {k: _norm(v[k]) for k in sorted(v)}
+    if isinstance(v, tuple) and hasattr(v, "_fields"):      # KnownRegion, Autoguidance, Perturbed, X0Threshold: by member
+        return [type(v).__name__, {k: _norm(getattr(v, k)) for k in v._fields}]
     if isinstance(v, (list, tuple, np.ndarray)):
         a = np.asarray(v)
         if a.dtype.kind == "f":
@@ -149,7 +155,8 @@ class _Log(list):
 
 
 class _Ctx:
-    """ddpm_step / affine_step / multistep_step / to_images: logged, and each step adds 1 to x so the log tracks x's state"""
+    """ddpm_step / affine_step / multistep_step / threshold_step / known_blend / to_images: logged, and each adds 1 to x so the log
+    tracks x's state; noise_images: image i filled with its seed; image_seeds: enter and exit logged around the calls inside"""
 
     def __init__(self, log):
         self.log = log
@@ -171,6 +178,26 @@ class _Ctx:
         h.add_(1)
         return self._step("multistep_step", x, out, m=m, z=z, a=a, b=b, c=c, d=d, p=p, q=q, use_hist=use_hist)
 
+    def threshold_step(self, x, m, z, h, threshold, a, b, c, d, p, q, use_hist, out=None):
+        self.log.add("threshold_h", h=h)
+        h.add_(1)
+        return self._step("threshold_step", x, out, m=m, z=z, threshold=threshold, a=a, b=b, c=c, d=d, p=p, q=q, use_hist=use_hist)
+
+    def known_blend(self, x, x0, mask, z2, ka, kb, out=None):
+        return self._step("known_blend", x, out, x0=x0, mask=mask, z2=z2, ka=ka, kb=kb)
+
+    def noise_images(self, B, C, S, seed=0, image_seeds=None, counter=0):
+        self.log.add("noise_images", B=B, C=C, S=S, seed=seed, image_seeds=image_seeds, counter=counter)
+        return torch.stack([torch.full((C, S, S), float(s)) for s in image_seeds])
+
+    @contextlib.contextmanager
+    def image_seeds(self, seeds):
+        self.log.add("image_seeds_enter", seeds=seeds)
+        try:
+            yield
+        finally:
+            self.log.add("image_seeds_exit", seeds=seeds)
+
     def to_images(self, x):
         self.log.add("to_images", x=x)
         return x.permute(0, 2, 3, 1) * 0.5 + 0.5
@@ -179,9 +206,10 @@ class _Ctx:
 class _Model:
     """The UViT and its engine model in one: engine_model returns itself; forward writes t into out"""
     device = "cpu"
+    depth = 3
 
-    def __init__(self, name, log, ctx):
-        self.name, self.log, self.ctx = name, log, ctx
+    def __init__(self, name, log, ctx, num_classes=11):
+        self.name, self.log, self.ctx, self.mp = name, log, ctx, types.SimpleNamespace(num_classes=num_classes)
 
     def engine_model(self, rows):
         self.log.add("engine_model", model=self, rows=rows)
@@ -194,6 +222,14 @@ class _Model:
     def forward_guided(self, x, t, y, scale, null_label, out=None):
         self.log.add("forward_guided", model=self, x=x, t=t, y=y, scale=scale, null_label=null_label)
         return out.fill_(float(t) + 0.5)
+
+    def forward_autoguided(self, x, t, y, guide, scale, out=None):
+        self.log.add("forward_autoguided", model=self, x=x, t=t, y=y, guide=guide, scale=scale)
+        return out.fill_(float(t) + 0.25)
+
+    def forward_perturbed(self, x, t, y, scale, layers, out=None):
+        self.log.add("forward_perturbed", model=self, x=x, t=t, y=y, scale=scale, layers=layers)
+        return out.fill_(float(t) + 0.75)
 
     def sample_step(self, x, t, y=None, z=None, noise="buffer"):
         self.log.add("sample_step", model=self, x=x, t=t, y=y, z=z, noise=noise)
@@ -221,9 +257,9 @@ def _loop_fake(log, fn):
             kw.pop("switch_after", None)
             kw.pop("t_switch", None)
         log.add(fn.__name__, **kw)
-        if fn is engine.sample_loop:
+        if "t_start" in kw:
             kw["x"].add_(kw["t_start"] - kw["t_end"] + 1)
-        elif fn is engine.sample_affine_loop:
+        elif "rows" not in kw:
             kw["x"].add_(len(kw["t"]))
         else:
             kw["x"].add_(len(kw["rows"]["t"]))
@@ -232,16 +268,22 @@ def _loop_fake(log, fn):
     return fake
 
 
+LOOPS = (engine.sample_loop, engine.sample_affine_loop, engine.sample_multistep_loop, engine.sample_region_loop,
+         engine.sample_affine_region_loop, engine.sample_multistep_region_loop, engine.sample_multistep_threshold_loop)
+
+
 def record(monkeypatch, kw, log=None):
     """get_samples(**kw) with fakes: the call log, ending with the returned samples and intermediates"""
     log = _Log() if log is None else log
     ctx = _Ctx(log)
-    for fn in (engine.sample_loop, engine.sample_affine_loop, engine.sample_multistep_loop):
+    for fn in LOOPS:
         monkeypatch.setattr(sampler, fn.__name__, _loop_fake(log, fn))
     kw = dict(kw)
-    kw["model"] = _Model("first", log, ctx)
+    kw["model"] = _Model("first", log, ctx, kw.pop("first_classes", 11))
     if kw.pop("late", False):
         kw["late_model"] = _Model("late", log, ctx)
+    if kw.pop("guide", False):
+        kw["guide_model"] = _Model("guide", log, ctx)
     if kw.pop("ae", False):
         kw["autoencoder"] = _Autoencoder(log)
     kw["postprocessing"] = getattr(sampler, kw.pop("post", "predict_noise") + "_postprocessing")
@@ -283,6 +325,41 @@ def _cases():
     out["ddpm-device-1000"] = dict(base, noise="device", late=True, t_switch=300, timesteps_save=[100, 300, 301, 1000])
     out["ddpm-device-1000-guided-ae"] = dict(base, noise="device", late=True, t_switch=999, timesteps_save=[999], y=[0, 1],
                                               cfg_scale=0.0, ae=True)
+
+    # ---- the options that came after the plan: each on a plain run and on one with saves and a late model that switches inside it
+    def add(tag, names, extra, noises=("device", "torch_cpu"), runs=None):
+        for name in names:
+            kw, saves, switches = (runs or samplers)[name]
+            for noise in noises:
+                c = dict(base, **kw, noise=noise, **extra)
+                out[f"{name}-{noise}-{tag}"] = c
+                out[f"{name}-{noise}-{tag}-late{switches[0]}-saves"] = dict(c, late=True, t_switch=switches[0], timesteps_save=saves)
+
+    # (a leading-1 image broadcast over the batch; a mask per image with 0, 1 and a fractional value)
+    region = dict(known_image=np.linspace(-1, 1, 48, dtype=np.float32).reshape(1, 3, 4, 4),
+                  known_mask=np.tile(np.float32([0, 1, 0.25, 1]), 8).reshape(2, 1, 4, 4))
+    # strength 0.5 starts at t0 = 500.  DDPM t = 500 .. 489 (1000 - t = 500 .. 511, t_switch 504: the late model from step 5);
+    # DDIM t = 500, 428, 357, 285, 214, 142, 71; the solver's grid 500, 417, 333, 250, 167, 83: t_switch 700 switches at the first t < 300
+    init = dict(init_image=np.cos(np.arange(96, dtype=np.float32)).reshape(2, 3, 4, 4), strength=0.5)
+    init_runs = {"ddpm": (samplers["ddpm"][0], [503, 507, 3], [504]), "ddim": (samplers["ddim"][0], [572, 715, 144], [700]),
+                 "ode": (samplers["ode"][0], [583, 750, 2], [700])}
+    static, dynamic = engine.X0Threshold("static", range=0.75), engine.X0Threshold("dynamic", quantile=0.9, s_max=2.5)
+    add("known", ("ddpm", "original", "ddim", "ode"), region)
+    add("init", ("ddpm", "ddim", "ode"), init, runs=init_runs)
+    add("init-known", ("ddim",), dict(init, **region), runs=init_runs)
+    add("clip", ("ddpm", "ddim", "ode"), dict(threshold=static))
+    add("dynamic", ("ddpm", "ddim", "ode"), dict(threshold=dynamic))
+    add("clip-known", ("ode",), dict(region, threshold=static))
+    # autoguidance: the first model guides the late one (only the pair variant exists), an explicit guide, labels with an unconditional guide
+    add("autoguided", ("ddpm", "ddim", "ode"), dict(autoguidance_scale=0.75, late=True))
+    add("autoguided-explicit", ("ddpm", "ddim", "ode"), dict(autoguidance_scale=1.25, guide=True))
+    add("autoguided-labels", ("ddpm", "ddim", "ode"), dict(autoguidance_scale=0.5, late=True, y=[4, 9], first_classes=0))
+    # PAG: one model (no layers_late given / a bit mask), a pair (its saves leave a segment that starts on the late model)
+    add("pag", ("ddpm", "ddim", "ode"), dict(pag=(1.5, [1])))
+    add("pag-masks", ("ddpm",), dict(pag=(0.0, 0b101, 0b010), y=[4, 9]))
+    add("pag-pair", ("ddpm", "ddim", "ode"), dict(pag=(1.5, [1], [0, 2]), late=True))
+    add("image_seeds", ("ddpm", "ode"), dict(image_seeds=[7, 5], timesteps_save=[3, samplers["ode"][1][0]]), noises=("device",))
+    add("image_seeds-labels-ae", ("ode",), dict(image_seeds=[2 ** 40, 0], y=[1, 2], ae=True), noises=("device",))
     return out
 
 
@@ -318,6 +395,73 @@ def test_unknown_noise_mode_raises_before_any_call(monkeypatch, name):
     with pytest.raises(ValueError, match="noise"):
         record(monkeypatch, dict(CASES[name], noise="philox"), log)
     assert log == []
+
+
+def _rejections():
+    """name -> (arguments on top of ddim-device, the error's text): every ValueError get_samples raises itself, and a few inputs wrong
+    in two ways, which raise the error the checks meet first"""
+    img, mask = np.zeros((1, 3, 4, 4), np.float32), np.ones((1, 1, 4, 4), np.float32)
+    clip = engine.X0Threshold("static")
+    pag_with = "perturbed-attention guidance does not combine"
+    return {
+        "autoguidance+cfg": (dict(autoguidance_scale=1.0, cfg_scale=1.0, y=[1, 2], late=True), "autoguidance are exclusive"),
+        "autoguidance-inf": (dict(autoguidance_scale=math.inf, late=True), "autoguidance_scale must be finite"),
+        "autoguidance-nan": (dict(autoguidance_scale=math.nan, guide=True), "autoguidance_scale must be finite"),
+        "autoguidance-no-guide": (dict(autoguidance_scale=1.0), "autoguidance needs a guide model"),
+        "guide-no-scale": (dict(guide=True), "guide_model without autoguidance_scale"),
+        "pag+cfg": (dict(pag=(1.0, [1]), cfg_scale=1.0, y=[1, 2]), pag_with),
+        "pag+autoguidance": (dict(pag=(1.0, [1]), autoguidance_scale=1.0, late=True), pag_with),
+        "pag+known": (dict(pag=(1.0, [1]), known_image=img, known_mask=mask), pag_with),
+        "pag+init": (dict(pag=(1.0, [1]), init_image=img, strength=0.5), pag_with),
+        "pag+threshold": (dict(pag=(1.0, [1]), threshold=clip), pag_with),
+        "pag-inf": (dict(pag=(math.inf, [1])), "pag scale must be finite"),
+        "pag-layer-first": (dict(pag=(1.0, [3])), "pag layers_first names a block at or above the model's depth 3"),
+        "pag-layer-late": (dict(pag=(1.0, [1], 0b1000), late=True), "pag layers_late names a block at or above the model's depth 3"),
+        "image_seeds-torch_cpu": (dict(image_seeds=[1, 2], noise="torch_cpu"), "image_seeds need noise='device'"),
+        "image_seeds-length": (dict(image_seeds=[1, 2, 3]), "image_seeds holds 3 seeds for batch_size 2"),
+        "init-no-strength": (dict(init_image=img), "init_image and strength go together"),
+        "strength-no-init": (dict(strength=0.5), "init_image and strength go together"),
+        "known-no-mask": (dict(known_image=img), "known_image and known_mask go together"),
+        "mask-no-known": (dict(known_mask=mask), "known_image and known_mask go together"),
+        "mask-above": (dict(known_image=img, known_mask=mask * 1.5), r"known_mask must lie in \[0, 1\]"),
+        "mask-below": (dict(known_image=img, known_mask=mask - 1.5), r"known_mask must lie in \[0, 1\]"),
+        "mask-shape": (dict(known_image=img, known_mask=np.ones((1, 3, 4, 4), np.float32)), "known_mask must have shape"),
+        "threshold-ae": (dict(threshold=clip, ae=True), "x0 thresholding is for pixel-space models"),
+        "threshold-previous": (dict(threshold=clip, post="predict_previous"), "x0 thresholding needs a model that predicts"),
+        "threshold-mode": (dict(threshold=engine.X0Threshold("soft")), "threshold mode must be"),
+        "cfg-no-labels": (dict(cfg_scale=1.0), "classifier-free guidance needs class labels"),
+        # wrong in two ways: the first check met wins
+        "noise, then autoguidance+cfg": (dict(noise="philox", autoguidance_scale=1.0, cfg_scale=1.0), "noise must be"),
+        "autoguidance+cfg, then no guide": (dict(autoguidance_scale=math.inf, cfg_scale=1.0), "autoguidance are exclusive"),
+        "guide-no-scale, then pag": (dict(guide=True, pag=(math.inf, [7])), "guide_model without autoguidance_scale"),
+        "pag+cfg, then labels": (dict(pag=(math.inf, [7]), cfg_scale=1.0), pag_with),
+        "pag-inf, then layer": (dict(pag=(math.inf, [7])), "pag scale must be finite"),
+        "pag, then image_seeds": (dict(pag=(1.0, [3]), image_seeds=[1]), "pag layers_first"),
+        "image_seeds, then init": (dict(image_seeds=[1], init_image=img), "image_seeds holds 1 seeds"),
+        "init, then known": (dict(init_image=img, known_mask=mask), "init_image and strength go together"),
+        "known, then plan": (dict(known_image=img, solver="dpmsolver++"), "known_image and known_mask go together"),
+        "plan, then threshold-ae": (dict(threshold=clip, ae=True, post="predict_previous"), "x0 thresholding needs a model that predicts"),
+        "threshold-ae, then labels": (dict(threshold=clip, ae=True, cfg_scale=1.0), "x0 thresholding is for pixel-space models"),
+        "labels, then mask": (dict(cfg_scale=1.0, known_image=img, known_mask=mask * 2), "classifier-free guidance needs class labels"),
+    }
+
+
+REJECTIONS = _rejections()
+
+
+@pytest.mark.parametrize("name", sorted(REJECTIONS))
+def test_bad_options_raise_before_any_call(monkeypatch, name):
+    extra, text = REJECTIONS[name]
+    log = _Log()
+    with pytest.raises(ValueError, match=text):
+        record(monkeypatch, dict(CASES["ddim-device"], **extra), log)
+    assert log == []
+
+
+def test_image_seeds_need_square_images(monkeypatch):
+    """(raised where x_T is drawn, behind the models' engine_model calls)"""
+    with pytest.raises(ValueError, match="image_seeds: square images only"):
+        record(monkeypatch, dict(CASES["ddpm-device"], image_seeds=[1, 2], sample_width=6))
 
 
 if __name__ == "__main__" and "--write" in sys.argv:

@@ -194,6 +194,12 @@ SIGNATURES = {
     "dd_dev_embed": (C.c_int, [C.c_void_p] + [C.c_int] * 9 + [C.c_void_p] * 7 + [C.c_float] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_time_mlp": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 6 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_vae_gather": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dd_dev_groupnorm": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 6),
+    "dd_dev_softmax_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dd_dev_vae_input": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_void_p, C.c_void_p]),
+    "dd_dev_vae_output": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3),
+    "dd_dev_vae_moments": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7),
+    "dd_dev_cast": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dd_dev_final": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_final_args), C.c_void_p]),
     "dd_dev_final_seeded": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_final_args), C.c_void_p, C.c_int, C.c_void_p]),
     "dd_dev_poison_workspaces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,5 +1,5 @@
 // The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_block_tail, dd_dev_block_tail_frag, dd_dev_qkv_attention, dd_dev_qkv_attention_rows, dd_dev_qkv_attention_frag, dd_dev_v_identity, dd_dev_v_copy, dd_dev_head_dec, dd_dev_gemm,
-// dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather, dd_dev_final): test scaffolding, not product.  Each one owns its host operands, device buffers, canaries and
+// dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather, dd_dev_groupnorm, dd_dev_softmax_rows, dd_dev_vae_input, dd_dev_vae_output, dd_dev_vae_moments, dd_dev_cast, dd_dev_final): test scaffolding, not product.  Each one owns its host operands, device buffers, canaries and
 // downloads, and nothing of the launch: the weight images come from finalize's packers and the launch arguments from the model's builders (launch_args.h:
 // dd_dev_mlp and dd_dev_block_tail* run block_tail_plan / block_tail_finish exactly as Backbone::block_tail does), then `iters` further launch sequences
 // are timed.  Buffers, transfers, timing and HIP errors go through one DevScope (dev_scope.h); of the context it reads num_cus and dev_flags (engine_state.h).
@@ -591,21 +591,27 @@ int dd_dev_time_mlp(dd_ctx* c, int B, int D, int L, int extras, int normalize, c
 int dd_dev_vae_gather(dd_ctx* c, int kind, int precision, int B, int H, int W, int Cn, const void* src_host, void* dst_host, size_t dst_bytes,
                       void* stream) {
     const bool bf = precision == DD_PREC_BF16;
-    if (!c || (!bf && precision != DD_PREC_FP32) || (kind != 0 && kind != 1) || B < 1 || H < 1 || W < 1 || !src_host || !dst_host) return DD_ERR_INVALID;
+    if (!c || (!bf && precision != DD_PREC_FP32) || kind < 0 || kind > 3 || B < 1 || H < 1 || W < 1 || !src_host || !dst_host) return DD_ERR_INVALID;
+    if (kind == 3 && (H % 2 || W % 2)) return DD_ERR_INVALID;            // the 2x upsample of a whole source pixel grid
     hipStream_t s = (hipStream_t)stream;
     const size_t esz = bf ? 2 : 4, kt = 128 / esz;
-    const int C = kind == 0 ? Cn : 4;
+    const int C = kind == 1 ? 4 : Cn;
     if (C < 1) return DD_ERR_INVALID;
     const int Kpad = (int)((9 * (size_t)C + kt - 1) / kt * kt);          // as dd_vae_finalize pads a conv's K to the GEMM k-tile
     const size_t rows = (size_t)B * H * W, need = rows * Kpad * esz;
     if (dst_bytes < need) return ctx_fail(c, DD_ERR_INVALID, "vae_gather: dst_bytes below B H W Kpad elements");
-    if (kind == 0 && C % (16 / (int)esz)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "vae_gather: C must fill 16-byte vectors");
+    if (kind != 1 && C % (16 / (int)esz)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "vae_gather: C must fill 16-byte vectors");
     DevScope dev(c);
     void* dD = dev.filled(dst_bytes, 0xFF);
     if (kind == 0) {
         const void* dS = dev.upload((const char*)src_host, rows * 4 * C * esz);
         DEV_HIP(dev, bf ? launch_im2col3x3_s2<bf16_t>((const bf16_t*)dS, (bf16_t*)dD, B, H, W, C, Kpad, s)
                         : launch_im2col3x3_s2<float>((const float*)dS, (float*)dD, B, H, W, C, Kpad, s));
+    } else if (kind >= 2) {
+        const int up = kind == 3;
+        const void* dS = dev.upload((const char*)src_host, (up ? rows / 4 : rows) * C * esz);
+        DEV_HIP(dev, bf ? launch_im2col3x3<bf16_t>((const bf16_t*)dS, (bf16_t*)dD, B, H, W, C, up, Kpad, s)
+                        : launch_im2col3x3<float>((const float*)dS, (float*)dD, B, H, W, C, up, Kpad, s));
     } else {
         const float* dS = dev.upload((const float*)src_host, rows * 3 * 4);
         float* dI = dev.filled<float>(rows * 4 * 4, 0xFF);
@@ -614,6 +620,108 @@ int dd_dev_vae_gather(dd_ctx* c, int kind, int precision, int B, int H, int W, i
     }
     DEV_HIP(dev, hipStreamSynchronize(s));
     dev.download(dst_host, dD, dst_bytes);
+    return dev.status();
+}
+
+// The KL-VAE kernels that are no gather (vae_kernels.hip), each alone: every output and scratch buffer has DD_DEV_VAE_TAIL elements behind the
+// last one the launch may write, holds 0xFF bytes before the launch and is downloaded whole.
+int dd_dev_groupnorm(dd_ctx* c, int precision, int B, int HW, int C, int swish, const float* x_host, const float* gamma, const float* beta,
+                     void* out_host, float* part_host, void* stream) {
+    const bool bf = precision == DD_PREC_BF16;
+    if (!c || (!bf && precision != DD_PREC_FP32) || B < 1 || B > 4096 || HW < 1 || HW > (1 << 20) || C < 1 || C > (1 << 14) ||
+        (long long)B * HW * C > (1ll << 28) || !x_host || !gamma || !beta || !out_host)
+        return DD_ERR_INVALID;
+    if (C % 128 || C > 1024) return ctx_fail(c, DD_ERR_UNSUPPORTED, "groupnorm: C % 128 == 0, C <= 1024");      // what launch_groupnorm refuses
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)B * HW * C, esz = bf ? 2 : 4;
+    const size_t n_part = (size_t)groupnorm_partials(B, HW) + DD_DEV_VAE_TAIL;
+    DevScope dev(c);
+    const float* dX = dev.upload(x_host, n * 4);
+    const float* dG = dev.upload(gamma, (size_t)C * 4);
+    const float* dB = dev.upload(beta, (size_t)C * 4);
+    float* dP = dev.filled<float>(n_part * 4, 0xFF);
+    void* dO = dev.filled((n + DD_DEV_VAE_TAIL) * esz, 0xFF);
+    DEV_HIP(dev, bf ? launch_groupnorm<bf16_t>(dX, dP, dG, dB, (bf16_t*)dO, B, HW, C, swish, s)
+                    : launch_groupnorm<float>(dX, dP, dG, dB, (float*)dO, B, HW, C, swish, s));
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(out_host, dO, (n + DD_DEV_VAE_TAIL) * esz);
+    if (part_host) dev.download(part_host, dP, n_part * 4);
+    return dev.status();
+}
+
+int dd_dev_softmax_rows(dd_ctx* c, int precision, int rows, int n, float scale, const float* s_host, void* p_host, void* stream) {
+    const bool bf = precision == DD_PREC_BF16;
+    if (!c || (!bf && precision != DD_PREC_FP32) || rows < 1 || n < 1 || (long long)rows * n > (1ll << 28) || !s_host || !p_host) return DD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t cnt = (size_t)rows * n, esz = bf ? 2 : 4;
+    DevScope dev(c);
+    const float* dS = dev.upload(s_host, cnt * 4);
+    void* dP = dev.filled((cnt + DD_DEV_VAE_TAIL) * esz, 0xFF);
+    DEV_HIP(dev, bf ? launch_softmax_rows<bf16_t>(dS, (bf16_t*)dP, rows, n, scale, s) : launch_softmax_rows<float>(dS, (float*)dP, rows, n, scale, s));
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(p_host, dP, (cnt + DD_DEV_VAE_TAIL) * esz);
+    return dev.status();
+}
+
+int dd_dev_vae_input(dd_ctx* c, int B, int HW, const float* z_host, const float* w, const float* b, float inv_scale, float* out_host,
+                     void* stream) {
+    if (!c || B < 1 || HW < 1 || (long long)B * HW > (1ll << 26) || !z_host || !w || !b || !out_host) return DD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)B * HW * 4;
+    DevScope dev(c);
+    const float* dZ = dev.upload(z_host, n * 4);
+    const float* dW = dev.upload(w, 16 * 4);
+    const float* dB = dev.upload(b, 4 * 4);
+    float* dO = dev.filled<float>((n + DD_DEV_VAE_TAIL) * 4, 0xFF);
+    DEV_HIP(dev, launch_vae_input(dZ, dW, dB, inv_scale, dO, B, HW, s));
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(out_host, dO, (n + DD_DEV_VAE_TAIL) * 4);
+    return dev.status();
+}
+
+int dd_dev_vae_output(dd_ctx* c, int B, int C, int HW, int ldc, const float* in_host, float* out_host, void* stream) {
+    if (!c || B < 1 || HW < 1 || C < 1 || ldc < C || ldc > 4096 || (long long)B * HW > (1ll << 24) || !in_host || !out_host) return DD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)B * C * HW;
+    DevScope dev(c);
+    const float* dI = dev.upload(in_host, (size_t)B * HW * ldc * 4);
+    float* dO = dev.filled<float>((n + DD_DEV_VAE_TAIL) * 4, 0xFF);
+    DEV_HIP(dev, launch_vae_output(dI, dO, B, C, HW, ldc, s));
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(out_host, dO, (n + DD_DEV_VAE_TAIL) * 4);
+    return dev.status();
+}
+
+int dd_dev_vae_moments(dd_ctx* c, int B, int HW, const float* h_host, const float* w, const float* b, const float* eps_host,
+                       float* moments_host, float* z_host, void* stream) {
+    if (!c || B < 1 || HW < 1 || (long long)B * HW > (1ll << 26) || !h_host || !w || !b || (!moments_host && !z_host)) return DD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t px = (size_t)B * HW;
+    DevScope dev(c);
+    const float* dH = dev.upload(h_host, px * 8 * 4);
+    const float* dW = dev.upload(w, 64 * 4);
+    const float* dB = dev.upload(b, 8 * 4);
+    const float* dE = eps_host ? dev.upload(eps_host, px * 4 * 4) : nullptr;
+    float* dM = moments_host ? dev.filled<float>((px * 8 + DD_DEV_VAE_TAIL) * 4, 0xFF) : nullptr;
+    float* dZ = z_host ? dev.filled<float>((px * 4 + DD_DEV_VAE_TAIL) * 4, 0xFF) : nullptr;
+    DEV_HIP(dev, launch_vae_moments(dH, dW, dB, dE, dM, dZ, B, HW, s));
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    if (moments_host) dev.download(moments_host, dM, (px * 8 + DD_DEV_VAE_TAIL) * 4);
+    if (z_host) dev.download(z_host, dZ, (px * 4 + DD_DEV_VAE_TAIL) * 4);
+    return dev.status();
+}
+
+int dd_dev_cast(dd_ctx* c, int precision, long long n, const float* x_host, void* out_host, void* stream) {
+    const bool bf = precision == DD_PREC_BF16;
+    if (!c || (!bf && precision != DD_PREC_FP32) || n < 1 || n > (1ll << 28) || !x_host || !out_host) return DD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t esz = bf ? 2 : 4;
+    DevScope dev(c);
+    const float* dX = dev.upload(x_host, (size_t)n * 4);
+    void* dO = dev.filled(((size_t)n + DD_DEV_VAE_TAIL) * esz, 0xFF);
+    DEV_HIP(dev, bf ? launch_cast<bf16_t>(dX, (bf16_t*)dO, n, s) : launch_cast<float>(dX, (float*)dO, n, s));
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(out_host, dO, ((size_t)n + DD_DEV_VAE_TAIL) * esz);
     return dev.status();
 }
 

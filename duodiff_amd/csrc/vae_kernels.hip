@@ -51,7 +51,7 @@ template <typename T>
 __global__ void im2col3x3_kernel(const T* __restrict__ src, T* __restrict__ dst, int B, int H, int W, int C, int up,
                                  int Kpad) {
     constexpr int V = 16 / (int)sizeof(T);
-    const int cv = C / V;                       // vectors per pixel (C % V == 0), or 1 for the C = 4 input conv
+    const int cv = C / V;                       // vectors per pixel (C % V == 0: the launcher refuses anything else)
     const long long per_row = (long long)Kpad / V;
     const long long total = (long long)B * H * W * per_row;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -175,10 +175,14 @@ __global__ void im2col3x3_c4_kernel(const float* __restrict__ src, T* __restrict
 }
 
 // GroupNorm(32 groups, eps 1e-6) in three deterministic passes over the NHWC fp32 stream:
-//   gn_stats    one workgroup per (image, chunk of kGnChunk pixels): per-group (sum, sum of squares) partials, fp32,
+//   gn_stats    one workgroup per (image, chunk of kGnChunk pixels): per-group (sum, sum of squares) partials of d = x - pivot, fp32,
 //               16-byte loads (a float4 = 4 channels of one group since C/32 >= 4), fixed-order LDS reduction;
-//   gn_finalize one thread per (image, group): partials combined in double -> (mean, rstd);
+//   gn_finalize one thread per (image, group): partials combined in double -> (mean, rstd) = (pivot + s / n, q / n - (s / n)^2);
 //   gn_apply    y = swish?((x - mean) * rstd * gamma + beta) -> T, 16-byte loads.
+// The pivot of an (image, group) is the group's first channel at the image's first pixel: a value of the group itself, so d is of the
+// order of the group's spread and q / n - (s / n)^2 does not cancel however far the group's mean lies from zero (the sums of x and x^2
+// lose (mean / std)^2 ulps in fp32, which the double of the finalize cannot give back); a constant group has d = 0 and var = 0 exactly.
+// It depends on the image alone, as every partial does: an image normalises the same in any batch.
 constexpr int kGnChunk = 256;
 __global__ void __launch_bounds__(256) gn_stats_kernel(const float* __restrict__ x, float* __restrict__ part, int HW,
                                                        int C, int chunks) {
@@ -188,10 +192,12 @@ __global__ void __launch_bounds__(256) gn_stats_kernel(const float* __restrict__
     const int rows = 256 / c4;                   // pixels covered per pass
     const int col = threadIdx.x % c4, r0 = threadIdx.x / c4;
     const int p0 = ch * kGnChunk, p1 = min(HW, p0 + kGnChunk);
-    const f32x4* xp = reinterpret_cast<const f32x4*>(x + (long long)bi * HW * C) + col;
+    const float* xi = x + (long long)bi * HW * C;
+    const float pv = xi[(col / (c4 >> 5)) * (C >> 5)];      // the pivot of this column's group
+    const f32x4* xp = reinterpret_cast<const f32x4*>(xi) + col;
     f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
     for (int p = p0 + r0; p < p1; p += rows) {
-        const f32x4 v = xp[(long long)p * c4];
+        const f32x4 v = xp[(long long)p * c4] - pv;
         s += v;
         q += v * v;
     }
@@ -213,8 +219,8 @@ __global__ void __launch_bounds__(256) gn_stats_kernel(const float* __restrict__
     }
 }
 
-__global__ void gn_finalize_kernel(const float* __restrict__ part, float* __restrict__ stat, int n_img_groups, int chunks,
-                                   double count) {
+__global__ void gn_finalize_kernel(const float* __restrict__ x, const float* __restrict__ part, float* __restrict__ stat,
+                                   int n_img_groups, int chunks, int HW, int C, double count) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;   // (image, group)
     if (i >= n_img_groups) return;
     const int bi = i >> 5, g = i & 31;
@@ -224,10 +230,10 @@ __global__ void gn_finalize_kernel(const float* __restrict__ part, float* __rest
         s += o[0];
         q += o[1];
     }
-    const double mean = s / count;
-    double var = q / count - mean * mean;
+    const double ds = s / count;                           // mean - pivot
+    double var = q / count - ds * ds;
     var = var > 0.0 ? var : 0.0;
-    stat[2 * i] = (float)mean;
+    stat[2 * i] = (float)((double)x[(long long)bi * HW * C + g * (C >> 5)] + ds);
     stat[2 * i + 1] = (float)(1.0 / sqrt(var + 1e-6));
 }
 
@@ -342,8 +348,8 @@ hipError_t launch_groupnorm(const float* x, float* part, const float* gamma, con
     const int chunks = (HW + kGnChunk - 1) / kGnChunk;
     hipLaunchKernelGGL(gn_stats_kernel, dim3(B * chunks), dim3(256), 0, s, x, part, HW, C, chunks);
     float* stat = part + (long long)B * chunks * 64;      // (mean, rstd) per (image, group) behind the partials
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3((B * 32 + 255) / 256), dim3(256), 0, s, part, stat, B * 32, chunks,
-                       (double)HW * (C / 32));
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3((B * 32 + 255) / 256), dim3(256), 0, s, x, part, stat, B * 32, chunks,
+                       HW, C, (double)HW * (C / 32));
     const long long total4 = (long long)B * HW * (C / 4);
     hipLaunchKernelGGL(gn_apply_kernel<T>, grid1d(total4), dim3(256), 0, s, x, stat, gamma, beta, out, HW, C, swish, total4);
     return hipGetLastError();

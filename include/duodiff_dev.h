@@ -197,10 +197,39 @@ int dd_dev_time_mlp(dd_ctx* ctx, int B, int D, int L, int extras, int normalize,
  *         dst rows = the B H W output pixels, Kpad columns in order (ky, kx, c), columns [9 C, Kpad) zero.
  * kind 1: the encoder's input path (launch_vae_image + launch_im2col3x3_c4): src_host = NCHW fp32 [B, 3, H, W], C is ignored;
  *         dst rows = the B H W pixels, Kpad columns (ky, kx, c of 4) with c = 3 and columns [36, Kpad) zero.
+ * kind 2: the 3x3 / pad 1 im2col of the decoder and encoder convolutions (launch_im2col3x3, up = 0): src_host = NHWC [B, H, W, C] elements
+ *         of `precision`; rows, columns and padding as kind 0.
+ * kind 3: the same through the nearest-2x upsample (up = 1): src_host = NHWC [B, H / 2, W / 2, C], H and W even (else DD_ERR_INVALID).
+ * Kpad = 9 C (36 for kind 1) rounded up to the GEMM k-tile of 128 bytes (64 bf16 / 32 fp32 elements), as dd_vae_finalize pads it.
  * dst_host holds dst_bytes >= B H W Kpad elements of `precision`; it is filled with 0xFF bytes before the launch and comes back WHOLE, so
- * the bytes behind the last row keep the canary.  A shape the launcher refuses is DD_ERR_UNSUPPORTED; nothing is launched. */
+ * the bytes behind the last row keep the canary.  A shape the launcher refuses (kinds 0, 2, 3: C does not fill 16-byte vectors) is
+ * DD_ERR_UNSUPPORTED; nothing is launched. */
 int dd_dev_vae_gather(dd_ctx* ctx, int kind, int precision, int B, int H, int W, int C, const void* src_host, void* dst_host,
                       size_t dst_bytes, void* stream);
+
+/* Development harnesses for the other kernels of the KL-VAE (vae_kernels.hip), each through its production launch_* function on host arrays.
+ * Every output (and the GroupNorm scratch) has DD_DEV_VAE_TAIL elements behind the last one the launch may write; the whole buffer is filled
+ * with 0xFF bytes before the launch and comes back WHOLE.  Arguments are checked before anything touches the GPU (DD_ERR_INVALID); a shape
+ * the launcher refuses is DD_ERR_UNSUPPORTED and nothing is launched.
+ * dd_dev_groupnorm: launch_groupnorm (statistics, finalize, apply): GroupNorm(32 groups, eps 1e-6) [+ x sigmoid(x)] of x_host [B HW, C] fp32
+ *   (NHWC) with gamma, beta [C] -> out_host [B HW C + TAIL] of `precision`.  part_host (or NULL): the launch's scratch,
+ *   B ceil(HW / 256) 64 + B 64 + TAIL floats (per-chunk partial sums, then (mean, rstd) per (image, group)).  C % 128 != 0 or C > 1024 is refused.
+ * dd_dev_softmax_rows: launch_softmax_rows: p = softmax(scale s) over the last dimension of s_host [rows, n] fp32 -> p_host [rows n + TAIL].
+ * dd_dev_vae_input: launch_vae_input: z_host [B, 4, HW] -> post_quant_conv(inv_scale z) (w [4, 4], b [4]) -> out_host [B HW 4 + TAIL] (NHWC).
+ * dd_dev_vae_output: launch_vae_output: the first C channels of in_host [B HW, ldc] -> out_host [B C HW + TAIL] (NCHW).
+ * dd_dev_vae_moments: launch_vae_moments: h_host [B HW, 8] -> quant_conv (w [8, 8], b [8]) -> moments_host [B 8 HW + TAIL] (NCHW) and / or
+ *   z_host [B 4 HW + TAIL] = the posterior sample under eps_host [B, 4, HW] (NULL: the mode); either output may be NULL, not both.
+ * dd_dev_cast: launch_cast: x_host [n] fp32 -> out_host [n + TAIL] of `precision`. */
+#define DD_DEV_VAE_TAIL 64
+int dd_dev_groupnorm(dd_ctx* ctx, int precision, int B, int HW, int C, int swish, const float* x_host, const float* gamma, const float* beta,
+                     void* out_host, float* part_host, void* stream);
+int dd_dev_softmax_rows(dd_ctx* ctx, int precision, int rows, int n, float scale, const float* s_host, void* p_host, void* stream);
+int dd_dev_vae_input(dd_ctx* ctx, int B, int HW, const float* z_host, const float* w, const float* b, float inv_scale, float* out_host,
+                     void* stream);
+int dd_dev_vae_output(dd_ctx* ctx, int B, int C, int HW, int ldc, const float* in_host, float* out_host, void* stream);
+int dd_dev_vae_moments(dd_ctx* ctx, int B, int HW, const float* h_host, const float* w, const float* b, const float* eps_host,
+                       float* moments_host, float* z_host, void* stream);
+int dd_dev_cast(dd_ctx* ctx, int precision, long long n, const float* x_host, void* out_host, void* stream);
 
 /* Development harness for the launch that ends every sampling step and every forward (step.hip final_tiled_kernel through launch_final:
  * unpatchify, the 3x3 conv, guidance, the step update of step_update.h): ONE launch, from a FinalArgs filled the way forward.hip fills it.

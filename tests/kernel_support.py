@@ -1,6 +1,7 @@
 """What the per-element kernel tests share (test_attention, test_block_tail, test_frag_handoff, test_gemm_path, test_row_kernels,
 test_qkv_attention, test_mlp_fused, test_pag, test_head_dec): bf16 arithmetic on the host, the elementwise gate, the constants of the bounds,
-the LayerNorm bound of the GEMM-path tests and the MFMA fragment order.  tests/test_kernel_support.py (CPU) pins every piece of it."""
+the LayerNorm bound of the GEMM-path tests, the MFMA fragment order, the references of the output head + step launch (test_final_step) and
+of the KL-VAE kernels (test_vae_kernels).  tests/test_kernel_support.py (CPU) pins every piece of it."""
 import numpy as np
 
 from duodiff_amd import _lib
@@ -352,3 +353,332 @@ PHILOX_CASES = [
     dict(S=32, B=3, C=4, b0=5, seed=(7 << 32) | 0x9ABCDEF1, ctr=941, z2=True),
     dict(S=64, B=1, C=3, b0=(1 << 20) + 5, seed=(1 << 63) | 0x55, ctr=3, z2=False),
 ]
+
+
+# ---------------------------------------------------------------------------------------------------------------- the KL-VAE kernels
+# What tests/test_vae_kernels.py (GPU, through dd_dev_vae_gather, dd_dev_groupnorm, dd_dev_softmax_rows, dd_dev_vae_input / _output /
+# _moments and dd_dev_cast) compares csrc/vae_kernels.hip with: float64 restatements (index arithmetic for the gathers), the inputs of
+# every case, and the derived bounds.  The switches (`mutant=`) are the deliberate errors that the CPU tests of tests/test_kernel_support.py
+# prove those inputs can see.
+VAE_TAIL = 64                  # DD_DEV_VAE_TAIL: canary elements behind every output
+VAE_SCALE = 0.18215
+GATHER_C = (8, 128)
+# (kind, B, H, W): kind 2 = 3x3 im2col, kind 3 = the same through the nearest-2x upsample (H, W: the convolution's size)
+GATHER_SHAPES = [(2, 1, 1, 1), (2, 3, 2, 2), (3, 3, 2, 2), (2, 2, 4, 6), (3, 2, 4, 6), (3, 2, 6, 4)]
+
+
+def vae_kpad(C, prec):
+    """9 C rounded up to the GEMM k-tile (128 bytes of elements), as dd_vae_finalize pads a conv's K"""
+    return round_up(9 * C, 64 if prec == "bf16" else 32)
+
+
+def gather_input(kind, B, H, W, C):
+    """the source of a gather case, exact in bf16: [B, H, W, C], or [B, H / 2, W / 2, C] for the upsample"""
+    r = np.random.default_rng(10000 * kind + 1000 * B + 100 * H + 10 * W + C)
+    s = 2 if kind == 3 else 1
+    return r.integers(-64, 64, (B, H // s, W // s, C)).astype(F32) / 8.0
+
+
+def im2col3x3_ref(src, up, kpad, mutant=None):
+    """rows [B H W, kpad] of the 3x3 / pad 1 im2col over NHWC src, columns (ky, kx, c), [9 C, kpad) zero; up: through np.repeat by 2.
+    mutant: "taps" (ky, kx transposed), "half_x" (the upsample's / 2 dropped along x: column x reads source column min(x, Ws - 1)),
+    "edge" (a pad tap reads the clamped edge pixel instead of zero)"""
+    src = np.asarray(src)
+    img = src
+    if up:
+        img = np.repeat(src, 2, axis=1)
+        img = np.repeat(img, 2, axis=2) if mutant != "half_x" else img[:, :, np.minimum(np.arange(2 * src.shape[2]), src.shape[2] - 1)]
+    B, H, W, C = img.shape
+    padded = np.pad(img, ((0, 0), (1, 1), (1, 1), (0, 0)), mode="edge" if mutant == "edge" else "constant")
+    out = np.zeros((B, H, W, kpad), src.dtype)
+    for ky in range(3):
+        for kx in range(3):
+            t = kx * 3 + ky if mutant == "taps" else ky * 3 + kx
+            out[..., t * C:(t + 1) * C] = padded[:, ky:ky + H, kx:kx + W]
+    return out.reshape(B * H * W, kpad)
+
+
+# ---- GroupNorm(32, eps 1e-6) [+ swish] over NHWC rows x [B HW, C]
+GN_SHAPES = [(2, 64, 128), (2, 9, 256), (3, 300, 512), (2, 576, 128), (1, 64, 384)]      # (B, HW, C)
+GN_PAIRS = [(0.0, 1.0), (10.0, 1.0), (100.0, 1.0), (30.0, 0.1)]                           # (mean, std) of an (image, group)
+GN_MARGIN = 8.0                # an fp32 kernel against torch's fp32 group_norm: summation order and expf (as test_encode_moments_fp32)
+
+
+def gn_pair_index(B, C):
+    """[B, C]: which of GN_PAIRS a channel's group has in an image; rotated by the image, so a cross-image mix-up shows"""
+    g = np.arange(C) // (C // 32)
+    return (g[None, :] + np.arange(B)[:, None]) % len(GN_PAIRS)
+
+
+def gn_inputs(B, HW, C, const=False):
+    """x [B HW, C] fp32, gamma, beta.  const: (image 0, group 7) holds 123.456 and (image B - 1, group 5) holds 0.1 everywhere"""
+    r = np.random.default_rng(100000 * B + 100 * HW + C + (1 if const else 0))
+    k = gn_pair_index(B, C)
+    mean, std = np.array(GN_PAIRS)[k, 0], np.array(GN_PAIRS)[k, 1]
+    x = (mean[:, None, :] + std[:, None, :] * r.standard_normal((B, HW, C))).astype(F32)
+    if const:
+        cpg = C // 32
+        x[0, :, 7 * cpg:8 * cpg] = F32(123.456)
+        x[B - 1, :, 5 * cpg:6 * cpg] = F32(0.1)
+    gamma = (1.0 + 0.5 * r.standard_normal(C)).astype(F32)
+    beta = r.standard_normal(C).astype(F32)
+    return x.reshape(B * HW, C), gamma, beta
+
+
+def _swish(y):
+    with np.errstate(over="ignore"):
+        return y / (1.0 + np.exp(-y))
+
+
+def groupnorm_ref(x, gamma, beta, B, HW, C, swish, mutant=None):
+    """float64 GroupNorm(32 groups over C / 32 consecutive channels, biased variance, eps 1e-6) * gamma + beta [-> y sigmoid(y)].
+    mutant: "group_map" (a channel's group taken as its float4 column, (c // 4) % 32: right at C = 128 only), "drop_tail" (the partial last
+    256-pixel chunk left out of the element count)"""
+    x64 = np.asarray(x, np.float64).reshape(B, HW, C)
+    gid = (np.arange(C) // 4) % 32 if mutant == "group_map" else np.arange(C) // (C // 32)
+    hw_n = HW // 256 * 256 if mutant == "drop_tail" and HW > 256 else HW
+    y = np.empty_like(x64)
+    for g in range(32):
+        m = gid == g
+        xg = x64[:, :, m]
+        n = float(hw_n * m.sum())
+        mean = xg.sum((1, 2), keepdims=True) / n
+        var = np.maximum((xg * xg).sum((1, 2), keepdims=True) / n - mean * mean, 0.0) if mutant == "drop_tail" else xg.var((1, 2), keepdims=True)
+        y[:, :, m] = (xg - mean) / np.sqrt(var + 1e-6)
+    y = y * np.asarray(gamma, np.float64) + np.asarray(beta, np.float64)
+    return (_swish(y) if swish else y).reshape(B * HW, C)
+
+
+def groupnorm_torch(x, gamma, beta, B, HW, C, swish, dtype):
+    """torch's F.group_norm (+ F.silu) on the CPU in `dtype` -> float64 rows [B HW, C]"""
+    import torch
+    import torch.nn.functional as TF
+    t = torch.from_numpy(np.ascontiguousarray(np.asarray(x).reshape(B, HW, C).transpose(0, 2, 1))).to(dtype).reshape(B, C, HW, 1).contiguous()
+    y = TF.group_norm(t, 32, torch.from_numpy(gamma).to(dtype), torch.from_numpy(beta).to(dtype), eps=1e-6)
+    y = TF.silu(y) if swish else y
+    return y.reshape(B, C, HW).permute(0, 2, 1).reshape(B * HW, C).to(torch.float64).numpy()
+
+
+def groupnorm_emulated(x, gamma, beta, B, HW, C, swish, pivot):
+    """the three kernels in numpy float32, in their summation order: per 256-pixel chunk every thread adds its pixels in turn, the four lanes
+    of a float4 pair up, one thread per group adds the chunk's columns in turn; the chunks are combined in double; apply in float32.
+    pivot False: the sums of x and x^2 (the one-pass formula q / n - mean^2).  pivot True: the sums of d and d^2, d = x - the group's first
+    channel at the image's first pixel, mean = pivot + s / n, var = q / n - (s / n)^2."""
+    x3 = np.asarray(x, F32).reshape(B, HW, C)
+    c4, cpg = C // 4, C // 32
+    rows, w = 256 // c4, c4 // 32
+    chunks = (HW + 255) // 256
+    S, Q = np.zeros((B, 32)), np.zeros((B, 32))
+    pv = x3[:, 0, ::cpg].copy() if pivot else np.zeros((B, 32), F32)                     # [B, 32]
+    for ch in range(chunks):
+        xc = x3[:, ch * 256:min(HW, ch * 256 + 256)] - np.repeat(pv, cpg, axis=1)[:, None, :]
+        xc = xc.astype(F32).reshape(B, -1, c4, 4)
+        s, q = np.zeros((B, rows, c4, 4), F32), np.zeros((B, rows, c4, 4), F32)
+        for k in range(0, xc.shape[1], rows):
+            v = xc[:, k:k + rows]
+            s[:, :v.shape[1]] += v
+            q[:, :v.shape[1]] += v * v
+        ss, sq = (s[..., 0] + s[..., 1]) + (s[..., 2] + s[..., 3]), (q[..., 0] + q[..., 1]) + (q[..., 2] + q[..., 3])      # [B, rows, c4]
+        a, b2 = np.zeros((B, 32), F32), np.zeros((B, 32), F32)
+        for r in range(rows):
+            for k in range(w):
+                a += ss[:, r, k::w]
+                b2 += sq[:, r, k::w]
+        S += a
+        Q += b2
+    n = float(HW * cpg)
+    ds = S / n
+    mean = (pv.astype(np.float64) + ds).astype(F32)
+    rstd = (1.0 / np.sqrt(np.maximum(Q / n - ds * ds, 0.0) + 1e-6)).astype(F32)
+    t = (x3 - np.repeat(mean, cpg, axis=1)[:, None, :]) * np.repeat(rstd, cpg, axis=1)[:, None, :] * np.asarray(gamma, F32) + np.asarray(beta, F32)
+    t = t.astype(F32)
+    if swish:
+        t = (t / (F32(1.0) + np.exp(-t, dtype=F32))).astype(F32)
+    return t.reshape(B * HW, C)
+
+
+_gn_cache = {}
+
+
+def gn_case(B, HW, C, swish, const=False):
+    """dict of a GroupNorm case, computed once: the inputs, want (torch float64), e32 [B HW, C] = per element the largest error of torch's
+    fp32 group_norm (+ silu) against float64 among the elements of the case whose (image, group) has the same (mean, std) pair, and
+    e32_case, the largest over the case.  A quantity of the reference alone."""
+    key = (B, HW, C, bool(swish), const)
+    if key not in _gn_cache:
+        import torch
+        x, gamma, beta = gn_inputs(B, HW, C, const)
+        want = groupnorm_torch(x, gamma, beta, B, HW, C, swish, torch.float64)
+        e = np.abs(groupnorm_torch(x, gamma, beta, B, HW, C, swish, torch.float32) - want)
+        cls = np.broadcast_to(gn_pair_index(B, C)[:, None, :], (B, HW, C)).reshape(B * HW, C)
+        e32 = np.zeros_like(want)
+        for k in range(len(GN_PAIRS)):
+            e32[cls == k] = e[cls == k].max()
+        _gn_cache[key] = dict(x=x, gamma=gamma, beta=beta, want=want, e32=e32, e32_case=float(e.max()), cls=cls)
+    return _gn_cache[key]
+
+
+def gn_tol(case, prec):
+    """fp32: 8 e32; bf16: one ulp of the result + 8 e32.  e32 is taken per (mean, std) pair, never above the case's own e32"""
+    t = GN_MARGIN * case["e32"]
+    return t + ulp_bf16(case["want"]) if prec == "bf16" else t
+
+
+# ---- softmax over rows
+SOFTMAX_SHAPES = [(1, 64), (5, 64), (6, 576), (3, 1024), (7, 100), (2, 1)]      # (rows, n)
+SOFTMAX_SCALE = F32(1.0 / np.sqrt(512.0))
+
+
+def softmax_inputs(rows, n):
+    """scores [rows, n] fp32; row i is of kind i % 4: Gaussian of std 40; one dominant entry in the last column, the rest underflowing;
+    constant; a permutation of a ramp whose scaled values reach +-80"""
+    r = np.random.default_rng(1000 * rows + n)
+    s = (40.0 * r.standard_normal((rows, n))).astype(F32)
+    for i in range(rows):
+        if i % 4 == 1:
+            s[i, -1] = 4000.0
+        elif i % 4 == 2:
+            s[i] = 7.3
+        elif i % 4 == 3:
+            s[i] = r.permutation(np.linspace(-80.0, 80.0, n) / float(SOFTMAX_SCALE)).astype(F32)
+    return s
+
+
+def softmax_ref(s, scale, prec="fp32", mutant=None):
+    """(p, tol): softmax(a) in float64, a = s * scale formed in float64 from the fp32 operands, and the elementwise bound.
+    Derivation (u = 2^-24).  The kernel forms t_j = fl(s_j scale), d_j = fl(t_j - mx) and e_j = expf(d_j); softmax does not change under a
+    common shift, so mx's own error cancels and the argument is off by at most u |a_j| + u |d_j| <= 2 u (|a_j| + |a_max|); expf is allowed
+    4 ulp: e_j has relative error E_j u, E_j = 2 (|a_j| + |a_max|) + 4.  The sum adds ceil(n / 64) terms per lane and 6 shuffle levels, one
+    rounding each, and inherits the terms' errors weighted by p: relative error (sum_k p_k E_k + ceil(n / 64) + 6) u.  1 / sum and the
+    product round once each.  Second-order terms: x 1.01.  A flushed denormal (an expf below 2^-126, times 1 / sum <= 1): + 2^-126.
+    bf16 output: + one bf16 ulp.  mutant: "no_scale" (a = s), "drop_tail" (the elements behind the last whole 64 left out of the sum)"""
+    a = np.asarray(s, np.float64) * (1.0 if mutant == "no_scale" else float(F32(scale)))
+    amax = a.max(-1, keepdims=True)
+    e = np.exp(a - amax)
+    n = a.shape[-1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = e / (e[:, :n // 64 * 64] if mutant == "drop_tail" else e).sum(-1, keepdims=True)
+    E = 2.0 * (np.abs(a) + np.abs(amax)) + 4.0
+    tol = 1.01 * p * U24 * (E + (p * E).sum(-1, keepdims=True) + -(-n // 64) + 6 + 2) + 2.0 ** -126
+    return p, tol + ulp_bf16(p) if prec == "bf16" else tol
+
+
+# ---- the point-wise kernels
+def fma_chain64(v, w, b, n_extra=0):
+    """(y, tol): y[..., o] = b[o] + sum_c w[o, c] v[..., c] in float64 and the bound of an fmaf chain of n = w.shape[1] terms started on
+    the bias: term c passes through n - c roundings and the bias through n, so |error| <= n u (|b| + sum |w| |v|) to first order;
+    (n + 3) u covers the higher orders (gamma_n <= (n + 3) u here) with room; n_extra: roundings the operands v already carry"""
+    v, w, b = np.asarray(v, np.float64), np.asarray(w, np.float64), np.asarray(b, np.float64)
+    y = v @ w.T + b
+    mag = np.abs(v) @ np.abs(w).T + np.abs(b)
+    return y, (w.shape[1] + 3 + n_extra) * U24 * mag
+
+
+VAE_INPUT_SHAPES = [(3, 5), (2, 300)]      # (B, HW)
+
+
+def vae_input_case(B, HW):
+    r = np.random.default_rng(10 * HW + B)
+    return dict(B=B, HW=HW, z=r.standard_normal((B, 4, HW)).astype(F32), w=r.standard_normal((4, 4)).astype(F32),
+                b=r.standard_normal(4).astype(F32), inv_scale=F32(1.0 / VAE_SCALE))
+
+
+def vae_input_ref(z, w, b, inv_scale, mutant=None):
+    """(out [B HW, 4], tol): post_quant_conv(inv_scale z) in float64, inv_scale at its fp32 value; z inv_scale rounds once before the chain.
+    mutant: "w_transposed" """
+    v = np.asarray(z, np.float64).transpose(0, 2, 1).reshape(-1, 4) * float(F32(inv_scale))
+    return fma_chain64(v, np.asarray(w).T if mutant == "w_transposed" else w, b, n_extra=1)
+
+
+def vae_output_ref(inp, B, C, HW, ldc):
+    """NHWC rows [B HW, ldc] -> NCHW [B, C, HW] of the first C channels"""
+    return np.ascontiguousarray(np.asarray(inp).reshape(B, HW, ldc)[:, :, :C].transpose(0, 2, 1))
+
+
+VAE_MOMENTS_SHAPES = [(3, 5), (2, 300)]      # (B, HW)
+
+
+def vae_moments_case(B, HW):
+    """h [B HW, 8], w, b, eps: h solves w h + b = target, so the log-variances (channels 4..7) cover [-45, 35]: below -30, above 20, between"""
+    r = np.random.default_rng(100 * HW + B)
+    w = (r.standard_normal((8, 8)) + 2.0 * np.eye(8)).astype(F32)
+    b = r.standard_normal(8).astype(F32)
+    target = np.concatenate([2.0 * r.standard_normal((B * HW, 4)), r.uniform(-45.0, 35.0, (B * HW, 4))], axis=1)
+    target[0, 4:] = (-44.0, -29.0, 19.0, 34.0)
+    h = np.ascontiguousarray(np.linalg.solve(w.astype(np.float64), (target - b).T).T, F32)
+    return dict(B=B, HW=HW, h=h, w=w, b=b, eps=r.standard_normal((B, 4, HW)).astype(F32))
+
+
+def vae_moments_ref(h, w, b, eps, B, HW, mutant=None):
+    """(moments [B, 8, HW], tol_m, z [B, 4, HW], tol_z) in float64: quant_conv as an fmaf chain of 8 terms, then
+    z = SCALE (mean + exp(0.5 clamp(logvar, -30, 20)) eps), or SCALE mean without eps (the mode).
+    The bound of z: the sample's own arithmetic on the kernel's fp32 moments is within 4 u SCALE (|mean| + std |eps|) (the rounding of
+    std eps, of the sum, of the product with SCALE, the correctly rounded exp and the fp32 value of SCALE: _sample_bound of
+    tests/test_vae_encode.py); the moments' errors dm arrive through dz = SCALE (dmean + 1/2 std |eps| dlogvar) (the clamp has slope <= 1;
+    exp(x / 2) has derivative std / 2; x 1.001 for the second order).
+    mutant: "w_transposed", "no_clamp", "logvar_from_mean" (z takes its log-variance from the mean channels)"""
+    m, tol_m = fma_chain64(h, np.asarray(w).T if mutant == "w_transposed" else w, b)
+    m = m.reshape(B, HW, 8).transpose(0, 2, 1)
+    tol_m = tol_m.reshape(B, HW, 8).transpose(0, 2, 1)
+    mean, lv = m[:, :4], (m[:, :4] if mutant == "logvar_from_mean" else m[:, 4:])
+    scale = float(F32(VAE_SCALE))
+    if eps is None:
+        return m, tol_m, scale * mean, 4 * U24 * scale * np.abs(mean) + 1.001 * scale * tol_m[:, :4]
+    ae = np.abs(np.asarray(eps, np.float64))
+    std = np.exp(0.5 * (lv if mutant == "no_clamp" else np.clip(lv, -30.0, 20.0)))
+    z = scale * (mean + std * np.asarray(eps, np.float64))
+    tol_z = 4 * U24 * scale * (np.abs(mean) + std * ae) + 1.001 * scale * (tol_m[:, :4] + 0.5 * std * ae * tol_m[:, 4:])
+    return m, tol_m, z, tol_z
+
+
+def cast_inputs():
+    """fp32 values for the cast: normals over 2^+-20; exact round-to-even ties (low half 0x8000) above even and odd upper halves of both
+    signs, and their neighbours one fp32 ulp either side; +-0.  The count is no multiple of 256."""
+    r = np.random.default_rng(3)
+    normals = (r.standard_normal(1000) * 2.0 ** r.integers(-20, 21, 1000)).astype(F32)
+    hi = np.concatenate([np.arange(0x3500, 0x3600), np.arange(0x4900, 0x4A00)]).astype(np.uint32)      # exponents 2^-21.. and 2^19..
+    ties = (np.concatenate([hi, hi | 0x8000]) << 16) | 0x8000
+    x = np.concatenate([normals, np.concatenate([ties, ties - 1, ties + 1, np.array([0, 0x80000000], np.uint32)]).view(F32)])
+    assert x.size % 256 != 0
+    return x
+
+
+# ---- the GPU calls (tests marked gpu only)
+def _prec(prec):
+    return (PREC_BF16, np.uint16) if prec == "bf16" else (PREC_FP32, F32)
+
+
+def vae_gather(kind, prec, B, H, W, C, src):
+    """dd_dev_vae_gather -> (rows [B H W + 64, kpad] of bf16 bits / fp32, kpad); src fp32, exact in bf16"""
+    c = ctx()
+    code, dt = _prec(prec)
+    kpad = vae_kpad(4 if kind == 1 else C, prec)
+    rows = B * H * W
+    dst = np.zeros((rows + VAE_TAIL) * kpad, dt)
+    src = np.ascontiguousarray(src, F32)
+    src = bf16_bits(src) if prec == "bf16" and kind != 1 else src
+    c.check(c.lib.dd_dev_vae_gather(c.handle, kind, code, B, H, W, C, P(src), P(dst), dst.nbytes, None))
+    return dst.reshape(rows + VAE_TAIL, kpad), kpad
+
+
+def run_groupnorm(prec, B, HW, C, swish, x, gamma, beta):
+    """dd_dev_groupnorm -> (out [B HW C + TAIL] as float64 values of the bf16 bits / fp32, the raw output, the scratch)"""
+    c = ctx()
+    code, dt = _prec(prec)
+    out = np.zeros(B * HW * C + VAE_TAIL, dt)
+    part = np.zeros(B * ((HW + 255) // 256) * 64 + B * 64 + VAE_TAIL, F32)
+    c.check(c.lib.dd_dev_groupnorm(c.handle, code, B, HW, C, int(swish), P(np.ascontiguousarray(x, F32)), P(gamma), P(beta), P(out), P(part), None))
+    return out, part
+
+
+def run_softmax(prec, rows, n, scale, s):
+    c = ctx()
+    code, dt = _prec(prec)
+    out = np.zeros(rows * n + VAE_TAIL, dt)
+    c.check(c.lib.dd_dev_softmax_rows(c.handle, code, rows, n, float(scale), P(np.ascontiguousarray(s, F32)), P(out), None))
+    return out
+
+
+def values(out, prec):
+    """the fp32 values of an output buffer (bf16 bits or fp32)"""
+    return from_bf16_bits(out) if prec == "bf16" else out

@@ -3,7 +3,9 @@ the bf16 ulp, the gate's predicate at and around its bound, and the two fragment
 formulas in include/duodiff_dev.h (dd_dev_block_tail_frag); and the references of the output head + step launch (tests/test_final_step.py):
 the float64 head against torch's conv2d on a rearrange written out index by index, the float32 restatement of step_update.h against a
 scalar evaluation with explicit roundings, Philox4x32-10 against the published Random123 vectors, the Box-Muller reference against a scalar
-one, and -- on the very inputs the GPU tests use -- that each deliberate error of the reference exceeds the bound the kernel is held to."""
+one, and -- on the very inputs the GPU tests use -- that each deliberate error of the reference exceeds the bound the kernel is held to; the
+references of the KL-VAE kernels (tests/test_vae_kernels.py) against torch in float64 and their deliberate errors likewise, the emulation of
+GroupNorm's one-pass fp32 statistics among them."""
 import math
 
 import numpy as np
@@ -268,3 +270,137 @@ def test_philox_cases_near_one_cap_and_the_transposed_id(case):
                   ks.final_philox_ref(case["seed"], case["B"], case["C"], case["S"], case["b0"] & 0xFFFFF, case["ctr"], stream)[0]
                   if case["b0"] >> 20 else None):
         assert other is None or (np.abs(other - z) > 1e-4).mean() > 0.99
+
+
+# ---------------------------------------------------------------------------------------------------------------- the KL-VAE kernels
+# The references of tests/test_vae_kernels.py against torch in float64, and -- on the very inputs the GPU tests use -- every deliberate error
+# against the bound (or the bit equality) the kernel is held to.
+@pytest.mark.parametrize("C", ks.GATHER_C)
+@pytest.mark.parametrize("kind,B,H,W", ks.GATHER_SHAPES)
+def test_im2col_reference_against_unfold_and_its_mutants(kind, B, H, W, C):
+    import torch.nn.functional as TF
+    src = ks.gather_input(kind, B, H, W, C)
+    assert np.array_equal(bf16(src), src) and src.shape == (B, H // (2 if kind == 3 else 1), W // (2 if kind == 3 else 1), C)
+    kpad = ks.vae_kpad(C, "bf16")
+    assert kpad % 64 == 0 and 9 * C <= kpad < 9 * C + 64 and ks.vae_kpad(C, "fp32") % 32 == 0
+    want = ks.im2col3x3_ref(src, kind == 3, kpad)
+    t = torch.from_numpy(src).permute(0, 3, 1, 2)
+    if kind == 3:
+        t = TF.interpolate(t, scale_factor=2.0, mode="nearest")
+    cols = TF.unfold(t, 3, padding=1).reshape(B, C, 3, 3, H * W).permute(0, 4, 2, 3, 1).reshape(B * H * W, 9 * C).numpy()
+    assert np.array_equal(want[:, :9 * C], cols) and not want[:, 9 * C:].any()
+    muts = ["edge"] + (["taps"] if H * W > 1 else []) + (["half_x"] if kind == 3 and W > 2 else [])      # (one source column: nothing to halve)
+    for mut in muts:
+        bad = ks.im2col3x3_ref(src, kind == 3, kpad, mutant=mut)
+        assert (bad != want).any(1).mean() >= 0.5, mut      # at least half of the rows differ (a 2 x 2 upsample of one pixel: the diagonal agrees)
+
+
+@pytest.mark.parametrize("swish", [0, 1])
+@pytest.mark.parametrize("B,HW,C", ks.GN_SHAPES)
+def test_groupnorm_reference_and_its_mutants(B, HW, C, swish):
+    """the numpy restatement equals torch's float64 group_norm; each mutant, and the emulation of the one-pass fp32 statistics, exceeds the
+    fp32 bound of tests/test_vae_kernels.py; the emulation of the statistics about a per-(image, group) pivot stays within it"""
+    case = ks.gn_case(B, HW, C, swish)
+    x, gamma, beta, want = case["x"], case["gamma"], case["beta"], case["want"]
+    assert np.abs(ks.groupnorm_ref(x, gamma, beta, B, HW, C, swish) - want).max() < 1e-11
+    tol = ks.gn_tol(case, "fp32")
+    assert (case["e32"] > 0).all() and case["e32"].max() == case["e32_case"] and tol.max() < 1e-3
+    if B > 1:      # the pairs rotate with the image
+        k = ks.gn_pair_index(B, C)
+        assert (k[0] != k[1]).all() and set(k[0]) == {0, 1, 2, 3}
+    if C != 128:
+        assert (np.abs(ks.groupnorm_ref(x, gamma, beta, B, HW, C, swish, mutant="group_map") - want) > tol).mean() > 0.5
+    else:
+        assert np.array_equal(ks.groupnorm_ref(x, gamma, beta, B, HW, C, swish, mutant="group_map"), ks.groupnorm_ref(x, gamma, beta, B, HW, C, swish))
+    if HW > 256 and HW % 256:
+        assert (np.abs(ks.groupnorm_ref(x, gamma, beta, B, HW, C, swish, mutant="drop_tail") - want) > tol).mean() > 0.5
+    one = np.abs(ks.groupnorm_emulated(x, gamma, beta, B, HW, C, swish, pivot=False) - want)
+    piv = np.abs(ks.groupnorm_emulated(x, gamma, beta, B, HW, C, swish, pivot=True) - want)
+    ratio = lambda e: [float((e / case["e32"])[case["cls"] == k].max()) for k in range(4)]
+    print(f"B {B} HW {HW} C {C} swish {swish}: err / e32 per (mean, std) pair, one-pass {ratio(one)}, about a pivot {ratio(piv)}")
+    assert (piv <= tol).all()
+    r = ratio(one)
+    assert r[0] <= 8 and r[1] > 8 and r[2] > 80 and r[3] > 80, r
+    assert one.max() > 8 * case["e32_case"]                # it fails the bound taken over the whole case, too
+
+
+def test_groupnorm_constant_case():
+    case = ks.gn_case(2, 64, 128, 0, const=True)
+    x = case["x"].reshape(2, 64, 128)
+    assert (x[0, :, 28:32] == np.float32(123.456)).all() and (x[1, :, 20:24] == np.float32(0.1)).all()
+    assert np.abs(case["want"].reshape(2, 64, 128)[1, :, 20:24] - case["beta"][20:24]).max() < 1e-9
+    assert (np.abs(ks.groupnorm_emulated(case["x"], case["gamma"], case["beta"], 2, 64, 128, 0, pivot=True) - case["want"]) <= ks.gn_tol(case, "fp32")).all()
+
+
+@pytest.mark.parametrize("rows,n", ks.SOFTMAX_SHAPES)
+def test_softmax_reference_and_its_mutants(rows, n):
+    s = ks.softmax_inputs(rows, n)
+    want, tol = ks.softmax_ref(s, ks.SOFTMAX_SCALE)
+    t = torch.softmax(torch.from_numpy(s).double() * float(ks.SOFTMAX_SCALE), dim=-1).numpy()
+    assert np.abs(want - t).max() < 1e-14 and np.abs(want.sum(-1) - 1).max() < 1e-12
+    assert tol.max() < 1e-4 and (tol >= 2.0 ** -126).all()
+    a = s.astype(np.float64) * float(ks.SOFTMAX_SCALE)
+    if rows >= 4 and n > 1:
+        assert a[3].max() > 79.9 and a[3].min() < -79.9 and (s[2] == s[2, 0]).all() and want[1, -1] == 1.0
+    if n > 1:
+        assert (np.abs(ks.softmax_ref(s, ks.SOFTMAX_SCALE, mutant="no_scale")[0] - want) > tol).any(1)[np.isin(np.arange(rows) % 4, (0, 3))].all()      # (a constant or a one-hot row stays what it is)
+    if n % 64:
+        bad = ks.softmax_ref(s, ks.SOFTMAX_SCALE, mutant="drop_tail")[0]
+        over = ~(np.abs(bad - want) <= tol)
+        assert over.any(1)[np.arange(rows) % 4 != 3 if n > 64 else slice(None)].all()
+    # bf16: the bound grows by one ulp of the result
+    assert np.array_equal(ks.softmax_ref(s, ks.SOFTMAX_SCALE, "bf16")[1], tol + ulp_bf16(want))
+
+
+@pytest.mark.parametrize("B,HW", ks.VAE_MOMENTS_SHAPES)
+def test_moments_reference_and_its_mutants(B, HW):
+    import torch.nn.functional as TF
+    a = ks.vae_moments_case(B, HW)
+    m, tol_m, z, tol_z = ks.vae_moments_ref(a["h"], a["w"], a["b"], a["eps"], B, HW)
+    hh = torch.from_numpy(a["h"]).double().reshape(B, HW, 8).permute(0, 2, 1).reshape(B, 8, HW, 1)
+    mt = TF.conv2d(hh, torch.from_numpy(a["w"]).double().reshape(8, 8, 1, 1), torch.from_numpy(a["b"]).double()).reshape(B, 8, HW)
+    assert np.abs(m - mt.numpy()).max() < 1e-12
+    mean, lv = mt[:, :4], torch.clamp(mt[:, 4:], -30.0, 20.0)
+    zt = float(np.float32(ks.VAE_SCALE)) * (mean + torch.exp(0.5 * lv) * torch.from_numpy(a["eps"]).double())
+    assert (np.abs(z - zt.numpy()) <= 1e-12 * (1 + np.abs(z))).all()
+    lvr = m[:, 4:]
+    assert (lvr < -30).any() and (lvr > 20).any() and ((lvr > -30) & (lvr < 20)).any()
+    mode = ks.vae_moments_ref(a["h"], a["w"], a["b"], None, B, HW)
+    assert np.array_equal(mode[2], float(np.float32(ks.VAE_SCALE)) * m[:, :4]) and (mode[3] <= tol_z).all()
+    mw = ks.vae_moments_ref(a["h"], a["w"], a["b"], a["eps"], B, HW, mutant="w_transposed")
+    assert (np.abs(mw[0] - m) > tol_m).mean() > 0.9 and (np.abs(mw[2] - z) > tol_z).mean() > 0.9
+    nc = ks.vae_moments_ref(a["h"], a["w"], a["b"], a["eps"], B, HW, mutant="no_clamp")
+    assert np.array_equal(nc[0], m) and (np.abs(nc[2] - z) > tol_z)[lvr > 20.01].all() and np.array_equal(nc[2][np.abs(lvr + 5) < 25], z[np.abs(lvr + 5) < 25])
+    lm = ks.vae_moments_ref(a["h"], a["w"], a["b"], a["eps"], B, HW, mutant="logvar_from_mean")
+    assert np.array_equal(lm[0], m) and (np.abs(lm[2] - z) > tol_z).mean() > 0.9
+
+
+@pytest.mark.parametrize("B,HW", ks.VAE_INPUT_SHAPES)
+def test_vae_input_reference_and_its_mutant(B, HW):
+    a = ks.vae_input_case(B, HW)
+    want, tol = ks.vae_input_ref(a["z"], a["w"], a["b"], a["inv_scale"])
+    zz = torch.from_numpy(a["z"]).double() * float(a["inv_scale"])
+    t = torch.einsum("oc,bcp->bpo", torch.from_numpy(a["w"]).double(), zz) + torch.from_numpy(a["b"]).double()
+    assert np.abs(want - t.reshape(B * HW, 4).numpy()).max() < 1e-13 and tol.max() < 1e-4
+    assert (np.abs(ks.vae_input_ref(a["z"], a["w"], a["b"], a["inv_scale"], mutant="w_transposed")[0] - want) > tol).mean() > 0.9
+    # the fp32 restatement of the chain lies within the bound
+    v = (a["z"].transpose(0, 2, 1).reshape(-1, 4) * a["inv_scale"]).astype(np.float32)
+    acc = np.broadcast_to(a["b"], (B * HW, 4)).astype(np.float32)
+    for c in range(4):
+        acc = (acc.astype(np.float64) + a["w"][:, c].astype(np.float64) * v[:, c:c + 1].astype(np.float64)).astype(np.float32)      # an fmaf: one rounding
+    assert (np.abs(acc - want) <= tol).all()
+
+
+def test_vae_output_reference_and_cast_inputs():
+    inp = np.arange(2 * 5 * 4, dtype=np.float32).reshape(10, 4)
+    out = ks.vae_output_ref(inp, 2, 3, 5, 4)
+    assert out.shape == (2, 3, 5) and all(out[b, c, p] == inp[b * 5 + p, c] for b in range(2) for c in range(3) for p in range(5))
+    x = ks.cast_inputs()
+    u = x.view(np.uint32)
+    tie = (u & 0xFFFF) == 0x8000
+    up, down = tie & ((u >> 16) & 1 == 1), tie & ((u >> 16) & 1 == 0)
+    assert x.size % 256 and up.sum() >= 512 and down.sum() >= 512 and (x[tie] < 0).any() and (x[tie] > 0).any()
+    assert np.array_equal(bf16_bits(x[up]), (u[up] >> 16) + 1) and np.array_equal(bf16_bits(x[down]), u[down] >> 16)
+    assert (u == 0).any() and (u == 0x80000000).any()
+    mag = np.abs(x[x != 0])
+    assert mag.min() < 2.0 ** -19 and mag.max() > 2.0 ** 19

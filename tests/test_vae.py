@@ -79,6 +79,20 @@ def test_vae_decode_fp32_full(gold, sd):
 
 
 @pytest.mark.gpu
+def test_vae_decode_fp32_latent24(sd):
+    """24 x 24 latents (HW = 576 at the attention: GroupNorm chunks 256 + 256 + 64, 9 softmax elements per lane, M = 576 GEMMs) against the
+    numpy oracle, under the bound of the 32 x 32 test on a centre slice"""
+    z = torch.randn(1, 4, 24, 24, generator=torch.Generator().manual_seed(24))
+    want = vae_decode(z.numpy(), sd)
+    ae = FrozenAutoencoderKL(sd, precision="fp32", max_chunk=1, max_latent=24).to("cuda:0")
+    y = ae.decode(z).cpu().numpy()
+    assert y.shape == want.shape == (1, 3, 192, 192)
+    e = _err(y[:, :, 64:128, 64:128], want[:, :, 64:128, 64:128])
+    print(f"vae fp32 24x24 max|err| centre slice {e:.3e}, whole image {_err(y, want):.3e}")
+    assert e <= 3e-4, e
+
+
+@pytest.mark.gpu
 def test_vae_decode_bf16(gold, sd):
     """bf16 operands / fp32 accumulation; GroupNorm statistics, softmax and residual trunk in fp32."""
     ae = FrozenAutoencoderKL(sd, precision="bf16", max_chunk=2, max_latent=32).to("cuda:0")

@@ -126,7 +126,7 @@ def full_sd(esd):
 def cases(gold, esd):
     """name -> (x, float64 moments, float32 moments): the references every test below shares"""
     xs = {"x64": torch.from_numpy(gold["x64"]), "x256": uniform_image((1, 3, 256, 256), gold["x256_seed"]),
-          "x128": uniform_image((1, 3, 128, 128), 73)}
+          "x128": uniform_image((1, 3, 128, 128), 73), "x192": uniform_image((1, 3, 192, 192), 74)}      # x192: latent 24, HW = 576 at the attention
     out = {}
     for k, x in xs.items():
         out[k] = (x, restate_moments(x, esd, torch.float64), None if k == "x128" else restate_moments(x, esd, torch.float32))
@@ -340,11 +340,14 @@ def test_input_gather_bitwise(prec, H, B):
 
 
 @gpu
-@pytest.mark.parametrize("case", ["x64", "x256"])
+@pytest.mark.parametrize("case", ["x64", "x256", "x192"])
 def test_encode_moments_fp32(case, gold, cases, ae_fp32):
+    """x192 (latent 24: GroupNorm over two whole 256-pixel chunks and a part of a third, 9 softmax elements per lane, GEMMs of M = 576) has
+    no reference-generated fixture: it is held to the float64 restatement alone, under the same rule"""
     x, m64, m32 = cases[case]
     got = ae_fp32.encode_moments(x).cpu().numpy()
-    fix, tol_fix = gold["moments8"] if case == "x64" else gold["moments32"], fixture_tol(cases[case])
+    fix = {"x64": gold["moments8"], "x256": gold["moments32"], "x192": m32}[case]
+    tol_fix = fixture_tol(cases[case])
     assert got.shape == fix.shape and got.dtype == np.float32
     e32 = float(np.abs(m32.astype(np.float64) - m64).max())
     floor = 1e-6 * float(np.abs(m64).max())

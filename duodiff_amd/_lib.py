@@ -200,6 +200,9 @@ SIGNATURES = {
     "dd_dev_vae_output": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3),
     "dd_dev_vae_moments": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7),
     "dd_dev_cast": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dd_dev_ee_probe": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 6),
+    "dd_dev_ee_probe_reduce": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3),
+    "dd_dev_ee_attn_probe": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 10),
     "dd_dev_final": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_final_args), C.c_void_p]),
     "dd_dev_final_seeded": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_final_args), C.c_void_p, C.c_int, C.c_void_p]),
     "dd_dev_poison_workspaces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

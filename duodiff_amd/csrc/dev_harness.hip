@@ -1,5 +1,5 @@
 // The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_block_tail, dd_dev_block_tail_frag, dd_dev_qkv_attention, dd_dev_qkv_attention_rows, dd_dev_qkv_attention_frag, dd_dev_v_identity, dd_dev_v_copy, dd_dev_head_dec, dd_dev_gemm,
-// dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather, dd_dev_groupnorm, dd_dev_softmax_rows, dd_dev_vae_input, dd_dev_vae_output, dd_dev_vae_moments, dd_dev_cast, dd_dev_final): test scaffolding, not product.  Each one owns its host operands, device buffers, canaries and
+// dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather, dd_dev_groupnorm, dd_dev_softmax_rows, dd_dev_vae_input, dd_dev_vae_output, dd_dev_vae_moments, dd_dev_cast, dd_dev_ee_probe, dd_dev_ee_probe_reduce, dd_dev_ee_attn_probe, dd_dev_final): test scaffolding, not product.  Each one owns its host operands, device buffers, canaries and
 // downloads, and nothing of the launch: the weight images come from finalize's packers and the launch arguments from the model's builders (launch_args.h:
 // dd_dev_mlp and dd_dev_block_tail* run block_tail_plan / block_tail_finish exactly as Backbone::block_tail does), then `iters` further launch sequences
 // are timed.  Buffers, transfers, timing and HIP errors go through one DevScope (dev_scope.h); of the context it reads num_cus and dev_flags (engine_state.h).
@@ -722,6 +722,63 @@ int dd_dev_cast(dd_ctx* c, int precision, long long n, const float* x_host, void
     DEV_HIP(dev, bf ? launch_cast<bf16_t>(dX, (bf16_t*)dO, n, s) : launch_cast<float>(dX, (float*)dO, n, s));
     DEV_HIP(dev, hipStreamSynchronize(s));
     dev.download(out_host, dO, ((size_t)n + DD_DEV_VAE_TAIL) * esz);
+    return dev.status();
+}
+
+// The early-exit probes (rowops.hip), each through its production launch_* function on host arrays: every output has DD_DEV_EE_TAIL elements
+// behind the last one the launch may write, holds 0xFF bytes before the launch and is downloaded whole.
+int dd_dev_ee_probe(dd_ctx* c, int B, int L, int D, int n_probe, int t_state, int t_mul, int add, const float* x_host, const float* pw,
+                    const float* pb, float* srow_host, float* out_host, void* stream) {
+    if (!c || B < 1 || B > 4096 || L < 1 || D < 1 || (long long)B * L * D > (1ll << 28) || n_probe < 1 || n_probe > (1 << 20) || t_state < 0 ||
+        t_state > 65535 || t_mul < 0 || t_mul > 65535 || add < 0 || !x_host || !pw || !pb || !srow_host)
+        return DD_ERR_INVALID;
+    const long long pi = (long long)t_state * t_mul + add;      // the probe row the launch reads
+    if (pi >= n_probe) return DD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t rows = (size_t)B * L;
+    DevScope dev(c);
+    const float* dX = dev.upload(x_host, rows * D * 4);
+    const float* dW = dev.upload(pw, (size_t)n_probe * D * 4);
+    const float* dB = dev.upload(pb, (size_t)n_probe * 4);
+    StepState* st = dev.alloc<StepState>(sizeof(StepState));
+    float* dS = dev.filled<float>((rows + DD_DEV_EE_TAIL) * 4, 0xFF);
+    float* dO = out_host ? dev.filled<float>(((size_t)B + DD_DEV_EE_TAIL) * 4, 0xFF) : nullptr;
+    DEV_HIP(dev, launch_set_state(st, t_state, 0ull, s));
+    DEV_HIP(dev, launch_ee_probe(dX, dW, dB, dO, dS, B, L, D, st, t_mul, add, s));
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(srow_host, dS, (rows + DD_DEV_EE_TAIL) * 4);
+    if (out_host) dev.download(out_host, dO, ((size_t)B + DD_DEV_EE_TAIL) * 4);
+    return dev.status();
+}
+
+int dd_dev_ee_probe_reduce(dd_ctx* c, int rows, int L, const float* srow_host, float* out_host, void* stream) {
+    if (!c || rows < 1 || L < 1 || (long long)rows * L > (1ll << 28) || !srow_host || !out_host) return DD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    DevScope dev(c);
+    const float* dS = dev.upload(srow_host, (size_t)rows * L * 4);
+    float* dO = dev.filled<float>(((size_t)rows + DD_DEV_EE_TAIL) * 4, 0xFF);
+    DEV_HIP(dev, launch_ee_probe_reduce(dS, dO, rows, L, s));
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(out_host, dO, ((size_t)rows + DD_DEV_EE_TAIL) * 4);
+    return dev.status();
+}
+
+int dd_dev_ee_attn_probe(dd_ctx* c, int B, int L, int D, const float* x_host, const float* q, const float* wkv, const float* bkv,
+                         const float* w0, const float* b0, const float* w2, const float* b2, float* out_host, void* stream) {
+    if (!c || B < 1 || B > 4096 || L < 2 || D < 64 || D % 64 || (long long)B * L * D > (1ll << 28) || !x_host || !q || !wkv || !bkv || !w0 || !b0 ||
+        !w2 || !b2 || !out_host)
+        return DD_ERR_INVALID;
+    if (((size_t)L + 3 * (size_t)D) * 4 > 64 * 1024) return ctx_fail(c, DD_ERR_UNSUPPORTED, "ee_attn_probe: L + 3 D floats of LDS");
+    hipStream_t s = (hipStream_t)stream;
+    const AttnProbeFold f = fold_attn_probe(D, q, wkv, w0);      // as finalize folds the model's probes
+    DevScope dev(c);
+    const float* dX = dev.upload(x_host, (size_t)B * L * D * 4);
+    const AttnProbeW w{dev.upload(f.u.data(), (size_t)D * 4), dev.upload(f.wvt.data(), (size_t)D * D * 4), dev.upload(bkv + D, (size_t)D * 4),
+                       dev.upload(f.w0t.data(), (size_t)D * D * 4), dev.upload(b0, (size_t)D * 4), dev.upload(w2, (size_t)D * 4), dev.upload(b2, 4)};
+    float* dO = dev.filled<float>(((size_t)B + DD_DEV_EE_TAIL) * 4, 0xFF);
+    DEV_HIP(dev, launch_ee_attn_probe(dX, w, dO, B, L, D, s));
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(out_host, dO, ((size_t)B + DD_DEV_EE_TAIL) * 4);
     return dev.status();
 }
 

@@ -1,12 +1,13 @@
 // What the model (forward.hip: Backbone; model.hip: finalize) and the single-kernel development entry points (dev_harness.hip) share on the host side, each
 // defined once, so that a development entry point packs what finalize packs and launches what the model launches: the weight-image packers (the
-// fused block tail's image, the transposed embed / time_embed weights, an output head's folded operands) and the launch plans (the block tail's
+// fused block tail's image, the transposed embed / time_embed weights, an output head's and an attention probe's folded operands) and the launch plans (the block tail's
 // derived arguments, reduce arguments and follow-up launches; the row-resident and split-K row passes).  Callers own operands and buffers only.
 // Hidden visibility: nothing here joins the library's dynamic symbol table.  Not included by any kernel translation unit.
 #pragma once
 #include "dd_internal.h"
 #include "host_arena.h"
 
+#include <cmath>
 #include <vector>
 
 namespace dd {
@@ -68,6 +69,29 @@ inline HeadImage pack_head_image(int D, int pd, const float* wd, const float* bd
         pack_head_split(D, pd, h.wg.data(), host_f2bf, h.wsplit.data(), h.dcs.data() + pd);
     }
     return h;
+}
+
+// ee_attn_probe_kernel operands from an AttentionProbe's raw parameters (early_exit.py:40-80; one learned query q [D], one head, weight_kv
+// [2 D, D] = Wk over Wv, classification.0 w0 [D, D]).  q . (Wk x + bk) = (Wk^T q) . x + const, and the constant cancels in the softmax;
+// sum_l p_l (Wv x_l + bv) = Wv (sum_l p_l x_l) + bv.  So the probe needs u = Wk^T q / sqrt(D) (folded here, in double), and Wv /
+// classification.0 transposed for coalesced mat-vecs -- never the [L, 2D] kv.
+struct AttnProbeFold {
+    std::vector<float> u, wvt, w0t;
+};
+inline AttnProbeFold fold_attn_probe(int D, const float* q, const float* wkv, const float* w0) {
+    AttnProbeFold f{std::vector<float>(D), std::vector<float>((size_t)D * D), std::vector<float>((size_t)D * D)};
+    const double scale = 1.0 / std::sqrt((double)D);
+    for (int k = 0; k < D; ++k) {
+        double acc = 0.0;
+        for (int j = 0; j < D; ++j) acc += (double)q[j] * (double)wkv[(size_t)j * D + k];
+        f.u[k] = (float)(acc * scale);
+    }
+    for (int j = 0; j < D; ++j)
+        for (int k = 0; k < D; ++k) {
+            f.wvt[(size_t)k * D + j] = wkv[(size_t)(D + j) * D + k];
+            f.w0t[(size_t)k * D + j] = w0[(size_t)j * D + k];
+        }
+    return f;
 }
 
 // ---- the fused block tail (mlp_fused.hip) on B images of n_patches patch tokens behind `extras` extra tokens, width D with H heads

@@ -282,29 +282,16 @@ void pack_probes(dd_model* m, Arena& a) {
     int nt, nl;
     probe_grid(m, nt, nl);
     if (m->ee_type == DD_EE_ATTENTION_PROBE) {
-        // AttentionProbe (early_exit.py:40-80), one learned query, one head.  q . (Wk x + bk) = (Wk^T q) . x + const, and the
-        // constant cancels in the softmax; sum_l p_l (Wv x_l + bv) = Wv (sum_l p_l x_l) + bv.  So the probe needs u = Wk^T q /
-        // sqrt(D) (folded here, in double), and Wv / classification.0 transposed for coalesced mat-vecs -- never the [L, 2D] kv.
+        // AttentionProbe (early_exit.py:40-80), one learned query, one head: the operands folded by fold_attn_probe (launch_args.h)
         m->attn_probes.resize(nl);
         for (int layer = 0; layer < nl; ++layer) {
             const std::string pre = "matrix." + probe_key(m, layer, 0) + ".";
             const std::vector<float>&q = P(pre + "q"), &wkv = P(pre + "weight_kv.weight"), &bkv = P(pre + "weight_kv.bias"),
                                     &w0 = P(pre + "classification.0.weight");
-            std::vector<float> u(D), wvt((size_t)D * D), w0t((size_t)D * D);
-            const double scale = 1.0 / std::sqrt((double)D);
-            for (int k = 0; k < D; ++k) {
-                double acc = 0.0;
-                for (int j = 0; j < D; ++j) acc += (double)q[j] * (double)wkv[(size_t)j * D + k];
-                u[k] = (float)(acc * scale);
-            }
-            for (int j = 0; j < D; ++j)
-                for (int k = 0; k < D; ++k) {
-                    wvt[(size_t)k * D + j] = wkv[(size_t)(D + j) * D + k];
-                    w0t[(size_t)k * D + j] = w0[(size_t)j * D + k];
-                }
+            const AttnProbeFold f = fold_attn_probe(D, q.data(), wkv.data(), w0.data());
             AttnProbeW& w = m->attn_probes[layer];
-            a.f32(w.u, u); a.f32(w.wvt, wvt); a.f32(w.bv, bkv.data() + D, D);
-            a.f32(w.w0t, w0t); a.f32(w.b0, P(pre + "classification.0.bias"));
+            a.f32(w.u, f.u); a.f32(w.wvt, f.wvt); a.f32(w.bv, bkv.data() + D, D);
+            a.f32(w.w0t, f.w0t); a.f32(w.b0, P(pre + "classification.0.bias"));
             a.f32(w.w2, P(pre + "classification.2.weight")); a.f32(w.b2, P(pre + "classification.2.bias"));
         }
         return;

@@ -231,6 +231,26 @@ int dd_dev_vae_moments(dd_ctx* ctx, int B, int HW, const float* h_host, const fl
                        float* moments_host, float* z_host, void* stream);
 int dd_dev_cast(dd_ctx* ctx, int precision, long long n, const float* x_host, void* out_host, void* stream);
 
+/* Development harnesses for the early-exit probes (rowops.hip; reference models/early_exit.py:31-80), each through its production launch_*
+ * function on host fp32 arrays.  Every output has DD_DEV_EE_TAIL elements behind the last one the launch may write; the whole buffer is
+ * filled with 0xFF bytes before the launch and comes back WHOLE.  Arguments are checked before anything touches the GPU (DD_ERR_INVALID,
+ * nothing written).
+ * dd_dev_ee_probe: launch_ee_probe as forward.hip calls it: x_host [B L, D] token rows, the probe table pw [n_probe, D] / pb [n_probe], the
+ *   step state set to t_state (launch_set_state); the launch reads probe row t_state t_mul + add (outside [0, n_probe): DD_ERR_INVALID) ->
+ *   srow_host [B L + TAIL] = sigmoid(x_l . w + b) per token row and out_host [B + TAIL] = their mean per image; out_host NULL: the rows-only
+ *   form (the model reduces several layers' rows at once behind the last block: dd_dev_ee_probe_reduce).
+ * dd_dev_ee_probe_reduce: launch_ee_probe_reduce: srow_host [rows, L] -> out_host [rows + TAIL] = the mean of each row.
+ * dd_dev_ee_attn_probe: launch_ee_attn_probe on x_host [B L, D] with an AttentionProbe's RAW parameters -- q [D], weight_kv wkv [2 D, D] /
+ *   bkv [2 D], classification.0 w0 [D, D] / b0 [D], classification.2 w2 [D] / b2 [1] -- folded by the host function finalize folds the
+ *   model's probes with (launch_args.h fold_attn_probe) -> out_host [B + TAIL].  L < 2 or D % 64 != 0: DD_ERR_INVALID; more than 64 KB of
+ *   LDS (L + 3 D floats): DD_ERR_UNSUPPORTED. */
+#define DD_DEV_EE_TAIL 64
+int dd_dev_ee_probe(dd_ctx* ctx, int B, int L, int D, int n_probe, int t_state, int t_mul, int add, const float* x_host, const float* pw,
+                    const float* pb, float* srow_host, float* out_host, void* stream);
+int dd_dev_ee_probe_reduce(dd_ctx* ctx, int rows, int L, const float* srow_host, float* out_host, void* stream);
+int dd_dev_ee_attn_probe(dd_ctx* ctx, int B, int L, int D, const float* x_host, const float* q, const float* wkv, const float* bkv,
+                         const float* w0, const float* b0, const float* w2, const float* b2, float* out_host, void* stream);
+
 /* Development harness for the launch that ends every sampling step and every forward (step.hip final_tiled_kernel through launch_final:
  * unpatchify, the 3x3 conv, guidance, the step update of step_update.h): ONE launch, from a FinalArgs filled the way forward.hip fills it.
  * All arrays are host fp32.  Geometry: B images of C x S x S (the grid), patches of P, L = extras + (S / P)^2 decoder rows per image, b0 the

@@ -1,7 +1,7 @@
 """What the per-element kernel tests share (test_attention, test_block_tail, test_frag_handoff, test_gemm_path, test_row_kernels,
 test_qkv_attention, test_mlp_fused, test_pag, test_head_dec): bf16 arithmetic on the host, the elementwise gate, the constants of the bounds,
 the LayerNorm bound of the GEMM-path tests, the MFMA fragment order, the references of the output head + step launch (test_final_step) and
-of the KL-VAE kernels (test_vae_kernels).  tests/test_kernel_support.py (CPU) pins every piece of it."""
+of the KL-VAE kernels (test_vae_kernels) and of the early-exit probes (test_ee_probes).  tests/test_kernel_support.py (CPU) pins every piece of it."""
 import numpy as np
 
 from duodiff_amd import _lib
@@ -682,3 +682,296 @@ def run_softmax(prec, rows, n, scale, s):
 def values(out, prec):
     """the fp32 values of an output buffer (bf16 bits or fp32)"""
     return from_bf16_bits(out) if prec == "bf16" else out
+
+
+# ---------------------------------------------------------------------------------------------------------------- the early-exit probes
+# What tests/test_ee_probes.py (GPU, through dd_dev_ee_probe / dd_dev_ee_probe_reduce / dd_dev_ee_attn_probe) compares the probe kernels of
+# csrc/rowops.hip with: float64 restatements from the fp32 operands with derived elementwise bounds, the reduce kernel in float32 in its
+# fixed order, float32 restatements of the row and attention probes, and the inputs of every case.  `mutant` switches on one deliberate
+# error; tests/test_kernel_support.py proves on the CPU that the inputs used on the GPU see each of them.
+EE_TAIL = 64                   # DD_DEV_EE_TAIL: canary elements behind every output
+EE_B = 3
+EE_PROBE_L = (1, 5, 8, 9, 17, 65, 66, 257, 258)
+EE_PROBE_CASES = [(512, L) for L in EE_PROBE_L] + [(D, L) for D in (64, 256, 768, 1024) for L in (17, 257)]      # (D, L)
+EE_REDUCE_ROWS = (1, 3, 4, 5, 91)
+EE_REDUCE_L = (1, 63, 64, 65, 257)
+EE_ATTN_CASES = [(64, 2), (64, 17), (256, 65), (512, 257), (512, 258), (768, 257), (1024, 258)]                    # (D, L)
+EE_ROW_MUTANTS = ("drop_slice_end", "pair_repeats", "no_bias")      # + "wrong_probe_row", which needs a table
+EE_MEAN_MUTANTS = ("drop_tail", "over_patches")
+EE_ATTN_MUTANTS = ("keep_first_token", "no_scale", "v_from_k", "w0_untransposed", "no_bv", "drop_far_tokens")
+EE_PLANTED = (-120.0, 95.0, -88.9, 88.2, -95.0, 120.0, -90.0, -100.0)      # logits (before the bias) of the planted rows
+FLOOR = 2.0 ** -126            # a result below the smallest normal fp32 may be flushed
+
+
+def ee_probe_case(B, L, D, n_probe=1, row=0):
+    """x [B, L, D], the probe table pw [n_probe, D] / pb [n_probe] (every row but `row` NaN), w = pw[row], b = pb[row].
+    w ~ N(0, 1) / sqrt(D), shifted so that sum(w) = 0.02; b = 0.7.  Token row l of image b is of kind (l + b) % 4: N(0, 1) (logits within a
+    few units); 30 N(0, 1) (logits of +-30); a multiple of w that plants the logit EE_PLANTED[(l // 4 + b) % 8] (saturation either way, expf
+    overflow, results below 2^-126); 100 + N(0, 1) (a common offset of 100 sigma: sum |w| |x| = 80 sqrt(D) against a logit near 2 + b)"""
+    r = np.random.default_rng(100000 * D + 100 * L + B + 7 * row)
+    w = r.standard_normal(D) / np.sqrt(D)
+    w = (w + (0.02 - w.sum()) / D).astype(F32)
+    x = r.standard_normal((B, L, D))
+    w64 = w.astype(np.float64)
+    for b in range(B):
+        for l in range(L):
+            k = (l + b) % 4
+            if k == 1:
+                x[b, l] *= 30.0
+            elif k == 2:
+                x[b, l] = EE_PLANTED[(l // 4 + b) % 8] * w64 / (w64 @ w64) + 0.01 * x[b, l]
+            elif k == 3:
+                x[b, l] += 100.0
+    pw = np.full((n_probe, D), np.nan, F32)
+    pb = np.full(n_probe, np.nan, F32)
+    pw[row], pb[row] = w, F32(0.7)
+    return dict(B=B, L=L, D=D, x=x.astype(F32), pw=pw, pb=pb, w=w, b=F32(0.7))
+
+
+def ee_slices(L):
+    """the (l0, l1) row ranges of ee_probe_rows_kernel's 8 slices (the empty ones left out)"""
+    per = -(-L // 8)
+    return [(y * per, min(y * per + per, L)) for y in range(8) if y * per < L]
+
+
+def _ee_row_mutation(s, mutant):
+    """the row mutants, on s [B, L]: "drop_slice_end" -- the last row of each 8th-of-L slice keeps a stale value (the row's before it; the
+    image's first row: 0); "pair_repeats" -- the second row in flight, l + 4, gets row l's value"""
+    s = s.copy()
+    L = s.shape[-1]
+    if mutant == "drop_slice_end":
+        src = s.copy()
+        for _, l1 in ee_slices(L):
+            s[:, l1 - 1] = src[:, l1 - 2] if l1 >= 2 else 0.0
+    elif mutant == "pair_repeats":
+        for l0, l1 in ee_slices(L):
+            for l in range(l0, l1):
+                if (l - l0) % 8 < 4 and l + 4 < l1:
+                    s[:, l + 4] = s[:, l]
+    return s
+
+
+def probe_rows_ref(x, w, b, mutant=None, row=0, wrong_row=0):
+    """(s, tol_s) [B, L]: s = sigmoid(x . w + b) in float64 from the fp32 operands; w [D] and b, or the probe table [n, D] / [n] and `row`.
+    Derivation (u = 2^-24).  The kernel's logit is a per-lane fmaf chain of D / 64 terms, six xor-shuffle levels and the bias add, one
+    rounding each (+ 1 spare): |da| <= (D / 64 + 6 + 2) u (|b| + sum |w| |x|).  It enters s with slope s (1 - s).  e = expf(-a) is allowed
+    4 ulp, and its argument's own rounding is u |a|: relative error (4 + |a|) u of e, which enters s = 1 / (1 + e) as s (1 - s) (4 + |a|) u.
+    The add and the divide round once each: 2 u s.  Second order: x 1.01.  An s below 2^-126 (a < -87.3; expf overflows from 88.7, then
+    s = 0) may be flushed: + 2^-126.
+    mutant: "drop_slice_end", "pair_repeats" (_ee_row_mutation), "no_bias", "wrong_probe_row" (table row `wrong_row` instead of `row`)"""
+    w, b = np.asarray(w, np.float64), np.asarray(b, np.float64)
+    if w.ndim == 2:
+        pick = wrong_row if mutant == "wrong_probe_row" else row
+        wm, bm, w, b = w[pick], b[pick], w[row], b[row]
+    else:
+        wm, bm = w, b
+    x = np.asarray(x, np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        a = x @ w + b
+        am = x @ wm + (0.0 if mutant == "no_bias" else bm)
+        s, sm = 1.0 / (1.0 + np.exp(-a)), 1.0 / (1.0 + np.exp(-am))
+    D = x.shape[-1]
+    tol_a = (D / 64 + 6 + 2) * U24 * (np.abs(b) + np.abs(x) @ np.abs(w))
+    tol = 1.01 * (s * (1 - s) * (tol_a + (4 + np.abs(a)) * U24) + 2 * U24 * s) + FLOOR
+    return _ee_row_mutation(sm, mutant), tol
+
+
+def probe_rows_f32(x, w, b):
+    """ee_probe_rows_kernel in float32, in its own order: lane i's fmaf chain over k = i, i + 64, ..., the xor-shuffle tree, the bias, the
+    sigmoid (numpy's float32 exp in expf's place; an fmaf as the float64 sum rounded once)"""
+    x, w = np.asarray(x, F32), np.asarray(w, F32)
+    D = x.shape[-1]
+    acc = np.zeros(x.shape[:-1] + (64,), F32)
+    for j in range(D // 64):
+        acc = (acc.astype(np.float64) + x[..., 64 * j:64 * j + 64].astype(np.float64) * w[64 * j:64 * j + 64].astype(np.float64)).astype(F32)
+    for o in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[..., np.arange(64) ^ o]
+    with np.errstate(over="ignore"):
+        return F32(1.0) / (F32(1.0) + np.exp(-(acc[..., 0] + F32(b))))
+
+
+def probe_mean_ref(s, tol_s=None, mutant=None):
+    """(out, tol) [rows]: the mean over the last dimension of s in float64.  Derivation: lane i adds its ceil(L / 64) rows, six shuffle
+    levels and one division follow, one rounding each; the terms are positive, so nothing cancels and the relative error is at most
+    (ceil(L / 64) + 6 + 1) u (x 1.01, + 2^-126).  tol_s: the bound of the rows where s is their float64 reference and not the kernel's own
+    fp32 rows -- the mean inherits its mean.
+    mutant: "drop_tail" (the rows behind the last whole 64 left out of the sum), "over_patches" (the sum divided by L - 1)"""
+    s = np.asarray(s, np.float64)
+    L = s.shape[-1]
+    out = s.mean(-1)
+    tol = 1.01 * (-(-L // 64) + 6 + 1) * U24 * out + FLOOR + (0.0 if tol_s is None else np.asarray(tol_s).mean(-1))
+    if mutant == "drop_tail":
+        return s[..., :L // 64 * 64].sum(-1) / L, tol
+    if mutant == "over_patches":
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return s.sum(-1) / (L - 1), tol
+    return out, tol
+
+
+def probe_mean_f32(s):
+    """ee_probe_reduce_kernel in float32 in its fixed order, bit for bit: lane i adds rows i, i + 64, ... ascending from 0, the xor-shuffle
+    tree 32 .. 1, one division by (float)L.  s [rows, L] fp32 -> [rows] fp32"""
+    s = np.asarray(s, F32)
+    rows, L = s.shape
+    pad = np.zeros((rows, round_up(L, 64)), F32)      # (a lane past the end adds nothing: + 0 is exact)
+    pad[:, :L] = s
+    acc = np.zeros((rows, 64), F32)
+    for j in range(pad.shape[1] // 64):
+        acc = acc + pad[:, 64 * j:64 * j + 64]
+    for o in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[:, np.arange(64) ^ o]
+    return acc[:, 0] / F32(L)
+
+
+def ee_reduce_rows(rows, L):
+    """srow [rows, L] fp32 for the reduce alone: sigmoid-like values in (0, 1) across 30 decades, with exact 0 and 1 among them"""
+    r = np.random.default_rng(1000 * rows + L)
+    s = r.uniform(0.0, 1.0, (rows, L)) * 10.0 ** -r.integers(0, 31, (rows, L)) * (r.uniform(size=(rows, L)) < 0.5)
+    s = np.where(r.uniform(size=(rows, L)) < 0.3, r.uniform(0.0, 1.0, (rows, L)), s)
+    s[::2, ::7] = 1.0
+    s[:, L // 2] = 0.37
+    s[:, L - 1] = 0.61      # (the last row: what a dropped tail drops)
+    return s.astype(F32)
+
+
+def _sparse_rows(r, rows, cols, nnz=4):
+    """[rows, cols] with nnz entries N(0, 1) / 2 per row at random columns: |W v| is about |v| and sum |W| |v| is within 1.3 of it"""
+    w = np.zeros((rows, cols))
+    idx = np.argsort(r.random((rows, cols)), axis=1)[:, :nnz]
+    w[np.arange(rows)[:, None], idx] = r.standard_normal((rows, nnz)) / 2.0
+    return w
+
+
+def ee_attn_case(B, L, D):
+    """x [B, L, D] and an AttentionProbe's raw parameters.  q ~ 3 N(0, 1) and Wk ~ N(0, 1) / sqrt(D), dense, so the scores of N(0, 1) tokens
+    have std about 3 and a few tokens share the softmax; bk ~ 5 N(0, 1) (the constant bk . q / sqrt(D) the fold drops), bv ~ N(0, 1).
+    Wv and classification.0 hold four entries per row at random columns and classification.2 is positive: a bound carried elementwise
+    through a dense Gaussian matrix grows by sqrt(2 D / pi) per stage over the error a kernel makes (5800 over the three stages at D = 512:
+    no mutant below a relative error of 1 would show); through these it grows by 1.3, and a wrong index, row or transposition still hits
+    other values.  With g = u / |u|^2 (u = Wk^T q / sqrt(D): adding c g to a token adds c to its score): token 0 of every image scores
+    30 above the largest of the image's other tokens; the last token scores 0.5 below that (the tokens behind index 256 carry weight where
+    there are any); in image 1 it scores 120 above (a single dominant token: every other probability underflows); every token of image 2 carries a
+    common offset of 1000"""
+    r = np.random.default_rng(100000 * D + 100 * L + B)
+    q = (3.0 * r.standard_normal(D)).astype(F32)
+    wkv = np.concatenate([r.standard_normal((D, D)) / np.sqrt(D), _sparse_rows(r, D, D)]).astype(F32)
+    bkv = np.concatenate([5.0 * r.standard_normal(D), r.standard_normal(D)]).astype(F32)
+    w0 = _sparse_rows(r, D, D).astype(F32)
+    b0 = (0.5 * r.standard_normal(D)).astype(F32)
+    w2 = (r.uniform(0.5, 1.5, D) * 4.0 / D).astype(F32)
+    b2 = np.asarray([0.3], F32)
+    u = wkv[:D].astype(np.float64).T @ q.astype(np.float64) / np.sqrt(D)
+    g = u / (u @ u)
+    x = r.standard_normal((B, L, D))
+    for b in range(B):
+        sc = x[b] @ u
+        top = sc[1:max(L - 1, 2)].max()                                # the bulk's largest score
+        x[b, L - 1] += (top + (120.0 if b % 3 == 1 else -0.5) - sc[L - 1]) * g
+        x[b, 0] += (top + 30.0 - sc[0]) * g
+        if b % 3 == 2:
+            x[b] += 1000.0 * g
+    return dict(B=B, L=L, D=D, x=x.astype(F32), q=q, wkv=wkv, bkv=bkv, w0=w0, b0=b0, w2=w2, b2=b2)
+
+
+def attn_probe_ref(x, q, wkv, bkv, w0, b0, w2, b2, mutant=None):
+    """(out, tol) [B]: AttentionProbe in float64 from the RAW fp32 parameters: tokens 1: only, k = Wk x + bk, score = q . k / sqrt(D),
+    p = softmax(score), o = Wv sum_l p_l x_l + bv (= sum_l p_l v_l), out = w2 . silu(W0 o + b0) + b2.
+    The bound, carried elementwise through the kernel's stages (u = 2^-24, n = L - 1 tokens, each stage x 1.01 for its second order):
+    scores -- the kernel's are uf . x with uf = fl(Wk^T q / sqrt(D)) (one rounding each, the fold's sum is in double), a per-lane fmaf
+      chain of D / 64 terms and six shuffle levels; they differ from the reference's by the constant bk . q / sqrt(D), which the softmax
+      cancels, and by at most tsc_l = (1 + D / 64 + 6) u sum_k |uf_k| |x_lk|.
+    softmax, as softmax_ref -- d_l = fl(sc_l - mx) rounds once, u |sc_l - sc_max| (a difference: the constant is not in it); expf is
+      allowed 4 ulp: e_l has relative error R_l = tsc_l + (|sc_l - sc_max| + 4) u (a common shift of all scores, mx's own error, cancels).
+      The sum adds ceil(n / 256) terms per thread, then the two-level block reduce (six shuffle levels, two adds across the four waves),
+      T = ceil(n / 256) + 8 roundings, and inherits sum_l p_l R_l; 1 / sum rounds once.
+    xbar_k = (chain of n fmaf of e_l x_lk) / sum: each term passes at most n roundings, the product with 1 / sum one more:
+      txbar_k = sum_l p_l |x_lk| (R_l + sum_j p_j R_j + (n + T + 2) u) + 2^-126 sum_l |x_lk| (an e_l below 2^-126 may be flushed; sum >= 1).
+    o = Wv xbar + bv and h = W0 o + b0 -- fmaf chains of D terms started on the bias (fma_chain64): (D + 3) u (|bias| + sum |W| |v|), plus
+      the operand's bound through |W|.
+    SiLU -- act = h / (1 + expf(-h)): slope <= 1.1 on h's bound; its own arithmetic (expf 4 ulp weighted 1 - sigmoid <= 1, the add, the
+      divide) 6 u |act|; + 2^-126 (1 + |h|) where expf overflows.
+    out -- per thread an fmaf chain of ceil(D / 256) terms, the block reduce's 8 roundings: (ceil(D / 256) + 8) u sum |w2| |act|; the add of
+      b2 rounds the result itself, u |out|; and the bound of act through |w2|.
+    mutant: "keep_first_token", "no_scale", "v_from_k" (rows 0 .. D-1 of weight_kv as Wv), "w0_untransposed", "no_bv", "drop_far_tokens"
+    (the tokens behind index 256 left out of the softmax)"""
+    x, q, wkv, bkv, w0, b0, w2, b2 = (np.asarray(a, np.float64) for a in (x, q, wkv, bkv, w0, b0, w2, b2))
+    D = x.shape[-1]
+    xs = x if mutant == "keep_first_token" else x[:, 1:]
+    if mutant == "drop_far_tokens":
+        xs = x[:, 1:257]
+    n = xs.shape[1]
+    wk, bk = wkv[:D], bkv[:D]
+    wv = wk if mutant == "v_from_k" else wkv[D:]
+    bv = np.zeros(D) if mutant == "no_bv" else bkv[D:]
+    w0 = w0.T if mutant == "w0_untransposed" else w0
+    sc = (xs @ wk.T + bk) @ q / (1.0 if mutant == "no_scale" else np.sqrt(D))
+    d = sc - sc.max(-1, keepdims=True)
+    e = np.exp(d)
+    p = e / e.sum(-1, keepdims=True)
+    ax = np.abs(xs)
+    xbar = np.einsum("bl,blk->bk", p, xs)
+    o = xbar @ wv.T + bv
+    h = o @ w0.T + b0
+    with np.errstate(over="ignore"):
+        act = h / (1.0 + np.exp(-h))
+    out = act @ w2.reshape(-1) + b2.reshape(-1)[0]
+    # ---- the bound
+    uf = np.abs(wk.T @ q / np.sqrt(D))
+    tsc = (1 + D / 64 + 6) * U24 * (ax @ uf)
+    R = 1.01 * (tsc + (np.abs(d) + 4) * U24)
+    T = -(-n // 256) + 8
+    pr = (p * R).sum(-1, keepdims=True)
+    txbar = 1.01 * np.einsum("bl,blk->bk", p * (R + pr + (n + T + 2) * U24), ax) + FLOOR * ax.sum(1)
+    to = 1.01 * ((D + 3) * U24 * (np.abs(bv) + np.abs(xbar) @ np.abs(wv).T) + txbar @ np.abs(wv).T)
+    th = 1.01 * ((D + 3) * U24 * (np.abs(b0) + np.abs(o) @ np.abs(w0).T) + to @ np.abs(w0).T)
+    tact = 1.01 * (1.1 * th + 6 * U24 * np.abs(act)) + FLOOR * (1 + np.abs(h))
+    aw2 = np.abs(w2.reshape(-1))
+    tol = 1.01 * ((-(-D // 256) + 8) * U24 * (np.abs(act) @ aw2) + U24 * np.abs(out) + tact @ aw2)
+    return out, tol
+
+
+def attn_probe_f32(x, q, wkv, bkv, w0, b0, w2, b2):
+    """the folded form ee_attn_probe_kernel computes (u = Wk^T q / sqrt(D) in double, rounded once; no bk), evaluated in float32"""
+    x, q64, wkv, bkv, w0, b0, w2, b2 = (np.asarray(a, F32) for a in (x, q, wkv, bkv, w0, b0, w2, b2))
+    D = x.shape[-1]
+    u = (wkv[:D].astype(np.float64).T @ q64.astype(np.float64) / np.sqrt(D)).astype(F32)
+    xs = x[:, 1:]
+    sc = xs @ u
+    e = np.exp(sc - sc.max(-1, keepdims=True))
+    inv = F32(1.0) / e.sum(-1, keepdims=True, dtype=F32)
+    xbar = np.einsum("bl,blk->bk", e, xs).astype(F32) * inv
+    o = xbar @ wkv[D:].T + bkv[D:]
+    h = o @ w0.T + b0
+    with np.errstate(over="ignore"):
+        act = h / (F32(1.0) + np.exp(-h))
+    return act @ w2.reshape(-1) + b2.reshape(-1)[0]
+
+
+# ---- the GPU calls (tests marked gpu only)
+def run_ee_probe(case, t_state=0, t_mul=0, add=0, reduce=True):
+    """dd_dev_ee_probe -> (srow [B L + TAIL], out [B + TAIL] or None: the rows-only form)"""
+    c = ctx()
+    B, L, D = case["B"], case["L"], case["D"]
+    srow = np.zeros(B * L + EE_TAIL, F32)
+    out = np.zeros(B + EE_TAIL, F32) if reduce else None
+    c.check(c.lib.dd_dev_ee_probe(c.handle, B, L, D, case["pw"].shape[0], t_state, t_mul, add, P(case["x"]), P(case["pw"]), P(case["pb"]),
+                                  P(srow), P(out), None))
+    return srow, out
+
+
+def run_ee_reduce(s):
+    c = ctx()
+    s = np.ascontiguousarray(s, F32)
+    out = np.zeros(s.shape[0] + EE_TAIL, F32)
+    c.check(c.lib.dd_dev_ee_probe_reduce(c.handle, s.shape[0], s.shape[1], P(s), P(out), None))
+    return out
+
+
+def run_ee_attn(case, images=None):
+    """dd_dev_ee_attn_probe on the case's images (all, or the slice `images`) -> out [B + TAIL]"""
+    c = ctx()
+    x = np.ascontiguousarray(case["x"] if images is None else case["x"][images])
+    out = np.zeros(x.shape[0] + EE_TAIL, F32)
+    c.check(c.lib.dd_dev_ee_attn_probe(c.handle, x.shape[0], case["L"], case["D"], P(x), *(P(case[k]) for k in ("q", "wkv", "bkv", "w0", "b0", "w2", "b2")),
+                                       P(out), None))
+    return out

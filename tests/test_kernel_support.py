@@ -5,7 +5,8 @@ the float64 head against torch's conv2d on a rearrange written out index by inde
 scalar evaluation with explicit roundings, Philox4x32-10 against the published Random123 vectors, the Box-Muller reference against a scalar
 one, and -- on the very inputs the GPU tests use -- that each deliberate error of the reference exceeds the bound the kernel is held to; the
 references of the KL-VAE kernels (tests/test_vae_kernels.py) against torch in float64 and their deliberate errors likewise, the emulation of
-GroupNorm's one-pass fp32 statistics among them."""
+GroupNorm's one-pass fp32 statistics among them; the references of the early-exit probes (tests/test_ee_probes.py) against torch's float64
+modules, their float32 restatements inside the bounds and their deliberate errors outside them."""
 import math
 
 import numpy as np
@@ -404,3 +405,122 @@ def test_vae_output_reference_and_cast_inputs():
     assert (u == 0).any() and (u == 0x80000000).any()
     mag = np.abs(x[x != 0])
     assert mag.min() < 2.0 ** -19 and mag.max() > 2.0 ** 19
+
+
+# ---------------------------------------------------------------------------------------------------------------- the early-exit probes
+@pytest.mark.parametrize("D,L", ks.EE_PROBE_CASES)
+def test_probe_rows_reference_and_its_mutants(D, L):
+    """the inputs of tests/test_ee_probes.py: the reference is torch's float64 Linear + Sigmoid + mean, the float32 restatement of the kernel
+    lies within the bound, every mutant of the rows and of the mean lies outside it"""
+    B = ks.EE_B
+    a = ks.ee_probe_case(B, L, D)
+    s, tol_s = ks.probe_rows_ref(a["x"], a["w"], a["b"])
+    lin = torch.nn.Linear(D, 1).double()
+    with torch.no_grad():
+        lin.weight.copy_(torch.from_numpy(a["w"]).double()[None])
+        lin.bias.fill_(float(a["b"]))
+        st = torch.sigmoid(lin(torch.from_numpy(a["x"]).double())).squeeze(-1)
+    assert np.abs(s - st.numpy()).max() < 1e-13 and tol_s.max() < 1e-3 and (tol_s >= ks.FLOOR).all()      # (the largest: the offset rows)
+    out, tol = ks.probe_mean_ref(s, tol_s)
+    assert np.abs(out - st.mean(1).numpy()).max() < 1e-14 and tol.max() < 2e-4
+    # what the inputs cover: logits within a few units, of +-30, saturated either way, below 2^-126, and the offset rows' cancellation
+    logit = a["x"].astype(np.float64) @ a["w"].astype(np.float64) + 0.7
+    mag = np.abs(a["x"].astype(np.float64)) @ np.abs(a["w"].astype(np.float64))
+    assert (np.abs(logit) < 3).any() and abs(float(a["w"].astype(np.float64).sum()) - 0.02) < 1e-6
+    if L >= 9:
+        assert (np.abs(logit) > 20).any() and (logit > 90).any() and (logit < -90).any() and ((s < ks.FLOOR) & (s > 0)).any()
+        assert (mag > 50 * np.sqrt(D))[np.abs(logit) < 8].any()
+    # the float32 restatement of the kernel, and of the reduce on its rows (against the float64 rows and against its own)
+    s32 = ks.probe_rows_f32(a["x"], a["w"], a["b"])
+    assert gate(s32, s, tol_s, "float32 rows") <= 1.0
+    m32 = ks.probe_mean_f32(s32)
+    assert gate(m32, out, tol, "float32 mean of the float32 rows") <= 1.0
+    assert gate(m32, *ks.probe_mean_ref(s32), "float32 mean against its own rows") <= 1.0
+    # the row mutants: out of bound in the rows and in the mean, of image 0 at least
+    per = -(-L // 8)
+    for mut in ks.EE_ROW_MUTANTS:
+        if mut == "pair_repeats" and per < 5:      # (slices of fewer than five rows have no second row in flight)
+            assert np.array_equal(ks.probe_rows_ref(a["x"], a["w"], a["b"], mutant=mut)[0], s)
+            continue
+        bad = ks.probe_rows_ref(a["x"], a["w"], a["b"], mutant=mut)[0]
+        assert (np.abs(bad - s) > tol_s)[0].any(), mut
+        assert (np.abs(bad.mean(-1) - out) > tol)[0], mut
+    for mut in ks.EE_MEAN_MUTANTS:
+        if mut == "drop_tail" and L % 64 == 0:
+            continue
+        bad = ks.probe_mean_ref(s, tol_s, mutant=mut)[0]
+        assert (~(np.abs(bad - out) <= tol))[0], mut      # (at L = 1 image 2 is one row below 2^-126: nothing to drop)
+
+
+def test_probe_row_selection_reference():
+    """the per-timestep table of test_ee_probe_selects_its_row_from_the_step_state: only the selected row is finite, so the row `add` is NaN"""
+    D, L, t_mul, add = 512, 17, 4, 2
+    for t in (0, 3, 6):
+        a = ks.ee_probe_case(ks.EE_B, L, D, n_probe=7 * 4, row=t * t_mul + add)
+        s, tol_s = ks.probe_rows_ref(a["x"], a["pw"], a["pb"], row=t * t_mul + add)
+        assert np.array_equal(s, ks.probe_rows_ref(a["x"], a["w"], a["b"])[0]) and np.isfinite(s).all()
+        assert np.isnan(a["pw"]).all(1).sum() == 27 and np.isnan(a["pb"]).sum() == 27
+        if t:
+            bad = ks.probe_rows_ref(a["x"], a["pw"], a["pb"], row=t * t_mul + add, mutant="wrong_probe_row", wrong_row=add)[0]
+            with pytest.raises(AssertionError):
+                gate(bad, s, tol_s, "row `add` of the table")
+
+
+@pytest.mark.parametrize("L", ks.EE_REDUCE_L)
+@pytest.mark.parametrize("rows", ks.EE_REDUCE_ROWS)
+def test_probe_reduce_emulation_and_its_mutants(rows, L):
+    s = ks.ee_reduce_rows(rows, L)
+    assert s.min() >= 0 and s.max() <= 1 and (L == 1 or (s == 1).any()) and not ((s > 0) & (s < ks.FLOOR)).any()
+    out, tol = ks.probe_mean_ref(s)
+    assert np.abs(out - torch.from_numpy(s).double().mean(1).numpy()).max() < 1e-15 and (out > 0).all()
+    emu = ks.probe_mean_f32(s)
+    assert emu.dtype == np.float32 and gate(emu, out, tol, "the float32 emulation") <= 1.0
+    # the emulation's order, spelled out for one row with scalars
+    acc = [np.float32(0)] * 64
+    for l in range(L):
+        acc[l % 64] = np.float32(acc[l % 64] + s[0, l])
+    for o in (32, 16, 8, 4, 2, 1):
+        acc = [np.float32(acc[i] + acc[i ^ o]) for i in range(64)]
+    assert np.float32(acc[0] / np.float32(L)) == emu[0]
+    for mut in ks.EE_MEAN_MUTANTS:
+        if mut == "drop_tail" and L % 64 == 0:
+            continue
+        assert (~(np.abs(ks.probe_mean_ref(s, mutant=mut)[0] - out) <= tol)).all(), mut
+
+
+@pytest.mark.parametrize("D,L", ks.EE_ATTN_CASES)
+def test_attn_probe_reference_and_its_mutants(D, L):
+    import torch.nn.functional as TF
+    B = ks.EE_B
+    a = ks.ee_attn_case(B, L, D)
+    ops = [a[k] for k in ("x", "q", "wkv", "bkv", "w0", "b0", "w2", "b2")]
+    out, tol = ks.attn_probe_ref(*ops)
+    # models/early_exit.py AttentionProbe.forward in float64: scaled_dot_product_attention of the learned query, then the Sequential
+    t = {k: torch.from_numpy(v).double() for k, v in a.items() if isinstance(v, np.ndarray)}
+    kv = TF.linear(t["x"][:, 1:], t["wkv"], t["bkv"])
+    k_, v_ = kv[..., :D][:, None], kv[..., D:][:, None]                    # [B, 1 head, n, D]
+    att = TF.scaled_dot_product_attention(t["q"].reshape(1, 1, 1, D).expand(B, 1, 1, D), k_, v_).reshape(B, D)
+    seq = torch.nn.Sequential(torch.nn.Linear(D, D), torch.nn.SiLU(), torch.nn.Linear(D, 1)).double()
+    with torch.no_grad():
+        seq[0].weight.copy_(t["w0"]); seq[0].bias.copy_(t["b0"]); seq[2].weight.copy_(t["w2"][None]); seq[2].bias.copy_(t["b2"])
+        want = seq(att).squeeze(-1).numpy()
+    assert (np.abs(out - want) <= 1e-9 * (1 + np.abs(want))).all()
+    assert (tol[:2] < 1e-2).all() and tol[2] < 0.5      # (image 2: scores near 1e3 carry fp32 errors near 1e-3)
+    # what the inputs hold: bk's constant is large; token 0 would take the softmax over; the last token carries weight; image 1 is one-hot
+    u = a["wkv"][:D].astype(np.float64).T @ a["q"].astype(np.float64) / np.sqrt(D)
+    sc = a["x"].astype(np.float64) @ u
+    assert abs(float(a["bkv"][:D].astype(np.float64) @ a["q"].astype(np.float64))) / np.sqrt(D) > 0.5
+    assert (sc[:, 0] - sc[:, 1:].max(-1))[[0, 2]].min() > 29 and sc[2, 1:].min() > 900
+    if L > 2:
+        assert (sc[1, -1] - sc[1, 1:-1].max()) > 100
+        p0 = np.exp(sc[0, 1:] - sc[0, 1:].max())
+        assert p0[-1] / p0.sum() > 2.0 / L
+    # the float32 restatement of the folded form lies within the bound
+    assert gate(ks.attn_probe_f32(*ops), out, tol, "float32 evaluation of the folded form") <= 1.0
+    for mut in ks.EE_ATTN_MUTANTS:
+        bad = ks.attn_probe_ref(*ops, mutant=mut)[0]
+        if (mut == "drop_far_tokens" and L <= 257) or (mut == "no_scale" and L == 2):      # (no token behind index 256; one token: p = 1)
+            assert np.array_equal(bad, out)
+            continue
+        over = np.abs(bad - out) > tol
+        assert over[1 if mut == "drop_far_tokens" else 0], (mut, np.abs(bad - out) / tol)

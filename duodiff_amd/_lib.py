@@ -81,6 +81,23 @@ class dd_ee_sample_args(C.Structure):
                 ("y_dev", C.c_void_p), ("x_dev", C.c_void_p), ("err_dev", C.c_void_p), ("idx_dev", C.c_void_p)]
 
 
+class dd_scan_args(C.Structure):
+    """dd_scan_error (include/duodiff.h): the images, the scan's rows and where the per-image errors go"""
+    _fields_ = [("model", C.c_void_p), ("x0_dev", C.c_void_p), ("y_dev", C.c_void_p), ("B", C.c_int32), ("n_steps", C.c_int32)] + \
+               [(n, C.POINTER(C.c_float)) for n in ("t", "ka", "kb", "tz", "t0", "tx")] + \
+               [("seed", C.c_uint64), ("counter_base", C.c_int32), ("noise_mode", C.c_int32), ("use_graph", C.c_int32),
+                ("reserved", C.c_int32), ("err_dev", C.c_void_p)]
+    x_dev = property(lambda self: self.x0_dev, lambda self, v: setattr(self, "x0_dev", v))     # (the name engine._run_loop fills the image tensor in by)
+
+
+class dd_dev_scan_args(C.Structure):
+    """the operands of dd_dev_scan_diffuse / dd_dev_scan_error (include/duodiff_dev.h), field for field"""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "C", "S", "b0", "B_all", "k")] +
+                [(n, C.c_float) for n in ("t_model", "ka", "kb", "tz", "t0", "tx")] +
+                [("ctr", C.c_int32), ("next_t_model", C.c_float), ("seed", C.c_uint64), ("advance", C.c_int32), ("t_out", C.c_int32),
+                 ("t_final_out", C.c_int32), ("t_model_out", C.c_float), ("iters", C.c_int32), ("ms_out", C.c_float)])
+
+
 class dd_dev_final_args(C.Structure):
     """the operands of dd_dev_final (include/duodiff_dev.h), field for field"""
     _fields_ = ([(n, C.c_int32) for n in ("B", "C", "S", "P", "L", "extras", "b0", "images")] +
@@ -162,6 +179,7 @@ SIGNATURES = {
                                                 C.POINTER(dd_autoguidance), C.POINTER(dd_known_region), C.POINTER(dd_x0_threshold), C.c_void_p]),
     "dd_set_image_seeds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "dd_noise_images": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "dd_scan_error": (C.c_int, [C.c_void_p, C.POINTER(dd_scan_args), C.c_void_p]),
     "dd_bench_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
     "dd_vae_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "dd_vae_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
@@ -205,6 +223,8 @@ SIGNATURES = {
     "dd_dev_ee_attn_probe": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 10),
     "dd_dev_final": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_final_args), C.c_void_p]),
     "dd_dev_final_seeded": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_final_args), C.c_void_p, C.c_int, C.c_void_p]),
+    "dd_dev_scan_diffuse": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_scan_args), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "dd_dev_scan_error": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_scan_args), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "dd_dev_poison_workspaces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "dd_dev_graph_captures": (C.c_longlong, [C.c_void_p]),
     "dd_dev_last_sample_chains": (C.c_int, [C.c_void_p]),

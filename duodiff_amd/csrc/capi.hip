@@ -66,6 +66,7 @@ void dd_ctx_destroy(dd_ctx* c) {
     if (c->coef) (void)hipFree(c->coef);
     c->x_stage.release(); c->y_stage.release(); c->h_stage.release(); c->k_stage.release(); c->m_stage.release();
     c->atab.release(); c->htab.release(); c->ktab.release(); c->seeds_stage.release();
+    c->stab.release(); c->scan_ws.release();
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     delete c;
 }

@@ -65,6 +65,13 @@ struct KnownRow {
     float ka, kb;
 };
 
+// one step of the denoising-error scan (dd_scan_error; step_update.h scan_target): the images are noised to x_t = ka x0 + kb z, the model
+// sees t_model, its output is compared with tz z + t0 x0 + tx x_t
+struct ScanRow {
+    float t_model, ka, kb, tz, t0, tx;
+    int ctr, pad;                 // ctr: the Philox counter of this step's z (counter_base + the step's index in the call)
+};
+
 enum GemmEpilogue {
     EPI_STORE = 0,        // out = T(acc)                                  (qkv)
     EPI_BIAS_GELU = 1,    // out = T(gelu_erf(acc + bias))                 (fc1)
@@ -473,6 +480,14 @@ hipError_t launch_ee_mean_combine(const float* s0, const float* s1, float* err, 
 hipError_t launch_set_state(StepState* st, int t, unsigned long long seed, hipStream_t s);
 hipError_t launch_set_state_table(StepState* st, const AffineRow* atab, unsigned long long seed, hipStream_t s);   // step index 0
 hipError_t launch_set_state_float(StepState* st, float t, hipStream_t s);
+// ---- the denoising-error scan (scan.hip), B images [B, C, S, S] of a whole batch of B_all whose first is image b0; seeds as FinalArgs::seeds.
+// Both follow the step-state contract: diffuse is the step's FIRST kernel (row st->t), error its LAST (row st->t_final; advance != 0: one
+// thread hands on t + 1 and row t + 1's t_model).  C outside 1..4, C S S > 2^24 or a null pointer: hipErrorInvalidValue, nothing launched.
+hipError_t launch_scan_diffuse(const float* x0, float* xt, const StepState* st, const ScanRow* tab, const unsigned long long* seeds, int B, int C,
+                               int S, int b0, hipStream_t s);                       // xt = ka x0 + kb z
+hipError_t launch_scan_error(const float* x0, const float* m, float* err, StepState* st, const ScanRow* tab, const unsigned long long* seeds,
+                             int B, int C, int S, int b0, int B_all, int advance, hipStream_t s);   // err[t_final B_all + b0 + b]
+hipError_t launch_set_state_scan(StepState* st, const ScanRow* tab, unsigned long long seed, hipStream_t s);   // step index 0
 hipError_t launch_guided_labels(const long long* y, long long* out, int B, long long null_label, hipStream_t s);   // out [2 B] = [y [0, B) | null_label x B]
 // (x + 1) / 2, NCHW -> NHWC: the output convention of reference sampler.py:145-146
 hipError_t launch_to_images(const float* x, float* out, int B, int C, int S, hipStream_t s);

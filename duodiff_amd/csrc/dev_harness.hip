@@ -1,5 +1,5 @@
 // The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_block_tail, dd_dev_block_tail_frag, dd_dev_qkv_attention, dd_dev_qkv_attention_rows, dd_dev_qkv_attention_frag, dd_dev_v_identity, dd_dev_v_copy, dd_dev_head_dec, dd_dev_gemm,
-// dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather, dd_dev_groupnorm, dd_dev_softmax_rows, dd_dev_vae_input, dd_dev_vae_output, dd_dev_vae_moments, dd_dev_cast, dd_dev_ee_probe, dd_dev_ee_probe_reduce, dd_dev_ee_attn_probe, dd_dev_final): test scaffolding, not product.  Each one owns its host operands, device buffers, canaries and
+// dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather, dd_dev_groupnorm, dd_dev_softmax_rows, dd_dev_vae_input, dd_dev_vae_output, dd_dev_vae_moments, dd_dev_cast, dd_dev_ee_probe, dd_dev_ee_probe_reduce, dd_dev_ee_attn_probe, dd_dev_final, dd_dev_scan_diffuse, dd_dev_scan_error): test scaffolding, not product.  Each one owns its host operands, device buffers, canaries and
 // downloads, and nothing of the launch: the weight images come from finalize's packers and the launch arguments from the model's builders (launch_args.h:
 // dd_dev_mlp and dd_dev_block_tail* run block_tail_plan / block_tail_finish exactly as Backbone::block_tail does), then `iters` further launch sequences
 // are timed.  Buffers, transfers, timing and HIP errors go through one DevScope (dev_scope.h); of the context it reads num_cus and dev_flags (engine_state.h).
@@ -882,7 +882,77 @@ static int dev_final(dd_ctx* c, dd_dev_final_args* p, const uint64_t* seeds_host
     return dev.status();
 }
 
+// dd_dev_scan_diffuse (m_host null, xt_host set) and dd_dev_scan_error (m_host and err_host set): the checks, the step state and the row table they share
+static int dev_scan(dd_ctx* c, dd_dev_scan_args* p, const float* x0_host, const float* m_host, const uint64_t* seeds_host, int n_seeds,
+                    float* xt_host, float* err_host, void* stream) {
+    if (!c || !p || !x0_host || (!xt_host && (!m_host || !err_host))) return DD_ERR_INVALID;
+    const dd_dev_scan_args& q = *p;
+    if (q.B < 1 || q.B > 4096 || q.C < 1 || q.S < 1 || q.S > 4096 || q.b0 < 0 || q.B_all > (1 << 20) || (long long)q.b0 + q.B > q.B_all || q.k < 0 ||
+        q.k > 65535 || ((long long)q.k + 1) * q.B_all > (1ll << 24) || q.ctr < 0 || q.iters < 0 || q.iters > 10000 || (q.iters > 0 && q.advance))
+        return DD_ERR_INVALID;
+    if ((seeds_host != nullptr) != (n_seeds > 0) || n_seeds > (1 << 22) || (seeds_host && n_seeds < q.b0 + q.B)) return DD_ERR_INVALID;
+    if (q.C > 4 || (long long)q.C * q.S * q.S > (1ll << 24)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "scan: 1..4 channels, at most 2^24 elements per image");
+    if ((long long)q.B * q.C * q.S * q.S > (1ll << 26)) return DD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)q.B * q.C * q.S * q.S, rows = (size_t)q.k + 2;
+    DevScope dev(c);
+    const StepState st0{q.k, q.t_model, q.seed, q.k, 0};
+    StepState* st = dev.upload(&st0, sizeof st0);
+    ScanRow* tab = dev.filled<ScanRow>(rows * sizeof(ScanRow), 0xFF);
+    const ScanRow row{q.t_model, q.ka, q.kb, q.tz, q.t0, q.tx, q.ctr, 0};
+    if (dev.ok()) dev.ok(hipMemcpy(tab + q.k, &row, sizeof row, hipMemcpyHostToDevice), "hipMemcpy to the device");
+    if (dev.ok()) dev.ok(hipMemcpy(&tab[q.k + 1].t_model, &q.next_t_model, sizeof(float), hipMemcpyHostToDevice), "hipMemcpy to the device");
+    const unsigned long long* seeds = seeds_host ? (const unsigned long long*)dev.upload(seeds_host, (size_t)n_seeds * sizeof(uint64_t)) : nullptr;
+    // an input between 8 + 8 elements the kernel must never read
+    auto fenced = [&](const float* host) {
+        float* d = dev.filled<float>((n + 16) * 4, 0xFF);
+        if (dev.ok()) dev.ok(hipMemcpy(d + 8, host, n * 4, hipMemcpyHostToDevice), "hipMemcpy to the device");
+        return d + 8;
+    };
+    const float* dX0 = fenced(x0_host);
+    hipError_t first = hipSuccess;
+    float* dOut = nullptr;
+    const float* dM = nullptr;
+    size_t out_elems = 0;
+    if (xt_host) {
+        out_elems = n + 16;
+        dOut = dev.filled<float>(out_elems * 4, 0xFF);
+        if (dev.ok()) first = launch_scan_diffuse(dX0, dOut + 8, st, tab, seeds, q.B, q.C, q.S, q.b0, s);
+    } else {
+        dM = fenced(m_host);
+        out_elems = ((size_t)q.k + 1) * q.B_all + 8;
+        dOut = dev.filled<float>(out_elems * 4, 0xFF);
+        if (dev.ok()) first = launch_scan_error(dX0, dM, dOut, st, tab, seeds, q.B, q.C, q.S, q.b0, q.B_all, q.advance, s);
+    }
+    if (first == hipErrorInvalidValue) return ctx_fail(c, DD_ERR_INVALID, "scan: operands the launcher refuses");      // (refused before any launch)
+    DEV_HIP(dev, first);
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(xt_host ? xt_host : err_host, dOut, out_elems * 4);
+    StepState st1{};
+    dev.download(&st1, st, sizeof st1);
+    if (dev.ok()) { p->t_out = st1.t; p->t_final_out = st1.t_final; p->t_model_out = st1.t_model; }
+    if (q.iters > 0 && dev.ok()) {      // (advance == 0: the launch leaves the state as it found it)
+        float ms = 0.f;
+        DEV_HIP(dev, time_launches(s, q.iters, [&] {
+            return xt_host ? launch_scan_diffuse(dX0, dOut + 8, st, tab, seeds, q.B, q.C, q.S, q.b0, s)
+                           : launch_scan_error(dX0, dM, dOut, st, tab, seeds, q.B, q.C, q.S, q.b0, q.B_all, 0, s);
+        }, &ms));
+        p->ms_out = ms;
+    }
+    return dev.status();
+}
+
 extern "C" {
+
+int dd_dev_scan_diffuse(dd_ctx* c, dd_dev_scan_args* p, const float* x0_host, const uint64_t* seeds_host, int n_seeds, float* xt_host, void* stream) {
+    if (!xt_host) return DD_ERR_INVALID;
+    return dev_scan(c, p, x0_host, nullptr, seeds_host, n_seeds, xt_host, nullptr, stream);
+}
+int dd_dev_scan_error(dd_ctx* c, dd_dev_scan_args* p, const float* x0_host, const float* m_host, const uint64_t* seeds_host, int n_seeds,
+                      float* err_host, void* stream) {
+    if (!m_host || !err_host) return DD_ERR_INVALID;
+    return dev_scan(c, p, x0_host, m_host, seeds_host, n_seeds, nullptr, err_host, stream);
+}
 
 int dd_dev_final(dd_ctx* c, dd_dev_final_args* p, void* stream) { return dev_final(c, p, nullptr, 0, stream); }
 

@@ -79,6 +79,9 @@ struct dd_ctx {
     dd::DevBuf<float> k_stage;       //   and the known image and mask the loop reads (x0 [B, C, S, S] | mask [B, 1, S, S], staged like x)
     dd::DevBuf<float> m_stage;       // dd_sample_multistep_threshold: the step's (guided) model output [B, C, S, S], chain k's images at its first image:
                                  //   written by the output head and read by threshold_step_kernel within one step, never across steps
+    dd::RowTable<dd::ScanRow> stab;      // dd_scan_error: the scan's rows,
+    dd::DevBuf<float> scan_ws;       //   and its scratch, x_t | eps ([B, C, S, S] each; chain k's images at its first image) | err [n, B]: grown before the loop,
+                                 //   never on the launch path
     // dd_set_image_seeds: the caller's per-image seeds (device, seeds_n of them; null: the plain noise), and the context's own copy that
     // the kernels read -- copied at every call that draws device noise (stage_image_seeds), so a captured step is reused across seeds
     const uint64_t* seeds_user = nullptr;
@@ -137,7 +140,7 @@ struct GraphKey {
 };
 
 // the captured step of each sampling loop: dd_model::graph[kind][chain]
-enum GraphKind { GRAPH_DDPM, GRAPH_AFFINE, GRAPH_EARLY_EXIT, GRAPH_MULTISTEP, GRAPH_KINDS };
+enum GraphKind { GRAPH_DDPM, GRAPH_AFFINE, GRAPH_EARLY_EXIT, GRAPH_MULTISTEP, GRAPH_SCAN, GRAPH_KINDS };
 
 // The activation workspace of one chain: dd_sample runs a large batch as TWO independent half-batch chains on two streams (one
 // chain's HBM-bound kernel phases then run under the other's MFMA phases); the second chain has its own copy of every buffer.

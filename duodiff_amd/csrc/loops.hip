@@ -440,9 +440,71 @@ int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, Mods mo, void
     };
     return run_loop(c, L, s);
 }
+
+// dd_scan_error: the denoising-error scan as one more loop of run_loop.  A step is diffuse -> forward_eps -> error (scan.hip); the
+// images x0 are staged like a known image (k_stage: a later call with other tensors of the same shape replays the same graphs), the
+// rows live in the context's stab, and x_t, the model output and the err rows in its scan_ws (x_t | eps | err).  With graphs run_loop's
+// staged x is the chain's x_t buffer (scan_ws' x_t part then only passes through its copies); eagerly the loop runs on scan_ws itself.
+// The err rows are disjoint per image: two half-batch chains need no join kernel.
+int scan_error(dd_ctx* c, const dd_scan_args* a, void* stream) {
+    if (!c || !a) return DD_ERR_INVALID;
+    dd_model* m = a->model;
+    if (m && m->ctx == c && m->ee_type >= 0)
+        return ctx_fail(c, DD_ERR_INVALID, "dd_scan_error takes a plain model, not one created with dd_model_enable_early_exit");
+    int rc = check_call(c, m, a->B, a->y_dev);
+    if (rc) return rc;
+    if (!a->x0_dev || !a->err_dev || !a->t || !a->ka || !a->kb || !a->tz || !a->t0 || !a->tx) return ctx_fail(c, DD_ERR_INVALID, "null tensor / table");
+    if (a->n_steps < 1 || a->n_steps > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "n_steps outside [1, 2^20]");
+    if (a->counter_base < 0 || a->counter_base > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "counter_base outside [0, 2^20]");
+    if (a->noise_mode != DD_NOISE_PHILOX) return ctx_fail(c, DD_ERR_INVALID, "dd_scan_error draws its noise on the device: noise_mode must be DD_NOISE_PHILOX");
+    if ((rc = check_image_seeds(c, a->noise_mode, a->B))) return rc;
+    const int C = m->cfg.in_chans, S = m->cfg.img_size;
+    const size_t chw = (size_t)C * S * S, elems = (size_t)a->B * chw;
+    if (C < 1 || C > 4 || chw > ((size_t)1 << 24))
+        return ctx_fail(c, DD_ERR_UNSUPPORTED, "the scan kernels take 1..4 channels and at most 2^24 elements per image");
+    hipStream_t s = (hipStream_t)stream;
+    const int n = a->n_steps;
+    const unsigned long long* seeds = nullptr;
+    if ((rc = stage_image_seeds(c, a->noise_mode, s, &seeds))) return rc;
+    // n rows + one more whose timestep the last step hands on (never used), as the step table of dd_sample_affine
+    rc = upload_rows(c, c->stab, (size_t)n + 1, s, [a, n](size_t k) {
+        return k < (size_t)n ? ScanRow{a->t[k], a->ka[k], a->kb[k], a->tz[k], a->t0[k], a->tx[k], a->counter_base + (int)k, 0}
+                             : ScanRow{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0, 0};
+    });
+    if (rc) return rc;
+    if ((rc = c->k_stage.grow(c, elems))) return rc;
+    const size_t err_elems = (size_t)n * a->B;
+    if ((rc = c->scan_ws.grow(c, 2 * elems + err_elems))) return rc;
+    DD_HIP(c, hipMemcpyAsync(c->k_stage.p, a->x0_dev, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    const ScanRow* tab = c->stab.dev.p;
+    const float* x0_run = c->k_stage.p;
+    float* eps_run = c->scan_ws.p + elems;
+    float* err_run = eps_run + elems;       // [n, B]: copied to the caller's tensor behind the loop, so a captured step never names it
+    Loop L{GRAPH_SCAN, m, nullptr, n, -1, c->scan_ws.p, a->y_dev, a->B, Mods{.seeds = seeds}, a->use_graph != 0};
+    L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_scan(st, tab, (unsigned long long)a->seed, ss); };
+    L.key = [&](GraphKey& k, const Slice& sl) {
+        k.noise = a->noise_mode; k.atab = tab; k.kx0 = x0_run + (size_t)sl.b0 * chw; k.aux0 = err_run; k.aux1 = eps_run;
+        if (sl.chains == 2 && sl.chain == 0) k.b0 = -1;     // (chain 0 of two writes rows of 2 B images -- not the whole batch's graph)
+    };
+    L.step = [&](dd_model* mm, const Chain& ch, const Slice& sl, hipStream_t ss) -> int {
+        const float* x0 = x0_run + (size_t)sl.b0 * chw;
+        float* eps = eps_run + (size_t)sl.b0 * chw;
+        DD_HIP(c, launch_scan_diffuse(x0, sl.x, ch.st, tab, sl.mods.seeds, sl.B, C, S, sl.b0, ss));
+        if (int r = forward_eps(c, mm, ch, sl.x, sl.y, eps, sl.B, ss, {})) return r;
+        DD_HIP(c, launch_scan_error(x0, eps, err_run, ch.st, tab, sl.mods.seeds, sl.B, C, S, sl.b0, a->B, 1, ss));
+        return DD_OK;
+    };
+    L.tail = [&](int, hipStream_t ss) -> int {
+        DD_HIP(c, hipMemcpyAsync(a->err_dev, err_run, err_elems * sizeof(float), hipMemcpyDeviceToDevice, ss));
+        return DD_OK;
+    };
+    return run_loop(c, L, s);
+}
 }  // namespace
 
 extern "C" {
+
+int dd_scan_error(dd_ctx* c, const dd_scan_args* a, void* stream) { return scan_error(c, a, stream); }
 
 int dd_sample(dd_ctx* c, const dd_sample_args* a, void* stream) { return sample_ddpm(c, a, Mods{}, stream); }
 int dd_sample_guided(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* stream) { return sample_ddpm(c, a, guided(g), stream); }

@@ -14,6 +14,7 @@ namespace dd {
 // the same key, pixel and counter give two independent draws.  PHILOX_START is the stream of x_T (dd_noise_images).
 // ------------------------------------------------------------------------------------------
 constexpr unsigned PHILOX_STEP = 0x5eedu, PHILOX_KNOWN = 0x6b6e6f77u, PHILOX_START = 0x78545f30u;
+constexpr unsigned PHILOX_SCAN = 0x7363616e;      // "scan": the z that noises a real image in the denoising-error scan (scan_target below)
 
 // The draw site, defined once: the Philox key and pixel id of pixel p = y S + x (hw = S S pixels per image) of image bg of the WHOLE batch
 // (bg = the launch's first image b0 + the launch's image b: a half-batch chain draws what the undivided batch would).
@@ -161,6 +162,24 @@ struct KnownRule {
     __device__ __forceinline__ float apply(float xp, float x0, float m, float z2) const { return known(xp, x0, m, row.ka, row.kb, z2, philox); }
     __device__ __forceinline__ float value(float x0, float z2) const { return known_value(x0, row.ka, row.kb, z2, philox); }
 };
+
+// The denoising-error scan (dd_scan_error; reference trainer.py:307-352 evaluated at one timestep): an image x0 is noised to row k's level
+// with a z of its own stream word, x_t = known_value(x0, ka, kb, z, true) = ka x0 + kb z, the model sees x_t, and its output m is compared with
+//     tgt = tz z + t0 x0 + tx x_t      predict_noise (1, 0, 0) | predict_original (0, 1, 0) | predict_previous (0, clean_image_coef, noisy_image_coef)
+//     err = (1 / CHW) sum (m - tgt)^2
+// each product, sum and square rounded on its own, the sum taken left to right.  The reduction order belongs to the kernel (scan.hip).
+__device__ __forceinline__ float scan_target(float z, float x0, float xt, float tz, float t0, float tx) {
+#pragma clang fp contract(off)
+    return tz * z + t0 * x0 + tx * xt;
+}
+// one element's share of the sum: acc + (m - tgt)^2
+__device__ __forceinline__ float scan_accumulate(float acc, float m, float tgt) {
+#pragma clang fp contract(off)
+    const float d = m - tgt;
+    return acc + d * d;
+}
+// the mean over an image's n = C H W elements (n <= 2^24: exact as a float), a correctly rounded division
+__device__ __forceinline__ float scan_mean(float sum, int n) { return __fdiv_rn(sum, (float)n); }
 
 // x0 thresholding of a multistep step (dd_x0_threshold): the step's data prediction x0 = p x + q m (StepRule::history) is pulled back
 // before it drives the update, and the update then takes it in m's place -- a and b are the UNFOLDED row, b multiplying xh:

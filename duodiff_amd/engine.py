@@ -633,3 +633,28 @@ def sample_early_exit_loop(ctx: Context, model: Model, x, threshold, *, t_start=
     args.idx_dev = idx.data_ptr() if idx is not None else None
     call = lambda st: ctx.lib.dd_sample_early_exit(ctx.handle, C.byref(args), st)
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
+
+
+def scan_error_loop(ctx: Context, model: Model, x0, rows, *, y=None, seed=0, counter_base=0, err=None, use_graph=True, stream=None):
+    """dd_scan_error: the denoising error of `model` on the images x0 [B, C, S, S] (model space; only read) at every row of `rows`
+    (step_plan.scan_rows, or any slice of it): step k noises the images to x_t = ka[k] x0 + kb[k] z with the image's own Philox draw
+    (counter counter_base + k, a stream word of its own; per-image seeds are honoured), runs the model at t[k] and writes
+    err[k, i] = mean((model(x_t) - (tz[k] z + t0[k] x0 + tx[k] x_t))^2) over image i.  One device-resident loop, graph replays and
+    half-batch chains as sample_loop.  Returns err [n, B] fp32 on the device.  Two models called with the same x0, seed (or image
+    seeds) and counter_base see the same (x0, z, t): a paired comparison."""
+    assert x0.is_cuda and x0.dtype == torch.float32 and x0.is_contiguous() and x0.dim() == 4
+    args = L.dd_scan_args()
+    tab = {k: np.ascontiguousarray(rows[k], np.float32) for k in ("t", "ka", "kb", "tz", "t0", "tx")}
+    n = len(tab["t"])
+    assert all(v.shape == (n,) for v in tab.values())
+    for k, v in tab.items():
+        setattr(args, k, v.ctypes.data_as(C.POINTER(C.c_float)))
+    args.model = model.handle
+    args.n_steps = n
+    args.counter_base = int(counter_base)
+    err = torch.empty(n, x0.shape[0], device=x0.device, dtype=torch.float32) if err is None else err
+    assert err.is_cuda and err.dtype == torch.float32 and err.is_contiguous() and tuple(err.shape) == (n, x0.shape[0])
+    args.err_dev = err.data_ptr()
+    _run_loop(ctx, args, x0, y, seed, "philox", use_graph, stream, lambda st: ctx.lib.dd_scan_error(ctx.handle, C.byref(args), st))
+    return err
+

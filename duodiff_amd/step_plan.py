@@ -271,6 +271,37 @@ def known_rows(plan):
     return ka, kb
 
 
+SCAN_PARAMETRIZATIONS = ("predict_noise", "predict_original", "predict_previous")
+
+
+def scan_rows(timesteps, parametrization):
+    """The fp32 rows of the denoising-error scan (dd_scan_error) at the integer timesteps given, from the engine's bit-exact schedule
+    tables, each coefficient computed in float64 and rounded once:
+        x_t = ka x0 + kb z with ka = sqrt(alphas_bar[t]), kb = sqrt(1 - alphas_bar[t])  -- what known_rows gives a step landing on t
+        tgt = tz z + t0 x0 + tx x_t, the training target of the reference (trainer.py:319-352): predict_noise (1, 0, 0), predict_original
+        (0, 1, 0), predict_previous (0, clean_image_coef, noisy_image_coef) = (0, sqrt(abar_prev) beta / (1 - abar), sqrt(alpha) (1 - abar_prev) / (1 - abar))
+    Returns a dict of float32 arrays t, ka, kb, tz, t0, tx.  Host arithmetic only."""
+    if parametrization not in SCAN_PARAMETRIZATIONS:
+        raise ValueError(f"parametrization must be one of {SCAN_PARAMETRIZATIONS}, not {parametrization!r}")
+    ts = np.asarray(timesteps, np.int64)
+    if ts.ndim != 1 or len(ts) < 1 or (ts < 0).any() or (ts > 999).any():
+        raise ValueError("timesteps must be a non-empty list of integers in [0, 999]")
+    tb = {k: v.astype(np.float64) for k, v in schedule_tables().items()}
+    ab = tb["alphas_bar"][ts]
+    n = len(ts)
+    if parametrization == "predict_noise":
+        tz, t0, tx = np.ones(n), np.zeros(n), np.zeros(n)
+    elif parametrization == "predict_original":
+        tz, t0, tx = np.zeros(n), np.ones(n), np.zeros(n)
+    else:
+        ab_p = tb["alphas_bar_previous"][ts]
+        tz = np.zeros(n)
+        t0 = np.sqrt(ab_p) * tb["betas"][ts] / (1.0 - ab)
+        tx = np.sqrt(tb["alphas"][ts]) * (1.0 - ab_p) / (1.0 - ab)
+    rows = {"t": ts, "ka": np.sqrt(ab), "kb": np.sqrt(1.0 - ab), "tz": tz, "t0": t0, "tx": tx}
+    return {k: np.ascontiguousarray(v, np.float32) for k, v in rows.items()}
+
+
 def _affine_rows(ts, coefficients, noise):
     a, b, c = zip(*coefficients) if coefficients else ((), (), ())
     return {"t": np.array(ts, np.float32), "a": np.array(a, np.float32), "b": np.array(b, np.float32), "c": np.array(c, np.float32),

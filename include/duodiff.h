@@ -450,6 +450,42 @@ int dd_set_image_seeds(dd_ctx* ctx, const uint64_t* seeds_dev, int n);
  * DD_ERR_INVALID with nothing launched; B == 0 does nothing. */
 int dd_noise_images(dd_ctx* ctx, uint64_t seed, const uint64_t* seeds_dev, int counter, float* out_dev, int B, int C, int S, void* stream);
 
+/* ---- denoising-error scan on real images (version 6 addition: new symbols only) ---------------- */
+/* The training loss of the reference (trainer.py:307-352) evaluated per timestep on the caller's images, as one device-resident loop:
+ * for step k = 0 .. n_steps - 1 and image i of x0_dev [B, C, S, S] (model space: pixels in [-1, 1], or latents)
+ *     z    = the image's Philox draw with counter counter_base + k and a stream word of its own (independent of every sampling draw)
+ *     x_t  = ka[k] x0 + kb[k] z                                  (each product rounded on its own, as the known region's rule)
+ *     m    = model(x_t, t[k], y)
+ *     tgt  = tz[k] z + t0[k] x0 + tx[k] x_t                      predict_noise (1, 0, 0) | predict_original (0, 1, 0) | predict_previous (0, c_clean, c_noisy)
+ *     err_dev[k B + i] = (1 / CHW) sum (m - tgt)^2               fp32, in a summation order that depends on (C, S) alone
+ * One hipGraph for the step, replayed (use_graph), or the same launches eagerly, bit for bit the same; two half-batch chains as dd_sample.
+ * x0_dev is only read; x_t and the model output live in scratch of the context.  Per-image seeds (dd_set_image_seeds) are honoured like
+ * in every other draw: an image's numbers then depend on the image and its seed, not on its batch.  duodiff_amd/step_plan.py scan_rows
+ * builds the rows from the bit-exact schedule tables.
+ * DD_ERR_INVALID (with dd_last_error) before anything is enqueued: a null pointer, n_steps outside [1, 2^20], counter_base outside [0, 2^20],
+ * a noise_mode other than DD_NOISE_PHILOX, an early-exit model, labels that do not fit the model, B outside [1, max_batch], image seeds
+ * set for another B.  DD_ERR_UNSUPPORTED: in_chans outside 1..4 or more than 2^24 elements per image.  Guidance is not accepted. */
+typedef struct dd_scan_args {
+    dd_model* model;
+    const float* x0_dev;    /* [B,C,S,S] fp32, read only                                                        */
+    const int64_t* y_dev;   /* [B] or NULL                                                                      */
+    int32_t B;
+    int32_t n_steps;
+    const float* t;         /* host [n_steps]: the timestep the model sees at step k                            */
+    const float* ka;        /* host [n_steps]: x_t = ka x0 + kb z                                               */
+    const float* kb;
+    const float* tz;        /* host [n_steps]: tgt = tz z + t0 x0 + tx x_t                                      */
+    const float* t0;
+    const float* tx;
+    uint64_t seed;          /* the Philox key (unused while image seeds are set)                                */
+    int32_t counter_base;   /* step k draws with counter counter_base + k: repeats pass r n_steps for fresh z   */
+    int32_t noise_mode;     /* DD_NOISE_PHILOX                                                                  */
+    int32_t use_graph;
+    int32_t reserved;
+    float* err_dev;         /* out [n_steps, B] fp32                                                            */
+} dd_scan_args;
+int dd_scan_error(dd_ctx* ctx, const dd_scan_args* args, void* stream);
+
 /* ---- KL-VAE decode: autoencoder.decode(x) at sampler.py:141-143 ---------------- */
 /* Replaces FrozenAutoencoderKL.decode (models/utils/autoencoder.py:486-490, Decoder :320-449) for the fixed ddconfig of
  * get_autoencoder (:503-516).  Parameters are set by the reference state_dict keys ("decoder.*", "post_quant_conv.*";

@@ -306,6 +306,37 @@ int dd_dev_final(dd_ctx* ctx, dd_dev_final_args* args, void* stream);
  * the draw.  NULL, n < 1, n < b0 + B or n > 2^22: DD_ERR_INVALID, nothing launched. */
 int dd_dev_final_seeded(dd_ctx* ctx, dd_dev_final_args* args, const uint64_t* seeds_host, int n, void* stream);
 
+/* Development harnesses for the two kernels of the denoising-error scan (scan.hip; include/duodiff.h dd_scan_error), each through its
+ * production launch_* function, ONE launch.  The launch covers B images of C x S x S, images [b0, b0 + B) of a whole batch of B_all >= b0 + B.
+ * The step state is created on the device with t = t_final = k (the step index, 0..65535), seed, and t_model = the row's; the row table has
+ * k + 2 rows, row k holding the caller's coefficients (t_model, ka, kb, tz, t0, tx, ctr), row k + 1 next_t_model, every other row and field
+ * 0xFF bytes.  seeds_host [n_seeds] (or NULL, 0): the per-image seeds of the WHOLE batch, n_seeds >= b0 + B.  t_out, t_final_out and
+ * t_model_out are read back after the launch.
+ * dd_dev_scan_diffuse: x0_host [B, C, S, S] -> xt_host [8 + B C S S + 8], filled with 0xFF bytes before the launch and returned WHOLE (the
+ *   data behind 8 canary elements and in front of 8 more).
+ * dd_dev_scan_error: x0_host, m_host [B, C, S, S] (their device copies sit between 8 + 8 elements of 0xFF bytes, NaN, which the kernel must
+ *   never read) -> err_host [(k + 1) B_all + 8], filled with 0xFF bytes before the launch and returned WHOLE: the launch writes elements
+ *   k B_all + b0 .. + B - 1.  advance as FinalArgs::advance.
+ * Everything is checked before anything touches the GPU (B in 1..4096, S in 1..4096, b0 >= 0, B_all <= 2^20, (k + 1) B_all <= 2^24,
+ * B C S S <= 2^26, n_seeds <= 2^22, iters in 0..10000 and 0 with advance: DD_ERR_INVALID); a shape the launcher refuses (C outside 1..4, C S S > 2^24) is DD_ERR_UNSUPPORTED with
+ * nothing launched. */
+typedef struct dd_dev_scan_args {
+    int B, C, S, b0, B_all, k;
+    float t_model, ka, kb, tz, t0, tx;
+    int ctr;
+    float next_t_model;
+    unsigned long long seed;
+    int advance;
+    int t_out, t_final_out;
+    float t_model_out;
+    int iters;          /* > 0 (needs advance == 0): `iters` more launches between two events -> ms_out, the mean of one */
+    float ms_out;
+} dd_dev_scan_args;
+int dd_dev_scan_diffuse(dd_ctx* ctx, dd_dev_scan_args* args, const float* x0_host, const uint64_t* seeds_host, int n_seeds, float* xt_host,
+                        void* stream);
+int dd_dev_scan_error(dd_ctx* ctx, dd_dev_scan_args* args, const float* x0_host, const float* m_host, const uint64_t* seeds_host, int n_seeds,
+                      float* err_host, void* stream);
+
 /* Kernel-variant switches for same-process A/B runs (tools/mlp_check.py, tools/all_configs.py).  They act on models
  * FINALIZED after the call (the kernel paths a model takes, the DD_DEV_NO_FRAG_* hand-offs among them) or on launches made after it; the product never sets them and the library
  * reads no environment variable. */

@@ -98,6 +98,20 @@ class dd_dev_scan_args(C.Structure):
                  ("t_final_out", C.c_int32), ("t_model_out", C.c_float), ("iters", C.c_int32), ("ms_out", C.c_float)])
 
 
+class dd_scan_exits_args(C.Structure):
+    """dd_scan_error_early_exit (include/duodiff.h): dd_scan_args with the three result tables in err_dev's place"""
+    _fields_ = dd_scan_args._fields_[:-1] + [("mse_dev", C.c_void_p), ("target_dev", C.c_void_p), ("pred_dev", C.c_void_p)]
+    x_dev = property(lambda self: self.x0_dev, lambda self, v: setattr(self, "x0_dev", v))
+
+
+class dd_dev_scan_exits_args(C.Structure):
+    """the operands of dd_dev_scan_exits_error (include/duodiff_dev.h), field for field"""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "C", "S", "exits", "b0", "B_all", "k", "t", "next")] +
+                [(n, C.c_float) for n in ("t_model", "ka", "kb", "tz", "t0", "tx")] +
+                [("ctr", C.c_int32), ("next_t_model", C.c_float), ("seed", C.c_uint64), ("advance", C.c_int32), ("t_out", C.c_int32),
+                 ("t_final_out", C.c_int32), ("t_model_out", C.c_float), ("iters", C.c_int32), ("ms_out", C.c_float)])
+
+
 class dd_dev_final_args(C.Structure):
     """the operands of dd_dev_final (include/duodiff_dev.h), field for field"""
     _fields_ = ([(n, C.c_int32) for n in ("B", "C", "S", "P", "L", "extras", "b0", "images")] +
@@ -180,6 +194,7 @@ SIGNATURES = {
     "dd_set_image_seeds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "dd_noise_images": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dd_scan_error": (C.c_int, [C.c_void_p, C.POINTER(dd_scan_args), C.c_void_p]),
+    "dd_scan_error_early_exit": (C.c_int, [C.c_void_p, C.POINTER(dd_scan_exits_args), C.c_void_p]),
     "dd_bench_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
     "dd_vae_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "dd_vae_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
@@ -225,6 +240,7 @@ SIGNATURES = {
     "dd_dev_final_seeded": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_final_args), C.c_void_p, C.c_int, C.c_void_p]),
     "dd_dev_scan_diffuse": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_scan_args), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "dd_dev_scan_error": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_scan_args), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "dd_dev_scan_exits_error": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_scan_exits_args)] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4),
     "dd_dev_poison_workspaces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "dd_dev_graph_captures": (C.c_longlong, [C.c_void_p]),
     "dd_dev_last_sample_chains": (C.c_int, [C.c_void_p]),

@@ -69,7 +69,8 @@ struct KnownRow {
 // sees t_model, its output is compared with tz z + t0 x0 + tx x_t
 struct ScanRow {
     float t_model, ka, kb, tz, t0, tx;
-    int ctr, pad;                 // ctr: the Philox counter of this step's z (counter_base + the step's index in the call)
+    int ctr, next;                // ctr: the Philox counter of this step's z (counter_base + the step's index in the call); next: the row the
+                                  // early-exit scan hands on to (its table is indexed by timestep); dd_scan_error writes 0 and never reads it
 };
 
 enum GemmEpilogue {
@@ -487,7 +488,15 @@ hipError_t launch_scan_diffuse(const float* x0, float* xt, const StepState* st, 
                                int S, int b0, hipStream_t s);                       // xt = ka x0 + kb z
 hipError_t launch_scan_error(const float* x0, const float* m, float* err, StepState* st, const ScanRow* tab, const unsigned long long* seeds,
                              int B, int C, int S, int b0, int B_all, int advance, hipStream_t s);   // err[t_final B_all + b0 + b]
-hipError_t launch_set_state_scan(StepState* st, const ScanRow* tab, unsigned long long seed, hipStream_t s);   // step index 0
+hipError_t launch_set_state_scan(StepState* st, const ScanRow* tab, unsigned long long seed, hipStream_t s, int row = 0);   // t = t_final = row
+// The early-exit scan's last kernel: `exits` = depth + 1 outputs of one forward (outs [exits - 1, B, C, S, S], eps [B, C, S, S], cls [exits - 1, B];
+// exits == 1: eps alone, outs / cls / pred may be null) against the one target; the row is tab[st->t_final], a table indexed by TIMESTEP, the
+// output row is row.ctr - tab[SCAN_EXITS_ROWS].ctr (that row's ctr: the call's counter_base): mse, tgtu [.., exits, B_all], pred [.., exits - 1, B_all] at column b0 + b.  advance != 0: one thread hands on
+// t = row.next and that row's t_model.  C outside 1..4, C S S > 2^24, exits outside 1..32, a null pointer: hipErrorInvalidValue, nothing launched.
+hipError_t launch_scan_exits_error(const float* x0, const float* outs, const float* eps, const float* cls, float* mse, float* tgtu, float* pred,
+                                   StepState* st, const ScanRow* tab, const unsigned long long* seeds, int B, int C, int S, int exits, int b0,
+                                   int B_all, int advance, hipStream_t s);
+constexpr int SCAN_EXITS_ROWS = 1000;      // the early-exit scan's table: rows 0 .. 999 by timestep, row 1000 the base row
 hipError_t launch_guided_labels(const long long* y, long long* out, int B, long long null_label, hipStream_t s);   // out [2 B] = [y [0, B) | null_label x B]
 // (x + 1) / 2, NCHW -> NHWC: the output convention of reference sampler.py:145-146
 hipError_t launch_to_images(const float* x, float* out, int B, int C, int S, hipStream_t s);

@@ -1,5 +1,5 @@
 // The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_block_tail, dd_dev_block_tail_frag, dd_dev_qkv_attention, dd_dev_qkv_attention_rows, dd_dev_qkv_attention_frag, dd_dev_v_identity, dd_dev_v_copy, dd_dev_head_dec, dd_dev_gemm,
-// dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather, dd_dev_groupnorm, dd_dev_softmax_rows, dd_dev_vae_input, dd_dev_vae_output, dd_dev_vae_moments, dd_dev_cast, dd_dev_ee_probe, dd_dev_ee_probe_reduce, dd_dev_ee_attn_probe, dd_dev_final, dd_dev_scan_diffuse, dd_dev_scan_error): test scaffolding, not product.  Each one owns its host operands, device buffers, canaries and
+// dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather, dd_dev_groupnorm, dd_dev_softmax_rows, dd_dev_vae_input, dd_dev_vae_output, dd_dev_vae_moments, dd_dev_cast, dd_dev_ee_probe, dd_dev_ee_probe_reduce, dd_dev_ee_attn_probe, dd_dev_final, dd_dev_scan_diffuse, dd_dev_scan_error, dd_dev_scan_exits_error): test scaffolding, not product.  Each one owns its host operands, device buffers, canaries and
 // downloads, and nothing of the launch: the weight images come from finalize's packers and the launch arguments from the model's builders (launch_args.h:
 // dd_dev_mlp and dd_dev_block_tail* run block_tail_plan / block_tail_finish exactly as Backbone::block_tail does), then `iters` further launch sequences
 // are timed.  Buffers, transfers, timing and HIP errors go through one DevScope (dev_scope.h); of the context it reads num_cus and dev_flags (engine_state.h).
@@ -942,7 +942,76 @@ static int dev_scan(dd_ctx* c, dd_dev_scan_args* p, const float* x0_host, const 
     return dev.status();
 }
 
+// dd_dev_scan_exits_error: scan_exits_error_kernel through launch_scan_exits_error, once.  The table has 1001 rows of 0xFF bytes; row t holds the
+// caller's row, row `next` the next timestep's t_model, row 1000 the counter base ctr - k.
+static int dev_scan_exits(dd_ctx* c, dd_dev_scan_exits_args* p, const float* x0_host, const float* outs_host, const float* eps_host,
+                          const float* cls_host, const uint64_t* seeds_host, int n_seeds, float* mse_host, float* tgtu_host, float* pred_host,
+                          void* stream) {
+    if (!c || !p || !x0_host || !eps_host || !mse_host || !tgtu_host) return DD_ERR_INVALID;
+    const dd_dev_scan_exits_args& q = *p;
+    if (q.exits < 1 || (q.exits > 1 && (!outs_host || !cls_host || !pred_host))) return DD_ERR_INVALID;
+    if (q.B < 1 || q.B > 4096 || q.C < 1 || q.S < 1 || q.S > 4096 || q.b0 < 0 || q.B_all > (1 << 20) || (long long)q.b0 + q.B > q.B_all || q.k < 0 ||
+        q.k > 65535 || q.t < 0 || q.t > 999 || q.next < 0 || q.next > 999 || q.ctr < q.k || q.iters < 0 || q.iters > 10000 || (q.iters > 0 && q.advance))
+        return DD_ERR_INVALID;
+    if ((seeds_host != nullptr) != (n_seeds > 0) || n_seeds > (1 << 22) || (seeds_host && n_seeds < q.b0 + q.B)) return DD_ERR_INVALID;
+    if (q.C > 4 || (long long)q.C * q.S * q.S > (1ll << 24)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "scan: 1..4 channels, at most 2^24 elements per image");
+    if (q.exits > 32) return ctx_fail(c, DD_ERR_UNSUPPORTED, "scan: at most 32 exits");
+    if (((long long)q.k + 1) * q.exits * q.B_all > (1ll << 24) || (long long)q.B * q.C * q.S * q.S * q.exits > (1ll << 27)) return DD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const int E = q.exits;
+    const size_t n = (size_t)q.B * q.C * q.S * q.S;
+    DevScope dev(c);
+    const StepState st0{q.t, q.t_model, q.seed, q.t, 0};
+    StepState* st = dev.upload(&st0, sizeof st0);
+    ScanRow* tab = dev.filled<ScanRow>((size_t)(SCAN_EXITS_ROWS + 1) * sizeof(ScanRow), 0xFF);
+    const ScanRow row{q.t_model, q.ka, q.kb, q.tz, q.t0, q.tx, q.ctr, q.next}, base{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, q.ctr - q.k, 0};
+    if (dev.ok() && q.next != q.t) dev.ok(hipMemcpy(&tab[q.next].t_model, &q.next_t_model, sizeof(float), hipMemcpyHostToDevice), "hipMemcpy to the device");
+    if (dev.ok()) dev.ok(hipMemcpy(tab + q.t, &row, sizeof row, hipMemcpyHostToDevice), "hipMemcpy to the device");
+    if (dev.ok()) dev.ok(hipMemcpy(tab + SCAN_EXITS_ROWS, &base, sizeof base, hipMemcpyHostToDevice), "hipMemcpy to the device");
+    const unsigned long long* seeds = seeds_host ? (const unsigned long long*)dev.upload(seeds_host, (size_t)n_seeds * sizeof(uint64_t)) : nullptr;
+    // an input between 8 + 8 elements the kernel must never read
+    auto fenced = [&](const float* host, size_t elems) {
+        float* d = dev.filled<float>((elems + 16) * 4, 0xFF);
+        if (dev.ok()) dev.ok(hipMemcpy(d + 8, host, elems * 4, hipMemcpyHostToDevice), "hipMemcpy to the device");
+        return d + 8;
+    };
+    const float* dX0 = fenced(x0_host, n);
+    const float* dEps = fenced(eps_host, n);
+    const float* dOuts = E > 1 ? fenced(outs_host, n * (E - 1)) : nullptr;
+    const float* dCls = E > 1 ? fenced(cls_host, (size_t)(E - 1) * q.B) : nullptr;
+    const size_t mse_elems = ((size_t)q.k + 1) * E * q.B_all + 8, pred_elems = ((size_t)q.k + 1) * (E - 1) * q.B_all + 8;
+    float* dMse = dev.filled<float>(mse_elems * 4, 0xFF);
+    float* dTgt = dev.filled<float>(mse_elems * 4, 0xFF);
+    float* dPred = E > 1 ? dev.filled<float>(pred_elems * 4, 0xFF) : nullptr;
+    auto launch = [&](int advance) {
+        return launch_scan_exits_error(dX0, dOuts, dEps, dCls, dMse, dTgt, dPred, st, tab, seeds, q.B, q.C, q.S, E, q.b0, q.B_all, advance, s);
+    };
+    hipError_t first = hipSuccess;
+    if (dev.ok()) first = launch(q.advance);
+    if (first == hipErrorInvalidValue) return ctx_fail(c, DD_ERR_INVALID, "scan: operands the launcher refuses");      // (refused before any launch)
+    DEV_HIP(dev, first);
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(mse_host, dMse, mse_elems * 4);
+    dev.download(tgtu_host, dTgt, mse_elems * 4);
+    if (E > 1) dev.download(pred_host, dPred, pred_elems * 4);
+    StepState st1{};
+    dev.download(&st1, st, sizeof st1);
+    if (dev.ok()) { p->t_out = st1.t; p->t_final_out = st1.t_final; p->t_model_out = st1.t_model; }
+    if (q.iters > 0 && dev.ok()) {      // (advance == 0: the launch leaves the state as it found it)
+        float ms = 0.f;
+        DEV_HIP(dev, time_launches(s, q.iters, [&] { return launch(0); }, &ms));
+        p->ms_out = ms;
+    }
+    return dev.status();
+}
+
 extern "C" {
+
+int dd_dev_scan_exits_error(dd_ctx* c, dd_dev_scan_exits_args* p, const float* x0_host, const float* outs_host, const float* eps_host,
+                            const float* cls_host, const uint64_t* seeds_host, int n_seeds, float* mse_host, float* tgtu_host, float* pred_host,
+                            void* stream) {
+    return dev_scan_exits(c, p, x0_host, outs_host, eps_host, cls_host, seeds_host, n_seeds, mse_host, tgtu_host, pred_host, stream);
+}
 
 int dd_dev_scan_diffuse(dd_ctx* c, dd_dev_scan_args* p, const float* x0_host, const uint64_t* seeds_host, int n_seeds, float* xt_host, void* stream) {
     if (!xt_host) return DD_ERR_INVALID;

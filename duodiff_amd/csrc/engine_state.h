@@ -81,7 +81,8 @@ struct dd_ctx {
                                  //   written by the output head and read by threshold_step_kernel within one step, never across steps
     dd::RowTable<dd::ScanRow> stab;      // dd_scan_error: the scan's rows,
     dd::DevBuf<float> scan_ws;       //   and its scratch, x_t | eps ([B, C, S, S] each; chain k's images at its first image) | err [n, B]: grown before the loop,
-                                 //   never on the launch path
+                                 //   never on the launch path.  dd_scan_error_early_exit: x_t | mse [n, depth + 1, B] | target (the same) | pred [n, depth, B]; its
+                                 //   table has 1001 rows (by timestep, and the base row) and its taps live in the model's ee_ws
     // dd_set_image_seeds: the caller's per-image seeds (device, seeds_n of them; null: the plain noise), and the context's own copy that
     // the kernels read -- copied at every call that draws device noise (stage_image_seeds), so a captured step is reused across seeds
     const uint64_t* seeds_user = nullptr;
@@ -140,7 +141,7 @@ struct GraphKey {
 };
 
 // the captured step of each sampling loop: dd_model::graph[kind][chain]
-enum GraphKind { GRAPH_DDPM, GRAPH_AFFINE, GRAPH_EARLY_EXIT, GRAPH_MULTISTEP, GRAPH_SCAN, GRAPH_KINDS };
+enum GraphKind { GRAPH_DDPM, GRAPH_AFFINE, GRAPH_EARLY_EXIT, GRAPH_MULTISTEP, GRAPH_SCAN, GRAPH_SCAN_EXITS, GRAPH_KINDS };
 
 // The activation workspace of one chain: dd_sample runs a large batch as TWO independent half-batch chains on two streams (one
 // chain's HBM-bound kernel phases then run under the other's MFMA phases); the second chain has its own copy of every buffer.

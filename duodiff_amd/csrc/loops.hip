@@ -96,7 +96,7 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
     // so that one's HBM-bound phases (row prologues / epilogues, attention row fetch) run under the other's MFMA phases.
     // Guided: the decisions are made on the 2 B backbone rows and the split is by image (chain 0 takes the larger half, on the workspace
     // sized for max_batch >= 2 B rows; the second chain's workspace holds (max_batch + 1) / 2 rows >= 2 * floor(B / 2)).
-    const bool ee = L.kind == GRAPH_EARLY_EXIT;
+    const bool ee = L.kind == GRAPH_EARLY_EXIT || L.kind == GRAPH_SCAN_EXITS;      // the loops of an early-exit model
     const dd_pag* pag = L.mods.pag;
     const bool paired = g || pag;        // B images as 2 B backbone rows (stage_guided's layout): classifier-free or perturbed-attention guidance
     const int rows = paired ? 2 * L.B : L.B;
@@ -500,11 +500,100 @@ int scan_error(dd_ctx* c, const dd_scan_args* a, void* stream) {
     };
     return run_loop(c, L, s);
 }
+// the early-exit scratch of a model (eps | cls | outs per chain, then dd_sample_early_exit's two sum tables), allocated on first use
+int ensure_ee_ws(dd_ctx* c, dd_model* m) {
+    const size_t tab = (size_t)1000 * m->cfg.depth;
+    if (!m->ee_ws) DD_HIP(c, hipMalloc((void**)&m->ee_ws, (ee_scratch_elems(m, m->cfg.max_batch) + 2 * tab) * sizeof(float)));
+    return DD_OK;
+}
+
+// dd_scan_error_early_exit: dd_scan_error's loop for an early-exit model.  A step is diffuse -> forward_eps with EeTaps -> exits error
+// (scan.hip).  The step state holds the integer TIMESTEP, not the step's index (the per-timestep probe tables read it), so the row table is
+// indexed by timestep -- 1000 rows of which the grid's are filled, each naming the next, and the base row with the call's counter_base.
+// The taps go to the model's early-exit scratch (each chain's block, as dd_sample_early_exit), the three result tables to scan_ws behind
+// x_t; they are copied to the caller's tensors behind the join.  Rows are disjoint per image: no join kernel.
+int scan_exits(dd_ctx* c, const dd_scan_exits_args* a, void* stream) {
+    if (!c || !a) return DD_ERR_INVALID;
+    dd_model* m = a->model;
+    int rc = check_call(c, m, a->B, a->y_dev);
+    if (rc) return rc;
+    if (m->ee_type < 0) return ctx_fail(c, DD_ERR_STATE, "model was not created with dd_model_enable_early_exit");
+    if (!a->x0_dev || !a->mse_dev || !a->target_dev || !a->pred_dev || !a->t || !a->ka || !a->kb || !a->tz || !a->t0 || !a->tx)
+        return ctx_fail(c, DD_ERR_INVALID, "null tensor / table");
+    if (a->n_steps < 1 || a->n_steps > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "n_steps outside [1, 2^20]");
+    if (a->counter_base < 0 || a->counter_base > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "counter_base outside [0, 2^20]");
+    if (a->noise_mode != DD_NOISE_PHILOX)
+        return ctx_fail(c, DD_ERR_INVALID, "dd_scan_error_early_exit draws its noise on the device: noise_mode must be DD_NOISE_PHILOX");
+    const int n = a->n_steps;
+    bool seen[SCAN_EXITS_ROWS] = {};
+    for (int k = 0; k < n; ++k) {
+        const float t = a->t[k];
+        if (!(t >= 0.f && t <= 999.f) || t != (float)(int)t)
+            return ctx_fail(c, DD_ERR_INVALID, "timestep " + std::to_string(k) + " is not an integer in [0, 999]: the probe tables are indexed by it");
+        if (seen[(int)t]) return ctx_fail(c, DD_ERR_INVALID, "timestep " + std::to_string((int)t) + " occurs twice");
+        seen[(int)t] = true;
+    }
+    if ((rc = check_image_seeds(c, a->noise_mode, a->B))) return rc;
+    const int C = m->cfg.in_chans, S = m->cfg.img_size, depth = m->cfg.depth, E = depth + 1;
+    const size_t chw = (size_t)C * S * S, elems = (size_t)a->B * chw;
+    if (C < 1 || C > 4 || chw > ((size_t)1 << 24))
+        return ctx_fail(c, DD_ERR_UNSUPPORTED, "the scan kernels take 1..4 channels and at most 2^24 elements per image");
+    if (E > 32) return ctx_fail(c, DD_ERR_UNSUPPORTED, "the early-exit scan takes at most 32 exits (depth + 1)");
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned long long* seeds = nullptr;
+    if ((rc = stage_image_seeds(c, a->noise_mode, s, &seeds))) return rc;
+    if ((rc = ensure_ee_ws(c, m))) return rc;
+    std::vector<int> at(SCAN_EXITS_ROWS, -1);       // timestep -> its step in the call
+    for (int k = 0; k < n; ++k) at[(int)a->t[k]] = k;
+    rc = upload_rows(c, c->stab, (size_t)SCAN_EXITS_ROWS + 1, s, [&](size_t t) {
+        if (t == (size_t)SCAN_EXITS_ROWS) return ScanRow{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, a->counter_base, 0};
+        const int k = at[t];
+        if (k < 0) return ScanRow{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0, 0};
+        // (the last step hands on the first timestep: a valid row, never used)
+        return ScanRow{a->t[k], a->ka[k], a->kb[k], a->tz[k], a->t0[k], a->tx[k], a->counter_base + k, (int)a->t[k + 1 < n ? k + 1 : 0]};
+    });
+    if (rc) return rc;
+    if ((rc = c->k_stage.grow(c, elems))) return rc;
+    const size_t mse_elems = (size_t)n * E * a->B, pred_elems = (size_t)n * depth * a->B;
+    if ((rc = c->scan_ws.grow(c, elems + 2 * mse_elems + pred_elems))) return rc;
+    DD_HIP(c, hipMemcpyAsync(c->k_stage.p, a->x0_dev, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    const ScanRow* tab = c->stab.dev.p;
+    const float* x0_run = c->k_stage.p;
+    float* mse_run = c->scan_ws.p + elems;       // mse | target | pred: copied out behind the loop, so a captured step never names the caller's
+    float* tgt_run = mse_run + mse_elems;
+    float* pred_run = tgt_run + mse_elems;
+    const int t_first = (int)a->t[0];
+    Loop L{GRAPH_SCAN_EXITS, m, nullptr, n, -1, c->scan_ws.p, a->y_dev, a->B, Mods{.seeds = seeds}, a->use_graph != 0};
+    L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_scan(st, tab, (unsigned long long)a->seed, ss, t_first); };
+    L.key = [&](GraphKey& k, const Slice& sl) {
+        k.noise = a->noise_mode; k.variance = n; k.atab = tab; k.kx0 = x0_run + (size_t)sl.b0 * chw; k.aux0 = mse_run; k.aux1 = m->ee_ws;
+        if (sl.chains == 2 && sl.chain == 0) k.b0 = -1;     // (chain 0 of two writes rows of 2 B images -- not the whole batch's graph)
+    };
+    L.step = [&](dd_model* mm, const Chain& ch, const Slice& sl, hipStream_t ss) -> int {
+        const float* x0 = x0_run + (size_t)sl.b0 * chw;
+        float* eps = mm->ee_ws + ee_scratch_elems(mm, sl.b0);      // the chain's block: eps | cls | outs (enqueue_ee_step's layout)
+        float* cls = eps + (size_t)sl.B * chw;
+        float* outs = cls + (size_t)depth * sl.B;
+        const EeTaps ee{cls, outs, 0};
+        DD_HIP(c, launch_scan_diffuse(x0, sl.x, ch.st, tab, sl.mods.seeds, sl.B, C, S, sl.b0, ss));
+        if (int r = forward_eps(c, mm, ch, sl.x, sl.y, eps, sl.B, ss, {.ee = &ee})) return r;
+        DD_HIP(c, launch_scan_exits_error(x0, outs, eps, cls, mse_run, tgt_run, pred_run, ch.st, tab, sl.mods.seeds, sl.B, C, S, E, sl.b0, a->B, 1, ss));
+        return DD_OK;
+    };
+    L.tail = [&](int, hipStream_t ss) -> int {
+        DD_HIP(c, hipMemcpyAsync(a->mse_dev, mse_run, mse_elems * sizeof(float), hipMemcpyDeviceToDevice, ss));
+        DD_HIP(c, hipMemcpyAsync(a->target_dev, tgt_run, mse_elems * sizeof(float), hipMemcpyDeviceToDevice, ss));
+        DD_HIP(c, hipMemcpyAsync(a->pred_dev, pred_run, pred_elems * sizeof(float), hipMemcpyDeviceToDevice, ss));
+        return DD_OK;
+    };
+    return run_loop(c, L, s);
+}
 }  // namespace
 
 extern "C" {
 
 int dd_scan_error(dd_ctx* c, const dd_scan_args* a, void* stream) { return scan_error(c, a, stream); }
+int dd_scan_error_early_exit(dd_ctx* c, const dd_scan_exits_args* a, void* stream) { return scan_exits(c, a, stream); }
 
 int dd_sample(dd_ctx* c, const dd_sample_args* a, void* stream) { return sample_ddpm(c, a, Mods{}, stream); }
 int dd_sample_guided(dd_ctx* c, const dd_sample_args* a, const dd_guidance* g, void* stream) { return sample_ddpm(c, a, guided(g), stream); }
@@ -584,7 +673,7 @@ int dd_sample_early_exit(dd_ctx* c, const dd_ee_sample_args* a, void* stream) {
     // behind the loop, (chain 0 + chain 1) / B.  Heads and probes stay on each chain's own stream (measured: the 13 forks as parallel
     // branches of each chain's graph cost +0.9 ms per step -- 5.22 against 4.23 ms; profiles/r05/ab_round5.txt).
     const size_t tab = (size_t)1000 * m->cfg.depth;
-    if (!m->ee_ws) DD_HIP(c, hipMalloc((void**)&m->ee_ws, (ee_scratch_elems(m, m->cfg.max_batch) + 2 * tab) * sizeof(float)));
+    if ((rc = ensure_ee_ws(c, m))) return rc;
     float* sums = m->ee_ws + ee_scratch_elems(m, m->cfg.max_batch);
     auto err_tab = [&](const Slice& sl) { return sl.chains == 1 || !a->err_dev ? a->err_dev : sums + sl.chain * tab; };
     Loop L{GRAPH_EARLY_EXIT, m, nullptr, a->t_start - a->t_end + 1, -1, a->x_dev, a->y_dev, a->B, Mods{.seeds = seeds}, a->use_graph != 0};

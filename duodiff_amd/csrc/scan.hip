@@ -3,7 +3,8 @@
 // step-state contract of dd_internal.h: scan_diffuse_kernel is a step's first kernel and reads row st->t, token assembly copies t to
 // t_final, scan_error_kernel is its last, reads row t_final, and one of its threads hands the next step its t / t_model.  All arithmetic
 // is step_update.h's (draw_site, philox_normal4, known_value, scan_target, scan_accumulate, scan_mean): the kernels hold none of their own.
-// Both are launch-latency sized (a few MB each way at the largest batch).
+// Both are launch-latency sized (a few MB each way at the largest batch).  dd_scan_error_early_exit keeps the diffuse kernel and ends its
+// step with scan_exits_error_kernel: every exit's error and the probes' training target from one forward's taps.
 #include "dd_internal.h"
 #include "step_update.h"
 #include "wave_prims.h"
@@ -73,10 +74,71 @@ __global__ void __launch_bounds__(256) scan_error_kernel(const float* __restrict
     }
 }
 
-__global__ void set_state_scan_kernel(StepState* st, const ScanRow* tab, unsigned long long seed) {
-    st->t = 0;
-    st->t_final = 0;
-    st->t_model = tab[0].t_model;
+// The early-exit form (dd_scan_error_early_exit): one forward's E = depth + 1 outputs against the one target.  Exit l < E - 1 reads plane l
+// of outs [E - 1, B, C, S, S], exit E - 1 the backbone's eps; workgroup (b, l) takes image b and exit l: scan_error_kernel with blockIdx.y
+// over the exits and a second accumulator.  Both sums run in exactly scan_error_kernel's order (pixels tid, tid + 256, ..., channels in
+// turn; wave_reduce_add; the four waves through LDS in index order), so mse[k][l] is bit-equal to scan_error_kernel on plane l and the
+// SUMMATION DEPTH above holds for both.  Consecutive lanes read consecutive pixels of one plane.
+//   mse [k][l][b0 + b] = scan_mean(sum scan_accumulate(., o_l, tgt))         k = row.ctr - tab[1000].ctr, the step's index in the call
+//   tgtu[k][l][b0 + b] = scan_mean(sum scan_accumulate_tanh(., o_l, tgt))    the probes' training target (trainer.py:376)
+//   pred[k][l][b0 + b] = cls[l][b]  (l < E - 1)                              what the probes predicted: a copy
+// The row table is indexed by the TIMESTEP here (st->t_final is the integer timestep, which the per-timestep probe tables of the forward
+// need): rows 0 .. 999, and row SCAN_EXITS_ROWS = 1000 whose ctr is the call's counter_base; the handoff goes to row `next`.
+// One exit per workgroup is the measured choice (tools/scan_exits_bench.py; 64 images of 3 x 64 x 64, 14 exits, the launch alone).  A form
+// that drew z and formed tgt once per pixel for a group of G exits (accumulators in registers, the exit loop inside the pixel loop) took
+// 84.6 us at G = 4, 54.6 us at G = 2 and 41.8 us at G = 1 against 37.9 us for this kernel, and 151 us for 14 launches of scan_error_kernel: the summation order
+// fixes 256 threads per (image, exit), so the launch has 3.5 waves per SIMD here and under one at G = 4, and the waves that hide the
+// planes' load latency are worth more than the Philox draws that grouping saves.  The grouped form is not in this tree.
+template <int C>
+__global__ void __launch_bounds__(256) scan_exits_error_kernel(const float* __restrict__ x0, const float* __restrict__ outs, const float* __restrict__ eps,
+                                                               const float* __restrict__ cls, float* __restrict__ mse, float* __restrict__ tgtu,
+                                                               float* __restrict__ pred, StepState* st, const ScanRow* __restrict__ tab,
+                                                               const unsigned long long* __restrict__ seeds, int hw, int b0, int B, int B_all, int E,
+                                                               int advance) {
+    __shared__ float part[2][4];
+    const int tid = threadIdx.x, b = blockIdx.x, l = blockIdx.y;
+    const int t = st->t_final;
+    const ScanRow row = tab[t];
+    const int k = row.ctr - tab[SCAN_EXITS_ROWS].ctr;      // (the call's counter_base: device data, so a captured step serves every base)
+    const float t_next = advance ? tab[row.next].t_model : 0.f;
+    const unsigned long long seed = st->seed;
+    const float* __restrict__ m = l < E - 1 ? outs + (long long)l * B * C * hw : eps;
+    float acc = 0.f, acu = 0.f;
+    for (int p = tid; p < hw; p += 256) {
+        const DrawSite ds = draw_site(seeds, seed, (unsigned long long)(b + b0), (unsigned long long)p, (unsigned long long)hw);
+        const f32x4 z = philox_normal4(ds.key, ds.id, row.ctr, PHILOX_SCAN);
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const long long e = ((long long)b * C + c) * hw + p;
+            const float xv = x0[e];
+            const float xt = known_value(xv, row.ka, row.kb, z[c], true);
+            const float tgt = scan_target(z[c], xv, xt, row.tz, row.t0, row.tx);
+            const float o = m[e];
+            acc = scan_accumulate(acc, o, tgt);
+            acu = scan_accumulate_tanh(acu, o, tgt);
+        }
+    }
+    acc = wave_reduce_add(acc);
+    acu = wave_reduce_add(acu);
+    if ((tid & 63) == 0) { part[0][tid >> 6] = acc; part[1][tid >> 6] = acu; }
+    __syncthreads();
+    if (tid < 2) {       // thread 0: the squares, thread 1: the tanh sum; the four waves in index order
+        float sum = part[tid][0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) sum += part[tid][w];
+        (tid ? tgtu : mse)[((long long)k * E + l) * B_all + b0 + b] = scan_mean(sum, C * hw);
+        if (tid == 0 && l < E - 1) pred[((long long)k * (E - 1) + l) * B_all + b0 + b] = cls[(long long)l * B + b];
+    }
+    if (tid == 0 && b == 0 && l == 0 && advance) {      // (no workgroup reads t / t_model: they read t_final)
+        st->t = row.next;
+        st->t_model = t_next;
+    }
+}
+
+__global__ void set_state_scan_kernel(StepState* st, const ScanRow* tab, unsigned long long seed, int row) {
+    st->t = row;
+    st->t_final = row;
+    st->t_model = tab[row].t_model;
     st->seed = seed;
 }
 
@@ -112,8 +174,26 @@ hipError_t launch_scan_error(const float* x0, const float* m, float* err, StepSt
     return hipGetLastError();
 }
 
-hipError_t launch_set_state_scan(StepState* st, const ScanRow* tab, unsigned long long seed, hipStream_t s) {
-    hipLaunchKernelGGL(set_state_scan_kernel, dim3(1), dim3(1), 0, s, st, tab, seed);
+hipError_t launch_scan_exits_error(const float* x0, const float* outs, const float* eps, const float* cls, float* mse, float* tgtu, float* pred,
+                                   StepState* st, const ScanRow* tab, const unsigned long long* seeds, int B, int C, int S, int exits, int b0,
+                                   int B_all, int advance, hipStream_t s) {
+    if (!scan_shape_ok(B, C, S) || exits < 1 || exits > 32 || !x0 || !eps || !mse || !tgtu || !st || !tab || b0 < 0 || B_all < b0 + B)
+        return hipErrorInvalidValue;
+    if (exits > 1 && (!outs || !cls || !pred)) return hipErrorInvalidValue;
+    const int hw = S * S;
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)B, (unsigned)exits), dim3(256), 0, s, x0, outs, eps, cls, mse, tgtu, pred, st, tab, seeds, hw, b0, B,
+                           B_all, exits, advance);
+    };
+    if (C == 1) go(scan_exits_error_kernel<1>);
+    else if (C == 2) go(scan_exits_error_kernel<2>);
+    else if (C == 3) go(scan_exits_error_kernel<3>);
+    else go(scan_exits_error_kernel<4>);
+    return hipGetLastError();
+}
+
+hipError_t launch_set_state_scan(StepState* st, const ScanRow* tab, unsigned long long seed, hipStream_t s, int row) {
+    hipLaunchKernelGGL(set_state_scan_kernel, dim3(1), dim3(1), 0, s, st, tab, seed, row);
     return hipGetLastError();
 }
 

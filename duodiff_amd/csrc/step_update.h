@@ -181,6 +181,33 @@ __device__ __forceinline__ float scan_accumulate(float acc, float m, float tgt) 
 // the mean over an image's n = C H W elements (n <= 2^24: exact as a float), a correctly rounded division
 __device__ __forceinline__ float scan_mean(float sum, int n) { return __fdiv_rn(sum, (float)n); }
 
+// tanh|d| for the early-exit scan's second loss (dd_scan_error_early_exit; reference trainer.py:376, u_t_hats = mean(tanh|ee_output - true_output|)):
+// the probes' training target.  No library tanhf / expf: only individually rounded + and x, two correctly rounded divisions, fabs and min, so
+// that a numpy-float32 mirror (duodiff_amd/threshold_scan.py tanh_abs_f32) reproduces it bit for bit.  With a = min(|d|, 10), h = a / 2, s = h h:
+//     t = h (135135 + 17325 s + 378 s^2 + s^3) / (135135 + 62370 s + 3150 s^2 + 28 s^3)     Lambert's continued fraction of tanh h, 7 levels
+//     tanh a = min(2 t / (1 + t t), 1)                                                       the double-argument formula
+// an odd rational in |d| behind a clamp; every coefficient is an integer, exact in fp32, and every term is >= 0 (no cancellation).  The result
+// lies in [0, 1] and scan_tanh_abs(0) == 0.  inf gives the clamp's value; a NaN is not an argument (fminf drops it).
+// E_TANH: the largest |scan_tanh_abs(d) - tanh|d|| over EVERY fp32 d against float64 tanh, swept on the CPU with the mirror
+// (tools/scan_tanh_sweep.py: all 1 092 616 193 values of [0, 10] and the clamp's tail) = 1.66e-7
+// (1.6533e-7, taken at d = 1.1165210; spec: <= 1e-6).
+constexpr float SCAN_TANH_CLAMP = 10.f;
+__device__ __forceinline__ float scan_tanh_abs(float d) {
+#pragma clang fp contract(off)
+    const float h = 0.5f * fminf(fabsf(d), SCAN_TANH_CLAMP);
+    const float s = h * h;
+    const float p = ((s + 378.f) * s + 17325.f) * s + 135135.f;
+    const float q = ((28.f * s + 3150.f) * s + 62370.f) * s + 135135.f;
+    const float t = __fdiv_rn(h * p, q);
+    return fminf(__fdiv_rn(t + t, t * t + 1.f), 1.f);
+}
+// one element's share of the second sum: acc + tanh|m - tgt|
+__device__ __forceinline__ float scan_accumulate_tanh(float acc, float m, float tgt) {
+#pragma clang fp contract(off)
+    const float d = m - tgt;
+    return acc + scan_tanh_abs(d);
+}
+
 // x0 thresholding of a multistep step (dd_x0_threshold): the step's data prediction x0 = p x + q m (StepRule::history) is pulled back
 // before it drives the update, and the update then takes it in m's place -- a and b are the UNFOLDED row, b multiplying xh:
 //     static   xh = min(max(x0, -r), r)

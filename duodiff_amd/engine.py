@@ -658,3 +658,26 @@ def scan_error_loop(ctx: Context, model: Model, x0, rows, *, y=None, seed=0, cou
     _run_loop(ctx, args, x0, y, seed, "philox", use_graph, stream, lambda st: ctx.lib.dd_scan_error(ctx.handle, C.byref(args), st))
     return err
 
+
+def scan_exits_loop(ctx: Context, model: Model, x0, rows, *, y=None, seed=0, counter_base=0, use_graph=True, stream=None):
+    """dd_scan_error_early_exit: scan_error_loop for an early-exit model -- from the one forward of step k every exit's error.  rows as
+    scan_error_loop, their t distinct integers in [0, 999].  Returns (mse [n, depth + 1, B], target [n, depth + 1, B], pred [n, depth, B])
+    fp32 on the device: exit l < depth is the head behind block l, exit depth the backbone; mse as scan_error_loop's err, target the
+    mean of tanh|output - training target| (what probe l was trained to predict), pred the probes' predictions (what the early-exit
+    sampler compares with --threshold)."""
+    assert x0.is_cuda and x0.dtype == torch.float32 and x0.is_contiguous() and x0.dim() == 4
+    args = L.dd_scan_exits_args()
+    tab = {k: np.ascontiguousarray(rows[k], np.float32) for k in ("t", "ka", "kb", "tz", "t0", "tx")}
+    n = len(tab["t"])
+    assert all(v.shape == (n,) for v in tab.values())
+    for k, v in tab.items():
+        setattr(args, k, v.ctypes.data_as(C.POINTER(C.c_float)))
+    args.model = model.handle
+    args.n_steps = n
+    args.counter_base = int(counter_base)
+    B, depth = x0.shape[0], model.mp.depth
+    mse, target = (torch.empty(n, depth + 1, B, device=x0.device, dtype=torch.float32) for _ in range(2))
+    pred = torch.empty(n, depth, B, device=x0.device, dtype=torch.float32)
+    args.mse_dev, args.target_dev, args.pred_dev = mse.data_ptr(), target.data_ptr(), pred.data_ptr()
+    _run_loop(ctx, args, x0, y, seed, "philox", use_graph, stream, lambda st: ctx.lib.dd_scan_error_early_exit(ctx.handle, C.byref(args), st))
+    return mse, target, pred

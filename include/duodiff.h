@@ -486,6 +486,42 @@ typedef struct dd_scan_args {
 } dd_scan_args;
 int dd_scan_error(dd_ctx* ctx, const dd_scan_args* args, void* stream);
 
+/* ---- the early-exit form of the scan (version 6 addition: new symbols only) ---------------- */
+/* dd_scan_error for a model created with dd_model_enable_early_exit: the same x_t, target and loop, and from the ONE forward of step k
+ * every exit's error.  With depth = the model's depth, exit l < depth the head behind block l and exit depth the backbone's output
+ * (the reference's L_n_t and u_t_hats, trainer.py:358-398, per timestep and image):
+ *     mse_dev   [(k (depth + 1) + l) B + i] = (1 / CHW) sum (o_l - tgt)^2            summed exactly as dd_scan_error sums it
+ *     target_dev[(k (depth + 1) + l) B + i] = (1 / CHW) sum tanh|o_l - tgt|          what probe l was trained to predict
+ *     pred_dev  [(k depth + l) B + i]       = probe l's prediction (l < depth)       what dd_sample_early_exit compares with its threshold
+ * t[k] must be distinct INTEGERS in [0, 999]: the per-timestep probe tables are indexed by them.  Graph replay, half-batch chains and
+ * per-image seeds as dd_scan_error; the three result tables live in scratch of the context and are copied out behind the loop.
+ * DD_ERR_STATE: a model without early exit.  DD_ERR_INVALID (with dd_last_error) before anything is enqueued: a null pointer, n_steps
+ * outside [1, 2^20], counter_base outside [0, 2^20], a noise_mode other than DD_NOISE_PHILOX, a timestep that is no integer, lies outside
+ * [0, 999] or occurs twice, labels that do not fit the model, B outside [1, max_batch], image seeds set for another B.
+ * DD_ERR_UNSUPPORTED: in_chans outside 1..4, more than 2^24 elements per image or depth + 1 > 32. */
+typedef struct dd_scan_exits_args {
+    dd_model* model;
+    const float* x0_dev;    /* [B,C,S,S] fp32, read only                                                        */
+    const int64_t* y_dev;   /* [B] or NULL                                                                      */
+    int32_t B;
+    int32_t n_steps;
+    const float* t;         /* host [n_steps]: distinct integer timesteps in [0, 999]                           */
+    const float* ka;        /* host [n_steps]: x_t = ka x0 + kb z                                               */
+    const float* kb;
+    const float* tz;        /* host [n_steps]: tgt = tz z + t0 x0 + tx x_t                                      */
+    const float* t0;
+    const float* tx;
+    uint64_t seed;
+    int32_t counter_base;
+    int32_t noise_mode;     /* DD_NOISE_PHILOX                                                                  */
+    int32_t use_graph;
+    int32_t reserved;
+    float* mse_dev;         /* out [n_steps, depth + 1, B] fp32                                                 */
+    float* target_dev;      /* out [n_steps, depth + 1, B] fp32                                                 */
+    float* pred_dev;        /* out [n_steps, depth, B] fp32                                                     */
+} dd_scan_exits_args;
+int dd_scan_error_early_exit(dd_ctx* ctx, const dd_scan_exits_args* args, void* stream);
+
 /* ---- KL-VAE decode: autoencoder.decode(x) at sampler.py:141-143 ---------------- */
 /* Replaces FrozenAutoencoderKL.decode (models/utils/autoencoder.py:486-490, Decoder :320-449) for the fixed ddconfig of
  * get_autoencoder (:503-516).  Parameters are set by the reference state_dict keys ("decoder.*", "post_quant_conv.*";

@@ -337,6 +337,34 @@ int dd_dev_scan_diffuse(dd_ctx* ctx, dd_dev_scan_args* args, const float* x0_hos
 int dd_dev_scan_error(dd_ctx* ctx, dd_dev_scan_args* args, const float* x0_host, const float* m_host, const uint64_t* seeds_host, int n_seeds,
                       float* err_host, void* stream);
 
+/* Development harness for the early-exit scan's last kernel (scan.hip scan_exits_error_kernel; include/duodiff.h dd_scan_error_early_exit)
+ * through launch_scan_exits_error, ONE launch: B images of C x S x S, images [b0, b0 + B) of a whole batch of B_all, `exits` outputs of one
+ * forward -- outs_host [exits - 1, B, C, S, S], eps_host [B, C, S, S] (the last exit), cls_host [exits - 1, B]; exits == 1: outs, cls and pred
+ * may be NULL.  The step state is created with t = t_final = the TIMESTEP t (0..999), seed and t_model; the row table has 1001 rows of 0xFF
+ * bytes of which row t holds the caller's (t_model, ka, kb, tz, t0, tx, ctr, next), row `next` (0..999) next_t_model and row 1000 the
+ * counter base ctr - k, so that the launch writes output row k (0..65535, ctr >= k).  Every input's device copy sits between 8 + 8
+ * elements of 0xFF bytes, NaN, which the kernel must never read.  mse_host, tgtu_host [(k + 1) exits B_all + 8] and pred_host
+ * [(k + 1) (exits - 1) B_all + 8] are filled with 0xFF bytes before the launch and returned WHOLE: the launch writes elements
+ * (k exits + l) B_all + b0 .. + B - 1 of the first two and (k (exits - 1) + l) B_all + b0 .. + B - 1 of pred.  advance, seeds, t_out,
+ * t_final_out, t_model_out, iters and ms_out as dd_dev_scan_error.  Everything is checked before anything touches the GPU (the limits of
+ * dd_dev_scan_error, (k + 1) exits B_all <= 2^24, B C S S exits <= 2^27: DD_ERR_INVALID); C outside 1..4, C S S > 2^24 or exits > 32 is
+ * DD_ERR_UNSUPPORTED with nothing launched. */
+typedef struct dd_dev_scan_exits_args {
+    int B, C, S, exits, b0, B_all, k, t, next;
+    float t_model, ka, kb, tz, t0, tx;
+    int ctr;
+    float next_t_model;
+    unsigned long long seed;
+    int advance;
+    int t_out, t_final_out;
+    float t_model_out;
+    int iters;
+    float ms_out;
+} dd_dev_scan_exits_args;
+int dd_dev_scan_exits_error(dd_ctx* ctx, dd_dev_scan_exits_args* args, const float* x0_host, const float* outs_host, const float* eps_host,
+                            const float* cls_host, const uint64_t* seeds_host, int n_seeds, float* mse_host, float* tgtu_host,
+                            float* pred_host, void* stream);
+
 /* Kernel-variant switches for same-process A/B runs (tools/mlp_check.py, tools/all_configs.py).  They act on models
  * FINALIZED after the call (the kernel paths a model takes, the DD_DEV_NO_FRAG_* hand-offs among them) or on launches made after it; the product never sets them and the library
  * reads no environment variable. */

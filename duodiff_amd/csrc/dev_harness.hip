@@ -882,16 +882,52 @@ static int dev_final(dd_ctx* c, dd_dev_final_args* p, const uint64_t* seeds_host
     return dev.status();
 }
 
-// dd_dev_scan_diffuse (m_host null, xt_host set) and dd_dev_scan_error (m_host and err_host set): the checks, the step state and the row table they share
+// What the scan entries (dev_scan, dev_scan_exits) share.  The limits on the fields their two args structs have in common and on the seeds
+// (own_ok: the entry's own limits), all DD_ERR_INVALID, then the shape the launchers refuse
+template <typename Args>
+static int scan_dev_check(dd_ctx* c, const Args& q, bool own_ok, const uint64_t* seeds_host, int n_seeds) {
+    if (!own_ok || q.B < 1 || q.B > 4096 || q.C < 1 || q.S < 1 || q.S > 4096 || q.b0 < 0 || q.B_all > (1 << 20) || (long long)q.b0 + q.B > q.B_all ||
+        q.k < 0 || q.k > 65535 || q.iters < 0 || q.iters > 10000 || (q.iters > 0 && q.advance))
+        return DD_ERR_INVALID;
+    if ((seeds_host != nullptr) != (n_seeds > 0) || n_seeds > (1 << 22) || (seeds_host && n_seeds < q.b0 + q.B)) return DD_ERR_INVALID;
+    if (q.C > 4 || (long long)q.C * q.S * q.S > (1ll << 24)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "scan: 1..4 channels, at most 2^24 elements per image");
+    return DD_OK;
+}
+static const unsigned long long* scan_dev_seeds(DevScope& dev, const uint64_t* seeds_host, int n_seeds) {
+    return seeds_host ? (const unsigned long long*)dev.upload(seeds_host, (size_t)n_seeds * sizeof(uint64_t)) : nullptr;
+}
+// an input between 8 + 8 elements the kernel must never read
+static const float* scan_dev_fenced(DevScope& dev, const float* host, size_t elems) {
+    float* d = dev.filled<float>((elems + 16) * 4, 0xFF);
+    if (dev.ok()) dev.ok(hipMemcpy(d + 8, host, elems * 4, hipMemcpyHostToDevice), "hipMemcpy to the device");
+    return d + 8;
+}
+// The launch and what follows it: launch(p->advance) once (refused by the launcher: DD_ERR_INVALID, nothing launched), results() downloads
+// the entry's outputs, the step state is read back into the args, and iters > 0 times that many more launches
+template <typename Args, typename Launch, typename Results>
+static int scan_dev_run(dd_ctx* c, DevScope& dev, Args* p, const StepState* st, hipStream_t s, Launch&& launch, Results&& results) {
+    const hipError_t first = dev.ok() ? launch(p->advance) : hipSuccess;
+    if (first == hipErrorInvalidValue) return ctx_fail(c, DD_ERR_INVALID, "scan: operands the launcher refuses");      // (refused before any launch)
+    DEV_HIP(dev, first);
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    results();
+    StepState st1{};
+    dev.download(&st1, st, sizeof st1);
+    if (dev.ok()) { p->t_out = st1.t; p->t_final_out = st1.t_final; p->t_model_out = st1.t_model; }
+    if (p->iters > 0 && dev.ok()) {      // (advance == 0: the launch leaves the state as it found it)
+        float ms = 0.f;
+        DEV_HIP(dev, time_launches(s, p->iters, [&] { return launch(0); }, &ms));
+        p->ms_out = ms;
+    }
+    return dev.status();
+}
+
+// dd_dev_scan_diffuse (m_host null, xt_host set) and dd_dev_scan_error (m_host and err_host set): the step state and the row table they share
 static int dev_scan(dd_ctx* c, dd_dev_scan_args* p, const float* x0_host, const float* m_host, const uint64_t* seeds_host, int n_seeds,
                     float* xt_host, float* err_host, void* stream) {
     if (!c || !p || !x0_host || (!xt_host && (!m_host || !err_host))) return DD_ERR_INVALID;
     const dd_dev_scan_args& q = *p;
-    if (q.B < 1 || q.B > 4096 || q.C < 1 || q.S < 1 || q.S > 4096 || q.b0 < 0 || q.B_all > (1 << 20) || (long long)q.b0 + q.B > q.B_all || q.k < 0 ||
-        q.k > 65535 || ((long long)q.k + 1) * q.B_all > (1ll << 24) || q.ctr < 0 || q.iters < 0 || q.iters > 10000 || (q.iters > 0 && q.advance))
-        return DD_ERR_INVALID;
-    if ((seeds_host != nullptr) != (n_seeds > 0) || n_seeds > (1 << 22) || (seeds_host && n_seeds < q.b0 + q.B)) return DD_ERR_INVALID;
-    if (q.C > 4 || (long long)q.C * q.S * q.S > (1ll << 24)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "scan: 1..4 channels, at most 2^24 elements per image");
+    if (int rc = scan_dev_check(c, q, ((long long)q.k + 1) * q.B_all <= (1ll << 24) && q.ctr >= 0, seeds_host, n_seeds)) return rc;
     if ((long long)q.B * q.C * q.S * q.S > (1ll << 26)) return DD_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)q.B * q.C * q.S * q.S, rows = (size_t)q.k + 2;
@@ -902,44 +938,15 @@ static int dev_scan(dd_ctx* c, dd_dev_scan_args* p, const float* x0_host, const 
     const ScanRow row{q.t_model, q.ka, q.kb, q.tz, q.t0, q.tx, q.ctr, 0};
     if (dev.ok()) dev.ok(hipMemcpy(tab + q.k, &row, sizeof row, hipMemcpyHostToDevice), "hipMemcpy to the device");
     if (dev.ok()) dev.ok(hipMemcpy(&tab[q.k + 1].t_model, &q.next_t_model, sizeof(float), hipMemcpyHostToDevice), "hipMemcpy to the device");
-    const unsigned long long* seeds = seeds_host ? (const unsigned long long*)dev.upload(seeds_host, (size_t)n_seeds * sizeof(uint64_t)) : nullptr;
-    // an input between 8 + 8 elements the kernel must never read
-    auto fenced = [&](const float* host) {
-        float* d = dev.filled<float>((n + 16) * 4, 0xFF);
-        if (dev.ok()) dev.ok(hipMemcpy(d + 8, host, n * 4, hipMemcpyHostToDevice), "hipMemcpy to the device");
-        return d + 8;
-    };
-    const float* dX0 = fenced(x0_host);
-    hipError_t first = hipSuccess;
-    float* dOut = nullptr;
-    const float* dM = nullptr;
-    size_t out_elems = 0;
-    if (xt_host) {
-        out_elems = n + 16;
-        dOut = dev.filled<float>(out_elems * 4, 0xFF);
-        if (dev.ok()) first = launch_scan_diffuse(dX0, dOut + 8, st, tab, seeds, q.B, q.C, q.S, q.b0, s);
-    } else {
-        dM = fenced(m_host);
-        out_elems = ((size_t)q.k + 1) * q.B_all + 8;
-        dOut = dev.filled<float>(out_elems * 4, 0xFF);
-        if (dev.ok()) first = launch_scan_error(dX0, dM, dOut, st, tab, seeds, q.B, q.C, q.S, q.b0, q.B_all, q.advance, s);
-    }
-    if (first == hipErrorInvalidValue) return ctx_fail(c, DD_ERR_INVALID, "scan: operands the launcher refuses");      // (refused before any launch)
-    DEV_HIP(dev, first);
-    DEV_HIP(dev, hipStreamSynchronize(s));
-    dev.download(xt_host ? xt_host : err_host, dOut, out_elems * 4);
-    StepState st1{};
-    dev.download(&st1, st, sizeof st1);
-    if (dev.ok()) { p->t_out = st1.t; p->t_final_out = st1.t_final; p->t_model_out = st1.t_model; }
-    if (q.iters > 0 && dev.ok()) {      // (advance == 0: the launch leaves the state as it found it)
-        float ms = 0.f;
-        DEV_HIP(dev, time_launches(s, q.iters, [&] {
-            return xt_host ? launch_scan_diffuse(dX0, dOut + 8, st, tab, seeds, q.B, q.C, q.S, q.b0, s)
-                           : launch_scan_error(dX0, dM, dOut, st, tab, seeds, q.B, q.C, q.S, q.b0, q.B_all, 0, s);
-        }, &ms));
-        p->ms_out = ms;
-    }
-    return dev.status();
+    const unsigned long long* seeds = scan_dev_seeds(dev, seeds_host, n_seeds);
+    const float* dX0 = scan_dev_fenced(dev, x0_host, n);
+    const float* dM = xt_host ? nullptr : scan_dev_fenced(dev, m_host, n);
+    const size_t out_elems = xt_host ? n + 16 : ((size_t)q.k + 1) * q.B_all + 8;
+    float* dOut = dev.filled<float>(out_elems * 4, 0xFF);
+    return scan_dev_run(c, dev, p, st, s, [&](int advance) {
+        return xt_host ? launch_scan_diffuse(dX0, dOut + 8, st, tab, seeds, q.B, q.C, q.S, q.b0, s)
+                       : launch_scan_error(dX0, dM, dOut, st, tab, seeds, q.B, q.C, q.S, q.b0, q.B_all, advance, s);
+    }, [&] { dev.download(xt_host ? xt_host : err_host, dOut, out_elems * 4); });
 }
 
 // dd_dev_scan_exits_error: scan_exits_error_kernel through launch_scan_exits_error, once.  The table has 1001 rows of 0xFF bytes; row t holds the
@@ -950,11 +957,7 @@ static int dev_scan_exits(dd_ctx* c, dd_dev_scan_exits_args* p, const float* x0_
     if (!c || !p || !x0_host || !eps_host || !mse_host || !tgtu_host) return DD_ERR_INVALID;
     const dd_dev_scan_exits_args& q = *p;
     if (q.exits < 1 || (q.exits > 1 && (!outs_host || !cls_host || !pred_host))) return DD_ERR_INVALID;
-    if (q.B < 1 || q.B > 4096 || q.C < 1 || q.S < 1 || q.S > 4096 || q.b0 < 0 || q.B_all > (1 << 20) || (long long)q.b0 + q.B > q.B_all || q.k < 0 ||
-        q.k > 65535 || q.t < 0 || q.t > 999 || q.next < 0 || q.next > 999 || q.ctr < q.k || q.iters < 0 || q.iters > 10000 || (q.iters > 0 && q.advance))
-        return DD_ERR_INVALID;
-    if ((seeds_host != nullptr) != (n_seeds > 0) || n_seeds > (1 << 22) || (seeds_host && n_seeds < q.b0 + q.B)) return DD_ERR_INVALID;
-    if (q.C > 4 || (long long)q.C * q.S * q.S > (1ll << 24)) return ctx_fail(c, DD_ERR_UNSUPPORTED, "scan: 1..4 channels, at most 2^24 elements per image");
+    if (int rc = scan_dev_check(c, q, q.t >= 0 && q.t <= 999 && q.next >= 0 && q.next <= 999 && q.ctr >= q.k, seeds_host, n_seeds)) return rc;
     if (q.exits > 32) return ctx_fail(c, DD_ERR_UNSUPPORTED, "scan: at most 32 exits");
     if (((long long)q.k + 1) * q.exits * q.B_all > (1ll << 24) || (long long)q.B * q.C * q.S * q.S * q.exits > (1ll << 27)) return DD_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
@@ -968,41 +971,22 @@ static int dev_scan_exits(dd_ctx* c, dd_dev_scan_exits_args* p, const float* x0_
     if (dev.ok() && q.next != q.t) dev.ok(hipMemcpy(&tab[q.next].t_model, &q.next_t_model, sizeof(float), hipMemcpyHostToDevice), "hipMemcpy to the device");
     if (dev.ok()) dev.ok(hipMemcpy(tab + q.t, &row, sizeof row, hipMemcpyHostToDevice), "hipMemcpy to the device");
     if (dev.ok()) dev.ok(hipMemcpy(tab + SCAN_EXITS_ROWS, &base, sizeof base, hipMemcpyHostToDevice), "hipMemcpy to the device");
-    const unsigned long long* seeds = seeds_host ? (const unsigned long long*)dev.upload(seeds_host, (size_t)n_seeds * sizeof(uint64_t)) : nullptr;
-    // an input between 8 + 8 elements the kernel must never read
-    auto fenced = [&](const float* host, size_t elems) {
-        float* d = dev.filled<float>((elems + 16) * 4, 0xFF);
-        if (dev.ok()) dev.ok(hipMemcpy(d + 8, host, elems * 4, hipMemcpyHostToDevice), "hipMemcpy to the device");
-        return d + 8;
-    };
-    const float* dX0 = fenced(x0_host, n);
-    const float* dEps = fenced(eps_host, n);
-    const float* dOuts = E > 1 ? fenced(outs_host, n * (E - 1)) : nullptr;
-    const float* dCls = E > 1 ? fenced(cls_host, (size_t)(E - 1) * q.B) : nullptr;
+    const unsigned long long* seeds = scan_dev_seeds(dev, seeds_host, n_seeds);
+    const float* dX0 = scan_dev_fenced(dev, x0_host, n);
+    const float* dEps = scan_dev_fenced(dev, eps_host, n);
+    const float* dOuts = E > 1 ? scan_dev_fenced(dev, outs_host, n * (E - 1)) : nullptr;
+    const float* dCls = E > 1 ? scan_dev_fenced(dev, cls_host, (size_t)(E - 1) * q.B) : nullptr;
     const size_t mse_elems = ((size_t)q.k + 1) * E * q.B_all + 8, pred_elems = ((size_t)q.k + 1) * (E - 1) * q.B_all + 8;
     float* dMse = dev.filled<float>(mse_elems * 4, 0xFF);
     float* dTgt = dev.filled<float>(mse_elems * 4, 0xFF);
     float* dPred = E > 1 ? dev.filled<float>(pred_elems * 4, 0xFF) : nullptr;
-    auto launch = [&](int advance) {
+    return scan_dev_run(c, dev, p, st, s, [&](int advance) {
         return launch_scan_exits_error(dX0, dOuts, dEps, dCls, dMse, dTgt, dPred, st, tab, seeds, q.B, q.C, q.S, E, q.b0, q.B_all, advance, s);
-    };
-    hipError_t first = hipSuccess;
-    if (dev.ok()) first = launch(q.advance);
-    if (first == hipErrorInvalidValue) return ctx_fail(c, DD_ERR_INVALID, "scan: operands the launcher refuses");      // (refused before any launch)
-    DEV_HIP(dev, first);
-    DEV_HIP(dev, hipStreamSynchronize(s));
-    dev.download(mse_host, dMse, mse_elems * 4);
-    dev.download(tgtu_host, dTgt, mse_elems * 4);
-    if (E > 1) dev.download(pred_host, dPred, pred_elems * 4);
-    StepState st1{};
-    dev.download(&st1, st, sizeof st1);
-    if (dev.ok()) { p->t_out = st1.t; p->t_final_out = st1.t_final; p->t_model_out = st1.t_model; }
-    if (q.iters > 0 && dev.ok()) {      // (advance == 0: the launch leaves the state as it found it)
-        float ms = 0.f;
-        DEV_HIP(dev, time_launches(s, q.iters, [&] { return launch(0); }, &ms));
-        p->ms_out = ms;
-    }
-    return dev.status();
+    }, [&] {
+        dev.download(mse_host, dMse, mse_elems * 4);
+        dev.download(tgtu_host, dTgt, mse_elems * 4);
+        if (E > 1) dev.download(pred_host, dPred, pred_elems * 4);
+    });
 }
 
 extern "C" {

@@ -79,7 +79,7 @@ struct dd_ctx {
     dd::DevBuf<float> k_stage;       //   and the known image and mask the loop reads (x0 [B, C, S, S] | mask [B, 1, S, S], staged like x)
     dd::DevBuf<float> m_stage;       // dd_sample_multistep_threshold: the step's (guided) model output [B, C, S, S], chain k's images at its first image:
                                  //   written by the output head and read by threshold_step_kernel within one step, never across steps
-    dd::RowTable<dd::ScanRow> stab;      // dd_scan_error: the scan's rows,
+    dd::RowTable<dd::ScanRow> stab;      // the scans (loops.hip stage_scan fills both).  dd_scan_error: the scan's rows,
     dd::DevBuf<float> scan_ws;       //   and its scratch, x_t | eps ([B, C, S, S] each; chain k's images at its first image) | err [n, B]: grown before the loop,
                                  //   never on the launch path.  dd_scan_error_early_exit: x_t | mse [n, depth + 1, B] | target (the same) | pred [n, depth, B]; its
                                  //   table has 1001 rows (by timestep, and the base row) and its taps live in the model's ee_ws

@@ -441,64 +441,106 @@ int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, Mods mo, void
     return run_loop(c, L, s);
 }
 
-// dd_scan_error: the denoising-error scan as one more loop of run_loop.  A step is diffuse -> forward_eps -> error (scan.hip); the
-// images x0 are staged like a known image (k_stage: a later call with other tensors of the same shape replays the same graphs), the
-// rows live in the context's stab, and x_t, the model output and the err rows in its scan_ws (x_t | eps | err).  With graphs run_loop's
-// staged x is the chain's x_t buffer (scan_ws' x_t part then only passes through its copies); eagerly the loop runs on scan_ws itself.
-// The err rows are disjoint per image: two half-batch chains need no join kernel.
+// The denoising-error scans (dd_scan_error, dd_scan_error_early_exit) as one more loop of run_loop.  A step is diffuse -> forward_eps ->
+// the entry's error kernel (scan.hip); the images x0 are staged like a known image (k_stage: a later call with other tensors of the same
+// shape replays the same graphs), the rows live in the context's stab, and x_t with the entry's results behind it in its scan_ws
+// (engine_state.h has the layouts).  With graphs run_loop's staged x is the chain's x_t buffer (scan_ws' x_t part then only passes through
+// its copies); eagerly the loop runs on scan_ws itself.  The result rows are disjoint per image: two half-batch chains need no join kernel.
+//
+// The checks of a scan behind check_call, in this order (Args: dd_scan_args or dd_scan_exits_args, one layout up to `reserved`): the
+// pointers (results: the entry's own result tensors are all there), the step count, the counter base, the noise mode, the entry's own
+// checks, the image seeds and the shape the scan kernels take
+template <typename Args, typename Own>
+int check_scan(dd_ctx* c, const Args* a, const char* entry, bool results, Own&& own_checks) {
+    if (!results || !a->x0_dev || !a->t || !a->ka || !a->kb || !a->tz || !a->t0 || !a->tx) return ctx_fail(c, DD_ERR_INVALID, "null tensor / table");
+    if (a->n_steps < 1 || a->n_steps > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "n_steps outside [1, 2^20]");
+    if (a->counter_base < 0 || a->counter_base > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "counter_base outside [0, 2^20]");
+    if (a->noise_mode != DD_NOISE_PHILOX)
+        return ctx_fail(c, DD_ERR_INVALID, std::string(entry) + " draws its noise on the device: noise_mode must be DD_NOISE_PHILOX");
+    int rc = own_checks();
+    if (rc || (rc = check_image_seeds(c, a->noise_mode, a->B))) return rc;
+    const dd_config& cfg = a->model->cfg;
+    if (cfg.in_chans < 1 || cfg.in_chans > 4 || (size_t)cfg.in_chans * cfg.img_size * cfg.img_size > ((size_t)1 << 24))
+        return ctx_fail(c, DD_ERR_UNSUPPORTED, "the scan kernels take 1..4 channels and at most 2^24 elements per image");
+    return DD_OK;
+}
+
+// What a checked scan runs on: the staged seeds, row table and images (chw elements each, elems in all), and scan_ws as x_t | `results`
+struct ScanStage { const unsigned long long* seeds = nullptr; const ScanRow* tab; const float* x0; float* results; size_t chw, elems; };
+// ... staged on s: the image seeds, `rows` rows (row(i) each) in stab, x0 in k_stage, and scan_ws grown to x_t and result_elems behind it
+template <typename Args, typename F>
+int stage_scan(dd_ctx* c, const Args* a, size_t rows, F&& row, size_t result_elems, hipStream_t s, ScanStage* g) {
+    const dd_config& cfg = a->model->cfg;
+    g->chw = (size_t)cfg.in_chans * cfg.img_size * cfg.img_size;
+    g->elems = (size_t)a->B * g->chw;
+    int rc = stage_image_seeds(c, a->noise_mode, s, &g->seeds);
+    if (rc || (rc = upload_rows(c, c->stab, rows, s, row))) return rc;
+    if ((rc = c->k_stage.grow(c, g->elems))) return rc;
+    DD_HIP(c, hipMemcpyAsync(c->k_stage.p, a->x0_dev, g->elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if ((rc = c->scan_ws.grow(c, g->elems + result_elems))) return rc;
+    g->tab = c->stab.dev.p; g->x0 = c->k_stage.p; g->results = c->scan_ws.p + g->elems;
+    return DD_OK;
+}
+
+// where a chain's forward of a scan step writes its output, and the taps it takes (tapped: an early-exit model's)
+struct ScanForward { float* eps; EeTaps ee; bool tapped; };
+// a result table of a scan, copied to the caller's tensor behind the loop, so that a captured step never names it
+struct ScanOut { float* dst; const float* src; size_t elems; };
+
+// The loop of a staged scan: `kind`'s graphs, the step state started at row first_row, key(k) the entry's own key fields, forward(m, slice)
+// the chain's ScanForward, error(f, x0, chain, slice, s) the launch that ends the step, and outs
+template <typename Args, typename Key, typename Forward, typename Error>
+int run_scan(dd_ctx* c, const Args* a, const ScanStage& g, GraphKind kind, int first_row, Key&& key, Forward&& forward, Error&& error,
+             std::initializer_list<ScanOut> outs, hipStream_t s) {
+    const int C = a->model->cfg.in_chans, S = a->model->cfg.img_size;
+    Loop L{kind, a->model, nullptr, a->n_steps, -1, c->scan_ws.p, a->y_dev, a->B, Mods{.seeds = g.seeds}, a->use_graph != 0};
+    L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_scan(st, g.tab, (unsigned long long)a->seed, ss, first_row); };
+    L.key = [&](GraphKey& k, const Slice& sl) {
+        k.noise = a->noise_mode; k.atab = g.tab; k.kx0 = g.x0 + (size_t)sl.b0 * g.chw;
+        key(k);
+        if (sl.chains == 2 && sl.chain == 0) k.b0 = -1;     // (chain 0 of two writes rows of 2 B images -- not the whole batch's graph)
+    };
+    L.step = [&](dd_model* mm, const Chain& ch, const Slice& sl, hipStream_t ss) -> int {
+        const float* x0 = g.x0 + (size_t)sl.b0 * g.chw;
+        const ScanForward f = forward(mm, sl);
+        DD_HIP(c, launch_scan_diffuse(x0, sl.x, ch.st, g.tab, sl.mods.seeds, sl.B, C, S, sl.b0, ss));
+        if (int r = forward_eps(c, mm, ch, sl.x, sl.y, f.eps, sl.B, ss, {.ee = f.tapped ? &f.ee : nullptr})) return r;
+        DD_HIP(c, error(f, x0, ch, sl, ss));
+        return DD_OK;
+    };
+    L.tail = [&](int, hipStream_t ss) -> int {
+        for (const ScanOut& o : outs) DD_HIP(c, hipMemcpyAsync(o.dst, o.src, o.elems * sizeof(float), hipMemcpyDeviceToDevice, ss));
+        return DD_OK;
+    };
+    return run_loop(c, L, s);
+}
+
+// dd_scan_error: a plain model; the step's index is the row, and scan_ws holds x_t | eps | err [n, B]
 int scan_error(dd_ctx* c, const dd_scan_args* a, void* stream) {
     if (!c || !a) return DD_ERR_INVALID;
     dd_model* m = a->model;
     if (m && m->ctx == c && m->ee_type >= 0)
         return ctx_fail(c, DD_ERR_INVALID, "dd_scan_error takes a plain model, not one created with dd_model_enable_early_exit");
     int rc = check_call(c, m, a->B, a->y_dev);
-    if (rc) return rc;
-    if (!a->x0_dev || !a->err_dev || !a->t || !a->ka || !a->kb || !a->tz || !a->t0 || !a->tx) return ctx_fail(c, DD_ERR_INVALID, "null tensor / table");
-    if (a->n_steps < 1 || a->n_steps > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "n_steps outside [1, 2^20]");
-    if (a->counter_base < 0 || a->counter_base > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "counter_base outside [0, 2^20]");
-    if (a->noise_mode != DD_NOISE_PHILOX) return ctx_fail(c, DD_ERR_INVALID, "dd_scan_error draws its noise on the device: noise_mode must be DD_NOISE_PHILOX");
-    if ((rc = check_image_seeds(c, a->noise_mode, a->B))) return rc;
-    const int C = m->cfg.in_chans, S = m->cfg.img_size;
-    const size_t chw = (size_t)C * S * S, elems = (size_t)a->B * chw;
-    if (C < 1 || C > 4 || chw > ((size_t)1 << 24))
-        return ctx_fail(c, DD_ERR_UNSUPPORTED, "the scan kernels take 1..4 channels and at most 2^24 elements per image");
+    if (rc || (rc = check_scan(c, a, "dd_scan_error", a->err_dev != nullptr, [] { return DD_OK; }))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int n = a->n_steps;
-    const unsigned long long* seeds = nullptr;
-    if ((rc = stage_image_seeds(c, a->noise_mode, s, &seeds))) return rc;
+    const int n = a->n_steps, C = m->cfg.in_chans, S = m->cfg.img_size;
+    const size_t err_elems = (size_t)n * a->B;
+    ScanStage g;
     // n rows + one more whose timestep the last step hands on (never used), as the step table of dd_sample_affine
-    rc = upload_rows(c, c->stab, (size_t)n + 1, s, [a, n](size_t k) {
+    rc = stage_scan(c, a, (size_t)n + 1, [a, n](size_t k) {
         return k < (size_t)n ? ScanRow{a->t[k], a->ka[k], a->kb[k], a->tz[k], a->t0[k], a->tx[k], a->counter_base + (int)k, 0}
                              : ScanRow{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0, 0};
-    });
+    }, (size_t)a->B * C * S * S + err_elems, s, &g);
     if (rc) return rc;
-    if ((rc = c->k_stage.grow(c, elems))) return rc;
-    const size_t err_elems = (size_t)n * a->B;
-    if ((rc = c->scan_ws.grow(c, 2 * elems + err_elems))) return rc;
-    DD_HIP(c, hipMemcpyAsync(c->k_stage.p, a->x0_dev, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
-    const ScanRow* tab = c->stab.dev.p;
-    const float* x0_run = c->k_stage.p;
-    float* eps_run = c->scan_ws.p + elems;
-    float* err_run = eps_run + elems;       // [n, B]: copied to the caller's tensor behind the loop, so a captured step never names it
-    Loop L{GRAPH_SCAN, m, nullptr, n, -1, c->scan_ws.p, a->y_dev, a->B, Mods{.seeds = seeds}, a->use_graph != 0};
-    L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_scan(st, tab, (unsigned long long)a->seed, ss); };
-    L.key = [&](GraphKey& k, const Slice& sl) {
-        k.noise = a->noise_mode; k.atab = tab; k.kx0 = x0_run + (size_t)sl.b0 * chw; k.aux0 = err_run; k.aux1 = eps_run;
-        if (sl.chains == 2 && sl.chain == 0) k.b0 = -1;     // (chain 0 of two writes rows of 2 B images -- not the whole batch's graph)
-    };
-    L.step = [&](dd_model* mm, const Chain& ch, const Slice& sl, hipStream_t ss) -> int {
-        const float* x0 = x0_run + (size_t)sl.b0 * chw;
-        float* eps = eps_run + (size_t)sl.b0 * chw;
-        DD_HIP(c, launch_scan_diffuse(x0, sl.x, ch.st, tab, sl.mods.seeds, sl.B, C, S, sl.b0, ss));
-        if (int r = forward_eps(c, mm, ch, sl.x, sl.y, eps, sl.B, ss, {})) return r;
-        DD_HIP(c, launch_scan_error(x0, eps, err_run, ch.st, tab, sl.mods.seeds, sl.B, C, S, sl.b0, a->B, 1, ss));
-        return DD_OK;
-    };
-    L.tail = [&](int, hipStream_t ss) -> int {
-        DD_HIP(c, hipMemcpyAsync(a->err_dev, err_run, err_elems * sizeof(float), hipMemcpyDeviceToDevice, ss));
-        return DD_OK;
-    };
-    return run_loop(c, L, s);
+    float* eps_run = g.results;
+    float* err_run = eps_run + g.elems;
+    return run_scan(c, a, g, GRAPH_SCAN, 0, [&](GraphKey& k) { k.aux0 = err_run; k.aux1 = eps_run; },
+                    [&](dd_model*, const Slice& sl) { return ScanForward{eps_run + (size_t)sl.b0 * g.chw, {}, false}; },
+                    [&](const ScanForward& f, const float* x0, const Chain& ch, const Slice& sl, hipStream_t ss) {
+                        return launch_scan_error(x0, f.eps, err_run, ch.st, g.tab, sl.mods.seeds, sl.B, C, S, sl.b0, a->B, 1, ss);
+                    },
+                    {{a->err_dev, err_run, err_elems}}, s);
 }
 // the early-exit scratch of a model (eps | cls | outs per chain, then dd_sample_early_exit's two sum tables), allocated on first use
 int ensure_ee_ws(dd_ctx* c, dd_model* m) {
@@ -507,86 +549,56 @@ int ensure_ee_ws(dd_ctx* c, dd_model* m) {
     return DD_OK;
 }
 
-// dd_scan_error_early_exit: dd_scan_error's loop for an early-exit model.  A step is diffuse -> forward_eps with EeTaps -> exits error
-// (scan.hip).  The step state holds the integer TIMESTEP, not the step's index (the per-timestep probe tables read it), so the row table is
-// indexed by timestep -- 1000 rows of which the grid's are filled, each naming the next, and the base row with the call's counter_base.
-// The taps go to the model's early-exit scratch (each chain's block, as dd_sample_early_exit), the three result tables to scan_ws behind
-// x_t; they are copied to the caller's tensors behind the join.  Rows are disjoint per image: no join kernel.
+// dd_scan_error_early_exit: an early-exit model.  The step state holds the integer TIMESTEP, not the step's index (the per-timestep probe
+// tables of the forward read it), so the row table is indexed by timestep -- 1000 rows of which the grid's are filled, each naming the
+// next, and the base row with the call's counter_base.  The taps go to the model's early-exit scratch (each chain's block, as
+// dd_sample_early_exit), and scan_ws holds x_t | mse | target | pred.
 int scan_exits(dd_ctx* c, const dd_scan_exits_args* a, void* stream) {
     if (!c || !a) return DD_ERR_INVALID;
     dd_model* m = a->model;
     int rc = check_call(c, m, a->B, a->y_dev);
     if (rc) return rc;
     if (m->ee_type < 0) return ctx_fail(c, DD_ERR_STATE, "model was not created with dd_model_enable_early_exit");
-    if (!a->x0_dev || !a->mse_dev || !a->target_dev || !a->pred_dev || !a->t || !a->ka || !a->kb || !a->tz || !a->t0 || !a->tx)
-        return ctx_fail(c, DD_ERR_INVALID, "null tensor / table");
-    if (a->n_steps < 1 || a->n_steps > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "n_steps outside [1, 2^20]");
-    if (a->counter_base < 0 || a->counter_base > (1 << 20)) return ctx_fail(c, DD_ERR_INVALID, "counter_base outside [0, 2^20]");
-    if (a->noise_mode != DD_NOISE_PHILOX)
-        return ctx_fail(c, DD_ERR_INVALID, "dd_scan_error_early_exit draws its noise on the device: noise_mode must be DD_NOISE_PHILOX");
-    const int n = a->n_steps;
-    bool seen[SCAN_EXITS_ROWS] = {};
-    for (int k = 0; k < n; ++k) {
-        const float t = a->t[k];
-        if (!(t >= 0.f && t <= 999.f) || t != (float)(int)t)
-            return ctx_fail(c, DD_ERR_INVALID, "timestep " + std::to_string(k) + " is not an integer in [0, 999]: the probe tables are indexed by it");
-        if (seen[(int)t]) return ctx_fail(c, DD_ERR_INVALID, "timestep " + std::to_string((int)t) + " occurs twice");
-        seen[(int)t] = true;
-    }
-    if ((rc = check_image_seeds(c, a->noise_mode, a->B))) return rc;
-    const int C = m->cfg.in_chans, S = m->cfg.img_size, depth = m->cfg.depth, E = depth + 1;
-    const size_t chw = (size_t)C * S * S, elems = (size_t)a->B * chw;
-    if (C < 1 || C > 4 || chw > ((size_t)1 << 24))
-        return ctx_fail(c, DD_ERR_UNSUPPORTED, "the scan kernels take 1..4 channels and at most 2^24 elements per image");
+    std::vector<int> at(SCAN_EXITS_ROWS, -1);       // timestep -> its step in the call
+    rc = check_scan(c, a, "dd_scan_error_early_exit", a->mse_dev && a->target_dev && a->pred_dev, [&]() -> int {
+        for (int k = 0; k < a->n_steps; ++k) {
+            const float t = a->t[k];
+            if (!(t >= 0.f && t <= 999.f) || t != (float)(int)t)
+                return ctx_fail(c, DD_ERR_INVALID, "timestep " + std::to_string(k) + " is not an integer in [0, 999]: the probe tables are indexed by it");
+            if (at[(int)t] >= 0) return ctx_fail(c, DD_ERR_INVALID, "timestep " + std::to_string((int)t) + " occurs twice");
+            at[(int)t] = k;
+        }
+        return DD_OK;
+    });
+    if (rc) return rc;
+    const int n = a->n_steps, C = m->cfg.in_chans, S = m->cfg.img_size, depth = m->cfg.depth, E = depth + 1;
     if (E > 32) return ctx_fail(c, DD_ERR_UNSUPPORTED, "the early-exit scan takes at most 32 exits (depth + 1)");
     hipStream_t s = (hipStream_t)stream;
-    const unsigned long long* seeds = nullptr;
-    if ((rc = stage_image_seeds(c, a->noise_mode, s, &seeds))) return rc;
     if ((rc = ensure_ee_ws(c, m))) return rc;
-    std::vector<int> at(SCAN_EXITS_ROWS, -1);       // timestep -> its step in the call
-    for (int k = 0; k < n; ++k) at[(int)a->t[k]] = k;
-    rc = upload_rows(c, c->stab, (size_t)SCAN_EXITS_ROWS + 1, s, [&](size_t t) {
+    const size_t mse_elems = (size_t)n * E * a->B, pred_elems = (size_t)n * depth * a->B;
+    ScanStage g;
+    rc = stage_scan(c, a, (size_t)SCAN_EXITS_ROWS + 1, [&](size_t t) {
         if (t == (size_t)SCAN_EXITS_ROWS) return ScanRow{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, a->counter_base, 0};
         const int k = at[t];
         if (k < 0) return ScanRow{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0, 0};
         // (the last step hands on the first timestep: a valid row, never used)
         return ScanRow{a->t[k], a->ka[k], a->kb[k], a->tz[k], a->t0[k], a->tx[k], a->counter_base + k, (int)a->t[k + 1 < n ? k + 1 : 0]};
-    });
+    }, 2 * mse_elems + pred_elems, s, &g);
     if (rc) return rc;
-    if ((rc = c->k_stage.grow(c, elems))) return rc;
-    const size_t mse_elems = (size_t)n * E * a->B, pred_elems = (size_t)n * depth * a->B;
-    if ((rc = c->scan_ws.grow(c, elems + 2 * mse_elems + pred_elems))) return rc;
-    DD_HIP(c, hipMemcpyAsync(c->k_stage.p, a->x0_dev, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
-    const ScanRow* tab = c->stab.dev.p;
-    const float* x0_run = c->k_stage.p;
-    float* mse_run = c->scan_ws.p + elems;       // mse | target | pred: copied out behind the loop, so a captured step never names the caller's
+    float* mse_run = g.results;
     float* tgt_run = mse_run + mse_elems;
     float* pred_run = tgt_run + mse_elems;
-    const int t_first = (int)a->t[0];
-    Loop L{GRAPH_SCAN_EXITS, m, nullptr, n, -1, c->scan_ws.p, a->y_dev, a->B, Mods{.seeds = seeds}, a->use_graph != 0};
-    L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_scan(st, tab, (unsigned long long)a->seed, ss, t_first); };
-    L.key = [&](GraphKey& k, const Slice& sl) {
-        k.noise = a->noise_mode; k.variance = n; k.atab = tab; k.kx0 = x0_run + (size_t)sl.b0 * chw; k.aux0 = mse_run; k.aux1 = m->ee_ws;
-        if (sl.chains == 2 && sl.chain == 0) k.b0 = -1;     // (chain 0 of two writes rows of 2 B images -- not the whole batch's graph)
-    };
-    L.step = [&](dd_model* mm, const Chain& ch, const Slice& sl, hipStream_t ss) -> int {
-        const float* x0 = x0_run + (size_t)sl.b0 * chw;
-        float* eps = mm->ee_ws + ee_scratch_elems(mm, sl.b0);      // the chain's block: eps | cls | outs (enqueue_ee_step's layout)
-        float* cls = eps + (size_t)sl.B * chw;
-        float* outs = cls + (size_t)depth * sl.B;
-        const EeTaps ee{cls, outs, 0};
-        DD_HIP(c, launch_scan_diffuse(x0, sl.x, ch.st, tab, sl.mods.seeds, sl.B, C, S, sl.b0, ss));
-        if (int r = forward_eps(c, mm, ch, sl.x, sl.y, eps, sl.B, ss, {.ee = &ee})) return r;
-        DD_HIP(c, launch_scan_exits_error(x0, outs, eps, cls, mse_run, tgt_run, pred_run, ch.st, tab, sl.mods.seeds, sl.B, C, S, E, sl.b0, a->B, 1, ss));
-        return DD_OK;
-    };
-    L.tail = [&](int, hipStream_t ss) -> int {
-        DD_HIP(c, hipMemcpyAsync(a->mse_dev, mse_run, mse_elems * sizeof(float), hipMemcpyDeviceToDevice, ss));
-        DD_HIP(c, hipMemcpyAsync(a->target_dev, tgt_run, mse_elems * sizeof(float), hipMemcpyDeviceToDevice, ss));
-        DD_HIP(c, hipMemcpyAsync(a->pred_dev, pred_run, pred_elems * sizeof(float), hipMemcpyDeviceToDevice, ss));
-        return DD_OK;
-    };
-    return run_loop(c, L, s);
+    return run_scan(c, a, g, GRAPH_SCAN_EXITS, (int)a->t[0], [&](GraphKey& k) { k.variance = n; k.aux0 = mse_run; k.aux1 = m->ee_ws; },
+                    [&](dd_model* mm, const Slice& sl) {      // the chain's block: eps | cls | outs (enqueue_ee_step's layout)
+                        float* eps = mm->ee_ws + ee_scratch_elems(mm, sl.b0);
+                        float* cls = eps + (size_t)sl.B * g.chw;
+                        return ScanForward{eps, EeTaps{cls, cls + (size_t)depth * sl.B, 0}, true};
+                    },
+                    [&](const ScanForward& f, const float* x0, const Chain& ch, const Slice& sl, hipStream_t ss) {
+                        return launch_scan_exits_error(x0, f.ee.outs, f.eps, f.ee.cls, mse_run, tgt_run, pred_run, ch.st, g.tab, sl.mods.seeds, sl.B, C, S,
+                                                       E, sl.b0, a->B, 1, ss);
+                    },
+                    {{a->mse_dev, mse_run, mse_elems}, {a->target_dev, tgt_run, mse_elems}, {a->pred_dev, pred_run, pred_elems}}, s);
 }
 }  // namespace
 

@@ -190,7 +190,7 @@ __device__ __forceinline__ float scan_mean(float sum, int n) { return __fdiv_rn(
 // lies in [0, 1] and scan_tanh_abs(0) == 0.  inf gives the clamp's value; a NaN is not an argument (fminf drops it).
 // E_TANH: the largest |scan_tanh_abs(d) - tanh|d|| over EVERY fp32 d against float64 tanh, swept on the CPU with the mirror
 // (tools/scan_tanh_sweep.py: all 1 092 616 193 values of [0, 10] and the clamp's tail) = 1.66e-7
-// (1.6533e-7, taken at d = 1.1165210; spec: <= 1e-6).
+// (1.6533e-7, taken at d = 1.1165210; spec: <= 1e-6); the tests' bounds take it from tests/scan_support.py E_TANH.
 constexpr float SCAN_TANH_CLAMP = 10.f;
 __device__ __forceinline__ float scan_tanh_abs(float d) {
 #pragma clang fp contract(off)

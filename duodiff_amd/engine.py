@@ -635,6 +635,19 @@ def sample_early_exit_loop(ctx: Context, model: Model, x, threshold, *, t_start=
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
 
+def _scan_args(args, model, rows, counter_base):
+    """The fields dd_scan_args and dd_scan_exits_args share, from the six row arrays (kept alive on args as float32); returns n."""
+    args._rows = {k: np.ascontiguousarray(rows[k], np.float32) for k in ("t", "ka", "kb", "tz", "t0", "tx")}
+    n = len(args._rows["t"])
+    assert all(v.shape == (n,) for v in args._rows.values())
+    for k, v in args._rows.items():
+        setattr(args, k, v.ctypes.data_as(C.POINTER(C.c_float)))
+    args.model = model.handle
+    args.n_steps = n
+    args.counter_base = int(counter_base)
+    return n
+
+
 def scan_error_loop(ctx: Context, model: Model, x0, rows, *, y=None, seed=0, counter_base=0, err=None, use_graph=True, stream=None):
     """dd_scan_error: the denoising error of `model` on the images x0 [B, C, S, S] (model space; only read) at every row of `rows`
     (step_plan.scan_rows, or any slice of it): step k noises the images to x_t = ka[k] x0 + kb[k] z with the image's own Philox draw
@@ -644,14 +657,7 @@ def scan_error_loop(ctx: Context, model: Model, x0, rows, *, y=None, seed=0, cou
     seeds) and counter_base see the same (x0, z, t): a paired comparison."""
     assert x0.is_cuda and x0.dtype == torch.float32 and x0.is_contiguous() and x0.dim() == 4
     args = L.dd_scan_args()
-    tab = {k: np.ascontiguousarray(rows[k], np.float32) for k in ("t", "ka", "kb", "tz", "t0", "tx")}
-    n = len(tab["t"])
-    assert all(v.shape == (n,) for v in tab.values())
-    for k, v in tab.items():
-        setattr(args, k, v.ctypes.data_as(C.POINTER(C.c_float)))
-    args.model = model.handle
-    args.n_steps = n
-    args.counter_base = int(counter_base)
+    n = _scan_args(args, model, rows, counter_base)
     err = torch.empty(n, x0.shape[0], device=x0.device, dtype=torch.float32) if err is None else err
     assert err.is_cuda and err.dtype == torch.float32 and err.is_contiguous() and tuple(err.shape) == (n, x0.shape[0])
     args.err_dev = err.data_ptr()
@@ -667,14 +673,7 @@ def scan_exits_loop(ctx: Context, model: Model, x0, rows, *, y=None, seed=0, cou
     sampler compares with --threshold)."""
     assert x0.is_cuda and x0.dtype == torch.float32 and x0.is_contiguous() and x0.dim() == 4
     args = L.dd_scan_exits_args()
-    tab = {k: np.ascontiguousarray(rows[k], np.float32) for k in ("t", "ka", "kb", "tz", "t0", "tx")}
-    n = len(tab["t"])
-    assert all(v.shape == (n,) for v in tab.values())
-    for k, v in tab.items():
-        setattr(args, k, v.ctypes.data_as(C.POINTER(C.c_float)))
-    args.model = model.handle
-    args.n_steps = n
-    args.counter_base = int(counter_base)
+    n = _scan_args(args, model, rows, counter_base)
     B, depth = x0.shape[0], model.mp.depth
     mse, target = (torch.empty(n, depth + 1, B, device=x0.device, dtype=torch.float32) for _ in range(2))
     pred = torch.empty(n, depth, B, device=x0.device, dtype=torch.float32)

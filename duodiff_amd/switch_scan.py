@@ -16,12 +16,13 @@ Images: a folder of PNGs of the model's size (mapped through 2 v - 1) or a ``.np
 its numbers depend on the image and its seed, not on the batch it ran in.
 """
 import json
-import math
 from argparse import ArgumentParser
 from pathlib import Path
 
 import numpy as np
 
+from .scan_common import (add_scan_options, batches, check_images_path, check_label_options, check_labels, check_numbers, gap_statistics,
+                          load_images, load_labels, scan_timesteps)
 from .step_plan import SCAN_PARAMETRIZATIONS, scan_rows
 
 
@@ -34,17 +35,6 @@ def suggest_t_switch(timesteps, e_first, e_late, tolerance, sems=2.0):
     999 .. 700.  None -- run the late model alone -- where 999 itself is not acceptable (never 0: to the sampler 0 means the first model
     everywhere).  ValueError where 999 is not on the grid.  Pure numpy."""
     return _suggest(timesteps, *gap_statistics(e_first, e_late), tolerance, sems)
-
-
-def gap_statistics(e_first, e_late):
-    """(gap, sem) per timestep of suggest_t_switch, float64; one image: sem = 0"""
-    ef, el = np.asarray(e_first, np.float64), np.asarray(e_late, np.float64)
-    if ef.shape != el.shape or ef.ndim != 2 or ef.shape[1] < 1:
-        raise ValueError("e_first and e_late must both be [timesteps, images]")
-    d, base = ef - el, el.mean(axis=1)
-    n = ef.shape[1]
-    sem = d.std(axis=1, ddof=1) / np.sqrt(n) / base if n > 1 else np.zeros(len(base))
-    return d.mean(axis=1) / base, sem
 
 
 def _suggest(timesteps, gap, sem, tolerance, sems):
@@ -62,45 +52,19 @@ def _suggest(timesteps, gap, sem, tolerance, sems):
     return None if t_min is None else 1000 - int(t_min)
 
 
-def scan_timesteps(timesteps=None, stride=None):
-    """--timesteps as given, or --stride N: 999, 999 - N, ... (999 always, 0 only if it is hit)"""
-    if (timesteps is None) == (stride is None):
-        raise ValueError("give --timesteps or --stride, one of them")
-    if stride is not None:
-        if stride < 1:
-            raise ValueError(f"--stride {stride} must be at least 1")
-        return list(range(999, -1, -int(stride)))
-    ts = [int(t) for t in timesteps]
-    if not ts or any(not 0 <= t <= 999 for t in ts):
-        raise ValueError("--timesteps must lie in [0, 999]")
-    if len(set(ts)) != len(ts):
-        raise ValueError("--timesteps holds a timestep twice")
-    return ts
-
-
 def get_args(argv=None):
     p = ArgumentParser(description=__doc__.split("\n\n")[0])
-    p.add_argument("--seed", type=int, default=0, help="image i is noised under seed --seed + i")
-    p.add_argument("--config_path", type=str, required=True, help="Path to yaml config file")
-    p.add_argument("--checkpoint_path", type=str, required=True, help="Path to checkpoint of the model")
-    p.add_argument("--config_path_late", type=str, default=None, help="yaml config of the late (full) model: a paired scan")
-    p.add_argument("--checkpoint_path_late", type=str, default=None, help="checkpoint of the late (full) model")
-    p.add_argument("--autoencoder_checkpoint_path", type=str, default=None, help="overrides config['autoencoder']['autoencoder_checkpoint_path']")
-    p.add_argument("--parametrization", type=str, required=True, choices=list(SCAN_PARAMETRIZATIONS))
-    p.add_argument("--images", type=str, required=True, help="a folder of PNGs of the model's size, or a .npy [N, C, S, S] in the model's space")
-    p.add_argument("--encode_images", action="store_true", help="latent models: --images are pixels ([N, 3, 8S, 8S] in [-1, 1], or PNGs); they go through the KL-VAE encoder")
-    p.add_argument("--encode_mean", action="store_true", help="with --encode_images: the posterior's mode instead of a sample")
-    p.add_argument("--class_label", type=int, default=None, help="every image gets this class label")
-    p.add_argument("--labels", type=str, default=None, help=".npy of one integer label per image")
-    p.add_argument("--timesteps", type=int, nargs="+", default=None, metavar="T")
-    p.add_argument("--stride", type=int, default=None, metavar="N", help="the grid 999, 999 - N, ...")
-    p.add_argument("--repeats", type=int, default=1, metavar="R", help="R scans with fresh noise (Philox counters r * len(grid) + k), averaged per image")
-    p.add_argument("--tolerance", type=float, default=0.02, help="largest acceptable relative gap of the first model's error over the late model's")
-    p.add_argument("--sems", type=float, default=2.0, help="standard errors of the gap added before it is compared with --tolerance")
-    p.add_argument("--batch_size", type=int, default=128)
-    p.add_argument("--output_folder", type=str, required=True)
-    p.add_argument("--precision", choices=["bf16", "fp32"], default="bf16")
-    p.add_argument("--no_graph", action="store_true", help="launch kernels eagerly instead of hipGraph replay")
+    def own(p, after):
+        if after == "checkpoint_path":
+            p.add_argument("--config_path_late", type=str, default=None, help="yaml config of the late (full) model: a paired scan")
+            p.add_argument("--checkpoint_path_late", type=str, default=None, help="checkpoint of the late (full) model")
+            p.add_argument("--autoencoder_checkpoint_path", type=str, default=None, help="overrides config['autoencoder']['autoencoder_checkpoint_path']")
+            p.add_argument("--parametrization", type=str, required=True, choices=list(SCAN_PARAMETRIZATIONS))
+        if after == "images":
+            p.add_argument("--encode_images", action="store_true", help="latent models: --images are pixels ([N, 3, 8S, 8S] in [-1, 1], or PNGs); they go through the KL-VAE encoder")
+            p.add_argument("--encode_mean", action="store_true", help="with --encode_images: the posterior's mode instead of a sample")
+    add_scan_options(p, "Path to yaml config file", "Path to checkpoint of the model",
+                     "largest acceptable relative gap of the first model's error over the late model's", own)
     return p.parse_args(argv)
 
 
@@ -108,20 +72,10 @@ def validate(args, config, config_late=None):
     """Every option check that needs no image and no GPU, before the first model is built: ValueError on a bad combination.  Returns the grid."""
     from .config import ModelParams
     grid = scan_timesteps(args.timesteps, args.stride)
-    if args.seed < 0:
-        raise ValueError("--seed must not be negative: image i is noised under seed --seed + i")
-    if args.repeats < 1:
-        raise ValueError(f"--repeats {args.repeats} must be at least 1")
-    if args.batch_size < 1:
-        raise ValueError(f"--batch_size {args.batch_size} must be at least 1")
-    if not (math.isfinite(args.tolerance) and args.tolerance >= 0):
-        raise ValueError(f"--tolerance {args.tolerance} must be finite and not negative")
-    if not (math.isfinite(args.sems) and args.sems >= 0):
-        raise ValueError(f"--sems {args.sems} must be finite and not negative")
+    check_numbers(args)
     if (args.config_path_late is None) != (args.checkpoint_path_late is None):
         raise ValueError("--config_path_late and --checkpoint_path_late go together")
-    if args.class_label is not None and args.labels is not None:
-        raise ValueError("--class_label and --labels are exclusive")
+    check_label_options(args)
     mp = ModelParams.from_dict(config)
     latent = "autoencoder" in config
     for name, cfg in (("--config_path", config), ("--config_path_late", config_late)):
@@ -130,13 +84,7 @@ def validate(args, config, config_late=None):
         m = ModelParams.from_dict(cfg)
         if (m.img_size, m.in_chans) != (mp.img_size, mp.in_chans) or ("autoencoder" in cfg) != latent:
             raise ValueError("the two models disagree on the image shape (img_size, in_chans, autoencoder)")
-        labelled = args.class_label is not None or args.labels is not None
-        if m.num_classes > 0 and not labelled:
-            raise ValueError(f"{name} is class-conditional: give --class_label or --labels")
-        if m.num_classes <= 0 and labelled:
-            raise ValueError(f"--class_label / --labels need class-conditional configs; {name} has none")
-        if args.class_label is not None and not 0 <= args.class_label < m.num_classes:
-            raise ValueError(f"--class_label {args.class_label} outside [0, {m.num_classes}) of {name}")
+        check_labels(args, m.num_classes, name)
     if config_late is not None and 999 not in grid:
         raise ValueError("a paired scan suggests a t_switch: the grid must include t = 999")
     if args.encode_images:
@@ -146,62 +94,22 @@ def validate(args, config, config_late=None):
             raise ValueError("--encode_images: the KL-VAE encoder gives 4-channel latents of a size that is a multiple of 8, at most 32")
     elif args.encode_mean:
         raise ValueError("--encode_mean goes with --encode_images")
-    path = Path(args.images)
-    if path.suffix.lower() != ".npy" and not path.is_dir():
-        raise ValueError(f"--images {args.images}: a folder of PNGs or a .npy file")
-    if path.is_dir() and latent and not args.encode_images:
-        raise ValueError("--images: a latent model takes .npy latents, or pixel images with --encode_images")
-    if path.is_dir() and not latent and mp.in_chans != 3:
-        raise ValueError(f"--images: PNGs need an in_chans = 3 config, this one has in_chans = {mp.in_chans}")
+    check_images_path(args.images, mp.in_chans, latent, args.encode_images)
     return grid
-
-
-def load_images(args, mp):
-    """--images -> float32 [N, C, S, S] in [-1, 1] (PNGs) or as stored (.npy); the size must be the model's (8 x under --encode_images)"""
-    path = Path(args.images)
-    if path.is_dir():
-        from .evaluation import read_samples
-        x = 2.0 * read_samples(path).numpy().astype(np.float32) - 1.0
-    else:
-        x = np.asarray(np.load(path), np.float32)
-    chans, size = (3, 8 * mp.img_size) if args.encode_images else (mp.in_chans, mp.img_size)
-    if x.ndim != 4 or x.shape[0] < 1 or x.shape[1:] != (chans, size, size):
-        raise ValueError(f"--images: shape {list(x.shape)} does not match [N, {chans}, {size}, {size}] (images are not resized)")
-    if not np.isfinite(x).all():
-        raise ValueError("--images: non-finite values")
-    return np.ascontiguousarray(x)
-
-
-def load_labels(args, n, num_classes):
-    if args.class_label is not None:
-        return np.full(n, int(args.class_label), np.int64)
-    if args.labels is None:
-        return None
-    y = np.load(args.labels)
-    if y.shape != (n,) or not np.issubdtype(y.dtype, np.integer):
-        raise ValueError(f"--labels: need {n} integers, one per image")
-    if y.min() < 0 or y.max() >= num_classes:
-        raise ValueError(f"--labels outside [0, {num_classes})")
-    return y.astype(np.int64)
 
 
 def scan(models, x0, y, rows, seed, repeats, batch_size, use_graph=True):
     """The errors of every model of `models` (engine Models) on x0 [N, C, S, S] (numpy): [len(models), repeats, len(grid), N] float32.  The
     images run in batches of batch_size; image i under seed + i whatever its batch; repeat r draws with Philox counters r n + k.  Every
     model sees the same (x0, z, t)."""
-    import torch
     from .engine import scan_error_loop
     n, N = len(rows["t"]), len(x0)
     out = np.zeros((len(models), repeats, n, N), np.float32)
     ctx = models[0].ctx
-    for i0 in range(0, N, batch_size):
-        i1 = min(i0 + batch_size, N)
-        xb = torch.from_numpy(x0[i0:i1]).cuda().contiguous()
-        yb = None if y is None else torch.from_numpy(y[i0:i1]).cuda()
-        with ctx.image_seeds([int(seed) + i for i in range(i0, i1)]):
-            for r in range(repeats):
-                for j, m in enumerate(models):
-                    out[j, r, :, i0:i1] = scan_error_loop(ctx, m, xb, rows, y=yb, counter_base=r * n, use_graph=use_graph).cpu().numpy()
+    for xb, yb, at in batches(ctx, x0, y, seed, batch_size):
+        for r in range(repeats):
+            for j, m in enumerate(models):
+                out[j, r, :, at] = scan_error_loop(ctx, m, xb, rows, y=yb, counter_base=r * n, use_graph=use_graph).cpu().numpy()
     return out
 
 
@@ -229,7 +137,7 @@ def main(argv=None):
     config_late = load_config(args.config_path_late) if args.config_path_late else None
     grid = validate(args, config, config_late)
     mp = ModelParams.from_dict(config)
-    x0 = load_images(args, mp)
+    x0 = load_images(args.images, *((3, 8 * mp.img_size) if args.encode_images else (mp.in_chans, mp.img_size)))
     y = load_labels(args, len(x0), mp.num_classes)
     out = Path(args.output_folder)
     out.mkdir(parents=True, exist_ok=True)

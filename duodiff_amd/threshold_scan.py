@@ -21,7 +21,8 @@ from pathlib import Path
 
 import numpy as np
 
-from .switch_scan import gap_statistics, load_images, load_labels, scan_timesteps
+from .scan_common import (add_scan_options, batches, check_images_path, check_label_options, check_labels, check_numbers, gap_statistics,
+                          load_images, load_labels, scan_timesteps)
 
 PARAMETRIZATIONS = ("predict_noise", "predict_original")       # the two the reference's trainer allows for the early-exit model
 F32 = np.float32
@@ -53,7 +54,7 @@ def simulate_exits(pred, threshold):
 
 def threshold_statistics(mse, idx):
     """What the exits idx [n, N] (simulate_exits) cost on mse [n, depth + 1, N]: the realised error mse[k, idx[k, i], i] against the
-    backbone's mse[k, depth, i], paired per image.  Returns (gap [n], sem [n], blocks): gap and sem as switch_scan.gap_statistics,
+    backbone's mse[k, depth, i], paired per image.  Returns (gap [n], sem [n], blocks): gap and sem as scan_common.gap_statistics,
     blocks = mean(idx) / depth -- exit l reads the input of block l, so it costs l blocks, the backbone depth.  With a leading repeats
     axis on both (mse [R, n, depth + 1, N], idx [R, n, N]: the rule replayed per repeat, as the sampler decides on one draw) the realised
     and the backbone's error are averaged per image over the repeats first.  Pure numpy."""
@@ -118,25 +119,15 @@ def candidate_thresholds(pred, thresholds=None, num_thresholds=None):
 
 def get_args(argv=None):
     p = ArgumentParser(description=__doc__.split("\n\n")[0])
-    p.add_argument("--seed", type=int, default=0, help="image i is noised under seed --seed + i")
-    p.add_argument("--config_path", type=str, required=True, help="Path to yaml config file (with model_params.classifier_type)")
-    p.add_argument("--checkpoint_path", type=str, required=True, help="Path to checkpoint of the early-exit model")
-    p.add_argument("--parametrization", type=str, required=True, help=f"one of {PARAMETRIZATIONS}")
-    p.add_argument("--images", type=str, required=True, help="a folder of PNGs of the model's size, or a .npy [N, C, S, S] in the model's space")
-    p.add_argument("--class_label", type=int, default=None, help="every image gets this class label")
-    p.add_argument("--labels", type=str, default=None, help=".npy of one integer label per image")
-    p.add_argument("--timesteps", type=int, nargs="+", default=None, metavar="T")
-    p.add_argument("--stride", type=int, default=None, metavar="N", help="the grid 999, 999 - N, ...")
-    p.add_argument("--thresholds", type=float, nargs="+", default=None, metavar="T", help="the candidate thresholds")
-    p.add_argument("--num_thresholds", type=int, default=None, metavar="N",
-                   help="candidates = the distinct N quantiles of the recorded predictions (default 32 where --thresholds is not given)")
-    p.add_argument("--repeats", type=int, default=1, metavar="R", help="R scans with fresh noise (Philox counters r * len(grid) + k), averaged per image")
-    p.add_argument("--tolerance", type=float, default=0.02, help="largest acceptable relative gap of the realised error over the backbone's")
-    p.add_argument("--sems", type=float, default=2.0, help="standard errors of the gap added before it is compared with --tolerance")
-    p.add_argument("--batch_size", type=int, default=128)
-    p.add_argument("--output_folder", type=str, required=True)
-    p.add_argument("--precision", choices=["bf16", "fp32"], default="bf16")
-    p.add_argument("--no_graph", action="store_true", help="launch kernels eagerly instead of hipGraph replay")
+    def own(p, after):
+        if after == "checkpoint_path":
+            p.add_argument("--parametrization", type=str, required=True, help=f"one of {PARAMETRIZATIONS}")
+        if after == "stride":
+            p.add_argument("--thresholds", type=float, nargs="+", default=None, metavar="T", help="the candidate thresholds")
+            p.add_argument("--num_thresholds", type=int, default=None, metavar="N",
+                           help="candidates = the distinct N quantiles of the recorded predictions (default 32 where --thresholds is not given)")
+    add_scan_options(p, "Path to yaml config file (with model_params.classifier_type)", "Path to checkpoint of the early-exit model",
+                     "largest acceptable relative gap of the realised error over the backbone's", own)
     return p.parse_args(argv)
 
 
@@ -147,24 +138,13 @@ def validate(args, config):
     if args.parametrization not in PARAMETRIZATIONS:
         raise ValueError(f"--parametrization must be one of {PARAMETRIZATIONS} (the early-exit trainer allows no other), not {args.parametrization!r}")
     grid = scan_timesteps(args.timesteps, args.stride)
-    args.encode_images = False                  # (load_images is switch_scan's: no latent models here)
     if args.thresholds is not None and args.num_thresholds is not None:
         raise ValueError("--thresholds and --num_thresholds are exclusive")
     if args.thresholds is None and args.num_thresholds is None:
         args.num_thresholds = 32
     candidate_thresholds(np.zeros(1), args.thresholds, args.num_thresholds)        # (the list's own checks)
-    if args.seed < 0:
-        raise ValueError("--seed must not be negative: image i is noised under seed --seed + i")
-    if args.repeats < 1:
-        raise ValueError(f"--repeats {args.repeats} must be at least 1")
-    if args.batch_size < 1:
-        raise ValueError(f"--batch_size {args.batch_size} must be at least 1")
-    if not (math.isfinite(args.tolerance) and args.tolerance >= 0):
-        raise ValueError(f"--tolerance {args.tolerance} must be finite and not negative")
-    if not (math.isfinite(args.sems) and args.sems >= 0):
-        raise ValueError(f"--sems {args.sems} must be finite and not negative")
-    if args.class_label is not None and args.labels is not None:
-        raise ValueError("--class_label and --labels are exclusive")
+    check_numbers(args)
+    check_label_options(args)
     params = dict(config["model_params"])
     if "classifier_type" not in params:
         raise ValueError("--config_path has no model_params.classifier_type: not an early-exit model (switch_scan scans plain models)")
@@ -172,39 +152,23 @@ def validate(args, config):
     mp = ModelParams.from_dict({**config, "model_params": params})
     if "autoencoder" in config:
         raise ValueError("latent early-exit models are not supported by this tool")
-    labelled = args.class_label is not None or args.labels is not None
-    if mp.num_classes > 0 and not labelled:
-        raise ValueError("--config_path is class-conditional: give --class_label or --labels")
-    if mp.num_classes <= 0 and labelled:
-        raise ValueError("--class_label / --labels need a class-conditional config")
-    if args.class_label is not None and not 0 <= args.class_label < mp.num_classes:
-        raise ValueError(f"--class_label {args.class_label} outside [0, {mp.num_classes})")
-    path = Path(args.images)
-    if path.suffix.lower() != ".npy" and not path.is_dir():
-        raise ValueError(f"--images {args.images}: a folder of PNGs or a .npy file")
-    if path.is_dir() and mp.in_chans != 3:
-        raise ValueError(f"--images: PNGs need an in_chans = 3 config, this one has in_chans = {mp.in_chans}")
+    check_labels(args, mp.num_classes)
+    check_images_path(args.images, mp.in_chans)
     return grid
 
 
 def scan(model, x0, y, rows, seed, repeats, batch_size, use_graph=True):
     """(mse [repeats, n, depth + 1, N], target (the same), predicted [repeats, n, depth, N]) float32 of the engine Model on x0
     [N, C, S, S] (numpy), in batches of batch_size; image i under seed + i whatever its batch; repeat r draws with Philox counters r n + k."""
-    import torch
     from .engine import scan_exits_loop
     n, N, depth = len(rows["t"]), len(x0), model.mp.depth
     mse, target = (np.zeros((repeats, n, depth + 1, N), F32) for _ in range(2))
     pred = np.zeros((repeats, n, depth, N), F32)
-    ctx = model.ctx
-    for i0 in range(0, N, batch_size):
-        i1 = min(i0 + batch_size, N)
-        xb = torch.from_numpy(x0[i0:i1]).cuda().contiguous()
-        yb = None if y is None else torch.from_numpy(y[i0:i1]).cuda()
-        with ctx.image_seeds([int(seed) + i for i in range(i0, i1)]):
-            for r in range(repeats):
-                out = scan_exits_loop(ctx, model, xb, rows, y=yb, counter_base=r * n, use_graph=use_graph)
-                for dst, src in zip((mse, target, pred), out):
-                    dst[r, :, :, i0:i1] = src.cpu().numpy()
+    for xb, yb, at in batches(model.ctx, x0, y, seed, batch_size):
+        for r in range(repeats):
+            out = scan_exits_loop(model.ctx, model, xb, rows, y=yb, counter_base=r * n, use_graph=use_graph)
+            for dst, src in zip((mse, target, pred), out):
+                dst[r, :, :, at] = src.cpu().numpy()
     return mse, target, pred
 
 
@@ -247,7 +211,7 @@ def main(argv=None):
     params = dict(config["model_params"])
     classifier_type = params.pop("classifier_type")
     mp = ModelParams.from_dict(config)
-    x0 = load_images(args, mp)
+    x0 = load_images(args.images, mp.in_chans, mp.img_size)
     y = load_labels(args, len(x0), mp.num_classes)
     out = Path(args.output_folder)
     out.mkdir(parents=True, exist_ok=True)

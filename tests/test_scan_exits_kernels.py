@@ -1,7 +1,7 @@
 """scan_exits_error_kernel (csrc/scan.hip) alone, through dd_dev_scan_exits_error (GPU).
 
 The old kernel is the reference for order and arithmetic: mse[l] must be bit-equal to dd_dev_scan_error on plane l.  Both sums against
-float64 of the same fp32 operands (mse under test_scan_kernels.error_ref's bound, tgtu under scan_exits_support.tgtu_ref's); scan_tanh_abs
+float64 of the same fp32 operands (mse under scan_support.error_ref's bound, tgtu under scan_support.tgtu_ref's); scan_tanh_abs
 on the device against its numpy mirror, bit for bit; one element of one plane moved by 1; wrong references the gate must refuse; the copy
 of the probes' predictions, the canaries, the fences; the step state's hand-off to row `next`; seeded images; the launcher's refusals."""
 import ctypes as C
@@ -13,15 +13,14 @@ import kernel_support as ks
 from duodiff_amd import _lib
 from duodiff_amd.threshold_scan import tanh_abs_f32
 from kernel_support import F32, P, untouched
-from scan_exits_support import E_TANH, exits_args, exits_error, tgtu_ref, written_mask
-from test_scan_kernels import KA, KB, ROWS, SEED, _seeds, draw, error, error_ref
+from scan_support import E_TANH, KA, KB, ROWS, SEED, _seeds, draw, error, error_ref, exits_args, exits_error, tgtu_ref, written_mask
 
 pytestmark = pytest.mark.gpu
 
 
-# (B, C, S, exits): a mostly idle workgroup and one exit; four exits; two exits of one channel; every thread looping and the largest
-# shipped depth + 1
-SHAPES = [(1, 3, 6, 1), (3, 4, 8, 4), (5, 1, 16, 2), (2, 3, 64, 22)]
+# (B, C, S, exits): a mostly idle workgroup and one exit; four exits; two exits of one channel; two channels and a second pass that 33
+# threads take; every thread looping and the largest shipped depth + 1
+SHAPES = [(1, 3, 6, 1), (3, 4, 8, 4), (5, 1, 16, 2), (2, 2, 17, 3), (2, 3, 64, 22)]
 
 
 def _geometry(B):

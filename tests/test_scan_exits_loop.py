@@ -18,12 +18,10 @@ from duodiff_amd.config import ModelParams
 from duodiff_amd.weights import synthetic_ee_state_dict
 from kernel_support import F32
 from loop_support import side_stream, uvit
-from scan_exits_support import exits_error
+from scan_support import _images, diffuse, exits_error
+from scan_support import _scan as _scan_loop
 from test_autoguidance import _flags, _x0
 from test_early_exit import CASES, _engine
-from test_scan_kernels import diffuse
-from test_scan_loop import _images
-from test_scan_loop import _scan as _scan_plain
 
 pytestmark = pytest.mark.gpu
 
@@ -34,13 +32,14 @@ CELEBA_EE = dict(img_size=64, patch_size=4, in_chans=3, embed_dim=512, depth=13,
                  num_classes=-1, normalize_timesteps=True)
 
 
-def _scan(em, x0, rows, y=None, stream=None, **kw):
+def _scan(*args, **kw):
     from duodiff_amd.engine import scan_exits_loop
-    stream = side_stream() if stream is None else stream
-    with torch.cuda.stream(stream):
-        out = scan_exits_loop(em.ctx, em, x0, rows, y=y, stream=stream, **kw)
-    stream.synchronize()
-    return tuple(o.cpu().numpy() for o in out)
+    return _scan_loop(scan_exits_loop, *args, **kw)
+
+
+def _scan_plain(*args, **kw):
+    from duodiff_amd.engine import scan_error_loop
+    return _scan_loop(scan_error_loop, *args, **kw)
 
 
 def _same(a, b):
@@ -237,7 +236,7 @@ def test_against_the_oracle_fp32(tag):
     output is within delta = 1e-4 of the oracle's elementwise (the forward bound the suite already uses), so mse is within 2 delta sqrt(want)
     + delta^2 (Cauchy-Schwarz) and the mean of the 1-Lipschitz tanh|.| within delta; pred within the 1e-5 / 2e-5 the suite uses for cls."""
     import oracle
-    from test_scan_kernels import draw
+    from scan_support import draw
     cfg, ctype = BY_TAG[tag]
     B = 3
     mp = ModelParams.from_dict(cfg)

@@ -19,73 +19,18 @@ import pytest
 
 import kernel_support as ks
 from duodiff_amd import _lib
-from kernel_support import F32, U24, P, untouched
+from kernel_support import F32, P, untouched
+from scan_support import KA, KB, ROWS, SEED, _args, _seeds, diffuse, draw, error, error_ref, z_ref
 from test_final_step import PHILOX_BOUND
 
 pytestmark = pytest.mark.gpu
 
-PHILOX_SCAN = 0x7363616E
-SHAPES = [(1, 3, 6), (3, 4, 8), (5, 1, 16), (2, 3, 64)]       # (B, C, S): most of a workgroup idle .. every thread loops
-# target rows (tz, t0, tx) at (ka, kb) of a mid timestep: predict_noise, predict_original, predict_previous (values of t = 500)
-KA, KB = F32(0.27892652), F32(0.96031439)
-ROWS = {"predict_noise": (1.0, 0.0, 0.0), "predict_original": (0.0, 1.0, 0.0), "predict_previous": (0.0, 0.0080282, 0.9895465)}
-SEED = (7 << 32) | 0x9ABCDEF1
+SHAPES = [(1, 3, 6), (3, 4, 8), (5, 1, 16), (2, 2, 17), (2, 3, 64)]       # (B, C, S): most of a workgroup idle .. every thread loops
 
 
 def _geometry(B):
     """every case: the launch starts at image b0 > 0 of a whole batch B_all > B"""
     return dict(b0=2, B_all=B + 5)
-
-
-def _seeds(n):
-    return (np.arange(n, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(12345)).astype(np.uint64)
-
-
-def _args(B, Cn, S, b0, B_all, k, ka, kb, row=(1.0, 0.0, 0.0), ctr=0, t_model=500.0, next_t_model=250.0, seed=SEED, advance=0):
-    a = _lib.dd_dev_scan_args()
-    a.B, a.C, a.S, a.b0, a.B_all, a.k = B, Cn, S, b0, B_all, k
-    a.t_model, a.ka, a.kb, a.tz, a.t0, a.tx = t_model, ka, kb, *row
-    a.ctr, a.next_t_model, a.seed, a.advance = ctr, next_t_model, seed, advance
-    a.t_out = a.t_final_out = -12345
-    a.t_model_out = -1.0
-    return a
-
-
-def diffuse(x0, b0, B_all, k=3, ka=KA, kb=KB, ctr=0, seeds=None, seed=SEED, expect=_lib.DD_OK):
-    """dd_dev_scan_diffuse -> (x_t [B, C, S, S], the whole output buffer, the args read back)"""
-    B, Cn, S, _ = x0.shape
-    n = x0.size
-    a = _args(B, Cn, S, b0, B_all, k, ka, kb, ctr=ctr, seed=seed)
-    out = np.zeros(n + 16, F32)
-    c = ks.ctx()
-    rc = c.lib.dd_dev_scan_diffuse(c.handle, C.byref(a), P(np.ascontiguousarray(x0, F32)), P(seeds), 0 if seeds is None else len(seeds), P(out), None)
-    assert rc == expect, (rc, c.lib.dd_last_error(c.handle))
-    return out[8:8 + n].reshape(x0.shape), out, a
-
-
-def error(x0, m, b0, B_all, row, k=3, ka=KA, kb=KB, ctr=0, seeds=None, seed=SEED, advance=0, expect=_lib.DD_OK):
-    """dd_dev_scan_error -> (err [B], the whole err buffer, the args read back)"""
-    B, Cn, S, _ = x0.shape
-    a = _args(B, Cn, S, b0, B_all, k, ka, kb, row, ctr=ctr, seed=seed, advance=advance)
-    out = np.zeros((k + 1) * B_all + 8, F32)
-    c = ks.ctx()
-    rc = c.lib.dd_dev_scan_error(c.handle, C.byref(a), P(np.ascontiguousarray(x0, F32)), P(np.ascontiguousarray(m, F32)), P(seeds),
-                                 0 if seeds is None else len(seeds), P(out), None)
-    assert rc == expect, (rc, c.lib.dd_last_error(c.handle))
-    return out[k * B_all + b0:k * B_all + b0 + B].copy(), out, a
-
-
-def draw(B, Cn, S, b0, B_all, ctr=0, seeds=None, seed=SEED):
-    """the kernel's z: (ka, kb) = (0, 1) on x0 = 0 returns 0 * 0 + 1 * z"""
-    return diffuse(np.zeros((B, Cn, S, S), F32), b0, B_all, ka=0.0, kb=1.0, ctr=ctr, seeds=seeds, seed=seed)[0]
-
-
-def z_ref(B, Cn, S, b0, ctr, seeds, seed):
-    """the host reference of the draw: draw_site's (key, id) -- plain: the call's seed and batch-wide pixel ids from b0; seeded: the image's
-    own seed and image-local ids"""
-    if seeds is None:
-        return ks.final_philox_ref(seed, B, Cn, S, b0, ctr, PHILOX_SCAN)[0]
-    return np.concatenate([ks.final_philox_ref(int(seeds[b0 + b]), 1, Cn, S, 0, ctr, PHILOX_SCAN)[0] for b in range(B)])
 
 
 def _inputs(B, Cn, S, seed):
@@ -161,21 +106,6 @@ def test_diffuse_general_rows_bit_equal_and_canaries(shape, seeded):
 
 
 # ---------------------------------------------------------------------------------------------------------------- error
-def error_ref(x0, m, z, ka, kb, row):
-    """(err64 [B], bound [B], d [B, C, S, S]) from the fp32 operands: x_t in fp32 as the kernel forms it (bit-equal: the diffuse test), then float64"""
-    B, Cn, S, _ = x0.shape
-    xt = (F32(ka) * x0 + F32(kb) * z).astype(np.float64)
-    tz, t0, tx = (float(F32(v)) for v in row)
-    z64, x64 = z.astype(np.float64), x0.astype(np.float64)
-    tgt = tz * z64 + t0 * x64 + tx * xt
-    dt = 3 * U24 * (np.abs(tz * z64) + np.abs(t0 * x64) + np.abs(tx * xt))
-    d = m.astype(np.float64) - tgt
-    n = Cn * S * S
-    depth = Cn * -(-S * S // 256) + 6 + 3                    # the summation depth scan_error_kernel states
-    bound = ((depth + 4) * U24 * (d * d).sum((1, 2, 3)) + (2 * np.abs(d) * dt).sum((1, 2, 3))) / n
-    return (d * d).sum((1, 2, 3)) / n, bound, d
-
-
 @pytest.mark.parametrize("seeded", [False, True], ids=["plain", "seeded"])
 @pytest.mark.parametrize("par", sorted(ROWS))
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "B%d-C%d-S%d" % s)

@@ -17,9 +17,10 @@ from duodiff_amd.config import ModelParams
 from duodiff_amd.weights import synthetic_state_dict
 from kernel_support import F32
 from loop_support import eps_rms_bound, side_stream, uvit
+from scan_support import _images, diffuse, draw, error
+from scan_support import _scan as _scan_loop
 from test_autoguidance import _flags, _x0
 from test_pag import QA512, TINY_COND
-from test_scan_kernels import diffuse, draw, error
 
 pytestmark = pytest.mark.gpu
 
@@ -28,20 +29,9 @@ CASES = {"tiny": (TINY, 5), "tiny_classes": (TINY_COND, 5), "qa512": (QA512, 2)}
 PARS = ("predict_noise", "predict_original", "predict_previous")
 
 
-def _images(B, mp, seed):
-    g = torch.Generator().manual_seed(seed)
-    x0 = (torch.rand(B, mp.in_chans, mp.img_size, mp.img_size, generator=g) * 2 - 1).cuda().contiguous()
-    y = torch.randint(0, mp.num_classes, (B,), generator=g).cuda() if mp.num_classes > 0 else None
-    return x0, y
-
-
-def _scan(em, x0, rows, y=None, stream=None, **kw):
+def _scan(*args, **kw):
     from duodiff_amd.engine import scan_error_loop
-    stream = side_stream() if stream is None else stream
-    with torch.cuda.stream(stream):
-        err = scan_error_loop(em.ctx, em, x0, rows, y=y, stream=stream, **kw)
-    stream.synchronize()
-    return err.cpu().numpy()
+    return _scan_loop(scan_error_loop, *args, **kw)
 
 
 def _manual(em, x0, rows, y, seed, counter_base=0, seeds=None):

@@ -11,7 +11,7 @@ import pytest
 
 from conftest import REPO
 from duodiff_amd import _lib as L
-from duodiff_amd import step_plan, switch_scan
+from duodiff_amd import scan_common, step_plan, switch_scan
 from duodiff_amd.config import load_config
 from duodiff_amd.engine import schedule_tables
 
@@ -80,7 +80,7 @@ def test_suggest_the_300_case():
     # every timestep acceptable, 0 on the grid: the first model everywhere
     first3, late3 = _errors([0.0] * 7)
     assert switch_scan.suggest_t_switch(TS, first3, late3, tolerance=0.02) == 1000
-    gap, sem = switch_scan.gap_statistics(first, late)
+    gap, sem = scan_common.gap_statistics(first, late)
     d = first - late
     assert np.allclose(gap, d.mean(1) / late.mean(1), rtol=1e-14) and np.allclose(sem, d.std(1, ddof=1) / 8.0 / late.mean(1), rtol=1e-14)
 
@@ -91,7 +91,7 @@ def test_suggest_a_noisy_gap_only_the_sems_term_rejects():
     first, late = _errors(gaps, n=64, seed=3)
     noise = np.random.default_rng(4).standard_normal(64)
     first[2] = late[2] + 0.01 * late[2].mean() + 0.5 * (noise - noise.mean())
-    gap, sem = switch_scan.gap_statistics(first, late)
+    gap, sem = scan_common.gap_statistics(first, late)
     assert gap[2] <= 0.02 < gap[2] + 2 * sem[2]
     assert switch_scan.suggest_t_switch(TS, first, late, tolerance=0.02, sems=2.0) == 100
     assert switch_scan.suggest_t_switch(TS, first, late, tolerance=0.02, sems=0.0) == 300
@@ -111,13 +111,13 @@ def test_suggest_none_and_a_grid_without_999():
 
 
 def test_scan_timesteps():
-    assert switch_scan.scan_timesteps(stride=250) == [999, 749, 499, 249]
-    assert switch_scan.scan_timesteps(stride=333) == [999, 666, 333, 0]
-    assert switch_scan.scan_timesteps(stride=5000) == [999]
-    assert switch_scan.scan_timesteps(timesteps=[5, 999, 0]) == [5, 999, 0]
+    assert scan_common.scan_timesteps(stride=250) == [999, 749, 499, 249]
+    assert scan_common.scan_timesteps(stride=333) == [999, 666, 333, 0]
+    assert scan_common.scan_timesteps(stride=5000) == [999]
+    assert scan_common.scan_timesteps(timesteps=[5, 999, 0]) == [5, 999, 0]
     for kw in (dict(), dict(timesteps=[1], stride=2), dict(stride=0), dict(timesteps=[1000]), dict(timesteps=[-1]), dict(timesteps=[3, 3])):
         with pytest.raises(ValueError):
-            switch_scan.scan_timesteps(**kw)
+            scan_common.scan_timesteps(**kw)
 
 
 # ---- the command line ------------------------------------------------------------------------------------------------------------
@@ -184,30 +184,30 @@ def test_images_and_labels_must_fit_the_model(tmp_path):
         np.save(tmp_path / "x.npy", np.zeros(shape, np.float32))
         args = switch_scan.get_args(_argv("uvit_celeba.yaml", tmp_path))
         if ok:
-            assert switch_scan.load_images(args, mp).shape == shape
+            assert scan_common.load_images(args.images, mp.in_chans, mp.img_size).shape == shape
         else:
             with pytest.raises(ValueError, match="resized"):
-                switch_scan.load_images(args, mp)
+                scan_common.load_images(args.images, mp.in_chans, mp.img_size)
     np.save(tmp_path / "x.npy", np.full((1, 3, 64, 64), np.nan, np.float32))
     with pytest.raises(ValueError, match="finite"):
-        switch_scan.load_images(switch_scan.get_args(_argv("uvit_celeba.yaml", tmp_path)), mp)
+        scan_common.load_images(switch_scan.get_args(_argv("uvit_celeba.yaml", tmp_path)).images, mp.in_chans, mp.img_size)
     # PNGs: through evaluation.read_samples, then 2 v - 1
     from PIL import Image
     (tmp_path / "pngs").mkdir()
     px = np.random.default_rng(1).integers(0, 256, (64, 64, 3), dtype=np.uint8)
     Image.fromarray(px).save(tmp_path / "pngs" / "a.png")
-    got = switch_scan.load_images(switch_scan.get_args(_argv("uvit_celeba.yaml", tmp_path, images=tmp_path / "pngs")), mp)
+    got = scan_common.load_images(switch_scan.get_args(_argv("uvit_celeba.yaml", tmp_path, images=tmp_path / "pngs")).images, mp.in_chans, mp.img_size)
     assert got.shape == (1, 3, 64, 64) and np.array_equal(got[0], 2.0 * (px.transpose(2, 0, 1).astype(np.float32) / 255.0) - 1.0)
     # labels
     args = switch_scan.get_args(_argv("uvit_imagenet64.yaml", tmp_path, "--class_label", "7"))
-    assert switch_scan.load_labels(args, 3, 1000).tolist() == [7, 7, 7]
+    assert scan_common.load_labels(args, 3, 1000).tolist() == [7, 7, 7]
     np.save(tmp_path / "y.npy", np.array([1, 2, 999]))
     args = switch_scan.get_args(_argv("uvit_imagenet64.yaml", tmp_path, "--labels", str(tmp_path / "y.npy")))
-    assert switch_scan.load_labels(args, 3, 1000).dtype == np.int64
+    assert scan_common.load_labels(args, 3, 1000).dtype == np.int64
     for n, classes in ((4, 1000), (3, 999)):
         with pytest.raises(ValueError):
-            switch_scan.load_labels(args, n, classes)
-    assert switch_scan.load_labels(switch_scan.get_args(_argv("uvit_celeba.yaml", tmp_path)), 3, -1) is None
+            scan_common.load_labels(args, n, classes)
+    assert scan_common.load_labels(switch_scan.get_args(_argv("uvit_celeba.yaml", tmp_path)), 3, -1) is None
 
 
 def test_main_rejects_before_it_builds_a_model(tmp_path):

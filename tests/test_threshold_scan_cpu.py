@@ -7,7 +7,7 @@ import pytest
 
 from duodiff_amd import threshold_scan as ts
 from oracle.early_exit_oracle import early_exit_select
-from scan_exits_support import E_TANH, TANH_BREAKPOINTS
+from scan_support import E_TANH, TANH_BREAKPOINTS
 
 F32 = np.float32
 

@@ -5,7 +5,7 @@
 Sweeps the bit patterns of all fp32 values from 0 to the clamp in chunks (--stride 1: every one of them), then the tail behind the
 clamp (every value there gives the clamp's value: the error is 1 - tanh at the clamp's side and falls from there), inf, and the negative
 mirror of a sample.  Prints one JSON line: e_tanh, where it is taken, the largest result and the count.  The result goes into
-scan_tanh_abs's comment (csrc/step_update.h), DESIGN section 7k and tests/scan_exits_support.py E_TANH."""
+scan_tanh_abs's comment (csrc/step_update.h), DESIGN section 7k and tests/scan_support.py E_TANH."""
 import argparse
 import json
 import sys

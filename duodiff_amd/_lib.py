@@ -70,6 +70,11 @@ class dd_known_region(C.Structure):
     _fields_ = [("x0_dev", C.c_void_p), ("mask_dev", C.c_void_p), ("ka", C.POINTER(C.c_float)), ("kb", C.POINTER(C.c_float))]
 
 
+class dd_walk(C.Structure):
+    """a walk's per-row program beside the step table: jump[k] != 0: row k is a resampling jump; late[k] (or NULL): step row k runs the late model"""
+    _fields_ = [("jump", C.POINTER(C.c_int32)), ("late", C.POINTER(C.c_int32))]
+
+
 class dd_x0_threshold(C.Structure):
     """x0 thresholding of the multistep loop: static (clamp to +-range) or dynamic (the image's own quantile scale, at most s_max)"""
     _fields_ = [("mode", C.c_int32), ("quantile", C.c_float), ("range", C.c_float), ("s_max", C.c_float)]
@@ -187,6 +192,9 @@ SIGNATURES = {
                                           C.POINTER(dd_known_region), C.c_void_p]),
     "dd_sample_multistep_region": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_guidance),
                                              C.POINTER(dd_autoguidance), C.POINTER(dd_known_region), C.c_void_p]),
+    "dd_jump_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
+    "dd_sample_affine_walk": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.POINTER(dd_guidance), C.POINTER(dd_autoguidance),
+                                        C.POINTER(dd_known_region), C.POINTER(dd_walk), C.c_void_p]),
     "dd_threshold_step": (C.c_int, [C.c_void_p] * 5 + [C.POINTER(dd_x0_threshold)] + [C.c_float] * 6 +
                           [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dd_sample_multistep_threshold": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_guidance),

@@ -62,6 +62,7 @@ void dd_ctx_destroy(dd_ctx* c) {
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->ev_ee_fork) (void)hipEventDestroy(c->ev_ee_fork);
     if (c->ev_ee_join) (void)hipEventDestroy(c->ev_ee_join);
+    for (hipGraphExec_t g : c->jump_graph) if (g) (void)hipGraphExecDestroy(g);
     for (StepState* st : c->st) if (st) (void)hipFree(st);
     if (c->coef) (void)hipFree(c->coef);
     c->x_stage.release(); c->y_stage.release(); c->h_stage.release(); c->k_stage.release(); c->m_stage.release();
@@ -119,6 +120,14 @@ int dd_affine_step(dd_ctx* c, const float* x_dev, const float* m_dev, const floa
     if (!x_dev || !m_dev || !out_dev || n < 0) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
     if (n == 0) return DD_OK;
     DD_HIP(c, launch_affine_step(x_dev, m_dev, z_dev, out_dev, a, b, cc, (long long)n, (hipStream_t)stream));
+    return DD_OK;
+}
+
+int dd_jump_step(dd_ctx* c, const float* x_dev, const float* z_dev, float ja, float jc, float* out_dev, int64_t n, void* stream) {
+    if (!c) return DD_ERR_INVALID;
+    if (!x_dev || !out_dev || n < 0) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    if (n == 0) return DD_OK;
+    DD_HIP(c, launch_jump_step(x_dev, z_dev, out_dev, ja, jc, (long long)n, (hipStream_t)stream));
     return DD_OK;
 }
 

@@ -477,6 +477,14 @@ hipError_t launch_ee_select_step(float* x, const float* outs, const float* eps, 
 // out [B, C, S, S] = the x_T draw of step_update.h (PHILOX_START) under `seed` (seeds null) or the per-image seeds [B]; C in 1..4; a bad
 // argument is hipErrorInvalidValue with nothing launched
 hipError_t launch_noise_images(float* out, const unsigned long long* seeds, unsigned long long seed, int ctr, int B, int C, int S, hipStream_t s);
+// A resampling jump of a table-driven loop, in place on B images x [B, C, S, S] whose first is image b0 of the whole batch (seeds as
+// FinalArgs::seeds): x' = a x [+ c z3] from row st->t of atab (step_update.h jump), written to the twin image pair_B images on as well
+// (pair_B > 0: classifier-free guidance); a second, one-thread launch then hands row st->t + 1 its index and t_model.  C outside 1..4 or a
+// null pointer: hipErrorInvalidValue, nothing launched.
+hipError_t launch_jump(float* x, StepState* st, const AffineRow* atab, const unsigned long long* seeds, int B, int C, int S, int b0, int pair_B,
+                       int noise_mode, hipStream_t s);
+// out = ja x [+ jc z if z] on n elements: the unfused jump (x and out may alias)
+hipError_t launch_jump_step(const float* x, const float* z, float* out, float ja, float jc, long long n, hipStream_t s);
 hipError_t launch_ee_mean_combine(const float* s0, const float* s1, float* err, int depth, int t_lo, int t_hi, int B, hipStream_t s);
 hipError_t launch_set_state(StepState* st, int t, unsigned long long seed, hipStream_t s);
 hipError_t launch_set_state_table(StepState* st, const AffineRow* atab, unsigned long long seed, hipStream_t s);   // step index 0

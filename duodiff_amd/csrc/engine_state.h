@@ -50,6 +50,36 @@ struct RowTable {
         uploaded = nullptr;
     }
 };
+// What a captured step was captured for: a graph is replayed while its key matches (in front of dd_ctx, which holds the jump's graphs)
+struct GraphKey {
+    const void* x; const void* y; int B, noise, variance, num_cus;   // num_cus: the captured persistent grids are sized from it
+    const void* atab;                                                // dd_sample_affine's table (null: the DDPM update)
+    const void *aux0 = nullptr, *aux1 = nullptr;                     // dd_sample_early_exit: the two log tables
+    float thr = 0.f;                                                 //                        and the threshold
+    int b0 = 0;                                                      // first image of a half-batch chain within the whole batch
+    int gnull = -1;                                                  // classifier-free guidance: the null label (-1: unguided)
+    unsigned gscale = 0;                                             //   and the bits of the scale (+0 and -0 round differently)
+    const void* aguide = nullptr;                                    // autoguidance: the guide model of a two-model step (null: CFG / unguided; gscale: the scale's bits)
+    unsigned long long aserial = 0;                                  //   and its serial: an address can come back with another model behind it
+    const void *kx0 = nullptr, *kmask = nullptr, *ktab = nullptr;    // known region: the chain's staged x0 / mask and the rows (null: none)
+    int tmode = -1;                                                  // x0 thresholding: the mode (-1: none), the bits of quantile, range and s_max,
+    unsigned tq = 0, tr = 0, ts = 0;                                 //   and the model-output scratch the step goes through
+    const void* tscratch = nullptr;
+    int pag = 0;                                                     // perturbed-attention guidance: set (gscale: the scale's bits), and the
+    unsigned pfirst = 0, plate = 0;                                  //   masks of the loop's two models
+    const void* seeds = nullptr;                                     // per-image seeds: the context's staged copy (null: the plain noise)
+    int jchans = 0, jsize = 0;                                       // a jump's graph (dd_ctx::jump_graph: no model's): the image shape C, S
+    bool operator==(const GraphKey&) const = default;
+    void perturb(const dd_pag* p) {
+        if (p) { pag = 1; gscale = __builtin_bit_cast(unsigned, p->scale); pfirst = p->layers_first; plate = p->layers_late; }
+    }
+    void guide(const dd_guidance* g) {
+        if (g) { gnull = g->null_label; gscale = __builtin_bit_cast(unsigned, g->scale); }
+    }
+};
+
+// the captured step of each sampling loop: dd_model::graph[kind][chain]
+enum GraphKind { GRAPH_DDPM, GRAPH_AFFINE, GRAPH_EARLY_EXIT, GRAPH_MULTISTEP, GRAPH_SCAN, GRAPH_SCAN_EXITS, GRAPH_KINDS };
 }  // namespace dd
 #pragma GCC visibility pop
 
@@ -72,6 +102,8 @@ struct dd_ctx {
     dd::DevBuf<int64_t> y_stage;
     long long graph_captures = 0;
     int last_chains = 1;         // chains the last dd_sample call ran (dd_dev_last_sample_chains)
+    hipGraphExec_t jump_graph[2] = {nullptr, nullptr};   // dd_sample_affine_walk: the captured resampling jump of each chain (launch_jump: it runs no
+    dd::GraphKey jump_key[2]{};                          //   model, so it lives here), keyed like a step's graph
     dd::RowTable<dd::AffineRow> atab;    // dd_sample_affine: the step table
     dd::RowTable<dd::HistRow> htab;      // dd_sample_multistep: the history half of the rows beside atab,
     dd::DevBuf<float> h_stage;       //   and the history register the loop runs on ([B, C, S, S], staged like x)
@@ -113,35 +145,6 @@ struct BlockW {
 };
 
 struct HeadW { const float *ng, *nb, *wdec, *bdec, *wconv, *bconv; const float *wg = nullptr, *dc = nullptr; const float *wsplit = nullptr, *dcs = nullptr; };   // wg / dc: head_dec_kernel operands (norm folded into decoder_pred; dc = c [pd], row sums of wg [pd]) or null; wsplit / dcs: the same for the split-bf16 product (bf16 engine, embed_dim 256 / 512) or null
-
-struct GraphKey {
-    const void* x; const void* y; int B, noise, variance, num_cus;   // num_cus: the captured persistent grids are sized from it
-    const void* atab;                                                // dd_sample_affine's table (null: the DDPM update)
-    const void *aux0 = nullptr, *aux1 = nullptr;                     // dd_sample_early_exit: the two log tables
-    float thr = 0.f;                                                 //                        and the threshold
-    int b0 = 0;                                                      // first image of a half-batch chain within the whole batch
-    int gnull = -1;                                                  // classifier-free guidance: the null label (-1: unguided)
-    unsigned gscale = 0;                                             //   and the bits of the scale (+0 and -0 round differently)
-    const void* aguide = nullptr;                                    // autoguidance: the guide model of a two-model step (null: CFG / unguided; gscale: the scale's bits)
-    unsigned long long aserial = 0;                                  //   and its serial: an address can come back with another model behind it
-    const void *kx0 = nullptr, *kmask = nullptr, *ktab = nullptr;    // known region: the chain's staged x0 / mask and the rows (null: none)
-    int tmode = -1;                                                  // x0 thresholding: the mode (-1: none), the bits of quantile, range and s_max,
-    unsigned tq = 0, tr = 0, ts = 0;                                 //   and the model-output scratch the step goes through
-    const void* tscratch = nullptr;
-    int pag = 0;                                                     // perturbed-attention guidance: set (gscale: the scale's bits), and the
-    unsigned pfirst = 0, plate = 0;                                  //   masks of the loop's two models
-    const void* seeds = nullptr;                                     // per-image seeds: the context's staged copy (null: the plain noise)
-    bool operator==(const GraphKey&) const = default;
-    void perturb(const dd_pag* p) {
-        if (p) { pag = 1; gscale = __builtin_bit_cast(unsigned, p->scale); pfirst = p->layers_first; plate = p->layers_late; }
-    }
-    void guide(const dd_guidance* g) {
-        if (g) { gnull = g->null_label; gscale = __builtin_bit_cast(unsigned, g->scale); }
-    }
-};
-
-// the captured step of each sampling loop: dd_model::graph[kind][chain]
-enum GraphKind { GRAPH_DDPM, GRAPH_AFFINE, GRAPH_EARLY_EXIT, GRAPH_MULTISTEP, GRAPH_SCAN, GRAPH_SCAN_EXITS, GRAPH_KINDS };
 
 // The activation workspace of one chain: dd_sample runs a large batch as TWO independent half-batch chains on two streams (one
 // chain's HBM-bound kernel phases then run under the other's MFMA phases); the second chain has its own copy of every buffer.

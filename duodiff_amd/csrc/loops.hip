@@ -44,11 +44,10 @@ struct SideJoin {
     ~SideJoin() { if (armed && c->side) (void)hipStreamSynchronize(c->side); }
 };
 
-// the model's captured step of this kind for this chain and key: reused, or captured now from enqueue()
+// the captured graph in `exec`, captured under the key `have`: reused if that is `key`, else captured now from enqueue()
 template <typename F>
-int get_graph(dd_ctx* c, dd_model* m, GraphKind kind, int chain, const GraphKey& key, hipStream_t s, F&& enqueue) {
-    hipGraphExec_t& exec = m->graph[kind][chain];
-    if (exec && m->gkey[kind][chain] == key) return DD_OK;
+int capture_graph(dd_ctx* c, hipGraphExec_t& exec, GraphKey& have, const GraphKey& key, hipStream_t s, F&& enqueue) {
+    if (exec && have == key) return DD_OK;
     if (exec) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
     hipGraph_t g = nullptr;
     DD_HIP(c, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
@@ -59,9 +58,14 @@ int get_graph(dd_ctx* c, dd_model* m, GraphKind kind, int chain, const GraphKey&
     const hipError_t e3 = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
     if (e3 != hipSuccess) { exec = nullptr; return fail_hip(c, e3, "hipGraphInstantiate"); }
-    m->gkey[kind][chain] = key;
+    have = key;
     ++c->graph_captures;
     return DD_OK;
+}
+// the model's captured step of this kind for this chain and key
+template <typename F>
+int get_graph(dd_ctx* c, dd_model* m, GraphKind kind, int chain, const GraphKey& key, hipStream_t s, F&& enqueue) {
+    return capture_graph(c, m->graph[kind][chain], m->gkey[kind][chain], key, s, enqueue);
 }
 
 // One chain's share of a sampling loop's batch: the caller's images [b0, b0 + B), at x / y in the buffers the loop runs on
@@ -84,7 +88,13 @@ struct Loop {
     std::function<void(GraphKey&, const Slice&)> key;                                // the loop's own fields of a chain's graph key
     std::function<int(dd_model*, const Chain&, const Slice&, hipStream_t)> step;     // one step of one chain
     std::function<int(int chains, hipStream_t)> tail = nullptr;                      // behind the join of the chains
+    // A walk (dd_sample_affine_walk): what each of the `steps` rows runs, in place of switch_at's rule -- null: none, and the loop enqueues
+    // what it always has.  A jump row runs no model: with graphs it replays the context's captured jump of the chain (dd_ctx::jump_graph,
+    // keyed like a step's graph), eagerly it is jump() itself.  ev[1] is recorded in front of the first late step.
+    const int* program = nullptr;                                                    // [steps] of STEP_FIRST / STEP_LATE / STEP_JUMP
+    std::function<int(const Chain&, const Slice&, hipStream_t)> jump = nullptr;      // one jump of one chain
 };
+enum { STEP_FIRST = 0, STEP_LATE = 1, STEP_JUMP = 2 };
 
 // dd_sample, dd_sample_affine (both also guided) and dd_sample_early_exit: staging, the half-batch chains, graph capture and replay, timing
 int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
@@ -122,6 +132,12 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
         return sl;
     };
     auto chain = [&](dd_model* m, int k) { return Chain{&m->ws[k], c->st[k], cus, !chained}; };
+    bool uses[3] = {true, true, false};      // what the rows run: without a walk both models' graphs are captured up front, whoever runs
+    if (L.program) {
+        uses[STEP_FIRST] = uses[STEP_LATE] = false;
+        for (int k = 0; k < L.steps; ++k) uses[L.program[k]] = true;
+        if (L.late == L.first) uses[STEP_FIRST] = uses[STEP_LATE] = uses[STEP_FIRST] || uses[STEP_LATE];
+    }
     if (L.use_graph) {
         for (int k = 0; k < chains; ++k) {
             const Slice sl = slice(k);
@@ -132,8 +148,13 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
             key.kx0 = sl.mods.kn.x0; key.kmask = sl.mods.kn.mask; key.ktab = sl.mods.kn.ktab;
             key.seeds = L.mods.seeds;
             L.key(key, sl);
+            if (uses[STEP_JUMP]) {
+                GraphKey jkey = key;
+                jkey.jchans = L.first->cfg.in_chans; jkey.jsize = L.first->cfg.img_size;
+                if ((rc = capture_graph(c, c->jump_graph[k], c->jump_key[k], jkey, s, [&] { return L.jump(chain(L.first, k), sl, s); }))) return rc;
+            }
             for (dd_model* m : {L.first, L.late}) {
-                if (!m) continue;
+                if (!m || !uses[m == L.first ? STEP_FIRST : STEP_LATE]) continue;
                 if (k && (rc = ensure_chain_ws(c, m, s))) return rc;
                 GraphKey mkey = key;
                 if (ag) {   // the step of the guide model itself is the unguided loop's step, under the unguided loop's key
@@ -155,8 +176,25 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
     SideJoin side_join{c, chained};
     DD_HIP(c, hipEventRecord(c->ev[0], s));
     dd_model* cur = L.first;
+    bool split = false;                      // (a walk: ev[1] has been recorded)
     for (int k = 0; k < L.steps; ++k) {
-        if (k == L.switch_at) {
+        if (L.program) {
+            const int op = L.program[k];
+            if (op == STEP_JUMP) {
+                if (L.use_graph) {
+                    DD_HIP(c, hipGraphLaunch(c->jump_graph[0], s));
+                    if (chained) DD_HIP(c, hipGraphLaunch(c->jump_graph[1], c->side));
+                } else if ((rc = L.jump(chain(L.first, 0), slice(0), s))) {
+                    return rc;
+                }
+                continue;
+            }
+            cur = op == STEP_LATE ? L.late : L.first;
+            if (op == STEP_LATE && !split) {
+                DD_HIP(c, hipEventRecord(c->ev[1], s));
+                split = true;
+            }
+        } else if (k == L.switch_at) {
             cur = L.late;
             DD_HIP(c, hipEventRecord(c->ev[1], s));
         }
@@ -167,14 +205,14 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
             return rc;
         }
     }
-    if (L.switch_at == L.steps) DD_HIP(c, hipEventRecord(c->ev[1], s));
+    if (!L.program && L.switch_at == L.steps) DD_HIP(c, hipEventRecord(c->ev[1], s));
     if (chained) {
         DD_HIP(c, hipEventRecord(c->ev_join, c->side));
         DD_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0));
         side_join.armed = false;
     }
     if (L.tail && (rc = L.tail(chains, s))) return rc;
-    if (L.switch_at < 0) DD_HIP(c, hipEventRecord(c->ev[1], s));
+    if (L.program ? !split : L.switch_at < 0) DD_HIP(c, hipEventRecord(c->ev[1], s));
     DD_HIP(c, hipEventRecord(c->ev[2], s));
     if (paired) return unstage_guided(c, L.x_dev, x_run, L.B, B0, chw, s);
     if (x_run != L.x_dev) DD_HIP(c, hipMemcpyAsync(L.x_dev, x_run, (size_t)L.B * chw * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -359,13 +397,24 @@ int sample_ddpm(dd_ctx* c, const dd_sample_args* a, Mods mo, void* stream) {
 }
 
 // dd_sample_affine and its _guided, _autoguided and _region forms: one path
-int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, Mods mo, void* stream) {
-    int rc = check_loop(c, a, mo, nullptr, "dd_sample_affine generates noise on the device; for host noise drive dd_forward + dd_affine_step",
+// w (dd_sample_affine_walk; its own checks have passed): the rows' program -- a jump row runs launch_jump, a step row the model w->late names
+// (null: switch_after's rule)
+int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, Mods mo, void* stream, const dd_walk* w = nullptr) {
+    int rc = check_loop(c, a, mo, w ? "resampling jumps are not supported for early-exit models" : nullptr,
+                        w ? "dd_sample_affine_walk generates noise on the device; for host noise drive dd_forward, dd_affine_step, dd_known_blend and dd_jump_step"
+                          : "dd_sample_affine generates noise on the device; for host noise drive dd_forward + dd_affine_step",
                         [&] { return check_table(c, a); });
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int n = a->n_steps;
     const bool switching = a->late && a->switch_after >= 0 && a->switch_after < n;
+    std::vector<int> program;
+    if (w) {
+        if (a->first->cfg.in_chans > 4) return ctx_fail(c, DD_ERR_UNSUPPORTED, "a resampling jump draws one Philox block per pixel: at most 4 channels");
+        program.resize((size_t)n);
+        for (int k = 0; k < n; ++k)
+            program[k] = w->jump[k] ? STEP_JUMP : (w->late ? w->late[k] != 0 : switching && k >= a->switch_after) ? STEP_LATE : STEP_FIRST;
+    }
     if ((rc = stage_image_seeds(c, a->noise_mode, s, &mo.seeds))) return rc;
     if ((rc = upload_atab(c, a, s))) return rc;
     if ((rc = stage_table_known(c, mo, a->first, a->B, n, s))) return rc;
@@ -378,7 +427,38 @@ int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, Mods mo, void* stre
     L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
         return enqueue_step(c, m, ch, sl.x, sl.y, sl.B, ss, {.mods = sl.mods, .noise_mode = a->noise_mode, .advance = 1, .atab = atab, .b0 = sl.b0});
     };
+    if (w) {
+        if (w->late) L.late = a->late;       // (the rows name their model; null where no row runs it: checked)
+        L.switch_at = -1;
+        L.program = program.data();
+        L.jump = [&](const Chain& ch, const Slice& sl, hipStream_t ss) -> int {      // (guided: the chain's twins stand sl.B images on)
+            DD_HIP(c, launch_jump(sl.x, ch.st, atab, sl.mods.seeds, sl.B, a->first->cfg.in_chans, a->first->cfg.img_size, sl.b0, mo.g ? sl.B : 0,
+                                  a->noise_mode, ss));
+            return DD_OK;
+        };
+    }
     return run_loop(c, L, s);
+}
+
+// dd_sample_affine_walk: its own checks, in front of the loop's (the table's pointers and n_steps are checked there: unreadable ones are left
+// to it), then dd_sample_affine's path with the walk
+int sample_affine_walk(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr,
+                       const dd_walk* w, void* stream) {
+    if (!c) return DD_ERR_INVALID;
+    if (!w || !w->jump) return ctx_fail(c, DD_ERR_INVALID, "null dd_walk / null jump array");
+    if (!a) return DD_ERR_INVALID;
+    if (a->b && a->n_steps >= 1 && a->n_steps <= (1 << 20)) {
+        for (int k = 0; k < a->n_steps; ++k) {
+            if (w->jump[k]) {
+                if (a->b[k] != 0.f) return ctx_fail(c, DD_ERR_INVALID, "row " + std::to_string(k) + " is a jump with b != 0: a jump runs no model");
+            } else if (w->late) {
+                if (w->late[k] != 0 && w->late[k] != 1) return ctx_fail(c, DD_ERR_INVALID, "late[" + std::to_string(k) + "] is outside {0, 1}");
+                if (w->late[k] == 1 && !a->late) return ctx_fail(c, DD_ERR_INVALID, "late[" + std::to_string(k) + "] is 1 without a late model");
+            }
+        }
+    }
+    if (g && ag) return ctx_fail(c, DD_ERR_INVALID, "classifier-free guidance and autoguidance are exclusive");
+    return sample_affine(c, a, Mods{.g = g, .ag = ag, .kr = kr, .region = kr != nullptr}, stream, w);
 }
 
 // dd_sample_multistep and its forms: dd_sample_affine's loop with the history register.  h is staged like x: copied into the context's
@@ -621,6 +701,10 @@ int dd_sample_affine_autoguided(dd_ctx* c, const dd_affine_sample_args* a, const
 int dd_sample_affine_region(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr,
                             void* stream) {
     return sample_affine(c, a, in_region(g, ag, kr), stream);
+}
+int dd_sample_affine_walk(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr,
+                          const dd_walk* w, void* stream) {
+    return sample_affine_walk(c, a, g, ag, kr, w, stream);
 }
 int dd_sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, void* stream) { return sample_multistep(c, a, Mods{}, stream); }
 int dd_sample_multistep_guided(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, void* stream) {

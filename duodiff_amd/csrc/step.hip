@@ -3,6 +3,7 @@
 // All arithmetic here is fp32 in both precision modes.
 #include "dd_internal.h"
 #include "step_update.h"
+#include "vec_access.h"
 
 namespace dd {
 namespace {
@@ -236,22 +237,6 @@ __global__ void multistep_step_kernel(const float* x, const float* __restrict__ 
 // x and out may alias: a thread reads its own elements before it writes them, and no workgroup reads another image (the twin is only written).
 // W = 1: the same with scalar accesses (S * S no multiple of 4, or a pointer not 16-byte aligned).
 // ------------------------------------------------------------------------------------------
-template <int W>
-__device__ __forceinline__ void load_w(float (&d)[W], const float* p) {
-    if constexpr (W == 4) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(p);
-        d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
-    } else {
-        d[0] = *p;
-    }
-}
-template <int W>
-__device__ __forceinline__ void store_w(float* p, const float (&d)[W]) {
-    if constexpr (W == 4) *reinterpret_cast<f32x4*>(p) = f32x4{d[0], d[1], d[2], d[3]};
-    else *p = d[0];
-}
-__device__ __forceinline__ float pick(const f32x4& v, int c) { return c == 0 ? v[0] : c == 1 ? v[1] : c == 2 ? v[2] : v[3]; }
-
 template <int W>
 __global__ void __launch_bounds__(1024) threshold_step_kernel(const ThresholdArgs a) {
 #pragma clang fp contract(off)

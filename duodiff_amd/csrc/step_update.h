@@ -15,6 +15,7 @@ namespace dd {
 // ------------------------------------------------------------------------------------------
 constexpr unsigned PHILOX_STEP = 0x5eedu, PHILOX_KNOWN = 0x6b6e6f77u, PHILOX_START = 0x78545f30u;
 constexpr unsigned PHILOX_SCAN = 0x7363616e;      // "scan": the z that noises a real image in the denoising-error scan (scan_target below)
+constexpr unsigned PHILOX_JUMP = 0x6a756d70;      // "jump": the z3 of a resampling jump (jump below); z, z2 and z3 of one counter are three independent draws
 
 // The draw site, defined once: the Philox key and pixel id of pixel p = y S + x (hw = S S pixels per image) of image bg of the WHOLE batch
 // (bg = the launch's first image b0 + the launch's image b: a half-batch chain draws what the undivided batch would).
@@ -162,6 +163,16 @@ struct KnownRule {
     __device__ __forceinline__ float apply(float xp, float x0, float m, float z2) const { return known(xp, x0, m, row.ka, row.kb, z2, philox); }
     __device__ __forceinline__ float value(float x0, float z2) const { return known_value(x0, row.ka, row.kb, z2, philox); }
 };
+
+// A resampling jump (RePaint's resampling, Restart sampling: dd_sample_affine_walk, dd_jump_step): x at the noise level of timestep s goes
+// back up to that of timestep u >= s by forward noising, with no model evaluation,
+//     x' = ja x [+ jc z3  if a z3 is there]        ja = sqrt(abar[u] / abar[s]), jc = sqrt(1 - abar[u] / abar[s])
+// each product rounded on its own.  Every pixel takes it, the known ones of a region too: they are at level s and land at level u.
+__device__ __forceinline__ float jump(float x, float z3, float ja, float jc, bool use_z3) {
+#pragma clang fp contract(off)
+    const float v = ja * x;
+    return use_z3 ? v + jc * z3 : v;
+}
 
 // The denoising-error scan (dd_scan_error; reference trainer.py:307-352 evaluated at one timestep): an image x0 is noised to row k's level
 // with a z of its own stream word, x_t = known_value(x0, ka, kb, z, true) = ka x0 + kb z, the model sees x_t, and its output m is compared with

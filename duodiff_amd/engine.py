@@ -153,6 +153,16 @@ class Context:
                                            B, Cc, S, _stream_ptr(stream)))
         return out
 
+    def jump_step(self, x, z, ja, jc, out=None, stream=None):
+        """The resampling jump on device tensors (dd_jump_step): out = ja*x [+ jc*z if z is not None], each product rounded on its own.
+        out may be x."""
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        if z is not None:
+            assert z.is_cuda and z.dtype == torch.float32 and z.is_contiguous() and z.numel() == x.numel()
+        out = torch.empty_like(x) if out is None else out
+        self.check(self.lib.dd_jump_step(self.handle, _ptr(x), _ptr(z), float(ja), float(jc), _ptr(out), x.numel(), _stream_ptr(stream)))
+        return out
+
     def _seeds_tensor(self, seeds, device=None):
         """a sequence of ints in [0, 2^64) -> the uint64 seeds on the device (an int64 tensor of the same bits)"""
         seeds = [int(s) for s in seeds]
@@ -577,6 +587,40 @@ def _sample_affine_loop(ctx, first, late, x, region, t, a, b, c, noise_flags, sw
     tab = _step_table(args, first, late, dict(t=t, a=a, b=b, c=c, noise=noise_flags), "tabc", ("noise",), switch_after,  # noqa: F841
                       counter_base)
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, _loop_call(ctx, args, "dd_sample_affine", guidance, region, x))
+
+
+def sample_affine_walk_loop(ctx: Context, first: Model, late, x, rows, *, region=None, guidance=None, switch_after=None, y=None, seed=0,
+                            counter_base=0, noise="philox", use_graph=True, stream=None):
+    """dd_sample_affine_walk: sample_affine_loop over a walk that may go back up (RePaint's resampling, Restart sampling), in place on x.
+    rows: a dict with t, a, b, c, noise, jump and optionally late (a walk plan's rows, step_plan.step_plan(..., resample_jump= ...), or any
+    slice of them).  Row k with jump[k] == 0 is sample_affine_loop's step, run by the late model where late[k] == 1 (no late row: from
+    row switch_after on); with jump[k] != 0 it runs no model: x <- a[k] x + c[k] z3, z3 a Philox draw of its own stream under the row's
+    counter counter_base + k.  region: a KnownRegion with one (ka, kb) per row (a jump's is not read); guidance: (scale, null_label) or
+    Autoguidance(guide_model, scale)."""
+    if isinstance(guidance, Perturbed):
+        raise ValueError("perturbed-attention guidance does not combine with resampling jumps")
+    args = L.dd_affine_sample_args()
+    tab = _step_table(args, first, late, rows, "tabc", ("noise",), switch_after, counter_base)
+    n = args.n_steps
+    prog = [np.ascontiguousarray(rows[k], np.int32) if k in rows and rows[k] is not None else None for k in ("jump", "late")]
+    assert prog[0] is not None and all(v is None or v.shape == (n,) for v in prog)
+    walk = L.dd_walk(*(v.ctypes.data_as(C.POINTER(C.c_int32)) if v is not None else None for v in prog))
+    g = ag = kr = None
+    if isinstance(guidance, Autoguidance):
+        ag = C.byref(L.dd_autoguidance(guidance.guide.handle, float(guidance.scale)))
+    elif guidance is not None:
+        g = C.byref(guidance_struct(guidance))
+    if region is not None:
+        B, Cc, S, _ = x.shape
+        for v, shape in ((region.x0, (B, Cc, S, S)), (region.mask, (B, 1, S, S))):
+            assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and tuple(v.shape) == shape
+        ka, kb = keep = [np.ascontiguousarray(v, np.float32) for v in (region.ka, region.kb)]
+        assert ka.shape == kb.shape == (n,)
+        kr = C.byref(L.dd_known_region(region.x0.data_ptr(), region.mask.data_ptr(), *(v.ctypes.data_as(C.POINTER(C.c_float)) for v in keep)))
+        prog = prog + keep
+    # (a byref keeps its struct alive, the closure the arrays)
+    call = lambda st, keep=(tab, prog): ctx.lib.dd_sample_affine_walk(ctx.handle, C.byref(args), g, ag, kr, C.byref(walk), st)
+    return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
 
 def sample_multistep_loop(ctx: Context, first: Model, late, x, h, rows, *, switch_after=None, y=None, seed=0, counter_base=0,

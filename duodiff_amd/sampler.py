@@ -32,6 +32,11 @@ given image noised to t = round(999 * 0.5) instead of from pure noise (SDEdit; l
 ``--encode_images``, which the KL-VAE encoder of the engine turns into latents); ``--known_image x.npy --known_mask m.npy`` keeps the
 masked region of the image fixed while the rest is generated (RePaint's replacement rule without resampling), fused into the step kernel.
 
+Resampling jumps (engine options, not in the reference): ``--resample_jump 10 --resample_count 10`` walks the DDPM / DDIM grid with
+RePaint's schedule (Lugmayr et al. 2022): every 10 grid steps x is noised back up 10 steps and brought down again, 10 times in all, so that
+the generated region of an inpainting run (``--known_image``) can agree with the known one; ``--restart T_MIN T_MAX K`` (repeatable) is
+Restart sampling (Xu et al. 2023): K returns from the level T_MIN up to T_MAX.  A jump runs no model; the whole walk is one device loop.
+
 DPM-Solver++ (engine option, not in the reference): ``--dpm_solver ode --dpm_solver_steps 20`` samples with the second-order multistep
 solver (``sde``: its SDE variant) in 20 model evaluations; the table-driven loop with one history register per image.
 """
@@ -49,11 +54,13 @@ import torch
 
 from .config import ModelParams, load_config
 from .autoencoder import get_autoencoder
-from .engine import (Autoguidance, Context, KnownRegion, Perturbed, X0Threshold, layer_mask, sample_affine_loop, sample_affine_region_loop, sample_loop,
+from .engine import (Autoguidance, Context, KnownRegion, Perturbed, X0Threshold, layer_mask, sample_affine_loop, sample_affine_region_loop,
+                     sample_affine_walk_loop, sample_loop,
                      sample_multistep_loop, sample_multistep_region_loop, sample_multistep_threshold_loop, sample_region_loop,
                      schedule_tables, threshold_struct)
 from .step_plan import (MULTISTEP_KINDS, StepPlan, _affine_rows, _data_prediction, _f32, _segments, affine_coefficients, known_rows,  # noqa: F401
-                        multistep_coefficients, multistep_grid, multistep_rows, start_timestep, step_plan, unfolded_coefficients, unfolded_rows)
+                        jump_coefficients, multistep_coefficients, multistep_grid, multistep_rows, repaint_jumps, restart_jumps, start_timestep,
+                        step_plan, unfolded_coefficients, unfolded_rows, walk_moves)
 from .uvit import UViT
 
 
@@ -136,7 +143,7 @@ def backbone_rows(batch_size, cfg_scale=None, pag=None):
 
 
 def _resolve_options(model, late_model, batch_size, image_shape, plan_args, noise, y, autoencoder, cfg_scale, cfg_null_label,
-                     autoguidance_scale, guide_model, pag, image_seeds, init_image, strength, known_image, known_mask, threshold):
+                     autoguidance_scale, guide_model, pag, image_seeds, init_image, strength, known_image, known_mask, threshold, walk=False):
     """get_samples' one options check, before any engine call: every ValueError it raises, in a fixed order.  Returns the StepPlan of
     plan_args; the run's ONE guidance, which the device loops take and the host step picks its forward call by -- None, (scale, null_label),
     Autoguidance(the guide's UViT, scale) or Perturbed(scale, mask_first, mask_late); the seeds as ints; the init image and KnownRegion."""
@@ -169,6 +176,11 @@ def _resolve_options(model, late_model, batch_size, image_shape, plan_args, nois
         image_seeds = [int(v) for v in image_seeds]
         if len(image_seeds) != batch_size:
             raise ValueError(f"image_seeds holds {len(image_seeds)} seeds for batch_size {batch_size}")
+    if walk:
+        if pag is not None:
+            raise ValueError("perturbed-attention guidance does not combine with resampling jumps (resample_jump / restart)")
+        if any(hasattr(m, "classifier_type") for m in (model, late_model) if m is not None):
+            raise ValueError("resampling jumps are not supported for early-exit models")
     if (init_image is None) != (strength is None):
         raise ValueError("init_image and strength go together")
     if (known_image is None) != (known_mask is None):
@@ -230,7 +242,9 @@ def _device_segment(run, k0, k1):
     known = () if run.region is None else (run.region._replace(ka=run.region.ka[k0:k1], kb=run.region.kb[k0:k1]),)   # -> the loop's _region form
     seg = {key: v[k0:k1] for key, v in tab.items()}
     with ctx.image_seeds(run.image_seeds) if run.image_seeds is not None else contextlib.nullcontext():   # (set around the segment's call)
-        if plan.kind == "ddpm":     # dd_sample: the late model unless the segment starts on it; t_switch counted from t = 999, not from t[0]
+        if plan.moves:              # a walk: the rows name their model, and a jump row runs none
+            sample_affine_walk_loop(ctx, run.first, run.late, x, seg, region=known[0] if known else None, counter_base=k0, **kw)
+        elif plan.kind == "ddpm":   # dd_sample: the late model unless the segment starts on it; t_switch counted from t = 999, not from t[0]
             (sample_region_loop if known else sample_loop)(
                 ctx, m0, None if sw == 0 else run.late, x, *known, t_switch=plan.switch_after + 999 - int(tab["t"][0]) if sw else 0,
                 t_start=int(seg["t"][0]), t_end=int(seg["t"][-1]), **kw)
@@ -248,7 +262,12 @@ def _device_segment(run, k0, k1):
 def _host_step(run, k, k1=None):
     """Step k, the segment [k, k + 1): z, then the known region's z2, from the torch CPU stream in the reference's order (sampler.py:103-139)"""
     ctx, plan, x, h, y, g, eps, tab = run.ctx, run.plan, run.x, run.h, run.y, run.guidance, run.eps, run.plan.rows
+    if plan.moves and tab["jump"][k]:                                        # a walk's jump: z3, its one draw; no model, no known blend
+        ctx.jump_step(x, torch.randn(x.shape).to(x.device) if tab["noise"][k] else None, tab["a"][k], tab["c"][k], out=x)
+        return
     cur, t = _segment_models(plan, k, k + 1, run.first, run.late)[0], tab["t"][k]
+    if plan.moves:
+        cur = run.late if tab["late"][k] else run.first
     z = torch.randn(x.shape).to(x.device) if tab["noise"][k] else None
     auto = isinstance(g, Autoguidance)
     if plan.kind == "ddpm" and (g is None or auto and g.guide is cur):      # :130-133, fused; the guide's own steps: unguided, y only if it takes one
@@ -280,7 +299,8 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
                 late_model=None, t_switch=np.inf, *, noise: str = "torch_cpu", use_graph: bool = True,
                 num_steps: int = 1000, return_device_tensor: bool = False, cfg_scale=None, cfg_null_label: int = 1000,
                 solver=None, solver_steps: int = 20, solver_order: int = 2, autoguidance_scale=None, guide_model=None,
-                init_image=None, strength=None, known_image=None, known_mask=None, threshold=None, pag=None, image_seeds=None):
+                init_image=None, strength=None, known_image=None, known_mask=None, threshold=None, pag=None, image_seeds=None,
+                resample_jump=None, resample_count=None, restart=None):
     """reference sampler.py:82-155.  Returns (samples[B,H,W,C] float32 numpy = (x+1)/2, intermediates).
 
     cfg_scale (None: the unguided loops, unchanged): classifier-free guidance of every step's model output,
@@ -321,13 +341,19 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
     threshold (an engine.X0Threshold; engine option): every step's predicted image x0 is clipped to a fixed range (mode "static") or to
         its own quantile scale and rescaled (mode "dynamic", Imagen's dynamic thresholding) before it drives the update; all three
         samplers then run as the thresholded multistep loop on unfolded rows.  predict_noise / predict_original models, pixel space.
+    resample_jump = j with resample_count = r (engine option; RePaint's resampling), or restart = [(t_min, t_max, K), ...] (engine option;
+        Restart sampling): the DDPM / DDIM loop becomes a walk over its grid that also goes back up (step_plan.walk_moves) -- a jump noises x
+        forward, x <- ja x + jc z3, and runs no model.  With or without a known region, guidance, image seeds and strength; not with a
+        solver, a threshold or pag.  noise="device": one device loop per segment, z3 from the device generator; noise="torch_cpu": step by
+        step, a jump's z3 drawn from the torch CPU stream in walk order.  Saves: after the last visit of a saved timestep.
     """
     image_shape = (num_channels, sample_height, sample_width)
     plan_args = (_PARAMETRIZATIONS.get(postprocessing), timesteps_save, late_model is not None, t_switch, num_steps, use_ddim, ddim_steps,
-                 ddim_eta, solver, solver_steps, solver_order, strength, threshold)
+                 ddim_eta, solver, solver_steps, solver_order, strength, threshold, resample_jump, resample_count, restart)
     plan, guidance, image_seeds, init, region = _resolve_options(
         model, late_model, batch_size, image_shape, plan_args, noise, y, autoencoder, cfg_scale, cfg_null_label, autoguidance_scale,
-        guide_model, pag, image_seeds, init_image, strength, known_image, known_mask, threshold)
+        guide_model, pag, image_seeds, init_image, strength, known_image, known_mask, threshold,
+        walk=resample_jump is not None or resample_count is not None or bool(restart))
     rows = backbone_rows(batch_size, cfg_scale, pag)
     y = None if y is None else torch.as_tensor(y).to(model.device, torch.int64).contiguous()
     first, late = model.engine_model(rows), late_model.engine_model(rows) if late_model is not None else None
@@ -584,6 +610,36 @@ def validate_threshold(args, config):
     return X0Threshold("dynamic", quantile=float(dyn), s_max=smax)
 
 
+def validate_resample(args):
+    """The resampling options (--resample_jump / --resample_count, --restart), before any GPU work: ValueError on a bad combination.
+    Returns get_samples' resample_jump / resample_count / restart arguments.  What depends on the grid (an interval that holds fewer than
+    two of its levels, overlaps) is step_plan's to reject, still before any GPU work."""
+    j, r, restart = args.resample_jump, args.resample_count, args.restart
+    if (j is None) != (r is None):
+        raise ValueError("--resample_jump and --resample_count go together")
+    if j is None and not restart:
+        return dict(resample_jump=None, resample_count=None, restart=None)
+    if j is not None and restart:
+        raise ValueError("--resample_jump / --resample_count (RePaint) and --restart are exclusive")
+    if j is not None and j < 1:
+        raise ValueError(f"--resample_jump {j} must be at least 1")
+    if r is not None and r < 1:
+        raise ValueError(f"--resample_count {r} must be at least 1")
+    for name in ("dpm_solver", "clip_x0", "dynamic_threshold", "pag_scale"):
+        if getattr(args, name, None) is not None:
+            raise ValueError(f"--resample_jump / --restart and --{name} are exclusive")
+    out = []
+    for t_min, t_max, k in restart or ():
+        if k != int(k) or k < 1:
+            raise ValueError(f"--restart {t_min:g} {t_max:g} {k:g}: K must be a whole number, at least 1")
+        if not 0 <= t_min < t_max <= 999:
+            raise ValueError(f"--restart {t_min:g} {t_max:g} {k:g}: need 0 <= T_MIN < T_MAX <= 999")
+        out.append((float(t_min), float(t_max), int(k)))
+    kw = dict(resample_jump=j, resample_count=r, restart=out or None)
+    step_plan(args.parametrization, use_ddim=args.use_ddim, ddim_steps=args.ddim_steps, ddim_eta=args.ddim_eta, strength=args.strength, **kw)
+    return kw
+
+
 def solver_kwargs(args):
     """get_samples' solver arguments from the command line"""
     return dict(solver=SOLVERS[args.dpm_solver] if args.dpm_solver is not None else None, solver_steps=args.dpm_solver_steps,
@@ -735,6 +791,15 @@ def get_args(argv=None):
                    help="(engine option) dynamic thresholding (Imagen): per image, s = the Q-quantile of |x0| (at least 1), x0 clipped to "
                         "[-s, s] and divided by s.  Exclusive with --clip_x0; pixel-space predict_noise / predict_original models, --noise device")
     p.add_argument("--threshold_max", type=float, default=None, metavar="S", help="(engine option) with --dynamic_threshold: s is at most S (>= 1)")
+    p.add_argument("--resample_jump", type=int, default=None, metavar="J",
+                   help="(engine option) RePaint's resampling: every J grid steps x is noised back up J steps (no model evaluation) and "
+                        "brought down again; with --resample_count.  DDPM and DDIM loops, with or without --known_image")
+    p.add_argument("--resample_count", type=int, default=None, metavar="R",
+                   help="(engine option) with --resample_jump: each stretch of J steps is run R times in all (1: no jumps)")
+    p.add_argument("--restart", type=float, nargs=3, action="append", default=None, metavar=("T_MIN", "T_MAX", "K"),
+                   help="(engine option, repeatable) Restart sampling: having come down to the timestep T_MIN the loop goes back up to T_MAX "
+                        "with fresh noise and comes down again, K times; intervals snap to the grid and must not overlap.  Exclusive with "
+                        "--resample_jump")
     add_image_seed_args(p)
     return p.parse_args(argv)
 
@@ -777,6 +842,7 @@ def setup_run(args):
     region_kwargs = validate_region(args, config_last)
     threshold = validate_threshold(args, config_last)
     pag = validate_pag(args, config, config_late)
+    resample = validate_resample(args)
     rows = backbone_rows(args.batch_size, args.cfg_scale, pag)
     model, mp = build_model(config, args.checkpoint_path, args.precision, rows)
     late = build_model(config_late, args.checkpoint_path_late, args.precision, rows)[0] if config_late is not None else None
@@ -791,7 +857,7 @@ def setup_run(args):
         sample_width=mp.img_size, use_ddim=args.use_ddim, ddim_steps=args.ddim_steps, ddim_eta=args.ddim_eta, autoencoder=autoencoder,
         late_model=late, t_switch=args.t_switch, noise=args.noise, use_graph=not args.no_graph, cfg_scale=args.cfg_scale,
         cfg_null_label=args.cfg_null_label, **solver_kwargs(args), autoguidance_scale=args.autoguidance_scale, guide_model=guide,
-        threshold=threshold, pag=pag, **region_kwargs))
+        threshold=threshold, pag=pag, **resample, **region_kwargs))
 
 
 def main(argv=None):

@@ -16,9 +16,17 @@ def affine_coefficients(kind, t, s=None, eta=0.0):
     from the engine's (bit-exact) tables:
       "predict_original"  sampler.py:59-72      "predict_previous"  sampler.py:75-79
       "ddim" (t -> s)     sampler.py:112-120 (noise scaled by sigma^2 = betas_tilde[t]*eta, as the reference does)
+      "predict_noise"     sampler.py:47-56 as a table row (the walk plans: resampling jumps need a table-driven loop), formed as
+                          unfolded_rows forms its rows -- float64 from the tables, each coefficient rounded once:
+                          a = 1 / sqrt(alpha_t), b = -beta_t / (sqrt(alpha_t) sqrt(1 - abar_t)), c = sqrt(betas_tilde[t]), with
+                          beta_t = 1 - alpha_t from the alphas table, as the DDPM kernel's c2 has it (the betas table differs
+                          from it by alpha's rounding, 2^-25 absolute: 3e-4 of beta_0)
     """
     tb = schedule_tables()
     one = _f32(1)
+    if kind == "predict_noise":
+        al, ab = float(tb["alphas"][t]), float(tb["alphas_bar"][t])
+        return _f32(1.0 / np.sqrt(al)), _f32(-(1.0 - al) / (np.sqrt(al) * np.sqrt(1.0 - ab))), _f32(np.sqrt(float(tb["betas_tilde"][t])))
     if kind == "predict_previous":
         return _f32(0), one, np.sqrt(tb["betas_tilde"][t])
     if kind == "predict_original":
@@ -184,12 +192,16 @@ class StepPlan(NamedTuple):
     or "multistep" (rows a, b, c, d, p, q, hist: multistep_coefficients).  rows: per-step arrays, always with t (the model timestep,
     float32) and noise (int32: the step draws z).  save_after[k]: x is saved after step k.  switch_after: the first step the late model
     runs, or None; it may lie past the last step (a DDPM switch beyond num_steps), where it only hands the late model to dd_sample.
-    lands[k]: the timestep whose noise level x has after step k, -1 for the final image (known_rows)."""
+    lands[k]: the timestep whose noise level x has after step k, -1 for the final image (known_rows).
+    moves: the walk of a plan with resampling jumps (walk_moves; empty: none).  Such a plan is of kind "affine", has one row per move
+    and two more int32 rows, jump (1: the row is a jump, x' = a x + c z3, no model) and late (1: the step runs the late model);
+    its switch_after is None."""
     kind: str
     rows: dict
     save_after: list
     switch_after: Optional[int]
     lands: tuple = ()
+    moves: tuple = ()
 
 
 def start_timestep(strength=None):
@@ -201,14 +213,152 @@ def start_timestep(strength=None):
     return int(round(999 * float(strength)))
 
 
+def walk_moves(n_steps, jumps):
+    """The walk over a grid of positions p = 0 .. N (x at p < N carries the noise level of the timestep the model sees at step p,
+    position N is the final image).  A step ("S", p) moves p -> p + 1 and evaluates the model at grid step p; a jump ("J", p, p - j)
+    moves p -> p - j and runs no model.  jumps: {position: (length, count)}.  The walk steps from p = 0; after a step arrives at a
+    position p < N that still has budget it spends one and jumps; budgets never refill.  A jump is legal only from 1 <= p < N with
+    p - j >= 0 (never from the final image).  Returns the list of moves."""
+    n = int(n_steps)
+    if n < 1:
+        raise ValueError("a walk needs at least one grid step")
+    budget = {}
+    for p, (length, count) in dict(jumps).items():
+        p, length, count = int(p), int(length), int(count)
+        if not 1 <= p < n or length < 1 or p - length < 0:
+            raise ValueError(f"a jump of length {length} from position {p} is not legal on a grid of {n} steps")
+        if count < 0:
+            raise ValueError(f"jump count {count} at position {p} is negative")
+        budget[p] = [length, count]
+    moves, p = [], 0
+    while p < n:
+        moves.append(("S", p))
+        p += 1
+        if p < n and p in budget and budget[p][1] > 0:
+            budget[p][1] -= 1
+            moves.append(("J", p, p - budget[p][0]))
+            p -= budget[p][0]
+    return moves
+
+
+def repaint_jumps(n_steps, jump, count):
+    """RePaint's schedule (Lugmayr et al., 2022; get_schedule_jump of its code) with jump length j and r resamplings as walk_moves'
+    jumps: the positions p with q = N - p >= 1, (q - 1) % j == 0 and p - j >= 0 get (j, r - 1)."""
+    n, j, r = int(n_steps), int(jump), int(count)
+    if j < 1:
+        raise ValueError(f"resample_jump must be at least 1, not {jump}")
+    if r < 1:
+        raise ValueError(f"resample_count must be at least 1, not {count}")
+    return {p: (j, r - 1) for p in range(1, n) if (n - p - 1) % j == 0 and p - j >= 0}
+
+
+def restart_jumps(levels, restart):
+    """Restart sampling (Xu et al., 2023) as walk_moves' jumps.  levels: the timestep the model sees at every grid position
+    (descending); restart: (t_min, t_max, K) triples.  An interval snaps to the grid: lo = the position of the smallest level >= t_min,
+    hi = the position of the largest level <= t_max, and lo gets (lo - hi, K): the walk comes down to lo, jumps back up to hi and
+    repeats K times.  An interval that snaps to lo <= hi, or two that overlap on the grid, are ValueErrors."""
+    levels = np.asarray(levels, np.float64)
+    jumps, taken = {}, []
+    for item in restart:
+        try:
+            t_min, t_max, k = item
+            t_min, t_max, k = float(t_min), float(t_max), int(k)
+        except (TypeError, ValueError):
+            raise ValueError(f"a restart interval is (t_min, t_max, K), not {item!r}") from None
+        if k < 1:
+            raise ValueError(f"restart count K must be at least 1, not {k}")
+        if not t_min < t_max:
+            raise ValueError(f"restart interval needs t_min < t_max, not ({t_min:g}, {t_max:g})")
+        above, below = np.nonzero(levels >= t_min)[0], np.nonzero(levels <= t_max)[0]
+        if not len(above) or not len(below) or above[-1] <= below[0]:
+            raise ValueError(f"restart interval ({t_min:g}, {t_max:g}) holds fewer than two levels of the grid")
+        lo, hi = int(above[-1]), int(below[0])
+        if any(hi < b and a < lo for a, b in taken):                           # (two intervals may share one grid point)
+            raise ValueError(f"restart interval ({t_min:g}, {t_max:g}) overlaps another one on the grid")
+        taken.append((hi, lo))
+        jumps[lo] = (lo - hi, k)
+    return jumps
+
+
+def jump_coefficients(s, u):
+    """(ja, jc) of the forward-noising jump from the noise level of timestep s up to that of timestep u >= s:
+    x_u = ja x_s + jc z3 with ja = sqrt(abar[u] / abar[s]), jc = sqrt(1 - abar[u] / abar[s]), in float64 from the engine's tables,
+    each rounded once."""
+    ab = schedule_tables()["alphas_bar"].astype(np.float64)
+    ratio = ab[int(u)] / ab[int(s)]
+    return _f32(np.sqrt(ratio)), _f32(np.sqrt(1.0 - ratio))
+
+
+def _walk_plan(base, parametrization, moves, timesteps_save):
+    """The plan of a walk over the jump-free plan `base` (kind "affine", or the predict_noise "ddpm" plan, which becomes affine rows):
+    a step row is base's row at the grid position, once per visit, a jump row is (a, b, c, noise) = (ja, 0, jc, 1) with the Philox
+    counter of its own index like any row.  late[k]: what base runs at that position (the late model's rule stays by timestep);
+    lands[k] of a jump: the level it reaches; save_after[k]: the last visit of a saved timestep."""
+    if base.kind == "ddpm":
+        ts = [int(t) for t in base.rows["t"]]
+        grid = _affine_rows(ts, [affine_coefficients(parametrization, t) for t in ts], list(base.rows["noise"]))
+    else:
+        grid = base.rows
+    level = [int(t) for t in grid["t"]]
+    n = len(level)
+    rows = {k: [] for k in ("t", "a", "b", "c", "noise", "jump", "late")}
+    lands = []
+    for mv in moves:
+        if mv[0] == "S":
+            p = mv[1]
+            vals = (grid["t"][p], grid["a"][p], grid["b"][p], grid["c"][p], grid["noise"][p], 0,
+                    int(base.switch_after is not None and p >= base.switch_after))
+            lands.append(base.lands[p])
+        else:
+            _, p, u = mv
+            ja, jc = jump_coefficients(level[p], level[u])
+            vals = (grid["t"][u], ja, 0.0, jc, 1, 1, 0)
+            lands.append(level[u])
+        for k, v in zip(rows, vals):
+            rows[k].append(v)
+    rows = {k: np.array(v, np.int32 if k in ("noise", "jump", "late") else np.float32) for k, v in rows.items()}
+    saves = set(int(v) for v in timesteps_save)
+    last = {}
+    for k, mv in enumerate(moves):
+        if mv[0] == "S" and (1000 - level[mv[1]]) in saves:
+            last[mv[1]] = k
+    save_after = [False] * len(moves)
+    for k in last.values():
+        save_after[k] = True
+    assert n == len(base.lands)
+    return StepPlan("affine", rows, save_after, None, tuple(lands), tuple(moves))
+
+
 def step_plan(parametrization, timesteps_save=(), has_late=False, t_switch=np.inf, num_steps=1000, use_ddim=False, ddim_steps=50,
-              ddim_eta=0.0, solver=None, solver_steps=20, solver_order=2, strength=None, threshold=None):
+              ddim_eta=0.0, solver=None, solver_steps=20, solver_order=2, strength=None, threshold=None, resample_jump=None,
+              resample_count=None, restart=None):
     """The StepPlan of get_samples' arguments (parametrization: "predict_noise" | "predict_original" | "predict_previous", or None
     for a postprocessing function of elsewhere; has_late: a late model is given).  Host arithmetic only, no torch.
     strength (None or 1: the start at t = 999): the loops start at t0 = start_timestep(strength) -- DDPM at t0, the DDIM and solver grids
     built from t0 down with the same spacing rule and step count; the late model's rule is unchanged (by timestep).
     threshold (anything but None): the plan of the thresholded loop -- kind "multistep" on UNFOLDED rows for all three samplers
-    (multistep_coefficients(..., unfolded=True), unfolded_coefficients); predict_previous has no x0 and is rejected."""
+    (multistep_coefficients(..., unfolded=True), unfolded_coefficients); predict_previous has no x0 and is rejected.
+    resample_jump = j with resample_count = r (RePaint's schedule, repaint_jumps) or restart = [(t_min, t_max, K), ...] (Restart
+    sampling, restart_jumps): the plan of a walk over the grid of the plan without them (walk_moves, _walk_plan) -- kind "affine" for
+    DDPM and DDIM alike.  Not with DPM-Solver++ (its history would have to restart behind a jump) or x0 thresholding, and not both
+    at once; r == 1, or a j too long for any jump, gives the plan without them."""
+    walk = resample_jump is not None or resample_count is not None or bool(restart)
+    if walk:
+        if (resample_jump is None) != (resample_count is None):
+            raise ValueError("resample_jump and resample_count go together")
+        if resample_jump is not None and restart:
+            raise ValueError("RePaint's resampling (resample_jump / resample_count) and Restart sampling (restart) are exclusive")
+        if solver is not None:
+            raise ValueError("resampling jumps are not supported with DPM-Solver++: its history would have to restart behind a jump")
+        if threshold is not None:
+            raise ValueError("resampling jumps are not supported with x0 thresholding")
+        base = step_plan(parametrization, timesteps_save, has_late, t_switch, num_steps, use_ddim, ddim_steps, ddim_eta, strength=strength)
+        n = len(base.rows["t"])
+        jumps = repaint_jumps(n, resample_jump, resample_count) if resample_jump is not None else restart_jumps(base.rows["t"], restart)
+        moves = walk_moves(n, jumps)
+        if len(moves) == n:
+            return base
+        return _walk_plan(base, parametrization, moves, timesteps_save)
     t0 = start_timestep(strength)
     if threshold is not None:
         _data_prediction(parametrization if parametrization is not None else "predict_noise", 0.5)

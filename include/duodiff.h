@@ -374,6 +374,31 @@ int dd_sample_affine_region(dd_ctx* ctx, const dd_affine_sample_args* args, cons
 int dd_sample_multistep_region(dd_ctx* ctx, const dd_multistep_sample_args* args, const dd_guidance* g, const dd_autoguidance* ag,
                                const dd_known_region* kr, void* stream);
 
+/* ---- resampling jumps: RePaint's resampling (Lugmayr et al. 2022) and Restart sampling (Xu et al. 2023) in the table-driven loop ---------- */
+/* A walk over a plan's timestep grid that may go back up.  Its table has one row per move: a STEP row is dd_sample_affine's row (the model
+ * runs at t[k]); a JUMP row (jump[k] != 0) runs no model and noises x forward from the level it has to a higher one,
+ *     x' = ja * x + jc * z3        ja = a[k] = sqrt(abar[u] / abar[s]), jc = c[k] = sqrt(1 - abar[u] / abar[s]), b[k] must be 0
+ * in fp32, contraction off, each product rounded on its own (duodiff_amd.step_plan jump_coefficients).  Every pixel takes it, the known
+ * ones of a region too (a known row of a jump is not read).  z3 comes from the device Philox generator with the key, pixel id and
+ * counter of a step's z (the row's index in the whole walk, counter_base included) under a third stream word: z, z2 and z3 of one counter
+ * are independent, and chained, cut and uncut runs draw the same.  noise[k] == 0 or DD_NOISE_NONE: no jc z3 term.
+ * A jump from below the switch to above it hands the steps back to the first model: late[k] names each step row's model. */
+typedef struct dd_walk {
+    const int32_t* jump;    /* host [n_steps]: != 0: row k is a jump */
+    const int32_t* late;    /* host [n_steps]: 1: step row k runs args->late, 0: args->first (a jump row's entry is not read); may be NULL:
+                             * args->switch_after rules, as in dd_sample_affine */
+} dd_walk;
+/* the jump alone, elementwise on n values: out = ja * x + jc * z (z_dev NULL: ja * x); x_dev and out_dev may alias */
+int dd_jump_step(dd_ctx* ctx, const float* x_dev, const float* z_dev, float ja, float jc, float* out_dev, int64_t n, void* stream);
+/* dd_sample_affine[_guided | _autoguided | _region] over a walk: g, ag and kr are optional (NULL), g and ag exclusive.  Everything that
+ * loop stages is staged as there (per-image seeds, two half-batch chains, graph replay or eager launches, counter_base); a jump replays
+ * a small captured graph of its own per chain.  A table may begin or end with a jump row, and a walk may be cut into calls anywhere.
+ * DD_ERR_INVALID before anything is enqueued when walk or its jump array is NULL, a jump row has b != 0, late[k] is outside {0, 1} or 1
+ * without a late model, both g and ag are given, a model carries early-exit heads, the noise mode is host noise (drive dd_forward,
+ * dd_affine_step, dd_known_blend and dd_jump_step), or a check of dd_sample_affine's own fails. */
+int dd_sample_affine_walk(dd_ctx* ctx, const dd_affine_sample_args* args, const dd_guidance* g, const dd_autoguidance* ag,
+                          const dd_known_region* kr, const dd_walk* walk, void* stream);
+
 /* ---- x0 clipping and dynamic thresholding (Ho et al. 2020; Saharia et al. 2022, Imagen; Lu et al. 2022) of the multistep loop ---------- */
 /* The multistep row's data prediction x0 = p*x + q*m (its history expression) is pulled back before it drives the update, and the update
  * takes the result xh in m's place: the rows a, b are UNFOLDED (b multiplies xh, not m; duodiff_amd.sampler multistep_coefficients(...,
@@ -599,7 +624,9 @@ int dd_plan_rows(int M, int N, int K, int num_cus, int* q_out, int* e_out);
 int dd_set_num_cus(dd_ctx* ctx, int num_cus);
 
 /* Per-step timing of the last dd_sample call, measured with hipEvents on its stream:
- * [0] total ms, [1] ms in first-model steps, [2] ms in late-model steps. */
+ * [0] total ms, [1] ms in first-model steps, [2] ms in late-model steps.  After dd_sample_affine_walk the split is taken in front of
+ * the FIRST late step; once a jump has handed the steps back to the first model the two models interleave, and [1] / [2] no longer
+ * mean a model's share: only [0] does. */
 int dd_last_sample_timing(dd_ctx* ctx, float out3[3]);
 
 #ifdef __cplusplus

@@ -75,6 +75,11 @@ class dd_walk(C.Structure):
     _fields_ = [("jump", C.POINTER(C.c_int32)), ("late", C.POINTER(C.c_int32))]
 
 
+class dd_block_cache(C.Structure):
+    """block caching beside the step table: K = blocks, the order, and per step the op (0 refresh, 1 reuse, 2 reuse with extrapolation) and its weight"""
+    _fields_ = [("blocks", C.c_int32), ("order", C.c_int32), ("op", C.POINTER(C.c_int32)), ("w", C.POINTER(C.c_float))]
+
+
 class dd_x0_threshold(C.Structure):
     """x0 thresholding of the multistep loop: static (clamp to +-range) or dynamic (the image's own quantile scale, at most s_max)"""
     _fields_ = [("mode", C.c_int32), ("quantile", C.c_float), ("range", C.c_float), ("s_max", C.c_float)]
@@ -195,6 +200,10 @@ SIGNATURES = {
     "dd_jump_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
     "dd_sample_affine_walk": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.POINTER(dd_guidance), C.POINTER(dd_autoguidance),
                                         C.POINTER(dd_known_region), C.POINTER(dd_walk), C.c_void_p]),
+    "dd_forward_cached": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.POINTER(dd_guidance), C.c_int32, C.c_int32,
+                                    C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
+    "dd_sample_affine_cached": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.POINTER(dd_guidance), C.POINTER(dd_known_region),
+                                          C.POINTER(dd_block_cache), C.c_void_p]),
     "dd_threshold_step": (C.c_int, [C.c_void_p] * 5 + [C.POINTER(dd_x0_threshold)] + [C.c_float] * 6 +
                           [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dd_sample_multistep_threshold": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_guidance),
@@ -232,6 +241,8 @@ SIGNATURES = {
     "dd_dev_rowlin": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 5 + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_attention": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_layernorm": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.POINTER(C.c_float)]),
+    "dd_dev_cache_extrapolate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p,
+                                           C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_embed": (C.c_int, [C.c_void_p] + [C.c_int] * 9 + [C.c_void_p] * 7 + [C.c_float] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_time_mlp": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 6 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_vae_gather": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

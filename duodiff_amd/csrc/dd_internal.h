@@ -485,6 +485,13 @@ hipError_t launch_jump(float* x, StepState* st, const AffineRow* atab, const uns
                        int noise_mode, hipStream_t s);
 // out = ja x [+ jc z if z] on n elements: the unfused jump (x and out may alias)
 hipError_t launch_jump_step(const float* x, const float* z, float* out, float ja, float jc, long long n, hipStream_t s);
+// Block caching (cache.hip): out = last + w (last - prev) on n elements of the activation type (n % 64 == 0, 16-byte aligned, out aliasing
+// neither input).  atab set: the op and w of row st->t (AffineRow::pad1 = the op, pad2 = the bits of w); else the arguments.  op 2
+// extrapolates, any other op copies last and does not read prev.  The grid holds at most CACHE_MAX_BLOCKS workgroups of 256 and strides.
+enum { CACHE_REFRESH = 0, CACHE_REUSE = 1, CACHE_EXTRAPOLATE = 2 };
+constexpr int CACHE_MAX_BLOCKS = 2048;
+hipError_t launch_cache_extrapolate(const void* last, const void* prev, void* out, long long n, bool bf16, const StepState* st,
+                                    const AffineRow* atab, int op, float w, hipStream_t s);
 hipError_t launch_ee_mean_combine(const float* s0, const float* s1, float* err, int depth, int t_lo, int t_hi, int B, hipStream_t s);
 hipError_t launch_set_state(StepState* st, int t, unsigned long long seed, hipStream_t s);
 hipError_t launch_set_state_table(StepState* st, const AffineRow* atab, unsigned long long seed, hipStream_t s);   // step index 0

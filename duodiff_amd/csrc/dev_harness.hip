@@ -526,6 +526,33 @@ int dd_dev_layernorm(dd_ctx* c, int precision, int rows, int D, const float* x_h
     return dev.status();
 }
 
+int dd_dev_cache_extrapolate(dd_ctx* c, int precision, int rows, int D, const void* last_host, const void* prev_host, int op, float w, int table,
+                             void* out_host, int iters, void* stream, float* ms_out) {
+    const bool bf = precision == DD_PREC_BF16;
+    if (!c || (!bf && precision != DD_PREC_FP32) || rows < 1 || rows > (1 << 24) || D < 64 || D % 64 || D > 4096 || !last_host || !prev_host ||
+        !out_host || op < 0 || op > 2 || iters < 0)
+        return DD_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t es = bf ? 2 : 4, n = (size_t)rows * D, n_out = ((size_t)rows + 8) * D;
+    DevScope dev(c);
+    const void* dL = dev.upload((const char*)last_host, n * es);
+    const void* dP = dev.upload((const char*)prev_host, n * es);
+    void* dO = dev.filled(n_out * es, 0xFF);
+    // the production form: the op and w in row 1 of a step table whose other rows hold 0xFF bytes, the step state at that row
+    std::vector<AffineRow> tab(3);
+    memset((void*)tab.data(), 0xFF, tab.size() * sizeof(AffineRow));
+    tab[1].pad1 = op; tab[1].pad2 = __builtin_bit_cast(int, w);
+    const StepState st_host{1, 0.f, 0ull, 1, 0};
+    const AffineRow* dT = table ? dev.upload(tab.data(), tab.size() * sizeof(AffineRow)) : nullptr;
+    const StepState* dS = table ? dev.upload(&st_host, sizeof(StepState)) : nullptr;
+    auto once = [&]() { return launch_cache_extrapolate(dL, dP, dO, (long long)n, bf, dS, dT, table ? -1 : op, table ? __builtin_nanf("") : w, s); };
+    DEV_HIP(dev, once());
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(out_host, dO, n_out * es);
+    DEV_HIP(dev, time_launches(s, iters, once, ms_out));
+    return dev.status();
+}
+
 int dd_dev_embed(dd_ctx* c, int B, int C, int S, int P, int D, int extras, int num_classes, int normalize, int generic, const float* x_img,
                  const float* w, const float* bias, const float* pos, const float* label_emb, const long long* y, const float* t_vec,
                  float t_state, const float* ln, float* x_tok_host, unsigned short* ln_frag_host, int iters, void* stream, float* ms_out) {

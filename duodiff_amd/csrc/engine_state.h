@@ -69,6 +69,7 @@ struct GraphKey {
     unsigned pfirst = 0, plate = 0;                                  //   masks of the loop's two models
     const void* seeds = nullptr;                                     // per-image seeds: the context's staged copy (null: the plain noise)
     int jchans = 0, jsize = 0;                                       // a jump's graph (dd_ctx::jump_graph: no model's): the image shape C, S
+    int cblocks = 0, corder = 0;                                     // block caching: K (0: none) and the order
     bool operator==(const GraphKey&) const = default;
     void perturb(const dd_pag* p) {
         if (p) { pag = 1; gscale = __builtin_bit_cast(unsigned, p->scale); pfirst = p->layers_first; plate = p->layers_late; }
@@ -79,7 +80,8 @@ struct GraphKey {
 };
 
 // the captured step of each sampling loop: dd_model::graph[kind][chain]
-enum GraphKind { GRAPH_DDPM, GRAPH_AFFINE, GRAPH_EARLY_EXIT, GRAPH_MULTISTEP, GRAPH_SCAN, GRAPH_SCAN_EXITS, GRAPH_KINDS };
+// (GRAPH_AFFINE_REUSE: the reuse step of dd_sample_affine_cached, beside the refresh step in GRAPH_AFFINE)
+enum GraphKind { GRAPH_DDPM, GRAPH_AFFINE, GRAPH_EARLY_EXIT, GRAPH_MULTISTEP, GRAPH_SCAN, GRAPH_SCAN_EXITS, GRAPH_AFFINE_REUSE, GRAPH_KINDS };
 }  // namespace dd
 #pragma GCC visibility pop
 
@@ -162,6 +164,22 @@ struct WsPtrs {
     float* ytap = nullptr;                // early-exit models with fused_skip: the block output y of the launches that run the next skip_linear (MlpFusedArgs::y_tap)
 };
 
+// The block cache of one chain of a model (include/duodiff.h dd_block_cache): y_deep of the last refresh, of the one before it, and the
+// extrapolated y^ an order-1 reuse step reads -- [Mp, D] of the activation type each, laid out like WsPtrs::xb, allocated on first use
+// (ensure_block_cache) and outside the workspace arena: no other forward writes them.  Beside them the host-side validity: what the
+// buffers hold, carried across calls so that a loop cut at a save point continues where the uncut loop would.
+struct BlockCache {
+    void *last = nullptr, *prev = nullptr, *yhat = nullptr;
+    int K = 0, rows = 0, b0 = 0, B = 0;     // the geometry `last` was written under: blocks, backbone rows, the chain's first image and size
+    bool has_last = false, has_prev = false;
+    bool holds(int K_, int rows_, int b0_, int B_) const { return has_last && K == K_ && rows == rows_ && b0 == b0_ && B == B_; }
+    // a refresh of this geometry; rotate: prev <- last went first
+    void refresh(int K_, int rows_, int b0_, int B_, bool rotate) {
+        has_prev = rotate && holds(K_, rows_, b0_, B_);
+        K = K_; rows = rows_; b0 = b0_; B = B_; has_last = true;
+    }
+};
+
 }  // namespace dd
 #pragma GCC visibility pop
 
@@ -209,6 +227,7 @@ struct dd_model {
     dd::WsPtrs ws[2];
     hipGraphExec_t graph[dd::GRAPH_KINDS][2] = {};                // each loop's captured step, per chain
     dd::GraphKey gkey[dd::GRAPH_KINDS][2]{};
+    dd::BlockCache cache[2];                                 // block caching: each chain's cache (ensure_block_cache)
     float* ee_ws = nullptr;                                  // dd_sample_early_exit scratch: eps | cls | outs (two chains: one such block per chain, half the batch each),
                                                              // then the chains' per-step sums of the predicted errors [2][1000][depth]
     // in-context timing (dd_profile_steps): event pairs recorded around each launch of kind ctx->prof_kind when enabled
@@ -268,12 +287,26 @@ struct EeTaps { float* cls; float* outs; int t; };
 // what a forward's perturbation record is made from (Backbone::pert_first / pert_mask)
 struct Perturb { int first = 0; unsigned mask = 0; };
 
+// What one forward does with the chain's block cache (BlockCache; Backbone reads it).  blocks == 0: nothing, the forward of an uncached call.
+// A refresh runs every block and stores y_deep, the output of block nb - 1 - K, in `last` (rotate: prev <- last first).  A reuse skips blocks
+// K .. nb - 1 - K: out-block nb - K takes y^ for its x operand -- `last` itself, or (extrapolate) what cache_extrapolate_kernel leaves in yhat:
+// under atab the op and w of the table's current row (an order-1 loop's reuse step, captured once for both ops), else last + w (last - prev).
+struct CacheUse {
+    int blocks = 0;                    // K
+    bool reuse = false;                // a reuse step (else a refresh)
+    bool rotate = false;               // a refresh: prev <- last first
+    bool extrapolate = false;          // a reuse: y^ comes from the kernel
+    float w = 0.f;                     //   with this weight,
+    const AffineRow* atab = nullptr;   //   or with the op and w of the step table's current row
+};
+
 // The options of one model evaluation (forward_eps) or one sampling step (enqueue_step), set by name at the call site
 struct StepOpts {
     const float* t_set = nullptr;      // put this timestep into the chain's step state first (else the state holds it)
     const float* t_vec = nullptr;      // per-image timesteps on the device (dd_forward*)
     const EeTaps* ee = nullptr;        // early-exit heads and probes of the forward
     Mods mods{};                       // g, ag; and (a step) kn: the known region of these B images finishes x'
+    CacheUse cache{};                  // block caching of this forward (none: blocks == 0)
     // a step only
     int noise_mode = DD_NOISE_NONE;
     const float* z = nullptr;          // DD_NOISE_BUFFER: the step's noise
@@ -297,6 +330,7 @@ struct Schedule {
 };
 const Schedule& schedule();
 int ensure_chain_ws(dd_ctx* c, dd_model* m, hipStream_t s);   // the second half-batch chain's workspace, laid out on the first chained call
+int ensure_block_cache(dd_ctx* c, dd_model* m, int chain, hipStream_t s);   // a chain's block cache, allocated and zeroed (on s) on first use
 
 // ---- forward.hip
 Mods perturbed(const dd_pag* p, const dd_model* late);
@@ -305,6 +339,7 @@ X0Threshold kernel_threshold(const dd_x0_threshold* t, long long n);
 int check_call(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev);
 int check_guided(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev, const dd_guidance* g);
 int check_perturbed(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev, const dd_pag* p, unsigned mask);
+int check_cached(dd_ctx* c, dd_model* m, int blocks);
 int check_autoguided(dd_ctx* c, dd_model* first, dd_model* late, int B, const int64_t* y_dev, const dd_autoguidance* ag);
 int enqueue_step(dd_ctx* c, dd_model* m, const Chain& ch, float* x_dev, const int64_t* y_dev, int B, hipStream_t s, const StepOpts& o);
 int forward_eps(dd_ctx* c, dd_model* m, const Chain& ch, const float* x_dev, const int64_t* y_dev, float* eps_dev, int B, hipStream_t s,

@@ -74,6 +74,11 @@ struct Backbone {
     // the blocks of pert_mask (bit i = block i in forward order); 0: no block, the launches of an unperturbed forward
     int pert_first = 0;
     unsigned pert_mask = 0;
+    // block caching (CacheUse; cu.blocks == 0: none, and every launch below is an uncached forward's).  The seam, on refresh and on reuse alike:
+    // block nb - 1 - K hands its output to the chain's cache and does not run the next skip_linear in its own launch (a fused launch consumes
+    // the patch rows' y without writing them); out-block nb - K runs its skip_linear as a stage of its own, from the cache and from the
+    // row-major long-skip copy that in-block K - 1 therefore writes whole (no fragment copy of its patch rows).
+    CacheUse cu{};
     dd_ctx* c = m->ctx;
     const WsPtrs& ws = *ch.ws;
     const int D = m->D, L = m->L, M = B * L, nb = (int)m->blocks.size();
@@ -86,6 +91,13 @@ struct Backbone {
     float* ee_dec_all = ee && m->ee_batched ? (float*)ws.hid : nullptr;
     float* ee_srow_all = ee_dec_all ? ee_dec_all + (size_t)nb * M * m->pd : nullptr;
     bool ao_in_frag = false;     // norm1_attention -> block_tail of the same block: the patch rows of the attention output are in aofrag
+    const BlockCache& bc = m->cache[ch.ws == &m->ws[1] ? 1 : 0];
+    const int deep_first = cu.blocks ? cu.blocks : -1, deep_last = cu.blocks ? nb - 1 - cu.blocks : -1;   // the deep range (-1: no caching)
+    // in-block bi is the last block in front of the deep range of a reuse pass: the block behind it does not run, so its tail leaves no norm1
+    // (and no fragment-order residual rows) for one -- only its long-skip copy is read, by the seam's skip_linear, which sets x
+    bool ends_outer(int bi) const { return cu.reuse && bi + 1 == deep_first; }
+    // the x operand of out-block deep_last + 1's skip_linear: the chain's cache, or the extrapolation of it
+    const T* cached_y() const { return (const T*)(cu.reuse && cu.extrapolate ? bc.yhat : bc.last); }
 
     // in-context timing (dd_profile_steps): an event on s in front of and behind every launch of the selected kind (DD_TIMED)
     int mark(int kind) {
@@ -201,7 +213,7 @@ struct Backbone {
     int skip_linear(int bi, Handoff& hand) {
         if (bi <= m->half_depth || hand.skip) return DD_OK;
         const BlockW& w = m->blocks[bi];
-        GemmArgs<T> g{xb, skip_of(bi), (const T*)w.skip_w, w.skip_b, ws.x, nullptr, M, D, 2 * D, D, D, D, D};
+        GemmArgs<T> g{bi == deep_last + 1 ? cached_y() : xb, skip_of(bi), (const T*)w.skip_w, w.skip_b, ws.x, nullptr, M, D, 2 * D, D, D, D, D};
         g.tile128 = tile128(D, 2 * D, D);
         if constexpr (bf16) {
             if (m->rowlin_skip || m->splitk) hand = norm1_written();
@@ -275,7 +287,8 @@ struct Backbone {
         const BlockW& w = m->blocks[bi];
         const bool is_in = bi < m->half_depth;   // the next block starts with norm1 (no skip_linear in between)
         const BlockW* wn = bi + 1 < nb ? &m->blocks[bi + 1] : nullptr;
-        T* copy = is_in ? (T*)ws.skips[bi] : (wn ? xb : nullptr);
+        T* copy = is_in ? (T*)ws.skips[bi] : bi == deep_last ? (T*)bc.last : (wn ? xb : nullptr);
+        const bool ln_next = is_in && !ends_outer(bi);   // the row passes below write that norm1 -- not for a block that will not run
         const Handoff in = next;     // (what this block found: the residual rows' form is this stage's to read)
         next = Handoff{};
         if constexpr (bf16) {
@@ -287,8 +300,8 @@ struct Backbone {
         GemmArgs<T> g{hid, nullptr, (const T*)w.fc2_w, w.fc2_b, ws.x, copy, M, D, m->hidden, m->hidden, m->hid_ld, m->hid_ld, D};
         g.tile128 = tile128(D, m->hidden, m->hidden);
         if constexpr (bf16) {   // (the row passes write the next block's norm1 where it starts with one)
-            const float *ln_g = is_in ? wn->ln1_g : nullptr, *ln_b = is_in ? wn->ln1_b : nullptr;
-            if (is_in && (m->rowlin_fc2 || m->splitk)) next = norm1_written();
+            const float *ln_g = ln_next ? wn->ln1_g : nullptr, *ln_b = ln_next ? wn->ln1_b : nullptr;
+            if (ln_next && (m->rowlin_fc2 || m->splitk)) next = norm1_written();
             if (m->rowlin_fc2) return rowlin_then_reduce(g, 1, w.rl_img, ln_g, ln_b, m->fused_qa);
             if (m->splitk) return splitk_then_reduce_ln(g, 1, ln_g, ln_b, m->fused_qa);
         }
@@ -307,8 +320,9 @@ struct Backbone {
         if (m->fused_proj) { fa.ao = (const bf16_t*)ao; fa.bproj = w.proj_b; }
         if (ao_in_frag) fa.ao_frag = ws.aofrag;
         // the long-skip operand's patch rows: in-block bi's copy into its fragment buffer, read back by the tail that runs out-block nb - 1 - bi's skip_linear
-        if (m->frag_skip && bi < m->half_depth) fa.out_frag = ws.skipfrags[bi];
-        next.skip = m->fused_skip && bi >= m->half_depth && bi + 1 < nb;   // the next block starts with skip_linear
+        // (not in-block K - 1's under block caching: out-block nb - K reads them row-major)
+        if (m->frag_skip && bi < m->half_depth && bi + 1 != deep_first) fa.out_frag = ws.skipfrags[bi];
+        next.skip = m->fused_skip && bi >= m->half_depth && bi + 1 < nb && bi != deep_last;   // the next block starts with skip_linear
         if (next.skip) {
             fa.skip = (const bf16_t*)skip_of(bi + 1);
             if (m->frag_skip) fa.skip_frag = ws.skipfrags[nb - 1 - (bi + 1)];
@@ -317,7 +331,7 @@ struct Backbone {
         }
         // the next block's norm1 where it starts with one (behind its skip_linear, if this launch runs that); its attn.qkv inside its attention
         // launch (fused_qa), else last of all in this launch (fused_qkv) -- wherever this launch leaves that block's norm1
-        const bool h_next = bi < m->half_depth || next.skip;
+        const bool h_next = (bi < m->half_depth || next.skip) && !ends_outer(bi);
         // the residual patch rows: from xfrag where the previous tail left them there, into xfrag where the next launch to touch them is another tail
         // (h_next: no skip_linear launch in between); the last tail writes x for the output head -- fragment order lives between tails only
         if (in.xfrag) fa.x_in_frag = ws.xfrag;
@@ -332,6 +346,20 @@ struct Backbone {
         block_tail_plan(fa, B, m->N, m->extras, D, m->H, m->hidden, bi + 1 == nb);
         DD_TIMED(DD_PROF_BLOCK_TAIL, launch_mlp_fused(fa, D, s));   // (the event pair brackets the fused kernel alone)
         DD_HIP(c, block_tail_finish(fa, D, s));
+        return DD_OK;
+    }
+
+    // block caching, in front of the seam's skip_linear.  A refresh: nothing (cache_rotate has run in front of the forward).  A reuse that
+    // extrapolates: y^ = last + w (last - prev) into yhat, by the table's row or by cu.w.
+    int cache_seam() {
+        if (!cu.reuse || !cu.extrapolate) return DD_OK;
+        DD_HIP(c, launch_cache_extrapolate(bc.last, bc.prev, bc.yhat, (long long)M * D, bf16, ch.st, cu.atab, CACHE_EXTRAPOLATE, cu.w, s));
+        return DD_OK;
+    }
+    // prev <- last, in front of a refresh that rotates
+    int cache_rotate() {
+        if (!cu.blocks || cu.reuse || !cu.rotate) return DD_OK;
+        DD_HIP(c, hipMemcpyAsync(bc.prev, bc.last, (size_t)M * D * sizeof(T), hipMemcpyDeviceToDevice, s));
         return DD_OK;
     }
 
@@ -367,11 +395,17 @@ struct Backbone {
 
 template <typename T>
 int run_backbone(dd_model* m, const Chain& ch, const float* x_img, const float* t_vec, const int64_t* y_dev, int B, hipStream_t s,
-                 const EeTaps* ee = nullptr, Perturb pert = {}) {
-    Backbone<T> f{m, ch, B, s, ee, pert.first, pert.mask};
+                 const EeTaps* ee = nullptr, Perturb pert = {}, const CacheUse& cu = {}) {
+    Backbone<T> f{m, ch, B, s, ee, pert.first, pert.mask, cu};
     Handoff hand;
+    if (int rc = f.cache_rotate()) return rc;
     if (int rc = f.embed(x_img, t_vec, y_dev, hand)) return rc;
     for (int bi = 0; bi < f.nb; ++bi) {
+        if (bi == f.deep_first && cu.reuse) {      // the deep blocks do not run: on to the out-block behind them, which starts from y^ alone
+            bi = f.deep_last + 1;
+            hand = Handoff{};
+            if (int rc = f.cache_seam()) return rc;
+        }
         bool side = false;   // this block's early-exit head / probe launches are in flight on the side stream
         if (int rc = f.ee_taps(bi, hand, side)) return rc;
         if (int rc = f.skip_linear(bi, hand)) return rc;
@@ -385,9 +419,9 @@ int run_backbone(dd_model* m, const Chain& ch, const float* x_img, const float* 
 }
 
 int run_model(dd_model* m, const Chain& ch, const float* x_img, const float* t_vec, const int64_t* y_dev, int B, hipStream_t s,
-              const EeTaps* ee = nullptr, Perturb pert = {}) {
-    return m->prec == DD_PREC_BF16 ? run_backbone<bf16_t>(m, ch, x_img, t_vec, y_dev, B, s, ee, pert)
-                                   : run_backbone<float>(m, ch, x_img, t_vec, y_dev, B, s, ee, pert);
+              const EeTaps* ee = nullptr, Perturb pert = {}, const CacheUse& cu = {}) {
+    return m->prec == DD_PREC_BF16 ? run_backbone<bf16_t>(m, ch, x_img, t_vec, y_dev, B, s, ee, pert, cu)
+                                   : run_backbone<float>(m, ch, x_img, t_vec, y_dev, B, s, ee, pert, cu);
 }
 
 // the checks of a call that do not concern labels
@@ -434,6 +468,15 @@ int check_perturbed(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev, const d
         return ctx_fail(c, DD_ERR_INVALID, "a perturbed batch of B images runs 2 B backbone rows: need 1 <= B and 2 B <= max_batch");
     if (m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, "perturbed-attention guidance is not supported for early-exit models");
     return check_call(c, m, 2 * B, y_dev);
+}
+
+// block caching with K = blocks on m (include/duodiff.h dd_block_cache): a plain model, 1 <= K <= depth / 2
+int check_cached(dd_ctx* c, dd_model* m, int blocks) {
+    if (!c || !m) return DD_ERR_INVALID;
+    if (m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, "block caching is not supported for early-exit models");
+    if (blocks < 1 || blocks > m->half_depth)
+        return ctx_fail(c, DD_ERR_INVALID, "block caching: blocks = " + std::to_string(blocks) + " outside [1, depth / 2 = " + std::to_string(m->half_depth) + "] of the model");
+    return DD_OK;
 }
 
 // an autoguided call of B images (include/duodiff.h dd_autoguidance) on first (and late, or null): every check before anything is enqueued
@@ -497,7 +540,7 @@ int model_eps(dd_ctx* c, dd_model* m, const Chain& ch, const float* x_dev, const
     if (ag && m->cfg.num_classes <= 0) y_dev = nullptr;
     const dd_pag* pag = o.mods.pag;
     const Perturb pert = pag ? Perturb{B, o.mods.pag_mask(m)} : Perturb{};
-    if ((rc = run_model(m, ch, x_dev, o.t_vec, y_dev, g || pag ? 2 * B : B, s, o.ee, pert))) return rc;
+    if ((rc = run_model(m, ch, x_dev, o.t_vec, y_dev, g || pag ? 2 * B : B, s, o.ee, pert, o.cache))) return rc;
     if (g) { fa.pair_B = B; fa.guide_scale = g->scale; }
     if (pag) { fa.pair_B = B; fa.guide_scale = pag->scale; }
     return DD_OK;
@@ -642,6 +685,41 @@ int dd_forward_guided(dd_ctx* c, dd_model* m, const float* x_dev, float t, const
     const int64_t* y_run = nullptr;
     if ((rc = stage_guided(c, x_dev, y_dev, B, B, chw, g->null_label, s, &x_run, &y_run))) return rc;
     return forward_eps(c, m, whole_batch(c, m), x_run, y_run, eps_dev, B, s, {.t_set = &t, .mods = {.g = g}});
+}
+
+int dd_forward_cached(dd_ctx* c, dd_model* m, const float* x_dev, float t, const int64_t* y_dev, const dd_guidance* g, int blocks, int op,
+                      float w, float* eps_dev, int B, void* stream) {
+    if (c && m && m->ctx == c && m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, "block caching is not supported for early-exit models");
+    int rc = g ? check_guided(c, m, B, y_dev, g) : check_call(c, m, B, y_dev);
+    if (rc || (rc = check_cached(c, m, blocks))) return rc;
+    if (!x_dev || !eps_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    if (op < CACHE_REFRESH || op > CACHE_EXTRAPOLATE) return ctx_fail(c, DD_ERR_INVALID, "block caching: op outside {0, 1, 2}");
+    if (op == CACHE_EXTRAPOLATE && !std::isfinite(w)) return ctx_fail(c, DD_ERR_INVALID, "block caching: the extrapolation weight is not finite");
+    // the whole-batch chain's cache: a refresh always rotates (prev is then the refresh before the last one wherever two have run)
+    BlockCache& bc = m->cache[0];
+    const int rows = g ? 2 * B : B;
+    if (op != CACHE_REFRESH && !bc.holds(blocks, rows, 0, B))
+        return ctx_fail(c, DD_ERR_INVALID, "block caching: a reuse step, and the model holds no refresh of this batch and these blocks");
+    if (op == CACHE_EXTRAPOLATE && !bc.has_prev)
+        return ctx_fail(c, DD_ERR_INVALID, "block caching: an extrapolating reuse step, and the model holds no second refresh of this batch and these blocks");
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = ensure_block_cache(c, m, 0, s))) return rc;
+    const float* x_run = x_dev;
+    const int64_t* y_run = y_dev;
+    if (g) {
+        const size_t chw = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
+        float* xs = nullptr;
+        if ((rc = stage_guided(c, x_dev, y_dev, B, B, chw, g->null_label, s, &xs, &y_run))) return rc;
+        x_run = xs;
+    }
+    const CacheUse cu{blocks, op != CACHE_REFRESH, op == CACHE_REFRESH, op == CACHE_EXTRAPOLATE, w, nullptr};
+    rc = forward_eps(c, m, whole_batch(c, m), x_run, y_run, eps_dev, B, s, {.t_set = &t, .mods = {.g = g}, .cache = cu});
+    // the refresh counts once its forward is enqueued whole; one that failed on the way may have rotated or half-written the buffers: they hold nothing
+    if (op == CACHE_REFRESH) {
+        if (rc) bc.has_last = bc.has_prev = false;
+        else bc.refresh(blocks, rows, 0, B, true);
+    }
+    return rc;
 }
 
 int dd_forward_autoguided(dd_ctx* c, dd_model* m, const float* x_dev, float t, const int64_t* y_dev, const dd_autoguidance* g,

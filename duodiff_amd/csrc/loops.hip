@@ -91,10 +91,20 @@ struct Loop {
     // A walk (dd_sample_affine_walk): what each of the `steps` rows runs, in place of switch_at's rule -- null: none, and the loop enqueues
     // what it always has.  A jump row runs no model: with graphs it replays the context's captured jump of the chain (dd_ctx::jump_graph,
     // keyed like a step's graph), eagerly it is jump() itself.  ev[1] is recorded in front of the first late step.
-    const int* program = nullptr;                                                    // [steps] of STEP_FIRST / STEP_LATE / STEP_JUMP
+    const int* program = nullptr;                                                    // [steps] of STEP_FIRST / STEP_LATE / STEP_JUMP / STEP_*_REUSE
     std::function<int(const Chain&, const Slice&, hipStream_t)> jump = nullptr;      // one jump of one chain
+    // Block caching (dd_sample_affine_cached): a STEP_*_REUSE row runs the model's reuse step -- its second captured graph (GRAPH_AFFINE_REUSE),
+    // eagerly reuse() itself.  admit: called once the chains are decided and before the loop captures, stages or launches anything, with their
+    // number and chain 0's images; it walks the program over the models' cache validity and refuses the call or admits it (the caller makes
+    // the walk the models' validity once run_loop has enqueued the whole loop).
+    std::function<int(dd_model*, const Chain&, const Slice&, hipStream_t)> reuse = nullptr;
+    std::function<int(int chains, int B0, hipStream_t)> admit = nullptr;
 };
-enum { STEP_FIRST = 0, STEP_LATE = 1, STEP_JUMP = 2 };
+enum StepOp { STEP_FIRST = 0, STEP_LATE = 1, STEP_JUMP = 2, STEP_FIRST_REUSE = 3, STEP_LATE_REUSE = 4, STEP_OPS = 5 };
+// a model's full step, its reuse step, and back
+constexpr int reuse_of(int full) { return full == STEP_LATE ? STEP_LATE_REUSE : STEP_FIRST_REUSE; }
+constexpr bool is_reuse(int op) { return op == STEP_FIRST_REUSE || op == STEP_LATE_REUSE; }
+constexpr int full_of(int op) { return op == STEP_LATE_REUSE ? STEP_LATE : op == STEP_FIRST_REUSE ? STEP_FIRST : op; }
 
 // dd_sample, dd_sample_affine (both also guided) and dd_sample_early_exit: staging, the half-batch chains, graph capture and replay, timing
 int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
@@ -122,6 +132,7 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
     float* x_run = L.x_dev;
     const int64_t* y_run = L.y_dev;
     int rc = DD_OK;
+    if (L.admit && (rc = L.admit(chains, B0, s))) return rc;
     if (paired) rc = stage_guided(c, L.x_dev, L.y_dev, L.B, B0, chw, g ? g->null_label : -1, s, &x_run, &y_run);
     else if (L.use_graph) rc = stage_inputs(c, L.x_dev, L.y_dev, L.B, (size_t)L.B * chw, s, &x_run, &y_run);
     if (rc) return rc;
@@ -132,11 +143,14 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
         return sl;
     };
     auto chain = [&](dd_model* m, int k) { return Chain{&m->ws[k], c->st[k], cus, !chained}; };
-    bool uses[3] = {true, true, false};      // what the rows run: without a walk both models' graphs are captured up front, whoever runs
+    bool uses[STEP_OPS] = {true, true, false, false, false};      // what the rows run: without a walk both models' graphs are captured up front, whoever runs
     if (L.program) {
         uses[STEP_FIRST] = uses[STEP_LATE] = false;
         for (int k = 0; k < L.steps; ++k) uses[L.program[k]] = true;
-        if (L.late == L.first) uses[STEP_FIRST] = uses[STEP_LATE] = uses[STEP_FIRST] || uses[STEP_LATE];
+        if (L.late == L.first) {
+            uses[STEP_FIRST] = uses[STEP_LATE] = uses[STEP_FIRST] || uses[STEP_LATE];
+            uses[STEP_FIRST_REUSE] = uses[STEP_LATE_REUSE] = uses[STEP_FIRST_REUSE] || uses[STEP_LATE_REUSE];
+        }
     }
     if (L.use_graph) {
         for (int k = 0; k < chains; ++k) {
@@ -154,7 +168,8 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
                 if ((rc = capture_graph(c, c->jump_graph[k], c->jump_key[k], jkey, s, [&] { return L.jump(chain(L.first, k), sl, s); }))) return rc;
             }
             for (dd_model* m : {L.first, L.late}) {
-                if (!m || !uses[m == L.first ? STEP_FIRST : STEP_LATE]) continue;
+                const int full = m == L.first ? STEP_FIRST : STEP_LATE;
+                if (!m || !(uses[full] || uses[reuse_of(full)])) continue;
                 if (k && (rc = ensure_chain_ws(c, m, s))) return rc;
                 GraphKey mkey = key;
                 if (ag) {   // the step of the guide model itself is the unguided loop's step, under the unguided loop's key
@@ -164,7 +179,8 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
                         mkey.aguide = ag->guide; mkey.aserial = ag->guide->serial; mkey.gscale = __builtin_bit_cast(unsigned, ag->scale);
                     }
                 }
-                if ((rc = get_graph(c, m, L.kind, k, mkey, s, [&] { return L.step(m, chain(m, k), sl, s); }))) return rc;
+                if (uses[full] && (rc = get_graph(c, m, L.kind, k, mkey, s, [&] { return L.step(m, chain(m, k), sl, s); }))) return rc;
+                if (uses[reuse_of(full)] && (rc = get_graph(c, m, GRAPH_AFFINE_REUSE, k, mkey, s, [&] { return L.reuse(m, chain(m, k), sl, s); }))) return rc;
             }
         }
     }
@@ -178,8 +194,9 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
     dd_model* cur = L.first;
     bool split = false;                      // (a walk: ev[1] has been recorded)
     for (int k = 0; k < L.steps; ++k) {
+        bool reuse = false;                  // (block caching: the row runs cur's reuse step)
         if (L.program) {
-            const int op = L.program[k];
+            int op = L.program[k];
             if (op == STEP_JUMP) {
                 if (L.use_graph) {
                     DD_HIP(c, hipGraphLaunch(c->jump_graph[0], s));
@@ -189,6 +206,7 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
                 }
                 continue;
             }
+            if (is_reuse(op)) { reuse = true; op = full_of(op); }
             cur = op == STEP_LATE ? L.late : L.first;
             if (op == STEP_LATE && !split) {
                 DD_HIP(c, hipEventRecord(c->ev[1], s));
@@ -199,9 +217,10 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
             DD_HIP(c, hipEventRecord(c->ev[1], s));
         }
         if (L.use_graph) {
-            DD_HIP(c, hipGraphLaunch(cur->graph[L.kind][0], s));
-            if (chained) DD_HIP(c, hipGraphLaunch(cur->graph[L.kind][1], c->side));
-        } else if ((rc = L.step(cur, chain(cur, 0), slice(0), s))) {
+            const GraphKind kind = reuse ? GRAPH_AFFINE_REUSE : L.kind;
+            DD_HIP(c, hipGraphLaunch(cur->graph[kind][0], s));
+            if (chained) DD_HIP(c, hipGraphLaunch(cur->graph[kind][1], c->side));
+        } else if ((rc = reuse ? L.reuse(cur, chain(cur, 0), slice(0), s) : L.step(cur, chain(cur, 0), slice(0), s))) {
             return rc;
         }
     }
@@ -339,10 +358,12 @@ int upload_rows(dd_ctx* c, RowTable<Row>& t, size_t rows, hipStream_t s, F&& row
     return DD_OK;
 }
 // the step table of dd_sample_affine / dd_sample_multistep on the device: n rows + one more whose timestep the last step hands on (never used)
+// (bc, dd_sample_affine_cached: the row's cache op and the bits of its extrapolation weight in the two spare words)
 template <typename Args>
-int upload_atab(dd_ctx* c, const Args* a, hipStream_t s) {
-    return upload_rows(c, c->atab, (size_t)a->n_steps + 1, s, [a](size_t k) {
-        return k < (size_t)a->n_steps ? AffineRow{a->t[k], a->a[k], a->b[k], a->c[k], a->noise[k] ? 1 : 0, a->counter_base + (int)k, 0, 0}
+int upload_atab(dd_ctx* c, const Args* a, hipStream_t s, const dd_block_cache* bc = nullptr) {
+    return upload_rows(c, c->atab, (size_t)a->n_steps + 1, s, [a, bc](size_t k) {
+        return k < (size_t)a->n_steps ? AffineRow{a->t[k], a->a[k], a->b[k], a->c[k], a->noise[k] ? 1 : 0, a->counter_base + (int)k,
+                                                  bc ? bc->op[k] : 0, bc ? __builtin_bit_cast(int, bc->w[k]) : 0}
                                       : AffineRow{0.f, 0.f, 0.f, 0.f, 0, 0, 0, 0};
     });
 }
@@ -399,9 +420,11 @@ int sample_ddpm(dd_ctx* c, const dd_sample_args* a, Mods mo, void* stream) {
 // dd_sample_affine and its _guided, _autoguided and _region forms: one path
 // w (dd_sample_affine_walk; its own checks have passed): the rows' program -- a jump row runs launch_jump, a step row the model w->late names
 // (null: switch_after's rule)
-int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, Mods mo, void* stream, const dd_walk* w = nullptr) {
-    int rc = check_loop(c, a, mo, w ? "resampling jumps are not supported for early-exit models" : nullptr,
+// bc (dd_sample_affine_cached; its own checks have passed): block caching -- a row with op != 0 runs its model's reuse step
+int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, Mods mo, void* stream, const dd_walk* w = nullptr, const dd_block_cache* bc = nullptr) {
+    int rc = check_loop(c, a, mo, w ? "resampling jumps are not supported for early-exit models" : bc ? "block caching is not supported for early-exit models" : nullptr,
                         w ? "dd_sample_affine_walk generates noise on the device; for host noise drive dd_forward, dd_affine_step, dd_known_blend and dd_jump_step"
+                        : bc ? "dd_sample_affine_cached generates noise on the device; for host noise drive dd_forward_cached + dd_affine_step"
                           : "dd_sample_affine generates noise on the device; for host noise drive dd_forward + dd_affine_step",
                         [&] { return check_table(c, a); });
     if (rc) return rc;
@@ -415,8 +438,16 @@ int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, Mods mo, void* stre
         for (int k = 0; k < n; ++k)
             program[k] = w->jump[k] ? STEP_JUMP : (w->late ? w->late[k] != 0 : switching && k >= a->switch_after) ? STEP_LATE : STEP_FIRST;
     }
+    if (bc) {       // the rows' program, and the checks that need the models: K against every model that runs a step
+        program.resize((size_t)n);
+        for (int k = 0; k < n; ++k) {
+            const bool late = switching && k >= a->switch_after;
+            program[k] = bc->op[k] ? reuse_of(late ? STEP_LATE : STEP_FIRST) : late ? STEP_LATE : STEP_FIRST;
+            if ((rc = check_cached(c, late ? a->late : a->first, bc->blocks))) return rc;
+        }
+    }
     if ((rc = stage_image_seeds(c, a->noise_mode, s, &mo.seeds))) return rc;
-    if ((rc = upload_atab(c, a, s))) return rc;
+    if ((rc = upload_atab(c, a, s, bc))) return rc;
     if ((rc = stage_table_known(c, mo, a->first, a->B, n, s))) return rc;
     const AffineRow* atab = c->atab.dev.p;
     // (two half-batch chains, as dd_sample: both read the one step table; each has its own step index and Philox image offset)
@@ -427,6 +458,47 @@ int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, Mods mo, void* stre
     L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
         return enqueue_step(c, m, ch, sl.x, sl.y, sl.B, ss, {.mods = sl.mods, .noise_mode = a->noise_mode, .advance = 1, .atab = atab, .b0 = sl.b0});
     };
+    std::vector<std::pair<BlockCache*, BlockCache>> walked;      // (block caching: each cache the call runs on, and what the walk leaves in it)
+    if (bc) {
+        auto cached_step = [&, bc](bool reuse) {
+            // order 1: a refresh rotates prev <- last first, and a reuse goes through the kernel, which reads the row's op and w
+            const CacheUse cu{bc->blocks, reuse, !reuse && bc->order == 1, reuse && bc->order == 1, 0.f, reuse && bc->order == 1 ? atab : nullptr};
+            return [&, cu](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
+                return enqueue_step(c, m, ch, sl.x, sl.y, sl.B, ss,
+                                    {.mods = sl.mods, .cache = cu, .noise_mode = a->noise_mode, .advance = 1, .atab = atab, .b0 = sl.b0});
+            };
+        };
+        L.step = cached_step(false);
+        L.reuse = cached_step(true);
+        L.key = [&, bc](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.atab = atab; k.cblocks = bc->blocks; k.corder = bc->order; };
+        L.program = program.data();
+        // the program walked over the models' cache validity for the chains run_loop has decided on (Loop::admit): a reuse row needs a refresh of
+        // its model, chain geometry and K in front of it -- in this call or left by an earlier one -- and an extrapolating row two of them
+        L.admit = [&, bc](int chains, int B0, hipStream_t ss) -> int {
+            dd_model* models[2] = {a->first, switching ? a->late : nullptr};
+            BlockCache sim[2][2];
+            for (int ck = 0; ck < chains; ++ck) {
+                const int b0 = ck ? B0 : 0, Bk = ck ? a->B - B0 : B0, rows = mo.g ? 2 * Bk : Bk;
+                for (int i = 0; i < 2; ++i) if (models[i]) sim[ck][i] = models[i]->cache[ck];
+                for (int k = 0; k < n; ++k) {
+                    const int i = (full_of(program[k]) == STEP_LATE && models[1] != models[0]) ? 1 : 0;
+                    BlockCache& v = sim[ck][i];
+                    if (bc->op[k] == CACHE_REFRESH) { v.refresh(bc->blocks, rows, b0, Bk, bc->order == 1); continue; }
+                    if (!v.holds(bc->blocks, rows, b0, Bk))
+                        return ctx_fail(c, DD_ERR_INVALID, "block caching: row " + std::to_string(k) + " is a reuse step, and its model holds no refresh of this batch and these blocks");
+                    if (bc->op[k] == CACHE_EXTRAPOLATE && !v.has_prev)
+                        return ctx_fail(c, DD_ERR_INVALID, "block caching: row " + std::to_string(k) + " extrapolates, and its model holds no second refresh of this batch and these blocks");
+                }
+            }
+            for (int ck = 0; ck < chains; ++ck)
+                for (int i = 0; i < 2; ++i) {
+                    if (!models[i] || (i && models[1] == models[0])) continue;
+                    if (int r = ensure_block_cache(c, models[i], ck, ss)) { walked.clear(); return r; }
+                    walked.push_back({&models[i]->cache[ck], sim[ck][i]});
+                }
+            return DD_OK;
+        };
+    }
     if (w) {
         if (w->late) L.late = a->late;       // (the rows name their model; null where no row runs it: checked)
         L.switch_at = -1;
@@ -437,7 +509,14 @@ int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, Mods mo, void* stre
             return DD_OK;
         };
     }
-    return run_loop(c, L, s);
+    rc = run_loop(c, L, s);
+    // the walk becomes the models' validity once the whole loop is enqueued; a call that fails behind the walk (a capture, a copy, a launch) may
+    // have rotated or half-written the buffers, so they then hold nothing
+    for (auto& [d, v] : walked) {
+        if (rc) { d->has_last = d->has_prev = false; continue; }
+        d->K = v.K; d->rows = v.rows; d->b0 = v.b0; d->B = v.B; d->has_last = v.has_last; d->has_prev = v.has_prev;
+    }
+    return rc;
 }
 
 // dd_sample_affine_walk: its own checks, in front of the loop's (the table's pointers and n_steps are checked there: unreadable ones are left
@@ -459,6 +538,27 @@ int sample_affine_walk(dd_ctx* c, const dd_affine_sample_args* a, const dd_guida
     }
     if (g && ag) return ctx_fail(c, DD_ERR_INVALID, "classifier-free guidance and autoguidance are exclusive");
     return sample_affine(c, a, Mods{.g = g, .ag = ag, .kr = kr, .region = kr != nullptr}, stream, w);
+}
+
+// dd_sample_affine_cached: its own checks, in front of the loop's (the table's pointers and n_steps are checked there), then dd_sample_affine's
+// path with the cache.  What needs the models or the chains -- K against each model that runs a step, the walk over the cache validity -- is
+// checked on that path: K before anything is enqueued, the walk (Loop::admit) behind the copies of the table, the seeds and the known rows into
+// the context's staging buffers and in front of every capture, copy or launch that touches x, a workspace or a cache.
+int sample_affine_cached(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, const dd_known_region* kr, const dd_block_cache* bc,
+                         void* stream) {
+    if (!c) return DD_ERR_INVALID;
+    if (!bc || !bc->op || !bc->w) return ctx_fail(c, DD_ERR_INVALID, "null dd_block_cache / null op or w array");
+    if (!a) return DD_ERR_INVALID;
+    if (bc->order != 0 && bc->order != 1) return ctx_fail(c, DD_ERR_INVALID, "block caching: order outside {0, 1}");
+    if (a->n_steps >= 1 && a->n_steps <= (1 << 20)) {
+        for (int k = 0; k < a->n_steps; ++k) {
+            if (bc->op[k] < CACHE_REFRESH || bc->op[k] > CACHE_EXTRAPOLATE)
+                return ctx_fail(c, DD_ERR_INVALID, "block caching: op[" + std::to_string(k) + "] is outside {0, 1, 2}");
+            if (bc->op[k] == CACHE_EXTRAPOLATE && bc->order == 0)
+                return ctx_fail(c, DD_ERR_INVALID, "block caching: op[" + std::to_string(k) + "] extrapolates under order 0");
+        }
+    }
+    return sample_affine(c, a, Mods{.g = g, .kr = kr, .region = kr != nullptr}, stream, nullptr, bc);
 }
 
 // dd_sample_multistep and its forms: dd_sample_affine's loop with the history register.  h is staged like x: copied into the context's
@@ -705,6 +805,10 @@ int dd_sample_affine_region(dd_ctx* c, const dd_affine_sample_args* a, const dd_
 int dd_sample_affine_walk(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr,
                           const dd_walk* w, void* stream) {
     return sample_affine_walk(c, a, g, ag, kr, w, stream);
+}
+int dd_sample_affine_cached(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, const dd_known_region* kr, const dd_block_cache* bc,
+                            void* stream) {
+    return sample_affine_cached(c, a, g, kr, bc, stream);
 }
 int dd_sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, void* stream) { return sample_multistep(c, a, Mods{}, stream); }
 int dd_sample_multistep_guided(dd_ctx* c, const dd_multistep_sample_args* a, const dd_guidance* g, void* stream) {

@@ -324,6 +324,18 @@ int ensure_chain_ws(dd_ctx* c, dd_model* m, hipStream_t s) {
     a.bind(m->wsarena[1]);
     return DD_OK;
 }
+// (chain 1's is laid out for half of max_batch, as its workspace; zeroed on the launch stream for the reason above: the GEMMs read whole
+// tiles of rows, the rows past the batch's included)
+int ensure_block_cache(dd_ctx* c, dd_model* m, int chain, hipStream_t s) {
+    BlockCache& bc = m->cache[chain];
+    if (bc.last) return DD_OK;
+    const size_t bytes = (size_t)round_up((chain ? (m->cfg.max_batch + 1) / 2 : m->cfg.max_batch) * m->L, 256) * m->D * m->esize;
+    for (void** p : {&bc.last, &bc.prev, &bc.yhat}) {
+        DD_HIP(c, hipMalloc(p, bytes));
+        DD_HIP(c, hipMemsetAsync(*p, 0, bytes, s));
+    }
+    return DD_OK;
+}
 }  // namespace dd
 
 // ==========================================================================================
@@ -495,6 +507,8 @@ void dd_model_destroy(dd_model* m) {
         for (hipGraphExec_t g : kind) if (g) (void)hipGraphExecDestroy(g);
     for (hipEvent_t e : m->fc1_events) (void)hipEventDestroy(e);
     if (m->ee_ws) (void)hipFree(m->ee_ws);
+    for (BlockCache& bc : m->cache)
+        for (void* p : {bc.last, bc.prev, bc.yhat}) if (p) (void)hipFree(p);
     if (m->warena) (void)hipFree(m->warena);
     for (char* a : m->wsarena) if (a) (void)hipFree(a);
     delete m;

@@ -328,6 +328,18 @@ class Model:
                                                       _ptr(out), B, _stream_ptr(stream)))
         return out
 
+    def forward_cached(self, x, t, y=None, *, blocks, op, w=0.0, guidance=None, out=None, stream=None):
+        """eps = model(x, t, y) with block caching (dd_forward_cached), on the whole-batch chain's cache of this model.  blocks = K: the
+        deep blocks K .. depth - 1 - K.  op 0: a refresh -- the full forward, which stores the deep blocks' output (the stored one before it
+        becomes prev); op 1: a reuse -- the deep blocks do not run, the out-block behind them takes the stored output; op 2: a reuse on
+        last + w (last - prev).  guidance = (scale, null_label): classifier-free guidance, the cache then holds the 2 B rows."""
+        B = x.shape[0]
+        out = torch.empty_like(x) if out is None else out
+        g = C.byref(guidance_struct(guidance)) if guidance is not None else None
+        self.ctx.check(self.ctx.lib.dd_forward_cached(self.ctx.handle, self.handle, _ptr(x), float(t), _ptr(y), g, int(blocks), int(op),
+                                                      float(w), _ptr(out), B, _stream_ptr(stream)))
+        return out
+
     def forward_autoguided(self, x, t, y, guide, scale, out=None, stream=None):
         """Autoguided eps = eps_main + scale * (eps_main - eps_guide) at timestep t (dd_forward_autoguided): `guide` (a Model of the same
         image geometry) and this model run the same B rows; y is required iff either model is class-conditional, and each model takes it
@@ -461,6 +473,18 @@ def threshold_struct(threshold):
                              float(threshold.range), float(threshold.s_max))
 
 
+def _known_region(region, x, n_steps):
+    """A KnownRegion as the loops' entries take it: the checks of its tensors against x and of its n_steps (ka, kb) rows, a byref of the
+    dd_known_region, and the row arrays, which must outlive the call (a byref keeps its struct alive)."""
+    B, Cc, S, _ = x.shape
+    for v, shape in ((region.x0, (B, Cc, S, S)), (region.mask, (B, 1, S, S))):
+        assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and tuple(v.shape) == shape
+    ka, kb = keep = [np.ascontiguousarray(v, np.float32) for v in (region.ka, region.kb)]
+    assert ka.shape == kb.shape == (n_steps,)
+    kr = L.dd_known_region(region.x0.data_ptr(), region.mask.data_ptr(), *(v.ctypes.data_as(C.POINTER(C.c_float)) for v in keep))
+    return C.byref(kr), keep
+
+
 def _loop_call(ctx, args, plain, guidance, region, x, threshold=None):
     """The loop entry of this argument struct as call(stream): `plain` (guidance None), its _guided form (guidance = (scale, null_label):
     classifier-free), its _autoguided form (guidance = Autoguidance(guide, scale)) or, with a KnownRegion, its _region form, which
@@ -484,14 +508,8 @@ def _loop_call(ctx, args, plain, guidance, region, x, threshold=None):
         keep = None
         name, extra = plain + "_threshold", [g, ag, None, C.byref(threshold_struct(threshold))]
     else:
-        B, Cc, S, _ = x.shape
-        n_steps = args.n_steps if hasattr(args, "n_steps") else args.t_start - args.t_end + 1
-        for v, shape in ((region.x0, (B, Cc, S, S)), (region.mask, (B, 1, S, S))):
-            assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and tuple(v.shape) == shape
-        keep = ka, kb = [np.ascontiguousarray(v, np.float32) for v in (region.ka, region.kb)]
-        assert ka.shape == kb.shape == (n_steps,)
-        kr = L.dd_known_region(region.x0.data_ptr(), region.mask.data_ptr(), *(v.ctypes.data_as(C.POINTER(C.c_float)) for v in keep))
-        name, extra = plain + "_region", [g, ag, C.byref(kr)]
+        kr, keep = _known_region(region, x, args.n_steps if hasattr(args, "n_steps") else args.t_start - args.t_end + 1)
+        name, extra = plain + "_region", [g, ag, kr]
         if threshold is not None:
             name, extra = plain + "_threshold", extra + [C.byref(threshold_struct(threshold))]
     fn = getattr(ctx.lib, name)
@@ -611,15 +629,36 @@ def sample_affine_walk_loop(ctx: Context, first: Model, late, x, rows, *, region
     elif guidance is not None:
         g = C.byref(guidance_struct(guidance))
     if region is not None:
-        B, Cc, S, _ = x.shape
-        for v, shape in ((region.x0, (B, Cc, S, S)), (region.mask, (B, 1, S, S))):
-            assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and tuple(v.shape) == shape
-        ka, kb = keep = [np.ascontiguousarray(v, np.float32) for v in (region.ka, region.kb)]
-        assert ka.shape == kb.shape == (n,)
-        kr = C.byref(L.dd_known_region(region.x0.data_ptr(), region.mask.data_ptr(), *(v.ctypes.data_as(C.POINTER(C.c_float)) for v in keep)))
+        kr, keep = _known_region(region, x, n)
         prog = prog + keep
     # (a byref keeps its struct alive, the closure the arrays)
     call = lambda st, keep=(tab, prog): ctx.lib.dd_sample_affine_walk(ctx.handle, C.byref(args), g, ag, kr, C.byref(walk), st)
+    return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
+
+
+def sample_affine_cached_loop(ctx: Context, first: Model, late, x, rows, *, blocks, order=0, region=None, guidance=None, switch_after=None,
+                              y=None, seed=0, counter_base=0, noise="philox", use_graph=True, stream=None):
+    """dd_sample_affine_cached: sample_affine_loop with block caching, in place on x.  rows: a dict with t, a, b, c, noise, cache and cw (a
+    cached plan's rows, step_plan.step_plan(..., cache_blocks= ...), or any slice of them): row k with cache[k] == 0 is a refresh step of
+    its model (the full forward, which stores the output of the deep blocks `blocks` .. depth - 1 - blocks), with cache[k] == 1 a reuse
+    step (those blocks do not run) and with cache[k] == 2 (order 1 only) a reuse step on the extrapolation last + cw[k] (last - prev).
+    What a model's cache holds outlives the call: a loop cut at any row continues where the uncut loop would.  region: a KnownRegion
+    with one (ka, kb) per row; guidance: (scale, null_label), classifier-free, or None."""
+    if guidance is not None and (isinstance(guidance, (Perturbed, Autoguidance)) or len(guidance) != 2):
+        raise ValueError("block caching combines with classifier-free guidance only")
+    args = L.dd_affine_sample_args()
+    tab = _step_table(args, first, late, rows, "tabc", ("noise",), switch_after, counter_base)
+    n = args.n_steps
+    keep = [np.ascontiguousarray(rows["cache"], np.int32), np.ascontiguousarray(rows["cw"], np.float32)]
+    assert all(v.shape == (n,) for v in keep)
+    bc = L.dd_block_cache(int(blocks), int(order), keep[0].ctypes.data_as(C.POINTER(C.c_int32)), keep[1].ctypes.data_as(C.POINTER(C.c_float)))
+    g = C.byref(guidance_struct(guidance)) if guidance is not None else None
+    kr = None
+    if region is not None:
+        kr, kab = _known_region(region, x, n)
+        keep = keep + kab
+    # (a byref keeps its struct alive, the closure the arrays)
+    call = lambda st, keep=(tab, keep): ctx.lib.dd_sample_affine_cached(ctx.handle, C.byref(args), g, kr, C.byref(bc), st)
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
 

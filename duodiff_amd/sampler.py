@@ -37,6 +37,11 @@ RePaint's schedule (Lugmayr et al. 2022): every 10 grid steps x is noised back u
 the generated region of an inpainting run (``--known_image``) can agree with the known one; ``--restart T_MIN T_MAX K`` (repeatable) is
 Restart sampling (Xu et al. 2023): K returns from the level T_MIN up to T_MAX.  A jump runs no model; the whole walk is one device loop.
 
+Block caching (engine option, not in the reference; DeepCache, Ma et al. 2024): ``--cache_blocks 2 --cache_interval 3`` runs the full
+backbone on every third step of a model only; the steps between run its two outermost blocks on either side and feed the long skip
+path the deep blocks' output of the last full step (``--cache_order 1``: a linear extrapolation of the last two, TaylorSeer).  DDPM and
+DDIM loops, with classifier-free guidance, a known region, an init image, image seeds and a late model; training-free, on any checkpoint.
+
 DPM-Solver++ (engine option, not in the reference): ``--dpm_solver ode --dpm_solver_steps 20`` samples with the second-order multistep
 solver (``sde``: its SDE variant) in 20 model evaluations; the table-driven loop with one history register per image.
 """
@@ -55,12 +60,12 @@ import torch
 from .config import ModelParams, load_config
 from .autoencoder import get_autoencoder
 from .engine import (Autoguidance, Context, KnownRegion, Perturbed, X0Threshold, layer_mask, sample_affine_loop, sample_affine_region_loop,
-                     sample_affine_walk_loop, sample_loop,
+                     sample_affine_cached_loop, sample_affine_walk_loop, sample_loop,
                      sample_multistep_loop, sample_multistep_region_loop, sample_multistep_threshold_loop, sample_region_loop,
                      schedule_tables, threshold_struct)
 from .step_plan import (MULTISTEP_KINDS, StepPlan, _affine_rows, _data_prediction, _f32, _segments, affine_coefficients, known_rows,  # noqa: F401
                         jump_coefficients, multistep_coefficients, multistep_grid, multistep_rows, repaint_jumps, restart_jumps, start_timestep,
-                        step_plan, unfolded_coefficients, unfolded_rows, walk_moves)
+                        cache_rows, step_plan, unfolded_coefficients, unfolded_rows, cache_settings, walk_moves)
 from .uvit import UViT
 
 
@@ -143,7 +148,8 @@ def backbone_rows(batch_size, cfg_scale=None, pag=None):
 
 
 def _resolve_options(model, late_model, batch_size, image_shape, plan_args, noise, y, autoencoder, cfg_scale, cfg_null_label,
-                     autoguidance_scale, guide_model, pag, image_seeds, init_image, strength, known_image, known_mask, threshold, walk=False):
+                     autoguidance_scale, guide_model, pag, image_seeds, init_image, strength, known_image, known_mask, threshold, walk=False,
+                     cache=None):
     """get_samples' one options check, before any engine call: every ValueError it raises, in a fixed order.  Returns the StepPlan of
     plan_args; the run's ONE guidance, which the device loops take and the host step picks its forward call by -- None, (scale, null_label),
     Autoguidance(the guide's UViT, scale) or Perturbed(scale, mask_first, mask_late); the seeds as ints; the init image and KnownRegion."""
@@ -181,6 +187,12 @@ def _resolve_options(model, late_model, batch_size, image_shape, plan_args, nois
             raise ValueError("perturbed-attention guidance does not combine with resampling jumps (resample_jump / restart)")
         if any(hasattr(m, "classifier_type") for m in (model, late_model) if m is not None):
             raise ValueError("resampling jumps are not supported for early-exit models")
+    if cache is not None:
+        if pag is not None or autoguidance_scale is not None:
+            raise ValueError("block caching does not combine with perturbed-attention guidance or autoguidance")
+        if any(hasattr(m, "classifier_type") for m in (model, late_model) if m is not None):
+            raise ValueError("block caching is not supported for early-exit models")
+        cache_settings(*cache, depths=[m.depth for m in (model, late_model) if m is not None])
     if (init_image is None) != (strength is None):
         raise ValueError("init_image and strength go together")
     if (known_image is None) != (known_mask is None):
@@ -221,7 +233,7 @@ def _start(ctx, device, batch_size, image_shape, seed, image_seeds, init, t0):
 
 
 # what a segment of get_samples works on: the models, x and the solver's history h (updated in place), the host step's eps buffer, the options
-_Run = namedtuple("_Run", "ctx plan first late x h eps y guidance threshold region seed use_graph image_seeds")
+_Run = namedtuple("_Run", "ctx plan first late x h eps y guidance threshold region seed use_graph image_seeds cache", defaults=(None,))
 
 
 def _segment_models(plan, k0, k1, first, late):
@@ -244,6 +256,9 @@ def _device_segment(run, k0, k1):
     with ctx.image_seeds(run.image_seeds) if run.image_seeds is not None else contextlib.nullcontext():   # (set around the segment's call)
         if plan.moves:              # a walk: the rows name their model, and a jump row runs none
             sample_affine_walk_loop(ctx, run.first, run.late, x, seg, region=known[0] if known else None, counter_base=k0, **kw)
+        elif run.cache is not None:  # block caching: the rows name refresh and reuse steps; the models' caches carry over the cuts
+            sample_affine_cached_loop(ctx, m0, m1, x, seg, blocks=run.cache[0], order=run.cache[2], region=known[0] if known else None,
+                                      switch_after=sw, counter_base=k0, **kw)
         elif plan.kind == "ddpm":   # dd_sample: the late model unless the segment starts on it; t_switch counted from t = 999, not from t[0]
             (sample_region_loop if known else sample_loop)(
                 ctx, m0, None if sw == 0 else run.late, x, *known, t_switch=plan.switch_after + 999 - int(tab["t"][0]) if sw else 0,
@@ -273,7 +288,9 @@ def _host_step(run, k, k1=None):
     if plan.kind == "ddpm" and (g is None or auto and g.guide is cur):      # :130-133, fused; the guide's own steps: unguided, y only if it takes one
         cur.sample_step(x, int(t), y=y if not auto or cur.mp.num_classes > 0 else None, z=z, noise="buffer")
     else:
-        if g is None:
+        if run.cache is not None:
+            cur.forward_cached(x, float(t), y, blocks=run.cache[0], op=tab["cache"][k], w=tab["cw"][k], guidance=g, out=eps)
+        elif g is None:
             cur.forward(x, float(t), y, out=eps)
         elif auto:
             cur.forward_autoguided(x, float(t), y, g.guide, g.scale, out=eps)
@@ -300,7 +317,7 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
                 num_steps: int = 1000, return_device_tensor: bool = False, cfg_scale=None, cfg_null_label: int = 1000,
                 solver=None, solver_steps: int = 20, solver_order: int = 2, autoguidance_scale=None, guide_model=None,
                 init_image=None, strength=None, known_image=None, known_mask=None, threshold=None, pag=None, image_seeds=None,
-                resample_jump=None, resample_count=None, restart=None):
+                resample_jump=None, resample_count=None, restart=None, cache=None):
     """reference sampler.py:82-155.  Returns (samples[B,H,W,C] float32 numpy = (x+1)/2, intermediates).
 
     cfg_scale (None: the unguided loops, unchanged): classifier-free guidance of every step's model output,
@@ -346,14 +363,23 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
         forward, x <- ja x + jc z3, and runs no model.  With or without a known region, guidance, image seeds and strength; not with a
         solver, a threshold or pag.  noise="device": one device loop per segment, z3 from the device generator; noise="torch_cpu": step by
         step, a jump's z3 drawn from the torch CPU stream in walk order.  Saves: after the last visit of a saved timestep.
+    cache = (K, N, order) (None: every step runs every block, unchanged; engine option; DeepCache): block caching.  Of a model of depth
+        2 h + 1 the deep blocks are K .. depth - 1 - K, 1 <= K <= h.  Counted from a model's first step, every N-th step is a refresh: the
+        full forward, which stores the deep blocks' output.  The steps between are reuse steps: blocks 0 .. K - 1, then the out-block
+        behind the deep range with the stored output (order 0) or with last + w (last - prev), w = (t_1 - t_k) / (t_0 - t_1) from the last
+        two refreshes' timesteps (order 1), then on through the head.  The late model starts with a refresh at the switch.  DDPM and DDIM
+        loops (the plan is of kind "affine": DDPM on predict_noise runs as table rows); with cfg_scale (the cache holds the 2 B rows), a
+        known region, an init image, image seeds and a late model; not with a solver, a threshold, resampling jumps, pag, autoguidance
+        or early-exit models.  noise="device": dd_sample_affine_cached; noise="torch_cpu": forward_cached step by step.
     """
     image_shape = (num_channels, sample_height, sample_width)
     plan_args = (_PARAMETRIZATIONS.get(postprocessing), timesteps_save, late_model is not None, t_switch, num_steps, use_ddim, ddim_steps,
-                 ddim_eta, solver, solver_steps, solver_order, strength, threshold, resample_jump, resample_count, restart)
+                 ddim_eta, solver, solver_steps, solver_order, strength, threshold, resample_jump, resample_count, restart,
+                 *(cache if cache is not None else ()))
     plan, guidance, image_seeds, init, region = _resolve_options(
         model, late_model, batch_size, image_shape, plan_args, noise, y, autoencoder, cfg_scale, cfg_null_label, autoguidance_scale,
         guide_model, pag, image_seeds, init_image, strength, known_image, known_mask, threshold,
-        walk=resample_jump is not None or resample_count is not None or bool(restart))
+        walk=resample_jump is not None or resample_count is not None or bool(restart), cache=cache)
     rows = backbone_rows(batch_size, cfg_scale, pag)
     y = None if y is None else torch.as_tensor(y).to(model.device, torch.int64).contiguous()
     first, late = model.engine_model(rows), late_model.engine_model(rows) if late_model is not None else None
@@ -364,7 +390,8 @@ def get_samples(model, batch_size: int, postprocessing: callable, seed: int, num
         guidance = guidance._replace(guide=first if g is model else late if g is late_model else g.engine_model(rows))
     h = torch.zeros_like(x) if plan.kind == "multistep" else None          # the solver's history, carried across save points
     device = noise == "device"
-    run = _Run(ctx, plan, first, late, x, h, None if device else torch.empty_like(x), y, guidance, threshold, region, seed, use_graph, image_seeds)
+    run = _Run(ctx, plan, first, late, x, h, None if device else torch.empty_like(x), y, guidance, threshold, region, seed, use_graph, image_seeds,
+               cache)
     intermediate = []                                                        # (on the host every step is a segment of its own)
     for k0, k1 in _segments(plan.save_after) if device else ((k, k + 1) for k in range(len(plan.save_after))):
         (_device_segment if device else _host_step)(run, k0, k1)
@@ -640,6 +667,21 @@ def validate_resample(args):
     return kw
 
 
+def validate_cache(args, config, config_late=None):
+    """The block-caching options (--cache_blocks, --cache_interval, --cache_order), before any GPU work: ValueError on a bad combination.
+    Returns get_samples' cache argument, (K, N, order) or None."""
+    if args.cache_blocks is None:
+        if args.cache_interval is not None or args.cache_order is not None:
+            raise ValueError("--cache_interval / --cache_order need --cache_blocks")
+        return None
+    for name in ("dpm_solver", "clip_x0", "dynamic_threshold", "resample_jump", "restart", "pag_scale", "autoguidance_scale"):
+        if getattr(args, name, None) is not None:
+            raise ValueError(f"--cache_blocks and --{name} are exclusive")
+    depths = [ModelParams.from_dict(c).depth for c in (config, config_late) if c is not None]
+    return cache_settings(args.cache_blocks, 3 if args.cache_interval is None else args.cache_interval,
+                          0 if args.cache_order is None else args.cache_order, depths=depths)
+
+
 def solver_kwargs(args):
     """get_samples' solver arguments from the command line"""
     return dict(solver=SOLVERS[args.dpm_solver] if args.dpm_solver is not None else None, solver_steps=args.dpm_solver_steps,
@@ -800,6 +842,13 @@ def get_args(argv=None):
                    help="(engine option, repeatable) Restart sampling: having come down to the timestep T_MIN the loop goes back up to T_MAX "
                         "with fresh noise and comes down again, K times; intervals snap to the grid and must not overlap.  Exclusive with "
                         "--resample_jump")
+    p.add_argument("--cache_blocks", type=int, default=None, metavar="K",
+                   help="(engine option) block caching (DeepCache): only every N-th step of a model runs its deep blocks K .. depth - 1 - K; "
+                        "the steps between reuse their stored output.  1 <= K <= depth // 2 of every model.  DDPM and DDIM loops")
+    p.add_argument("--cache_interval", type=int, default=None, metavar="N",
+                   help="(engine option) with --cache_blocks: a full step every N steps of a model (default 3; 1: every step)")
+    p.add_argument("--cache_order", type=int, choices=[0, 1], default=None,
+                   help="(engine option) with --cache_blocks: 0 (default) reuses the stored output, 1 extrapolates the last two linearly in t")
     add_image_seed_args(p)
     return p.parse_args(argv)
 
@@ -843,6 +892,7 @@ def setup_run(args):
     threshold = validate_threshold(args, config_last)
     pag = validate_pag(args, config, config_late)
     resample = validate_resample(args)
+    cache = validate_cache(args, config, config_late)
     rows = backbone_rows(args.batch_size, args.cfg_scale, pag)
     model, mp = build_model(config, args.checkpoint_path, args.precision, rows)
     late = build_model(config_late, args.checkpoint_path_late, args.precision, rows)[0] if config_late is not None else None
@@ -857,7 +907,7 @@ def setup_run(args):
         sample_width=mp.img_size, use_ddim=args.use_ddim, ddim_steps=args.ddim_steps, ddim_eta=args.ddim_eta, autoencoder=autoencoder,
         late_model=late, t_switch=args.t_switch, noise=args.noise, use_graph=not args.no_graph, cfg_scale=args.cfg_scale,
         cfg_null_label=args.cfg_null_label, **solver_kwargs(args), autoguidance_scale=args.autoguidance_scale, guide_model=guide,
-        threshold=threshold, pag=pag, **resample, **region_kwargs))
+        threshold=threshold, pag=pag, cache=cache, **resample, **region_kwargs))
 
 
 def main(argv=None):

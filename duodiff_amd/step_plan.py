@@ -195,7 +195,9 @@ class StepPlan(NamedTuple):
     lands[k]: the timestep whose noise level x has after step k, -1 for the final image (known_rows).
     moves: the walk of a plan with resampling jumps (walk_moves; empty: none).  Such a plan is of kind "affine", has one row per move
     and two more int32 rows, jump (1: the row is a jump, x' = a x + c z3, no model) and late (1: the step runs the late model);
-    its switch_after is None."""
+    its switch_after is None.
+    A plan with block caching (step_plan(..., cache_blocks= ...), cache_rows) is of kind "affine" and has two more rows, cache (int32: 0 the
+    step refreshes its model's cache, 1 it reuses it, 2 it reuses an extrapolation of it) and cw (float32: the extrapolation weight)."""
     kind: str
     rows: dict
     save_after: list
@@ -329,9 +331,51 @@ def _walk_plan(base, parametrization, moves, timesteps_save):
     return StepPlan("affine", rows, save_after, None, tuple(lands), tuple(moves))
 
 
+def cache_settings(cache_blocks, cache_interval=3, cache_order=0, depths=()):
+    """The checks of block caching's three numbers, before any model is built: K = cache_blocks >= 1 (and at most depth // 2 of every
+    depth given), the refresh interval N >= 1, the order 0 or 1.  Returns (K, N, order) as ints."""
+    try:
+        k, n, order = int(cache_blocks), int(cache_interval), int(cache_order)
+    except (TypeError, ValueError):
+        raise ValueError(f"block caching takes integers (blocks, interval, order), not {(cache_blocks, cache_interval, cache_order)!r}") from None
+    if k < 1:
+        raise ValueError(f"cache_blocks must be at least 1, not {k}")
+    if n < 1:
+        raise ValueError(f"cache_interval must be at least 1, not {n}")
+    if order not in (0, 1):
+        raise ValueError(f"cache_order must be 0 or 1, not {order}")
+    for depth in depths:
+        if k > int(depth) // 2:
+            raise ValueError(f"cache_blocks = {k} exceeds depth // 2 = {int(depth) // 2} of a model of depth {int(depth)}")
+    return k, n, order
+
+
+def cache_rows(t, switch_after, interval, order):
+    """The block-caching rows of a plan whose steps see the model timesteps t, the late model from step switch_after on (None: never).
+    Per model, j counts its steps from its first one (the late model starts again at 0 at the switch); step j refreshes iff
+    j % interval == 0.  cache[k]: 0 a refresh, 1 a reuse, 2 (order 1) a reuse with extrapolation, where its model has refreshed twice:
+    cw[k] = (t_1 - t_k) / (t_0 - t_1) with t_1 the last refresh's timestep and t_0 the one before it, in float64, rounded once.  A
+    reuse step in front of a model's second refresh is a 1 under either order.  Returns (cache int32, cw float32)."""
+    t = np.asarray(t, np.float64)
+    n = len(t)
+    cache, cw = np.zeros(n, np.int32), np.zeros(n, np.float32)
+    first = 0
+    t0 = t1 = None
+    for k in range(n):
+        if switch_after is not None and k == switch_after:
+            first, t0, t1 = k, None, None
+        if (k - first) % interval == 0:
+            t0, t1 = t1, t[k]
+        elif order == 1 and t0 is not None:
+            cache[k], cw[k] = 2, np.float32((t1 - t[k]) / (t0 - t1))
+        else:
+            cache[k] = 1
+    return cache, cw
+
+
 def step_plan(parametrization, timesteps_save=(), has_late=False, t_switch=np.inf, num_steps=1000, use_ddim=False, ddim_steps=50,
               ddim_eta=0.0, solver=None, solver_steps=20, solver_order=2, strength=None, threshold=None, resample_jump=None,
-              resample_count=None, restart=None):
+              resample_count=None, restart=None, cache_blocks=None, cache_interval=3, cache_order=0):
     """The StepPlan of get_samples' arguments (parametrization: "predict_noise" | "predict_original" | "predict_previous", or None
     for a postprocessing function of elsewhere; has_late: a late model is given).  Host arithmetic only, no torch.
     strength (None or 1: the start at t = 999): the loops start at t0 = start_timestep(strength) -- DDPM at t0, the DDIM and solver grids
@@ -341,8 +385,28 @@ def step_plan(parametrization, timesteps_save=(), has_late=False, t_switch=np.in
     resample_jump = j with resample_count = r (RePaint's schedule, repaint_jumps) or restart = [(t_min, t_max, K), ...] (Restart
     sampling, restart_jumps): the plan of a walk over the grid of the plan without them (walk_moves, _walk_plan) -- kind "affine" for
     DDPM and DDIM alike.  Not with DPM-Solver++ (its history would have to restart behind a jump) or x0 thresholding, and not both
-    at once; r == 1, or a j too long for any jump, gives the plan without them."""
+    at once; r == 1, or a j too long for any jump, gives the plan without them.
+    cache_blocks = K (None: no caching) with cache_interval = N and cache_order: the plan with block caching -- kind "affine" for DDPM
+    (predict_noise takes the affine rows a walk plan takes, so an N = 1 run is not promised bit-equal to the "ddpm"-kind loop) and DDIM,
+    with the rows of cache_rows.  Not with DPM-Solver++, x0 thresholding, resampling jumps or parametrization None."""
     walk = resample_jump is not None or resample_count is not None or bool(restart)
+    if cache_blocks is not None:
+        _, interval, order = cache_settings(cache_blocks, cache_interval, cache_order)
+        if solver is not None:
+            raise ValueError("block caching is not supported with DPM-Solver++")
+        if threshold is not None:
+            raise ValueError("block caching is not supported with x0 thresholding")
+        if walk:
+            raise ValueError("block caching is not supported with resampling jumps")
+        if parametrization is None:
+            raise ValueError("block caching needs one of this module's predict_*_postprocessing functions")
+        base = step_plan(parametrization, timesteps_save, has_late, t_switch, num_steps, use_ddim, ddim_steps, ddim_eta, strength=strength)
+        rows = dict(base.rows)
+        if base.kind == "ddpm":
+            ts = [int(t) for t in rows["t"]]
+            rows = _affine_rows(ts, [affine_coefficients(parametrization, t) for t in ts], list(rows["noise"]))
+        rows["cache"], rows["cw"] = cache_rows(rows["t"], base.switch_after, interval, order)
+        return base._replace(kind="affine", rows=rows)
     if walk:
         if (resample_jump is None) != (resample_count is None):
             raise ValueError("resample_jump and resample_count go together")

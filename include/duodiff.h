@@ -399,6 +399,43 @@ int dd_jump_step(dd_ctx* ctx, const float* x_dev, const float* z_dev, float ja, 
 int dd_sample_affine_walk(dd_ctx* ctx, const dd_affine_sample_args* args, const dd_guidance* g, const dd_autoguidance* ag,
                           const dd_known_region* kr, const dd_walk* walk, void* stream);
 
+/* ---- block caching: the deep blocks' output reused across sampling steps (DeepCache, Ma et al. 2024; order 1: TaylorSeer) ---------- */
+/* A U-ViT of depth nb = 2 h + 1 runs blocks 0 .. nb - 1 in forward order (in-blocks, mid, out-blocks).  With 1 <= K = blocks <= h the DEEP
+ * blocks are K .. nb - 1 - K; y_deep, the output of block nb - 1 - K, is the x operand of out-block nb - K's skip_linear, whose long-skip
+ * operand is block K - 1's output.  A REFRESH step (op 0) is the full forward and stores y_deep in the model's cache: [rows L, D] of the
+ * activation type (bf16 / fp32 by precision), one per chain; with order 1 the cache's `last` becomes `prev` first.  A REUSE step runs embed,
+ * blocks 0 .. K - 1, then out-block nb - K with y^ for its x operand and on through the head:
+ *     op 1:  y^ = last
+ *     op 2:  y^ = last + w * (last - prev)      in fp32 as d = last - prev; y^ = last + w * d, contraction off, rounded once to the activation type
+ * A row without a prev is an op-1 row: chosen by the op, never by w = 0 (0 * NaN is NaN).  The host computes op and w per step
+ * (duodiff_amd.step_plan: refresh every N-th step of a model, w = (t_1 - t_k) / (t_0 - t_1) from the last two refreshes' timesteps).
+ * The engine keeps, per model and chain, what its cache holds: K, the backbone rows, the chain's first image and size, and whether prev is
+ * set.  That state outlives a call, so a loop cut into several calls continues where the uncut loop would; every other entry point leaves
+ * the cache alone. */
+typedef struct dd_block_cache {
+    int32_t blocks;         /* K */
+    int32_t order;          /* 0: op 2 is not allowed; 1: a refresh rotates prev <- last, a reuse step may extrapolate */
+    const int32_t* op;      /* host [n_steps]: 0 refresh, 1 reuse, 2 reuse with extrapolation */
+    const float* w;         /* host [n_steps]: the extrapolation weight of an op-2 row (other rows: not read by the update) */
+} dd_block_cache;
+/* One forward on the whole-batch chain's cache (host-noise loops, parity): eps at timestep t under op (0, 1, 2) and w; g: classifier-free
+ * guidance or NULL (the cache then holds the 2 B rows).  A refresh here always rotates prev <- last first. */
+int dd_forward_cached(dd_ctx* ctx, dd_model* m, const float* x_dev, float t, const int64_t* y_dev, const dd_guidance* g, int32_t blocks,
+                      int32_t op, float w, float* eps_dev, int B, void* stream);
+/* dd_sample_affine[_guided | _region] with block caching: g and kr are optional (NULL).  Everything that loop stages is staged as there
+ * (per-image seeds, two half-batch chains, graph replay or eager launches, counter_base); each model replays a second captured graph for
+ * its reuse step, and the graphs are keyed on K and order.
+ * DD_ERR_INVALID before anything is enqueued when cache or one of its arrays is NULL, blocks is outside [1, depth / 2] of a model that runs
+ * a step, order is outside {0, 1}, an op is outside {0, 1, 2}, an op is 2 under order 0, a model carries early-exit heads, the noise mode
+ * is host noise (drive dd_forward_cached + dd_affine_step), or a check of dd_sample_affine's own fails.  DD_ERR_INVALID as well when a
+ * reuse row finds no refresh of its model, chain geometry and K in front of it (in this call or left by an earlier one), or an op-2 row
+ * no second one: that check needs the chains, so the step table, the per-image seeds and the known rows have by then been copied to the
+ * context's own staging buffers; the caller's tensors, the workspaces and the caches are untouched and no graph is captured.
+ * What the caches hold changes once the whole loop is enqueued (dd_forward_cached: the refresh's forward).  A call that fails later than
+ * these checks leaves the caches it ran on holding nothing: a reuse row on them is refused until they are refreshed. */
+int dd_sample_affine_cached(dd_ctx* ctx, const dd_affine_sample_args* args, const dd_guidance* g, const dd_known_region* kr,
+                            const dd_block_cache* cache, void* stream);
+
 /* ---- x0 clipping and dynamic thresholding (Ho et al. 2020; Saharia et al. 2022, Imagen; Lu et al. 2022) of the multistep loop ---------- */
 /* The multistep row's data prediction x0 = p*x + q*m (its history expression) is pulled back before it drives the update, and the update
  * takes the result xh in m's place: the rows a, b are UNFOLDED (b multiplies xh, not m; duodiff_amd.sampler multistep_coefficients(...,

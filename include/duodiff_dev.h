@@ -173,6 +173,15 @@ int dd_dev_attention(dd_ctx* ctx, int precision, int B, int L, int H, const floa
 int dd_dev_layernorm(dd_ctx* ctx, int precision, int rows, int D, const float* x_host, const float* gamma_beta, void* out_host,
                      unsigned short* frag_host, int tok_l, int tok_e, int iters, void* stream, float* ms_out);
 
+/* Development harness for the block cache's kernel (cache.hip cache_extrapolate_kernel<T> through launch_cache_extrapolate; include/duodiff.h
+ * dd_block_cache): out = last + w (last - prev) on host rows last_host, prev_host [rows, D] of the activation type (bf16 bits / fp32 by
+ * precision), D % 64 == 0.  op 2 extrapolates; op 0 / 1 copy last, and prev's device copy is then never read.  table != 0: the launch's
+ * production form -- the op and w travel in row 1 of a device step table (AffineRow::pad1, pad2) whose other rows hold 0xFF bytes, the step state
+ * names that row, and the launch's own op / w arguments are -1 / NaN; table == 0: they are the launch's arguments.  out_host [rows + 8, D] is
+ * filled with 0xFF bytes before the launch and comes back WHOLE.  out aliases neither input.  `iters` timed launches -> ms_out. */
+int dd_dev_cache_extrapolate(dd_ctx* ctx, int precision, int rows, int D, const void* last_host, const void* prev_host, int op, float w,
+                             int table, void* out_host, int iters, void* stream, float* ms_out);
+
 /* Development harness for token assembly (rowops.hip embed_kernel / embed_mfma_kernel through launch_embed; reference models/uvit.py:352-365):
  * rows of every image = [label_emb[y],] time sinusoid, (S / P)^2 patch tokens, + pos; L = extras + (S / P)^2, extras = 1 (time) or 2 (label + time).
  * x_img [B, C, S, S], w [D, C, P, P] (transposed here as finalize does), bias [D], pos [L, D], label_emb [num_classes, D] + y [B] (extras == 2),

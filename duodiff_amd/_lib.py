@@ -91,6 +91,11 @@ class dd_ee_sample_args(C.Structure):
                 ("y_dev", C.c_void_p), ("x_dev", C.c_void_p), ("err_dev", C.c_void_p), ("idx_dev", C.c_void_p)]
 
 
+class dd_ee_real(C.Structure):
+    """dd_sample_early_exit_real: layers l with l % compact_every == 0 compact the batch"""
+    _fields_ = [("compact_every", C.c_int32), ("reserved", C.c_int32)]
+
+
 class dd_scan_args(C.Structure):
     """dd_scan_error (include/duodiff.h): the images, the scan's rows and where the per-image errors go"""
     _fields_ = [("model", C.c_void_p), ("x0_dev", C.c_void_p), ("y_dev", C.c_void_p), ("B", C.c_int32), ("n_steps", C.c_int32)] + \
@@ -172,6 +177,7 @@ SIGNATURES = {
     "dd_sample": (C.c_int, [C.c_void_p, C.POINTER(dd_sample_args), C.c_void_p]),
     "dd_sample_affine": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.c_void_p]),
     "dd_sample_early_exit": (C.c_int, [C.c_void_p, C.POINTER(dd_ee_sample_args), C.c_void_p]),
+    "dd_sample_early_exit_real": (C.c_int, [C.c_void_p, C.POINTER(dd_ee_sample_args), C.POINTER(dd_ee_real), C.c_void_p]),
     "dd_forward_guided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.POINTER(dd_guidance), C.c_void_p,
                                     C.c_int, C.c_void_p]),
     "dd_sample_guided": (C.c_int, [C.c_void_p, C.POINTER(dd_sample_args), C.POINTER(dd_guidance), C.c_void_p]),
@@ -263,6 +269,9 @@ SIGNATURES = {
     "dd_dev_poison_workspaces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "dd_dev_graph_captures": (C.c_longlong, [C.c_void_p]),
     "dd_dev_last_sample_chains": (C.c_int, [C.c_void_p]),
+    "dd_dev_ee_real_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
+    "dd_dev_ee_real_cost": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "dd_dev_ee_real_plan": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dd_dev_set_flags": (C.c_int, [C.c_void_p, C.c_uint]),
     "dd_set_num_cus": (C.c_int, [C.c_void_p, C.c_int]),
     "dd_plan_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -122,6 +122,9 @@ struct dd_ctx {
     const uint64_t* seeds_user = nullptr;
     int seeds_n = 0;
     dd::DevBuf<unsigned long long> seeds_stage;
+    long long real_stats[3] = {0, 0, 0};     // dd_sample_early_exit_real's last call: block-rows run, moves made, compactions made (dd_dev_ee_real_stats),
+    double real_wait_ms = 0.0;               //   the time its calling thread spent waiting for counts and the number of such waits (dd_dev_ee_real_wait)
+    long long real_waits = 0, real_bytes = 0;   //   and the bytes its compactions moved
     int prof_kind = 0;           // dd_profile_select: which launches dd_profile_steps brackets (DD_PROF_*)
     unsigned dev_flags = 0;      // dd_dev_set_flags (include/duodiff_dev.h): kernel-variant switches of the development harness
 };
@@ -230,6 +233,11 @@ struct dd_model {
     dd::BlockCache cache[2];                                 // block caching: each chain's cache (ensure_block_cache)
     float* ee_ws = nullptr;                                  // dd_sample_early_exit scratch: eps | cls | outs (two chains: one such block per chain, half the batch each),
                                                              // then the chains' per-step sums of the predicted errors [2][1000][depth]
+    // dd_sample_early_exit_real: each chain's tables on the device (RealTables, one allocation), the pinned pair of counts each chain's
+    // compaction layers copy to the host, and the event behind that copy
+    int* real_tabs = nullptr;
+    int* real_counts_host = nullptr;
+    hipEvent_t real_ev[2] = {nullptr, nullptr};
     // in-context timing (dd_profile_steps): event pairs recorded around each launch of kind ctx->prof_kind when enabled
     bool time_fc1 = false;
     std::vector<hipEvent_t> fc1_events;   // pairs, grown on demand
@@ -279,6 +287,17 @@ struct Mods {
     const unsigned long long* seeds = nullptr;   // per-image seeds of the WHOLE batch, staged (stage_image_seeds), or null: in a Slice too -- the
                                               //   kernels index them by b0 + b, the image, under either guidance that doubles the rows
     unsigned pag_mask(const dd_model* m) const { return !pag ? 0u : (pag_late && m == pag_late) ? pag->layers_late : pag->layers_first; }
+};
+
+// What block bi finds already done when it starts: left by the launches in front of it (the embed launch; the previous block's last launches).
+// h, frag and qkv say where its norm1 went and exclude one another; all false: the block starts from the residual stream x alone.
+struct Handoff {
+    bool h = false;      // its norm1 is in h (row-major)
+    bool frag = false;   // the patch rows' norm1 is in hfrag, in the order the attention launch loads it: that launch computes attn.qkv (and
+                         // normalises the extra-token rows itself, from x)
+    bool qkv = false;    // its attn.qkv is in qkv
+    bool skip = false;   // its skip_linear has run: x holds the output, ytap the block input y that its early-exit heads read
+    bool xfrag = false;  // the patch rows of the residual stream are in xfrag, in the order the block tail loads them (x holds the extra-token rows only)
 };
 
 // early-exit taps of one forward (EarlyExitUViT.forward, early_exit.py:290-313): cls [depth, B], outs [depth, B, C, S, S]
@@ -344,6 +363,18 @@ int check_autoguided(dd_ctx* c, dd_model* first, dd_model* late, int B, const in
 int enqueue_step(dd_ctx* c, dd_model* m, const Chain& ch, float* x_dev, const int64_t* y_dev, int B, hipStream_t s, const StepOpts& o);
 int forward_eps(dd_ctx* c, dd_model* m, const Chain& ch, const float* x_dev, const int64_t* y_dev, float* eps_dev, int B, hipStream_t s,
                 const StepOpts& o);
+// One stage of a forward that dd_sample_early_exit_real drives block by block, on the B active slots of a chain whose step started with
+// B_full images (the strides of the taps' tables): REAL_EMBED (x_img, y -> hand), REAL_TAPS (layer bi's head and probe into ee, finished at
+// once), REAL_BLOCK (block bi: hand in, hand out), REAL_HEAD (the output head: eps).  The launches are those of run_backbone.
+enum RealStageKind { REAL_EMBED, REAL_TAPS, REAL_BLOCK, REAL_HEAD };
+struct RealStage {
+    int kind, bi, B, B_full;
+    const float* x_img = nullptr;
+    const int64_t* y = nullptr;
+    const EeTaps* ee = nullptr;
+    float* eps = nullptr;
+};
+int real_exit_stage(dd_model* m, const Chain& ch, const RealStage& r, Handoff& hand, hipStream_t s);
 int stage_inputs(dd_ctx* c, const float* x_dev, const int64_t* y_dev, int B, size_t x_elems, hipStream_t s, float** x_run,
                  const int64_t** y_run);
 int stage_guided(dd_ctx* c, const float* x_dev, const int64_t* y_dev, int B, int B0, size_t chw, int null_label, hipStream_t s,

@@ -49,17 +49,6 @@ FinalArgs final_args(const dd_model* m, const Chain& ch, const float* dec, const
 }
 
 // ---- the forward: tokens -> blocks -> decoder_pred patches (the chain's dec) -----------------------
-// What block bi finds already done when it starts: left by the launches in front of it (the embed launch; the previous block's last launches).
-// h, frag and qkv say where its norm1 went and exclude one another; all false: the block starts from the residual stream x alone.
-struct Handoff {
-    bool h = false;      // its norm1 is in h (row-major)
-    bool frag = false;   // the patch rows' norm1 is in hfrag, in the order the attention launch loads it: that launch computes attn.qkv (and
-                         // normalises the extra-token rows itself, from x)
-    bool qkv = false;    // its attn.qkv is in qkv
-    bool skip = false;   // its skip_linear has run: x holds the output, ytap the block input y that its early-exit heads read
-    bool xfrag = false;  // the patch rows of the residual stream are in xfrag, in the order the block tail loads them (x holds the extra-token rows only)
-};
-
 // one forward of B rows of chain ch, enqueued on s (Backbone<T>{m, ch, B, s, ee}): the stages of a block each enqueue their launches and
 // pass the next one a Handoff
 template <typename T>
@@ -79,6 +68,11 @@ struct Backbone {
     // the patch rows' y without writing them); out-block nb - K runs its skip_linear as a stage of its own, from the cache and from the
     // row-major long-skip copy that in-block K - 1 therefore writes whole (no fragment copy of its patch rows).
     CacheUse cu{};
+    // real early exit (real_exit_stage; 0: none, every launch below is run_backbone's): B is the active prefix of a chain whose step started
+    // with B_full images.  The taps' tables keep B_full for their layer stride, so no slot of one layer aliases another's, and each layer's
+    // taps are finished in ee_taps itself (its unpatchify / conv and its probe reduce on the layer's own slice: the same kernels, per image the
+    // same arithmetic as the one batched launch of ee_finish) -- the exit decision behind them cannot wait for the last block.
+    int B_full = 0;
     dd_ctx* c = m->ctx;
     const WsPtrs& ws = *ch.ws;
     const int D = m->D, L = m->L, M = B * L, nb = (int)m->blocks.size();
@@ -89,7 +83,8 @@ struct Backbone {
     // layers (the per-layer arithmetic is unchanged; 2 x 12 launches less on each step's critical path).  The buffers live in the MLP hidden
     // buffer, which the fused block tail never touches.
     float* ee_dec_all = ee && m->ee_batched ? (float*)ws.hid : nullptr;
-    float* ee_srow_all = ee_dec_all ? ee_dec_all + (size_t)nb * M * m->pd : nullptr;
+    const int Bs = B_full ? B_full : B;       // images per layer of the taps' tables
+    float* ee_srow_all = ee_dec_all ? ee_dec_all + (size_t)nb * Bs * L * m->pd : nullptr;
     bool ao_in_frag = false;     // norm1_attention -> block_tail of the same block: the patch rows of the attention output are in aofrag
     const BlockCache& bc = m->cache[ch.ws == &m->ws[1] ? 1 : 0];
     const int deep_first = cu.blocks ? cu.blocks : -1, deep_last = cu.blocks ? nb - 1 - cu.blocks : -1;   // the deep range (-1: no caching)
@@ -179,10 +174,10 @@ struct Backbone {
         const int add = m->ee_type == DD_EE_MLP_PER_TIMESTEP ? 0 : bi;
         bool probe_done = false;
         if (hd.wg) {   // the head's LayerNorm + decoder_pred in one exact-fp32 launch (the final head's kernel), patch rows only
-            HeadDecArgs ha{xin, hd.wg, hd.dc, ee_dec_all ? ee_dec_all + (size_t)bi * M * m->pd : ws.dec, M, m->pd, (L - m->extras) % 16 == 0 ? L : 0, m->extras};
+            HeadDecArgs ha{xin, hd.wg, hd.dc, ee_dec_all ? ee_dec_all + (size_t)bi * Bs * L * m->pd : ws.dec, M, m->pd, (L - m->extras) % 16 == 0 ? L : 0, m->extras};
             if (hd.wsplit) { ha.wg = hd.wsplit; ha.c = hd.dcs; ha.split = 1; }      // (bf16 engine: the split-bf16 product, rowops.hip SPLIT)
             if (ee_srow_all && m->ee_type != DD_EE_ATTENTION_PROBE && head_dec_probe_supported(D)) {   // ... and the MLP probe's per-token values of the same rows
-                ha.srow = ee_srow_all + (size_t)bi * B * L; ha.pw_base = m->probe_w; ha.pb_base = m->probe_b; ha.st = ch.st; ha.t_mul = t_mul; ha.add = add;
+                ha.srow = ee_srow_all + (size_t)bi * Bs * L; ha.pw_base = m->probe_w; ha.pb_base = m->probe_b; ha.st = ch.st; ha.t_mul = t_mul; ha.add = add;
                 probe_done = true;
             }
             DD_HIP(c, launch_head_dec(ha, D, ch.cus, hs));
@@ -195,14 +190,21 @@ struct Backbone {
         if (!ee_dec_all) {
             const long long chw = (long long)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
             FinalArgs fa = final_args(m, ch, ws.dec, hd.wconv, hd.bconv, B);
-            fa.eps_out = ee->outs + (long long)bi * B * chw;
+            fa.eps_out = ee->outs + (long long)bi * Bs * chw;
             DD_HIP(c, launch_final(fa, hs));
         }
         if (m->ee_type == DD_EE_ATTENTION_PROBE) {
-            DD_HIP(c, launch_ee_attn_probe(xin, m->attn_probes[bi], ee->cls + (long long)bi * B, B, L, D, hs));
+            DD_HIP(c, launch_ee_attn_probe(xin, m->attn_probes[bi], ee->cls + (long long)bi * Bs, B, L, D, hs));
         } else if (!probe_done) {
-            if (ee_srow_all) DD_HIP(c, launch_ee_probe(xin, m->probe_w, m->probe_b, nullptr, ee_srow_all + (size_t)bi * B * L, B, L, D, ch.st, t_mul, add, hs));   // rows only: reduced behind the last block
-            else DD_HIP(c, launch_ee_probe(xin, m->probe_w, m->probe_b, ee->cls + (long long)bi * B, (float*)ws.hid, B, L, D, ch.st, t_mul, add, hs));   // (the MLP hidden buffer is free between blocks)
+            if (ee_srow_all) DD_HIP(c, launch_ee_probe(xin, m->probe_w, m->probe_b, nullptr, ee_srow_all + (size_t)bi * Bs * L, B, L, D, ch.st, t_mul, add, hs));   // rows only: reduced behind the last block
+            else DD_HIP(c, launch_ee_probe(xin, m->probe_w, m->probe_b, ee->cls + (long long)bi * Bs, (float*)ws.hid, B, L, D, ch.st, t_mul, add, hs));   // (the MLP hidden buffer is free between blocks)
+        }
+        if (B_full && ee_dec_all) {      // real early exit: this layer's share of ee_finish, now
+            const long long chw = (long long)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
+            FinalArgs fa = final_args(m, ch, ee_dec_all + (size_t)bi * Bs * L * m->pd, hd.wconv, hd.bconv, B);
+            fa.eps_out = ee->outs + (long long)bi * Bs * chw;
+            DD_HIP(c, launch_final(fa, hs));
+            if (m->ee_type != DD_EE_ATTENTION_PROBE) DD_HIP(c, launch_ee_probe_reduce(ee_srow_all + (size_t)bi * Bs * L, ee->cls + (long long)bi * Bs, B, L, hs));
         }
         if (side) DD_HIP(c, hipEventRecord(c->ev_ee_join, c->side));
         return DD_OK;
@@ -365,7 +367,7 @@ struct Backbone {
 
     // every layer's unpatchify + conv in one launch (layer i: images [i B, (i + 1) B) of nb B, its own conv weights), every MLP probe's mean in one
     int ee_finish() {
-        if (!ee_dec_all) return DD_OK;
+        if (!ee_dec_all || B_full) return DD_OK;
         FinalArgs fa = final_args(m, ch, ee_dec_all, m->heads[0].wconv, m->heads[0].bconv, nb * B);
         fa.eps_out = ee->outs;
         fa.layer_B = B; fa.w_stride = m->ee_wconv_stride; fa.b_stride = m->ee_bconv_stride;
@@ -424,6 +426,33 @@ int run_model(dd_model* m, const Chain& ch, const float* x_img, const float* t_v
                                    : run_backbone<float>(m, ch, x_img, t_vec, y_dev, B, s, ee, pert, cu);
 }
 
+// run_backbone's stages one at a time, on the active prefix of a chain (dd_sample_early_exit_real)
+template <typename T>
+int real_stage(dd_model* m, const Chain& ch, const RealStage& r, Handoff& hand, hipStream_t s) {
+    Backbone<T> f{m, ch, r.B, s, r.ee, 0, 0, CacheUse{}, r.B_full};
+    switch (r.kind) {
+    case REAL_EMBED:
+        hand = Handoff{};
+        return f.embed(r.x_img, nullptr, r.y, hand);
+    case REAL_TAPS: {
+        bool side = false;      // (the chain's Chain has ee_fork off: the decision behind the taps is in line with them)
+        return f.ee_taps(r.bi, hand, side);
+    }
+    case REAL_BLOCK:
+        if (int rc = f.skip_linear(r.bi, hand)) return rc;
+        if (int rc = f.norm1_attention(r.bi, hand)) return rc;
+        if (int rc = f.proj(r.bi)) return rc;
+        return f.mlp(r.bi, hand);
+    default: {
+        if (int rc = f.head()) return rc;
+        FinalArgs fa = final_args(m, ch, ch.ws->dec, m->head.wconv, m->head.bconv, r.B);
+        fa.eps_out = r.eps;
+        DD_HIP(m->ctx, launch_final(fa, s));
+        return DD_OK;
+    }
+    }
+}
+
 // the checks of a call that do not concern labels
 int check_model(dd_ctx* c, dd_model* m, int B) {
     if (!c || !m) return DD_ERR_INVALID;
@@ -435,6 +464,10 @@ int check_model(dd_ctx* c, dd_model* m, int B) {
 }  // namespace
 
 namespace dd {
+int real_exit_stage(dd_model* m, const Chain& ch, const RealStage& r, Handoff& hand, hipStream_t s) {
+    return m->prec == DD_PREC_BF16 ? real_stage<bf16_t>(m, ch, r, hand, s) : real_stage<float>(m, ch, r, hand, s);
+}
+
 int check_call(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev) {
     if (int rc = check_model(c, m, B)) return rc;
     if (m->cfg.num_classes > 0 && !y_dev)

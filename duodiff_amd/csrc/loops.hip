@@ -6,8 +6,10 @@
 #include "../../include/duodiff.h"
 #include "../../include/duodiff_dev.h"
 #include "engine_state.h"
+#include "ee_real.h"
 
 #include <algorithm>
+#include <chrono>
 #include <functional>
 
 using namespace dd;
@@ -891,6 +893,219 @@ int dd_sample_early_exit(dd_ctx* c, const dd_ee_sample_args* a, void* stream) {
         return DD_OK;
     };
     return run_loop(c, L, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+namespace {
+// The buffers of chain workspace ws that are live between the taps of block bi and its first launch, as image slabs: what a compaction in
+// front of block bi has to move.  Read off the flags and the Handoff that Backbone itself reads (forward.hip):
+//   x                              the residual stream (under hand.xfrag: its extra-token rows)
+//   xfrag                          hand.xfrag: the patch rows of the residual stream
+//   h | hfrag | qkv                where the launches in front left the block's norm1 (hand.h / hand.frag) or attn.qkv (hand.qkv)
+//   xb                             an out-block whose skip_linear has not run: its x operand
+//   skips[j], skipfrags[j]         every long-skip copy no skip_linear has consumed yet: j < bi (in- and mid-blocks); j < nb - bi, less the
+//                                  one the previous block's fused launch consumed (hand.skip)
+// ao / aofrag, hid, dec, mlp_partial and ytap are written and read inside one block or one taps stage: never live here.
+int real_live_set(dd_ctx* c, const dd_model* m, const WsPtrs& ws, int bi, const Handoff& hand, RealSlabs& out) {
+    const long long D = m->D, L = m->L, N = m->N, es = (long long)m->esize, nb = (long long)m->blocks.size();
+    out.n = 0;
+    int rc = DD_OK;
+    auto add = [&](const void* p, long long bytes) {
+        if (!p) return;
+        if (out.n == EE_REAL_MAX_SLABS || bytes % 16 || (uintptr_t)p % 16) { rc = DD_ERR_UNSUPPORTED; return; }
+        out.s[out.n++] = RealSlab{(char*)p, bytes};
+    };
+    add(ws.x, L * D * 4);
+    if (hand.xfrag) add(ws.xfrag, N * D * 4);
+    if (hand.h) add(ws.h, L * D * es);
+    if (hand.frag) add(ws.hfrag, N * D * 2);
+    if (hand.qkv) add(ws.qkv, 3 * D * (long long)make_head_major(m->L, m->H).Lp * es);
+    if (bi > m->half_depth && !hand.skip) add(ws.xb, L * D * es);
+    const long long unconsumed = bi <= m->half_depth ? bi : nb - bi - (hand.skip ? 1 : 0);
+    for (long long j = 0; j < unconsumed; ++j) {
+        add(ws.skips[j], L * D * es);
+        if (m->frag_skip) add(ws.skipfrags[j], N * D * 2);
+    }
+    if (rc) return ctx_fail(c, rc, "real early exit: a per-image buffer of this model is no multiple of 16 bytes, or too many are live");
+    return DD_OK;
+}
+
+// a chain's tables (RealTables) as one run of ints: rec [2 B] | moves [2 (B / 2 + 1)] | tab [B] | counts [2], an even number (rec and moves hold pairs)
+size_t real_tab_ints(size_t B) { return (2 * B + 2 * (B / 2 + 1) + B + 2 + 1) / 2 * 2; }
+int ensure_real_ws(dd_ctx* c, dd_model* m) {
+    if (!m->real_tabs) DD_HIP(c, hipMalloc((void**)&m->real_tabs, 2 * real_tab_ints((size_t)m->cfg.max_batch) * sizeof(int)));
+    if (!m->real_counts_host) DD_HIP(c, hipHostMalloc((void**)&m->real_counts_host, 4 * sizeof(int), hipHostMallocDefault));
+    for (hipEvent_t& e : m->real_ev)
+        if (!e) DD_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return DD_OK;
+}
+
+// One chain of dd_sample_early_exit_real: its share of the batch, its scratch (eps | cls | outs: dd_sample_early_exit's block) and where it
+// stands.  run() enqueues on the chain's stream until the chain is done or has to know a count: then the copy of the two counts and an
+// event are enqueued behind the decision launch and run() returns, to be called again -- it waits on the event first.
+struct RealChain {
+    dd_ctx* c; dd_model* m; const dd_ee_sample_args* a;
+    Chain ch; hipStream_t s;
+    float* x; const int64_t* y; int B, b0;
+    float *eps, *cls, *outs;
+    RealTables t; int* counts_host; hipEvent_t ev;
+    const unsigned long long* seeds;
+    int compact_every;
+    int step = 0, layer = 0, Ba = 0;
+    bool waiting = false, done = false;
+    Handoff hand{};
+    long long stats[3] = {0, 0, 0};
+    double wait_ms = 0.0; long long waits = 0, bytes = 0;
+
+    // (every stage is given the taps: a block's fused tail writes the y its successor's head reads only where the forward has taps)
+    int stage(int kind) {
+        const EeTaps ee{cls, outs, 0};
+        RealStage r{kind, layer, kind == REAL_EMBED ? B : Ba, B};
+        r.x_img = x; r.y = y; r.ee = &ee; r.eps = eps;
+        return real_exit_stage(m, ch, r, hand, s);
+    }
+    int finish_step() {
+        DD_HIP(c, launch_ee_real_step(x, outs, eps, t, a->threshold, m->cfg.depth, ch.st, c->coef, B, m->cfg.in_chans, m->cfg.img_size, a->noise_mode, b0, seeds, s));
+        layer = 0;
+        done = ++step == a->t_start - a->t_end + 1;
+        return DD_OK;
+    }
+    int run() {
+        const int depth = m->cfg.depth;
+        while (!done) {
+            if (!waiting) {
+                if (layer == 0) {
+                    if (int rc = stage(REAL_EMBED)) return rc;
+                    Ba = B;
+                }
+                if (int rc = stage(REAL_TAPS)) return rc;
+                const bool compact = layer % compact_every == 0;
+                DD_HIP(c, launch_ee_real_decide(cls + (size_t)layer * B, a->threshold, layer, depth, Ba, compact, t, a->idx_dev, a->B, b0, ch.st, s));
+                if (compact) {
+                    DD_HIP(c, hipMemcpyAsync(counts_host, t.counts, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+                    DD_HIP(c, hipEventRecord(ev, s));
+                    waiting = true;
+                    return DD_OK;
+                }
+            } else {
+                const auto t0 = std::chrono::steady_clock::now();
+                DD_HIP(c, hipEventSynchronize(ev));
+                wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+                ++waits;
+                waiting = false;
+                const int keep = counts_host[0], moves = counts_host[1];
+                if (keep < 0 || keep > Ba || moves < 0 || moves > Ba - keep) return ctx_fail(c, DD_ERR_HIP, "real early exit: the decision launch returned counts outside the batch");
+                if (moves > 0 && keep > 0) {
+                    RealSlabs slabs;
+                    if (int rc = real_live_set(c, m, *ch.ws, layer, hand, slabs)) return rc;
+                    DD_HIP(c, launch_ee_real_compact(t, moves, slabs, s));
+                    stats[1] += moves; stats[2] += 1;
+                    for (int i = 0; i < slabs.n; ++i) bytes += (long long)moves * slabs.s[i].bytes;
+                }
+                Ba = keep;
+                if (Ba == 0) {       // every image of the chain has left: no further block, no output head
+                    if (int rc = finish_step()) return rc;
+                    continue;
+                }
+            }
+            if (int rc = stage(REAL_BLOCK)) return rc;
+            stats[0] += Ba;
+            if (++layer == depth) {
+                if (int rc = stage(REAL_HEAD)) return rc;
+                if (int rc = finish_step()) return rc;
+            }
+        }
+        return DD_OK;
+    }
+};
+}  // namespace
+
+extern "C" {
+
+// dd_sample_early_exit with the exits taken.  Eager launches; the calling thread waits for each compaction layer's counts.
+int dd_sample_early_exit_real(dd_ctx* c, const dd_ee_sample_args* a, const dd_ee_real* r, void* stream) {
+    if (!c || !a) return DD_ERR_INVALID;
+    if (!r) return ctx_fail(c, DD_ERR_INVALID, "null dd_ee_real");
+    dd_model* m = a->model;
+    int rc = check_call(c, m, a->B, a->y_dev);
+    if (rc) return rc;
+    if (m->ee_type < 0) return ctx_fail(c, DD_ERR_STATE, "model was not created with dd_model_enable_early_exit");
+    if (!a->x_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    if (a->err_dev) return ctx_fail(c, DD_ERR_INVALID, "dd_sample_early_exit_real: err_dev must be NULL (an image that has left has no predicted error at the layers behind its exit)");
+    if (r->compact_every < 1) return ctx_fail(c, DD_ERR_INVALID, "dd_sample_early_exit_real: compact_every must be at least 1");
+    if (a->t_start > 999 || a->t_end < 0 || a->t_end > a->t_start) return ctx_fail(c, DD_ERR_INVALID, "need 999 >= t_start >= t_end >= 0");
+    if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE)
+        return ctx_fail(c, DD_ERR_INVALID, "dd_sample_early_exit_real generates noise on the device; for host noise drive dd_forward_early_exit");
+    if (a->B > EE_REAL_MAX_SLOTS) return ctx_fail(c, DD_ERR_UNSUPPORTED, "dd_sample_early_exit_real takes at most 1024 images");
+    if ((rc = check_image_seeds(c, a->noise_mode, a->B))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned long long* seeds = nullptr;
+    if ((rc = stage_image_seeds(c, a->noise_mode, s, &seeds))) return rc;
+    if ((rc = ensure_ee_ws(c, m)) || (rc = ensure_real_ws(c, m))) return rc;
+    for (long long& v : c->real_stats) v = 0;
+    c->real_wait_ms = 0.0; c->real_waits = c->real_bytes = 0;
+    // the chains of dd_sample_early_exit's policy (an eager loop here: no graph is asked for)
+    const bool chained = use_chains(c, m, a->B, true);
+    const int chains = chained ? 2 : 1, B0 = chained ? a->B / 2 : a->B, depth = m->cfg.depth;
+    c->last_chains = chains;
+    if (chained && (rc = ensure_chain_ws(c, m, s))) return rc;
+    const size_t chw = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size, mb = (size_t)m->cfg.max_batch;
+    for (int k = 0; k < chains; ++k) DD_HIP(c, launch_set_state(c->st[k], a->t_start, (unsigned long long)a->seed, s));
+    if (chained) {
+        DD_HIP(c, hipEventRecord(c->ev_fork, s));
+        DD_HIP(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
+    }
+    SideJoin side_join{c, chained};
+    DD_HIP(c, hipEventRecord(c->ev[0], s));
+    RealChain rcs[2];
+    for (int k = 0; k < chains; ++k) {
+        const int b0 = k ? B0 : 0, Bk = k ? a->B - B0 : B0;
+        float* eps = m->ee_ws + ee_scratch_elems(m, b0);
+        float* cls = eps + (size_t)Bk * chw;
+        int* tabs = m->real_tabs + (size_t)k * real_tab_ints(mb);
+        rcs[k] = RealChain{c, m, a, Chain{&m->ws[k], c->st[k], c->num_cus, false}, k ? c->side : s,
+                           a->x_dev + (size_t)b0 * chw, a->y_dev ? a->y_dev + b0 : nullptr, Bk, b0, eps, cls, cls + (size_t)depth * Bk,
+                           RealTables{tabs + 2 * mb + 2 * (mb / 2 + 1), tabs, tabs + 2 * mb + 2 * (mb / 2 + 1) + mb, tabs + 2 * mb},
+                           m->real_counts_host + 2 * k, m->real_ev[k], seeds, r->compact_every};
+    }
+    // one host thread alternates the chains: one chain's blocks run while the other's counts travel
+    for (bool busy = true; busy;) {
+        busy = false;
+        for (int k = 0; k < chains; ++k) {
+            if (rcs[k].done) continue;
+            if ((rc = rcs[k].run())) return rc;
+            busy = busy || !rcs[k].done;
+        }
+    }
+    for (int k = 0; k < chains; ++k) {
+        for (int i = 0; i < 3; ++i) c->real_stats[i] += rcs[k].stats[i];
+        c->real_wait_ms += rcs[k].wait_ms; c->real_waits += rcs[k].waits; c->real_bytes += rcs[k].bytes;
+    }
+    if (chained) {
+        DD_HIP(c, hipEventRecord(c->ev_join, c->side));
+        DD_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0));
+        side_join.armed = false;
+    }
+    DD_HIP(c, hipEventRecord(c->ev[1], s));
+    DD_HIP(c, hipEventRecord(c->ev[2], s));
+    return DD_OK;
+}
+
+int dd_dev_ee_real_stats(dd_ctx* c, long long out3[3]) {
+    if (!c || !out3) return DD_ERR_INVALID;
+    for (int i = 0; i < 3; ++i) out3[i] = c->real_stats[i];
+    return DD_OK;
+}
+int dd_dev_ee_real_cost(dd_ctx* c, double* ms_out, long long* waits_out, long long* bytes_out) {
+    if (!c || !ms_out || !waits_out || !bytes_out) return DD_ERR_INVALID;
+    *ms_out = c->real_wait_ms; *waits_out = c->real_waits; *bytes_out = c->real_bytes;
+    return DD_OK;
+}
+int dd_dev_ee_real_plan(const int* alive, int n, int* keep_out, int* n_moves_out, int* moves_src_dst) {
+    if (!alive || n < 0 || !keep_out || !n_moves_out || !moves_src_dst) return DD_ERR_INVALID;
+    *keep_out = real_exit_plan(alive, n, n_moves_out, moves_src_dst);
+    return DD_OK;
 }
 
 long long dd_dev_graph_captures(dd_ctx* c) { return c ? c->graph_captures : -1; }

@@ -507,6 +507,9 @@ void dd_model_destroy(dd_model* m) {
         for (hipGraphExec_t g : kind) if (g) (void)hipGraphExecDestroy(g);
     for (hipEvent_t e : m->fc1_events) (void)hipEventDestroy(e);
     if (m->ee_ws) (void)hipFree(m->ee_ws);
+    if (m->real_tabs) (void)hipFree(m->real_tabs);
+    if (m->real_counts_host) (void)hipHostFree(m->real_counts_host);
+    for (hipEvent_t e : m->real_ev) if (e) (void)hipEventDestroy(e);
     for (BlockCache& bc : m->cache)
         for (void* p : {bc.last, bc.prev, bc.yhat}) if (p) (void)hipFree(p);
     if (m->warena) (void)hipFree(m->warena);

@@ -15,6 +15,20 @@ from .uvit import UViT
 from .weights import EE_CLASSIFIER_TYPES, ee_param_shapes
 
 
+def real_exit_block_rows(idx, depth: int, compact_every: int = 1) -> int:
+    """Block-rows a real-exit run (dd_sample_early_exit_real) launches for the exit indices idx (any shape, one entry per image and step,
+    values in [0, depth]; depth: the image never left).  An image with exit index e runs blocks 0 .. l* - 1, where l* is the first
+    compaction layer (l % compact_every == 0, l < depth) at or behind e; if there is none it runs all depth blocks.  For a threshold
+    >= 0 -- under a negative one the reference's rule gives an image that no layer lets go the index 0, and it has run every block."""
+    import numpy as np
+    e = np.asarray(idx).astype(np.int64).ravel()
+    depth, s = int(depth), int(compact_every)
+    if s < 1 or depth < 1 or (e.size and (e.min() < 0 or e.max() > depth)):
+        raise ValueError("real_exit_block_rows: need compact_every >= 1, depth >= 1 and exit indices in [0, depth]")
+    first = -(-e // s) * s                     # the first multiple of s at or behind e
+    return int(np.where(first < depth, first, depth).sum())
+
+
 class EarlyExitUViT:
     def __init__(self, uvit: UViT, classifier_type="attention_probe", exit_threshold=0.2):
         if classifier_type not in EE_CLASSIFIER_TYPES:

@@ -718,6 +718,39 @@ def sample_early_exit_loop(ctx: Context, model: Model, x, threshold, *, t_start=
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
 
+def sample_early_exit_real_loop(ctx: Context, model: Model, x, threshold, *, t_start=999, t_end=0, y=None, seed=0, noise="philox",
+                                idx=None, compact_every=1, err=None, stream=None):
+    """dd_sample_early_exit_real: sample_early_exit_loop with the exits taken -- an image that has left runs no block from the next
+    compaction layer (every compact_every-th, from layer 0) on.  Images and idx rows equal sample_early_exit_loop's bit for bit.  The
+    loop runs as eager launches and blocks the calling thread: the host waits for the active count at every compaction layer; no graph
+    is captured or replayed.  err must be None (the batch mean of a layer's predicted errors does not exist once images have left).
+    Returns x; real_exit_stats(ctx) reports what the call ran."""
+    if err is not None:
+        raise ValueError("real early exit writes no error_prediction_by_timestep: err must be None")
+    if int(compact_every) != compact_every or int(compact_every) < 1:
+        raise ValueError(f"compact_every must be an integer >= 1, got {compact_every!r}")
+    if noise not in ("none", "philox"):
+        raise ValueError("real early exit draws its noise on the device: noise must be 'philox' or 'none'")
+    args = L.dd_ee_sample_args()
+    args.model = model.handle
+    args.threshold = float(threshold)
+    args.t_start, args.t_end = int(t_start), int(t_end)
+    if idx is not None:
+        assert idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and tuple(idx.shape) == (1000, x.shape[0])
+    args.err_dev = None
+    args.idx_dev = idx.data_ptr() if idx is not None else None
+    real = L.dd_ee_real(int(compact_every), 0)
+    call = lambda st: ctx.lib.dd_sample_early_exit_real(ctx.handle, C.byref(args), C.byref(real), st)
+    return _run_loop(ctx, args, x, y, seed, noise, False, stream, call)
+
+
+def real_exit_stats(ctx: Context):
+    """dd_dev_ee_real_stats of the last sample_early_exit_real_loop call: (block-rows run, moves made, compactions made)."""
+    out = (C.c_longlong * 3)()
+    ctx.check(ctx.lib.dd_dev_ee_real_stats(ctx.handle, out))
+    return tuple(int(v) for v in out)
+
+
 def _scan_args(args, model, rows, counter_base):
     """The fields dd_scan_args and dd_scan_exits_args share, from the six row arrays (kept alive on args as float32); returns n."""
     args._rows = {k: np.ascontiguousarray(rows[k], np.float32) for k in ("t", "ka", "kb", "tz", "t0", "tx")}

@@ -490,6 +490,24 @@ typedef struct dd_ee_sample_args {
 } dd_ee_sample_args;
 int dd_sample_early_exit(dd_ctx* ctx, const dd_ee_sample_args* args, void* stream);
 
+/* dd_sample_early_exit with the exits TAKEN (an addition to version 6: new symbols, no struct changes).  dd_sample_early_exit, like the
+ * reference, only simulates the exit: every image runs every block.  Here an image whose probe at layer l passes the threshold runs no block
+ * from the next compaction layer on: the chain's active images are kept as a prefix of its buffers' slots, a decision launch behind every
+ * layer's probe records who leaves, and at the layers l with l % compact_every == 0 the surviving images are moved into the holes and block
+ * l runs on the survivors alone.  Every image receives, bit for bit, the images and idx_dev rows dd_sample_early_exit gives for the same
+ * arguments (a row takes the same kernels in any slot of any batch; noise is drawn by image).
+ * The loop runs as eager launches and BLOCKS THE CALLING THREAD: at every compaction layer the host waits for two counts from the device
+ * before it can size the next launches.  It captures no graph and replays none; args->use_graph is not read.  Two half-batch chains under
+ * dd_sample_early_exit's policy, alternated by the calling thread.
+ * DD_ERR_INVALID (with dd_last_error) before anything is enqueued: a NULL real, compact_every < 1, args->err_dev != NULL (the batch mean of
+ * a layer's predicted errors does not exist once images have left in front of it), host noise, and every check dd_sample_early_exit makes;
+ * DD_ERR_STATE for a model without early exit. */
+typedef struct dd_ee_real {
+    int32_t compact_every;  /* >= 1: layers l with l % compact_every == 0 compact (1: every layer) */
+    int32_t reserved;
+} dd_ee_real;
+int dd_sample_early_exit_real(dd_ctx* ctx, const dd_ee_sample_args* args, const dd_ee_real* real, void* stream);
+
 /* ---- per-image seeds (version 6 additions: new symbols, no struct changes): image i = f(seed_i), whatever its batch ---- */
 /* Plain (the default, every bit as before): the device noise of a call is Philox with key = the call's seed and a pixel id that runs
  * over the WHOLE batch, id = (i S S + y S + x) for pixel (y, x) of image i -- an image's noise depends on where it sits in its batch.

@@ -410,6 +410,16 @@ int dd_dev_poison_workspaces(dd_ctx* ctx, dd_model* m, void* stream);
 /* Number of chains the last dd_sample call on this context ran (1, or 2 half-batch chains on two streams). */
 int dd_dev_last_sample_chains(dd_ctx* ctx);
 
+/* The last dd_sample_early_exit_real call on this context: out3 = block-rows run (the sum over steps, chains and blocks of the images the
+ * block was launched on), moves made (image slabs copied, per buffer set), compaction launches made. */
+int dd_dev_ee_real_stats(dd_ctx* ctx, long long out3[3]);
+/* ... and what the exits cost it: the time its calling thread spent waiting for the counts of compaction layers (ms, host clock), the number
+ * of such waits, and the bytes its compactions moved. */
+int dd_dev_ee_real_cost(dd_ctx* ctx, double* ms_out, long long* waits_out, long long* bytes_out);
+/* The hole-fill plan of a compaction on the host (no device, no context): alive [n] -> *keep_out survivors, *n_moves_out moves (source slot,
+ * destination slot) in moves_src_dst [2 * (n / 2)] -- the rule the decision kernel applies. */
+int dd_dev_ee_real_plan(const int* alive, int n, int* keep_out, int* n_moves_out, int* moves_src_dst);
+
 #ifdef __cplusplus
 }
 #endif

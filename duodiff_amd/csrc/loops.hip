@@ -1,6 +1,11 @@
-// The device-resident sampling loops: the half-batch chains, the captured step of each loop and its replay, staging of the loops' tables and
-// known regions, in-context launch timing; every dd_sample* entry point except dd_sample_step, and dd_profile_steps*.  Above forward.hip, below
-// capi.hip (engine_state.h).
+// The device-resident sampling loops and scans: every dd_sample* entry point except dd_sample_step, dd_scan_error*, and dd_profile_steps*.
+// Host code that enqueues launches; above forward.hip, below capi.hip (engine_state.h).  In this order:
+//   - the half-batch chains: when a call splits (use_chains) and the one fork / join of the two streams (ChainFork);
+//   - a loop as data (Loop): what each row runs (Program: the switch rule, a walk's jumps, block caching's reuse steps) and the callbacks
+//     that differ between the entries; run_loop drives it -- staging, graph capture and replay, the timing events;
+//   - the entries on run_loop: their checks (check_loop), the staging of tables and known regions, then dd_sample, the three dd_sample_affine
+//     paths on one shared check and base loop, dd_sample_multistep, the two scans and dd_sample_early_exit;
+//   - dd_sample_early_exit_real: an eager loop of its own on the same early-exit setup, scratch block and chain fork.
 //
 // Host-side restatement of: get_samples DDPM branch and backbone switch (reference sampler.py:128-139), the early-exit sampler (eesampler.py:56-81).
 #include "../../include/duodiff.h"
@@ -9,6 +14,7 @@
 #include "ee_real.h"
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <functional>
 
@@ -39,11 +45,26 @@ int chain_gemm_cus(dd_ctx* c, dd_model* m, int B) {
     const int half = c->num_cus / 2 / 8 * 8;
     return half >= 8 ? half : c->num_cus;
 }
-// a failure between the fork and the join of a chained call must not leave the side stream running on the second chain's buffers behind
-// the caller's back: armed after the fork, disarmed by the regular join
-struct SideJoin {
-    dd_ctx* c; bool armed;
-    ~SideJoin() { if (armed && c->side) (void)hipStreamSynchronize(c->side); }
+// The fork and the join of the two half-batch chains of a chained call (chained false: nothing).  fork() behind the staging copies and the
+// state: the side stream starts behind them; join() in front of the tail: the caller's stream goes on behind the side stream.  A failure
+// between the two must not leave the side stream running on the second chain's buffers behind the caller's back: the scope waits for it.
+struct ChainFork {
+    dd_ctx* c; hipStream_t s; bool chained; bool armed = false;
+    int fork() {
+        if (!chained) return DD_OK;
+        DD_HIP(c, hipEventRecord(c->ev_fork, s));
+        DD_HIP(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
+        armed = true;
+        return DD_OK;
+    }
+    int join() {
+        if (!chained) return DD_OK;
+        DD_HIP(c, hipEventRecord(c->ev_join, c->side));
+        DD_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0));
+        armed = false;
+        return DD_OK;
+    }
+    ~ChainFork() { if (armed && c->side) (void)hipStreamSynchronize(c->side); }
 };
 
 // the captured graph in `exec`, captured under the key `have`: reused if that is `key`, else captured now from enqueue()
@@ -74,13 +95,32 @@ int get_graph(dd_ctx* c, dd_model* m, GraphKind kind, int chain, const GraphKey&
 // (mods: the loop's, with the chain's share of the known region)
 struct Slice { int chain, chains; float* x; const int64_t* y; int B, b0; Mods mods; };
 
+// What a row of a sampling loop runs: a model's full step, a jump (dd_sample_affine_walk: no model), or a model's reuse step (block caching)
+enum StepOp { STEP_FIRST = 0, STEP_LATE = 1, STEP_JUMP = 2, STEP_FIRST_REUSE = 3, STEP_LATE_REUSE = 4, STEP_OPS = 5 };
+// a model's full step, its reuse step, and back
+constexpr int reuse_of(int full) { return full == STEP_LATE ? STEP_LATE_REUSE : STEP_FIRST_REUSE; }
+constexpr bool is_reuse(int op) { return op == STEP_FIRST_REUSE || op == STEP_LATE_REUSE; }
+constexpr int full_of(int op) { return op == STEP_LATE_REUSE ? STEP_LATE : op == STEP_FIRST_REUSE ? STEP_FIRST : op; }
+
+// The rows of a loop: a StepOp each.  switched: the program states the switch rule (switch_program) -- such a loop captures both models' full
+// step whoever runs; late_behind: and that rule puts the switch behind the last step.
+struct Program { std::vector<int> ops; bool switched = false, late_behind = false; };
+// the switch rule: of `steps` rows the late model runs [switch_at, steps); switch_at == steps or -1: none
+Program switch_program(int steps, int switch_at) {
+    Program p{std::vector<int>((size_t)steps, STEP_FIRST), true, switch_at == steps};
+    for (int k = switch_at; k >= 0 && k < steps; ++k) p.ops[k] = STEP_LATE;
+    return p;
+}
+// the switch row of a table-driven loop's arguments, for switch_program (-1: the late model runs no row)
+template <typename Args>
+int switch_row(const Args* a) { return a->late && a->switch_after >= 0 && a->switch_after < a->n_steps ? a->switch_after : -1; }
+
 // A sampling loop as run_loop drives it: the entry point has run its checks and supplies what differs between the loops
 struct Loop {
     GraphKind kind;
     dd_model* first;
-    dd_model* late;      // the model the loop may switch to (its graphs are captured along with first's), or null
-    int steps;
-    int switch_at;       // late runs steps [switch_at, steps), ev[1] is recorded in front of step switch_at; -1: ev[1] behind the join and the tail
+    dd_model* late;      // the model of the STEP_LATE rows, or null
+    Program program;
     float* x_dev;
     const int64_t* y_dev;
     int B;
@@ -88,30 +128,38 @@ struct Loop {
     bool use_graph;
     std::function<hipError_t(StepState*, hipStream_t)> set_state;                   // a chain's step state at the start of the loop
     std::function<void(GraphKey&, const Slice&)> key;                                // the loop's own fields of a chain's graph key
-    std::function<int(dd_model*, const Chain&, const Slice&, hipStream_t)> step;     // one step of one chain
+    // one step of one chain.  reuse (block caching, a STEP_*_REUSE row): the model's reuse step -- with graphs its second captured graph
+    // (GRAPH_AFFINE_REUSE)
+    std::function<int(dd_model*, const Chain&, const Slice&, bool reuse, hipStream_t)> step;
     std::function<int(int chains, hipStream_t)> tail = nullptr;                      // behind the join of the chains
-    // A walk (dd_sample_affine_walk): what each of the `steps` rows runs, in place of switch_at's rule -- null: none, and the loop enqueues
-    // what it always has.  A jump row runs no model: with graphs it replays the context's captured jump of the chain (dd_ctx::jump_graph,
-    // keyed like a step's graph), eagerly it is jump() itself.  ev[1] is recorded in front of the first late step.
-    const int* program = nullptr;                                                    // [steps] of STEP_FIRST / STEP_LATE / STEP_JUMP / STEP_*_REUSE
-    std::function<int(const Chain&, const Slice&, hipStream_t)> jump = nullptr;      // one jump of one chain
-    // Block caching (dd_sample_affine_cached): a STEP_*_REUSE row runs the model's reuse step -- its second captured graph (GRAPH_AFFINE_REUSE),
-    // eagerly reuse() itself.  admit: called once the chains are decided and before the loop captures, stages or launches anything, with their
-    // number and chain 0's images; it walks the program over the models' cache validity and refuses the call or admits it (the caller makes
-    // the walk the models' validity once run_loop has enqueued the whole loop).
-    std::function<int(dd_model*, const Chain&, const Slice&, hipStream_t)> reuse = nullptr;
+    // one jump of one chain (a STEP_JUMP row).  With graphs the row replays the context's captured jump of the chain (dd_ctx::jump_graph, keyed
+    // like a step's graph)
+    std::function<int(const Chain&, const Slice&, hipStream_t)> jump = nullptr;
+    // called once the chains are decided and before the loop captures, stages or launches anything, with their number and chain 0's images:
+    // refuses the call or admits it
     std::function<int(int chains, int B0, hipStream_t)> admit = nullptr;
 };
-enum StepOp { STEP_FIRST = 0, STEP_LATE = 1, STEP_JUMP = 2, STEP_FIRST_REUSE = 3, STEP_LATE_REUSE = 4, STEP_OPS = 5 };
-// a model's full step, its reuse step, and back
-constexpr int reuse_of(int full) { return full == STEP_LATE ? STEP_LATE_REUSE : STEP_FIRST_REUSE; }
-constexpr bool is_reuse(int op) { return op == STEP_FIRST_REUSE || op == STEP_LATE_REUSE; }
-constexpr int full_of(int op) { return op == STEP_LATE_REUSE ? STEP_LATE : op == STEP_FIRST_REUSE ? STEP_FIRST : op; }
 
-// dd_sample, dd_sample_affine (both also guided) and dd_sample_early_exit: staging, the half-batch chains, graph capture and replay, timing
+// The graphs a call captures, by op.  A loop given by the switch rule captures both models' full step (the late model's where it has one) even
+// when no row runs it; a walk or cached loop captures what its rows name.  late == first is one model: either name stands for both.
+std::array<bool, STEP_OPS> captured_ops(const Loop& L) {
+    std::array<bool, STEP_OPS> uses{};
+    uses[STEP_FIRST] = uses[STEP_LATE] = L.program.switched;
+    for (int op : L.program.ops) uses[op] = true;
+    if (L.late == L.first) {
+        uses[STEP_FIRST] = uses[STEP_LATE] = uses[STEP_FIRST] || uses[STEP_LATE];
+        uses[STEP_FIRST_REUSE] = uses[STEP_LATE_REUSE] = uses[STEP_FIRST_REUSE] || uses[STEP_LATE_REUSE];
+    }
+    return uses;
+}
+
+// Every dd_sample* loop that replays captured steps and both scans: staging, the half-batch chains, graph capture, the rows of the program
+// (replayed or eager), timing.  ev[0] .. ev[2] bracket the loop; ev[1] splits it into the first and the late model's share.
 int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
     const dd_guidance* g = L.mods.g;
     const dd_autoguidance* ag = L.mods.ag;
+    const std::vector<int>& ops = L.program.ops;
+    const int steps = (int)ops.size();
     // Two half-batch chains (graph replays only).  Images are independent and a row's path through the kernels does not depend on the
     // batch size, so chain 0 = images [0, B0) on the caller's stream and chain 1 = images [B0, B) on the context's side stream compute
     // bit for bit what the undivided batch computes (Philox pixel ids carry the image offset) -- with the two chains free to drift apart,
@@ -145,16 +193,8 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
         return sl;
     };
     auto chain = [&](dd_model* m, int k) { return Chain{&m->ws[k], c->st[k], cus, !chained}; };
-    bool uses[STEP_OPS] = {true, true, false, false, false};      // what the rows run: without a walk both models' graphs are captured up front, whoever runs
-    if (L.program) {
-        uses[STEP_FIRST] = uses[STEP_LATE] = false;
-        for (int k = 0; k < L.steps; ++k) uses[L.program[k]] = true;
-        if (L.late == L.first) {
-            uses[STEP_FIRST] = uses[STEP_LATE] = uses[STEP_FIRST] || uses[STEP_LATE];
-            uses[STEP_FIRST_REUSE] = uses[STEP_LATE_REUSE] = uses[STEP_FIRST_REUSE] || uses[STEP_LATE_REUSE];
-        }
-    }
     if (L.use_graph) {
+        const auto uses = captured_ops(L);
         for (int k = 0; k < chains; ++k) {
             const Slice sl = slice(k);
             GraphKey key{sl.x, sl.y, sl.B, 0, 0, cus, nullptr};
@@ -181,59 +221,36 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
                         mkey.aguide = ag->guide; mkey.aserial = ag->guide->serial; mkey.gscale = __builtin_bit_cast(unsigned, ag->scale);
                     }
                 }
-                if (uses[full] && (rc = get_graph(c, m, L.kind, k, mkey, s, [&] { return L.step(m, chain(m, k), sl, s); }))) return rc;
-                if (uses[reuse_of(full)] && (rc = get_graph(c, m, GRAPH_AFFINE_REUSE, k, mkey, s, [&] { return L.reuse(m, chain(m, k), sl, s); }))) return rc;
+                if (uses[full] && (rc = get_graph(c, m, L.kind, k, mkey, s, [&] { return L.step(m, chain(m, k), sl, false, s); }))) return rc;
+                if (uses[reuse_of(full)] && (rc = get_graph(c, m, GRAPH_AFFINE_REUSE, k, mkey, s, [&] { return L.step(m, chain(m, k), sl, true, s); }))) return rc;
             }
         }
     }
     for (int k = 0; k < chains; ++k) DD_HIP(c, L.set_state(c->st[k], s));
-    if (chained) {
-        DD_HIP(c, hipEventRecord(c->ev_fork, s));                 // the side stream starts behind the staging copies and the state
-        DD_HIP(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-    }
-    SideJoin side_join{c, chained};
+    ChainFork chain_fork{c, s, chained};
+    if ((rc = chain_fork.fork())) return rc;
     DD_HIP(c, hipEventRecord(c->ev[0], s));
-    dd_model* cur = L.first;
-    bool split = false;                      // (a walk: ev[1] has been recorded)
-    for (int k = 0; k < L.steps; ++k) {
-        bool reuse = false;                  // (block caching: the row runs cur's reuse step)
-        if (L.program) {
-            int op = L.program[k];
-            if (op == STEP_JUMP) {
-                if (L.use_graph) {
-                    DD_HIP(c, hipGraphLaunch(c->jump_graph[0], s));
-                    if (chained) DD_HIP(c, hipGraphLaunch(c->jump_graph[1], c->side));
-                } else if ((rc = L.jump(chain(L.first, 0), slice(0), s))) {
-                    return rc;
-                }
-                continue;
-            }
-            if (is_reuse(op)) { reuse = true; op = full_of(op); }
-            cur = op == STEP_LATE ? L.late : L.first;
-            if (op == STEP_LATE && !split) {
-                DD_HIP(c, hipEventRecord(c->ev[1], s));
-                split = true;
-            }
-        } else if (k == L.switch_at) {
-            cur = L.late;
-            DD_HIP(c, hipEventRecord(c->ev[1], s));
-        }
+    // ev[1] is recorded in front of row `split`, the first row the late model runs.  It runs none: behind the last row and in front of the
+    // join (split == steps) where the switch rule puts the switch there, else behind the join and the tail (split < 0).
+    int split = L.program.late_behind ? steps : -1;
+    for (int k = steps; k-- > 0;)
+        if (full_of(ops[k]) == STEP_LATE) split = k;
+    for (int k = 0; k < steps; ++k) {
+        if (k == split) DD_HIP(c, hipEventRecord(c->ev[1], s));
+        const bool jump = ops[k] == STEP_JUMP, reuse = is_reuse(ops[k]);
+        dd_model* cur = full_of(ops[k]) == STEP_LATE ? L.late : L.first;       // (a jump: no model runs)
         if (L.use_graph) {
-            const GraphKind kind = reuse ? GRAPH_AFFINE_REUSE : L.kind;
-            DD_HIP(c, hipGraphLaunch(cur->graph[kind][0], s));
-            if (chained) DD_HIP(c, hipGraphLaunch(cur->graph[kind][1], c->side));
-        } else if ((rc = reuse ? L.reuse(cur, chain(cur, 0), slice(0), s) : L.step(cur, chain(cur, 0), slice(0), s))) {
+            const hipGraphExec_t* graphs = jump ? c->jump_graph : cur->graph[reuse ? GRAPH_AFFINE_REUSE : L.kind];
+            DD_HIP(c, hipGraphLaunch(graphs[0], s));
+            if (chained) DD_HIP(c, hipGraphLaunch(graphs[1], c->side));
+        } else if ((rc = jump ? L.jump(chain(cur, 0), slice(0), s) : L.step(cur, chain(cur, 0), slice(0), reuse, s))) {
             return rc;
         }
     }
-    if (!L.program && L.switch_at == L.steps) DD_HIP(c, hipEventRecord(c->ev[1], s));
-    if (chained) {
-        DD_HIP(c, hipEventRecord(c->ev_join, c->side));
-        DD_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0));
-        side_join.armed = false;
-    }
+    if (split == steps) DD_HIP(c, hipEventRecord(c->ev[1], s));
+    if ((rc = chain_fork.join())) return rc;
     if (L.tail && (rc = L.tail(chains, s))) return rc;
-    if (L.program ? !split : L.switch_at < 0) DD_HIP(c, hipEventRecord(c->ev[1], s));
+    if (split < 0) DD_HIP(c, hipEventRecord(c->ev[1], s));
     DD_HIP(c, hipEventRecord(c->ev[2], s));
     if (paired) return unstage_guided(c, L.x_dev, x_run, L.B, B0, chw, s);
     if (x_run != L.x_dev) DD_HIP(c, hipMemcpyAsync(L.x_dev, x_run, (size_t)L.B * chw * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -244,6 +261,15 @@ int run_loop(dd_ctx* c, const Loop& L, hipStream_t s) {
 size_t ee_scratch_elems(const dd_model* m, int B) {
     const size_t chw = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
     return (size_t)B * ((1 + m->cfg.depth) * chw + m->cfg.depth);
+}
+// Where a chain's forward writes eps and the taps it takes (taps.cls null: none, a plain model's forward) -- ee_block: the block of the chain
+// that runs images [b0, b0 + B) in the model's early-exit scratch, eps | cls | outs
+struct EeBlock { float* eps; EeTaps taps; };
+EeBlock ee_block(const dd_model* m, int b0, int B) {
+    const size_t chw = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
+    float* eps = m->ee_ws + ee_scratch_elems(m, b0);
+    float* cls = eps + (size_t)B * chw;                 // [depth, B]
+    return EeBlock{eps, EeTaps{cls, cls + (size_t)m->cfg.depth * B, 0}};
 }
 
 // dd_profile_steps (chains == 1) and dd_profile_steps_chained (chains == 2: dd_sample's two half-batch chains enqueued eagerly on `stream`
@@ -262,11 +288,8 @@ int profile_steps(dd_ctx* c, dd_model* m, float* x_dev, const int64_t* y_dev, in
     const int B0 = B / chains;
     const size_t chw = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
     const int cus = chained ? chain_gemm_cus(c, m, B) : c->num_cus;     // (both chains' persistent GEMM grids sized as dd_sample sizes them)
-    if (chained) {
-        DD_HIP(c, hipEventRecord(c->ev_fork, s));
-        DD_HIP(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-    }
-    SideJoin side_join{c, chained};
+    ChainFork chain_fork{c, s, chained};
+    if ((rc = chain_fork.fork())) return rc;
     m->time_fc1 = true;
     m->fc1_used = 0;
     for (int i = 0; i < steps && !rc; ++i) {
@@ -280,12 +303,7 @@ int profile_steps(dd_ctx* c, dd_model* m, float* x_dev, const int64_t* y_dev, in
         }
     }
     m->time_fc1 = false;
-    if (rc) return rc;
-    if (chained) {
-        DD_HIP(c, hipEventRecord(c->ev_join, c->side));
-        DD_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0));
-        side_join.armed = false;
-    }
+    if (rc || (rc = chain_fork.join())) return rc;
     DD_HIP(c, hipStreamSynchronize(s));
     double total = 0.0;
     for (size_t i = 0; i + 1 < m->fc1_used; i += 2) {
@@ -408,121 +426,48 @@ int sample_ddpm(dd_ctx* c, const dd_sample_args* a, Mods mo, void* stream) {
     };
     if ((rc = stage_image_seeds(c, a->noise_mode, (hipStream_t)stream, &mo.seeds))) return rc;
     if ((rc = stage_known(c, mo, a->first, a->B, 1000, (hipStream_t)stream, known_row))) return rc;
-    Loop L{GRAPH_DDPM, a->first, switching ? a->late : nullptr, n, switch_here ? a->t_start - t_sw + 1 : -1, a->x_dev, a->y_dev, a->B, mo,
-           a->use_graph != 0};
+    Loop L{GRAPH_DDPM, a->first, switching ? a->late : nullptr, switch_program(n, switch_here ? a->t_start - t_sw + 1 : -1), a->x_dev, a->y_dev,
+           a->B, mo, a->use_graph != 0};
     L.set_state = [&](StepState* st, hipStream_t s) { return launch_set_state(st, a->t_start, (unsigned long long)a->seed, s); };
     L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.variance = a->variance; };
-    L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t s) {
+    L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, bool, hipStream_t s) {
         return enqueue_step(c, m, ch, sl.x, sl.y, sl.B, s,
                             {.mods = sl.mods, .noise_mode = a->noise_mode, .variance = a->variance, .advance = 1, .b0 = sl.b0});
     };
     return run_loop(c, L, (hipStream_t)stream);
 }
 
-// dd_sample_affine and its _guided, _autoguided and _region forms: one path
-// w (dd_sample_affine_walk; its own checks have passed): the rows' program -- a jump row runs launch_jump, a step row the model w->late names
-// (null: switch_after's rule)
-// bc (dd_sample_affine_cached; its own checks have passed): block caching -- a row with op != 0 runs its model's reuse step
-int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, Mods mo, void* stream, const dd_walk* w = nullptr, const dd_block_cache* bc = nullptr) {
-    int rc = check_loop(c, a, mo, w ? "resampling jumps are not supported for early-exit models" : bc ? "block caching is not supported for early-exit models" : nullptr,
-                        w ? "dd_sample_affine_walk generates noise on the device; for host noise drive dd_forward, dd_affine_step, dd_known_blend and dd_jump_step"
-                        : bc ? "dd_sample_affine_cached generates noise on the device; for host noise drive dd_forward_cached + dd_affine_step"
-                          : "dd_sample_affine generates noise on the device; for host noise drive dd_forward + dd_affine_step",
-                        [&] { return check_table(c, a); });
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int n = a->n_steps;
-    const bool switching = a->late && a->switch_after >= 0 && a->switch_after < n;
-    std::vector<int> program;
-    if (w) {
-        if (a->first->cfg.in_chans > 4) return ctx_fail(c, DD_ERR_UNSUPPORTED, "a resampling jump draws one Philox block per pixel: at most 4 channels");
-        program.resize((size_t)n);
-        for (int k = 0; k < n; ++k)
-            program[k] = w->jump[k] ? STEP_JUMP : (w->late ? w->late[k] != 0 : switching && k >= a->switch_after) ? STEP_LATE : STEP_FIRST;
-    }
-    if (bc) {       // the rows' program, and the checks that need the models: K against every model that runs a step
-        program.resize((size_t)n);
-        for (int k = 0; k < n; ++k) {
-            const bool late = switching && k >= a->switch_after;
-            program[k] = bc->op[k] ? reuse_of(late ? STEP_LATE : STEP_FIRST) : late ? STEP_LATE : STEP_FIRST;
-            if ((rc = check_cached(c, late ? a->late : a->first, bc->blocks))) return rc;
-        }
-    }
-    if ((rc = stage_image_seeds(c, a->noise_mode, s, &mo.seeds))) return rc;
-    if ((rc = upload_atab(c, a, s, bc))) return rc;
-    if ((rc = stage_table_known(c, mo, a->first, a->B, n, s))) return rc;
+// What dd_sample_affine, dd_sample_affine_walk and dd_sample_affine_cached share.  The loop's checks, with the entry's two rejection texts,
+int check_affine(dd_ctx* c, const dd_affine_sample_args* a, const Mods& mo, const char* no_early_exit, const char* host_noise) {
+    return check_loop(c, a, mo, no_early_exit, host_noise, [&] { return check_table(c, a); });
+}
+// and behind them: the seeds, the step table (bc: upload_atab) and the known rows staged on s, and the loop of switch_after's rule over that
+// table (two half-batch chains, as dd_sample: both read the one step table; each has its own step index and Philox image offset)
+int affine_loop(dd_ctx* c, const dd_affine_sample_args* a, Mods mo, hipStream_t s, const dd_block_cache* bc, Loop& L) {
+    int rc = stage_image_seeds(c, a->noise_mode, s, &mo.seeds);
+    if (rc || (rc = upload_atab(c, a, s, bc)) || (rc = stage_table_known(c, mo, a->first, a->B, a->n_steps, s))) return rc;
     const AffineRow* atab = c->atab.dev.p;
-    // (two half-batch chains, as dd_sample: both read the one step table; each has its own step index and Philox image offset)
-    Loop L{GRAPH_AFFINE, a->first, switching ? a->late : nullptr, n, switching ? a->switch_after : -1, a->x_dev, a->y_dev, a->B, mo,
-           a->use_graph != 0};
-    L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_table(st, atab, (unsigned long long)a->seed, ss); };
-    L.key = [&](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.atab = atab; };
-    L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
+    const int sw = switch_row(a);
+    L = Loop{GRAPH_AFFINE, a->first, sw >= 0 ? a->late : nullptr, switch_program(a->n_steps, sw), a->x_dev, a->y_dev, a->B, mo, a->use_graph != 0};
+    L.set_state = [=](StepState* st, hipStream_t ss) { return launch_set_state_table(st, atab, (unsigned long long)a->seed, ss); };
+    L.key = [=](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.atab = atab; };
+    L.step = [=](dd_model* m, const Chain& ch, const Slice& sl, bool, hipStream_t ss) {
         return enqueue_step(c, m, ch, sl.x, sl.y, sl.B, ss, {.mods = sl.mods, .noise_mode = a->noise_mode, .advance = 1, .atab = atab, .b0 = sl.b0});
     };
-    std::vector<std::pair<BlockCache*, BlockCache>> walked;      // (block caching: each cache the call runs on, and what the walk leaves in it)
-    if (bc) {
-        auto cached_step = [&, bc](bool reuse) {
-            // order 1: a refresh rotates prev <- last first, and a reuse goes through the kernel, which reads the row's op and w
-            const CacheUse cu{bc->blocks, reuse, !reuse && bc->order == 1, reuse && bc->order == 1, 0.f, reuse && bc->order == 1 ? atab : nullptr};
-            return [&, cu](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
-                return enqueue_step(c, m, ch, sl.x, sl.y, sl.B, ss,
-                                    {.mods = sl.mods, .cache = cu, .noise_mode = a->noise_mode, .advance = 1, .atab = atab, .b0 = sl.b0});
-            };
-        };
-        L.step = cached_step(false);
-        L.reuse = cached_step(true);
-        L.key = [&, bc](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.atab = atab; k.cblocks = bc->blocks; k.corder = bc->order; };
-        L.program = program.data();
-        // the program walked over the models' cache validity for the chains run_loop has decided on (Loop::admit): a reuse row needs a refresh of
-        // its model, chain geometry and K in front of it -- in this call or left by an earlier one -- and an extrapolating row two of them
-        L.admit = [&, bc](int chains, int B0, hipStream_t ss) -> int {
-            dd_model* models[2] = {a->first, switching ? a->late : nullptr};
-            BlockCache sim[2][2];
-            for (int ck = 0; ck < chains; ++ck) {
-                const int b0 = ck ? B0 : 0, Bk = ck ? a->B - B0 : B0, rows = mo.g ? 2 * Bk : Bk;
-                for (int i = 0; i < 2; ++i) if (models[i]) sim[ck][i] = models[i]->cache[ck];
-                for (int k = 0; k < n; ++k) {
-                    const int i = (full_of(program[k]) == STEP_LATE && models[1] != models[0]) ? 1 : 0;
-                    BlockCache& v = sim[ck][i];
-                    if (bc->op[k] == CACHE_REFRESH) { v.refresh(bc->blocks, rows, b0, Bk, bc->order == 1); continue; }
-                    if (!v.holds(bc->blocks, rows, b0, Bk))
-                        return ctx_fail(c, DD_ERR_INVALID, "block caching: row " + std::to_string(k) + " is a reuse step, and its model holds no refresh of this batch and these blocks");
-                    if (bc->op[k] == CACHE_EXTRAPOLATE && !v.has_prev)
-                        return ctx_fail(c, DD_ERR_INVALID, "block caching: row " + std::to_string(k) + " extrapolates, and its model holds no second refresh of this batch and these blocks");
-                }
-            }
-            for (int ck = 0; ck < chains; ++ck)
-                for (int i = 0; i < 2; ++i) {
-                    if (!models[i] || (i && models[1] == models[0])) continue;
-                    if (int r = ensure_block_cache(c, models[i], ck, ss)) { walked.clear(); return r; }
-                    walked.push_back({&models[i]->cache[ck], sim[ck][i]});
-                }
-            return DD_OK;
-        };
-    }
-    if (w) {
-        if (w->late) L.late = a->late;       // (the rows name their model; null where no row runs it: checked)
-        L.switch_at = -1;
-        L.program = program.data();
-        L.jump = [&](const Chain& ch, const Slice& sl, hipStream_t ss) -> int {      // (guided: the chain's twins stand sl.B images on)
-            DD_HIP(c, launch_jump(sl.x, ch.st, atab, sl.mods.seeds, sl.B, a->first->cfg.in_chans, a->first->cfg.img_size, sl.b0, mo.g ? sl.B : 0,
-                                  a->noise_mode, ss));
-            return DD_OK;
-        };
-    }
-    rc = run_loop(c, L, s);
-    // the walk becomes the models' validity once the whole loop is enqueued; a call that fails behind the walk (a capture, a copy, a launch) may
-    // have rotated or half-written the buffers, so they then hold nothing
-    for (auto& [d, v] : walked) {
-        if (rc) { d->has_last = d->has_prev = false; continue; }
-        d->K = v.K; d->rows = v.rows; d->b0 = v.b0; d->B = v.B; d->has_last = v.has_last; d->has_prev = v.has_prev;
-    }
-    return rc;
+    return DD_OK;
+}
+
+// dd_sample_affine and its _guided, _autoguided, _region and _perturbed forms: one path
+int sample_affine(dd_ctx* c, const dd_affine_sample_args* a, Mods mo, void* stream) {
+    int rc = check_affine(c, a, mo, nullptr, "dd_sample_affine generates noise on the device; for host noise drive dd_forward + dd_affine_step");
+    Loop L;
+    if (rc || (rc = affine_loop(c, a, mo, (hipStream_t)stream, nullptr, L))) return rc;
+    return run_loop(c, L, (hipStream_t)stream);
 }
 
 // dd_sample_affine_walk: its own checks, in front of the loop's (the table's pointers and n_steps are checked there: unreadable ones are left
-// to it), then dd_sample_affine's path with the walk
+// to it), then dd_sample_affine's loop with the rows the walk names: a jump row runs launch_jump, a step row the model w->late names (null:
+// switch_after's rule)
 int sample_affine_walk(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, const dd_autoguidance* ag, const dd_known_region* kr,
                        const dd_walk* w, void* stream) {
     if (!c) return DD_ERR_INVALID;
@@ -539,13 +484,71 @@ int sample_affine_walk(dd_ctx* c, const dd_affine_sample_args* a, const dd_guida
         }
     }
     if (g && ag) return ctx_fail(c, DD_ERR_INVALID, "classifier-free guidance and autoguidance are exclusive");
-    return sample_affine(c, a, Mods{.g = g, .ag = ag, .kr = kr, .region = kr != nullptr}, stream, w);
+    const Mods mo{.g = g, .ag = ag, .kr = kr, .region = kr != nullptr};
+    int rc = check_affine(c, a, mo, "resampling jumps are not supported for early-exit models",
+                          "dd_sample_affine_walk generates noise on the device; for host noise drive dd_forward, dd_affine_step, dd_known_blend and dd_jump_step");
+    if (rc) return rc;
+    if (a->first->cfg.in_chans > 4) return ctx_fail(c, DD_ERR_UNSUPPORTED, "a resampling jump draws one Philox block per pixel: at most 4 channels");
+    hipStream_t s = (hipStream_t)stream;
+    Loop L;
+    if ((rc = affine_loop(c, a, mo, s, nullptr, L))) return rc;
+    for (int k = 0; k < a->n_steps; ++k) {
+        if (w->jump[k]) L.program.ops[k] = STEP_JUMP;
+        else if (w->late) L.program.ops[k] = w->late[k] ? STEP_LATE : STEP_FIRST;
+    }
+    L.program.switched = false;          // (the call captures what its rows name)
+    if (w->late) L.late = a->late;       // (the rows name their model; null where no row runs it: checked)
+    const AffineRow* atab = c->atab.dev.p;
+    L.jump = [=](const Chain& ch, const Slice& sl, hipStream_t ss) -> int {      // (guided: the chain's twins stand sl.B images on)
+        DD_HIP(c, launch_jump(sl.x, ch.st, atab, sl.mods.seeds, sl.B, a->first->cfg.in_chans, a->first->cfg.img_size, sl.b0, g ? sl.B : 0,
+                              a->noise_mode, ss));
+        return DD_OK;
+    };
+    return run_loop(c, L, s);
+}
+
+// Block caching: each cache a call runs on, and what the call's rows leave in it
+using CacheWalk = std::vector<std::pair<BlockCache*, BlockCache>>;
+// The rows of a cached loop walked over its models' cache validity, for the chains run_loop has decided on (Loop::admit): a reuse row needs a
+// refresh of its model, chain geometry and K in front of it -- in this call or left by an earlier one -- and an extrapolating row two of them
+int walk_cache_validity(dd_ctx* c, const Loop& L, const dd_block_cache* bc, int chains, int B0, hipStream_t s, CacheWalk& walked) {
+    dd_model* models[2] = {L.first, L.late};
+    BlockCache sim[2][2];
+    for (int ck = 0; ck < chains; ++ck) {
+        const int b0 = ck ? B0 : 0, Bk = ck ? L.B - B0 : B0, rows = L.mods.g ? 2 * Bk : Bk;
+        for (int i = 0; i < 2; ++i) if (models[i]) sim[ck][i] = models[i]->cache[ck];
+        for (int k = 0; k < (int)L.program.ops.size(); ++k) {
+            const int i = (full_of(L.program.ops[k]) == STEP_LATE && models[1] != models[0]) ? 1 : 0;
+            BlockCache& v = sim[ck][i];
+            if (bc->op[k] == CACHE_REFRESH) { v.refresh(bc->blocks, rows, b0, Bk, bc->order == 1); continue; }
+            if (!v.holds(bc->blocks, rows, b0, Bk))
+                return ctx_fail(c, DD_ERR_INVALID, "block caching: row " + std::to_string(k) + " is a reuse step, and its model holds no refresh of this batch and these blocks");
+            if (bc->op[k] == CACHE_EXTRAPOLATE && !v.has_prev)
+                return ctx_fail(c, DD_ERR_INVALID, "block caching: row " + std::to_string(k) + " extrapolates, and its model holds no second refresh of this batch and these blocks");
+        }
+    }
+    for (int ck = 0; ck < chains; ++ck)
+        for (int i = 0; i < 2; ++i) {
+            if (!models[i] || (i && models[1] == models[0])) continue;
+            if (int r = ensure_block_cache(c, models[i], ck, s)) { walked.clear(); return r; }
+            walked.push_back({&models[i]->cache[ck], sim[ck][i]});
+        }
+    return DD_OK;
+}
+// The walk becomes the models' validity once the whole loop is enqueued (rc: run_loop's).  A call that fails behind the walk (a capture, a
+// copy, a launch) may have rotated or half-written the buffers, so they then hold nothing.
+void commit_cache_walk(const CacheWalk& walked, int rc) {
+    for (auto& [d, v] : walked) {
+        if (rc) { d->has_last = d->has_prev = false; continue; }
+        d->K = v.K; d->rows = v.rows; d->b0 = v.b0; d->B = v.B; d->has_last = v.has_last; d->has_prev = v.has_prev;
+    }
 }
 
 // dd_sample_affine_cached: its own checks, in front of the loop's (the table's pointers and n_steps are checked there), then dd_sample_affine's
-// path with the cache.  What needs the models or the chains -- K against each model that runs a step, the walk over the cache validity -- is
-// checked on that path: K before anything is enqueued, the walk (Loop::admit) behind the copies of the table, the seeds and the known rows into
-// the context's staging buffers and in front of every capture, copy or launch that touches x, a workspace or a cache.
+// loop with the cache: a row with op != 0 runs its model's reuse step.  What needs the models or the chains is checked behind the loop's
+// checks: K against every model that runs a step before anything is enqueued, the walk over the cache validity (Loop::admit) behind the copies
+// of the table, the seeds and the known rows into the context's staging buffers and in front of every capture, copy or launch that touches x, a
+// workspace or a cache.
 int sample_affine_cached(dd_ctx* c, const dd_affine_sample_args* a, const dd_guidance* g, const dd_known_region* kr, const dd_block_cache* bc,
                          void* stream) {
     if (!c) return DD_ERR_INVALID;
@@ -560,7 +563,32 @@ int sample_affine_cached(dd_ctx* c, const dd_affine_sample_args* a, const dd_gui
                 return ctx_fail(c, DD_ERR_INVALID, "block caching: op[" + std::to_string(k) + "] extrapolates under order 0");
         }
     }
-    return sample_affine(c, a, Mods{.g = g, .kr = kr, .region = kr != nullptr}, stream, nullptr, bc);
+    const Mods mo{.g = g, .kr = kr, .region = kr != nullptr};
+    int rc = check_affine(c, a, mo, "block caching is not supported for early-exit models",
+                          "dd_sample_affine_cached generates noise on the device; for host noise drive dd_forward_cached + dd_affine_step");
+    if (rc) return rc;
+    const int sw = switch_row(a);
+    for (int k = 0; k < a->n_steps; ++k)
+        if ((rc = check_cached(c, sw >= 0 && k >= sw ? a->late : a->first, bc->blocks))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Loop L;
+    if ((rc = affine_loop(c, a, mo, s, bc, L))) return rc;
+    for (int k = 0; k < a->n_steps; ++k)
+        if (bc->op[k]) L.program.ops[k] = reuse_of(L.program.ops[k]);
+    L.program.switched = false;          // (the call captures what its rows name)
+    const AffineRow* atab = c->atab.dev.p;
+    L.key = [=](GraphKey& k, const Slice&) { k.noise = a->noise_mode; k.atab = atab; k.cblocks = bc->blocks; k.corder = bc->order; };
+    L.step = [=](dd_model* m, const Chain& ch, const Slice& sl, bool reuse, hipStream_t ss) {
+        // order 1: a refresh rotates prev <- last first, and a reuse goes through the kernel, which reads the row's op and w
+        const bool order1 = bc->order == 1;
+        const CacheUse cu{bc->blocks, reuse, !reuse && order1, reuse && order1, 0.f, reuse && order1 ? atab : nullptr};
+        return enqueue_step(c, m, ch, sl.x, sl.y, sl.B, ss, {.mods = sl.mods, .cache = cu, .noise_mode = a->noise_mode, .advance = 1, .atab = atab, .b0 = sl.b0});
+    };
+    CacheWalk walked;
+    L.admit = [&](int chains, int B0, hipStream_t ss) { return walk_cache_validity(c, L, bc, chains, B0, ss, walked); };
+    rc = run_loop(c, L, s);
+    commit_cache_walk(walked, rc);
+    return rc;
 }
 
 // dd_sample_multistep and its forms: dd_sample_affine's loop with the history register.  h is staged like x: copied into the context's
@@ -582,7 +610,7 @@ int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, Mods mo, void
     }
     hipStream_t s = (hipStream_t)stream;
     const int n = a->n_steps;
-    const bool switching = a->late && a->switch_after >= 0 && a->switch_after < n;
+    const int sw = switch_row(a);
     if ((rc = stage_image_seeds(c, a->noise_mode, s, &mo.seeds))) return rc;
     if ((rc = upload_atab(c, a, s))) return rc;
     rc = upload_rows(c, c->htab, (size_t)n + 1, s, [a, n](size_t k) {
@@ -600,8 +628,7 @@ int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, Mods mo, void
     if ((rc = stage_table_known(c, mo, a->first, a->B, n, s))) return rc;
     const AffineRow* atab = c->atab.dev.p;
     const HistRow* htab = c->htab.dev.p;
-    Loop L{GRAPH_MULTISTEP, a->first, switching ? a->late : nullptr, n, switching ? a->switch_after : -1, a->x_dev, a->y_dev, a->B, mo,
-           a->use_graph != 0};
+    Loop L{GRAPH_MULTISTEP, a->first, sw >= 0 ? a->late : nullptr, switch_program(n, sw), a->x_dev, a->y_dev, a->B, mo, a->use_graph != 0};
     L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_table(st, atab, (unsigned long long)a->seed, ss); };
     L.key = [&](GraphKey& k, const Slice&) {
         k.noise = a->noise_mode; k.atab = atab; k.aux0 = htab; k.aux1 = h_run;
@@ -611,7 +638,7 @@ int sample_multistep(dd_ctx* c, const dd_multistep_sample_args* a, Mods mo, void
             k.ts = __builtin_bit_cast(unsigned, mo.thr->s_max);
         }
     };
-    L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, hipStream_t ss) {
+    L.step = [&](dd_model* m, const Chain& ch, const Slice& sl, bool, hipStream_t ss) {
         return enqueue_step(c, m, ch, sl.x, sl.y, sl.B, ss, {.mods = sl.mods, .noise_mode = a->noise_mode, .advance = 1, .atab = atab, .b0 = sl.b0,
                                                              .htab = htab, .h = h_run + (size_t)sl.b0 * chw, .thr = thr_p,
                                                              .m_scratch = m_run ? m_run + (size_t)sl.b0 * chw : nullptr});
@@ -664,29 +691,27 @@ int stage_scan(dd_ctx* c, const Args* a, size_t rows, F&& row, size_t result_ele
     return DD_OK;
 }
 
-// where a chain's forward of a scan step writes its output, and the taps it takes (tapped: an early-exit model's)
-struct ScanForward { float* eps; EeTaps ee; bool tapped; };
 // a result table of a scan, copied to the caller's tensor behind the loop, so that a captured step never names it
 struct ScanOut { float* dst; const float* src; size_t elems; };
 
 // The loop of a staged scan: `kind`'s graphs, the step state started at row first_row, key(k) the entry's own key fields, forward(m, slice)
-// the chain's ScanForward, error(f, x0, chain, slice, s) the launch that ends the step, and outs
+// the chain's EeBlock (no taps: a plain model's), error(f, x0, chain, slice, s) the launch that ends the step, and outs
 template <typename Args, typename Key, typename Forward, typename Error>
 int run_scan(dd_ctx* c, const Args* a, const ScanStage& g, GraphKind kind, int first_row, Key&& key, Forward&& forward, Error&& error,
              std::initializer_list<ScanOut> outs, hipStream_t s) {
     const int C = a->model->cfg.in_chans, S = a->model->cfg.img_size;
-    Loop L{kind, a->model, nullptr, a->n_steps, -1, c->scan_ws.p, a->y_dev, a->B, Mods{.seeds = g.seeds}, a->use_graph != 0};
+    Loop L{kind, a->model, nullptr, switch_program(a->n_steps, -1), c->scan_ws.p, a->y_dev, a->B, Mods{.seeds = g.seeds}, a->use_graph != 0};
     L.set_state = [&](StepState* st, hipStream_t ss) { return launch_set_state_scan(st, g.tab, (unsigned long long)a->seed, ss, first_row); };
     L.key = [&](GraphKey& k, const Slice& sl) {
         k.noise = a->noise_mode; k.atab = g.tab; k.kx0 = g.x0 + (size_t)sl.b0 * g.chw;
         key(k);
         if (sl.chains == 2 && sl.chain == 0) k.b0 = -1;     // (chain 0 of two writes rows of 2 B images -- not the whole batch's graph)
     };
-    L.step = [&](dd_model* mm, const Chain& ch, const Slice& sl, hipStream_t ss) -> int {
+    L.step = [&](dd_model* mm, const Chain& ch, const Slice& sl, bool, hipStream_t ss) -> int {
         const float* x0 = g.x0 + (size_t)sl.b0 * g.chw;
-        const ScanForward f = forward(mm, sl);
+        const EeBlock f = forward(mm, sl);
         DD_HIP(c, launch_scan_diffuse(x0, sl.x, ch.st, g.tab, sl.mods.seeds, sl.B, C, S, sl.b0, ss));
-        if (int r = forward_eps(c, mm, ch, sl.x, sl.y, f.eps, sl.B, ss, {.ee = f.tapped ? &f.ee : nullptr})) return r;
+        if (int r = forward_eps(c, mm, ch, sl.x, sl.y, f.eps, sl.B, ss, {.ee = f.taps.cls ? &f.taps : nullptr})) return r;
         DD_HIP(c, error(f, x0, ch, sl, ss));
         return DD_OK;
     };
@@ -718,8 +743,8 @@ int scan_error(dd_ctx* c, const dd_scan_args* a, void* stream) {
     float* eps_run = g.results;
     float* err_run = eps_run + g.elems;
     return run_scan(c, a, g, GRAPH_SCAN, 0, [&](GraphKey& k) { k.aux0 = err_run; k.aux1 = eps_run; },
-                    [&](dd_model*, const Slice& sl) { return ScanForward{eps_run + (size_t)sl.b0 * g.chw, {}, false}; },
-                    [&](const ScanForward& f, const float* x0, const Chain& ch, const Slice& sl, hipStream_t ss) {
+                    [&](dd_model*, const Slice& sl) { return EeBlock{eps_run + (size_t)sl.b0 * g.chw, {}}; },
+                    [&](const EeBlock& f, const float* x0, const Chain& ch, const Slice& sl, hipStream_t ss) {
                         return launch_scan_error(x0, f.eps, err_run, ch.st, g.tab, sl.mods.seeds, sl.B, C, S, sl.b0, a->B, 1, ss);
                     },
                     {{a->err_dev, err_run, err_elems}}, s);
@@ -771,16 +796,45 @@ int scan_exits(dd_ctx* c, const dd_scan_exits_args* a, void* stream) {
     float* tgt_run = mse_run + mse_elems;
     float* pred_run = tgt_run + mse_elems;
     return run_scan(c, a, g, GRAPH_SCAN_EXITS, (int)a->t[0], [&](GraphKey& k) { k.variance = n; k.aux0 = mse_run; k.aux1 = m->ee_ws; },
-                    [&](dd_model* mm, const Slice& sl) {      // the chain's block: eps | cls | outs (enqueue_ee_step's layout)
-                        float* eps = mm->ee_ws + ee_scratch_elems(mm, sl.b0);
-                        float* cls = eps + (size_t)sl.B * g.chw;
-                        return ScanForward{eps, EeTaps{cls, cls + (size_t)depth * sl.B, 0}, true};
-                    },
-                    [&](const ScanForward& f, const float* x0, const Chain& ch, const Slice& sl, hipStream_t ss) {
-                        return launch_scan_exits_error(x0, f.ee.outs, f.eps, f.ee.cls, mse_run, tgt_run, pred_run, ch.st, g.tab, sl.mods.seeds, sl.B, C, S,
+                    [&](dd_model* mm, const Slice& sl) { return ee_block(mm, sl.b0, sl.B); },
+                    [&](const EeBlock& f, const float* x0, const Chain& ch, const Slice& sl, hipStream_t ss) {
+                        return launch_scan_exits_error(x0, f.taps.outs, f.eps, f.taps.cls, mse_run, tgt_run, pred_run, ch.st, g.tab, sl.mods.seeds, sl.B, C, S,
                                                        E, sl.b0, a->B, 1, ss);
                     },
                     {{a->mse_dev, mse_run, mse_elems}, {a->target_dev, tgt_run, mse_elems}, {a->pred_dev, pred_run, pred_elems}}, s);
+}
+
+// One early-exit sampling step on the device (reference eesampler.py:56-81): EarlyExitUViT.forward with every head and
+// probe -> per-sample exit selection -> DDPM update with the selected output; rows t of the two log tables are written.
+// b0 / B_all: the chain's first image within the whole batch (its scratch block: ee_block) and the whole batch (idx_tab rows are B_all wide);
+// seeds: the whole batch's staged per-image seeds or null; sums: err_tab is the chain's table of per-layer SUMS (launch_ee_mean_combine joins the chains)
+int enqueue_ee_step(dd_ctx* c, dd_model* m, const Chain& ch, float* x, const int64_t* y, float thr, float* err_tab, int32_t* idx_tab,
+                    int noise_mode, int B, hipStream_t s, int b0, int B_all, bool sums, const unsigned long long* seeds) {
+    const EeBlock blk = ee_block(m, b0, B);
+    if (int rc = forward_eps(c, m, ch, x, y, blk.eps, B, s, {.ee = &blk.taps})) return rc;
+    // exit layer per image, the selected output and the DDPM update in one launch (dd_early_exit_select + the step kernel, fused: same arithmetic)
+    DD_HIP(c, launch_ee_select_step(x, blk.taps.outs, blk.eps, blk.taps.cls, thr, m->cfg.depth, idx_tab, err_tab, B_all, b0, sums, ch.st, c->coef, B,
+                                    m->cfg.in_chans, m->cfg.img_size, noise_mode, 1, s, seeds));
+    return DD_OK;
+}
+
+// What dd_sample_early_exit and dd_sample_early_exit_real (`entry`: the one that is called) share in front of their loops: the checks, in this
+// order and with the entry's own between them -- behind_tensor() behind the check of x_dev, behind_noise() behind the noise mode's -- then the
+// image seeds staged on s and the model's early-exit scratch
+int ee_sample_setup(dd_ctx* c, const dd_ee_sample_args* a, const char* entry, hipStream_t s, const unsigned long long** seeds,
+                    const std::function<int()>& behind_tensor = nullptr, const std::function<int()>& behind_noise = nullptr) {
+    if (!c || !a) return DD_ERR_INVALID;
+    dd_model* m = a->model;
+    int rc = check_call(c, m, a->B, a->y_dev);
+    if (rc) return rc;
+    if (m->ee_type < 0) return ctx_fail(c, DD_ERR_STATE, "model was not created with dd_model_enable_early_exit");
+    if (!a->x_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
+    if (behind_tensor && (rc = behind_tensor())) return rc;
+    if (a->t_start > 999 || a->t_end < 0 || a->t_end > a->t_start) return ctx_fail(c, DD_ERR_INVALID, "need 999 >= t_start >= t_end >= 0");
+    if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE)
+        return ctx_fail(c, DD_ERR_INVALID, std::string(entry) + " generates noise on the device; for host noise drive dd_forward_early_exit");
+    if ((behind_noise && (rc = behind_noise())) || (rc = check_image_seeds(c, a->noise_mode, a->B))) return rc;
+    return (rc = stage_image_seeds(c, a->noise_mode, s, seeds)) ? rc : ensure_ee_ws(c, m);
 }
 }  // namespace
 
@@ -838,55 +892,27 @@ int dd_sample_multistep_threshold(dd_ctx* c, const dd_multistep_sample_args* a, 
     return sample_multistep(c, a, thresholding(g, ag, kr, thr), stream);
 }
 
-// One early-exit sampling step on the device (reference eesampler.py:56-81): EarlyExitUViT.forward with every head and
-// probe -> per-sample exit selection -> DDPM update with the selected output; rows t of the two log tables are written.
-// ws: the chain's scratch block (eps | cls | outs for B images, ee_scratch_elems); b0 / B_all: the chain's first image within the whole batch
-// and the whole batch (idx_tab rows are B_all wide); seeds: the whole batch's staged per-image seeds or null; sums: err_tab is the chain's table of per-layer SUMS (launch_ee_mean_combine joins the chains)
-static int enqueue_ee_step(dd_ctx* c, dd_model* m, const Chain& ch, float* ws, float* x, const int64_t* y, float thr, float* err_tab,
-                           int32_t* idx_tab, int noise_mode, int B, hipStream_t s, int b0, int B_all, bool sums, const unsigned long long* seeds) {
-    const long long chw = (long long)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
-    const int depth = m->cfg.depth;
-    float* eps = ws;
-    float* cls = eps + (size_t)B * chw;
-    float* outs = cls + (size_t)depth * B;
-    const EeTaps ee{cls, outs, 0};
-    if (int rc = forward_eps(c, m, ch, x, y, eps, B, s, {.ee = &ee})) return rc;
-    // exit layer per image, the selected output and the DDPM update in one launch (dd_early_exit_select + the step kernel, fused: same arithmetic)
-    DD_HIP(c, launch_ee_select_step(x, outs, eps, cls, thr, depth, idx_tab, err_tab, B_all, b0, sums, ch.st, c->coef, B,
-                                    m->cfg.in_chans, m->cfg.img_size, noise_mode, 1, s, seeds));
-    return DD_OK;
-}
-
 int dd_sample_early_exit(dd_ctx* c, const dd_ee_sample_args* a, void* stream) {
-    if (!c || !a) return DD_ERR_INVALID;
-    dd_model* m = a->model;
-    int rc = check_call(c, m, a->B, a->y_dev);
-    if (rc) return rc;
-    if (m->ee_type < 0) return ctx_fail(c, DD_ERR_STATE, "model was not created with dd_model_enable_early_exit");
-    if (!a->x_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
-    if (a->t_start > 999 || a->t_end < 0 || a->t_end > a->t_start) return ctx_fail(c, DD_ERR_INVALID, "need 999 >= t_start >= t_end >= 0");
-    if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE)
-        return ctx_fail(c, DD_ERR_INVALID, "dd_sample_early_exit generates noise on the device; for host noise drive dd_forward_early_exit");
-    if ((rc = check_image_seeds(c, a->noise_mode, a->B))) return rc;
     const unsigned long long* seeds = nullptr;
-    if ((rc = stage_image_seeds(c, a->noise_mode, (hipStream_t)stream, &seeds))) return rc;
+    if (int rc = ee_sample_setup(c, a, "dd_sample_early_exit", (hipStream_t)stream, &seeds)) return rc;
+    dd_model* m = a->model;
     // Two half-batch chains, as dd_sample: the samples are independent (every exit decision is per sample); the one quantity over the whole
     // batch -- the logged per-layer mean of the predicted errors, eesampler.py:70 -- becomes per-chain sums that one small launch joins
     // behind the loop, (chain 0 + chain 1) / B.  Heads and probes stay on each chain's own stream (measured: the 13 forks as parallel
     // branches of each chain's graph cost +0.9 ms per step -- 5.22 against 4.23 ms; profiles/r05/ab_round5.txt).
     const size_t tab = (size_t)1000 * m->cfg.depth;
-    if ((rc = ensure_ee_ws(c, m))) return rc;
     float* sums = m->ee_ws + ee_scratch_elems(m, m->cfg.max_batch);
     auto err_tab = [&](const Slice& sl) { return sl.chains == 1 || !a->err_dev ? a->err_dev : sums + sl.chain * tab; };
-    Loop L{GRAPH_EARLY_EXIT, m, nullptr, a->t_start - a->t_end + 1, -1, a->x_dev, a->y_dev, a->B, Mods{.seeds = seeds}, a->use_graph != 0};
+    Loop L{GRAPH_EARLY_EXIT, m, nullptr, switch_program(a->t_start - a->t_end + 1, -1), a->x_dev, a->y_dev, a->B, Mods{.seeds = seeds},
+           a->use_graph != 0};
     L.set_state = [&](StepState* st, hipStream_t s) { return launch_set_state(st, a->t_start, (unsigned long long)a->seed, s); };
     L.key = [&](GraphKey& k, const Slice& sl) {
         k.noise = a->noise_mode; k.aux0 = err_tab(sl); k.aux1 = a->idx_dev; k.thr = a->threshold;
         if (sl.chains == 2 && sl.chain == 0) k.b0 = -1;     // (chain 0 of two -- not the whole batch's graph)
     };
-    L.step = [&](dd_model* mm, const Chain& ch, const Slice& sl, hipStream_t s) {
-        return enqueue_ee_step(c, mm, ch, mm->ee_ws + ee_scratch_elems(mm, sl.b0), sl.x, sl.y, a->threshold, err_tab(sl), a->idx_dev,
-                               a->noise_mode, sl.B, s, sl.b0, a->B, sl.chains == 2, sl.mods.seeds);
+    L.step = [&](dd_model* mm, const Chain& ch, const Slice& sl, bool, hipStream_t s) {
+        return enqueue_ee_step(c, mm, ch, sl.x, sl.y, a->threshold, err_tab(sl), a->idx_dev, a->noise_mode, sl.B, s, sl.b0, a->B, sl.chains == 2,
+                               sl.mods.seeds);
     };
     L.tail = [&](int chains, hipStream_t s) -> int {
         if (chains == 2 && a->err_dev) DD_HIP(c, launch_ee_mean_combine(sums, sums + tab, a->err_dev, m->cfg.depth, a->t_end, a->t_start, a->B, s));
@@ -933,6 +959,12 @@ int real_live_set(dd_ctx* c, const dd_model* m, const WsPtrs& ws, int bi, const 
 
 // a chain's tables (RealTables) as one run of ints: rec [2 B] | moves [2 (B / 2 + 1)] | tab [B] | counts [2], an even number (rec and moves hold pairs)
 size_t real_tab_ints(size_t B) { return (2 * B + 2 * (B / 2 + 1) + B + 2 + 1) / 2 * 2; }
+// ... of chain k in the model's allocation (ensure_real_ws: both chains' runs, each sized for max_batch)
+RealTables real_tables(const dd_model* m, int k) {
+    const size_t B = (size_t)m->cfg.max_batch;
+    int *rec = m->real_tabs + (size_t)k * real_tab_ints(B), *moves = rec + 2 * B, *tab = moves + 2 * (B / 2 + 1);
+    return RealTables{tab, rec, tab + B, moves};
+}
 int ensure_real_ws(dd_ctx* c, dd_model* m) {
     if (!m->real_tabs) DD_HIP(c, hipMalloc((void**)&m->real_tabs, 2 * real_tab_ints((size_t)m->cfg.max_batch) * sizeof(int)));
     if (!m->real_counts_host) DD_HIP(c, hipHostMalloc((void**)&m->real_counts_host, 4 * sizeof(int), hipHostMallocDefault));
@@ -941,14 +973,14 @@ int ensure_real_ws(dd_ctx* c, dd_model* m) {
     return DD_OK;
 }
 
-// One chain of dd_sample_early_exit_real: its share of the batch, its scratch (eps | cls | outs: dd_sample_early_exit's block) and where it
+// One chain of dd_sample_early_exit_real: its share of the batch, its scratch (ee_block: dd_sample_early_exit's block) and where it
 // stands.  run() enqueues on the chain's stream until the chain is done or has to know a count: then the copy of the two counts and an
 // event are enqueued behind the decision launch and run() returns, to be called again -- it waits on the event first.
 struct RealChain {
     dd_ctx* c; dd_model* m; const dd_ee_sample_args* a;
     Chain ch; hipStream_t s;
     float* x; const int64_t* y; int B, b0;
-    float *eps, *cls, *outs;
+    EeBlock blk;
     RealTables t; int* counts_host; hipEvent_t ev;
     const unsigned long long* seeds;
     int compact_every;
@@ -960,13 +992,12 @@ struct RealChain {
 
     // (every stage is given the taps: a block's fused tail writes the y its successor's head reads only where the forward has taps)
     int stage(int kind) {
-        const EeTaps ee{cls, outs, 0};
         RealStage r{kind, layer, kind == REAL_EMBED ? B : Ba, B};
-        r.x_img = x; r.y = y; r.ee = &ee; r.eps = eps;
+        r.x_img = x; r.y = y; r.ee = &blk.taps; r.eps = blk.eps;
         return real_exit_stage(m, ch, r, hand, s);
     }
     int finish_step() {
-        DD_HIP(c, launch_ee_real_step(x, outs, eps, t, a->threshold, m->cfg.depth, ch.st, c->coef, B, m->cfg.in_chans, m->cfg.img_size, a->noise_mode, b0, seeds, s));
+        DD_HIP(c, launch_ee_real_step(x, blk.taps.outs, blk.eps, t, a->threshold, m->cfg.depth, ch.st, c->coef, B, m->cfg.in_chans, m->cfg.img_size, a->noise_mode, b0, seeds, s));
         layer = 0;
         done = ++step == a->t_start - a->t_end + 1;
         return DD_OK;
@@ -981,7 +1012,7 @@ struct RealChain {
                 }
                 if (int rc = stage(REAL_TAPS)) return rc;
                 const bool compact = layer % compact_every == 0;
-                DD_HIP(c, launch_ee_real_decide(cls + (size_t)layer * B, a->threshold, layer, depth, Ba, compact, t, a->idx_dev, a->B, b0, ch.st, s));
+                DD_HIP(c, launch_ee_real_decide(blk.taps.cls + (size_t)layer * B, a->threshold, layer, depth, Ba, compact, t, a->idx_dev, a->B, b0, ch.st, s));
                 if (compact) {
                     DD_HIP(c, hipMemcpyAsync(counts_host, t.counts, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
                     DD_HIP(c, hipEventRecord(ev, s));
@@ -1025,48 +1056,37 @@ extern "C" {
 
 // dd_sample_early_exit with the exits taken.  Eager launches; the calling thread waits for each compaction layer's counts.
 int dd_sample_early_exit_real(dd_ctx* c, const dd_ee_sample_args* a, const dd_ee_real* r, void* stream) {
-    if (!c || !a) return DD_ERR_INVALID;
-    if (!r) return ctx_fail(c, DD_ERR_INVALID, "null dd_ee_real");
-    dd_model* m = a->model;
-    int rc = check_call(c, m, a->B, a->y_dev);
-    if (rc) return rc;
-    if (m->ee_type < 0) return ctx_fail(c, DD_ERR_STATE, "model was not created with dd_model_enable_early_exit");
-    if (!a->x_dev) return ctx_fail(c, DD_ERR_INVALID, "null tensor");
-    if (a->err_dev) return ctx_fail(c, DD_ERR_INVALID, "dd_sample_early_exit_real: err_dev must be NULL (an image that has left has no predicted error at the layers behind its exit)");
-    if (r->compact_every < 1) return ctx_fail(c, DD_ERR_INVALID, "dd_sample_early_exit_real: compact_every must be at least 1");
-    if (a->t_start > 999 || a->t_end < 0 || a->t_end > a->t_start) return ctx_fail(c, DD_ERR_INVALID, "need 999 >= t_start >= t_end >= 0");
-    if (a->noise_mode != DD_NOISE_PHILOX && a->noise_mode != DD_NOISE_NONE)
-        return ctx_fail(c, DD_ERR_INVALID, "dd_sample_early_exit_real generates noise on the device; for host noise drive dd_forward_early_exit");
-    if (a->B > EE_REAL_MAX_SLOTS) return ctx_fail(c, DD_ERR_UNSUPPORTED, "dd_sample_early_exit_real takes at most 1024 images");
-    if ((rc = check_image_seeds(c, a->noise_mode, a->B))) return rc;
+    if (c && a && !r) return ctx_fail(c, DD_ERR_INVALID, "null dd_ee_real");
     hipStream_t s = (hipStream_t)stream;
     const unsigned long long* seeds = nullptr;
-    if ((rc = stage_image_seeds(c, a->noise_mode, s, &seeds))) return rc;
-    if ((rc = ensure_ee_ws(c, m)) || (rc = ensure_real_ws(c, m))) return rc;
+    int rc = ee_sample_setup(c, a, "dd_sample_early_exit_real", s, &seeds, [&]() -> int {
+        if (a->err_dev) return ctx_fail(c, DD_ERR_INVALID, "dd_sample_early_exit_real: err_dev must be NULL (an image that has left has no predicted error at the layers behind its exit)");
+        if (r->compact_every < 1) return ctx_fail(c, DD_ERR_INVALID, "dd_sample_early_exit_real: compact_every must be at least 1");
+        return DD_OK;
+    }, [&]() -> int {
+        if (a->B > EE_REAL_MAX_SLOTS) return ctx_fail(c, DD_ERR_UNSUPPORTED, "dd_sample_early_exit_real takes at most 1024 images");
+        return DD_OK;
+    });
+    if (rc) return rc;
+    dd_model* m = a->model;
+    if ((rc = ensure_real_ws(c, m))) return rc;
     for (long long& v : c->real_stats) v = 0;
     c->real_wait_ms = 0.0; c->real_waits = c->real_bytes = 0;
     // the chains of dd_sample_early_exit's policy (an eager loop here: no graph is asked for)
     const bool chained = use_chains(c, m, a->B, true);
-    const int chains = chained ? 2 : 1, B0 = chained ? a->B / 2 : a->B, depth = m->cfg.depth;
+    const int chains = chained ? 2 : 1, B0 = chained ? a->B / 2 : a->B;
     c->last_chains = chains;
     if (chained && (rc = ensure_chain_ws(c, m, s))) return rc;
-    const size_t chw = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size, mb = (size_t)m->cfg.max_batch;
+    const size_t chw = (size_t)m->cfg.in_chans * m->cfg.img_size * m->cfg.img_size;
     for (int k = 0; k < chains; ++k) DD_HIP(c, launch_set_state(c->st[k], a->t_start, (unsigned long long)a->seed, s));
-    if (chained) {
-        DD_HIP(c, hipEventRecord(c->ev_fork, s));
-        DD_HIP(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-    }
-    SideJoin side_join{c, chained};
+    ChainFork chain_fork{c, s, chained};
+    if ((rc = chain_fork.fork())) return rc;
     DD_HIP(c, hipEventRecord(c->ev[0], s));
     RealChain rcs[2];
     for (int k = 0; k < chains; ++k) {
         const int b0 = k ? B0 : 0, Bk = k ? a->B - B0 : B0;
-        float* eps = m->ee_ws + ee_scratch_elems(m, b0);
-        float* cls = eps + (size_t)Bk * chw;
-        int* tabs = m->real_tabs + (size_t)k * real_tab_ints(mb);
         rcs[k] = RealChain{c, m, a, Chain{&m->ws[k], c->st[k], c->num_cus, false}, k ? c->side : s,
-                           a->x_dev + (size_t)b0 * chw, a->y_dev ? a->y_dev + b0 : nullptr, Bk, b0, eps, cls, cls + (size_t)depth * Bk,
-                           RealTables{tabs + 2 * mb + 2 * (mb / 2 + 1), tabs, tabs + 2 * mb + 2 * (mb / 2 + 1) + mb, tabs + 2 * mb},
+                           a->x_dev + (size_t)b0 * chw, a->y_dev ? a->y_dev + b0 : nullptr, Bk, b0, ee_block(m, b0, Bk), real_tables(m, k),
                            m->real_counts_host + 2 * k, m->real_ev[k], seeds, r->compact_every};
     }
     // one host thread alternates the chains: one chain's blocks run while the other's counts travel
@@ -1082,11 +1102,7 @@ int dd_sample_early_exit_real(dd_ctx* c, const dd_ee_sample_args* a, const dd_ee
         for (int i = 0; i < 3; ++i) c->real_stats[i] += rcs[k].stats[i];
         c->real_wait_ms += rcs[k].wait_ms; c->real_waits += rcs[k].waits; c->real_bytes += rcs[k].bytes;
     }
-    if (chained) {
-        DD_HIP(c, hipEventRecord(c->ev_join, c->side));
-        DD_HIP(c, hipStreamWaitEvent(s, c->ev_join, 0));
-        side_join.armed = false;
-    }
+    if ((rc = chain_fork.join())) return rc;
     DD_HIP(c, hipEventRecord(c->ev[1], s));
     DD_HIP(c, hipEventRecord(c->ev[2], s));
     return DD_OK;

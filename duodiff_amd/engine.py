@@ -475,7 +475,9 @@ def threshold_struct(threshold):
 
 def _known_region(region, x, n_steps):
     """A KnownRegion as the loops' entries take it: the checks of its tensors against x and of its n_steps (ka, kb) rows, a byref of the
-    dd_known_region, and the row arrays, which must outlive the call (a byref keeps its struct alive)."""
+    dd_known_region, and the row arrays, which must outlive the call (a byref keeps its struct alive).  None: (None, None)."""
+    if region is None:
+        return None, None
     B, Cc, S, _ = x.shape
     for v, shape in ((region.x0, (B, Cc, S, S)), (region.mask, (B, 1, S, S))):
         assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and tuple(v.shape) == shape
@@ -485,33 +487,33 @@ def _known_region(region, x, n_steps):
     return C.byref(kr), keep
 
 
+def _guidance_refs(guidance):
+    """A loop's `guidance` value (None, (scale, null_label) or Autoguidance) as the entries' (dd_guidance, dd_autoguidance) byrefs, at most
+    one of them set (a byref keeps its struct alive)."""
+    if isinstance(guidance, Autoguidance):
+        return None, C.byref(L.dd_autoguidance(guidance.guide.handle, float(guidance.scale)))
+    return (C.byref(guidance_struct(guidance)) if guidance is not None else None), None
+
+
 def _loop_call(ctx, args, plain, guidance, region, x, threshold=None):
     """The loop entry of this argument struct as call(stream): `plain` (guidance None), its _guided form (guidance = (scale, null_label):
     classifier-free), its _autoguided form (guidance = Autoguidance(guide, scale)) or, with a KnownRegion, its _region form, which
     takes either kind of guidance, or none, beside the dd_known_region.  guidance = Perturbed(scale, layers_first, layers_late): its
     _perturbed form, alone.  No entry takes two kinds of guidance."""
-    g = ag = None
     if isinstance(guidance, Perturbed):
         if region is not None or threshold is not None:
             raise ValueError("perturbed-attention guidance does not combine with a known region or x0 thresholding")
         pag = L.dd_pag(float(guidance.scale), layer_mask(guidance.layers_first), layer_mask(guidance.layers_late))
         fn = getattr(ctx.lib, plain + "_perturbed")
         return lambda st: fn(ctx.handle, C.byref(args), C.byref(pag), st)
-    if isinstance(guidance, Autoguidance):
-        ag = C.byref(L.dd_autoguidance(guidance.guide.handle, float(guidance.scale)))
-    elif guidance is not None:
-        g = C.byref(guidance_struct(guidance))
+    g, ag = _guidance_refs(guidance)
+    kr, keep = _known_region(region, x, args.n_steps if hasattr(args, "n_steps") else args.t_start - args.t_end + 1)
     if region is None and threshold is None:
-        keep = None
         name, extra = plain + ("" if guidance is None else "_autoguided" if g is None else "_guided"), [r for r in (g, ag) if r is not None]
-    elif region is None:
-        keep = None
-        name, extra = plain + "_threshold", [g, ag, None, C.byref(threshold_struct(threshold))]
-    else:
-        kr, keep = _known_region(region, x, args.n_steps if hasattr(args, "n_steps") else args.t_start - args.t_end + 1)
+    elif threshold is None:
         name, extra = plain + "_region", [g, ag, kr]
-        if threshold is not None:
-            name, extra = plain + "_threshold", extra + [C.byref(threshold_struct(threshold))]
+    else:
+        name, extra = plain + "_threshold", [g, ag, kr, C.byref(threshold_struct(threshold))]
     fn = getattr(ctx.lib, name)
     return lambda st, keep=keep: fn(ctx.handle, C.byref(args), *extra, st)     # (a byref keeps its struct alive, the closure the arrays)
 
@@ -623,16 +625,9 @@ def sample_affine_walk_loop(ctx: Context, first: Model, late, x, rows, *, region
     prog = [np.ascontiguousarray(rows[k], np.int32) if k in rows and rows[k] is not None else None for k in ("jump", "late")]
     assert prog[0] is not None and all(v is None or v.shape == (n,) for v in prog)
     walk = L.dd_walk(*(v.ctypes.data_as(C.POINTER(C.c_int32)) if v is not None else None for v in prog))
-    g = ag = kr = None
-    if isinstance(guidance, Autoguidance):
-        ag = C.byref(L.dd_autoguidance(guidance.guide.handle, float(guidance.scale)))
-    elif guidance is not None:
-        g = C.byref(guidance_struct(guidance))
-    if region is not None:
-        kr, keep = _known_region(region, x, n)
-        prog = prog + keep
+    (g, ag), (kr, keep) = _guidance_refs(guidance), _known_region(region, x, n)
     # (a byref keeps its struct alive, the closure the arrays)
-    call = lambda st, keep=(tab, prog): ctx.lib.dd_sample_affine_walk(ctx.handle, C.byref(args), g, ag, kr, C.byref(walk), st)
+    call = lambda st, keep=(tab, prog, keep): ctx.lib.dd_sample_affine_walk(ctx.handle, C.byref(args), g, ag, kr, C.byref(walk), st)
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
 
@@ -652,13 +647,9 @@ def sample_affine_cached_loop(ctx: Context, first: Model, late, x, rows, *, bloc
     keep = [np.ascontiguousarray(rows["cache"], np.int32), np.ascontiguousarray(rows["cw"], np.float32)]
     assert all(v.shape == (n,) for v in keep)
     bc = L.dd_block_cache(int(blocks), int(order), keep[0].ctypes.data_as(C.POINTER(C.c_int32)), keep[1].ctypes.data_as(C.POINTER(C.c_float)))
-    g = C.byref(guidance_struct(guidance)) if guidance is not None else None
-    kr = None
-    if region is not None:
-        kr, kab = _known_region(region, x, n)
-        keep = keep + kab
+    (g, _), (kr, kab) = _guidance_refs(guidance), _known_region(region, x, n)
     # (a byref keeps its struct alive, the closure the arrays)
-    call = lambda st, keep=(tab, keep): ctx.lib.dd_sample_affine_cached(ctx.handle, C.byref(args), g, kr, C.byref(bc), st)
+    call = lambda st, keep=(tab, keep, kab): ctx.lib.dd_sample_affine_cached(ctx.handle, C.byref(args), g, kr, C.byref(bc), st)
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
 
@@ -700,10 +691,8 @@ def _sample_multistep_loop(ctx, first, late, x, region, h, rows, switch_after, y
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, _loop_call(ctx, args, "dd_sample_multistep", guidance, region, x, threshold))
 
 
-def sample_early_exit_loop(ctx: Context, model: Model, x, threshold, *, t_start=999, t_end=0, y=None, seed=0, noise="philox",
-                           err=None, idx=None, use_graph=True, stream=None):
-    """dd_sample_early_exit: the early-exit baseline's loop (eesampler.py:40-89) on the device, in place on x.
-    err [1000, depth] fp32 / idx [1000, B] int32 device tensors (or None): rows t_start .. t_end are written."""
+def _ee_sample_args(model, x, threshold, t_start, t_end, err, idx):
+    """The dd_ee_sample_args of the two early-exit loops: the fields of their own, and the checks of the two log tables (each may be None)"""
     args = L.dd_ee_sample_args()
     args.model = model.handle
     args.threshold = float(threshold)
@@ -714,6 +703,14 @@ def sample_early_exit_loop(ctx: Context, model: Model, x, threshold, *, t_start=
         assert idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and tuple(idx.shape) == (1000, x.shape[0])
     args.err_dev = err.data_ptr() if err is not None else None
     args.idx_dev = idx.data_ptr() if idx is not None else None
+    return args
+
+
+def sample_early_exit_loop(ctx: Context, model: Model, x, threshold, *, t_start=999, t_end=0, y=None, seed=0, noise="philox",
+                           err=None, idx=None, use_graph=True, stream=None):
+    """dd_sample_early_exit: the early-exit baseline's loop (eesampler.py:40-89) on the device, in place on x.
+    err [1000, depth] fp32 / idx [1000, B] int32 device tensors (or None): rows t_start .. t_end are written."""
+    args = _ee_sample_args(model, x, threshold, t_start, t_end, err, idx)
     call = lambda st: ctx.lib.dd_sample_early_exit(ctx.handle, C.byref(args), st)
     return _run_loop(ctx, args, x, y, seed, noise, use_graph, stream, call)
 
@@ -731,14 +728,7 @@ def sample_early_exit_real_loop(ctx: Context, model: Model, x, threshold, *, t_s
         raise ValueError(f"compact_every must be an integer >= 1, got {compact_every!r}")
     if noise not in ("none", "philox"):
         raise ValueError("real early exit draws its noise on the device: noise must be 'philox' or 'none'")
-    args = L.dd_ee_sample_args()
-    args.model = model.handle
-    args.threshold = float(threshold)
-    args.t_start, args.t_end = int(t_start), int(t_end)
-    if idx is not None:
-        assert idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and tuple(idx.shape) == (1000, x.shape[0])
-    args.err_dev = None
-    args.idx_dev = idx.data_ptr() if idx is not None else None
+    args = _ee_sample_args(model, x, threshold, t_start, t_end, None, idx)
     real = L.dd_ee_real(int(compact_every), 0)
     call = lambda st: ctx.lib.dd_sample_early_exit_real(ctx.handle, C.byref(args), C.byref(real), st)
     return _run_loop(ctx, args, x, y, seed, noise, False, stream, call)

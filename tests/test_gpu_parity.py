@@ -172,6 +172,52 @@ def test_switch_and_graph_replay_match_manual_steps():
     assert torch.isfinite(xm).all()
 
 
+def test_timing_split_follows_the_switch():
+    """ctx.last_sample_timing() = (total, first, late) splits a loop's GPU time where the late model takes over: in front of its first
+    row; behind the last row where the switch falls behind the last step; behind the join and the tail where no late model runs.  Two
+    models of one config, 8 steps, two half-batch chains (so that there is a join), graph replays; each call is made twice and the second
+    is read, so that the first replay's cost is outside.  The inequalities compare 7 steps with 1 step of equal models, or 8 steps with
+    two adjacent event records."""
+    from duodiff_amd import _lib as L
+    from duodiff_amd.engine import sample_affine_loop, sample_loop
+    B, n = 4, 8
+    m_a, _ = uvit(dict(TINY, depth=1), 11, "bf16", max_batch=B)
+    m_b, _ = uvit(dict(TINY, depth=1), 12, "bf16", max_batch=B)
+    ea, eb = m_a.engine_model(B), m_b.engine_model(B)
+    ctx = ea.ctx
+    x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(3)).cuda()
+    t = np.arange(999, 999 - n, -1, dtype=np.float32)
+    tab = (t, np.ones(n, np.float32), np.full(n, -0.01, np.float32), np.full(n, 0.01, np.float32), np.ones(n, np.int32))
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    ddpm = lambda x, late, **kw: sample_loop(ctx, ea, late, x, t_start=999, t_end=1000 - n, seed=7, noise="philox", use_graph=True,
+                                             stream=stream, **kw)
+    cases = {"late runs 7 of 8 steps": lambda x: ddpm(x, eb, t_switch=1),
+             "the switch falls behind the last step": lambda x: ddpm(x, eb, t_switch=n),
+             "no late model": lambda x: ddpm(x, None),
+             "affine, late runs 7 of 8 steps": lambda x: sample_affine_loop(ctx, ea, eb, x, *tab, switch_after=1, seed=7, noise="philox",
+                                                                            use_graph=True, stream=stream)}
+    timing = {}
+    try:
+        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, L.DD_DEV_FORCE_CHAINS))
+        with torch.cuda.stream(stream):
+            for name, call in cases.items():
+                for _ in range(2):
+                    call(x0.clone())
+                    stream.synchronize()
+                assert ctx.lib.dd_dev_last_sample_chains(ctx.handle) == 2
+                timing[name] = ctx.last_sample_timing()
+    finally:
+        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
+    for name, (total, t_first, t_late) in timing.items():
+        print(f"{name}: total {total:.4f} ms, first {t_first:.4f} ms, late {t_late:.4f} ms")
+        assert total > 0 and abs(t_first + t_late - total) <= 1e-3 * total, name
+        if "7 of 8" in name:
+            assert t_late > t_first > 0, name
+        else:
+            assert t_first > t_late, name
+
+
 @pytest.mark.parametrize("case", ["tiny_forced", "tiny_cond_forced", "celeba_default", "imagenet64_gemm_path"])
 def test_half_batch_chains_equal_the_single_chain(case):
     """dd_sample runs an even batch of >= 32 images as two half-batch chains on two streams (each with its own workspace, step

@@ -246,6 +246,7 @@ SIGNATURES = {
                     [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_rowlin": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 5 + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_attention": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
+    "dd_dev_attention_long": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_layernorm": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.POINTER(C.c_float)]),
     "dd_dev_cache_extrapolate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p,
                                            C.c_int, C.c_void_p, C.POINTER(C.c_float)]),

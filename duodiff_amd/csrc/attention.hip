@@ -1,4 +1,4 @@
-// Single-pass attention for the U-ViT token sequence (L <= 288, head_dim = 64) on gfx950.
+// Attention for the U-ViT token sequence (head_dim = 64) on gfx950: single-pass for L <= 288, streaming (attention_long_kernel) beyond.
 //
 // reference models/uvit.py:155-164: q,k,v = split(qkv) ; softmax(q k^T / sqrt(64)) v per (b, h),
 // fp32 softmax, no mask, heads merged back as "B H L D -> B L (H D)".
@@ -247,6 +247,44 @@ __device__ __forceinline__ void attend_tiles(const char* Ks, const char* Vt, int
     }
 }
 
+// One chunk's result to its output rows: orow = this lane's row (lane = query; a query past L: any valid row, keep = false drops it at the
+// store), o * inv in registers = d, 4 consecutive d per register quad.  attention_long_kernel's store; attention_kernel keeps its own inline
+// copy of these lines, because calling this from it changes its code object (wave_prims.h: the rule of the hot kernels).
+template <typename T>
+__device__ __forceinline__ void store_chunk(T* orow, const f32x16 (&o)[2], float inv, bool keep, int half) {
+    if constexpr (sizeof(T) == 2) {
+        // register quads g, g + 1 hold d = 8g + 4 half .. and 8g + 8 + 4 half ..: v_permlane32_swap pairs the two lane halves
+        // into 16 contiguous bytes per lane (d = 8g .. 8g+7 on half 0, 8g+8 .. 8g+15 on half 1), as the GEMM epilogue does
+        // (all lanes take part in the swap; rows past L are dropped at the store)
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+            uint2 v[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                bf16_t v4[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v4[e] = f2bf(o[dt][4 * g + e] * inv);
+                v[g] = *reinterpret_cast<const uint2*>(v4);
+            }
+#pragma unroll
+            for (int gp = 0; gp < 4; gp += 2) {
+                const auto s0 = __builtin_amdgcn_permlane32_swap(v[gp].x, v[gp + 1].x, false, false);
+                const auto s1 = __builtin_amdgcn_permlane32_swap(v[gp].y, v[gp + 1].y, false, false);
+                const uint4 o4 = {s0[0], s1[0], s0[1], s1[1]};
+                if (keep) *reinterpret_cast<uint4*>(orow + dt * 32 + 8 * gp + 8 * half) = o4;
+            }
+        }
+    } else if (keep) {
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int d = dt * 32 + 8 * g + 4 * half;
+                *reinterpret_cast<f32x4*>(orow + d) = f32x4{o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv, o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv};
+            }
+    }
+}
+
 // NKT > 0: the number of 32-key tiles is a compile-time constant (9 for L = 257/258: every shipped
 // config), which removes the per-tile uniform guards, confines the padded-key mask to the last tile's
 // 16 registers and takes ~1000 SGPR-spill lane moves out of the chunk body.  NKT == 0: generic L <= 288.
@@ -419,6 +457,126 @@ attention_kernel(const T* __restrict__ qkv, T* __restrict__ out, int B, int L, i
             out[((long long)b * L + 256 + qi) * D + hh * kHD + d] = Elem<T>::from_f32(num / den);
         }
     }
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Long sequences (288 < L <= kMaxLongL; valid from L = 1): K and V no longer fit one LDS image, so they STREAM through it in key blocks of
+// kMaxKeyTiles tiles (288 keys, the images and swizzles of attention_kernel) and a query chunk's result is merged across the blocks by the
+// online softmax: running maximum M, running sum l and the unnormalised accumulator O, all fp32,
+//     M' = max(M, m_b);   O = O f(M - M') + o_b f(m_b - M');   l = l f(M - M') + sum_b f(m_b - M');   out = O / l
+// with f the exponential of attend_tiles (exp2(x log2e / 8) in bf16 mode, expf(x / 8) in fp32 mode): the arithmetic of the split chunk's
+// merge above, one block at a time.  attend_tiles is the block's whole softmax, so P is rounded to bf16 once per block, relative to that
+// block's own maximum.  The L x L scores still never reach memory.
+// One workgroup = (image, head, slab of 128 queries), one 32-query chunk per wave, which keeps its Q fragments in registers for the whole
+// loop (s[9] + o[2] + O[2] + Q is what a wave holds: 256 VGPRs at two waves per SIMD in bf16 mode).  ONE K / V slot (72 KB in bf16 mode):
+// two workgroups share a CU and one computes while the other stages.  The rule of the slot: block j + 1 may be requested only after every
+// wave has finished block j (the barrier at the top of the loop), and is read only after every wave's pieces have landed (the barrier
+// behind the staging).
+// Keys: block j holds keys 288 j .. ; only the sequence's last tile can hold padded keys, and attend_tiles masks it where the block is the
+// last one (key index and L both relative to the block).  ceil(tiles / 9) blocks: none is empty, so none is all padding and every block
+// maximum is finite.  Rows [L, Lp) of a unit may hold anything: their lanes fetch row L - 1 (bf16) or zeros (fp32), as attention_kernel does.
+constexpr int kLongSlab = 128;
+
+template <typename T>
+__global__ void __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1)
+attention_long_kernel(const T* __restrict__ qkv, T* __restrict__ out, int L, int H, int D, int Lp) {
+    using Lay = AttnLayout<T>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* Ks = smem;                                   // [kLP][kRowK]
+    char* Vt = smem + kLP * Lay::kRowK;                // bf16: V [kLP][128 B] swizzled; fp32: V^T [64][kRowV]
+
+    const int nslab = (L + kLongSlab - 1) / kLongSlab;
+    const int slab = blockIdx.x % nslab, bh = blockIdx.x / nslab, b = bh / H, hh = bh % H;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int half = lane >> 5, r32 = lane & 31;
+    const long long unit = (long long)Lp * kHD;                        // elements per (q | k | v, head) unit
+    const T* qbase = qkv + ((long long)b * 3 * H + hh) * unit;
+    const T* kbase = qbase + (long long)H * unit;
+    const T* vbase = kbase + (long long)H * unit;
+    constexpr int EPC = 16 / (int)sizeof(T);           // elements per 16-byte chunk
+    constexpr int CPR = kHD / EPC;                     // chunks per row (8 bf16 / 16 fp32)
+
+    // this wave's chunk: Q fragments straight from HBM/L2 (rows >= L are clamped and dropped at the store).  A wave whose chunk lies wholly
+    // behind L (the last slab) stages and keeps the barriers, nothing else.
+    const int q = slab * kLongSlab + wave * 32 + r32;
+    const bool live = slab * kLongSlab + wave * 32 < L;                // wave-uniform
+    constexpr int NQF = sizeof(T) == 2 ? 4 : 8;
+    f32x4 qf[NQF];
+    {
+        const T* qrow = qbase + (long long)(q < L ? q : L - 1) * kHD;
+#pragma unroll
+        for (int i = 0; i < NQF; ++i)
+            qf[i] = sizeof(T) == 2 ? *reinterpret_cast<const f32x4*>(qrow + 16 * i + 8 * half)
+                                   : *reinterpret_cast<const f32x4*>(qrow + 32 * half + 4 * i);
+    }
+
+    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    f32x16 O[2] = {zero16, zero16};
+    float M = -INFINITY, l = 0.f;
+    const int nkt = (L + 31) / 32, nblk = (nkt + kMaxKeyTiles - 1) / kMaxKeyTiles;
+    for (int blk = 0; blk < nblk; ++blk) {
+        const int key0 = blk * kLP;                                    // the block's first key
+        const int ntl = nkt - blk * kMaxKeyTiles < kMaxKeyTiles ? nkt - blk * kMaxKeyTiles : kMaxKeyTiles;   // its tiles: 1 .. 9
+        if (blk > 0) __syncthreads();                                  // every wave has finished the block that the slot still holds
+        if constexpr (sizeof(T) == 2) {
+            // LDS-DMA, 1 KB pieces of 8 rows x 128 B as in attention_kernel: the K pieces of the block's tiles, then the V pieces; lane =
+            // (row 8p + (lane >> 3), slot lane & 7) fetches the chunk that belongs in its slot.  Every row of the block's tiles is fetched:
+            // keys >= L (only in the sequence's last tile) are copies of row L - 1 -- finite K and V for keys that the softmax masks
+            const int np = ntl * 4;                                    // pieces per operand
+            const int lr = lane >> 3, slot = lane & 7;
+            constexpr int MAXP = kLP / 8 * 2 / 4;                      // pieces per wave, at most
+#pragma unroll
+            for (int i = 0; i < MAXP; ++i) {
+                const int p2 = wave + 4 * i;                           // wave-uniform: [0, np) = K pieces, [np, 2 np) = V pieces
+                if (p2 < 2 * np) {
+                    const bool isv = p2 >= np;
+                    const int p = isv ? p2 - np : p2, r = 8 * p + lr, key = key0 + r;
+                    const int ch = isv ? (slot ^ v_swz(r)) : (slot ^ k_swz(r));
+                    const T* src = (isv ? vbase : kbase) + (long long)(key < L ? key : L - 1) * kHD + ch * 8;
+                    lds_dma16(src, (isv ? Vt : Ks) + p * 1024);
+                }
+            }
+            waitcnt_vm<0>();                                           // this wave's pieces have landed (hipcc does not track LDS-DMA writes)
+        } else {
+            for (int idx = tid; idx < ntl * 32 * CPR; idx += 256) {
+                const int r = idx / CPR, ch = idx % CPR, key = key0 + r;
+                f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
+                if (key < L) {
+                    kv = *reinterpret_cast<const f32x4*>(kbase + (long long)key * kHD + ch * EPC);
+                    vv = *reinterpret_cast<const f32x4*>(vbase + (long long)key * kHD + ch * EPC);
+                }
+                *reinterpret_cast<f32x4*>(Ks + r * Lay::kRowK + ch * 16) = kv;
+#pragma unroll
+                for (int e = 0; e < EPC; ++e)
+                    *reinterpret_cast<T*>(Vt + (ch * EPC + e) * Lay::kRowV + r * (int)sizeof(T)) = vv[e];
+            }
+        }
+        __syncthreads();                                               // the block is complete
+
+        if (live) {
+            f32x16 o[2];
+            float mx, sum;
+            // (L and the masked tile relative to the block; a block in front of the last has no tile to mask)
+            attend_tiles<T, 0, kMaxKeyTiles, false>(Ks, Vt, L - key0, blk + 1 == nblk ? ntl : 0, lane, [&](int k) { return k < ntl ? k : -1; }, qf, o, mx, sum);
+            const float Mn = fmaxf(M, mx);
+            float fo, fn;                                              // (first block: M = -inf, fo = 0)
+            if constexpr (sizeof(T) == 2) {
+                fo = __builtin_amdgcn_exp2f((M - Mn) * (0.125f * 1.4426950408889634f));
+                fn = __builtin_amdgcn_exp2f((mx - Mn) * (0.125f * 1.4426950408889634f));
+            } else {
+                fo = expf((M - Mn) * 0.125f);
+                fn = expf((mx - Mn) * 0.125f);
+            }
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) O[dt][e] = fmaf(o[dt][e], fn, O[dt][e] * fo);
+            l = fmaf(sum, fn, l * fo);
+            M = Mn;
+        }
+    }
+    if (live) store_chunk<T>(out + ((long long)b * L + (q < L ? q : L - 1)) * D + hh * kHD, O, 1.0f / l, q < L, half);
 }
 
 
@@ -952,6 +1110,18 @@ hipError_t launch_attention(const T* qkv, T* out, int B, int L, int H, int D, hi
     return hipGetLastError();
 }
 
+template <typename T>
+static constexpr size_t attention_long_lds() { return (size_t)kLP * AttnLayout<T>::kRowK + (size_t)AttnLayout<T>::kVBytes; }
+
+template <typename T>
+hipError_t launch_attention_long(const T* qkv, T* out, int B, int L, int H, int D, hipStream_t s) {
+    if (!qkv || !out || B < 1 || L < 1 || L > kMaxLongL || H < 1 || D != H * kHD) return hipErrorInvalidValue;
+    const long long grid = (long long)B * H * ((L + kLongSlab - 1) / kLongSlab);
+    if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((attention_long_kernel<T>), dim3((unsigned)grid), dim3(256), attention_long_lds<T>(), s, qkv, out, L, H, D, make_head_major(L, H).Lp);
+    return hipGetLastError();
+}
+
 // attn.qkv weight [3 D, D] (nn.Linear layout) -> per head the weight blocks the kernel streams, in stream order: [slice q of the k range:
 // 8 k-steps][tile pair jj][tile t of the pair][k-step] x 1 KB fragment in natural k order (tiles j = 2 jj + t = q0 q1 k0 k1 v0 v1): tile j of head hh =
 // rows (j >> 1) D + 64 hh + 32 (j & 1) .. + 31 of W
@@ -1019,11 +1189,15 @@ hipError_t init_attention_kernels() {
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attention_kernel<bf16_t, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lb);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attention_kernel<float, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, lf);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attention_kernel<float, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lf);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attention_long_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attention_long_lds<bf16_t>());
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attention_long_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attention_long_lds<float>());
     return e;
 }
 
 template hipError_t launch_attention<bf16_t>(const bf16_t*, bf16_t*, int, int, int, int, hipStream_t);
 template hipError_t launch_attention<float>(const float*, float*, int, int, int, int, hipStream_t);
+template hipError_t launch_attention_long<bf16_t>(const bf16_t*, bf16_t*, int, int, int, int, hipStream_t);
+template hipError_t launch_attention_long<float>(const float*, float*, int, int, int, int, hipStream_t);
 template hipError_t launch_v_copy<bf16_t>(const bf16_t*, bf16_t*, int, int, int, int, hipStream_t);
 template hipError_t launch_v_copy<float>(const float*, float*, int, int, int, int, hipStream_t);
 

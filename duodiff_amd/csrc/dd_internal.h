@@ -305,6 +305,11 @@ hipError_t launch_layernorm_frag(const float* x, const float* gamma, const float
 // qkv: head-major (HeadMajor, make_head_major(L, H)); out: [B * L, D] rows
 template <typename T>
 hipError_t launch_attention(const T* qkv, T* out, int B, int L, int H, int D, hipStream_t s);
+// the same operands for 1 <= L <= kMaxLongL (4096 patches + 2 extra tokens): K / V stream through LDS in key blocks, online softmax
+// (attention.hip attention_long_kernel).  The model takes it where L > 288 only; launch_attention and launch_v_copy keep their bound.
+constexpr int kMaxLongL = 4098;
+template <typename T>
+hipError_t launch_attention_long(const T* qkv, T* out, int B, int L, int H, int D, hipStream_t s);
 hipError_t init_attention_kernels();
 // attn.qkv + attention in one launch (attention.hip qkv_attention_kernel): h = norm1 of the patch rows in fragment order
 // (MlpFusedArgs::ln_out_frag); the extra-token rows: hx = norm1 row-major [B L, D], or hx = nullptr and xres / ln_g / ln_b = the fp32

@@ -1,5 +1,5 @@
 // The single-kernel development entry points of include/duodiff_dev.h (dd_dev_mlp, dd_dev_block_tail, dd_dev_block_tail_frag, dd_dev_qkv_attention, dd_dev_qkv_attention_rows, dd_dev_qkv_attention_frag, dd_dev_v_identity, dd_dev_v_copy, dd_dev_head_dec, dd_dev_gemm,
-// dd_dev_rowlin, dd_dev_attention, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather, dd_dev_groupnorm, dd_dev_softmax_rows, dd_dev_vae_input, dd_dev_vae_output, dd_dev_vae_moments, dd_dev_cast, dd_dev_ee_probe, dd_dev_ee_probe_reduce, dd_dev_ee_attn_probe, dd_dev_final, dd_dev_scan_diffuse, dd_dev_scan_error, dd_dev_scan_exits_error): test scaffolding, not product.  Each one owns its host operands, device buffers, canaries and
+// dd_dev_rowlin, dd_dev_attention, dd_dev_attention_long, dd_dev_layernorm, dd_dev_embed, dd_dev_time_mlp, dd_dev_vae_gather, dd_dev_groupnorm, dd_dev_softmax_rows, dd_dev_vae_input, dd_dev_vae_output, dd_dev_vae_moments, dd_dev_cast, dd_dev_ee_probe, dd_dev_ee_probe_reduce, dd_dev_ee_attn_probe, dd_dev_final, dd_dev_scan_diffuse, dd_dev_scan_error, dd_dev_scan_exits_error): test scaffolding, not product.  Each one owns its host operands, device buffers, canaries and
 // downloads, and nothing of the launch: the weight images come from finalize's packers and the launch arguments from the model's builders (launch_args.h:
 // dd_dev_mlp and dd_dev_block_tail* run block_tail_plan / block_tail_finish exactly as Backbone::block_tail does), then `iters` further launch sequences
 // are timed.  Buffers, transfers, timing and HIP errors go through one DevScope (dev_scope.h); of the context it reads num_cus and dev_flags (engine_state.h).
@@ -274,6 +274,36 @@ static int qkv_attention_run(dd_ctx* c, int B, int L, int H, int extras, const f
     return dev.status();
 }
 
+// dd_dev_attention (launch_attention) and dd_dev_attention_long (long_kernel: launch_attention_long) on the same operands
+static int attention_run(dd_ctx* c, int precision, int B, int L, int H, const float* q, const float* k, const float* v, void* out_host,
+                         bool long_kernel, int iters, void* stream, float* ms_out) {
+    const bool bf = precision == DD_PREC_BF16;
+    if (!c || (!bf && precision != DD_PREC_FP32) || B < 1 || L < 1 || H < 1 || !q || !k || !v || !out_host || iters < 0) return DD_ERR_INVALID;
+    const char* bound = long_kernel ? "attention_long: 1 <= L <= 4098, heads of 64" : "attention: 1 <= L <= 288, heads of 64";
+    if (L > (long_kernel ? kMaxLongL : 288)) return ctx_fail(c, DD_ERR_UNSUPPORTED, bound);      // (before the host image of such an L is built)
+    hipStream_t s = (hipStream_t)stream;
+    const int D = 64 * H;
+    const size_t esz = bf ? 2 : 4, out_elems = ((size_t)B * L + 8) * D;
+    const float* src[3] = {q, k, v};      // unit u = (b 3 + j) H + head: q | k | v [B, H, L, 64]
+    const std::vector<unsigned char> img = head_major_image(bf, B, L, H, [&](size_t u, int l) {
+        return src[u / H % 3] + ((u / (3 * (size_t)H) * H + u % H) * L + l) * 64;
+    });
+    DevScope dev(c);
+    const void* dQ = dev.upload(img.data(), img.size());
+    void* dO = dev.filled(out_elems * esz, 0xFF);
+    auto once = [&]() {
+        if (long_kernel) return bf ? launch_attention_long<bf16_t>((const bf16_t*)dQ, (bf16_t*)dO, B, L, H, D, s) : launch_attention_long<float>((const float*)dQ, (float*)dO, B, L, H, D, s);
+        return bf ? launch_attention<bf16_t>((const bf16_t*)dQ, (bf16_t*)dO, B, L, H, D, s) : launch_attention<float>((const float*)dQ, (float*)dO, B, L, H, D, s);
+    };
+    const hipError_t first = dev.ok() ? once() : hipSuccess;
+    if (first == hipErrorInvalidValue) return ctx_fail(c, DD_ERR_UNSUPPORTED, bound);      // (refused before any launch)
+    DEV_HIP(dev, first);
+    DEV_HIP(dev, hipStreamSynchronize(s));
+    dev.download(out_host, dO, out_elems * esz);
+    DEV_HIP(dev, time_launches(s, iters, once, ms_out));
+    return dev.status();
+}
+
 extern "C" {
 
 int dd_dev_qkv_attention_rows(dd_ctx* c, int B, int L, int H, int extras, const float* h_host, const float* wqkv, const float* bqkv,
@@ -475,28 +505,12 @@ int dd_dev_rowlin(dd_ctx* c, int B, int n_patches, int extras, int K, int k_spli
 
 int dd_dev_attention(dd_ctx* c, int precision, int B, int L, int H, const float* q, const float* k, const float* v, void* out_host,
                      int iters, void* stream, float* ms_out) {
-    const bool bf = precision == DD_PREC_BF16;
-    if (!c || (!bf && precision != DD_PREC_FP32) || B < 1 || L < 1 || H < 1 || !q || !k || !v || !out_host || iters < 0) return DD_ERR_INVALID;
-    hipStream_t s = (hipStream_t)stream;
-    const int D = 64 * H;
-    const size_t esz = bf ? 2 : 4, out_elems = ((size_t)B * L + 8) * D;
-    const float* src[3] = {q, k, v};      // unit u = (b 3 + j) H + head: q | k | v [B, H, L, 64]
-    const std::vector<unsigned char> img = head_major_image(bf, B, L, H, [&](size_t u, int l) {
-        return src[u / H % 3] + ((u / (3 * (size_t)H) * H + u % H) * L + l) * 64;
-    });
-    DevScope dev(c);
-    const void* dQ = dev.upload(img.data(), img.size());
-    void* dO = dev.filled(out_elems * esz, 0xFF);
-    auto once = [&]() {
-        return bf ? launch_attention<bf16_t>((const bf16_t*)dQ, (bf16_t*)dO, B, L, H, D, s) : launch_attention<float>((const float*)dQ, (float*)dO, B, L, H, D, s);
-    };
-    const hipError_t first = dev.ok() ? once() : hipSuccess;
-    if (first == hipErrorInvalidValue) return ctx_fail(c, DD_ERR_UNSUPPORTED, "attention: 1 <= L <= 288, heads of 64");      // (refused before any launch)
-    DEV_HIP(dev, first);
-    DEV_HIP(dev, hipStreamSynchronize(s));
-    dev.download(out_host, dO, out_elems * esz);
-    DEV_HIP(dev, time_launches(s, iters, once, ms_out));
-    return dev.status();
+    return attention_run(c, precision, B, L, H, q, k, v, out_host, false, iters, stream, ms_out);
+}
+
+int dd_dev_attention_long(dd_ctx* c, int precision, int B, int L, int H, const float* q, const float* k, const float* v, void* out_host,
+                          int iters, void* stream, float* ms_out) {
+    return attention_run(c, precision, B, L, H, q, k, v, out_host, true, iters, stream, ms_out);
 }
 
 int dd_dev_layernorm(dd_ctx* c, int precision, int rows, int D, const float* x_host, const float* gamma_beta, void* out_host,

@@ -262,7 +262,9 @@ struct Backbone {
             g.hm = make_head_major(L, m->H);     // head-major: each (q | k | v, head) unit of an image is contiguous (attention.hip)
             DD_HIP(c, launch_gemm<T>(g, w.qkv_b ? EPI_BIAS_STORE : EPI_STORE, s, ch.cus));
         }
-        if (Bn > 0) DD_TIMED(DD_PROF_QKV_ATTENTION, launch_attention<T>(qkv, ao, Bn, L, m->H, D, s));
+        // (the kernel is a function of the model, never of the call: beyond 288 tokens K / V stream through LDS; such a model is never perturbed
+        // -- check_perturbed -- so the identity launch below keeps launch_v_copy's bound)
+        if (Bn > 0) DD_TIMED(DD_PROF_QKV_ATTENTION, L > 288 ? launch_attention_long<T>(qkv, ao, Bn, L, m->H, D, s) : launch_attention<T>(qkv, ao, Bn, L, m->H, D, s));
         if (Bi > 0)
             DD_HIP(c, launch_v_copy<T>(qkv + (size_t)Bn * 3 * D * make_head_major(L, m->H).Lp, ao + (size_t)Bn * L * D, Bi, L, m->H, D, s));
         return DD_OK;
@@ -500,6 +502,7 @@ int check_perturbed(dd_ctx* c, dd_model* m, int B, const int64_t* y_dev, const d
     if (B < 1 || 2LL * B > m->cfg.max_batch)
         return ctx_fail(c, DD_ERR_INVALID, "a perturbed batch of B images runs 2 B backbone rows: need 1 <= B and 2 B <= max_batch");
     if (m->ee_type >= 0) return ctx_fail(c, DD_ERR_INVALID, "perturbed-attention guidance is not supported for early-exit models");
+    if (m->L > 288) return ctx_fail(c, DD_ERR_UNSUPPORTED, "perturbed-attention guidance: sequence length must be <= 288 tokens (the identity launches)");
     return check_call(c, m, 2 * B, y_dev);
 }
 

@@ -196,6 +196,9 @@ void choose_paths(dd_model* m, int precision, unsigned flags) {
     m->frag_x = frag && m->ee_type < 0 && !(flags & DD_DEV_NO_FRAG_X);
     // (embed_dim 768, no fused block tail) mlp.fc2 with the residual rows resident in registers: x read and written once, the next norm1 from registers
     m->rowlin_fc2 = precision == DD_PREC_BF16 && !m->fused_mlp && rowlin_supported(D, hid) && m->N % 32 == 0 && !(flags & DD_DEV_NO_ROWLIN);
+    // (its operand row offsets are 32 bits: rows x hidden x 2 bytes < 2^32, 2427 images at 288 tokens.  A long-sequence model whose max_batch
+    // passes that takes the GEMM sequence for every batch; the models of up to 288 tokens keep the launch's own check)
+    if (L > 288 && (long long)m->cfg.max_batch * L * hid * 2 >= (1ll << 32)) m->rowlin_fc2 = false;
     m->rowlin_proj = m->rowlin_fc2 && !(flags & DD_DEV_NO_ROWLIN_PROJ);
     m->rowlin_skip = m->rowlin_fc2 && rowlin_supported(D, 2 * D) && !(flags & DD_DEV_NO_ROWLIN_SKIP);
     // split-K for the N = embed_dim Linears (skip_linear, attn.proj, mlp.fc2) where even max_batch leaves half of the CUs without a 256 x 256
@@ -399,7 +402,14 @@ int dd_model_create(dd_ctx* c, const dd_config* cfg, dd_model** out) {
     m->hid_ld = m->hidden;   // row stride of the MLP hidden activation (a +64 pad against power-of-two strides measured no gain)
     m->half_depth = g.depth / 2;
     m->Mp_max = round_up(g.max_batch * m->L, 256);
-    if (m->L > 288) { delete m; return ctx_fail(c, DD_ERR_UNSUPPORTED, "sequence length must be <= 288 tokens"); }
+    // (L <= 288: attention_kernel, K and V of a head in one LDS image; beyond: attention_long_kernel streams them, launch_attention_long's bound)
+    if (m->N > kMaxLongL - 2) { delete m; return ctx_fail(c, DD_ERR_UNSUPPORTED, "(img_size / patch_size)^2 must be <= 4096 patches"); }
+    // the head-major row map of the qkv Linear (hm_offset) divides a row index by L with a 32-bit multiply: exact while rows x L < 2^32.  Below 289
+    // tokens that is a batch of 51 781 and stays the launch's own check; beyond, it is within reach (255 images of 4098 tokens) and is refused here
+    if (m->L > 288 && (long long)g.max_batch * m->L * m->L >= (1ll << 32)) {
+        delete m;
+        return ctx_fail(c, DD_ERR_UNSUPPORTED, "above 288 tokens max_batch x tokens^2 must be < 2^32 (" + std::to_string((1ll << 32) / ((long long)m->L * m->L)) + " images at this size)");
+    }
     if (m->pd > 64) { delete m; return ctx_fail(c, DD_ERR_UNSUPPORTED, "patch_size^2 * in_chans must be <= 64"); }
     m->params = catalogue(m);
     static std::atomic<unsigned long long> serials{0};
@@ -524,6 +534,7 @@ int dd_model_enable_early_exit(dd_model* m, int classifier_type) {
     if (m->finalized || any_set) return ctx_fail(c, DD_ERR_STATE, "enable early exit before any parameter is set");
     if (classifier_type < DD_EE_MLP_PER_LAYER || classifier_type > DD_EE_ATTENTION_PROBE)
         return ctx_fail(c, DD_ERR_UNSUPPORTED, "unknown classifier type");
+    if (m->L > 288) return ctx_fail(c, DD_ERR_UNSUPPORTED, "early-exit models: sequence length must be <= 288 tokens");
     m->ee_type = classifier_type;
     m->params = catalogue(m);   // the heads and probes of this classifier type
     return DD_OK;

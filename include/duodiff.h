@@ -97,6 +97,9 @@ int dd_schedule_build(float beta_init, float beta_final, int steps, float* betas
                       float* alphas_bar_prev, float* betas_tilde);
 
 /* ---- model: replaces UViT(**model_params) + load_state_dict (sampler.py:271-293) ---- */
+/* Limits (DD_ERR_UNSUPPORTED beyond them): head_dim 64, embed_dim <= 1024, in_chans <= 4, patch_size^2 * in_chans <= 64 and
+ * (img_size / patch_size)^2 <= 4096 patches.  Above 288 tokens (patches + the time and label tokens) the attention streams its keys; there
+ * dd_model_enable_early_exit and the *_perturbed entries answer DD_ERR_UNSUPPORTED, and x0 thresholding keeps its 16384 elements per image. */
 int dd_model_create(dd_ctx* ctx, const dd_config* cfg, dd_model** out);
 /* name = the reference state_dict key (models/uvit.py:228-336), data = host fp32,
  * shape must match the reference's exactly.  Copies; may be called in any order. */

@@ -164,6 +164,13 @@ int dd_dev_rowlin(dd_ctx* ctx, int B, int n_patches, int extras, int K, int k_sp
 int dd_dev_attention(dd_ctx* ctx, int precision, int B, int L, int H, const float* q, const float* k, const float* v, void* out_host,
                      int iters, void* stream, float* ms_out);
 
+/* The same harness for the streaming attention launch of long sequences (attention.hip attention_long_kernel<T>: launch_attention_long; the model
+ * takes it where L > 288): the operands, NaN pad rows, canary rows and timing of dd_dev_attention.  It accepts every L the launcher accepts,
+ * 1 <= L <= 4098 -- L <= 288 included, so that the two kernels can be compared on the same operands; L > 4098 is DD_ERR_UNSUPPORTED, L < 1
+ * DD_ERR_INVALID; nothing is launched. */
+int dd_dev_attention_long(dd_ctx* ctx, int precision, int B, int L, int H, const float* q, const float* k, const float* v, void* out_host,
+                          int iters, void* stream, float* ms_out);
+
 /* Development harness for the LayerNorm launches (rowops.hip layernorm_kernel<T>): out = LayerNorm(x) gamma + beta (eps 1e-5, biased variance)
  * of host fp32 rows x [rows, D], gamma_beta [2, D].  frag_host NULL: launch_layernorm<T> (T by precision) into out_host, row-major.
  * frag_host non-NULL (bf16 only): launch_layernorm_frag -- the patch rows of the tok_l-token images (behind tok_e extra tokens) go to frag_host in

@@ -1,289 +1,130 @@
-"""ctypes binding of libduodiff.so (include/duodiff.h).  No CPU fallback: a missing
-library is an ImportError-class failure raised at first use, loudly."""
+"""ctypes binding of libduodiff.so, derived at import from include/duodiff.h and include/duodiff_dev.h: the two headers are the only
+declaration of the ABI.  Every DD_* constant, every argument struct and SIGNATURES (name -> (restype, argtypes)) below come from their
+text; a declaration outside the small subset of C they use raises HeaderError, quoting it.  No CPU fallback: a missing library is an
+ImportError-class failure raised at first use, loudly."""
 import ctypes as C
 import os
+import re
 from pathlib import Path
 
 LIB_PATH = Path(os.environ.get("DUODIFF_LIB") or Path(__file__).resolve().parent / "libduodiff.so")
-
-DD_OK = 0
-DD_ERR_INVALID, DD_ERR_NOT_FOUND, DD_ERR_STATE, DD_ERR_HIP, DD_ERR_NOMEM, DD_ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6
-DD_PREC_BF16, DD_PREC_FP32 = 0, 1
-DD_VAR_BETA_TILDE, DD_VAR_BETA = 0, 1
-DD_NOISE_NONE, DD_NOISE_BUFFER, DD_NOISE_PHILOX = 0, 1, 2
-DD_X0_STATIC, DD_X0_DYNAMIC = 0, 1
-DD_EE_MLP_PER_LAYER, DD_EE_MLP_PER_TIMESTEP, DD_EE_MLP_PER_LAYER_PER_TIMESTEP, DD_EE_ATTENTION_PROBE = 0, 1, 2, 3
-ABI_VERSION = 6
-DD_DEV_NO_FUSED_MLP, DD_DEV_NO_FUSED_PROJ, DD_DEV_NO_FUSED_HEAD, DD_DEV_GENERIC_EMBED, DD_DEV_MLP_EXTRAS_ONLY = 1, 2, 4, 8, 16
-DD_DEV_NO_FUSED_SKIP, DD_DEV_NO_FUSED_QKV, DD_DEV_NO_FUSED_QA = 32, 64, 128
-DD_PROF_DOMINANT, DD_PROF_BLOCK_TAIL, DD_PROF_FC1, DD_PROF_ROWLIN, DD_PROF_QKV_ATTENTION, DD_PROF_SPLITK = 0, 1, 2, 3, 4, 5
-DD_DEV_NO_CHAINS, DD_DEV_FORCE_CHAINS, DD_DEV_NO_ROWLIN, DD_DEV_NO_ROWLIN_PROJ, DD_DEV_NO_EMBED_LN, DD_DEV_NO_SPLITK, DD_DEV_NO_ROWLIN_SKIP = 256, 512, 1024, 2048, 4096, 8192, 16384
-DD_DEV_NO_SPLIT_HEADS = 32768
-DD_DEV_NO_FRAG_AO, DD_DEV_NO_FRAG_SKIP, DD_DEV_NO_FRAG_X = 65536, 131072, 262144
-
-
-class dd_config(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in (
-        "img_size", "patch_size", "in_chans", "embed_dim", "depth", "num_heads", "mlp_ratio",
-        "num_classes", "normalize_timesteps", "max_batch", "qkv_bias", "mlp_time_embed")]
-
-
-class dd_sample_args(C.Structure):
-    _fields_ = [("first", C.c_void_p), ("late", C.c_void_p), ("t_switch", C.c_int32),
-                ("t_start", C.c_int32), ("t_end", C.c_int32), ("variance", C.c_int32),
-                ("noise_mode", C.c_int32), ("use_graph", C.c_int32), ("seed", C.c_uint64),
-                ("y_dev", C.c_void_p), ("x_dev", C.c_void_p), ("B", C.c_int32), ("reserved", C.c_int32)]
-
-
-class dd_affine_sample_args(C.Structure):
-    _fields_ = [("first", C.c_void_p), ("late", C.c_void_p), ("n_steps", C.c_int32), ("switch_after", C.c_int32),
-                ("t", C.POINTER(C.c_float)), ("a", C.POINTER(C.c_float)), ("b", C.POINTER(C.c_float)),
-                ("c", C.POINTER(C.c_float)), ("noise", C.POINTER(C.c_int32)), ("noise_mode", C.c_int32),
-                ("use_graph", C.c_int32), ("seed", C.c_uint64), ("y_dev", C.c_void_p), ("x_dev", C.c_void_p),
-                ("B", C.c_int32), ("counter_base", C.c_int32)]
-
-
-class dd_multistep_sample_args(C.Structure):
-    """dd_affine_sample_args' fields, then the history half of the rows and the history register (include/duodiff.h)"""
-    _fields_ = dd_affine_sample_args._fields_ + [
-        ("d", C.POINTER(C.c_float)), ("p", C.POINTER(C.c_float)), ("q", C.POINTER(C.c_float)), ("hist", C.POINTER(C.c_int32)),
-        ("h_dev", C.c_void_p)]
-
-
-class dd_guidance(C.Structure):
-    """classifier-free guidance: eps = eps_c + scale * (eps_c - eps_u), the unconditional rows labelled null_label"""
-    _fields_ = [("scale", C.c_float), ("null_label", C.c_int32)]
-
-
-class dd_autoguidance(C.Structure):
-    """autoguidance: eps = eps_main + scale * (eps_main - eps_guide), guide = the weaker dd_model of the same image geometry"""
-    _fields_ = [("guide", C.c_void_p), ("scale", C.c_float)]
-
-
-class dd_pag(C.Structure):
-    """perturbed-attention guidance: eps = eps + scale * (eps - eps_perturbed), identity attention in the blocks of the model's mask"""
-    _fields_ = [("scale", C.c_float), ("layers_first", C.c_uint32), ("layers_late", C.c_uint32)]
-
-
-class dd_known_region(C.Structure):
-    """a known region: x' is finished as m * (ka x0 + kb z2) + (1 - m) x' from the known image x0, the mask m and per-step rows ka, kb"""
-    _fields_ = [("x0_dev", C.c_void_p), ("mask_dev", C.c_void_p), ("ka", C.POINTER(C.c_float)), ("kb", C.POINTER(C.c_float))]
-
-
-class dd_walk(C.Structure):
-    """a walk's per-row program beside the step table: jump[k] != 0: row k is a resampling jump; late[k] (or NULL): step row k runs the late model"""
-    _fields_ = [("jump", C.POINTER(C.c_int32)), ("late", C.POINTER(C.c_int32))]
-
-
-class dd_block_cache(C.Structure):
-    """block caching beside the step table: K = blocks, the order, and per step the op (0 refresh, 1 reuse, 2 reuse with extrapolation) and its weight"""
-    _fields_ = [("blocks", C.c_int32), ("order", C.c_int32), ("op", C.POINTER(C.c_int32)), ("w", C.POINTER(C.c_float))]
-
-
-class dd_x0_threshold(C.Structure):
-    """x0 thresholding of the multistep loop: static (clamp to +-range) or dynamic (the image's own quantile scale, at most s_max)"""
-    _fields_ = [("mode", C.c_int32), ("quantile", C.c_float), ("range", C.c_float), ("s_max", C.c_float)]
-
-
-class dd_ee_sample_args(C.Structure):
-    _fields_ = [("model", C.c_void_p), ("threshold", C.c_float), ("t_start", C.c_int32), ("t_end", C.c_int32),
-                ("noise_mode", C.c_int32), ("use_graph", C.c_int32), ("B", C.c_int32), ("seed", C.c_uint64),
-                ("y_dev", C.c_void_p), ("x_dev", C.c_void_p), ("err_dev", C.c_void_p), ("idx_dev", C.c_void_p)]
-
-
-class dd_ee_real(C.Structure):
-    """dd_sample_early_exit_real: layers l with l % compact_every == 0 compact the batch"""
-    _fields_ = [("compact_every", C.c_int32), ("reserved", C.c_int32)]
-
-
-class dd_scan_args(C.Structure):
-    """dd_scan_error (include/duodiff.h): the images, the scan's rows and where the per-image errors go"""
-    _fields_ = [("model", C.c_void_p), ("x0_dev", C.c_void_p), ("y_dev", C.c_void_p), ("B", C.c_int32), ("n_steps", C.c_int32)] + \
-               [(n, C.POINTER(C.c_float)) for n in ("t", "ka", "kb", "tz", "t0", "tx")] + \
-               [("seed", C.c_uint64), ("counter_base", C.c_int32), ("noise_mode", C.c_int32), ("use_graph", C.c_int32),
-                ("reserved", C.c_int32), ("err_dev", C.c_void_p)]
-    x_dev = property(lambda self: self.x0_dev, lambda self, v: setattr(self, "x0_dev", v))     # (the name engine._run_loop fills the image tensor in by)
-
-
-class dd_dev_scan_args(C.Structure):
-    """the operands of dd_dev_scan_diffuse / dd_dev_scan_error (include/duodiff_dev.h), field for field"""
-    _fields_ = ([(n, C.c_int32) for n in ("B", "C", "S", "b0", "B_all", "k")] +
-                [(n, C.c_float) for n in ("t_model", "ka", "kb", "tz", "t0", "tx")] +
-                [("ctr", C.c_int32), ("next_t_model", C.c_float), ("seed", C.c_uint64), ("advance", C.c_int32), ("t_out", C.c_int32),
-                 ("t_final_out", C.c_int32), ("t_model_out", C.c_float), ("iters", C.c_int32), ("ms_out", C.c_float)])
-
-
-class dd_scan_exits_args(C.Structure):
-    """dd_scan_error_early_exit (include/duodiff.h): dd_scan_args with the three result tables in err_dev's place"""
-    _fields_ = dd_scan_args._fields_[:-1] + [("mse_dev", C.c_void_p), ("target_dev", C.c_void_p), ("pred_dev", C.c_void_p)]
-    x_dev = property(lambda self: self.x0_dev, lambda self, v: setattr(self, "x0_dev", v))
-
-
-class dd_dev_scan_exits_args(C.Structure):
-    """the operands of dd_dev_scan_exits_error (include/duodiff_dev.h), field for field"""
-    _fields_ = ([(n, C.c_int32) for n in ("B", "C", "S", "exits", "b0", "B_all", "k", "t", "next")] +
-                [(n, C.c_float) for n in ("t_model", "ka", "kb", "tz", "t0", "tx")] +
-                [("ctr", C.c_int32), ("next_t_model", C.c_float), ("seed", C.c_uint64), ("advance", C.c_int32), ("t_out", C.c_int32),
-                 ("t_final_out", C.c_int32), ("t_model_out", C.c_float), ("iters", C.c_int32), ("ms_out", C.c_float)])
-
-
-class dd_dev_final_args(C.Structure):
-    """the operands of dd_dev_final (include/duodiff_dev.h), field for field"""
-    _fields_ = ([(n, C.c_int32) for n in ("B", "C", "S", "P", "L", "extras", "b0", "images")] +
-                [(n, C.c_void_p) for n in ("dec", "wconv", "bconv", "dec2", "wconv2", "bconv2")] +
-                [(n, C.c_int32) for n in ("L2", "extras2", "pair_B", "layer_B")] +
-                [("w_stride", C.c_int64), ("b_stride", C.c_int64), ("guide_scale", C.c_float)] +
-                [(n, C.c_int32) for n in ("write_eps", "write_x", "x_alias")] +
-                [(n, C.c_void_p) for n in ("eps_out", "x_out", "x_in", "z")] +
-                [(n, C.c_int32) for n in ("t", "advance", "noise_mode", "variance")] +
-                [("seed", C.c_uint64), ("table", C.c_int32)] +
-                [(n, C.c_float) for n in ("c1", "c2", "sigma_tilde", "sigma_beta", "row_t_model", "row_a", "row_b", "row_c")] +
-                [("row_noise", C.c_int32), ("row_ctr", C.c_int32), ("next_t_model", C.c_float), ("hist_row", C.c_int32)] +
-                [(n, C.c_float) for n in ("hist_d", "hist_p", "hist_q")] +
-                [("hist", C.c_int32), ("h", C.c_void_p), ("known", C.c_int32), ("known_ka", C.c_float), ("known_kb", C.c_float),
-                 ("kx0", C.c_void_p), ("kmask", C.c_void_p), ("t_out", C.c_int32), ("t_final_out", C.c_int32), ("t_model_out", C.c_float),
-                 ("seed_out", C.c_uint64)])
-
-
-# every symbol include/duodiff.h (and include/duodiff_dev.h: dd_dev_*) declares: name -> (restype, argtypes)
-SIGNATURES = {
-    "dd_abi_version": (C.c_int, []),
-    "dd_build_id": (C.c_char_p, []),
-    "dd_ctx_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
-    "dd_ctx_destroy": (None, [C.c_void_p]),
-    "dd_last_error": (C.c_char_p, [C.c_void_p]),
-    "dd_sync": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "dd_schedule_table": (C.c_int, [C.c_int, C.POINTER(C.c_float)]),
-    "dd_schedule_build": (C.c_int, [C.c_float, C.c_float, C.c_int] + [C.POINTER(C.c_float)] * 5),
-    "dd_model_create": (C.c_int, [C.c_void_p, C.POINTER(dd_config), C.POINTER(C.c_void_p)]),
-    "dd_model_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
-    "dd_model_finalize": (C.c_int, [C.c_void_p, C.c_int]),
-    "dd_model_num_params": (C.c_int64, [C.c_void_p]),
-    "dd_model_destroy": (None, [C.c_void_p]),
-    "dd_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "dd_model_enable_early_exit": (C.c_int, [C.c_void_p, C.c_int]),
-    "dd_forward_early_exit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "dd_early_exit_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int64,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "dd_ddpm_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
-    "dd_ddpm_step_coef": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
-                                    C.c_void_p, C.c_int64, C.c_void_p]),
-    "dd_affine_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
-                                 C.c_void_p, C.c_int64, C.c_void_p]),
-    "dd_sample_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                 C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
-    "dd_to_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "dd_sample": (C.c_int, [C.c_void_p, C.POINTER(dd_sample_args), C.c_void_p]),
-    "dd_sample_affine": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.c_void_p]),
-    "dd_sample_early_exit": (C.c_int, [C.c_void_p, C.POINTER(dd_ee_sample_args), C.c_void_p]),
-    "dd_sample_early_exit_real": (C.c_int, [C.c_void_p, C.POINTER(dd_ee_sample_args), C.POINTER(dd_ee_real), C.c_void_p]),
-    "dd_forward_guided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.POINTER(dd_guidance), C.c_void_p,
-                                    C.c_int, C.c_void_p]),
-    "dd_sample_guided": (C.c_int, [C.c_void_p, C.POINTER(dd_sample_args), C.POINTER(dd_guidance), C.c_void_p]),
-    "dd_sample_affine_guided": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.POINTER(dd_guidance), C.c_void_p]),
-    "dd_multistep_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_float] * 6 +
-                          [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
-    "dd_sample_multistep": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.c_void_p]),
-    "dd_sample_multistep_guided": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_guidance), C.c_void_p]),
-    "dd_forward_autoguided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.POINTER(dd_autoguidance), C.c_void_p,
-                                        C.c_int, C.c_void_p]),
-    "dd_sample_autoguided": (C.c_int, [C.c_void_p, C.POINTER(dd_sample_args), C.POINTER(dd_autoguidance), C.c_void_p]),
-    "dd_sample_affine_autoguided": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.POINTER(dd_autoguidance), C.c_void_p]),
-    "dd_sample_multistep_autoguided": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_autoguidance), C.c_void_p]),
-    "dd_forward_perturbed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.POINTER(dd_pag), C.c_void_p,
-                                       C.c_int, C.c_void_p]),
-    "dd_sample_perturbed": (C.c_int, [C.c_void_p, C.POINTER(dd_sample_args), C.POINTER(dd_pag), C.c_void_p]),
-    "dd_sample_affine_perturbed": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.POINTER(dd_pag), C.c_void_p]),
-    "dd_sample_multistep_perturbed": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_pag), C.c_void_p]),
-    "dd_known_blend": (C.c_int, [C.c_void_p] * 5 + [C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "dd_sample_region": (C.c_int, [C.c_void_p, C.POINTER(dd_sample_args), C.POINTER(dd_guidance), C.POINTER(dd_autoguidance),
-                                   C.POINTER(dd_known_region), C.c_void_p]),
-    "dd_sample_affine_region": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.POINTER(dd_guidance), C.POINTER(dd_autoguidance),
-                                          C.POINTER(dd_known_region), C.c_void_p]),
-    "dd_sample_multistep_region": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_guidance),
-                                             C.POINTER(dd_autoguidance), C.POINTER(dd_known_region), C.c_void_p]),
-    "dd_jump_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
-    "dd_sample_affine_walk": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.POINTER(dd_guidance), C.POINTER(dd_autoguidance),
-                                        C.POINTER(dd_known_region), C.POINTER(dd_walk), C.c_void_p]),
-    "dd_forward_cached": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.POINTER(dd_guidance), C.c_int32, C.c_int32,
-                                    C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
-    "dd_sample_affine_cached": (C.c_int, [C.c_void_p, C.POINTER(dd_affine_sample_args), C.POINTER(dd_guidance), C.POINTER(dd_known_region),
-                                          C.POINTER(dd_block_cache), C.c_void_p]),
-    "dd_threshold_step": (C.c_int, [C.c_void_p] * 5 + [C.POINTER(dd_x0_threshold)] + [C.c_float] * 6 +
-                          [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "dd_sample_multistep_threshold": (C.c_int, [C.c_void_p, C.POINTER(dd_multistep_sample_args), C.POINTER(dd_guidance),
-                                                C.POINTER(dd_autoguidance), C.POINTER(dd_known_region), C.POINTER(dd_x0_threshold), C.c_void_p]),
-    "dd_set_image_seeds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
-    "dd_noise_images": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "dd_scan_error": (C.c_int, [C.c_void_p, C.POINTER(dd_scan_args), C.c_void_p]),
-    "dd_scan_error_early_exit": (C.c_int, [C.c_void_p, C.POINTER(dd_scan_exits_args), C.c_void_p]),
-    "dd_bench_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
-    "dd_vae_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
-    "dd_vae_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
-    "dd_vae_finalize": (C.c_int, [C.c_void_p, C.c_int]),
-    "dd_vae_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "dd_vae_destroy": (None, [C.c_void_p]),
-    "dd_vae_has_encoder": (C.c_int, [C.c_void_p]),
-    "dd_vae_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "dd_vae_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "dd_profile_steps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                   C.POINTER(C.c_float), C.POINTER(C.c_int)]),
-    "dd_profile_steps_chained": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                           C.POINTER(C.c_float), C.POINTER(C.c_int)]),
-    "dd_profile_select": (C.c_int, [C.c_void_p, C.c_int]),
-    "dd_dev_qkv_attention": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
-    "dd_dev_qkv_attention_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
-    "dd_dev_v_identity": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
-    "dd_dev_v_copy": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
-    "dd_dev_mlp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)] + [C.c_void_p] * 8),
-    "dd_dev_block_tail": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 21 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
-    "dd_dev_block_tail_frag": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 21 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)] + [C.c_void_p] * 5),
-    "dd_dev_qkv_attention_frag": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
-    "dd_dev_head_dec": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
-    "dd_dev_gemm": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p] + [C.c_int] * 2 + [C.c_void_p] * 2 +
-                    [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
-    "dd_dev_rowlin": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 5 + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
-    "dd_dev_attention": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
-    "dd_dev_attention_long": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
-    "dd_dev_layernorm": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.POINTER(C.c_float)]),
-    "dd_dev_cache_extrapolate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p,
-                                           C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
-    "dd_dev_embed": (C.c_int, [C.c_void_p] + [C.c_int] * 9 + [C.c_void_p] * 7 + [C.c_float] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
-    "dd_dev_time_mlp": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 6 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
-    "dd_dev_vae_gather": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "dd_dev_groupnorm": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 6),
-    "dd_dev_softmax_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "dd_dev_vae_input": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_void_p, C.c_void_p]),
-    "dd_dev_vae_output": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3),
-    "dd_dev_vae_moments": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7),
-    "dd_dev_cast": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "dd_dev_ee_probe": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 6),
-    "dd_dev_ee_probe_reduce": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3),
-    "dd_dev_ee_attn_probe": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 10),
-    "dd_dev_final": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_final_args), C.c_void_p]),
-    "dd_dev_final_seeded": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_final_args), C.c_void_p, C.c_int, C.c_void_p]),
-    "dd_dev_scan_diffuse": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_scan_args), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "dd_dev_scan_error": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_scan_args), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "dd_dev_scan_exits_error": (C.c_int, [C.c_void_p, C.POINTER(dd_dev_scan_exits_args)] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4),
-    "dd_dev_poison_workspaces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "dd_dev_graph_captures": (C.c_longlong, [C.c_void_p]),
-    "dd_dev_last_sample_chains": (C.c_int, [C.c_void_p]),
-    "dd_dev_ee_real_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong)]),
-    "dd_dev_ee_real_cost": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
-    "dd_dev_ee_real_plan": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "dd_dev_set_flags": (C.c_int, [C.c_void_p, C.c_uint]),
-    "dd_set_num_cus": (C.c_int, [C.c_void_p, C.c_int]),
-    "dd_plan_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "dd_last_sample_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
-}
-
-_lib = None
+INCLUDE = Path(__file__).resolve().parent.parent / "include"
 
 
 class EngineUnavailable(RuntimeError):
-    """libduodiff.so is missing or unusable.  There is no CPU path to fall back to."""
+    """libduodiff.so (or a header it is bound from) is missing or unusable.  There is no CPU path to fall back to."""
+
+
+class HeaderError(ValueError):
+    """a declaration of the headers that the binding does not derive a type for"""
+
+
+SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "unsigned": C.c_uint, "uint32_t": C.c_uint32, "int64_t": C.c_int64,
+           "uint64_t": C.c_uint64, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong, "unsigned short": C.c_ushort,
+           "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
+
+
+def _ctype(base, stars, types, field, host_rows, decl):
+    """the ctypes type of `stars` pointers to `base`; types: struct name -> its class, or None for an opaque handle"""
+    if base not in SCALARS and base not in types and base not in ("void", "char"):
+        raise HeaderError(f"unknown type {base!r} in: {decl}")
+    if stars == 0:
+        if base not in SCALARS:
+            raise HeaderError(f"{base!r} by value in: {decl}")
+        return SCALARS[base]
+    if stars == 1 and base == "char":
+        return C.c_char_p
+    if stars == 1 and types.get(base) is not None:
+        return C.POINTER(types[base])
+    # a scalar pointer field that is not *_dev is one of the public header's "host [n_steps]" arrays; every other pointer is an address
+    return C.POINTER(SCALARS[base]) if field and host_rows and stars == 1 and base in SCALARS else C.c_void_p
+
+
+def _declare(decl, types, field, dev, quote=None):
+    """[(name, ctype)] of one field line (several declarators allowed) or one parameter (an array is a pointer); errors quote `quote`"""
+    decl, quote = decl.strip(), quote or decl.strip()
+    if "(" in decl:
+        raise HeaderError(f"function pointer in: {quote}")
+    if ":" in decl:
+        raise HeaderError(f"bit-field in: {quote}")
+    if re.search(r"[{}]|\b(struct|union|enum)\b", decl):
+        raise HeaderError(f"nested or anonymous struct in: {quote}")
+    out, base = [], None
+    for piece in re.sub(r"\bconst\b", " ", decl).split(","):
+        m = re.fullmatch(r"([\w\s*]*?)(\w+)\s*(\[\w*\])?", piece.strip())
+        if not m:
+            raise HeaderError(f"cannot read the declarator {piece.strip()!r} in: {quote}")
+        prefix, name, array = m.groups()
+        if array and field:
+            raise HeaderError(f"array field in: {quote}")
+        if base is None:
+            base = " ".join(prefix.replace("*", " ").split())
+        elif prefix.replace("*", "").strip():
+            raise HeaderError(f"cannot read the declarator {piece.strip()!r} in: {quote}")
+        out.append((name, _ctype(base, prefix.count("*") + bool(array), types, field, not dev and not name.endswith("_dev"), quote)))
+    return out
+
+
+def parse_header(text, dev=False, types=None):
+    """(constants, types, signatures) of one header's text; types continues the dict of the headers read before it.  dev: the header
+    is duodiff_dev.h, whose structs hold no host row arrays."""
+    constants, types, signatures = {}, {} if types is None else types, {}
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#[ \t]*ifdef __cplusplus\b.*?^[ \t]*#[ \t]*endif\b[^\n]*", "", text, flags=re.S | re.M)     # extern "C" { ... }
+    for line in re.findall(r"^[ \t]*#[^\n]*", text, flags=re.M):
+        m = re.fullmatch(r"#\s*define\s+(DD_\w+)\b\s*(.*)", line.strip())
+        if m:
+            if not re.fullmatch(r"-?\d+[uU]?", m.group(2).strip()):
+                raise HeaderError(f"not an integer constant: {line.strip()}")
+            constants[m.group(1)] = int(m.group(2).strip().rstrip("uU"))
+    text = re.sub(r"^[ \t]*#[^\n]*", "", text, flags=re.M)
+    depth, start, statements = 0, 0, []
+    for i, ch in enumerate(text):
+        depth += (ch == "{") - (ch == "}")
+        if ch == ";" and depth == 0:
+            statements.append(" ".join(text[start:i].split()))
+            start = i + 1
+    if text[start:].strip():
+        raise HeaderError(f"unfinished declaration: {' '.join(text[start:].split())}")
+    for st in statements:
+        if m := re.fullmatch(r"typedef struct (\w+) (\w+)", st):
+            types.setdefault(m.group(1), None)
+        elif m := re.fullmatch(r"(?:typedef )?enum \w*\s*\{(.*)\}\s*\w*", st):
+            for item in filter(None, (s.strip() for s in m.group(1).split(","))):
+                if not (e := re.fullmatch(r"(DD_\w+) = (-?\d+)", item)):
+                    raise HeaderError(f"enumerator without an integer value {item!r} in: {st}")
+                constants[e.group(1)] = int(e.group(2))
+        elif m := re.fullmatch(r"typedef struct (\w+) \{(.*)\} (\w+)", st):
+            if m.group(1) != m.group(3) or "{" in m.group(2):
+                raise HeaderError(f"nested or anonymous struct in: {st}")
+            fields = [f for d in m.group(2).split(";") if d.strip() for f in _declare(d, types, True, dev)]
+            types[m.group(1)] = type(m.group(1), (C.Structure,), {"_fields_": fields})
+        elif (m := re.fullmatch(r"([\w\s*]+?)\b(dd_\w+)\s*\((.*)\)", st)) and "(" not in m.group(3):
+            ret, params = re.sub(r"\bconst\b", " ", m.group(1)), m.group(3).strip()
+            res = None if ret.split() == ["void"] else _ctype(" ".join(ret.replace("*", " ").split()), ret.count("*"), types, False, False, st)
+            signatures[m.group(2)] = (res, [] if params == "void" else [_declare(p, types, False, dev, st)[0][1] for p in params.split(",")])
+        else:
+            raise HeaderError(f"{'function pointer in' if '(*' in st else 'cannot read'}: {st}")
+    return constants, types, signatures
+
+
+def _bind():
+    """every DD_* constant and struct class becomes a module attribute; SIGNATURES holds every prototype of both headers"""
+    types = {}
+    for name, dev in (("duodiff.h", False), ("duodiff_dev.h", True)):
+        if not (INCLUDE / name).exists():
+            raise EngineUnavailable(f"{INCLUDE / name} not found: duodiff_amd binds libduodiff.so from the headers of its own tree")
+        constants, types, signatures = parse_header((INCLUDE / name).read_text(), dev, types)
+        globals().update(constants)
+        SIGNATURES.update(signatures)
+    globals().update({k: v for k, v in types.items() if v is not None})
+
+
+SIGNATURES = {}
+_bind()
+ABI_VERSION = DD_ABI_VERSION  # noqa: F821  (bound from duodiff.h just above)
+
+_lib = None
 
 
 def load():

@@ -518,13 +518,14 @@ def _loop_call(ctx, args, plain, guidance, region, x, threshold=None):
     return lambda st, keep=keep: fn(ctx.handle, C.byref(args), *extra, st)     # (a byref keeps its struct alive, the closure the arrays)
 
 
-def _run_loop(ctx: Context, args, x, y, seed, noise, use_graph, stream, call):
-    """Fill the fields every loop's argument struct shares (x in place, y, the device noise) and run call(stream) on the caller's stream."""
+def _run_loop(ctx: Context, args, x, y, seed, noise, use_graph, stream, call, image="x_dev"):
+    """Fill the fields every loop's argument struct shares (x in place, y, the device noise) and run call(stream) on the caller's stream.
+    image: the field that receives x's pointer (the scans only read their images: x0_dev)."""
     args.noise_mode = {"none": L.DD_NOISE_NONE, "philox": L.DD_NOISE_PHILOX}[noise]
     args.use_graph = int(bool(use_graph))
     args.seed = int(seed)
     args.y_dev = y.data_ptr() if y is not None else None
-    args.x_dev = x.data_ptr()
+    setattr(args, image, x.data_ptr())
     args.B = x.shape[0]
     cur = stream if stream is not None else torch.cuda.current_stream(x.device)
     if use_graph and cur.cuda_stream == 0:
@@ -767,7 +768,8 @@ def scan_error_loop(ctx: Context, model: Model, x0, rows, *, y=None, seed=0, cou
     err = torch.empty(n, x0.shape[0], device=x0.device, dtype=torch.float32) if err is None else err
     assert err.is_cuda and err.dtype == torch.float32 and err.is_contiguous() and tuple(err.shape) == (n, x0.shape[0])
     args.err_dev = err.data_ptr()
-    _run_loop(ctx, args, x0, y, seed, "philox", use_graph, stream, lambda st: ctx.lib.dd_scan_error(ctx.handle, C.byref(args), st))
+    _run_loop(ctx, args, x0, y, seed, "philox", use_graph, stream, lambda st: ctx.lib.dd_scan_error(ctx.handle, C.byref(args), st),
+              image="x0_dev")
     return err
 
 
@@ -784,5 +786,6 @@ def scan_exits_loop(ctx: Context, model: Model, x0, rows, *, y=None, seed=0, cou
     mse, target = (torch.empty(n, depth + 1, B, device=x0.device, dtype=torch.float32) for _ in range(2))
     pred = torch.empty(n, depth, B, device=x0.device, dtype=torch.float32)
     args.mse_dev, args.target_dev, args.pred_dev = mse.data_ptr(), target.data_ptr(), pred.data_ptr()
-    _run_loop(ctx, args, x0, y, seed, "philox", use_graph, stream, lambda st: ctx.lib.dd_scan_error_early_exit(ctx.handle, C.byref(args), st))
+    _run_loop(ctx, args, x0, y, seed, "philox", use_graph, stream, lambda st: ctx.lib.dd_scan_error_early_exit(ctx.handle, C.byref(args), st),
+              image="x0_dev")
     return mse, target, pred

@@ -271,12 +271,19 @@ def test_signatures_declared_in_both_headers():
     assert fields(dev, "dd_dev_scan_args") == [f[0] for f in L.dd_dev_scan_args._fields_]
     assert C.sizeof(L.dd_scan_args) == 112 and L.dd_scan_args.err_dev.offset == 104 and L.dd_scan_args.seed.offset == 80
     assert C.sizeof(L.dd_dev_scan_args) == 88 and L.dd_dev_scan_args.seed.offset == 56
-    a = L.dd_scan_args()
-    a.x_dev = 4096                                      # engine._run_loop's name for the image tensor
-    assert a.x0_dev == 4096
     lib = L.load()
     assert lib.dd_abi_version() == 6
     for name in ("dd_scan_error", "dd_dev_scan_diffuse", "dd_dev_scan_error"):
         assert hasattr(lib, name)
     from duodiff_amd import engine
     assert callable(engine.scan_error_loop)
+    # engine._run_loop puts the image tensor into the field its caller names: x0_dev for the scans, whose structs have no x_dev
+    from types import SimpleNamespace as NS
+    assert "x_dev" not in dict(L.dd_scan_args._fields_) and "x_dev" not in dict(L.dd_scan_exits_args._fields_)
+    image, ctx, seen = NS(data_ptr=lambda: 4096, shape=(3, 1, 2, 2), device=None), NS(check=lambda rc: None), []
+    for a in (L.dd_scan_args(), L.dd_scan_exits_args()):
+        engine._run_loop(ctx, a, image, None, 7, "philox", False, NS(cuda_stream=64), lambda st: seen.append(st.value), image="x0_dev")
+        assert a.x0_dev == 4096 and (a.B, a.seed, a.y_dev, a.noise_mode, a.use_graph) == (3, 7, None, L.DD_NOISE_PHILOX, 0)
+    a = L.dd_sample_args()
+    engine._run_loop(ctx, a, image, None, 7, "none", False, NS(cuda_stream=64), lambda st: seen.append(st.value))
+    assert a.x_dev == 4096 and seen == [64, 64, 64]

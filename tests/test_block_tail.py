@@ -222,6 +222,14 @@ def emulate(o, mode, bug=None):
         y2 = y.copy()
         y2[o.patch] = y[np.flatnonzero(o.patch) - E]
         y = y2
+    if bug == "tok_l":                # the image of a patch row taken with tok_l = N: image b's patch rows computed from the rows b E further up
+        y2 = y.copy()
+        y2[o.patch] = y[np.flatnonzero(o.patch) - E * (np.flatnonzero(o.patch) // L)]
+        y = y2
+    if bug == "ragged":               # the last, ragged 32-row group of every image left out: its rows keep what the launch found in x
+        rows = np.flatnonzero(o.patch & ((np.arange(M) % L) - E >= o.N // 32 * 32))
+        y = y.copy()
+        y[rows] = (o.x0 if "proj" in sw else o.x1)[rows]
     res = dict(M=M, Mo=Mo, mode=mode, poison=0xFF, status=0)
     full32 = lambda rows_: np.concatenate([rows_, np.full((Mo - M, D), NAN32, np.uint32).view(np.float32)])
     blank16 = lambda: np.full((Mo, D), NAN16, np.uint16)

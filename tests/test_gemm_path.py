@@ -66,7 +66,7 @@ def run_gemm(A, W, bias, x_in, epi, K1=0, prec=PREC_BF16, tile128=-1, hm=None, s
     L, H = hm if hm else (0, 0)
     if hm:
         Lp = round_up(L, 8)
-        out = np.zeros((M // L * 3 * H * Lp + 64) * 64, np.uint16)
+        out = np.zeros((M // L * 3 * H * Lp + 64) * 64, np.uint16 if prec == PREC_BF16 else np.float32)
     else:
         out = np.zeros((Mo, ldo), np.uint16 if prec == PREC_BF16 else np.float32)
     out = out if with_out else None
@@ -226,20 +226,19 @@ SPLITK = [
 ]
 
 
-@gpu
-@pytest.mark.parametrize("D,K,K1,splits,resid,with_ln,frag,L,B,x_offset", SPLITK)
-def test_split_k_and_reduce_ln_against_float64_reference(D, K, K1, splits, resid, with_ln, frag, L, B, x_offset):
-    """every reduce_ln_kernel<NQ> (D = 256 .. 1024), 2 and 4 slabs, residual or not, LayerNorm row-major or in fragment order (rows with a
-    common offset of 100 sigma included); the slabs themselves against their k ranges"""
+def check_split_k(D, K, K1, splits, resid, with_ln, frag, L, B, x_offset, n_patches=256):
+    """split-K + reduce_ln on B images of L tokens, the last n_patches of each its patch rows: the slabs against their k ranges, x, the bf16
+    copy and the LayerNorm under the gates of the module docstring.  Returns the largest error / bound ratio of each"""
     M = B * L
     A, W, bias, x_in = operands(M, D, K, D + K + splits, x_offset=x_offset)
     ln = ln_params(D, D) if with_ln else None
-    xres, out, h, fr, slab = run_gemm(A, W, bias, x_in, EPI_BIAS_RESID, K1=K1, splits=splits, resid=resid, ln=ln, tok=(L, L - 256), frag=frag)
+    xres, out, h, fr, slab = run_gemm(A, W, bias, x_in, EPI_BIAS_RESID, K1=K1, splits=splits, resid=resid, ln=ln, tok=(L, L - n_patches), frag=frag)
     nk = K // 64
+    ratios = {}
     for sp in range(splits):
         k0, k1 = sp * nk // splits * 64, (sp + 1) * nk // splits * 64
         acc, absum = linear_ref(A, W, k0=k0, k1=k1)
-        gate(slab.reshape(-1)[sp * M * D: (sp + 1) * M * D].reshape(M, D), acc, FP32_REL * absum, f"slab {sp}")     # (slab sp at sp M N)
+        ratios[f"slab {sp}"] = gate(slab.reshape(-1)[sp * M * D: (sp + 1) * M * D].reshape(M, D), acc, FP32_REL * absum, f"slab {sp}")     # (slab sp at sp M N)
     assert untouched(slab.reshape(-1)[splits * M * D:]), "slab area past M N splits written"
     acc, absum = linear_ref(A, W)
     xref = acc + bias + (x_in.astype(np.float64) if resid else 0.0)
@@ -251,9 +250,9 @@ def test_split_k_and_reduce_ln_against_float64_reference(D, K, K1, splits, resid
     msg = f"split-K D={D} K={K} K1={K1 or K} splits={splits} resid={resid} ln={with_ln} frag={frag} L={L} B={B}: max err/bound x {rx:.3f}, copy {ro:.3f}"
     if with_ln:
         want, tol = ln_ref_and_tol(xres[:M], *ln)
-        patch = (np.arange(M) % L) >= L - 256
+        patch = (np.arange(M) % L) >= L - n_patches
         if frag:
-            groups = B * 256 // 32
+            groups = B * n_patches // 32
             got_p = unfrag(fr.reshape(-1), groups, D)
             rh = gate(from_bf16_bits(got_p), want[patch], tol[patch], "LayerNorm (fragment order)")
             assert untouched(fr.reshape(-1)[groups * 32 * D:]), "fragment buffer written past the patch rows"
@@ -264,7 +263,18 @@ def test_split_k_and_reduce_ln_against_float64_reference(D, K, K1, splits, resid
         rh2 = gate(from_bf16_bits(h[:M][rows]), want[rows], tol[rows], "LayerNorm (row-major)")
         assert untouched(h[M:]), "LayerNorm rows >= M written"
         msg += f", LayerNorm row-major {rh2:.3f}" + (f", fragment order {rh:.3f}" if frag else "")
+        ratios["LayerNorm"] = max(rh2, rh if frag else 0.0)
     print(msg)
+    ratios.update(x=rx, copy=ro)
+    return ratios
+
+
+@gpu
+@pytest.mark.parametrize("D,K,K1,splits,resid,with_ln,frag,L,B,x_offset", SPLITK)
+def test_split_k_and_reduce_ln_against_float64_reference(D, K, K1, splits, resid, with_ln, frag, L, B, x_offset):
+    """every reduce_ln_kernel<NQ> (D = 256 .. 1024), 2 and 4 slabs, residual or not, LayerNorm row-major or in fragment order (rows with a
+    common offset of 100 sigma included); the slabs themselves against their k ranges"""
+    check_split_k(D, K, K1, splits, resid, with_ln, frag, L, B, x_offset, n_patches=256)
 
 
 # rowlin768: (B, patches, extras, K, k_split, set_x, frag, x_copy, LayerNorm, x offset)

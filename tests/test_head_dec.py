@@ -19,6 +19,8 @@ from kernel_support import P
 
 pytestmark = pytest.mark.gpu
 
+HEAD_DEC_REL = 5e-6          # the exact kernel's bound, as a fraction of the largest |dec| of the case (derived where it is asserted below)
+
 
 def _reference(x, g, b, w, bias):
     x = x.astype(np.float64)
@@ -69,7 +71,7 @@ def test_head_dec_patch_rows_against_float64_reference(D, pd, B, L, extras, prob
     print(f"head_dec D={D} pd={pd} B={B} L={L}: max err {err.max():.3e} of |dec| max {scale:.2f}; rows with offset 2000: {err[(np.arange(M) % 4 == 2)[patch]].max():.3e}; {us:.1f} us/launch")
     # fp32 accumulation of D products + the statistics: a few 1e-6 of the output's scale (measured 1.1e-6 .. 2.2e-6), offset rows included --
     # x - x[0] is exact for a row whose elements share an exponent, so the offset costs nothing beyond what it cost the fp32 INPUT
-    assert err.max() <= 5e-6 * scale
+    assert err.max() <= HEAD_DEC_REL * scale
     if probe:
         es = np.abs(srow - want_s)
         print(f"  probe rows: max err {es.max():.3e}")
@@ -85,7 +87,7 @@ def test_head_dec_every_row_ragged_and_more_units_than_waves(D, pd, M, probe):
     dec, srow, want, want_s, us = _run(M, D, pd, 0, 0, x, probe)
     err = np.abs(dec - want)
     print(f"head_dec every row D={D} pd={pd} M={M}: max err {err.max():.3e} of |dec| max {np.abs(want).max():.2f}; {us:.1f} us/launch")
-    assert err.max() <= 5e-6 * max(1.0, np.abs(want).max())
+    assert err.max() <= HEAD_DEC_REL * max(1.0, np.abs(want).max())
     if probe:
         assert np.abs(srow - want_s).max() <= 2e-6
 

@@ -4,8 +4,11 @@ reference by tests/test_oracle_golden.py), both engines, with the bounds of test
 1e-4; bf16: rms <= eps_rms_bound(depth) sigma (loop_support: the error model of the bf16 engine).  The configurations put the long sequence
 through each family of launches: embed_dim 128 (fused block tail with the next qkv inside, N = 324 not a multiple of 16 or 32), 512
 class-conditional (fused tail, two extra tokens), 768 (row-resident Linears, N % 32 == 0), 1024 (GEMM path, 4 latent channels at patch 2) and
-one 1024-patch model.  Then: an image does not depend on its batch; the device loops replay a graph on two half-batch chains bit-identically
-to the eager single chain; what keeps a bound is refused where it is set up, with nothing launched."""
+one 1024-patch model; a sixth, embed_dim 1024 at 1024 patches, is the family that runs split-K.  Then, without a tolerance: a forward after
+dd_dev_poison_workspaces equals a forward on a fresh model bit for bit, in every configuration and both engines (with NaN in the rows [L, Lp)
+of every head-major qkv unit: no kernel reads them); an image does not depend on its batch, the first and the last image of every family;
+the device loops replay a graph on two half-batch chains bit-identically to the eager single chain; what keeps a bound is refused where it is
+set up, with nothing launched.  The launches themselves are gated per element by tests/test_long_geometry.py."""
 import numpy as np
 import pytest
 import torch
@@ -43,13 +46,18 @@ def test_a_325_token_model_loads_and_runs():
     assert got.shape == (2, 3, 72, 72) and np.isfinite(got).all() and got.std() > 0
 
 
-@pytest.mark.parametrize("name,c,B", [
+# the five configurations every whole-model test below shares: (name, config, batch)
+CONFIGS = [
     ("D128 L325", L325, 3),
     ("D512 L578 class-conditional", cfg(512, 96, num_classes=10), 2),
     ("D768 L577", cfg(768, 96), 2),
     ("D1024 L577 latents", cfg(1024, 48, patch=2, in_chans=4), 2),
     ("D128 L1025", cfg(128, 128), 1),
-], ids=["d128_l325", "d512_l578", "d768_l577", "d1024_l577", "d128_l1025"])
+]
+CONFIG_IDS = ["d128_l325", "d512_l578", "d768_l577", "d1024_l577", "d128_l1025"]
+
+
+@pytest.mark.parametrize("name,c,B", CONFIGS, ids=CONFIG_IDS)
 def test_long_sequence_models_vs_oracle(name, c, B):
     x, t, y = inputs(c, B, 77 + B)
     mp = ModelParams.from_dict(c)
@@ -70,6 +78,13 @@ def test_long_sequence_models_vs_oracle(name, c, B):
             assert rms <= eps_rms_bound(mp.depth) * sigma
 
 
+def test_the_split_k_model_vs_oracle():
+    """embed_dim 1024 at 1024 patches (64 x 64 latents, patch 2): the one long family whose N = embed_dim Linears run split-K + reduce_ln.
+    choose_paths asks for a row partition of the 256 x 256 kernel at every batch: 1025 B = 256 x 4 B + B has one (one tail row per tile), while
+    577 and 1154 rows have none, so the 577-token model above runs the GEMM sequence.  Same bounds as above."""
+    test_long_sequence_models_vs_oracle("D1024 L1025 latents (split-K)", cfg(1024, 64, patch=2, in_chans=4), 2)
+
+
 @pytest.mark.parametrize("prec", ["bf16", "fp32"])
 def test_an_image_does_not_depend_on_its_batch(prec):
     m, _ = uvit(L325, 12, prec, max_batch=3)
@@ -77,6 +92,42 @@ def test_an_image_does_not_depend_on_its_batch(prec):
     whole = m(x, t, None).cpu().numpy()
     alone = m(x[:1].contiguous(), t[:1], None).cpu().numpy()
     assert np.isfinite(whole).all() and np.array_equal(whole[:1], alone)
+
+
+@pytest.mark.parametrize("prec", ["bf16", "fp32"])
+@pytest.mark.parametrize("name,c,B", CONFIGS, ids=CONFIG_IDS)
+def test_poisoned_workspaces_do_not_reach_the_output(name, c, B, prec):
+    """a forward on a fresh model and a forward after dd_dev_poison_workspaces (every activation buffer 0xFF bytes, on the launch stream; the
+    method of tools/poison_probe.py): both finite, bit-identical.  The rows [L, Lp) of every head-major qkv unit then hold NaN where a fresh
+    workspace holds zeros: no kernel reads them, nor a stale slab or a padding row"""
+    x, t, y = inputs(c, B, 55 + B)
+    outs = []
+    for poison in (False, True):
+        m, _ = uvit(c, 4246, prec, max_batch=B)
+        em = m.engine_model(B)
+        if poison:
+            em.ctx.check(em.ctx.lib.dd_dev_poison_workspaces(em.ctx.handle, em.handle, torch.cuda.current_stream().cuda_stream))
+        outs.append(m(x, t, y).cpu().numpy())
+        del em, m
+    assert np.isfinite(outs[0]).all() and outs[0].std() > 0, f"{name} {prec}: the fresh model's output"
+    assert np.isfinite(outs[1]).all(), f"{name} {prec}: NaN after the workspaces were poisoned"
+    assert np.array_equal(outs[0].view(np.uint32), outs[1].view(np.uint32)), f"{name} {prec}: the output depends on what a workspace held"
+
+
+# bf16 for the four families the test above does not run; fp32 for one of them (the class-conditional one: two extra tokens)
+@pytest.mark.parametrize("k,prec", [(1, "bf16"), (2, "bf16"), (3, "bf16"), (4, "bf16"), (1, "fp32")],
+                         ids=[CONFIG_IDS[1], CONFIG_IDS[2], CONFIG_IDS[3], CONFIG_IDS[4], CONFIG_IDS[1] + "_fp32"])
+def test_first_and_last_image_do_not_depend_on_their_batch(k, prec):
+    """the other families: the first and the last image of a batch of 2 (3 at embed_dim 128, L = 1025) equal that image run alone, bit for bit"""
+    name, c, B = CONFIGS[k]
+    B = max(B, 2) if k != 4 else 3
+    m, _ = uvit(c, 12 + k, prec, max_batch=B)
+    x, t, y = inputs(c, B, 2 + k)
+    whole = m(x, t, y).cpu().numpy()
+    assert np.isfinite(whole).all() and whole.std() > 0
+    for b in (0, B - 1):
+        alone = m(x[b:b + 1].contiguous(), t[b:b + 1], y[b:b + 1].contiguous() if y is not None else None).cpu().numpy()
+        assert np.array_equal(whole[b:b + 1].view(np.uint32), alone.view(np.uint32)), f"{name} {prec}: image {b} of {B} differs from the image alone"
 
 
 def test_device_loops_chained_graph_replay_equals_the_eager_single_chain():

@@ -398,7 +398,7 @@ int dd_dev_gemm(dd_ctx* c, int precision, int M, int N, int K, int K1, const flo
     if (splits > 0 && (!bf || splits < 2 || !bias || hm_L || (ln && !h_host) || (frag_host && (!ln || tok_l <= tok_e))))
         return ctx_fail(c, DD_ERR_INVALID, "split-K: bf16, splits >= 2, bias, no head-major map; LayerNorm output needs h (and frag tok_l > tok_e)");
     if (splits == 0 && (epilogue < EPI_STORE || epilogue > EPI_BIAS_STORE || ((epilogue == EPI_BIAS_RESID || epilogue == EPI_BIAS_SET) && !xres_host) ||
-                        (epilogue != EPI_STORE && !bias) || (hm_L && (hm_H < 1 || M % hm_L || !out_host))))
+                        (epilogue != EPI_STORE && epilogue != EPI_BIAS_SET && !bias) || (hm_L && (hm_H < 1 || M % hm_L || !out_host))))
         return DD_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const size_t esz = bf ? 2 : 4, Mo = (size_t)round_up(M, 256) + 8;

@@ -11,6 +11,7 @@
 //   state_dict carried every encoder tensor.  Encode and decode of one object share one workspace: calls are ordered by the stream
 //   they are given, and two calls on different streams must be ordered by the caller.
 #include "../../include/duodiff.h"
+#include "../../include/duodiff_dev.h"
 #include "dd_internal.h"
 #include "engine_state.h"
 #include "host_arena.h"
@@ -32,6 +33,7 @@ struct NormW { const float* g = nullptr; const float* b = nullptr; int c = 0; };
 struct ResW { NormW n1, n2; ConvW c1, c2, nin; };
 
 struct HostT { std::vector<float> d; std::vector<int64_t> shape; };
+struct GemmTap { dd_dev_vae_tap* t = nullptr; int seen = 0; };   // dd_dev_vae_trace: the caller's record, GEMM launches issued so far
 
 }  // namespace
 
@@ -60,6 +62,7 @@ struct dd_vae {
     // workspace
     float *s0 = nullptr, *s1 = nullptr, *h1 = nullptr, *part = nullptr, *score = nullptr, *ao = nullptr, *z4 = nullptr;
     void *nb = nullptr, *col = nullptr, *q = nullptr, *kk = nullptr, *vt = nullptr, *pp = nullptr;
+    GemmTap* tap = nullptr;     // set by dd_dev_vae_trace for the length of its call, null otherwise
 };
 
 namespace {
@@ -139,10 +142,41 @@ struct Net {
     Net(dd_vae* v_, int B_, int H_, hipStream_t s_)
         : v(v_), c(v_->ctx), s(s_), B(B_), H(H_), nb((T*)v_->nb), col((T*)v_->col), cur(v_->s0), other(v_->s1) {}
 
-    int gemm(const T* A, int M, int K, const ConvW& w, int epi, float* xres, T* o, int ldo) {
-        GemmArgs<T> g{A, nullptr, (const T*)w.w, w.b, xres, o, M, w.cout == 3 ? 4 : w.cout, K, K, K, 0, ldo};
+    // every GEMM of both directions is launched here; under dd_dev_vae_trace the chosen one is copied out around its launch
+    int launch(const GemmArgs<T>& g, int epi) {
+        if (v->tap) return traced(*v->tap, g, epi);
         VHIP(c, launch_gemm<T>(g, epi, s, c->num_cus));
         return DD_OK;
+    }
+    int traced(GemmTap& tp, const GemmArgs<T>& g, int epi) {
+        dd_dev_vae_tap& t = *tp.t;
+        const bool writes_x = epi == EPI_BIAS_RESID || epi == EPI_BIAS_SET, has_out = !writes_x && g.out;
+        const size_t a_b = (size_t)g.M * g.K * sizeof(T), w_b = (size_t)g.N * g.K * sizeof(T), x_b = writes_x ? (size_t)g.M * g.N * 4 : 0,
+                     o_b = has_out ? (size_t)g.M * g.ldo * sizeof(T) : 0;
+        t.max_a_bytes = std::max(t.max_a_bytes, (long long)a_b); t.max_w_bytes = std::max(t.max_w_bytes, (long long)w_b);
+        t.max_x_bytes = std::max(t.max_x_bytes, (long long)x_b); t.max_out_bytes = std::max(t.max_out_bytes, (long long)o_b);
+        if (tp.seen++ != t.ordinal) {
+            VHIP(c, launch_gemm<T>(g, epi, s, c->num_cus));
+            return DD_OK;
+        }
+        if (g.lda != g.K || g.K1 != g.K || g.A2) return ctx_fail(c, DD_ERR_UNSUPPORTED, "dd_dev_vae_trace: a launch whose A is not one [M, K] matrix");
+        if ((long long)a_b > t.a_bytes || (long long)w_b > t.w_bytes || (long long)g.N * 4 > t.bias_bytes || (long long)x_b > t.x_bytes || (long long)o_b > t.out_bytes || !t.A || !t.W ||
+            !t.bias || (x_b && (!t.x_before || !t.x_after)) || (o_b && !t.out))
+            return ctx_fail(c, DD_ERR_INVALID, "dd_dev_vae_trace: a host buffer is missing or too small for the chosen launch");
+        t.M = g.M; t.N = g.N; t.K = g.K; t.epilogue = epi; t.ldo = has_out ? g.ldo : 0; t.has_bias = g.bias ? 1 : 0; t.tapped = 1;
+        VHIP(c, hipStreamSynchronize(s));
+        VHIP(c, hipMemcpy(t.A, g.A, a_b, hipMemcpyDeviceToHost));
+        VHIP(c, hipMemcpy(t.W, g.W, w_b, hipMemcpyDeviceToHost));
+        if (g.bias) VHIP(c, hipMemcpy(t.bias, g.bias, (size_t)g.N * 4, hipMemcpyDeviceToHost));
+        if (x_b) VHIP(c, hipMemcpy(t.x_before, g.xres, x_b, hipMemcpyDeviceToHost));
+        VHIP(c, launch_gemm<T>(g, epi, s, c->num_cus));
+        VHIP(c, hipStreamSynchronize(s));
+        if (x_b) VHIP(c, hipMemcpy(t.x_after, g.xres, x_b, hipMemcpyDeviceToHost));
+        if (o_b) VHIP(c, hipMemcpy(t.out, g.out, o_b, hipMemcpyDeviceToHost));
+        return DD_OK;
+    }
+    int gemm(const T* A, int M, int K, const ConvW& w, int epi, float* xres, T* o, int ldo) {
+        return launch(GemmArgs<T>{A, nullptr, (const T*)w.w, w.b, xres, o, M, w.cout == 3 ? 4 : w.cout, K, K, K, 0, ldo}, epi);
     }
     // 3x3 conv of the T-typed NHWC image `src` (C channels at Hs x Hs, optionally upsampled 2x first)
     int conv3(const T* src, int Bn, int Hout, int C, int up, const ConvW& w, int epi, float* xres) {
@@ -182,16 +216,16 @@ struct Net {
             const T* hb = nb + (long long)b * HW * C;
             // V^T[c][tok] = Wv[c][:] . h[tok][:]  (bias of v is added after P.V: softmax rows sum to 1)
             GemmArgs<T> gv{(const T*)wv.w, nullptr, hb, nullptr, nullptr, (T*)v->vt, C, HW, C, C, C, 0, HW};
-            VHIP(c, launch_gemm<T>(gv, EPI_STORE, s, c->num_cus));
+            if ((rc = launch(gv, EPI_STORE))) return rc;
             // S[i][j] = q_i . k_j  -> fp32
             GemmArgs<T> gs{(const T*)v->q + (long long)b * HW * C, nullptr, (const T*)v->kk + (long long)b * HW * C, nullptr,
                            v->score, nullptr, HW, HW, C, C, C, 0, 0};
-            VHIP(c, launch_gemm<T>(gs, EPI_BIAS_SET, s, c->num_cus));
+            if ((rc = launch(gs, EPI_BIAS_SET))) return rc;
             VHIP(c, launch_softmax_rows<T>(v->score, (T*)v->pp, HW, HW, 1.0f / sqrtf((float)C), s));
             // O[i][c] = sum_j P[i][j] V^T[c][j] + b_v[c]
             GemmArgs<T> go{(const T*)v->pp, nullptr, (const T*)v->vt, wv.b, v->ao + (long long)b * HW * C, nullptr,
                            HW, C, HW, HW, HW, 0, 0};
-            VHIP(c, launch_gemm<T>(go, EPI_BIAS_SET, s, c->num_cus));
+            if ((rc = launch(go, EPI_BIAS_SET))) return rc;
         }
         VHIP(c, launch_cast<T>(v->ao, (T*)v->q, (long long)M * C, s));
         return gemm((const T*)v->q, M, C, wproj, EPI_BIAS_RESID, cur, nullptr, 0);  // x + proj_out(h_)
@@ -436,6 +470,27 @@ int dd_vae_sample(dd_ctx* c, const float* moments_dev, const float* eps_dev, flo
     if (!moments_dev || !z_dev || B < 1 || latent_hw < 1) return ctx_fail(c, DD_ERR_INVALID, "null tensor, empty batch or empty image");
     VHIP(c, launch_vae_sample(moments_dev, eps_dev, z_dev, B, latent_hw * latent_hw, (hipStream_t)stream));
     return DD_OK;
+}
+
+int dd_dev_vae_trace(dd_ctx* c, dd_vae* v, int encode, const float* in_dev, float* out_dev, int B, int hw, dd_dev_vae_tap* tap, void* stream) {
+    if (!c || !v || v->ctx != c || !tap) return DD_ERR_INVALID;
+    if (!v->finalized) return ctx_fail(c, DD_ERR_STATE, "dd_vae_finalize has not been called");
+    if (encode && !v->has_encoder) return ctx_fail(c, DD_ERR_UNSUPPORTED, "this autoencoder was loaded without the encoder (decode-only)");
+    const int hl = encode ? hw / 8 : hw;
+    if (!in_dev || !out_dev || B < 1 || B > v->max_chunk || hl < 1 || hl > v->max_latent || (encode && hw % 8) || (hl * hl) % 64)
+        return ctx_fail(c, DD_ERR_INVALID, "dd_dev_vae_trace: one chunk of images (B <= max_chunk) at a size dd_vae_decode / dd_vae_encode accepts");
+    hipStream_t s = (hipStream_t)stream;
+    GemmTap tp;
+    tp.t = tap;
+    tap->tapped = 0; tap->launches = 0;
+    tap->max_a_bytes = tap->max_w_bytes = tap->max_x_bytes = tap->max_out_bytes = 0;
+    v->tap = &tp;
+    const bool bf = v->prec == DD_PREC_BF16;
+    const int rc = encode ? (bf ? run_encode<bf16_t>(v, in_dev, nullptr, out_dev, nullptr, B, hw, s) : run_encode<float>(v, in_dev, nullptr, out_dev, nullptr, B, hw, s))
+                          : (bf ? run_decode<bf16_t>(v, in_dev, out_dev, B, hw, s) : run_decode<float>(v, in_dev, out_dev, B, hw, s));
+    v->tap = nullptr;
+    tap->launches = tp.seen;
+    return rc;
 }
 
 void dd_vae_destroy(dd_vae* v) {

@@ -128,7 +128,8 @@ int dd_dev_head_dec(dd_ctx* ctx, int M, int D, int pd, int tok_l, int tok_e, con
                     int split, int iters, void* stream, float* ms_out);
 
 /* Development harness for the GEMM path (gemm.hip; what the model's Linears launch): C = [A | A2] . W^T from host arrays -- A [M, K1]
- * (K1 = 0: K), A2 [M, K - K1] or NULL (K1 == K), W [N, K], bias [N] or NULL; precision DD_PREC_BF16 (operands rounded to bf16: the persistent
+ * (K1 = 0: K), A2 [M, K - K1] or NULL (K1 == K), W [N, K], bias [N] or NULL (NULL: EPI_STORE, or EPI_BIAS_SET without a bias as the KL-VAE's
+ * S = Q . K^T launches it; any other epilogue without one is DD_ERR_INVALID); precision DD_PREC_BF16 (operands rounded to bf16: the persistent
  * 256 x 256 kernel where the shape fits it, else the 128 x 128 one; tile128 -1 / 0 / 1 as GemmArgs::tile128) or DD_PREC_FP32 (the exact-f32 parity
  * kernels, 128 x 128 or, N <= 64, 128 x 64).  splits == 0: ONE launch_gemm with `epilogue` (dd_internal.h GemmEpilogue EPI_STORE .. EPI_BIAS_STORE),
  * hm_L > 0: out is written head-major (HeadMajor: images of hm_L rows, hm_H heads, N = 192 hm_H).  splits >= 2 (bf16): the split-K launch into
@@ -246,6 +247,28 @@ int dd_dev_vae_output(dd_ctx* ctx, int B, int C, int HW, int ldc, const float* i
 int dd_dev_vae_moments(dd_ctx* ctx, int B, int HW, const float* h_host, const float* w, const float* b, const float* eps_host,
                        float* moments_host, float* z_host, void* stream);
 int dd_dev_cast(dd_ctx* ctx, int precision, long long n, const float* x_host, void* out_host, void* stream);
+
+/* One GEMM launch of a real KL-VAE decode or encode, copied out as the kernel sees it.  dd_dev_vae_trace runs run_decode (encode == 0:
+ * in_dev = z [B, 4, hw, hw], out_dev = images [B, 3, 8 hw, 8 hw]) or run_encode (encode != 0: in_dev = x [B, 3, hw, hw], out_dev = moments
+ * [B, 8, hw / 8, hw / 8]) on ONE chunk (B <= max_chunk) of a finalized dd_vae; both are device pointers.  Every GEMM of either direction leaves
+ * through one function (vae.hip Net::launch); they are counted in issue order, and launch number `ordinal` is copied to the caller's host
+ * buffers around its launch (two stream synchronisations, only in this entry): A [M, K] and W [N, K] elements of the object's precision
+ * (bf16 bits / fp32; W is the launch's second operand, whatever it holds), bias [N] fp32 (has_bias == 0: the launch has none, nothing is
+ * written), and for the epilogues that write the fp32 stream (EPI_BIAS_SET, EPI_BIAS_RESID) x_before / x_after [M, N] fp32, else out
+ * [M, ldo] elements of the precision.  *_bytes are the buffers' capacities; a launch that needs more is DD_ERR_INVALID.  ordinal < 0 (or
+ * past the last launch) copies nothing: `launches` and the max_*_bytes any launch of the pass would need come back either way, tapped says
+ * whether a launch was copied.  The pass computes what dd_vae_decode / dd_vae_encode compute. */
+typedef struct dd_dev_vae_tap {
+    int ordinal;
+    void *A, *W;
+    float *bias, *x_before, *x_after;
+    void* out;
+    long long a_bytes, w_bytes, bias_bytes, x_bytes, out_bytes;
+    int tapped, launches, M, N, K, epilogue, ldo, has_bias;
+    long long max_a_bytes, max_w_bytes, max_x_bytes, max_out_bytes;
+} dd_dev_vae_tap;
+int dd_dev_vae_trace(dd_ctx* ctx, dd_vae* vae, int encode, const float* in_dev, float* out_dev, int B, int hw, dd_dev_vae_tap* tap,
+                     void* stream);
 
 /* Development harnesses for the early-exit probes (rowops.hip; reference models/early_exit.py:31-80), each through its production launch_*
  * function on host fp32 arrays.  Every output has DD_DEV_EE_TAIL elements behind the last one the launch may write; the whole buffer is

@@ -1,5 +1,5 @@
 """What the per-element kernel tests share (test_attention, test_block_tail, test_frag_handoff, test_gemm_path, test_row_kernels,
-test_qkv_attention, test_mlp_fused, test_pag, test_head_dec): bf16 arithmetic on the host, the elementwise gate, the constants of the bounds,
+test_qkv_attention, test_mlp_fused, test_pag, test_head_dec, test_vae_gemm): bf16 arithmetic on the host, the elementwise gate, the constants of the bounds,
 the LayerNorm bound of the GEMM-path tests, the MFMA fragment order, the references of the output head + step launch (test_final_step) and
 of the KL-VAE kernels (test_vae_kernels) and of the early-exit probes (test_ee_probes).  tests/test_kernel_support.py (CPU) pins every piece of it."""
 import numpy as np

@@ -153,6 +153,9 @@ def test_longest_prototypes_position_by_position():
     assert len(thr) == 18 and L.SIGNATURES["dd_threshold_step"] == (C.c_int, thr)
     # ctx | B C S P D extras num_classes normalize generic | x_img w bias pos label_emb y t_vec | t_state | ln x_tok_host ln_frag_host | iters stream ms_out
     assert L.SIGNATURES["dd_dev_embed"] == (C.c_int, _kinds("p i*9 p*7 f p*3 i p p")) and len(L.SIGNATURES["dd_dev_embed"][1]) == 24
+    # ctx vae | encode | in_dev out_dev | B hw | tap | stream; the tap record: ordinal | 6 host buffers | 5 capacities | 8 results | 4 sizes
+    assert L.SIGNATURES["dd_dev_vae_trace"] == (C.c_int, _kinds("p p i p p i i") + [C.POINTER(L.dd_dev_vae_tap)] + _kinds("p"))
+    assert [t for _, t in L.dd_dev_vae_tap._fields_] == _kinds("i p*6") + [C.c_longlong] * 5 + _kinds("i*8") + [C.c_longlong] * 4
     f = L.dd_dev_final_args._fields_
     assert len(f) == 60 and f[-1] == ("seed_out", C.c_ulonglong) and f[0] == ("B", C.c_int) and f[8] == ("dec", C.c_void_p)
     assert dict(f)["w_stride"] is C.c_longlong and dict(f)["guide_scale"] is C.c_float and dict(f)["h"] is C.c_void_p

@@ -102,13 +102,22 @@ def ln_params(D, seed):
 
 
 # ---------------------------------------------------------------------------------------------------------------- checks
-def check_linear(name, M, N, K, epi, K1=0, prec=PREC_BF16, tile128=-1, ldo=None, seed=0, with_out=True, num_cus=0):
+def check_linear(name, M, N, K, epi, K1=0, prec=PREC_BF16, tile128=-1, ldo=None, seed=0, with_out=True, num_cus=0, ops=None, rel=None,
+                 report=None):
+    """one launch under the gates of the module docstring.  ops: the caller's (A, W, bias, x_in) instead of operands(seed) -- bias None
+    (EPI_STORE, or EPI_BIAS_SET without a bias): the launch gets a null bias and the reference adds none; x_in None: x holds canary bytes
+    before the launch.  rel: the factor of the fp32 term where the caller has derived one for its class of operands (tests/test_vae_gemm.py);
+    None: FP32_REL / PARITY_REL.  report: a dict that receives the largest error / bound ratios"""
     span = 12.0 if epi == EPI_BIAS_GELU else None
-    A, W, bias, x_in = operands(M, N, K, seed, bias_span=span)
+    A, W, bias, x_in = ops if ops is not None else operands(M, N, K, seed, bias_span=span)
+    assert A.shape == (M, K) and W.shape == (N, K) and (bias is not None or epi in (EPI_STORE, EPI_BIAS_SET))
     xres, out, _, _, _ = run_gemm(A, W, bias, x_in, epi, K1=K1, prec=prec, tile128=tile128, ldo=ldo, with_out=with_out, num_cus=num_cus)
     acc, absum = linear_ref(A, W, prec)
-    rel = FP32_REL if prec == PREC_BF16 else PARITY_REL
-    b64 = bias.astype(np.float64)
+    rel = rel if rel is not None else FP32_REL if prec == PREC_BF16 else PARITY_REL
+    b64 = bias.astype(np.float64) if bias is not None else np.zeros(N)
+    if x_in is None:
+        assert epi != EPI_BIAS_RESID
+        x_in = np.full((M, N), NAN32, np.uint32).view(np.float32)      # (the canary bytes run_gemm fills x with: an epilogue that does not write x leaves them)
     pre = acc + (b64 if epi != EPI_STORE else 0.0)
     t32 = rel * (absum + (np.abs(b64) if epi != EPI_STORE else 0.0))
     ratios = {}
@@ -118,7 +127,7 @@ def check_linear(name, M, N, K, epi, K1=0, prec=PREC_BF16, tile128=-1, ldo=None,
         ratios["x"] = gate(xres[:M], xref, tx, f"{name}: x")
         oref, tout = xref, tx
     else:
-        assert np.array_equal(xres[:M], x_in), f"{name}: x written by an epilogue that does not write it"
+        assert np.array_equal(xres[:M].view(np.uint32), np.ascontiguousarray(x_in, np.float32).view(np.uint32)), f"{name}: x written by an epilogue that does not write it"
         if epi == EPI_BIAS_GELU:
             oref = gelu_exact(pre)
             tout = GELU_SLOPE * t32 + (GELU_POLY + 2.0 ** -22 * np.abs(pre) if prec == PREC_BF16 else 4 * 2.0 ** -24 * np.abs(oref))
@@ -137,6 +146,8 @@ def check_linear(name, M, N, K, epi, K1=0, prec=PREC_BF16, tile128=-1, ldo=None,
         assert untouched(out), f"{name}: EPI_BIAS_SET wrote out"
     print(f"{name}: M={M} N={N} K={K} K1={K1 or K} {EPI_NAME[epi]} tile128={tile128} ldo={ldo or N}: max err/bound "
           + ", ".join(f"{k} {v:.3f}" for k, v in ratios.items()))
+    if report is not None:
+        report.update(ratios)
     return xres, out
 
 

@@ -203,7 +203,7 @@ def test_bench_roofline_leg_follows_the_committed_kernel_table():
     # pointer null and every integer 0: they check the context before anything touches the GPU
     for name in ("dd_dev_mlp", "dd_dev_block_tail", "dd_dev_qkv_attention", "dd_dev_qkv_attention_rows", "dd_dev_head_dec", "dd_dev_gemm", "dd_dev_rowlin", "dd_dev_attention",
                  "dd_dev_layernorm", "dd_dev_embed", "dd_dev_time_mlp", "dd_dev_final", "dd_dev_vae_gather", "dd_dev_groupnorm", "dd_dev_softmax_rows", "dd_dev_vae_input",
-                 "dd_dev_vae_output", "dd_dev_vae_moments", "dd_dev_cast", "dd_dev_ee_probe", "dd_dev_ee_probe_reduce", "dd_dev_ee_attn_probe"):
+                 "dd_dev_vae_output", "dd_dev_vae_moments", "dd_dev_cast", "dd_dev_vae_trace", "dd_dev_ee_probe", "dd_dev_ee_probe_reduce", "dd_dev_ee_attn_probe"):
         args = [0 if t in (ctypes.c_int, ctypes.c_longlong, ctypes.c_size_t) else 0.0 if t is ctypes.c_float else None for t in _lib.SIGNATURES[name][1]]
         assert getattr(lib, name)(*args) == _lib.DD_ERR_INVALID, name
 

@@ -16,10 +16,11 @@ import torch
 
 from conftest import REPO, TINY
 from duodiff_amd import _lib as L
-from duodiff_amd.config import ModelParams, load_config
+from duodiff_amd.config import ModelParams
 from duodiff_amd.engine import Autoguidance
 from duodiff_amd.weights import synthetic_state_dict
-from loop_support import cli_argv, engine_pair, eps_rms_bound, side_stream, uvit
+from loop_support import KINDS, celeba_pair, cli_argv, engine_pair, eps_rms_bound, first_rows, imagenet256_pair, images, labels
+from loop_support import run_first_steps, run_steps, side_stream, uvit
 
 gpu = pytest.mark.gpu
 
@@ -107,65 +108,6 @@ def _tiny_pair(seeds=(41, 42), max_batch=12, precision="bf16"):
     return _pair(TINY_G, TINY_M, seeds, max_batch, precision)
 
 
-def _celeba_pair(max_batch=128):
-    return _pair(load_config(CONFIGS / "uvit_celeba_3.yaml"), load_config(CONFIGS / "uvit_celeba.yaml"), (51, 52), max_batch)
-
-
-def _imagenet256_pair(max_batch=32):
-    return _pair(load_config(CONFIGS / "uvit_imagenet256_3.yaml"), load_config(CONFIGS / "uvit_imagenet256.yaml"), (53, 54), max_batch)
-
-
-def _x0(B, Cc, S, seed):
-    return torch.randn(B, Cc, S, S, generator=torch.Generator().manual_seed(seed)).cuda()
-
-
-class _flags:
-    def __init__(self, ctx, flags):
-        self.ctx, self.flags = ctx, flags
-
-    def __enter__(self):
-        self.ctx.check(self.ctx.lib.dd_dev_set_flags(self.ctx.handle, self.flags))
-
-    def __exit__(self, *exc):
-        self.ctx.check(self.ctx.lib.dd_dev_set_flags(self.ctx.handle, 0))
-
-
-def _affine_rows(n):
-    """n predict_original rows, t = 999 .. 1000 - n: finite a, b and a noise coefficient c > 0 (a DDIM row's c is 0 at eta 0, and at
-    eta > 0 the reference's last DDIM row is NaN)"""
-    from duodiff_amd import sampler
-    ts = list(range(999, 999 - n, -1))
-    co = [sampler.affine_coefficients("predict_original", t) for t in ts]
-    return dict(t=np.array(ts, F32), a=np.array([c[0] for c in co], F32), b=np.array([c[1] for c in co], F32),
-                c=np.array([c[2] for c in co], F32), noise=np.array([int(t > 0) for t in ts], np.int32))
-
-
-def _ms_rows(n, kind="sde-dpmsolver++"):
-    from duodiff_amd import sampler
-    return sampler.multistep_coefficients(kind, sampler.multistep_grid(n), 2)
-
-
-def _run(kind, ctx, first, late, x0, stream, *, switch, n=8, **kw):
-    """One device loop of `kind` over n steps on a copy of x0: DDPM t = 999 .. 1000 - n (late after `switch` steps), n predict_original rows or
-    DPM-Solver++-n (late from step `switch`).  Returns x (multistep: (x, h))."""
-    from duodiff_amd.engine import sample_affine_loop, sample_loop, sample_multistep_loop
-    x = x0.clone()
-    with torch.cuda.stream(stream):
-        if kind == "ddpm":
-            sample_loop(ctx, first, late, x, t_switch=switch, t_start=999, t_end=1000 - n, stream=stream, **kw)
-        elif kind == "affine":
-            r = _affine_rows(n)
-            sample_affine_loop(ctx, first, late, x, r["t"], r["a"], r["b"], r["c"], r["noise"], switch_after=switch, stream=stream, **kw)
-        else:
-            h = torch.zeros_like(x)
-            sample_multistep_loop(ctx, first, late, x, h, _ms_rows(n), switch_after=switch, stream=stream, **kw)
-        stream.synchronize()
-    return x if kind != "multistep" else torch.stack([x, h])
-
-
-KINDS = ["ddpm", "affine", "multistep"]
-
-
 @gpu
 @pytest.mark.parametrize("case", ["tiny_one_tile", "tiled_32x32", "conditional_main_unconditional_guide"])
 def test_forward_autoguided_vs_oracle(case):
@@ -225,13 +167,12 @@ def test_scale_zero_equals_the_unguided_loop(case, kind):
         eg, em = _tiny_pair(max_batch=B)
     else:
         B, S, n, flags = 128, 64, 3, 0
-        eg, em = _celeba_pair(B)
-    ctx, x0, stream = em.ctx, _x0(B, 3, S, 7), side_stream()
-    with _flags(ctx, flags):
-        want = _run(kind, ctx, em, None, x0, stream, switch=0, n=n, seed=21)
-        chains = ctx.lib.dd_dev_last_sample_chains(ctx.handle)
-        got = _run(kind, ctx, em, None, x0, stream, switch=0, n=n, seed=21, guidance=Autoguidance(eg, 0.0))
-        assert chains == ctx.lib.dd_dev_last_sample_chains(ctx.handle) == 2
+        eg, em = celeba_pair(B)[:2]
+    ctx, x0, stream = em.ctx, images(B, 3, S, 7), side_stream()
+    want = run_first_steps(kind, em, None, x0, stream, switch=0, n=n, seed=21, flags=flags)
+    chains = ctx.lib.dd_dev_last_sample_chains(ctx.handle)
+    got = run_first_steps(kind, em, None, x0, stream, switch=0, n=n, seed=21, flags=flags, guidance=Autoguidance(eg, 0.0))
+    assert chains == ctx.lib.dd_dev_last_sample_chains(ctx.handle) == 2
     assert torch.isfinite(got).all() and not torch.equal(got if kind != "multistep" else got[0], x0)
     assert torch.equal(got, want), "scale 0 differs from the unguided loop"
 
@@ -245,12 +186,12 @@ def test_the_guides_identity_decides_the_launch_not_its_weights(kind):
     B = 4
     _, em = _tiny_pair(max_batch=B)
     _, twin = _tiny_pair(max_batch=B)                # the same seeds: the same weights, another dd_model
-    ctx, x0, stream = em.ctx, _x0(B, 3, 8, 9), side_stream()
-    want = _run(kind, ctx, em, None, x0, stream, switch=0, seed=22)
+    ctx, x0, stream = em.ctx, images(B, 3, 8, 9), side_stream()
+    want = run_first_steps(kind, em, None, x0, stream, switch=0, seed=22)
     n0 = ctx.lib.dd_dev_graph_captures(ctx.handle)
-    same = _run(kind, ctx, em, None, x0, stream, switch=0, seed=22, guidance=Autoguidance(em, 1.7))
+    same = run_first_steps(kind, em, None, x0, stream, switch=0, seed=22, guidance=Autoguidance(em, 1.7))
     assert ctx.lib.dd_dev_graph_captures(ctx.handle) == n0, "guide == the running model captured a graph of its own"
-    other = _run(kind, ctx, em, None, x0, stream, switch=0, seed=22, guidance=Autoguidance(twin, 1.7))
+    other = run_first_steps(kind, em, None, x0, stream, switch=0, seed=22, guidance=Autoguidance(twin, 1.7))
     assert ctx.lib.dd_dev_graph_captures(ctx.handle) == n0 + 1, "the two-model path did not capture its own graph"
     assert torch.isfinite(want).all()
     assert torch.equal(same, want), "guide == the running model differs from the unguided loop"
@@ -265,7 +206,7 @@ def test_the_duodiff_call():
     from duodiff_amd.engine import sample_loop
     B, s = 4, 1.7
     eg, em = _tiny_pair(max_batch=B)
-    ctx, x0, stream = em.ctx, _x0(B, 3, 8, 10), side_stream()
+    ctx, x0, stream = em.ctx, images(B, 3, 8, 10), side_stream()
     out = {}
     with torch.cuda.stream(stream):
         for name, ag in (("unguided", None), ("auto", Autoguidance(eg, s))):
@@ -296,27 +237,12 @@ def test_autoguided_loops_equal_manual_steps(kind):
     """No noise, s = 1.7, the backbone switch inside (the guide runs the first steps itself): the device loop, graph-replayed and eager,
     == forward_autoguided + ddpm_step / affine_step / multistep_step per step; and (Philox noise) the loop cut at a save point, with
     counter_base and h carried over, == the uncut loop."""
-    from duodiff_amd.engine import sample_affine_loop, sample_multistep_loop
     B, s, n, sw = 4, 1.7, 8, 3
     eg, em = _tiny_pair(max_batch=B)
-    ctx, x0, stream = em.ctx, _x0(B, 3, 8, 11), side_stream()
+    x0, stream = images(B, 3, 8, 11), side_stream()
     ag = Autoguidance(eg, s)
-    loops = [_run(kind, ctx, eg, em, x0, stream, switch=sw, n=n, noise="none", use_graph=ug, guidance=ag) for ug in (True, False)]
-    rows = None if kind == "ddpm" else _affine_rows(n) if kind == "affine" else _ms_rows(n)
-    xm, eps, h = x0.clone(), torch.empty_like(x0), torch.zeros_like(x0)
-    with torch.cuda.stream(stream):
-        for k in range(n):
-            t = 999 - k if kind == "ddpm" else float(rows["t"][k])
-            # dd_sample switches AFTER the step at t == 1000 - t_switch; the table loops run late FROM step switch_after
-            cur = (eg if k < sw else em)
-            cur.forward_autoguided(xm, t, None, eg, s, out=eps, stream=stream)
-            if kind == "ddpm":
-                ctx.ddpm_step(xm, eps, None, t, out=xm, stream=stream)
-            elif kind == "affine":
-                ctx.affine_step(xm, eps, None, rows["a"][k], rows["b"][k], 0.0, out=xm, stream=stream)
-            else:
-                ctx.multistep_step(xm, eps, None, h, *(rows[key][k] for key in "abcdpq"), rows["hist"][k], out=xm, stream=stream)
-        stream.synchronize()
+    loops = [run_first_steps(kind, eg, em, x0, stream, switch=sw, n=n, noise="none", use_graph=ug, guidance=ag) for ug in (True, False)]
+    xm, h = run_steps(kind, eg, x0, first_rows(kind, n), stream, late=em, switch_after=sw, noise="none", guidance=ag)
     manual = xm if kind != "multistep" else torch.stack([xm, h])
     assert torch.isfinite(manual).all() and not torch.equal(xm, x0)
     assert torch.equal(loops[0], loops[1]), "graph replay differs from eager launches"
@@ -324,18 +250,8 @@ def test_autoguided_loops_equal_manual_steps(kind):
     if kind == "ddpm":
         return
     # save-point cut after 5 steps (past the switch): counter_base = 5, h carried over
-    whole = _run(kind, ctx, eg, em, x0, stream, switch=sw, n=n, seed=24, guidance=ag)
-    x, hh = x0.clone(), torch.zeros_like(x0)
-    with torch.cuda.stream(stream):
-        for k0, k1, first, late, sw_seg in ((0, 5, eg, em, sw), (5, n, em, None, None)):
-            seg = {key: v[k0:k1] for key, v in rows.items()}
-            kw = dict(switch_after=sw_seg, seed=24, counter_base=k0, stream=stream, guidance=ag)
-            if kind == "affine":
-                sample_affine_loop(ctx, first, late, x, seg["t"], seg["a"], seg["b"], seg["c"], seg["noise"], **kw)
-            else:
-                sample_multistep_loop(ctx, first, late, x, hh, seg, **kw)
-        stream.synchronize()
-    cut = x if kind == "affine" else torch.stack([x, hh])
+    whole = run_first_steps(kind, eg, em, x0, stream, switch=sw, n=n, seed=24, guidance=ag)
+    cut = run_first_steps(kind, eg, em, x0, stream, switch=sw, n=n, seed=24, guidance=ag, cuts=(5,))
     assert torch.equal(cut, whole), "the cut loop differs from the uncut loop"
 
 
@@ -350,20 +266,16 @@ def test_autoguided_two_chains_equal_one_chain(case):
         eg, em = _tiny_pair(max_batch=B)
     elif case == "celeba_b128":
         B, S, Cc, n, sw, force = 128, 64, 3, 3, 1, 0
-        eg, em = _celeba_pair(B)
+        eg, em = celeba_pair(B)[:2]
     else:
         B, S, Cc, n, sw, force = 32, 32, 4, 3, 1, 0
-        eg, em = _imagenet256_pair(B)
-        y = torch.randint(0, 1000, (B,), generator=torch.Generator().manual_seed(12)).cuda()
-    ctx, x0, stream = em.ctx, _x0(B, Cc, S, 12), side_stream()
+        eg, em = imagenet256_pair(B, (53, 54))[:2]
+        y = labels(B, 1000, 12)
+    ctx, x0, stream = em.ctx, images(B, Cc, S, 12), side_stream()
     outs = {}
-    try:
-        for name, flags in (("chained", force), ("single", L.DD_DEV_NO_CHAINS)):
-            ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
-            x = _run("ddpm", ctx, eg, em, x0, stream, switch=sw, n=n, seed=25, y=y, guidance=Autoguidance(eg, 1.7))
-            outs[name] = (x, ctx.lib.dd_dev_last_sample_chains(ctx.handle))
-    finally:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
+    for name, flags in (("chained", force), ("single", L.DD_DEV_NO_CHAINS)):
+        x = run_first_steps("ddpm", eg, em, x0, stream, switch=sw, n=n, seed=25, y=y, flags=flags, guidance=Autoguidance(eg, 1.7))
+        outs[name] = (x, ctx.lib.dd_dev_last_sample_chains(ctx.handle))
     assert outs["chained"][1] == 2 and outs["single"][1] == 1
     assert torch.isfinite(outs["single"][0]).all() and not torch.equal(outs["single"][0], x0)
     assert torch.equal(outs["chained"][0], outs["single"][0]), "autoguided chains differ from the single chain"
@@ -375,8 +287,8 @@ def test_no_stale_graph():
     autoguided and unguided calls alternated on one (class-conditional) pair each reproduce their own first result."""
     B = 4
     cfg_g, cfg_m = dict(TINY_G, num_classes=11), dict(TINY_M, num_classes=11)
-    x0, stream = _x0(B, 3, 8, 13), side_stream()
-    y = torch.randint(0, 10, (B,), generator=torch.Generator().manual_seed(14)).cuda()
+    x0, stream = images(B, 3, 8, 13), side_stream()
+    y = labels(B, 10, 14)
 
     def models():
         eg, em = _pair(cfg_g, cfg_m, (41, 42), 2 * B)
@@ -386,12 +298,12 @@ def test_no_stale_graph():
     def run(ms, what):
         eg, em, eg2 = ms
         kw = dict(switch=0, seed=26, y=y)
-        return {"s0.4": lambda: _run("ddpm", em.ctx, em, None, x0, stream, guidance=Autoguidance(eg, 0.4), **kw),
-                "s1.7": lambda: _run("ddpm", em.ctx, em, None, x0, stream, guidance=Autoguidance(eg, 1.7), **kw),
-                "guide2": lambda: _run("ddpm", em.ctx, em, None, x0, stream, guidance=Autoguidance(eg2, 1.7), **kw),
-                "swapped": lambda: _run("ddpm", em.ctx, eg, None, x0, stream, guidance=Autoguidance(em, 1.7), **kw),
-                "cfg": lambda: _run("ddpm", em.ctx, em, None, x0, stream, guidance=(1.7, 10), **kw),
-                "plain": lambda: _run("ddpm", em.ctx, em, None, x0, stream, **kw)}[what]()
+        return {"s0.4": lambda: run_first_steps("ddpm", em, None, x0, stream, guidance=Autoguidance(eg, 0.4), **kw),
+                "s1.7": lambda: run_first_steps("ddpm", em, None, x0, stream, guidance=Autoguidance(eg, 1.7), **kw),
+                "guide2": lambda: run_first_steps("ddpm", em, None, x0, stream, guidance=Autoguidance(eg2, 1.7), **kw),
+                "swapped": lambda: run_first_steps("ddpm", eg, None, x0, stream, guidance=Autoguidance(em, 1.7), **kw),
+                "cfg": lambda: run_first_steps("ddpm", em, None, x0, stream, guidance=(1.7, 10), **kw),
+                "plain": lambda: run_first_steps("ddpm", em, None, x0, stream, **kw)}[what]()
 
     ms = models()
     ctx = ms[0].ctx
@@ -419,18 +331,17 @@ def test_no_stale_graph():
 def test_autoguided_loop_reads_no_stale_workspace_bytes():
     """Both chains' workspaces of both models poisoned (NaN bytes) in front of the first autoguided dd_sample == fresh models."""
     B = 6
-    x0, stream = _x0(B, 3, 8, 15), side_stream()
+    x0, stream = images(B, 3, 8, 15), side_stream()
     outs = []
     for poison in (False, True):
         eg, em = _tiny_pair(seeds=(71, 72), max_batch=B)
         ctx = em.ctx
-        with _flags(ctx, L.DD_DEV_FORCE_CHAINS):
-            if poison:
-                with torch.cuda.stream(stream):
-                    for e in (eg, em):
-                        ctx.check(ctx.lib.dd_dev_poison_workspaces(ctx.handle, e.handle, stream.cuda_stream))
-            x = _run("ddpm", ctx, eg, em, x0, stream, switch=3, seed=27, guidance=Autoguidance(eg, 1.7))
-            outs.append((x, ctx.lib.dd_dev_last_sample_chains(ctx.handle)))
+        if poison:
+            with torch.cuda.stream(stream):
+                for e in (eg, em):
+                    ctx.check(ctx.lib.dd_dev_poison_workspaces(ctx.handle, e.handle, stream.cuda_stream))
+        x = run_first_steps("ddpm", eg, em, x0, stream, switch=3, seed=27, flags=L.DD_DEV_FORCE_CHAINS, guidance=Autoguidance(eg, 1.7))
+        outs.append((x, ctx.lib.dd_dev_last_sample_chains(ctx.handle)))
         del eg, em
     assert outs[0][1] == outs[1][1] == 2
     assert torch.isfinite(outs[0][0]).all() and not torch.equal(outs[0][0], x0)
@@ -460,8 +371,8 @@ def test_invalid_autoguided_calls_are_rejected_before_anything_is_enqueued():
     for k, v in synthetic_state_dict(ModelParams.from_dict(TINY_G), 90).items():
         g_other.set_param(k, v)
     g_other.finalize("bf16")
-    x0, stream = _x0(B, 3, 8, 17), side_stream()
-    y = torch.randint(0, 10, (B,), generator=torch.Generator().manual_seed(18)).cuda()
+    x0, stream = images(B, 3, 8, 17), side_stream()
+    y = labels(B, 10, 18)
     NULLG = object()
     #        first  late   guide    scale          y     message
     cases = [(em, None, NULLG, 1.0, None, "dd_autoguidance"), (em, None, None, 1.0, None, "guide"),

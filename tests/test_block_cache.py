@@ -25,10 +25,9 @@ from duodiff_amd import step_plan as sp
 from duodiff_amd.config import ModelParams
 from duodiff_amd.weights import synthetic_state_dict
 from kernel_support import NAN16, NAN32, P, bf16_bits, from_bf16_bits, gate
-from loop_support import engine_pair, eps_rms_bound, philox_z, philox_z2, side_stream, uvit
-from test_autoguidance import _flags, _x0
+from loop_support import QA512, TAIL256, TINY_COND, dev_flags, engine_pair, eps_rms_bound, images, known_region, labels, run_loop, run_steps
+from loop_support import side_stream, uvit
 from test_block_cache_cpu import extrapolate_operands, extrapolate_ref
-from test_pag import QA512, TAIL256
 
 gpu = pytest.mark.gpu
 
@@ -98,8 +97,6 @@ IMNET64_768 = dict(img_size=64, patch_size=4, in_chans=3, embed_dim=768, depth=5
                    mlp_time_embed=False, num_classes=11, normalize_timesteps=False)          # row-resident launches, class-conditional
 IMNET256_1024 = dict(img_size=32, patch_size=2, in_chans=4, embed_dim=1024, depth=5, num_heads=16, mlp_ratio=4, qkv_bias=False,
                      mlp_time_embed=False, num_classes=11, normalize_timesteps=False)        # split-K
-TINY_COND = dict(TINY, num_classes=11)
-
 # name: (config, depth, K, B, dev flags)
 FORWARD_CASES = {}
 for _name, _cfg, _B, _flags_ in (("tiny", TINY, 3, 0), ("tail256", TAIL256, 3, 0), ("qa512", QA512, 2, 0),
@@ -208,7 +205,7 @@ def test_forward_cached_vs_oracle(monkeypatch, case):
     yd = None if y is None else y.cuda()
     xd = [x.cuda() for x in xs]
     for prec in ("fp32", "bf16"):
-        with _flags(kernel_support.ctx(), flags):
+        with dev_flags(kernel_support.ctx(), flags):
             m, _ = uvit(cfg, 61, prec, max_batch=B)
             em = m.engine_model(B)
         r1 = em.forward_cached(xd[0], TS[0], yd, blocks=K, op=0)
@@ -291,40 +288,15 @@ def _plan(kind, n, N, order, late=True, t_switch=4, K=1, **kw):
                         cache_interval=N, cache_order=order, **kw)
 
 
-def _device(plan, K, order, first, late, x0, stream, *, cuts=(), region=None, **kw):
-    """the plan as device loop calls on a copy of x0, cut after the steps `cuts`"""
-    from duodiff_amd import sampler
-    from duodiff_amd.engine import sample_affine_cached_loop
-    x, n = x0.clone(), len(plan.rows["t"])
-    edges = [0, *[c + 1 for c in cuts], n]
-    with torch.cuda.stream(stream):
-        for k0, k1 in zip(edges[:-1], edges[1:]):
-            m0, m1, sw = sampler._segment_models(plan, k0, k1, first, late)
-            seg = {key: v[k0:k1] for key, v in plan.rows.items()}
-            reg = None if region is None else region._replace(ka=region.ka[k0:k1], kb=region.kb[k0:k1])
-            sample_affine_cached_loop(first.ctx, m0, m1, x, seg, blocks=K, order=order, switch_after=sw, counter_base=k0, region=reg,
-                                      stream=stream, **kw)
-        stream.synchronize()
-    return x
+def _device(plan, K, order, first, late, x0, stream, *, cuts=(), seed=0, **kw):
+    """the plan as device loop calls on a copy of x0, cut AFTER the steps `cuts`; kw: run_loop's (region: a KnownRegion) -> x"""
+    return run_loop("cached", first, x0, plan, stream, late=late, switch_after=plan.switch_after, cache=(K, order), cuts=[c + 1 for c in cuts],
+                    seed=seed, **kw)[0]
 
 
-def _manual(plan, K, first, late, x0, stream, *, seed=0, noise="none", guidance=None, y=None, region=None):
+def _manual(plan, K, first, late, x0, stream, *, seed=0, noise="none", **kw):
     """forward_cached + affine_step [+ known_blend] per step, z and z2 as the device loop draws them"""
-    ctx, tab = first.ctx, plan.rows
-    x, eps = x0.clone(), torch.empty_like(x0)
-    for k in range(len(tab["t"])):
-        cur = late if plan.switch_after is not None and k >= plan.switch_after else first
-        yk = y if cur.mp.num_classes > 0 else None
-        z = philox_z(cur, x0, k, seed, stream, yk) if noise == "philox" and tab["noise"][k] else None
-        z2 = philox_z2(cur, x0, k, seed, stream, yk) if region is not None and noise == "philox" and region.kb[k] != 0 else None
-        with torch.cuda.stream(stream):
-            cur.forward_cached(x, float(tab["t"][k]), yk, blocks=K, op=int(tab["cache"][k]), w=float(tab["cw"][k]), guidance=guidance, out=eps,
-                               stream=stream)
-            ctx.affine_step(x, eps, z, tab["a"][k], tab["b"][k], tab["c"][k], out=x, stream=stream)
-            if region is not None:
-                ctx.known_blend(x, region.x0, region.mask, z2, region.ka[k], region.kb[k], out=x, stream=stream)
-    stream.synchronize()
-    return x
+    return run_steps("cached", first, x0, plan, stream, late=late, switch_after=plan.switch_after, cache=(K, None), seed=seed, noise=noise, **kw)[0]
 
 
 @gpu
@@ -336,7 +308,7 @@ def test_cached_loop_equals_manual_steps(kind, noise, order):
     from duodiff_amd.engine import sample_affine_loop
     B = 4
     es, ef = _pair(B)
-    x0, stream = _x0(B, 3, 8, 11), side_stream()
+    x0, stream = images(B, 3, 8, 11), side_stream()
     plan = _plan(kind, 9, 3, order)
     assert plan.switch_after is not None and plan.rows["cache"][plan.switch_after] == 0 and (plan.switch_after % 3) != 0
     assert (2 in plan.rows["cache"]) == (order == 1)
@@ -360,7 +332,7 @@ def test_interval_one_equals_the_uncached_affine_loop():
     from duodiff_amd.engine import sample_affine_loop
     B = 4
     es, ef, _ = engine_pair(dict(TINY, depth=3), dict(TINY, depth=5), (41, 42), B, precision="fp32")
-    x0, stream = _x0(B, 3, 8, 12), side_stream()
+    x0, stream = images(B, 3, 8, 12), side_stream()
     plan = _plan("ddpm", 6, 1, 0)
     got = _device(plan, 1, 0, es, ef, x0, stream, seed=3, noise="philox")
     r, plain = plan.rows, x0.clone()
@@ -376,12 +348,11 @@ def test_interval_one_equals_the_uncached_affine_loop():
 def test_cached_two_chains_equal_one_chain(order):
     B = 6
     es, ef = _pair(B)
-    x0, stream = _x0(B, 3, 8, 13), side_stream()
+    x0, stream = images(B, 3, 8, 13), side_stream()
     plan = _plan("ddpm", 9, 3, order)
     outs = {}
     for name, flags in (("chained", L.DD_DEV_FORCE_CHAINS), ("single", L.DD_DEV_NO_CHAINS)):
-        with _flags(es.ctx, flags):
-            outs[name] = (_device(plan, 1, order, es, ef, x0, stream, seed=23, noise="philox"), es.ctx.lib.dd_dev_last_sample_chains(es.ctx.handle))
+        outs[name] = (_device(plan, 1, order, es, ef, x0, stream, seed=23, noise="philox", flags=flags), es.ctx.lib.dd_dev_last_sample_chains(es.ctx.handle))
     assert outs["chained"][1] == 2 and outs["single"][1] == 1
     assert torch.isfinite(outs["single"][0]).all()
     assert torch.equal(outs["chained"][0], outs["single"][0]), "cached chains differ from the single chain"
@@ -394,23 +365,21 @@ def test_a_cut_cached_loop_equals_the_uncut_one(flags, order):
     """cut after steps 2 and 5, both reuse rows (N = 3; under order 1 step 5 extrapolates), and after steps 1 and 4: the caches carry over the calls"""
     B = 4
     es, ef = _pair(B)
-    x0, stream = _x0(B, 3, 8, 14), side_stream()
+    x0, stream = images(B, 3, 8, 14), side_stream()
     plan = _plan("ddpm", 9, 3, order, t_switch=7)
     assert list(plan.rows["cache"][:7]) == [0, 1, 1, 0, 2 if order else 1, 2 if order else 1, 0]
-    with _flags(es.ctx, flags):
-        whole = _device(plan, 1, order, es, ef, x0, stream, seed=25, noise="philox")
-        for cuts in ((2, 5), (1, 4)):      # behind reuse rows; and in front of them: rows 2 and 5 then open a call on an earlier call's cache
-            cut = _device(plan, 1, order, es, ef, x0, stream, cuts=cuts, seed=25, noise="philox")
-            assert torch.equal(cut, whole), f"cut after steps {cuts} differs from the uncut loop"
+    whole = _device(plan, 1, order, es, ef, x0, stream, seed=25, noise="philox", flags=flags)
+    for cuts in ((2, 5), (1, 4)):      # behind reuse rows; and in front of them: rows 2 and 5 then open a call on an earlier call's cache
+        cut = _device(plan, 1, order, es, ef, x0, stream, cuts=cuts, seed=25, noise="philox", flags=flags)
+        assert torch.equal(cut, whole), f"cut after steps {cuts} differs from the uncut loop"
     assert torch.isfinite(whole).all()
 
 
 @gpu
 def test_cached_loop_with_a_known_region_equals_manual_steps():
-    from loop_support import known_region
     B = 4
     es, ef = _pair(B)
-    x0, stream = _x0(B, 3, 8, 15), side_stream()
+    x0, stream = images(B, 3, 8, 15), side_stream()
     plan = _plan("ddpm", 9, 3, 1)
     g = torch.Generator().manual_seed(16)
     region = known_region(plan, torch.randn(B, 3, 8, 8, generator=g).cuda(), (torch.rand(B, 1, 8, 8, generator=g) > 0.5).float().cuda())
@@ -425,11 +394,10 @@ def test_cached_loop_with_a_known_region_equals_manual_steps():
 def test_cached_loop_with_cfg_equals_manual_guided_steps(flags):
     B, g = 4, (0.7, 10)
     es, ef = _pair(2 * B, cond=True)
-    x0, stream = _x0(B, 3, 8, 17), side_stream()
-    y = torch.randint(0, 10, (B,), generator=torch.Generator().manual_seed(18)).cuda()
+    x0, stream = images(B, 3, 8, 17), side_stream()
+    y = labels(B, 10, 18)
     plan = _plan("ddpm", 9, 3, 1)
-    with _flags(es.ctx, flags):
-        got = _device(plan, 1, 1, es, ef, x0, stream, seed=29, noise="philox", guidance=g, y=y)
+    got = _device(plan, 1, 1, es, ef, x0, stream, seed=29, noise="philox", guidance=g, y=y, flags=flags)
     manual = _manual(plan, 1, es, ef, x0, stream, seed=29, noise="philox", guidance=g, y=y)
     unguided = _device(plan, 1, 1, es, ef, x0, stream, seed=29, noise="philox", guidance=(0.0, 10), y=y)
     assert torch.isfinite(got).all() and torch.equal(got, manual) and not torch.equal(got, unguided)
@@ -440,7 +408,7 @@ def test_cached_loop_with_image_seeds_an_image_equals_its_own_run():
     B = 4
     es, ef = _pair(B)
     ctx, stream = es.ctx, side_stream()
-    x0 = _x0(B, 3, 8, 19)
+    x0 = images(B, 3, 8, 19)
     seeds = [101, 7, 55, 3]
     plan = _plan("ddpm", 9, 3, 1)
     with ctx.image_seeds(seeds, stream):
@@ -455,7 +423,7 @@ def test_cached_loop_with_image_seeds_an_image_equals_its_own_run():
 def test_a_new_cache_setting_is_not_a_stale_graph():
     """(K, N, order) changed one at a time on the same model, and back: each == a freshly built model"""
     B = 4
-    x0, stream = _x0(B, 3, 8, 31), side_stream()
+    x0, stream = images(B, 3, 8, 31), side_stream()
     settings = [(1, 3, 0), (2, 3, 0), (2, 2, 0), (2, 2, 1), (1, 3, 0)]
 
     def run(em, K, N, order):
@@ -483,18 +451,18 @@ def test_cached_loop_reads_no_stale_workspace_bytes(case):
     seam's skip_linear finds block K - 1's patch rows row-major"""
     cfg_s, cfg_f, B, S, n, K = (dict(TINY, depth=3), dict(TINY, depth=5), 6, 8, 7, 1) if case == "tiny" else \
         (dict(QA512, depth=5), dict(QA512, depth=5), 2, 64, 4, 2)
-    x0, stream = _x0(B, 3, S, 35), side_stream()
+    x0, stream = images(B, 3, S, 35), side_stream()
     plan = _plan("ddpm", n, 2, 1, t_switch=3, K=K)
     outs = []
     for poison in (False, True):
         es, ef, _ = engine_pair(cfg_s, cfg_f, (71, 72), B)
         ctx = es.ctx
-        with _flags(ctx, L.DD_DEV_FORCE_CHAINS):
-            if poison:
-                with torch.cuda.stream(stream):
-                    for e in (es, ef):
-                        ctx.check(ctx.lib.dd_dev_poison_workspaces(ctx.handle, e.handle, stream.cuda_stream))
-            outs.append((_device(plan, K, 1, es, ef, x0, stream, seed=37, noise="philox"), ctx.lib.dd_dev_last_sample_chains(ctx.handle)))
+        if poison:
+            with torch.cuda.stream(stream):
+                for e in (es, ef):
+                    ctx.check(ctx.lib.dd_dev_poison_workspaces(ctx.handle, e.handle, stream.cuda_stream))
+        outs.append((_device(plan, K, 1, es, ef, x0, stream, seed=37, noise="philox", flags=L.DD_DEV_FORCE_CHAINS),
+                     ctx.lib.dd_dev_last_sample_chains(ctx.handle)))
         del es, ef
     assert outs[0][1] == outs[1][1] == 2
     assert torch.isfinite(outs[0][0]).all() and not torch.equal(outs[0][0], x0)
@@ -510,7 +478,7 @@ def test_invalid_cached_calls_are_rejected_before_anything_is_enqueued():
     ctx, lib = es.ctx, es.ctx.lib
     ee = Model(ctx, ModelParams.from_dict(dict(TINY, depth=5)), B)
     ee.enable_early_exit("mlp_probe_per_layer")
-    x0, stream = _x0(B, 3, 8, 39), side_stream()
+    x0, stream = images(B, 3, 8, 39), side_stream()
     f = (C.c_float * n)(900.0, 600.0, 300.0)
     one = (C.c_float * n)(1.0, 1.0, 1.0)
     nz = (C.c_int32 * n)(0, 0, 0)

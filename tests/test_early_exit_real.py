@@ -12,6 +12,7 @@ from duodiff_amd.early_exit import real_exit_block_rows
 from duodiff_amd.weights import synthetic_ee_state_dict, synthetic_state_dict
 
 from conftest import GOLDEN, REPO, TINY
+from loop_support import dev_flags
 
 pytestmark = pytest.mark.gpu
 
@@ -39,18 +40,6 @@ def _first_cls(m, mp, B, y=None, seed=1):
     x = torch.randn(B, mp.in_chans, S, S, generator=torch.Generator().manual_seed(seed))
     _, cls, _ = m.forward_device(x, torch.full((B,), 999.0), y)
     return cls.cpu()
-
-
-class Flags:
-    """development flags for the block, cleared behind it"""
-    def __init__(self, ctx, flags):
-        self.ctx, self.flags = ctx, flags
-
-    def __enter__(self):
-        self.ctx.check(self.ctx.lib.dd_dev_set_flags(self.ctx.handle, self.flags))
-
-    def __exit__(self, *exc):
-        self.ctx.check(self.ctx.lib.dd_dev_set_flags(self.ctx.handle, 0))
 
 
 def _run(m, mp, B, thr, noise, steps, y=None, image_seeds=None, compact_every=1, stats=None, seed=5):
@@ -103,13 +92,13 @@ def test_real_exit_equals_the_simulated_loop_tiny(ctype, cfg, precision):
         cls0 = _first_cls(m, mp, B, y)
         thr = float(cls0.median())          # inside the spread of the predicted errors: the run takes more than one exit
         ctx = m.engine_model(B).ctx
-        with Flags(ctx, L.DD_DEV_NO_CHAINS):
+        with dev_flags(ctx, L.DD_DEV_NO_CHAINS):
             want = {n: _run(m, mp, B, thr, n, steps, y) for n in ("device_none", "device")}
             want["seeded"] = _run(m, mp, B, thr, "device", steps, y, image_seeds=list(range(40, 40 + B)))
         assert len(set(want["device_none"][1].flatten().tolist())) > 1, "the run should take more than one exit"
         assert not np.array_equal(want["device"][0], want["seeded"][0])
         for flags, chains in ((L.DD_DEV_NO_CHAINS, 1), (L.DD_DEV_FORCE_CHAINS, 2 if B % 2 == 0 else 1)):
-            with Flags(ctx, flags):
+            with dev_flags(ctx, flags):
                 for s in (1, 2, depth + 1):
                     for name, noise, seeds in (("device_none", "device_real_none", None), ("device", "device_real", None),
                                                ("seeded", "device_real", list(range(40, 40 + B)))):
@@ -137,7 +126,7 @@ def _check_case(m, mp, B, steps, picked, sweeps=((1, 0), (2, 0))):
     thr, want, w_ind = picked
     assert np.isfinite(want).all()
     for s, flags in sweeps:
-        with Flags(ctx, flags):
+        with dev_flags(ctx, flags):
             st = {}
             got, g_ind = _run(m, mp, B, thr, "device_real", steps, compact_every=s, stats=st)
         print(f"B {B} compact_every {s} flags {flags}: block-rows {st['block_rows']} of {st['block_rows_full']}, moves {st['moves']}")
@@ -221,7 +210,7 @@ def _skipping_setup():
         ctx = m.engine_model(B).ctx
         cls0 = np.sort(_first_cls(m, mp, B).numpy().ravel())
         for thr in ((cls0[:-1] + cls0[1:]) / 2)[2::3]:
-            with Flags(ctx, L.DD_DEV_NO_CHAINS):
+            with dev_flags(ctx, L.DD_DEV_NO_CHAINS):
                 want, w_ind = _run(m, mp, B, float(thr), "device", steps)
             per_step = [_moves_of_step(list(r), mp.depth, 1)[1] for r in w_ind.numpy().astype(int)]
             if len(set(w_ind.flatten().tolist())) > 1 and max(per_step) > 0 and min(per_step) == 0:
@@ -236,7 +225,7 @@ def test_real_exit_runs_fewer_block_rows():
     for s in (1, 2, depth + 1):
         for flags, halves in ((L.DD_DEV_NO_CHAINS, [(0, B)]), (L.DD_DEV_FORCE_CHAINS, [(0, B // 2), (B // 2, B)])):
             st = {}
-            with Flags(ctx, flags):
+            with dev_flags(ctx, flags):
                 got, g_ind = _run(m, mp, B, thr, "device_real", steps, compact_every=s, stats=st)
             assert np.array_equal(got, want) and torch.equal(g_ind, w_ind)
             rows, moves = _expected(w_ind, depth, s, halves)
@@ -305,7 +294,7 @@ def test_real_exit_reads_no_stale_slab(case_b):
                                                      (tm, tmp_, tB, tsteps, tthr, twant, tind, L.DD_DEV_FORCE_CHAINS)):
         em = m.engine_model(B)
         ctx = em.ctx
-        with Flags(ctx, flags):
+        with dev_flags(ctx, flags):
             st = {}
             ctx.check(ctx.lib.dd_dev_poison_workspaces(ctx.handle, em.handle, torch.cuda.current_stream().cuda_stream))
             got, g_ind = _run(m, mp, B, thr, "device_real", steps, stats=st)

@@ -17,8 +17,7 @@ import torch
 import kernel_support
 from duodiff_amd import _lib as L
 from kernel_support import P, bf16, bf16_bits, frag16_index, frag32_index, round_up, to_frag, unfrag
-from loop_support import side_stream, uvit
-from test_autoguidance import _flags, _run, _x0
+from loop_support import QA512, ddpm_rows, dev_flags, ee_uvit, images, run_loop, side_stream, uvit
 
 gpu = pytest.mark.gpu
 
@@ -214,15 +213,13 @@ def test_block_tail_refuses_fragment_hand_offs_it_has_no_path_for():
 
 
 # ---------------------------------------------------------------------------------------------------------------- the model
-QA512 = dict(img_size=64, patch_size=4, in_chans=3, embed_dim=512, depth=3, num_heads=8, mlp_ratio=4, qkv_bias=False,
-             mlp_time_embed=False, num_classes=-1, normalize_timesteps=True)
 STAGES = {"all_frag": 0, "no_ao": L.DD_DEV_NO_FRAG_AO, "no_skip": L.DD_DEV_NO_FRAG_SKIP, "no_x": L.DD_DEV_NO_FRAG_X, "row_major": ALL_OFF}
 
 
 def _model(flags, B):
     """an engine model finalized under `flags` (the hand-offs are a property of the model, chosen in dd_model_finalize)"""
     m, _ = uvit(QA512, 71, "bf16", max_batch=B)
-    with _flags(kernel_support.ctx(), flags):
+    with dev_flags(kernel_support.ctx(), flags):
         em = m.engine_model(B)
     return m, em
 
@@ -231,7 +228,7 @@ def _model(flags, B):
 def test_model_outputs_do_not_depend_on_the_form_of_the_hand_offs():
     B = 4
     ctx = kernel_support.ctx()
-    x = _x0(B, 3, 64, 5)
+    x = images(B, 3, 64, 5)
     outs = {}
     for name, flags in STAGES.items():
         m, em = _model(flags, B)
@@ -240,9 +237,8 @@ def test_model_outputs_do_not_depend_on_the_form_of_the_hand_offs():
         s = side_stream()
         loops = {}
         for chains, cf in (("two", L.DD_DEV_FORCE_CHAINS), ("one", L.DD_DEV_NO_CHAINS)):
-            with _flags(ctx, cf):
-                loops[chains] = _run("ddpm", ctx, em, None, x, s, switch=0, n=4)
-                assert ctx.lib.dd_dev_last_sample_chains(ctx.handle) == (2 if chains == "two" else 1)
+            loops[chains], _, count = run_loop("ddpm", em, x, ddpm_rows(4), s, flags=cf, seed=0)
+            assert count == (2 if chains == "two" else 1)
         torch.cuda.synchronize()
         assert torch.isfinite(fwd).all() and torch.isfinite(loops["one"]).all()
         assert torch.equal(loops["one"], loops["two"]), f"{name}: two half-batch chains differ from one chain"
@@ -262,7 +258,7 @@ def test_stale_workspace_bytes_do_not_reach_the_outputs():
     B = 4
     ctx = kernel_support.ctx()
     m, em = _model(0, B)
-    x = _x0(B, 3, 64, 6)
+    x = images(B, 3, 64, 6)
     first = em.forward(x, 100.0, None).clone()
     torch.cuda.synchronize()
     ctx.check(ctx.lib.dd_dev_poison_workspaces(ctx.handle, em.handle, None))
@@ -275,13 +271,12 @@ def test_stale_workspace_bytes_do_not_reach_the_outputs():
 @gpu
 def test_early_exit_model_keeps_the_residual_rows_row_major():
     """the early-exit heads read x every block, so such a model takes ao_frag and the skip hand-off only: the same bits as all row-major"""
-    from test_early_exit import _engine
     B = 2
     x = torch.randn(B, 3, 64, 64, generator=torch.Generator().manual_seed(9))
     got = {}
     for name, flags in (("frag", 0), ("row_major", ALL_OFF)):
-        with _flags(kernel_support.ctx(), flags):
-            m, mp = _engine(QA512, 73, "mlp_probe_per_layer", "bf16", max_batch=B)
+        with dev_flags(kernel_support.ctx(), flags):
+            m, mp = ee_uvit(QA512, 73, "mlp_probe_per_layer", "bf16", max_batch=B)
             eps, cls, outs = m(x, torch.full((B,), 300.0), None)
             got[name] = (eps.clone(), torch.stack(cls).clone(), torch.stack(outs).clone())
             torch.cuda.synchronize()

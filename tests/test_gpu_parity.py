@@ -18,7 +18,7 @@ import oracle
 from conftest import FULL_NAMES, REPO, TINY, tiny_cfg_from_fixture
 from duodiff_amd.config import ModelParams, load_config
 from duodiff_amd.weights import synthetic_state_dict
-from loop_support import eps_rms_bound, uvit
+from loop_support import dev_flags, eps_rms_bound, images, labels, side_stream, uvit
 
 pytestmark = pytest.mark.gpu
 
@@ -153,8 +153,8 @@ def test_switch_and_graph_replay_match_manual_steps():
     m_f, _ = uvit(cfg_f, 12, "bf16")
     B = 4
     es, ef = m_s.engine_model(B), m_f.engine_model(B)
-    x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(3)).cuda()
-    stream = torch.cuda.Stream()
+    x0 = images(B, 3, 8, 3)
+    stream = side_stream()
     outs = []
     with torch.cuda.stream(stream):
         for use_graph in (True, False):
@@ -185,11 +185,10 @@ def test_timing_split_follows_the_switch():
     m_b, _ = uvit(dict(TINY, depth=1), 12, "bf16", max_batch=B)
     ea, eb = m_a.engine_model(B), m_b.engine_model(B)
     ctx = ea.ctx
-    x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(3)).cuda()
+    x0 = images(B, 3, 8, 3)
     t = np.arange(999, 999 - n, -1, dtype=np.float32)
     tab = (t, np.ones(n, np.float32), np.full(n, -0.01, np.float32), np.full(n, 0.01, np.float32), np.ones(n, np.int32))
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
+    stream = side_stream()
     ddpm = lambda x, late, **kw: sample_loop(ctx, ea, late, x, t_start=999, t_end=1000 - n, seed=7, noise="philox", use_graph=True,
                                              stream=stream, **kw)
     cases = {"late runs 7 of 8 steps": lambda x: ddpm(x, eb, t_switch=1),
@@ -198,17 +197,13 @@ def test_timing_split_follows_the_switch():
              "affine, late runs 7 of 8 steps": lambda x: sample_affine_loop(ctx, ea, eb, x, *tab, switch_after=1, seed=7, noise="philox",
                                                                             use_graph=True, stream=stream)}
     timing = {}
-    try:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, L.DD_DEV_FORCE_CHAINS))
-        with torch.cuda.stream(stream):
-            for name, call in cases.items():
-                for _ in range(2):
-                    call(x0.clone())
-                    stream.synchronize()
-                assert ctx.lib.dd_dev_last_sample_chains(ctx.handle) == 2
-                timing[name] = ctx.last_sample_timing()
-    finally:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
+    with dev_flags(ctx, L.DD_DEV_FORCE_CHAINS), torch.cuda.stream(stream):
+        for name, call in cases.items():
+            for _ in range(2):
+                call(x0.clone())
+                stream.synchronize()
+            assert ctx.lib.dd_dev_last_sample_chains(ctx.handle) == 2
+            timing[name] = ctx.last_sample_timing()
     for name, (total, t_first, t_late) in timing.items():
         print(f"{name}: total {total:.4f} ms, first {t_first:.4f} ms, late {t_late:.4f} ms")
         assert total > 0 and abs(t_first + t_late - total) <= 1e-3 * total, name
@@ -242,23 +237,18 @@ def test_half_batch_chains_equal_the_single_chain(case):
     m_f, mp_f = uvit(cfg_f, 32, "bf16", max_batch=B)
     es, ef = m_s.engine_model(B), m_f.engine_model(B)
     ctx = es.ctx
-    x0 = torch.randn(B, C_, S, S, generator=torch.Generator().manual_seed(4)).cuda()
+    x0 = images(B, C_, S, 4)
     ncls = int(mp_f.num_classes)
-    y = torch.randint(0, ncls, (B,), generator=torch.Generator().manual_seed(5)).cuda() if ncls > 0 else None
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
+    y = labels(B, ncls, 5) if ncls > 0 else None
+    stream = side_stream()
     outs = {}
-    try:
-        with torch.cuda.stream(stream):
-            for name, flags in (("chained", force), ("single", L.DD_DEV_NO_CHAINS)):
-                ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
-                n0 = ctx.lib.dd_dev_graph_captures(ctx.handle)
-                x = x0.clone()
-                sample_loop(ctx, es, ef, x, t_switch=tsw, t_start=999, t_end=1000 - steps, y=y, seed=9, noise="philox", use_graph=True, stream=stream)
-                stream.synchronize()
-                outs[name] = (x.clone(), ctx.lib.dd_dev_graph_captures(ctx.handle) - n0)
-    finally:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
+    for name, flags in (("chained", force), ("single", L.DD_DEV_NO_CHAINS)):
+        with dev_flags(ctx, flags), torch.cuda.stream(stream):
+            n0 = ctx.lib.dd_dev_graph_captures(ctx.handle)
+            x = x0.clone()
+            sample_loop(ctx, es, ef, x, t_switch=tsw, t_start=999, t_end=1000 - steps, y=y, seed=9, noise="philox", use_graph=True, stream=stream)
+            stream.synchronize()
+            outs[name] = (x.clone(), ctx.lib.dd_dev_graph_captures(ctx.handle) - n0)
     assert outs["chained"][1] == 4 and outs["single"][1] == 2, f"graph captures: {outs['chained'][1]} chained, {outs['single'][1]} single"
     assert torch.isfinite(outs["single"][0]).all() and not torch.equal(outs["single"][0], x0)
     assert torch.equal(outs["chained"][0], outs["single"][0]), "two half-batch chains differ from the single chain"
@@ -288,9 +278,8 @@ def test_no_kernel_depends_on_stale_workspace_bytes(case):
         cfg_s, cfg_f = dict(TINY, depth=1, num_classes=nc), dict(TINY, depth=3, num_classes=nc)
         if case == "tiny_fp32_single":
             prec, flags = "fp32", L.DD_DEV_NO_CHAINS
-    x0 = torch.randn(B, C_, S, S, generator=torch.Generator().manual_seed(14)).cuda()
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
+    x0 = images(B, C_, S, 14)
+    stream = side_stream()
     outs = []
     for poison in (False, True):
         m_s, _ = uvit(cfg_s, 131, prec, max_batch=B)
@@ -298,19 +287,15 @@ def test_no_kernel_depends_on_stale_workspace_bytes(case):
         es, ef = m_s.engine_model(B), m_f.engine_model(B)
         ctx = es.ctx
         ncls = int(mp_f.num_classes)
-        y = torch.randint(0, ncls, (B,), generator=torch.Generator().manual_seed(15)).cuda() if ncls > 0 else None
-        try:
-            ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
-            with torch.cuda.stream(stream):
-                if poison:
-                    for e in (es, ef):
-                        ctx.check(ctx.lib.dd_dev_poison_workspaces(ctx.handle, e.handle, stream.cuda_stream))
-                x = x0.clone()
-                sample_loop(ctx, es, ef, x, t_switch=tsw, t_start=999, t_end=1000 - steps, y=y, seed=19, noise="philox", use_graph=True, stream=stream)
-                stream.synchronize()
+        y = labels(B, ncls, 15) if ncls > 0 else None
+        with dev_flags(ctx, flags), torch.cuda.stream(stream):
+            if poison:
+                for e in (es, ef):
+                    ctx.check(ctx.lib.dd_dev_poison_workspaces(ctx.handle, e.handle, stream.cuda_stream))
+            x = x0.clone()
+            sample_loop(ctx, es, ef, x, t_switch=tsw, t_start=999, t_end=1000 - steps, y=y, seed=19, noise="philox", use_graph=True, stream=stream)
+            stream.synchronize()
             outs.append((x.clone(), ctx.lib.dd_dev_last_sample_chains(ctx.handle)))
-        finally:
-            ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
         del es, ef, m_s, m_f
     assert outs[0][1] == outs[1][1] == (1 if flags == L.DD_DEV_NO_CHAINS else 2)
     assert torch.isfinite(outs[0][0]).all() and not torch.equal(outs[0][0], x0)
@@ -324,9 +309,8 @@ def test_profile_steps_chained_counts_and_grid():
     cfg = load_config(REPO / "configs" / "uvit_celeba_3.yaml")
     m, mp = uvit(cfg, 7, "bf16", max_batch=64)
     em = m.engine_model(64)
-    x = torch.randn(64, 3, 64, 64, generator=torch.Generator().manual_seed(3)).cuda()
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
+    x = images(64, 3, 64, 3)
+    stream = side_stream()
     with torch.cuda.stream(stream):
         ms1, n1 = em.profile_steps(x.clone(), t_start=699, steps=3, stream=stream)
         ms2, n2 = em.profile_steps_chained(x.clone(), t_start=699, steps=3, stream=stream)
@@ -347,20 +331,17 @@ def test_half_batch_chains_in_the_table_driven_loops():
     ctx = m_s.engine_model(6).ctx
     run = lambda **kw: sampler.get_samples(m_s, 6, kw.pop("post", sampler.predict_noise_postprocessing), 5, 3, 8, 8,
                                            late_model=m_f, noise="device", **kw)
-    try:
-        for kw in (dict(use_ddim=True, ddim_steps=30, ddim_eta=0.05, t_switch=400),
-                   dict(post=sampler.predict_original_postprocessing, num_steps=40, t_switch=980),
-                   dict(post=sampler.predict_previous_postprocessing, num_steps=30, t_switch=985, timesteps_save=[4, 20])):
-            outs = []
-            for flags in (L.DD_DEV_FORCE_CHAINS, L.DD_DEV_NO_CHAINS):
-                ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
+    for kw in (dict(use_ddim=True, ddim_steps=30, ddim_eta=0.05, t_switch=400),
+               dict(post=sampler.predict_original_postprocessing, num_steps=40, t_switch=980),
+               dict(post=sampler.predict_previous_postprocessing, num_steps=30, t_switch=985, timesteps_save=[4, 20])):
+        outs = []
+        for flags in (L.DD_DEV_FORCE_CHAINS, L.DD_DEV_NO_CHAINS):
+            with dev_flags(ctx, flags):
                 g, gi = run(**dict(kw))
                 outs.append((g, gi, ctx.lib.dd_dev_last_sample_chains(ctx.handle)))
-            assert outs[0][2] == 2 and outs[1][2] == 1
-            assert np.isfinite(outs[1][0]).all() and np.array_equal(outs[0][0], outs[1][0]), f"{kw}: chained loop differs"
-            assert len(outs[0][1]) == len(outs[1][1]) and all(np.array_equal(a, b) for a, b in zip(outs[0][1], outs[1][1]))
-    finally:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
+        assert outs[0][2] == 2 and outs[1][2] == 1
+        assert np.isfinite(outs[1][0]).all() and np.array_equal(outs[0][0], outs[1][0]), f"{kw}: chained loop differs"
+        assert len(outs[0][1]) == len(outs[1][1]) and all(np.array_equal(a, b) for a, b in zip(outs[0][1], outs[1][1]))
 
 
 def test_graphs_are_not_recaptured_for_new_tensors():
@@ -373,7 +354,7 @@ def test_graphs_are_not_recaptured_for_new_tensors():
     B = 3
     es, ef = m_s.engine_model(B), m_f.engine_model(B)
     lib, h = es.ctx.lib, es.ctx.handle
-    stream = torch.cuda.Stream()
+    stream = side_stream()
     g = torch.Generator().manual_seed(9)
     xa, xb = torch.randn(B, 3, 8, 8, generator=g).cuda(), torch.randn(B, 3, 8, 8, generator=g).cuda()
     with torch.cuda.stream(stream):
@@ -396,7 +377,7 @@ def test_philox_noise_is_standard_normal():
     m, mp = uvit(dict(TINY), 21, "bf16")
     B = 64
     em = m.engine_model(B)
-    x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(1)).cuda()
+    x0 = images(B, 3, 8, 1)
     sig = oracle.schedule_oracle.step_coefficients(oracle.sampler_schedule(), 500)[2]
     zs = []
     for t, seed in ((500, 1), (500, 2), (499, 1)):
@@ -417,7 +398,7 @@ def test_batch_independence_at_full_size():
     equals the same image run at B=2, bit for bit.  Also exercises the BASELINE batch size."""
     cfg = load_config(REPO / "configs" / "uvit_celeba_3.yaml")
     m, mp = uvit(cfg, 1237, "bf16", max_batch=128)
-    x = torch.randn(128, 3, 64, 64, generator=torch.Generator().manual_seed(8)).cuda()
+    x = images(128, 3, 64, 8)
     t = torch.full((128,), 640.0)
     eps_big = m(x, t)
     eps_small = m(x[:2].contiguous(), t[:2])
@@ -430,7 +411,7 @@ def test_batch_independence_at_full_size():
 def test_full_size_bf16_close_to_fp32_at_batch_128():
     cfg = load_config(REPO / "configs" / "uvit_celeba.yaml")
     mb, _ = uvit(cfg, 1236, "bf16", max_batch=128)
-    x = torch.randn(128, 3, 64, 64, generator=torch.Generator().manual_seed(9)).cuda()
+    x = images(128, 3, 64, 9)
     t = torch.full((128,), 123.0)
     eb = mb(x, t)
     del mb
@@ -490,7 +471,7 @@ def test_benchmarked_path_drift_bf16_vs_fp32(K):
     from duodiff_amd.engine import sample_loop
     B = 128
     cfg_s, cfg_f = load_config(REPO / "configs" / "uvit_celeba_3.yaml"), load_config(REPO / "configs" / "uvit_celeba.yaml")
-    x_T = torch.randn(B, 3, 64, 64, generator=torch.Generator().manual_seed(77)).cuda().contiguous()
+    x_T = images(B, 3, 64, 77).contiguous()
     k_switch = max(1, round(0.3 * K))
     out = {}
     for prec in ("bf16", "fp32"):
@@ -498,8 +479,7 @@ def test_benchmarked_path_drift_bf16_vs_fp32(K):
         mf, _ = uvit(cfg_f, 1236, prec, max_batch=B)
         es, ef = ms.engine_model(B), mf.engine_model(B)
         x = x_T.clone()
-        stream = torch.cuda.Stream()
-        stream.wait_stream(torch.cuda.current_stream())
+        stream = side_stream()
         with torch.cuda.stream(stream):
             sample_loop(es.ctx, es, ef, x, t_switch=k_switch, t_start=999, t_end=1000 - K, seed=5, noise="philox",
                         use_graph=True, stream=stream)
@@ -670,13 +650,10 @@ def test_kernel_variant_flags_agree_with_the_default_path(flags):
     want = _oracle(cfg, 4243)(x.numpy(), t.numpy(), y.numpy())
     sigma = float(want.std())
     ctx = Context.get()
-    try:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
+    with dev_flags(ctx, flags):
         m, _ = uvit(cfg, 4243, "bf16", max_batch=B)
         got = m(x, t, y).cpu().numpy()
         del m
-    finally:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
     err, rms = float(np.abs(got - want).max()), float(np.sqrt(((got - want).astype(np.float64) ** 2).mean()))
     print(f"dev_flags {flags}: vs oracle max {err:.3e} rms {rms:.3e} (sigma {sigma:.3f})")
     assert np.isfinite(got).all() and err <= 6e-2 * sigma and rms <= 1.4e-2 * sigma
@@ -699,14 +676,11 @@ def test_row_resident_fc2_at_embed_dim_768(img, B, flags, ncls):
     want = _oracle(cfg, 4244)(x.numpy(), t.numpy(), y.numpy() if y is not None else None)
     sigma = float(want.std())
     ctx = Context.get()
-    try:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
+    with dev_flags(ctx, flags):
         m, _ = uvit(cfg, 4244, "bf16", max_batch=B)
         got = m(x, t, y).cpu().numpy()
         alone = m(x[B - 1:].contiguous(), t[:1], y[B - 1:].contiguous() if y is not None else None).cpu().numpy()
         del m
-    finally:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
     err, rms = float(np.abs(got - want).max()), float(np.sqrt(((got - want).astype(np.float64) ** 2).mean()))
     print(f"D=768 img {img} B={B} classes {ncls} dev_flags {flags}: vs oracle max {err:.3e} rms {rms:.3e} (sigma {sigma:.3f})")
     assert np.isfinite(got).all() and err <= 6e-2 * sigma and rms <= 1.4e-2 * sigma
@@ -730,14 +704,11 @@ def test_split_k_linears_at_embed_dim_1024(img, B, flags, ncls):
     want = _oracle(cfg, 4245)(x.numpy(), t.numpy(), y.numpy() if y is not None else None)
     sigma = float(want.std())
     ctx = Context.get()
-    try:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
+    with dev_flags(ctx, flags):
         m, _ = uvit(cfg, 4245, "bf16", max_batch=B)
         got = m(x, t, y).cpu().numpy()
         alone = m(x[B - 1:].contiguous(), t[:1], y[B - 1:].contiguous() if y is not None else None).cpu().numpy()
         del m
-    finally:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
     err, rms = float(np.abs(got - want).max()), float(np.sqrt(((got - want).astype(np.float64) ** 2).mean()))
     print(f"D=1024 img {img} B={B} classes {ncls} dev_flags {flags}: vs oracle max {err:.3e} rms {rms:.3e} (sigma {sigma:.3f})")
     assert np.isfinite(got).all() and err <= 6e-2 * sigma and rms <= 1.4e-2 * sigma

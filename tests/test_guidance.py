@@ -14,9 +14,10 @@ import torch
 
 from conftest import REPO, TINY
 from duodiff_amd import _lib as L
-from duodiff_amd.config import ModelParams, load_config
+from duodiff_amd.config import ModelParams
 from duodiff_amd.weights import synthetic_state_dict
-from loop_support import cli_argv, engine_pair, eps_rms_bound, uvit
+from loop_support import NULL, TINY_COND, cli_argv, ddpm_rows, engine_pair, eps_rms_bound, imagenet256_pair, images, labels, run_loop
+from loop_support import run_steps, side_stream, uvit
 
 gpu = pytest.mark.gpu
 
@@ -81,20 +82,8 @@ def test_lib_binds_the_guided_entry_points():
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
-NULL = 10
-TINY_COND = dict(TINY, num_classes=11)     # 10 classes + the null row
-
-
 def _tiny_pair(seeds=(41, 42), max_batch=12, precision="bf16"):
     return engine_pair(dict(TINY_COND, depth=1), dict(TINY_COND, depth=3), seeds, max_batch, precision)
-
-
-def _imagenet256_pair(max_batch=64):
-    return engine_pair(load_config(IMAGENET256_3), load_config(IMAGENET256), (51, 52), max_batch)
-
-
-def _labels(B, ncls, seed):
-    return torch.randint(0, ncls, (B,), generator=torch.Generator().manual_seed(seed)).cuda()
 
 
 @gpu
@@ -138,30 +127,16 @@ def test_forward_guided_vs_oracle(case):
 @pytest.mark.parametrize("case", ["tiny_forced", "imagenet256_default"])
 def test_scale_zero_equals_the_unguided_loop(case):
     """dd_sample_guided with scale 0 and Philox noise == dd_sample with the same labels, bit for bit, backbone switch included."""
-    from duodiff_amd.engine import sample_loop
     if case == "tiny_forced":
         B, S, Cc, steps, tsw, flags = 6, 8, 3, 10, 4, L.DD_DEV_FORCE_CHAINS
         es, ef, mp = _tiny_pair(max_batch=2 * B)
     else:
         B, S, Cc, steps, tsw, flags = 32, 32, 4, 3, 1, 0
-        es, ef, mp = _imagenet256_pair(max_batch=2 * B)
-    ctx = es.ctx
-    x0 = torch.randn(B, Cc, S, S, generator=torch.Generator().manual_seed(7)).cuda()
-    y = _labels(B, 10, 8)
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
+        es, ef, mp = imagenet256_pair(2 * B, (51, 52))
+    x0, y, stream = images(B, Cc, S, 7), labels(B, 10, 8), side_stream()
     outs = {}
-    try:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
-        with torch.cuda.stream(stream):
-            for name, guidance in (("unguided", None), ("scale0", (0.0, NULL if case == "tiny_forced" else 1000))):
-                x = x0.clone()
-                sample_loop(ctx, es, ef, x, t_switch=tsw, t_start=999, t_end=1000 - steps, y=y, seed=21, noise="philox",
-                            stream=stream, guidance=guidance)
-                stream.synchronize()
-                outs[name] = (x, ctx.lib.dd_dev_last_sample_chains(ctx.handle))
-    finally:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
+    for name, guidance in (("unguided", None), ("scale0", (0.0, NULL if case == "tiny_forced" else 1000))):
+        outs[name] = run_loop("ddpm", es, x0, ddpm_rows(steps), stream, late=ef, t_switch=tsw, y=y, seed=21, flags=flags, guidance=guidance)[::2]
     assert outs["unguided"][1] == outs["scale0"][1] == 2
     assert torch.isfinite(outs["scale0"][0]).all() and not torch.equal(outs["scale0"][0], x0)
     assert torch.equal(outs["scale0"][0], outs["unguided"][0]), "scale 0 differs from the unguided loop"
@@ -172,76 +147,43 @@ def test_guided_loops_equal_manual_steps():
     """Scale 0.4, no noise: dd_sample_guided (graph replay and eager) == forward_guided + ddpm_step per step, and
     dd_sample_affine_guided (DDIM-10) == forward_guided + affine_step per step, bit for bit, backbone switch inside."""
     from duodiff_amd import sampler
-    from duodiff_amd.engine import sample_affine_loop, sample_loop
     B, s = 4, 0.4
     es, ef, _ = _tiny_pair(max_batch=2 * B)
-    ctx = es.ctx
-    x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(9)).cuda()
-    y = _labels(B, 10, 10)
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(stream):
-        loops = []
-        for use_graph in (True, False):
-            x = x0.clone()
-            sample_loop(ctx, es, ef, x, t_switch=5, t_start=999, t_end=988, y=y, noise="none", use_graph=use_graph, stream=stream,
-                        guidance=(s, NULL))
-            stream.synchronize()
-            loops.append(x)
-        xm, eps = x0.clone(), torch.empty_like(x0)
-        for t in range(999, 987, -1):
-            (es if t >= 995 else ef).forward_guided(xm, t, y, s, NULL, out=eps, stream=stream)
-            ctx.ddpm_step(xm, eps, None, t, out=xm, stream=stream)
-        stream.synchronize()
-        assert torch.equal(loops[0], loops[1]), "graph replay differs from eager launches"
-        assert torch.equal(loops[0], xm), "guided DDPM loop differs from forward_guided + ddpm_step"
-        assert torch.isfinite(xm).all()
+    x0, y, stream = images(B, 3, 8, 9), labels(B, 10, 10), side_stream()
+    kw = dict(late=ef, noise="none", guidance=(s, NULL), y=y)
+    rows = ddpm_rows(12)
+    loops = [run_loop("ddpm", es, x0, rows, stream, t_switch=5, use_graph=use_graph, **kw)[0] for use_graph in (True, False)]
+    xm, _ = run_steps("ddpm", es, x0, rows, stream, switch_after=5, **kw)
+    assert torch.equal(loops[0], loops[1]), "graph replay differs from eager launches"
+    assert torch.equal(loops[0], xm), "guided DDPM loop differs from forward_guided + ddpm_step"
+    assert torch.isfinite(xm).all()
 
-        ts = np.linspace(0, 999, 11).astype(int)[::-1]
-        pairs = [(int(a), int(b)) for a, b in zip(ts[:-1], ts[1:])]
-        coefs = [sampler.affine_coefficients("ddim", t, t2, 0.0) for t, t2 in pairs]
-        for use_graph in (True, False):
-            xa = x0.clone()
-            sample_affine_loop(ctx, es, ef, xa, [float(t) for t, _ in pairs], [c[0] for c in coefs], [c[1] for c in coefs],
-                               [c[2] for c in coefs], [int(t2 > 0) for _, t2 in pairs], switch_after=4, y=y, noise="none",
-                               use_graph=use_graph, stream=stream, guidance=(s, NULL))
-            xm = x0.clone()
-            for k, ((t, _), (a, b, _c)) in enumerate(zip(pairs, coefs)):
-                (es if k < 4 else ef).forward_guided(xm, float(t), y, s, NULL, out=eps, stream=stream)
-                ctx.affine_step(xm, eps, None, a, b, 0.0, out=xm, stream=stream)
-            stream.synchronize()
-            assert torch.isfinite(xa).all() and not torch.equal(xa, x0)
-            assert torch.equal(xa, xm), f"guided DDIM loop (graph={use_graph}) differs from forward_guided + affine_step"
+    ts = np.linspace(0, 999, 11).astype(int)[::-1]
+    pairs = [(int(a), int(b)) for a, b in zip(ts[:-1], ts[1:])]
+    coefs = [sampler.affine_coefficients("ddim", t, t2, 0.0) for t, t2 in pairs]
+    rows = dict(t=[float(t) for t, _ in pairs], a=[c[0] for c in coefs], b=[c[1] for c in coefs], c=[c[2] for c in coefs],
+                noise=[int(t2 > 0) for _, t2 in pairs])
+    xm, _ = run_steps("affine", es, x0, rows, stream, switch_after=4, **kw)
+    for use_graph in (True, False):
+        xa = run_loop("affine", es, x0, rows, stream, switch_after=4, use_graph=use_graph, **kw)[0]
+        assert torch.isfinite(xa).all() and not torch.equal(xa, x0)
+        assert torch.equal(xa, xm), f"guided DDIM loop (graph={use_graph}) differs from forward_guided + affine_step"
 
 
 @gpu
 @pytest.mark.parametrize("case", ["tiny_forced", "imagenet256_default"])
 def test_guided_two_chains_equal_one_chain(case):
     """Guided loop, scale 0.4, Philox noise, switch inside: the two image-split chains == DD_DEV_NO_CHAINS bit for bit."""
-    from duodiff_amd.engine import sample_loop
     if case == "tiny_forced":
         B, S, Cc, steps, tsw, force, null = 6, 8, 3, 10, 4, L.DD_DEV_FORCE_CHAINS, NULL
         es, ef, _ = _tiny_pair(max_batch=2 * B)
     else:
         B, S, Cc, steps, tsw, force, null = 32, 32, 4, 3, 1, 0, 1000
-        es, ef, _ = _imagenet256_pair(max_batch=2 * B)
-    ctx = es.ctx
-    x0 = torch.randn(B, Cc, S, S, generator=torch.Generator().manual_seed(11)).cuda()
-    y = _labels(B, 10, 12)
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
+        es, ef, _ = imagenet256_pair(2 * B, (51, 52))
+    x0, y, stream = images(B, Cc, S, 11), labels(B, 10, 12), side_stream()
     outs = {}
-    try:
-        with torch.cuda.stream(stream):
-            for name, flags in (("chained", force), ("single", L.DD_DEV_NO_CHAINS)):
-                ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
-                x = x0.clone()
-                sample_loop(ctx, es, ef, x, t_switch=tsw, t_start=999, t_end=1000 - steps, y=y, seed=23, noise="philox",
-                            stream=stream, guidance=(0.4, null))
-                stream.synchronize()
-                outs[name] = (x, ctx.lib.dd_dev_last_sample_chains(ctx.handle))
-    finally:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
+    for name, flags in (("chained", force), ("single", L.DD_DEV_NO_CHAINS)):
+        outs[name] = run_loop("ddpm", es, x0, ddpm_rows(steps), stream, late=ef, t_switch=tsw, y=y, seed=23, flags=flags, guidance=(0.4, null))[::2]
     assert outs["chained"][1] == 2 and outs["single"][1] == 1
     assert torch.isfinite(outs["single"][0]).all() and not torch.equal(outs["single"][0], x0)
     assert torch.equal(outs["chained"][0], outs["single"][0]), "guided chains differ from the single chain"
@@ -250,20 +192,11 @@ def test_guided_two_chains_equal_one_chain(case):
 @gpu
 def test_a_new_scale_is_not_a_stale_graph():
     """Guided calls at 0.4, 1.0, 0.4 on the same models: each equals a run of freshly built models at that scale."""
-    from duodiff_amd.engine import sample_loop
     B = 4
-    x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(13)).cuda()
-    y = _labels(B, 10, 14)
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
+    x0, y, stream = images(B, 3, 8, 13), labels(B, 10, 14), side_stream()
 
     def run(es, ef, scale):
-        x = x0.clone()
-        with torch.cuda.stream(stream):
-            sample_loop(es.ctx, es, ef, x, t_switch=3, t_start=999, t_end=992, y=y, seed=25, noise="philox", stream=stream,
-                        guidance=(scale, NULL))
-        stream.synchronize()
-        return x
+        return run_loop("ddpm", es, x0, ddpm_rows(8), stream, late=ef, t_switch=3, y=y, seed=25, guidance=(scale, NULL))[0]
 
     es, ef, _ = _tiny_pair(max_batch=2 * B)
     got = [run(es, ef, s) for s in (0.4, 1.0, 0.4)]
@@ -280,29 +213,18 @@ def test_a_new_scale_is_not_a_stale_graph():
 @gpu
 def test_guided_loop_reads_no_stale_workspace_bytes():
     """One guided tiny case with both chains' workspaces poisoned (NaN bytes) before the call == the same case on fresh models."""
-    from duodiff_amd.engine import sample_loop
     B = 6
-    x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(15)).cuda()
-    y = _labels(B, 10, 16)
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
+    x0, y, stream = images(B, 3, 8, 15), labels(B, 10, 16), side_stream()
     outs = []
     for poison in (False, True):
         es, ef, _ = _tiny_pair(seeds=(71, 72), max_batch=2 * B)
         ctx = es.ctx
-        try:
-            ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, L.DD_DEV_FORCE_CHAINS))
+        if poison:
             with torch.cuda.stream(stream):
-                if poison:
-                    for e in (es, ef):
-                        ctx.check(ctx.lib.dd_dev_poison_workspaces(ctx.handle, e.handle, stream.cuda_stream))
-                x = x0.clone()
-                sample_loop(ctx, es, ef, x, t_switch=3, t_start=999, t_end=992, y=y, seed=27, noise="philox", stream=stream,
-                            guidance=(0.4, NULL))
-                stream.synchronize()
-            outs.append((x, ctx.lib.dd_dev_last_sample_chains(ctx.handle)))
-        finally:
-            ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
+                for e in (es, ef):
+                    ctx.check(ctx.lib.dd_dev_poison_workspaces(ctx.handle, e.handle, stream.cuda_stream))
+        outs.append(run_loop("ddpm", es, x0, ddpm_rows(8), stream, late=ef, t_switch=3, y=y, seed=27, flags=L.DD_DEV_FORCE_CHAINS,
+                             guidance=(0.4, NULL))[::2])
         del es, ef
     assert outs[0][1] == outs[1][1] == 2
     assert torch.isfinite(outs[0][0]).all() and not torch.equal(outs[0][0], x0)
@@ -325,10 +247,9 @@ def test_invalid_guided_calls_are_rejected_before_anything_is_enqueued():
     eu = unc.engine_model(2 * B)
     ee = Model(ctx, ModelParams.from_dict(TINY_COND), 2 * B)
     ee.enable_early_exit("mlp_probe_per_layer")
-    x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(17)).cuda()
-    y = _labels(B, 10, 18)
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
+    x0 = images(B, 3, 8, 17)
+    y = labels(B, 10, 18)
+    stream = side_stream()
     cases = [(es, None, (0.4, 11), "null_label"), (es, None, (0.4, -1), "null_label"), (es, el10, (0.4, NULL), "null_label"),
              (eu, None, (0.4, 0), "class-conditional"), (es_small, None, (0.4, NULL), "max_batch"), (ee, None, (0.4, NULL), "early-exit"),
              (es, None, (float("inf"), NULL), "finite")]

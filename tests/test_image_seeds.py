@@ -14,6 +14,7 @@ loop tests compare row i of a seeded batch with the PLAIN call on image i alone,
   sampler        get_samples(image_seeds=) of 4 == two calls of 2; the command lines (--image_seeds --first_image; two ranks over gloo).
 """
 import contextlib
+import functools
 import os
 import socket
 import subprocess
@@ -30,7 +31,7 @@ from duodiff_amd import _lib as L
 from duodiff_amd.config import ModelParams
 from duodiff_amd.weights import synthetic_state_dict
 from kernel_support import F32
-from loop_support import known_region, side_stream, uvit
+from loop_support import NULL, TINY_COND, ddpm_rows, dev_flags, ee_uvit, images, known_region, run_loop, side_stream, uvit
 
 pytestmark = pytest.mark.gpu
 
@@ -213,8 +214,7 @@ def test_context_noise_images_wrapper():
 
 
 # ---------------------------------------------------------------------------------------------------------------- the loops
-B6, NULL = 6, 10
-CFG = dict(TINY, num_classes=NULL + 1)
+B6, CFG = 6, TINY_COND
 KINDS = ["ddpm_switch", "affine_eta", "multistep_sde", "threshold", "region", "guided", "autoguided", "perturbed", "early_exit"]
 
 
@@ -225,16 +225,10 @@ class Models:
 @pytest.fixture(scope="module")
 def M():
     """one set of models for every loop test (max_batch 12: the 2 B backbone rows of either row-doubling guidance at B = 6)"""
-    from duodiff_amd.early_exit import EarlyExitUViT
-    from duodiff_amd.uvit import UViT
-    from duodiff_amd.weights import synthetic_ee_state_dict
     m = Models()
     m.first = uvit(dict(CFG, depth=1), 31, "bf16", 12)[0].engine_model(12)
     m.late = uvit(dict(CFG, depth=3), 32, "bf16", 12)[0].engine_model(12)
-    mp = ModelParams.from_dict(dict(CFG))
-    ee = EarlyExitUViT(UViT(**mp.as_dict(), precision="bf16", max_batch=12), "mlp_probe_per_layer")
-    ee.load_state_dict(synthetic_ee_state_dict(mp, 33, "mlp_probe_per_layer"))
-    m.ee_module = ee.eval().to("cuda")
+    m.ee_module = ee_uvit(dict(CFG), 33, "mlp_probe_per_layer", "bf16", 12)[0]
     m.ee = m.ee_module.engine_model(12)
     g = torch.Generator().manual_seed(77)
     m.x = torch.randn(B6, 3, 8, 8, generator=g).cuda()
@@ -252,6 +246,7 @@ def M():
     return m
 
 
+@functools.lru_cache(maxsize=None)
 def plans():
     from duodiff_amd import sampler
     from duodiff_amd.engine import X0Threshold
@@ -263,58 +258,37 @@ def plans():
         region=sampler.step_plan("predict_noise", strength=5 / 999))
 
 
-PLANS = plans()
-
-
 def run(kind, M, idx, *, seeds=None, seed=0, noise="philox", flags=0, use_graph=True, cut=None):
     """loop `kind` on the images idx of the module's batch (x, y, known image and mask), seeded (seeds: one per image of idx) or plain under
     `seed`; cut: the loop in two calls, the second from step `cut` on (counter base / timestep and h carried) -> x"""
     from duodiff_amd import engine
     ctx, st = M.late.ctx, M.stream
     idx = list(idx)
-    x, y = M.x[idx].clone(), M.y[idx].clone()
-    h = torch.zeros_like(x)
-    kw = dict(y=y, seed=seed, noise=noise, use_graph=use_graph, stream=st)
-    n = {"ddpm_switch": 10, "early_exit": 10, "guided": 6, "perturbed": 6, "region": 6}.get(kind, 6)
-    bounds = [0, n] if cut is None else [0, cut, n]
-
-    def segment(k0, k1):
-        ddpm = dict(t_start=n - 1 - k0, t_end=n - k1)
-        if kind == "ddpm_switch":                                            # the late model takes over behind t = 5
-            engine.sample_loop(ctx, M.first, M.late, x, t_switch=995, **ddpm, **kw)
-        elif kind == "guided":
-            engine.sample_loop(ctx, M.late, None, x, guidance=(0.4, NULL), **ddpm, **kw)
-        elif kind == "perturbed":
-            engine.sample_loop(ctx, M.late, None, x, guidance=engine.Perturbed(0.5, [1]), **ddpm, **kw)
-        elif kind == "region":
-            reg = known_region(PLANS["region"], M.x0[idx].clone(), M.mask[idx].clone(), k0, k1)
-            assert k0 or (reg.kb != 0).any(), "the region's rows must draw z2"
-            engine.sample_region_loop(ctx, M.late, None, x, reg, **ddpm, **kw)
-        elif kind == "early_exit":
-            engine.sample_early_exit_loop(ctx, M.ee, x, M.ee_thr, **ddpm, **kw)
-        elif kind in ("affine_eta", "autoguided"):
-            seg = {k: v[k0:k1] for k, v in PLANS["affine"].rows.items()}
-            assert k0 or seg["noise"].any()
-            g = engine.Autoguidance(M.first, 0.7) if kind == "autoguided" else None
-            engine.sample_affine_loop(ctx, M.late, None, x, seg["t"], seg["a"], seg["b"], seg["c"], seg["noise"], counter_base=k0, guidance=g, **kw)
-        elif kind == "multistep_sde":
-            seg = {k: v[k0:k1] for k, v in PLANS["multistep"].rows.items()}
-            assert k0 or seg["noise"].any()
-            engine.sample_multistep_loop(ctx, M.late, None, x, h, seg, counter_base=k0, **kw)
-        else:
-            plan, thr = PLANS["threshold"]
-            seg = {k: v[k0:k1] for k, v in plan.rows.items()}
-            engine.sample_multistep_threshold_loop(ctx, M.late, None, x, h, seg, thr, counter_base=k0, **kw)
-
-    try:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
-        with torch.cuda.stream(st), ctx.image_seeds(seeds, st):
-            for k0, k1 in zip(bounds[:-1], bounds[1:]):
-                segment(k0, k1)
-        st.synchronize()
-        chains = ctx.lib.dd_dev_last_sample_chains(ctx.handle)
-    finally:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
+    x_in, y = M.x[idx], M.y[idx].clone()
+    kw = dict(y=y, seed=seed, noise=noise, use_graph=use_graph, flags=flags, image_seeds=seeds, cuts=() if cut is None else (cut,))
+    if kind == "early_exit":                                                 # the one entry run_loop does not drive
+        x, n = x_in.clone(), 10
+        with dev_flags(ctx, flags), torch.cuda.stream(st), ctx.image_seeds(seeds, st):
+            for k0, k1 in zip([0, *kw["cuts"]], [*kw["cuts"], n]):
+                engine.sample_early_exit_loop(ctx, M.ee, x, M.ee_thr, t_start=n - 1 - k0, t_end=n - k1, y=y, seed=seed, noise=noise,
+                                              use_graph=use_graph, stream=st)
+            st.synchronize()
+            chains = ctx.lib.dd_dev_last_sample_chains(ctx.handle)
+    elif kind == "ddpm_switch":                                              # the late model takes over behind t = 5
+        x, _, chains = run_loop("ddpm", M.first, x_in, ddpm_rows(10, 9), st, late=M.late, t_switch=995, **kw)
+    elif kind in ("guided", "perturbed"):
+        g = (0.4, NULL) if kind == "guided" else engine.Perturbed(0.5, [1])
+        x, _, chains = run_loop("ddpm", M.late, x_in, ddpm_rows(6, 5), st, guidance=g, **kw)
+    elif kind == "region":
+        plan = plans()["region"]
+        assert (known_region(plan, None, None, 0, cut).kb != 0).any(), "the region's rows must draw z2"
+        x, _, chains = run_loop("ddpm", M.late, x_in, plan, st, region=(M.x0[idx].clone(), M.mask[idx].clone()), **kw)
+    else:
+        plan, thr = plans()["threshold"] if kind == "threshold" else (plans()["multistep" if kind == "multistep_sde" else "affine"], None)
+        assert kind == "threshold" or plan.rows["noise"][:cut].any()
+        g = engine.Autoguidance(M.first, 0.7) if kind == "autoguided" else None
+        x, _, chains = run_loop("affine" if kind in ("affine_eta", "autoguided") else "multistep", M.late, x_in, plan, st, threshold=thr,
+                                guidance=g, **kw)
     assert flags != L.DD_DEV_FORCE_CHAINS or chains == 2
     assert bool(torch.isfinite(x).all())
     return x
@@ -368,7 +342,7 @@ def test_sample_step_driven_step_by_step_equals_the_loop(M):
         st.synchronize()
         assert torch.equal(got, want), "control without noise: the backbone is at fault" if noise == "none" else "dd_sample_step under per-image seeds"
     # DD_NOISE_BUFFER steps are what they are without the seeds
-    z = torch.randn(B6, 3, 8, 8, generator=torch.Generator().manual_seed(3)).cuda()
+    z = images(B6, 3, 8, 3)
     a, b = M.x.clone(), M.x.clone()
     with torch.cuda.stream(st):
         M.late.sample_step(a, 5, y=M.y, z=z, noise="buffer", stream=st)

@@ -18,12 +18,10 @@ from conftest import REPO, TINY
 from duodiff_amd import _lib as L
 from duodiff_amd.config import ModelParams, load_config
 from duodiff_amd.weights import synthetic_state_dict
-from loop_support import known_region, philox_z, philox_z2, side_stream, uvit
+from loop_support import KINDS, NULL, labels, philox_z, philox_z2, region_inputs, run_loop, run_steps, side_stream, tiny_model, uvit
 
 gpu = pytest.mark.gpu
 CELEBA_3 = REPO / "configs" / "uvit_celeba_3.yaml"
-KINDS = ("ddpm", "affine", "multistep")
-NULL = 10
 
 
 def _plan(kind, n=6, cut=0):
@@ -193,89 +191,9 @@ def test_lib_binds_the_region_entry_points():
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
-def _model(max_batch, seed=42, precision="bf16", **kw):
-    return uvit(dict(TINY, **kw), seed, precision, max_batch)[0].engine_model(max_batch)
-
-
-def _inputs(B, seed, C_=3, S=8, mask="checker"):
-    """x_T, the known image and a mask: a checkerboard with some 0.5 entries, a half image, or a constant"""
-    g = torch.Generator().manual_seed(seed)
-    x, x0 = torch.randn(B, C_, S, S, generator=g), torch.randn(B, C_, S, S, generator=g)
-    if mask == "checker":
-        i = torch.arange(S)
-        m = ((i[:, None] + i[None, :]) % 2).float().expand(B, 1, S, S).clone()
-        m[:, :, 1::3, ::2] = 0.5
-        m[B - 1] = 1 - m[B - 1]                                   # (the images' masks differ)
-    elif mask == "half":
-        m = torch.zeros(B, 1, S, S)
-        m[..., : S // 2] = 1
-    else:
-        m = torch.full((B, 1, S, S), float(mask))
-    return x.cuda(), x0.cuda(), m.cuda()
-
-
-def _loop(kind, plan, m, x_in, stream, *, region=None, seed=5, use_graph=True, guidance=None, y=None, flags=0, cuts=(), noise="philox"):
-    """the device loop of the plan's kind on model m, cut after the steps in cuts (h and the Philox counter carried); region: (x0, mask)
-    -> (x, h, chains of the last call)"""
-    from duodiff_amd import engine
-    ctx, tab = m.ctx, plan.rows
-    x, h = x_in.clone(), torch.zeros_like(x_in)
-    bounds = [0, *cuts, len(tab["t"])]
-    try:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
-        with torch.cuda.stream(stream):
-            for k0, k1 in zip(bounds[:-1], bounds[1:]):
-                kw = dict(y=y, seed=seed, noise=noise, use_graph=use_graph, stream=stream, guidance=guidance)
-                known = () if region is None else (known_region(plan, *region, k0, k1),)
-                seg = {k: v[k0:k1] for k, v in tab.items()}
-                if kind == "ddpm":
-                    (engine.sample_region_loop if known else engine.sample_loop)(
-                        ctx, m, None, x, *known, t_start=int(seg["t"][0]), t_end=int(seg["t"][-1]), **kw)
-                elif kind == "affine":
-                    (engine.sample_affine_region_loop if known else engine.sample_affine_loop)(
-                        ctx, m, None, x, *known, seg["t"], seg["a"], seg["b"], seg["c"], seg["noise"], counter_base=k0, **kw)
-                else:
-                    (engine.sample_multistep_region_loop if known else engine.sample_multistep_loop)(
-                        ctx, m, None, x, *known, h, seg, counter_base=k0, **kw)
-        stream.synchronize()
-        chains = ctx.lib.dd_dev_last_sample_chains(ctx.handle)
-    finally:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
-    return x, h, chains
-
-
 def _counter(kind, plan, k):
     """the Philox counter of step k: the timestep in the DDPM loop, the step index in a table-driven one"""
     return int(plan.rows["t"][k]) if kind == "ddpm" else k
-
-
-def _step_by_step(kind, plan, m, x_in, stream, region, *, seed=5, guidance=None, y=None, with_z2=True):
-    """forward[_guided | _autoguided] + the existing unfused step + known_blend, z and z2 as the device loop draws them"""
-    from duodiff_amd.engine import Autoguidance
-    from duodiff_amd import sampler
-    ctx, tab = m.ctx, plan.rows
-    ka, kb = sampler.known_rows(plan)
-    x, h, eps = x_in.clone(), torch.zeros_like(x_in), torch.empty_like(x_in)
-    for k in range(len(tab["t"])):
-        t, ctr = float(tab["t"][k]), _counter(kind, plan, k)
-        z = philox_z(m, x_in, ctr, seed, stream, y if m.mp.num_classes > 0 else None) if tab["noise"][k] else None
-        z2 = philox_z2(m, x_in, ctr, seed, stream, y if m.mp.num_classes > 0 else None) if kb[k] != 0 and with_z2 else None
-        with torch.cuda.stream(stream):
-            if isinstance(guidance, Autoguidance):
-                m.forward_autoguided(x, t, y, guidance.guide, guidance.scale, out=eps, stream=stream)
-            elif guidance is not None:
-                m.forward_guided(x, t, y, guidance[0], guidance[1], out=eps, stream=stream)
-            else:
-                m.forward(x, t, y, out=eps, stream=stream)
-            if kind == "ddpm":
-                ctx.ddpm_step(x, eps, z, int(t), out=x, stream=stream)
-            elif kind == "affine":
-                ctx.affine_step(x, eps, z, tab["a"][k], tab["b"][k], tab["c"][k], out=x, stream=stream)
-            else:
-                ctx.multistep_step(x, eps, z, h, *(tab[c][k] for c in "abcdpq"), tab["hist"][k], out=x, stream=stream)
-            ctx.known_blend(x, region[0], region[1], z2, ka[k], kb[k], out=x, stream=stream)
-    stream.synchronize()
-    return x, h
 
 
 def _blend_numpy(x, x0, m, z2, ka, kb):
@@ -335,14 +253,14 @@ def test_zero_mask_equals_the_plain_loop(kind, guided):
     """m == 0 everywhere (x0 NaN-filled): the region loop == the plain loop of the same arguments, bit for bit, x and h; also with
     classifier-free guidance on a class-conditional model."""
     B = 2
-    m = _model(2 * B, num_classes=11) if guided else _model(B)
-    x, x0, mask = _inputs(B, 31, mask=0.0)
+    m = tiny_model(2 * B, num_classes=11) if guided else tiny_model(B)
+    x, x0, mask = region_inputs(B, 31, mask=0.0)
     x0.fill_(float("nan"))
     y = torch.tensor([3, 7]).cuda() if guided else None
     guidance = (0.6, NULL) if guided else None
     plan, st = _plan(kind), side_stream()
-    xp, hp, _ = _loop(kind, plan, m, x, st, y=y, guidance=guidance)
-    xr, hr, _ = _loop(kind, plan, m, x, st, y=y, guidance=guidance, region=(x0, mask))
+    xp, hp, _ = run_loop(kind, m, x, plan, st, y=y, guidance=guidance)
+    xr, hr, _ = run_loop(kind, m, x, plan, st, y=y, guidance=guidance, region=(x0, mask))
     assert torch.isfinite(xp).all() and not torch.equal(xp, x)
     assert torch.equal(xr, xp) and torch.equal(hr, hp), "an all-zero mask changed the loop"
 
@@ -353,14 +271,14 @@ def test_one_mask_gives_the_known_image(kind):
     """m == 1 everywhere: the result is x0 itself; a run cut one step early ends on ka x0 + kb z2 of its last step."""
     from duodiff_amd import sampler
     B = 2
-    m = _model(B)
-    x, x0, mask = _inputs(B, 32, mask=1.0)
+    m = tiny_model(B)
+    x, x0, mask = region_inputs(B, 32, mask=1.0)
     st = side_stream()
     plan = _plan(kind)
-    xr, _, _ = _loop(kind, plan, m, x, st, region=(x0, mask))
+    xr, _, _ = run_loop(kind, m, x, plan, st, region=(x0, mask))
     assert torch.equal(xr, x0), "the known pixels of the result are not x0"
     short = _plan(kind, cut=1)
-    xs, _, _ = _loop(kind, short, m, x, st, region=(x0, mask))
+    xs, _, _ = run_loop(kind, m, x, short, st, region=(x0, mask))
     ka, kb = sampler.known_rows(short)
     k = len(ka) - 1
     assert kb[k] > 0 and ka[k] < 1
@@ -374,14 +292,14 @@ def test_one_mask_gives_the_known_image(kind):
 def test_loop_forms_agree(kind):
     """A checkerboard mask with some 0.5 entries: graph replay == eager launches == forward + the unfused step + known_blend."""
     B = 2
-    m = _model(B)
-    x, x0, mask = _inputs(B, 33)
+    m = tiny_model(B)
+    x, x0, mask = region_inputs(B, 33)
     assert set(mask.unique().tolist()) == {0.0, 0.5, 1.0}
     plan, st = _plan(kind), side_stream()
-    xg, hg, _ = _loop(kind, plan, m, x, st, region=(x0, mask), use_graph=True)
-    xe, he, _ = _loop(kind, plan, m, x, st, region=(x0, mask), use_graph=False)
-    xs, hs = _step_by_step(kind, plan, m, x, st, (x0, mask))
-    xp, _, _ = _loop(kind, plan, m, x, st)
+    xg, hg, _ = run_loop(kind, m, x, plan, st, region=(x0, mask), use_graph=True)
+    xe, he, _ = run_loop(kind, m, x, plan, st, region=(x0, mask), use_graph=False)
+    xs, hs = run_steps(kind, m, x, plan, st, region=(x0, mask))
+    xp, _, _ = run_loop(kind, m, x, plan, st)
     assert torch.isfinite(xg).all() and not torch.equal(xg, xp), "the region changed nothing"
     assert torch.equal(xg, xe) and torch.equal(hg, he), "graph replay differs from eager launches"
     assert torch.equal(xg, xs), "device loop differs from forward + step + known_blend"
@@ -390,9 +308,9 @@ def test_loop_forms_agree(kind):
     keep = (mask == 1).expand_as(x0)
     assert torch.equal(xg[keep], x0[keep])
     # DD_NOISE_NONE: neither c z nor kb z2 is added
-    xn, _, _ = _loop(kind, plan, m, x, st, region=(x0, mask), noise="none")
+    xn, _, _ = run_loop(kind, m, x, plan, st, region=(x0, mask), noise="none")
     plan_nz = plan._replace(rows=dict(plan.rows, noise=np.zeros_like(plan.rows["noise"])))
-    xns, _ = _step_by_step(kind, plan_nz, m, x, st, (x0, mask), with_z2=False)
+    xns, _ = run_steps(kind, m, x, plan_nz, st, region=(x0, mask), with_z2=False)
     assert torch.equal(xn, xns), "DD_NOISE_NONE differs from the steps without z and z2"
 
 
@@ -401,14 +319,14 @@ def test_loop_forms_agree(kind):
 def test_two_chains_and_cut_loops(kind):
     """B = 6 with the chain split forced: two chains == one chain, and a loop cut into calls (counter_base and h carried) == the uncut one."""
     B = 6
-    m = _model(B)
-    x, x0, mask = _inputs(B, 34)
+    m = tiny_model(B)
+    x, x0, mask = region_inputs(B, 34)
     plan, st = _plan(kind, n=7), side_stream()
-    x2, h2, c2 = _loop(kind, plan, m, x, st, region=(x0, mask), flags=L.DD_DEV_FORCE_CHAINS)
-    x1, h1, c1 = _loop(kind, plan, m, x, st, region=(x0, mask), flags=L.DD_DEV_NO_CHAINS)
+    x2, h2, c2 = run_loop(kind, m, x, plan, st, region=(x0, mask), flags=L.DD_DEV_FORCE_CHAINS)
+    x1, h1, c1 = run_loop(kind, m, x, plan, st, region=(x0, mask), flags=L.DD_DEV_NO_CHAINS)
     assert (c2, c1) == (2, 1)
     assert torch.isfinite(x1).all() and torch.equal(x2, x1) and torch.equal(h2, h1), "two chains differ from one"
-    xc, hc, _ = _loop(kind, plan, m, x, st, region=(x0, mask), flags=L.DD_DEV_FORCE_CHAINS, cuts=(2, 3, 6))
+    xc, hc, _ = run_loop(kind, m, x, plan, st, region=(x0, mask), flags=L.DD_DEV_FORCE_CHAINS, cuts=(2, 3, 6))
     assert torch.equal(xc, x2) and torch.equal(hc, h2), "a cut loop differs from the uncut loop"
 
 
@@ -417,12 +335,12 @@ def test_two_chains_and_cut_loops(kind):
 def test_guided_region_equals_the_steps(kind):
     """Classifier-free guidance with a region, chains forced: == forward_guided + step + blend (both rows of an image carry x'')."""
     B = 6
-    m = _model(2 * B, num_classes=11)
-    x, x0, mask = _inputs(B, 35)
-    y = torch.randint(0, NULL, (B,), generator=torch.Generator().manual_seed(6)).cuda()
+    m = tiny_model(2 * B, num_classes=11)
+    x, x0, mask = region_inputs(B, 35)
+    y = labels(B, NULL, 6)
     plan, st = _plan(kind, n=5), side_stream()
-    xg, hg, c = _loop(kind, plan, m, x, st, region=(x0, mask), y=y, guidance=(0.4, NULL), flags=L.DD_DEV_FORCE_CHAINS)
-    xs, hs = _step_by_step(kind, plan, m, x, st, (x0, mask), y=y, guidance=(0.4, NULL))
+    xg, hg, c = run_loop(kind, m, x, plan, st, region=(x0, mask), y=y, guidance=(0.4, NULL), flags=L.DD_DEV_FORCE_CHAINS)
+    xs, hs = run_steps(kind, m, x, plan, st, region=(x0, mask), y=y, guidance=(0.4, NULL))
     assert c == 2 and torch.isfinite(xg).all()
     assert torch.equal(xg, xs) and torch.equal(hg, hs), "guided region loop differs from forward_guided + step + blend"
 
@@ -433,13 +351,13 @@ def test_autoguided_region_equals_the_steps(kind):
     """Autoguidance of the depth-3 model by the depth-1 one, with a region, chains forced: == forward_autoguided + step + blend."""
     from duodiff_amd.engine import Autoguidance
     B = 6
-    guide, m = _model(B, seed=41, depth=1), _model(B, seed=42)
-    x, x0, mask = _inputs(B, 36)
+    guide, m = tiny_model(B, seed=41, depth=1), tiny_model(B, seed=42)
+    x, x0, mask = region_inputs(B, 36)
     plan, st = _plan(kind, n=5), side_stream()
     ag = Autoguidance(guide, 0.7)
-    xg, hg, c = _loop(kind, plan, m, x, st, region=(x0, mask), guidance=ag, flags=L.DD_DEV_FORCE_CHAINS)
-    xs, hs = _step_by_step(kind, plan, m, x, st, (x0, mask), guidance=ag)
-    xu, _, _ = _loop(kind, plan, m, x, st, region=(x0, mask))
+    xg, hg, c = run_loop(kind, m, x, plan, st, region=(x0, mask), guidance=ag, flags=L.DD_DEV_FORCE_CHAINS)
+    xs, hs = run_steps(kind, m, x, plan, st, region=(x0, mask), guidance=ag)
+    xu, _, _ = run_loop(kind, m, x, plan, st, region=(x0, mask))
     assert c == 2 and torch.isfinite(xg).all() and not torch.equal(xg, xu)
     assert torch.equal(xg, xs) and torch.equal(hg, hs), "autoguided region loop differs from forward_autoguided + step + blend"
 
@@ -449,8 +367,8 @@ def test_z2_is_independent_of_z():
     """z2 differs from z at the same step, and over the B C S S values of 8 steps their sample correlation is below 5 / sqrt(N):
     independent normals give a standard deviation of 1 / sqrt(N)."""
     B = 2
-    m = _model(B)
-    x, _, _ = _inputs(B, 37)
+    m = tiny_model(B)
+    x, _, _ = region_inputs(B, 37)
     st = side_stream()
     zs, z2s = [], []
     for k in range(8):
@@ -472,25 +390,25 @@ def test_z2_is_independent_of_z():
 def test_second_call_with_other_tensors():
     """A second call with another x0 / mask of the same shape gives that call's own step-by-step result, replaying the graphs of the first."""
     B = 2
-    m = _model(B)
+    m = tiny_model(B)
     plan, st = _plan("affine"), side_stream()
-    x, x0a, ma = _inputs(B, 38)
-    _, x0b, _ = _inputs(B, 39)
+    x, x0a, ma = region_inputs(B, 38)
+    _, x0b, _ = region_inputs(B, 39)
     mb = (1 - ma).contiguous()
     lib, h = m.ctx.lib, m.ctx.handle
-    ra, _, _ = _loop("affine", plan, m, x, st, region=(x0a, ma))
+    ra, _, _ = run_loop("affine", m, x, plan, st, region=(x0a, ma))
     n0 = lib.dd_dev_graph_captures(h)
-    rb, _, _ = _loop("affine", plan, m, x, st, region=(x0b, mb))
+    rb, _, _ = run_loop("affine", m, x, plan, st, region=(x0b, mb))
     assert lib.dd_dev_graph_captures(h) == n0, "the second call re-captured a graph"
-    re_, _, _ = _loop("affine", plan, m, x, st, region=(x0b, mb), use_graph=False)
-    sa, _ = _step_by_step("affine", plan, m, x, st, (x0a, ma))
-    sb, _ = _step_by_step("affine", plan, m, x, st, (x0b, mb))
+    re_, _, _ = run_loop("affine", m, x, plan, st, region=(x0b, mb), use_graph=False)
+    sa, _ = run_steps("affine", m, x, plan, st, region=(x0a, ma))
+    sb, _ = run_steps("affine", m, x, plan, st, region=(x0b, mb))
     assert not torch.equal(ra, rb)
     assert torch.equal(ra, sa) and torch.equal(rb, sb) and torch.equal(re_, sb)
     # a plain call in between keeps its own graph and result
-    p1, _, _ = _loop("affine", plan, m, x, st)
-    ra2, _, _ = _loop("affine", plan, m, x, st, region=(x0a, ma))
-    p2, _, _ = _loop("affine", plan, m, x, st)
+    p1, _, _ = run_loop("affine", m, x, plan, st)
+    ra2, _, _ = run_loop("affine", m, x, plan, st, region=(x0a, ma))
+    p2, _, _ = run_loop("affine", m, x, plan, st)
     assert torch.equal(p1, p2) and torch.equal(ra2, ra) and not torch.equal(p1, ra)
 
 
@@ -498,14 +416,14 @@ def test_second_call_with_other_tensors():
 def test_poisoned_workspaces_and_history_with_a_region():
     """Both chains' workspaces NaN-poisoned before the call, on fresh models: == the clean run (multistep, chains forced)."""
     B = 6
-    x, x0, mask = _inputs(B, 40)
+    x, x0, mask = region_inputs(B, 40)
     plan, st = _plan("multistep", n=8), side_stream()
     outs = []
     for poison in (False, True):
-        m = _model(B, seed=71)
+        m = tiny_model(B, seed=71)
         if poison:
             m.ctx.check(m.ctx.lib.dd_dev_poison_workspaces(m.ctx.handle, m.handle, st.cuda_stream))
-        outs.append(_loop("multistep", plan, m, x, st, region=(x0, mask), flags=L.DD_DEV_FORCE_CHAINS))
+        outs.append(run_loop("multistep", m, x, plan, st, region=(x0, mask), flags=L.DD_DEV_FORCE_CHAINS))
         del m
     assert outs[0][2] == outs[1][2] == 2
     assert torch.isfinite(outs[0][0]).all() and torch.isfinite(outs[1][1]).all()
@@ -517,11 +435,11 @@ def test_poisoned_workspaces_and_history_with_a_region():
 def test_invalid_region_calls_are_rejected_before_anything_is_enqueued(kind):
     from duodiff_amd.engine import Model
     B = 2
-    m, guide = _model(B), _model(B, seed=41, depth=1)
+    m, guide = tiny_model(B), tiny_model(B, seed=41, depth=1)
     ctx, lib = m.ctx, m.ctx.lib
     ee = Model(ctx, ModelParams.from_dict(dict(TINY)), B)
     ee.enable_early_exit("mlp_probe_per_layer")
-    x_in, x0, mask = _inputs(B, 41)
+    x_in, x0, mask = region_inputs(B, 41)
     plan, st = _plan(kind, n=3), side_stream()
     tab = {k: np.ascontiguousarray(v, np.int32 if k in ("noise", "hist") else np.float32) for k, v in plan.rows.items()}
     ka, kb = np.ones(3, np.float32), np.zeros(3, np.float32)
@@ -568,11 +486,11 @@ def test_loop_rejections_keep_their_order():
     region's own rules, the multistep loop's early-exit exclusion, the models, the loop's tensors and ranges, the noise mode)."""
     from duodiff_amd.engine import Model
     B = 2
-    m, guide = _model(B), _model(B, seed=41, depth=1)
+    m, guide = tiny_model(B), tiny_model(B, seed=41, depth=1)
     ctx, lib = m.ctx, m.ctx.lib
     ee = Model(ctx, ModelParams.from_dict(dict(TINY)), B)
     ee.enable_early_exit("mlp_probe_per_layer")
-    x_in, x0, mask = _inputs(B, 43)
+    x_in, x0, mask = region_inputs(B, 43)
     x, h, st = x_in.clone(), torch.zeros_like(x_in), side_stream()
     tab = {k: np.ascontiguousarray(v, np.int32 if k in ("noise", "hist") else np.float32) for k, v in _plan("multistep", n=3).rows.items()}
     ka, kb = np.ones(3, np.float32), np.zeros(3, np.float32)
@@ -633,7 +551,7 @@ def test_fp32_engine_matches_the_oracle_with_a_half_image_mask():
     plan = sampler.step_plan(None, use_ddim=True, ddim_steps=9, ddim_eta=0.01)
     assert len(plan.rows["t"]) == 8
     ka, kb = sampler.known_rows(plan)
-    xd, x0, mask = _inputs(B, 62, mask="half")
+    xd, x0, mask = region_inputs(B, 62, mask="half")
     st = side_stream()
     x, k0, mk = xd.cpu().numpy().astype(np.float64), x0.cpu().numpy().astype(np.float64), mask.cpu().numpy().astype(np.float64)
     r = plan.rows
@@ -646,7 +564,7 @@ def test_fp32_engine_matches_the_oracle_with_a_half_image_mask():
         if kb[k] != 0:
             kn = kn + float(kb[k]) * philox_z2(em, xd, k, 5, st).cpu().numpy().astype(np.float64)
         x = np.where(mk == 0, v, mk * kn + (1 - mk) * v)
-    got, _, _ = _loop("affine", plan, em, xd, st, region=(x0, mask))
+    got, _, _ = run_loop("affine", em, xd, plan, st, region=(x0, mask))
     err = float(np.abs(got.cpu().numpy() - x).max())
     print(f"fp32 engine vs the oracle, 8 DDIM steps with a half-image mask: max abs {err:.3e} (|x| max {np.abs(x).max():.3f})")
     assert np.isfinite(err) and err <= 1e-3
@@ -659,11 +577,11 @@ def test_celeba_width_two_real_chains():
     from duodiff_amd import sampler
     B = 32
     m = uvit(load_config(CELEBA_3), 51, "bf16", B)[0].engine_model(B)
-    x, x0, mask = _inputs(B, 42, S=64)
+    x, x0, mask = region_inputs(B, 42, S=64)
     plan, st = sampler.step_plan("predict_noise", num_steps=3), side_stream()
-    xg, _, chains = _loop("ddpm", plan, m, x, st, region=(x0, mask))
-    xs, _ = _step_by_step("ddpm", plan, m, x, st, (x0, mask))
-    xp, _, _ = _loop("ddpm", plan, m, x, st)
+    xg, _, chains = run_loop("ddpm", m, x, plan, st, region=(x0, mask))
+    xs, _ = run_steps("ddpm", m, x, plan, st, region=(x0, mask))
+    xp, _, _ = run_loop("ddpm", m, x, plan, st)
     assert chains == 2 and torch.isfinite(xg).all() and not torch.equal(xg, xp)
     assert torch.equal(xg, xs), "the product path differs from forward + ddpm_step + known_blend"
 

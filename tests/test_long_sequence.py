@@ -16,7 +16,7 @@ import torch
 import oracle
 from duodiff_amd.config import ModelParams
 from duodiff_amd.weights import synthetic_state_dict
-from loop_support import eps_rms_bound, uvit
+from loop_support import dev_flags, eps_rms_bound, images, side_stream, uvit
 
 pytestmark = pytest.mark.gpu
 
@@ -143,13 +143,11 @@ def test_device_loops_chained_graph_replay_equals_the_eager_single_chain():
     m_f, _ = uvit(L325, 32, "bf16", max_batch=B)
     es, ef = m_s.engine_model(B), m_f.engine_model(B)
     ctx = es.ctx
-    x0 = torch.randn(B, 3, 72, 72, generator=torch.Generator().manual_seed(4)).cuda()
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
+    x0 = images(B, 3, 72, 4)
+    stream = side_stream()
     ddpm, ddim = [], []
-    try:
-        for flags, graph in ((L.DD_DEV_FORCE_CHAINS, True), (L.DD_DEV_NO_CHAINS, False)):
-            ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
+    for flags, graph in ((L.DD_DEV_FORCE_CHAINS, True), (L.DD_DEV_NO_CHAINS, False)):
+        with dev_flags(ctx, flags):
             x = x0.clone()
             with torch.cuda.stream(stream):
                 sample_loop(ctx, es, ef, x, t_switch=997, t_start=999, t_end=996, seed=9, noise="philox", use_graph=graph, stream=stream)
@@ -158,8 +156,6 @@ def test_device_loops_chained_graph_replay_equals_the_eager_single_chain():
             g, _ = sampler.get_samples(m_s, B, sampler.predict_noise_postprocessing, 5, 3, 72, 72, late_model=m_f, noise="device",
                                        use_ddim=True, ddim_steps=4, ddim_eta=0.0, t_switch=400, use_graph=graph)
             ddim.append((g, ctx.lib.dd_dev_last_sample_chains(ctx.handle)))
-    finally:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
     for name, (a, b) in (("dd_sample", ddpm), ("DDIM", ddim)):
         assert a[1] == 2 and b[1] == 1, (name, a[1], b[1])
     assert torch.isfinite(ddpm[1][0]).all() and not torch.equal(ddpm[1][0], x0)

@@ -16,12 +16,12 @@ import torch
 
 from conftest import REPO, TINY
 from duodiff_amd import _lib as L
-from duodiff_amd.config import ModelParams, load_config
+from duodiff_amd.config import ModelParams
 from duodiff_amd.weights import synthetic_state_dict
-from loop_support import cli_argv, engine_pair, philox_z, side_stream, uvit
+from loop_support import NULL, celeba_pair, cli_argv, dev_flags, engine_pair, images, labels, run_loop, run_steps, side_stream, uvit
 
 gpu = pytest.mark.gpu
-CELEBA, CELEBA_3 = REPO / "configs" / "uvit_celeba.yaml", REPO / "configs" / "uvit_celeba_3.yaml"
+CELEBA = REPO / "configs" / "uvit_celeba.yaml"
 
 
 def _abar():
@@ -216,17 +216,13 @@ def test_lib_binds_the_multistep_entry_points():
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
-NULL = 10
-TINY_COND = dict(TINY, num_classes=11)
-
-
 def _tiny_pair(max_batch, seeds=(41, 42), **kw):
     return engine_pair(dict(TINY, depth=1, **kw), dict(TINY, depth=3, **kw), seeds, max_batch)
 
 
-@pytest.fixture(scope="module")
-def celeba_pair():
-    return engine_pair(load_config(CELEBA_3), load_config(CELEBA), (51, 52), 32)
+@pytest.fixture(scope="module", name="celeba_pair")
+def _celeba_pair_of_the_module():
+    return celeba_pair(32)
 
 
 def _rows(kind="sde-dpmsolver++", n=20, order=2, steps=None):
@@ -235,46 +231,14 @@ def _rows(kind="sde-dpmsolver++", n=20, order=2, steps=None):
     return r if steps is None else {k: v[:steps] for k, v in r.items()}
 
 
-def _loop(es, ef, x0, rows, stream, *, switch_after=None, seed=5, use_graph=True, guidance=None, y=None, h0=None, flags=0, cuts=()):
-    """the device loop from x0 (h zero, or h0), cut after the steps in cuts; -> (x, h, chains of the last call)"""
-    from duodiff_amd.engine import sample_multistep_loop
-    ctx = es.ctx
-    x = x0.clone()
-    h = torch.zeros_like(x0) if h0 is None else h0.clone()
-    n = len(rows["t"])
-    bounds = [0, *cuts, n]
-    try:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
-        with torch.cuda.stream(stream):
-            for k0, k1 in zip(bounds[:-1], bounds[1:]):
-                sw = None if switch_after is None else min(max(switch_after - k0, 0), k1 - k0)
-                first, late = (es, ef) if (sw is None or sw > 0) else (ef, None)
-                sample_multistep_loop(ctx, first, late if sw is not None and 0 < sw < k1 - k0 else None, x, h,
-                                      {k: v[k0:k1] for k, v in rows.items()}, switch_after=sw, y=y, seed=seed, counter_base=k0,
-                                      noise="philox", use_graph=use_graph, stream=stream, guidance=guidance)
-        stream.synchronize()
-        chains = ctx.lib.dd_dev_last_sample_chains(ctx.handle)
-    finally:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
-    return x, h, chains
+def _loop(es, ef, x0, rows, stream, **kw):
+    """the device loop from x0 on the pair; kw: run_loop's -> (x, h, chains of the last call)"""
+    return run_loop("multistep", es, x0, rows, stream, late=ef, **kw)
 
 
-def _host_loop(es, ef, x0, rows, stream, *, switch_after=None, seed=5, guidance=None, y=None):
-    """step by step: dd_forward[_guided] + dd_multistep_step, z from _philox_z"""
-    ctx = es.ctx
-    x, h, eps = x0.clone(), torch.zeros_like(x0), torch.empty_like(x0)
-    for k in range(len(rows["t"])):
-        t = float(rows["t"][k])
-        z = philox_z(es, x0, k, seed, stream, y, t=t) if rows["noise"][k] else None
-        m = ef if (switch_after is not None and k >= switch_after) else es
-        with torch.cuda.stream(stream):
-            if guidance is None:
-                m.forward(x, t, y, out=eps, stream=stream)
-            else:
-                m.forward_guided(x, t, y, guidance[0], guidance[1], out=eps, stream=stream)
-            ctx.multistep_step(x, eps, z, h, *(rows[c][k] for c in "abcdpq"), rows["hist"][k], out=x, stream=stream)
-    stream.synchronize()
-    return x, h
+def _host_loop(es, ef, x0, rows, stream, **kw):
+    """step by step: dd_forward[_guided] + dd_multistep_step, z as the device loop draws it"""
+    return run_steps("multistep", es, x0, rows, stream, late=ef, **kw)
 
 
 @gpu
@@ -318,7 +282,7 @@ def test_loop_forms_agree(kind):
     """TINY pair, backbone switch inside: graph replay == eager launches == dd_forward + dd_multistep_step, bit for bit (x and h)."""
     B = 4
     es, ef, _ = _tiny_pair(max_batch=B)
-    x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(2)).cuda()
+    x0 = images(B, 3, 8, 2)
     rows = _rows(kind, n=10)
     st = side_stream()
     xg, hg, _ = _loop(es, ef, x0, rows, st, switch_after=4, use_graph=True)
@@ -338,7 +302,7 @@ def test_two_chains_equal_one_chain(case, request):
     else:
         B, S, force = 32, 64, 0
         es, ef, _ = request.getfixturevalue("celeba_pair")
-    x0 = torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(3)).cuda()
+    x0 = images(B, 3, S, 3)
     rows = _rows("sde-dpmsolver++", n=20, steps=8)
     st = side_stream()
     x2, h2, c2 = _loop(es, ef, x0, rows, st, switch_after=5, flags=force)
@@ -358,7 +322,7 @@ def test_cut_loop_equals_the_uncut_loop(case, request):
     else:
         B, S, force = 32, 64, 0
         es, ef, _ = request.getfixturevalue("celeba_pair")
-    x0 = torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(4)).cuda()
+    x0 = images(B, 3, S, 4)
     rows = _rows("sde-dpmsolver++", n=12)
     st = side_stream()
     xu, hu, _ = _loop(es, ef, x0, rows, st, switch_after=6, flags=force)
@@ -373,8 +337,8 @@ def test_guided_multistep(S):
     same labels (SDE, Philox noise); scale 0.4 ODE == forward_guided + multistep_step, bit for bit."""
     B = 6
     es, ef, _ = _tiny_pair(max_batch=2 * B, num_classes=11, img_size=S)
-    x0 = torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(5)).cuda()
-    y = torch.randint(0, NULL, (B,), generator=torch.Generator().manual_seed(6)).cuda()
+    x0 = images(B, 3, S, 5)
+    y = labels(B, NULL, 6)
     st = side_stream()
     rows = _rows("sde-dpmsolver++", n=10)
     xu, hu, cu = _loop(es, ef, x0, rows, st, switch_after=3, y=y, flags=L.DD_DEV_FORCE_CHAINS)
@@ -401,7 +365,7 @@ def test_ddim_rows_reproduce_the_affine_loop(case, request):
     else:
         B, S, force = 32, 64, 0
         es, ef, _ = request.getfixturevalue("celeba_pair")
-    x0 = torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(7)).cuda()
+    x0 = images(B, 3, S, 7)
     ts = np.linspace(0, 999, 11).astype(int)[::-1]
     pairs = [(int(t), int(s)) for t, s in zip(ts[:-1], ts[1:])]
     tables = {"ddim": ([float(t) for t, _ in pairs], [sampler.affine_coefficients("ddim", t, s, 0.0) for t, s in pairs], [0] * 10),
@@ -414,14 +378,10 @@ def test_ddim_rows_reproduce_the_affine_loop(case, request):
                     q=np.zeros(n), hist=np.zeros(n, np.int32))
         xm, hm, _ = _loop(es, ef, x0, rows, st, switch_after=4, flags=force, seed=8)
         xa = x0.clone()
-        try:
-            es.ctx.check(es.ctx.lib.dd_dev_set_flags(es.ctx.handle, force))
-            with torch.cuda.stream(st):
-                sample_affine_loop(es.ctx, es, ef, xa, rows["t"], rows["a"], rows["b"], rows["c"], rows["noise"], switch_after=4, seed=8,
-                                   noise="philox", stream=st)
+        with dev_flags(es.ctx, force), torch.cuda.stream(st):
+            sample_affine_loop(es.ctx, es, ef, xa, rows["t"], rows["a"], rows["b"], rows["c"], rows["noise"], switch_after=4, seed=8,
+                               noise="philox", stream=st)
             st.synchronize()
-        finally:
-            es.ctx.check(es.ctx.lib.dd_dev_set_flags(es.ctx.handle, 0))
         assert torch.isfinite(xa).all() and not torch.equal(xa, x0), name
         assert torch.equal(xm, xa), f"multistep loop with {name} rows differs from dd_sample_affine"
         assert not hm.any()
@@ -434,7 +394,7 @@ def test_affine_and_multistep_calls_do_not_share_graphs():
     from duodiff_amd import sampler
     from duodiff_amd.engine import sample_affine_loop
     B = 4
-    x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(9)).cuda()
+    x0 = images(B, 3, 8, 9)
     rows = _rows("dpmsolver++", n=10)
     co = [sampler.affine_coefficients("ddim", int(t), int(s), 0.0)
           for t, s in zip(sampler.multistep_grid(10)[:-1], sampler.multistep_grid(10)[1:])]
@@ -467,7 +427,7 @@ def test_affine_and_multistep_calls_do_not_share_graphs():
 def test_poisoned_workspaces_and_history():
     """Both chains' workspaces NaN-poisoned and h NaN-filled before the call (step 0 has no history) == the clean run."""
     B = 6
-    x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(10)).cuda()
+    x0 = images(B, 3, 8, 10)
     rows = _rows("sde-dpmsolver++", n=10)
     st = side_stream()
     outs = []
@@ -493,7 +453,7 @@ def test_invalid_multistep_calls_are_rejected_before_anything_is_enqueued():
     ctx, lib = es.ctx, es.ctx.lib
     ee = Model(ctx, ModelParams.from_dict(dict(TINY, depth=3)), B)
     ee.enable_early_exit("mlp_probe_per_layer")
-    x0 = torch.randn(B, 3, 8, 8, generator=torch.Generator().manual_seed(11)).cuda()
+    x0 = images(B, 3, 8, 11)
     rows = _rows("dpmsolver++", n=3)
     st = side_stream()
     n0 = lib.dd_dev_graph_captures(ctx.handle)

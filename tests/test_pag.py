@@ -30,8 +30,8 @@ from duodiff_amd import _lib as L
 from duodiff_amd.config import ModelParams, load_config
 from duodiff_amd.weights import synthetic_state_dict
 from kernel_support import FP32_REL, NAN16, P, bf16, from_bf16_bits, gate, ulp_bf16
-from loop_support import cli_argv, engine_pair, eps_rms_bound, side_stream, uvit
-from test_autoguidance import KINDS, _affine_rows, _flags, _ms_rows, _run, _x0
+from loop_support import KINDS, QA512, TAIL256, TINY_COND, celeba_pair, cli_argv, dev_flags, engine_pair, eps_rms_bound, first_rows, images
+from loop_support import labels, run_first_steps, run_steps, side_stream, uvit
 from test_row_kernels import ln_rows, ln_tolerances
 
 gpu = pytest.mark.gpu
@@ -281,12 +281,6 @@ def test_v_copy_refuses_a_long_sequence():
 
 
 # ---- GPU, model -------------------------------------------------------------------------------------------------------------
-TINY_COND = dict(TINY, num_classes=11)
-QA512 = dict(img_size=64, patch_size=4, in_chans=3, embed_dim=512, depth=3, num_heads=8, mlp_ratio=4, qkv_bias=False,
-             mlp_time_embed=False, num_classes=-1, normalize_timesteps=True)          # L = 257: attn.qkv inside the attention launch
-TAIL256 = dict(img_size=16, patch_size=2, in_chans=3, embed_dim=256, depth=3, num_heads=4, mlp_ratio=4, qkv_bias=False,
-               mlp_time_embed=False, num_classes=-1, normalize_timesteps=True)        # the block tail computes the next attn.qkv
-
 FORWARD_CASES = {
     "tiny": (TINY, 5, 0), "tiny_classes": (TINY_COND, 5, 0), "qa512": (QA512, 2, 0), "qa512_no_fused_qa": (QA512, 2, L.DD_DEV_NO_FUSED_QA),
     "tail256": (TAIL256, 3, 0),
@@ -342,7 +336,7 @@ def test_forward_perturbed_vs_oracle(monkeypatch, case, mask):
     assert moved >= 0.05, "the oracle's own perturbation is too small to test anything"
     for prec in ("fp32", "bf16"):
         m, _ = uvit(cfg, 61, prec, max_batch=2 * B)
-        with _flags(kernel_support.ctx(), flags):
+        with dev_flags(kernel_support.ctx(), flags):
             em = m.engine_model(2 * B)
         yd = None if y is None else y.cuda()
         got = em.forward_perturbed(x.cuda(), t, yd, s, layers).cpu().numpy().astype(np.float64)
@@ -384,10 +378,6 @@ def _tiny_pair(seeds=(41, 42), max_batch=12):
     return engine_pair(dict(TINY, depth=1), dict(TINY, depth=3), seeds, max_batch)[:2]
 
 
-def _celeba_pair(max_batch):
-    return engine_pair(load_config(CELEBA_3), load_config(CELEBA), (51, 52), max_batch)[:2]
-
-
 @gpu
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("case", ["tiny_forced", "celeba_default"])
@@ -401,14 +391,13 @@ def test_scale_zero_equals_the_unguided_loop(case, kind):
         full = Perturbed(0.0, [0], [0, 1, 2])
     else:
         B, S, n, sw, flags = 32, 64, 3, 1, 0
-        es, ef = _celeba_pair(max_batch=2 * B)
+        es, ef = celeba_pair(2 * B)[:2]
         full = Perturbed(0.0, [0, 1, 2], list(range(13)))
-    ctx, x0, stream = es.ctx, _x0(B, 3, S, 7), side_stream()
+    ctx, x0, stream = es.ctx, images(B, 3, S, 7), side_stream()
     outs = {}
-    with _flags(ctx, flags):
-        for name, guidance in (("unguided", None), ("scale0", full)):
-            outs[name] = (_run(kind, ctx, es, ef, x0, stream, switch=sw, n=n, seed=21, noise="philox", guidance=guidance),
-                          ctx.lib.dd_dev_last_sample_chains(ctx.handle))
+    for name, guidance in (("unguided", None), ("scale0", full)):
+        outs[name] = (run_first_steps(kind, es, ef, x0, stream, switch=sw, n=n, seed=21, noise="philox", flags=flags, guidance=guidance),
+                      ctx.lib.dd_dev_last_sample_chains(ctx.handle))
     assert outs["unguided"][1] == outs["scale0"][1] == 2
     assert torch.isfinite(outs["scale0"][0]).all()
     assert torch.equal(outs["scale0"][0], outs["unguided"][0]), "scale 0 differs from the unguided loop"
@@ -422,26 +411,11 @@ def test_perturbed_loops_equal_manual_steps(kind):
     from duodiff_amd.engine import Perturbed
     B, s, n, sw = 4, 1.7, 8, 3
     es, ef = _tiny_pair(max_batch=2 * B)
-    ctx, x0, stream = ef.ctx, _x0(B, 3, 8, 11), side_stream()
+    x0, stream = images(B, 3, 8, 11), side_stream()
     pag = Perturbed(s, [0], [1, 2])
-    loops = [_run(kind, ctx, es, ef, x0, stream, switch=sw, n=n, noise="none", use_graph=ug, guidance=pag) for ug in (True, False)]
-    plain = _run(kind, ctx, es, ef, x0, stream, switch=sw, n=n, noise="none", guidance=None)
-    rows = None if kind == "ddpm" else _affine_rows(n) if kind == "affine" else _ms_rows(n)
-    xm, eps, h = x0.clone(), torch.empty_like(x0), torch.zeros_like(x0)
-    with torch.cuda.stream(stream):
-        for k in range(n):
-            t = 999 - k if kind == "ddpm" else float(rows["t"][k])
-            if k < sw:
-                es.forward_perturbed(xm, t, None, s, [0], out=eps, stream=stream)
-            else:
-                ef.forward_perturbed(xm, t, None, s, [1, 2], out=eps, stream=stream)
-            if kind == "ddpm":
-                ctx.ddpm_step(xm, eps, None, t, out=xm, stream=stream)
-            elif kind == "affine":
-                ctx.affine_step(xm, eps, None, rows["a"][k], rows["b"][k], 0.0, out=xm, stream=stream)
-            else:
-                ctx.multistep_step(xm, eps, None, h, *(rows[key][k] for key in "abcdpq"), rows["hist"][k], out=xm, stream=stream)
-        stream.synchronize()
+    loops = [run_first_steps(kind, es, ef, x0, stream, switch=sw, n=n, noise="none", use_graph=ug, guidance=pag) for ug in (True, False)]
+    plain = run_first_steps(kind, es, ef, x0, stream, switch=sw, n=n, noise="none", guidance=None)
+    xm, h = run_steps(kind, es, x0, first_rows(kind, n), stream, late=ef, switch_after=sw, noise="none", guidance=pag)
     manual = xm if kind != "multistep" else torch.stack([xm, h])
     assert torch.isfinite(manual).all() and not torch.equal(xm, x0)
     assert torch.equal(loops[0], loops[1]), "graph replay differs from eager launches"
@@ -456,13 +430,12 @@ def test_perturbed_two_chains_equal_one_chain(kind):
     from duodiff_amd.engine import Perturbed
     B = 6
     es, ef = _tiny_pair(max_batch=2 * B)
-    ctx, x0, stream = es.ctx, _x0(B, 3, 8, 13), side_stream()
+    ctx, x0, stream = es.ctx, images(B, 3, 8, 13), side_stream()
     pag = Perturbed(0.4, [0], [1])
     outs = {}
     for name, flags in (("chained", L.DD_DEV_FORCE_CHAINS), ("single", L.DD_DEV_NO_CHAINS)):
-        with _flags(ctx, flags):
-            outs[name] = (_run(kind, ctx, es, ef, x0, stream, switch=3, n=8, seed=23, noise="philox", guidance=pag),
-                          ctx.lib.dd_dev_last_sample_chains(ctx.handle))
+        outs[name] = (run_first_steps(kind, es, ef, x0, stream, switch=3, n=8, seed=23, noise="philox", flags=flags, guidance=pag),
+                      ctx.lib.dd_dev_last_sample_chains(ctx.handle))
     assert outs["chained"][1] == 2 and outs["single"][1] == 1
     assert torch.isfinite(outs["single"][0]).all()
     assert torch.equal(outs["chained"][0], outs["single"][0]), "perturbed chains differ from the single chain"
@@ -473,11 +446,11 @@ def test_a_new_mask_or_scale_is_not_a_stale_graph():
     """Calls with (scale, first mask, late mask) changing one at a time on the same models: each equals a run of freshly built models"""
     from duodiff_amd.engine import Perturbed
     B = 4
-    x0, stream = _x0(B, 3, 8, 15), side_stream()
+    x0, stream = images(B, 3, 8, 15), side_stream()
     settings = [Perturbed(0.4, [0], [1]), Perturbed(1.0, [0], [1]), Perturbed(1.0, [0], [2]), Perturbed(1.0, [], [2]), Perturbed(0.4, [0], [1])]
 
     def run(es, ef, pag):
-        return _run("ddpm", es.ctx, es, ef, x0, stream, switch=3, n=8, seed=25, noise="philox", guidance=pag)
+        return run_first_steps("ddpm", es, ef, x0, stream, switch=3, n=8, seed=25, noise="philox", guidance=pag)
 
     es, ef = _tiny_pair(max_batch=2 * B)
     got = [run(es, ef, p) for p in settings]
@@ -499,18 +472,17 @@ def test_perturbed_loop_reads_no_stale_workspace_bytes():
     path that reads the qkv tensor (tiny) and on the one that reads norm1 in fragment order (embed_dim 512)"""
     from duodiff_amd.engine import Perturbed
     for cfg_s, cfg_f, B, S, n in ((dict(TINY, depth=1), dict(TINY, depth=3), 6, 8, 6), (dict(QA512, depth=1), QA512, 2, 64, 2)):
-        x0, stream = _x0(B, 3, S, 17), side_stream()
+        x0, stream = images(B, 3, S, 17), side_stream()
         outs = []
         for poison in (False, True):
             es, ef, _ = engine_pair(cfg_s, cfg_f, (71, 72), 2 * B)
             ctx = es.ctx
-            with _flags(ctx, L.DD_DEV_FORCE_CHAINS):
-                if poison:
-                    with torch.cuda.stream(stream):
-                        for e in (es, ef):
-                            ctx.check(ctx.lib.dd_dev_poison_workspaces(ctx.handle, e.handle, stream.cuda_stream))
-                outs.append((_run("ddpm", ctx, es, ef, x0, stream, switch=1, n=n, seed=27, noise="philox", guidance=Perturbed(0.4, [0], [1, 2])),
-                             ctx.lib.dd_dev_last_sample_chains(ctx.handle)))
+            if poison:
+                with torch.cuda.stream(stream):
+                    for e in (es, ef):
+                        ctx.check(ctx.lib.dd_dev_poison_workspaces(ctx.handle, e.handle, stream.cuda_stream))
+            outs.append((run_first_steps("ddpm", es, ef, x0, stream, switch=1, n=n, seed=27, noise="philox", flags=L.DD_DEV_FORCE_CHAINS,
+                                         guidance=Perturbed(0.4, [0], [1, 2])), ctx.lib.dd_dev_last_sample_chains(ctx.handle)))
             del es, ef
         assert outs[0][1] == outs[1][1] == 2
         assert torch.isfinite(outs[0][0]).all() and not torch.equal(outs[0][0], x0)
@@ -531,18 +503,18 @@ def test_invalid_perturbed_calls_are_rejected_before_anything_is_enqueued():
     ec = cond.engine_model(2 * B)
     ee = Model(ctx, ModelParams.from_dict(TINY), 2 * B)
     ee.enable_early_exit("mlp_probe_per_layer")
-    x0 = _x0(B, 3, 8, 19)
-    y = torch.randint(0, 10, (B,), generator=torch.Generator().manual_seed(20)).cuda()
+    x0 = images(B, 3, 8, 19)
+    y = labels(B, 10, 20)
     stream = side_stream()
     # (first, late, (scale, first mask, late mask) or None, labels, message)
     cases = [(es, None, None, None, "null dd_pag"), (es, None, (float("inf"), 1, 0), None, "finite"), (es, None, (float("nan"), 1, 0), None, "finite"),
              (es, None, (0.4, 2, 0), None, "depth"), (es, ef, (0.4, 1, 8), None, "depth"), (es_small, None, (0.4, 1, 0), None, "max_batch"),
              (ee, None, (0.4, 1, 0), None, "early-exit"), (ec, None, (0.4, 1, 0), None, "without labels"), (es, None, (0.4, 1, 0), y, "with labels")]
     n0 = lib.dd_dev_graph_captures(ctx.handle)
-    for first, late, p, labels, msg in cases:
+    for first, late, p, given, msg in cases:
         ps = L.dd_pag(*p) if p else None
         pref = C.byref(ps) if ps else None
-        yp = labels.data_ptr() if labels is not None else None
+        yp = given.data_ptr() if given is not None else None
         for entry in ("sample", "affine", "multistep") if late else ("forward", "sample", "affine", "multistep"):
             x, eps, h = x0.clone(), torch.zeros_like(x0), torch.zeros_like(x0)
             with torch.cuda.stream(stream):

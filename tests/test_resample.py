@@ -7,7 +7,6 @@ loop draws them (DDIM and predict_noise DDPM as affine rows; a region, both kind
 stale bytes; the rejected calls; the fp32 engine against the numpy oracle; the product width; the command line.  Bit for bit unless a bound
 is named.
 """
-import contextlib
 import ctypes as C
 import subprocess
 import sys
@@ -20,11 +19,11 @@ from conftest import REPO, TINY
 from duodiff_amd import _lib as L
 from duodiff_amd.config import ModelParams, load_config
 from duodiff_amd.weights import synthetic_state_dict
-from loop_support import known_region, philox_z, philox_z2, side_stream, uvit
+from loop_support import NULL, dev_flags, known_region, labels, philox_z, philox_z2, philox_z3, region_inputs, run_loop, run_steps, side_stream
+from loop_support import tiny_model, uvit
 
 pytestmark = pytest.mark.gpu
 CELEBA_3 = REPO / "configs" / "uvit_celeba_3.yaml"
-NULL = 10
 
 
 def _plan(kind, **kw):
@@ -40,98 +39,18 @@ def _plan(kind, **kw):
     return p
 
 
-def _model(max_batch, seed=42, precision="bf16", **kw):
-    return uvit(dict(TINY, **kw), seed, precision, max_batch)[0].engine_model(max_batch)
-
-
-def _inputs(B, seed, S=8, mask="checker"):
-    """x_T, the known image and a mask: a checkerboard with some 0.5 entries (the images' masks differ), or a half image"""
-    g = torch.Generator().manual_seed(seed)
-    x, x0 = torch.randn(B, 3, S, S, generator=g), torch.randn(B, 3, S, S, generator=g)
-    if mask == "checker":
-        i = torch.arange(S)
-        m = ((i[:, None] + i[None, :]) % 2).float().expand(B, 1, S, S).clone()
-        m[:, :, 1::3, ::2] = 0.5
-        m[B - 1] = 1 - m[B - 1]
-    else:
-        m = torch.zeros(B, 1, S, S)
-        m[..., : S // 2] = 1
-    return x.cuda(), x0.cuda(), m.cuda()
-
-
-def _seeded(ctx, image_seeds, stream):
-    return ctx.image_seeds(image_seeds, stream) if image_seeds is not None else contextlib.nullcontext()
-
-
-def philox_z3(em, like, k, seed, stream, y=None):
-    """the z3 a jump draws at Philox counter k: a one-row walk call on x = 0 with the jump row (ja, jc) = (0, 1) returns 0 * 0 + 1 * z3"""
-    from duodiff_amd.engine import sample_affine_walk_loop
-    z = torch.zeros_like(like)
-    rows = dict(t=[500.0], a=[0.0], b=[0.0], c=[1.0], noise=[1], jump=[1])
-    with torch.cuda.stream(stream):
-        sample_affine_walk_loop(em.ctx, em, None, z, rows, y=y, seed=seed, counter_base=k, noise="philox", use_graph=False, stream=stream)
-    stream.synchronize()
-    return z
-
-
-def _walk(plan, first, x_in, stream, *, late=None, region=None, seed=5, use_graph=True, guidance=None, y=None, flags=0, cuts=(),
-          noise="philox", image_seeds=None, rows=None, switch_after=None):
-    """the device walk of the plan's rows (rows: others, e.g. without a late row), cut after the rows in cuts (the Philox counter carried)
+def _walk(plan, first, x_in, stream, *, rows=None, region=None, **kw):
+    """the device walk of the plan's rows (rows: others, e.g. without a late row; the region's (ka, kb) are the plan's); kw: run_loop's
     -> (x, chains of the last call)"""
-    from duodiff_amd import engine
-    ctx, tab = first.ctx, plan.rows if rows is None else rows
-    x = x_in.clone()
-    bounds = [0, *cuts, len(tab["t"])]
-    try:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
-        with torch.cuda.stream(stream), _seeded(ctx, image_seeds, stream):
-            for k0, k1 in zip(bounds[:-1], bounds[1:]):
-                engine.sample_affine_walk_loop(ctx, first, late, x, {k: v[k0:k1] for k, v in tab.items()},
-                                               region=None if region is None else known_region(plan, *region, k0, k1), guidance=guidance,
-                                               switch_after=None if switch_after is None else switch_after - k0, y=y, seed=seed,
-                                               counter_base=k0, noise=noise, use_graph=use_graph, stream=stream)
-        stream.synchronize()
-        chains = ctx.lib.dd_dev_last_sample_chains(ctx.handle)
-    finally:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
+    region = None if region is None else known_region(plan, *region)
+    x, _, chains = run_loop("walk", first, x_in, plan.rows if rows is None else rows, stream, region=region, **kw)
     return x, chains
 
 
-def _step_by_step(plan, first, x_in, stream, *, late=None, region=None, seed=5, guidance=None, y=None, image_seeds=None, sticky_late=False):
+def _step_by_step(plan, first, x_in, stream, **kw):
     """row by row: a step is forward[_guided | _autoguided] of the row's model + affine_step [+ known_blend], a jump is jump_step, with z,
-    z2 and z3 as the device loop draws them at the row's counter.  sticky_late: once the late model has run it keeps the steps (what one
-    switch_at could express)"""
-    from duodiff_amd import step_plan as sp
-    from duodiff_amd.engine import Autoguidance
-    ctx, tab = first.ctx, plan.rows
-    ka, kb = sp.known_rows(plan)
-    x, eps = x_in.clone(), torch.empty_like(x_in)
-    switched = False
-    with _seeded(ctx, image_seeds, stream):
-        for k in range(len(tab["t"])):
-            yz = y if first.mp.num_classes > 0 else None
-            if tab["jump"][k]:
-                z3 = philox_z3(first, x_in, k, seed, stream, yz)
-                with torch.cuda.stream(stream):
-                    ctx.jump_step(x, z3, tab["a"][k], tab["c"][k], out=x, stream=stream)
-                continue
-            switched = switched or bool(tab["late"][k])
-            m = late if tab["late"][k] or (sticky_late and switched) else first
-            z = philox_z(first, x_in, k, seed, stream, yz) if tab["noise"][k] else None
-            z2 = philox_z2(first, x_in, k, seed, stream, yz) if region is not None and kb[k] != 0 else None
-            t = float(tab["t"][k])
-            with torch.cuda.stream(stream):
-                if isinstance(guidance, Autoguidance) and m is not guidance.guide:
-                    m.forward_autoguided(x, t, y, guidance.guide, guidance.scale, out=eps, stream=stream)
-                elif guidance is not None and not isinstance(guidance, Autoguidance):
-                    m.forward_guided(x, t, y, guidance[0], guidance[1], out=eps, stream=stream)
-                else:
-                    m.forward(x, t, y, out=eps, stream=stream)
-                ctx.affine_step(x, eps, z, tab["a"][k], tab["b"][k], tab["c"][k], out=x, stream=stream)
-                if region is not None:
-                    ctx.known_blend(x, region[0], region[1], z2, ka[k], kb[k], out=x, stream=stream)
-    stream.synchronize()
-    return x
+    z2 and z3 as the device loop draws them at the row's counter"""
+    return run_steps("walk", first, x_in, plan, stream, **kw)[0]
 
 
 # ---- 1. the rule ----------------------------------------------------------------------------------------------------------------
@@ -188,16 +107,16 @@ def test_walk_equals_the_steps(kind, variant):
     B = 2 if what == "plain" or variant == "region" else 6
     guidance = y = seeds = None
     if what == "guided":
-        m = _model(2 * B, num_classes=11)
-        y = torch.randint(0, NULL, (B,), generator=torch.Generator().manual_seed(6)).cuda()
+        m = tiny_model(2 * B, num_classes=11)
+        y = labels(B, NULL, 6)
         guidance = (0.4, NULL)
     elif what == "autoguided":
-        m = _model(B)
-        guidance = Autoguidance(_model(B, seed=41, depth=1), 0.7)
+        m = tiny_model(B)
+        guidance = Autoguidance(tiny_model(B, seed=41, depth=1), 0.7)
     else:
-        m = _model(B)
+        m = tiny_model(B)
         seeds = [11, 2 ** 63 + 5, 11, 3, 2 ** 64 - 1, 0][:B] if what == "seeds" else None
-    x, x0, mask = _inputs(B, 33)
+    x, x0, mask = region_inputs(B, 33)
     region = (x0, mask) if reg or variant == "region" else None
     plan, st = _plan(kind), side_stream()
     flags = L.DD_DEV_FORCE_CHAINS if B == 6 else 0
@@ -216,8 +135,8 @@ def test_walk_equals_the_steps(kind, variant):
 # ---- 3. loop forms ----------------------------------------------------------------------------------------------------------------
 def test_graph_equals_eager_and_two_chains_equal_one():
     B = 6
-    m = _model(B)
-    x, x0, mask = _inputs(B, 34)
+    m = tiny_model(B)
+    x, x0, mask = region_inputs(B, 34)
     plan, st = _plan("ddim"), side_stream()
     xg, c1 = _walk(plan, m, x, st, region=(x0, mask), flags=L.DD_DEV_NO_CHAINS)
     xe, _ = _walk(plan, m, x, st, region=(x0, mask), use_graph=False)
@@ -236,8 +155,8 @@ def test_graph_equals_eager_and_two_chains_equal_one():
 def test_cut_walks_equal_the_uncut_walk(cuts):
     """cuts in front of a jump (3), behind it (4), and with a jump as a call's only row (3..4, 8..9); chains forced"""
     B = 6
-    m = _model(B)
-    x, x0, mask = _inputs(B, 35)
+    m = tiny_model(B)
+    x, x0, mask = region_inputs(B, 35)
     plan, st = _plan("ddpm"), side_stream()
     xu, _ = _walk(plan, m, x, st, region=(x0, mask), flags=L.DD_DEV_FORCE_CHAINS)
     xc, c = _walk(plan, m, x, st, region=(x0, mask), flags=L.DD_DEV_FORCE_CHAINS, cuts=cuts)
@@ -252,23 +171,19 @@ def test_walk_without_jumps_equals_sample_affine(with_region):
     from duodiff_amd import engine
     from duodiff_amd import step_plan as sp
     B = 6
-    first, late = _model(B, seed=41, depth=1), _model(B, seed=42)
-    x, x0, mask = _inputs(B, 36)
+    first, late = tiny_model(B, seed=41, depth=1), tiny_model(B, seed=42)
+    x, x0, mask = region_inputs(B, 36)
     plan, st = sp.step_plan(None, use_ddim=True, ddim_steps=7, ddim_eta=0.01), side_stream()
     r = plan.rows
     rows = dict(r, jump=np.zeros(6, np.int32))
     region = (x0, mask) if with_region else None
     xw, _ = _walk(plan, first, x, st, late=late, region=region, rows=rows, switch_after=2, flags=L.DD_DEV_FORCE_CHAINS)
     xa = x.clone()
-    try:
-        first.ctx.check(first.ctx.lib.dd_dev_set_flags(first.ctx.handle, L.DD_DEV_FORCE_CHAINS))
-        with torch.cuda.stream(st):
-            known = (known_region(plan, x0, mask),) if with_region else ()
-            (engine.sample_affine_region_loop if with_region else engine.sample_affine_loop)(
-                first.ctx, first, late, xa, *known, r["t"], r["a"], r["b"], r["c"], r["noise"], switch_after=2, seed=5, stream=st)
+    with dev_flags(first.ctx, L.DD_DEV_FORCE_CHAINS), torch.cuda.stream(st):
+        known = (known_region(plan, x0, mask),) if with_region else ()
+        (engine.sample_affine_region_loop if with_region else engine.sample_affine_loop)(
+            first.ctx, first, late, xa, *known, r["t"], r["a"], r["b"], r["c"], r["noise"], switch_after=2, seed=5, stream=st)
         st.synchronize()
-    finally:
-        first.ctx.check(first.ctx.lib.dd_dev_set_flags(first.ctx.handle, 0))
     assert torch.isfinite(xw).all() and torch.equal(xw, xa)
     # ... and a late row that says the same is the same
     rows["late"] = (np.arange(6) >= 2).astype(np.int32)
@@ -282,8 +197,8 @@ def test_a_jump_across_the_switch_returns_to_the_first_model():
     """t_switch = 500 on the 6-step DDIM grid: the late model has positions 4 and 5, the jump 5 -> 3 crosses the boundary upward and
     position 3 runs the first model again.  == the steps with the model chosen per row; != the run that stays on the late model."""
     B = 6
-    first, late = _model(B, seed=41, depth=1), _model(B, seed=42)
-    x, x0, mask = _inputs(B, 37)
+    first, late = tiny_model(B, seed=41, depth=1), tiny_model(B, seed=42)
+    x, x0, mask = region_inputs(B, 37)
     plan, st = _plan("ddim", has_late=True, t_switch=500), side_stream()
     assert plan.rows["late"].tolist() == [0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1, 1]
     for region in (None, (x0, mask)):
@@ -302,8 +217,8 @@ def test_z3_is_independent_of_z_and_z2():
     """z3 differs from z and from z2 at the same counter; over the 3 072 values of 8 counters |corr| <= 5 / sqrt(N) against each
     (independent normals: a standard deviation of 1 / sqrt(N)); mean and variance of z3 within 5 standard errors of (0, 1)."""
     B = 2
-    m = _model(B)
-    x, _, _ = _inputs(B, 38)
+    m = tiny_model(B)
+    x, _, _ = region_inputs(B, 38)
     st = side_stream()
     zs, z2s, z3s = [], [], []
     for k in range(8):
@@ -327,10 +242,10 @@ def test_second_call_replays_the_graphs():
     """A second call with other tensors of the same shape gives that call's own result and captures nothing: the step's graph and the
     jump's are replayed."""
     B = 2
-    m = _model(B)
+    m = tiny_model(B)
     plan, st = _plan("ddim"), side_stream()
-    x, x0a, ma = _inputs(B, 39)
-    xb, x0b, _ = _inputs(B, 40)
+    x, x0a, ma = region_inputs(B, 39)
+    xb, x0b, _ = region_inputs(B, 40)
     mb = (1 - ma).contiguous()
     lib, h = m.ctx.lib, m.ctx.handle
     n_before = lib.dd_dev_graph_captures(h)
@@ -348,11 +263,11 @@ def test_second_call_replays_the_graphs():
 def test_poisoned_workspaces_change_nothing():
     """Both chains' workspaces NaN-poisoned before the call, on fresh models: == the clean run (chains forced)."""
     B = 6
-    x, x0, mask = _inputs(B, 41)
+    x, x0, mask = region_inputs(B, 41)
     plan, st = _plan("ddim"), side_stream()
     outs = []
     for poison in (False, True):
-        m = _model(B, seed=71)
+        m = tiny_model(B, seed=71)
         if poison:
             m.ctx.check(m.ctx.lib.dd_dev_poison_workspaces(m.ctx.handle, m.handle, st.cuda_stream))
         outs.append(_walk(plan, m, x, st, region=(x0, mask), flags=L.DD_DEV_FORCE_CHAINS))
@@ -365,11 +280,11 @@ def test_poisoned_workspaces_change_nothing():
 def test_invalid_walk_calls_are_rejected_before_anything_is_enqueued():
     from duodiff_amd.engine import Model
     B = 2
-    m, guide = _model(B), _model(B, seed=41, depth=1)
+    m, guide = tiny_model(B), tiny_model(B, seed=41, depth=1)
     ctx, lib = m.ctx, m.ctx.lib
     ee = Model(ctx, ModelParams.from_dict(dict(TINY)), B)
     ee.enable_early_exit("mlp_probe_per_layer")
-    x_in, x0, mask = _inputs(B, 42)
+    x_in, x0, mask = region_inputs(B, 42)
     st = side_stream()
     plan = _plan("ddim")
     tab = {k: np.ascontiguousarray(v[2:5]) for k, v in plan.rows.items()}         # a step, the jump, a step
@@ -447,7 +362,7 @@ def test_fp32_engine_matches_the_oracle_over_the_walk():
     em = uvit(cfg, 61, "fp32", B)[0].engine_model(B)
     plan = _plan("ddim")
     ka, kb = sp.known_rows(plan)
-    xd, x0, mask = _inputs(B, 62, mask="half")
+    xd, x0, mask = region_inputs(B, 62, mask="half")
     st = side_stream()
     x, k0, mk = xd.cpu().numpy().astype(np.float64), x0.cpu().numpy().astype(np.float64), mask.cpu().numpy().astype(np.float64)
     r = plan.rows
@@ -477,7 +392,7 @@ def test_celeba_width_two_real_chains():
     from duodiff_amd import step_plan as sp
     B = 32
     m = uvit(load_config(CELEBA_3), 51, "bf16", B)[0].engine_model(B)
-    x, x0, mask = _inputs(B, 43, S=64)
+    x, x0, mask = region_inputs(B, 43, S=64)
     plan = sp.step_plan("predict_noise", use_ddim=True, ddim_steps=5, ddim_eta=0.01, resample_jump=2, resample_count=2)
     assert [mv[0] for mv in plan.moves] == ["S", "S", "S", "J", "S", "S", "S"]
     st = side_stream()

@@ -17,11 +17,10 @@ from duodiff_amd import step_plan, threshold_scan
 from duodiff_amd.config import ModelParams
 from duodiff_amd.weights import synthetic_ee_state_dict
 from kernel_support import F32
-from loop_support import side_stream, uvit
+from loop_support import dev_flags, ee_uvit, images, labels, side_stream, uvit
 from scan_support import _images, diffuse, exits_error
 from scan_support import _scan as _scan_loop
-from test_autoguidance import _flags, _x0
-from test_early_exit import CASES, _engine
+from test_early_exit import CASES
 
 pytestmark = pytest.mark.gpu
 
@@ -67,7 +66,7 @@ def _manual(em, x0, rows, y, seed, counter_base=0, seeds=None):
 def test_loop_equals_manual_composition_and_graph_equals_eager(tag):
     cfg, ctype = BY_TAG[tag]
     B = 5
-    m, mp = _engine(cfg, 11, ctype, "bf16", B)
+    m, mp = ee_uvit(cfg, 11, ctype, "bf16", B)
     em = m.engine_model(B)
     x0, y = _images(B, mp, 12)
     for par in ("predict_noise", "predict_original") if tag == "layer" else ("predict_noise",):
@@ -92,7 +91,7 @@ def test_loop_equals_manual_composition_and_graph_equals_eager(tag):
 def test_image_seeds_an_image_does_not_depend_on_its_batch():
     B = 6
     cfg, ctype = BY_TAG["timestep"]
-    m, mp = _engine(cfg, 13, ctype, "bf16", B)
+    m, mp = ee_uvit(cfg, 13, ctype, "bf16", B)
     em = m.engine_model(B)
     x0, _ = _images(B, mp, 14)
     rows = step_plan.scan_rows(GRID, "predict_noise")
@@ -111,24 +110,24 @@ def test_image_seeds_an_image_does_not_depend_on_its_batch():
 def test_two_chains_equal_one():
     B = 4
     cfg, ctype = BY_TAG["layer_timestep_cond"]
-    m, mp = _engine(cfg, 15, ctype, "bf16", B)
+    m, mp = ee_uvit(cfg, 15, ctype, "bf16", B)
     em = m.engine_model(B)
     ctx = em.ctx
     x0, y = _images(B, mp, 16)
     rows = step_plan.scan_rows(GRID, "predict_original")
     outs = {}
     for name, flags in (("chained", L.DD_DEV_FORCE_CHAINS), ("single", L.DD_DEV_NO_CHAINS)):
-        with _flags(ctx, flags):
+        with dev_flags(ctx, flags):
             outs[name] = (_scan(em, x0, rows, y, seed=5), ctx.lib.dd_dev_last_sample_chains(ctx.handle))
     assert outs["chained"][1] == 2 and outs["single"][1] == 1
     assert all(np.isfinite(o).all() for o in outs["single"][0])
     assert _same(outs["chained"][0], outs["single"][0]), "the two half-batch chains differ from the single chain"
     # chain 0 of two (2 images from image 0, rows of 4) is not the whole batch's captured step of 2 images
-    with _flags(ctx, L.DD_DEV_NO_CHAINS):
+    with dev_flags(ctx, L.DD_DEV_NO_CHAINS):
         half = _scan(em, x0[:2].contiguous(), rows, y[:2].contiguous(), seed=5)
-    with _flags(ctx, L.DD_DEV_FORCE_CHAINS):
+    with dev_flags(ctx, L.DD_DEV_FORCE_CHAINS):
         both = _scan(em, x0, rows, y, seed=5)
-    with _flags(ctx, L.DD_DEV_NO_CHAINS):
+    with dev_flags(ctx, L.DD_DEV_NO_CHAINS):
         assert _same(_scan(em, x0[:2].contiguous(), rows, y[:2].contiguous(), seed=5), half)
     assert _same(both, outs["single"][0]) and _same(half, tuple(b[:, :, :2] for b in both))
 
@@ -137,7 +136,7 @@ def test_graph_reuse_and_no_stale_graph():
     """other tensors of the same shape replay the captured step; another grid, target or counter base is honoured by the replay"""
     B = 3
     cfg, ctype = BY_TAG["timestep"]
-    m, mp = _engine(cfg, 17, ctype, "bf16", B)
+    m, mp = ee_uvit(cfg, 17, ctype, "bf16", B)
     em = m.engine_model(B)
     ctx = em.ctx
     rows = step_plan.scan_rows(GRID, "predict_noise")
@@ -166,11 +165,11 @@ def test_loops_around_a_scan_are_unchanged():
     from duodiff_amd.engine import sample_early_exit_loop
     B = 4
     cfg, ctype = BY_TAG["layer"]
-    m, mp = _engine(cfg, 21, ctype, "bf16", B)
+    m, mp = ee_uvit(cfg, 21, ctype, "bf16", B)
     em = m.engine_model(B)
     plain = uvit(TINY, 21, "bf16", B)[0].engine_model(B)
     ctx = em.ctx
-    xT = _x0(B, 3, 8, 22)
+    xT = images(B, 3, 8, 22)
     x0, _ = _images(B, mp, 23)
     rows = step_plan.scan_rows(GRID, "predict_noise")
     stream = side_stream()
@@ -202,9 +201,9 @@ def test_scan_reads_no_stale_workspace_bytes():
     rows = step_plan.scan_rows(GRID[:3], "predict_noise")
     outs = []
     for poison in (False, True):
-        em = _engine(cfg, 26, ctype, "bf16", B)[0].engine_model(B)
+        em = ee_uvit(cfg, 26, ctype, "bf16", B)[0].engine_model(B)
         ctx, stream = em.ctx, side_stream()
-        with _flags(ctx, L.DD_DEV_FORCE_CHAINS):
+        with dev_flags(ctx, L.DD_DEV_FORCE_CHAINS):
             if poison:
                 with torch.cuda.stream(stream):
                     ctx.check(ctx.lib.dd_dev_poison_workspaces(ctx.handle, em.handle, stream.cuda_stream))
@@ -218,7 +217,7 @@ def test_full_width_celeba_shape():
     """deediff_celeba's shape (D = 512, depth 13), synthetic weights, B = 2, bf16: the loop is its manual composition, and the backbone's
     exit is dd_scan_error of the plain U-ViT with the same backbone weights, bit for bit"""
     B, grid = 2, [999, 0]
-    m, mp = _engine(CELEBA_EE, 61, "mlp_probe_per_layer", "bf16", B)
+    m, mp = ee_uvit(CELEBA_EE, 61, "mlp_probe_per_layer", "bf16", B)
     em = m.engine_model(B)
     x0, _ = _images(B, mp, 62)
     rows = step_plan.scan_rows(grid, "predict_noise")
@@ -255,7 +254,7 @@ def test_against_the_oracle_fp32(tag):
         want_u.append(np.tanh(np.abs(d)).mean((2, 3, 4)))
         want_p.append(np.stack(cls))
     want_m, want_u, want_p = np.stack(want_m), np.stack(want_u), np.stack(want_p)
-    em = _engine(cfg, 31, ctype, "fp32", B)[0].engine_model(B)
+    em = ee_uvit(cfg, 31, ctype, "fp32", B)[0].engine_model(B)
     mse, target, pred = _scan(em, x0, rows, y, seed=55)
     delta = 1e-4
     r_m = ks.gate(mse, want_m, 2 * delta * np.sqrt(want_m) + delta ** 2, f"{tag}: mse against the oracle")
@@ -267,7 +266,7 @@ def test_against_the_oracle_fp32(tag):
 def test_the_samplers_selection_is_simulate_exits():
     B = 6
     cfg, ctype = BY_TAG["layer"]
-    m, mp = _engine(cfg, 35, ctype, "bf16", B)
+    m, mp = ee_uvit(cfg, 35, ctype, "bf16", B)
     em = m.engine_model(B)
     x0, _ = _images(B, mp, 36)
     rows = step_plan.scan_rows(GRID, "predict_noise")
@@ -286,13 +285,13 @@ def test_the_samplers_selection_is_simulate_exits():
 def test_invalid_calls_are_rejected_before_anything_is_enqueued():
     B = 4
     cfg, ctype = BY_TAG["layer"]
-    em = _engine(cfg, 41, ctype, "bf16", B)[0].engine_model(B)
-    ec = _engine(BY_TAG["attention_cond"][0], 42, "attention_probe", "bf16", B)[0].engine_model(B)
+    em = ee_uvit(cfg, 41, ctype, "bf16", B)[0].engine_model(B)
+    ec = ee_uvit(BY_TAG["attention_cond"][0], 42, "attention_probe", "bf16", B)[0].engine_model(B)
     plain = uvit(TINY, 43, "bf16", B)[0].engine_model(B)
     ctx, lib = em.ctx, em.ctx.lib
     depth = 3
     x0, _ = _images(B, ModelParams.from_dict(TINY), 43)
-    y = torch.randint(0, 10, (B,), generator=torch.Generator().manual_seed(44)).cuda()
+    y = labels(B, 10, 44)
     stream = side_stream()
     n = 3
     f = (C.c_float * n)(900.0, 600.0, 300.0)
@@ -354,12 +353,12 @@ def test_invalid_calls_are_rejected_before_anything_is_enqueued():
     assert all(bool((t == -7.0).all()) for t in o)
     # unsupported shapes: DD_ERR_UNSUPPORTED.  Model creation refuses in_chans outside 1..4 of the scan's range and images of more than 2^24
     # elements never fit a test, so those two branches are out of reach here; depth + 1 > 32 is not: dd_model_create takes any odd depth
-    deep = _engine(dict(TINY, depth=33), 45, "mlp_probe_per_layer", "bf16", B)[0].engine_model(B)
+    deep = ee_uvit(dict(TINY, depth=33), 45, "mlp_probe_per_layer", "bf16", B)[0].engine_model(B)
     o = [torch.full((n, 34, B), -7.0, device="cuda") for _ in range(3)]
     assert call(args(deep, mse_dev=o[0].data_ptr(), target_dev=o[1].data_ptr(), pred_dev=o[2].data_ptr())) == L.DD_ERR_UNSUPPORTED
     assert "at most 32 exits" in lib.dd_last_error(ctx.handle).decode()
     assert all(bool((t == -7.0).all()) for t in o), "depth 33: something was enqueued"
-    shallower = _engine(dict(TINY, depth=31), 46, "mlp_probe_per_layer", "bf16", B)[0].engine_model(B)      # 32 exits: the largest accepted
+    shallower = ee_uvit(dict(TINY, depth=31), 46, "mlp_probe_per_layer", "bf16", B)[0].engine_model(B)      # 32 exits: the largest accepted
     o = [torch.full((n, 32, B), -7.0, device="cuda"), torch.full((n, 32, B), -7.0, device="cuda"), torch.full((n, 31, B), -7.0, device="cuda")]
     n1 = lib.dd_dev_graph_captures(ctx.handle)
     assert n1 == n0, "a rejected call captured a graph"

@@ -16,11 +16,9 @@ from duodiff_amd import step_plan
 from duodiff_amd.config import ModelParams
 from duodiff_amd.weights import synthetic_state_dict
 from kernel_support import F32
-from loop_support import eps_rms_bound, side_stream, uvit
+from loop_support import QA512, TINY_COND, dev_flags, eps_rms_bound, images, labels, side_stream, uvit
 from scan_support import _images, diffuse, draw, error
 from scan_support import _scan as _scan_loop
-from test_autoguidance import _flags, _x0
-from test_pag import QA512, TINY_COND
 
 pytestmark = pytest.mark.gpu
 
@@ -91,17 +89,17 @@ def test_two_chains_equal_one():
     rows = step_plan.scan_rows(GRID, "predict_previous")
     outs = {}
     for name, flags in (("chained", L.DD_DEV_FORCE_CHAINS), ("single", L.DD_DEV_NO_CHAINS)):
-        with _flags(ctx, flags):
+        with dev_flags(ctx, flags):
             outs[name] = (_scan(em, x0, rows, seed=5), ctx.lib.dd_dev_last_sample_chains(ctx.handle))
     assert outs["chained"][1] == 2 and outs["single"][1] == 1
     assert np.isfinite(outs["single"][0]).all()
     assert np.array_equal(outs["chained"][0], outs["single"][0]), "the two half-batch chains differ from the single chain"
     # chain 0 of two (2 images from image 0, err rows of 4) is not the whole batch's captured step of 2 images
-    with _flags(ctx, L.DD_DEV_NO_CHAINS):
+    with dev_flags(ctx, L.DD_DEV_NO_CHAINS):
         half = _scan(em, x0[:2].contiguous(), rows, seed=5)
-    with _flags(ctx, L.DD_DEV_FORCE_CHAINS):
+    with dev_flags(ctx, L.DD_DEV_FORCE_CHAINS):
         both = _scan(em, x0, rows, seed=5)
-    with _flags(ctx, L.DD_DEV_NO_CHAINS):
+    with dev_flags(ctx, L.DD_DEV_NO_CHAINS):
         assert np.array_equal(_scan(em, x0[:2].contiguous(), rows, seed=5), half)
     assert np.array_equal(both, outs["single"][0]) and np.array_equal(half, both[:, :2])
 
@@ -135,7 +133,7 @@ def test_sampling_loops_around_a_scan_are_unchanged():
     B = 4
     em = uvit(TINY, 21, "bf16", B)[0].engine_model(B)
     ctx, mp = em.ctx, ModelParams.from_dict(TINY)
-    xT = _x0(B, 3, 8, 22)
+    xT = images(B, 3, 8, 22)
     x0, _ = _images(B, mp, 23)
     mask = (torch.rand(B, 1, 8, 8, generator=torch.Generator().manual_seed(24)) < 0.5).float().cuda()
     n = 5
@@ -166,7 +164,7 @@ def test_scan_reads_no_stale_workspace_bytes(case):
     for poison in (False, True):
         em = uvit(cfg, 26, "bf16", B)[0].engine_model(B)
         ctx, stream = em.ctx, side_stream()
-        with _flags(ctx, L.DD_DEV_FORCE_CHAINS):
+        with dev_flags(ctx, L.DD_DEV_FORCE_CHAINS):
             if poison:
                 with torch.cuda.stream(stream):
                     ctx.check(ctx.lib.dd_dev_poison_workspaces(ctx.handle, em.handle, stream.cuda_stream))
@@ -220,7 +218,7 @@ def test_invalid_calls_are_rejected_before_anything_is_enqueued():
     ee = Model(ctx, ModelParams.from_dict(TINY), B)
     ee.enable_early_exit("mlp_probe_per_layer")
     x0, _ = _images(B, ModelParams.from_dict(TINY), 43)
-    y = torch.randint(0, 10, (B,), generator=torch.Generator().manual_seed(44)).cuda()
+    y = labels(B, 10, 44)
     stream = side_stream()
     n = 3
     f = (C.c_float * n)(900.0, 600.0, 300.0)

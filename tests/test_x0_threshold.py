@@ -13,7 +13,7 @@ from duodiff_amd import _lib as L
 from duodiff_amd.config import ModelParams
 from duodiff_amd.weights import synthetic_state_dict
 from kernel_support import step_history, step_table
-from loop_support import cli_argv, known_region, philox_z, philox_z2, side_stream, uvit
+from loop_support import NULL, cli_argv, images, labels, run_loop, run_steps, side_stream, tiny_model, uvit
 
 gpu = pytest.mark.gpu
 CELEBA, IMAGENET256 = REPO / "configs" / "uvit_celeba.yaml", REPO / "configs" / "uvit_imagenet256.yaml"
@@ -364,13 +364,8 @@ def test_threshold_step_images_are_independent_canaries_and_aliasing():
 
 
 # ---- GPU: the loop ----------------------------------------------------------------------------------------------------------------
-NULL = 10
-
-
 def _model(S=8, cond=False, precision="bf16", depth=3, seed=42, max_batch=12):
-    cfg = dict(TINY, img_size=S, depth=depth, num_classes=11 if cond else TINY.get("num_classes", -1))
-    m, _ = uvit(cfg, seed, precision, max_batch)
-    return m.engine_model(max_batch)
+    return tiny_model(max_batch, seed, precision, img_size=S, depth=depth, **(dict(num_classes=11) if cond else {}))
 
 
 def _plan(sampler_kind, par="predict_noise"):
@@ -378,62 +373,6 @@ def _plan(sampler_kind, par="predict_noise"):
     kw = {"ode": dict(solver="dpmsolver++", solver_steps=6), "sde": dict(solver="sde-dpmsolver++", solver_steps=6),
           "ddim": dict(use_ddim=True, ddim_steps=7, ddim_eta=0.02), "ddpm": dict(num_steps=12)}[sampler_kind]
     return sampler.step_plan(par, threshold=_thr("static"), **kw)
-
-
-def _loop(em, x_in, plan, thr, stream, *, region=None, seed=5, use_graph=True, guidance=None, y=None, flags=0, cuts=(), h0=None):
-    """the thresholded device loop (thr None: the plain multistep loop on the same rows), cut after the steps in cuts"""
-    from duodiff_amd import engine
-    ctx, tab = em.ctx, plan.rows
-    x, h = x_in.clone(), torch.zeros_like(x_in) if h0 is None else h0.clone()
-    bounds = [0, *cuts, len(tab["t"])]
-    try:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, flags))
-        with torch.cuda.stream(stream):
-            for k0, k1 in zip(bounds[:-1], bounds[1:]):
-                seg = {k: v[k0:k1] for k, v in tab.items()}
-                kw = dict(y=y, seed=seed, counter_base=k0, noise="philox", use_graph=use_graph, stream=stream, guidance=guidance)
-                reg = None if region is None else known_region(plan, *region, k0, k1)
-                if thr is not None:
-                    engine.sample_multistep_threshold_loop(ctx, em, None, x, h, seg, thr, region=reg, **kw)
-                elif reg is not None:
-                    engine.sample_multistep_region_loop(ctx, em, None, x, reg, h, seg, **kw)
-                else:
-                    engine.sample_multistep_loop(ctx, em, None, x, h, seg, **kw)
-        stream.synchronize()
-        chains = ctx.lib.dd_dev_last_sample_chains(ctx.handle)
-    finally:
-        ctx.check(ctx.lib.dd_dev_set_flags(ctx.handle, 0))
-    return x, h, chains
-
-
-def _composition(em, x_in, plan, thr, stream, *, region=None, seed=5, guidance=None, y=None):
-    """dd_forward[_guided | _autoguided], dd_threshold_step, dd_known_blend, fed the loop's z and z2"""
-    from duodiff_amd import sampler
-    from duodiff_amd.engine import Autoguidance
-    ctx, tab = em.ctx, plan.rows
-    ka, kb = sampler.known_rows(plan)
-    x, h, eps = x_in.clone(), torch.zeros_like(x_in), torch.empty_like(x_in)
-    yz = y if em.mp.num_classes > 0 else None
-    for k in range(len(tab["t"])):
-        t = float(tab["t"][k])
-        z = philox_z(em, x_in, k, seed, stream, yz, t=t) if tab["noise"][k] else None
-        z2 = philox_z2(em, x_in, k, seed, stream, yz) if region is not None and kb[k] != 0 else None
-        with torch.cuda.stream(stream):
-            if isinstance(guidance, Autoguidance):
-                em.forward_autoguided(x, t, y, guidance.guide, guidance.scale, out=eps, stream=stream)
-            elif guidance is not None:
-                em.forward_guided(x, t, y, guidance[0], guidance[1], out=eps, stream=stream)
-            else:
-                em.forward(x, t, y, out=eps, stream=stream)
-            ctx.threshold_step(x, eps, z, h, thr, *(tab[c][k] for c in "abcdpq"), tab["hist"][k], out=x, stream=stream)
-            if region is not None:
-                ctx.known_blend(x, region[0], region[1], z2, ka[k], kb[k], out=x, stream=stream)
-    stream.synchronize()
-    return x, h
-
-
-def _start(B, S, seed=2, scale=1.0):
-    return (torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(seed)) * scale).cuda()
 
 
 def _known(B, S, seed=3):
@@ -457,20 +396,20 @@ def test_loop_equals_the_composition_of_its_parts(kind, S, prec, mode, mods):
     em = _model(S, cond=mods == "cfg", precision=prec)
     kw = {}
     if mods == "cfg":
-        kw = dict(guidance=(1.7, NULL), y=torch.randint(0, 10, (B,), generator=torch.Generator().manual_seed(4)).cuda())
+        kw = dict(guidance=(1.7, NULL), y=labels(B, 10, 4))
     elif mods == "autoguided":
         kw = dict(guidance=Autoguidance(_model(S, precision=prec, depth=1, seed=41), 1.3))
     elif mods == "known":
         kw = dict(region=_known(B, S))
     plan, thr, st = _plan(kind), _thr(mode, **THR[mode]), side_stream()
-    x_in = _start(B, S)
-    xc, hc = _composition(em, x_in, plan, thr, st, **kw)
+    x_in = images(B, 3, S, 2)
+    xc, hc = run_steps("threshold", em, x_in, plan, st, threshold=thr, **kw)
     assert torch.isfinite(xc).all() and not torch.equal(xc, x_in)
     for name, args in (("graph", dict(flags=L.DD_DEV_NO_CHAINS)), ("eager", dict(use_graph=False)), ("two chains", dict(flags=L.DD_DEV_FORCE_CHAINS))):
-        x, h, chains = _loop(em, x_in, plan, thr, st, **kw, **args)
+        x, h, chains = run_loop("threshold", em, x_in, plan, st, threshold=thr, **kw, **args)
         assert chains == (2 if name == "two chains" else 1), (name, chains)
         assert torch.equal(x, xc) and torch.equal(h, hc), f"{name}: the loop differs from the composition"
-    plain, _, _ = _loop(em, x_in, plan, None, st, **kw)
+    plain, _, _ = run_loop("multistep", em, x_in, plan, st, **kw)
     assert not torch.equal(plain, xc), "thresholding changed nothing: the test does not exercise it"
 
 
@@ -479,10 +418,10 @@ def test_loop_equals_the_composition_of_its_parts(kind, S, prec, mode, mods):
 def test_cut_loop_resumes_to_the_bits_of_the_uncut_loop(kind):
     B, S = 6, 8
     em, st = _model(S), side_stream()
-    plan, thr, x_in = _plan(kind), _thr("dynamic", quantile=0.995), _start(B, S)
+    plan, thr, x_in = _plan(kind), _thr("dynamic", quantile=0.995), images(B, 3, S, 2)
     n = len(plan.rows["t"])
-    whole = _loop(em, x_in, plan, thr, st, flags=L.DD_DEV_FORCE_CHAINS, region=_known(B, S))
-    cut = _loop(em, x_in, plan, thr, st, flags=L.DD_DEV_FORCE_CHAINS, region=_known(B, S), cuts=(1, n // 2))
+    whole = run_loop("threshold", em, x_in, plan, st, threshold=thr, flags=L.DD_DEV_FORCE_CHAINS, region=_known(B, S))
+    cut = run_loop("threshold", em, x_in, plan, st, threshold=thr, flags=L.DD_DEV_FORCE_CHAINS, region=_known(B, S), cuts=(1, n // 2))
     assert torch.equal(whole[0], cut[0]) and torch.equal(whole[1], cut[1])
 
 
@@ -494,13 +433,13 @@ def test_graph_keys_separate_thresholded_and_plain_calls():
     from duodiff_amd.engine import sample_loop
     B, S = 6, 8
     em, st = _model(S), side_stream()
-    plan, x_in = _plan("sde"), _start(B, S)
+    plan, x_in = _plan("sde"), images(B, 3, S, 2)
     variants = [None, _thr("dynamic", quantile=0.995), _thr("dynamic", quantile=0.9), _thr("dynamic", quantile=0.995, s_max=2.0),
                 _thr("static", range=1.0), _thr("static", range=0.5)]
     alone = []
     for thr in variants:
         fresh = _model(S)
-        alone.append(_loop(fresh, x_in, plan, thr, side_stream())[0])
+        alone.append(run_loop("threshold", fresh, x_in, plan, side_stream(), threshold=thr)[0])
         del fresh
     assert len({a.cpu().numpy().tobytes() for a in alone}) == len(variants)
 
@@ -513,15 +452,15 @@ def test_graph_keys_separate_thresholded_and_plain_calls():
     before = ddpm(em)
     for _ in range(2):
         for thr, want in zip(variants, alone):
-            assert torch.equal(_loop(em, x_in, plan, thr, st)[0], want), thr
+            assert torch.equal(run_loop("threshold", em, x_in, plan, st, threshold=thr)[0], want), thr
     assert torch.equal(ddpm(em), before), "a thresholded call changed a following dd_sample"
     # one step, nothing clipped: unfolded rows through the thresholded loop vs the folded plain loop
     ode = _plan("ode")
     one = sampler.StepPlan("multistep", {k: v[:1] for k, v in ode.rows.items()}, [False], None, ode.lands[:1])
     folded = sampler.step_plan("predict_noise", solver="dpmsolver++", solver_steps=6)
     fold1 = sampler.StepPlan("multistep", {k: v[:1] for k, v in folded.rows.items()}, [False], None, folded.lands[:1])
-    got = _loop(em, x_in, one, _thr("static", range=3e38), st)[0].cpu().numpy()
-    ref = _loop(em, x_in, fold1, None, st)[0].cpu().numpy()
+    got = run_loop("threshold", em, x_in, one, st, threshold=_thr("static", range=3e38))[0].cpu().numpy()
+    ref = run_loop("multistep", em, x_in, fold1, st)[0].cpu().numpy()
     eps = torch.empty_like(x_in)
     em.forward(x_in, float(ode.rows["t"][0]), None, out=eps)
     torch.cuda.synchronize()
@@ -551,7 +490,7 @@ def test_invalid_threshold_calls_are_rejected_before_anything_is_enqueued():
              ("early_exit", ok, "early-exit"), ("h_dev", ok, "h_dev"), ("both", ok, "exclusive")]
     for what, t, msg in cases:
         model = ee if what == "early_exit" else em
-        x0 = _start(B, 8)
+        x0 = images(B, 3, 8, 2)
         x, h = x0.clone(), torch.zeros_like(x0)
         a = L.dd_multistep_sample_args()
         a.first, a.late, a.n_steps, a.switch_after = model.handle, None, 3, 3
@@ -635,16 +574,16 @@ def test_no_kernel_of_a_thresholded_call_depends_on_stale_bytes():
     """Both chains' workspaces and the context's model-output scratch are filled with NaN bytes on the launch stream before a model's
     first thresholded call (h NaN-filled too: step 0 has no history); the samples equal those of a fresh model, bit for bit."""
     B, S = 6, 8
-    plan, thr, x_in, st = _plan("sde"), _thr("dynamic", quantile=0.995), _start(B, S), side_stream()
+    plan, thr, x_in, st = _plan("sde"), _thr("dynamic", quantile=0.995), images(B, 3, S, 2), side_stream()
     outs = []
     for poison in (False, True):
         em = _model(S, cond=True, seed=73)
-        y = torch.randint(0, 10, (B,), generator=torch.Generator().manual_seed(15)).cuda()
+        y = labels(B, 10, 15)
         h0 = None
         if poison:
             em.ctx.check(em.ctx.lib.dd_dev_poison_workspaces(em.ctx.handle, em.handle, st.cuda_stream))
             h0 = torch.full_like(x_in, float("nan"))
-        outs.append(_loop(em, x_in, plan, thr, st, flags=L.DD_DEV_FORCE_CHAINS, guidance=(1.5, NULL), y=y, region=_known(B, S), h0=h0))
+        outs.append(run_loop("threshold", em, x_in, plan, st, threshold=thr, flags=L.DD_DEV_FORCE_CHAINS, guidance=(1.5, NULL), y=y, region=_known(B, S), h0=h0))
         del em
     assert outs[0][2] == outs[1][2] == 2
     assert torch.isfinite(outs[0][0]).all() and torch.isfinite(outs[1][1]).all()

@@ -1096,30 +1096,38 @@ __global__ void __launch_bounds__(256) v_copy_kernel(const T* __restrict__ qkv, 
     *reinterpret_cast<f32x4*>(out + idx * EPC) = *reinterpret_cast<const f32x4*>(src);
 }
 
+template <typename T>
+constexpr size_t attention_lds() { return (size_t)kLP * AttnLayout<T>::kRowK + (size_t)AttnLayout<T>::kVBytes + kPartBytes; }
+template <typename T>
+constexpr size_t attention_long_lds() { return (size_t)kLP * AttnLayout<T>::kRowK + (size_t)AttnLayout<T>::kVBytes; }
+
+// attention_kernel<T, NKT> keyed by (sizeof(T), NKT), attention_long_kernel<T> by sizeof(T); a table per operand type (the launchers are typed by T)
+template <typename T>
+const KernelEntry<const T*, T*, int, int, int, int, int> kAttention[2] = {
+    entry<attention_kernel<T, 9>>({(int)sizeof(T), 9}, 256, attention_lds<T>()),
+    entry<attention_kernel<T, 0>>({(int)sizeof(T), 0}, 256, attention_lds<T>()),
+};
+template <typename T>
+const KernelEntry<const T*, T*, int, int, int, int> kAttentionLong[1] = {entry<attention_long_kernel<T>>({(int)sizeof(T)}, 256, attention_long_lds<T>())};
+const KernelFamily kAttentionFamilies[] = {family<kAttention<bf16_t>>("attention_kernel"), family<kAttention<float>>("attention_kernel"),
+                                           family<kAttentionLong<bf16_t>>("attention_long_kernel"), family<kAttentionLong<float>>("attention_long_kernel")};
+
 }  // namespace
 
 template <typename T>
 hipError_t launch_attention(const T* qkv, T* out, int B, int L, int H, int D, hipStream_t s) {
     if (L > kLP || D != H * kHD || L < 1) return hipErrorInvalidValue;
-    using Lay = AttnLayout<T>;
-    const size_t lds = (size_t)kLP * Lay::kRowK + (size_t)Lay::kVBytes + kPartBytes;
-    const int Lp = make_head_major(L, H).Lp;
     // the <T, 9> specialisation assumes L = 256 + 1 or 2 (one or two real keys / queries in the 9th tile): every shipped config
-    if (L == 257 || L == 258) hipLaunchKernelGGL((attention_kernel<T, 9>), dim3(B * H), dim3(256), lds, s, qkv, out, B, L, H, D, Lp);
-    else hipLaunchKernelGGL((attention_kernel<T, 0>), dim3(B * H), dim3(256), lds, s, qkv, out, B, L, H, D, Lp);
-    return hipGetLastError();
+    const int nkt = L == 257 || L == 258 ? 9 : 0;
+    return launch(find(kAttention<T>, (int)sizeof(T), nkt), dim3(B * H), attention_lds<T>(), s, qkv, out, B, L, H, D, make_head_major(L, H).Lp);
 }
-
-template <typename T>
-static constexpr size_t attention_long_lds() { return (size_t)kLP * AttnLayout<T>::kRowK + (size_t)AttnLayout<T>::kVBytes; }
 
 template <typename T>
 hipError_t launch_attention_long(const T* qkv, T* out, int B, int L, int H, int D, hipStream_t s) {
     if (!qkv || !out || B < 1 || L < 1 || L > kMaxLongL || H < 1 || D != H * kHD) return hipErrorInvalidValue;
     const long long grid = (long long)B * H * ((L + kLongSlab - 1) / kLongSlab);
     if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((attention_long_kernel<T>), dim3((unsigned)grid), dim3(256), attention_long_lds<T>(), s, qkv, out, L, H, D, make_head_major(L, H).Lp);
-    return hipGetLastError();
+    return launch(find(kAttentionLong<T>, (int)sizeof(T)), dim3((unsigned)grid), attention_long_lds<T>(), s, qkv, out, L, H, D, make_head_major(L, H).Lp);
 }
 
 // attn.qkv weight [3 D, D] (nn.Linear layout) -> per head the weight blocks the kernel streams, in stream order: [slice q of the k range:
@@ -1135,23 +1143,33 @@ void qkv_attention_pack(int D, int H, const float* w, unsigned short (*to_bf16)(
                                   img + ((((size_t)hh * NS + q) * 6 + j) * kQaKQ + ks) * 512);
 }
 
-bool qkv_attention_supported(int D, int H, int L, int extras) {
-    return (D == 512 || D == 768 || D == 1024) && H * kHD == D && (extras == 1 || extras == 2) && L == 256 + extras;
-}
+namespace {
+constexpr size_t v_identity_lds(int D) { return (size_t)2 * (D / 16) * 1024; }     // 64 rows of h in fragment order
+constexpr size_t qkv_attention_lds() { return (size_t)kLP * AttnLayout<bf16_t>::kRowK + AttnLayout<bf16_t>::kVBytes + kQaAuxBytes + kQaRing; }
 
-static size_t v_identity_lds(int D) { return (size_t)2 * (D / 16) * 1024; }     // 64 rows of h in fragment order
-static size_t qkv_attention_lds() { return (size_t)kLP * AttnLayout<bf16_t>::kRowK + AttnLayout<bf16_t>::kVBytes + kQaAuxBytes + kQaRing; }
+// qkv_attention_kernel<D> and v_identity_kernel<D>, keyed by D
+const KernelEntry<QkvAttnArgs> kQkvAttention[] = {
+    entry<qkv_attention_kernel<512>>({512}, 512, qkv_attention_lds()),
+    entry<qkv_attention_kernel<768>>({768}, 512, qkv_attention_lds()),
+    entry<qkv_attention_kernel<1024>>({1024}, 512, qkv_attention_lds()),
+};
+const KernelEntry<VIdentityArgs> kVIdentity[] = {
+    entry<v_identity_kernel<512>>({512}, 512, v_identity_lds(512)),
+    entry<v_identity_kernel<768>>({768}, 512, v_identity_lds(768)),
+    entry<v_identity_kernel<1024>>({1024}, 512, v_identity_lds(1024)),
+};
+const KernelFamily kQkvAttentionFamilies[] = {family<kQkvAttention>("qkv_attention_kernel"), family<kVIdentity>("v_identity_kernel")};
+}  // namespace
+
+bool qkv_attention_supported(int D, int H, int L, int extras) {
+    return find(kQkvAttention, D) && H * kHD == D && (extras == 1 || extras == 2) && L == 256 + extras;
+}
 
 hipError_t launch_qkv_attention(const bf16_t* h, const bf16_t* wimg, const float* bias, const bf16_t* hx, const float* xres,
                                 const float* ln_g, const float* ln_b, bf16_t* out, int B, int L, int H, int D, int extras, hipStream_t s, bf16_t* out_frag) {
     if (!qkv_attention_supported(D, H, L, extras) || !h || !wimg || (!hx && (!xres || !ln_g || !ln_b)) || !out || B < 1) return hipErrorInvalidValue;
     const QkvAttnArgs a{h, wimg, bias, hx, xres, ln_g, ln_b, out, B, L, H, make_head_major(L, H).Lp, extras, out_frag};
-    switch (D) {
-        case 512: hipLaunchKernelGGL((qkv_attention_kernel<512>), dim3(B * H), dim3(512), qkv_attention_lds(), s, a); break;
-        case 768: hipLaunchKernelGGL((qkv_attention_kernel<768>), dim3(B * H), dim3(512), qkv_attention_lds(), s, a); break;
-        default: hipLaunchKernelGGL((qkv_attention_kernel<1024>), dim3(B * H), dim3(512), qkv_attention_lds(), s, a); break;
-    }
-    return hipGetLastError();
+    return launch(find(kQkvAttention, D), dim3(B * H), qkv_attention_lds(), s, a);
 }
 
 // identity attention of images whose attention map is the identity (v_identity_kernel): launch_qkv_attention's operands without the hx mode
@@ -1159,13 +1177,7 @@ hipError_t launch_v_identity(const bf16_t* h, const bf16_t* wimg, const float* b
                              bf16_t* out, int B, int L, int H, int D, int extras, hipStream_t s) {
     if (!qkv_attention_supported(D, H, L, extras) || !h || !wimg || !xres || !ln_g || !ln_b || !out || B < 1) return hipErrorInvalidValue;
     const VIdentityArgs a{h, wimg, bias, xres, ln_g, ln_b, out, B, L, extras};
-    const dim3 grid(B * 4 + (B * extras + 63) / 64);
-    switch (D) {
-        case 512: hipLaunchKernelGGL((v_identity_kernel<512>), grid, dim3(512), v_identity_lds(512), s, a); break;
-        case 768: hipLaunchKernelGGL((v_identity_kernel<768>), grid, dim3(512), v_identity_lds(768), s, a); break;
-        default: hipLaunchKernelGGL((v_identity_kernel<1024>), grid, dim3(512), v_identity_lds(1024), s, a); break;
-    }
-    return hipGetLastError();
+    return launch(find(kVIdentity, D), dim3(B * 4 + (B * extras + 63) / 64), v_identity_lds(D), s, a);
 }
 
 // ... from the head-major qkv tensor (make_head_major(L, H)): out [B L, D] rows = the v rows
@@ -1175,23 +1187,6 @@ hipError_t launch_v_copy(const T* qkv, T* out, int B, int L, int H, int D, hipSt
     const long long n_chunks = (long long)B * L * D / (16 / (int)sizeof(T));
     hipLaunchKernelGGL((v_copy_kernel<T>), dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, s, qkv, out, n_chunks, L, H, make_head_major(L, H).Lp);
     return hipGetLastError();
-}
-
-hipError_t init_attention_kernels() {
-    for (const void* f : {(const void*)qkv_attention_kernel<512>, (const void*)qkv_attention_kernel<768>, (const void*)qkv_attention_kernel<1024>})
-        if (hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)qkv_attention_lds()); e != hipSuccess) return e;
-    if (hipError_t e = hipFuncSetAttribute((const void*)v_identity_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v_identity_lds(512)); e != hipSuccess) return e;
-    if (hipError_t e = hipFuncSetAttribute((const void*)v_identity_kernel<768>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v_identity_lds(768)); e != hipSuccess) return e;
-    if (hipError_t e = hipFuncSetAttribute((const void*)v_identity_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v_identity_lds(1024)); e != hipSuccess) return e;
-    const int lb = kLP * AttnLayout<bf16_t>::kRowK + AttnLayout<bf16_t>::kVBytes + kPartBytes;
-    const int lf = kLP * AttnLayout<float>::kRowK + AttnLayout<float>::kVBytes + kPartBytes;
-    hipError_t e = hipFuncSetAttribute((const void*)attention_kernel<bf16_t, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, lb);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attention_kernel<bf16_t, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lb);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attention_kernel<float, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, lf);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attention_kernel<float, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lf);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attention_long_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attention_long_lds<bf16_t>());
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attention_long_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attention_long_lds<float>());
-    return e;
 }
 
 template hipError_t launch_attention<bf16_t>(const bf16_t*, bf16_t*, int, int, int, int, hipStream_t);

@@ -5,6 +5,7 @@
 #include "../../include/duodiff_dev.h"
 #include "engine_state.h"
 
+#include <cstdio>
 #include <cstring>
 #include <new>
 #include <string>
@@ -47,8 +48,7 @@ int dd_ctx_create(int device, dd_ctx** out) {
               hipEventCreateWithFlags(&c->ev_ee_join, hipEventDisableTiming) == hipSuccess;
     for (int i = 0; ok && i < 3; ++i) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
     ok = ok && hipStreamSynchronize(nullptr) == hipSuccess;     // the null-stream memsets above, before any caller stream touches the state
-    ok = ok && init_gemm_kernels() == hipSuccess && init_attention_kernels() == hipSuccess &&
-         init_rowops_kernels() == hipSuccess && init_mlp_fused_kernels() == hipSuccess && init_rowlin_kernels() == hipSuccess;
+    ok = ok && init_kernel_tables() == hipSuccess;
     if (!ok) { dd_ctx_destroy(c); return DD_ERR_HIP; }
     *out = c;
     return DD_OK;
@@ -236,6 +236,37 @@ int dd_bench_gemm(dd_ctx* c, dd_model* m, int B, int iters, void* stream, float*
 int dd_plan_rows(int M, int N, int K, int num_cus, int* q_out, int* e_out) {
     if (!q_out || !e_out) return DD_ERR_INVALID;
     return plan_rows_256(M, N, K, num_cus, q_out, e_out) ? DD_OK : DD_ERR_UNSUPPORTED;
+}
+
+int dd_dev_kernel_table(int index, char family[32], int key[4], int* block, int* lds_max) {
+    if (index < 0 || !family || !key || !block || !lds_max) return DD_ERR_INVALID;
+    for (const KernelFamily& f : kernel_families())
+        for (int i = 0; const KernelInfo* e = f.at(i); ++i, --index)
+            if (index == 0) {
+                std::snprintf(family, 32, "%s", f.name);
+                std::memcpy(key, e->key.data(), sizeof(e->key));
+                *block = e->block;
+                *lds_max = e->lds_max;
+                return 0;
+            }
+    return 1;
+}
+
+int dd_dev_kernel_supported(int predicate, const int args[6]) {
+    if (!args) return DD_ERR_INVALID;
+    EmbedArgs ea{};
+    ea.P = args[0]; ea.C = args[1]; ea.D = args[2]; ea.S = args[3]; ea.L = args[4]; ea.extras = args[5];
+    size_t lds = 0;
+    switch (predicate) {
+        case DD_DEV_SUP_MLP_FUSED: return mlp_fused_supported(args[0], args[1]);
+        case DD_DEV_SUP_HEAD_DEC: return head_dec_supported(args[0], args[1]);
+        case DD_DEV_SUP_HEAD_DEC_PROBE: return head_dec_probe_supported(args[0]);
+        case DD_DEV_SUP_QKV_ATTENTION: return qkv_attention_supported(args[0], args[1], args[2], args[3]);
+        case DD_DEV_SUP_ROWLIN: return rowlin_supported(args[0], args[1]);
+        case DD_DEV_SUP_EMBED_MFMA: return embed_mfma_ok(ea, lds);
+        case DD_DEV_SUP_EMBED_LN: return embed_ln_supported(ea);
+    }
+    return DD_ERR_INVALID;
 }
 
 int dd_set_num_cus(dd_ctx* c, int n) {

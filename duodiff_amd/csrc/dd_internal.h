@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernel_table.h"
+
 namespace dd {
 
 typedef unsigned short bf16_t;  // raw bf16 bits
@@ -125,7 +127,6 @@ bool gemm_prefers_128(int M, int N, int K, int K1, int num_cus);   // the 256 x 
 bool gemm_splitk_supported(int M, int N, int K, int K1, int splits);
 hipError_t launch_gemm_splitk(const GemmArgs<bf16_t>& a, hipStream_t s, int num_cus);
 int device_num_cus();
-hipError_t init_gemm_kernels();
 
 // ---- fused MLP (mlp_fused.hip): x += fc2(gelu(fc1(h) + b1)) + b2 in one launch
 struct MlpFusedArgs {
@@ -222,7 +223,6 @@ void mlp_fused_pack(int D, int hidden, const float* w1, const float* b1, const f
                     unsigned short (*to_bf16)(float), unsigned short* img, float* b1p);
 hipError_t launch_mlp_fused(const MlpFusedArgs& a, int D, hipStream_t s);
 hipError_t launch_mlp_reduce(const MlpFusedArgs& a, int D, hipStream_t s);
-hipError_t init_mlp_fused_kernels();
 
 // ---- row-resident Linear + bias + residual + LayerNorm for embed_dim 768 (rowlin.hip): x += A . W^T + b ; LayerNorm(x) g + beta as bf16
 struct RowLinArgs {
@@ -248,7 +248,6 @@ void rowlin_pack(int K, const float* w, unsigned short (*to_bf16)(float), unsign
 void rowlin_plan(int B, int n_patches, int extras, int seq_len, int K, RowLinArgs& a);
 size_t rowlin_partial_bytes(int max_batch, int extras, int K);
 hipError_t launch_rowlin(const RowLinArgs& a, hipStream_t s);
-hipError_t init_rowlin_kernels();
 
 struct EmbedArgs {
     const float* x_img;      // [B,C,S,S]
@@ -266,6 +265,7 @@ struct EmbedArgs {
     const float* ln_b = nullptr;
     bf16_t* ln_frag = nullptr;     // MFMA fragment order (launch_layernorm_frag's `frag`)
 };
+bool embed_mfma_ok(const EmbedArgs& a, size_t& lds);     // the MFMA kernel takes the shape; lds = the bytes its launch asks for
 bool embed_ln_supported(const EmbedArgs& a);
 
 // finishes a split-K Linear (launch_gemm_splitk) and runs the LayerNorm behind it: rowops.hip reduce_ln_kernel
@@ -310,7 +310,6 @@ hipError_t launch_attention(const T* qkv, T* out, int B, int L, int H, int D, hi
 constexpr int kMaxLongL = 4098;
 template <typename T>
 hipError_t launch_attention_long(const T* qkv, T* out, int B, int L, int H, int D, hipStream_t s);
-hipError_t init_attention_kernels();
 // attn.qkv + attention in one launch (attention.hip qkv_attention_kernel): h = norm1 of the patch rows in fragment order
 // (MlpFusedArgs::ln_out_frag); the extra-token rows: hx = norm1 row-major [B L, D], or hx = nullptr and xres / ln_g / ln_b = the fp32
 // residual stream and this block's norm1 parameters (the kernel normalises the rows itself); wimg from qkv_attention_pack;
@@ -377,7 +376,6 @@ struct FinalArgs {
     const unsigned long long* seeds = nullptr;
 };
 hipError_t launch_final(const FinalArgs& a, hipStream_t s);
-hipError_t init_rowops_kernels();
 
 // final LayerNorm + decoder_pred in one launch (rowops.hip); wg = decoder weight * norm gamma [pd, D], c = decoder bias + W . norm beta
 struct HeadDecArgs {

@@ -616,38 +616,37 @@ gemm256_kernel(const GemmArgs<bf16_t> a, const Part256 part) {
     }
 }
 
-template <typename T, int BM, int BN, int WM, int WN, int STAGES>
-hipError_t launch_cfg(const GemmArgs<T>& a, int epi, hipStream_t s) {
-    const int m_tiles = (a.M + BM - 1) / BM, n_tiles = (a.N + BN - 1) / BN;
-    const dim3 grid(m_tiles * n_tiles), block(WM * WN * 64);
-    const size_t lds = (size_t)STAGES * (BM + BN) * 128;
-#define DD_LAUNCH(E)                                                                              \
-    {                                                                                             \
-        hipLaunchKernelGGL((gemm_kernel<T, BM, BN, WM, WN, STAGES, E>), grid, block, lds, s, a);  \
-        return hipGetLastError();                                                                 \
-    }
-    switch (epi) {
-        case EPI_STORE: DD_LAUNCH(EPI_STORE)
-        case EPI_BIAS_GELU: DD_LAUNCH(EPI_BIAS_GELU)
-        case EPI_BIAS_RESID: DD_LAUNCH(EPI_BIAS_RESID)
-        case EPI_BIAS_SET: DD_LAUNCH(EPI_BIAS_SET)
-        case EPI_BIAS_STORE: DD_LAUNCH(EPI_BIAS_STORE)
-    }
-#undef DD_LAUNCH
-    return hipErrorInvalidValue;
-}
+// gemm_kernel<T, 128, BN, 2, 2, 2, E>, keyed by (sizeof(T), BN, E); a table per operand type (the launcher is typed by GemmArgs<T>)
+constexpr size_t gemm_lds(int BN) { return (size_t)2 * (128 + BN) * 128; }     // STAGES * (BM + BN) * 128
+template <typename T, int BN, int E>
+KernelEntry<GemmArgs<T>> gemm_entry() { return entry<gemm_kernel<T, 128, BN, 2, 2, 2, E>>({(int)sizeof(T), BN, E}, 256, gemm_lds(BN)); }
+const KernelEntry<GemmArgs<float>> kGemmF32[] = {
+    gemm_entry<float, 128, EPI_STORE>(), gemm_entry<float, 128, EPI_BIAS_GELU>(), gemm_entry<float, 128, EPI_BIAS_RESID>(),
+    gemm_entry<float, 128, EPI_BIAS_SET>(), gemm_entry<float, 128, EPI_BIAS_STORE>(),
+    gemm_entry<float, 64, EPI_STORE>(), gemm_entry<float, 64, EPI_BIAS_GELU>(), gemm_entry<float, 64, EPI_BIAS_RESID>(),
+    gemm_entry<float, 64, EPI_BIAS_SET>(), gemm_entry<float, 64, EPI_BIAS_STORE>(),
+};
+const KernelFamily kGemmF32Family = family<kGemmF32>("gemm_kernel");
+const KernelEntry<GemmArgs<bf16_t>> kGemmBf16[] = {
+    gemm_entry<bf16_t, 128, EPI_STORE>(), gemm_entry<bf16_t, 128, EPI_BIAS_GELU>(), gemm_entry<bf16_t, 128, EPI_BIAS_RESID>(),
+    gemm_entry<bf16_t, 128, EPI_BIAS_SET>(), gemm_entry<bf16_t, 128, EPI_BIAS_STORE>(),
+};
+const KernelFamily kGemmBf16Family = family<kGemmBf16>("gemm_kernel");
+// gemm256_kernel<E>, keyed by E
+template <int E>
+KernelEntry<GemmArgs<bf16_t>, Part256> gemm256_entry() { return entry<gemm256_kernel<E>>({E}, 512, k256Lds); }
+const KernelEntry<GemmArgs<bf16_t>, Part256> kGemm256[] = {
+    gemm256_entry<EPI_STORE>(), gemm256_entry<EPI_BIAS_GELU>(), gemm256_entry<EPI_BIAS_RESID>(),
+    gemm256_entry<EPI_BIAS_SET>(), gemm256_entry<EPI_BIAS_STORE>(), gemm256_entry<EPI_PARTIAL>(),
+};
+const KernelFamily kGemm256Family = family<kGemm256>("gemm256_kernel");
 
-template <typename T, int BM, int BN, int WM, int WN, int STAGES>
-hipError_t init_cfg() {
-    const int lds = STAGES * (BM + BN) * 128;
-    hipError_t e = hipSuccess;
-#define DD_ATTR(E)                                                                                         \
-    if (e == hipSuccess)                                                                                   \
-        e = hipFuncSetAttribute((const void*)gemm_kernel<T, BM, BN, WM, WN, STAGES, E>,                    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    DD_ATTR(EPI_STORE) DD_ATTR(EPI_BIAS_GELU) DD_ATTR(EPI_BIAS_RESID) DD_ATTR(EPI_BIAS_SET) DD_ATTR(EPI_BIAS_STORE)
-#undef DD_ATTR
-    return e;
+// the generic kernel at 128 x BN tiles
+template <typename T>
+hipError_t launch_128(const GemmArgs<T>& a, int BN, int epi, hipStream_t s) {
+    const int m_tiles = (a.M + 127) / 128, n_tiles = (a.N + BN - 1) / BN;
+    if constexpr (sizeof(T) == 4) return launch(find(kGemmF32, 4, BN, epi), dim3(m_tiles * n_tiles), gemm_lds(BN), s, a);
+    else return launch(find(kGemmBf16, 2, BN, epi), dim3(m_tiles * n_tiles), gemm_lds(BN), s, a);
 }
 
 // Row partition for gemm256 (see the kernel's header): q main tiles, e tail rows per tile, chosen to
@@ -679,38 +678,10 @@ hipError_t launch_256(const GemmArgs<bf16_t>& a, int epi, const Part256& p, int 
     const int tiles = p.q * (a.N / 256) * (epi == EPI_PARTIAL ? a.splits : 1);
     int grid = num_cus;                             // a multiple of 8: the kernel groups workgroups by XCD (gx = G >> 3)
     if (tiles < grid) grid = (tiles + 7) / 8 * 8;
-#define DD_LAUNCH(E)                                                                                  \
-    {                                                                                                 \
-        hipLaunchKernelGGL((gemm256_kernel<E>), dim3(grid), dim3(512), k256Lds, s, a, p);             \
-        return hipGetLastError();                                                                     \
-    }
-    switch (epi) {
-        case EPI_STORE: DD_LAUNCH(EPI_STORE)
-        case EPI_BIAS_GELU: DD_LAUNCH(EPI_BIAS_GELU)
-        case EPI_BIAS_RESID: DD_LAUNCH(EPI_BIAS_RESID)
-        case EPI_BIAS_SET: DD_LAUNCH(EPI_BIAS_SET)
-        case EPI_BIAS_STORE: DD_LAUNCH(EPI_BIAS_STORE)
-        case EPI_PARTIAL: DD_LAUNCH(EPI_PARTIAL)
-    }
-#undef DD_LAUNCH
-    return hipErrorInvalidValue;
+    return launch(find(kGemm256, epi), dim3(grid), k256Lds, s, a, p);
 }
 
 }  // namespace
-
-// dynamic-LDS opt-in for every instantiation, once per process (kept out of the launch path so
-// that launches are capturable into a hipGraph)
-hipError_t init_gemm_kernels() {
-    hipError_t e = init_cfg<float, 128, 128, 2, 2, 2>();
-    if (e == hipSuccess) e = init_cfg<float, 128, 64, 2, 2, 2>();
-    if (e == hipSuccess) e = init_cfg<bf16_t, 128, 128, 2, 2, 2>();
-#define DD_ATTR(E)                                                                                  \
-    if (e == hipSuccess)                                                                            \
-        e = hipFuncSetAttribute((const void*)gemm256_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, k256Lds);
-    DD_ATTR(EPI_STORE) DD_ATTR(EPI_BIAS_GELU) DD_ATTR(EPI_BIAS_RESID) DD_ATTR(EPI_BIAS_SET) DD_ATTR(EPI_BIAS_STORE) DD_ATTR(EPI_PARTIAL)
-#undef DD_ATTR
-    return e;
-}
 
 // CU count the persistent grids are sized for: the device's, rounded down to a multiple of 8 (the kernel assumes it)
 int device_num_cus() {
@@ -761,17 +732,17 @@ hipError_t launch_gemm(const GemmArgs<T>& a, int epilogue, hipStream_t s, int nu
     if (a.K % KT || a.K1 % KT || a.K1 > a.K || (a.K1 < a.K && !a.A2)) return hipErrorInvalidValue;
     if (a.hm.L && (a.N % 64 || a.N != 3 * 64 * a.hm.H || (long long)a.M * a.hm.L >= (1ll << 32))) return hipErrorInvalidValue;
     if constexpr (sizeof(T) == 4) {
-        if (a.N <= 64) return launch_cfg<T, 128, 64, 2, 2, 2>(a, epilogue, s);  // decoder_pred: N = P*P*C <= 64
-        return launch_cfg<T, 128, 128, 2, 2, 2>(a, epilogue, s);
+        if (a.N <= 64) return launch_128(a, 64, epilogue, s);  // decoder_pred: N = P*P*C <= 64
+        return launch_128(a, 128, epilogue, s);
     } else {
         Part256 p;
         const int cus = num_cus >= 8 ? num_cus / 8 * 8 : 256;
         if ((a.K1 == a.K || a.lda == a.lda2) && plan256(a.M, a.N, a.K, a.K1, cus, p)) {
             const bool small = a.tile128 < 0 ? (long long)p.q * (a.N / 256) * 2 <= cus : a.tile128 == 1;     // (gemm_prefers_128; the caller's decision if it made one)
-            if (small && !a.hm.L) return launch_cfg<T, 128, 128, 2, 2, 2>(a, epilogue, s);
+            if (small && !a.hm.L) return launch_128(a, 128, epilogue, s);
             return launch_256(a, epilogue, p, cus, s);
         }
-        return launch_cfg<T, 128, 128, 2, 2, 2>(a, epilogue, s);   // shapes the 256x256 kernel does not take (small N, tiny M)
+        return launch_128(a, 128, epilogue, s);   // shapes the 256x256 kernel does not take (small N, tiny M)
     }
 }
 

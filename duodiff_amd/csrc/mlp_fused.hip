@@ -1260,55 +1260,51 @@ __global__ void __launch_bounds__(256) qkv_rows_kernel(const MlpFusedArgs a) {
 }
 
 template <int D>
-hipError_t launch_d(const MlpFusedArgs& a, hipStream_t s) {
-    const size_t lds = MlpCfg<D>::RING + (size_t)(a.nchunks + 1) * 32 * sizeof(float) + 7 * D * sizeof(float);   // ring | bias table (+ one chunk: bias_init(c1) is read, unused) | 7 column vectors
-    const int grid = a.tiles_main + a.tiles_left * a.groups;
-    if (a.nskip > 0 && (a.nproj <= 0 || a.nskip != D / 16 || !a.skip || !a.bskip || (!a.ln_out && a.nqkv <= 0) || a.nchunks % 2)) return hipErrorInvalidValue;
-    if (a.nqkv > 0 && a.nproj <= 0) return hipErrorInvalidValue;
-    if (a.y_tap && (a.nskip <= 0 || a.nqkv > 0)) return hipErrorInvalidValue;      // (the tap rides on the SKIP launches of early-exit models)
-    if (a.ln_out_frag && (!a.ln_out || a.nqkv > 0 || a.tok_n % 32)) return hipErrorInvalidValue;   // (whole 32-row groups of patch rows per wave)
-    // the fragment-order hand-offs: the proj-fused launches at D = 512, whole 32-row groups of patch rows per wave, no qkv phases; the residual rows not
-    // where a y_tap exists (early-exit models keep x row-major); out_frag from the launches that write the bf16 copy, skip_frag into the SKIP phases
-    if (a.ao_frag || a.x_in_frag || a.x_out_frag || a.out_frag || a.skip_frag) {
-        if (D != 512 || a.nproj <= 0 || a.nqkv > 0 || a.tok_n % 32) return hipErrorInvalidValue;
-        if ((a.x_in_frag || a.x_out_frag) && a.y_tap) return hipErrorInvalidValue;
-        if ((a.out_frag && a.nskip > 0) || (a.skip_frag && a.nskip <= 0)) return hipErrorInvalidValue;
-    }
-    if (a.nproj > 0) {
-        if constexpr (D % 128 == 0) {
-            if (!a.ln_in_g || !a.ao || !a.bproj || a.nproj != D / 32) return hipErrorInvalidValue;
-            if (a.nqkv > 0) {
-                if (a.nqkv != 3 * D / 32 || !a.qkv_out || !a.qkv_dump || !a.ln_out_g || !a.ln_out_b || a.hm.L != a.tok_l || a.nchunks % 2) return hipErrorInvalidValue;
-                if (a.nskip > 0) hipLaunchKernelGGL((mlp_fused_kernel<D, true, true, true, true>), dim3(grid), dim3(256), lds, s, a);
-                else hipLaunchKernelGGL((mlp_fused_kernel<D, true, true, false, true>), dim3(grid), dim3(256), lds, s, a);
-            } else if (a.nskip > 0 && a.y_tap) hipLaunchKernelGGL((mlp_fused_kernel<D, true, true, true, false, true>), dim3(grid), dim3(256), lds, s, a);
-            else if (a.nskip > 0) hipLaunchKernelGGL((mlp_fused_kernel<D, true, true, true>), dim3(grid), dim3(256), lds, s, a);
-            else hipLaunchKernelGGL((mlp_fused_kernel<D, true, true>), dim3(grid), dim3(256), lds, s, a);
-        } else {
-            return hipErrorInvalidValue;
-        }
-    } else if (a.ln_in_g) {
-        hipLaunchKernelGGL((mlp_fused_kernel<D, true, false>), dim3(grid), dim3(256), lds, s, a);
-    } else {
-        hipLaunchKernelGGL((mlp_fused_kernel<D, false, false>), dim3(grid), dim3(256), lds, s, a);
-    }
-    return hipGetLastError();
-}
-
-template <int D>
 hipError_t launch_reduce_d(const MlpFusedArgs& a, hipStream_t s) {
     if (a.tiles_left <= 0) return hipSuccess;
     hipLaunchKernelGGL(mlp_reduce_kernel<D / 64>, dim3((unsigned)((a.n_extra + 3) / 4)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
+// mlp_fused_kernel<D, LNIN, PROJ, SKIP, QKV, TAP>, keyed by (D, the phases as bits).  LDS = ring | bias table (+ one chunk: bias_init(c1) is
+// read, unused) | 7 column vectors; the table and the vectors depend on the call, the opt-in is for the largest hidden size and width
+enum { LNIN = 1, PROJ = 2, SKIP = 4, QKV = 8, TAP = 16 };
+constexpr size_t mlp_fused_lds(int D, int nchunks, int vec_d) { return (size_t)D * 256 + (size_t)(nchunks + 1) * 32 * sizeof(float) + 7 * vec_d * sizeof(float); }
+template <int D, int V>
+KernelEntry<MlpFusedArgs> mlp_entry() {
+    static_assert(MlpCfg<D>::RING == D * 256);
+    return entry<mlp_fused_kernel<D, (V & LNIN) != 0, (V & PROJ) != 0, (V & SKIP) != 0, (V & QKV) != 0, (V & TAP) != 0>>(
+        {D, V}, 256, mlp_fused_lds(D, kMaxHidden / 32, 512));
+}
+const KernelEntry<MlpFusedArgs> kMlpFused[] = {
+    mlp_entry<64, 0>(), mlp_entry<64, LNIN>(),
+    mlp_entry<128, 0>(), mlp_entry<128, LNIN>(), mlp_entry<128, LNIN | PROJ>(), mlp_entry<128, LNIN | PROJ | SKIP>(),
+    mlp_entry<128, LNIN | PROJ | SKIP | TAP>(), mlp_entry<128, LNIN | PROJ | QKV>(), mlp_entry<128, LNIN | PROJ | SKIP | QKV>(),
+    mlp_entry<256, 0>(), mlp_entry<256, LNIN>(), mlp_entry<256, LNIN | PROJ>(), mlp_entry<256, LNIN | PROJ | SKIP>(),
+    mlp_entry<256, LNIN | PROJ | SKIP | TAP>(), mlp_entry<256, LNIN | PROJ | QKV>(), mlp_entry<256, LNIN | PROJ | SKIP | QKV>(),
+    mlp_entry<512, 0>(), mlp_entry<512, LNIN>(), mlp_entry<512, LNIN | PROJ>(), mlp_entry<512, LNIN | PROJ | SKIP>(),
+    mlp_entry<512, LNIN | PROJ | SKIP | TAP>(), mlp_entry<512, LNIN | PROJ | QKV>(), mlp_entry<512, LNIN | PROJ | SKIP | QKV>(),
+};
+
+// skip_rows_ln_kernel<D, WPG, LN> keyed by (D, LN), qkv_rows_kernel<D> by D
+constexpr size_t skip_rows_lds(int D) { return (size_t)64 * (D * 2 + 16) + (size_t)2 * (D / 32) * 32 * sizeof(float); }
+const KernelEntry<MlpFusedArgs> kSkipRowsLn[] = {
+    entry<skip_rows_ln_kernel<128>>({128, true}, 256, skip_rows_lds(128)),
+    entry<skip_rows_ln_kernel<256>>({256, true}, 512, skip_rows_lds(256)),
+    entry<skip_rows_ln_kernel<512>>({512, true}, 1024, skip_rows_lds(512)),
+    entry<skip_rows_ln_kernel<512, 2, false>>({512, false}, 128, skip_rows_lds(512)),
+};
+const KernelEntry<MlpFusedArgs> kQkvRows[] = {
+    entry<qkv_rows_kernel<128>>({128}, 256, kProjRowsLds),
+    entry<qkv_rows_kernel<256>>({256}, 256, kProjRowsLds),
+    entry<qkv_rows_kernel<512>>({512}, 256, kProjRowsLds),
+};
+const KernelFamily kMlpFusedFamilies[] = {family<kMlpFused>("mlp_fused_kernel"), family<kSkipRowsLn>("skip_rows_ln_kernel"), family<kQkvRows>("qkv_rows_kernel")};
 
 }  // namespace
 
-static size_t skip_rows_lds(int D) { return (size_t)64 * (D * 2 + 16) + (size_t)2 * (D / 32) * 32 * sizeof(float); }
-
 bool mlp_fused_supported(int D, int hidden) {
-    return (D == 64 || D == 128 || D == 256 || D == 512) && hidden % 64 == 0 && hidden >= 64 && hidden <= kMaxHidden;
+    return find(kMlpFused, D) && hidden % 64 == 0 && hidden >= 64 && hidden <= kMaxHidden;
 }
 
 void mlp_fused_pack_rows(int D, int nrows, const float* w, unsigned short (*to_bf16)(float), unsigned short* img) {
@@ -1389,89 +1385,44 @@ void mlp_fused_pack(int D, int hidden, const float* w1, const float* b1, const f
     }
 }
 
-hipError_t init_mlp_fused_kernels() {
-    hipError_t e = hipSuccess;
-    const int bias = (kMaxHidden + 32 + 7 * 512) * (int)sizeof(float);
-#define DD_ATTR(DV)                                                                                          \
-    if (e == hipSuccess)                                                                                     \
-        e = hipFuncSetAttribute((const void*)mlp_fused_kernel<DV, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                MlpCfg<DV>::RING + bias);                                                    \
-    if (e == hipSuccess)                                                                                     \
-        e = hipFuncSetAttribute((const void*)mlp_fused_kernel<DV, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                MlpCfg<DV>::RING + bias);                                                    \
-    if constexpr (DV % 128 == 0) {                                                                           \
-        if (e == hipSuccess)                                                                                 \
-            e = hipFuncSetAttribute((const void*)mlp_fused_kernel<DV, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    MlpCfg<DV>::RING + bias);                                                \
-        if (e == hipSuccess)                                                                                 \
-            e = hipFuncSetAttribute((const void*)mlp_fused_kernel<DV, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    MlpCfg<DV>::RING + bias);                                                \
-        if (e == hipSuccess)                                                                                 \
-            e = hipFuncSetAttribute((const void*)mlp_fused_kernel<DV, true, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    MlpCfg<DV>::RING + bias);                                                \
-        if (e == hipSuccess)                                                                                 \
-            e = hipFuncSetAttribute((const void*)mlp_fused_kernel<DV, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    MlpCfg<DV>::RING + bias);                                                \
-        if (e == hipSuccess)                                                                                 \
-            e = hipFuncSetAttribute((const void*)mlp_fused_kernel<DV, true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    MlpCfg<DV>::RING + bias);                                                \
-    }
-    DD_ATTR(64) DD_ATTR(128) DD_ATTR(256) DD_ATTR(512)
-#undef DD_ATTR
-#define DD_ATTR_P(DV)                                                                                        \
-    if (e == hipSuccess)                                                                                     \
-        e = hipFuncSetAttribute((const void*)qkv_rows_kernel<DV>, hipFuncAttributeMaxDynamicSharedMemorySize, kProjRowsLds); \
-    if (e == hipSuccess)                                                                                     \
-        e = hipFuncSetAttribute((const void*)skip_rows_ln_kernel<DV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)skip_rows_lds(DV));
-    DD_ATTR_P(128) DD_ATTR_P(256) DD_ATTR_P(512)
-#undef DD_ATTR_P
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)skip_rows_ln_kernel<512, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)skip_rows_lds(512));
-    return e;
-}
-
 // skip_linear + norm1 of the extra-token rows of a SKIP launch (after launch_mlp_reduce, which stored their y in a.out); no-op without extras
 hipError_t launch_skip_rows_ln(const MlpFusedArgs& a, int D, hipStream_t s, bool with_ln) {
     if (a.n_extra <= 0 || a.nskip <= 0) return hipSuccess;
     if (!a.out || !a.skip || !a.bskip || (with_ln && (!a.ln_out || !a.ln_out_g || !a.ln_out_b))) return hipErrorInvalidValue;
-    const size_t lds = skip_rows_lds(D);
-    if (!with_ln) {     // column-split form: 2 column tiles per workgroup (the consumer normalises the rows)
-        if (D != 512) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((skip_rows_ln_kernel<512, 2, false>), dim3((a.n_extra + 31) / 32, 512 / 32 / 2), dim3(128), lds, s, a);
-        return hipGetLastError();
-    }
-    const dim3 grid((a.n_extra + 31) / 32);
-    switch (D) {
-        case 128: hipLaunchKernelGGL((skip_rows_ln_kernel<128>), grid, dim3(256), lds, s, a); break;
-        case 256: hipLaunchKernelGGL((skip_rows_ln_kernel<256>), grid, dim3(512), lds, s, a); break;
-        case 512: hipLaunchKernelGGL((skip_rows_ln_kernel<512>), grid, dim3(1024), lds, s, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    // without the LayerNorm, the column-split form: 2 column tiles per workgroup (the consumer normalises the rows)
+    const dim3 grid((a.n_extra + 31) / 32, with_ln ? 1 : D / 32 / 2);
+    return launch(find(kSkipRowsLn, D, with_ln), grid, skip_rows_lds(D), s, a);
 }
 
 hipError_t launch_qkv_rows(const MlpFusedArgs& a, int D, hipStream_t s) {
     if (a.n_extra <= 0 || a.nqkv <= 0) return hipSuccess;
     if (!a.ln_out || !a.qkv_out || a.nqkv != 3 * D / 32) return hipErrorInvalidValue;
-    const dim3 grid(a.nqkv, (a.n_extra + 127) / 128);
-    switch (D) {
-        case 128: hipLaunchKernelGGL((qkv_rows_kernel<128>), grid, dim3(256), kProjRowsLds, s, a); break;
-        case 256: hipLaunchKernelGGL((qkv_rows_kernel<256>), grid, dim3(256), kProjRowsLds, s, a); break;
-        case 512: hipLaunchKernelGGL((qkv_rows_kernel<512>), grid, dim3(256), kProjRowsLds, s, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch(find(kQkvRows, D), dim3(a.nqkv, (a.n_extra + 127) / 128), kProjRowsLds, s, a);
 }
 
 // the fused launch itself; the extra-token rows are finished by launch_mlp_reduce right behind it
 hipError_t launch_mlp_fused(const MlpFusedArgs& a, int D, hipStream_t s) {
-    switch (D) {
-        case 64: return launch_d<64>(a, s);
-        case 128: return launch_d<128>(a, s);
-        case 256: return launch_d<256>(a, s);
-        case 512: return launch_d<512>(a, s);
+    if (!find(kMlpFused, D)) return hipErrorInvalidValue;
+    const size_t lds = mlp_fused_lds(D, a.nchunks, D);
+    const int grid = a.tiles_main + a.tiles_left * a.groups;
+    if (a.nskip > 0 && (a.nproj <= 0 || a.nskip != D / 16 || !a.skip || !a.bskip || (!a.ln_out && a.nqkv <= 0) || a.nchunks % 2)) return hipErrorInvalidValue;
+    if (a.nqkv > 0 && a.nproj <= 0) return hipErrorInvalidValue;
+    if (a.y_tap && (a.nskip <= 0 || a.nqkv > 0)) return hipErrorInvalidValue;      // (the tap rides on the SKIP launches of early-exit models)
+    if (a.ln_out_frag && (!a.ln_out || a.nqkv > 0 || a.tok_n % 32)) return hipErrorInvalidValue;   // (whole 32-row groups of patch rows per wave)
+    // the fragment-order hand-offs: the proj-fused launches at D = 512, whole 32-row groups of patch rows per wave, no qkv phases; the residual rows not
+    // where a y_tap exists (early-exit models keep x row-major); out_frag from the launches that write the bf16 copy, skip_frag into the SKIP phases
+    if (a.ao_frag || a.x_in_frag || a.x_out_frag || a.out_frag || a.skip_frag) {
+        if (D != 512 || a.nproj <= 0 || a.nqkv > 0 || a.tok_n % 32) return hipErrorInvalidValue;
+        if ((a.x_in_frag || a.x_out_frag) && a.y_tap) return hipErrorInvalidValue;
+        if ((a.out_frag && a.nskip > 0) || (a.skip_frag && a.nskip <= 0)) return hipErrorInvalidValue;
     }
-    return hipErrorInvalidValue;
+    int phases = a.ln_in_g ? LNIN : 0;
+    if (a.nproj > 0) {      // (the widths without these forms have no entry)
+        if (!a.ln_in_g || !a.ao || !a.bproj || a.nproj != D / 32) return hipErrorInvalidValue;
+        if (a.nqkv > 0 && (a.nqkv != 3 * D / 32 || !a.qkv_out || !a.qkv_dump || !a.ln_out_g || !a.ln_out_b || a.hm.L != a.tok_l || a.nchunks % 2)) return hipErrorInvalidValue;
+        phases |= PROJ | (a.nskip > 0 ? SKIP : 0) | (a.nqkv > 0 ? QKV : 0) | (a.y_tap ? TAP : 0);      // (a tap: SKIP without QKV, checked above)
+    }
+    return launch(find(kMlpFused, D, phases), dim3(grid), lds, s, a);
 }
 hipError_t launch_mlp_reduce(const MlpFusedArgs& a, int D, hipStream_t s) {
     switch (D) {

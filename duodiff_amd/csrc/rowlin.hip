@@ -279,9 +279,12 @@ __global__ void __launch_bounds__(256) rowlin768_kernel(const RowLinArgs a) {
     }
 }
 
+const KernelEntry<RowLinArgs> kRowlin[] = {entry<rowlin768_kernel>({kRlD}, 256, kRlLds)};     // keyed by embed_dim
+const KernelFamily kRowlinFamily = family<kRowlin>("rowlin768_kernel");
+
 }  // namespace
 
-bool rowlin_supported(int D, int K) { return D == kRlD && K % 64 == 0 && K >= 192; }
+bool rowlin_supported(int D, int K) { return find(kRowlin, D) && K % 64 == 0 && K >= 192; }
 
 // nn.Linear weight [768, K] -> the stream the kernel reads: [k-step][output tile t] x 1 KB fragment, natural k order (the rows' operand is loaded as stored)
 void rowlin_pack(int K, const float* w, unsigned short (*to_bf16)(float), unsigned short* img) {
@@ -315,12 +318,7 @@ hipError_t launch_rowlin(const RowLinArgs& a, hipStream_t s) {
     if (rows_all * a.lda * 2 >= (1ll << 32)) return hipErrorInvalidValue;     // the kernel's operand row offsets are 32 bits
     const int grid = a.tok_n > 0 ? a.tiles_main + a.tiles_extra * a.groups : (a.M + 127) / 128;
     if (a.tok_n > 0 && (a.cpg % 4 || a.groups < 1 || (a.tiles_extra > 0 && !a.partial) || a.tok_n % 32)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rowlin768_kernel, dim3(grid), dim3(256), kRlLds, s, a);
-    return hipGetLastError();
-}
-
-hipError_t init_rowlin_kernels() {
-    return hipFuncSetAttribute((const void*)rowlin768_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kRlLds);
+    return launch(find(kRowlin, kRlD), dim3(grid), kRlLds, s, a);
 }
 
 }  // namespace dd

@@ -571,19 +571,28 @@ __global__ void __launch_bounds__(256) ee_attn_probe_kernel(const float* __restr
     if (tid == 0) out[b] = part + w.b2[0];
 }
 
+// embed_mfma_kernel<P, C, LND>, keyed by (P, C, LND); the launch's LDS is the weight image of its D and patch size, under one ceiling
+constexpr size_t kEmbedLdsMax = 156 * 1024;
+const KernelEntry<EmbedArgs> kEmbedMfma[] = {
+    entry<embed_mfma_kernel<4, 3, 512>>({4, 3, 512}, 512, kEmbedLdsMax),
+    entry<embed_mfma_kernel<4, 3>>({4, 3}, 512, kEmbedLdsMax),
+    entry<embed_mfma_kernel<2, 3>>({2, 3}, 512, kEmbedLdsMax),
+    entry<embed_mfma_kernel<2, 4>>({2, 4}, 512, kEmbedLdsMax),
+};
+const KernelFamily kEmbedMfmaFamily = family<kEmbedMfma>("embed_mfma_kernel");
+
 }  // namespace
 
 bool embed_mfma_ok(const EmbedArgs& a, size_t& lds) {
     const int pd = a.C * a.P * a.P;
     lds = (size_t)(a.D / 32) * 2 * ((pd / 4 + 3) / 4) * 1024;
-    return a.S == 16 * a.P && a.D % 32 == 0 && pd % 4 == 0 && lds <= 156 * 1024 && a.L == a.extras + 256 &&
-           ((a.P == 4 && a.C == 3) || (a.P == 2 && a.C == 3) || (a.P == 2 && a.C == 4));
+    return a.S == 16 * a.P && a.D % 32 == 0 && pd % 4 == 0 && lds <= kEmbedLdsMax && a.L == a.extras + 256 && find(kEmbedMfma, a.P, a.C);
 }
 
 // the MFMA kernel's variant that also writes the first block's norm1 in fragment order: the CelebA shape (patch 4, 3 channels, embed_dim 512)
 bool embed_ln_supported(const EmbedArgs& a) {
     size_t lds = 0;
-    return !a.generic && embed_mfma_ok(a, lds) && a.P == 4 && a.C == 3 && a.D == 512;
+    return !a.generic && embed_mfma_ok(a, lds) && a.D > 0 && find(kEmbedMfma, a.P, a.C, a.D);     // (key 0 = the kernel without norm1)
 }
 
 hipError_t launch_embed(const EmbedArgs& a, hipStream_t s) {
@@ -592,16 +601,12 @@ hipError_t launch_embed(const EmbedArgs& a, hipStream_t s) {
         dim3 grid((unsigned)((a.B * 16 + 7) / 8));
         if (a.ln_frag) {      // + the first block's norm1 (embed_ln_supported)
             if (!embed_ln_supported(a) || !a.ln_g || !a.ln_b) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((embed_mfma_kernel<4, 3, 512>), grid, dim3(512), mlds, s, a);
-            return hipGetLastError();
+            return launch(find(kEmbedMfma, a.P, a.C, a.D), grid, mlds, s, a);
         }
         // few images: deal the column pairs over grid.y until the launch has about one workgroup per CU (an even share of pairs each)
         const int np = a.D / 32;
         while (grid.x * grid.y * 2 <= 256 && np % (grid.y * 4) == 0) grid.y *= 2;
-        if (a.P == 4) hipLaunchKernelGGL((embed_mfma_kernel<4, 3>), grid, dim3(512), mlds, s, a);
-        else if (a.C == 3) hipLaunchKernelGGL((embed_mfma_kernel<2, 3>), grid, dim3(512), mlds, s, a);
-        else hipLaunchKernelGGL((embed_mfma_kernel<2, 4>), grid, dim3(512), mlds, s, a);
-        return hipGetLastError();
+        return launch(find(kEmbedMfma, a.P, a.C), grid, mlds, s, a);
     }
     const int per_img = (a.L + kEmbedTok - 1) / kEmbedTok;
     const long long pad_rows = (long long)a.Mp - (long long)a.B * a.L;
@@ -887,13 +892,34 @@ __global__ void __launch_bounds__(NW * 64) head_dec_kernel(const HeadDecArgs a) 
     }
 }
 
+// head_dec_kernel<D, NT, NW, PROBE, SPLIT>, keyed by (D, NT, PROBE, SPLIT): 8 waves and the probe / split forms at D = 256 and 512, 4 waves and
+// as many column tiles as (D / 16) NT KB of LDS for Wg allow at 768 and 1024
+namespace {
+constexpr size_t head_dec_lds(int D, int nt, bool probe) { return (size_t)(D / 16) * nt * 1024 + (probe ? (size_t)D * 4 : 0); }
+template <int D, int NT, int NW = 8, bool PROBE = false, bool SPLIT = false>
+KernelEntry<HeadDecArgs> head_entry() { return entry<head_dec_kernel<D, NT, NW, PROBE, SPLIT>>({D, NT, PROBE, SPLIT}, NW * 64, head_dec_lds(D, NT, PROBE)); }
+const KernelEntry<HeadDecArgs> kHeadDec[] = {
+    head_entry<512, 1>(), head_entry<512, 1, 8, true>(), head_entry<512, 1, 8, true, true>(), head_entry<512, 1, 8, false, true>(),
+    head_entry<512, 2>(), head_entry<512, 2, 8, true>(), head_entry<512, 2, 8, true, true>(), head_entry<512, 2, 8, false, true>(),
+    head_entry<512, 3>(), head_entry<512, 3, 8, true>(), head_entry<512, 3, 8, true, true>(), head_entry<512, 3, 8, false, true>(),
+    head_entry<512, 4>(), head_entry<512, 4, 8, true>(), head_entry<512, 4, 8, true, true>(), head_entry<512, 4, 8, false, true>(),
+    head_entry<256, 1>(), head_entry<256, 1, 8, true>(), head_entry<256, 1, 8, true, true>(), head_entry<256, 1, 8, false, true>(),
+    head_entry<256, 2>(), head_entry<256, 2, 8, true>(), head_entry<256, 2, 8, true, true>(), head_entry<256, 2, 8, false, true>(),
+    head_entry<256, 3>(), head_entry<256, 3, 8, true>(), head_entry<256, 3, 8, true, true>(), head_entry<256, 3, 8, false, true>(),
+    head_entry<256, 4>(), head_entry<256, 4, 8, true>(), head_entry<256, 4, 8, true, true>(), head_entry<256, 4, 8, false, true>(),
+    head_entry<768, 1, 4>(), head_entry<768, 2, 4>(), head_entry<768, 3, 4>(),
+    head_entry<1024, 1, 4>(), head_entry<1024, 2, 4>(),
+};
+const KernelFamily kHeadDecFamily = family<kHeadDec>("head_dec_kernel");
+}  // namespace
+
 bool head_dec_supported(int D, int pd) {
     if (pd < 1 || pd > 64 || pd % 4) return false;
-    const int nt = (pd + 15) / 16;
-    return D == 256 || D == 512 || (D == 768 && nt <= 3) || (D == 1024 && nt <= 2);     // (D / 16) nt KB of LDS for Wg
+    return find(kHeadDec, D, (pd + 15) / 16);
 }
 
-bool head_dec_probe_supported(int D) { return D == 256 || D == 512; }
+// the widths that have the probe and the split forms (the same: every column-tile count of such a width has both)
+bool head_dec_probe_supported(int D) { return find(kHeadDec, D, 1, true, true); }
 
 void pack_head_split(int D, int pd, const float* wg, unsigned short (*f2bf)(float), unsigned short* img, float* wsum) {
     const int nt = (pd + 15) / 16, J2 = D / 32;
@@ -923,52 +949,7 @@ hipError_t launch_head_dec(const HeadDecArgs& a, int D, int num_cus, hipStream_t
     const int nt = (a.pd + 15) / 16;
     const int wgs = (a.M + 127) / 128;
     const dim3 grid((unsigned)(wgs < num_cus ? wgs : num_cus));     // one workgroup per CU (LDS), 16-row units dealt inside
-    const size_t lds = (size_t)(D / 16) * nt * 1024 + (a.srow ? (size_t)D * 4 : 0);
-#define DD_HEAD(DV, NV)                                                                                  \
-    do {                                                                                                 \
-        if (a.split && a.srow) hipLaunchKernelGGL((head_dec_kernel<DV, NV, 8, true, true>), grid, dim3(512), lds, s, a);   \
-        else if (a.split) hipLaunchKernelGGL((head_dec_kernel<DV, NV, 8, false, true>), grid, dim3(512), lds, s, a);       \
-        else if (a.srow) hipLaunchKernelGGL((head_dec_kernel<DV, NV, 8, true>), grid, dim3(512), lds, s, a);  \
-        else hipLaunchKernelGGL((head_dec_kernel<DV, NV>), grid, dim3(512), lds, s, a);                  \
-    } while (0)
-    if (D == 1024) {
-        if (nt == 1) hipLaunchKernelGGL((head_dec_kernel<1024, 1, 4>), grid, dim3(256), lds, s, a);
-        else hipLaunchKernelGGL((head_dec_kernel<1024, 2, 4>), grid, dim3(256), lds, s, a);
-    } else if (D == 768) {
-#define DD_HEAD4(NV) hipLaunchKernelGGL((head_dec_kernel<768, NV, 4>), grid, dim3(256), lds, s, a)
-        if (nt == 1) DD_HEAD4(1); else if (nt == 2) DD_HEAD4(2); else if (nt == 3) DD_HEAD4(3); else return hipErrorInvalidValue;
-#undef DD_HEAD4
-    }
-    else if (D == 512) { if (nt == 1) DD_HEAD(512, 1); else if (nt == 2) DD_HEAD(512, 2); else if (nt == 3) DD_HEAD(512, 3); else DD_HEAD(512, 4); }
-    else { if (nt == 1) DD_HEAD(256, 1); else if (nt == 2) DD_HEAD(256, 2); else if (nt == 3) DD_HEAD(256, 3); else DD_HEAD(256, 4); }
-#undef DD_HEAD
-    return hipGetLastError();
-}
-
-hipError_t init_rowops_kernels() {
-    hipError_t e = hipSuccess;
-#define DD_HEAD_ATTR(DV, NV)                                                                                       \
-    if (e == hipSuccess)                                                                                           \
-        e = hipFuncSetAttribute((const void*)head_dec_kernel<DV, NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (DV / 16) * NV * 1024); \
-    if (e == hipSuccess)                                                                                           \
-        e = hipFuncSetAttribute((const void*)head_dec_kernel<DV, NV, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (DV / 16) * NV * 1024 + DV * 4); \
-    if (e == hipSuccess)                                                                                           \
-        e = hipFuncSetAttribute((const void*)head_dec_kernel<DV, NV, 8, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (DV / 16) * NV * 1024 + DV * 4); \
-    if (e == hipSuccess)                                                                                           \
-        e = hipFuncSetAttribute((const void*)head_dec_kernel<DV, NV, 8, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (DV / 16) * NV * 1024);
-    DD_HEAD_ATTR(512, 1) DD_HEAD_ATTR(512, 2) DD_HEAD_ATTR(512, 3) DD_HEAD_ATTR(512, 4)
-    DD_HEAD_ATTR(256, 1) DD_HEAD_ATTR(256, 2) DD_HEAD_ATTR(256, 3) DD_HEAD_ATTR(256, 4)
-#undef DD_HEAD_ATTR
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)head_dec_kernel<768, 1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 48 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)head_dec_kernel<768, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)head_dec_kernel<768, 3, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)head_dec_kernel<1024, 1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)head_dec_kernel<1024, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)embed_mfma_kernel<4, 3, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)embed_mfma_kernel<4, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)embed_mfma_kernel<2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)embed_mfma_kernel<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-    return e;
+    return launch(find(kHeadDec, D, nt, a.srow != nullptr, a.split != 0), grid, head_dec_lds(D, nt, a.srow != nullptr), s, a);
 }
 
 namespace {

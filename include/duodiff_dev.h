@@ -450,6 +450,20 @@ int dd_dev_ee_real_cost(dd_ctx* ctx, double* ms_out, long long* waits_out, long 
  * destination slot) in moves_src_dst [2 * (n / 2)] -- the rule the decision kernel applies. */
 int dd_dev_ee_real_plan(const int* alive, int n, int* keep_out, int* n_moves_out, int* moves_src_dst);
 
+/* Host-only (no device, no context): entry `index` of the library's kernel tables, one per instantiation of a kernel that needs the dynamic-LDS
+ * opt-in -- the kernel's name, the template arguments its dispatcher selects it by (unused slots 0), its workgroup size and the LDS ceiling it is
+ * opted in to.  Returns 0, or 1 past the last entry. */
+int dd_dev_kernel_table(int index, char family[32], int key[4], int* block, int* lds_max);
+/* ... and the predicates that ask those tables which shapes have a kernel: 1 or 0, DD_ERR_INVALID for an unknown predicate. */
+#define DD_DEV_SUP_MLP_FUSED 0        /* args: D, hidden */
+#define DD_DEV_SUP_HEAD_DEC 1         /* D, pd */
+#define DD_DEV_SUP_HEAD_DEC_PROBE 2   /* D */
+#define DD_DEV_SUP_QKV_ATTENTION 3    /* D, H, L, extras */
+#define DD_DEV_SUP_ROWLIN 4           /* D, K */
+#define DD_DEV_SUP_EMBED_MFMA 5       /* P, C, D, S, L, extras */
+#define DD_DEV_SUP_EMBED_LN 6         /* P, C, D, S, L, extras */
+int dd_dev_kernel_supported(int predicate, const int args[6]);
+
 #ifdef __cplusplus
 }
 #endif
